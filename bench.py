@@ -7,7 +7,7 @@ One "step" = one complete pass of the hot path over that batch: frame-rate front
 persistent decode launch (prologue + 66 000 generation steps), inputs (features, noise, packed
 weights) already resident in HBM, samples left in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--utts B] [--frames Tf] [--no-legs]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--utts B] [--frames Tf] [--no-legs] [--dump-outputs DIR]
   N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
          or plainly `python bench.py --gpus N`: with WORLD_SIZE unset the script starts its N ranks itself (child
          processes, before the parent makes any GPU call) and exits non-zero if any of them fails.
@@ -23,6 +23,10 @@ At N=1 the line also carries `legs`: every other BASELINE.json config measured i
   cfg1 (softmax 16 kHz), cfg3 (seg=5, lpc=4), cfg5's 64-utterance per-GPU share, the run.sh-geometry
   (REF6) companions of cfg1/2/3/5, cfg4 (teacher-forced forward and full training step incl. Adam, BL6 and REF6,
   fp32 and bf16), and `batch_fast_generate` as a caller sees it (noise draw + launch + device->host copy).
+
+--dump-outputs DIR: after the timed steps, write what the headline's last step returned to its caller (the decoded
+samples, (utterances, samples) fp32) as DIR/samples.npy (DIR/samples_rank<r>.npy per rank when N > 1).  Weights, features
+and noise come from fixed seeds, so two builds run with the same arguments can be compared file for file.
 """
 from __future__ import annotations
 
@@ -106,6 +110,7 @@ MFMA_FP32_TFLOPS = 157.0         # fp32 matrix peak (exact-fp32 MFMA parity kern
 # MI355X_MICROARCH.md section HBM) + WRITE_SIZE, in bytes.  Measured offline: counters cannot be read
 # from inside this process.  Other shapes report null.
 PMC_TRAFFIC_BYTES = {(1, 600): int((2 * 1378.2 + 257.8) * 1024)}
+DUMP_BYTES = 64 << 20            # --dump-outputs writes at most this much in all (every rank together)
 
 
 def algorithmic_bytes_per_position(cfg: C.NetConfig, batch: int) -> float:
@@ -185,6 +190,21 @@ def _mfma(flops_per_launch: float, ms: float, peak: float, **extra):
     ach = flops_per_launch / (ms * 1e-3) / 1e12
     return dict(bound="mfma", achieved=round(ach, 2), peak=peak, unit="TFLOP/s", frac=round(ach / peak, 5),
                 traffic=None, **extra)
+
+
+def dump_outputs(path: str, arrays: dict, budget: int) -> None:
+    """write each array as path/<name>.npy in float32 (float64 stays float64).  An array larger than its share of `budget`
+    bytes is replaced by a fixed, seeded sample of its elements in flat order: the same positions for the same shape, so
+    that the dumps of two builds stay comparable."""
+    os.makedirs(path, exist_ok=True)
+    share = budget // len(arrays) - 4096                           # room for the .npy header
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            pick = np.random.Generator(np.random.PCG64(0)).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------- cpu baseline
@@ -523,7 +543,12 @@ def main():
                          "(what the CPU tests drive)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
                     help="where rank 0 writes the verbose per-leg dictionaries ('' = nowhere)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the headline's last decoded samples to DIR/samples.npy "
+                         "(float32, at most 64 MB in all: a seeded sample of a larger output)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.plan_only:
         rank, world, local = D.init_from_env(backend="gloo")
@@ -589,6 +614,9 @@ def main():
     torch.cuda.synchronize()
     elapsed = D.max_over_ranks(time.perf_counter() - t0, dev)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))         # decode launch, HIP events on its stream
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"samples" if world == 1 else f"samples_rank{rank}": out.cpu().numpy()},
+                     DUMP_BYTES // world)
 
     total_samples = world * B * n_steps * cfg.seg * args.steps
     value = total_samples / elapsed

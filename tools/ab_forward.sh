@@ -1,6 +1,6 @@
 #!/bin/bash
 # dev tool: bf16 forward time of several library variants (tools/build_variant.sh), both cfg4 shapes
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 for v in "$@"; do
   lib=$R/shallow_wavenet_amd/libswn_hip_$v.so; [ "$v" = main ] && lib=$R/shallow_wavenet_amd/libswn_hip.so
   for shape in "8 150" "64 150"; do

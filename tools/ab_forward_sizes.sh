@@ -1,4 +1,4 @@
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 for v in main old; do
   lib=$R/shallow_wavenet_amd/libswn_hip_$v.so; [ "$v" = main ] && lib=$R/shallow_wavenet_amd/libswn_hip.so
   for shape in "4 150" "16 150" "32 150" "64 150"; do

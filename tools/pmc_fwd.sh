@@ -1,7 +1,7 @@
 #!/bin/bash
 # dev tool (GPU box): SQ counter passes over the bf16 forward (tools/time_forward.py B Tf); per-kernel means of the layer kernel
 # usage: tools/pmc_fwd.sh B Tf [libvariant]  -> gpurun_out/pmc_fwd_<tag>.txt
-R=${GRAFT_REPO_ROOT:-/root/repo}; B=${1:-64}; TF=${2:-150}; V=${3:-main}
+R=$(cd "$(dirname "$0")/.." && pwd); B=${1:-64}; TF=${2:-150}; V=${3:-main}
 lib=$R/shallow_wavenet_amd/libswn_hip_$V.so; [ "$V" = main ] && lib=$R/shallow_wavenet_amd/libswn_hip.so
 export SWN_HIP_LIB=$lib
 O=$R/gpurun_out/pmc_fwd_${V}_${B}x${TF}; mkdir -p $O
