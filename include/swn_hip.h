@@ -175,6 +175,26 @@ int    swn_decode(const swn_net_desc* d, const float* packed_dev, const float* c
                   float* state_dev, void* out_dev, float* heads_dev,
                   int variant, void* stream);
 
+/* ---- streamed decode: swn_decode in resumable chunks, bit-identical to the one-shot call --------------------------
+ * A session holds everything a decode kernel carries from one step to the next (history rings, sample window, and
+ * whatever the kernel computes one step ahead).  Chunk k runs steps [step0, step0 + n_steps): positions, conditioning
+ * frames and generator counters (swn_decode_io.rng_*) are absolute, the io arrays and out / heads are chunk-local
+ * (B, n_steps, ...).  Concatenating the chunks of any partition of [0, N) gives swn_decode(..., n_steps = N) bit for bit.
+ *   cond_dev    frames [0, n_frames) as swn_frontend wrote them; the bound (step0 + n_steps) * seg <= n_frames * U applies
+ *   flags       SWN_CHUNK_BEGIN on the first chunk (runs the prologue from io->seed_dev; step0 must be 0), else 0: the
+ *               state comes from session_dev, which the previous chunk of the SAME (net, batch, variant) left there
+ *   session_dev swn_decode_session_floats() floats, owned by the caller for the life of the stream
+ * A chunk of 0 steps without BEGIN changes nothing.  SWN_E_BADARG: a null pointer, BEGIN with step0 != 0, a negative
+ * step0 / n_steps, the bound above, or a variant that is retired or does not resolve for the net - all checked before
+ * anything is launched. */
+#define SWN_CHUNK_BEGIN 1
+/* the kernel swn_decode(variant) runs for (net, batch): 1, 2 (either BL6 form), 3, 6, or a negative SWN_E_* */
+int    swn_decode_resolve_variant(const swn_net_desc* d, int batch, int variant);
+size_t swn_decode_session_floats(const swn_net_desc* d, int batch, int variant);
+int    swn_decode_chunk(const swn_net_desc* d, const float* packed_dev, const float* cond_dev, int batch, int n_frames,
+                        int step0, int n_steps, int flags, const swn_decode_io* io, float* session_dev,
+                        void* out_dev, float* heads_dev, int variant, void* stream);
+
 /* ---- teacher-forced stack  (CSWNV.forward cswnv_shift1.py:191-267,
  *                             DSWNV.forward dswnv.py:250-276) ----------------------------
  *   audio_dev   laplace: (B, 1, T - seg) fp32 samples ; softmax: (B, T - 1) int32 indices

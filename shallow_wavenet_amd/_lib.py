@@ -37,6 +37,7 @@ class DecodeIO(ctypes.Structure):
 
 
 ABI_VERSION = 3
+CHUNK_BEGIN = 1                                # SWN_CHUNK_BEGIN (include/swn_hip.h): first chunk of a streamed decode
 PRECISION_FP32, PRECISION_BF16 = 0, 1          # SWN_PRECISION_* (include/swn_hip.h)
 
 
@@ -70,6 +71,10 @@ SIGNATURES = {
     "swn_decode_state_floats": (c_size_t, [POINTER(NetDesc), c_int]),
     "swn_decode": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecodeIO),
                            c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "swn_decode_resolve_variant": (c_int, [POINTER(NetDesc), c_int, c_int]),
+    "swn_decode_session_floats": (c_size_t, [POINTER(NetDesc), c_int, c_int]),
+    "swn_decode_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(DecodeIO),
+                                 c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "swn_forward_work_floats": (c_size_t, [POINTER(NetDesc), c_int, c_int]),
     "swn_forward": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                             c_void_p, c_void_p, c_void_p]),

@@ -37,6 +37,10 @@ struct DecArgs {
     int ring_off[SWN_MAXL];
     int ring_len[SWN_MAXL];
     int state_stride;
+    // streamed chunk (STREAM instantiations only): absolute index of the chunk's first step, 1 = the state comes from
+    // the session (no prologue), the session's sample windows ([B][round4(WN)] floats behind the rings in `state`)
+    int step0, resume;
+    float* win;
 };
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
@@ -93,7 +97,10 @@ __device__ __forceinline__ void matvec16(const float* __restrict__ W, int NR, in
     }
 }
 
-template <int SEGT, int KIND>
+// STREAM: a chunk of a streamed decode (swn_decode_chunk): steps [step0, step0 + n_steps) with absolute positions and
+// generator counters, chunk-local out / heads / noise / forced rows; the rings stay in the session (a.state) and the sample
+// window is loaded from / saved to the session.  STREAM = false is the one-shot decode.
+template <int SEGT, int KIND, bool STREAM = false>
 __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const SwnGeom& g = a.g;
@@ -125,6 +132,11 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
         for (int e = tid; e < seg; e += NT) shist[WN - seg + e] = reinterpret_cast<const float*>(a.seed)[(size_t)b * seg + e];
     }
     __syncthreads();
+    const int WNR = swn_round4(WN);
+    if (STREAM && a.resume) {
+        for (int e = tid; e < WN; e += NT) shist[e] = a.win[(size_t)b * WNR + e];
+        __syncthreads();
+    }
 
     float* st = a.state + (size_t)b * a.state_stride;
     const float* condb = a.cond + (size_t)b * a.Tf * g.N;
@@ -132,12 +144,14 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
     const int rf = g.rf;
     const int n_pro = rf - seg + 1;                          // prologue positions 0..rf-seg
     const int total = n_pro + a.n_steps;
+    const int s0 = STREAM ? a.step0 : 0;                    // absolute index of step i = 0
 
-    for (int it = 0; it < total; ++it) {
+    for (int it = (STREAM && a.resume) ? n_pro : 0; it < total; ++it) {
         const bool gen = it >= n_pro;
-        const int i = it - n_pro;                            // generation step index
+        const int i = it - n_pro;                            // generation step index (chunk-local)
+        const int ia = s0 + i;                               // ... and of the utterance
         const int np = gen ? seg : 1;
-        const int q0 = gen ? rf + 1 - seg + i * seg : it;    // first position handled now
+        const int q0 = gen ? rf + 1 - seg + ia * seg : it;   // first position handled now
 
         // ---- conditioning lookups for this step (frame index / upsampler tap per (j,s))
         if (tid < np * seg) {
@@ -158,13 +172,13 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
                 if (KIND == SWN_KIND_LAPLACE) {
                     if (r >= -(seg - 1)) {
                         // window holds S[qe-WN+1..qe], qe = last known position
-                        const int qe = gen ? rf + i * seg : rf;
+                        const int qe = gen ? rf + ia * seg : rf;
                         const float sv = gen ? shist[r - qe + WN - 1] : 0.f;
                         acc += fmaf(P[a.y.cv + (size_t)k * H + o], sv, P[a.y.cc + (size_t)k * H + o]);
                     }
                 } else {
                     if (r >= 0) {
-                        const int qe = gen ? rf + i : rf;
+                        const int qe = gen ? rf + ia : rf;
                         const int idx = gen ? ihist[r - qe + WN - 1] : g.Q / 2;
                         acc += P[a.y.ct + ((size_t)k * g.Q + idx) * H + o];
                     }
@@ -196,7 +210,7 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
                     gxc = fmaf(w, cr[H + o], gxc);
                 }
                 if (KIND == SWN_KIND_SOFTMAX && g.audio_in) {
-                    const int qe = gen ? rf + i : rf;
+                    const int qe = gen ? rf + ia : rf;
                     const int idx = gen ? ihist[q - qe + WN - 1] : g.Q / 2;
                     const float* wa = P + a.y.wxa + ((size_t)l * g.Q + idx) * H2;
                     gxz += wa[o]; gxc += wa[H + o];
@@ -244,7 +258,7 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
                     const float bsc = expf(fminf(yv, 0.f) - log1pf(expf(-fabsf(yv))));
                     float lpv = 0.f;
                     for (int k = 0; k < lpc; ++k) lpv += o2v[2 * seg + lpc - 1 - k] * lp[k];
-                    const float e = swn_noise_laplace(a.nz, b, i, j, a.n_steps, seg);
+                    const float e = swn_noise_laplace_at(a.nz, b, i, ia, j, a.n_steps, seg);
                     const float sg = (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : 0.f);
                     const float t = (bsc * sg) * log1pf(-2.f * fabsf(e));
                     float sv = (lpc > 0) ? (lpv + mu) - t : mu - t;
@@ -274,7 +288,7 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
                 for (int d = 32; d >= 1; d >>= 1) sum2 += __shfl_xor(sum2, d, 64);
                 float best = -1.f; int bi = 0x7fffffff;
                 for (int e = tid; e < Q; e += 64) {
-                    const float r = ((expf(o2v[e] - m) / sum) / sum2) / swn_noise_exp1(a.nz, b, i, e, a.n_steps, Q);
+                    const float r = ((expf(o2v[e] - m) / sum) / sum2) / swn_noise_exp1_at(a.nz, b, i, ia, e, a.n_steps, Q);
                     if (r > best) { best = r; bi = e; }
                 }
                 for (int d = 32; d >= 1; d >>= 1) {
@@ -293,14 +307,16 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
         }
         __syncthreads();
     }
+    if (STREAM)
+        for (int e = tid; e < WN; e += NT) a.win[(size_t)b * WNR + e] = shist[e];
 }
 
-template <int SEGT>
+template <int SEGT, bool STREAM = false>
 int launch_generic(const DecArgs& a, size_t lds, hipStream_t st) {
     if (a.g.kind == SWN_KIND_LAPLACE)
-        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_LAPLACE>), dim3(a.B), dim3(NT), lds, st, a);
+        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_LAPLACE, STREAM>), dim3(a.B), dim3(NT), lds, st, a);
     else
-        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX>), dim3(a.B), dim3(NT), lds, st, a);
+        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX, STREAM>), dim3(a.B), dim3(NT), lds, st, a);
     return swn_launch_status("swn_decode(generic)");
 }
 
@@ -311,6 +327,30 @@ int ring_plan(const SwnGeom& g, int* off, int* len) {
         o += len[l] * g.Hp;
     }
     return (o + 63) & ~63;
+}
+
+int generic_segt(const SwnGeom& g) { return g.seg <= 1 ? 1 : (g.seg <= 2 ? 2 : (g.seg <= 5 ? 5 : 10)); }
+int generic_wn(const SwnGeom& g) { return (g.K - 1 > g.lpc ? g.K - 1 : g.lpc) + g.seg; }
+size_t generic_lds(const SwnGeom& g) {
+    const int segt = generic_segt(g);
+    const size_t lds_floats = (size_t)segt * swn_round4(2 * g.H) + (size_t)g.L * g.Hp + g.Sp + g.O1p +
+                              swn_round4(g.NO) + swn_round4(generic_wn(g)) + 2 * (size_t)segt * segt;
+    return lds_floats * sizeof(float);
+}
+
+// the generic kernel over a filled DecArgs (state = the rings, zeroed here unless a streamed chunk resumes)
+int generic_run(DecArgs& a, bool stream, hipStream_t st) {
+    const size_t lds = generic_lds(a.g);
+    if (lds > 160 * 1024) return SWN_E_UNSUPPORTED;
+    if (!(stream && a.resume) &&
+        hipMemsetAsync(a.state, 0, sizeof(float) * (size_t)a.state_stride * a.B, st) != hipSuccess)
+        return SWN_E_LAUNCH;
+    switch (generic_segt(a.g)) {
+        case 1: return stream ? launch_generic<1, true>(a, lds, st) : launch_generic<1>(a, lds, st);
+        case 2: return stream ? launch_generic<2, true>(a, lds, st) : launch_generic<2>(a, lds, st);
+        case 5: return stream ? launch_generic<5, true>(a, lds, st) : launch_generic<5>(a, lds, st);
+        default: return stream ? launch_generic<10, true>(a, lds, st) : launch_generic<10>(a, lds, st);
+    }
 }
 
 }  // namespace
@@ -325,8 +365,22 @@ extern "C" int swn_decode_bl6w_try(const swn_net_desc* d, const float* packed, c
                                    int batch, int n_frames, int n_steps, const SwnNoise* nz,
                                    const void* forced, const void* seed, void* out, float* heads, void* stream);
 
+// streamed forms of the three (swn_decode_chunk): session sizes per utterance (0 = the kernel does not apply) and one chunk
+extern "C" size_t swn_decode_bl6_session_floats(const swn_net_desc* d);
+extern "C" size_t swn_decode_bl6w_session_floats(const swn_net_desc* d);
+extern "C" int swn_decode_bl6_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                    int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
+                                    const void* seed, float* sess, void* out, float* heads, void* stream);
+extern "C" int swn_decode_bl6w_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                     int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
+                                     const void* seed, float* sess, void* out, float* heads, void* stream);
+
 // defined in swn_decode_stepped.hip
 extern "C" size_t swn_decode_stepped_state_floats(const swn_net_desc* d, int batch);
+extern "C" int swn_decode_stepped_supported(const swn_net_desc* d, int batch);
+extern "C" int swn_decode_stepped_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                        int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
+                                        const void* seed, float* sess, void* out, float* heads, void* stream);
 extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
                                   int n_steps, const SwnNoise* nz, const void* forced, const void* seed, float* state,
                                   void* out, float* heads, void* stream);
@@ -376,19 +430,92 @@ extern "C" int swn_decode(const swn_net_desc* d, const float* packed, const floa
     a.packed = packed; a.cond = cond; a.nz = nz; a.forced = forced; a.seed = seed; a.state = state;
     a.out = out; a.heads = heads; a.B = batch; a.Tf = n_frames; a.n_steps = n_steps;
     a.state_stride = ring_plan(a.g, a.ring_off, a.ring_len);
-    if (hipMemsetAsync(state, 0, sizeof(float) * (size_t)a.state_stride * batch, st) != hipSuccess)
-        return SWN_E_LAUNCH;
-    const SwnGeom& g = a.g;
-    const int segt = g.seg <= 1 ? 1 : (g.seg <= 2 ? 2 : (g.seg <= 5 ? 5 : 10));
-    const int WN = (g.K - 1 > g.lpc ? g.K - 1 : g.lpc) + g.seg;
-    const size_t lds_floats = (size_t)segt * swn_round4(2 * g.H) + (size_t)g.L * g.Hp + g.Sp + g.O1p +
-                              swn_round4(g.NO) + swn_round4(WN) + 2 * (size_t)segt * segt;
-    const size_t lds = lds_floats * sizeof(float);
-    if (lds > 160 * 1024) return SWN_E_UNSUPPORTED;
-    switch (segt) {
-        case 1: return launch_generic<1>(a, lds, st);
-        case 2: return launch_generic<2>(a, lds, st);
-        case 5: return launch_generic<5>(a, lds, st);
-        default: return launch_generic<10>(a, lds, st);
+    a.step0 = 0; a.resume = 0; a.win = nullptr;
+    return generic_run(a, false, st);
+}
+
+// ---- streamed decode ---------------------------------------------------------------------------------------------
+namespace {
+
+enum { KSEL_GENERIC = 1, KSEL_BL6W = 2, KSEL_STEPPED = 3, KSEL_BL6 = 6 };
+
+// the kernel swn_decode(variant) runs for (net, batch): KSEL_*, or a negative SWN_E_* (the same decisions in the same order)
+int resolve_kernel(const swn_net_desc* d, int batch, int variant) {
+    SwnGeom g;
+    const int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (batch < 1) return SWN_E_BADARG;
+    if ((variant == 0 || variant == 2) && swn_decode_bl6w_session_floats(d) > 0) return KSEL_BL6W;
+    if (variant == 0 || variant == 2 || variant == 6) {
+        if (swn_decode_bl6_session_floats(d) > 0) return KSEL_BL6;
+        if (variant != 0) return SWN_E_UNSUPPORTED;
     }
+    if (variant < 0 || variant > 3) return SWN_E_BADARG;   // 4 and 5 retired
+    const bool big = (size_t)g.L * 2 * g.H * g.K * g.Hp >= (size_t)256 * 1024;
+    if (variant == 3 || (variant == 0 && big)) {
+        if (swn_decode_stepped_supported(d, batch)) return KSEL_STEPPED;
+        if (variant == 3) return SWN_E_UNSUPPORTED;
+    }
+    if (generic_lds(g) > 160 * 1024) return SWN_E_UNSUPPORTED;
+    return KSEL_GENERIC;
+}
+
+}  // namespace
+
+extern "C" int swn_decode_resolve_variant(const swn_net_desc* d, int batch, int variant) {
+    const int k = resolve_kernel(d, batch, variant);
+    if (k < 0) return k;
+    if (k == KSEL_BL6W) return 2;
+    if (k == KSEL_BL6) return variant == 6 ? 6 : 2;
+    return k;
+}
+
+extern "C" size_t swn_decode_session_floats(const swn_net_desc* d, int batch, int variant) {
+    const int k = resolve_kernel(d, batch, variant);
+    if (k < 0) return 0;
+    if (k == KSEL_BL6W) return swn_decode_bl6w_session_floats(d) * (size_t)batch;
+    if (k == KSEL_BL6) return swn_decode_bl6_session_floats(d) * (size_t)batch;
+    if (k == KSEL_STEPPED) return swn_decode_stepped_state_floats(d, batch);
+    SwnGeom g; swn_make_geom(d, &g);
+    int off[SWN_MAXL], len[SWN_MAXL];
+    return ((size_t)ring_plan(g, off, len) + swn_round4(generic_wn(g))) * (size_t)batch;   // rings, then the sample windows
+}
+
+extern "C" int swn_decode_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                int step0, int n_steps, int flags, const swn_decode_io* io, float* session,
+                                void* out, float* heads, int variant, void* stream_) {
+    SwnGeom g;
+    int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (!io || !session || !packed || !cond) return SWN_E_BADARG;
+    if (batch < 1 || n_frames < 1 || step0 < 0 || n_steps < 0 || (flags & ~SWN_CHUNK_BEGIN)) return SWN_E_BADARG;
+    const bool begin = (flags & SWN_CHUNK_BEGIN) != 0;
+    if (begin && step0 != 0) return SWN_E_BADARG;
+    if (n_steps > 0 && !out) return SWN_E_BADARG;
+    if (((long long)step0 + n_steps) * g.seg > (long long)n_frames * g.U) return SWN_E_BADARG;   // conditioning not final yet
+    const int k = resolve_kernel(d, batch, variant);
+    if (k < 0) return SWN_E_BADARG;
+    if (n_steps == 0 && !begin) return SWN_OK;             // nothing to generate, the session stays as it is
+    SwnNoise nz;
+    nz.ptr = io->noise_dev; nz.dump = io->noise_out_dev;
+    nz.key0 = (uint32_t)(io->rng_seed & 0xffffffffu); nz.key1 = (uint32_t)(io->rng_seed >> 32); nz.utt0 = io->rng_utt0; nz.ids = io->rng_utt_ids_dev;
+    const int resume = begin ? 0 : 1;
+    (void)hipGetLastError();
+    if (k == KSEL_BL6W)
+        return swn_decode_bl6w_chunk(d, packed, cond, batch, n_frames, step0, n_steps, resume, &nz, io->forced_dev, io->seed_dev,
+                                     session, out, heads, stream_);
+    if (k == KSEL_BL6)
+        return swn_decode_bl6_chunk(d, packed, cond, batch, n_frames, step0, n_steps, resume, &nz, io->forced_dev, io->seed_dev,
+                                    session, out, heads, stream_);
+    if (k == KSEL_STEPPED)
+        return swn_decode_stepped_chunk(d, packed, cond, batch, n_frames, step0, n_steps, resume, &nz, io->forced_dev,
+                                        io->seed_dev, session, out, heads, stream_);
+    DecArgs a;
+    a.g = g;
+    swn_make_layout(&a.g, &a.y);
+    a.packed = packed; a.cond = cond; a.nz = nz; a.forced = io->forced_dev; a.seed = io->seed_dev; a.state = session;
+    a.out = out; a.heads = heads; a.B = batch; a.Tf = n_frames; a.n_steps = n_steps;
+    a.state_stride = ring_plan(a.g, a.ring_off, a.ring_len);
+    a.step0 = step0; a.resume = resume; a.win = session + (size_t)a.state_stride * batch;
+    return generic_run(a, true, (hipStream_t)stream_);
 }

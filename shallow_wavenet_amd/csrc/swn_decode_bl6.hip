@@ -44,6 +44,10 @@ struct B6Args {
     // extended mode only (in-kernel generator, noise dump, caller's seed waveform)
     SwnNoise nz;
     const void* seed;
+    // streamed chunk only (STREAM instantiations): absolute index of the chunk's first step, 1 = resume from the
+    // session instead of running the prologue, the session ([B][T::sess_floats])
+    int step0, resume;
+    float* sess;
 };
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
@@ -90,6 +94,8 @@ struct Tr {
     static constexpr int o_w1l = o_wl + (L - NREG) * 8 * NT * 4;
     static constexpr int o_end = o_w1l + W1L * O1 * 16;
     static constexpr size_t lds_bytes = (size_t)o_end * sizeof(float);
+    // per-utterance session of a streamed decode: the history rings as LDS holds them, then the sample window
+    static constexpr int sess_floats = ring_off(L) + r4(WN);
 };
 
 // Streamed weights go through a buffer resource: one 32-bit per-thread offset plus scalar /
@@ -331,7 +337,10 @@ __device__ __forceinline__ void tiled_matvec(__amdgpu_buffer_rsrc_t wt, const fl
 
 // EXT = false: the classic instantiation (host-drawn noise stream, zero seed) - the code the round-1 measurements
 // belong to, kept instruction for instruction; EXT = true adds the in-kernel generator / noise dump / seed waveform.
-template <class T>
+// STREAM (with EXT only): one chunk of a streamed decode (swn_decode_chunk) - steps [step0, step0 + n_steps) at absolute
+// positions and generator counters, chunk-local out / heads / noise / forced rows; when resuming, the rings and the sample
+// window come from the session instead of the prologue, and they go back to it at the end.  The step itself is the same code.
+template <class T, bool STREAM = false>
 __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int SEG = T::SEG, S = T::S, KIND = T::KIND;
@@ -339,6 +348,11 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
     const int tid = threadIdx.x, b = blockIdx.x;
     const float* __restrict__ P = a.P;
     const int U = a.U;
+    static_assert(!STREAM || EXT, "streamed chunks run the extended mode");
+    const int s0 = STREAM ? a.step0 : 0;                  // absolute index of step i = 0
+    const bool resume = STREAM && a.resume;
+    // conditioning frame of the first step: the frame pair the one-shot decode holds in LDS when it reaches that step
+    const int fb0 = STREAM ? cmax(0, 1 - SEG + s0 * SEG) / U : 0;
 
     // ---- one-time loads: LDS constants, register-resident dilated-conv weights
     for (int e = tid; e < T::o_end; e += NT) lds[e] = 0.f;
@@ -371,7 +385,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
                     buf_ld4(condr, (unsigned)tid * 16u, (unsigned)(fr * a.N * 4 + it * NT * 16));
         }
     };
-    for (int fr = 0; fr < 2 && fr < a.Tf; ++fr) load_frame(fr);
+    for (int fr = fb0; fr < fb0 + 2 && fr < a.Tf; ++fr) load_frame(fr);
     float wreg[L][2][16];
 #pragma unroll
     for (int l = 0; l < L; ++l) {
@@ -390,8 +404,13 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
         }
     }
     __syncthreads();
+    const float* sess_b = STREAM ? a.sess + (size_t)b * T::sess_floats : nullptr;
+    if (resume) {
+        for (int e = tid; e < T::ring_off(L); e += NT) lds[T::o_ring + e] = sess_b[e];
+        __syncthreads();
+    }
 
-    int fb = 0, tb = 0;                       // base conditioning frame resident in buffer fb&1
+    int fb = fb0, tb = fb0 * U;               // base conditioning frame resident in buffer fb&1
     const int p = tid & 7;
     const int n_pro = RF - SEG + 1;
 
@@ -458,6 +477,12 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
             iwin[WNI - 1] = reinterpret_cast<const int*>(a.seed)[b];
         }
     }
+    if (resume) {              // the window as the previous chunk left it
+#pragma unroll
+        for (int k = 0; k < WNF; ++k) if (KIND == SWN_KIND_LAPLACE) win[k] = sess_b[T::ring_off(L) + k];
+#pragma unroll
+        for (int k = 0; k < WNI; ++k) if (KIND == SWN_KIND_SOFTMAX) iwin[k] = __builtin_bit_cast(int, sess_b[T::ring_off(L) + k]);
+    }
     auto input_gen = [&](int q0n) {
         if (tid < H) {
             const int o = tid;
@@ -486,7 +511,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
             if (step < a.n_steps) {
 #pragma unroll
                 for (int j = 0; j < SEG; ++j) {
-                    const float e = swn_noise_laplace(a.nz, b, step, j, a.n_steps, SEG);
+                    const float e = swn_noise_laplace_at(a.nz, b, step, s0 + step, j, a.n_steps, SEG);
                     const float sg = (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : 0.f);
                     lds[T::o_tnz + ((c & (T::NZB - 1)) * T::NZC + k) * SEG + j] = sg * log1pf(-2.f * fabsf(e));
                 }
@@ -499,7 +524,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
             static_assert(T::Q == 256, "one float4 of classes per lane");
             if (tid >= 128 && tid < 192 && step < a.n_steps) {
                 float4 q4;
-                if constexpr (EXT) q4 = swn_noise_exp1x4(a.nz, b, step, tid - 128, a.n_steps, T::Q);
+                if constexpr (EXT) q4 = swn_noise_exp1x4_at(a.nz, b, step, s0 + step, tid - 128, a.n_steps, T::Q);
                 else q4 = *reinterpret_cast<const float4*>(a.noise + ((size_t)b * a.n_steps + step) * T::Q + 4 * (tid - 128));
                 *reinterpret_cast<float4*>(lds + T::o_tnz + (step & 1) * T::Q + 4 * (tid - 128)) = q4;
             }
@@ -526,7 +551,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
 
     // ---- prologue: seed positions 0..rf-seg, one position per pass (cswnv_shift1.py:321-334)
 #pragma unroll 1
-    for (int q = 0; q < n_pro; ++q) {
+    for (int q = resume ? n_pro : 0; q < n_pro; ++q) {
         float wj[SEG]; int pb[SEG];
         cond_taps(q, wj, pb, true);
         input_seed(q);
@@ -552,10 +577,10 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
 #else
 #define STAMP(k)
 #endif
-    input_gen(RF + 1 - SEG);
+    input_gen(RF + 1 - SEG + s0 * SEG);
     noise_ahead(0);       // classic mode: visible to wave 0 after the barriers of step 0
     auto gen_step = [&](const int i) __attribute__((always_inline)) {
-        const int q0 = RF + 1 - SEG + i * SEG;
+        const int q0 = RF + 1 - SEG + (s0 + i) * SEG;
         float wj[SEG]; int pb[SEG];
 #ifdef SWN_STAMP
         tprev = __builtin_amdgcn_s_memtime();
@@ -770,16 +795,27 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
 #pragma unroll 1
         for (int i = 0; i < a.n_steps; ++i) gen_step(i);
     }
+    if constexpr (STREAM) {    // the state the next chunk resumes from: rings (all written behind barriers) and wave 0's window
+        __syncthreads();
+        float* so = a.sess + (size_t)b * T::sess_floats;
+        for (int e = tid; e < T::ring_off(L); e += NT) so[e] = lds[T::o_ring + e];
+        if (tid == 0) {
+#pragma unroll
+            for (int k = 0; k < WNF; ++k) if (KIND == SWN_KIND_LAPLACE) so[T::ring_off(L) + k] = win[k];
+#pragma unroll
+            for (int k = 0; k < WNI; ++k) if (KIND == SWN_KIND_SOFTMAX) so[T::ring_off(L) + k] = __builtin_bit_cast(float, iwin[k]);
+        }
+    }
 #ifdef SWN_STAMP
     if (tid == 0 && b == 0 && a.heads)
         for (int k = 0; k < 10; ++k) a.heads[k] = (float)((double)tacc[k] / (double)a.n_steps);
 #endif
 }
 
-template <class T>
+template <class T, bool STREAM = false>
 int launch_mode(const B6Args& a, hipStream_t st) {
     static_assert(T::lds_bytes <= 160 * 1024, "LDS budget");
-    auto kern = decode_bl6_kernel<T>;
+    auto kern = decode_bl6_kernel<T, STREAM>;
     if (T::lds_bytes > 64 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)T::lds_bytes) != hipSuccess)
@@ -795,7 +831,47 @@ int launch(const B6Args& a, hipStream_t st) {
     return ext ? launch_mode<typename T::Ext>(a, st) : launch_mode<T>(a, st);
 }
 
+// the instantiation a geometry runs: f(Tr<...>{}) for a BL6-class net, SWN_E_UNSUPPORTED otherwise
+template <class F>
+int with_tr(const SwnGeom& g, F&& f) {
+    if (!g.bl6 || g.U > 256 || g.U < 2 * g.seg || g.audio_in) return SWN_E_UNSUPPORTED;
+    if (g.kind == SWN_KIND_LAPLACE && g.S == 128) {
+        if (g.seg == 1 && g.lpc == 0) return f(Tr<128, 1, 0, SWN_KIND_LAPLACE, 0>{});
+        if (g.seg == 1 && g.lpc == 4) return f(Tr<128, 1, 4, SWN_KIND_LAPLACE, 0>{});
+        if (g.seg == 2 && g.lpc == 4) return f(Tr<128, 2, 4, SWN_KIND_LAPLACE, 0>{});
+        if (g.seg == 5 && g.lpc == 0) return f(Tr<128, 5, 0, SWN_KIND_LAPLACE, 0>{});
+        if (g.seg == 5 && g.lpc == 4) return f(Tr<128, 5, 4, SWN_KIND_LAPLACE, 0>{});
+    }
+    if (g.kind == SWN_KIND_SOFTMAX && g.S == 256 && g.Q == 256) return f(Tr<256, 1, 0, SWN_KIND_SOFTMAX, 256>{});
+    return SWN_E_UNSUPPORTED;
+}
+
 }  // namespace
+
+// streamed decode (swn_decode_chunk): per-utterance session floats of the symmetric kernel, 0 = not a BL6-class net
+extern "C" size_t swn_decode_bl6_session_floats(const swn_net_desc* d) {
+    SwnGeom g;
+    if (swn_make_geom(d, &g) < 0) return 0;
+    int n = 0;
+    with_tr(g, [&](auto t) { n = decltype(t)::sess_floats; return SWN_OK; });
+    return (size_t)n;
+}
+
+// one chunk on the symmetric kernel; `sess` holds swn_decode_bl6_session_floats() floats per utterance
+extern "C" int swn_decode_bl6_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                    int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
+                                    const void* seed, float* sess, void* out, float* heads, void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    B6Args a;
+    swn_make_layout(&g, &a.y);
+    a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
+    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
+    a.step0 = step0; a.resume = resume; a.sess = sess;
+    hipStream_t st = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    return with_tr(g, [&](auto t) { return launch_mode<typename decltype(t)::Ext, true>(a, st); });
+}
 
 extern "C" int swn_decode_bl6_try(const swn_net_desc* d, const float* packed, const float* cond, int batch,
                                   int n_frames, int n_steps, const SwnNoise* nz, const void* forced,
@@ -807,6 +883,7 @@ extern "C" int swn_decode_bl6_try(const swn_net_desc* d, const float* packed, co
     swn_make_layout(&g, &a.y);
     a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
     a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
+    a.step0 = 0; a.resume = 0; a.sess = nullptr;
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();   // drop stale errors of earlier runtime calls; only our launches are reported
     if (g.kind == SWN_KIND_LAPLACE && g.S == 128) {

@@ -49,6 +49,10 @@ struct W6Args {
     int B, Tf, n_steps, U, N;
     SwnNoise nz;                   // extended mode
     const void* seed;
+    // streamed chunk only (STREAM instantiations): absolute index of the chunk's first step, 1 = resume from the
+    // session instead of running the prologue, the session ([B][T::sess_floats])
+    int step0, resume;
+    float* sess;
 };
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
@@ -86,6 +90,11 @@ struct Tw {
                                                            // too (192 + the out_skip weights in flight) the kernel spilled 22-35 registers
     static constexpr int o_end = o_wl + 8 * NG * 4;
     static constexpr size_t lds_bytes = (size_t)o_end * sizeof(float);
+    // per-utterance session of a streamed decode: the history rings, the older-tap products group B formed one step ahead
+    // (both parities, as LDS holds them), then the sample window
+    static constexpr int sess_old = ring_off(L);
+    static constexpr int sess_win = sess_old + 2 * L * 2 * H;
+    static constexpr int sess_floats = sess_win + r4(WN);
 };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
@@ -268,9 +277,15 @@ __device__ __forceinline__ void skip_consume_b(const float* lds, const float4 (&
 // The program of one group (GA: group A).  The two groups run the SAME sequence of barriers; they are separate instantiations -
 // not one body with a run-time branch per phase - so that each has its own register allocation: as one body the allocation was the
 // union (192 weight registers of A + the out_skip weights B keeps in flight: 22-65 registers spilled inside the step loop).
-template <class T, bool GA>
+// STREAM (with EXT only): one chunk of a streamed decode (swn_decode_chunk) - steps [step0, step0 + n_steps) at absolute
+// positions and generator counters, chunk-local out / heads / noise / forced rows.  When resuming, the rings, the sample
+// window and the older-tap products of the first position (group B formed them during the previous chunk's last step)
+// are loaded from the session - carried over bit for bit, not recomputed - and the prologue is skipped; the next input
+// layer is then formed by the same input_gen as in the one-shot loop.  At the end all of it goes back to the session.
+template <class T, bool GA, bool STREAM>
 __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
     constexpr bool EXT = T::EXT;
+    static_assert(!STREAM || EXT, "streamed chunks run the extended mode");
     constexpr bool grpA = GA;
     const int tid = threadIdx.x, b = blockIdx.x;
     __builtin_assume(GA ? tid < NG : tid >= NG);              // group B compiles none of wave 0's and wave 1's side jobs (head, noise, input layer)
@@ -279,6 +294,9 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
     const int tg = tid & (NG - 1);                            // index inside the group
     const float* __restrict__ P = a.P;
     const int U = a.U;
+    const int s0 = STREAM ? a.step0 : 0;                      // absolute index of step i = 0
+    const bool resume = STREAM && a.resume;
+    const int fb0 = STREAM ? s0 / U : 0;                      // conditioning frame of the first step (t = q - RF = step)
 
     // ---- one-time loads
     for (int e = tid; e < T::o_end; e += NT) lds[e] = 0.f;
@@ -309,7 +327,7 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
                     buf_ld4(condr, (unsigned)tid * 16u, (unsigned)(fr * a.N * 4 + it * NT * 16));
         }
     };
-    for (int fr = 0; fr < 2 && fr < a.Tf; ++fr) load_frame(fr);
+    for (int fr = fb0; fr < fb0 + 2 && fr < a.Tf; ++fr) load_frame(fr);
     // register-resident halves of the six matrices: group A tap 1 (current), group B tap 0 (older); rows (o, o + 64), inputs 16 p ..
     float wreg[L][2][16];                                     // (group B: the last layer's entries stay unused - its half is in LDS)
     {
@@ -332,8 +350,14 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
             }
     }
     __syncthreads();
+    const float* sess_b = STREAM ? a.sess + (size_t)b * T::sess_floats : nullptr;
+    if (resume) {
+        for (int e = tid; e < T::ring_off(L); e += NT) lds[T::o_ring + e] = sess_b[e];
+        for (int e = tid; e < 2 * L * 2 * H; e += NT) lds[T::o_old + e] = sess_b[T::sess_old + e];
+        __syncthreads();
+    }
 
-    int fb = 0, tb0 = 0;                      // base conditioning frame resident in buffer fb & 1
+    int fb = fb0, tb0 = fb0 * U;              // base conditioning frame resident in buffer fb & 1
     const int n_pro = RF;                     // seed positions 0 .. rf - 1 (seg = 1)
     auto cond_taps = [&](int q, float& wj, int& pb) {
         const int t0 = q - RF;
@@ -372,6 +396,10 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
 #pragma unroll
     for (int k = 0; k < T::WN; ++k) win[k] = 0.f;
     if (EXT && a.seed) win[T::WN - 1] = reinterpret_cast<const float*>(a.seed)[b];
+    if (resume) {
+#pragma unroll
+        for (int k = 0; k < T::WN; ++k) win[k] = sess_b[T::sess_win + k];
+    }
     // (the five input-layer constants of wave 0's channel stay in registers: the tail phase is one wave's dependent chain)
     float kcb = 0.f, kv0 = 0.f, kv1 = 0.f, kc0 = 0.f, kc1 = 0.f;
     if (tid < H) { const int o = tid; kcb = c_b; kv0 = c_v0; kv1 = c_v1; kc0 = c_c0; kc1 = c_c1; }
@@ -388,7 +416,7 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
         if (EXT && tid >= 64 && tid < 128) {
             const int k = tid - 64, step = c * T::NZC + k;
             if (step < a.n_steps) {
-                const float e = swn_noise_laplace(a.nz, b, step, 0, a.n_steps, 1);
+                const float e = swn_noise_laplace_at(a.nz, b, step, s0 + step, 0, a.n_steps, 1);
                 const float sg = (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : 0.f);
                 lds[T::o_tnz + (c & (T::NZB - 1)) * T::NZC + k] = sg * log1pf(-2.f * fabsf(e));
             }
@@ -438,7 +466,7 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
 
     // ---- prologue: seed positions 0 .. rf - 1 (cswnv_shift1.py:321-334)
 #pragma unroll 1
-    for (int q = 0; q < n_pro; ++q) {
+    for (int q = resume ? n_pro : 0; q < n_pro; ++q) {
         float wj; int pb;
         float4 wsl[8]; float sacc[2]; const unsigned step0 = 0;
         cond_taps(q, wj, pb);
@@ -449,10 +477,10 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
     }
 
     // ---- generation (cswnv_shift1.py:348-402)
-    input_gen(RF);
+    input_gen(RF + s0);
     noise_ahead(0);
     auto gen_step = [&](const int i) __attribute__((always_inline)) {
-        const int q = RF + i;
+        const int q = RF + s0 + i;
         float wj; int pb;
         cond_taps(q, wj, pb);
         float4 wsl[8];
@@ -569,6 +597,16 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
 #pragma unroll 1
         for (int i = 0; i < a.n_steps; ++i) gen_step(i);
     }
+    if constexpr (STREAM) {    // the state the next chunk resumes from (all LDS writes of the last step are behind barriers)
+        __syncthreads();
+        float* so = a.sess + (size_t)b * T::sess_floats;
+        for (int e = tid; e < T::ring_off(L); e += NT) so[e] = lds[T::o_ring + e];
+        for (int e = tid; e < 2 * L * 2 * H; e += NT) so[T::sess_old + e] = lds[T::o_old + e];
+        if (tid == 0) {
+#pragma unroll
+            for (int k = 0; k < T::WN; ++k) so[T::sess_win + k] = win[k];
+        }
+    }
 #undef SWN_PHASE
 #undef SWN_BAR
 #ifdef SWN_STAMP
@@ -580,17 +618,17 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
 #endif
 }
 
-template <class T>
+template <class T, bool STREAM = false>
 __global__ __launch_bounds__(NT) void decode_bl6w_kernel(const W6Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    if (threadIdx.x < NG) decode_body<T, true>(a, lds);       // wave-uniform
-    else decode_body<T, false>(a, lds);
+    if (threadIdx.x < NG) decode_body<T, true, STREAM>(a, lds);       // wave-uniform
+    else decode_body<T, false, STREAM>(a, lds);
 }
 
-template <class T>
+template <class T, bool STREAM = false>
 int launch_mode(const W6Args& a, hipStream_t st) {
     static_assert(T::lds_bytes <= 160 * 1024, "LDS budget");
-    auto kern = decode_bl6w_kernel<T>;
+    auto kern = decode_bl6w_kernel<T, STREAM>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::lds_bytes) != hipSuccess)
         return SWN_E_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(a.B), dim3(NT), T::lds_bytes, st, a);
@@ -603,6 +641,12 @@ int launch(const W6Args& a, hipStream_t st) {
     return ext ? launch_mode<typename T::Ext>(a, st) : launch_mode<T>(a, st);
 }
 
+
+bool bl6w_applies(const SwnGeom& g) {
+    return g.bl6 && g.U <= 256 && g.U >= 2 && !g.audio_in && g.kind == SWN_KIND_LAPLACE && g.S == 128 && g.O1 == 128 &&
+           g.seg == 1 && (g.lpc == 0 || g.lpc == 4);
+}
+
 }  // namespace
 
 // SWN_E_UNSUPPORTED: not a single-sample Laplace net of the BL6 class (the symmetric kernel, swn_decode_bl6.hip, takes the others)
@@ -611,15 +655,39 @@ extern "C" int swn_decode_bl6w_try(const swn_net_desc* d, const float* packed, c
                                    const void* seed, void* out, float* heads, void* stream_) {
     SwnGeom g; int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    if (!g.bl6 || g.U > 256 || g.U < 2 || g.audio_in || g.kind != SWN_KIND_LAPLACE || g.S != 128 || g.O1 != 128 || g.seg != 1 ||
-        (g.lpc != 0 && g.lpc != 4))
-        return SWN_E_UNSUPPORTED;
+    if (!bl6w_applies(g)) return SWN_E_UNSUPPORTED;
     W6Args a;
     swn_make_layout(&g, &a.y);
     a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
     a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
+    a.step0 = 0; a.resume = 0; a.sess = nullptr;
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();
     if (g.lpc == 0) return launch<Tw<0, false>>(a, st);
     return launch<Tw<4, false>>(a, st);
+}
+
+// streamed decode (swn_decode_chunk): per-utterance session floats of the wave-specialised kernel, 0 = it does not apply
+extern "C" size_t swn_decode_bl6w_session_floats(const swn_net_desc* d) {
+    SwnGeom g;
+    if (swn_make_geom(d, &g) < 0 || !bl6w_applies(g)) return 0;
+    return (size_t)(g.lpc == 0 ? Tw<0, true>::sess_floats : Tw<4, true>::sess_floats);
+}
+
+// one chunk on the wave-specialised kernel; `sess` holds swn_decode_bl6w_session_floats() floats per utterance
+extern "C" int swn_decode_bl6w_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                     int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
+                                     const void* seed, float* sess, void* out, float* heads, void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (!bl6w_applies(g)) return SWN_E_UNSUPPORTED;
+    W6Args a;
+    swn_make_layout(&g, &a.y);
+    a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
+    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
+    a.step0 = step0; a.resume = resume; a.sess = sess;
+    hipStream_t st = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    if (g.lpc == 0) return launch_mode<Tw<0, true>, true>(a, st);
+    return launch_mode<Tw<4, true>, true>(a, st);
 }

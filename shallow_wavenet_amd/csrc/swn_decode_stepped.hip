@@ -29,6 +29,7 @@ struct StArgs {
     int ring_off[SWN_MAXL], ring_len[SWN_MAXL];
     int o_hcat, o_skip, o_o1, o_o2, o_hist, o_cnt, stride;      // per-utterance float offsets
     int o2_by_rowvec;                                           // out_2 was computed by a rowvec launch into o_o2 (wide heads)
+    int step0;                                                  // streamed chunk (STREAM tails): absolute index of its step 0
 };
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
@@ -431,14 +432,16 @@ __global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StArgs a,
 }
 
 // ---- step_tail: out_2, sampling, history update, then the input layer of the next step ---------------
-template <int KIND>
+// STREAM: a chunk of a streamed decode (swn_decode_chunk): `it` stays the absolute iteration (positions, generator counters),
+// out / heads / noise / forced rows are chunk-local (step ia - step0).  The other launches of the chain need no such form.
+template <int KIND, bool STREAM = false>
 __global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const int it) {
     __shared__ float o2v[4096 + 16];
     __shared__ float lwin[32];                 // the updated sample window, for the fused next input layer
     const SwnGeom& g = a.g;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
     float* st = a.state + (size_t)b * a.stride;
-    const int i = it - a.n_pro, seg = g.seg, WN = a.WN;
+    const int ia = it - a.n_pro, i = STREAM ? ia - a.step0 : ia, seg = g.seg, WN = a.WN;
     // out_2.  Wide heads (softmax: Q rows) arrive from a rowvec launch - one wave per row over the chip, like skip and
     // out_1 - in the state block; narrow heads (Laplace: <= 2 seg + lpc rows) are computed here:
     // 8 rows per pass, 32 lanes per row; branch-free loads (a row past NO / an input past O1p reads zeros)
@@ -488,7 +491,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const in
                 const float bsc = expf(fminf(yv, 0.f) - log1pf(expf(-fabsf(yv))));
                 float lpv = 0.f;
                 for (int k = 0; k < lpc; ++k) lpv += o2v[2 * seg + lpc - 1 - k] * lp[k];
-                const float e = swn_noise_laplace(a.nz, b, i, j, a.n_steps, seg);
+                const float e = swn_noise_laplace_at(a.nz, b, i, ia, j, a.n_steps, seg);
                 const float sg = (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : 0.f);
                 const float t = (bsc * sg) * log1pf(-2.f * fabsf(e));
                 float sv = (lpc > 0) ? (lpv + mu) - t : mu - t;
@@ -517,7 +520,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const in
         float best = -1.f; int bi = 0x7fffffff;
         if ((Q & 3) == 0) {          // four classes per generator call / 16-byte noise load
             for (int g4 = tid; 4 * g4 < Q; g4 += 64) {
-                const float4 q4 = swn_noise_exp1x4(a.nz, b, i, g4, a.n_steps, Q);
+                const float4 q4 = swn_noise_exp1x4_at(a.nz, b, i, ia, g4, a.n_steps, Q);
                 const float qv[4] = {q4.x, q4.y, q4.z, q4.w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -528,7 +531,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const in
             }
         } else {
             for (int e = tid; e < Q; e += 64) {
-                const float r = ((expf(o2v[e] - m) / sum) / sum2) / swn_noise_exp1(a.nz, b, i, e, a.n_steps, Q);
+                const float r = ((expf(o2v[e] - m) / sum) / sum2) / swn_noise_exp1_at(a.nz, b, i, ia, e, a.n_steps, Q);
                 if (r > best) { best = r; bi = e; }
             }
         }
@@ -557,7 +560,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const in
 //      arithmetic, so here the sample window, the step's noise draws, the out_2 bias and the K + 1 parameter rows of the
 //      next input layer are all in flight with the out_2 operands, and what follows the first barrier works on LDS and
 //      registers.  Same formulas in the same order as step_tail_kernel<LAPLACE> + input_layer (bit-identical results).
-template <int MAXE>      // elements (channel, position) of the next input layer per thread: ceil(H * seg / 256) <= MAXE
+template <int MAXE, bool STREAM = false>      // elements (channel, position) of the next input layer per thread: ceil(H * seg / 256) <= MAXE
 __global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StArgs a, const int it) {
     __shared__ float o2v[64];                  // NO <= 48
     __shared__ float lwin[32];                 // the updated sample window, for the fused next input layer
@@ -566,7 +569,7 @@ __global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StArgs a, 
     const SwnGeom& g = a.g;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
     float* st = a.state + (size_t)b * a.stride;
-    const int i = it - a.n_pro, seg = g.seg, WN = a.WN, H = g.H, K = g.K;
+    const int ia = it - a.n_pro, i = STREAM ? ia - a.step0 : ia, seg = g.seg, WN = a.WN, H = g.H, K = g.K;
     const float* P = a.P;
     float* shist = st + a.o_hist;
     // ---- requests: out_2 rows and bias, window, noise, input-layer parameters
@@ -586,7 +589,7 @@ __global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StArgs a, 
     const float b2v2 = st_ld1(rP, (rok2 && lane == 0) ? (unsigned)((a.y.b2 + grp + 8) * 4) : ST_OOB);
     const float hv = st_ld1(rS, tid < WN ? (unsigned)((((size_t)b * a.stride) + a.o_hist + tid) * 4) : ST_OOB);
     float ev = 0.f;
-    if (tid >= 64 && tid < 64 + seg) ev = swn_noise_laplace(a.nz, b, i, tid - 64, a.n_steps, seg);
+    if (tid >= 64 && tid < 64 + seg) ev = swn_noise_laplace_at(a.nz, b, i, ia, tid - 64, a.n_steps, seg);
     // next input layer (iteration it + 1, a generation step): element e = tid + 256 m -> position j = e / H, channel o
     const bool more = i + 1 < a.n_steps;
     float pcb[MAXE], pcv[MAXE][8], pcc[MAXE][8];
@@ -650,7 +653,7 @@ __global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StArgs a, 
     __syncthreads();
     if (!more) return;
     // ---- input layer of iteration it + 1 out of the prefetched rows (input_layer<LAPLACE>, generation form)
-    const int i1 = i + 1;
+    const int i1 = ia + 1;
     const int q0 = g.rf + 1 - seg + i1 * seg, qe = g.rf + i1 * seg;
 #pragma unroll
     for (int m = 0; m < MAXE; ++m) {
@@ -709,9 +712,11 @@ extern "C" size_t swn_decode_stepped_state_floats(const swn_net_desc* d, int bat
     return (size_t)plan(a) * batch;
 }
 
-extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                  int n_steps, const SwnNoise* nz, const void* forced, const void* seed, float* state,
-                                  void* out, float* heads, void* stream_) {
+// the launch chain of steps [step0, step0 + n_steps); stream = a chunk of a streamed decode: `state` is the session, which the
+// prologue fills only when !resume, and the tails take their STREAM form (chunk-local rows).  stream = false: swn_decode_stepped.
+static int stepped_run(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int step0,
+                       int n_steps, bool stream, bool resume, const SwnNoise* nz, const void* forced, const void* seed,
+                       float* state, void* out, float* heads, void* stream_) {
     StArgs a;
     int rc = swn_make_geom(d, &a.g);
     if (rc < 0) return rc;
@@ -722,12 +727,14 @@ extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, co
     swn_make_layout(&a.g, &a.y);
     plan(a);
     a.P = packed; a.cond = cond; a.nz = *nz; a.forced = forced; a.seed = seed; a.state = state; a.out = out; a.heads = heads;
-    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.n_pro = g.rf - g.seg + 1;
+    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.n_pro = g.rf - g.seg + 1; a.step0 = step0;
     // one 256-thread workgroup evaluates 8 rows per pass: beyond 64 rows (8 passes, ~7 us) a launch of its own is cheaper
     a.o2_by_rowvec = g.NO > 64 ? 1 : 0;
     hipStream_t st = (hipStream_t)stream_;
-    if (hipMemsetAsync(state, 0, sizeof(float) * (size_t)a.stride * batch, st) != hipSuccess) return SWN_E_LAUNCH;
-    if (g.kind == SWN_KIND_SOFTMAX || seed) hipLaunchKernelGGL(step_seed_kernel, dim3(batch), dim3(64), 0, st, a);
+    if (!resume) {
+        if (hipMemsetAsync(state, 0, sizeof(float) * (size_t)a.stride * batch, st) != hipSuccess) return SWN_E_LAUNCH;
+        if (g.kind == SWN_KIND_SOFTMAX || seed) hipLaunchKernelGGL(step_seed_kernel, dim3(batch), dim3(64), 0, st, a);
+    }
     // up to 64 utterances: one utterance per workgroup (weights re-read per utterance from the Infinity Cache;
     // measured faster than sharing: B=8 63 vs 137 us/step, B=64 162 vs 182 us/step on REF6);
     // otherwise tiles of 8 utterances share one weight fetch and are processed concurrently
@@ -778,11 +785,12 @@ extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, co
     // Laplace heads of up to 16 rows over up to 512 inputs, K <= 8 taps, <= 1 024 input-layer elements: the prefetching tail
     const bool fast_tail = g.kind == SWN_KIND_LAPLACE && g.NO <= 16 && g.O1p <= 512 && g.K <= 8 && g.H * g.seg <= 1024 &&
                            g.seg <= 16 && a.WN <= 32;
-    const int total = a.n_pro + n_steps;
-    for (int it = 0; it < total; ++it) {
-        // prologue positions and the very first generation step launch their own input layer; later steps
-        // get it from the tail of the step before
-        if (it <= a.n_pro) {
+    // iterations: the prologue positions (not when resuming), then the chunk's generation steps at absolute indices
+    const int it_gen0 = a.n_pro + step0, total = it_gen0 + n_steps;
+    for (int it = resume ? it_gen0 : 0; it < total; ++it) {
+        // prologue positions and the first generation step of the launch sequence run their own input layer; later
+        // steps get it from the tail of the step before
+        if (it < a.n_pro || it == it_gen0) {
             if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(step_in_kernel<SWN_KIND_LAPLACE>, dim3(batch), dim3(256), 0, st, a, it);
             else hipLaunchKernelGGL(step_in_kernel<SWN_KIND_SOFTMAX>, dim3(batch), dim3(256), 0, st, a, it);
         }
@@ -791,11 +799,40 @@ extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, co
         rowvec(g.S, a.y.wsk, g.L * g.Hp, a.y.bsk, g.L * g.Hp, a.o_hcat, a.o_skip, 1);
         rowvec(g.O1, a.y.w1, g.Sp, a.y.b1, g.Sp, a.o_skip, a.o_o1, 1);
         if (a.o2_by_rowvec) rowvec(g.NO, a.y.w2, g.O1p, a.y.b2, g.O1p, a.o_o1, a.o_o2, 0);
-        if (fast_tail) {
+        if (stream) {
+            if (fast_tail) {
+                if (g.H * g.seg <= 256) hipLaunchKernelGGL((step_tail_laplace_kernel<1, true>), dim3(batch), dim3(256), 0, st, a, it);
+                else hipLaunchKernelGGL((step_tail_laplace_kernel<4, true>), dim3(batch), dim3(256), 0, st, a, it);
+            } else if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL((step_tail_kernel<SWN_KIND_LAPLACE, true>), dim3(batch), dim3(256), 0, st, a, it);
+            else hipLaunchKernelGGL((step_tail_kernel<SWN_KIND_SOFTMAX, true>), dim3(batch), dim3(256), 0, st, a, it);
+        } else if (fast_tail) {
             if (g.H * g.seg <= 256) hipLaunchKernelGGL(step_tail_laplace_kernel<1>, dim3(batch), dim3(256), 0, st, a, it);
             else hipLaunchKernelGGL(step_tail_laplace_kernel<4>, dim3(batch), dim3(256), 0, st, a, it);
         } else if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(step_tail_kernel<SWN_KIND_LAPLACE>, dim3(batch), dim3(256), 0, st, a, it);
         else hipLaunchKernelGGL(step_tail_kernel<SWN_KIND_SOFTMAX>, dim3(batch), dim3(256), 0, st, a, it);
     }
     return swn_launch_status("swn_decode(stepped)");
+}
+
+extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                  int n_steps, const SwnNoise* nz, const void* forced, const void* seed, float* state,
+                                  void* out, float* heads, void* stream_) {
+    return stepped_run(d, packed, cond, batch, n_frames, 0, n_steps, false, false, nz, forced, seed, state, out, heads, stream_);
+}
+
+// 1 when the stepped chain runs this (net, batch) (the conditions swn_decode_stepped returns SWN_E_UNSUPPORTED under)
+extern "C" int swn_decode_stepped_supported(const swn_net_desc* d, int batch) {
+    StArgs t;
+    if (swn_make_geom(d, &t.g) < 0 || batch < 1) return 0;
+    const SwnGeom& g = t.g;
+    if ((g.K * g.Hp + 255) / 256 > 8 || g.seg > 16 || g.lpc > 16 || g.NO > 4096) return 0;
+    return ((size_t)plan(t) * batch * sizeof(float) < (1ull << 31) && t.WN <= 32) ? 1 : 0;
+}
+
+// one chunk of a streamed decode; the session is the state buffer of the chain (swn_decode_stepped_state_floats())
+extern "C" int swn_decode_stepped_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                        int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
+                                        const void* seed, float* sess, void* out, float* heads, void* stream_) {
+    return stepped_run(d, packed, cond, batch, n_frames, step0, n_steps, true, resume != 0, nz, forced, seed, sess, out, heads,
+                       stream_);
 }

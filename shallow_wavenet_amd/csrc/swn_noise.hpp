@@ -40,43 +40,52 @@ __device__ __forceinline__ uint32_t swn_rng_word(const SwnNoise& n, uint32_t utt
     return s == 0 ? r.x : (s == 1 ? r.y : (s == 2 ? r.z : r.w));
 }
 
-// uniform(-0.4999, 0.5) draw j of generation step `step` of utterance b (width = seg draws per step)
-__device__ __forceinline__ float swn_noise_laplace(const SwnNoise& n, int b, int step, int j, int n_steps, int seg) {
+// uniform(-0.4999, 0.5) draw j of generation step `step` of utterance b (width = seg draws per step).
+// The _at forms are those of a streamed chunk (swn_decode_chunk): `step` indexes the chunk-local host stream / dump of
+// n_steps steps, `abs_step` is the step of the whole utterance the generator counter takes; the plain forms are the
+// one-shot decode (abs_step == step).
+__device__ __forceinline__ float swn_noise_laplace_at(const SwnNoise& n, int b, int step, int abs_step, int j, int n_steps, int seg) {
     const size_t at = ((size_t)b * n_steps + step) * seg + j;
     float e;
     if (n.ptr) {
         e = n.ptr[at];
     } else {
-        const float u = (float)(swn_rng_word(n, (uint32_t)b, (uint32_t)step, (uint32_t)j, 0x4C41504Cu) >> 8) * 5.9604644775390625e-8f;
+        const float u = (float)(swn_rng_word(n, (uint32_t)b, (uint32_t)abs_step, (uint32_t)j, 0x4C41504Cu) >> 8) * 5.9604644775390625e-8f;
         e = fminf(fmaf(0.9999f, u, -0.4999f), 0.49999997f);
     }
     if (n.dump) n.dump[at] = e;
     return e;
 }
+__device__ __forceinline__ float swn_noise_laplace(const SwnNoise& n, int b, int step, int j, int n_steps, int seg) {
+    return swn_noise_laplace_at(n, b, step, step, j, n_steps, seg);
+}
 
 // Exp(1) draw of class `cls` at generation step `step` of utterance b
-__device__ __forceinline__ float swn_noise_exp1(const SwnNoise& n, int b, int step, int cls, int n_steps, int Q) {
+__device__ __forceinline__ float swn_noise_exp1_at(const SwnNoise& n, int b, int step, int abs_step, int cls, int n_steps, int Q) {
     const size_t at = ((size_t)b * n_steps + step) * Q + cls;
     float q;
     if (n.ptr) {
         q = n.ptr[at];
     } else {
-        const float u = ((float)(swn_rng_word(n, (uint32_t)b, (uint32_t)step, (uint32_t)cls, 0x45585031u) >> 9) + 0.5f) * 1.1920928955078125e-7f;
+        const float u = ((float)(swn_rng_word(n, (uint32_t)b, (uint32_t)abs_step, (uint32_t)cls, 0x45585031u) >> 9) + 0.5f) * 1.1920928955078125e-7f;
         q = -logf(u);
     }
     if (n.dump) n.dump[at] = q;
     return q;
 }
+__device__ __forceinline__ float swn_noise_exp1(const SwnNoise& n, int b, int step, int cls, int n_steps, int Q) {
+    return swn_noise_exp1_at(n, b, step, step, cls, n_steps, Q);
+}
 
 // the four Exp(1) draws of classes 4g .. 4g+3 (one generator call): same values as swn_noise_exp1 element by element.
 // Q must be a multiple of 4.
-__device__ __forceinline__ float4 swn_noise_exp1x4(const SwnNoise& n, int b, int step, int g, int n_steps, int Q) {
+__device__ __forceinline__ float4 swn_noise_exp1x4_at(const SwnNoise& n, int b, int step, int abs_step, int g, int n_steps, int Q) {
     const size_t at = ((size_t)b * n_steps + step) * Q + 4 * (size_t)g;
     float4 q;
     if (n.ptr) {
         q = *reinterpret_cast<const float4*>(n.ptr + at);
     } else {
-        const uint4 r = swn_philox4x32_10(make_uint4(swn_utt_id(n, (uint32_t)b), (uint32_t)step, (uint32_t)g, 0x45585031u),
+        const uint4 r = swn_philox4x32_10(make_uint4(swn_utt_id(n, (uint32_t)b), (uint32_t)abs_step, (uint32_t)g, 0x45585031u),
                                           make_uint2(n.key0, n.key1));
         q.x = -logf(((float)(r.x >> 9) + 0.5f) * 1.1920928955078125e-7f);
         q.y = -logf(((float)(r.y >> 9) + 0.5f) * 1.1920928955078125e-7f);
@@ -85,4 +94,7 @@ __device__ __forceinline__ float4 swn_noise_exp1x4(const SwnNoise& n, int b, int
     }
     if (n.dump) *reinterpret_cast<float4*>(n.dump + at) = q;
     return q;
+}
+__device__ __forceinline__ float4 swn_noise_exp1x4(const SwnNoise& n, int b, int step, int g, int n_steps, int Q) {
+    return swn_noise_exp1x4_at(n, b, step, step, g, n_steps, Q);
 }

@@ -175,7 +175,10 @@ def gpu_decode(kind: str, args, config, feat_list: Sequence[str], device, packed
                 seed = torch.full((len(ids), 1), config.n_quantize // 2, dtype=torch.int64, device=device)
             logging.info("decoding start")
             start = time.time()
-            samples_list = model.batch_fast_generate(seed, aux, n_samples_list, args.intervals)
+            if getattr(args, "stream_frames", 0) > 0:
+                samples_list = stream_generate(model, seed, aux, n_samples_list, args.stream_frames)
+            else:
+                samples_list = model.batch_fast_generate(seed, aux, n_samples_list, args.intervals)
             t_total += time.time() - start
             n_max += max(n_samples_list)
             n_tot += max(n_samples_list) * len(n_samples_list)
@@ -189,6 +192,24 @@ def gpu_decode(kind: str, args, config, feat_list: Sequence[str], device, packed
             logging.info("average throughput / sample = %.6f sec (%ld samples) [%.3f kHz/s]" % (
                 t_total / n_tot, n_tot, n_tot / (1000 * t_total)))
         return n_tot, t_total
+
+
+def stream_generate(model, seed, aux, n_samples_list, frames_per_push: int):
+    """batch_fast_generate's result by a streamed decode: the features are pushed `frames_per_push` frames at a time and
+    the samples collected as they become final (shallow_wavenet_amd.streaming; device-drawn noise only)."""
+    B = aux.shape[0]
+    stream = model.open_stream(B, seed)
+    pieces = []
+    for f0 in range(0, aux.shape[2], frames_per_push):
+        pieces.append(stream.push(aux[:, :, f0:f0 + frames_per_push])[0])
+    pieces.append(stream.finish()[0])
+    samples = torch.cat(pieces, dim=1).cpu().numpy()
+    max_samples = max(n_samples_list)
+    if model._cfg.kind == "softmax":
+        samples = samples.astype(np.int64)
+    elif max_samples <= samples.shape[1]:
+        samples = samples[:, -max_samples:]
+    return [samples[b, :n] for b, n in zip(range(B), n_samples_list)]
 
 
 def make_parser() -> argparse.ArgumentParser:
@@ -211,6 +232,9 @@ def make_parser() -> argparse.ArgumentParser:
                    help="not a reference flag: where the sampling noise is drawn - host = the torch CPU generator in "
                         "the reference's order (reproduces the reference's CPU decode), device = inside the kernels; "
                         "default: the model's own default (Laplace host, softmax device)")
+    p.add_argument("--stream_frames", default=0, type=int,
+                   help="not a reference flag: > 0 decodes each batch as a stream, pushing this many feature frames at a "
+                        "time (needs device-drawn noise; the WAVs are those of the one-shot decode)")
     p.add_argument("--plan_only", action="store_true",
                    help="not a reference flag: stop after listing, sharding and the parameter broadcast and write "
                         "<outdir>/decode.<rank>.plan.json (needs no GPU: what the CPU tests of the fan-out drive)")
@@ -282,6 +306,10 @@ def fan_out(kind: str, argv, n_gpus: int, visible: str = None) -> int:
 
 def main(kind: str, argv=None) -> int:
     args = make_parser().parse_args(argv)
+    if args.stream_frames > 0 and (args.noise_source or ("host" if kind == "laplace" else "device")) != "device":
+        print("--stream_frames needs device-drawn noise (--noise_source device): the host stream is drawn for the whole run "
+              "up front", file=sys.stderr)
+        return 2
     if "WORLD_SIZE" not in os.environ and args.n_gpus > 1:
         return fan_out(kind, argv, args.n_gpus, args.GPU_device_str)        # before anything below can touch a GPU
     rank, world, local = D.init_from_env()

@@ -120,6 +120,31 @@ class EngineMixin:
             return net
         return cache[1]
 
+    def open_stream(self, batch: int, audio=None, variant: int = 0):
+        """a streamed decode of `batch` utterances on the module's current engine (shallow_wavenet_amd.streaming.DecodeStream):
+        push features as they arrive, get the samples whose conditioning is final.  Bit-identical to batch_fast_generate with
+        noise_source = "device" and the same key: the kernels draw the noise, keyed by `noise_rng_seed` when the caller
+        pinned one (else one fresh key per stream, taken from the torch CPU generator) and indexed by
+        `noise_utterance_ids` / `noise_utterance_offset`.  The host-noise default of the Laplace model's
+        batch_fast_generate draws the whole run up front in the reference's order and is not streamed (DecodeStream.advance
+        takes host noise chunk by chunk).  audio: the seed waveform as batch_fast_generate takes it (None = zeros / Q/2)."""
+        from .. import noise as _noise
+        from ..streaming import DecodeStream
+        net = self._engine()
+        cfg = self._cfg
+        seed = None
+        if audio is not None:
+            if cfg.kind == "softmax":
+                seed = audio.reshape(batch, -1)[:, -1] % cfg.n_quantize
+                seed = seed if torch.count_nonzero(seed - cfg.n_quantize // 2).item() != 0 else None
+            else:
+                seed = audio.reshape(batch, -1)[:, -cfg.seg:] if torch.count_nonzero(audio).item() != 0 else None
+        key = getattr(self, "noise_rng_seed", None)
+        return DecodeStream(net, batch, variant=variant, seed=seed,
+                            rng_seed=_noise.draw_rng_seed() if key is None else int(key),
+                            rng_utt0=int(getattr(self, "noise_utterance_offset", 0)),
+                            utt_ids=getattr(self, "noise_utterance_ids", None))
+
     def set_packed_engine(self, net: HipNet) -> None:
         """install an engine whose packed buffer arrived by RCCL broadcast (dist.py)."""
         self.__dict__["_engine_cache"] = (self._engine_key(), net)

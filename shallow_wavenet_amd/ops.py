@@ -15,6 +15,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.frontend(packed, aux, desc)                      -> (cond, work)
     torch.ops.swn.decode(packed, cond, noise?, forced?, seed?, desc, n_steps, variant, rng_seed, rng_utt0,
                          want_heads, want_noise, utt_ids?)         -> (out, heads, noise_used)
+    torch.ops.swn.decode_chunk(packed, cond, session, noise?, forced?, seed?, desc, step0, n_steps, begin, variant,
+                               rng_seed, rng_utt0, want_heads, want_noise, utt_ids?)  -> (out, heads, noise_used)
     torch.ops.swn.stack_forward(packed, cond, audio, desc, want_hidden) -> (raw, work, hidden)
     torch.ops.swn.stack_forward_bf16(packed, wbf16, cond, audio, desc)  -> (raw, work)
     torch.ops.swn.pack_bf16(packed, desc)                          -> wbf16
@@ -202,6 +204,73 @@ decode = custom_op("swn::decode", mutates_args=())(decode_impl)
 
 @decode.register_fake
 def _(packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise, utt_ids=None):
+    d = _desc(desc)
+    soft, seg, _, _, n_out, _ = _geom(d)
+    B = cond.shape[0]
+    width = d.n_quantize if soft else seg
+    return (packed.new_empty((B, n_steps * seg), dtype=torch.int32 if soft else torch.float32),
+            packed.new_empty((B, n_steps, n_out) if want_heads else (0,)),
+            packed.new_empty((B, n_steps, width) if want_noise else (0,)))
+
+
+# ------------------------------------------------------------------------------------------ streamed decode
+def decode_chunk_impl(packed: torch.Tensor, cond: torch.Tensor, session: torch.Tensor, noise: Optional[torch.Tensor],
+                      forced: Optional[torch.Tensor], seed: Optional[torch.Tensor], desc: List[int], step0: int,
+                      n_steps: int, begin: bool, variant: int, rng_seed: int, rng_utt0: int, want_heads: bool,
+                      want_noise: bool, utt_ids: Optional[torch.Tensor] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """steps [step0, step0 + n_steps) of a streamed decode (swn_decode_chunk): `session` (swn_decode_session_floats() fp32,
+    updated in place) carries the decode state from one chunk to the next; begin=True runs the prologue (step0 0).  cond
+    holds the frames final so far (absolute indexing); noise / forced / out / heads / used noise are the chunk's rows."""
+    L = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(packed, "the packed parameters")
+    dev = packed.device
+    soft, seg, _, _, n_out, _ = _geom(d)
+    B, Tf = cond.shape[0], cond.shape[1]
+    width = d.n_quantize if soft else seg
+    cond = cond.contiguous()
+    if session.device != dev or session.dtype != torch.float32 or not session.is_contiguous():
+        raise RuntimeError("session must be a contiguous fp32 tensor on the device of the packed parameters")
+    if session.numel() < L.swn_decode_session_floats(ctypes.byref(d), B, variant):
+        raise RuntimeError("session buffer too small for this (net, batch, variant)")
+    if noise is not None:
+        noise = noise.to(dev, torch.float32).contiguous()
+        if tuple(noise.shape) != (B, n_steps, width):
+            raise RuntimeError(f"noise shape {tuple(noise.shape)} != {(B, n_steps, width)}")
+    if forced is not None:
+        forced = forced.to(dev, torch.int32 if soft else torch.float32).contiguous()
+        if forced.numel() != B * n_steps * seg:
+            raise RuntimeError("forced history has the wrong size")
+    if seed is not None:
+        seed = seed.to(dev, torch.int32 if soft else torch.float32).contiguous()
+        if seed.numel() != B * seg:
+            raise RuntimeError(f"seed waveform has {seed.numel()} elements, expected {B * seg}")
+    if utt_ids is not None:
+        utt_ids = utt_ids.to(dev, torch.int32).contiguous()
+        if utt_ids.numel() != B:
+            raise RuntimeError(f"utt_ids has {utt_ids.numel()} elements, expected {B}")
+    out = torch.empty((B, n_steps * seg), dtype=torch.int32 if soft else torch.float32, device=dev)
+    heads = torch.empty((B, n_steps, n_out) if want_heads else (0,), dtype=torch.float32, device=dev)
+    used = torch.empty((B, n_steps, width) if want_noise else (0,), dtype=torch.float32, device=dev)
+    io = _lib.DecodeIO(noise_dev=_ptr(noise), forced_dev=_ptr(forced), seed_dev=_ptr(seed),
+                       noise_out_dev=_ptr(used if want_noise else None),
+                       rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=int(rng_utt0) & 0xFFFFFFFF, reserved=0,
+                       rng_utt_ids_dev=_ptr(utt_ids))
+    with _on(dev):
+        _lib.check(L.swn_decode_chunk(ctypes.byref(d), _ptr(packed), _ptr(cond), B, Tf, int(step0), int(n_steps),
+                                      _lib.CHUNK_BEGIN if begin else 0, ctypes.byref(io), _ptr(session),
+                                      _ptr(out if n_steps > 0 else None), _ptr(heads if want_heads else None), int(variant),
+                                      _stream(dev)), "decode_chunk")
+    return out, heads, used
+
+
+decode_chunk = custom_op("swn::decode_chunk", mutates_args=("session",))(decode_chunk_impl)
+
+
+@decode_chunk.register_fake
+def _(packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0, want_heads,
+      want_noise, utt_ids=None):
     d = _desc(desc)
     soft, seg, _, _, n_out, _ = _geom(d)
     B = cond.shape[0]
@@ -439,5 +508,5 @@ def backward_bf16_supported(desc: List[int], batch: int, n_frames: int) -> bool:
     return _lib.lib().swn_backward_bf16_work_floats(ctypes.byref(_desc(desc)), batch, n_frames) > 0
 
 
-OP_NAMES = ("pack_params", "frontend", "decode", "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
+OP_NAMES = ("pack_params", "frontend", "decode", "decode_chunk", "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16")

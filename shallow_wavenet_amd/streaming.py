@@ -1,0 +1,218 @@
+"""Streaming decode: features arrive a few frames at a time, samples come out as soon as their conditioning is final.
+
+`DecodeStream` wraps the resumable decode of the C ABI (swn_decode_chunk): a session buffer on the device carries the
+decode state from one chunk to the next, so the concatenated output of any sequence of chunks is bit-identical to one
+`HipNet.decode` over the whole utterance (same kernel variant, noise key, seed waveform and utterance indices).
+
+Conditioning.  conv_aux is two-sided (cswnv_shift1.py:95-127): frame f depends on frames f - la .. f + la, with the
+halo la = lookahead_frames(cfg).  After R frames have arrived, frames [0, R - la) are final.  Each push runs the front end
+(swn_frontend) on the window [max(0, done - la), R) and keeps only its interior frames [done, R - la): those see exactly
+the inputs the one-shot front end sees, so their cond rows are bit-identical.  `finish` ends the features; the front end's
+own zero padding on the right then is the one-shot padding, and every remaining frame becomes final.
+
+Steps.  A generation step i reads cond frames up to ((i + 1) * seg - 1) // U, so with F final frames the steps
+[0, F * U // seg) can run (the bound of swn_decode).  Step counts come from frame counts on the host: nothing here
+waits for the device.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import torch
+
+from . import _lib
+from . import ops as _ops          # registers torch.ops.swn.*
+from .config import NetConfig
+
+_O = torch.ops.swn
+
+
+def lookahead_frames(cfg: NetConfig) -> int:
+    """frames of right context conv_aux needs before a frame's conditioning is final: the half-width of the two-sided
+    dilated stack, sum over layers of dilation * (k - 1) / 2 = (k ** layers - 1) / 2 for an odd kernel k."""
+    k, layers = int(cfg.aux_kernel_size), int(cfg.aux_dilation_size)
+    if k % 2 == 0:
+        raise ValueError("conv_aux needs an odd kernel size")
+    return (k ** layers - 1) // 2
+
+
+def final_frames(received: int, lookahead: int, finished: bool) -> int:
+    """frames whose conditioning is final after `received` frames (all of them once the features have ended)."""
+    return received if finished else max(0, received - lookahead)
+
+
+def ready_steps(cfg: NetConfig, frames_final: int) -> int:
+    """generation steps whose conditioning lies inside the first `frames_final` frames."""
+    seg = 1 if cfg.kind == "softmax" else int(cfg.seg)
+    return frames_final * int(cfg.U) // seg
+
+
+class DecodeStream:
+    """one streamed decode of a batch of `batch` utterances that advance in lockstep.
+
+    net        a HipNet (packed parameters on the device); anything with `cfg`, `packed`, `device` and `dlist`
+    variant    decode kernel, as HipNet.decode (0 = auto); it is resolved once and kept for the whole stream
+    seed       the seed waveform of batch_fast_generate: laplace (B, seg) fp32 | softmax (B,) classes; None = zeros / Q/2
+    rng_seed, rng_utt0, utt_ids   the device generator's key and utterance indices, as HipNet.decode
+    want_heads / want_noise       also return the raw out_2 rows / the noise the kernels used, per chunk
+
+    push / finish / advance return what HipNet.decode returns for the new steps: (out, heads) or, with want_noise,
+    (out, heads, noise) - out laplace (B, n * seg) fp32 | softmax (B, n) int32 on the device, heads None unless asked for.
+    With generate=False, push / finish only extend the final conditioning (then `advance` runs steps explicitly: host
+    noise and teacher forcing are streamed that way) and return None.
+    """
+
+    def __init__(self, net, batch: int, *, variant: int = 0, seed: Optional[torch.Tensor] = None, rng_seed: int = 0,
+                 rng_utt0: int = 0, utt_ids: Optional[Sequence[int]] = None, want_heads: bool = False,
+                 want_noise: bool = False):
+        cfg = net.cfg
+        if not isinstance(batch, int) or batch < 1:
+            raise ValueError(f"batch must be a positive integer, not {batch!r}")
+        self.net, self.cfg, self.batch = net, cfg, batch
+        self.soft = cfg.kind == "softmax"
+        self.seg = 1 if self.soft else int(cfg.seg)
+        self.width = int(cfg.n_quantize) if self.soft else self.seg
+        self.lookahead_frames = lookahead_frames(cfg)
+        desc = _ops._desc(net.dlist)
+        lib = _lib.lib()
+        resolved = lib.swn_decode_resolve_variant(desc, batch, int(variant))
+        if resolved < 0:
+            raise ValueError(f"decode variant {variant} does not resolve for this net and batch "
+                             f"({lib.swn_strerror(resolved).decode()})")
+        self.variant = int(variant)
+        self.resolved_variant = resolved
+        self._session_floats = int(lib.swn_decode_session_floats(desc, batch, int(variant)))
+        if seed is not None:
+            seed = torch.as_tensor(seed)
+            if seed.numel() != batch * self.seg:
+                raise ValueError(f"seed has {seed.numel()} elements, expected {batch * self.seg}")
+        if utt_ids is not None:
+            utt_ids = [int(u) for u in utt_ids]
+            if len(utt_ids) != batch:
+                raise ValueError(f"utt_ids has {len(utt_ids)} entries, expected {batch}")
+        self._seed = seed
+        self._ids = None if utt_ids is None else torch.tensor(utt_ids, dtype=torch.int32)
+        self.rng_seed = int(rng_seed) & 0x7FFFFFFFFFFFFFFF
+        self.rng_utt0 = int(rng_utt0) & 0xFFFFFFFF
+        self.want_heads, self.want_noise = bool(want_heads), bool(want_noise)
+        self.steps_done = 0
+        self.frames_received = 0
+        self.frames_final = 0
+        self.finished = False
+        self._begun = False
+        self._session = None          # device buffers: allocated on the first push
+        self._aux = None              # (B, n_aux, capacity) features received so far
+        self._cond = None             # (B, capacity, N) final conditioning rows (zeros beyond frames_final)
+
+    # ------------------------------------------------------------------ properties
+    @property
+    def steps_ready(self) -> int:
+        return ready_steps(self.cfg, self.frames_final)
+
+    @property
+    def cond(self) -> Optional[torch.Tensor]:
+        """the final conditioning rows so far, (B, frames_final, N)."""
+        return None if self._cond is None else self._cond[:, :self.frames_final]
+
+    # ------------------------------------------------------------------ features
+    def _check_aux(self, aux: torch.Tensor) -> torch.Tensor:
+        if self.finished:
+            raise RuntimeError("the stream is finished: no features can be pushed after finish()")
+        if not isinstance(aux, torch.Tensor) or aux.dim() != 3:
+            raise ValueError("features must be a (B, n_aux, frames) tensor")
+        if aux.shape[0] != self.batch:
+            raise ValueError(f"features for {aux.shape[0]} utterances pushed to a stream of batch {self.batch}")
+        if aux.shape[1] != self.cfg.n_aux:
+            raise ValueError(f"features have {aux.shape[1]} channels, the model expects {self.cfg.n_aux}")
+        return aux
+
+    @staticmethod
+    def _grow(buf: Optional[torch.Tensor], dim: int, need: int, shape, device) -> torch.Tensor:
+        """buffer with at least `need` entries along `dim`, capacity doubled on growth (old contents kept)."""
+        cap = 0 if buf is None else buf.shape[dim]
+        if cap >= need:
+            return buf
+        new_cap = max(64, cap)
+        while new_cap < need:
+            new_cap *= 2
+        shp = list(shape)
+        shp[dim] = new_cap
+        nb = torch.zeros(shp, dtype=torch.float32, device=device)
+        if buf is not None:
+            nb.narrow(dim, 0, cap).copy_(buf)
+        return nb
+
+    def _append(self, aux: torch.Tensor) -> None:
+        B, na, f = aux.shape
+        if f == 0:
+            return
+        dev = self.net.device
+        self._aux = self._grow(self._aux, 2, self.frames_received + f, (B, na, 0), dev)
+        self._aux[:, :, self.frames_received:self.frames_received + f].copy_(aux.to(dev, torch.float32))
+        self.frames_received += f
+
+    def _finalise(self, upto: int) -> None:
+        """cond rows of frames [frames_final, upto) from the front end over the window they need."""
+        if upto <= self.frames_final:
+            return
+        w0 = max(0, self.frames_final - self.lookahead_frames)
+        window = self._aux[:, :, w0:self.frames_received].contiguous()
+        cw, _work = _O.frontend(self.net.packed, window, self.net.dlist)
+        self._cond = self._grow(self._cond, 1, upto, (self.batch, 0, cw.shape[2]), self.net.device)
+        self._cond[:, self.frames_final:upto].copy_(cw[:, self.frames_final - w0:upto - w0])
+        self.frames_final = upto
+
+    def push(self, aux_chunk: torch.Tensor, generate: bool = True):
+        """append (B, n_aux, f) fp32 features; finalise the conditioning they complete and generate every step it
+        allows (possibly none)."""
+        self._append(self._check_aux(aux_chunk))
+        if self.frames_received > 0:
+            self._finalise(final_frames(self.frames_received, self.lookahead_frames, False))
+        return self._run_to(self.steps_ready) if generate else None
+
+    def finish(self, aux_tail: Optional[torch.Tensor] = None, generate: bool = True):
+        """the features end here (optionally with a last piece): every frame becomes final (zero padding on the right, as
+        the one-shot front end pads) and the steps up to frames * U // seg are generated."""
+        if aux_tail is not None:
+            self._append(self._check_aux(aux_tail))
+        elif self.finished:
+            raise RuntimeError("the stream is already finished")
+        self.finished = True
+        if self.frames_received == 0:
+            raise RuntimeError("finish() on a stream that received no features")
+        self._finalise(self.frames_received)
+        return self._run_to(self.steps_ready) if generate else None
+
+    # ------------------------------------------------------------------ steps
+    def _run_to(self, target: int):
+        return self.advance(max(0, target - self.steps_done))
+
+    def advance(self, n_steps: int, noise: Optional[torch.Tensor] = None, forced: Optional[torch.Tensor] = None):
+        """run the next n_steps steps over conditioning that is already final.  noise: the host-drawn stream of these steps,
+        laplace (B, n_steps, seg) | softmax (B, n_steps, Q); forced: their teacher-forced inputs, as HipNet.decode."""
+        n = int(n_steps)
+        if n < 0:
+            raise ValueError("n_steps must be >= 0")
+        if self.steps_done + n > self.steps_ready:
+            raise RuntimeError(f"steps [{self.steps_done}, {self.steps_done + n}) need conditioning beyond the "
+                               f"{self.frames_final} final frames (at most {self.steps_ready} steps)")
+        if n == 0:
+            dev = self.net.device
+            out = torch.empty((self.batch, 0), dtype=torch.int32 if self.soft else torch.float32, device=dev)
+            heads = torch.empty((self.batch, 0, self.cfg.n_out), dtype=torch.float32, device=dev) if self.want_heads else None
+            if self.want_noise:
+                return out, heads, torch.empty((self.batch, 0, self.width), dtype=torch.float32, device=dev)
+            return out, heads
+        if self._session is None:
+            self._session = torch.empty(self._session_floats, dtype=torch.float32, device=self.net.device)
+        # n_frames of the call = the buffer's capacity (the per-utterance stride of the rows); the bound that matters is
+        # the one on frames_final checked above - rows past it are zeros that no step of this chunk reads
+        out, heads, used = _O.decode_chunk(self.net.packed, self._cond, self._session, noise, forced, self._seed,
+                                           self.net.dlist, self.steps_done, n, not self._begun, self.variant,
+                                           self.rng_seed, self.rng_utt0, self.want_heads, self.want_noise, self._ids)
+        self._begun = True
+        self.steps_done += n
+        heads = heads if self.want_heads else None
+        if self.want_noise:
+            return out, heads, used
+        return out, heads
