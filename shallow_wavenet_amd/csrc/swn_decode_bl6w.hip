@@ -10,15 +10,16 @@
 //   * group A (waves 0-3, one per SIMD) owns the chain: per layer the CURRENT-tap half (128 rows x 64 inputs: thread (o, p) two
 //     rows x 16 inputs, reduced over 4 lanes), the gate epilogue, the hand-off through LDS;
 //   * group B (waves 4-7, the other wave of every SIMD) works one step AHEAD and off the chain: the OLDER-tap halves (+ bias) of
-//     all six layers for step t + 1, left in LDS (formed where group B has room: one in the first layer phase, three beside group
-//     A's out_1, two beside wave 0's tail), and the whole out_skip accumulation of step t (slice l in the phase after layer l);
+//     all six layers for step t + 1, left in LDS (formed where group B has room: three in the first phase, three beside group
+//     A's out_1), and the whole out_skip accumulation of step t (slice l in the phase after layer l);
 //   * group A keeps its halves of all six matrices in registers (192 per thread), group B five of them (160) and the sixth in LDS
 //     (it also holds a slice of out_skip weights in flight); the out_1 matrix is LDS-resident whole (the 64 KB the sixth layer of
 //     the symmetric kernel took), only out_skip streams from L2;
-//   * out_1 is group A's alone (two rows per thread), out_2 + sampling + the next input layer wave 0's, as before.
+//   * out_1 is group A's alone (two rows per thread); out_2 + sampling + the next input layer run in every wave of group A, each
+//     forming its own copy of h0 and going straight on into layer 0 (wave 0 alone stores the sample and the heads).
 // Same arithmetic per element as the symmetric kernel up to the order of the partial sums (1e-7 relative); same noise, seed,
 // forced-input and heads interface (swn_decode_bl6.hip: classic = host-drawn noise, zero seed; extended = in-kernel generator,
-// noise dump, caller's seed waveform).  9 barriers per step.  cswnv_shift1.py:281-430.
+// noise dump, caller's seed waveform).  8 barriers per step.  cswnv_shift1.py:281-430.
 #include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
 #include "swn_noise.hpp"
@@ -88,7 +89,9 @@ struct Tw {
     static constexpr int o_w1 = o_bias + S + O1;           // out_1, lane-tiled [8][O1][4][4] like the global copy w12
     static constexpr int o_wl = o_w1 + 8 * O1 * 16;        // group B's half of the LAST layer, [8][256 threads][4]: with it in registers
                                                            // too (192 + the out_skip weights in flight) the kernel spilled 22-35 registers
-    static constexpr int o_end = o_wl + 8 * NG * 4;
+    static constexpr int o_h0w = o_wl + 8 * NG * 4;        // h0 of the next position as waves 1-3 of group A form it, [3][H] (wave 0's copy
+                                                           // is the layer-0 ring slot); past 64 KB: addressed from a per-wave base
+    static constexpr int o_end = o_h0w + 3 * H;
     static constexpr size_t lds_bytes = (size_t)o_end * sizeof(float);
     // per-utterance session of a streamed decode: the history rings, the older-tap products group B formed one step ahead
     // (both parities, as LDS holds them), then the sample window
@@ -133,20 +136,20 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 // ---- group A: layer LAYER at position q - current tap, gate epilogue, hand-off.  Thread (o, p): rows o (gate) and o + 64
-//      (candidate) over inputs 16 p .. 16 p + 15 of h_{l-1}(q); lanes 0 / 1 of the quad finish the gate / the candidate.
+//      (candidate) over inputs 16 p .. 16 p + 15 of h_{l-1}(q), read from the row `xr`; lanes 0 / 1 of the quad finish the gate / the
+//      candidate.
 template <class T, int LAYER>
-__device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], const int q, const float wj, const int pb, const int ta) {
-    constexpr int R = T::ring_len(LAYER);
+__device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], const int q, const float wj, const int pb, const int ta,
+                                        const float* xr) {
     const int o = ta >> 2, p = ta & 3, pr = p & 1;
-    const float* ring = lds + T::o_ring + T::ring_off(LAYER);
     // epilogue operands first: their LDS latency hides under the FMAs
     const float e_old = lds[T::o_old + (q & 1) * (L * 2 * H) + LAYER * 2 * H + pr * H + o];
     const float e_gx = fmaf(wj, lds[T::o_gp + pb + LAYER * 2 * H + pr * H + o], lds[T::o_bx + LAYER * 2 * H + pr * H + o]);
-    const float e_hp = ring[(q & (R - 1)) * H + o];
+    const float e_hp = xr[o];
     float az = 0.f, ac = 0.f;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        const float4 x = *reinterpret_cast<const float4*>(ring + (q & (R - 1)) * H + 16 * p + 4 * m);
+        const float4 x = *reinterpret_cast<const float4*>(xr + 16 * p + 4 * m);
         az = fmaf(w[0][4 * m], x.x, az); ac = fmaf(w[1][4 * m], x.x, ac);
         az = fmaf(w[0][4 * m + 1], x.y, az); ac = fmaf(w[1][4 * m + 1], x.y, ac);
         az = fmaf(w[0][4 * m + 2], x.z, az); ac = fmaf(w[1][4 * m + 2], x.z, ac);
@@ -221,16 +224,6 @@ __device__ __forceinline__ void older_b(float* lds, const float (&w)[2][16], con
 // three layers at once: one basic block of three independent chains (the stores' lane branch between them kept the scheduler from
 // overlapping the products: 570 cycles each, one after the other)
 template <class T, int LA>
-__device__ __forceinline__ void older_b2(float* lds, const float (&w)[L][2][16], const int qn, const int tb) {
-    float az0, ac0, az1, ac1;
-    older_sum<T, LA>(lds, w[LA], qn, tb, az0, ac0);
-    older_sum<T, LA + 1>(lds, w[LA + 1], qn, tb, az1, ac1);
-    if ((tb & 3) < 2) {
-        older_store<T, LA>(lds, qn, tb, az0, ac0);
-        older_store<T, LA + 1>(lds, qn, tb, az1, ac1);
-    }
-}
-template <class T, int LA>
 __device__ __forceinline__ void older_b3(float* lds, const float (&w)[L][2][16], const int qn, const int tb) {
     float az0, ac0, az1, ac1, az2, ac2;
     older_sum<T, LA>(lds, w[LA], qn, tb, az0, ac0);
@@ -288,7 +281,7 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
     static_assert(!STREAM || EXT, "streamed chunks run the extended mode");
     constexpr bool grpA = GA;
     const int tid = threadIdx.x, b = blockIdx.x;
-    __builtin_assume(GA ? tid < NG : tid >= NG);              // group B compiles none of wave 0's and wave 1's side jobs (head, noise, input layer)
+    __builtin_assume(GA ? tid < NG : tid >= NG);              // group B compiles none of group A's side jobs (head, noise, input layer)
     // (a raised s_setprio for group A - the chain first at the SIMD's issue arbitration - measured no gain: 283.6 / 278.8 / 282.9 k
     //  samples/s at priority 0 / 1 / 3)
     const int tg = tid & (NG - 1);                            // index inside the group
@@ -400,15 +393,25 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
 #pragma unroll
         for (int k = 0; k < T::WN; ++k) win[k] = sess_b[T::sess_win + k];
     }
-    // (the five input-layer constants of wave 0's channel stay in registers: the tail phase is one wave's dependent chain)
+    // Every wave of group A forms h0 of the next position itself (lane = channel, the same instructions on the same inputs: the four
+    // copies agree bit for bit) and goes straight into layer 0 with it - no barrier between the sample and the first layer.  Wave 0's
+    // copy is the layer-0 ring slot (group B's older tap and the session read it), waves 1-3 keep theirs at o_h0w.
+    // (the five input-layer constants of the wave's channel stay in registers: the tail is a dependent chain)
+    const int wv = __builtin_amdgcn_readfirstlane(tg >> 6);   // wave inside the group
     float kcb = 0.f, kv0 = 0.f, kv1 = 0.f, kc0 = 0.f, kc1 = 0.f;
-    if (tid < H) { const int o = tid; kcb = c_b; kv0 = c_v0; kv1 = c_v1; kc0 = c_c0; kc1 = c_c1; }
+    if (grpA) { const int o = tg & (H - 1); kcb = c_b; kv0 = c_v0; kv1 = c_v1; kc0 = c_c0; kc1 = c_c1; }
+    auto h0_row = [&](int qn) -> float* {
+        return wv == 0 ? lds + T::o_ring + (qn & 1) * H : lds + T::o_h0w + (wv - 1) * H;
+    };
     auto input_gen = [&](int qn) {
-        if (tid < H) {
+        if constexpr (grpA) {
             float acc = kcb;
             acc += fmaf(kv0, win[T::WN - 2], kc0);
             acc += fmaf(kv1, win[T::WN - 1], kc1);
-            lds[T::o_ring + (qn & 1) * H + tid] = ssign(acc);
+            h0_row(qn)[tg & (H - 1)] = ssign(acc);
+            // the row is read by the other lanes of this wave only: LDS serves a wave's instructions in order, so its own
+            // counter is all the ordering needed (the clobber keeps the compiler from moving the reads above the write)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
     };
     // sampling noise staged off the chain (swn_decode_bl6.hip): wave 1 transforms tn = sign(e) log1p(-2|e|)
@@ -441,16 +444,20 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
 
 #ifdef SWN_STAMP
     // diagnostic build only (tools/stamp_decode_w.py): per phase, the cycles each group's first wave WORKS between two barriers
-    // (barrier waits excluded) leave through the `heads` debug buffer: [0..9) group A, [9] A's whole step, [10..19) group B
+    // (barrier waits excluded) leave through the `heads` debug buffer: [0..8) group A (phase 0 = the previous step's tail + layer
+    // 0), [8] the tail's share of phase 0, [9] A's whole step, [10..18) group B
     unsigned long long tw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tstep = 0, tlast = 0, tbeg = 0;
 #define SWN_BAR(k) { tw[k] += __builtin_amdgcn_s_memtime() - tlast; lds_barrier(); tlast = __builtin_amdgcn_s_memtime(); }
 #else
 #define SWN_BAR(k) lds_barrier();
 #endif
     // one layer phase: group A runs the chain, group B prepares position q + 1 (and, during generation, accumulates out_skip)
-    // (OLD: the layer whose older-tap product for position q + 1 group B forms in this phase, -1 = none)
-#define SWN_PHASE(LAYER, GEN, OLD)                                                                                    \
-    if constexpr (grpA) layer_a<T, LAYER>(lds, wreg[LAYER], q, wj, pb, tg);                                            \
+    // (OLD: the first layer whose older-tap product for position q + 1 group B forms in this phase, -1 = none; NOLD: how many,
+    //  1 or 3; X0: the row of h0(q) layer 0 reads)
+#define SWN_PHASE(LAYER, GEN, OLD, NOLD, X0)                                                                          \
+    if constexpr (grpA) layer_a<T, LAYER>(lds, wreg[LAYER], q, wj, pb, tg,                                             \
+                                          LAYER == 0 ? (X0) : lds + T::o_ring + T::ring_off(LAYER) +                   \
+                                                                  (q & (T::ring_len(LAYER) - 1)) * H);                 \
     else {                                                                                                             \
         if (GEN) {   /* the slice in flight is consumed BEFORE the next one is requested (both live at once are 64 registers  */ \
                      /* beside the 160 of the weights); the request then flies under the older-tap product and the barrier    */ \
@@ -459,7 +466,8 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
             skip_issue_b<LAYER>(wsk2, wsl, tg, step0);                                                                 \
             __builtin_amdgcn_sched_barrier(0);                                                                         \
         }                                                                                                              \
-        if (OLD >= 0) older_b<T, (OLD >= 0 ? OLD : 0)>(lds, wreg[OLD >= 0 ? OLD : 0], q + 1, tg);                        \
+        if (OLD >= 0 && NOLD == 1) older_b<T, (OLD >= 0 ? OLD : 0)>(lds, wreg[OLD >= 0 ? OLD : 0], q + 1, tg);           \
+        if (OLD >= 0 && NOLD == 3) older_b3<T, (OLD >= 0 && OLD + 3 <= L ? OLD : 0)>(lds, wreg, q + 1, tg);              \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
     }                                                                                                                  \
     if (GEN) { SWN_BAR(LAYER) } else lds_barrier();
@@ -472,13 +480,21 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
         cond_taps(q, wj, pb);
         input_seed(q);
         lds_barrier();
-        SWN_PHASE(0, false, 0) SWN_PHASE(1, false, 1) SWN_PHASE(2, false, 2) SWN_PHASE(3, false, 3) SWN_PHASE(4, false, 4) SWN_PHASE(5, false, 5)
+        const float* x0 = lds + T::o_ring + (q & 1) * H;
+        SWN_PHASE(0, false, 0, 1, x0) SWN_PHASE(1, false, 1, 1, x0) SWN_PHASE(2, false, 2, 1, x0) SWN_PHASE(3, false, 3, 1, x0)
+        SWN_PHASE(4, false, 4, 1, x0) SWN_PHASE(5, false, 5, 1, x0)
         (void)wsl; (void)sacc; (void)step0;
     }
 
-    // ---- generation (cswnv_shift1.py:348-402)
+    // ---- generation (cswnv_shift1.py:348-402).  Eight barriers per step: the first phase of step q is the tail of step q - 1
+    //      (out_2, head, sample, h0(q) in every wave of group A) followed by layer 0 of step q.  The conditioning refill of a frame
+    //      crossing (cond_taps) is written in that phase too: the buffer it fills was last read before the previous step's barriers,
+    //      and the next reader comes U steps later.
     input_gen(RF + s0);
     noise_ahead(0);
+#ifdef SWN_STAMP
+    tlast = tbeg = __builtin_amdgcn_s_memtime();
+#endif
     auto gen_step = [&](const int i) __attribute__((always_inline)) {
         const int q = RF + s0 + i;
         float wj; int pb;
@@ -487,14 +503,13 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
         float sacc[2] = {0.f, 0.f};
         unsigned step0 = 0;
         asm volatile("" : "+s"(step0));                       // opaque zero, see skip_issue_b
-        lds_barrier();
-#ifdef SWN_STAMP
-        tlast = tbeg = __builtin_amdgcn_s_memtime();
-#endif
-        // group B's older-tap products of position q + 1 sit in the out_1 phase (layers 0-2: group A runs out_1 alone), in the tail
-        // phase (layers 3-4: only wave 0 has work there) and in the first layer phase (layer 5: no slice to consume yet); all six
-        // beside the out_skip slices made group B take 1 050 cycles per layer phase against group A's 710
-        SWN_PHASE(0, true, 5) SWN_PHASE(1, true, -1) SWN_PHASE(2, true, -1) SWN_PHASE(3, true, -1) SWN_PHASE(4, true, -1) SWN_PHASE(5, true, -1)
+        const float* x0 = h0_row(q);
+        // group B's older-tap products of position q + 1 sit in the first phase (layers 3-5: no slice to consume yet, group A's tail
+        // + layer 0 the longest phase) and in the out_1 phase (layers 0-2: group A runs out_1 alone; layer 0 needs h0(q), which
+        // is not ready before the first barrier); all six beside the out_skip slices made group B take 1 050 cycles per layer phase
+        // against group A's 710
+        SWN_PHASE(0, true, 3, 3, x0) SWN_PHASE(1, true, -1, 0, x0) SWN_PHASE(2, true, -1, 0, x0) SWN_PHASE(3, true, -1, 0, x0)
+        SWN_PHASE(4, true, -1, 0, x0) SWN_PHASE(5, true, -1, 0, x0)
         // out_skip: the last slice and the reduction (group B); group A has nothing on this phase
         if constexpr (!grpA) {
             skip_consume_b<T, 5>(lds, wsl, sacc, tg);
@@ -505,8 +520,10 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
                 if (hp == 0) lds[T::o_skip + r + 64 * ps] = fmaxf(v + lds[T::o_bias + r + 64 * ps], 0.f);
             }
         }
-        SWN_BAR(6)
+        // the next step's deviate (classic mode: one lane of wave 1, a ~130-instruction log1p chain) where group A has no work:
+        // in the out_1 phase it made wave 1 the last of the group to reach the barrier
         noise_ahead(i + 1);
+        SWN_BAR(6)
         if constexpr (grpA) {
             // out_1, 128 x 128, LDS-resident, by group A alone: thread (hr, hp) rows hr and hr + 64 over inputs 16 mm + 4 hp .. + 3 - one
             // read of the inputs serves both rows.  Group B meanwhile forms three of the older-tap products of position q + 1 (with
@@ -533,14 +550,19 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
             older_b3<T, 0>(lds, wreg, q + 1, tg);
         }
         SWN_BAR(7)
-        if constexpr (!grpA) {
-            older_b2<T, 3>(lds, wreg, q + 1, tg);
-        }
-        if (tid < 64) {
+        if constexpr (grpA) {
             // out_2: NO <= 6 rows, 4 lanes per row, weights resident in LDS; then the Laplace head, evaluated uniformly by every
-            // lane of wave 0 so that the new sample is in registers for the next input layer (cswnv_shift1.py:368-391)
+            // lane of every wave of group A so that the new sample is in registers for the next input layer (cswnv_shift1.py:368-391)
             // (eight lanes per row, 16 inputs each, two chains: the serial 32-deep chain of the four-lane form was a third of this phase)
-            const int r = tid >> 3, pp = tid & 7;
+            // Only wave 0 stores the heads and the sample.
+            const int ln = tg & 63, r = ln >> 3, pp = ln & 7;
+            // the deviate (classic mode) and the forced sample are requested first: the deviate's LDS latency then hides under
+            // out_2, and the forced load is older than this step's stores - waiting for it must not wait for them (vmcnt counts
+            // stores too)
+            float tz = 0.f;                                // (an early read in the extended mode spilled four registers)
+            if constexpr (!EXT) tz = lds[T::o_tnz + (i & 1) * 8];
+            float fv = 0.f;
+            if (a.forced) fv = reinterpret_cast<const float*>(a.forced)[(size_t)b * a.n_steps + i];
             float acc = 0.f, acc1 = 0.f;
             if (r < T::NO) {
 #pragma unroll
@@ -555,9 +577,8 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
             acc = sum4(acc + acc1);
             acc += dpp_f<0x141>(acc);                          // row_half_mirror: the octet's sum
             if (r < T::NO) acc += lds[T::o_w2 + T::NO * S + r];
-            if (HEADS_ON && a.heads && pp == 0 && r < T::NO) a.heads[((size_t)b * a.n_steps + i) * T::NO + r] = acc;
             // the NO head outputs sit in lanes 0, 8, 16, ...: broadcast them through scalar registers (an LDS write, a wave barrier and
-            // a broadcast read stood here: ~150 cycles of the one wave the whole workgroup waits for)
+            // a broadcast read stood here: ~150 cycles of the chain the whole workgroup waits for)
             float o2[T::NO];
 #pragma unroll
             for (int k = 0; k < T::NO; ++k) o2[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, acc), 8 * k));
@@ -569,20 +590,23 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
                 float lpv = 0.f;
 #pragma unroll
                 for (int k = 0; k < T::LPC; ++k) lpv += o2[2 + T::LPC - 1 - k] * win[T::WN - T::LPC + k];
-                const float t = bsc * (EXT ? lds[T::o_tnz + ((i >> 6) & (T::NZB - 1)) * T::NZC + (i & (T::NZC - 1))]
-                                           : lds[T::o_tnz + (i & 1) * 8]);
+                const float t = bsc * (EXT ? lds[T::o_tnz + ((i >> 6) & (T::NZB - 1)) * T::NZC + (i & (T::NZC - 1))] : tz);
                 float sv = (T::LPC > 0) ? (lpv + mu) - t : mu - t;
                 sv = fminf(fmaxf(sv, -1.f), 1.f);
-                if (tid == 0) outp[0] = sv;
-                const float fd = a.forced ? reinterpret_cast<const float*>(a.forced)[(size_t)b * a.n_steps + i] : sv;
+                // the window is updated BEFORE the sample and the heads are stored: the input layer that follows would otherwise
+                // wait for the stores themselves (a use of the forced load behind a conditional store compiles to vmcnt(0))
+                float fd = a.forced ? fv : sv;
+                asm volatile("" : "+v"(fd));
 #pragma unroll
                 for (int k = 0; k + 1 < T::WN; ++k) win[k] = win[k + 1];
                 win[T::WN - 1] = fd;
+                if (tid == 0) outp[0] = sv;
             }
+            if (HEADS_ON && a.heads && wv == 0 && pp == 0 && r < T::NO) a.heads[((size_t)b * a.n_steps + i) * T::NO + r] = acc;
         }
         if (i + 1 < a.n_steps) input_gen(q + 1);
 #ifdef SWN_STAMP
-        { const unsigned long long tn = __builtin_amdgcn_s_memtime(); tw[8] += tn - tlast; tstep += tn - tbeg; }
+        if constexpr (grpA) tw[8] += __builtin_amdgcn_s_memtime() - tlast;
 #endif
     };
     if constexpr (EXT) {
@@ -597,6 +621,9 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
 #pragma unroll 1
         for (int i = 0; i < a.n_steps; ++i) gen_step(i);
     }
+#ifdef SWN_STAMP
+    { const unsigned long long tn = __builtin_amdgcn_s_memtime(); tw[0] += tn - tlast; tstep = tn - tbeg; }
+#endif
     if constexpr (STREAM) {    // the state the next chunk resumes from (all LDS writes of the last step are behind barriers)
         __syncthreads();
         float* so = a.sess + (size_t)b * T::sess_floats;

@@ -8,7 +8,8 @@ from shallow_wavenet_amd import config as C
 from shallow_wavenet_amd.runtime import HipNet
 from shallow_wavenet_amd.synth import synth_state_dict, synth_aux
 
-names = ["L0", "L1", "L2", "L3", "L4", "L5", "skip-fin", "out_1", "tail"]
+# eight barriers per step: phase 0 is the previous step's tail (out_2, head, sample, h0 in every wave of group A) + layer 0
+names = ["tail+L0", "L1", "L2", "L3", "L4", "L5", "skip-fin", "out_1"]
 cfg = C.bl6_laplace(1, 0)
 sd = synth_state_dict(cfg, seed=1, flavor="trained", identity_scale_in=True)
 net = HipNet.from_state_dict(cfg, sd, "cuda:0")
@@ -23,4 +24,5 @@ h = heads.flatten()[:20].cpu().numpy()
 print("step total (group A clock): %.0f ticks" % h[9])
 for k, n in enumerate(names):
     print("   %-10s A works %7.0f   B works %7.0f" % (n, h[k], h[10 + k]))
-print("   sum        A %7.0f   B %7.0f" % (h[:9].sum(), h[10:19].sum()))
+print("   (of tail+L0: the tail, group A %7.0f)" % h[8])
+print("   sum        A %7.0f   B %7.0f" % (h[:8].sum(), h[10:18].sum()))
