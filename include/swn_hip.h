@@ -195,6 +195,36 @@ int    swn_decode_chunk(const swn_net_desc* d, const float* packed_dev, const fl
                         int step0, int n_steps, int flags, const swn_decode_io* io, float* session_dev,
                         void* out_dev, float* heads_dev, int variant, void* stream);
 
+/* ---- decode pool: many independent streamed decodes advanced by one launch -----------------------------------------
+ * session_dev holds swn_decode_session_floats(d, capacity, variant) floats: `capacity` session slots, slot s laid out as
+ * utterance b = s of a streamed decode of batch `capacity`.  Entry e of the table is one workgroup: it runs steps
+ * [step0, step0 + n_steps) of the session in its slot over its own conditioning, exactly as swn_decode_chunk of that
+ * session alone (batch 1) would.  The io arrays are indexed by entry, with n_max = max_e n_steps:
+ *   out_dev  laplace (E, n_max*seg) fp32 | softmax (E, n_max) int32;  heads_dev (E, n_max, n_out);  io->noise_out_dev
+ *   (E, n_max, width);  io->seed_dev (E, seg) fp32 | (E) int32;  io->rng_utt_ids_dev (E) (else entry e draws as rng_utt0 + e).
+ *   Rows past an entry's own n_steps are not written.
+ * An entry of 0 steps without SWN_CHUNK_BEGIN leaves its slot as it was.  The table travels in the kernel arguments: the
+ * call neither copies nor synchronises on the host.  SWN_E_BADARG, checked before anything is launched: a null pointer,
+ * n_entries outside [1, SWN_DECODE_POOL_MAX_ENTRIES], a slot outside [0, capacity) or in two entries, BEGIN with
+ * step0 != 0, a negative step0 / n_steps, the conditioning bound, a non-zero reserved field or unknown flag, a non-NULL
+ * io->noise_dev or io->forced_dev (pools draw their noise on the device), a variant that does not resolve.
+ * SWN_E_UNSUPPORTED: the variant resolves to the stepped multi-launch decode (variant 0 on REF6-class nets; variant 1
+ * runs them on the generic kernel). */
+typedef struct swn_decode_pool_entry {
+    const float* cond_dev;   /* this session's cond rows (n_frames, N) as swn_frontend wrote them */
+    int32_t n_frames;        /* rows in cond_dev; (step0 + n_steps) * seg <= n_frames * U */
+    int32_t slot;            /* session slot in [0, capacity) */
+    int32_t step0;           /* absolute index of the entry's first step (0 with SWN_CHUNK_BEGIN) */
+    int32_t n_steps;         /* >= 0 */
+    int32_t flags;           /* SWN_CHUNK_BEGIN: run the prologue from io->seed_dev[e] into the slot */
+    int32_t reserved;        /* 0 */
+} swn_decode_pool_entry;
+#define SWN_DECODE_POOL_MAX_ENTRIES 64
+int    swn_decode_pool_chunk(const swn_net_desc* d, const float* packed_dev, int capacity,
+                             const swn_decode_pool_entry* entries_host, int n_entries,
+                             const swn_decode_io* io, float* session_dev,
+                             void* out_dev, float* heads_dev, int variant, void* stream);
+
 /* ---- teacher-forced stack  (CSWNV.forward cswnv_shift1.py:191-267,
  *                             DSWNV.forward dswnv.py:250-276) ----------------------------
  *   audio_dev   laplace: (B, 1, T - seg) fp32 samples ; softmax: (B, T - 1) int32 indices

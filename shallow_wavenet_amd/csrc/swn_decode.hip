@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
 #include "swn_noise.hpp"
+#include "swn_pool.hpp"
 
 namespace {
 
@@ -97,15 +98,43 @@ __device__ __forceinline__ void matvec16(const float* __restrict__ W, int NR, in
     }
 }
 
+// the arguments of a pool launch: a streamed chunk over the entries (batch = E, n_steps = n_max), then the entry table
+struct DecPoolArgs {
+    DecArgs c;
+    SwnPoolTable t;
+};
+static_assert(sizeof(DecPoolArgs) <= 4096, "kernel arguments are limited to 4 KB");
+template <bool POOL> struct GenericArgs { using type = DecArgs; };
+template <> struct GenericArgs<true> { using type = DecPoolArgs; };
+__device__ __forceinline__ const DecArgs& pool_or_launch(const DecArgs& launch, const DecArgs&) { return launch; }
+__device__ __forceinline__ const DecArgs& pool_or_launch(const DecPoolArgs&, const DecArgs& entry) { return entry; }
+__device__ __forceinline__ const DecArgs& launch_args(const DecArgs& launch) { return launch; }
+__device__ __forceinline__ const DecArgs& launch_args(const DecPoolArgs& launch) { return launch.c; }
+
 // STREAM: a chunk of a streamed decode (swn_decode_chunk): steps [step0, step0 + n_steps) with absolute positions and
 // generator counters, chunk-local out / heads / noise / forced rows; the rings stay in the session (a.state) and the sample
 // window is loaded from / saved to the session.  STREAM = false is the one-shot decode.
-template <int SEGT, int KIND, bool STREAM = false>
-__global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
+// POOL (with STREAM): the workgroup runs one entry of a decode pool (swn_decode_pool_chunk) - `a` already holds that entry as
+// a batch-1 chunk (swn_pool_entry_args), so b = 0; a BEGIN entry zeroes its own slot's rings here (the other slots of the
+// session buffer belong to other streams).
+template <int SEGT, int KIND, bool STREAM = false, bool POOL = false>
+__global__ __launch_bounds__(NT) void decode_generic_kernel(const typename GenericArgs<POOL>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const SwnGeom& g = a.g;
+    DecArgs pa;                                             // POOL: this workgroup's entry as a batch-1 chunk
+    if constexpr (POOL) {
+        pa = ka.c;
+        const SwnGeom& g = ka.c.g;
+        if (!swn_pool_entry_args(pa, ka.t, g.seg, KIND == SWN_KIND_SOFTMAX ? g.Q : g.seg, g.NO)) return;
+        const int slot = swn_pool_slot(ka.t);
+        pa.state += (size_t)slot * pa.state_stride;
+        pa.win += (size_t)slot * swn_round4((g.K - 1 > g.lpc ? g.K - 1 : g.lpc) + g.seg);
+    }
+    const DecArgs& a = pool_or_launch(ka, pa);
+    // the geometry and the ring plan are read where the launch put them: indexed by layer, a private copy would be scratch
+    const DecArgs& ar = launch_args(ka);
+    const SwnGeom& g = ar.g;
     const int tid = threadIdx.x;
-    const int b = blockIdx.x;
+    const int b = POOL ? 0 : blockIdx.x;
     const int H = g.H, Hp = g.Hp, H2 = 2 * g.H, K = g.K, L = g.L, seg = g.seg, S = g.S;
     const int WN = (K - 1 > g.lpc ? K - 1 : g.lpc) + seg;
     const float* __restrict__ P = a.packed;
@@ -122,6 +151,8 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
     const int lds_floats = (int)((tf + SEGT * SEGT) - reinterpret_cast<int*>(smem));
     for (int e = tid; e < lds_floats; e += NT) smem[e] = 0.f;
     int* ihist = reinterpret_cast<int*>(shist);
+    if (POOL && !a.resume)
+        for (int e = tid; e < a.state_stride; e += NT) a.state[e] = 0.f;
     __syncthreads();
     if (KIND == SWN_KIND_SOFTMAX) {
         // padding class Q/2 = encode_mu_law(0), dswnv.py:308; the newest slot is the caller's seed class
@@ -184,14 +215,14 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
                     }
                 }
             }
-            st[a.ring_off[0] + pmod(q, a.ring_len[0]) * Hp + o] = softsignf_(acc);
+            st[ar.ring_off[0] + pmod(q, ar.ring_len[0]) * Hp + o] = softsignf_(acc);
         }
         __syncthreads();
 
         // ---- stack
         for (int l = 0; l < L; ++l) {
-            const int dil = g.dil[l], R = a.ring_len[l];
-            const float* ring = st + a.ring_off[l];
+            const int dil = g.dil[l], R = ar.ring_len[l];
+            const float* ring = st + ar.ring_off[l];
             auto xf = [&](int j, int k) -> const float* {
                 return ring + (size_t)pmod(q0 + j - (K - 1 - k) * dil, R) * Hp;
             };
@@ -219,7 +250,7 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
                 const float c = tanhf(gxc * a_out[j * ld_a + H + o]);
                 const float hp = ring[(size_t)pmod(q, R) * Hp + o];
                 const float hn = (1.f - z) * c + z * hp;
-                if (l + 1 < L) st[a.ring_off[l + 1] + pmod(q, a.ring_len[l + 1]) * Hp + o] = hn;
+                if (l + 1 < L) st[ar.ring_off[l + 1] + pmod(q, ar.ring_len[l + 1]) * Hp + o] = hn;
                 if (j == np - 1) hcat[l * Hp + o] = hn;
             }
             __syncthreads();
@@ -309,6 +340,15 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const DecArgs a) {
     }
     if (STREAM)
         for (int e = tid; e < WN; e += NT) a.win[(size_t)b * WNR + e] = shist[e];
+}
+
+template <int SEGT>
+int launch_generic_pool(const DecPoolArgs& p, int n_entries, size_t lds, hipStream_t st) {
+    if (p.c.g.kind == SWN_KIND_LAPLACE)
+        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_LAPLACE, true, true>), dim3(n_entries), dim3(NT), lds, st, p);
+    else
+        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX, true, true>), dim3(n_entries), dim3(NT), lds, st, p);
+    return swn_launch_status("swn_decode_pool_chunk(generic)");
 }
 
 template <int SEGT, bool STREAM = false>
@@ -518,4 +558,71 @@ extern "C" int swn_decode_chunk(const swn_net_desc* d, const float* packed, cons
     a.state_stride = ring_plan(a.g, a.ring_off, a.ring_len);
     a.step0 = step0; a.resume = resume; a.win = session + (size_t)a.state_stride * batch;
     return generic_run(a, true, (hipStream_t)stream_);
+}
+
+// ---- decode pool ---------------------------------------------------------------------------------------------------
+// defined in swn_decode_bl6.hip / swn_decode_bl6w.hip: one pool launch of those kernels over the checked entry table
+extern "C" int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries,
+                                   int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
+                                   void* stream);
+extern "C" int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries,
+                                    int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
+                                    void* stream);
+
+extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed, int capacity,
+                                     const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                     float* session, void* out, float* heads, int variant, void* stream_) {
+    SwnGeom g;
+    int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (!packed || !entries || !io || !session) return SWN_E_BADARG;
+    if (capacity < 1 || n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
+    if (io->noise_dev || io->forced_dev) return SWN_E_BADARG;    // pools draw their noise on the device, no teacher forcing
+    SwnPoolTable t = {};
+    int n_max = 0;
+    bool work = false;
+    for (int e = 0; e < n_entries; ++e) {
+        const swn_decode_pool_entry& en = entries[e];
+        const bool begin = (en.flags & SWN_CHUNK_BEGIN) != 0;
+        if (!en.cond_dev || en.n_frames < 1 || en.slot < 0 || en.slot >= capacity || en.step0 < 0 || en.n_steps < 0 ||
+            (en.flags & ~SWN_CHUNK_BEGIN) || en.reserved != 0)
+            return SWN_E_BADARG;
+        if (begin && en.step0 != 0) return SWN_E_BADARG;
+        if (((long long)en.step0 + en.n_steps) * g.seg > (long long)en.n_frames * g.U) return SWN_E_BADARG;
+        for (int f = 0; f < e; ++f)
+            if (entries[f].slot == en.slot) return SWN_E_BADARG;   // two workgroups on one session
+        t.e[e] = en;
+        n_max = en.n_steps > n_max ? en.n_steps : n_max;
+        work = work || begin || en.n_steps > 0;
+    }
+    if (n_max > 0 && !out) return SWN_E_BADARG;
+    const int k = resolve_kernel(d, capacity, variant);
+    if (k == KSEL_STEPPED || variant == 3) return SWN_E_UNSUPPORTED;   // one launch per phase for all utterances at one step
+    if (k < 0) return SWN_E_BADARG;
+    if (!work) return SWN_OK;                              // every slot stays as it is
+    SwnNoise nz;
+    nz.ptr = nullptr; nz.dump = io->noise_out_dev;
+    nz.key0 = (uint32_t)(io->rng_seed & 0xffffffffu); nz.key1 = (uint32_t)(io->rng_seed >> 32); nz.utt0 = io->rng_utt0; nz.ids = io->rng_utt_ids_dev;
+    (void)hipGetLastError();
+    if (k == KSEL_BL6W)
+        return swn_decode_bl6w_pool(d, packed, &t, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
+    if (k == KSEL_BL6)
+        return swn_decode_bl6_pool(d, packed, &t, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
+    DecPoolArgs p;
+    DecArgs& a = p.c;
+    a.g = g;
+    swn_make_layout(&a.g, &a.y);
+    a.packed = packed; a.cond = nullptr; a.nz = nz; a.forced = nullptr; a.seed = io->seed_dev; a.state = session;
+    a.out = out; a.heads = heads; a.B = n_entries; a.Tf = 0; a.n_steps = n_max;
+    a.state_stride = ring_plan(a.g, a.ring_off, a.ring_len);
+    a.step0 = 0; a.resume = 0; a.win = session + (size_t)a.state_stride * capacity;
+    p.t = t;
+    const size_t lds = generic_lds(g);
+    hipStream_t st = (hipStream_t)stream_;
+    switch (generic_segt(g)) {
+        case 1: return launch_generic_pool<1>(p, n_entries, lds, st);
+        case 2: return launch_generic_pool<2>(p, n_entries, lds, st);
+        case 5: return launch_generic_pool<5>(p, n_entries, lds, st);
+        default: return launch_generic_pool<10>(p, n_entries, lds, st);
+    }
 }

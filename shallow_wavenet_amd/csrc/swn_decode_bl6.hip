@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
 #include "swn_noise.hpp"
+#include "swn_pool.hpp"
 
 namespace {
 
@@ -335,17 +336,38 @@ __device__ __forceinline__ void tiled_matvec(__amdgpu_buffer_rsrc_t wt, const fl
     }
 }
 
+// the arguments of a pool launch: a streamed chunk over the entries (batch = E, n_steps = n_max), then the entry table
+struct B6PoolArgs {
+    B6Args c;
+    SwnPoolTable t;
+};
+static_assert(sizeof(B6PoolArgs) <= 4096, "kernel arguments are limited to 4 KB");
+template <bool POOL> struct B6ArgsOf { using type = B6Args; };
+template <> struct B6ArgsOf<true> { using type = B6PoolArgs; };
+__device__ __forceinline__ const B6Args& pool_or_launch(const B6Args& launch, const B6Args&) { return launch; }
+__device__ __forceinline__ const B6Args& pool_or_launch(const B6PoolArgs&, const B6Args& entry) { return entry; }
+
 // EXT = false: the classic instantiation (host-drawn noise stream, zero seed) - the code the round-1 measurements
 // belong to, kept instruction for instruction; EXT = true adds the in-kernel generator / noise dump / seed waveform.
 // STREAM (with EXT only): one chunk of a streamed decode (swn_decode_chunk) - steps [step0, step0 + n_steps) at absolute
 // positions and generator counters, chunk-local out / heads / noise / forced rows; when resuming, the rings and the sample
 // window come from the session instead of the prologue, and they go back to it at the end.  The step itself is the same code.
-template <class T, bool STREAM = false>
-__global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6Args a) {
+// POOL (with STREAM): one entry of a decode pool (swn_decode_pool_chunk); `a` holds the workgroup's entry as a batch-1 chunk
+// (swn_pool_entry_args), b = 0.
+template <class T, bool STREAM = false, bool POOL = false>
+__global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    B6Args pa;                                            // POOL: this workgroup's entry as a batch-1 chunk
+    if constexpr (POOL) {
+        static_assert(STREAM && T::EXT, "pools run the streamed extended mode");
+        pa = ka.c;
+        if (!swn_pool_entry_args(pa, ka.t, T::SEG, T::KIND == SWN_KIND_SOFTMAX ? T::Q : T::SEG, T::NO)) return;
+        pa.sess += (size_t)swn_pool_slot(ka.t) * T::sess_floats;
+    }
+    const B6Args& a = pool_or_launch(ka, pa);
     constexpr int SEG = T::SEG, S = T::S, KIND = T::KIND;
     constexpr bool EXT = T::EXT;
-    const int tid = threadIdx.x, b = blockIdx.x;
+    const int tid = threadIdx.x, b = POOL ? 0 : blockIdx.x;
     const float* __restrict__ P = a.P;
     const int U = a.U;
     static_assert(!STREAM || EXT, "streamed chunks run the extended mode");
@@ -847,6 +869,32 @@ int with_tr(const SwnGeom& g, F&& f) {
 }
 
 }  // namespace
+
+// one pool launch (swn_decode_pool_chunk checked the entries): one workgroup per entry, sessions [capacity][sess_floats]
+extern "C" int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries,
+                                   int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
+                                   void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    B6PoolArgs p;
+    B6Args& a = p.c;
+    swn_make_layout(&g, &a.y);
+    a.P = packed; a.cond = nullptr; a.noise = nullptr; a.nz = *nz; a.forced = nullptr; a.seed = seed; a.out = out; a.heads = heads;
+    a.B = n_entries; a.Tf = 0; a.n_steps = n_max; a.U = g.U; a.N = g.N;
+    a.step0 = 0; a.resume = 0; a.sess = sess;
+    p.t = *t;
+    hipStream_t st = (hipStream_t)stream_;
+    return with_tr(g, [&](auto tr) {
+        using T = typename decltype(tr)::Ext;
+        auto kern = decode_bl6_kernel<T, true, true>;
+        if (T::lds_bytes > 64 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)T::lds_bytes) != hipSuccess)
+            return (int)SWN_E_LAUNCH;
+        hipLaunchKernelGGL(kern, dim3(n_entries), dim3(NT), T::lds_bytes, st, p);
+        return swn_launch_status("swn_decode_pool_chunk(bl6)");
+    });
+}
 
 // streamed decode (swn_decode_chunk): per-utterance session floats of the symmetric kernel, 0 = not a BL6-class net
 extern "C" size_t swn_decode_bl6_session_floats(const swn_net_desc* d) {

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
 #include "swn_noise.hpp"
+#include "swn_pool.hpp"
 
 namespace {
 
@@ -275,12 +276,14 @@ __device__ __forceinline__ void skip_consume_b(const float* lds, const float4 (&
 // window and the older-tap products of the first position (group B formed them during the previous chunk's last step)
 // are loaded from the session - carried over bit for bit, not recomputed - and the prologue is skipped; the next input
 // layer is then formed by the same input_gen as in the one-shot loop.  At the end all of it goes back to the session.
-template <class T, bool GA, bool STREAM>
+// POOL (with STREAM): one entry of a decode pool (swn_decode_pool_chunk); `a` already holds it as a batch-1 chunk, b = 0.  The
+// noise staging and the frame boundaries follow the entry's own step0 and n_steps, so entries of one launch sit at any phase.
+template <class T, bool GA, bool STREAM, bool POOL = false>
 __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
     constexpr bool EXT = T::EXT;
     static_assert(!STREAM || EXT, "streamed chunks run the extended mode");
     constexpr bool grpA = GA;
-    const int tid = threadIdx.x, b = blockIdx.x;
+    const int tid = threadIdx.x, b = POOL ? 0 : blockIdx.x;
     __builtin_assume(GA ? tid < NG : tid >= NG);              // group B compiles none of group A's side jobs (head, noise, input layer)
     // (a raised s_setprio for group A - the chain first at the SIMD's issue arbitration - measured no gain: 283.6 / 278.8 / 282.9 k
     //  samples/s at priority 0 / 1 / 3)
@@ -652,6 +655,33 @@ __global__ __launch_bounds__(NT) void decode_bl6w_kernel(const W6Args a) {
     else decode_body<T, false, STREAM>(a, lds);
 }
 
+// the arguments of a pool launch: a streamed chunk over the entries (batch = E, n_steps = n_max), then the entry table
+struct W6PoolArgs {
+    W6Args c;
+    SwnPoolTable t;
+};
+static_assert(sizeof(W6PoolArgs) <= 4096, "kernel arguments are limited to 4 KB");
+
+template <class T>
+__global__ __launch_bounds__(NT) void decode_bl6w_pool_kernel(const W6PoolArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    static_assert(T::EXT, "pools run the extended mode");
+    W6Args a = p.c;
+    if (!swn_pool_entry_args(a, p.t, 1, 1, T::NO)) return;
+    a.sess += (size_t)swn_pool_slot(p.t) * T::sess_floats;
+    if (threadIdx.x < NG) decode_body<T, true, true, true>(a, lds);   // wave-uniform
+    else decode_body<T, false, true, true>(a, lds);
+}
+
+template <class T>
+int launch_pool(const W6PoolArgs& p, int n_entries, hipStream_t st) {
+    auto kern = decode_bl6w_pool_kernel<T>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::lds_bytes) != hipSuccess)
+        return SWN_E_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(n_entries), dim3(NT), T::lds_bytes, st, p);
+    return swn_launch_status("swn_decode_pool_chunk(bl6w)");
+}
+
 template <class T, bool STREAM = false>
 int launch_mode(const W6Args& a, hipStream_t st) {
     static_assert(T::lds_bytes <= 160 * 1024, "LDS budget");
@@ -717,4 +747,23 @@ extern "C" int swn_decode_bl6w_chunk(const swn_net_desc* d, const float* packed,
     (void)hipGetLastError();
     if (g.lpc == 0) return launch_mode<Tw<0, true>, true>(a, st);
     return launch_mode<Tw<4, true>, true>(a, st);
+}
+
+// one pool launch (swn_decode_pool_chunk checked the entries): one workgroup per entry, sessions [capacity][sess_floats]
+extern "C" int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries,
+                                    int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
+                                    void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (!bl6w_applies(g)) return SWN_E_UNSUPPORTED;
+    W6PoolArgs p;
+    W6Args& a = p.c;
+    swn_make_layout(&g, &a.y);
+    a.P = packed; a.cond = nullptr; a.noise = nullptr; a.nz = *nz; a.forced = nullptr; a.seed = seed; a.out = out; a.heads = heads;
+    a.B = n_entries; a.Tf = 0; a.n_steps = n_max; a.U = g.U; a.N = g.N;
+    a.step0 = 0; a.resume = 0; a.sess = sess;
+    p.t = *t;
+    hipStream_t st = (hipStream_t)stream_;
+    if (g.lpc == 0) return launch_pool<Tw<0, true>>(p, n_entries, st);
+    return launch_pool<Tw<4, true>>(p, n_entries, st);
 }

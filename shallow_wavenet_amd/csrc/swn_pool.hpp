@@ -1,0 +1,42 @@
+// Decode pool (swn_decode_pool_chunk, include/swn_hip.h): one launch advances many independent streamed decodes, one
+// workgroup per entry of a table that travels in the kernel arguments.  Each workgroup turns the launch-wide arguments of a
+// streamed chunk into those of its own entry - one session of batch 1 - and then runs the STREAM code path unchanged.
+#pragma once
+#include "swn_geom.hpp"
+#include "swn_noise.hpp"
+
+// the entry table of a pool launch (64 x 32 B of kernel arguments)
+struct SwnPoolTable {
+    swn_decode_pool_entry e[SWN_DECODE_POOL_MAX_ENTRIES];
+};
+static_assert(sizeof(swn_decode_pool_entry) == 32, "swn_decode_pool_entry is 32 bytes (include/swn_hip.h)");
+
+// Rewrites `a` - the arguments of a streamed chunk over the E entries (io rows indexed by entry, n_steps = n_max) - into those
+// of entry blockIdx.x as a batch-1 chunk: conditioning, frame count, step0, resume and step count come from the entry, and
+// every io pointer moves to the entry's row, so that the body runs with utterance index b = 0.  The caller moves its session
+// pointer to swn_pool_slot().  The entry index is uniform over the workgroup, so its fields are scalar loads and stay in SGPRs.
+// false: the entry has nothing to do (0 steps, no BEGIN) - the workgroup returns before its first barrier.
+//   seg    out elements (fp32 samples | int32 classes) and seed elements per step / entry
+//   width  noise values per step;  n_out  head outputs per step
+template <class A>
+__device__ __forceinline__ bool swn_pool_entry_args(A& a, const SwnPoolTable& t, int seg, int width, int n_out) {
+    const int e = blockIdx.x;
+    const swn_decode_pool_entry& en = t.e[e];
+    const bool begin = (en.flags & SWN_CHUNK_BEGIN) != 0;
+    if (en.n_steps == 0 && !begin) return false;
+    const size_t n_max = (size_t)a.n_steps;
+    a.cond = en.cond_dev;
+    a.Tf = en.n_frames;
+    a.step0 = en.step0;
+    a.resume = begin ? 0 : 1;
+    a.n_steps = en.n_steps;
+    a.out = reinterpret_cast<char*>(a.out) + (size_t)e * n_max * seg * 4;
+    if (a.heads) a.heads += (size_t)e * n_max * n_out;
+    if (a.seed) a.seed = reinterpret_cast<const char*>(a.seed) + (size_t)e * seg * 4;
+    if (a.nz.dump) a.nz.dump += (size_t)e * n_max * width;
+    if (a.nz.ids) a.nz.ids += e;
+    else a.nz.utt0 += (uint32_t)e;
+    return true;
+}
+
+__device__ __forceinline__ int swn_pool_slot(const SwnPoolTable& t) { return t.e[blockIdx.x].slot; }

@@ -164,6 +164,8 @@ def gpu_decode(kind: str, args, config, feat_list: Sequence[str], device, packed
             global_index = list(range(len(feat_list)))
         model.set_packed_engine(HipNet(cfg, D.broadcast_packed(cfg, packed, device, src=packed_src_rank), device))
         string_path = getattr(config, "string_path", "/feat_org_lf0")
+        if getattr(args, "pool_slots", 0) > 0:
+            return pool_decode(kind, args, model, feat_list, global_index, string_path, device)
         t_total, n_max, n_tot = 0.0, 0, 0
         for ids, batch_h, n_samples_list, utt_index in decode_batches(feat_list, args.batch_size, string_path,
                                                                       config.upsampling_factor, global_index):
@@ -212,6 +214,39 @@ def stream_generate(model, seed, aux, n_samples_list, frames_per_push: int):
     return [samples[b, :n] for b, n in zip(range(B), n_samples_list)]
 
 
+def pool_decode(kind: str, args, model, feat_list: Sequence[str], global_index: Sequence[int], string_path: str, device):
+    """--pool_slots N: the utterances go through a decode pool of N slots (shallow_wavenet_amd.streaming.DecodePool), admitted
+    in list order as slots free up; each runs its own n_samples / seg steps over its own features, so its WAV is that of the
+    default path with --batch_size 1 (device-drawn noise, utterance index = position in the unsorted list)."""
+    cfg = model._cfg
+    pool = model.open_pool(args.pool_slots)
+    pending = list(range(len(feat_list)))
+    live = {}                                   # session -> (utterance id, n_samples, out pieces)
+    t0, n_tot = time.time(), 0
+    while pending or live:
+        while pending and len(live) < args.pool_slots:
+            i = pending.pop(0)
+            h = read_feature(feat_list[i], string_path)
+            s = pool.open(utt_id=int(global_index[i]))
+            s.finish(torch.from_numpy(np.ascontiguousarray(h.T[None])).to(device, torch.float32))
+            live[s] = (os.path.splitext(os.path.basename(feat_list[i]))[0], h.shape[0] * int(cfg.U), [])
+        for s, r in pool.step().items():
+            live[s][2].append(r[0])
+        for s in [s for s in live if s.done]:
+            feat_id, n, pieces = live.pop(s)
+            pool.close(s)
+            samples = torch.cat(pieces, dim=1)[0, :n].cpu().numpy()
+            wav = samples if kind == "laplace" else softmax_mod.decode_mu_law(samples.astype(np.int64), cfg.n_quantize)
+            write_wav_pcm16(os.path.join(args.outdir, feat_id + ".wav"), np.clip(wav, -1, 1), args.fs)
+            logging.info("wrote %s.wav in %s." % (feat_id, args.outdir))
+            n_tot += n
+    t_total = time.time() - t0
+    if n_tot:
+        logging.info("pool of %d slots: %ld samples in %.3f s [%.3f kHz/s]" % (args.pool_slots, n_tot, t_total,
+                                                                              n_tot / (1000 * t_total)))
+    return n_tot, t_total
+
+
 def make_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser()
     p.add_argument("--feats", required=True, type=str, help="list or directory of aux feat files")
@@ -235,6 +270,9 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--stream_frames", default=0, type=int,
                    help="not a reference flag: > 0 decodes each batch as a stream, pushing this many feature frames at a "
                         "time (needs device-drawn noise; the WAVs are those of the one-shot decode)")
+    p.add_argument("--pool_slots", default=0, type=int,
+                   help="not a reference flag: > 0 decodes the utterances through a decode pool of this many slots, each "
+                        "over its own features and steps (needs device-drawn noise; the WAVs are those of --batch_size 1)")
     p.add_argument("--plan_only", action="store_true",
                    help="not a reference flag: stop after listing, sharding and the parameter broadcast and write "
                         "<outdir>/decode.<rank>.plan.json (needs no GPU: what the CPU tests of the fan-out drive)")
@@ -308,6 +346,10 @@ def main(kind: str, argv=None) -> int:
     args = make_parser().parse_args(argv)
     if args.stream_frames > 0 and (args.noise_source or ("host" if kind == "laplace" else "device")) != "device":
         print("--stream_frames needs device-drawn noise (--noise_source device): the host stream is drawn for the whole run "
+              "up front", file=sys.stderr)
+        return 2
+    if args.pool_slots > 0 and (args.noise_source or ("host" if kind == "laplace" else "device")) != "device":
+        print("--pool_slots needs device-drawn noise (--noise_source device): the host stream is drawn for the whole run "
               "up front", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.n_gpus > 1:

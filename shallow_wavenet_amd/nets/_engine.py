@@ -145,6 +145,17 @@ class EngineMixin:
                             rng_utt0=int(getattr(self, "noise_utterance_offset", 0)),
                             utt_ids=getattr(self, "noise_utterance_ids", None))
 
+    def open_pool(self, capacity: int, variant: int = 0):
+        """a decode pool of `capacity` session slots on the module's current engine (shallow_wavenet_amd.streaming.DecodePool):
+        independent utterances open, receive features and end at their own pace, and one launch per tick advances all of
+        them.  The noise key follows open_stream: `noise_rng_seed` when the caller pinned one, else one fresh key per pool.
+        A session opened with utt_id = i draws what utterance i of batch_fast_generate with noise_source = "device" draws."""
+        from .. import noise as _noise
+        from ..streaming import DecodePool
+        key = getattr(self, "noise_rng_seed", None)
+        return DecodePool(self._engine(), capacity, variant=variant,
+                          rng_seed=_noise.draw_rng_seed() if key is None else int(key))
+
     def set_packed_engine(self, net: HipNet) -> None:
         """install an engine whose packed buffer arrived by RCCL broadcast (dist.py)."""
         self.__dict__["_engine_cache"] = (self._engine_key(), net)

@@ -17,6 +17,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
                          want_heads, want_noise, utt_ids?)         -> (out, heads, noise_used)
     torch.ops.swn.decode_chunk(packed, cond, session, noise?, forced?, seed?, desc, step0, n_steps, begin, variant,
                                rng_seed, rng_utt0, want_heads, want_noise, utt_ids?)  -> (out, heads, noise_used)
+    torch.ops.swn.decode_pool_chunk(packed, session, conds, slots, step0s, n_steps, begins, seeds?, utt_ids, desc, capacity,
+                                    variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.stack_forward(packed, cond, audio, desc, want_hidden) -> (raw, work, hidden)
     torch.ops.swn.stack_forward_bf16(packed, wbf16, cond, audio, desc)  -> (raw, work)
     torch.ops.swn.pack_bf16(packed, desc)                          -> wbf16
@@ -280,6 +282,74 @@ def _(packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, v
             packed.new_empty((B, n_steps, width) if want_noise else (0,)))
 
 
+# ------------------------------------------------------------------------------------------ decode pool
+def decode_pool_chunk_impl(packed: torch.Tensor, session: torch.Tensor, conds: List[torch.Tensor], slots: List[int],
+                           step0s: List[int], n_steps: List[int], begins: List[bool], seeds: Optional[torch.Tensor],
+                           utt_ids: List[int], desc: List[int], capacity: int, variant: int, rng_seed: int,
+                           want_heads: bool, want_noise: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """one launch of a decode pool (swn_decode_pool_chunk): entry e advances the session in slot slots[e] of `session`
+    (swn_decode_session_floats(capacity) fp32, updated in place) by steps [step0s[e], step0s[e] + n_steps[e]) over its own
+    conditioning conds[e] (n_frames, N); begins[e] runs the prologue from seeds[e] (laplace (E, seg) fp32 | softmax (E,)
+    classes; None = zeros / Q/2).  Noise is drawn on the device, keyed by rng_seed and utt_ids[e].  out / heads / used noise
+    are dense (E, n_max * seg) | (E, n_max, n_out) | (E, n_max, width), n_max = max(n_steps); rows past an entry's own steps
+    are not written."""
+    L = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(packed, "the packed parameters")
+    dev = packed.device
+    soft, seg, _, _, n_out, _ = _geom(d)
+    E = len(conds)
+    if not (len(slots) == len(step0s) == len(n_steps) == len(begins) == len(utt_ids) == E):
+        raise RuntimeError("decode_pool_chunk: conds, slots, step0s, n_steps, begins and utt_ids must have one entry each")
+    if not 1 <= E <= _lib.DECODE_POOL_MAX_ENTRIES:
+        raise RuntimeError(f"decode_pool_chunk: {E} entries, a launch takes 1 .. {_lib.DECODE_POOL_MAX_ENTRIES}")
+    width = d.n_quantize if soft else seg
+    if session.device != dev or session.dtype != torch.float32 or not session.is_contiguous():
+        raise RuntimeError("session must be a contiguous fp32 tensor on the device of the packed parameters")
+    if session.numel() < L.swn_decode_session_floats(ctypes.byref(d), int(capacity), int(variant)):
+        raise RuntimeError("session buffer too small for this (net, capacity, variant)")
+    table = (_lib.DecodePoolEntry * E)()
+    for e, c in enumerate(conds):
+        if c.device != dev or c.dtype != torch.float32 or not c.is_contiguous() or c.dim() != 2:
+            raise RuntimeError("every cond buffer must be a contiguous (n_frames, N) fp32 tensor on the device")
+        table[e] = _lib.DecodePoolEntry(cond_dev=c.data_ptr(), n_frames=int(c.shape[0]), slot=int(slots[e]),
+                                        step0=int(step0s[e]), n_steps=int(n_steps[e]),
+                                        flags=_lib.CHUNK_BEGIN if begins[e] else 0, reserved=0)
+    if seeds is not None:
+        seeds = seeds.to(dev, torch.int32 if soft else torch.float32).contiguous()
+        if seeds.numel() != E * seg:
+            raise RuntimeError(f"seeds have {seeds.numel()} elements, expected {E * seg}")
+    ids = torch.tensor([int(u) & 0xFFFFFFFF for u in utt_ids], dtype=torch.int64).to(torch.int32).to(dev)
+    n_max = max(int(n) for n in n_steps)
+    out = torch.empty((E, n_max * seg), dtype=torch.int32 if soft else torch.float32, device=dev)
+    heads = torch.empty((E, n_max, n_out) if want_heads else (0,), dtype=torch.float32, device=dev)
+    used = torch.empty((E, n_max, width) if want_noise else (0,), dtype=torch.float32, device=dev)
+    io = _lib.DecodeIO(noise_dev=None, forced_dev=None, seed_dev=_ptr(seeds),
+                       noise_out_dev=_ptr(used if want_noise else None),
+                       rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=0, reserved=0, rng_utt_ids_dev=_ptr(ids))
+    with _on(dev):
+        _lib.check(L.swn_decode_pool_chunk(ctypes.byref(d), _ptr(packed), int(capacity), table, E, ctypes.byref(io),
+                                           _ptr(session), _ptr(out if n_max > 0 else None),
+                                           _ptr(heads if want_heads else None), int(variant), _stream(dev)),
+                   "decode_pool_chunk")
+    return out, heads, used
+
+
+decode_pool_chunk = custom_op("swn::decode_pool_chunk", mutates_args=("session",))(decode_pool_chunk_impl)
+
+
+@decode_pool_chunk.register_fake
+def _(packed, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
+      want_heads, want_noise):
+    d = _desc(desc)
+    soft, seg, _, _, n_out, _ = _geom(d)
+    E, n_max = len(conds), max(int(n) for n in n_steps)
+    width = d.n_quantize if soft else seg
+    return (packed.new_empty((E, n_max * seg), dtype=torch.int32 if soft else torch.float32),
+            packed.new_empty((E, n_max, n_out) if want_heads else (0,)),
+            packed.new_empty((E, n_max, width) if want_noise else (0,)))
+
+
 # ------------------------------------------------------------------------------------------ teacher-forced stack
 def _tp(d, Tf: int) -> Tuple[int, int]:
     soft, seg, *_ = _geom(d)
@@ -508,5 +578,5 @@ def backward_bf16_supported(desc: List[int], batch: int, n_frames: int) -> bool:
     return _lib.lib().swn_backward_bf16_work_floats(ctypes.byref(_desc(desc)), batch, n_frames) > 0
 
 
-OP_NAMES = ("pack_params", "frontend", "decode", "decode_chunk", "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
+OP_NAMES = ("pack_params", "frontend", "decode", "decode_chunk", "decode_pool_chunk", "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16")

@@ -16,7 +16,7 @@ waits for the device.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -216,3 +216,165 @@ class DecodeStream:
         if self.want_noise:
             return out, heads, used
         return out, heads
+
+
+# ---------------------------------------------------------------------------------------------------------- decode pool
+def plan_tick(sessions: Sequence[Tuple[object, int, int]], max_steps: Optional[int] = None,
+              limit: int = _lib.DECODE_POOL_MAX_ENTRIES) -> List[List[Tuple[object, int, int]]]:
+    """the launches of one pool tick.  sessions: (key, steps_ready, steps_done) of every open session, in admission order.
+    Each session with ready steps runs min(ready - done, max_steps) of them; the entries (key, step0, n_steps) are split
+    into launches of at most `limit`.  Pure host arithmetic: nothing here touches a device."""
+    if max_steps is not None and int(max_steps) < 1:
+        raise ValueError(f"max_steps must be a positive integer or None, not {max_steps!r}")
+    entries = []
+    for key, ready, done in sessions:
+        n = int(ready) - int(done)
+        if max_steps is not None:
+            n = min(n, int(max_steps))
+        if n > 0:
+            entries.append((key, int(done), n))
+    return [entries[i:i + limit] for i in range(0, len(entries), limit)]
+
+
+class PoolSession:
+    """one utterance of a DecodePool.  push / finish hand it features (they only finalise conditioning: the pool's ticks
+    generate); steps_ready / steps_done / finished tell where it stands.  Made by DecodePool.open."""
+
+    def __init__(self, pool: "DecodePool", slot: int, utt_id: int, seed: Optional[torch.Tensor]):
+        self._pool = pool
+        self.slot, self.utt_id = slot, utt_id
+        # the conditioning of a batch-1 DecodeStream: the pool reads its _cond, steps_ready and steps_done
+        self._stream = DecodeStream(pool.net, 1, variant=pool.variant, seed=seed, rng_seed=pool.rng_seed, utt_ids=[utt_id])
+        self._seed = self._stream._seed
+        self.closed = False
+
+    def _check(self) -> None:
+        if self.closed:
+            raise RuntimeError(f"pool session {self.utt_id} (slot {self.slot}) is closed")
+
+    def push(self, aux_chunk: torch.Tensor) -> None:
+        """append (1, n_aux, f) fp32 features."""
+        self._check()
+        self._stream.push(aux_chunk, generate=False)
+
+    def finish(self, aux_tail: Optional[torch.Tensor] = None) -> None:
+        """the features end here (optionally with a last piece)."""
+        self._check()
+        self._stream.finish(aux_tail, generate=False)
+
+    @property
+    def steps_ready(self) -> int:
+        return self._stream.steps_ready
+
+    @property
+    def steps_done(self) -> int:
+        return self._stream.steps_done
+
+    @property
+    def finished(self) -> bool:
+        """no more features will come."""
+        return self._stream.finished
+
+    @property
+    def done(self) -> bool:
+        """finished and every step generated."""
+        return self._stream.finished and self.steps_done == self.steps_ready
+
+
+class DecodePool:
+    """many independent streamed decodes advanced together: one kernel launch per tick (per 64 active sessions) instead of
+    one per session (swn_decode_pool_chunk).  Sessions arrive, receive features at their own rate and end at their own
+    length; each one's output is bit-identical to HipNet.decode of that utterance alone (batch 1, the same variant, rng_seed,
+    utterance id and seed waveform), whatever else shares its launches.
+
+    net        a HipNet;  capacity  session slots (sessions open at once)
+    variant    decode kernel as HipNet.decode; the stepped multi-launch decode (variant 3, and what 0 picks for REF6-class
+               nets) cannot serve a pool - variant 1 runs those nets on the generic kernel
+    rng_seed   the device generator's key (pools draw their noise on the device)
+    want_heads / want_noise   also return the raw out_2 rows / the noise used
+
+        s = pool.open(seed=None, utt_id=None)   # a free slot; utt_id defaults to the admission counter
+        s.push(aux_piece); s.finish(aux_tail)  # (1, n_aux, f) features
+        results = pool.step(max_steps=None)    # one tick -> {session: (out, heads[, noise])}, views of the launch outputs
+        pool.close(s)                          # frees the slot, finished or not
+    """
+
+    def __init__(self, net, capacity: int, *, variant: int = 0, rng_seed: int = 0, want_heads: bool = False,
+                 want_noise: bool = False):
+        if not isinstance(capacity, int) or capacity < 1:
+            raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
+        self.net, self.cfg, self.capacity = net, net.cfg, capacity
+        self.soft = self.cfg.kind == "softmax"
+        self.seg = 1 if self.soft else int(self.cfg.seg)
+        desc = _ops._desc(net.dlist)
+        lib = _lib.lib()
+        resolved = lib.swn_decode_resolve_variant(desc, capacity, int(variant))
+        if resolved < 0:
+            raise ValueError(f"decode variant {variant} does not resolve for this net ({lib.swn_strerror(resolved).decode()})")
+        if resolved == 3:
+            raise ValueError(f"decode variant {variant} resolves to the stepped multi-launch decode, which cannot serve a "
+                             "pool; variant=1 runs this net on the generic kernel")
+        self.variant, self.resolved_variant = int(variant), resolved
+        self.rng_seed = int(rng_seed) & 0x7FFFFFFFFFFFFFFF
+        self.want_heads, self.want_noise = bool(want_heads), bool(want_noise)
+        self._session = torch.empty(int(lib.swn_decode_session_floats(desc, capacity, int(variant))), dtype=torch.float32,
+                                    device=net.device)
+        self._free = list(range(capacity))          # free slots, lowest first
+        self._open: dict = {}                       # slot -> PoolSession, in admission order
+        self.admitted = 0
+
+    @property
+    def sessions(self) -> List[PoolSession]:
+        return list(self._open.values())
+
+    def open(self, seed: Optional[torch.Tensor] = None, utt_id: Optional[int] = None) -> PoolSession:
+        """claim a free slot for a new utterance (its generator index is utt_id, else the admission count)."""
+        if not self._free:
+            raise RuntimeError(f"the pool is full: all {self.capacity} slots hold open sessions")
+        uid = self.admitted if utt_id is None else int(utt_id)
+        slot = self._free[0]
+        s = PoolSession(self, slot, uid, seed)
+        self._free.pop(0)
+        self._open[slot] = s
+        self.admitted += 1
+        return s
+
+    def close(self, s: PoolSession) -> None:
+        """free the session's slot (finished or not); a new session may begin in it at the next tick."""
+        if s.closed or self._open.get(s.slot) is not s:
+            raise RuntimeError("this session is not open in this pool")
+        s.closed = True
+        del self._open[s.slot]
+        self._free.append(s.slot)
+        self._free.sort()
+
+    def step(self, max_steps: Optional[int] = None) -> dict:
+        """one tick: every open session with ready steps advances by min(ready, max_steps) of them, in launches of at most
+        64 sessions.  Returns {session: (out, heads) or (out, heads, noise)} for the sessions that ran - out laplace
+        (1, n * seg) fp32 | softmax (1, n) int32, heads (1, n, n_out) or None, noise (1, n, width) - views of the dense
+        launch outputs.  Nothing here waits for the device."""
+        launches = plan_tick([(s, s.steps_ready, s.steps_done) for s in self._open.values()], max_steps)
+        results = {}
+        for entries in launches:
+            sess = [e[0] for e in entries]
+            begins = [not s._stream._begun for s in sess]
+            seeds = None
+            if any(b and s._seed is not None for s, b in zip(sess, begins)):
+                seeds = torch.stack([s._seed.reshape(-1).to(torch.int32 if self.soft else torch.float32).cpu()
+                                     if s._seed is not None else self._default_seed() for s in sess])
+            out, heads, used = _O.decode_pool_chunk(
+                self.net.packed, self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
+                [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
+                self.net.dlist, self.capacity, self.variant, self.rng_seed, self.want_heads, self.want_noise)
+            for e, (s, step0, n) in enumerate(entries):
+                s._stream.steps_done = step0 + n
+                s._stream._begun = True
+                o = out[e:e + 1, :n * self.seg]
+                h = heads[e:e + 1, :n] if self.want_heads else None
+                results[s] = (o, h, used[e:e + 1, :n]) if self.want_noise else (o, h)
+        return results
+
+    def _default_seed(self) -> torch.Tensor:
+        if self.soft:
+            return torch.full((1,), int(self.cfg.n_quantize) // 2, dtype=torch.int32)
+        return torch.zeros(self.seg, dtype=torch.float32)
