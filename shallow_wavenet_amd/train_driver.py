@@ -98,14 +98,30 @@ def chunk_plan(n_frames: int, receptive_field: int, batch_size: int, seg: int, u
     return out
 
 
-def make_adam(params, lr: float):
+def make_adam(params, lr: float, fused: Optional[bool] = None):
     """torch.optim.Adam as the reference constructs it (train_cswnv...py:456: default betas / eps, no weight decay), in torch's single-
-    launch `fused` form when every parameter lives on a GPU: the same update rule in one kernel instead of four multi-tensor passes
-    over the 51 parameter tensors (BL6 step 1.49 -> 1.36 ms; the optimizer's state_dict is interchangeable with the default form)."""
+    launch `fused` form when every parameter lives on a GPU (`fused=None`; True / False force the choice): the same update rule in one
+    kernel instead of four multi-tensor passes over the 51 parameter tensors.  The optimizer's state_dict is interchangeable with the
+    default form.
+
+    The modules' kernels read a packed copy of the parameters that is refreshed when a parameter's (data_ptr, _version) changes
+    (nets/_engine.py).  torch's fused step writes the parameters without bumping their version counters, so a step-post hook bumps
+    them (torch.autograd.graph.increment_version, ~4 us of host time): without it every later forward would run on the weights
+    from before the first step.  Writes that bypass the version counter elsewhere - a caller's own fused optimizer, in-place writes
+    through `.data` - are not seen either: call torch.autograd.graph.increment_version(model.parameters()) after them."""
     params = list(params)
     flat = [q for p in params for q in (p["params"] if isinstance(p, dict) else [p])]
-    fused = len(flat) > 0 and all(q.is_cuda and q.is_floating_point() for q in flat)
-    return torch.optim.Adam(params, lr=lr, **({"fused": True} if fused else {}))
+    if fused is None:
+        fused = len(flat) > 0 and all(q.is_cuda and q.is_floating_point() for q in flat)
+    opt = torch.optim.Adam(params, lr=lr, **({"fused": True} if fused else {}))
+    if fused:
+        opt.register_step_post_hook(_bump_versions)
+    return opt
+
+
+def _bump_versions(optimizer, args, kwargs) -> None:
+    """step-post hook of make_adam's fused optimizer: mark every parameter it updated as modified in place."""
+    torch.autograd.graph.increment_version([p for g in optimizer.param_groups for p in g["params"]])
 
 
 def read_wav(path: str) -> np.ndarray:

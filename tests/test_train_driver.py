@@ -109,3 +109,30 @@ def test_softmax_driver_chunk_plan_and_flags():
     bh, bx, trg = S.slice_chunk(x, h, 17, 340, 14, 280)
     assert bh.shape == (1, 3, 17) and bx.shape == (1, 339) and trg.shape == (339,)
     assert int(bx[0, 0]) == 280 and int(trg[0]) == 281 and int(trg[-1]) == 280 + 339
+
+
+@pytest.mark.parametrize("driver", ["laplace", "softmax"])
+def test_fused_adam_step_is_seen_by_the_engine_cache(driver):
+    """the modules' kernels read a packed copy of the parameters that is refreshed only when model._engine_key()
+    (data_ptr, _version of every parameter) changes.  torch's fused Adam writes the parameters without bumping _version,
+    so make_adam must bump it itself, or every forward after the first step runs on the weights from before training.
+    make_adam picks the fused form only on a GPU; `fused=True` forces it here on CPU parameters.  Both drivers share
+    make_adam; each is driven through its own optimizer parameter list."""
+    from shallow_wavenet_amd import config as C
+    from shallow_wavenet_amd import train_softmax_driver as S
+    from shallow_wavenet_amd.nets import dswnv as md
+    if driver == "laplace":
+        mod, m = T, mc.CSWNV(**C.bl6_laplace(1, 0).ctor_kwargs())
+    else:
+        mod, m = S, md.DSWNV(**C.tiny("softmax").ctor_kwargs())
+    params = mod.optimizer_parameters(m)
+    for fused in (True, False):
+        opt = mod.make_adam(params, 1e-3, fused=fused)
+        assert bool(opt.defaults["fused"]) is fused
+        for p in params:
+            p.grad = torch.full_like(p, 0.5)
+        before = m._engine_key()
+        w = params[0].detach().clone()
+        opt.step()
+        assert not torch.equal(params[0].detach(), w)          # the step did move the weights
+        assert m._engine_key() != before, f"fused={fused}: an optimizer step left the engine cache key unchanged"
