@@ -225,6 +225,41 @@ int    swn_decode_pool_chunk(const swn_net_desc* d, const float* packed_dev, int
                              const swn_decode_io* io, float* session_dev,
                              void* out_dev, float* heads_dev, int variant, void* stream);
 
+/* ---- stepped decode pool: the decode pool of the stepped multi-launch decode (variant 3: REF6-class nets) -----------
+ * Every launch of the stepped chain (input layer, L gated layers, skip / out_1 [/ out_2] mat-vecs, tail) serves all
+ * entries of the table, each at its own iteration, so a tick costs about what one utterance's chunk costs while up to 64
+ * sessions share it.  Entries count ITERATIONS: iterations 0 .. n_pro - 1 are the prologue positions
+ * (n_pro = swn_decode_stepped_prologue_iterations()), iteration n_pro + i is generation step i; a new session's prologue
+ * can therefore be spread over several ticks.  Entry e runs iterations [it0, it0 + n_it) of the session in its slot over its
+ * own conditioning, exactly as swn_decode_chunk of that session alone (batch 1, variant 3) would; its generation steps of
+ * the call go to rows [0, n_gen_e) of its out / heads / noise row (n_max = max_e n_gen_e, layouts of swn_decode_pool_chunk).
+ *   session_dev  swn_decode_session_floats(d, capacity, 3) + SWN_DECODE_STEPPED_POOL_TABLE_FLOATS floats: slot s is laid
+ *                out as utterance s of the stepped state; the tail holds the device copy of each call's entry table
+ *                (written by the call's first launch, read by the others: the table travels once per call).
+ * A BEGIN entry's slot is zeroed and seeded by a kernel; no other slot is touched.  An entry of 0 iterations without BEGIN
+ * leaves its slot as it was.  SWN_E_BADARG, checked before anything is launched: a null pointer, n_entries outside
+ * [1, SWN_DECODE_POOL_MAX_ENTRIES], a slot outside [0, capacity) or in two entries, BEGIN with it0 != 0, it0 == 0 without
+ * BEGIN and n_it > 0, a negative it0 / n_it, a last generation step beyond the conditioning bound
+ * (step + 1) * seg <= n_frames * U, an unknown flag or non-zero reserved field, a non-NULL io->noise_dev or io->forced_dev.
+ * SWN_E_UNSUPPORTED: the stepped chain does not run this net at this capacity (swn_decode_resolve_variant(d, capacity, 3)
+ * fails). */
+typedef struct swn_decode_stepped_pool_entry {
+    const float* cond_dev;   /* this session's cond rows (n_frames, N) as swn_frontend wrote them */
+    int32_t n_frames;
+    int32_t slot;            /* [0, capacity) */
+    int32_t it0;             /* absolute iteration of the entry's first: prologue positions 0 .. n_pro - 1, then generation
+                                step i at n_pro + i */
+    int32_t n_it;            /* >= 0 */
+    int32_t flags;           /* SWN_CHUNK_BEGIN: zero this slot, seed it from io->seed_dev[e]; it0 must be 0 */
+    int32_t reserved;        /* 0 */
+} swn_decode_stepped_pool_entry;
+#define SWN_DECODE_STEPPED_POOL_TABLE_FLOATS 512
+int    swn_decode_stepped_prologue_iterations(const swn_net_desc* d);
+int    swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float* packed_dev, int capacity,
+                                     const swn_decode_stepped_pool_entry* entries_host, int n_entries,
+                                     const swn_decode_io* io, float* session_dev, void* out_dev, float* heads_dev,
+                                     void* stream);
+
 /* ---- teacher-forced stack  (CSWNV.forward cswnv_shift1.py:191-267,
  *                             DSWNV.forward dswnv.py:250-276) ----------------------------
  *   audio_dev   laplace: (B, 1, T - seg) fp32 samples ; softmax: (B, T - 1) int32 indices

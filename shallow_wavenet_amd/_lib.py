@@ -42,8 +42,15 @@ class DecodePoolEntry(ctypes.Structure):
                 ("n_steps", c_int32), ("flags", c_int32), ("reserved", c_int32)]
 
 
+class DecodeSteppedPoolEntry(ctypes.Structure):
+    """mirror of `swn_decode_stepped_pool_entry` (include/swn_hip.h): one session's share of a stepped pool call."""
+    _fields_ = [("cond_dev", c_void_p), ("n_frames", c_int32), ("slot", c_int32), ("it0", c_int32),
+                ("n_it", c_int32), ("flags", c_int32), ("reserved", c_int32)]
+
+
 ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
+DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
 CHUNK_BEGIN = 1                                # SWN_CHUNK_BEGIN (include/swn_hip.h): first chunk of a streamed decode
 PRECISION_FP32, PRECISION_BF16 = 0, 1          # SWN_PRECISION_* (include/swn_hip.h)
 
@@ -84,6 +91,9 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "swn_decode_pool_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodePoolEntry), c_int, POINTER(DecodeIO),
                                       c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "swn_decode_stepped_prologue_iterations": (c_int, [POINTER(NetDesc)]),
+    "swn_decode_pool_stepped_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodeSteppedPoolEntry), c_int,
+                                              POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_void_p]),
     "swn_forward_work_floats": (c_size_t, [POINTER(NetDesc), c_int, c_int]),
     "swn_forward": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                             c_void_p, c_void_p, c_void_p]),

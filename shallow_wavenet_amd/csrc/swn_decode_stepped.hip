@@ -15,10 +15,13 @@
 // State (history rings, hcat, skip, out_1, sample window) lives in the caller's scratch buffer; the math
 // and the ring layout are those of the generic persistent kernel (swn_decode.hip).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "swn_geom.hpp"
 #include "swn_noise.hpp"
 
 namespace {
+
+constexpr size_t ST_OOB_FLOATS = 0x20000000u;   // 2 GiB of floats: first offset a buffer load cannot take
 
 struct StArgs {
     SwnGeom g;
@@ -31,6 +34,33 @@ struct StArgs {
     int o2_by_rowvec;                                           // out_2 was computed by a rowvec launch into o_o2 (wide heads)
     int step0;                                                  // streamed chunk (STREAM tails): absolute index of its step 0
 };
+
+// ---- stepped decode pool (swn_decode_pool_stepped_chunk): the launch chain serves the entries of a tick, each at its own
+//      iteration.  Utterance index b of a launch is the entry's place in the tick's table (sorted by n_it, descending, so
+//      that the entries still active at tick-local iteration j are a prefix); the launch argument is j, the entry works at
+//      its absolute iteration it0 + j while j < n_it.  The table is written to the device once per tick (by
+//      step_pool_setup_kernel, from its kernel arguments) and read by every later launch of the tick.
+struct StPoolEnt {
+    const float* cond;                         // the entry's cond rows (Tf, N)
+    int Tf, slot, it0, n_it;
+    int row;                                   // the entry's row of out / heads / noise / seed / utterance ids
+    int g0;                                    // absolute iteration of its first generation step here: max(it0, n_pro)
+};
+static_assert(sizeof(StPoolEnt) == 32 && SWN_DECODE_POOL_MAX_ENTRIES * sizeof(StPoolEnt) <= SWN_DECODE_STEPPED_POOL_TABLE_FLOATS * 4,
+              "the device copy of a pool table fits SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)");
+struct StPoolTable {
+    StPoolEnt e[SWN_DECODE_POOL_MAX_ENTRIES];
+};
+static_assert(sizeof(StArgs) + sizeof(StPoolTable) + 16 <= 4096, "step_pool_setup_kernel's arguments fit 4 KB");
+struct StPoolArgs : StArgs {
+    const StPoolEnt* tab;                      // the device copy of the tick's table
+};
+template <bool POOL> using StA = typename std::conditional<POOL, StPoolArgs, StArgs>::type;
+
+// 64-bit float offset -> buffer byte offset, ST_OOB when it does not fit the 31-bit range (never wraps)
+__device__ __forceinline__ unsigned st_off(size_t floats) {
+    return floats < (size_t)(ST_OOB_FLOATS) ? (unsigned)(floats * 4) : 0x80000000u;
+}
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ int pmod(int r, int m) { int t = r % m; return t < 0 ? t + m : t; }
@@ -127,10 +157,21 @@ __device__ __forceinline__ void input_layer(const StArgs& a, float* st, const in
     }
 }
 
-template <int KIND>
-__global__ __launch_bounds__(256) void step_in_kernel(const StArgs a, const int it) {
+// POOL: entry blockIdx.x, when it is in its prologue or at the first generation iteration of its range (later steps get their
+// input layer from the tail of the step before)
+template <int KIND, bool POOL = false>
+__global__ __launch_bounds__(256) void step_in_kernel(const StA<POOL> a, const int itj) {
     __shared__ float lwin[32];
-    float* st = a.state + (size_t)blockIdx.x * a.stride;
+    int it = itj;
+    float* st;
+    if constexpr (POOL) {
+        const StPoolEnt& en = a.tab[blockIdx.x];
+        it = en.it0 + itj;
+        if (itj >= en.n_it || !(it < a.n_pro || it == en.g0)) return;
+        st = a.state + (size_t)en.slot * a.stride;
+    } else {
+        st = a.state + (size_t)blockIdx.x * a.stride;
+    }
     if ((int)threadIdx.x < a.WN) lwin[threadIdx.x] = st[a.o_hist + threadIdx.x];
     __syncthreads();
     input_layer<KIND>(a, st, it, threadIdx.x, 256, lwin);
@@ -139,12 +180,23 @@ __global__ __launch_bounds__(256) void step_in_kernel(const StArgs a, const int 
 // ---- step_layer: ONE wave per channel pair (gate row + candidate row), weights kept in registers.
 //      Kernel boundaries invalidate the per-XCD L2s, so every launch re-fetches its weight rows from the
 //      Infinity Cache at ~30 GB/s per CU: H workgroups of 64 lanes keep each CU's share at ~10 KB.
-template <int NI, int KIND, int BT>   // NI = ceil(K*Hp / 256): float4 pieces per lane and row; BT = utterances per tile
-__global__ __launch_bounds__(64) void step_layer_kernel(const StArgs a, const int l, const int it) {
+// POOL (BT = 1): entry blockIdx.y at its own iteration, its state block in its slot, its own conditioning
+template <int NI, int KIND, int BT, bool POOL = false>   // NI = ceil(K*Hp / 256): float4 pieces per lane and row; BT = utterances per tile
+__global__ __launch_bounds__(64) void step_layer_kernel(const StA<POOL> a, const int l, const int itj) {
+    static_assert(!POOL || BT == 1, "pool form: one entry per workgroup");
     const SwnGeom& g = a.g;
     const int lane = threadIdx.x;
     const int o = blockIdx.x;
     const int H = g.H, Hp = g.Hp, K = g.K, H2 = 2 * g.H, seg = g.seg, KH = K * Hp;
+    int it = itj;
+    size_t pbase = 0;                                          // POOL: the entry's state block, in floats
+    const float* pcond = nullptr;
+    int pTf = 0;
+    if constexpr (POOL) {
+        const StPoolEnt& en = a.tab[blockIdx.y];
+        if (itj >= en.n_it) return;
+        it = en.it0 + itj; pbase = (size_t)en.slot * a.stride; pcond = en.cond; pTf = en.Tf;
+    }
     const bool live = o < H;
     const float* P = a.P;
     const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
@@ -176,23 +228,26 @@ __global__ __launch_bounds__(64) void step_layer_kernel(const StArgs a, const in
             const int tap = ic / Hp, i = ic - tap * Hp;
             const size_t xo = a.ring_off[l] + (size_t)pmod(q - (K - 1 - tap) * dil, R) * Hp + i;
 #pragma unroll
-            for (int u = 0; u < BT; ++u)
-                xv[pc][u] = st_ld4(rS, (idx < KH && u < nb) ? (unsigned)(((size_t)(b0 + u) * a.stride + xo) * 4) : ST_OOB);
+            for (int u = 0; u < BT; ++u) {
+                if constexpr (POOL) xv[pc][u] = st_ld4(rS, idx < KH ? st_off(pbase + xo) : ST_OOB);
+                else xv[pc][u] = st_ld4(rS, (idx < KH && u < nb) ? (unsigned)(((size_t)(b0 + u) * a.stride + xo) * 4) : ST_OOB);
+            }
         }
         // epilogue operands: issued behind the activation loads (this block is an exec-masked branch that waits for
         // its own loads; placed first it would hold the activation loads back by a round trip)
         float gz = 0.f, gc = 0.f, bdz = 0.f, bdc = 0.f, hp = 0.f;
         if (lane < nb && live) {
             const int b = b0 + lane;
-            const float* st = a.state + (size_t)b * a.stride;
+            const float* st = POOL ? a.state + pbase : a.state + (size_t)b * a.stride;
             gz = P[a.y.bx + (size_t)l * H2 + o]; gc = P[a.y.bx + (size_t)l * H2 + H + o];
             bdz = P[a.y.bd + (size_t)l * H2 + o]; bdc = P[a.y.bd + (size_t)l * H2 + H + o];
             hp = st[a.ring_off[l] + (size_t)pmod(q, R) * Hp + o];
-            const float* condb = a.cond + (size_t)b * a.Tf * g.N;
+            const int Tf = POOL ? pTf : a.Tf;
+            const float* condb = POOL ? pcond : a.cond + (size_t)b * a.Tf * g.N;
             for (int s = 0; s < seg; ++s) {
                 int tt = q + s - g.rf; tt = tt < 0 ? 0 : tt;
                 int f = tt / g.U; const int jj = tt - f * g.U;
-                f = f < a.Tf ? f : a.Tf - 1;
+                f = f < Tf ? f : Tf - 1;
                 const float w = P[a.y.wup + jj];
                 const float* cr = condb + (size_t)f * g.N + (size_t)(l * seg + s) * H2;
                 gz = fmaf(w, cr[o], gz); gc = fmaf(w, cr[H + o], gc);
@@ -224,7 +279,7 @@ __global__ __launch_bounds__(64) void step_layer_kernel(const StArgs a, const in
             }
         }
         if (lane < nb && live) {
-            float* st = a.state + (size_t)(b0 + lane) * a.stride;
+            float* st = POOL ? a.state + pbase : a.state + (size_t)(b0 + lane) * a.stride;
             const float z = sigm(gz * (myz + bdz));
             const float c = tanhf(gc * (myc + bdc));
             const float hn = (1.f - z) * c + z * hp;
@@ -242,14 +297,117 @@ __global__ __launch_bounds__(64) void step_layer_kernel(const StArgs a, const in
 //      wave forms its pair's two sums for the eight utterances out of LDS - the same lane-by-lane sums as the kernels above
 //      (bit-identical results).  Lane 8 u of a wave finishes utterance u.
 constexpr int ST_TU = 8;                                       // utterances (= waves) of a tile
-template <int NI, int KIND>
-__global__ __launch_bounds__(64 * ST_TU) void step_layer_tile_kernel(const StArgs a, const int l, const int it) {
+// POOL: the eight entries of a tile may be at different iterations.  Wave w stages entry 8 by + w at its own position, lane
+// octet u finishes entry 8 by + u at its own; the position loop (barriers inside) runs to the largest count of positions of
+// the tile (1 in the prologue, seg in generation), and an entry past its own count, or past its n_it, stays idle.
+template <int NI, int KIND, bool POOL = false>
+__global__ __launch_bounds__(64 * ST_TU) void step_layer_tile_kernel(const StA<POOL> a, const int l, const int itj) {
     extern __shared__ __attribute__((aligned(16))) float xs[];  // [ST_TU][NI * 256]
     const SwnGeom& g = a.g;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int o = blockIdx.x * ST_TU + w;
     const int H = g.H, Hp = g.Hp, K = g.K, H2 = 2 * g.H, seg = g.seg, KH = K * Hp;
+    if constexpr (POOL) {
+        const int b0 = blockIdx.y * ST_TU;
+        const int nb = a.B - b0 < ST_TU ? a.B - b0 : ST_TU;
+        // the staging entry of this wave (uniform) and the finishing entry of this lane's octet
+        const int kw = b0 + (w < nb ? w : 0), ku = b0 + ((lane >> 3) < nb ? (lane >> 3) : 0);
+        const StPoolEnt& ew = a.tab[kw];
+        const StPoolEnt& eu = a.tab[ku];
+        const bool onw = w < nb && itj < ew.n_it, onu = (lane >> 3) < nb && itj < eu.n_it;
+        const Iter rw = iter_of(a, ew.it0 + itj), ru = iter_of(a, eu.it0 + itj);
+        // positions of the tile: the largest count over its active entries (every lane holds its octet's entry)
+        int npm = onu ? ru.np : 0;
+        npm = max(npm, __shfl_xor(npm, 8, 64)); npm = max(npm, __shfl_xor(npm, 16, 64)); npm = max(npm, __shfl_xor(npm, 32, 64));
+        npm = __builtin_amdgcn_readfirstlane(npm);
+        if (npm == 0) return;                                  // uniform over the workgroup: no entry of the tile is active
+        const bool live = o < H;
+        const float* P = a.P;
+        const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
+        float4 wz[NI], wc[NI];
+        {
+            const size_t rz = a.y.wd + ((size_t)l * H2 + (live ? o : 0)) * KH, rc = rz + (size_t)H * KH;
+#pragma unroll
+            for (int pc = 0; pc < NI; ++pc) {
+                const int idx = pc * 256 + lane * 4;
+                const bool ok = live && idx < KH;
+                wz[pc] = st_ld4(rP, ok ? (unsigned)((rz + idx) * 4) : ST_OOB);
+                wc[pc] = st_ld4(rP, ok ? (unsigned)((rc + idx) * 4) : ST_OOB);
+            }
+        }
+        const int dil = g.dil[l], R = a.ring_len[l];
+        const size_t basew = (size_t)ew.slot * a.stride, baseu = (size_t)eu.slot * a.stride;
+        for (int j = 0; j < npm; ++j) {
+            const int qw = rw.q0 + j, qu = ru.q0 + j;
+            {
+                float4 xv[NI];
+                const bool stage = onw && j < rw.np;
+#pragma unroll
+                for (int pc = 0; pc < NI; ++pc) {
+                    const int idx = pc * 256 + lane * 4;
+                    const int ic = idx < KH ? idx : 0;
+                    const int tap = ic / Hp, i = ic - tap * Hp;
+                    const size_t xo = a.ring_off[l] + (size_t)pmod(qw - (K - 1 - tap) * dil, R) * Hp + i;
+                    xv[pc] = st_ld4(rS, (idx < KH && stage) ? st_off(basew + xo) : ST_OOB);
+                }
+                if (j > 0) __syncthreads();
+#pragma unroll
+                for (int pc = 0; pc < NI; ++pc) *reinterpret_cast<float4*>(xs + (w * NI + pc) * 256 + lane * 4) = xv[pc];
+            }
+            float gz = 0.f, gc = 0.f, bdz = 0.f, bdc = 0.f, hp = 0.f;
+            const bool fin = (lane & 7) == 0 && onu && j < ru.np && live;
+            if (fin) {
+                const float* st = a.state + baseu;
+                gz = P[a.y.bx + (size_t)l * H2 + o]; gc = P[a.y.bx + (size_t)l * H2 + H + o];
+                bdz = P[a.y.bd + (size_t)l * H2 + o]; bdc = P[a.y.bd + (size_t)l * H2 + H + o];
+                hp = st[a.ring_off[l] + (size_t)pmod(qu, R) * Hp + o];
+                const float* condb = eu.cond;
+                const int Tf = eu.Tf;
+                for (int s = 0; s < seg; ++s) {
+                    int tt = qu + s - g.rf; tt = tt < 0 ? 0 : tt;
+                    int f = tt / g.U; const int jj = tt - f * g.U;
+                    f = f < Tf ? f : Tf - 1;
+                    const float wv = P[a.y.wup + jj];
+                    const float* cr = condb + (size_t)f * g.N + (size_t)(l * seg + s) * H2;
+                    gz = fmaf(wv, cr[o], gz); gc = fmaf(wv, cr[H + o], gc);
+                }
+                if (KIND == SWN_KIND_SOFTMAX && g.audio_in) {
+                    const int* ihist = reinterpret_cast<const int*>(st + a.o_hist);
+                    const int qe = ru.gen ? g.rf + ru.i : g.rf;
+                    const int idx = ru.gen ? ihist[qu - qe + a.WN - 1] : g.Q / 2;
+                    const float* wa = P + a.y.wxa + ((size_t)l * g.Q + idx) * H2;
+                    gz += wa[o]; gc += wa[H + o];
+                }
+            }
+            __syncthreads();
+            float azv[ST_TU], acv[ST_TU];
+#pragma unroll
+            for (int u = 0; u < ST_TU; ++u) {
+                float az = 0.f, ac = 0.f;
+#pragma unroll
+                for (int pc = 0; pc < NI; ++pc) {
+                    const float4 x = *reinterpret_cast<const float4*>(xs + (u * NI + pc) * 256 + lane * 4);
+                    az = fmaf(wz[pc].x, x.x, az); az = fmaf(wz[pc].y, x.y, az);
+                    az = fmaf(wz[pc].z, x.z, az); az = fmaf(wz[pc].w, x.w, az);
+                    ac = fmaf(wc[pc].x, x.x, ac); ac = fmaf(wc[pc].y, x.y, ac);
+                    ac = fmaf(wc[pc].z, x.z, ac); ac = fmaf(wc[pc].w, x.w, ac);
+                }
+                azv[u] = az; acv[u] = ac;
+            }
+            const float myz = sum64x8(azv, lane), myc = sum64x8(acv, lane);
+            if (fin) {
+                float* st = a.state + baseu;
+                const float z = sigm(gz * (myz + bdz));
+                const float c = tanhf(gc * (myc + bdc));
+                const float hn = (1.f - z) * c + z * hp;
+                if (l + 1 < g.L) st[a.ring_off[l + 1] + pmod(qu, a.ring_len[l + 1]) * Hp + o] = hn;
+                if (j == ru.np - 1) st[a.o_hcat + l * Hp + o] = hn;
+            }
+        }
+        return;
+    }
+    const int it = itj;
     const bool live = o < H;
     const float* P = a.P;
     const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
@@ -383,6 +541,39 @@ __global__ __launch_bounds__(64) void rowvec_kernel(const StArgs a, size_t w_off
     }
 }
 
+// pool form of rowvec_kernel<1>: entry blockIdx.y, when it is generating at tick-local iteration `itj`
+__global__ __launch_bounds__(64) void rowvec_pool_kernel(const StPoolArgs a, size_t w_off, int ldw, size_t b_off, int rows,
+                                                         int ni, int x_off, int y_off, int relu, int itj) {
+    const int lane = threadIdx.x, row = blockIdx.x;
+    const StPoolEnt& en = a.tab[blockIdx.y];
+    if (itj >= en.n_it || en.it0 + itj < en.g0) return;
+    const __amdgpu_buffer_rsrc_t rP = st_rsrc(a.P), rS = st_rsrc(a.state);
+    const size_t wr = w_off + (size_t)row * ldw, base = (size_t)en.slot * a.stride;
+    const float bias = a.P[b_off + row];
+    float acc = 0.f;
+    constexpr int RV = 5;
+    for (int i0 = 0; i0 < ni; i0 += 256 * RV) {
+        float4 wv[RV], xv[RV];
+#pragma unroll
+        for (int pc = 0; pc < RV; ++pc) {
+            const int idx = i0 + pc * 256 + lane * 4;
+            const bool ok = idx < ni;
+            wv[pc] = st_ld4(rP, ok ? (unsigned)((wr + idx) * 4) : ST_OOB);
+            xv[pc] = st_ld4(rS, ok ? st_off(base + x_off + idx) : ST_OOB);
+        }
+#pragma unroll
+        for (int pc = 0; pc < RV; ++pc) {
+            acc = fmaf(wv[pc].x, xv[pc].x, acc); acc = fmaf(wv[pc].y, xv[pc].y, acc);
+            acc = fmaf(wv[pc].z, xv[pc].z, acc); acc = fmaf(wv[pc].w, xv[pc].w, acc);
+        }
+    }
+    const float sv = sum64(acc);
+    if (lane == 0) {
+        const float v = sv + bias;
+        a.state[base + y_off + row] = relu ? fmaxf(v, 0.f) : v;
+    }
+}
+
 // the same for the 1x1 layers: 8 rows x 8 utterances per workgroup, the utterances' input vectors staged in LDS
 template <int RV>                                              // host: ni <= 256 RV
 __global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StArgs a, size_t w_off, int ldw, size_t b_off, int rows,
@@ -431,17 +622,83 @@ __global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StArgs a,
     }
 }
 
+// pool form of rowvec_tile_kernel: wave w stages entry 8 by + w, lane octet u finishes entry 8 by + u, each only when that
+// entry is generating at tick-local iteration `itj`
+template <int RV>
+__global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_pool_kernel(const StPoolArgs a, size_t w_off, int ldw, size_t b_off,
+                                                                      int rows, int ni, int x_off, int y_off, int relu, int itj) {
+    extern __shared__ __attribute__((aligned(16))) float xs[];  // [ST_TU][RV * 256]
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int row = blockIdx.x * ST_TU + w;
+    const bool live = row < rows;
+    const int b0 = blockIdx.y * ST_TU;
+    const int nb = a.B - b0 < ST_TU ? a.B - b0 : ST_TU;
+    const int ut = lane >> 3;
+    const StPoolEnt& ew = a.tab[b0 + (w < nb ? w : 0)];
+    const StPoolEnt& eu = a.tab[b0 + (ut < nb ? ut : 0)];
+    const bool genw = w < nb && itj < ew.n_it && ew.it0 + itj >= ew.g0;
+    const bool genu = ut < nb && itj < eu.n_it && eu.it0 + itj >= eu.g0;
+    const __amdgpu_buffer_rsrc_t rP = st_rsrc(a.P), rS = st_rsrc(a.state);
+    const size_t wr = w_off + (size_t)(live ? row : 0) * ldw;
+    const float bias = live ? a.P[b_off + row] : 0.f;
+    const size_t basew = (size_t)ew.slot * a.stride;
+    float4 wv[RV];
+    {
+        float4 xv[RV];
+#pragma unroll
+        for (int pc = 0; pc < RV; ++pc) {
+            const int idx = pc * 256 + lane * 4;
+            const bool ok = idx < ni;
+            wv[pc] = st_ld4(rP, (ok && live) ? (unsigned)((wr + idx) * 4) : ST_OOB);
+            xv[pc] = st_ld4(rS, (ok && genw) ? st_off(basew + x_off + idx) : ST_OOB);
+        }
+#pragma unroll
+        for (int pc = 0; pc < RV; ++pc) *reinterpret_cast<float4*>(xs + (w * RV + pc) * 256 + lane * 4) = xv[pc];
+    }
+    __syncthreads();
+    float accv[ST_TU];
+#pragma unroll
+    for (int u = 0; u < ST_TU; ++u) {
+        float acc = 0.f;
+#pragma unroll
+        for (int pc = 0; pc < RV; ++pc) {
+            const float4 x = *reinterpret_cast<const float4*>(xs + (u * RV + pc) * 256 + lane * 4);
+            acc = fmaf(wv[pc].x, x.x, acc); acc = fmaf(wv[pc].y, x.y, acc);
+            acc = fmaf(wv[pc].z, x.z, acc); acc = fmaf(wv[pc].w, x.w, acc);
+        }
+        accv[u] = acc;
+    }
+    const float mine = sum64x8(accv, lane);
+    if ((lane & 7) == 0 && genu && live) {
+        const float v = mine + bias;
+        a.state[(size_t)eu.slot * a.stride + y_off + row] = relu ? fmaxf(v, 0.f) : v;
+    }
+}
+
 // ---- step_tail: out_2, sampling, history update, then the input layer of the next step ---------------
 // STREAM: a chunk of a streamed decode (swn_decode_chunk): `it` stays the absolute iteration (positions, generator counters),
 // out / heads / noise / forced rows are chunk-local (step ia - step0).  The other launches of the chain need no such form.
-template <int KIND, bool STREAM = false>
-__global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const int it) {
+// POOL (with STREAM): entry blockIdx.x when it is generating at tick-local iteration `itj`; its io rows are those of its row
+// (n_steps = the launch's n_max), its state block is in its slot, and the next input layer is formed while the entry's range
+// goes on.
+template <int KIND, bool STREAM = false, bool POOL = false>
+__global__ __launch_bounds__(256) void step_tail_kernel(const StA<POOL> a, const int itj) {
+    static_assert(!POOL || STREAM, "the pool form is a streamed chunk per entry");
     __shared__ float o2v[4096 + 16];
     __shared__ float lwin[32];                 // the updated sample window, for the fused next input layer
     const SwnGeom& g = a.g;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
-    float* st = a.state + (size_t)b * a.stride;
-    const int ia = it - a.n_pro, i = STREAM ? ia - a.step0 : ia, seg = g.seg, WN = a.WN;
+    int b = blockIdx.x, it = itj, step0 = a.step0, it_end = 0;
+    size_t sb = (size_t)b;                     // state block
+    if constexpr (POOL) {
+        const StPoolEnt& en = a.tab[blockIdx.x];
+        it = en.it0 + itj;
+        if (itj >= en.n_it || it < en.g0) return;
+        b = en.row; sb = (size_t)en.slot; step0 = en.g0 - a.n_pro; it_end = en.it0 + en.n_it;
+    }
+    const int tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
+    float* st = a.state + sb * a.stride;
+    const int ia = it - a.n_pro, i = STREAM ? ia - step0 : ia, seg = g.seg, WN = a.WN;
     // out_2.  Wide heads (softmax: Q rows) arrive from a rowvec launch - one wave per row over the chip, like skip and
     // out_1 - in the state block; narrow heads (Laplace: <= 2 seg + lpc rows) are computed here:
     // 8 rows per pass, 32 lanes per row; branch-free loads (a row past NO / an input past O1p reads zeros)
@@ -449,7 +706,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const in
         for (int e = tid; e < g.NO; e += 256) o2v[e] = st[a.o_o2 + e];
     } else {
         const __amdgpu_buffer_rsrc_t rP = st_rsrc(a.P), rS = st_rsrc(a.state);
-        const size_t xb = (size_t)b * a.stride + a.o_o1;
+        const size_t xb = sb * a.stride + a.o_o1;
         for (int r0 = 0; r0 < g.NO; r0 += 8) {
             const int row = r0 + grp;
             const bool rok = row < g.NO;
@@ -461,7 +718,8 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const in
                     const int idx = i0 + u * 128 + lane * 4;
                     const bool ok = rok && idx < g.O1p;
                     wv[u] = st_ld4(rP, ok ? (unsigned)((a.y.w2 + (size_t)row * g.O1p + idx) * 4) : ST_OOB);
-                    xv[u] = st_ld4(rS, ok ? (unsigned)((xb + idx) * 4) : ST_OOB);
+                    if constexpr (POOL) xv[u] = st_ld4(rS, ok ? st_off(xb + idx) : ST_OOB);
+                    else xv[u] = st_ld4(rS, ok ? (unsigned)((xb + idx) * 4) : ST_OOB);
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
@@ -551,7 +809,11 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const in
     // the sample window was just updated through global memory by thread 0: make it visible to the
     // block (same CU), then run the next step's input layer here - one launch less per step
     __syncthreads();
-    if (i + 1 < a.n_steps) input_layer<KIND>(a, st, it + 1, tid, 256, lwin);
+    if constexpr (POOL) {
+        if (it + 1 < it_end) input_layer<KIND>(a, st, it + 1, tid, 256, lwin);
+    } else {
+        if (i + 1 < a.n_steps) input_layer<KIND>(a, st, it + 1, tid, 256, lwin);
+    }
 }
 
 // ---- step_tail of the Laplace nets with every global operand requested up front.  The kernel above pays its dependent
@@ -560,21 +822,31 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StArgs a, const in
 //      arithmetic, so here the sample window, the step's noise draws, the out_2 bias and the K + 1 parameter rows of the
 //      next input layer are all in flight with the out_2 operands, and what follows the first barrier works on LDS and
 //      registers.  Same formulas in the same order as step_tail_kernel<LAPLACE> + input_layer (bit-identical results).
-template <int MAXE, bool STREAM = false>      // elements (channel, position) of the next input layer per thread: ceil(H * seg / 256) <= MAXE
-__global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StArgs a, const int it) {
+// POOL (with STREAM): as step_tail_kernel
+template <int MAXE, bool STREAM = false, bool POOL = false>      // elements (channel, position) of the next input layer per thread: ceil(H * seg / 256) <= MAXE
+__global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StA<POOL> a, const int itj) {
+    static_assert(!POOL || STREAM, "the pool form is a streamed chunk per entry");
     __shared__ float o2v[64];                  // NO <= 48
     __shared__ float lwin[32];                 // the updated sample window, for the fused next input layer
     __shared__ float lold[32];                 // the window as the step found it
     __shared__ float lnz[16];                  // the step's noise draws
     const SwnGeom& g = a.g;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
-    float* st = a.state + (size_t)b * a.stride;
-    const int ia = it - a.n_pro, i = STREAM ? ia - a.step0 : ia, seg = g.seg, WN = a.WN, H = g.H, K = g.K;
+    int b = blockIdx.x, it = itj, step0 = a.step0, it_end = 0;
+    size_t sb = (size_t)b;                     // state block
+    if constexpr (POOL) {
+        const StPoolEnt& en = a.tab[blockIdx.x];
+        it = en.it0 + itj;
+        if (itj >= en.n_it || it < en.g0) return;
+        b = en.row; sb = (size_t)en.slot; step0 = en.g0 - a.n_pro; it_end = en.it0 + en.n_it;
+    }
+    const int tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
+    float* st = a.state + sb * a.stride;
+    const int ia = it - a.n_pro, i = STREAM ? ia - step0 : ia, seg = g.seg, WN = a.WN, H = g.H, K = g.K;
     const float* P = a.P;
     float* shist = st + a.o_hist;
     // ---- requests: out_2 rows and bias, window, noise, input-layer parameters
     const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
-    const size_t xb = (size_t)b * a.stride + a.o_o1;
+    const size_t xb = sb * a.stride + a.o_o1;
     const int nin = g.O1p;                     // <= 512 (host)
     float4 wv[4], wv2[4], xv[4];
     const bool rok = grp < g.NO, rok2 = grp + 8 < g.NO;          // NO <= 16 (host): rows grp and grp + 8 of the 32-lane group
@@ -583,15 +855,18 @@ __global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StArgs a, 
         const int idx = u * 128 + lane * 4;
         wv[u] = st_ld4(rP, (rok && idx < nin) ? (unsigned)((a.y.w2 + (size_t)grp * g.O1p + idx) * 4) : ST_OOB);
         wv2[u] = st_ld4(rP, (rok2 && idx < nin) ? (unsigned)((a.y.w2 + (size_t)(grp + 8) * g.O1p + idx) * 4) : ST_OOB);
-        xv[u] = st_ld4(rS, (rok && idx < nin) ? (unsigned)((xb + idx) * 4) : ST_OOB);
+        if constexpr (POOL) xv[u] = st_ld4(rS, (rok && idx < nin) ? st_off(xb + idx) : ST_OOB);
+        else xv[u] = st_ld4(rS, (rok && idx < nin) ? (unsigned)((xb + idx) * 4) : ST_OOB);
     }
     const float b2v = st_ld1(rP, (rok && lane == 0) ? (unsigned)((a.y.b2 + grp) * 4) : ST_OOB);
     const float b2v2 = st_ld1(rP, (rok2 && lane == 0) ? (unsigned)((a.y.b2 + grp + 8) * 4) : ST_OOB);
-    const float hv = st_ld1(rS, tid < WN ? (unsigned)((((size_t)b * a.stride) + a.o_hist + tid) * 4) : ST_OOB);
+    float hv;
+    if constexpr (POOL) hv = st_ld1(rS, tid < WN ? st_off(sb * a.stride + a.o_hist + tid) : ST_OOB);
+    else hv = st_ld1(rS, tid < WN ? (unsigned)((((size_t)b * a.stride) + a.o_hist + tid) * 4) : ST_OOB);
     float ev = 0.f;
     if (tid >= 64 && tid < 64 + seg) ev = swn_noise_laplace_at(a.nz, b, i, ia, tid - 64, a.n_steps, seg);
     // next input layer (iteration it + 1, a generation step): element e = tid + 256 m -> position j = e / H, channel o
-    const bool more = i + 1 < a.n_steps;
+    const bool more = POOL ? it + 1 < it_end : i + 1 < a.n_steps;
     float pcb[MAXE], pcv[MAXE][8], pcc[MAXE][8];
 #pragma unroll
     for (int m = 0; m < MAXE; ++m) {
@@ -686,6 +961,39 @@ __global__ void step_seed_kernel(const StArgs a) {
         reinterpret_cast<int*>(hist)[k] = (k == a.WN - 1) ? sc : a.g.Q / 2;
     } else if (a.seed && k >= a.WN - a.g.seg) {
         hist[k] = reinterpret_cast<const float*>(a.seed)[(size_t)b * a.g.seg + (k - (a.WN - a.g.seg))];
+    }
+}
+
+// first launch of a pool tick: block (0, k) writes entry k of the table to the device copy the later launches read, and the
+// blocks (x, k) of a BEGIN entry zero its slot and seed its sample window - what hipMemsetAsync + step_seed_kernel do for a
+// whole streamed chunk, here for that slot alone (the other slots belong to other sessions).  Grid (zero blocks, entries).
+__global__ __launch_bounds__(256) void step_pool_setup_kernel(const StArgs a, const StPoolTable t, StPoolEnt* tab,
+                                                              unsigned long long begin_mask) {
+    const int k = blockIdx.y, tid = threadIdx.x;
+    const StPoolEnt& en = t.e[k];
+    if (blockIdx.x == 0 && tid < 8) reinterpret_cast<int*>(tab + k)[tid] = reinterpret_cast<const int*>(&en)[tid];
+    if (!((begin_mask >> k) & 1ull)) return;
+    float* blk = a.state + (size_t)en.slot * a.stride;
+    const int n4 = a.stride / 4;                               // stride: a multiple of 64 floats
+    const int WN = a.WN, seg = a.g.seg;
+    const bool soft = a.g.kind == SWN_KIND_SOFTMAX;
+    for (int v = blockIdx.x * 256 + tid; v < n4; v += gridDim.x * 256) {
+        float q[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int kk = 4 * v + c - a.o_hist;               // step_seed_kernel's window slot
+            float x = 0.f;
+            if (kk >= 0 && kk < WN) {
+                if (soft) {
+                    const int sc = a.seed ? reinterpret_cast<const int*>(a.seed)[en.row] : a.g.Q / 2;
+                    x = __builtin_bit_cast(float, (kk == WN - 1) ? sc : a.g.Q / 2);
+                } else if (a.seed && kk >= WN - seg) {
+                    x = reinterpret_cast<const float*>(a.seed)[(size_t)en.row * seg + (kk - (WN - seg))];
+                }
+            }
+            q[c] = x;
+        }
+        reinterpret_cast<float4*>(blk)[v] = make_float4(q[0], q[1], q[2], q[3]);
     }
 }
 
@@ -835,4 +1143,148 @@ extern "C" int swn_decode_stepped_chunk(const swn_net_desc* d, const float* pack
                                         const void* seed, float* sess, void* out, float* heads, void* stream_) {
     return stepped_run(d, packed, cond, batch, n_frames, step0, n_steps, true, resume != 0, nz, forced, seed, sess, out, heads,
                        stream_);
+}
+
+// ---- stepped decode pool -------------------------------------------------------------------------------------------
+extern "C" int swn_decode_stepped_prologue_iterations(const swn_net_desc* d) {
+    SwnGeom g;
+    const int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    return g.rf - g.seg + 1;
+}
+
+extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float* packed, int capacity,
+                                             const swn_decode_stepped_pool_entry* entries, int n_entries,
+                                             const swn_decode_io* io, float* session, void* out, float* heads,
+                                             void* stream_) {
+    StPoolArgs a;
+    int rc = swn_make_geom(d, &a.g);
+    if (rc < 0) return rc;
+    const SwnGeom& g = a.g;
+    if (!packed || !entries || !io || !session) return SWN_E_BADARG;
+    if (capacity < 1 || n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
+    if (io->noise_dev || io->forced_dev) return SWN_E_BADARG;    // pools draw their noise on the device, no teacher forcing
+    const int n_pro = g.rf - g.seg + 1;
+    int n_max = 0, it_max = 0;
+    bool any_begin = false;
+    for (int e = 0; e < n_entries; ++e) {
+        const swn_decode_stepped_pool_entry& en = entries[e];
+        const bool begin = (en.flags & SWN_CHUNK_BEGIN) != 0;
+        if (!en.cond_dev || en.n_frames < 1 || en.slot < 0 || en.slot >= capacity || en.it0 < 0 || en.n_it < 0 ||
+            (en.flags & ~SWN_CHUNK_BEGIN) || en.reserved != 0)
+            return SWN_E_BADARG;
+        if (begin && en.it0 != 0) return SWN_E_BADARG;
+        if (!begin && en.it0 == 0 && en.n_it > 0) return SWN_E_BADARG;     // a session's iteration 0 runs from BEGIN only
+        const long long end = (long long)en.it0 + en.n_it;
+        if (end > (long long)INT32_MAX) return SWN_E_BADARG;
+        const long long n_gen = end > n_pro ? end - (en.it0 > n_pro ? en.it0 : n_pro) : 0;
+        if (end > n_pro && (end - n_pro) * g.seg > (long long)en.n_frames * g.U) return SWN_E_BADARG;   // conditioning
+        for (int f = 0; f < e; ++f)
+            if (entries[f].slot == en.slot) return SWN_E_BADARG;   // two entries on one session
+        n_max = n_gen > n_max ? (int)n_gen : n_max;
+        it_max = en.n_it > it_max ? en.n_it : it_max;
+        any_begin = any_begin || begin;
+    }
+    if (n_max > 0 && !out) return SWN_E_BADARG;
+    if (!swn_decode_stepped_supported(d, capacity)) return SWN_E_UNSUPPORTED;
+    const int ni = (g.K * g.Hp + 255) / 256;
+    if (!any_begin && it_max == 0) return SWN_OK;           // every slot stays as it is
+
+    swn_make_layout(&a.g, &a.y);
+    plan(a);
+    SwnNoise nz;
+    nz.ptr = nullptr; nz.dump = io->noise_out_dev;
+    nz.key0 = (uint32_t)(io->rng_seed & 0xffffffffu); nz.key1 = (uint32_t)(io->rng_seed >> 32); nz.utt0 = io->rng_utt0;
+    nz.ids = io->rng_utt_ids_dev;
+    a.P = packed; a.cond = nullptr; a.nz = nz; a.forced = nullptr; a.seed = io->seed_dev; a.state = session; a.out = out;
+    a.heads = heads; a.B = n_entries; a.Tf = 0; a.n_steps = n_max; a.n_pro = n_pro; a.step0 = 0;
+    a.o2_by_rowvec = g.NO > 64 ? 1 : 0;
+    // the table, sorted by n_it (descending, stable): the entries active at tick-local iteration j are a prefix of it
+    StPoolTable t = {};
+    int order[SWN_DECODE_POOL_MAX_ENTRIES];
+    for (int e = 0; e < n_entries; ++e) order[e] = e;
+    for (int x = 1; x < n_entries; ++x)
+        for (int y = x; y > 0 && entries[order[y]].n_it > entries[order[y - 1]].n_it; --y) {
+            const int tmp = order[y]; order[y] = order[y - 1]; order[y - 1] = tmp;
+        }
+    unsigned long long begin_mask = 0;
+    for (int k = 0; k < n_entries; ++k) {
+        const swn_decode_stepped_pool_entry& en = entries[order[k]];
+        t.e[k].cond = en.cond_dev; t.e[k].Tf = en.n_frames; t.e[k].slot = en.slot; t.e[k].it0 = en.it0;
+        t.e[k].n_it = en.n_it; t.e[k].row = order[k]; t.e[k].g0 = en.it0 > n_pro ? en.it0 : n_pro;
+        if (en.flags & SWN_CHUNK_BEGIN) begin_mask |= 1ull << k;
+    }
+    StPoolEnt* tab = reinterpret_cast<StPoolEnt*>(session + (size_t)a.stride * capacity);
+    a.tab = tab;
+    hipStream_t st = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    const StArgs& base = a;
+    hipLaunchKernelGGL(step_pool_setup_kernel, dim3(any_begin ? 64 : 1, n_entries), dim3(256), 0, st, base, t, tab, begin_mask);
+
+    // dynamic LDS above 64 KB for the tile forms (set on every call that uses them: the attribute is per device)
+    bool any_seq = false;
+    for (int j = 0; j < it_max && !any_seq; ++j) {
+        int nact = 0;
+        while (nact < n_entries && t.e[nact].n_it > j) ++nact;
+        any_seq = nact >= 24;
+    }
+    if (any_seq) {
+        const int big = 72 * 1024;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_LAPLACE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_SOFTMAX, true>), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(rowvec_tile_pool_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess)
+            return SWN_E_LAUNCH;
+    }
+    const bool fast_tail = g.kind == SWN_KIND_LAPLACE && g.NO <= 16 && g.O1p <= 512 && g.K <= 8 && g.H * g.seg <= 1024 &&
+                           g.seg <= 16 && a.WN <= 32;
+    int nact = n_entries;
+    for (int j = 0; j < it_max; ++j) {
+        while (nact > 0 && t.e[nact - 1].n_it <= j) --nact;
+        bool need_in = false, need_gen = false;
+        for (int k = 0; k < nact; ++k) {
+            const int it = t.e[k].it0 + j;
+            need_in = need_in || it < n_pro || it == t.e[k].g0;
+            need_gen = need_gen || it >= t.e[k].g0;
+        }
+        a.B = nact;
+        const bool seq = nact >= 24;
+        const unsigned sy = (unsigned)((nact + ST_TU - 1) / ST_TU);
+        if (need_in) {
+            if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL((step_in_kernel<SWN_KIND_LAPLACE, true>), dim3(nact), dim3(256), 0, st, a, j);
+            else hipLaunchKernelGGL((step_in_kernel<SWN_KIND_SOFTMAX, true>), dim3(nact), dim3(256), 0, st, a, j);
+        }
+#define SWN_PLAYER(NI_, KIND_)                                                                                 \
+        do {                                                                                                    \
+            if (seq) hipLaunchKernelGGL((step_layer_tile_kernel<NI_, KIND_, true>), dim3((g.H + ST_TU - 1) / ST_TU, sy),  \
+                                        dim3(64 * ST_TU), (size_t)ST_TU * NI_ * 256 * sizeof(float), st, a, l, j);   \
+            else hipLaunchKernelGGL((step_layer_kernel<NI_, KIND_, 1, true>), dim3(g.H, nact), dim3(64), 0, st, a, l, j); \
+        } while (0)
+        for (int l = 0; l < g.L; ++l) {
+            if (g.kind == SWN_KIND_LAPLACE) {
+                if (ni <= 1) SWN_PLAYER(1, SWN_KIND_LAPLACE);
+                else if (ni <= 6) SWN_PLAYER(6, SWN_KIND_LAPLACE);
+                else SWN_PLAYER(8, SWN_KIND_LAPLACE);
+            } else {
+                if (ni <= 1) SWN_PLAYER(1, SWN_KIND_SOFTMAX);
+                else if (ni <= 6) SWN_PLAYER(6, SWN_KIND_SOFTMAX);
+                else SWN_PLAYER(8, SWN_KIND_SOFTMAX);
+            }
+        }
+#undef SWN_PLAYER
+        if (!need_gen) continue;
+        auto rowvec = [&](int rows, size_t w_off, int ldw, size_t b_off, int nin, int x_off, int y_off, int relu) {
+            if (seq && nin <= 1280) hipLaunchKernelGGL(rowvec_tile_pool_kernel<5>, dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 5 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, j);
+            else if (seq && nin <= 2304) hipLaunchKernelGGL(rowvec_tile_pool_kernel<9>, dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 9 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, j);
+            else hipLaunchKernelGGL(rowvec_pool_kernel, dim3(rows, nact), dim3(64), 0, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, j);
+        };
+        rowvec(g.S, a.y.wsk, g.L * g.Hp, a.y.bsk, g.L * g.Hp, a.o_hcat, a.o_skip, 1);
+        rowvec(g.O1, a.y.w1, g.Sp, a.y.b1, g.Sp, a.o_skip, a.o_o1, 1);
+        if (a.o2_by_rowvec) rowvec(g.NO, a.y.w2, g.O1p, a.y.b2, g.O1p, a.o_o1, a.o_o2, 0);
+        if (fast_tail) {
+            if (g.H * g.seg <= 256) hipLaunchKernelGGL((step_tail_laplace_kernel<1, true, true>), dim3(nact), dim3(256), 0, st, a, j);
+            else hipLaunchKernelGGL((step_tail_laplace_kernel<4, true, true>), dim3(nact), dim3(256), 0, st, a, j);
+        } else if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL((step_tail_kernel<SWN_KIND_LAPLACE, true, true>), dim3(nact), dim3(256), 0, st, a, j);
+        else hipLaunchKernelGGL((step_tail_kernel<SWN_KIND_SOFTMAX, true, true>), dim3(nact), dim3(256), 0, st, a, j);
+    }
+    return swn_launch_status("swn_decode_pool_stepped_chunk");
 }

@@ -149,12 +149,17 @@ class EngineMixin:
         """a decode pool of `capacity` session slots on the module's current engine (shallow_wavenet_amd.streaming.DecodePool):
         independent utterances open, receive features and end at their own pace, and one launch per tick advances all of
         them.  The noise key follows open_stream: `noise_rng_seed` when the caller pinned one, else one fresh key per pool.
-        A session opened with utt_id = i draws what utterance i of batch_fast_generate with noise_source = "device" draws."""
-        from .. import noise as _noise
-        from ..streaming import DecodePool
+        A session opened with utt_id = i draws what utterance i of batch_fast_generate with noise_source = "device" draws.
+        When the engine resolves to the stepped multi-launch decode (REF6-class nets: variant 0 or 3), the pool is a
+        SteppedDecodePool (its step() also takes max_prologue)."""
+        from .. import _lib, noise as _noise, ops as _ops
+        from ..streaming import DecodePool, SteppedDecodePool
         key = getattr(self, "noise_rng_seed", None)
-        return DecodePool(self._engine(), capacity, variant=variant,
-                          rng_seed=_noise.draw_rng_seed() if key is None else int(key))
+        rng_seed = _noise.draw_rng_seed() if key is None else int(key)
+        net = self._engine()
+        if _lib.lib().swn_decode_resolve_variant(_ops._desc(net.dlist), capacity, int(variant)) == 3:
+            return SteppedDecodePool(net, capacity, rng_seed=rng_seed)
+        return DecodePool(net, capacity, variant=variant, rng_seed=rng_seed)
 
     def set_packed_engine(self, net: HipNet) -> None:
         """install an engine whose packed buffer arrived by RCCL broadcast (dist.py)."""

@@ -19,6 +19,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
                                rng_seed, rng_utt0, want_heads, want_noise, utt_ids?)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_chunk(packed, session, conds, slots, step0s, n_steps, begins, seeds?, utt_ids, desc, capacity,
                                     variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
+    torch.ops.swn.decode_pool_stepped_chunk(packed, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids, desc,
+                                            capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.stack_forward(packed, cond, audio, desc, want_hidden) -> (raw, work, hidden)
     torch.ops.swn.stack_forward_bf16(packed, wbf16, cond, audio, desc)  -> (raw, work)
     torch.ops.swn.pack_bf16(packed, desc)                          -> wbf16
@@ -350,6 +352,91 @@ def _(packed, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, de
             packed.new_empty((E, n_max, width) if want_noise else (0,)))
 
 
+def stepped_pool_session_floats(d, capacity: int) -> int:
+    """floats of a stepped pool's session buffer: the slots (swn_decode_session_floats(capacity, 3)) and the device copy of
+    each call's entry table; 0 when the stepped chain does not run the net at this capacity"""
+    n = int(_lib.lib().swn_decode_session_floats(ctypes.byref(d), int(capacity), 3))
+    return n + _lib.DECODE_STEPPED_POOL_TABLE_FLOATS if n > 0 else 0
+
+
+def _gen_steps(it0: int, n_it: int, n_pro: int) -> int:
+    """generation steps among iterations [it0, it0 + n_it)"""
+    return max(0, it0 + n_it - max(it0, n_pro))
+
+
+def decode_pool_stepped_chunk_impl(packed: torch.Tensor, session: torch.Tensor, conds: List[torch.Tensor],
+                                   slots: List[int], it0s: List[int], n_its: List[int], begins: List[bool],
+                                   seeds: Optional[torch.Tensor], utt_ids: List[int], desc: List[int], capacity: int,
+                                   rng_seed: int, want_heads: bool, want_noise: bool
+                                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """one call of a stepped decode pool (swn_decode_pool_stepped_chunk): entry e runs iterations [it0s[e], it0s[e] + n_its[e])
+    (prologue positions, then generation steps) of the session in slot slots[e] of `session` (stepped_pool_session_floats()
+    fp32, updated in place) over its own conditioning conds[e] (n_frames, N); begins[e] zeroes and seeds that slot from
+    seeds[e] (laplace (E, seg) fp32 | softmax (E,) classes; None = zeros / Q/2).  out / heads / used noise are dense
+    (E, n_max * seg) | (E, n_max, n_out) | (E, n_max, width) over the entries' generation steps, n_max = their maximum."""
+    L = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(packed, "the packed parameters")
+    dev = packed.device
+    soft, seg, _, _, n_out, _ = _geom(d)
+    E = len(conds)
+    if not (len(slots) == len(it0s) == len(n_its) == len(begins) == len(utt_ids) == E):
+        raise RuntimeError("decode_pool_stepped_chunk: conds, slots, it0s, n_its, begins and utt_ids must have one entry each")
+    if not 1 <= E <= _lib.DECODE_POOL_MAX_ENTRIES:
+        raise RuntimeError(f"decode_pool_stepped_chunk: {E} entries, a call takes 1 .. {_lib.DECODE_POOL_MAX_ENTRIES}")
+    width = d.n_quantize if soft else seg
+    if session.device != dev or session.dtype != torch.float32 or not session.is_contiguous():
+        raise RuntimeError("session must be a contiguous fp32 tensor on the device of the packed parameters")
+    need = stepped_pool_session_floats(d, int(capacity))
+    if need == 0:
+        raise RuntimeError("decode_pool_stepped_chunk: the stepped decode does not run this net at this capacity")
+    if session.numel() < need:
+        raise RuntimeError("session buffer too small for this (net, capacity)")
+    table = (_lib.DecodeSteppedPoolEntry * E)()
+    for e, c in enumerate(conds):
+        if c.device != dev or c.dtype != torch.float32 or not c.is_contiguous() or c.dim() != 2:
+            raise RuntimeError("every cond buffer must be a contiguous (n_frames, N) fp32 tensor on the device")
+        table[e] = _lib.DecodeSteppedPoolEntry(cond_dev=c.data_ptr(), n_frames=int(c.shape[0]), slot=int(slots[e]),
+                                               it0=int(it0s[e]), n_it=int(n_its[e]),
+                                               flags=_lib.CHUNK_BEGIN if begins[e] else 0, reserved=0)
+    if seeds is not None:
+        seeds = seeds.to(dev, torch.int32 if soft else torch.float32).contiguous()
+        if seeds.numel() != E * seg:
+            raise RuntimeError(f"seeds have {seeds.numel()} elements, expected {E * seg}")
+    ids = torch.tensor([int(u) & 0xFFFFFFFF for u in utt_ids], dtype=torch.int64).to(torch.int32).to(dev)
+    n_pro = int(L.swn_decode_stepped_prologue_iterations(ctypes.byref(d)))
+    n_max = max(_gen_steps(int(i), int(n), n_pro) for i, n in zip(it0s, n_its))
+    out = torch.empty((E, n_max * seg), dtype=torch.int32 if soft else torch.float32, device=dev)
+    heads = torch.empty((E, n_max, n_out) if want_heads else (0,), dtype=torch.float32, device=dev)
+    used = torch.empty((E, n_max, width) if want_noise else (0,), dtype=torch.float32, device=dev)
+    io = _lib.DecodeIO(noise_dev=None, forced_dev=None, seed_dev=_ptr(seeds),
+                       noise_out_dev=_ptr(used if want_noise else None),
+                       rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=0, reserved=0, rng_utt_ids_dev=_ptr(ids))
+    with _on(dev):
+        _lib.check(L.swn_decode_pool_stepped_chunk(ctypes.byref(d), _ptr(packed), int(capacity), table, E,
+                                                   ctypes.byref(io), _ptr(session), _ptr(out if n_max > 0 else None),
+                                                   _ptr(heads if want_heads else None), _stream(dev)),
+                   "decode_pool_stepped_chunk")
+    return out, heads, used
+
+
+decode_pool_stepped_chunk = custom_op("swn::decode_pool_stepped_chunk", mutates_args=("session",))(
+    decode_pool_stepped_chunk_impl)
+
+
+@decode_pool_stepped_chunk.register_fake
+def _(packed, session, conds, slots, it0s, n_its, begins, seeds, utt_ids, desc, capacity, rng_seed, want_heads,
+      want_noise):
+    d = _desc(desc)
+    soft, seg, _, _, n_out, _ = _geom(d)
+    n_pro = int(_lib.lib().swn_decode_stepped_prologue_iterations(ctypes.byref(d)))
+    E, n_max = len(conds), max(_gen_steps(int(i), int(n), n_pro) for i, n in zip(it0s, n_its))
+    width = d.n_quantize if soft else seg
+    return (packed.new_empty((E, n_max * seg), dtype=torch.int32 if soft else torch.float32),
+            packed.new_empty((E, n_max, n_out) if want_heads else (0,)),
+            packed.new_empty((E, n_max, width) if want_noise else (0,)))
+
+
 # ------------------------------------------------------------------------------------------ teacher-forced stack
 def _tp(d, Tf: int) -> Tuple[int, int]:
     soft, seg, *_ = _geom(d)
@@ -578,5 +665,5 @@ def backward_bf16_supported(desc: List[int], batch: int, n_frames: int) -> bool:
     return _lib.lib().swn_backward_bf16_work_floats(ctypes.byref(_desc(desc)), batch, n_frames) > 0
 
 
-OP_NAMES = ("pack_params", "frontend", "decode", "decode_chunk", "decode_pool_chunk", "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
+OP_NAMES = ("pack_params", "frontend", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk", "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16")

@@ -378,3 +378,101 @@ class DecodePool:
         if self.soft:
             return torch.full((1,), int(self.cfg.n_quantize) // 2, dtype=torch.int32)
         return torch.zeros(self.seg, dtype=torch.float32)
+
+
+# -------------------------------------------------------------------------------------------------- stepped decode pool
+def plan_stepped_tick(sessions: Sequence[Tuple[object, int, int]], n_pro: int, max_steps: Optional[int] = None,
+                      max_prologue: Optional[int] = None,
+                      limit: int = _lib.DECODE_POOL_MAX_ENTRIES) -> List[List[Tuple[object, int, int]]]:
+    """the calls of one stepped-pool tick.  sessions: (key, steps_ready, iterations_done) of every open session, in
+    admission order; n_pro: prologue iterations of the net (swn_decode_stepped_prologue_iterations).  A session with ready
+    steps (its first frame is final: the prologue reads it) runs the rest of its prologue, at most max_prologue iterations
+    of it, and - once the prologue is complete - min(ready - done, max_steps) generation steps.  Entries (key, it0, n_it) are
+    split into calls of at most `limit`.  Pure host arithmetic: nothing here touches a device."""
+    if max_steps is not None and int(max_steps) < 1:
+        raise ValueError(f"max_steps must be a positive integer or None, not {max_steps!r}")
+    if max_prologue is not None and int(max_prologue) < 1:
+        raise ValueError(f"max_prologue must be a positive integer or None, not {max_prologue!r}")
+    n_pro = int(n_pro)
+    entries = []
+    for key, ready, it_done in sessions:
+        ready, it_done = int(ready), int(it_done)
+        if ready <= 0:
+            continue                                   # waiting for features
+        p = max(0, n_pro - it_done)
+        if max_prologue is not None:
+            p = min(p, int(max_prologue))
+        g = 0
+        if it_done + p >= n_pro:
+            g = ready - max(0, it_done - n_pro)
+            if max_steps is not None:
+                g = min(g, int(max_steps))
+        if p + g > 0:
+            entries.append((key, it_done, p + g))
+    return [entries[i:i + limit] for i in range(0, len(entries), limit)]
+
+
+class SteppedDecodePool(DecodePool):
+    """the decode pool of the stepped multi-launch decode (variant 3: what REF6-class nets resolve to;
+    swn_decode_pool_stepped_chunk).  Every launch of the chain serves all sessions of a call, each at its own iteration, so a
+    tick costs about one session's chunk; each session's output is bit-identical to HipNet.decode of that utterance alone
+    with variant=3 (same rng_seed, utterance id and seed waveform).  Same interface and results as DecodePool; in addition,
+    step(max_prologue=n) spreads a new session's prologue (rf - seg + 1 iterations, each a launch per layer) over ticks of at
+    most n iterations, so the sessions already generating do not wait for all of it in one tick.  A session that only
+    advanced its prologue in a tick has no result for it."""
+
+    def __init__(self, net, capacity: int, *, rng_seed: int = 0, want_heads: bool = False, want_noise: bool = False):
+        if not isinstance(capacity, int) or capacity < 1:
+            raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
+        self.net, self.cfg, self.capacity = net, net.cfg, capacity
+        self.soft = self.cfg.kind == "softmax"
+        self.seg = 1 if self.soft else int(self.cfg.seg)
+        desc = _ops._desc(net.dlist)
+        lib = _lib.lib()
+        floats = _ops.stepped_pool_session_floats(desc, capacity)
+        if floats == 0:
+            raise ValueError(f"the stepped decode does not run this net with {capacity} slots "
+                             f"({lib.swn_strerror(lib.swn_decode_resolve_variant(desc, capacity, 3)).decode()})")
+        self.variant = self.resolved_variant = 3
+        self.n_pro = int(lib.swn_decode_stepped_prologue_iterations(desc))
+        self.rng_seed = int(rng_seed) & 0x7FFFFFFFFFFFFFFF
+        self.want_heads, self.want_noise = bool(want_heads), bool(want_noise)
+        self._session = torch.empty(floats, dtype=torch.float32, device=net.device)
+        self._free = list(range(capacity))
+        self._open: dict = {}
+        self.admitted = 0
+
+    def open(self, seed: Optional[torch.Tensor] = None, utt_id: Optional[int] = None) -> PoolSession:
+        s = super().open(seed, utt_id)
+        s._it_done = 0                               # iterations run: prologue positions, then generation steps
+        return s
+
+    def step(self, max_steps: Optional[int] = None, max_prologue: Optional[int] = None) -> dict:
+        """one tick: every open session with ready steps runs the rest of its prologue (at most max_prologue iterations of
+        it) and then up to min(ready, max_steps) steps, in calls of at most 64 sessions.  Returns {session: (out, heads) or
+        (out, heads, noise)} for the sessions that generated, as DecodePool.step.  Nothing here waits for the device."""
+        calls = plan_stepped_tick([(s, s.steps_ready, s._it_done) for s in self._open.values()], self.n_pro, max_steps,
+                                  max_prologue)
+        results = {}
+        for entries in calls:
+            sess = [e[0] for e in entries]
+            begins = [s._it_done == 0 for s in sess]
+            seeds = None
+            if any(b and s._seed is not None for s, b in zip(sess, begins)):
+                seeds = torch.stack([s._seed.reshape(-1).to(torch.int32 if self.soft else torch.float32).cpu()
+                                     if s._seed is not None else self._default_seed() for s in sess])
+            out, heads, used = _O.decode_pool_stepped_chunk(
+                self.net.packed, self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
+                [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
+                self.net.dlist, self.capacity, self.rng_seed, self.want_heads, self.want_noise)
+            for e, (s, it0, n_it) in enumerate(entries):
+                s._it_done = it0 + n_it
+                s._stream._begun = True
+                n = max(0, it0 + n_it - max(it0, self.n_pro))
+                s._stream.steps_done = max(0, s._it_done - self.n_pro)
+                if n == 0:
+                    continue
+                o = out[e:e + 1, :n * self.seg]
+                h = heads[e:e + 1, :n] if self.want_heads else None
+                results[s] = (o, h, used[e:e + 1, :n]) if self.want_noise else (o, h)
+        return results
