@@ -18,7 +18,7 @@ from shallow_wavenet_amd.synth import synth_aux, synth_state_dict
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("U,seg,lpc", [(200, 2, 0), (130, 1, 0), (256, 5, 4), (64, 1, 0)])
+@pytest.mark.parametrize("U,seg,lpc", [(200, 2, 0), (130, 1, 0), (256, 5, 4), (64, 1, 0), (256, 10, 4), (240, 1, 4)])
 def test_conditioning_gradients_at_wide_upsampling_factors(gpu_ok, U, seg, lpc):
     cfg = dataclasses.replace(C.bl6_laplace(seg, lpc), upsampling_factor=U)
     B, Tf = 2, 5

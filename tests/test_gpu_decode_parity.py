@@ -6,12 +6,15 @@ Tolerances (north_star / SURVEY.md 8c):
   * Laplace teacher-forced heads  <= 2e-6 abs (mu, pre-sigmoid scale, LP coefficients)
   * softmax indices bit-exact (fixtures have top-2 margins >= 1e-4), logits <= 2e-5
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden_names, load_golden
 from oracle import cpu_ref
+from shallow_wavenet_amd import _lib
 from shallow_wavenet_amd.runtime import HipNet
 from shallow_wavenet_amd.synth import synth_state_dict
 
@@ -30,11 +33,16 @@ def _net(cfg, d):
     return HipNet.from_state_dict(cfg, sd, "cuda:0"), cpu_ref.as_params(sd)
 
 
-def _variants(cfg):
-    """1 generic persistent, 3 stepped multi-launch, 0 auto (BL6 fast kernels / stepped for REF6); BL6-class nets also 6 = the
-    symmetric BL6 kernel (auto takes the wave-specialised one for the single-sample Laplace nets)"""
-    bl6 = cfg.H == 64 and cfg.kernel_size == 2 and cfg.dilation_depth == 6 and cfg.dilation_repeat == 1
-    return [1, 3, 0] + ([6] if bl6 else [])
+def _variants(cfg, batch):
+    """1 generic persistent, 3 stepped multi-launch, 0 auto (BL6 fast kernels / stepped for REF6 / generic); plus 6, the
+    symmetric BL6 kernel, wherever the library has it for this net (auto takes the wave-specialised one for the
+    single-sample Laplace nets).  Asked of the library (swn_decode_resolve_variant), not guessed from the shape: a BL6-shaped
+    net at seg 10 has no BL6 kernel and decodes on the generic one."""
+    desc = _lib.desc_from_cfg(cfg)
+    resolve = lambda v: _lib.lib().swn_decode_resolve_variant(ctypes.byref(desc), batch, v)
+    for v in (1, 3, 0):
+        assert resolve(v) >= 0, (cfg, batch, v, resolve(v))
+    return [1, 3, 0] + ([6] if resolve(6) == 6 else [])
 
 
 @pytest.mark.parametrize("name", LAP)
@@ -43,9 +51,10 @@ def test_laplace_free_running_matches_reference(gpu_ok, name):
     net, _ = _net(cfg, d)
     n_steps = d["noise"].shape[0]
     if name.startswith("g2_"):
-        n_steps = min(n_steps, BIG_STEPS // cfg.seg)
+        # past the receptive field and one more frame whatever seg is (BIG_STEPS samples alone end inside it at seg 10)
+        n_steps = min(n_steps, max(BIG_STEPS, cfg.receptive_field + 2 * cfg.U) // cfg.seg)
     noise = torch.from_numpy(d["noise"][:n_steps]).permute(1, 0, 2).contiguous()
-    for variant in _variants(cfg):
+    for variant in _variants(cfg, d["aux"].shape[0]):
         out, heads = net.decode(torch.from_numpy(d["aux"]), n_steps, noise, want_heads=True, variant=variant)
         out, heads = out.cpu().numpy(), heads.cpu().numpy()
         ref_heads = np.transpose(d["heads"][:n_steps], (1, 0, 2))
@@ -65,7 +74,7 @@ def test_laplace_teacher_forced_matches_oracle(gpu_ok, name):
                                                [n_steps * cfg.seg] * B, d["noise"], return_heads=True)
     forced = torch.from_numpy(np.stack(full))
     noise = torch.from_numpy(d["noise"]).permute(1, 0, 2).contiguous()
-    for variant in _variants(cfg):
+    for variant in _variants(cfg, d["aux"].shape[0]):
         out, heads = net.decode(torch.from_numpy(d["aux"]), n_steps, noise, forced=forced,
                                 want_heads=True, variant=variant)
         got, ref = heads.cpu().numpy(), np.transpose(heads_ref, (1, 0, 2))
@@ -93,7 +102,7 @@ def test_softmax_free_running_bit_exact(gpu_ok, name):
         n_steps = min(n_steps, BIG_STEPS)
     noise = torch.from_numpy(q[:n_steps]).permute(1, 0, 2).contiguous()
     st = int(d["head_stride"])
-    for variant in _variants(cfg):
+    for variant in _variants(cfg, d["aux"].shape[0]):
         out, heads = net.decode(torch.from_numpy(d["aux"]), n_steps, noise, want_heads=True, variant=variant)
         out, heads = out.cpu().numpy(), heads.cpu().numpy()
         ref_heads = np.transpose(d["heads"], (1, 0, 2))

@@ -30,8 +30,11 @@ SMX = [n for n in golden_names() if "softmax" in n and not n.startswith(("g5_", 
 
 def test_fixture_inventory():
     names = golden_names()
-    assert len([n for n in names if n.startswith("g0_")]) >= 13
-    assert len([n for n in names if n.startswith("g1_")]) >= 7
+    assert len([n for n in names if n.startswith("g0_")]) >= 15
+    assert len([n for n in names if n.startswith("g1_")]) >= 9
+    assert len([n for n in names if n.startswith("g2_")]) >= 5
+    assert len([n for n in names if n.startswith("g7_")]) >= 6
+    assert len([n for n in names if n.startswith("g9_drop")]) >= 4
     assert "g3_numerics" in names
 
 
@@ -295,7 +298,7 @@ def test_oracle_dropout_mode_at_the_trained_geometries(name):
     """G9: model.train(), forward(do=True), do_prob = 0.5 (run.sh:198) through the REFERENCE at REF6 Laplace / BL6 Laplace /
     REF6 softmax; the oracle with the re-drawn masks, differentiated by autograd, gives its outputs, loss and gradients."""
     cfg, d = load_golden(name)
-    assert len(G9) == 3 and float(d["drop_p"]) == 0.5
+    assert len(G9) == 4 and float(d["drop_p"]) == 0.5
     P = {k: v.clone().requires_grad_(True) for k, v in _params(cfg, d).items()}
     loss, res = oracle_dropout_loss(cfg, P, d)
     if cfg.kind == "laplace":
