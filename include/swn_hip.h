@@ -260,6 +260,43 @@ int    swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float* packed_
                                      const swn_decode_io* io, float* session_dev, void* out_dev, float* heads_dev,
                                      void* stream);
 
+/* ---- noise-shaping restoration on the device (run.sh stage 6 / 9: noise_shaping.py --inv false, run.sh:713-740) -------------
+ * y = lowcut(MLSA_b(x)): the time-invariant MLSA filter of the coefficients b[0 .. order] (gain exp(b[0]) applied to the input,
+ * Pade order `pade`, all-pass constant alpha; csrc/swn_dsp.c is the host version) followed by the causal FIR taps[0 .. n_taps-1],
+ * both in fp64 from zero state.  Resumable: each session slot of state_dev keeps both filters' state between calls, so the
+ * concatenated outputs of any sequence of chunks are bit-identical to one call over the whole signal.
+ *   b_dev, taps_dev   device fp64 arrays of order + 1 / n_taps values;  mulaw_dev  device fp64 table of
+ *                     SWN_POSTFILTER_MULAW_ENTRIES values (class -> sample; classes are clamped to it), or NULL without
+ *                     mu-law entries
+ *   state_dev         capacity slots of swn_postfilter_state_doubles(order, pade, n_taps) doubles, laid out as
+ *                     [stage 1: 2 (pade + 1)] [stage 2: pade (order + 2) + pade + 1] (the layout of swn_dsp.c) [last n_taps - 1
+ *                     MLSA outputs]
+ *   entries_host      one entry per session of the call, any number (launched in groups of SWN_POSTFILTER_MAX_ENTRIES, one
+ *                     wave each); a slot may appear once per call.  SWN_POSTFILTER_RESET starts the slot from zero state.
+ * SWN_E_BADARG, before any device call: pade other than 4 / 5, |alpha| >= 1, n_taps outside [1, SWN_POSTFILTER_MAX_TAPS],
+ * order < 1, a null pointer, capacity < 1, n_entries < 0, a slot outside [0, capacity) or in two entries, n < 0, an unknown
+ * kind or flag, a mu-law entry without mulaw_dev.  SWN_E_UNSUPPORTED: order > SWN_POSTFILTER_MAX_ORDER.
+ * swn_postfilter_state_doubles returns 0 for a bad (order, pade, n_taps). */
+#define SWN_POSTFILTER_IN_F32 0         /* in_dev: fp32 samples */
+#define SWN_POSTFILTER_IN_MULAW 1       /* in_dev: int32 mu-law classes, looked up in mulaw_dev */
+#define SWN_POSTFILTER_RESET 1          /* flags: the slot starts from zero state */
+#define SWN_POSTFILTER_MAX_ORDER 62
+#define SWN_POSTFILTER_MAX_TAPS 256
+#define SWN_POSTFILTER_MAX_ENTRIES 64
+#define SWN_POSTFILTER_MULAW_ENTRIES 256
+typedef struct swn_postfilter_entry {
+    const void* in_dev;      /* n input samples (kind) */
+    float* out_dev;          /* n fp32 restored samples */
+    int32_t slot;            /* [0, capacity) */
+    int32_t n;               /* >= 0; 0 with SWN_POSTFILTER_RESET only clears the slot */
+    int32_t kind;            /* SWN_POSTFILTER_IN_* */
+    int32_t flags;           /* SWN_POSTFILTER_RESET or 0 */
+} swn_postfilter_entry;
+size_t swn_postfilter_state_doubles(int order, int pade, int n_taps);
+int    swn_postfilter_chunk(int order, double alpha, int pade, const double* b_dev, int n_taps, const double* taps_dev,
+                            const double* mulaw_dev, double* state_dev, int capacity,
+                            const swn_postfilter_entry* entries_host, int n_entries, void* stream);
+
 /* ---- teacher-forced stack  (CSWNV.forward cswnv_shift1.py:191-267,
  *                             DSWNV.forward dswnv.py:250-276) ----------------------------
  *   audio_dev   laplace: (B, 1, T - seg) fp32 samples ; softmax: (B, T - 1) int32 indices

@@ -48,11 +48,22 @@ class DecodeSteppedPoolEntry(ctypes.Structure):
                 ("n_it", c_int32), ("flags", c_int32), ("reserved", c_int32)]
 
 
+class PostfilterEntry(ctypes.Structure):
+    """mirror of `swn_postfilter_entry` (include/swn_hip.h): one session's share of a post-filter call."""
+    _fields_ = [("in_dev", c_void_p), ("out_dev", c_void_p), ("slot", c_int32), ("n", c_int32), ("kind", c_int32),
+                ("flags", c_int32)]
+
+
 ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
 DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
 CHUNK_BEGIN = 1                                # SWN_CHUNK_BEGIN (include/swn_hip.h): first chunk of a streamed decode
 PRECISION_FP32, PRECISION_BF16 = 0, 1          # SWN_PRECISION_* (include/swn_hip.h)
+POSTFILTER_IN_F32, POSTFILTER_IN_MULAW = 0, 1   # SWN_POSTFILTER_IN_* (include/swn_hip.h)
+POSTFILTER_RESET = 1                           # SWN_POSTFILTER_RESET
+POSTFILTER_MAX_ORDER = 62                      # SWN_POSTFILTER_MAX_ORDER
+POSTFILTER_MAX_TAPS = 256                      # SWN_POSTFILTER_MAX_TAPS
+POSTFILTER_MULAW_ENTRIES = 256                 # SWN_POSTFILTER_MULAW_ENTRIES
 
 
 def desc_from_cfg(cfg: NetConfig) -> NetDesc:
@@ -94,6 +105,9 @@ SIGNATURES = {
     "swn_decode_stepped_prologue_iterations": (c_int, [POINTER(NetDesc)]),
     "swn_decode_pool_stepped_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodeSteppedPoolEntry), c_int,
                                               POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "swn_postfilter_state_doubles": (c_size_t, [c_int, c_int, c_int]),
+    "swn_postfilter_chunk": (c_int, [c_int, ctypes.c_double, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                     POINTER(PostfilterEntry), c_int, c_void_p]),
     "swn_forward_work_floats": (c_size_t, [POINTER(NetDesc), c_int, c_int]),
     "swn_forward": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                             c_void_p, c_void_p, c_void_p]),

@@ -16,6 +16,10 @@ Device-drawn sampling noise (`--noise_source device`, the softmax default) is ke
 `torch.manual_seed(--seed)` and by each utterance's position in the unsorted `--feats` list, so an utterance draws
 the same stream whatever `--n_gpus` and wherever the length sort puts it.
 
+`--restore_stats` / `--restore_writedir` (not reference flags) also restore every waveform on the device as run.sh stage 6
+does with `noise_shaping.py --inv false` (shallow_wavenet_amd.postfilter; --mcep_dim_start, --mcep_alpha and --mag as that
+script takes them) and write the restored WAVs under --restore_writedir; the unrestored WAVs under --outdir stay as they are.
+
 Feature files: `<utt>.npy` (T x n_aux float arrays) always; `<utt>.h5` with the dataset named by
 `config.string_path` when h5py is importable (it is not in the build image).
 """
@@ -164,8 +168,9 @@ def gpu_decode(kind: str, args, config, feat_list: Sequence[str], device, packed
             global_index = list(range(len(feat_list)))
         model.set_packed_engine(HipNet(cfg, D.broadcast_packed(cfg, packed, device, src=packed_src_rank), device))
         string_path = getattr(config, "string_path", "/feat_org_lf0")
+        restorer = make_restorer(args, device)
         if getattr(args, "pool_slots", 0) > 0:
-            return pool_decode(kind, args, model, feat_list, global_index, string_path, device)
+            return pool_decode(kind, args, model, feat_list, global_index, string_path, device, restorer)
         t_total, n_max, n_tot = 0.0, 0, 0
         for ids, batch_h, n_samples_list, utt_index in decode_batches(feat_list, args.batch_size, string_path,
                                                                       config.upsampling_factor, global_index):
@@ -177,17 +182,26 @@ def gpu_decode(kind: str, args, config, feat_list: Sequence[str], device, packed
                 seed = torch.full((len(ids), 1), config.n_quantize // 2, dtype=torch.int64, device=device)
             logging.info("decoding start")
             start = time.time()
+            restored = None
             if getattr(args, "stream_frames", 0) > 0:
-                samples_list = stream_generate(model, seed, aux, n_samples_list, args.stream_frames)
+                samples_list = stream_generate(model, seed, aux, n_samples_list, args.stream_frames, restorer)
+                if restorer is not None:
+                    samples_list, restored = samples_list
             else:
                 samples_list = model.batch_fast_generate(seed, aux, n_samples_list, args.intervals)
+                if restorer is not None:
+                    restored = restorer.restore([torch.from_numpy(np.ascontiguousarray(x)) for x in samples_list],
+                                                config.n_quantize if kind == "softmax" else None)
+                    restored = [r.cpu().numpy() for r in restored]
             t_total += time.time() - start
             n_max += max(n_samples_list)
             n_tot += max(n_samples_list) * len(n_samples_list)
-            for feat_id, samples in zip(ids, samples_list):
+            for b, (feat_id, samples) in enumerate(zip(ids, samples_list)):
                 wav = samples if kind == "laplace" else softmax_mod.decode_mu_law(samples, config.n_quantize)
                 write_wav_pcm16(os.path.join(args.outdir, feat_id + ".wav"), np.clip(wav, -1, 1), args.fs)
                 logging.info("wrote %s.wav in %s." % (feat_id, args.outdir))
+                if restored is not None:
+                    write_restored(args, feat_id, restored[b])
         if n_max:
             logging.info("average time / sample = %.6f sec (%ld samples) [%.3f kHz/s]" % (
                 t_total / n_max, n_max, n_max / (1000 * t_total)))
@@ -196,32 +210,58 @@ def gpu_decode(kind: str, args, config, feat_list: Sequence[str], device, packed
         return n_tot, t_total
 
 
-def stream_generate(model, seed, aux, n_samples_list, frames_per_push: int):
+def stream_generate(model, seed, aux, n_samples_list, frames_per_push: int, restorer=None):
     """batch_fast_generate's result by a streamed decode: the features are pushed `frames_per_push` frames at a time and
-    the samples collected as they become final (shallow_wavenet_amd.streaming; device-drawn noise only)."""
+    the samples collected as they become final (shallow_wavenet_amd.streaming; device-drawn noise only).  With a restorer
+    (postfilter.NoiseShapingRestorer): (samples, restored samples), each chunk restored on the device as it comes."""
     B = aux.shape[0]
-    stream = model.open_stream(B, seed)
-    pieces = []
-    for f0 in range(0, aux.shape[2], frames_per_push):
-        pieces.append(stream.push(aux[:, :, f0:f0 + frames_per_push])[0])
-    pieces.append(stream.finish()[0])
+    stream = model.open_stream(B, seed, post_filter=restorer)
+    pieces, rpieces = [], []
+    for r in [stream.push(aux[:, :, f0:f0 + frames_per_push]) for f0 in range(0, aux.shape[2], frames_per_push)] + [stream.finish()]:
+        pieces.append(r[0])
+        if restorer is not None:
+            rpieces.append(r[-1])
+    stream.close()
     samples = torch.cat(pieces, dim=1).cpu().numpy()
+    restored = torch.cat(rpieces, dim=1).cpu().numpy() if restorer is not None else None
     max_samples = max(n_samples_list)
     if model._cfg.kind == "softmax":
         samples = samples.astype(np.int64)
     elif max_samples <= samples.shape[1]:
         samples = samples[:, -max_samples:]
-    return [samples[b, :n] for b, n in zip(range(B), n_samples_list)]
+        restored = restored[:, -max_samples:] if restored is not None else None
+    out = [samples[b, :n] for b, n in zip(range(B), n_samples_list)]
+    if restorer is None:
+        return out
+    return out, [restored[b, :n] for b, n in zip(range(B), n_samples_list)]
 
 
-def pool_decode(kind: str, args, model, feat_list: Sequence[str], global_index: Sequence[int], string_path: str, device):
+def make_restorer(args, device):
+    """--restore_stats: the device post-filter of run.sh stage 6 (noise_shaping.py --inv false) for this run, else None"""
+    if not getattr(args, "restore_stats", None):
+        return None
+    from .noise_shaping_driver import mean_mcep_vector
+    from .postfilter import NoiseShapingRestorer
+    return NoiseShapingRestorer(mean_mcep_vector(args.restore_stats), args.fs, args.mcep_alpha, mag=args.mag,
+                                mcep_dim_start=args.mcep_dim_start, inv=False,
+                                capacity=max(1, args.batch_size, getattr(args, "pool_slots", 0)), device=device)
+
+
+def write_restored(args, feat_id: str, restored) -> None:
+    path = os.path.join(args.restore_writedir, feat_id + ".wav")
+    write_wav_pcm16(path, np.clip(np.asarray(restored, dtype=np.float64), -1, 1), args.fs)
+    logging.info("wrote %s.wav in %s." % (feat_id, args.restore_writedir))
+
+
+def pool_decode(kind: str, args, model, feat_list: Sequence[str], global_index: Sequence[int], string_path: str, device,
+                restorer=None):
     """--pool_slots N: the utterances go through a decode pool of N slots (shallow_wavenet_amd.streaming.DecodePool), admitted
     in list order as slots free up; each runs its own n_samples / seg steps over its own features, so its WAV is that of the
     default path with --batch_size 1 (device-drawn noise, utterance index = position in the unsorted list)."""
     cfg = model._cfg
-    pool = model.open_pool(args.pool_slots)
+    pool = model.open_pool(args.pool_slots, post_filter=restorer)
     pending = list(range(len(feat_list)))
-    live = {}                                   # session -> (utterance id, n_samples, out pieces)
+    live = {}                                   # session -> (utterance id, n_samples, out pieces, restored pieces)
     t0, n_tot = time.time(), 0
     while pending or live:
         while pending and len(live) < args.pool_slots:
@@ -229,16 +269,20 @@ def pool_decode(kind: str, args, model, feat_list: Sequence[str], global_index: 
             h = read_feature(feat_list[i], string_path)
             s = pool.open(utt_id=int(global_index[i]))
             s.finish(torch.from_numpy(np.ascontiguousarray(h.T[None])).to(device, torch.float32))
-            live[s] = (os.path.splitext(os.path.basename(feat_list[i]))[0], h.shape[0] * int(cfg.U), [])
+            live[s] = (os.path.splitext(os.path.basename(feat_list[i]))[0], h.shape[0] * int(cfg.U), [], [])
         for s, r in pool.step().items():
             live[s][2].append(r[0])
+            if restorer is not None:
+                live[s][3].append(r[-1])
         for s in [s for s in live if s.done]:
-            feat_id, n, pieces = live.pop(s)
+            feat_id, n, pieces, rpieces = live.pop(s)
             pool.close(s)
             samples = torch.cat(pieces, dim=1)[0, :n].cpu().numpy()
             wav = samples if kind == "laplace" else softmax_mod.decode_mu_law(samples.astype(np.int64), cfg.n_quantize)
             write_wav_pcm16(os.path.join(args.outdir, feat_id + ".wav"), np.clip(wav, -1, 1), args.fs)
             logging.info("wrote %s.wav in %s." % (feat_id, args.outdir))
+            if restorer is not None:
+                write_restored(args, feat_id, torch.cat(rpieces, dim=1)[0, :n].cpu().numpy())
             n_tot += n
     t_total = time.time() - t0
     if n_tot:
@@ -273,6 +317,17 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--pool_slots", default=0, type=int,
                    help="not a reference flag: > 0 decodes the utterances through a decode pool of this many slots, each "
                         "over its own features and steps (needs device-drawn noise; the WAVs are those of --batch_size 1)")
+    from .noise_shaping_driver import MAG, MCEP_ALPHA, MCEP_DIM_START
+    p.add_argument("--restore_stats", default=None, type=str,
+                   help="not a reference flag: statistics file of the noise shaping (as noise_shaping.py --stats); with "
+                        "--restore_writedir, every waveform is also restored on the device (run.sh stage 6, --inv false)")
+    p.add_argument("--restore_writedir", default=None, type=str,
+                   help="not a reference flag: directory of the restored WAVs (needs --restore_stats)")
+    p.add_argument("--mcep_dim_start", default=MCEP_DIM_START, type=int,
+                   help="index of c(0) in the statistics vector (restoration; as noise_shaping.py)")
+    p.add_argument("--mcep_alpha", default=MCEP_ALPHA, type=float,
+                   help="all-pass constant of the mel-cepstrum (restoration; as noise_shaping.py)")
+    p.add_argument("--mag", default=MAG, type=float, help="magnification of the shaping filter (restoration; as noise_shaping.py)")
     p.add_argument("--plan_only", action="store_true",
                    help="not a reference flag: stop after listing, sharding and the parameter broadcast and write "
                         "<outdir>/decode.<rank>.plan.json (needs no GPU: what the CPU tests of the fan-out drive)")
@@ -352,10 +407,15 @@ def main(kind: str, argv=None) -> int:
         print("--pool_slots needs device-drawn noise (--noise_source device): the host stream is drawn for the whole run "
               "up front", file=sys.stderr)
         return 2
+    if bool(args.restore_stats) != bool(args.restore_writedir):
+        print("--restore_stats and --restore_writedir go together", file=sys.stderr)
+        return 2
     if "WORLD_SIZE" not in os.environ and args.n_gpus > 1:
         return fan_out(kind, argv, args.n_gpus, args.GPU_device_str)        # before anything below can touch a GPU
     rank, world, local = D.init_from_env()
     os.makedirs(args.outdir, exist_ok=True)
+    if args.restore_writedir:
+        os.makedirs(args.restore_writedir, exist_ok=True)
     level = logging.INFO if args.verbose > 0 else logging.WARN
     logging.basicConfig(level=level, format="%(asctime)s (%(module)s:%(lineno)d) %(levelname)s: %(message)s",
                         datefmt="%m/%d/%Y %I:%M:%S", filename=os.path.join(args.outdir, f"decode.{rank}.log"

@@ -103,10 +103,15 @@ def _fir(numtaps: int, cutoff: float, highpass: bool):
     return firwin(numtaps, cutoff, pass_zero=not highpass)
 
 
+def low_cut_taps(fs: int, cutoff: float = 70.0) -> np.ndarray:
+    """the 255 taps of low_cut_filter"""
+    return _fir(255, cutoff / (fs // 2), True)
+
+
 def low_cut_filter(x, fs: int, cutoff: float = 70.0) -> np.ndarray:
     """255-tap FIR high-pass at `cutoff` Hz, causal (feature_extract.py:57-76: the group delay stays in the signal)"""
     from scipy.signal import lfilter
-    return lfilter(_fir(255, cutoff / (fs // 2), True), 1, np.asarray(x, dtype=np.float64))
+    return lfilter(low_cut_taps(fs, cutoff), 1, np.asarray(x, dtype=np.float64))
 
 
 def low_pass_filter(x, fs: int, cutoff: float = 20.0) -> np.ndarray:
@@ -128,6 +133,16 @@ def continuous_f0(f0) -> Tuple[np.ndarray, np.ndarray]:
     return uv, np.interp(np.arange(f0.size), voiced, f0[voiced])
 
 
+def shaping_mcep(mean_mcep, mag: float = 0.5, mcep_dim_start: int = 5, inv: bool = False) -> np.ndarray:
+    """the differential mel-cepstrum of noise_shaping: the statistics vector from `mcep_dim_start` on, scaled by `mag`, c(0)
+    zeroed, c(1..) negated when `inv`"""
+    coef = np.array(mean_mcep, dtype=np.float64)[mcep_dim_start:] * mag
+    coef[0] = 0.0
+    if inv:
+        coef[1:] = -coef[1:]
+    return coef
+
+
 def noise_shaping(x, mean_mcep, fs: int, alpha: float, mag: float = 0.5, mcep_dim_start: int = 5, inv: bool = False,
                   shiftms: float = 5.0, cutoff: float = 70.0) -> np.ndarray:
     """one utterance of noise_shaping.py:144-181: the time-invariant MLSA filter built from the corpus-mean mel-cepstrum (the
@@ -135,10 +150,7 @@ def noise_shaping(x, mean_mcep, fs: int, alpha: float, mag: float = 0.5, mcep_di
     with `--inv true` before training (run.sh:529-543) and RESTORES decoded waveforms with `--inv false` (run.sh:725-740)), then the
     70 Hz low cut."""
     x = np.asarray(x, dtype=np.float64)
-    coef = np.array(mean_mcep, dtype=np.float64)[mcep_dim_start:] * mag
-    coef[0] = 0.0
-    if inv:
-        coef[1:] = -coef[1:]
+    coef = shaping_mcep(mean_mcep, mag, mcep_dim_start, inv)
     frames = np.tile(coef, (world_frame_count(x.size, fs, shiftms), 1))
     return low_cut_filter(synthesis_diff(x, frames, alpha, fs, shiftms), fs, cutoff)
 

@@ -120,14 +120,15 @@ class EngineMixin:
             return net
         return cache[1]
 
-    def open_stream(self, batch: int, audio=None, variant: int = 0):
+    def open_stream(self, batch: int, audio=None, variant: int = 0, post_filter=None):
         """a streamed decode of `batch` utterances on the module's current engine (shallow_wavenet_amd.streaming.DecodeStream):
         push features as they arrive, get the samples whose conditioning is final.  Bit-identical to batch_fast_generate with
         noise_source = "device" and the same key: the kernels draw the noise, keyed by `noise_rng_seed` when the caller
         pinned one (else one fresh key per stream, taken from the torch CPU generator) and indexed by
         `noise_utterance_ids` / `noise_utterance_offset`.  The host-noise default of the Laplace model's
         batch_fast_generate draws the whole run up front in the reference's order and is not streamed (DecodeStream.advance
-        takes host noise chunk by chunk).  audio: the seed waveform as batch_fast_generate takes it (None = zeros / Q/2)."""
+        takes host noise chunk by chunk).  audio: the seed waveform as batch_fast_generate takes it (None = zeros / Q/2).
+        post_filter: a postfilter.NoiseShapingRestorer - every chunk is also returned restored (run.sh stage 6) on the device."""
         from .. import noise as _noise
         from ..streaming import DecodeStream
         net = self._engine()
@@ -143,23 +144,23 @@ class EngineMixin:
         return DecodeStream(net, batch, variant=variant, seed=seed,
                             rng_seed=_noise.draw_rng_seed() if key is None else int(key),
                             rng_utt0=int(getattr(self, "noise_utterance_offset", 0)),
-                            utt_ids=getattr(self, "noise_utterance_ids", None))
+                            utt_ids=getattr(self, "noise_utterance_ids", None), post_filter=post_filter)
 
-    def open_pool(self, capacity: int, variant: int = 0):
+    def open_pool(self, capacity: int, variant: int = 0, post_filter=None):
         """a decode pool of `capacity` session slots on the module's current engine (shallow_wavenet_amd.streaming.DecodePool):
         independent utterances open, receive features and end at their own pace, and one launch per tick advances all of
         them.  The noise key follows open_stream: `noise_rng_seed` when the caller pinned one, else one fresh key per pool.
         A session opened with utt_id = i draws what utterance i of batch_fast_generate with noise_source = "device" draws.
         When the engine resolves to the stepped multi-launch decode (REF6-class nets: variant 0 or 3), the pool is a
-        SteppedDecodePool (its step() also takes max_prologue)."""
+        SteppedDecodePool (its step() also takes max_prologue).  post_filter: as open_stream, one slot per session."""
         from .. import _lib, noise as _noise, ops as _ops
         from ..streaming import DecodePool, SteppedDecodePool
         key = getattr(self, "noise_rng_seed", None)
         rng_seed = _noise.draw_rng_seed() if key is None else int(key)
         net = self._engine()
         if _lib.lib().swn_decode_resolve_variant(_ops._desc(net.dlist), capacity, int(variant)) == 3:
-            return SteppedDecodePool(net, capacity, rng_seed=rng_seed)
-        return DecodePool(net, capacity, variant=variant, rng_seed=rng_seed)
+            return SteppedDecodePool(net, capacity, rng_seed=rng_seed, post_filter=post_filter)
+        return DecodePool(net, capacity, variant=variant, rng_seed=rng_seed, post_filter=post_filter)
 
     def set_packed_engine(self, net: HipNet) -> None:
         """install an engine whose packed buffer arrived by RCCL broadcast (dist.py)."""

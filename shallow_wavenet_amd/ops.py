@@ -21,6 +21,7 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
                                     variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_stepped_chunk(packed, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids, desc,
                                             capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
+    torch.ops.swn.postfilter_chunk(image, state, inputs, slots, resets, order, alpha, pade, n_taps, capacity)  -> restored
     torch.ops.swn.stack_forward(packed, cond, audio, desc, want_hidden) -> (raw, work, hidden)
     torch.ops.swn.stack_forward_bf16(packed, wbf16, cond, audio, desc)  -> (raw, work)
     torch.ops.swn.pack_bf16(packed, desc)                          -> wbf16
@@ -437,6 +438,63 @@ def _(packed, session, conds, slots, it0s, n_its, begins, seeds, utt_ids, desc, 
             packed.new_empty((E, n_max, width) if want_noise else (0,)))
 
 
+# ------------------------------------------------------------------------------------------ noise-shaping post-filter
+def postfilter_chunk_impl(image: torch.Tensor, state: torch.Tensor, inputs: List[torch.Tensor], slots: List[int],
+                          resets: List[bool], order: int, alpha: float, pade: int, n_taps: int,
+                          capacity: int) -> torch.Tensor:
+    """one call of the device post-filter (swn_postfilter_chunk): entry e filters inputs[e] (1-D: fp32 samples | int32 mu-law
+    classes) as the next chunk of the session in slot slots[e] of `state` (capacity * swn_postfilter_state_doubles() fp64,
+    updated in place); resets[e] starts that slot from zero state.  image: fp64 [b (order + 1) | FIR taps (n_taps) | mu-law
+    table (SWN_POSTFILTER_MULAW_ENTRIES), only needed for class inputs].  -> (E, n_max) fp32, rows past an entry's own length
+    not written."""
+    L = _lib.lib()
+    dev = image.device
+    _need_cuda(image, "the filter image")
+    E = len(inputs)
+    if not (len(slots) == len(resets) == E):
+        raise RuntimeError("postfilter_chunk: inputs, slots and resets must have one entry each")
+    if image.dtype != torch.float64 or not image.is_contiguous() or image.dim() != 1:
+        raise RuntimeError("postfilter_chunk: the filter image must be a contiguous 1-D fp64 tensor")
+    base = int(order) + 1 + int(n_taps)
+    has_mulaw = image.numel() == base + _lib.POSTFILTER_MULAW_ENTRIES
+    if image.numel() != base and not has_mulaw:
+        raise RuntimeError(f"postfilter_chunk: the filter image has {image.numel()} values, expected {base} "
+                           f"(+ {_lib.POSTFILTER_MULAW_ENTRIES} with a mu-law table)")
+    per = int(L.swn_postfilter_state_doubles(int(order), int(pade), int(n_taps)))
+    if state.device != dev or state.dtype != torch.float64 or not state.is_contiguous() or state.numel() < per * int(capacity):
+        raise RuntimeError("postfilter_chunk: state must be a contiguous fp64 tensor of capacity * "
+                           "swn_postfilter_state_doubles() values on the device of the image")
+    ins = []
+    for x in inputs:
+        if x.device != dev or x.dim() != 1 or x.dtype not in (torch.float32, torch.int32):
+            raise RuntimeError("postfilter_chunk: every input must be a 1-D fp32 or int32 tensor on the device")
+        ins.append(x.contiguous())
+    n_max = max((x.numel() for x in ins), default=0)
+    out = torch.empty((E, n_max), dtype=torch.float32, device=dev)
+    table = (_lib.PostfilterEntry * max(E, 1))()
+    for e, x in enumerate(ins):
+        n = x.numel()
+        table[e] = _lib.PostfilterEntry(in_dev=x.data_ptr() if n else None, out_dev=out[e].data_ptr() if n else None,
+                                        slot=int(slots[e]), n=n,
+                                        kind=_lib.POSTFILTER_IN_MULAW if x.dtype == torch.int32 else _lib.POSTFILTER_IN_F32,
+                                        flags=_lib.POSTFILTER_RESET if resets[e] else 0)
+    b = image[: int(order) + 1]
+    taps = image[int(order) + 1: base]
+    with _on(dev):
+        _lib.check(L.swn_postfilter_chunk(int(order), float(alpha), int(pade), _ptr(b), int(n_taps), _ptr(taps),
+                                          _ptr(image[base:] if has_mulaw else None), _ptr(state), int(capacity), table, E,
+                                          _stream(dev)), "postfilter_chunk")
+    return out
+
+
+postfilter_chunk = custom_op("swn::postfilter_chunk", mutates_args=("state",))(postfilter_chunk_impl)
+
+
+@postfilter_chunk.register_fake
+def _(image, state, inputs, slots, resets, order, alpha, pade, n_taps, capacity):
+    return image.new_empty((len(inputs), max((x.numel() for x in inputs), default=0)), dtype=torch.float32)
+
+
 # ------------------------------------------------------------------------------------------ teacher-forced stack
 def _tp(d, Tf: int) -> Tuple[int, int]:
     soft, seg, *_ = _geom(d)
@@ -665,5 +723,6 @@ def backward_bf16_supported(desc: List[int], batch: int, n_frames: int) -> bool:
     return _lib.lib().swn_backward_bf16_work_floats(ctypes.byref(_desc(desc)), batch, n_frames) > 0
 
 
-OP_NAMES = ("pack_params", "frontend", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk", "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
+OP_NAMES = ("pack_params", "frontend", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk", "postfilter_chunk",
+            "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16")

@@ -56,15 +56,20 @@ class DecodeStream:
     rng_seed, rng_utt0, utt_ids   the device generator's key and utterance indices, as HipNet.decode
     want_heads / want_noise       also return the raw out_2 rows / the noise the kernels used, per chunk
 
+    post_filter   a postfilter.NoiseShapingRestorer: the stream claims `batch` of its slots (close() frees them) and
+                  restores every chunk on the device (run.sh stage 6)
+
     push / finish / advance return what HipNet.decode returns for the new steps: (out, heads) or, with want_noise,
     (out, heads, noise) - out laplace (B, n * seg) fp32 | softmax (B, n) int32 on the device, heads None unless asked for.
+    With a post_filter, one more element follows: the restored chunk, (B, n * seg) fp32 (softmax classes mu-law decoded on
+    the device); its concatenation over the chunks is the restore of the whole output.
     With generate=False, push / finish only extend the final conditioning (then `advance` runs steps explicitly: host
     noise and teacher forcing are streamed that way) and return None.
     """
 
     def __init__(self, net, batch: int, *, variant: int = 0, seed: Optional[torch.Tensor] = None, rng_seed: int = 0,
                  rng_utt0: int = 0, utt_ids: Optional[Sequence[int]] = None, want_heads: bool = False,
-                 want_noise: bool = False):
+                 want_noise: bool = False, post_filter=None):
         cfg = net.cfg
         if not isinstance(batch, int) or batch < 1:
             raise ValueError(f"batch must be a positive integer, not {batch!r}")
@@ -103,6 +108,14 @@ class DecodeStream:
         self._session = None          # device buffers: allocated on the first push
         self._aux = None              # (B, n_aux, capacity) features received so far
         self._cond = None             # (B, capacity, N) final conditioning rows (zeros beyond frames_final)
+        self.post_filter = post_filter
+        self._pf_slots = [post_filter.open() for _ in range(batch)] if post_filter is not None else []
+
+    def close(self) -> None:
+        """free the post-filter slots of the stream (nothing else to release)."""
+        for s in self._pf_slots:
+            self.post_filter.close(s)
+        self._pf_slots = []
 
     # ------------------------------------------------------------------ properties
     @property
@@ -200,9 +213,12 @@ class DecodeStream:
             dev = self.net.device
             out = torch.empty((self.batch, 0), dtype=torch.int32 if self.soft else torch.float32, device=dev)
             heads = torch.empty((self.batch, 0, self.cfg.n_out), dtype=torch.float32, device=dev) if self.want_heads else None
+            res = (out, heads)
             if self.want_noise:
-                return out, heads, torch.empty((self.batch, 0, self.width), dtype=torch.float32, device=dev)
-            return out, heads
+                res += (torch.empty((self.batch, 0, self.width), dtype=torch.float32, device=dev),)
+            if self.post_filter is not None:
+                res += (torch.empty((self.batch, 0), dtype=torch.float32, device=dev),)
+            return res
         if self._session is None:
             self._session = torch.empty(self._session_floats, dtype=torch.float32, device=self.net.device)
         # n_frames of the call = the buffer's capacity (the per-utterance stride of the rows); the bound that matters is
@@ -213,9 +229,15 @@ class DecodeStream:
         self._begun = True
         self.steps_done += n
         heads = heads if self.want_heads else None
-        if self.want_noise:
-            return out, heads, used
-        return out, heads
+        res = (out, heads, used) if self.want_noise else (out, heads)
+        if self.post_filter is not None:
+            if not self._pf_slots:
+                raise RuntimeError("the stream's post-filter slots were closed")
+            res += (self.post_filter.run_dense(self._pf_slots, list(out), self._n_quantize()),)
+        return res
+
+    def _n_quantize(self) -> Optional[int]:
+        return int(self.cfg.n_quantize) if self.soft else None
 
 
 # ---------------------------------------------------------------------------------------------------------- decode pool
@@ -247,6 +269,7 @@ class PoolSession:
         self._stream = DecodeStream(pool.net, 1, variant=pool.variant, seed=seed, rng_seed=pool.rng_seed, utt_ids=[utt_id])
         self._seed = self._stream._seed
         self.closed = False
+        self._pf_slot = pool.post_filter.open() if pool.post_filter is not None else None
 
     def _check(self) -> None:
         if self.closed:
@@ -292,6 +315,8 @@ class DecodePool:
                nets) cannot serve a pool - variant 1 runs those nets on the generic kernel
     rng_seed   the device generator's key (pools draw their noise on the device)
     want_heads / want_noise   also return the raw out_2 rows / the noise used
+    post_filter   a postfilter.NoiseShapingRestorer: every session holds one of its slots, and each tick ends with one
+               post-filter call over the sessions that ran; each result then ends with the restored chunk (1, n * seg) fp32
 
         s = pool.open(seed=None, utt_id=None)   # a free slot; utt_id defaults to the admission counter
         s.push(aux_piece); s.finish(aux_tail)  # (1, n_aux, f) features
@@ -300,7 +325,7 @@ class DecodePool:
     """
 
     def __init__(self, net, capacity: int, *, variant: int = 0, rng_seed: int = 0, want_heads: bool = False,
-                 want_noise: bool = False):
+                 want_noise: bool = False, post_filter=None):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
         self.net, self.cfg, self.capacity = net, net.cfg, capacity
@@ -319,6 +344,7 @@ class DecodePool:
         self.want_heads, self.want_noise = bool(want_heads), bool(want_noise)
         self._session = torch.empty(int(lib.swn_decode_session_floats(desc, capacity, int(variant))), dtype=torch.float32,
                                     device=net.device)
+        self.post_filter = post_filter
         self._free = list(range(capacity))          # free slots, lowest first
         self._open: dict = {}                       # slot -> PoolSession, in admission order
         self.admitted = 0
@@ -345,6 +371,8 @@ class DecodePool:
             raise RuntimeError("this session is not open in this pool")
         s.closed = True
         del self._open[s.slot]
+        if s._pf_slot is not None:
+            self.post_filter.close(s._pf_slot)
         self._free.append(s.slot)
         self._free.sort()
 
@@ -372,7 +400,16 @@ class DecodePool:
                 o = out[e:e + 1, :n * self.seg]
                 h = heads[e:e + 1, :n] if self.want_heads else None
                 results[s] = (o, h, used[e:e + 1, :n]) if self.want_noise else (o, h)
-        return results
+        return self._post_filter(results)
+
+    def _post_filter(self, results: dict) -> dict:
+        """with a post_filter: one call restores the outputs of every session of the tick, each result gains its row."""
+        if self.post_filter is None or not results:
+            return results
+        sess = list(results)
+        restored = self.post_filter.run_dense([s._pf_slot for s in sess], [results[s][0][0] for s in sess],
+                                              int(self.cfg.n_quantize) if self.soft else None)
+        return {s: results[s] + (restored[e:e + 1, :results[s][0].shape[1]],) for e, s in enumerate(sess)}
 
     def _default_seed(self) -> torch.Tensor:
         if self.soft:
@@ -421,7 +458,8 @@ class SteppedDecodePool(DecodePool):
     most n iterations, so the sessions already generating do not wait for all of it in one tick.  A session that only
     advanced its prologue in a tick has no result for it."""
 
-    def __init__(self, net, capacity: int, *, rng_seed: int = 0, want_heads: bool = False, want_noise: bool = False):
+    def __init__(self, net, capacity: int, *, rng_seed: int = 0, want_heads: bool = False, want_noise: bool = False,
+                 post_filter=None):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
         self.net, self.cfg, self.capacity = net, net.cfg, capacity
@@ -438,6 +476,7 @@ class SteppedDecodePool(DecodePool):
         self.rng_seed = int(rng_seed) & 0x7FFFFFFFFFFFFFFF
         self.want_heads, self.want_noise = bool(want_heads), bool(want_noise)
         self._session = torch.empty(floats, dtype=torch.float32, device=net.device)
+        self.post_filter = post_filter
         self._free = list(range(capacity))
         self._open: dict = {}
         self.admitted = 0
@@ -475,4 +514,4 @@ class SteppedDecodePool(DecodePool):
                 o = out[e:e + 1, :n * self.seg]
                 h = heads[e:e + 1, :n] if self.want_heads else None
                 results[s] = (o, h, used[e:e + 1, :n]) if self.want_noise else (o, h)
-        return results
+        return self._post_filter(results)
