@@ -15,8 +15,9 @@
 //   * group A keeps its halves of all six matrices in registers (192 per thread), group B five of them (160) and the sixth in LDS
 //     (it also holds a slice of out_skip weights in flight); the out_1 matrix is LDS-resident whole (the 64 KB the sixth layer of
 //     the symmetric kernel took), only out_skip streams from L2;
-//   * out_1 is group A's alone (two rows per thread); out_2 + sampling + the next input layer run in every wave of group A, each
-//     forming its own copy of h0 and going straight on into layer 0 (wave 0 alone stores the sample and the heads).
+//   * out_1 is group A's alone (two rows per thread), and out_2 beside it as one partial sum per wave; the sum of the four partials
+//     + sampling + the next input layer run in every wave of group A, each forming its own copy of h0 and going straight on into
+//     layer 0 (wave 0 alone stores the sample and the heads).
 // Same arithmetic per element as the symmetric kernel up to the order of the partial sums (1e-7 relative); same noise, seed,
 // forced-input and heads interface (swn_decode_bl6.hip: classic = host-drawn noise, zero seed; extended = in-kernel generator,
 // noise dump, caller's seed waveform).  8 barriers per step.  cswnv_shift1.py:281-430.
@@ -81,9 +82,8 @@ struct Tw {
     static constexpr int o_old = o_bd + L * 2 * H;         // [2][L][2H]: older-tap products + bias of the step in progress / the next
     static constexpr int o_wup = o_old + 2 * L * 2 * H;
     static constexpr int o_skip = o_wup + 256;
-    static constexpr int o_o1 = o_skip + S;
-    static constexpr int o_o2 = o_o1 + O1;
-    static constexpr int o_tnz = o_o2 + r4(NO);
+    static constexpr int o_p2 = o_skip + S;                // out_2 as [NO][4] partial sums, one per wave of group A (b2 in wave 0's)
+    static constexpr int o_tnz = o_p2 + 4 * NO;
     static constexpr int o_cz = o_tnz + (EXT_ ? r4(NZB * NZC) : 16);   // cb[64], cv[2][64], cc[2][64]
     static constexpr int o_w2 = o_cz + 5 * H;              // out_2 rows [NO][S] (+b2)
     static constexpr int o_bias = o_w2 + NO * S + r4(NO);  // bsk[S], b1[O1]
@@ -115,6 +115,19 @@ __device__ __forceinline__ float sum4(float v) {      // all 4 lanes of a quad g
     v += dpp_f<0xB1>(v);      // quad_perm [1,0,3,2]
     v += dpp_f<0x4E>(v);      // quad_perm [2,3,0,1]
     return v;
+}
+// the sum over the wave's 16 quads, per position in the quad: lane hp of the first quad gets the sum of lanes hp + 4 n
+// (the swaps in inline assembly, with the two wait states a VALU write needs before them: the compiler returns the builtins'
+//  second result as a copy of the first)
+__device__ __forceinline__ float sum_quads(float v) {
+    v += dpp_f<0x124>(v);     // row_ror:4
+    v += dpp_f<0x128>(v);     // row_ror:8: the row's four quads
+    float w = v;
+    asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(v), "+v"(w));   // rows 0 + 1, 2 + 3
+    v += w;
+    w = v;
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(v), "+v"(w));   // the two halves
+    return v + w;
 }
 // exp, reciprocal, sigmoid as in swn_decode_bl6.hip (<= 1.5 ulp: the 1e-5 bar is held through 66 000 recurrent steps)
 __device__ __forceinline__ float exp_c(float x) {
@@ -266,6 +279,29 @@ __device__ __forceinline__ void skip_consume_b(const float* lds, const float4 (&
     // pin the partial sums to this phase: only the end of the step uses them, and the optimiser otherwise sinks all six slices'
     // multiply-adds down to that use - with their 48 operand registers per slice live until then (238 registers spilled)
     asm volatile("" : "+v"(sacc[0]), "+v"(sacc[1]));
+}
+// the last slice (the skip-fin phase, the only work left there): four independent 4-deep chains per row instead of one 16-deep
+// one, then the quad sums of both rows in three DPP steps - lane 0 finishes row r, lane 2 row r + 64 - and the ReLU (the bias
+// entered sacc with the first slice)
+template <class T>
+__device__ __forceinline__ void skip_last_b(float* lds, const float4 (&wsl)[8], const float (&sacc)[2], const int tb) {
+    const int r = tb >> 2, hp = tb & 3;
+    float part[2][4];
+#pragma unroll
+    for (int mm = 0; mm < 4; ++mm) {
+        const float4 x = *reinterpret_cast<const float4*>(lds + T::o_hcat + (L - 1) * H + 16 * mm + 4 * hp);
+#pragma unroll
+        for (int ps = 0; ps < 2; ++ps) {
+            const float4 w = wsl[ps * 4 + mm];
+            part[ps][mm] = fmaf(w.w, x.w, fmaf(w.z, x.z, fmaf(w.y, x.y, w.x * x.x)));
+        }
+    }
+    float s[2];
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) s[ps] = sacc[ps] + ((part[ps][0] + part[ps][1]) + (part[ps][2] + part[ps][3]));
+    const float t0 = s[0] + dpp_f<0xB1>(s[0]), t1 = s[1] + dpp_f<0xB1>(s[1]);   // lanes 0, 1: hp 0 + 1; lanes 2, 3: hp 2 + 3
+    const float v = (hp < 2 ? t0 : t1) + dpp_f<0x4E>(hp < 2 ? t1 : t0);        // lane 0 <- lane 2's half of row r, and back
+    if ((hp & 1) == 0) lds[T::o_skip + r + 32 * hp] = fmaxf(v, 0.f);
 }
 
 // The program of one group (GA: group A).  The two groups run the SAME sequence of barriers; they are separate instantiations -
@@ -504,6 +540,10 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
         cond_taps(q, wj, pb);
         float4 wsl[8];
         float sacc[2] = {0.f, 0.f};
+        if constexpr (!grpA) {                                // the out_skip bias enters in lane 0 of each row's quad
+            const float bs0 = lds[T::o_bias + (tg >> 2)], bs1 = lds[T::o_bias + (tg >> 2) + 64];
+            if ((tg & 3) == 0) { sacc[0] = bs0; sacc[1] = bs1; }
+        }
         unsigned step0 = 0;
         asm volatile("" : "+s"(step0));                       // opaque zero, see skip_issue_b
         const float* x0 = h0_row(q);
@@ -514,15 +554,7 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
         SWN_PHASE(0, true, 3, 3, x0) SWN_PHASE(1, true, -1, 0, x0) SWN_PHASE(2, true, -1, 0, x0) SWN_PHASE(3, true, -1, 0, x0)
         SWN_PHASE(4, true, -1, 0, x0) SWN_PHASE(5, true, -1, 0, x0)
         // out_skip: the last slice and the reduction (group B); group A has nothing on this phase
-        if constexpr (!grpA) {
-            skip_consume_b<T, 5>(lds, wsl, sacc, tg);
-            const int r = tg >> 2, hp = tg & 3;
-#pragma unroll
-            for (int ps = 0; ps < 2; ++ps) {
-                const float v = sum4(sacc[ps]);
-                if (hp == 0) lds[T::o_skip + r + 64 * ps] = fmaxf(v + lds[T::o_bias + r + 64 * ps], 0.f);
-            }
-        }
+        if constexpr (!grpA) skip_last_b<T>(lds, wsl, sacc, tg);
         // the next step's deviate (classic mode: one lane of wave 1, a ~130-instruction log1p chain) where group A has no work:
         // in the out_1 phase it made wave 1 the last of the group to reach the barrier
         noise_ahead(i + 1);
@@ -545,46 +577,40 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
                 if ((mm & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // at most four slices of operands live beside the 192 weight registers
             }
             const float v = sum4(a0 + a1), u = sum4(b0 + b1);
-            if (hp == 0) {
-                lds[T::o_o1 + hr] = fmaxf(v + lds[T::o_bias + S + hr], 0.f);
-                lds[T::o_o1 + hr + 64] = fmaxf(u + lds[T::o_bias + S + hr + 64], 0.f);
+            // out_2 of this wave's 32 out_1 rows, off the chain: lane hp of every quad takes out_2 rows hp and hp + 4, the wave sums
+            // them (sum_quads) and its first quad leaves them in o_p2 for the tail; wave 0's lane 0 .. 3 carry b2
+            const float o1a = fmaxf(v + lds[T::o_bias + S + hr], 0.f), o1b = fmaxf(u + lds[T::o_bias + S + hr + 64], 0.f);
+#pragma unroll
+            for (int j = 0; j < (T::NO + 3) / 4; ++j) {
+                const int k = hp + 4 * j, kc = k < T::NO ? k : T::NO - 1;
+                const float* w2 = lds + T::o_w2 + kc * S;
+                const float b2 = lds[T::o_w2 + T::NO * S + kc];
+                const float pz = sum_quads(fmaf(w2[hr + 64], o1b, fmaf(w2[hr], o1a, tg < 4 ? b2 : 0.f)));
+                if ((tg & 63) < 4 && k < T::NO) lds[T::o_p2 + 4 * k + wv] = pz;
             }
         } else {
             older_b3<T, 0>(lds, wreg, q + 1, tg);
         }
         SWN_BAR(7)
         if constexpr (grpA) {
-            // out_2: NO <= 6 rows, 4 lanes per row, weights resident in LDS; then the Laplace head, evaluated uniformly by every
-            // lane of every wave of group A so that the new sample is in registers for the next input layer (cswnv_shift1.py:368-391)
-            // (eight lanes per row, 16 inputs each, two chains: the serial 32-deep chain of the four-lane form was a third of this phase)
-            // Only wave 0 stores the heads and the sample.
-            const int ln = tg & 63, r = ln >> 3, pp = ln & 7;
+            // out_2 (NO <= 6 rows): the four waves' partial sums from the out_1 phase, added in one fixed order - all four waves form
+            // the same sample; then the Laplace head, evaluated uniformly by every lane of every wave of group A so that the new sample
+            // is in registers for the next input layer (cswnv_shift1.py:368-391).  Only wave 0 stores the heads and the sample.
+            const int ln = tg & 63;
             // the deviate (classic mode) and the forced sample are requested first: the deviate's LDS latency then hides under
-            // out_2, and the forced load is older than this step's stores - waiting for it must not wait for them (vmcnt counts
-            // stores too)
+            // the partials' read, and the forced load is older than this step's stores - waiting for it must not wait for them
+            // (vmcnt counts stores too)
             float tz = 0.f;                                // (an early read in the extended mode spilled four registers)
             if constexpr (!EXT) tz = lds[T::o_tnz + (i & 1) * 8];
             float fv = 0.f;
             if (a.forced) fv = reinterpret_cast<const float*>(a.forced)[(size_t)b * a.n_steps + i];
-            float acc = 0.f, acc1 = 0.f;
-            if (r < T::NO) {
-#pragma unroll
-                for (int mm = 0; mm < 4; ++mm) {
-                    const float4 w = *reinterpret_cast<const float4*>(lds + T::o_w2 + r * S + 16 * pp + 4 * mm);
-                    const float4 x = *reinterpret_cast<const float4*>(lds + T::o_o1 + 16 * pp + 4 * mm);
-                    float& ac = (mm & 1) ? acc1 : acc;
-                    ac = fmaf(w.x, x.x, ac); ac = fmaf(w.y, x.y, ac);
-                    ac = fmaf(w.z, x.z, ac); ac = fmaf(w.w, x.w, ac);
-                }
-            }
-            acc = sum4(acc + acc1);
-            acc += dpp_f<0x141>(acc);                          // row_half_mirror: the octet's sum
-            if (r < T::NO) acc += lds[T::o_w2 + T::NO * S + r];
-            // the NO head outputs sit in lanes 0, 8, 16, ...: broadcast them through scalar registers (an LDS write, a wave barrier and
+            const float4 pz = *reinterpret_cast<const float4*>(lds + T::o_p2 + 4 * (ln < T::NO ? ln : T::NO - 1));
+            const float acc = (pz.x + pz.y) + (pz.z + pz.w);   // lane k < NO: out_2 row k
+            // the NO head outputs sit in lanes 0 .. NO - 1: broadcast them through scalar registers (an LDS write, a wave barrier and
             // a broadcast read stood here: ~150 cycles of the chain the whole workgroup waits for)
             float o2[T::NO];
 #pragma unroll
-            for (int k = 0; k < T::NO; ++k) o2[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, acc), 8 * k));
+            for (int k = 0; k < T::NO; ++k) o2[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, acc), k));
             {
 #pragma clang fp contract(off)
                 float* outp = reinterpret_cast<float*>(a.out) + (size_t)b * a.n_steps + (size_t)i;
@@ -605,7 +631,7 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
                 win[T::WN - 1] = fd;
                 if (tid == 0) outp[0] = sv;
             }
-            if (HEADS_ON && a.heads && wv == 0 && pp == 0 && r < T::NO) a.heads[((size_t)b * a.n_steps + i) * T::NO + r] = acc;
+            if (HEADS_ON && a.heads && wv == 0 && ln < T::NO) a.heads[((size_t)b * a.n_steps + i) * T::NO + ln] = acc;
         }
         if (i + 1 < a.n_steps) input_gen(q + 1);
 #ifdef SWN_STAMP
