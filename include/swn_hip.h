@@ -427,6 +427,27 @@ int    swn_laplace_head_backward(const swn_net_desc* d, const float* out_dev, in
                                  const float* ga_dev, const float* gb_clip_dev, const float* glogb_clip_dev,
                                  float* graw_dev, void* stream);
 
+/* ---- multi-resolution STFT loss (train_driver.batch_loss's spectral terms; csrc/swn_spectral.hip) ------------------------
+ * rows sample signals and rows target signals of len samples (fp32, contiguous), n_sizes FFT sizes (HOST array `sizes`):
+ *   l1_dev [rows][n_sizes]   mean over (bins, frames, re/im) of |STFT_n(sample) - STFT_n(target)|
+ *   lsd_dev[rows][n_sizes]   mean_frames sqrt(mean_bins (10 log10 |S|^2 - 10 log10 |T|^2)^2), inf / nan as the formula gives them
+ * STFT_n = torch.stft(x, n, window=hann_window(n)) with its defaults (hop n/4, reflect-centred, one-sided, 1 + len / hop
+ * frames).  tables_dev: per size, in the order of `sizes`, cos(2 pi m / n) for m < n followed by the periodic Hann window
+ * (2 n floats each).  state_dev (swn_spectral_state_bytes) receives what swn_spectral_backward needs, one byte per
+ * (row, frame, bin); NULL (evaluation) writes none.  The backward gives grad_dev[rows][len] = d sum(g * l1) / d samples for
+ * g_dev[rows][n_sizes]; targets get no gradient.  work_dev: swn_spectral_work_bytes, scratch of either call.  Results are
+ * bit-identical from call to call.  SWN_E_BADARG: a null pointer, n_sizes outside [1, SWN_SPECTRAL_MAX_SIZES], a size that
+ * is not a multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT], or len <= size / 2 (the size queries return 0 then). */
+#define SWN_SPECTRAL_MAX_SIZES 32
+#define SWN_SPECTRAL_MAX_FFT 2048
+size_t swn_spectral_work_bytes(int rows, int len, const int* sizes, int n_sizes);
+size_t swn_spectral_state_bytes(int rows, int len, const int* sizes, int n_sizes);
+int    swn_spectral_forward(const float* samples_dev, const float* targets_dev, int rows, int len, const int* sizes,
+                            int n_sizes, const float* tables_dev, float* l1_dev, float* lsd_dev,
+                            unsigned char* state_dev, void* work_dev, void* stream);
+int    swn_spectral_backward(const float* g_dev, const unsigned char* state_dev, int rows, int len, const int* sizes,
+                             int n_sizes, const float* tables_dev, float* grad_dev, void* work_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,7 @@ POSTFILTER_RESET = 1                           # SWN_POSTFILTER_RESET
 POSTFILTER_MAX_ORDER = 62                      # SWN_POSTFILTER_MAX_ORDER
 POSTFILTER_MAX_TAPS = 256                      # SWN_POSTFILTER_MAX_TAPS
 POSTFILTER_MULAW_ENTRIES = 256                 # SWN_POSTFILTER_MULAW_ENTRIES
+SPECTRAL_MAX_SIZES, SPECTRAL_MAX_FFT = 32, 2048   # SWN_SPECTRAL_MAX_SIZES, SWN_SPECTRAL_MAX_FFT
 
 
 def desc_from_cfg(cfg: NetConfig) -> NetDesc:
@@ -141,6 +142,12 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "swn_laplace_head": (c_int, [POINTER(NetDesc), c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "swn_spectral_work_bytes": (c_size_t, [c_int, c_int, POINTER(c_int), c_int]),
+    "swn_spectral_state_bytes": (c_size_t, [c_int, c_int, POINTER(c_int), c_int]),
+    "swn_spectral_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p]),
+    "swn_spectral_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
 }
 
 

@@ -28,6 +28,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.laplace_head(raw, desc, clip)                    -> (mu, b, logb, a, b_clip, logb_clip, below_floor)
     torch.ops.swn.stack_backward(packed, aux, cond, fe_work, audio, fwd_work, grad_raw, desc, precision) -> grad_packed
     torch.ops.swn.laplace_head_backward(raw, gmu?, gb?, glogb?, ga?, gb_clip?, glogb_clip?, desc) -> grad_raw
+    torch.ops.swn.spectral_loss(samples, targets, tables, sizes, keep_state) -> (l1, lsd, state)
+    torch.ops.swn.spectral_loss_backward(grad_l1, state, tables, sizes, length) -> grad_samples
 """
 from __future__ import annotations
 
@@ -723,6 +725,112 @@ def backward_bf16_supported(desc: List[int], batch: int, n_frames: int) -> bool:
     return _lib.lib().swn_backward_bf16_work_floats(ctypes.byref(_desc(desc)), batch, n_frames) > 0
 
 
+# ------------------------------------------------------------------------------------------ multi-resolution STFT loss
+def _spectral_sizes(sizes: Sequence[int]):
+    return (ctypes.c_int * len(sizes))(*[int(n) for n in sizes])
+
+
+def _spectral_check(rows: int, length: int, sizes: Sequence[int]) -> None:
+    """the argument rules of swn_spectral_* as messages (the library itself answers SWN_E_BADARG)."""
+    if not 1 <= len(sizes) <= _lib.SPECTRAL_MAX_SIZES:
+        raise RuntimeError(f"spectral_loss takes 1 to {_lib.SPECTRAL_MAX_SIZES} FFT sizes, got {len(sizes)}")
+    for n in sizes:
+        if n % 32 != 0 or not 32 <= n <= _lib.SPECTRAL_MAX_FFT:
+            raise RuntimeError(f"FFT size {n} is not a multiple of 32 in [32, {_lib.SPECTRAL_MAX_FFT}]")
+        if length <= n // 2:
+            raise RuntimeError(f"FFT size {n} needs signals longer than {n // 2} samples (reflect padding), got {length}")
+    if rows < 1:
+        raise RuntimeError("spectral_loss needs at least one row")
+
+
+def spectral_loss_impl(samples: torch.Tensor, targets: torch.Tensor, tables: torch.Tensor, sizes: List[int],
+                       keep_state: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """samples, targets (R, T) -> l1 (R, K), lsd (R, K) per FFT size (swn_spectral_forward) and, with keep_state, the byte
+    state spectral_loss_backward reads (empty otherwise).  tables: cos and Hann tables of the K sizes (spectral.py)."""
+    Lb = _lib.lib()
+    _need_cuda(samples, "the signals")
+    dev = samples.device
+    if samples.dim() != 2 or samples.shape != targets.shape:
+        raise RuntimeError(f"spectral_loss needs samples and targets of one shape (R, T), got {tuple(samples.shape)} and "
+                           f"{tuple(targets.shape)}")
+    R, T = samples.shape
+    _spectral_check(R, T, sizes)
+    if tables.numel() != 2 * sum(sizes):
+        raise RuntimeError(f"tables hold {tables.numel()} floats, the sizes need {2 * sum(sizes)}")
+    samples = samples.to(dev, torch.float32).contiguous()
+    targets = targets.to(dev, torch.float32).contiguous()
+    tables = tables.to(dev, torch.float32).contiguous()
+    K, sz = len(sizes), _spectral_sizes(sizes)
+    l1 = torch.empty((R, K), dtype=torch.float32, device=dev)
+    lsd = torch.empty((R, K), dtype=torch.float32, device=dev)
+    state = torch.empty(Lb.swn_spectral_state_bytes(R, T, sz, K) if keep_state else 0, dtype=torch.uint8, device=dev)
+    work = torch.empty(Lb.swn_spectral_work_bytes(R, T, sz, K), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _lib.check(Lb.swn_spectral_forward(_ptr(samples), _ptr(targets), R, T, sz, K, _ptr(tables), _ptr(l1), _ptr(lsd),
+                                           _ptr(state if keep_state else None), _ptr(work), _stream(dev)), "spectral_forward")
+    return l1, lsd, state
+
+
+spectral_loss = custom_op("swn::spectral_loss", mutates_args=())(spectral_loss_impl)
+
+
+@spectral_loss.register_fake
+def _(samples, targets, tables, sizes, keep_state):
+    R, T = samples.shape
+    _spectral_check(R, T, sizes)
+    K, sz = len(sizes), _spectral_sizes(sizes)
+    nb = _lib.lib().swn_spectral_state_bytes(R, T, sz, K) if keep_state else 0
+    return (samples.new_empty((R, K), dtype=torch.float32), samples.new_empty((R, K), dtype=torch.float32),
+            samples.new_empty(nb, dtype=torch.uint8))
+
+
+def spectral_loss_backward_impl(grad_l1: torch.Tensor, state: torch.Tensor, tables: torch.Tensor, sizes: List[int],
+                                length: int) -> torch.Tensor:
+    """d sum(grad_l1 * l1) / d samples, (R, T), from the state of a spectral_loss(keep_state=True) call
+    (swn_spectral_backward)."""
+    Lb = _lib.lib()
+    _need_cuda(state, "the forward state")
+    dev = state.device
+    R, K = grad_l1.shape
+    _spectral_check(R, length, sizes)
+    sz = _spectral_sizes(sizes)
+    if K != len(sizes) or state.numel() != Lb.swn_spectral_state_bytes(R, length, sz, K):
+        raise RuntimeError("spectral_loss_backward: grad_l1 / state do not belong to these sizes and this length")
+    g = grad_l1.to(dev, torch.float32).contiguous()
+    grad = torch.empty((R, length), dtype=torch.float32, device=dev)
+    work = torch.empty(Lb.swn_spectral_work_bytes(R, length, sz, K), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _lib.check(Lb.swn_spectral_backward(_ptr(g), _ptr(state.contiguous()), R, length, sz, K, _ptr(tables.contiguous()),
+                                            _ptr(grad), _ptr(work), _stream(dev)), "spectral_backward")
+    return grad
+
+
+spectral_loss_backward = custom_op("swn::spectral_loss_backward", mutates_args=())(spectral_loss_backward_impl)
+
+
+@spectral_loss_backward.register_fake
+def _(grad_l1, state, tables, sizes, length):
+    return grad_l1.new_empty((grad_l1.shape[0], length), dtype=torch.float32)
+
+
+class SpectralLossFunction(torch.autograd.Function):
+    """l1, lsd = SpectralLossFunction.apply(samples, targets, tables, sizes): l1 differentiable in the samples, lsd a
+    reported figure; like the stack Functions of nets/_autograd.py it calls the _impl functions directly."""
+
+    @staticmethod
+    def forward(ctx, samples, targets, tables, sizes):
+        l1, lsd, state = spectral_loss_impl(samples, targets, tables, list(sizes), True)
+        ctx.save_for_backward(state, tables)
+        ctx.sizes, ctx.length = list(sizes), samples.shape[1]
+        ctx.mark_non_differentiable(lsd)
+        return l1, lsd
+
+    @staticmethod
+    def backward(ctx, g_l1, _g_lsd):
+        state, tables = ctx.saved_tensors
+        return spectral_loss_backward_impl(g_l1, state, tables, ctx.sizes, ctx.length), None, None, None
+
+
 OP_NAMES = ("pack_params", "frontend", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk", "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
-            "laplace_head_backward", "stack_backward", "stack_backward_bf16")
+            "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward")

@@ -215,7 +215,7 @@ def _stft(x: torch.Tensor, n_fft: int, window: torch.Tensor) -> torch.Tensor:
 
 def batch_loss(model, criterion_laplace, criterion_lsd, batch_h, batch_x, target, x_prob, feat_len, h_ss,
                fft_facts: Sequence[int], hann_win: Sequence[torch.Tensor], do: bool = True,
-               eps_generator: Optional[torch.Generator] = None, eps_on_device: bool = False):
+               eps_generator: Optional[torch.Generator] = None, eps_on_device: bool = False, spectral_loss=None):
     """forward + loss of one chunk (train_cswnv...py:744-868): returns
     (batch_loss, batch_loss_laplace, batch_loss_lsd or None, batch_loss_err).
 
@@ -223,7 +223,9 @@ def batch_loss(model, criterion_laplace, criterion_lsd, batch_h, batch_x, target
     loss = mean_j NLL_j + mean_j mean_fft L1(STFT(sample_j), STFT(target_j)) with
     sample = mu - b_noclip * sign(eps) * log1p(-2|eps|), eps ~ U(-0.4999, 0.5): drawn on the HOST generator by default (what
     the g6_trainstep fixtures replay), with eps_on_device=True on the model's device like the reference (the driver does
-    that whenever its dropout masks are device-drawn: a host draw is a pageable host->device copy per segment)."""
+    that whenever its dropout masks are device-drawn: a host draw is a pageable host->device copy per segment).
+    spectral_loss: None = the spectral terms through `torch.stft` and autograd; a `spectral.MultiResolutionSTFTLoss` over
+    `fft_facts` = the same (R, K) terms from the HIP operator (one forward and one backward launch pair per chunk)."""
     seg, lpc, rf = model.seg, model.lpc, model.receptive_field
     if lpc > 0:
         mus, bs_noclip, bs, log_bs, ass = model(batch_h, batch_x, do=do, clip=True)
@@ -258,15 +260,20 @@ def batch_loss(model, criterion_laplace, criterion_lsd, batch_h, batch_x, target
         """samples / targets: lists of R equally long signals -> ((l1_mean[R], l1_count[R]), (lsd_mean[R], lsd_count[R]))
         or (None, None) when no FFT size applies"""
         R = len(samples)
-        sig = torch.stack(list(samples) + list(targets))                      # (2R, T)
         l1, lsd = [], []
-        for n_fft, win in zip(fft_facts, hann_win):
-            if feat_len > n_fft // 2:
-                sp = _stft(sig, n_fft, win)                                   # (2R, F, N, 2)
-                so, st = sp[:R], sp[R:]
-                l1.append(torch.abs(so - st).mean(dim=(1, 2, 3)))             # LSDloss(LSD=False, L2=False)
-                pow_x, pow_y = torch.sum(so ** 2, -1), torch.sum(st ** 2, -1)
-                lsd.append(torch.sqrt(torch.mean((10 * (torch.log10(pow_x) - torch.log10(pow_y))) ** 2, 1)).mean(1))   # LSDloss()
+        if spectral_loss is not None:
+            if spectral_loss.sizes_for(feat_len):
+                l1_rk, lsd_rk = spectral_loss(samples, targets, feat_len)     # (R, K) each, the same K terms as below
+                l1, lsd = list(l1_rk.unbind(1)), list(lsd_rk.unbind(1))
+        else:
+            sig = torch.stack(list(samples) + list(targets))                  # (2R, T)
+            for n_fft, win in zip(fft_facts, hann_win):
+                if feat_len > n_fft // 2:
+                    sp = _stft(sig, n_fft, win)                               # (2R, F, N, 2)
+                    so, st = sp[:R], sp[R:]
+                    l1.append(torch.abs(so - st).mean(dim=(1, 2, 3)))         # LSDloss(LSD=False, L2=False)
+                    pow_x, pow_y = torch.sum(so ** 2, -1), torch.sum(st ** 2, -1)
+                    lsd.append(torch.sqrt(torch.mean((10 * (torch.log10(pow_x) - torch.log10(pow_y))) ** 2, 1)).mean(1))   # LSDloss()
         if not l1:
             return None, None
 
@@ -379,6 +386,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--aux_dilation_size", default=2, type=int)
     p.add_argument("--upsampling_factor", default=110, type=int)
     p.add_argument("--n_fft_facts", default=17, type=int)
+    p.add_argument("--spectral_loss", default="torch", choices=("torch", "hip"),
+                   help="spectral terms of the loss: torch.stft + autograd per FFT size, or the HIP operator (spectral.py)")
     p.add_argument("--string_path", default="/feat_org_lf0", type=str)
     p.add_argument("--lr", default=1e-4, type=float)
     p.add_argument("--batch_size", default=8800, type=int)
@@ -491,6 +500,10 @@ def _run(args) -> int:
     fft_facts = fft_sizes(args.n_fft_facts)
     hann_win = [torch.hann_window(n).cuda() for n in fft_facts]
     logging.info(fft_facts)
+    spectral_loss = None
+    if args.spectral_loss == "hip":
+        from .spectral import MultiResolutionSTFTLoss
+        spectral_loss = MultiResolutionSTFTLoss(fft_facts, dev)
     if args.resume is not None:
         np.random.set_state(checkpoint["numpy_random_state"])
         torch.set_rng_state(checkpoint["torch_random_state"])
@@ -523,7 +536,8 @@ def _run(args) -> int:
                 with torch.no_grad():
                     bh, bx, trg, xp, flen = slice_chunk(model, x, h, h_bs, x_bs, h_ss, x_ss)
                     _, l_lap, l_lsd, l_err = batch_loss(model, criterion_laplace, criterion_lsd, bh, bx, trg, xp, flen,
-                                                        h_ss, fft_facts, hann_win, do=False, eps_on_device=dev_rng)
+                                                        h_ss, fft_facts, hann_win, do=False, eps_on_device=dev_rng,
+                                                        spectral_loss=spectral_loss)
                 ev_lap.append(l_lap.item()); ev_err.append(l_err.item())
                 if l_lsd is not None:
                     ev_lsd.append(l_lsd.item())
@@ -558,7 +572,8 @@ def _run(args) -> int:
         tf, ts = h.shape[0], x.shape[0]
         bh, bx, trg, xp, flen = slice_chunk(model, x, h, h_bs, x_bs, h_ss, x_ss)
         loss, l_lap, l_lsd, l_err = batch_loss(model, criterion_laplace, criterion_lsd, bh, bx, trg, xp, flen, h_ss,
-                                               fft_facts, hann_win, do=True, eps_on_device=dev_rng)
+                                               fft_facts, hann_win, do=True, eps_on_device=dev_rng,
+                                               spectral_loss=spectral_loss)
         optimizer.zero_grad()
         loss.backward()
         optimizer.step()
