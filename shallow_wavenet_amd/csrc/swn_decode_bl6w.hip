@@ -251,7 +251,8 @@ __device__ __forceinline__ void older_b3(float* lds, const float (&w)[L][2][16],
 }
 
 // ---- group B: out_skip, slice by slice.  Thread (r, hp): rows r and r + 64 over inputs 16 mm + 4 hp .. + 3 of the slice (the
-//      lane-tiled global copy wsk2 of the symmetric kernel: 1 KiB contiguous per wave instruction); weights issued a phase ahead.
+//      lane-tiled global copy wsk2 of the symmetric kernel: 1 KiB contiguous per wave instruction); weights issued a phase ahead
+//      (slice 0 whole, at the start of the step; the others by skip_roll_b).
 // (`step0` is an opaque zero the caller renews every step: the addresses are loop-invariant, and hoisted out of the step loop the
 //  six slices - 192 registers - would be kept resident beside the 160 weight registers)
 template <int LAYER>
@@ -263,18 +264,36 @@ __device__ __forceinline__ void skip_issue_b(__amdgpu_buffer_rsrc_t wsk2, float4
         for (int mm = 0; mm < 4; ++mm)
             wsl[ps * 4 + mm] = buf_ld4(wsk2, (unsigned)((r + 64 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 4 + mm) * S) * 64u + step0);
 }
+// the rolling request of a layer phase: slice LAYER - 1 is consumed half by half (inputs 16 mm .., mm = 0, 1, then 2, 3, both rows),
+// and behind each half the same half of slice LAYER is requested into the four float4 it has just freed (a second buffer does
+// not fit beside the 160 weight registers).  The four waves' 32 KB of requests then no longer queue at the end of the phase, in
+// front of the barrier: the first half leaves behind the phase's first sixteen multiply-adds.  The order of the multiply-adds inside each sacc
+// chain is that of a whole-slice pass.  (Measured per launch of 66 000 steps: whole slice behind its consumption 208.0 ms,
+// halves 188.5 ms, quarters 200.6 ms, eighths 226.1 ms.)
 template <class T, int LAYER>
-__device__ __forceinline__ void skip_consume_b(const float* lds, const float4 (&wsl)[8], float (&sacc)[2], const int tb) {
-    const int hp = tb & 3;
+__device__ __forceinline__ void skip_roll_b(const float* lds, __amdgpu_buffer_rsrc_t wsk2, float4 (&wsl)[8], float (&sacc)[2], const int tb,
+                                            const unsigned step0) {
+    static_assert(LAYER >= 1 && LAYER < L, "slice LAYER - 1 in flight, slice LAYER to request");
+    const int r = tb >> 2, hp = tb & 3;
 #pragma unroll
-    for (int mm = 0; mm < 4; ++mm) {
-        const float4 x = *reinterpret_cast<const float4*>(lds + T::o_hcat + LAYER * H + 16 * mm + 4 * hp);
+    for (int hf = 0; hf < 2; ++hf) {
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps) {
-            const float4 w = wsl[ps * 4 + mm];
-            sacc[ps] = fmaf(w.x, x.x, sacc[ps]); sacc[ps] = fmaf(w.y, x.y, sacc[ps]);
-            sacc[ps] = fmaf(w.z, x.z, sacc[ps]); sacc[ps] = fmaf(w.w, x.w, sacc[ps]);
+        for (int mm = 2 * hf; mm < 2 * hf + 2; ++mm) {
+            const float4 x = *reinterpret_cast<const float4*>(lds + T::o_hcat + (LAYER - 1) * H + 16 * mm + 4 * hp);
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps) {
+                const float4 w = wsl[ps * 4 + mm];
+                sacc[ps] = fmaf(w.x, x.x, sacc[ps]); sacc[ps] = fmaf(w.y, x.y, sacc[ps]);
+                sacc[ps] = fmaf(w.z, x.z, sacc[ps]); sacc[ps] = fmaf(w.w, x.w, sacc[ps]);
+            }
         }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int mm = 2 * hf; mm < 2 * hf + 2; ++mm)
+#pragma unroll
+            for (int ps = 0; ps < 2; ++ps)
+                wsl[ps * 4 + mm] = buf_ld4(wsk2, (unsigned)((r + 64 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 4 + mm) * S) * 64u + step0);
+        __builtin_amdgcn_sched_barrier(0);
     }
     // pin the partial sums to this phase: only the end of the step uses them, and the optimiser otherwise sinks all six slices'
     // multiply-adds down to that use - with their 48 operand registers per slice live until then (238 registers spilled)
@@ -484,11 +503,15 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
 #ifdef SWN_STAMP
     // diagnostic build only (tools/stamp_decode_w.py): per phase, the cycles each group's first wave WORKS between two barriers
     // (barrier waits excluded) leave through the `heads` debug buffer: [0..8) group A (phase 0 = the previous step's tail + layer
-    // 0), [8] the tail's share of phase 0, [9] A's whole step, [10..18) group B
-    unsigned long long tw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tstep = 0, tlast = 0, tbeg = 0;
+    // 0), [8] the tail's share of phase 0, [9] A's whole step, [10..18) group B, [20..26) of group B's phases L1 .. L5 and
+    // skip-fin the cycles from the barrier's release until the first out_skip weight register of the slice in flight has landed
+    unsigned long long tw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tv[6] = {0, 0, 0, 0, 0, 0}, tstep = 0, tlast = 0, tbeg = 0;
 #define SWN_BAR(k) { tw[k] += __builtin_amdgcn_s_memtime() - tlast; lds_barrier(); tlast = __builtin_amdgcn_s_memtime(); }
+    // (the empty asm uses the register, so the compiler places the vmcnt wait of the slice's oldest request in front of it)
+#define SWN_WAIT_STAMP(k) { asm volatile("" :: "v"(wsl[0].x)); tv[k] += __builtin_amdgcn_s_memtime() - tlast; }
 #else
 #define SWN_BAR(k) lds_barrier();
+#define SWN_WAIT_STAMP(k)
 #endif
     // one layer phase: group A runs the chain, group B prepares position q + 1 (and, during generation, accumulates out_skip)
     // (OLD: the first layer whose older-tap product for position q + 1 group B forms in this phase, -1 = none; NOLD: how many,
@@ -498,11 +521,11 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
                                           LAYER == 0 ? (X0) : lds + T::o_ring + T::ring_off(LAYER) +                   \
                                                                   (q & (T::ring_len(LAYER) - 1)) * H);                 \
     else {                                                                                                             \
-        if (GEN) {   /* the slice in flight is consumed BEFORE the next one is requested (both live at once are 64 registers  */ \
-                     /* beside the 160 of the weights); the request then flies under the older-tap product and the barrier    */ \
-            if (LAYER > 0) skip_consume_b<T, (LAYER > 0 ? LAYER - 1 : 0)>(lds, wsl, sacc, tg);                           \
-            __builtin_amdgcn_sched_barrier(0);                                                                         \
-            skip_issue_b<LAYER>(wsk2, wsl, tg, step0);                                                                 \
+        if (GEN) {   /* slice 0 is requested whole at the start of the step; every later slice rolls in, half by half, behind */ \
+                     /* the multiply-adds that free its registers (both slices live at once are 64 registers beside the 160   */ \
+                     /* of the weights)                                                                                       */ \
+            if (LAYER == 0) skip_issue_b<0>(wsk2, wsl, tg, step0);                                                     \
+            else { SWN_WAIT_STAMP(LAYER > 0 ? LAYER - 1 : 0) skip_roll_b<T, (LAYER > 0 ? LAYER : 1)>(lds, wsk2, wsl, sacc, tg, step0); } \
             __builtin_amdgcn_sched_barrier(0);                                                                         \
         }                                                                                                              \
         if (OLD >= 0 && NOLD == 1) older_b<T, (OLD >= 0 ? OLD : 0)>(lds, wreg[OLD >= 0 ? OLD : 0], q + 1, tg);           \
@@ -554,7 +577,7 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
         SWN_PHASE(0, true, 3, 3, x0) SWN_PHASE(1, true, -1, 0, x0) SWN_PHASE(2, true, -1, 0, x0) SWN_PHASE(3, true, -1, 0, x0)
         SWN_PHASE(4, true, -1, 0, x0) SWN_PHASE(5, true, -1, 0, x0)
         // out_skip: the last slice and the reduction (group B); group A has nothing on this phase
-        if constexpr (!grpA) skip_last_b<T>(lds, wsl, sacc, tg);
+        if constexpr (!grpA) { SWN_WAIT_STAMP(5) skip_last_b<T>(lds, wsl, sacc, tg); }
         // the next step's deviate (classic mode: one lane of wave 1, a ~130-instruction log1p chain) where group A has no work:
         // in the out_1 phase it made wave 1 the last of the group to reach the barrier
         noise_ahead(i + 1);
@@ -665,11 +688,13 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
     }
 #undef SWN_PHASE
 #undef SWN_BAR
+#undef SWN_WAIT_STAMP
 #ifdef SWN_STAMP
     if ((tid == 0 || tid == NG) && b == 0 && a.heads) {
         float* h = a.heads + (tid == 0 ? 0 : 10);
         for (int k = 0; k < 9; ++k) h[k] = (float)((double)tw[k] / (double)a.n_steps);
         if (tid == 0) h[9] = (float)((double)tstep / (double)a.n_steps);
+        else for (int k = 0; k < 6; ++k) h[10 + k] = (float)((double)tv[k] / (double)a.n_steps);
     }
 #endif
 }
