@@ -434,7 +434,9 @@ int    swn_laplace_head_backward(const swn_net_desc* d, const float* out_dev, in
  * STFT_n = torch.stft(x, n, window=hann_window(n)) with its defaults (hop n/4, reflect-centred, one-sided, 1 + len / hop
  * frames).  tables_dev: per size, in the order of `sizes`, cos(2 pi m / n) for m < n followed by the periodic Hann window
  * (2 n floats each).  state_dev (swn_spectral_state_bytes) receives what swn_spectral_backward needs, one byte per
- * (row, frame, bin); NULL (evaluation) writes none.  The backward gives grad_dev[rows][len] = d sum(g * l1) / d samples for
+ * (row, frame, bin); NULL (evaluation) writes none.  Its layout: the sizes in call order, per size [row][frame][bin], each
+ * byte the two signs of STFT_n(sample - target) at that entry - bits 0-1 the real part, bits 2-3 the imaginary part, as
+ * 1 = positive, 2 = negative, 0 = exactly zero; bits 4-7 are 0.  The backward gives grad_dev[rows][len] = d sum(g * l1) / d samples for
  * g_dev[rows][n_sizes]; targets get no gradient.  work_dev: swn_spectral_work_bytes, scratch of either call.  Results are
  * bit-identical from call to call.  SWN_E_BADARG: a null pointer, n_sizes outside [1, SWN_SPECTRAL_MAX_SIZES], a size that
  * is not a multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT], or len <= size / 2 (the size queries return 0 then). */
