@@ -15,9 +15,7 @@
 // The "true zero" left padding of the reference prologue is reproduced by zero-initialised
 // rings: a slot that would hold a negative position has not been written yet.
 #include <hip/hip_runtime.h>
-#include "swn_geom.hpp"
-#include "swn_noise.hpp"
-#include "swn_pool.hpp"
+#include "swn_decode_internal.hpp"
 
 namespace {
 
@@ -393,37 +391,33 @@ int generic_run(DecArgs& a, bool stream, hipStream_t st) {
     }
 }
 
+enum { KSEL_GENERIC = 1, KSEL_BL6W = 2, KSEL_STEPPED = 3, KSEL_BL6 = 6 };
+
+// the kernel that variant `variant` of swn_decode, swn_decode_chunk and swn_decode_pool_chunk runs for (net, batch): KSEL_*, or a
+// negative SWN_E_*.  0 = the best one that applies, 2 / 6 = the BL6 class only (6: the symmetric kernel, whatever the net - A/B
+// and parity runs), 3 = the stepped chain only, 1 = the generic kernel
+int resolve_kernel(const swn_net_desc* d, int batch, int variant) {
+    SwnGeom g;
+    const int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (batch < 1) return SWN_E_BADARG;
+    if ((variant == 0 || variant == 2) && swn_decode_bl6w_session_floats(d) > 0) return KSEL_BL6W;
+    if (variant == 0 || variant == 2 || variant == 6) {
+        if (swn_decode_bl6_session_floats(d) > 0) return KSEL_BL6;
+        if (variant != 0) return SWN_E_UNSUPPORTED;
+    }
+    if (variant < 0 || variant > 3) return SWN_E_BADARG;   // (4 and 5, the cohort and cluster experiments of ABI 2, are retired)
+    // large geometries (REF6: MBs of weights per step) run one launch per phase over many CUs
+    const bool big = (size_t)g.L * 2 * g.H * g.K * g.Hp >= (size_t)256 * 1024;
+    if (variant == 3 || (variant == 0 && big)) {
+        if (swn_decode_stepped_supported(d, batch)) return KSEL_STEPPED;
+        if (variant == 3) return SWN_E_UNSUPPORTED;
+    }
+    if (generic_lds(g) > 160 * 1024) return SWN_E_UNSUPPORTED;
+    return KSEL_GENERIC;
+}
+
 }  // namespace
-
-// defined in swn_decode_bl6.hip; returns SWN_E_UNSUPPORTED when the geometry is not a BL6-class one
-extern "C" int swn_decode_bl6_try(const swn_net_desc* d, const float* packed, const float* cond,
-                                  int batch, int n_frames, int n_steps, const SwnNoise* nz,
-                                  const void* forced, const void* seed, void* out, float* heads, void* stream);
-
-// defined in swn_decode_bl6w.hip: the wave-specialised form for the single-sample Laplace nets of that class
-extern "C" int swn_decode_bl6w_try(const swn_net_desc* d, const float* packed, const float* cond,
-                                   int batch, int n_frames, int n_steps, const SwnNoise* nz,
-                                   const void* forced, const void* seed, void* out, float* heads, void* stream);
-
-// streamed forms of the three (swn_decode_chunk): session sizes per utterance (0 = the kernel does not apply) and one chunk
-extern "C" size_t swn_decode_bl6_session_floats(const swn_net_desc* d);
-extern "C" size_t swn_decode_bl6w_session_floats(const swn_net_desc* d);
-extern "C" int swn_decode_bl6_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                    int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
-                                    const void* seed, float* sess, void* out, float* heads, void* stream);
-extern "C" int swn_decode_bl6w_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                     int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
-                                     const void* seed, float* sess, void* out, float* heads, void* stream);
-
-// defined in swn_decode_stepped.hip
-extern "C" size_t swn_decode_stepped_state_floats(const swn_net_desc* d, int batch);
-extern "C" int swn_decode_stepped_supported(const swn_net_desc* d, int batch);
-extern "C" int swn_decode_stepped_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                        int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
-                                        const void* seed, float* sess, void* out, float* heads, void* stream);
-extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                  int n_steps, const SwnNoise* nz, const void* forced, const void* seed, float* state,
-                                  void* out, float* heads, void* stream);
 
 extern "C" size_t swn_decode_state_floats(const swn_net_desc* d, int batch) {
     SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1) return 0;
@@ -443,29 +437,20 @@ extern "C" int swn_decode(const swn_net_desc* d, const float* packed, const floa
     if (n_steps == 0) return SWN_OK;                       // nothing to generate (empty buffers may be null)
     if (!packed || !cond || !out) return SWN_E_BADARG;
     if ((long)n_steps * a.g.seg > (long)n_frames * a.g.U) return SWN_E_BADARG;   // conditioning too short
-    SwnNoise nz;
-    nz.ptr = io->noise_dev; nz.dump = io->noise_out_dev;
-    nz.key0 = (uint32_t)(io->rng_seed & 0xffffffffu); nz.key1 = (uint32_t)(io->rng_seed >> 32); nz.utt0 = io->rng_utt0; nz.ids = io->rng_utt_ids_dev;
+    const SwnNoise nz = swn_noise_of(io);
     const void* forced = io->forced_dev;
     const void* seed = io->seed_dev;
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();   // drop stale errors of earlier runtime calls
-    if (variant == 0 || variant == 2) {        // BL6 class: the wave-specialised kernel where it applies, else the symmetric one
-        rc = swn_decode_bl6w_try(d, packed, cond, batch, n_frames, n_steps, &nz, forced, seed, out, heads, stream_);
-        if (rc != SWN_E_UNSUPPORTED) return rc;
-    }
-    if (variant == 0 || variant == 2 || variant == 6) {     // 6 = the symmetric BL6 kernel, whatever the net (A/B and parity runs)
-        rc = swn_decode_bl6_try(d, packed, cond, batch, n_frames, n_steps, &nz, forced, seed, out, heads, stream_);
-        if (rc != SWN_E_UNSUPPORTED || variant != 0) return rc;
-    }
-    if (!state) return SWN_E_BADARG;
-    // large geometries (REF6: MBs of weights per step) run one launch per phase over many CUs
-    const bool big = (size_t)a.g.L * 2 * a.g.H * a.g.K * a.g.Hp >= (size_t)256 * 1024;
-    if (variant < 0 || variant > 3) return SWN_E_BADARG;   // (4 and 5, the cohort and cluster experiments of ABI 2, are retired)
-    if (variant == 3 || (variant == 0 && big)) {
-        rc = swn_decode_stepped(d, packed, cond, batch, n_frames, n_steps, &nz, forced, seed, state, out, heads, stream_);
-        if (rc != SWN_E_UNSUPPORTED || variant == 3) return rc;
-    }
+    const int k = resolve_kernel(d, batch, variant);
+    if (k == KSEL_BL6W) return swn_decode_bl6w_try(d, packed, cond, batch, n_frames, n_steps, &nz, forced, seed, out, heads, stream_);
+    if (k == KSEL_BL6) return swn_decode_bl6_try(d, packed, cond, batch, n_frames, n_steps, &nz, forced, seed, out, heads, stream_);
+    // the BL6 kernels keep their state on chip; every other kernel, and every refusal but that of a variant that asks for the
+    // BL6 class alone, wants the caller's state buffer first
+    if (!state && variant != 2 && variant != 6) return SWN_E_BADARG;
+    if (k < 0) return k;
+    if (k == KSEL_STEPPED)
+        return swn_decode_stepped(d, packed, cond, batch, n_frames, n_steps, &nz, forced, seed, state, out, heads, stream_);
     swn_make_layout(&a.g, &a.y);
     a.packed = packed; a.cond = cond; a.nz = nz; a.forced = forced; a.seed = seed; a.state = state;
     a.out = out; a.heads = heads; a.B = batch; a.Tf = n_frames; a.n_steps = n_steps;
@@ -475,33 +460,6 @@ extern "C" int swn_decode(const swn_net_desc* d, const float* packed, const floa
 }
 
 // ---- streamed decode ---------------------------------------------------------------------------------------------
-namespace {
-
-enum { KSEL_GENERIC = 1, KSEL_BL6W = 2, KSEL_STEPPED = 3, KSEL_BL6 = 6 };
-
-// the kernel swn_decode(variant) runs for (net, batch): KSEL_*, or a negative SWN_E_* (the same decisions in the same order)
-int resolve_kernel(const swn_net_desc* d, int batch, int variant) {
-    SwnGeom g;
-    const int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    if (batch < 1) return SWN_E_BADARG;
-    if ((variant == 0 || variant == 2) && swn_decode_bl6w_session_floats(d) > 0) return KSEL_BL6W;
-    if (variant == 0 || variant == 2 || variant == 6) {
-        if (swn_decode_bl6_session_floats(d) > 0) return KSEL_BL6;
-        if (variant != 0) return SWN_E_UNSUPPORTED;
-    }
-    if (variant < 0 || variant > 3) return SWN_E_BADARG;   // 4 and 5 retired
-    const bool big = (size_t)g.L * 2 * g.H * g.K * g.Hp >= (size_t)256 * 1024;
-    if (variant == 3 || (variant == 0 && big)) {
-        if (swn_decode_stepped_supported(d, batch)) return KSEL_STEPPED;
-        if (variant == 3) return SWN_E_UNSUPPORTED;
-    }
-    if (generic_lds(g) > 160 * 1024) return SWN_E_UNSUPPORTED;
-    return KSEL_GENERIC;
-}
-
-}  // namespace
-
 extern "C" int swn_decode_resolve_variant(const swn_net_desc* d, int batch, int variant) {
     const int k = resolve_kernel(d, batch, variant);
     if (k < 0) return k;
@@ -536,9 +494,7 @@ extern "C" int swn_decode_chunk(const swn_net_desc* d, const float* packed, cons
     const int k = resolve_kernel(d, batch, variant);
     if (k < 0) return SWN_E_BADARG;
     if (n_steps == 0 && !begin) return SWN_OK;             // nothing to generate, the session stays as it is
-    SwnNoise nz;
-    nz.ptr = io->noise_dev; nz.dump = io->noise_out_dev;
-    nz.key0 = (uint32_t)(io->rng_seed & 0xffffffffu); nz.key1 = (uint32_t)(io->rng_seed >> 32); nz.utt0 = io->rng_utt0; nz.ids = io->rng_utt_ids_dev;
+    const SwnNoise nz = swn_noise_of(io);
     const int resume = begin ? 0 : 1;
     (void)hipGetLastError();
     if (k == KSEL_BL6W)
@@ -561,14 +517,6 @@ extern "C" int swn_decode_chunk(const swn_net_desc* d, const float* packed, cons
 }
 
 // ---- decode pool ---------------------------------------------------------------------------------------------------
-// defined in swn_decode_bl6.hip / swn_decode_bl6w.hip: one pool launch of those kernels over the checked entry table
-extern "C" int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries,
-                                   int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
-                                   void* stream);
-extern "C" int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries,
-                                    int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
-                                    void* stream);
-
 extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed, int capacity,
                                      const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
                                      float* session, void* out, float* heads, int variant, void* stream_) {
@@ -600,9 +548,7 @@ extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed,
     if (k == KSEL_STEPPED || variant == 3) return SWN_E_UNSUPPORTED;   // one launch per phase for all utterances at one step
     if (k < 0) return SWN_E_BADARG;
     if (!work) return SWN_OK;                              // every slot stays as it is
-    SwnNoise nz;
-    nz.ptr = nullptr; nz.dump = io->noise_out_dev;
-    nz.key0 = (uint32_t)(io->rng_seed & 0xffffffffu); nz.key1 = (uint32_t)(io->rng_seed >> 32); nz.utt0 = io->rng_utt0; nz.ids = io->rng_utt_ids_dev;
+    const SwnNoise nz = swn_pool_noise_of(io);
     (void)hipGetLastError();
     if (k == KSEL_BL6W)
         return swn_decode_bl6w_pool(d, packed, &t, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);

@@ -16,44 +16,12 @@
 //   * conditioning: the current and next frame of the hoisted in_x product sit in LDS, the
 //     rank-1 upsampler is one fma per gate input (cswnv_shift1.py:37-65,276).
 // 9 s_barriers per generated step (10 for softmax).
-#include <hip/hip_runtime.h>
-#include "swn_geom.hpp"
-#include "swn_noise.hpp"
-#include "swn_pool.hpp"
+#include "swn_decode_bl6_common.hpp"
+#include "swn_decode_internal.hpp"
 
 namespace {
 
-constexpr int NT = 512;
-constexpr int H = 64;
-constexpr int L = 6;
-constexpr int RF = 64;
-#ifdef SWN_STAMP
-constexpr bool HEADS_ON = false;
-#else
-constexpr bool HEADS_ON = true;
-#endif
-
-struct B6Args {
-    const float* P;
-    SwnLayout y;
-    const float* cond;
-    const float* noise;            // classic mode: the host-drawn stream
-    const void* forced;
-    void* out;
-    float* heads;
-    int B, Tf, n_steps, U, N;
-    // extended mode only (in-kernel generator, noise dump, caller's seed waveform)
-    SwnNoise nz;
-    const void* seed;
-    // streamed chunk only (STREAM instantiations): absolute index of the chunk's first step, 1 = resume from the
-    // session instead of running the prologue, the session ([B][T::sess_floats])
-    int step0, resume;
-    float* sess;
-};
-
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
-constexpr int pow2ceil(int x) { int r = 1; while (r < x) r <<= 1; return r; }
-constexpr int r4(int x) { return (x + 3) & ~3; }
+using namespace swn_bl6;
 
 template <int S_, int SEG_, int LPC_, int KIND_, int Q_, bool EXT_ = false>
 struct Tr {
@@ -98,60 +66,6 @@ struct Tr {
     // per-utterance session of a streamed decode: the history rings as LDS holds them, then the sample window
     static constexpr int sess_floats = ring_off(L) + r4(WN);
 };
-
-// Streamed weights go through a buffer resource: one 32-bit per-thread offset plus scalar /
-// immediate offsets per load, instead of a 64-bit VGPR address per load (which spilled).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, soff_bytes, 0));
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float sum4(float v) {      // all 4 lanes of a quad get the quad sum
-    v += dpp_f<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_f<0x4E>(v);      // quad_perm [2,3,0,1]
-    return v;
-}
-__device__ __forceinline__ float sum8(float v) {      // all 8 lanes of an aligned octet get the sum
-    v = sum4(v);
-    v += dpp_f<0x141>(v);     // row_half_mirror
-    return v;
-}
-// exp(x) = 2^(x*log2e) on the transcendental unit; the product's rounding error is fed back as a
-// first-order correction, so the result stays within ~1.5 ulp (libm-grade) at 6 instructions.
-__device__ __forceinline__ float exp_c(float x) {
-    const float t = x * 1.44269504f;
-    const float lo = fmaf(x, 1.44269504f, -t) + x * 1.92596299e-8f;
-    const float e = __builtin_amdgcn_exp2f(t);
-    return fmaf(e, lo * 0.693147181f, e);
-}
-__device__ __forceinline__ float rcp_c(float x) {        // v_rcp_f32 + one Newton step (<= 1 ulp)
-    const float r = __builtin_amdgcn_rcpf(x);
-    return fmaf(r, fmaf(-x, r, 1.f), r);
-}
-__device__ __forceinline__ float sigm(float x) { return rcp_c(1.f + exp_c(-x)); }
-__device__ __forceinline__ float tanh_c(float x) {        // (1 - e^-2|x|) / (1 + e^-2|x|), abs error ~1e-7
-    if (fabsf(x) > 9.02f) return copysignf(1.f, x);    // saturated in fp32 (also keeps this a branchy block)
-    const float t = exp_c(-2.f * fabsf(x));
-    return copysignf((1.f - t) * rcp_c(1.f + t), x);
-}
-__device__ __forceinline__ float ssign(float x) { return x * rcp_c(1.f + fabsf(x)); }
-
-// Workgroup barrier that orders LDS traffic only: the cross-wave hand-offs of this kernel all go
-// through LDS; a plain __syncthreads() also drains (vmcnt(0)) global loads that may stay in flight.
-__device__ __forceinline__ void lds_barrier() {
-#ifdef SWN_SYNC
-    __syncthreads(); return;
-#endif
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 template <int NP>
 __device__ __forceinline__ float pick(const float (&a)[NP], int p) {
@@ -336,16 +250,10 @@ __device__ __forceinline__ void tiled_matvec(__amdgpu_buffer_rsrc_t wt, const fl
     }
 }
 
-// the arguments of a pool launch: a streamed chunk over the entries (batch = E, n_steps = n_max), then the entry table
-struct B6PoolArgs {
-    B6Args c;
-    SwnPoolTable t;
-};
-static_assert(sizeof(B6PoolArgs) <= 4096, "kernel arguments are limited to 4 KB");
-template <bool POOL> struct B6ArgsOf { using type = B6Args; };
-template <> struct B6ArgsOf<true> { using type = B6PoolArgs; };
-__device__ __forceinline__ const B6Args& pool_or_launch(const B6Args& launch, const B6Args&) { return launch; }
-__device__ __forceinline__ const B6Args& pool_or_launch(const B6PoolArgs&, const B6Args& entry) { return entry; }
+template <bool POOL> struct B6ArgsOf { using type = Bl6Args; };
+template <> struct B6ArgsOf<true> { using type = Bl6PoolArgs; };
+__device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6Args& launch, const Bl6Args&) { return launch; }
+__device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, const Bl6Args& entry) { return entry; }
 
 // EXT = false: the classic instantiation (host-drawn noise stream, zero seed) - the code the round-1 measurements
 // belong to, kept instruction for instruction; EXT = true adds the in-kernel generator / noise dump / seed waveform.
@@ -357,14 +265,14 @@ __device__ __forceinline__ const B6Args& pool_or_launch(const B6PoolArgs&, const
 template <class T, bool STREAM = false, bool POOL = false>
 __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    B6Args pa;                                            // POOL: this workgroup's entry as a batch-1 chunk
+    Bl6Args pa;                                            // POOL: this workgroup's entry as a batch-1 chunk
     if constexpr (POOL) {
         static_assert(STREAM && T::EXT, "pools run the streamed extended mode");
         pa = ka.c;
         if (!swn_pool_entry_args(pa, ka.t, T::SEG, T::KIND == SWN_KIND_SOFTMAX ? T::Q : T::SEG, T::NO)) return;
         pa.sess += (size_t)swn_pool_slot(ka.t) * T::sess_floats;
     }
-    const B6Args& a = pool_or_launch(ka, pa);
+    const Bl6Args& a = pool_or_launch(ka, pa);
     constexpr int SEG = T::SEG, S = T::S, KIND = T::KIND;
     constexpr bool EXT = T::EXT;
     const int tid = threadIdx.x, b = POOL ? 0 : blockIdx.x;
@@ -460,11 +368,6 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
 
     // input layer h0 = softsign(causal(lift(S)))  (wave 0; fused wav_conv+causal taps).
     // Prologue form: all seed samples are zero / the mu-law zero index, only tap validity matters.
-#define c_b  lds[T::o_cz + o]
-#define c_v0 lds[T::o_cz + H + o]
-#define c_v1 lds[T::o_cz + 2 * H + o]
-#define c_c0 lds[T::o_cz + 3 * H + o]
-#define c_c1 lds[T::o_cz + 4 * H + o]
     auto input_seed = [&](int q) {
         if (tid < H) {
             const int o = tid;
@@ -835,22 +738,9 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
 }
 
 template <class T, bool STREAM = false>
-int launch_mode(const B6Args& a, hipStream_t st) {
+int launch_mode(const Bl6Args& a, hipStream_t st) {
     static_assert(T::lds_bytes <= 160 * 1024, "LDS budget");
-    auto kern = decode_bl6_kernel<T, STREAM>;
-    if (T::lds_bytes > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)T::lds_bytes) != hipSuccess)
-            return SWN_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(NT), T::lds_bytes, st, a);
-    return swn_launch_status("swn_decode(bl6)");
-}
-
-template <class T>
-int launch(const B6Args& a, hipStream_t st) {
-    const bool ext = !a.nz.ptr || a.nz.dump || a.seed;
-    return ext ? launch_mode<typename T::Ext>(a, st) : launch_mode<T>(a, st);
+    return launch_kernel(decode_bl6_kernel<T, STREAM>, T::lds_bytes, a.B, a, st, "swn_decode(bl6)");
 }
 
 // the instantiation a geometry runs: f(Tr<...>{}) for a BL6-class net, SWN_E_UNSUPPORTED otherwise
@@ -876,23 +766,13 @@ extern "C" int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, c
                                    void* stream_) {
     SwnGeom g; int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    B6PoolArgs p;
-    B6Args& a = p.c;
-    swn_make_layout(&g, &a.y);
-    a.P = packed; a.cond = nullptr; a.noise = nullptr; a.nz = *nz; a.forced = nullptr; a.seed = seed; a.out = out; a.heads = heads;
-    a.B = n_entries; a.Tf = 0; a.n_steps = n_max; a.U = g.U; a.N = g.N;
-    a.step0 = 0; a.resume = 0; a.sess = sess;
+    Bl6PoolArgs p;
+    fill_args(p.c, g, packed, nullptr, nz, nullptr, seed, out, heads, n_entries, 0, n_max, 0, 0, sess);
     p.t = *t;
     hipStream_t st = (hipStream_t)stream_;
     return with_tr(g, [&](auto tr) {
         using T = typename decltype(tr)::Ext;
-        auto kern = decode_bl6_kernel<T, true, true>;
-        if (T::lds_bytes > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)T::lds_bytes) != hipSuccess)
-            return (int)SWN_E_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(n_entries), dim3(NT), T::lds_bytes, st, p);
-        return swn_launch_status("swn_decode_pool_chunk(bl6)");
+        return launch_kernel(decode_bl6_kernel<T, true, true>, T::lds_bytes, n_entries, p, st, "swn_decode_pool_chunk(bl6)");
     });
 }
 
@@ -911,37 +791,25 @@ extern "C" int swn_decode_bl6_chunk(const swn_net_desc* d, const float* packed, 
                                     const void* seed, float* sess, void* out, float* heads, void* stream_) {
     SwnGeom g; int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    B6Args a;
-    swn_make_layout(&g, &a.y);
-    a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
-    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
-    a.step0 = step0; a.resume = resume; a.sess = sess;
+    Bl6Args a;
+    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, step0, resume, sess);
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();
     return with_tr(g, [&](auto t) { return launch_mode<typename decltype(t)::Ext, true>(a, st); });
 }
 
+// the one-shot decode; SWN_E_UNSUPPORTED when the geometry is not a BL6-class one
 extern "C" int swn_decode_bl6_try(const swn_net_desc* d, const float* packed, const float* cond, int batch,
                                   int n_frames, int n_steps, const SwnNoise* nz, const void* forced,
                                   const void* seed, void* out, float* heads, void* stream_) {
     SwnGeom g; int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    if (!g.bl6 || g.U > 256 || g.U < 2 * g.seg || g.audio_in) return SWN_E_UNSUPPORTED;
-    B6Args a;
-    swn_make_layout(&g, &a.y);
-    a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
-    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
-    a.step0 = 0; a.resume = 0; a.sess = nullptr;
+    Bl6Args a;
+    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, 0, 0, nullptr);
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();   // drop stale errors of earlier runtime calls; only our launches are reported
-    if (g.kind == SWN_KIND_LAPLACE && g.S == 128) {
-        if (g.seg == 1 && g.lpc == 0) return launch<Tr<128, 1, 0, SWN_KIND_LAPLACE, 0>>(a, st);
-        if (g.seg == 1 && g.lpc == 4) return launch<Tr<128, 1, 4, SWN_KIND_LAPLACE, 0>>(a, st);
-        if (g.seg == 2 && g.lpc == 4) return launch<Tr<128, 2, 4, SWN_KIND_LAPLACE, 0>>(a, st);
-        if (g.seg == 5 && g.lpc == 0) return launch<Tr<128, 5, 0, SWN_KIND_LAPLACE, 0>>(a, st);
-        if (g.seg == 5 && g.lpc == 4) return launch<Tr<128, 5, 4, SWN_KIND_LAPLACE, 0>>(a, st);
-    }
-    if (g.kind == SWN_KIND_SOFTMAX && g.S == 256 && g.Q == 256)
-        return launch<Tr<256, 1, 0, SWN_KIND_SOFTMAX, 256>>(a, st);
-    return SWN_E_UNSUPPORTED;
+    return with_tr(g, [&](auto t) {
+        using T = decltype(t);
+        return wants_ext(a) ? launch_mode<typename T::Ext>(a, st) : launch_mode<T>(a, st);
+    });
 }

@@ -1,0 +1,138 @@
+// What the two BL6-class decode kernels share (swn_decode_bl6.hip: the symmetric kernel, swn_decode_bl6w.hip: the
+// wave-specialised one): the launch arguments, the constants of the class, the device helpers both step loops are written
+// with, and the host side that fills the arguments and launches.  The kernels' own LDS carves (Tr, Tw) and phases stay in
+// their files.  Both kernels sit at the register limit: a change here changes the generated code of both.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "swn_geom.hpp"
+#include "swn_noise.hpp"
+#include "swn_pool.hpp"
+
+namespace swn_bl6 {
+
+constexpr int NT = 512;
+constexpr int H = 64;
+constexpr int L = 6;
+constexpr int RF = 64;
+#ifdef SWN_STAMP
+constexpr bool HEADS_ON = false;
+#else
+constexpr bool HEADS_ON = true;
+#endif
+
+struct Bl6Args {
+    const float* P;
+    SwnLayout y;
+    const float* cond;
+    const float* noise;            // classic mode: the host-drawn stream
+    const void* forced;
+    void* out;
+    float* heads;
+    int B, Tf, n_steps, U, N;
+    // extended mode only (in-kernel generator, noise dump, caller's seed waveform)
+    SwnNoise nz;
+    const void* seed;
+    // streamed chunk only (STREAM instantiations): absolute index of the chunk's first step, 1 = resume from the
+    // session instead of running the prologue, the session ([B][T::sess_floats])
+    int step0, resume;
+    float* sess;
+};
+
+// the arguments of a pool launch: a streamed chunk over the entries (batch = E, n_steps = n_max), then the entry table
+struct Bl6PoolArgs {
+    Bl6Args c;
+    SwnPoolTable t;
+};
+static_assert(sizeof(Bl6PoolArgs) <= 4096, "kernel arguments are limited to 4 KB");
+
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
+constexpr int pow2ceil(int x) { int r = 1; while (r < x) r <<= 1; return r; }
+constexpr int r4(int x) { return (x + 3) & ~3; }
+
+// Streamed weights go through a buffer resource: one 32-bit per-thread offset plus scalar /
+// immediate offsets per load, instead of a 64-bit VGPR address per load (which spilled).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, soff_bytes, 0));
+}
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_f(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float sum4(float v) {      // all 4 lanes of a quad get the quad sum
+    v += dpp_f<0xB1>(v);      // quad_perm [1,0,3,2]
+    v += dpp_f<0x4E>(v);      // quad_perm [2,3,0,1]
+    return v;
+}
+__device__ __forceinline__ float sum8(float v) {      // all 8 lanes of an aligned octet get the sum
+    v = sum4(v);
+    v += dpp_f<0x141>(v);     // row_half_mirror
+    return v;
+}
+// exp(x) = 2^(x*log2e) on the transcendental unit; the product's rounding error is fed back as a
+// first-order correction, so the result stays within ~1.5 ulp (libm-grade) at 6 instructions
+// (the 1e-5 bar is held through 66 000 recurrent steps).
+__device__ __forceinline__ float exp_c(float x) {
+    const float t = x * 1.44269504f;
+    const float lo = fmaf(x, 1.44269504f, -t) + x * 1.92596299e-8f;
+    const float e = __builtin_amdgcn_exp2f(t);
+    return fmaf(e, lo * 0.693147181f, e);
+}
+__device__ __forceinline__ float rcp_c(float x) {        // v_rcp_f32 + one Newton step (<= 1 ulp)
+    const float r = __builtin_amdgcn_rcpf(x);
+    return fmaf(r, fmaf(-x, r, 1.f), r);
+}
+__device__ __forceinline__ float sigm(float x) { return rcp_c(1.f + exp_c(-x)); }
+__device__ __forceinline__ float tanh_c(float x) {        // (1 - e^-2|x|) / (1 + e^-2|x|), abs error ~1e-7
+    if (fabsf(x) > 9.02f) return copysignf(1.f, x);    // saturated in fp32 (also keeps this a branchy block)
+    const float t = exp_c(-2.f * fabsf(x));
+    return copysignf((1.f - t) * rcp_c(1.f + t), x);
+}
+__device__ __forceinline__ float ssign(float x) { return x * rcp_c(1.f + fabsf(x)); }
+
+// Workgroup barrier that orders LDS traffic only: the cross-wave hand-offs of these kernels all go
+// through LDS; a plain __syncthreads() also drains (vmcnt(0)) global loads that may stay in flight.
+__device__ __forceinline__ void lds_barrier() {
+#ifdef SWN_SYNC
+    __syncthreads(); return;
+#endif
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// the five input-layer constants of channel `o` in a kernel's carve (cb[64], cv[2][64], cc[2][64] at T::o_cz of `lds`)
+#define c_b  lds[T::o_cz + o]
+#define c_v0 lds[T::o_cz + H + o]
+#define c_v1 lds[T::o_cz + 2 * H + o]
+#define c_c0 lds[T::o_cz + 3 * H + o]
+#define c_c1 lds[T::o_cz + 4 * H + o]
+
+// ---- host side
+// a launch (one-shot: step0 = resume = 0, sess = nullptr; pool: the launch-wide arguments over the entries)
+inline void fill_args(Bl6Args& a, const SwnGeom& g, const float* packed, const float* cond, const SwnNoise* nz,
+                      const void* forced, const void* seed, void* out, float* heads, int batch, int n_frames, int n_steps,
+                      int step0, int resume, float* sess) {
+    swn_make_layout(&g, &a.y);
+    a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
+    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
+    a.step0 = step0; a.resume = resume; a.sess = sess;
+}
+
+// the extended instantiation runs whenever the classic one's inputs (host-drawn noise, no dump, zero seed) are not given
+inline bool wants_ext(const Bl6Args& a) { return !a.nz.ptr || a.nz.dump || a.seed; }
+
+// one workgroup per utterance / pool entry; dynamic LDS above 64 KB has to be asked for
+template <class A>
+int launch_kernel(void (*kern)(A), size_t lds_bytes, int n_groups, const A& a, hipStream_t st, const char* where) {
+    if (lds_bytes > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+        return SWN_E_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(n_groups), dim3(NT), lds_bytes, st, a);
+    return swn_launch_status(where);
+}
+
+}  // namespace swn_bl6

@@ -21,46 +21,16 @@
 // Same arithmetic per element as the symmetric kernel up to the order of the partial sums (1e-7 relative); same noise, seed,
 // forced-input and heads interface (swn_decode_bl6.hip: classic = host-drawn noise, zero seed; extended = in-kernel generator,
 // noise dump, caller's seed waveform).  8 barriers per step.  cswnv_shift1.py:281-430.
-#include <hip/hip_runtime.h>
-#include "swn_geom.hpp"
-#include "swn_noise.hpp"
-#include "swn_pool.hpp"
+#include "swn_decode_bl6_common.hpp"
+#include "swn_decode_internal.hpp"
 
 namespace {
 
-constexpr int NT = 512;
+using namespace swn_bl6;
+
 constexpr int NG = 256;            // threads per group
-constexpr int H = 64;
-constexpr int L = 6;
-constexpr int RF = 64;
 constexpr int S = 128;
 constexpr int O1 = 128;
-#ifdef SWN_STAMP
-constexpr bool HEADS_ON = false;
-#else
-constexpr bool HEADS_ON = true;
-#endif
-
-struct W6Args {
-    const float* P;
-    SwnLayout y;
-    const float* cond;
-    const float* noise;            // classic mode: the host-drawn stream
-    const void* forced;
-    void* out;
-    float* heads;
-    int B, Tf, n_steps, U, N;
-    SwnNoise nz;                   // extended mode
-    const void* seed;
-    // streamed chunk only (STREAM instantiations): absolute index of the chunk's first step, 1 = resume from the
-    // session instead of running the prologue, the session ([B][T::sess_floats])
-    int step0, resume;
-    float* sess;
-};
-
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
-constexpr int pow2ceil(int x) { int r = 1; while (r < x) r <<= 1; return r; }
-constexpr int r4(int x) { return (x + 3) & ~3; }
 
 template <int LPC_, bool EXT_>
 struct Tw {
@@ -101,21 +71,6 @@ struct Tw {
     static constexpr int sess_floats = sess_win + r4(WN);
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, soff_bytes, 0));
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float sum4(float v) {      // all 4 lanes of a quad get the quad sum
-    v += dpp_f<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_f<0x4E>(v);      // quad_perm [2,3,0,1]
-    return v;
-}
 // the sum over the wave's 16 quads, per position in the quad: lane hp of the first quad gets the sum of lanes hp + 4 n
 // (the swaps in inline assembly, with the two wait states a VALU write needs before them: the compiler returns the builtins'
 //  second result as a copy of the first)
@@ -129,26 +84,6 @@ __device__ __forceinline__ float sum_quads(float v) {
     asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(v), "+v"(w));   // the two halves
     return v + w;
 }
-// exp, reciprocal, sigmoid as in swn_decode_bl6.hip (<= 1.5 ulp: the 1e-5 bar is held through 66 000 recurrent steps)
-__device__ __forceinline__ float exp_c(float x) {
-    const float t = x * 1.44269504f;
-    const float lo = fmaf(x, 1.44269504f, -t) + x * 1.92596299e-8f;
-    const float e = __builtin_amdgcn_exp2f(t);
-    return fmaf(e, lo * 0.693147181f, e);
-}
-__device__ __forceinline__ float rcp_c(float x) {
-    const float r = __builtin_amdgcn_rcpf(x);
-    return fmaf(r, fmaf(-x, r, 1.f), r);
-}
-__device__ __forceinline__ float sigm(float x) { return rcp_c(1.f + exp_c(-x)); }
-__device__ __forceinline__ float ssign(float x) { return x * rcp_c(1.f + fabsf(x)); }
-
-__device__ __forceinline__ void lds_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // ---- group A: layer LAYER at position q - current tap, gate epilogue, hand-off.  Thread (o, p): rows o (gate) and o + 64
 //      (candidate) over inputs 16 p .. 16 p + 15 of h_{l-1}(q), read from the row `xr`; lanes 0 / 1 of the quad finish the gate / the
 //      candidate.
@@ -334,7 +269,7 @@ __device__ __forceinline__ void skip_last_b(float* lds, const float4 (&wsl)[8], 
 // POOL (with STREAM): one entry of a decode pool (swn_decode_pool_chunk); `a` already holds it as a batch-1 chunk, b = 0.  The
 // noise staging and the frame boundaries follow the entry's own step0 and n_steps, so entries of one launch sit at any phase.
 template <class T, bool GA, bool STREAM, bool POOL = false>
-__device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
+__device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     constexpr bool EXT = T::EXT;
     static_assert(!STREAM || EXT, "streamed chunks run the extended mode");
     constexpr bool grpA = GA;
@@ -425,11 +360,6 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
         pb = (fsel & 1) * T::PF;
     };
 
-#define c_b  lds[T::o_cz + o]
-#define c_v0 lds[T::o_cz + H + o]
-#define c_v1 lds[T::o_cz + 2 * H + o]
-#define c_c0 lds[T::o_cz + 3 * H + o]
-#define c_c1 lds[T::o_cz + 4 * H + o]
     // input layer h0 = softsign(causal(lift(S)))  (wave 0).  Prologue: the seed samples are zero, only tap validity matters
     auto input_seed = [&](int q) {
         if (tid < H) {
@@ -700,86 +630,67 @@ __device__ __forceinline__ void decode_body(const W6Args& a, float* lds) {
 }
 
 template <class T, bool STREAM = false>
-__global__ __launch_bounds__(NT) void decode_bl6w_kernel(const W6Args a) {
+__global__ __launch_bounds__(NT) void decode_bl6w_kernel(const Bl6Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (threadIdx.x < NG) decode_body<T, true, STREAM>(a, lds);       // wave-uniform
     else decode_body<T, false, STREAM>(a, lds);
 }
 
-// the arguments of a pool launch: a streamed chunk over the entries (batch = E, n_steps = n_max), then the entry table
-struct W6PoolArgs {
-    W6Args c;
-    SwnPoolTable t;
-};
-static_assert(sizeof(W6PoolArgs) <= 4096, "kernel arguments are limited to 4 KB");
-
 template <class T>
-__global__ __launch_bounds__(NT) void decode_bl6w_pool_kernel(const W6PoolArgs p) {
+__global__ __launch_bounds__(NT) void decode_bl6w_pool_kernel(const Bl6PoolArgs p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     static_assert(T::EXT, "pools run the extended mode");
-    W6Args a = p.c;
+    Bl6Args a = p.c;
     if (!swn_pool_entry_args(a, p.t, 1, 1, T::NO)) return;
     a.sess += (size_t)swn_pool_slot(p.t) * T::sess_floats;
     if (threadIdx.x < NG) decode_body<T, true, true, true>(a, lds);   // wave-uniform
     else decode_body<T, false, true, true>(a, lds);
 }
 
-template <class T>
-int launch_pool(const W6PoolArgs& p, int n_entries, hipStream_t st) {
-    auto kern = decode_bl6w_pool_kernel<T>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::lds_bytes) != hipSuccess)
-        return SWN_E_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(n_entries), dim3(NT), T::lds_bytes, st, p);
-    return swn_launch_status("swn_decode_pool_chunk(bl6w)");
-}
-
 template <class T, bool STREAM = false>
-int launch_mode(const W6Args& a, hipStream_t st) {
+int launch_mode(const Bl6Args& a, hipStream_t st) {
     static_assert(T::lds_bytes <= 160 * 1024, "LDS budget");
-    auto kern = decode_bl6w_kernel<T, STREAM>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::lds_bytes) != hipSuccess)
-        return SWN_E_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(NT), T::lds_bytes, st, a);
-    return swn_launch_status("swn_decode(bl6w)");
+    return launch_kernel(decode_bl6w_kernel<T, STREAM>, T::lds_bytes, a.B, a, st, "swn_decode(bl6w)");
 }
-
-template <class T>
-int launch(const W6Args& a, hipStream_t st) {
-    const bool ext = !a.nz.ptr || a.nz.dump || a.seed;
-    return ext ? launch_mode<typename T::Ext>(a, st) : launch_mode<T>(a, st);
-}
-
 
 bool bl6w_applies(const SwnGeom& g) {
     return g.bl6 && g.U <= 256 && g.U >= 2 && !g.audio_in && g.kind == SWN_KIND_LAPLACE && g.S == 128 && g.O1 == 128 &&
            g.seg == 1 && (g.lpc == 0 || g.lpc == 4);
 }
 
+// the instantiation a geometry runs: f(Tw<lpc, false>{}) for a single-sample Laplace net of the BL6 class, SWN_E_UNSUPPORTED
+// otherwise (the symmetric kernel, swn_decode_bl6.hip, takes the others)
+template <class F>
+int with_tw(const SwnGeom& g, F&& f) {
+    if (!bl6w_applies(g)) return SWN_E_UNSUPPORTED;
+    if (g.lpc == 0) return f(Tw<0, false>{});
+    return f(Tw<4, false>{});
+}
+
 }  // namespace
 
-// SWN_E_UNSUPPORTED: not a single-sample Laplace net of the BL6 class (the symmetric kernel, swn_decode_bl6.hip, takes the others)
 extern "C" int swn_decode_bl6w_try(const swn_net_desc* d, const float* packed, const float* cond, int batch,
                                    int n_frames, int n_steps, const SwnNoise* nz, const void* forced,
                                    const void* seed, void* out, float* heads, void* stream_) {
     SwnGeom g; int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    if (!bl6w_applies(g)) return SWN_E_UNSUPPORTED;
-    W6Args a;
-    swn_make_layout(&g, &a.y);
-    a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
-    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
-    a.step0 = 0; a.resume = 0; a.sess = nullptr;
+    Bl6Args a;
+    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, 0, 0, nullptr);
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();
-    if (g.lpc == 0) return launch<Tw<0, false>>(a, st);
-    return launch<Tw<4, false>>(a, st);
+    return with_tw(g, [&](auto t) {
+        using T = decltype(t);
+        return wants_ext(a) ? launch_mode<typename T::Ext>(a, st) : launch_mode<T>(a, st);
+    });
 }
 
 // streamed decode (swn_decode_chunk): per-utterance session floats of the wave-specialised kernel, 0 = it does not apply
 extern "C" size_t swn_decode_bl6w_session_floats(const swn_net_desc* d) {
     SwnGeom g;
-    if (swn_make_geom(d, &g) < 0 || !bl6w_applies(g)) return 0;
-    return (size_t)(g.lpc == 0 ? Tw<0, true>::sess_floats : Tw<4, true>::sess_floats);
+    if (swn_make_geom(d, &g) < 0) return 0;
+    int n = 0;
+    with_tw(g, [&](auto t) { n = decltype(t)::sess_floats; return SWN_OK; });
+    return (size_t)n;
 }
 
 // one chunk on the wave-specialised kernel; `sess` holds swn_decode_bl6w_session_floats() floats per utterance
@@ -788,16 +699,11 @@ extern "C" int swn_decode_bl6w_chunk(const swn_net_desc* d, const float* packed,
                                      const void* seed, float* sess, void* out, float* heads, void* stream_) {
     SwnGeom g; int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    if (!bl6w_applies(g)) return SWN_E_UNSUPPORTED;
-    W6Args a;
-    swn_make_layout(&g, &a.y);
-    a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
-    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
-    a.step0 = step0; a.resume = resume; a.sess = sess;
+    Bl6Args a;
+    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, step0, resume, sess);
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();
-    if (g.lpc == 0) return launch_mode<Tw<0, true>, true>(a, st);
-    return launch_mode<Tw<4, true>, true>(a, st);
+    return with_tw(g, [&](auto t) { return launch_mode<typename decltype(t)::Ext, true>(a, st); });
 }
 
 // one pool launch (swn_decode_pool_chunk checked the entries): one workgroup per entry, sessions [capacity][sess_floats]
@@ -806,15 +712,12 @@ extern "C" int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, 
                                     void* stream_) {
     SwnGeom g; int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    if (!bl6w_applies(g)) return SWN_E_UNSUPPORTED;
-    W6PoolArgs p;
-    W6Args& a = p.c;
-    swn_make_layout(&g, &a.y);
-    a.P = packed; a.cond = nullptr; a.noise = nullptr; a.nz = *nz; a.forced = nullptr; a.seed = seed; a.out = out; a.heads = heads;
-    a.B = n_entries; a.Tf = 0; a.n_steps = n_max; a.U = g.U; a.N = g.N;
-    a.step0 = 0; a.resume = 0; a.sess = sess;
+    Bl6PoolArgs p;
+    fill_args(p.c, g, packed, nullptr, nz, nullptr, seed, out, heads, n_entries, 0, n_max, 0, 0, sess);
     p.t = *t;
     hipStream_t st = (hipStream_t)stream_;
-    if (g.lpc == 0) return launch_pool<Tw<0, true>>(p, n_entries, st);
-    return launch_pool<Tw<4, true>>(p, n_entries, st);
+    return with_tw(g, [&](auto tw) {
+        using T = typename decltype(tw)::Ext;
+        return launch_kernel(decode_bl6w_pool_kernel<T>, T::lds_bytes, n_entries, p, st, "swn_decode_pool_chunk(bl6w)");
+    });
 }

@@ -16,8 +16,7 @@
 // and the ring layout are those of the generic persistent kernel (swn_decode.hip).
 #include <hip/hip_runtime.h>
 #include <type_traits>
-#include "swn_geom.hpp"
-#include "swn_noise.hpp"
+#include "swn_decode_internal.hpp"
 
 namespace {
 
@@ -498,15 +497,26 @@ __global__ __launch_bounds__(64 * ST_TU) void step_layer_tile_kernel(const StA<P
 }
 
 // ---- rowvec: y[b][row] = act(bias[row] + W[row][:] . x[b][:]), ONE wave per row -------------------------
-template <int BT>
-__global__ __launch_bounds__(64) void rowvec_kernel(const StArgs a, size_t w_off, int ldw, size_t b_off, int rows,
-                                                    int ni, int x_off, int y_off, int relu) {
+// POOL (BT = 1): entry blockIdx.y, when it is generating at tick-local iteration `itj`; its state block is in its slot
+template <int BT, bool POOL = false>
+__global__ __launch_bounds__(64) void rowvec_kernel(const StA<POOL> a, size_t w_off, int ldw, size_t b_off, int rows,
+                                                    int ni, int x_off, int y_off, int relu, const int itj) {
+    static_assert(!POOL || BT == 1, "pool form: one entry per workgroup");
     const int lane = threadIdx.x, row = blockIdx.x;
+    size_t pbase = 0;                                          // POOL: the entry's state block, in floats
+    if constexpr (POOL) {
+        const StPoolEnt& en = a.tab[blockIdx.y];
+        if (itj >= en.n_it || en.it0 + itj < en.g0) return;
+        pbase = (size_t)en.slot * a.stride;
+    }
     const __amdgpu_buffer_rsrc_t rP = st_rsrc(a.P), rS = st_rsrc(a.state);
     const size_t wr = w_off + (size_t)row * ldw;
     const float bias = a.P[b_off + row];
+    // (POOL: fetched here, beside the kernel arguments, as the pool form always did; left to the compiler, the load sinks
+    //  behind the loop and costs a round trip of its own at the end of the launch)
+    if constexpr (POOL) asm volatile("" :: "s"(bias));
     const int b0 = blockIdx.y * BT;
-    const int nb = a.B - b0 < BT ? a.B - b0 : BT;              // utterances of this tile, processed concurrently
+    const int nb = POOL ? 1 : (a.B - b0 < BT ? a.B - b0 : BT);   // utterances of this tile, processed concurrently
     float acc[BT];
 #pragma unroll
     for (int u = 0; u < BT; ++u) acc[u] = 0.f;
@@ -519,8 +529,10 @@ __global__ __launch_bounds__(64) void rowvec_kernel(const StArgs a, size_t w_off
             const bool ok = idx < ni;
             wv[pc] = st_ld4(rP, ok ? (unsigned)((wr + idx) * 4) : ST_OOB);
 #pragma unroll
-            for (int u = 0; u < BT; ++u)
-                xv[pc][u] = st_ld4(rS, (ok && u < nb) ? (unsigned)(((size_t)(b0 + u) * a.stride + x_off + idx) * 4) : ST_OOB);
+            for (int u = 0; u < BT; ++u) {
+                if constexpr (POOL) xv[pc][u] = st_ld4(rS, ok ? st_off(pbase + x_off + idx) : ST_OOB);
+                else xv[pc][u] = st_ld4(rS, (ok && u < nb) ? (unsigned)(((size_t)(b0 + u) * a.stride + x_off + idx) * 4) : ST_OOB);
+            }
         }
 #pragma unroll
         for (int pc = 0; pc < RV; ++pc)
@@ -537,47 +549,16 @@ __global__ __launch_bounds__(64) void rowvec_kernel(const StArgs a, size_t w_off
     }
     if (lane < nb) {
         const float v = mine + bias;
-        a.state[(size_t)(b0 + lane) * a.stride + y_off + row] = relu ? fmaxf(v, 0.f) : v;
-    }
-}
-
-// pool form of rowvec_kernel<1>: entry blockIdx.y, when it is generating at tick-local iteration `itj`
-__global__ __launch_bounds__(64) void rowvec_pool_kernel(const StPoolArgs a, size_t w_off, int ldw, size_t b_off, int rows,
-                                                         int ni, int x_off, int y_off, int relu, int itj) {
-    const int lane = threadIdx.x, row = blockIdx.x;
-    const StPoolEnt& en = a.tab[blockIdx.y];
-    if (itj >= en.n_it || en.it0 + itj < en.g0) return;
-    const __amdgpu_buffer_rsrc_t rP = st_rsrc(a.P), rS = st_rsrc(a.state);
-    const size_t wr = w_off + (size_t)row * ldw, base = (size_t)en.slot * a.stride;
-    const float bias = a.P[b_off + row];
-    float acc = 0.f;
-    constexpr int RV = 5;
-    for (int i0 = 0; i0 < ni; i0 += 256 * RV) {
-        float4 wv[RV], xv[RV];
-#pragma unroll
-        for (int pc = 0; pc < RV; ++pc) {
-            const int idx = i0 + pc * 256 + lane * 4;
-            const bool ok = idx < ni;
-            wv[pc] = st_ld4(rP, ok ? (unsigned)((wr + idx) * 4) : ST_OOB);
-            xv[pc] = st_ld4(rS, ok ? st_off(base + x_off + idx) : ST_OOB);
-        }
-#pragma unroll
-        for (int pc = 0; pc < RV; ++pc) {
-            acc = fmaf(wv[pc].x, xv[pc].x, acc); acc = fmaf(wv[pc].y, xv[pc].y, acc);
-            acc = fmaf(wv[pc].z, xv[pc].z, acc); acc = fmaf(wv[pc].w, xv[pc].w, acc);
-        }
-    }
-    const float sv = sum64(acc);
-    if (lane == 0) {
-        const float v = sv + bias;
-        a.state[base + y_off + row] = relu ? fmaxf(v, 0.f) : v;
+        a.state[(POOL ? pbase : (size_t)(b0 + lane) * a.stride) + y_off + row] = relu ? fmaxf(v, 0.f) : v;
     }
 }
 
 // the same for the 1x1 layers: 8 rows x 8 utterances per workgroup, the utterances' input vectors staged in LDS
-template <int RV>                                              // host: ni <= 256 RV
-__global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StArgs a, size_t w_off, int ldw, size_t b_off, int rows,
-                                                                 int ni, int x_off, int y_off, int relu) {
+// POOL: wave w stages entry 8 by + w, lane octet u finishes entry 8 by + u, each only when that entry is generating at
+// tick-local iteration `itj`
+template <int RV, bool POOL = false>                           // host: ni <= 256 RV
+__global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StA<POOL> a, size_t w_off, int ldw, size_t b_off, int rows,
+                                                                 int ni, int x_off, int y_off, int relu, const int itj) {
     extern __shared__ __attribute__((aligned(16))) float xs[];  // [ST_TU][RV * 256]
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -588,6 +569,16 @@ __global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StArgs a,
     const float bias = live ? a.P[b_off + row] : 0.f;
     const int b0 = blockIdx.y * ST_TU;
     const int nb = a.B - b0 < ST_TU ? a.B - b0 : ST_TU;
+    const int ut = lane >> 3;                                  // the utterance this lane's octet ends up with (sum64x8)
+    bool onw = w < nb, onu = ut < nb;                          // this wave stages / this octet finishes an utterance
+    size_t basew = (size_t)(b0 + w) * a.stride, baseu = (size_t)(b0 + ut) * a.stride;
+    if constexpr (POOL) {
+        const StPoolEnt& ew = a.tab[b0 + (onw ? w : 0)];
+        const StPoolEnt& eu = a.tab[b0 + (onu ? ut : 0)];
+        onw = onw && itj < ew.n_it && ew.it0 + itj >= ew.g0;
+        onu = onu && itj < eu.n_it && eu.it0 + itj >= eu.g0;
+        basew = (size_t)ew.slot * a.stride; baseu = (size_t)eu.slot * a.stride;
+    }
     float4 wv[RV];
     {
         float4 xv[RV];
@@ -596,7 +587,8 @@ __global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StArgs a,
             const int idx = pc * 256 + lane * 4;
             const bool ok = idx < ni;
             wv[pc] = st_ld4(rP, (ok && live) ? (unsigned)((wr + idx) * 4) : ST_OOB);
-            xv[pc] = st_ld4(rS, (ok && w < nb) ? (unsigned)(((size_t)(b0 + w) * a.stride + x_off + idx) * 4) : ST_OOB);
+            if constexpr (POOL) xv[pc] = st_ld4(rS, (ok && onw) ? st_off(basew + x_off + idx) : ST_OOB);
+            else xv[pc] = st_ld4(rS, (ok && onw) ? (unsigned)((basew + x_off + idx) * 4) : ST_OOB);
         }
 #pragma unroll
         for (int pc = 0; pc < RV; ++pc) *reinterpret_cast<float4*>(xs + (w * RV + pc) * 256 + lane * 4) = xv[pc];
@@ -615,64 +607,9 @@ __global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StArgs a,
         accv[u] = acc;
     }
     const float mine = sum64x8(accv, lane);
-    const int ut = lane >> 3;
-    if ((lane & 7) == 0 && ut < nb && live) {
+    if ((lane & 7) == 0 && onu && live) {
         const float v = mine + bias;
-        a.state[(size_t)(b0 + ut) * a.stride + y_off + row] = relu ? fmaxf(v, 0.f) : v;
-    }
-}
-
-// pool form of rowvec_tile_kernel: wave w stages entry 8 by + w, lane octet u finishes entry 8 by + u, each only when that
-// entry is generating at tick-local iteration `itj`
-template <int RV>
-__global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_pool_kernel(const StPoolArgs a, size_t w_off, int ldw, size_t b_off,
-                                                                      int rows, int ni, int x_off, int y_off, int relu, int itj) {
-    extern __shared__ __attribute__((aligned(16))) float xs[];  // [ST_TU][RV * 256]
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int row = blockIdx.x * ST_TU + w;
-    const bool live = row < rows;
-    const int b0 = blockIdx.y * ST_TU;
-    const int nb = a.B - b0 < ST_TU ? a.B - b0 : ST_TU;
-    const int ut = lane >> 3;
-    const StPoolEnt& ew = a.tab[b0 + (w < nb ? w : 0)];
-    const StPoolEnt& eu = a.tab[b0 + (ut < nb ? ut : 0)];
-    const bool genw = w < nb && itj < ew.n_it && ew.it0 + itj >= ew.g0;
-    const bool genu = ut < nb && itj < eu.n_it && eu.it0 + itj >= eu.g0;
-    const __amdgpu_buffer_rsrc_t rP = st_rsrc(a.P), rS = st_rsrc(a.state);
-    const size_t wr = w_off + (size_t)(live ? row : 0) * ldw;
-    const float bias = live ? a.P[b_off + row] : 0.f;
-    const size_t basew = (size_t)ew.slot * a.stride;
-    float4 wv[RV];
-    {
-        float4 xv[RV];
-#pragma unroll
-        for (int pc = 0; pc < RV; ++pc) {
-            const int idx = pc * 256 + lane * 4;
-            const bool ok = idx < ni;
-            wv[pc] = st_ld4(rP, (ok && live) ? (unsigned)((wr + idx) * 4) : ST_OOB);
-            xv[pc] = st_ld4(rS, (ok && genw) ? st_off(basew + x_off + idx) : ST_OOB);
-        }
-#pragma unroll
-        for (int pc = 0; pc < RV; ++pc) *reinterpret_cast<float4*>(xs + (w * RV + pc) * 256 + lane * 4) = xv[pc];
-    }
-    __syncthreads();
-    float accv[ST_TU];
-#pragma unroll
-    for (int u = 0; u < ST_TU; ++u) {
-        float acc = 0.f;
-#pragma unroll
-        for (int pc = 0; pc < RV; ++pc) {
-            const float4 x = *reinterpret_cast<const float4*>(xs + (u * RV + pc) * 256 + lane * 4);
-            acc = fmaf(wv[pc].x, x.x, acc); acc = fmaf(wv[pc].y, x.y, acc);
-            acc = fmaf(wv[pc].z, x.z, acc); acc = fmaf(wv[pc].w, x.w, acc);
-        }
-        accv[u] = acc;
-    }
-    const float mine = sum64x8(accv, lane);
-    if ((lane & 7) == 0 && genu && live) {
-        const float v = mine + bias;
-        a.state[(size_t)eu.slot * a.stride + y_off + row] = relu ? fmaxf(v, 0.f) : v;
+        a.state[baseu + y_off + row] = relu ? fmaxf(v, 0.f) : v;
     }
 }
 
@@ -1012,114 +949,128 @@ int plan(StArgs& a) {
     return a.stride;
 }
 
+// the geometries the chain runs, for `batch` utterances (pool: slots)
+bool chain_takes(const SwnGeom& g, int batch) {
+    if ((g.K * g.Hp + 255) / 256 > 8 || g.seg > 16 || g.lpc > 16 || g.NO > 4096) return false;
+    StArgs t; t.g = g;
+    return (size_t)plan(t) * batch * sizeof(float) < (1ull << 31) && t.WN <= 32;   // 32-bit buffer offsets; LDS window
+}
+
+// the launch arguments of `n` utterances (pool: entries) over a.g, all but a pool's table
+void fill_args(StArgs& a, const float* packed, const float* cond, const SwnNoise& nz, const void* forced, const void* seed,
+               float* state, void* out, float* heads, int n, int n_frames, int n_steps, int step0) {
+    swn_make_layout(&a.g, &a.y);
+    plan(a);
+    a.P = packed; a.cond = cond; a.nz = nz; a.forced = forced; a.seed = seed; a.state = state; a.out = out; a.heads = heads;
+    a.B = n; a.Tf = n_frames; a.n_steps = n_steps; a.n_pro = a.g.rf - a.g.seg + 1; a.step0 = step0;
+    // one 256-thread workgroup evaluates 8 rows per pass: beyond 64 rows (8 passes, ~7 us) a launch of its own is cheaper
+    a.o2_by_rowvec = a.g.NO > 64 ? 1 : 0;
+}
+
+// dynamic LDS above 64 KB for the tile forms (NI = 8: 64 KB, RV = 9: 72 KB)
+template <bool POOL>
+bool allow_tile_lds() {
+    const int big = 72 * 1024;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_LAPLACE, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, big) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_SOFTMAX, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, big) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(rowvec_tile_kernel<9, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, big) == hipSuccess;
+}
+constexpr int ST_SEQ = 24;                                     // utterances from which the tile forms run (launch_iteration)
+
+// The launches of ONE iteration of the chain over the a.B utterances of `a` (POOL: the tick's active entries): the input layer
+// when `in` (prologue positions and the first generation step of a launch sequence run their own; later steps get it from
+// the tail of the step before), the L layers, and when `gen` the 1x1 mat-vecs and the tail.  `it` is the iteration every
+// kernel takes: the absolute one, POOL: the tick-local one.  STREAM: the tails write chunk-local rows.
+template <bool POOL, bool STREAM, int KIND>
+void launch_iteration_of(const StA<POOL>& a, int it, bool in, bool gen, hipStream_t st) {
+    const SwnGeom& g = a.g;
+    const int n = a.B;
+    // up to 64 utterances: one utterance per workgroup (weights re-read per utterance from the Infinity Cache;
+    // measured faster than sharing: B=8 63 vs 137 us/step, B=64 162 vs 182 us/step on REF6);
+    // otherwise tiles of 8 utterances share one weight fetch and are processed concurrently (a pool has at most 64 entries)
+    const bool solo = n <= 64;
+    const unsigned by = solo ? (unsigned)n : (unsigned)((n + 7) / 8);
+    // many utterances: tiles of 8 channel pairs (rows) x 8 utterances (step_layer_tile / rowvec_tile)
+    const bool seq = n >= ST_SEQ;                              // measured crossover at REF6: 16 utterances 47 (solo) / 53 us per step, 24: 59 / 56
+    const unsigned sy = (unsigned)((n + ST_TU - 1) / ST_TU);
+    if (in) hipLaunchKernelGGL((step_in_kernel<KIND, POOL>), dim3(n), dim3(256), 0, st, a, it);
+    auto layer = [&](auto ni_, int l) {
+        constexpr int NI = decltype(ni_)::value;
+        if (seq) hipLaunchKernelGGL((step_layer_tile_kernel<NI, KIND, POOL>), dim3((g.H + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU),
+                                    (size_t)ST_TU * NI * 256 * sizeof(float), st, a, l, it);
+        else if (solo) hipLaunchKernelGGL((step_layer_kernel<NI, KIND, 1, POOL>), dim3(g.H, by), dim3(64), 0, st, a, l, it);
+        else if constexpr (!POOL) hipLaunchKernelGGL((step_layer_kernel<NI, KIND, 8>), dim3(g.H, by), dim3(64), 0, st, a, l, it);
+    };
+    const int ni = (g.K * g.Hp + 255) / 256;
+    for (int l = 0; l < g.L; ++l) {
+        if (ni <= 1) layer(std::integral_constant<int, 1>{}, l);
+        else if (ni <= 6) layer(std::integral_constant<int, 6>{}, l);
+        else layer(std::integral_constant<int, 8>{}, l);
+    }
+    if (!gen) return;
+    auto rowvec = [&](int rows, size_t w_off, int ldw, size_t b_off, int nin, int x_off, int y_off, int relu) {
+        if (seq && nin <= 1280) hipLaunchKernelGGL((rowvec_tile_kernel<5, POOL>), dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 5 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
+        else if (seq && nin <= 2304) hipLaunchKernelGGL((rowvec_tile_kernel<9, POOL>), dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 9 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
+        else if (solo) hipLaunchKernelGGL((rowvec_kernel<1, POOL>), dim3(rows, by), dim3(64), 0, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
+        else if constexpr (!POOL) hipLaunchKernelGGL((rowvec_kernel<8>), dim3(rows, by), dim3(64), 0, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
+    };
+    rowvec(g.S, a.y.wsk, g.L * g.Hp, a.y.bsk, g.L * g.Hp, a.o_hcat, a.o_skip, 1);
+    rowvec(g.O1, a.y.w1, g.Sp, a.y.b1, g.Sp, a.o_skip, a.o_o1, 1);
+    if (a.o2_by_rowvec) rowvec(g.NO, a.y.w2, g.O1p, a.y.b2, g.O1p, a.o_o1, a.o_o2, 0);
+    if constexpr (KIND == SWN_KIND_LAPLACE) {
+        // Laplace heads of up to 16 rows over up to 512 inputs, K <= 8 taps, <= 1 024 input-layer elements: the prefetching tail
+        if (g.NO <= 16 && g.O1p <= 512 && g.K <= 8 && g.H * g.seg <= 1024 && g.seg <= 16 && a.WN <= 32) {
+            if (g.H * g.seg <= 256) hipLaunchKernelGGL((step_tail_laplace_kernel<1, STREAM, POOL>), dim3(n), dim3(256), 0, st, a, it);
+            else hipLaunchKernelGGL((step_tail_laplace_kernel<4, STREAM, POOL>), dim3(n), dim3(256), 0, st, a, it);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((step_tail_kernel<KIND, STREAM, POOL>), dim3(n), dim3(256), 0, st, a, it);
+}
+template <bool POOL, bool STREAM>
+void launch_iteration(const StA<POOL>& a, int it, bool in, bool gen, hipStream_t st) {
+    if (a.g.kind == SWN_KIND_LAPLACE) launch_iteration_of<POOL, STREAM, SWN_KIND_LAPLACE>(a, it, in, gen, st);
+    else launch_iteration_of<POOL, STREAM, SWN_KIND_SOFTMAX>(a, it, in, gen, st);
+}
+
+// the launch chain of steps [step0, step0 + n_steps); stream = a chunk of a streamed decode: `state` is the session, which the
+// prologue fills only when !resume, and the tails take their STREAM form (chunk-local rows).  stream = false: swn_decode_stepped.
+int stepped_run(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int step0,
+                int n_steps, bool stream, bool resume, const SwnNoise* nz, const void* forced, const void* seed,
+                float* state, void* out, float* heads, void* stream_) {
+    StArgs a;
+    int rc = swn_make_geom(d, &a.g);
+    if (rc < 0) return rc;
+    if (!chain_takes(a.g, batch)) return SWN_E_UNSUPPORTED;
+    fill_args(a, packed, cond, *nz, forced, seed, state, out, heads, batch, n_frames, n_steps, step0);
+    hipStream_t st = (hipStream_t)stream_;
+    if (!resume) {
+        if (hipMemsetAsync(state, 0, sizeof(float) * (size_t)a.stride * batch, st) != hipSuccess) return SWN_E_LAUNCH;
+        if (a.g.kind == SWN_KIND_SOFTMAX || seed) hipLaunchKernelGGL(step_seed_kernel, dim3(batch), dim3(64), 0, st, a);
+    }
+    if (batch >= ST_SEQ) {
+        static bool attr_set = false;
+        if (!attr_set) {
+            if (!allow_tile_lds<false>()) return SWN_E_LAUNCH;
+            attr_set = true;
+        }
+    }
+    // iterations: the prologue positions (not when resuming), then the chunk's generation steps at absolute indices
+    const int it_gen0 = a.n_pro + step0, total = it_gen0 + n_steps;
+    for (int it = resume ? it_gen0 : 0; it < total; ++it) {
+        const bool in = it < a.n_pro || it == it_gen0, gen = it >= a.n_pro;
+        if (stream) launch_iteration<false, true>(a, it, in, gen, st);
+        else launch_iteration<false, false>(a, it, in, gen, st);
+    }
+    return swn_launch_status("swn_decode(stepped)");
+}
+
 }  // namespace
 
 extern "C" size_t swn_decode_stepped_state_floats(const swn_net_desc* d, int batch) {
     StArgs a;
     if (swn_make_geom(d, &a.g) < 0 || batch < 1) return 0;
     return (size_t)plan(a) * batch;
-}
-
-// the launch chain of steps [step0, step0 + n_steps); stream = a chunk of a streamed decode: `state` is the session, which the
-// prologue fills only when !resume, and the tails take their STREAM form (chunk-local rows).  stream = false: swn_decode_stepped.
-static int stepped_run(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int step0,
-                       int n_steps, bool stream, bool resume, const SwnNoise* nz, const void* forced, const void* seed,
-                       float* state, void* out, float* heads, void* stream_) {
-    StArgs a;
-    int rc = swn_make_geom(d, &a.g);
-    if (rc < 0) return rc;
-    const SwnGeom& g = a.g;
-    const int ni = (g.K * g.Hp + 255) / 256;
-    if (ni > 8 || g.seg > 16 || g.lpc > 16 || g.NO > 4096) return SWN_E_UNSUPPORTED;
-    { StArgs t; t.g = a.g; if ((size_t)plan(t) * batch * sizeof(float) >= (1ull << 31) || t.WN > 32) return SWN_E_UNSUPPORTED; }   // 32-bit buffer offsets; LDS window
-    swn_make_layout(&a.g, &a.y);
-    plan(a);
-    a.P = packed; a.cond = cond; a.nz = *nz; a.forced = forced; a.seed = seed; a.state = state; a.out = out; a.heads = heads;
-    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.n_pro = g.rf - g.seg + 1; a.step0 = step0;
-    // one 256-thread workgroup evaluates 8 rows per pass: beyond 64 rows (8 passes, ~7 us) a launch of its own is cheaper
-    a.o2_by_rowvec = g.NO > 64 ? 1 : 0;
-    hipStream_t st = (hipStream_t)stream_;
-    if (!resume) {
-        if (hipMemsetAsync(state, 0, sizeof(float) * (size_t)a.stride * batch, st) != hipSuccess) return SWN_E_LAUNCH;
-        if (g.kind == SWN_KIND_SOFTMAX || seed) hipLaunchKernelGGL(step_seed_kernel, dim3(batch), dim3(64), 0, st, a);
-    }
-    // up to 64 utterances: one utterance per workgroup (weights re-read per utterance from the Infinity Cache;
-    // measured faster than sharing: B=8 63 vs 137 us/step, B=64 162 vs 182 us/step on REF6);
-    // otherwise tiles of 8 utterances share one weight fetch and are processed concurrently
-    const bool solo = batch <= 64;
-    const unsigned by = solo ? (unsigned)batch : (unsigned)((batch + 7) / 8);
-    // many utterances: tiles of 8 channel pairs (rows) x 8 utterances (step_layer_tile / rowvec_tile)
-    const bool seq = batch >= 24;                              // measured crossover at REF6: 16 utterances 47 (solo) / 53 us per step, 24: 59 / 56
-    const unsigned sy = (unsigned)((batch + ST_TU - 1) / ST_TU);
-    if (seq) {
-        static bool attr_set = false;                          // dynamic LDS above 64 KB (NI = 8: 64 KB, RV = 9: 72 KB)
-        if (!attr_set) {
-            const int big = 72 * 1024;
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_LAPLACE>), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_SOFTMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(rowvec_tile_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess)
-                return SWN_E_LAUNCH;
-            attr_set = true;
-        }
-    }
-#define SWN_LAYER(NI_, KIND_)                                                                                  \
-    do {                                                                                                        \
-        if (seq) hipLaunchKernelGGL((step_layer_tile_kernel<NI_, KIND_>), dim3((g.H + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), \
-                                    (size_t)ST_TU * NI_ * 256 * sizeof(float), st, a, l, it);                  \
-        else if (solo) hipLaunchKernelGGL((step_layer_kernel<NI_, KIND_, 1>), grid, dim3(64), 0, st, a, l, it);      \
-        else hipLaunchKernelGGL((step_layer_kernel<NI_, KIND_, 8>), grid, dim3(64), 0, st, a, l, it);           \
-    } while (0)
-    auto layers = [&](int it) {
-        for (int l = 0; l < g.L; ++l) {
-            dim3 grid(g.H, by);
-            if (g.kind == SWN_KIND_LAPLACE) {
-                if (ni <= 1) SWN_LAYER(1, SWN_KIND_LAPLACE);
-                else if (ni <= 6) SWN_LAYER(6, SWN_KIND_LAPLACE);
-                else SWN_LAYER(8, SWN_KIND_LAPLACE);
-            } else {
-                if (ni <= 1) SWN_LAYER(1, SWN_KIND_SOFTMAX);
-                else if (ni <= 6) SWN_LAYER(6, SWN_KIND_SOFTMAX);
-                else SWN_LAYER(8, SWN_KIND_SOFTMAX);
-            }
-        }
-    };
-#undef SWN_LAYER
-    auto rowvec = [&](int rows, size_t w_off, int ldw, size_t b_off, int nin, int x_off, int y_off, int relu) {
-        if (seq && nin <= 1280) hipLaunchKernelGGL(rowvec_tile_kernel<5>, dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 5 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu);
-        else if (seq && nin <= 2304) hipLaunchKernelGGL(rowvec_tile_kernel<9>, dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 9 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu);
-        else if (solo) hipLaunchKernelGGL(rowvec_kernel<1>, dim3(rows, by), dim3(64), 0, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu);
-        else hipLaunchKernelGGL(rowvec_kernel<8>, dim3(rows, by), dim3(64), 0, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu);
-    };
-    // Laplace heads of up to 16 rows over up to 512 inputs, K <= 8 taps, <= 1 024 input-layer elements: the prefetching tail
-    const bool fast_tail = g.kind == SWN_KIND_LAPLACE && g.NO <= 16 && g.O1p <= 512 && g.K <= 8 && g.H * g.seg <= 1024 &&
-                           g.seg <= 16 && a.WN <= 32;
-    // iterations: the prologue positions (not when resuming), then the chunk's generation steps at absolute indices
-    const int it_gen0 = a.n_pro + step0, total = it_gen0 + n_steps;
-    for (int it = resume ? it_gen0 : 0; it < total; ++it) {
-        // prologue positions and the first generation step of the launch sequence run their own input layer; later
-        // steps get it from the tail of the step before
-        if (it < a.n_pro || it == it_gen0) {
-            if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(step_in_kernel<SWN_KIND_LAPLACE>, dim3(batch), dim3(256), 0, st, a, it);
-            else hipLaunchKernelGGL(step_in_kernel<SWN_KIND_SOFTMAX>, dim3(batch), dim3(256), 0, st, a, it);
-        }
-        layers(it);
-        if (it < a.n_pro) continue;
-        rowvec(g.S, a.y.wsk, g.L * g.Hp, a.y.bsk, g.L * g.Hp, a.o_hcat, a.o_skip, 1);
-        rowvec(g.O1, a.y.w1, g.Sp, a.y.b1, g.Sp, a.o_skip, a.o_o1, 1);
-        if (a.o2_by_rowvec) rowvec(g.NO, a.y.w2, g.O1p, a.y.b2, g.O1p, a.o_o1, a.o_o2, 0);
-        if (stream) {
-            if (fast_tail) {
-                if (g.H * g.seg <= 256) hipLaunchKernelGGL((step_tail_laplace_kernel<1, true>), dim3(batch), dim3(256), 0, st, a, it);
-                else hipLaunchKernelGGL((step_tail_laplace_kernel<4, true>), dim3(batch), dim3(256), 0, st, a, it);
-            } else if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL((step_tail_kernel<SWN_KIND_LAPLACE, true>), dim3(batch), dim3(256), 0, st, a, it);
-            else hipLaunchKernelGGL((step_tail_kernel<SWN_KIND_SOFTMAX, true>), dim3(batch), dim3(256), 0, st, a, it);
-        } else if (fast_tail) {
-            if (g.H * g.seg <= 256) hipLaunchKernelGGL(step_tail_laplace_kernel<1>, dim3(batch), dim3(256), 0, st, a, it);
-            else hipLaunchKernelGGL(step_tail_laplace_kernel<4>, dim3(batch), dim3(256), 0, st, a, it);
-        } else if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(step_tail_kernel<SWN_KIND_LAPLACE>, dim3(batch), dim3(256), 0, st, a, it);
-        else hipLaunchKernelGGL(step_tail_kernel<SWN_KIND_SOFTMAX>, dim3(batch), dim3(256), 0, st, a, it);
-    }
-    return swn_launch_status("swn_decode(stepped)");
 }
 
 extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
@@ -1130,11 +1081,9 @@ extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, co
 
 // 1 when the stepped chain runs this (net, batch) (the conditions swn_decode_stepped returns SWN_E_UNSUPPORTED under)
 extern "C" int swn_decode_stepped_supported(const swn_net_desc* d, int batch) {
-    StArgs t;
-    if (swn_make_geom(d, &t.g) < 0 || batch < 1) return 0;
-    const SwnGeom& g = t.g;
-    if ((g.K * g.Hp + 255) / 256 > 8 || g.seg > 16 || g.lpc > 16 || g.NO > 4096) return 0;
-    return ((size_t)plan(t) * batch * sizeof(float) < (1ull << 31) && t.WN <= 32) ? 1 : 0;
+    SwnGeom g;
+    if (swn_make_geom(d, &g) < 0 || batch < 1) return 0;
+    return chain_takes(g, batch) ? 1 : 0;
 }
 
 // one chunk of a streamed decode; the session is the state buffer of the chain (swn_decode_stepped_state_floats())
@@ -1187,18 +1136,9 @@ extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float*
     }
     if (n_max > 0 && !out) return SWN_E_BADARG;
     if (!swn_decode_stepped_supported(d, capacity)) return SWN_E_UNSUPPORTED;
-    const int ni = (g.K * g.Hp + 255) / 256;
     if (!any_begin && it_max == 0) return SWN_OK;           // every slot stays as it is
 
-    swn_make_layout(&a.g, &a.y);
-    plan(a);
-    SwnNoise nz;
-    nz.ptr = nullptr; nz.dump = io->noise_out_dev;
-    nz.key0 = (uint32_t)(io->rng_seed & 0xffffffffu); nz.key1 = (uint32_t)(io->rng_seed >> 32); nz.utt0 = io->rng_utt0;
-    nz.ids = io->rng_utt_ids_dev;
-    a.P = packed; a.cond = nullptr; a.nz = nz; a.forced = nullptr; a.seed = io->seed_dev; a.state = session; a.out = out;
-    a.heads = heads; a.B = n_entries; a.Tf = 0; a.n_steps = n_max; a.n_pro = n_pro; a.step0 = 0;
-    a.o2_by_rowvec = g.NO > 64 ? 1 : 0;
+    fill_args(a, packed, nullptr, swn_pool_noise_of(io), nullptr, io->seed_dev, session, out, heads, n_entries, 0, n_max, 0);
     // the table, sorted by n_it (descending, stable): the entries active at tick-local iteration j are a prefix of it
     StPoolTable t = {};
     int order[SWN_DECODE_POOL_MAX_ENTRIES];
@@ -1226,17 +1166,9 @@ extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float*
     for (int j = 0; j < it_max && !any_seq; ++j) {
         int nact = 0;
         while (nact < n_entries && t.e[nact].n_it > j) ++nact;
-        any_seq = nact >= 24;
+        any_seq = nact >= ST_SEQ;
     }
-    if (any_seq) {
-        const int big = 72 * 1024;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_LAPLACE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_SOFTMAX, true>), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(rowvec_tile_pool_kernel<9>), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess)
-            return SWN_E_LAUNCH;
-    }
-    const bool fast_tail = g.kind == SWN_KIND_LAPLACE && g.NO <= 16 && g.O1p <= 512 && g.K <= 8 && g.H * g.seg <= 1024 &&
-                           g.seg <= 16 && a.WN <= 32;
+    if (any_seq && !allow_tile_lds<true>()) return SWN_E_LAUNCH;
     int nact = n_entries;
     for (int j = 0; j < it_max; ++j) {
         while (nact > 0 && t.e[nact - 1].n_it <= j) --nact;
@@ -1247,44 +1179,7 @@ extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float*
             need_gen = need_gen || it >= t.e[k].g0;
         }
         a.B = nact;
-        const bool seq = nact >= 24;
-        const unsigned sy = (unsigned)((nact + ST_TU - 1) / ST_TU);
-        if (need_in) {
-            if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL((step_in_kernel<SWN_KIND_LAPLACE, true>), dim3(nact), dim3(256), 0, st, a, j);
-            else hipLaunchKernelGGL((step_in_kernel<SWN_KIND_SOFTMAX, true>), dim3(nact), dim3(256), 0, st, a, j);
-        }
-#define SWN_PLAYER(NI_, KIND_)                                                                                 \
-        do {                                                                                                    \
-            if (seq) hipLaunchKernelGGL((step_layer_tile_kernel<NI_, KIND_, true>), dim3((g.H + ST_TU - 1) / ST_TU, sy),  \
-                                        dim3(64 * ST_TU), (size_t)ST_TU * NI_ * 256 * sizeof(float), st, a, l, j);   \
-            else hipLaunchKernelGGL((step_layer_kernel<NI_, KIND_, 1, true>), dim3(g.H, nact), dim3(64), 0, st, a, l, j); \
-        } while (0)
-        for (int l = 0; l < g.L; ++l) {
-            if (g.kind == SWN_KIND_LAPLACE) {
-                if (ni <= 1) SWN_PLAYER(1, SWN_KIND_LAPLACE);
-                else if (ni <= 6) SWN_PLAYER(6, SWN_KIND_LAPLACE);
-                else SWN_PLAYER(8, SWN_KIND_LAPLACE);
-            } else {
-                if (ni <= 1) SWN_PLAYER(1, SWN_KIND_SOFTMAX);
-                else if (ni <= 6) SWN_PLAYER(6, SWN_KIND_SOFTMAX);
-                else SWN_PLAYER(8, SWN_KIND_SOFTMAX);
-            }
-        }
-#undef SWN_PLAYER
-        if (!need_gen) continue;
-        auto rowvec = [&](int rows, size_t w_off, int ldw, size_t b_off, int nin, int x_off, int y_off, int relu) {
-            if (seq && nin <= 1280) hipLaunchKernelGGL(rowvec_tile_pool_kernel<5>, dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 5 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, j);
-            else if (seq && nin <= 2304) hipLaunchKernelGGL(rowvec_tile_pool_kernel<9>, dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 9 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, j);
-            else hipLaunchKernelGGL(rowvec_pool_kernel, dim3(rows, nact), dim3(64), 0, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, j);
-        };
-        rowvec(g.S, a.y.wsk, g.L * g.Hp, a.y.bsk, g.L * g.Hp, a.o_hcat, a.o_skip, 1);
-        rowvec(g.O1, a.y.w1, g.Sp, a.y.b1, g.Sp, a.o_skip, a.o_o1, 1);
-        if (a.o2_by_rowvec) rowvec(g.NO, a.y.w2, g.O1p, a.y.b2, g.O1p, a.o_o1, a.o_o2, 0);
-        if (fast_tail) {
-            if (g.H * g.seg <= 256) hipLaunchKernelGGL((step_tail_laplace_kernel<1, true, true>), dim3(nact), dim3(256), 0, st, a, j);
-            else hipLaunchKernelGGL((step_tail_laplace_kernel<4, true, true>), dim3(nact), dim3(256), 0, st, a, j);
-        } else if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL((step_tail_kernel<SWN_KIND_LAPLACE, true, true>), dim3(nact), dim3(256), 0, st, a, j);
-        else hipLaunchKernelGGL((step_tail_kernel<SWN_KIND_SOFTMAX, true, true>), dim3(nact), dim3(256), 0, st, a, j);
+        launch_iteration<true, true>(a, j, need_in, need_gen, st);
     }
     return swn_launch_status("swn_decode_pool_stepped_chunk");
 }
