@@ -127,6 +127,43 @@ size_t swn_cond_floats(const swn_net_desc* d, int batch, int n_frames);
 int    swn_frontend(const swn_net_desc* d, const float* packed_dev, const float* aux_dev,
                     int batch, int n_frames, float* work_dev, float* cond_dev, void* stream);
 
+/* ---- pool front end: the conditioning of many independent sessions finalised by one call --------------------------------
+ * The ragged form of swn_frontend for a decode pool's tick (csrc/swn_frontend_pool.hip).  Entry e of the table is one session
+ * at its own position: its feature buffer aux_dev, channel-major (n_aux, aux_stride), holds frames [0, n_received) once the
+ * call has appended the n_new frames new_dev (n_aux, n_new) - a slice of a staging buffer all entries may share - at frames
+ * [n_received - n_new, n_received); the call then writes the cond rows of the absolute frames [f0, f1) to
+ * cond_dev + frame * N (N = L*seg*2H, the row of swn_frontend), and no other row.  Every row is bit-identical to the row
+ * swn_frontend writes for the whole utterance: the same fmaf chains, frames outside [0, n_received) read as zero at every
+ * layer.  Without SWN_FRONTEND_FINAL more features may follow, so only frames whose right context has arrived can be written:
+ * f1 <= max(0, n_received - lookahead), lookahead = sum over conv_aux layers of dilation * (k - 1) / 2.  With it the features
+ * end at n_received (the one-shot front end's zero padding on the right) and f1 <= n_received.
+ * The call makes 3 + aux_dilation_size launches whatever n_entries is (the first one only when nothing is kept), works on the
+ * concatenated frame list of all entries, and neither copies nor synchronises on the host: the table travels in the first
+ * launch's arguments, which leaves a device copy at the head of work_dev for the others.
+ *   work_dev  swn_frontend_pool_work_floats(d, entries_host, n_entries) floats of scratch (0 = the table is refused)
+ * An entry with f1 == f0 and n_new == 0 does nothing.  SWN_E_BADARG, checked before anything is launched: a null pointer
+ * (new_dev may be NULL when n_new == 0), n_entries outside [1, SWN_FRONTEND_POOL_MAX_ENTRIES], f0 < 0, f1 < f0, n_new < 0,
+ * n_new > n_received, aux_stride < n_received, the bounds on f1 above, a cond_dev that is not 16-byte aligned when N is a multiple
+ * of 4 (rows are then stored in 16-byte pieces), the same cond_dev in two entries, an unknown flag or a
+ * non-zero reserved field, more than 2^24 frames in one stage over all entries.
+ * sizeof(swn_frontend_pool_entry) == 56. */
+typedef struct swn_frontend_pool_entry {
+    float*       aux_dev;      /* this session's feature buffer (n_aux, aux_stride); frames [n_received - n_new, n_received) are written */
+    const float* new_dev;      /* (n_aux, n_new) new frames, or NULL with n_new == 0 */
+    float*       cond_dev;     /* this session's cond rows, 16-byte aligned (N % 4 == 0), at least f1 rows of N floats; rows [f0, f1) are written */
+    int32_t aux_stride;        /* frames per channel row of aux_dev, >= n_received */
+    int32_t n_received;        /* frames received, the n_new new ones included */
+    int32_t n_new;             /* >= 0 */
+    int32_t f0, f1;            /* absolute frames whose cond rows the call writes, 0 <= f0 <= f1 */
+    int32_t flags;             /* SWN_FRONTEND_FINAL: the features end at n_received */
+    int32_t reserved[2];       /* 0 */
+} swn_frontend_pool_entry;
+#define SWN_FRONTEND_POOL_MAX_ENTRIES 64
+#define SWN_FRONTEND_FINAL 1
+size_t swn_frontend_pool_work_floats(const swn_net_desc* d, const swn_frontend_pool_entry* entries_host, int n_entries);
+int    swn_frontend_pool(const swn_net_desc* d, const float* packed_dev, const swn_frontend_pool_entry* entries_host,
+                         int n_entries, float* work_dev, void* stream);
+
 /* ---- autoregressive decode  (CSWNV.batch_fast_generate cswnv_shift1.py:287-430,
  *                              DSWNV.batch_fast_generate dswnv.py:296-399) ---------------
  * One persistent workgroup per utterance runs prologue (rf+1 seed positions) and all

@@ -48,6 +48,13 @@ class DecodeSteppedPoolEntry(ctypes.Structure):
                 ("n_it", c_int32), ("flags", c_int32), ("reserved", c_int32)]
 
 
+class FrontendPoolEntry(ctypes.Structure):
+    """mirror of `swn_frontend_pool_entry` (include/swn_hip.h): one session's share of a pool front end call."""
+    _fields_ = [("aux_dev", c_void_p), ("new_dev", c_void_p), ("cond_dev", c_void_p), ("aux_stride", c_int32),
+                ("n_received", c_int32), ("n_new", c_int32), ("f0", c_int32), ("f1", c_int32), ("flags", c_int32),
+                ("reserved", c_int32 * 2)]
+
+
 class PostfilterEntry(ctypes.Structure):
     """mirror of `swn_postfilter_entry` (include/swn_hip.h): one session's share of a post-filter call."""
     _fields_ = [("in_dev", c_void_p), ("out_dev", c_void_p), ("slot", c_int32), ("n", c_int32), ("kind", c_int32),
@@ -57,6 +64,8 @@ class PostfilterEntry(ctypes.Structure):
 ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
 DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
+FRONTEND_POOL_MAX_ENTRIES = 64                 # SWN_FRONTEND_POOL_MAX_ENTRIES (include/swn_hip.h): entries per front end call
+FRONTEND_FINAL = 1                             # SWN_FRONTEND_FINAL: the entry's features end at n_received
 CHUNK_BEGIN = 1                                # SWN_CHUNK_BEGIN (include/swn_hip.h): first chunk of a streamed decode
 PRECISION_FP32, PRECISION_BF16 = 0, 1          # SWN_PRECISION_* (include/swn_hip.h)
 POSTFILTER_IN_F32, POSTFILTER_IN_MULAW = 0, 1   # SWN_POSTFILTER_IN_* (include/swn_hip.h)
@@ -94,6 +103,8 @@ SIGNATURES = {
     "swn_frontend_work_floats": (c_size_t, [POINTER(NetDesc), c_int, c_int]),
     "swn_cond_floats": (c_size_t, [POINTER(NetDesc), c_int, c_int]),
     "swn_frontend": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "swn_frontend_pool_work_floats": (c_size_t, [POINTER(NetDesc), POINTER(FrontendPoolEntry), c_int]),
+    "swn_frontend_pool": (c_int, [POINTER(NetDesc), c_void_p, POINTER(FrontendPoolEntry), c_int, c_void_p, c_void_p]),
     "swn_decode_state_floats": (c_size_t, [POINTER(NetDesc), c_int]),
     "swn_decode": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecodeIO),
                            c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

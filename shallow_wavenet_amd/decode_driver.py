@@ -264,12 +264,15 @@ def pool_decode(kind: str, args, model, feat_list: Sequence[str], global_index: 
     live = {}                                   # session -> (utterance id, n_samples, out pieces, restored pieces)
     t0, n_tot = time.time(), 0
     while pending or live:
+        admitted = {}                           # every slot that is free this tick: one front end call for all of them
         while pending and len(live) < args.pool_slots:
             i = pending.pop(0)
             h = read_feature(feat_list[i], string_path)
             s = pool.open(utt_id=int(global_index[i]))
-            s.finish(torch.from_numpy(np.ascontiguousarray(h.T[None])).to(device, torch.float32))
+            admitted[s] = torch.from_numpy(np.ascontiguousarray(h.T[None])).to(torch.float32)
             live[s] = (os.path.splitext(os.path.basename(feat_list[i]))[0], h.shape[0] * int(cfg.U), [], [])
+        if admitted:
+            pool.push_many(admitted, finish=list(admitted))
         for s, r in pool.step().items():
             live[s][2].append(r[0])
             if restorer is not None:

@@ -13,6 +13,7 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
 
     torch.ops.swn.pack_params(tensors, desc)                       -> packed
     torch.ops.swn.frontend(packed, aux, desc)                      -> (cond, work)
+    torch.ops.swn.frontend_pool(packed, auxs, conds, staged?, n_news, n_receiveds, f0s, f1s, finals, desc)  -> ()
     torch.ops.swn.decode(packed, cond, noise?, forced?, seed?, desc, n_steps, variant, rng_seed, rng_utt0,
                          want_heads, want_noise, utt_ids?)         -> (out, heads, noise_used)
     torch.ops.swn.decode_chunk(packed, cond, session, noise?, forced?, seed?, desc, step0, n_steps, begin, variant,
@@ -158,6 +159,70 @@ def _(packed, aux, desc):
     r = ctypes.byref(d)
     n = L.swn_cond_floats(r, B, Tf)
     return packed.new_empty((B, Tf, n // (B * Tf))), packed.new_empty(L.swn_frontend_work_floats(r, B, Tf))
+
+
+# ------------------------------------------------------------------------------------------ pool front end
+def frontend_pool_impl(packed: torch.Tensor, auxs: List[torch.Tensor], conds: List[torch.Tensor],
+                       staged: Optional[torch.Tensor], n_news: List[int], n_receiveds: List[int], f0s: List[int],
+                       f1s: List[int], finals: List[bool], desc: List[int]) -> None:
+    """one front end call for the sessions of a pool tick (swn_frontend_pool): entry e appends its n_news[e] new frames - the
+    next n_aux * n_news[e] floats of `staged`, the flat concatenation of the entries' (n_aux, n_new) chunks - to its feature
+    buffer auxs[e] (n_aux, stride) at frames [n_receiveds[e] - n_news[e], n_receiveds[e]) and writes the cond rows of the
+    absolute frames [f0s[e], f1s[e]) into conds[e] (rows, N); finals[e]: the features end at n_receiveds[e].  Both lists are
+    updated in place; the rows are bit-identical to `frontend` over the whole utterance."""
+    L = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(packed, "the packed parameters")
+    dev = packed.device
+    E = len(auxs)
+    if not (len(conds) == len(n_news) == len(n_receiveds) == len(f0s) == len(f1s) == len(finals) == E):
+        raise RuntimeError("frontend_pool: auxs, conds, n_news, n_receiveds, f0s, f1s and finals must have one entry each")
+    if not 1 <= E <= _lib.FRONTEND_POOL_MAX_ENTRIES:
+        raise RuntimeError(f"frontend_pool: {E} entries, a call takes 1 .. {_lib.FRONTEND_POOL_MAX_ENTRIES}")
+    na = d.n_aux
+    total_new = sum(int(n) for n in n_news)
+    base = 0
+    if total_new > 0:
+        if staged is None or staged.device != dev or staged.dtype != torch.float32 or not staged.is_contiguous():
+            raise RuntimeError("frontend_pool: staged must be a contiguous fp32 tensor on the device of the packed parameters")
+        if staged.numel() != na * total_new:
+            raise RuntimeError(f"frontend_pool: staged holds {staged.numel()} floats, the entries' new frames need {na * total_new}")
+        base = staged.data_ptr()
+    table = (_lib.FrontendPoolEntry * E)()
+    r = ctypes.byref(d)
+    N = L.swn_cond_floats(r, 1, 1)
+    off = 0
+    for e in range(E):
+        a, c = auxs[e], conds[e]
+        if a.device != dev or a.dtype != torch.float32 or not a.is_contiguous() or a.dim() < 2 or \
+                a.numel() != na * a.shape[-1]:
+            raise RuntimeError("frontend_pool: every feature buffer must be a contiguous (n_aux, stride) fp32 tensor on the device")
+        if c.device != dev or c.dtype != torch.float32 or not c.is_contiguous() or c.dim() != 2 or c.shape[1] != N:
+            raise RuntimeError("frontend_pool: every cond buffer must be a contiguous (rows, N) fp32 tensor on the device")
+        n_new, f1 = int(n_news[e]), int(f1s[e])
+        if f1 > c.shape[0]:
+            raise RuntimeError(f"frontend_pool: entry {e} writes cond rows up to {f1}, its buffer has {c.shape[0]}")
+        t = table[e]
+        t.aux_dev, t.cond_dev = a.data_ptr(), c.data_ptr()
+        t.new_dev = base + 4 * na * off if n_new > 0 else None
+        t.aux_stride, t.n_received, t.n_new = int(a.shape[-1]), int(n_receiveds[e]), n_new
+        t.f0, t.f1, t.flags = int(f0s[e]), f1, _lib.FRONTEND_FINAL if finals[e] else 0
+        off += max(n_new, 0)
+    floats = L.swn_frontend_pool_work_floats(r, table, E)
+    if floats == 0:
+        raise RuntimeError("swn_hip frontend_pool: bad argument: the entry table is refused (frame ranges, strides, flags or a "
+                           "cond buffer in two entries)")
+    work = torch.empty(floats, dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(L.swn_frontend_pool(r, _ptr(packed), table, E, _ptr(work), _stream(dev)), "frontend_pool")
+
+
+frontend_pool = custom_op("swn::frontend_pool", mutates_args=("auxs", "conds"))(frontend_pool_impl)
+
+
+@frontend_pool.register_fake
+def _(packed, auxs, conds, staged, n_news, n_receiveds, f0s, f1s, finals, desc):
+    return None
 
 
 # ------------------------------------------------------------------------------------------ decode
@@ -831,6 +896,6 @@ class SpectralLossFunction(torch.autograd.Function):
         return spectral_loss_backward_impl(g_l1, state, tables, ctx.sizes, ctx.length), None, None, None
 
 
-OP_NAMES = ("pack_params", "frontend", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk", "postfilter_chunk",
+OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk", "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward")

@@ -10,6 +10,10 @@ halo la = lookahead_frames(cfg).  After R frames have arrived, frames [0, R - la
 the inputs the one-shot front end sees, so their cond rows are bit-identical.  `finish` ends the features; the front end's
 own zero padding on the right then is the one-shot padding, and every remaining frame becomes final.
 
+Pools.  DecodePool.push_many hands a whole tick of sessions their features at once: plan_push turns their frame counts into
+the entries of one swn_frontend_pool call, which appends every chunk and writes every new final row in a fixed number of
+launches (csrc/swn_frontend_pool.hip), bit-identical to the per-session pushes.
+
 Steps.  A generation step i reads cond frames up to ((i + 1) * seg - 1) // U, so with F final frames the steps
 [0, F * U // seg) can run (the bound of swn_decode).  Step counts come from frame counts on the host: nothing here
 waits for the device.
@@ -258,6 +262,34 @@ def plan_tick(sessions: Sequence[Tuple[object, int, int]], max_steps: Optional[i
     return [entries[i:i + limit] for i in range(0, len(entries), limit)]
 
 
+def plan_push(sessions: Sequence[Tuple[object, int, int, int, bool]], lookahead: int,
+              limit: int = _lib.FRONTEND_POOL_MAX_ENTRIES) -> List[List[tuple]]:
+    """the front end calls of one batched push.  sessions: (key, frames_received, frames_final, n_new, finishing) of every
+    session that is handed features or ended, in the caller's order.  Each one's entry (key, n_received_after, f0, f1, final)
+    appends its n_new frames and finalises the frames [f0, f1) = [frames_final, final_frames(n_received_after)); sessions with
+    neither (an empty chunk) have no entry.  The entries are split into calls of at most `limit`.  Pure host arithmetic:
+    nothing here touches a device."""
+    lookahead, limit = int(lookahead), int(limit)
+    if lookahead < 0:
+        raise ValueError(f"lookahead must be >= 0, not {lookahead}")
+    if limit < 1:
+        raise ValueError(f"limit must be a positive integer, not {limit}")
+    entries = []
+    for key, received, done, n_new, finishing in sessions:
+        received, done, n_new, finishing = int(received), int(done), int(n_new), bool(finishing)
+        if received < 0 or n_new < 0:
+            raise ValueError(f"session {key!r}: frames_received and n_new must be >= 0")
+        if not 0 <= done <= final_frames(received, lookahead, False):
+            raise ValueError(f"session {key!r}: {done} final frames do not fit {received} received frames")
+        after = received + n_new
+        if finishing and after == 0:
+            raise ValueError(f"session {key!r} ends without ever having received features")
+        f1 = final_frames(after, lookahead, finishing)
+        if n_new > 0 or f1 > done:
+            entries.append((key, after, done, f1, finishing))
+    return [entries[i:i + limit] for i in range(0, len(entries), limit)]
+
+
 class PoolSession:
     """one utterance of a DecodePool.  push / finish hand it features (they only finalise conditioning: the pool's ticks
     generate); steps_ready / steps_done / finished tell where it stands.  Made by DecodePool.open."""
@@ -320,6 +352,7 @@ class DecodePool:
 
         s = pool.open(seed=None, utt_id=None)   # a free slot; utt_id defaults to the admission counter
         s.push(aux_piece); s.finish(aux_tail)  # (1, n_aux, f) features
+        pool.push_many({s: aux_piece, ...}, finish=[...])   # the same for every session of a tick in ONE front end call
         results = pool.step(max_steps=None)    # one tick -> {session: (out, heads[, noise])}, views of the launch outputs
         pool.close(s)                          # frees the slot, finished or not
     """
@@ -401,6 +434,106 @@ class DecodePool:
                 h = heads[e:e + 1, :n] if self.want_heads else None
                 results[s] = (o, h, used[e:e + 1, :n]) if self.want_noise else (o, h)
         return self._post_filter(results)
+
+    # ------------------------------------------------------------------ batched features
+    def _check_push_many(self, chunks, finish) -> List[Tuple["PoolSession", Optional[torch.Tensor], bool]]:
+        """(session, chunk or None, finishing) of a push_many call in its order, or the error the separate calls would raise;
+        nothing is changed."""
+        if not isinstance(chunks, dict):
+            raise ValueError("chunks must map pool sessions to (1, n_aux, f) feature tensors")
+        finish = list(finish)
+        if len(set(map(id, finish))) != len(finish):
+            raise ValueError("a session is named twice in finish")
+        ending = set(map(id, finish))
+        order = [(s, c, id(s) in ending) for s, c in chunks.items()] + [(s, None, True) for s in finish if s not in chunks]
+        for s, c, fin in order:
+            if not isinstance(s, PoolSession) or s.closed or self._open.get(s.slot) is not s:
+                if isinstance(s, PoolSession) and s._pool is self and s.closed:
+                    raise RuntimeError(f"pool session {s.utt_id} (slot {s.slot}) is closed")
+                raise RuntimeError("this session is not open in this pool")
+            st = s._stream
+            if st.finished:
+                raise RuntimeError(f"pool session {s.utt_id} is finished: no features can be pushed after finish()")
+            if c is not None:
+                if not isinstance(c, torch.Tensor) or c.dim() != 3:
+                    raise ValueError("features must be a (1, n_aux, frames) tensor")
+                if c.shape[0] != 1:
+                    raise ValueError(f"features for {c.shape[0]} utterances pushed to a pool session (batch 1)")
+                if c.shape[1] != self.cfg.n_aux:
+                    raise ValueError(f"features have {c.shape[1]} channels, the model expects {self.cfg.n_aux}")
+            if fin and st.frames_received + (0 if c is None else c.shape[2]) == 0:
+                raise RuntimeError(f"pool session {s.utt_id} is named in finish but never received features")
+        return order
+
+    def _stage(self, pieces: List[torch.Tensor]) -> Optional[torch.Tensor]:
+        """the chunks of one call, flattened and concatenated in entry order, on the device: one host-to-device copy for the
+        host chunks, one cat for the device chunks."""
+        if not pieces:
+            return None
+        dev = self.net.device
+        flat = [c.reshape(-1) if c.dtype == torch.float32 else c.reshape(-1).to(torch.float32) for c in pieces]
+        host = [i for i, c in enumerate(flat) if not c.is_cuda]
+        if host:
+            up = (flat[host[0]] if len(host) == 1 else torch.cat([flat[i] for i in host])).to(dev)
+            if len(host) == len(flat):
+                return up
+            at = 0
+            for i in host:
+                n = flat[i].numel()
+                flat[i] = up[at:at + n]
+                at += n
+        return flat[0].contiguous() if len(flat) == 1 else torch.cat(flat)
+
+    def push_many(self, chunks: dict, finish: Sequence[PoolSession] = ()) -> None:
+        """one front end call for a whole tick of features: s.push(chunk) for every session of `chunks` ({session: (1, n_aux, f)
+        features on the host or the device, f >= 0}) and s.finish(chunk or None) for every session of `finish` (which may also
+        have a last chunk in `chunks`), with the same counters and bit-identical cond rows afterwards.  The chunks are staged
+        with one copy and finalised by one swn_frontend_pool call per 64 sessions, which appends them to the sessions' feature
+        buffers and writes the cond rows where the decode reads them.  Everything is checked first, and the counters move only
+        after every call is enqueued: a call that raises leaves every session's frames_received, frames_final, steps_ready,
+        finished and cond rows [0, frames_final) as they were.  Its _aux and _cond buffers may already have been grown
+        (new objects, old contents kept) and frames appended past frames_received, where the next push overwrites them."""
+        order = self._check_push_many(chunks, finish)
+        la = lookahead_frames(self.cfg)
+        calls = plan_push([(i, s._stream.frames_received, s._stream.frames_final, 0 if c is None else c.shape[2], fin)
+                           for i, (s, c, fin) in enumerate(order)], la)
+        dev = self.net.device
+        for entries in calls:
+            auxs, conds, pieces = [], [], []
+            for i, after, f0, f1, _fin in entries:
+                s, c, _ = order[i]
+                st = s._stream
+                if after > st.frames_received:
+                    st._aux = st._grow(st._aux, 2, after, (1, self.cfg.n_aux, 0), dev)
+                    pieces.append(c)
+                if f1 > f0:
+                    st._cond = st._grow(st._cond, 1, f1, (1, 0, self._cond_width()), dev)
+                auxs.append(st._aux[0])
+                # nothing final yet (the session only appends): the call still wants a row pointer of its own
+                conds.append(st._cond[0] if st._cond is not None else self._spare_cond(len(conds)))
+            _O.frontend_pool(self.net.packed, auxs, conds, self._stage(pieces),
+                             [e[1] - order[e[0]][0]._stream.frames_received for e in entries], [e[1] for e in entries],
+                             [e[2] for e in entries], [e[3] for e in entries], [e[4] for e in entries], self.net.dlist)
+        # every call has been enqueued: only now do the sessions move (a call that raised left the counters as they were)
+        for entries in calls:
+            for i, after, _f0, f1, _fin in entries:
+                st = order[i][0]._stream
+                st.frames_received, st.frames_final = after, f1
+        for s, _c, fin in order:
+            if fin:
+                s._stream.finished = True
+
+    def _spare_cond(self, e: int) -> torch.Tensor:
+        if getattr(self, "_spare", None) is None:
+            self._spare = torch.zeros((_lib.FRONTEND_POOL_MAX_ENTRIES, self._cond_width()), dtype=torch.float32,
+                                      device=self.net.device)
+        return self._spare[e:e + 1]
+
+    def _cond_width(self) -> int:
+        n = getattr(self, "_n_cond", None)
+        if n is None:
+            n = self._n_cond = int(_lib.lib().swn_cond_floats(_ops._desc(self.net.dlist), 1, 1))
+        return n
 
     def _post_filter(self, results: dict) -> dict:
         """with a post_filter: one call restores the outputs of every session of the tick, each result gains its row."""
