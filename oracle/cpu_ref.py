@@ -39,8 +39,10 @@ LOG_B_FLOOR = -14.162084148244246758816564788835   # cswnv_shift1.py:234
 
 
 # --------------------------------------------------------------------------- helpers
-def as_params(sd: Dict[str, np.ndarray]) -> Dict[str, torch.Tensor]:
-    return {k: torch.as_tensor(np.asarray(v), dtype=torch.float32) for k, v in sd.items()}
+def as_params(sd: Dict[str, np.ndarray], dtype: torch.dtype = torch.float32) -> Dict[str, torch.Tensor]:
+    """`dtype` = torch.float64: the high-precision yardstick of tests/mixed_ref.py (every building block below follows the
+    dtype of its parameters)."""
+    return {k: torch.as_tensor(np.asarray(v), dtype=dtype) for k, v in sd.items()}
 
 
 def encode_mu_law(x, mu: int = 256):
@@ -57,10 +59,10 @@ def decode_mu_law(y, mu: int = 256):
     return np.sign(fx) / m * ((1 + m) ** np.abs(fx) - 1)
 
 
-def one_hot(idx: torch.Tensor, depth: int) -> torch.Tensor:
-    """dswnv.py:68-93: (B,T) int64 -> (B,T,depth) fp32, applying idx % depth."""
+def one_hot(idx: torch.Tensor, depth: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """dswnv.py:68-93: (B,T) int64 -> (B,T,depth) fp32 (or `dtype`), applying idx % depth."""
     idx = idx % depth
-    out = torch.zeros(idx.shape[0], idx.shape[1], depth, dtype=torch.float32)
+    out = torch.zeros(idx.shape[0], idx.shape[1], depth, dtype=dtype)
     return out.scatter_(2, idx.unsqueeze(2), 1.0)
 
 
@@ -293,7 +295,7 @@ def laplace_generate(cfg, P, aux: torch.Tensor, n_samples_list: Sequence[int], n
 def softmax_stack(cfg, P, audio_idx: torch.Tensor, aux: torch.Tensor, drop=None):
     """teacher-forced logits (B, Q, T) and hidden states; audio_idx int64 (B, T); drop as in laplace_stack
     (dswnv.py:253-254,264-270)."""
-    oh = one_hot(audio_idx, cfg.n_quantize).transpose(1, 2)          # B,Q,T
+    oh = one_hot(audio_idx, cfg.n_quantize, dtype=P["causal.conv.weight"].dtype).transpose(1, 2)          # B,Q,T
     x = upsample(cfg, P, frontend(cfg, P, aux))[:, :, 1:]
     if drop is not None:
         x = x * drop[0]
