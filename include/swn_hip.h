@@ -487,6 +487,31 @@ int    swn_spectral_forward(const float* samples_dev, const float* targets_dev, 
 int    swn_spectral_backward(const float* g_dev, const unsigned char* state_dev, int rows, int len, const int* sizes,
                              int n_sizes, const float* tables_dev, float* grad_dev, void* work_dev, void* stream);
 
+/* ---- Laplace chunk loss (train_driver.batch_loss between the stack and the spectral terms; csrc/swn_laplace_loss.hip) ----
+ * NO = 2 seg + lpc, N = tp - skip >= 1.  Inputs (fp32, contiguous): raw_dev (batch, NO, tp) the stack's output; ctx_dev
+ * (batch, tp + seg + lpc - 1) the LP context, NULL allowed only with lpc == 0; target_dev (batch, tp + seg - 1); eps_dev
+ * (batch, seg, N) uniform deviates in (-0.5, 0.5); skip = leading positions dropped (the receptive field past the first
+ * chunk of an utterance).  Per b, segment j < seg and position t in [skip, tp):
+ *   mu = raw[j][t] + sum_k raw[2 seg + lpc-1-k][t] * ctx[j + t + k]      lb = logsigmoid(raw[seg + j][t])
+ *   b_noclip = exp(lb), lc = max(lb, -14.1621), b = exp(lc)              trg = target[t + j]
+ *   nll_dev[b][j]              = mean_t (ln 2 + lc + |trg - mu| / b)
+ *   samples_dev[b][j][t-skip]  = mu - b_noclip * sign(eps) * log1p(-2 |eps|)          targets_dev[b][j][t-skip] = trg
+ *   err_dev[b][j]              = mean_t |sample - trg|
+ * samples_dev / targets_dev are (batch * seg, N) rows as swn_spectral_forward takes them.  stats_dev[7]: min, mean, max and
+ * unbiased variance of mu, then min, mean, max of 2 b^2, of segment 0 over every b and kept position (the LaplaceLoss log
+ * line).  work_dev: swn_laplace_loss_work_bytes, scratch of the forward.  The backward recomputes the head from raw and
+ * writes every element of graw_dev (batch, NO, tp) = d (sum g_nll * nll + sum g_samples * samples) / d raw, zeros at
+ * positions < skip; g_nll_dev (batch, seg), g_samples_dev (batch * seg, N) or NULL; sign(0) = 0 in |trg - mu| and in
+ * sign(eps); the floor passes gradient only where lb >= -14.1621.  Results are bit-identical from call to call.
+ * SWN_E_BADARG: a null pointer (ctx_dev with lpc > 0 included), N < 1, a softmax descriptor (the size query returns 0). */
+size_t swn_laplace_loss_work_bytes(const swn_net_desc* d, int batch, int tp, int skip);
+int    swn_laplace_loss_forward(const swn_net_desc* d, const float* raw_dev, const float* ctx_dev, const float* target_dev,
+                                const float* eps_dev, int batch, int tp, int skip, float* nll_dev, float* err_dev,
+                                float* samples_dev, float* targets_dev, float* stats_dev, void* work_dev, void* stream);
+int    swn_laplace_loss_backward(const swn_net_desc* d, const float* raw_dev, const float* ctx_dev, const float* target_dev,
+                                 const float* eps_dev, int batch, int tp, int skip, const float* g_nll_dev,
+                                 const float* g_samples_dev, float* graw_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,11 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p]),
     "swn_spectral_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
+    "swn_laplace_loss_work_bytes": (c_size_t, [POINTER(NetDesc), c_int, c_int, c_int]),
+    "swn_laplace_loss_forward": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "swn_laplace_loss_backward": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

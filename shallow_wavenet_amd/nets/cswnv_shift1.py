@@ -102,10 +102,8 @@ class CSWNV(EngineMixin, nn.Module):
         assert self.receptive_field == self._cfg.receptive_field
 
     # ------------------------------------------------------------------ teacher-forced stack
-    def forward(self, aux, audio, do=False, clip=False):
-        """aux (B, n_aux, Tf), audio (B, 1, Tf*U - seg) -> the reference's tuples:
-        lpc>0: (mu, b, log_b, a) | clip: (mu, b_noclip, b, log_b, a); lpc==0 drops `a`;
-        seg==1 and lpc==0 returns 2-D (B, T') tensors (cswnv_shift1.py:228-267)."""
+    def _stack(self, aux, audio, do):
+        """-> (raw (B, 2 seg + lpc, Tp), behind autograd?, engine): the stack with `forward`'s dropout and autograd handling."""
         net = self._engine()
         # nn.Dropout only acts in training mode (model.train(), train_cswnv...py:716); masks are drawn on the host
         # in the reference's order and handed to the dropout-mode kernels
@@ -118,17 +116,31 @@ class CSWNV(EngineMixin, nn.Module):
                                         device=dropout_device(self))
         if drop is not None or (torch.is_grad_enabled() and any(p.requires_grad for p in self._param_list())):
             # training: HIP forward + HIP backward behind autograd Functions (nets/_autograd.py)
-            from shallow_wavenet_amd.nets._autograd import LaplaceHeadFunction, StackFunction
+            from shallow_wavenet_amd.nets._autograd import StackFunction
             self._pending_drop = drop
-            raw = StackFunction.apply(self, aux, audio, *self._param_list())
+            return StackFunction.apply(self, aux, audio, *self._param_list()), True, net
+        # opt-in: `model.bf16_forward = True` evaluates the stack with the bf16 MFMA kernels (fp32 accumulation;
+        # outputs differ from the fp32 path by ~5e-4) - evaluation passes that do not need the 1e-5 parity
+        return (net.forward_bf16(aux, audio) if getattr(self, "bf16_forward", False) else net.forward(aux, audio)[0]), False, net
+
+    def forward_raw(self, aux, audio, do=False):
+        """aux (B, n_aux, Tf), audio (B, 1, Tf*U - seg) -> the stack's output (B, 2 seg + lpc, Tp) ahead of the Laplace head:
+        rows [0, seg) the means, [seg, 2 seg) the scale logits, [2 seg, 2 seg + lpc) the LP coefficients - what
+        `laplace_loss.LaplaceChunkLoss` takes.  Dropout and autograd as in `forward`."""
+        return self._stack(aux, audio, do)[0]
+
+    def forward(self, aux, audio, do=False, clip=False):
+        """aux (B, n_aux, Tf), audio (B, 1, Tf*U - seg) -> the reference's tuples:
+        lpc>0: (mu, b, log_b, a) | clip: (mu, b_noclip, b, log_b, a); lpc==0 drops `a`;
+        seg==1 and lpc==0 returns 2-D (B, T') tensors (cswnv_shift1.py:228-267)."""
+        raw, train, net = self._stack(aux, audio, do)
+        if train:
+            from shallow_wavenet_amd.nets._autograd import LaplaceHeadFunction
             mu, b, log_b, a, b_clip, log_b_clip, flag = LaplaceHeadFunction.apply(net, raw, clip)
             a = a if self.lpc > 0 else None
             if not clip:
                 b_clip = log_b_clip = None
         else:
-            # opt-in: `model.bf16_forward = True` evaluates the stack with the bf16 MFMA kernels (fp32 accumulation;
-            # outputs differ from the fp32 path by ~5e-4) - evaluation passes that do not need the 1e-5 parity
-            raw = net.forward_bf16(aux, audio) if getattr(self, "bf16_forward", False) else net.forward(aux, audio)[0]
             mu, b, log_b, a, b_clip, log_b_clip, flag = net.laplace_head(raw, clip=clip)
         if self.lpc == 0 and self.seg == 1:
             sq = lambda x: None if x is None else x.reshape(x.shape[0], -1)

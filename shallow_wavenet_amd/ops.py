@@ -31,6 +31,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.laplace_head_backward(raw, gmu?, gb?, glogb?, ga?, gb_clip?, glogb_clip?, desc) -> grad_raw
     torch.ops.swn.spectral_loss(samples, targets, tables, sizes, keep_state) -> (l1, lsd, state)
     torch.ops.swn.spectral_loss_backward(grad_l1, state, tables, sizes, length) -> grad_samples
+    torch.ops.swn.laplace_loss(raw, ctx?, target, eps, desc, skip) -> (nll, err, samples, targets, stats)
+    torch.ops.swn.laplace_loss_backward(raw, ctx?, target, eps, g_nll, g_samples?, desc, skip) -> grad_raw
 """
 from __future__ import annotations
 
@@ -895,7 +897,116 @@ class SpectralLossFunction(torch.autograd.Function):
         state, tables = ctx.saved_tensors
         return spectral_loss_backward_impl(g_l1, state, tables, ctx.sizes, ctx.length), None, None, None
 
+# ------------------------------------------------------------------------------------------ Laplace chunk loss
+def _laplace_loss_check(raw, ctx, target, eps, d, skip: int) -> Tuple[int, int, int]:
+    """the argument rules of swn_laplace_loss_* as messages (the library itself answers SWN_E_BADARG) -> (B, tp, N)."""
+    if d.kind != 0:
+        raise RuntimeError("laplace_loss needs a Laplace (CSWNV) descriptor")
+    seg, lpc = d.seg, d.lpc
+    if raw.dim() != 3 or raw.shape[1] != 2 * seg + lpc:
+        raise RuntimeError(f"laplace_loss needs raw (B, {2 * seg + lpc}, Tp) for seg {seg} / lpc {lpc}, got {tuple(raw.shape)}")
+    B, _, tp = raw.shape
+    N = tp - skip
+    if skip < 0 or N < 1:
+        raise RuntimeError(f"laplace_loss: skip {skip} leaves no position of {tp}")
+    if lpc > 0 and ctx is None:
+        raise RuntimeError(f"laplace_loss needs the LP context with lpc {lpc}")
+    if lpc > 0 and tuple(ctx.shape) != (B, tp + seg + lpc - 1):
+        raise RuntimeError(f"laplace_loss needs an LP context ({B}, {tp + seg + lpc - 1}), got {tuple(ctx.shape)}")
+    if tuple(target.shape) != (B, tp + seg - 1):
+        raise RuntimeError(f"laplace_loss needs a target ({B}, {tp + seg - 1}), got {tuple(target.shape)}")
+    if tuple(eps.shape) != (B, seg, N):
+        raise RuntimeError(f"laplace_loss needs deviates ({B}, {seg}, {N}), got {tuple(eps.shape)}")
+    return B, tp, N
+
+
+def laplace_loss_impl(raw: torch.Tensor, ctx: Optional[torch.Tensor], target: torch.Tensor, eps: torch.Tensor,
+                      desc: List[int], skip: int
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """raw (B, NO, Tp), LP context (B, Tp + seg + lpc - 1) or None, target (B, Tp + seg - 1), deviates (B, seg, N) ->
+    nll (B, seg), err (B, seg), samples (B seg, N), targets (B seg, N), stats (7,)   (swn_laplace_loss_forward)."""
+    Lb = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(raw, "the stack outputs")
+    dev = raw.device
+    B, tp, N = _laplace_loss_check(raw, ctx, target, eps, d, skip)
+    c = lambda t: None if t is None else t.to(dev, torch.float32).contiguous()
+    raw, ctx, target, eps = c(raw), (c(ctx) if d.lpc > 0 else None), c(target), c(eps)
+    mk = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    nll, err, samples, targets, stats = mk(B, d.seg), mk(B, d.seg), mk(B * d.seg, N), mk(B * d.seg, N), mk(7)
+    r = ctypes.byref(d)
+    work = torch.empty(Lb.swn_laplace_loss_work_bytes(r, B, tp, skip), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _lib.check(Lb.swn_laplace_loss_forward(r, _ptr(raw), _ptr(ctx), _ptr(target), _ptr(eps), B, tp, skip, _ptr(nll),
+                                               _ptr(err), _ptr(samples), _ptr(targets), _ptr(stats), _ptr(work),
+                                               _stream(dev)), "laplace_loss_forward")
+    return nll, err, samples, targets, stats
+
+
+laplace_loss = custom_op("swn::laplace_loss", mutates_args=())(laplace_loss_impl)
+
+
+@laplace_loss.register_fake
+def _(raw, ctx, target, eps, desc, skip):
+    d = _desc(desc)
+    B, tp, N = _laplace_loss_check(raw, ctx, target, eps, d, skip)
+    mk = lambda *shape: raw.new_empty(shape, dtype=torch.float32)
+    return mk(B, d.seg), mk(B, d.seg), mk(B * d.seg, N), mk(B * d.seg, N), mk(7)
+
+
+def laplace_loss_backward_impl(raw: torch.Tensor, ctx: Optional[torch.Tensor], target: torch.Tensor, eps: torch.Tensor,
+                               g_nll: torch.Tensor, g_samples: Optional[torch.Tensor], desc: List[int],
+                               skip: int) -> torch.Tensor:
+    """d (sum g_nll * nll + sum g_samples * samples) / d raw, (B, NO, Tp), from the inputs of the forward
+    (swn_laplace_loss_backward)."""
+    Lb = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(raw, "the stack outputs")
+    dev = raw.device
+    B, tp, N = _laplace_loss_check(raw, ctx, target, eps, d, skip)
+    if tuple(g_nll.shape) != (B, d.seg) or (g_samples is not None and tuple(g_samples.shape) != (B * d.seg, N)):
+        raise RuntimeError("laplace_loss_backward: the upstream gradients do not belong to these shapes")
+    c = lambda t: None if t is None else t.to(dev, torch.float32).contiguous()
+    raw, ctx, target, eps, g_nll, g_samples = c(raw), (c(ctx) if d.lpc > 0 else None), c(target), c(eps), c(g_nll), c(g_samples)
+    graw = torch.empty_like(raw)
+    with _on(dev):
+        _lib.check(Lb.swn_laplace_loss_backward(ctypes.byref(d), _ptr(raw), _ptr(ctx), _ptr(target), _ptr(eps), B, tp, skip,
+                                                _ptr(g_nll), _ptr(g_samples), _ptr(graw), _stream(dev)),
+                   "laplace_loss_backward")
+    return graw
+
+
+laplace_loss_backward = custom_op("swn::laplace_loss_backward", mutates_args=())(laplace_loss_backward_impl)
+
+
+@laplace_loss_backward.register_fake
+def _(raw, ctx, target, eps, g_nll, g_samples, desc, skip):
+    return torch.empty_like(raw)
+
+
+class LaplaceLossFunction(torch.autograd.Function):
+    """nll, err, samples, targets, stats = LaplaceLossFunction.apply(raw, ctx, target, eps, desc, skip): nll and samples
+    differentiable in raw, the rest reported figures; calls the _impl functions directly like SpectralLossFunction."""
+
+    @staticmethod
+    def forward(ctx_, raw, ctx, target, eps, desc, skip):
+        out = laplace_loss_impl(raw, ctx, target, eps, list(desc), int(skip))
+        ctx_.save_for_backward(raw, target, eps, *(() if ctx is None else (ctx,)))
+        ctx_.desc, ctx_.skip = list(desc), int(skip)
+        ctx_.set_materialize_grads(False)           # an unused samples output reaches the kernel as NULL, not as zeros
+        ctx_.mark_non_differentiable(out[1], out[3], out[4])
+        return out
+
+    @staticmethod
+    def backward(ctx_, g_nll, _g_err, g_samples, _g_targets, _g_stats):
+        raw, target, eps, *rest = ctx_.saved_tensors
+        if g_nll is None:
+            g_nll = raw.new_zeros((raw.shape[0], ctx_.desc[DESC_FIELDS.index("seg")]))
+        graw = laplace_loss_backward_impl(raw, rest[0] if rest else None, target, eps, g_nll, g_samples, ctx_.desc, ctx_.skip)
+        return graw, None, None, None, None, None
+
 
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk", "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
-            "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward")
+            "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
+            "laplace_loss", "laplace_loss_backward")

@@ -215,7 +215,8 @@ def _stft(x: torch.Tensor, n_fft: int, window: torch.Tensor) -> torch.Tensor:
 
 def batch_loss(model, criterion_laplace, criterion_lsd, batch_h, batch_x, target, x_prob, feat_len, h_ss,
                fft_facts: Sequence[int], hann_win: Sequence[torch.Tensor], do: bool = True,
-               eps_generator: Optional[torch.Generator] = None, eps_on_device: bool = False, spectral_loss=None):
+               eps_generator: Optional[torch.Generator] = None, eps_on_device: bool = False, spectral_loss=None,
+               laplace_loss=None):
     """forward + loss of one chunk (train_cswnv...py:744-868): returns
     (batch_loss, batch_loss_laplace, batch_loss_lsd or None, batch_loss_err).
 
@@ -225,9 +226,24 @@ def batch_loss(model, criterion_laplace, criterion_lsd, batch_h, batch_x, target
     the g6_trainstep fixtures replay), with eps_on_device=True on the model's device like the reference (the driver does
     that whenever its dropout masks are device-drawn: a host draw is a pageable host->device copy per segment).
     spectral_loss: None = the spectral terms through `torch.stft` and autograd; a `spectral.MultiResolutionSTFTLoss` over
-    `fft_facts` = the same (R, K) terms from the HIP operator (one forward and one backward launch pair per chunk)."""
+    `fft_facts` = the same (R, K) terms from the HIP operator (one forward and one backward launch pair per chunk).
+    laplace_loss: None = the head op, the LP mean, LaplaceLoss and the sample draw as torch ops; a
+    `laplace_loss.LaplaceChunkLoss(seg, lpc)` = the same terms from the HIP operator on `model.forward_raw` (two launches
+    forward, one backward; the LaplaceLoss log line comes from the operator's statistics with one device->host copy).  The
+    host deviates are drawn per segment in the order below, the device deviates in one draw."""
     seg, lpc, rf = model.seg, model.lpc, model.receptive_field
-    if lpc > 0:
+    fused = None
+    if laplace_loss is not None:
+        raw = model.forward_raw(batch_h, batch_x, do=do)
+        skip = rf if h_ss > 0 else 0
+        shape = (raw.shape[0], seg, raw.shape[2] - skip)
+        if eps_on_device:
+            eps = torch.empty(shape, device=raw.device).uniform_(-0.4999, 0.5)
+        else:
+            eps = torch.stack([torch.empty(shape[0], shape[2]).uniform_(-0.4999, 0.5, generator=eps_generator)
+                               for _ in range(seg)], 1).to(raw.device)
+        fused = laplace_loss(raw, x_prob, target, eps, skip)
+    elif lpc > 0:
         mus, bs_noclip, bs, log_bs, ass = model(batch_h, batch_x, do=do, clip=True)
         ass = ass.flip(-1)
         init_mus = mus
@@ -239,7 +255,9 @@ def batch_loss(model, criterion_laplace, criterion_lsd, batch_h, batch_x, target
             mus, bs_noclip, bs, log_bs = (t.reshape(t.shape[0], -1) for t in (mus, bs_noclip, bs, log_bs))
     else:
         mus, bs_noclip, bs, log_bs = model(batch_h, batch_x, do=do, clip=True)
-    if h_ss > 0:
+    if fused is not None:
+        pass                                                                 # the operator applies `skip` itself
+    elif h_ss > 0:
         mus, bs_noclip, bs, log_bs, target = mus[0, rf:], bs_noclip[0, rf:], bs[0, rf:], log_bs[0, rf:], target[rf:]
     else:
         mus, bs_noclip, bs, log_bs = mus[0], bs_noclip[0], bs[0], log_bs[0]
@@ -290,7 +308,12 @@ def batch_loss(model, criterion_laplace, criterion_lsd, batch_h, batch_x, target
         k = has.sum()
         return torch.where(has, mean_r, torch.zeros_like(mean_r)).sum() / k.clamp(min=1), k
 
-    if seg > 1:
+    if fused is not None:
+        nll, err, samples, targets, stats = fused                          # (B, seg), (B, seg), (B seg, N), (B seg, N), (7,)
+        if logging.getLogger().isEnabledFor(logging.INFO):                 # LaplaceLoss's log line of segment 0
+            logging.info("%lf %E %lf %E %E %E %E" % tuple(stats.tolist()))
+        loss_laplace, loss_err = torch.mean(nll), torch.mean(err)
+    elif seg > 1:
         nll, err, samples, targets = [], [], [], []
         for i in range(seg):
             mus_i, bn_i = mus[:, i], bs_noclip[:, i]
@@ -388,6 +411,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--n_fft_facts", default=17, type=int)
     p.add_argument("--spectral_loss", default="torch", choices=("torch", "hip"),
                    help="spectral terms of the loss: torch.stft + autograd per FFT size, or the HIP operator (spectral.py)")
+    p.add_argument("--laplace_loss", default="torch", choices=("torch", "hip"),
+                   help="Laplace terms of the loss (LP mean, NLL, sample draw): torch ops on the head's outputs + autograd, or "
+                        "the HIP operator on the stack's raw output (laplace_loss.py)")
     p.add_argument("--string_path", default="/feat_org_lf0", type=str)
     p.add_argument("--lr", default=1e-4, type=float)
     p.add_argument("--batch_size", default=8800, type=int)
@@ -504,6 +530,10 @@ def _run(args) -> int:
     if args.spectral_loss == "hip":
         from .spectral import MultiResolutionSTFTLoss
         spectral_loss = MultiResolutionSTFTLoss(fft_facts, dev)
+    laplace_loss = None
+    if args.laplace_loss == "hip":
+        from .laplace_loss import LaplaceChunkLoss
+        laplace_loss = LaplaceChunkLoss(model.seg, model.lpc)
     if args.resume is not None:
         np.random.set_state(checkpoint["numpy_random_state"])
         torch.set_rng_state(checkpoint["torch_random_state"])
@@ -537,7 +567,7 @@ def _run(args) -> int:
                     bh, bx, trg, xp, flen = slice_chunk(model, x, h, h_bs, x_bs, h_ss, x_ss)
                     _, l_lap, l_lsd, l_err = batch_loss(model, criterion_laplace, criterion_lsd, bh, bx, trg, xp, flen,
                                                         h_ss, fft_facts, hann_win, do=False, eps_on_device=dev_rng,
-                                                        spectral_loss=spectral_loss)
+                                                        spectral_loss=spectral_loss, laplace_loss=laplace_loss)
                 ev_lap.append(l_lap.item()); ev_err.append(l_err.item())
                 if l_lsd is not None:
                     ev_lsd.append(l_lsd.item())
@@ -573,7 +603,7 @@ def _run(args) -> int:
         bh, bx, trg, xp, flen = slice_chunk(model, x, h, h_bs, x_bs, h_ss, x_ss)
         loss, l_lap, l_lsd, l_err = batch_loss(model, criterion_laplace, criterion_lsd, bh, bx, trg, xp, flen, h_ss,
                                                fft_facts, hann_win, do=True, eps_on_device=dev_rng,
-                                               spectral_loss=spectral_loss)
+                                               spectral_loss=spectral_loss, laplace_loss=laplace_loss)
         optimizer.zero_grad()
         loss.backward()
         optimizer.step()
