@@ -164,6 +164,28 @@ size_t swn_frontend_pool_work_floats(const swn_net_desc* d, const swn_frontend_p
 int    swn_frontend_pool(const swn_net_desc* d, const float* packed_dev, const swn_frontend_pool_entry* entries_host,
                          int n_entries, float* work_dev, void* stream);
 
+/* ---- pools over several models of one geometry ----------------------------------------------------------------------------
+ * A deployment of the recipe holds one checkpoint per target speaker (run.sh stage 8: the multi-speaker net fine-tuned per
+ * voice), all of one swn_net_desc.  The *_models calls serve sessions of different such models in ONE call: models_host is a
+ * HOST array of n_models DEVICE pointers, each to swn_packed_floats(d) floats, and model_of_entry_host[e] in [0, n_models)
+ * names the model of entry e.  A model that no entry names is allowed.  Entry structs, io layouts, bounds and every SWN_E_*
+ * rule are those of the single-model call; SWN_E_BADARG in addition: n_models outside [1, SWN_POOL_MAX_MODELS], a null array
+ * or a null model pointer, an index outside [0, n_models) - checked before anything is launched (the work-floats query then
+ * returns 0).  Every result is bit-identical to the single-model call made with that entry's model.  Like the entry tables,
+ * the model tables travel in kernel arguments: the calls neither copy nor synchronise on the host.
+ *   swn_frontend_pool_models   every tile of the ragged front end reads ONE model's weight rows: each stage's column list is
+ *       ordered by model and each model's columns start at a multiple of 64 (the padding columns between two models are
+ *       computed from valid addresses and never stored), so the call still makes 3 + aux_dilation_size launches whatever
+ *       n_entries and n_models are.  work_dev holds swn_frontend_pool_models_work_floats() floats (it includes that padding).
+ *   swn_decode_pool_chunk_models (declared behind swn_decode_pool_chunk below)   the workgroup of entry e runs with the weight
+ *       pointer of its model; the stepped chain is SWN_E_UNSUPPORTED as in swn_decode_pool_chunk. */
+#define SWN_POOL_MAX_MODELS 16
+size_t swn_frontend_pool_models_work_floats(const swn_net_desc* d, const swn_frontend_pool_entry* entries_host,
+                                            const int32_t* model_of_entry_host, int n_entries, int n_models);
+int    swn_frontend_pool_models(const swn_net_desc* d, const float* const* models_host, int n_models,
+                                const int32_t* model_of_entry_host, const swn_frontend_pool_entry* entries_host,
+                                int n_entries, float* work_dev, void* stream);
+
 /* ---- autoregressive decode  (CSWNV.batch_fast_generate cswnv_shift1.py:287-430,
  *                              DSWNV.batch_fast_generate dswnv.py:296-399) ---------------
  * One persistent workgroup per utterance runs prologue (rf+1 seed positions) and all
@@ -261,6 +283,13 @@ int    swn_decode_pool_chunk(const swn_net_desc* d, const float* packed_dev, int
                              const swn_decode_pool_entry* entries_host, int n_entries,
                              const swn_decode_io* io, float* session_dev,
                              void* out_dev, float* heads_dev, int variant, void* stream);
+/* the same launch with one model per entry (see "pools over several models" above): a session slot's layout depends on the
+ * geometry only, so slots of different models share session_dev, and a slot may pass from one model to another at BEGIN */
+int    swn_decode_pool_chunk_models(const swn_net_desc* d, const float* const* models_host, int n_models,
+                                    const int32_t* model_of_entry_host, int capacity,
+                                    const swn_decode_pool_entry* entries_host, int n_entries,
+                                    const swn_decode_io* io, float* session_dev,
+                                    void* out_dev, float* heads_dev, int variant, void* stream);
 
 /* ---- stepped decode pool: the decode pool of the stepped multi-launch decode (variant 3: REF6-class nets) -----------
  * Every launch of the stepped chain (input layer, L gated layers, skip / out_1 [/ out_2] mat-vecs, tail) serves all

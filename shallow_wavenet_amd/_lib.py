@@ -65,6 +65,7 @@ ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
 DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
 FRONTEND_POOL_MAX_ENTRIES = 64                 # SWN_FRONTEND_POOL_MAX_ENTRIES (include/swn_hip.h): entries per front end call
+POOL_MAX_MODELS = 16                           # SWN_POOL_MAX_MODELS (include/swn_hip.h): distinct models per *_models call
 FRONTEND_FINAL = 1                             # SWN_FRONTEND_FINAL: the entry's features end at n_received
 CHUNK_BEGIN = 1                                # SWN_CHUNK_BEGIN (include/swn_hip.h): first chunk of a streamed decode
 PRECISION_FP32, PRECISION_BF16 = 0, 1          # SWN_PRECISION_* (include/swn_hip.h)
@@ -105,6 +106,10 @@ SIGNATURES = {
     "swn_frontend": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "swn_frontend_pool_work_floats": (c_size_t, [POINTER(NetDesc), POINTER(FrontendPoolEntry), c_int]),
     "swn_frontend_pool": (c_int, [POINTER(NetDesc), c_void_p, POINTER(FrontendPoolEntry), c_int, c_void_p, c_void_p]),
+    "swn_frontend_pool_models_work_floats": (c_size_t, [POINTER(NetDesc), POINTER(FrontendPoolEntry), POINTER(c_int32), c_int,
+                                                        c_int]),
+    "swn_frontend_pool_models": (c_int, [POINTER(NetDesc), POINTER(c_void_p), c_int, POINTER(c_int32),
+                                         POINTER(FrontendPoolEntry), c_int, c_void_p, c_void_p]),
     "swn_decode_state_floats": (c_size_t, [POINTER(NetDesc), c_int]),
     "swn_decode": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecodeIO),
                            c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -114,6 +119,9 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "swn_decode_pool_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodePoolEntry), c_int, POINTER(DecodeIO),
                                       c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "swn_decode_pool_chunk_models": (c_int, [POINTER(NetDesc), POINTER(c_void_p), c_int, POINTER(c_int32), c_int,
+                                             POINTER(DecodePoolEntry), c_int, POINTER(DecodeIO), c_void_p, c_void_p, c_void_p,
+                                             c_int, c_void_p]),
     "swn_decode_stepped_prologue_iterations": (c_int, [POINTER(NetDesc)]),
     "swn_decode_pool_stepped_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodeSteppedPoolEntry), c_int,
                                               POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_void_p]),

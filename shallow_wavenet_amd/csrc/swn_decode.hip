@@ -102,8 +102,14 @@ struct DecPoolArgs {
     SwnPoolTable t;
 };
 static_assert(sizeof(DecPoolArgs) <= 4096, "kernel arguments are limited to 4 KB");
-template <bool POOL> struct GenericArgs { using type = DecArgs; };
-template <> struct GenericArgs<true> { using type = DecPoolArgs; };
+// ... and of a multi-model pool launch (swn_decode_pool_chunk_models): the model table behind them
+struct DecPoolModelsArgs : DecPoolArgs {
+    SwnPoolModels m;
+};
+static_assert(sizeof(DecPoolModelsArgs) <= 4096, "kernel arguments are limited to 4 KB");
+template <bool POOL, bool MODELS> struct GenericArgs { using type = DecArgs; };
+template <> struct GenericArgs<true, false> { using type = DecPoolArgs; };
+template <> struct GenericArgs<true, true> { using type = DecPoolModelsArgs; };
 __device__ __forceinline__ const DecArgs& pool_or_launch(const DecArgs& launch, const DecArgs&) { return launch; }
 __device__ __forceinline__ const DecArgs& pool_or_launch(const DecPoolArgs&, const DecArgs& entry) { return entry; }
 __device__ __forceinline__ const DecArgs& launch_args(const DecArgs& launch) { return launch; }
@@ -115,12 +121,16 @@ __device__ __forceinline__ const DecArgs& launch_args(const DecPoolArgs& launch)
 // POOL (with STREAM): the workgroup runs one entry of a decode pool (swn_decode_pool_chunk) - `a` already holds that entry as
 // a batch-1 chunk (swn_pool_entry_args), so b = 0; a BEGIN entry zeroes its own slot's rings here (the other slots of the
 // session buffer belong to other streams).
-template <int SEGT, int KIND, bool STREAM = false, bool POOL = false>
-__global__ __launch_bounds__(NT) void decode_generic_kernel(const typename GenericArgs<POOL>::type ka) {
+// MODELS (with POOL): the entry's weights are those of its model (SwnPoolModels); an instantiation of its own, so that the
+// single-model pool kernel stays the code it was.
+template <int SEGT, int KIND, bool STREAM = false, bool POOL = false, bool MODELS = false>
+__global__ __launch_bounds__(NT) void decode_generic_kernel(const typename GenericArgs<POOL, MODELS>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     DecArgs pa;                                             // POOL: this workgroup's entry as a batch-1 chunk
     if constexpr (POOL) {
+        static_assert(POOL || !MODELS, "only pools take a model table");
         pa = ka.c;
+        if constexpr (MODELS) pa.packed = swn_pool_model(ka.m);
         const SwnGeom& g = ka.c.g;
         if (!swn_pool_entry_args(pa, ka.t, g.seg, KIND == SWN_KIND_SOFTMAX ? g.Q : g.seg, g.NO)) return;
         const int slot = swn_pool_slot(ka.t);
@@ -349,6 +359,15 @@ int launch_generic_pool(const DecPoolArgs& p, int n_entries, size_t lds, hipStre
     return swn_launch_status("swn_decode_pool_chunk(generic)");
 }
 
+template <int SEGT>
+int launch_generic_pool(const DecPoolModelsArgs& p, int n_entries, size_t lds, hipStream_t st) {
+    if (p.c.g.kind == SWN_KIND_LAPLACE)
+        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_LAPLACE, true, true, true>), dim3(n_entries), dim3(NT), lds, st, p);
+    else
+        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX, true, true, true>), dim3(n_entries), dim3(NT), lds, st, p);
+    return swn_launch_status("swn_decode_pool_chunk_models(generic)");
+}
+
 template <int SEGT, bool STREAM = false>
 int launch_generic(const DecArgs& a, size_t lds, hipStream_t st) {
     if (a.g.kind == SWN_KIND_LAPLACE)
@@ -517,13 +536,30 @@ extern "C" int swn_decode_chunk(const swn_net_desc* d, const float* packed, cons
 }
 
 // ---- decode pool ---------------------------------------------------------------------------------------------------
-extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed, int capacity,
-                                     const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
-                                     float* session, void* out, float* heads, int variant, void* stream_) {
+namespace {
+
+int swn_make_geom_rc(const swn_net_desc* d) { SwnGeom g; return swn_make_geom(d, &g); }
+
+template <class PA>
+int launch_generic_pool_segt(const SwnGeom& g, const PA& p, int n_entries, hipStream_t st) {
+    const size_t lds = generic_lds(g);
+    switch (generic_segt(g)) {
+        case 1: return launch_generic_pool<1>(p, n_entries, lds, st);
+        case 2: return launch_generic_pool<2>(p, n_entries, lds, st);
+        case 5: return launch_generic_pool<5>(p, n_entries, lds, st);
+        default: return launch_generic_pool<10>(p, n_entries, lds, st);
+    }
+}
+
+// swn_decode_pool_chunk (models == nullptr: every entry runs `packed`) and swn_decode_pool_chunk_models (the checked table:
+// entry e runs models->p[models->of[e]], `packed` is not read)
+int pool_chunk(const swn_net_desc* d, const float* packed, const SwnPoolModels* models, int capacity,
+               const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+               float* session, void* out, float* heads, int variant, void* stream_) {
     SwnGeom g;
     int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    if (!packed || !entries || !io || !session) return SWN_E_BADARG;
+    if ((!packed && !models) || !entries || !io || !session) return SWN_E_BADARG;
     if (capacity < 1 || n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
     if (io->noise_dev || io->forced_dev) return SWN_E_BADARG;    // pools draw their noise on the device, no teacher forcing
     SwnPoolTable t = {};
@@ -551,10 +587,10 @@ extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed,
     const SwnNoise nz = swn_pool_noise_of(io);
     (void)hipGetLastError();
     if (k == KSEL_BL6W)
-        return swn_decode_bl6w_pool(d, packed, &t, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
+        return swn_decode_bl6w_pool(d, packed, &t, models, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
     if (k == KSEL_BL6)
-        return swn_decode_bl6_pool(d, packed, &t, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
-    DecPoolArgs p;
+        return swn_decode_bl6_pool(d, packed, &t, models, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
+    DecPoolModelsArgs p;
     DecArgs& a = p.c;
     a.g = g;
     swn_make_layout(&a.g, &a.y);
@@ -563,12 +599,33 @@ extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed,
     a.state_stride = ring_plan(a.g, a.ring_off, a.ring_len);
     a.step0 = 0; a.resume = 0; a.win = session + (size_t)a.state_stride * capacity;
     p.t = t;
-    const size_t lds = generic_lds(g);
     hipStream_t st = (hipStream_t)stream_;
-    switch (generic_segt(g)) {
-        case 1: return launch_generic_pool<1>(p, n_entries, lds, st);
-        case 2: return launch_generic_pool<2>(p, n_entries, lds, st);
-        case 5: return launch_generic_pool<5>(p, n_entries, lds, st);
-        default: return launch_generic_pool<10>(p, n_entries, lds, st);
-    }
+    if (!models) return launch_generic_pool_segt<DecPoolArgs>(g, p, n_entries, st);
+    p.m = *models;
+    return launch_generic_pool_segt(g, p, n_entries, st);
+}
+
+}  // namespace
+
+extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed, int capacity,
+                                     const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                     float* session, void* out, float* heads, int variant, void* stream_) {
+    const int rc = swn_make_geom_rc(d);
+    if (rc < 0) return rc;
+    if (!packed) return SWN_E_BADARG;
+    return pool_chunk(d, packed, nullptr, capacity, entries, n_entries, io, session, out, heads, variant, stream_);
+}
+
+extern "C" int swn_decode_pool_chunk_models(const swn_net_desc* d, const float* const* models, int n_models,
+                                            const int32_t* model_of_entry, int capacity,
+                                            const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                            float* session, void* out, float* heads, int variant, void* stream_) {
+    const int rc = swn_make_geom_rc(d);
+    if (rc < 0) return rc;
+    if (n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
+    if (swn_pool_models_check(models, n_models, model_of_entry, n_entries) < 0) return SWN_E_BADARG;
+    SwnPoolModels m = {};
+    for (int i = 0; i < SWN_POOL_MAX_MODELS; ++i) m.p[i] = models[i < n_models ? i : 0];
+    for (int e = 0; e < n_entries; ++e) m.of[e] = (unsigned char)model_of_entry[e];
+    return pool_chunk(d, nullptr, &m, capacity, entries, n_entries, io, session, out, heads, variant, stream_);
 }

@@ -250,8 +250,9 @@ __device__ __forceinline__ void tiled_matvec(__amdgpu_buffer_rsrc_t wt, const fl
     }
 }
 
-template <bool POOL> struct B6ArgsOf { using type = Bl6Args; };
-template <> struct B6ArgsOf<true> { using type = Bl6PoolArgs; };
+template <bool POOL, bool MODELS> struct B6ArgsOf { using type = Bl6Args; };
+template <> struct B6ArgsOf<true, false> { using type = Bl6PoolArgs; };
+template <> struct B6ArgsOf<true, true> { using type = Bl6PoolModelsArgs; };
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6Args& launch, const Bl6Args&) { return launch; }
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, const Bl6Args& entry) { return entry; }
 
@@ -261,14 +262,15 @@ __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, con
 // positions and generator counters, chunk-local out / heads / noise / forced rows; when resuming, the rings and the sample
 // window come from the session instead of the prologue, and they go back to it at the end.  The step itself is the same code.
 // POOL (with STREAM): one entry of a decode pool (swn_decode_pool_chunk); `a` holds the workgroup's entry as a batch-1 chunk
-// (swn_pool_entry_args), b = 0.
-template <class T, bool STREAM = false, bool POOL = false>
-__global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL>::type ka) {
+// (swn_pool_entry_args), b = 0.  MODELS (with POOL): the entry's weights are those of its model (SwnPoolModels).
+template <class T, bool STREAM = false, bool POOL = false, bool MODELS = false>
+__global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL, MODELS>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     Bl6Args pa;                                            // POOL: this workgroup's entry as a batch-1 chunk
     if constexpr (POOL) {
         static_assert(STREAM && T::EXT, "pools run the streamed extended mode");
         pa = ka.c;
+        if constexpr (MODELS) pa.P = swn_pool_model(ka.m);
         if (!swn_pool_entry_args(pa, ka.t, T::SEG, T::KIND == SWN_KIND_SOFTMAX ? T::Q : T::SEG, T::NO)) return;
         pa.sess += (size_t)swn_pool_slot(ka.t) * T::sess_floats;
     }
@@ -761,18 +763,27 @@ int with_tr(const SwnGeom& g, F&& f) {
 }  // namespace
 
 // one pool launch (swn_decode_pool_chunk checked the entries): one workgroup per entry, sessions [capacity][sess_floats]
-extern "C" int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries,
-                                   int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
-                                   void* stream_) {
+extern "C" int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t,
+                                   const SwnPoolModels* models, int n_entries, int n_max, const SwnNoise* nz, const void* seed,
+                                   float* sess, void* out, float* heads, void* stream_) {
     SwnGeom g; int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    Bl6PoolArgs p;
+    Bl6PoolModelsArgs p;
     fill_args(p.c, g, packed, nullptr, nz, nullptr, seed, out, heads, n_entries, 0, n_max, 0, 0, sess);
     p.t = *t;
     hipStream_t st = (hipStream_t)stream_;
+    if (models) {
+        p.m = *models;
+        return with_tr(g, [&](auto tr) {
+            using T = typename decltype(tr)::Ext;
+            return launch_kernel(decode_bl6_kernel<T, true, true, true>, T::lds_bytes, n_entries, p, st,
+                                 "swn_decode_pool_chunk_models(bl6)");
+        });
+    }
+    const Bl6PoolArgs& p1 = p;
     return with_tr(g, [&](auto tr) {
         using T = typename decltype(tr)::Ext;
-        return launch_kernel(decode_bl6_kernel<T, true, true>, T::lds_bytes, n_entries, p, st, "swn_decode_pool_chunk(bl6)");
+        return launch_kernel(decode_bl6_kernel<T, true, true>, T::lds_bytes, n_entries, p1, st, "swn_decode_pool_chunk(bl6)");
     });
 }
 

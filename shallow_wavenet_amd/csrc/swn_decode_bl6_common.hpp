@@ -44,6 +44,12 @@ struct Bl6PoolArgs {
     SwnPoolTable t;
 };
 static_assert(sizeof(Bl6PoolArgs) <= 4096, "kernel arguments are limited to 4 KB");
+// ... and of a multi-model pool launch (swn_decode_pool_chunk_models): the model table behind them.  The kernels that take it
+// are instantiations of their own (MODELS), so the single-model pool kernels stay the code they were.
+struct Bl6PoolModelsArgs : Bl6PoolArgs {
+    SwnPoolModels m;
+};
+static_assert(sizeof(Bl6PoolModelsArgs) <= 4096, "kernel arguments are limited to 4 KB");
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int pow2ceil(int x) { int r = 1; while (r < x) r <<= 1; return r; }

@@ -21,6 +21,7 @@
 // Same arithmetic per element as the symmetric kernel up to the order of the partial sums (1e-7 relative); same noise, seed,
 // forced-input and heads interface (swn_decode_bl6.hip: classic = host-drawn noise, zero seed; extended = in-kernel generator,
 // noise dump, caller's seed waveform).  8 barriers per step.  cswnv_shift1.py:281-430.
+#include <type_traits>
 #include "swn_decode_bl6_common.hpp"
 #include "swn_decode_internal.hpp"
 
@@ -636,11 +637,14 @@ __global__ __launch_bounds__(NT) void decode_bl6w_kernel(const Bl6Args a) {
     else decode_body<T, false, STREAM>(a, lds);
 }
 
-template <class T>
-__global__ __launch_bounds__(NT) void decode_bl6w_pool_kernel(const Bl6PoolArgs p) {
+// MODELS: the entry's weights are those of its model (SwnPoolModels)
+template <class T, bool MODELS = false>
+__global__ __launch_bounds__(NT) void decode_bl6w_pool_kernel(
+    const typename std::conditional<MODELS, Bl6PoolModelsArgs, Bl6PoolArgs>::type p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     static_assert(T::EXT, "pools run the extended mode");
     Bl6Args a = p.c;
+    if constexpr (MODELS) a.P = swn_pool_model(p.m);
     if (!swn_pool_entry_args(a, p.t, 1, 1, T::NO)) return;
     a.sess += (size_t)swn_pool_slot(p.t) * T::sess_floats;
     if (threadIdx.x < NG) decode_body<T, true, true, true>(a, lds);   // wave-uniform
@@ -707,17 +711,26 @@ extern "C" int swn_decode_bl6w_chunk(const swn_net_desc* d, const float* packed,
 }
 
 // one pool launch (swn_decode_pool_chunk checked the entries): one workgroup per entry, sessions [capacity][sess_floats]
-extern "C" int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries,
-                                    int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
-                                    void* stream_) {
+extern "C" int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t,
+                                    const SwnPoolModels* models, int n_entries, int n_max, const SwnNoise* nz, const void* seed,
+                                    float* sess, void* out, float* heads, void* stream_) {
     SwnGeom g; int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    Bl6PoolArgs p;
+    Bl6PoolModelsArgs p;
     fill_args(p.c, g, packed, nullptr, nz, nullptr, seed, out, heads, n_entries, 0, n_max, 0, 0, sess);
     p.t = *t;
     hipStream_t st = (hipStream_t)stream_;
+    if (models) {
+        p.m = *models;
+        return with_tw(g, [&](auto tw) {
+            using T = typename decltype(tw)::Ext;
+            return launch_kernel(decode_bl6w_pool_kernel<T, true>, T::lds_bytes, n_entries, p, st,
+                                 "swn_decode_pool_chunk_models(bl6w)");
+        });
+    }
+    const Bl6PoolArgs& p1 = p;
     return with_tw(g, [&](auto tw) {
         using T = typename decltype(tw)::Ext;
-        return launch_kernel(decode_bl6w_pool_kernel<T>, T::lds_bytes, n_entries, p, st, "swn_decode_pool_chunk(bl6w)");
+        return launch_kernel(decode_bl6w_pool_kernel<T>, T::lds_bytes, n_entries, p1, st, "swn_decode_pool_chunk(bl6w)");
     });
 }

@@ -26,7 +26,8 @@ extern "C" {
 // swn_decode_bl6.hip (the symmetric BL6-class kernel) and swn_decode_bl6w.hip (the wave-specialised form for the
 // single-sample Laplace nets of that class).  *_try: the one-shot decode, SWN_E_UNSUPPORTED when the kernel does not take
 // the geometry.  *_session_floats: per-utterance session of a streamed decode (swn_decode_chunk), 0 = the kernel does not
-// apply.  *_chunk: one chunk.  *_pool: one pool launch over the entry table swn_decode_pool_chunk checked.
+// apply.  *_chunk: one chunk.  *_pool: one pool launch over the entry table swn_decode_pool_chunk checked; with `models`
+// (swn_decode_pool_chunk_models) every entry runs its own model's weights and `packed` is not read.
 int swn_decode_bl6_try(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int n_steps,
                        const SwnNoise* nz, const void* forced, const void* seed, void* out, float* heads, void* stream);
 int swn_decode_bl6w_try(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int n_steps,
@@ -39,10 +40,12 @@ int swn_decode_bl6_chunk(const swn_net_desc* d, const float* packed, const float
 int swn_decode_bl6w_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int step0,
                           int n_steps, int resume, const SwnNoise* nz, const void* forced, const void* seed, float* sess,
                           void* out, float* heads, void* stream);
-int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries, int n_max,
-                        const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads, void* stream);
-int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, int n_entries, int n_max,
-                         const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads, void* stream);
+int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, const SwnPoolModels* models,
+                        int n_entries, int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
+                        void* stream);
+int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, const SwnPoolModels* models,
+                         int n_entries, int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
+                         void* stream);
 
 // swn_decode_stepped.hip (one launch per phase of a step, for the large geometries)
 size_t swn_decode_stepped_state_floats(const swn_net_desc* d, int batch);

@@ -18,8 +18,16 @@
 // Arithmetic: the fmaf chains of csrc/swn_frontend.hip - scale_in from the bias over ci ascending, conv_aux from the bias over
 // (ci ascending, k ascending), cond from 0 over c ascending.  A tap outside [0, n_received) contributes fmaf(w, 0, acc) exactly
 // as the one-shot kernels' zero padding does, so every row is bit-identical to swn_frontend over the whole utterance.
+//
+// Several models (swn_frontend_pool_models): a tile stages ONE set of weight rows, so it must not span two models.  The host
+// orders the entries by model (stably), and in every stage the first column of each model's entries is rounded up to a
+// multiple of 64: a tile then lies inside one model's columns, and takes that model's weights through the device table
+// (FpTabM::model of the entry of its first column).  The columns skipped by the rounding belong to no entry: they are
+// computed from valid addresses (their taps read as zero, their cond inputs are whatever the work buffer holds) and never
+// stored.  The kernels are instantiations of the same bodies (MODELS), the single-model ones stay the code they were.
 #include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
+#include "swn_pool.hpp"
 
 namespace {
 
@@ -51,6 +59,19 @@ struct FpTab {
 constexpr size_t FP_TAB_FLOATS = 1024;
 static_assert(sizeof(FpTab) <= FP_TAB_FLOATS * 4, "the device table fits the head of the work buffer");
 
+// ... of a call over several models: the entries are in model order, pre[s][e] of a model's first entry is a multiple of 64, so
+// pre[s][e + 1] - pre[s][e] no longer is entry e's column count
+struct FpTabM : FpTab {
+    int cnt[FP_STAGES][FP_MAXE];             // columns of the entry in stage s
+    const float* model[FP_MAXE];             // the entry's packed parameters
+};
+constexpr size_t FP_TABM_FLOATS = 2048;
+static_assert(sizeof(FpTabM) <= FP_TABM_FLOATS * 4, "the device table fits the head of the work buffer");
+
+// columns of entry e in stage s
+__device__ __forceinline__ int fp_cnt(const FpTab* t, int s, int e) { return t->pre[s][e + 1] - t->pre[s][e]; }
+__device__ __forceinline__ int fp_cnt(const FpTabM* t, int s, int e) { return t->cnt[s][e]; }
+
 struct FpSetupArgs {
     swn_frontend_pool_entry e[FP_MAXE];
     FpTab* tab;
@@ -60,23 +81,44 @@ struct FpSetupArgs {
 static_assert(sizeof(swn_frontend_pool_entry) == 56, "swn_frontend_pool_entry is 56 bytes (include/swn_hip.h)");
 static_assert(sizeof(FpSetupArgs) <= 4096, "fp_setup_kernel's arguments fit 4 KB");
 
-__global__ __launch_bounds__(256) void fp_setup_kernel(const FpSetupArgs a) {
+// the entries in model order, then the model table (m.of[e] = model of the e-th entry of THIS order)
+struct FpSetupArgsM {
+    swn_frontend_pool_entry e[FP_MAXE];
+    FpTabM* tab;
+    int n, n_aux, auxl;
+    int pad[SWN_MAXAUX];
+    SwnPoolModels m;
+};
+static_assert(sizeof(FpSetupArgsM) <= 4096, "fp_setup_models_kernel's arguments fit 4 KB");
+
+// first column of a stage's next entry: where a new model begins, the next multiple of 64
+__host__ __device__ inline int fp_model_start(int p, bool new_model) { return new_model ? (p + 63) & ~63 : p; }
+
+template <bool MODELS, class A>
+__device__ __forceinline__ void fp_setup_body(const A& a) {
     const int tid = threadIdx.x;
     if (blockIdx.x == 0) {
         if (blockIdx.y != 0) return;
         __shared__ int cnt[FP_STAGES][FP_MAXE];
-        FpTab* t = a.tab;
+        auto* t = a.tab;
         if (tid < a.n) {
             const swn_frontend_pool_entry& en = a.e[tid];
             int lo[FP_STAGES], c[FP_STAGES];
             fp_ranges(en.f0, en.f1, en.n_received, a.pad, a.auxl, lo, c);
             t->aux[tid] = en.aux_dev; t->cond[tid] = en.cond_dev; t->stride[tid] = en.aux_stride;
             for (int s = 0; s <= a.auxl; ++s) { t->lo[s][tid] = lo[s]; cnt[s][tid] = c[s]; }
+            if constexpr (MODELS) {
+                for (int s = 0; s <= a.auxl; ++s) t->cnt[s][tid] = c[s];
+                t->model[tid] = a.m.p[a.m.of[tid]];
+            }
         }
         __syncthreads();
         if (tid <= a.auxl) {                                 // one thread per stage: 64 additions
             int p = 0;
-            for (int e = 0; e < a.n; ++e) { t->pre[tid][e] = p; p += cnt[tid][e]; }
+            for (int e = 0; e < a.n; ++e) {
+                if constexpr (MODELS) p = fp_model_start(p, e > 0 && a.m.of[e] != a.m.of[e - 1]);
+                t->pre[tid][e] = p; p += cnt[tid][e];
+            }
             t->pre[tid][a.n] = p;
         }
         return;
@@ -92,6 +134,9 @@ __global__ __launch_bounds__(256) void fp_setup_kernel(const FpSetupArgs a) {
         en.aux_dev[c * (size_t)en.aux_stride + at + j] = en.new_dev[i];
     }
 }
+
+__global__ __launch_bounds__(256) void fp_setup_kernel(const FpSetupArgs a) { fp_setup_body<false>(a); }
+__global__ __launch_bounds__(256) void fp_setup_models_kernel(const FpSetupArgsM a) { fp_setup_body<true>(a); }
 
 // column g of a stage -> its entry: the last e with pre[e] <= g (entries without columns are stepped over)
 __device__ __forceinline__ int fp_entry_of(const int* pre, int n, int g) {
@@ -109,9 +154,10 @@ __device__ __forceinline__ int fp_entry_of(const int* pre, int n, int g) {
 // to different entries, so a tap is addressed per column and never by the column beside it) with eight loads in flight, the
 // sixteen weight rows of the pass are fetched coalesced, and the multiply-adds then run from LDS.  A tap outside the entry's
 // input range is loaded from a valid address and replaced by zero: no branch sits between the loads.
-template <int KS>
-__global__ __launch_bounds__(256) void fp_conv_kernel(
-    const FpTab* __restrict__ tab, int s, int n, const float* __restrict__ in, float* __restrict__ out,
+// MODELS: the columns between a model's last entry and the next model's first belong to no entry: not valid, whatever g is.
+template <int KS, bool MODELS, class Tab>
+__device__ __forceinline__ void fp_conv_body(
+    const Tab* __restrict__ tab, int s, int n, const float* __restrict__ in, float* __restrict__ out,
     const float* __restrict__ w, const float* __restrict__ bias, int cin, int cout, int ks_rt, int dil, int t_in, int t_out) {
     __shared__ float xs[FP_JB][64];
     __shared__ __attribute__((aligned(16))) float wl[4][FP_JB][4];
@@ -122,17 +168,17 @@ __global__ __launch_bounds__(256) void fp_conv_kernel(
     if (tid <= n) pre_s[tid] = tab->pre[s][tid];
     __syncthreads();
     const int g = blockIdx.x * 64 + lane;
-    const bool valid = g < t_out;
-    const int gc = valid ? g : t_out - 1;
+    const int gc = g < t_out ? g : t_out - 1;
     const int e = fp_entry_of(pre_s, n, gc);
+    const bool valid = g < t_out && (!MODELS || gc - pre_s[e] < fp_cnt(tab, s, e));
     const int f = tab->lo[s][e] + gc - pre_s[e];
     // the entry's input: its own feature buffer for scale_in (one tap, always inside), else its columns of the stage before
     const float* base; size_t pitch; int lo_in, hi_in;
     if (s == 0) {
         base = tab->aux[e]; pitch = (size_t)tab->stride[e]; lo_in = 0; hi_in = 0x7fffffff;
     } else {
-        const int p0 = tab->pre[s - 1][e], p1 = tab->pre[s - 1][e + 1];
-        lo_in = tab->lo[s - 1][e]; hi_in = lo_in + (p1 - p0);
+        const int p0 = tab->pre[s - 1][e];
+        lo_in = tab->lo[s - 1][e]; hi_in = lo_in + fp_cnt(tab, s - 1, e);
         base = in + ((ptrdiff_t)p0 - lo_in); pitch = (size_t)t_in;
     }
     const int co0 = blockIdx.y * 16 + 4 * cg;
@@ -196,11 +242,33 @@ __global__ __launch_bounds__(256) void fp_conv_kernel(
     }
 }
 
+template <int KS>
+__global__ __launch_bounds__(256) void fp_conv_kernel(
+    const FpTab* __restrict__ tab, int s, int n, const float* __restrict__ in, float* __restrict__ out,
+    const float* __restrict__ w, const float* __restrict__ bias, int cin, int cout, int ks_rt, int dil, int t_in, int t_out) {
+    fp_conv_body<KS, false>(tab, s, n, in, out, w, bias, cin, cout, ks_rt, dil, t_in, t_out);
+}
+
+// the packed parameters of a tile: those of the entry of its first column (a model's columns start at a multiple of 64)
+__device__ __forceinline__ const float* fp_tile_model(const FpTabM* tab, int s, int n) {
+    return tab->model[fp_entry_of(tab->pre[s], n, blockIdx.x * 64)];
+}
+
+// w_off, b_off: the layer's weights and bias in a packed buffer
+template <int KS>
+__global__ __launch_bounds__(256) void fp_conv_models_kernel(
+    const FpTabM* __restrict__ tab, int s, int n, const float* __restrict__ in, float* __restrict__ out,
+    size_t w_off, size_t b_off, int cin, int cout, int ks_rt, int dil, int t_in, int t_out) {
+    const float* P = fp_tile_model(tab, s, n);
+    fp_conv_body<KS, true>(tab, s, n, in, out, P + w_off, P + b_off, cin, cout, ks_rt, dil, t_in, t_out);
+}
+
 // cond row of column m of the last stage = sum_c Wx[n][c] * C[c][m]: the GEMM of cond_gemm_kernel (csrc/swn_frontend.hip: 64 x 64
 // tile, BK = 16, 4 x 4 outputs per thread, fp32 fmaf chains in ascending c, the next k-tile fetched ahead) over the kept rows of
 // ALL entries; row m is stored at its entry's cond_dev + frame * N.
-__global__ __launch_bounds__(256) void fp_cond_kernel(
-    const FpTab* __restrict__ tab, int s, int n, const float* __restrict__ C, const float* __restrict__ Wx,
+template <bool MODELS, class Tab>
+__device__ __forceinline__ void fp_cond_body(
+    const Tab* __restrict__ tab, int s, int n, const float* __restrict__ C, const float* __restrict__ Wx,
     int M, int N, int A0, int A0p) {
     __shared__ float As[16][64 + 4];
     __shared__ float Bs[16][64 + 4];
@@ -248,6 +316,7 @@ __global__ __launch_bounds__(256) void fp_cond_kernel(
         const int m = m0 + tm + i;
         if (m >= M) continue;
         const int e = fp_entry_of(pre_s, n, m);
+        if (MODELS && m - pre_s[e] >= fp_cnt(tab, s, e)) continue;     // a column between two models
         const size_t frame = (size_t)(tab->lo[s][e] + m - pre_s[e]);
         float* row = tab->cond[e] + frame * (size_t)N;
         if (n0 + tn + 3 < N && (N & 3) == 0) {
@@ -258,6 +327,17 @@ __global__ __launch_bounds__(256) void fp_cond_kernel(
                 if (n0 + tn + j < N) row[n0 + tn + j] = acc[i][j];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void fp_cond_kernel(
+    const FpTab* __restrict__ tab, int s, int n, const float* __restrict__ C, const float* __restrict__ Wx,
+    int M, int N, int A0, int A0p) {
+    fp_cond_body<false>(tab, s, n, C, Wx, M, N, A0, A0p);
+}
+
+__global__ __launch_bounds__(256) void fp_cond_models_kernel(
+    const FpTabM* __restrict__ tab, int s, int n, const float* __restrict__ C, size_t wx_off, int M, int N, int A0, int A0p) {
+    fp_cond_body<true>(tab, s, n, C, fp_tile_model(tab, s, n) + wx_off, M, N, A0, A0p);
 }
 
 // checks of swn_frontend_pool's table; on success tot[s] = columns of stage s over all entries, new_max = longest append
@@ -291,7 +371,94 @@ int fp_check(const SwnGeom& g, const swn_frontend_pool_entry* en, int n, long* t
     return SWN_OK;
 }
 
+// swn_frontend_pool_models: the checks of the table and of the model arguments; on success ord[i] = the entry at position i of
+// the model order (stable), tot[s] = columns of stage s with every model's first column at a multiple of 64
+int fp_check_models(const SwnGeom& g, const swn_frontend_pool_entry* en, const int32_t* model_of, int n, int n_models,
+                    int* ord, long* tot, int* new_max) {
+    long plain[FP_STAGES];
+    const int rc = fp_check(g, en, n, plain, new_max);
+    if (rc < 0) return rc;
+    if (!model_of || n_models < 1 || n_models > SWN_POOL_MAX_MODELS) return SWN_E_BADARG;
+    int at = 0;
+    for (int m = 0; m < n_models; ++m)
+        for (int e = 0; e < n; ++e) {
+            if (model_of[e] < 0 || model_of[e] >= n_models) return SWN_E_BADARG;
+            if (model_of[e] == m) ord[at++] = e;
+        }
+    for (int s = 0; s <= g.auxl; ++s) tot[s] = 0;
+    for (int i = 0; i < n; ++i) {
+        const swn_frontend_pool_entry& x = en[ord[i]];
+        int lo[FP_STAGES], cnt[FP_STAGES];
+        fp_ranges(x.f0, x.f1, x.n_received, g.aux_pad, g.auxl, lo, cnt);
+        const bool new_model = i > 0 && model_of[ord[i]] != model_of[ord[i - 1]];
+        for (int s = 0; s <= g.auxl; ++s) tot[s] = fp_model_start((int)tot[s], new_model) + cnt[s];
+    }
+    return SWN_OK;
+}
+
 }  // namespace
+
+extern "C" size_t swn_frontend_pool_models_work_floats(const swn_net_desc* d, const swn_frontend_pool_entry* entries_host,
+                                                       const int32_t* model_of_entry_host, int n_entries, int n_models) {
+    SwnGeom g; long tot[FP_STAGES]; int new_max, ord[FP_MAXE];
+    if (swn_make_geom(d, &g) < 0 ||
+        fp_check_models(g, entries_host, model_of_entry_host, n_entries, n_models, ord, tot, &new_max) < 0)
+        return 0;
+    size_t fl = FP_TABM_FLOATS + (size_t)g.n_aux * tot[0];
+    for (int i = 0; i < g.auxl; ++i) fl += (size_t)g.aux_cout[i] * tot[i + 1];
+    return fl;
+}
+
+extern "C" int swn_frontend_pool_models(const swn_net_desc* d, const float* const* models, int n_models,
+                                        const int32_t* model_of_entry, const swn_frontend_pool_entry* entries, int n_entries,
+                                        float* work, void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (!work) return SWN_E_BADARG;
+    long tot[FP_STAGES]; int new_max, ord[FP_MAXE];
+    if ((rc = fp_check_models(g, entries, model_of_entry, n_entries, n_models, ord, tot, &new_max)) < 0) return rc;
+    if (swn_pool_models_check(models, n_models, model_of_entry, n_entries) < 0) return SWN_E_BADARG;
+    if (tot[g.auxl] == 0 && new_max == 0) return SWN_OK;       // nothing to append, nothing to finalise
+    SwnLayout y; swn_make_layout(&g, &y);
+    hipStream_t st = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    FpTabM* tab = reinterpret_cast<FpTabM*>(work);
+    {
+        FpSetupArgsM a;
+        a.m = SwnPoolModels{};
+        for (int i = 0; i < n_entries; ++i) { a.e[i] = entries[ord[i]]; a.m.of[i] = (unsigned char)model_of_entry[ord[i]]; }
+        for (int i = n_entries; i < FP_MAXE; ++i) a.e[i] = swn_frontend_pool_entry{};
+        for (int m = 0; m < SWN_POOL_MAX_MODELS; ++m) a.m.p[m] = models[m < n_models ? m : 0];
+        a.tab = tab; a.n = n_entries; a.n_aux = g.n_aux; a.auxl = g.auxl;
+        for (int i = 0; i < SWN_MAXAUX; ++i) a.pad[i] = i < g.auxl ? g.aux_pad[i] : 0;
+        const size_t per = (size_t)g.n_aux * new_max;
+        const int gy = per > 256 * 8 ? 8 : (per > 256 ? (int)((per + 255) / 256) : 1);
+        hipLaunchKernelGGL(fp_setup_models_kernel, dim3(1 + n_entries, gy), dim3(256), 0, st, a);
+    }
+    if (tot[g.auxl] > 0) {
+        float* cur = work + FP_TABM_FLOATS;
+        const float* src = nullptr;
+        for (int s = 0; s <= g.auxl; ++s) {
+            const int cin = s == 0 ? g.n_aux : g.aux_cin[s - 1], cout = s == 0 ? g.n_aux : g.aux_cout[s - 1];
+            const int ks = s == 0 ? 1 : g.auxk, dil = s == 0 ? 1 : g.aux_dil[s - 1];
+            const size_t wo = s == 0 ? y.scale_w : y.aux_w[s - 1], bo = s == 0 ? y.scale_b : y.aux_b[s - 1];
+            const int t_in = s == 0 ? 0 : (int)tot[s - 1], t_out = (int)tot[s];
+            dim3 grid((t_out + 63) / 64, (cout + 15) / 16);
+            if (ks == 1)
+                hipLaunchKernelGGL(fp_conv_models_kernel<1>, grid, dim3(256), 0, st, tab, s, n_entries, src, cur, wo, bo, cin, cout, ks, dil, t_in, t_out);
+            else if (ks == 3)
+                hipLaunchKernelGGL(fp_conv_models_kernel<3>, grid, dim3(256), 0, st, tab, s, n_entries, src, cur, wo, bo, cin, cout, ks, dil, t_in, t_out);
+            else
+                hipLaunchKernelGGL(fp_conv_models_kernel<0>, grid, dim3(256), 0, st, tab, s, n_entries, src, cur, wo, bo, cin, cout, ks, dil, t_in, t_out);
+            src = cur;
+            cur += (size_t)cout * t_out;
+        }
+        const int M = (int)tot[g.auxl];
+        dim3 grid((M + 63) / 64, (g.N + 63) / 64);
+        hipLaunchKernelGGL(fp_cond_models_kernel, grid, dim3(256), 0, st, tab, g.auxl, n_entries, src, (size_t)y.wx, M, g.N, g.A0, g.A0p);
+    }
+    return swn_launch_status("swn_frontend_pool_models");
+}
 
 extern "C" size_t swn_frontend_pool_work_floats(const swn_net_desc* d, const swn_frontend_pool_entry* entries_host,
                                                 int n_entries) {

@@ -40,3 +40,22 @@ __device__ __forceinline__ bool swn_pool_entry_args(A& a, const SwnPoolTable& t,
 }
 
 __device__ __forceinline__ int swn_pool_slot(const SwnPoolTable& t) { return t.e[blockIdx.x].slot; }
+
+// the model table of a multi-model pool launch (swn_decode_pool_chunk_models, 192 B of kernel arguments behind the entry
+// table): the workgroup of entry e reads its weights through p[of[e]].  Like the entry index, the model index is uniform over
+// the workgroup, so the pointer is a scalar load and the body addresses its weights exactly as a single-model launch does.
+struct SwnPoolModels {
+    const float* p[SWN_POOL_MAX_MODELS];
+    unsigned char of[SWN_DECODE_POOL_MAX_ENTRIES];
+};
+__device__ __forceinline__ const float* swn_pool_model(const SwnPoolModels& m) { return m.p[m.of[blockIdx.x]]; }
+
+// the checks the *_models entry points add to their single-model twins; SWN_OK or SWN_E_BADARG
+inline int swn_pool_models_check(const float* const* models, int n_models, const int32_t* model_of_entry, int n_entries) {
+    if (!models || !model_of_entry || n_models < 1 || n_models > SWN_POOL_MAX_MODELS) return SWN_E_BADARG;
+    for (int m = 0; m < n_models; ++m)
+        if (!models[m]) return SWN_E_BADARG;
+    for (int e = 0; e < n_entries; ++e)
+        if (model_of_entry[e] < 0 || model_of_entry[e] >= n_models) return SWN_E_BADARG;
+    return SWN_OK;
+}

@@ -14,12 +14,15 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.pack_params(tensors, desc)                       -> packed
     torch.ops.swn.frontend(packed, aux, desc)                      -> (cond, work)
     torch.ops.swn.frontend_pool(packed, auxs, conds, staged?, n_news, n_receiveds, f0s, f1s, finals, desc)  -> ()
+    torch.ops.swn.frontend_pool_models(models, model_of, auxs, conds, staged?, n_news, n_receiveds, f0s, f1s, finals, desc)  -> ()
     torch.ops.swn.decode(packed, cond, noise?, forced?, seed?, desc, n_steps, variant, rng_seed, rng_utt0,
                          want_heads, want_noise, utt_ids?)         -> (out, heads, noise_used)
     torch.ops.swn.decode_chunk(packed, cond, session, noise?, forced?, seed?, desc, step0, n_steps, begin, variant,
                                rng_seed, rng_utt0, want_heads, want_noise, utt_ids?)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_chunk(packed, session, conds, slots, step0s, n_steps, begins, seeds?, utt_ids, desc, capacity,
                                     variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
+    torch.ops.swn.decode_pool_chunk_models(models, model_of, session, conds, slots, step0s, n_steps, begins, seeds?, utt_ids,
+                                           desc, capacity, variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_stepped_chunk(packed, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids, desc,
                                             capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.postfilter_chunk(image, state, inputs, slots, resets, order, alpha, pade, n_taps, capacity)  -> restored
@@ -176,6 +179,22 @@ def frontend_pool_impl(packed: torch.Tensor, auxs: List[torch.Tensor], conds: Li
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
     dev = packed.device
+    table = _frontend_pool_table(L, d, dev, auxs, conds, staged, n_news, n_receiveds, f0s, f1s, finals)
+    r, E = ctypes.byref(d), len(auxs)
+    floats = L.swn_frontend_pool_work_floats(r, table, E)
+    if floats == 0:
+        raise RuntimeError(_FP_REFUSED)
+    work = torch.empty(floats, dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(L.swn_frontend_pool(r, _ptr(packed), table, E, _ptr(work), _stream(dev)), "frontend_pool")
+
+
+_FP_REFUSED = ("swn_hip frontend_pool: bad argument: the entry table is refused (frame ranges, strides, flags or a "
+               "cond buffer in two entries)")
+
+
+def _frontend_pool_table(L, d, dev, auxs, conds, staged, n_news, n_receiveds, f0s, f1s, finals):
+    """the checked entry table of a pool front end call (frontend_pool and frontend_pool_models)"""
     E = len(auxs)
     if not (len(conds) == len(n_news) == len(n_receiveds) == len(f0s) == len(f1s) == len(finals) == E):
         raise RuntimeError("frontend_pool: auxs, conds, n_news, n_receiveds, f0s, f1s and finals must have one entry each")
@@ -210,13 +229,7 @@ def frontend_pool_impl(packed: torch.Tensor, auxs: List[torch.Tensor], conds: Li
         t.aux_stride, t.n_received, t.n_new = int(a.shape[-1]), int(n_receiveds[e]), n_new
         t.f0, t.f1, t.flags = int(f0s[e]), f1, _lib.FRONTEND_FINAL if finals[e] else 0
         off += max(n_new, 0)
-    floats = L.swn_frontend_pool_work_floats(r, table, E)
-    if floats == 0:
-        raise RuntimeError("swn_hip frontend_pool: bad argument: the entry table is refused (frame ranges, strides, flags or a "
-                           "cond buffer in two entries)")
-    work = torch.empty(floats, dtype=torch.float32, device=dev)
-    with _on(dev):
-        _lib.check(L.swn_frontend_pool(r, _ptr(packed), table, E, _ptr(work), _stream(dev)), "frontend_pool")
+    return table
 
 
 frontend_pool = custom_op("swn::frontend_pool", mutates_args=("auxs", "conds"))(frontend_pool_impl)
@@ -224,6 +237,56 @@ frontend_pool = custom_op("swn::frontend_pool", mutates_args=("auxs", "conds"))(
 
 @frontend_pool.register_fake
 def _(packed, auxs, conds, staged, n_news, n_receiveds, f0s, f1s, finals, desc):
+    return None
+
+
+def _model_tables(L, d, models: List[torch.Tensor], model_of: List[int], E: int, what: str):
+    """the checked model arguments of a *_models call -> (device, HOST array of the models' device pointers, int32 array of
+    the entries' model indices).  Every model buffer is fp32, contiguous, on one HIP device and swn_packed_floats long."""
+    if not 1 <= len(models) <= _lib.POOL_MAX_MODELS:
+        raise RuntimeError(f"{what}: {len(models)} models, a call takes 1 .. {_lib.POOL_MAX_MODELS}")
+    _need_cuda(models[0], "the packed parameters")
+    dev = models[0].device
+    total = L.swn_packed_floats(ctypes.byref(d))
+    for m, t in enumerate(models):
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != total:
+            raise RuntimeError(f"{what}: model {m} must be a contiguous fp32 buffer of {total} floats (swn_packed_floats) on "
+                               f"{dev}")
+    if len(model_of) != E:
+        raise RuntimeError(f"{what}: model_of has {len(model_of)} entries, the call has {E}")
+    for e, m in enumerate(model_of):
+        if not 0 <= int(m) < len(models):
+            raise RuntimeError(f"{what}: entry {e} names model {int(m)}, the call has {len(models)}")
+    ptrs = (ctypes.c_void_p * len(models))(*[t.data_ptr() for t in models])
+    return dev, ptrs, (ctypes.c_int32 * E)(*[int(m) for m in model_of])
+
+
+def frontend_pool_models_impl(models: List[torch.Tensor], model_of: List[int], auxs: List[torch.Tensor],
+                              conds: List[torch.Tensor], staged: Optional[torch.Tensor], n_news: List[int],
+                              n_receiveds: List[int], f0s: List[int], f1s: List[int], finals: List[bool],
+                              desc: List[int]) -> None:
+    """frontend_pool over sessions of several models of one geometry (swn_frontend_pool_models): entry e is finalised with the
+    packed parameters models[model_of[e]] (at most 16 models per call); everything else as frontend_pool, and every row
+    bit-identical to `frontend` with that entry's model."""
+    L = _lib.lib()
+    d = _desc(desc)
+    dev, ptrs, of = _model_tables(L, d, models, model_of, len(auxs), "frontend_pool_models")
+    table = _frontend_pool_table(L, d, dev, auxs, conds, staged, n_news, n_receiveds, f0s, f1s, finals)
+    r, E = ctypes.byref(d), len(auxs)
+    floats = L.swn_frontend_pool_models_work_floats(r, table, of, E, len(models))
+    if floats == 0:
+        raise RuntimeError(_FP_REFUSED)
+    work = torch.empty(floats, dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(L.swn_frontend_pool_models(r, ptrs, len(models), of, table, E, _ptr(work), _stream(dev)),
+                   "frontend_pool_models")
+
+
+frontend_pool_models = custom_op("swn::frontend_pool_models", mutates_args=("auxs", "conds"))(frontend_pool_models_impl)
+
+
+@frontend_pool_models.register_fake
+def _(models, model_of, auxs, conds, staged, n_news, n_receiveds, f0s, f1s, finals, desc):
     return None
 
 
@@ -369,6 +432,20 @@ def decode_pool_chunk_impl(packed: torch.Tensor, session: torch.Tensor, conds: L
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
     dev = packed.device
+    table, io, out, heads, used, n_max = _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins, seeds,
+                                                           utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
+    with _on(dev):
+        _lib.check(L.swn_decode_pool_chunk(ctypes.byref(d), _ptr(packed), int(capacity), table, len(conds), ctypes.byref(io),
+                                           _ptr(session), _ptr(out if n_max > 0 else None),
+                                           _ptr(heads if want_heads else None), int(variant), _stream(dev)),
+                   "decode_pool_chunk")
+    return out, heads, used
+
+
+def _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed,
+                      want_heads, want_noise):
+    """the checked entry table, io block and outputs of a pool launch (decode_pool_chunk and decode_pool_chunk_models) ->
+    (table, io, out, heads, used, n_max); io keeps the seeds and ids alive"""
     soft, seg, _, _, n_out, _ = _geom(d)
     E = len(conds)
     if not (len(slots) == len(step0s) == len(n_steps) == len(begins) == len(utt_ids) == E):
@@ -399,12 +476,8 @@ def decode_pool_chunk_impl(packed: torch.Tensor, session: torch.Tensor, conds: L
     io = _lib.DecodeIO(noise_dev=None, forced_dev=None, seed_dev=_ptr(seeds),
                        noise_out_dev=_ptr(used if want_noise else None),
                        rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=0, reserved=0, rng_utt_ids_dev=_ptr(ids))
-    with _on(dev):
-        _lib.check(L.swn_decode_pool_chunk(ctypes.byref(d), _ptr(packed), int(capacity), table, E, ctypes.byref(io),
-                                           _ptr(session), _ptr(out if n_max > 0 else None),
-                                           _ptr(heads if want_heads else None), int(variant), _stream(dev)),
-                   "decode_pool_chunk")
-    return out, heads, used
+    io._keep = (seeds, ids)
+    return table, io, out, heads, used, n_max
 
 
 decode_pool_chunk = custom_op("swn::decode_pool_chunk", mutates_args=("session",))(decode_pool_chunk_impl)
@@ -413,6 +486,10 @@ decode_pool_chunk = custom_op("swn::decode_pool_chunk", mutates_args=("session",
 @decode_pool_chunk.register_fake
 def _(packed, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
       want_heads, want_noise):
+    return _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise)
+
+
+def _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise):
     d = _desc(desc)
     soft, seg, _, _, n_out, _ = _geom(d)
     E, n_max = len(conds), max(int(n) for n in n_steps)
@@ -420,6 +497,37 @@ def _(packed, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, de
     return (packed.new_empty((E, n_max * seg), dtype=torch.int32 if soft else torch.float32),
             packed.new_empty((E, n_max, n_out) if want_heads else (0,)),
             packed.new_empty((E, n_max, width) if want_noise else (0,)))
+
+
+def decode_pool_chunk_models_impl(models: List[torch.Tensor], model_of: List[int], session: torch.Tensor,
+                                  conds: List[torch.Tensor], slots: List[int], step0s: List[int], n_steps: List[int],
+                                  begins: List[bool], seeds: Optional[torch.Tensor], utt_ids: List[int], desc: List[int],
+                                  capacity: int, variant: int, rng_seed: int, want_heads: bool, want_noise: bool
+                                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode_pool_chunk over sessions of several models of one geometry (swn_decode_pool_chunk_models): entry e runs with the
+    packed parameters models[model_of[e]] (at most 16 models per call); everything else as decode_pool_chunk, and every
+    entry's rows bit-identical to decode_pool_chunk with that entry's model."""
+    L = _lib.lib()
+    d = _desc(desc)
+    dev, ptrs, of = _model_tables(L, d, models, model_of, len(conds), "decode_pool_chunk_models")
+    table, io, out, heads, used, n_max = _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins, seeds,
+                                                           utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
+    with _on(dev):
+        _lib.check(L.swn_decode_pool_chunk_models(ctypes.byref(d), ptrs, len(models), of, int(capacity), table, len(conds),
+                                                  ctypes.byref(io), _ptr(session), _ptr(out if n_max > 0 else None),
+                                                  _ptr(heads if want_heads else None), int(variant), _stream(dev)),
+                   "decode_pool_chunk_models")
+    return out, heads, used
+
+
+decode_pool_chunk_models = custom_op("swn::decode_pool_chunk_models",
+                                     mutates_args=("session",))(decode_pool_chunk_models_impl)
+
+
+@decode_pool_chunk_models.register_fake
+def _(models, model_of, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
+      want_heads, want_noise):
+    return _decode_pool_fake(models[0], conds, n_steps, desc, want_heads, want_noise)
 
 
 def stepped_pool_session_floats(d, capacity: int) -> int:
@@ -1006,7 +1114,8 @@ class LaplaceLossFunction(torch.autograd.Function):
         return graw, None, None, None, None, None
 
 
-OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk", "postfilter_chunk",
+OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
+            "frontend_pool_models", "decode_pool_chunk_models", "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
             "laplace_loss", "laplace_loss_backward")

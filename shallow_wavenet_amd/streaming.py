@@ -14,13 +14,18 @@ Pools.  DecodePool.push_many hands a whole tick of sessions their features at on
 the entries of one swn_frontend_pool call, which appends every chunk and writes every new final row in a fixed number of
 launches (csrc/swn_frontend_pool.hip), bit-identical to the per-session pushes.
 
+Models.  A deployment holds one checkpoint per target speaker, all of one geometry (run.sh stage 8).  DecodePool.add_model
+registers further nets of the pool's NetConfig and open(model=k) binds a session to one of them; a tick whose sessions name
+more than one model issues the *_models ops (swn_decode_pool_chunk_models, swn_frontend_pool_models), which take at most 16
+models per call - split_models cuts the planned calls accordingly.  A tick over one model issues the single-model ops.
+
 Steps.  A generation step i reads cond frames up to ((i + 1) * seg - 1) // U, so with F final frames the steps
 [0, F * U // seg) can run (the bound of swn_decode).  Step counts come from frame counts on the host: nothing here
 waits for the device.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -290,15 +295,51 @@ def plan_push(sessions: Sequence[Tuple[object, int, int, int, bool]], lookahead:
     return [entries[i:i + limit] for i in range(0, len(entries), limit)]
 
 
+def split_models(calls: Sequence[Sequence[tuple]], model_of: Callable[[object], int],
+                 limit: int = _lib.POOL_MAX_MODELS) -> List[List[tuple]]:
+    """the calls of plan_tick / plan_push cut so that none names more than `limit` distinct models (SWN_POOL_MAX_MODELS): each
+    call is split greedily, in entry order, where the next entry would bring one model too many.  model_of maps an entry's key
+    (its first element) to its model.  Entries keep their order, and a call that is within the limit comes back as it was.
+    Pure host arithmetic: nothing here touches a device."""
+    limit = int(limit)
+    if limit < 1:
+        raise ValueError(f"limit must be a positive integer, not {limit}")
+    out: List[List[tuple]] = []
+    for entries in calls:
+        parts, cur, seen = [], [], set()
+        for en in entries:
+            m = model_of(en[0])
+            if m not in seen and len(seen) == limit:
+                parts.append(cur)
+                cur, seen = [], set()
+            seen.add(m)
+            cur.append(en)
+        parts.append(cur)
+        out.extend(parts if len(parts) > 1 else [entries])
+    return out
+
+
+def _local_models(models: Sequence[int]) -> Tuple[List[int], List[int]]:
+    """the distinct models of a call in order of first appearance, and every entry's index into that list"""
+    distinct: List[int] = []
+    at: dict = {}
+    for m in models:
+        if m not in at:
+            at[m] = len(distinct)
+            distinct.append(m)
+    return distinct, [at[m] for m in models]
+
+
 class PoolSession:
     """one utterance of a DecodePool.  push / finish hand it features (they only finalise conditioning: the pool's ticks
     generate); steps_ready / steps_done / finished tell where it stands.  Made by DecodePool.open."""
 
-    def __init__(self, pool: "DecodePool", slot: int, utt_id: int, seed: Optional[torch.Tensor]):
+    def __init__(self, pool: "DecodePool", slot: int, utt_id: int, seed: Optional[torch.Tensor], model: int = 0):
         self._pool = pool
-        self.slot, self.utt_id = slot, utt_id
-        # the conditioning of a batch-1 DecodeStream: the pool reads its _cond, steps_ready and steps_done
-        self._stream = DecodeStream(pool.net, 1, variant=pool.variant, seed=seed, rng_seed=pool.rng_seed, utt_ids=[utt_id])
+        self.slot, self.utt_id, self.model = slot, utt_id, model
+        # the conditioning of a batch-1 DecodeStream over the session's model: the pool reads its _cond, steps_ready and
+        # steps_done
+        self._stream = DecodeStream(pool._models[model], 1, variant=pool.variant, seed=seed, rng_seed=pool.rng_seed, utt_ids=[utt_id])
         self._seed = self._stream._seed
         self.closed = False
         self._pf_slot = pool.post_filter.open() if pool.post_filter is not None else None
@@ -350,7 +391,8 @@ class DecodePool:
     post_filter   a postfilter.NoiseShapingRestorer: every session holds one of its slots, and each tick ends with one
                post-filter call over the sessions that ran; each result then ends with the restored chunk (1, n * seg) fp32
 
-        s = pool.open(seed=None, utt_id=None)   # a free slot; utt_id defaults to the admission counter
+        k = pool.add_model(other_net)           # another net of the same NetConfig (the pool's own net is model 0)
+        s = pool.open(seed=None, utt_id=None, model=0)   # a free slot; utt_id defaults to the admission counter
         s.push(aux_piece); s.finish(aux_tail)  # (1, n_aux, f) features
         pool.push_many({s: aux_piece, ...}, finish=[...])   # the same for every session of a tick in ONE front end call
         results = pool.step(max_steps=None)    # one tick -> {session: (out, heads[, noise])}, views of the launch outputs
@@ -378,6 +420,7 @@ class DecodePool:
         self._session = torch.empty(int(lib.swn_decode_session_floats(desc, capacity, int(variant))), dtype=torch.float32,
                                     device=net.device)
         self.post_filter = post_filter
+        self._models = [net]                        # model 0 is the pool's own net
         self._free = list(range(capacity))          # free slots, lowest first
         self._open: dict = {}                       # slot -> PoolSession, in admission order
         self.admitted = 0
@@ -386,13 +429,27 @@ class DecodePool:
     def sessions(self) -> List[PoolSession]:
         return list(self._open.values())
 
-    def open(self, seed: Optional[torch.Tensor] = None, utt_id: Optional[int] = None) -> PoolSession:
-        """claim a free slot for a new utterance (its generator index is utt_id, else the admission count)."""
+    def add_model(self, net) -> int:
+        """register another net of the pool's geometry (a voice fine-tuned from the same recipe) -> its model index for
+        open(model=...).  A session slot's layout depends on the geometry only, so sessions of all models share the pool's
+        slots and launches.  The pool may hold any number of models; the nets' packed buffers are read at call time."""
+        if net.cfg != self.cfg:
+            raise ValueError("add_model: the net's NetConfig differs from the pool's - the models of a pool share one geometry")
+        if torch.device(net.device) != torch.device(self.net.device):
+            raise ValueError(f"add_model: the net lives on {net.device}, the pool on {self.net.device}")
+        self._models.append(net)
+        return len(self._models) - 1
+
+    def open(self, seed: Optional[torch.Tensor] = None, utt_id: Optional[int] = None, model: int = 0) -> PoolSession:
+        """claim a free slot for a new utterance of model `model` (its generator index is utt_id, else the admission
+        count)."""
         if not self._free:
             raise RuntimeError(f"the pool is full: all {self.capacity} slots hold open sessions")
+        if not isinstance(model, int) or not 0 <= model < len(self._models):
+            raise ValueError(f"model must be an index in [0, {len(self._models)}), not {model!r}")
         uid = self.admitted if utt_id is None else int(utt_id)
         slot = self._free[0]
-        s = PoolSession(self, slot, uid, seed)
+        s = PoolSession(self, slot, uid, seed, model)
         self._free.pop(0)
         self._open[slot] = s
         self.admitted += 1
@@ -415,6 +472,9 @@ class DecodePool:
         (1, n * seg) fp32 | softmax (1, n) int32, heads (1, n, n_out) or None, noise (1, n, width) - views of the dense
         launch outputs.  Nothing here waits for the device."""
         launches = plan_tick([(s, s.steps_ready, s.steps_done) for s in self._open.values()], max_steps)
+        several = len(self._models) > 1             # a pool of one model pays nothing for the others
+        if several:
+            launches = split_models(launches, lambda s: s.model)
         results = {}
         for entries in launches:
             sess = [e[0] for e in entries]
@@ -423,10 +483,14 @@ class DecodePool:
             if any(b and s._seed is not None for s, b in zip(sess, begins)):
                 seeds = torch.stack([s._seed.reshape(-1).to(torch.int32 if self.soft else torch.float32).cpu()
                                      if s._seed is not None else self._default_seed() for s in sess])
-            out, heads, used = _O.decode_pool_chunk(
-                self.net.packed, self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
-                [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
-                self.net.dlist, self.capacity, self.variant, self.rng_seed, self.want_heads, self.want_noise)
+            models, of = _local_models([s.model for s in sess]) if several else ([0], None)
+            args = (self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
+                    [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
+                    self.net.dlist, self.capacity, self.variant, self.rng_seed, self.want_heads, self.want_noise)
+            if len(models) == 1:
+                out, heads, used = _O.decode_pool_chunk(self._models[models[0]].packed, *args)
+            else:
+                out, heads, used = _O.decode_pool_chunk_models([self._models[m].packed for m in models], of, *args)
             for e, (s, step0, n) in enumerate(entries):
                 s._stream.steps_done = step0 + n
                 s._stream._begun = True
@@ -488,7 +552,8 @@ class DecodePool:
         """one front end call for a whole tick of features: s.push(chunk) for every session of `chunks` ({session: (1, n_aux, f)
         features on the host or the device, f >= 0}) and s.finish(chunk or None) for every session of `finish` (which may also
         have a last chunk in `chunks`), with the same counters and bit-identical cond rows afterwards.  The chunks are staged
-        with one copy and finalised by one swn_frontend_pool call per 64 sessions, which appends them to the sessions' feature
+        with one copy and finalised by one swn_frontend_pool call per 64 sessions (swn_frontend_pool_models where they name
+        several models, per 16 of those), which appends them to the sessions' feature
         buffers and writes the cond rows where the decode reads them.  Everything is checked first, and the counters move only
         after every call is enqueued: a call that raises leaves every session's frames_received, frames_final, steps_ready,
         finished and cond rows [0, frames_final) as they were.  Its _aux and _cond buffers may already have been grown
@@ -497,6 +562,9 @@ class DecodePool:
         la = lookahead_frames(self.cfg)
         calls = plan_push([(i, s._stream.frames_received, s._stream.frames_final, 0 if c is None else c.shape[2], fin)
                            for i, (s, c, fin) in enumerate(order)], la)
+        several = len(self._models) > 1
+        if several:
+            calls = split_models(calls, lambda i: order[i][0].model)
         dev = self.net.device
         for entries in calls:
             auxs, conds, pieces = [], [], []
@@ -511,9 +579,14 @@ class DecodePool:
                 auxs.append(st._aux[0])
                 # nothing final yet (the session only appends): the call still wants a row pointer of its own
                 conds.append(st._cond[0] if st._cond is not None else self._spare_cond(len(conds)))
-            _O.frontend_pool(self.net.packed, auxs, conds, self._stage(pieces),
-                             [e[1] - order[e[0]][0]._stream.frames_received for e in entries], [e[1] for e in entries],
-                             [e[2] for e in entries], [e[3] for e in entries], [e[4] for e in entries], self.net.dlist)
+            models, of = _local_models([order[e[0]][0].model for e in entries]) if several else ([0], None)
+            args = (auxs, conds, self._stage(pieces),
+                    [e[1] - order[e[0]][0]._stream.frames_received for e in entries], [e[1] for e in entries],
+                    [e[2] for e in entries], [e[3] for e in entries], [e[4] for e in entries], self.net.dlist)
+            if len(models) == 1:
+                _O.frontend_pool(self._models[models[0]].packed, *args)
+            else:
+                _O.frontend_pool_models([self._models[m].packed for m in models], of, *args)
         # every call has been enqueued: only now do the sessions move (a call that raised left the counters as they were)
         for entries in calls:
             for i, after, _f0, f1, _fin in entries:
@@ -610,9 +683,14 @@ class SteppedDecodePool(DecodePool):
         self.want_heads, self.want_noise = bool(want_heads), bool(want_noise)
         self._session = torch.empty(floats, dtype=torch.float32, device=net.device)
         self.post_filter = post_filter
+        self._models = [net]
         self._free = list(range(capacity))
         self._open: dict = {}
         self.admitted = 0
+
+    def add_model(self, net) -> int:
+        raise ValueError("a stepped decode pool serves one model: the chain's tile kernels fetch a channel pair's weight rows "
+                         "once for eight sessions, so the sessions of a call cannot run different weights")
 
     def open(self, seed: Optional[torch.Tensor] = None, utt_id: Optional[int] = None) -> PoolSession:
         s = super().open(seed, utt_id)
