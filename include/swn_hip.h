@@ -326,6 +326,35 @@ int    swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float* packed_
                                      const swn_decode_io* io, float* session_dev, void* out_dev, float* heads_dev,
                                      void* stream);
 
+/* ---- stepped decode pool over several models of one geometry -----------------------------------------------------------
+ * swn_decode_pool_stepped_chunk with one model per entry (see "pools over several models" above): the multi-voice pool for
+ * the nets people fine-tune per speaker (REF6).  Entry struct, io layouts, bounds and every SWN_E_* rule are those of
+ * swn_decode_pool_stepped_chunk; the model rules (n_models, null array or model pointer, index range - a model nobody names
+ * is allowed) are those of the other *_models calls, all checked before anything is launched.  Every entry's rows are
+ * bit-identical to swn_decode_pool_stepped_chunk made with that entry's model.  A slot may pass from one model to another at
+ * BEGIN.
+ *   session_dev  swn_decode_session_floats(d, capacity, 3) + SWN_DECODE_STEPPED_POOL_MODELS_TABLE_FLOATS floats.  The slot
+ *                region is that of swn_decode_pool_stepped_chunk, so both calls may serve one buffer of this size in turn; the
+ *                tail holds 40-byte table rows (the single-model row and the resolved weight pointer of the entry's model).
+ * The call makes exactly the launches the single-model call makes for the same entries, whatever n_models is.  The table is
+ * sorted by (model, n_it descending, stable): the per-entry kernels read their weights through their row's pointer, and while
+ * 24 or more entries are active the tile kernels serve tiles of at most 8 rows of ONE model, listed in the kernel arguments
+ * and rebuilt on the host when an entry runs out.
+ * swn_decode_stepped_pool_plan is that grouping as a pure host function (no device is touched): order_out[n_entries] is the
+ * table order, tiles_out[3 * t + {0, 1, 2}] = first table row, rows (1 .. 8) and model of tile t at tick-local iteration j (the
+ * entries with n_it > j).  tiles_out holds room for SWN_DECODE_STEPPED_POOL_MAX_TILES tiles.  Returns the number of tiles, or
+ * SWN_E_BADARG (a null pointer, n_entries outside [1, SWN_DECODE_POOL_MAX_ENTRIES], n_models outside [1, SWN_POOL_MAX_MODELS],
+ * a model index outside [0, n_models), a negative n_it or j). */
+#define SWN_DECODE_STEPPED_POOL_MODELS_TABLE_FLOATS 640
+#define SWN_DECODE_STEPPED_POOL_MAX_TILES 23
+int    swn_decode_stepped_pool_plan(const int32_t* model_of_entry_host, const int32_t* n_it_host, int n_entries, int n_models,
+                                    int j, int32_t* order_out, int32_t* tiles_out);
+int    swn_decode_pool_stepped_chunk_models(const swn_net_desc* d, const float* const* models_host, int n_models,
+                                            const int32_t* model_of_entry_host, int capacity,
+                                            const swn_decode_stepped_pool_entry* entries_host, int n_entries,
+                                            const swn_decode_io* io, float* session_dev, void* out_dev, float* heads_dev,
+                                            void* stream);
+
 /* ---- noise-shaping restoration on the device (run.sh stage 6 / 9: noise_shaping.py --inv false, run.sh:713-740) -------------
  * y = lowcut(MLSA_b(x)): the time-invariant MLSA filter of the coefficients b[0 .. order] (gain exp(b[0]) applied to the input,
  * Pade order `pade`, all-pass constant alpha; csrc/swn_dsp.c is the host version) followed by the causal FIR taps[0 .. n_taps-1],

@@ -64,6 +64,8 @@ class PostfilterEntry(ctypes.Structure):
 ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
 DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
+DECODE_STEPPED_POOL_MODELS_TABLE_FLOATS = 640   # SWN_DECODE_STEPPED_POOL_MODELS_TABLE_FLOATS (include/swn_hip.h)
+DECODE_STEPPED_POOL_MAX_TILES = 23             # SWN_DECODE_STEPPED_POOL_MAX_TILES (include/swn_hip.h)
 FRONTEND_POOL_MAX_ENTRIES = 64                 # SWN_FRONTEND_POOL_MAX_ENTRIES (include/swn_hip.h): entries per front end call
 POOL_MAX_MODELS = 16                           # SWN_POOL_MAX_MODELS (include/swn_hip.h): distinct models per *_models call
 FRONTEND_FINAL = 1                             # SWN_FRONTEND_FINAL: the entry's features end at n_received
@@ -125,6 +127,11 @@ SIGNATURES = {
     "swn_decode_stepped_prologue_iterations": (c_int, [POINTER(NetDesc)]),
     "swn_decode_pool_stepped_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodeSteppedPoolEntry), c_int,
                                               POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "swn_decode_stepped_pool_plan": (c_int, [POINTER(c_int32), POINTER(c_int32), c_int, c_int, c_int, POINTER(c_int32),
+                                             POINTER(c_int32)]),
+    "swn_decode_pool_stepped_chunk_models": (c_int, [POINTER(NetDesc), POINTER(c_void_p), c_int, POINTER(c_int32), c_int,
+                                                     POINTER(DecodeSteppedPoolEntry), c_int, POINTER(DecodeIO), c_void_p,
+                                                     c_void_p, c_void_p, c_void_p]),
     "swn_postfilter_state_doubles": (c_size_t, [c_int, c_int, c_int]),
     "swn_postfilter_chunk": (c_int, [c_int, ctypes.c_double, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                      POINTER(PostfilterEntry), c_int, c_void_p]),

@@ -54,7 +54,41 @@ static_assert(sizeof(StArgs) + sizeof(StPoolTable) + 16 <= 4096, "step_pool_setu
 struct StPoolArgs : StArgs {
     const StPoolEnt* tab;                      // the device copy of the tick's table
 };
-template <bool POOL> using StA = typename std::conditional<POOL, StPoolArgs, StArgs>::type;
+// ---- stepped decode pool over several models of one geometry (swn_decode_pool_stepped_chunk_models).  A table row also
+//      carries the resolved weight pointer of its entry's model: the per-entry kernels read their weights through their row's
+//      pointer, a tile kernel through that of its tile's first row.  The table is sorted by (model, n_it descending), so the
+//      entries of one model still active at tick-local iteration j are a prefix of that model's group; a tile is a run of at
+//      most 8 active rows of one group.  The tile list (swn_decode_stepped_pool_plan) travels in the kernel arguments and is
+//      rebuilt by the host when an entry runs out.  The per-entry kernels cover the rows up to the last active one (a row past
+//      its n_it returns at once).
+struct StPoolEntM : StPoolEnt {
+    const float* P;                            // the packed parameters of the entry's model
+};
+static_assert(sizeof(StPoolEntM) == 40 && SWN_DECODE_POOL_MAX_ENTRIES * sizeof(StPoolEntM) <= SWN_DECODE_STEPPED_POOL_MODELS_TABLE_FLOATS * 4,
+              "the device copy of a models table fits SWN_DECODE_STEPPED_POOL_MODELS_TABLE_FLOATS (include/swn_hip.h)");
+struct StPoolTableM {
+    StPoolEntM e[SWN_DECODE_POOL_MAX_ENTRIES];
+};
+static_assert(sizeof(StArgs) + sizeof(StPoolTableM) + 16 <= 4096, "step_pool_setup_kernel's arguments fit 4 KB");
+struct StModelsArgs : StArgs {
+    const StPoolEntM* tab;                     // the device copy of the tick's table
+    int n_tiles, n_act;                        // host side: tiles / active entries of the iteration
+    int tile[SWN_DECODE_STEPPED_POOL_MAX_TILES + 1];   // tile t: first table row | rows << 8
+};
+template <bool POOL, bool MODELS = false>
+using StA = typename std::conditional<MODELS, StModelsArgs, typename std::conditional<POOL, StPoolArgs, StArgs>::type>::type;
+
+// rows [b0, b0 + nb) of the table that tile blockIdx.y of a launch serves
+template <bool MODELS, class A>
+__device__ __forceinline__ int st_tile_b0(const A& a) {
+    if constexpr (MODELS) return a.tile[blockIdx.y] & 255;
+    else return blockIdx.y * 8;
+}
+template <bool MODELS, class A>
+__device__ __forceinline__ int st_tile_nb(const A& a, const int b0) {
+    if constexpr (MODELS) return a.tile[blockIdx.y] >> 8;
+    else return a.B - b0 < 8 ? a.B - b0 : 8;
+}
 
 // 64-bit float offset -> buffer byte offset, ST_OOB when it does not fit the 31-bit range (never wraps)
 __device__ __forceinline__ unsigned st_off(size_t floats) {
@@ -125,13 +159,12 @@ __device__ __forceinline__ Iter iter_of(const StArgs& a, int it) {
 // ---- input layer of iteration `it` -> ring 0 (device function: own launch in the prologue, fused into
 //      the tail of the previous step during generation)
 template <int KIND>
-__device__ __forceinline__ void input_layer(const StArgs& a, float* st, const int it, const int tid, const int nthreads,
-                                            const float* win) {
+__device__ __forceinline__ void input_layer(const StArgs& a, const float* P, float* st, const int it, const int tid,
+                                            const int nthreads, const float* win) {
     // win[0..WN): the sample window (LDS copy; float samples or int class indices).  All parameter loads are
     // unconditional and selected afterwards, so the K taps cost one memory round trip, not K.
     const SwnGeom& g = a.g;
     const Iter r = iter_of(a, it);
-    const float* P = a.P;
     const int H = g.H, K = g.K, seg = g.seg, WN = a.WN;
     for (int e = tid; e < H * r.np; e += nthreads) {
         const int j = e / H, o = e - j * H, q = r.q0 + j;
@@ -157,32 +190,37 @@ __device__ __forceinline__ void input_layer(const StArgs& a, float* st, const in
 }
 
 // POOL: entry blockIdx.x, when it is in its prologue or at the first generation iteration of its range (later steps get their
-// input layer from the tail of the step before)
-template <int KIND, bool POOL = false>
-__global__ __launch_bounds__(256) void step_in_kernel(const StA<POOL> a, const int itj) {
+// input layer from the tail of the step before).  MODELS (with POOL): the entry's weights are those of its row's model.
+template <int KIND, bool POOL = false, bool MODELS = false>
+__global__ __launch_bounds__(256) void step_in_kernel(const StA<POOL, MODELS> a, const int itj) {
+    static_assert(!MODELS || POOL, "several models: a pool form");
     __shared__ float lwin[32];
     int it = itj;
     float* st;
+    const float* P = a.P;
     if constexpr (POOL) {
-        const StPoolEnt& en = a.tab[blockIdx.x];
+        const auto& en = a.tab[blockIdx.x];
         it = en.it0 + itj;
         if (itj >= en.n_it || !(it < a.n_pro || it == en.g0)) return;
         st = a.state + (size_t)en.slot * a.stride;
+        if constexpr (MODELS) P = en.P;
     } else {
         st = a.state + (size_t)blockIdx.x * a.stride;
     }
     if ((int)threadIdx.x < a.WN) lwin[threadIdx.x] = st[a.o_hist + threadIdx.x];
     __syncthreads();
-    input_layer<KIND>(a, st, it, threadIdx.x, 256, lwin);
+    input_layer<KIND>(a, P, st, it, threadIdx.x, 256, lwin);
 }
 
 // ---- step_layer: ONE wave per channel pair (gate row + candidate row), weights kept in registers.
 //      Kernel boundaries invalidate the per-XCD L2s, so every launch re-fetches its weight rows from the
 //      Infinity Cache at ~30 GB/s per CU: H workgroups of 64 lanes keep each CU's share at ~10 KB.
 // POOL (BT = 1): entry blockIdx.y at its own iteration, its state block in its slot, its own conditioning
-template <int NI, int KIND, int BT, bool POOL = false>   // NI = ceil(K*Hp / 256): float4 pieces per lane and row; BT = utterances per tile
-__global__ __launch_bounds__(64) void step_layer_kernel(const StA<POOL> a, const int l, const int itj) {
+// MODELS (with POOL): the weight rows are those of the entry's model
+template <int NI, int KIND, int BT, bool POOL = false, bool MODELS = false>   // NI = ceil(K*Hp / 256): float4 pieces per lane and row; BT = utterances per tile
+__global__ __launch_bounds__(64) void step_layer_kernel(const StA<POOL, MODELS> a, const int l, const int itj) {
     static_assert(!POOL || BT == 1, "pool form: one entry per workgroup");
+    static_assert(!MODELS || POOL, "several models: a pool form");
     const SwnGeom& g = a.g;
     const int lane = threadIdx.x;
     const int o = blockIdx.x;
@@ -191,13 +229,16 @@ __global__ __launch_bounds__(64) void step_layer_kernel(const StA<POOL> a, const
     size_t pbase = 0;                                          // POOL: the entry's state block, in floats
     const float* pcond = nullptr;
     int pTf = 0;
+    const float* pP = nullptr;                                 // MODELS: the packed parameters of the entry's model
     if constexpr (POOL) {
-        const StPoolEnt& en = a.tab[blockIdx.y];
+        const auto& en = a.tab[blockIdx.y];
         if (itj >= en.n_it) return;
         it = en.it0 + itj; pbase = (size_t)en.slot * a.stride; pcond = en.cond; pTf = en.Tf;
+        if constexpr (MODELS) pP = en.P;
     }
     const bool live = o < H;
     const float* P = a.P;
+    if constexpr (MODELS) P = pP;
     const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
     float4 wz[NI], wc[NI];
     {
@@ -299,8 +340,11 @@ constexpr int ST_TU = 8;                                       // utterances (= 
 // POOL: the eight entries of a tile may be at different iterations.  Wave w stages entry 8 by + w at its own position, lane
 // octet u finishes entry 8 by + u at its own; the position loop (barriers inside) runs to the largest count of positions of
 // the tile (1 in the prologue, seg in generation), and an entry past its own count, or past its n_it, stays idle.
-template <int NI, int KIND, bool POOL = false>
-__global__ __launch_bounds__(64 * ST_TU) void step_layer_tile_kernel(const StA<POOL> a, const int l, const int itj) {
+// MODELS (with POOL): tile blockIdx.y is a run of rows of ONE model (a.tile), whose weight rows the waves fetch through the
+// pointer of the tile's first row.
+template <int NI, int KIND, bool POOL = false, bool MODELS = false>
+__global__ __launch_bounds__(64 * ST_TU) void step_layer_tile_kernel(const StA<POOL, MODELS> a, const int l, const int itj) {
+    static_assert(!MODELS || POOL, "several models: a pool form");
     extern __shared__ __attribute__((aligned(16))) float xs[];  // [ST_TU][NI * 256]
     const SwnGeom& g = a.g;
     const int lane = threadIdx.x & 63;
@@ -308,12 +352,13 @@ __global__ __launch_bounds__(64 * ST_TU) void step_layer_tile_kernel(const StA<P
     const int o = blockIdx.x * ST_TU + w;
     const int H = g.H, Hp = g.Hp, K = g.K, H2 = 2 * g.H, seg = g.seg, KH = K * Hp;
     if constexpr (POOL) {
-        const int b0 = blockIdx.y * ST_TU;
-        const int nb = a.B - b0 < ST_TU ? a.B - b0 : ST_TU;
+        static_assert(ST_TU == 8, "st_tile_b0 / st_tile_nb: tiles of 8 rows");
+        const int b0 = st_tile_b0<MODELS>(a);
+        const int nb = st_tile_nb<MODELS>(a, b0);
         // the staging entry of this wave (uniform) and the finishing entry of this lane's octet
         const int kw = b0 + (w < nb ? w : 0), ku = b0 + ((lane >> 3) < nb ? (lane >> 3) : 0);
-        const StPoolEnt& ew = a.tab[kw];
-        const StPoolEnt& eu = a.tab[ku];
+        const auto& ew = a.tab[kw];
+        const auto& eu = a.tab[ku];
         const bool onw = w < nb && itj < ew.n_it, onu = (lane >> 3) < nb && itj < eu.n_it;
         const Iter rw = iter_of(a, ew.it0 + itj), ru = iter_of(a, eu.it0 + itj);
         // positions of the tile: the largest count over its active entries (every lane holds its octet's entry)
@@ -323,6 +368,7 @@ __global__ __launch_bounds__(64 * ST_TU) void step_layer_tile_kernel(const StA<P
         if (npm == 0) return;                                  // uniform over the workgroup: no entry of the tile is active
         const bool live = o < H;
         const float* P = a.P;
+        if constexpr (MODELS) P = a.tab[b0].P;
         const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
         float4 wz[NI], wc[NI];
         {
@@ -498,20 +544,24 @@ __global__ __launch_bounds__(64 * ST_TU) void step_layer_tile_kernel(const StA<P
 
 // ---- rowvec: y[b][row] = act(bias[row] + W[row][:] . x[b][:]), ONE wave per row -------------------------
 // POOL (BT = 1): entry blockIdx.y, when it is generating at tick-local iteration `itj`; its state block is in its slot
-template <int BT, bool POOL = false>
-__global__ __launch_bounds__(64) void rowvec_kernel(const StA<POOL> a, size_t w_off, int ldw, size_t b_off, int rows,
+// MODELS (with POOL): the rows are those of the entry's model
+template <int BT, bool POOL = false, bool MODELS = false>
+__global__ __launch_bounds__(64) void rowvec_kernel(const StA<POOL, MODELS> a, size_t w_off, int ldw, size_t b_off, int rows,
                                                     int ni, int x_off, int y_off, int relu, const int itj) {
     static_assert(!POOL || BT == 1, "pool form: one entry per workgroup");
+    static_assert(!MODELS || POOL, "several models: a pool form");
     const int lane = threadIdx.x, row = blockIdx.x;
     size_t pbase = 0;                                          // POOL: the entry's state block, in floats
+    const float* P = a.P;
     if constexpr (POOL) {
-        const StPoolEnt& en = a.tab[blockIdx.y];
+        const auto& en = a.tab[blockIdx.y];
         if (itj >= en.n_it || en.it0 + itj < en.g0) return;
         pbase = (size_t)en.slot * a.stride;
+        if constexpr (MODELS) P = en.P;
     }
-    const __amdgpu_buffer_rsrc_t rP = st_rsrc(a.P), rS = st_rsrc(a.state);
+    const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
     const size_t wr = w_off + (size_t)row * ldw;
-    const float bias = a.P[b_off + row];
+    const float bias = P[b_off + row];
     // (POOL: fetched here, beside the kernel arguments, as the pool form always did; left to the compiler, the load sinks
     //  behind the loop and costs a round trip of its own at the end of the launch)
     if constexpr (POOL) asm volatile("" :: "s"(bias));
@@ -556,25 +606,29 @@ __global__ __launch_bounds__(64) void rowvec_kernel(const StA<POOL> a, size_t w_
 // the same for the 1x1 layers: 8 rows x 8 utterances per workgroup, the utterances' input vectors staged in LDS
 // POOL: wave w stages entry 8 by + w, lane octet u finishes entry 8 by + u, each only when that entry is generating at
 // tick-local iteration `itj`
-template <int RV, bool POOL = false>                           // host: ni <= 256 RV
-__global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StA<POOL> a, size_t w_off, int ldw, size_t b_off, int rows,
+// MODELS (with POOL): tile blockIdx.y is a run of rows of ONE model (a.tile); the weight rows are that model's
+template <int RV, bool POOL = false, bool MODELS = false>      // host: ni <= 256 RV
+__global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StA<POOL, MODELS> a, size_t w_off, int ldw, size_t b_off, int rows,
                                                                  int ni, int x_off, int y_off, int relu, const int itj) {
+    static_assert(!MODELS || POOL, "several models: a pool form");
     extern __shared__ __attribute__((aligned(16))) float xs[];  // [ST_TU][RV * 256]
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int row = blockIdx.x * ST_TU + w;
     const bool live = row < rows;
-    const __amdgpu_buffer_rsrc_t rP = st_rsrc(a.P), rS = st_rsrc(a.state);
+    const float* P = a.P;
+    if constexpr (MODELS) P = a.tab[st_tile_b0<MODELS>(a)].P;
+    const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
     const size_t wr = w_off + (size_t)(live ? row : 0) * ldw;
-    const float bias = live ? a.P[b_off + row] : 0.f;
-    const int b0 = blockIdx.y * ST_TU;
-    const int nb = a.B - b0 < ST_TU ? a.B - b0 : ST_TU;
+    const float bias = live ? P[b_off + row] : 0.f;
+    const int b0 = st_tile_b0<MODELS>(a);
+    const int nb = st_tile_nb<MODELS>(a, b0);
     const int ut = lane >> 3;                                  // the utterance this lane's octet ends up with (sum64x8)
     bool onw = w < nb, onu = ut < nb;                          // this wave stages / this octet finishes an utterance
     size_t basew = (size_t)(b0 + w) * a.stride, baseu = (size_t)(b0 + ut) * a.stride;
     if constexpr (POOL) {
-        const StPoolEnt& ew = a.tab[b0 + (onw ? w : 0)];
-        const StPoolEnt& eu = a.tab[b0 + (onu ? ut : 0)];
+        const auto& ew = a.tab[b0 + (onw ? w : 0)];
+        const auto& eu = a.tab[b0 + (onu ? ut : 0)];
         onw = onw && itj < ew.n_it && ew.it0 + itj >= ew.g0;
         onu = onu && itj < eu.n_it && eu.it0 + itj >= eu.g0;
         basew = (size_t)ew.slot * a.stride; baseu = (size_t)eu.slot * a.stride;
@@ -619,19 +673,23 @@ __global__ __launch_bounds__(64 * ST_TU) void rowvec_tile_kernel(const StA<POOL>
 // POOL (with STREAM): entry blockIdx.x when it is generating at tick-local iteration `itj`; its io rows are those of its row
 // (n_steps = the launch's n_max), its state block is in its slot, and the next input layer is formed while the entry's range
 // goes on.
-template <int KIND, bool STREAM = false, bool POOL = false>
-__global__ __launch_bounds__(256) void step_tail_kernel(const StA<POOL> a, const int itj) {
+// MODELS (with POOL): out_2 and the next input layer read the weights of the entry's model
+template <int KIND, bool STREAM = false, bool POOL = false, bool MODELS = false>
+__global__ __launch_bounds__(256) void step_tail_kernel(const StA<POOL, MODELS> a, const int itj) {
     static_assert(!POOL || STREAM, "the pool form is a streamed chunk per entry");
+    static_assert(!MODELS || POOL, "several models: a pool form");
     __shared__ float o2v[4096 + 16];
     __shared__ float lwin[32];                 // the updated sample window, for the fused next input layer
     const SwnGeom& g = a.g;
     int b = blockIdx.x, it = itj, step0 = a.step0, it_end = 0;
     size_t sb = (size_t)b;                     // state block
+    const float* P = a.P;
     if constexpr (POOL) {
-        const StPoolEnt& en = a.tab[blockIdx.x];
+        const auto& en = a.tab[blockIdx.x];
         it = en.it0 + itj;
         if (itj >= en.n_it || it < en.g0) return;
         b = en.row; sb = (size_t)en.slot; step0 = en.g0 - a.n_pro; it_end = en.it0 + en.n_it;
+        if constexpr (MODELS) P = en.P;
     }
     const int tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
     float* st = a.state + sb * a.stride;
@@ -642,7 +700,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StA<POOL> a, const
     if (a.o2_by_rowvec) {
         for (int e = tid; e < g.NO; e += 256) o2v[e] = st[a.o_o2 + e];
     } else {
-        const __amdgpu_buffer_rsrc_t rP = st_rsrc(a.P), rS = st_rsrc(a.state);
+        const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
         const size_t xb = sb * a.stride + a.o_o1;
         for (int r0 = 0; r0 < g.NO; r0 += 8) {
             const int row = r0 + grp;
@@ -665,7 +723,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StA<POOL> a, const
                 }
             }
             acc = sum32(acc);
-            if (lane == 0 && rok) o2v[row] = acc + a.P[a.y.b2 + row];
+            if (lane == 0 && rok) o2v[row] = acc + P[a.y.b2 + row];
         }
     }
     __syncthreads();
@@ -747,9 +805,9 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StA<POOL> a, const
     // block (same CU), then run the next step's input layer here - one launch less per step
     __syncthreads();
     if constexpr (POOL) {
-        if (it + 1 < it_end) input_layer<KIND>(a, st, it + 1, tid, 256, lwin);
+        if (it + 1 < it_end) input_layer<KIND>(a, P, st, it + 1, tid, 256, lwin);
     } else {
-        if (i + 1 < a.n_steps) input_layer<KIND>(a, st, it + 1, tid, 256, lwin);
+        if (i + 1 < a.n_steps) input_layer<KIND>(a, P, st, it + 1, tid, 256, lwin);
     }
 }
 
@@ -760,9 +818,11 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StA<POOL> a, const
 //      next input layer are all in flight with the out_2 operands, and what follows the first barrier works on LDS and
 //      registers.  Same formulas in the same order as step_tail_kernel<LAPLACE> + input_layer (bit-identical results).
 // POOL (with STREAM): as step_tail_kernel
-template <int MAXE, bool STREAM = false, bool POOL = false>      // elements (channel, position) of the next input layer per thread: ceil(H * seg / 256) <= MAXE
-__global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StA<POOL> a, const int itj) {
+// MODELS (with POOL): as step_tail_kernel
+template <int MAXE, bool STREAM = false, bool POOL = false, bool MODELS = false>   // elements (channel, position) of the next input layer per thread: ceil(H * seg / 256) <= MAXE
+__global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StA<POOL, MODELS> a, const int itj) {
     static_assert(!POOL || STREAM, "the pool form is a streamed chunk per entry");
+    static_assert(!MODELS || POOL, "several models: a pool form");
     __shared__ float o2v[64];                  // NO <= 48
     __shared__ float lwin[32];                 // the updated sample window, for the fused next input layer
     __shared__ float lold[32];                 // the window as the step found it
@@ -770,16 +830,17 @@ __global__ __launch_bounds__(256) void step_tail_laplace_kernel(const StA<POOL> 
     const SwnGeom& g = a.g;
     int b = blockIdx.x, it = itj, step0 = a.step0, it_end = 0;
     size_t sb = (size_t)b;                     // state block
+    const float* P = a.P;
     if constexpr (POOL) {
-        const StPoolEnt& en = a.tab[blockIdx.x];
+        const auto& en = a.tab[blockIdx.x];
         it = en.it0 + itj;
         if (itj >= en.n_it || it < en.g0) return;
         b = en.row; sb = (size_t)en.slot; step0 = en.g0 - a.n_pro; it_end = en.it0 + en.n_it;
+        if constexpr (MODELS) P = en.P;
     }
     const int tid = threadIdx.x, lane = tid & 31, grp = tid >> 5;
     float* st = a.state + sb * a.stride;
     const int ia = it - a.n_pro, i = STREAM ? ia - step0 : ia, seg = g.seg, WN = a.WN, H = g.H, K = g.K;
-    const float* P = a.P;
     float* shist = st + a.o_hist;
     // ---- requests: out_2 rows and bias, window, noise, input-layer parameters
     const __amdgpu_buffer_rsrc_t rP = st_rsrc(P), rS = st_rsrc(a.state);
@@ -904,11 +965,13 @@ __global__ void step_seed_kernel(const StArgs a) {
 // first launch of a pool tick: block (0, k) writes entry k of the table to the device copy the later launches read, and the
 // blocks (x, k) of a BEGIN entry zero its slot and seed its sample window - what hipMemsetAsync + step_seed_kernel do for a
 // whole streamed chunk, here for that slot alone (the other slots belong to other sessions).  Grid (zero blocks, entries).
-__global__ __launch_bounds__(256) void step_pool_setup_kernel(const StArgs a, const StPoolTable t, StPoolEnt* tab,
+// TAB / ENT: StPoolTable / StPoolEnt, or the wider rows of a call over several models (StPoolTableM / StPoolEntM).
+template <class TAB, class ENT>
+__global__ __launch_bounds__(256) void step_pool_setup_kernel(const StArgs a, const TAB t, ENT* tab,
                                                               unsigned long long begin_mask) {
     const int k = blockIdx.y, tid = threadIdx.x;
-    const StPoolEnt& en = t.e[k];
-    if (blockIdx.x == 0 && tid < 8) reinterpret_cast<int*>(tab + k)[tid] = reinterpret_cast<const int*>(&en)[tid];
+    const ENT& en = t.e[k];
+    if (blockIdx.x == 0 && tid < (int)(sizeof(ENT) / 4)) reinterpret_cast<int*>(tab + k)[tid] = reinterpret_cast<const int*>(&en)[tid];
     if (!((begin_mask >> k) & 1ull)) return;
     float* blk = a.state + (size_t)en.slot * a.stride;
     const int n4 = a.stride / 4;                               // stride: a multiple of 64 floats
@@ -968,12 +1031,12 @@ void fill_args(StArgs& a, const float* packed, const float* cond, const SwnNoise
 }
 
 // dynamic LDS above 64 KB for the tile forms (NI = 8: 64 KB, RV = 9: 72 KB)
-template <bool POOL>
+template <bool POOL, bool MODELS = false>
 bool allow_tile_lds() {
     const int big = 72 * 1024;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_LAPLACE, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, big) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_SOFTMAX, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, big) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(rowvec_tile_kernel<9, POOL>), hipFuncAttributeMaxDynamicSharedMemorySize, big) == hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_LAPLACE, POOL, MODELS>), hipFuncAttributeMaxDynamicSharedMemorySize, big) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(step_layer_tile_kernel<8, SWN_KIND_SOFTMAX, POOL, MODELS>), hipFuncAttributeMaxDynamicSharedMemorySize, big) == hipSuccess &&
+           hipFuncSetAttribute(reinterpret_cast<const void*>(rowvec_tile_kernel<9, POOL, MODELS>), hipFuncAttributeMaxDynamicSharedMemorySize, big) == hipSuccess;
 }
 constexpr int ST_SEQ = 24;                                     // utterances from which the tile forms run (launch_iteration)
 
@@ -981,8 +1044,11 @@ constexpr int ST_SEQ = 24;                                     // utterances fro
 // when `in` (prologue positions and the first generation step of a launch sequence run their own; later steps get it from
 // the tail of the step before), the L layers, and when `gen` the 1x1 mat-vecs and the tail.  `it` is the iteration every
 // kernel takes: the absolute one, POOL: the tick-local one.  STREAM: the tails write chunk-local rows.
-template <bool POOL, bool STREAM, int KIND>
-void launch_iteration_of(const StA<POOL>& a, int it, bool in, bool gen, hipStream_t st) {
+// MODELS: a.B covers the table rows up to the last active one (the per-entry kernels' grid), a.n_act of them are active (the
+// figure the tile forms are chosen by, as in the single-model call) and the tile kernels run one workgroup row per tile of
+// a.tile - the same launches as the single-model call makes.
+template <bool POOL, bool STREAM, int KIND, bool MODELS = false>
+void launch_iteration_of(const StA<POOL, MODELS>& a, int it, bool in, bool gen, hipStream_t st) {
     const SwnGeom& g = a.g;
     const int n = a.B;
     // up to 64 utterances: one utterance per workgroup (weights re-read per utterance from the Infinity Cache;
@@ -991,14 +1057,15 @@ void launch_iteration_of(const StA<POOL>& a, int it, bool in, bool gen, hipStrea
     const bool solo = n <= 64;
     const unsigned by = solo ? (unsigned)n : (unsigned)((n + 7) / 8);
     // many utterances: tiles of 8 channel pairs (rows) x 8 utterances (step_layer_tile / rowvec_tile)
-    const bool seq = n >= ST_SEQ;                              // measured crossover at REF6: 16 utterances 47 (solo) / 53 us per step, 24: 59 / 56
-    const unsigned sy = (unsigned)((n + ST_TU - 1) / ST_TU);
-    if (in) hipLaunchKernelGGL((step_in_kernel<KIND, POOL>), dim3(n), dim3(256), 0, st, a, it);
+    bool seq = n >= ST_SEQ;                                    // measured crossover at REF6: 16 utterances 47 (solo) / 53 us per step, 24: 59 / 56
+    unsigned sy = (unsigned)((n + ST_TU - 1) / ST_TU);
+    if constexpr (MODELS) { seq = a.n_act >= ST_SEQ; sy = (unsigned)a.n_tiles; }
+    if (in) hipLaunchKernelGGL((step_in_kernel<KIND, POOL, MODELS>), dim3(n), dim3(256), 0, st, a, it);
     auto layer = [&](auto ni_, int l) {
         constexpr int NI = decltype(ni_)::value;
-        if (seq) hipLaunchKernelGGL((step_layer_tile_kernel<NI, KIND, POOL>), dim3((g.H + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU),
+        if (seq) hipLaunchKernelGGL((step_layer_tile_kernel<NI, KIND, POOL, MODELS>), dim3((g.H + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU),
                                     (size_t)ST_TU * NI * 256 * sizeof(float), st, a, l, it);
-        else if (solo) hipLaunchKernelGGL((step_layer_kernel<NI, KIND, 1, POOL>), dim3(g.H, by), dim3(64), 0, st, a, l, it);
+        else if (solo) hipLaunchKernelGGL((step_layer_kernel<NI, KIND, 1, POOL, MODELS>), dim3(g.H, by), dim3(64), 0, st, a, l, it);
         else if constexpr (!POOL) hipLaunchKernelGGL((step_layer_kernel<NI, KIND, 8>), dim3(g.H, by), dim3(64), 0, st, a, l, it);
     };
     const int ni = (g.K * g.Hp + 255) / 256;
@@ -1009,9 +1076,9 @@ void launch_iteration_of(const StA<POOL>& a, int it, bool in, bool gen, hipStrea
     }
     if (!gen) return;
     auto rowvec = [&](int rows, size_t w_off, int ldw, size_t b_off, int nin, int x_off, int y_off, int relu) {
-        if (seq && nin <= 1280) hipLaunchKernelGGL((rowvec_tile_kernel<5, POOL>), dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 5 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
-        else if (seq && nin <= 2304) hipLaunchKernelGGL((rowvec_tile_kernel<9, POOL>), dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 9 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
-        else if (solo) hipLaunchKernelGGL((rowvec_kernel<1, POOL>), dim3(rows, by), dim3(64), 0, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
+        if (seq && nin <= 1280) hipLaunchKernelGGL((rowvec_tile_kernel<5, POOL, MODELS>), dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 5 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
+        else if (seq && nin <= 2304) hipLaunchKernelGGL((rowvec_tile_kernel<9, POOL, MODELS>), dim3((rows + ST_TU - 1) / ST_TU, sy), dim3(64 * ST_TU), (size_t)ST_TU * 9 * 1024, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
+        else if (solo) hipLaunchKernelGGL((rowvec_kernel<1, POOL, MODELS>), dim3(rows, by), dim3(64), 0, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
         else if constexpr (!POOL) hipLaunchKernelGGL((rowvec_kernel<8>), dim3(rows, by), dim3(64), 0, st, a, w_off, ldw, b_off, rows, nin, x_off, y_off, relu, it);
     };
     rowvec(g.S, a.y.wsk, g.L * g.Hp, a.y.bsk, g.L * g.Hp, a.o_hcat, a.o_skip, 1);
@@ -1020,17 +1087,17 @@ void launch_iteration_of(const StA<POOL>& a, int it, bool in, bool gen, hipStrea
     if constexpr (KIND == SWN_KIND_LAPLACE) {
         // Laplace heads of up to 16 rows over up to 512 inputs, K <= 8 taps, <= 1 024 input-layer elements: the prefetching tail
         if (g.NO <= 16 && g.O1p <= 512 && g.K <= 8 && g.H * g.seg <= 1024 && g.seg <= 16 && a.WN <= 32) {
-            if (g.H * g.seg <= 256) hipLaunchKernelGGL((step_tail_laplace_kernel<1, STREAM, POOL>), dim3(n), dim3(256), 0, st, a, it);
-            else hipLaunchKernelGGL((step_tail_laplace_kernel<4, STREAM, POOL>), dim3(n), dim3(256), 0, st, a, it);
+            if (g.H * g.seg <= 256) hipLaunchKernelGGL((step_tail_laplace_kernel<1, STREAM, POOL, MODELS>), dim3(n), dim3(256), 0, st, a, it);
+            else hipLaunchKernelGGL((step_tail_laplace_kernel<4, STREAM, POOL, MODELS>), dim3(n), dim3(256), 0, st, a, it);
             return;
         }
     }
-    hipLaunchKernelGGL((step_tail_kernel<KIND, STREAM, POOL>), dim3(n), dim3(256), 0, st, a, it);
+    hipLaunchKernelGGL((step_tail_kernel<KIND, STREAM, POOL, MODELS>), dim3(n), dim3(256), 0, st, a, it);
 }
-template <bool POOL, bool STREAM>
-void launch_iteration(const StA<POOL>& a, int it, bool in, bool gen, hipStream_t st) {
-    if (a.g.kind == SWN_KIND_LAPLACE) launch_iteration_of<POOL, STREAM, SWN_KIND_LAPLACE>(a, it, in, gen, st);
-    else launch_iteration_of<POOL, STREAM, SWN_KIND_SOFTMAX>(a, it, in, gen, st);
+template <bool POOL, bool STREAM, bool MODELS = false>
+void launch_iteration(const StA<POOL, MODELS>& a, int it, bool in, bool gen, hipStream_t st) {
+    if (a.g.kind == SWN_KIND_LAPLACE) launch_iteration_of<POOL, STREAM, SWN_KIND_LAPLACE, MODELS>(a, it, in, gen, st);
+    else launch_iteration_of<POOL, STREAM, SWN_KIND_SOFTMAX, MODELS>(a, it, in, gen, st);
 }
 
 // the launch chain of steps [step0, step0 + n_steps); stream = a chunk of a streamed decode: `state` is the session, which the
@@ -1102,16 +1169,25 @@ extern "C" int swn_decode_stepped_prologue_iterations(const swn_net_desc* d) {
     return g.rf - g.seg + 1;
 }
 
-extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float* packed, int capacity,
-                                             const swn_decode_stepped_pool_entry* entries, int n_entries,
-                                             const swn_decode_io* io, float* session, void* out, float* heads,
-                                             void* stream_) {
-    StPoolArgs a;
-    int rc = swn_make_geom(d, &a.g);
-    if (rc < 0) return rc;
-    const SwnGeom& g = a.g;
-    if (!packed || !entries || !io || !session) return SWN_E_BADARG;
+namespace {
+
+// what the checks of a stepped pool call find out about its table
+struct StPoolCall {
+    int n_max, it_max;                         // most generation steps / iterations of an entry
+    bool any_begin;
+};
+
+// the argument rules of swn_decode_pool_stepped_chunk (include/swn_hip.h), and with `models` those the call over several
+// models adds; nothing is launched before they pass
+int pool_check(const swn_net_desc* d, const SwnGeom& g, const float* packed, const float* const* models, int n_models,
+               const int32_t* model_of_entry, int capacity, const swn_decode_stepped_pool_entry* entries, int n_entries,
+               const swn_decode_io* io, const float* session, const void* out, StPoolCall& c) {
+    if ((!models && !packed) || !entries || !io || !session) return SWN_E_BADARG;
     if (capacity < 1 || n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
+    if (models || model_of_entry) {
+        const int rc = swn_pool_models_check(models, n_models, model_of_entry, n_entries);
+        if (rc != SWN_OK) return rc;
+    }
     if (io->noise_dev || io->forced_dev) return SWN_E_BADARG;    // pools draw their noise on the device, no teacher forcing
     const int n_pro = g.rf - g.seg + 1;
     int n_max = 0, it_max = 0;
@@ -1136,6 +1212,32 @@ extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float*
     }
     if (n_max > 0 && !out) return SWN_E_BADARG;
     if (!swn_decode_stepped_supported(d, capacity)) return SWN_E_UNSUPPORTED;
+    c.n_max = n_max; c.it_max = it_max; c.any_begin = any_begin;
+    return SWN_OK;
+}
+
+// row k of a tick's table: entry `e` of the caller's
+template <class ENT>
+void pool_row(ENT& r, const swn_decode_stepped_pool_entry& en, int e, int n_pro) {
+    r.cond = en.cond_dev; r.Tf = en.n_frames; r.slot = en.slot; r.it0 = en.it0;
+    r.n_it = en.n_it; r.row = e; r.g0 = en.it0 > n_pro ? en.it0 : n_pro;
+}
+
+}  // namespace
+
+extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float* packed, int capacity,
+                                             const swn_decode_stepped_pool_entry* entries, int n_entries,
+                                             const swn_decode_io* io, float* session, void* out, float* heads,
+                                             void* stream_) {
+    StPoolArgs a;
+    int rc = swn_make_geom(d, &a.g);
+    if (rc < 0) return rc;
+    const SwnGeom& g = a.g;
+    StPoolCall c;
+    rc = pool_check(d, g, packed, nullptr, 0, nullptr, capacity, entries, n_entries, io, session, out, c);
+    if (rc != SWN_OK) return rc;
+    const int n_pro = g.rf - g.seg + 1, n_max = c.n_max, it_max = c.it_max;
+    const bool any_begin = c.any_begin;
     if (!any_begin && it_max == 0) return SWN_OK;           // every slot stays as it is
 
     fill_args(a, packed, nullptr, swn_pool_noise_of(io), nullptr, io->seed_dev, session, out, heads, n_entries, 0, n_max, 0);
@@ -1150,8 +1252,7 @@ extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float*
     unsigned long long begin_mask = 0;
     for (int k = 0; k < n_entries; ++k) {
         const swn_decode_stepped_pool_entry& en = entries[order[k]];
-        t.e[k].cond = en.cond_dev; t.e[k].Tf = en.n_frames; t.e[k].slot = en.slot; t.e[k].it0 = en.it0;
-        t.e[k].n_it = en.n_it; t.e[k].row = order[k]; t.e[k].g0 = en.it0 > n_pro ? en.it0 : n_pro;
+        pool_row(t.e[k], en, order[k], n_pro);
         if (en.flags & SWN_CHUNK_BEGIN) begin_mask |= 1ull << k;
     }
     StPoolEnt* tab = reinterpret_cast<StPoolEnt*>(session + (size_t)a.stride * capacity);
@@ -1159,7 +1260,7 @@ extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float*
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();
     const StArgs& base = a;
-    hipLaunchKernelGGL(step_pool_setup_kernel, dim3(any_begin ? 64 : 1, n_entries), dim3(256), 0, st, base, t, tab, begin_mask);
+    hipLaunchKernelGGL((step_pool_setup_kernel<StPoolTable, StPoolEnt>), dim3(any_begin ? 64 : 1, n_entries), dim3(256), 0, st, base, t, tab, begin_mask);
 
     // dynamic LDS above 64 KB for the tile forms (set on every call that uses them: the attribute is per device)
     bool any_seq = false;
@@ -1182,4 +1283,110 @@ extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float*
         launch_iteration<true, true>(a, j, need_in, need_gen, st);
     }
     return swn_launch_status("swn_decode_pool_stepped_chunk");
+}
+
+// ---- stepped decode pool over several models -----------------------------------------------------------------------
+extern "C" int swn_decode_stepped_pool_plan(const int32_t* model_of_entry, const int32_t* n_it, int n_entries, int n_models,
+                                            int j, int32_t* order_out, int32_t* tiles_out) {
+    if (!model_of_entry || !n_it || !order_out || !tiles_out || j < 0) return SWN_E_BADARG;
+    if (n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES || n_models < 1 || n_models > SWN_POOL_MAX_MODELS)
+        return SWN_E_BADARG;
+    for (int e = 0; e < n_entries; ++e)
+        if (model_of_entry[e] < 0 || model_of_entry[e] >= n_models || n_it[e] < 0) return SWN_E_BADARG;
+    // (model, n_it descending), stable: insertion sort, as the single-model call sorts by n_it
+    for (int e = 0; e < n_entries; ++e) order_out[e] = e;
+    auto before = [&](int x, int y) {           // entry x must come in front of entry y, which now stands in front of it
+        return model_of_entry[x] < model_of_entry[y] || (model_of_entry[x] == model_of_entry[y] && n_it[x] > n_it[y]);
+    };
+    for (int x = 1; x < n_entries; ++x)
+        for (int y = x; y > 0 && before(order_out[y], order_out[y - 1]); --y) {
+            const int tmp = order_out[y]; order_out[y] = order_out[y - 1]; order_out[y - 1] = tmp;
+        }
+    // the active entries of a model are a prefix of its group: cut it into runs of at most 8 rows
+    int nt = 0;
+    for (int k = 0; k < n_entries;) {
+        const int m = model_of_entry[order_out[k]];
+        int end = k, act = k;
+        while (end < n_entries && model_of_entry[order_out[end]] == m) ++end;
+        while (act < end && n_it[order_out[act]] > j) ++act;
+        for (int r = k; r < act; r += ST_TU) {
+            if (nt >= SWN_DECODE_STEPPED_POOL_MAX_TILES) return SWN_E_BADARG;   // (not reached: 64 entries over 16 models give 22)
+            tiles_out[3 * nt] = r; tiles_out[3 * nt + 1] = act - r < ST_TU ? act - r : ST_TU; tiles_out[3 * nt + 2] = m;
+            ++nt;
+        }
+        k = end;
+    }
+    return nt;
+}
+
+extern "C" int swn_decode_pool_stepped_chunk_models(const swn_net_desc* d, const float* const* models, int n_models,
+                                                    const int32_t* model_of_entry, int capacity,
+                                                    const swn_decode_stepped_pool_entry* entries, int n_entries,
+                                                    const swn_decode_io* io, float* session, void* out, float* heads,
+                                                    void* stream_) {
+    StModelsArgs a;
+    int rc = swn_make_geom(d, &a.g);
+    if (rc < 0) return rc;
+    const SwnGeom& g = a.g;
+    if (!models || !model_of_entry) return SWN_E_BADARG;
+    StPoolCall c;
+    rc = pool_check(d, g, nullptr, models, n_models, model_of_entry, capacity, entries, n_entries, io, session, out, c);
+    if (rc != SWN_OK) return rc;
+    const int n_pro = g.rf - g.seg + 1, it_max = c.it_max;
+    if (!c.any_begin && it_max == 0) return SWN_OK;         // every slot stays as it is
+
+    // no kernel of this call reads a.P: every weight pointer comes from a table row
+    fill_args(a, models[0], nullptr, swn_pool_noise_of(io), nullptr, io->seed_dev, session, out, heads, n_entries, 0, c.n_max, 0);
+    // the table, sorted by (model, n_it descending), and the tiles of iteration 0
+    int32_t n_it[SWN_DECODE_POOL_MAX_ENTRIES], order[SWN_DECODE_POOL_MAX_ENTRIES], tiles[3 * (SWN_DECODE_STEPPED_POOL_MAX_TILES + 1)];
+    for (int e = 0; e < n_entries; ++e) n_it[e] = entries[e].n_it;
+    int nt = swn_decode_stepped_pool_plan(model_of_entry, n_it, n_entries, n_models, 0, order, tiles);
+    if (nt < 0) return nt;
+    StPoolTableM t = {};
+    unsigned long long begin_mask = 0;
+    int n_act0 = 0;
+    for (int k = 0; k < n_entries; ++k) {
+        const swn_decode_stepped_pool_entry& en = entries[order[k]];
+        pool_row(t.e[k], en, order[k], n_pro);
+        t.e[k].P = models[model_of_entry[order[k]]];
+        if (en.flags & SWN_CHUNK_BEGIN) begin_mask |= 1ull << k;
+        n_act0 += en.n_it > 0 ? 1 : 0;
+    }
+    StPoolEntM* tab = reinterpret_cast<StPoolEntM*>(session + (size_t)a.stride * capacity);
+    a.tab = tab;
+    a.n_tiles = 0; a.n_act = 0;
+    for (int& x : a.tile) x = 0;
+    hipStream_t st = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    const StArgs& base = a;
+    hipLaunchKernelGGL((step_pool_setup_kernel<StPoolTableM, StPoolEntM>), dim3(c.any_begin ? 64 : 1, n_entries), dim3(256), 0, st, base, t, tab, begin_mask);
+
+    // dynamic LDS above 64 KB for the tile forms (set on every call that uses them; iteration 0 has the most active entries)
+    if (n_act0 >= ST_SEQ && !allow_tile_lds<true, true>()) return SWN_E_LAUNCH;
+    for (int j = 0; j < it_max; ++j) {
+        // the tiles change only when an entry runs out
+        bool ran_out = false;
+        for (int e = 0; e < n_entries; ++e) ran_out = ran_out || n_it[e] == j;
+        if (j > 0 && ran_out) {
+            nt = swn_decode_stepped_pool_plan(model_of_entry, n_it, n_entries, n_models, j, order, tiles);
+            if (nt < 0) return nt;
+        }
+        if (j == 0 || ran_out) {
+            a.n_tiles = nt; a.n_act = 0; a.B = 0;
+            for (int x = 0; x < nt; ++x) {
+                a.tile[x] = tiles[3 * x] | (tiles[3 * x + 1] << 8);
+                a.n_act += tiles[3 * x + 1];
+                a.B = tiles[3 * x] + tiles[3 * x + 1];      // the tiles are in table order: the last one ends the active rows
+            }
+        }
+        bool need_in = false, need_gen = false;
+        for (int x = 0; x < nt; ++x)
+            for (int k = tiles[3 * x]; k < tiles[3 * x] + tiles[3 * x + 1]; ++k) {
+                const int it = t.e[k].it0 + j;
+                need_in = need_in || it < n_pro || it == t.e[k].g0;
+                need_gen = need_gen || it >= t.e[k].g0;
+            }
+        launch_iteration<true, true, true>(a, j, need_in, need_gen, st);
+    }
+    return swn_launch_status("swn_decode_pool_stepped_chunk_models");
 }

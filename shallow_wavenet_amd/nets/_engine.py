@@ -146,20 +146,23 @@ class EngineMixin:
                             rng_utt0=int(getattr(self, "noise_utterance_offset", 0)),
                             utt_ids=getattr(self, "noise_utterance_ids", None), post_filter=post_filter)
 
-    def open_pool(self, capacity: int, variant: int = 0, post_filter=None):
+    def open_pool(self, capacity: int, variant: int = 0, post_filter=None, multi_model: bool = False):
         """a decode pool of `capacity` session slots on the module's current engine (shallow_wavenet_amd.streaming.DecodePool):
         independent utterances open, receive features and end at their own pace, and one launch per tick advances all of
         them.  The noise key follows open_stream: `noise_rng_seed` when the caller pinned one, else one fresh key per pool.
         A session opened with utt_id = i draws what utterance i of batch_fast_generate with noise_source = "device" draws.
         When the engine resolves to the stepped multi-launch decode (REF6-class nets: variant 0 or 3), the pool is a
-        SteppedDecodePool (its step() also takes max_prologue).  post_filter: as open_stream, one slot per session."""
+        SteppedDecodePool (its step() also takes max_prologue).  post_filter: as open_stream, one slot per session.
+        multi_model: the pool is to serve further nets of this geometry (add_model, open(model=k)): a net of the stepped
+        decode then gets a SteppedModelPool; the DecodePool of the other nets takes add_model as it is."""
         from .. import _lib, noise as _noise, ops as _ops
-        from ..streaming import DecodePool, SteppedDecodePool
+        from ..streaming import DecodePool, SteppedDecodePool, SteppedModelPool
         key = getattr(self, "noise_rng_seed", None)
         rng_seed = _noise.draw_rng_seed() if key is None else int(key)
         net = self._engine()
         if _lib.lib().swn_decode_resolve_variant(_ops._desc(net.dlist), capacity, int(variant)) == 3:
-            return SteppedDecodePool(net, capacity, rng_seed=rng_seed, post_filter=post_filter)
+            cls = SteppedModelPool if multi_model else SteppedDecodePool
+            return cls(net, capacity, rng_seed=rng_seed, post_filter=post_filter)
         return DecodePool(net, capacity, variant=variant, rng_seed=rng_seed, post_filter=post_filter)
 
     def set_packed_engine(self, net: HipNet) -> None:

@@ -25,6 +25,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
                                            desc, capacity, variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_stepped_chunk(packed, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids, desc,
                                             capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
+    torch.ops.swn.decode_pool_stepped_chunk_models(models, model_of, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids,
+                                                   desc, capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.postfilter_chunk(image, state, inputs, slots, resets, order, alpha, pade, n_taps, capacity)  -> restored
     torch.ops.swn.stack_forward(packed, cond, audio, desc, want_hidden) -> (raw, work, hidden)
     torch.ops.swn.stack_forward_bf16(packed, wbf16, cond, audio, desc)  -> (raw, work)
@@ -556,6 +558,22 @@ def decode_pool_stepped_chunk_impl(packed: torch.Tensor, session: torch.Tensor, 
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
     dev = packed.device
+    table, io, out, heads, used, n_max = _stepped_pool_args(L, d, dev, session, conds, slots, it0s, n_its, begins, seeds,
+                                                            utt_ids, capacity, rng_seed, want_heads, want_noise,
+                                                            stepped_pool_session_floats(d, int(capacity)))
+    with _on(dev):
+        _lib.check(L.swn_decode_pool_stepped_chunk(ctypes.byref(d), _ptr(packed), int(capacity), table, len(conds),
+                                                   ctypes.byref(io), _ptr(session), _ptr(out if n_max > 0 else None),
+                                                   _ptr(heads if want_heads else None), _stream(dev)),
+                   "decode_pool_stepped_chunk")
+    return out, heads, used
+
+
+def _stepped_pool_args(L, d, dev, session, conds, slots, it0s, n_its, begins, seeds, utt_ids, capacity, rng_seed, want_heads,
+                       want_noise, need):
+    """the checked entry table, io block and outputs of a stepped pool call (decode_pool_stepped_chunk and
+    decode_pool_stepped_chunk_models) -> (table, io, out, heads, used, n_max); io keeps the seeds and ids alive.  need: floats
+    the call's session buffer holds (0 = the stepped chain does not run the net at this capacity)"""
     soft, seg, _, _, n_out, _ = _geom(d)
     E = len(conds)
     if not (len(slots) == len(it0s) == len(n_its) == len(begins) == len(utt_ids) == E):
@@ -565,7 +583,6 @@ def decode_pool_stepped_chunk_impl(packed: torch.Tensor, session: torch.Tensor, 
     width = d.n_quantize if soft else seg
     if session.device != dev or session.dtype != torch.float32 or not session.is_contiguous():
         raise RuntimeError("session must be a contiguous fp32 tensor on the device of the packed parameters")
-    need = stepped_pool_session_floats(d, int(capacity))
     if need == 0:
         raise RuntimeError("decode_pool_stepped_chunk: the stepped decode does not run this net at this capacity")
     if session.numel() < need:
@@ -590,12 +607,8 @@ def decode_pool_stepped_chunk_impl(packed: torch.Tensor, session: torch.Tensor, 
     io = _lib.DecodeIO(noise_dev=None, forced_dev=None, seed_dev=_ptr(seeds),
                        noise_out_dev=_ptr(used if want_noise else None),
                        rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=0, reserved=0, rng_utt_ids_dev=_ptr(ids))
-    with _on(dev):
-        _lib.check(L.swn_decode_pool_stepped_chunk(ctypes.byref(d), _ptr(packed), int(capacity), table, E,
-                                                   ctypes.byref(io), _ptr(session), _ptr(out if n_max > 0 else None),
-                                                   _ptr(heads if want_heads else None), _stream(dev)),
-                   "decode_pool_stepped_chunk")
-    return out, heads, used
+    io._keep = (seeds, ids)
+    return table, io, out, heads, used, n_max
 
 
 decode_pool_stepped_chunk = custom_op("swn::decode_pool_stepped_chunk", mutates_args=("session",))(
@@ -605,6 +618,10 @@ decode_pool_stepped_chunk = custom_op("swn::decode_pool_stepped_chunk", mutates_
 @decode_pool_stepped_chunk.register_fake
 def _(packed, session, conds, slots, it0s, n_its, begins, seeds, utt_ids, desc, capacity, rng_seed, want_heads,
       want_noise):
+    return _stepped_pool_fake(packed, conds, it0s, n_its, desc, want_heads, want_noise)
+
+
+def _stepped_pool_fake(packed, conds, it0s, n_its, desc, want_heads, want_noise):
     d = _desc(desc)
     soft, seg, _, _, n_out, _ = _geom(d)
     n_pro = int(_lib.lib().swn_decode_stepped_prologue_iterations(ctypes.byref(d)))
@@ -613,6 +630,63 @@ def _(packed, session, conds, slots, it0s, n_its, begins, seeds, utt_ids, desc, 
     return (packed.new_empty((E, n_max * seg), dtype=torch.int32 if soft else torch.float32),
             packed.new_empty((E, n_max, n_out) if want_heads else (0,)),
             packed.new_empty((E, n_max, width) if want_noise else (0,)))
+
+
+def stepped_pool_models_session_floats(d, capacity: int) -> int:
+    """floats of the session buffer of a stepped pool over several models: the slots of stepped_pool_session_floats and the
+    wider table rows of swn_decode_pool_stepped_chunk_models (the single-model call serves such a buffer too); 0 when the
+    stepped chain does not run the net at this capacity"""
+    n = int(_lib.lib().swn_decode_session_floats(ctypes.byref(d), int(capacity), 3))
+    return n + _lib.DECODE_STEPPED_POOL_MODELS_TABLE_FLOATS if n > 0 else 0
+
+
+def decode_pool_stepped_chunk_models_impl(models: List[torch.Tensor], model_of: List[int], session: torch.Tensor,
+                                          conds: List[torch.Tensor], slots: List[int], it0s: List[int], n_its: List[int],
+                                          begins: List[bool], seeds: Optional[torch.Tensor], utt_ids: List[int],
+                                          desc: List[int], capacity: int, rng_seed: int, want_heads: bool, want_noise: bool
+                                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode_pool_stepped_chunk over sessions of several models of one geometry (swn_decode_pool_stepped_chunk_models): entry
+    e runs with the packed parameters models[model_of[e]] (at most 16 models per call) in the same launches as the others;
+    `session` holds stepped_pool_models_session_floats() floats.  Everything else as decode_pool_stepped_chunk, and every
+    entry's rows bit-identical to decode_pool_stepped_chunk with that entry's model."""
+    L = _lib.lib()
+    d = _desc(desc)
+    dev, ptrs, of = _model_tables(L, d, models, model_of, len(conds), "decode_pool_stepped_chunk_models")
+    table, io, out, heads, used, n_max = _stepped_pool_args(L, d, dev, session, conds, slots, it0s, n_its, begins, seeds,
+                                                            utt_ids, capacity, rng_seed, want_heads, want_noise,
+                                                            stepped_pool_models_session_floats(d, int(capacity)))
+    with _on(dev):
+        _lib.check(L.swn_decode_pool_stepped_chunk_models(ctypes.byref(d), ptrs, len(models), of, int(capacity), table,
+                                                          len(conds), ctypes.byref(io), _ptr(session),
+                                                          _ptr(out if n_max > 0 else None),
+                                                          _ptr(heads if want_heads else None), _stream(dev)),
+                   "decode_pool_stepped_chunk_models")
+    return out, heads, used
+
+
+decode_pool_stepped_chunk_models = custom_op("swn::decode_pool_stepped_chunk_models", mutates_args=("session",))(
+    decode_pool_stepped_chunk_models_impl)
+
+
+@decode_pool_stepped_chunk_models.register_fake
+def _(models, model_of, session, conds, slots, it0s, n_its, begins, seeds, utt_ids, desc, capacity, rng_seed, want_heads,
+      want_noise):
+    return _stepped_pool_fake(models[0], conds, it0s, n_its, desc, want_heads, want_noise)
+
+
+def stepped_pool_plan(model_of: List[int], n_its: List[int], n_models: int, j: int = 0) -> Tuple[List[int], List[tuple]]:
+    """the grouping swn_decode_pool_stepped_chunk_models launches by (swn_decode_stepped_pool_plan; pure host arithmetic) ->
+    (table order, [(first table row, rows, model)] of the tiles of tick-local iteration j)"""
+    E = len(model_of)
+    if len(n_its) != E:
+        raise RuntimeError("stepped_pool_plan: model_of and n_its must have one entry each")
+    order = (ctypes.c_int32 * max(E, 1))()
+    tiles = (ctypes.c_int32 * (3 * _lib.DECODE_STEPPED_POOL_MAX_TILES))()
+    nt = _lib.lib().swn_decode_stepped_pool_plan((ctypes.c_int32 * max(E, 1))(*[int(m) for m in model_of]),
+                                                 (ctypes.c_int32 * max(E, 1))(*[int(n) for n in n_its]), E, int(n_models),
+                                                 int(j), order, tiles)
+    _lib.check(min(nt, 0), "stepped_pool_plan")
+    return list(order[:E]), [tuple(tiles[3 * t:3 * t + 3]) for t in range(nt)]
 
 
 # ------------------------------------------------------------------------------------------ noise-shaping post-filter
@@ -1115,7 +1189,7 @@ class LaplaceLossFunction(torch.autograd.Function):
 
 
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
-            "frontend_pool_models", "decode_pool_chunk_models", "postfilter_chunk",
+            "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
             "laplace_loss", "laplace_loss_backward")

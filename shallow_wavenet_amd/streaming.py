@@ -18,6 +18,9 @@ Models.  A deployment holds one checkpoint per target speaker, all of one geomet
 registers further nets of the pool's NetConfig and open(model=k) binds a session to one of them; a tick whose sessions name
 more than one model issues the *_models ops (swn_decode_pool_chunk_models, swn_frontend_pool_models), which take at most 16
 models per call - split_models cuts the planned calls accordingly.  A tick over one model issues the single-model ops.
+The nets people fine-tune per speaker (REF6) decode on the stepped chain: their multi-voice pool is SteppedModelPool
+(swn_decode_pool_stepped_chunk_models), whose launch chain serves the sessions of all models of a call at once - the table is
+grouped by model, so a tile of eight sessions fetches ONE model's weight rows.  SteppedDecodePool stays the one-model pool.
 
 Steps.  A generation step i reads cond frames up to ((i + 1) * seg - 1) // U, so with F final frames the steps
 [0, F * U // seg) can run (the bound of swn_decode).  Step counts come from frame counts on the host: nothing here
@@ -673,7 +676,7 @@ class SteppedDecodePool(DecodePool):
         self.seg = 1 if self.soft else int(self.cfg.seg)
         desc = _ops._desc(net.dlist)
         lib = _lib.lib()
-        floats = _ops.stepped_pool_session_floats(desc, capacity)
+        floats = self._session_floats(desc)
         if floats == 0:
             raise ValueError(f"the stepped decode does not run this net with {capacity} slots "
                              f"({lib.swn_strerror(lib.swn_decode_resolve_variant(desc, capacity, 3)).decode()})")
@@ -690,12 +693,20 @@ class SteppedDecodePool(DecodePool):
 
     def add_model(self, net) -> int:
         raise ValueError("a stepped decode pool serves one model: the chain's tile kernels fetch a channel pair's weight rows "
-                         "once for eight sessions, so the sessions of a call cannot run different weights")
+                         "once for eight sessions, so the sessions of a call cannot run different weights - SteppedModelPool "
+                         "groups a call's sessions by model and serves several")
 
     def open(self, seed: Optional[torch.Tensor] = None, utt_id: Optional[int] = None) -> PoolSession:
         s = super().open(seed, utt_id)
         s._it_done = 0                               # iterations run: prologue positions, then generation steps
         return s
+
+    def _session_floats(self, desc) -> int:
+        return _ops.stepped_pool_session_floats(desc, self.capacity)
+
+    def _calls(self, calls):
+        """the calls of a tick as (entries, models of the call, each entry's index into them)"""
+        return [(entries, [0], None) for entries in calls]
 
     def step(self, max_steps: Optional[int] = None, max_prologue: Optional[int] = None) -> dict:
         """one tick: every open session with ready steps runs the rest of its prologue (at most max_prologue iterations of
@@ -704,17 +715,20 @@ class SteppedDecodePool(DecodePool):
         calls = plan_stepped_tick([(s, s.steps_ready, s._it_done) for s in self._open.values()], self.n_pro, max_steps,
                                   max_prologue)
         results = {}
-        for entries in calls:
+        for entries, models, of in self._calls(calls):
             sess = [e[0] for e in entries]
             begins = [s._it_done == 0 for s in sess]
             seeds = None
             if any(b and s._seed is not None for s, b in zip(sess, begins)):
                 seeds = torch.stack([s._seed.reshape(-1).to(torch.int32 if self.soft else torch.float32).cpu()
                                      if s._seed is not None else self._default_seed() for s in sess])
-            out, heads, used = _O.decode_pool_stepped_chunk(
-                self.net.packed, self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
-                [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
-                self.net.dlist, self.capacity, self.rng_seed, self.want_heads, self.want_noise)
+            args = (self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
+                    [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
+                    self.net.dlist, self.capacity, self.rng_seed, self.want_heads, self.want_noise)
+            if len(models) == 1:
+                out, heads, used = _O.decode_pool_stepped_chunk(self._models[models[0]].packed, *args)
+            else:
+                out, heads, used = _O.decode_pool_stepped_chunk_models([self._models[m].packed for m in models], of, *args)
             for e, (s, it0, n_it) in enumerate(entries):
                 s._it_done = it0 + n_it
                 s._stream._begun = True
@@ -726,3 +740,30 @@ class SteppedDecodePool(DecodePool):
                 h = heads[e:e + 1, :n] if self.want_heads else None
                 results[s] = (o, h, used[e:e + 1, :n]) if self.want_noise else (o, h)
         return self._post_filter(results)
+
+
+class SteppedModelPool(SteppedDecodePool):
+    """a stepped decode pool whose sessions may each run a different model of the pool's geometry - one checkpoint per target
+    speaker of the REF6 recipe - in the SAME launch chain (swn_decode_pool_stepped_chunk_models): a tick over sessions of M
+    models makes the launches a one-model tick makes, not M chains.  add_model / open(model=k) as DecodePool; everything else
+    as SteppedDecodePool, and each session's output is bit-identical to HipNet.decode(variant=3) of that utterance alone on its
+    own model.  A tick whose sessions name one model issues the single-model op with that model's packed buffer, so a pool
+    that never mixes models pays nothing; calls are cut at 16 models (split_models).  The session buffer is that of
+    SteppedDecodePool with a wider table tail (ops.stepped_pool_models_session_floats)."""
+
+    def add_model(self, net) -> int:
+        return DecodePool.add_model(self, net)
+
+    def open(self, seed: Optional[torch.Tensor] = None, utt_id: Optional[int] = None, model: int = 0) -> PoolSession:
+        s = DecodePool.open(self, seed, utt_id, model)
+        s._it_done = 0
+        return s
+
+    def _session_floats(self, desc) -> int:
+        return _ops.stepped_pool_models_session_floats(desc, self.capacity)
+
+    def _calls(self, calls):
+        if len(self._models) == 1:
+            return super()._calls(calls)
+        return [(entries,) + _local_models([e[0].model for e in entries])
+                for entries in split_models(calls, lambda s: s.model)]
