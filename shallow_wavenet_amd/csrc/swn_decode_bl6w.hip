@@ -10,8 +10,9 @@
 //   * group A (waves 0-3, one per SIMD) owns the chain: per layer the CURRENT-tap half (128 rows x 64 inputs: thread (o, p) two
 //     rows x 16 inputs, reduced over 4 lanes), the gate epilogue, the hand-off through LDS;
 //   * group B (waves 4-7, the other wave of every SIMD) works one step AHEAD and off the chain: the OLDER-tap halves (+ bias) of
-//     all six layers for step t + 1, left in LDS (formed where group B has room: three in the first phase, three beside group
-//     A's out_1), and the whole out_skip accumulation of step t (slice l in the phase after layer l);
+//     layers 0-4 for step t + 1, left in LDS (formed where group B has room: two in the first phase, three beside group A's
+//     out_1; the last layer's is formed by group A, from group B's half in LDS, in the one phase where the chain waits for
+//     group B), and the whole out_skip accumulation of step t (slice l in the phase after layer l);
 //   * group A keeps its halves of all six matrices in registers (192 per thread), group B five of them (160) and the sixth in LDS
 //     (it also holds a slice of out_skip weights in flight); the out_1 matrix is LDS-resident whole (the 64 KB the sixth layer of
 //     the symmetric kernel took), only out_skip streams from L2;
@@ -55,7 +56,7 @@ struct Tw {
     static constexpr int o_skip = o_wup + 256;
     static constexpr int o_p2 = o_skip + S;                // out_2 as [NO][4] partial sums, one per wave of group A (b2 in wave 0's)
     static constexpr int o_tnz = o_p2 + 4 * NO;
-    static constexpr int o_cz = o_tnz + (EXT_ ? r4(NZB * NZC) : 16);   // cb[64], cv[2][64], cc[2][64]
+    static constexpr int o_cz = o_tnz + r4(NZB * NZC);     // (the noise ring, both modes)  cb[64], cv[2][64], cc[2][64]
     static constexpr int o_w2 = o_cz + 5 * H;              // out_2 rows [NO][S] (+b2)
     static constexpr int o_bias = o_w2 + NO * S + r4(NO);  // bsk[S], b1[O1]
     static constexpr int o_w1 = o_bias + S + O1;           // out_1, lane-tiled [8][O1][4][4] like the global copy w12
@@ -134,8 +135,9 @@ __device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], con
 }
 
 // ---- group B: older-tap product of layer LAYER for position qn = q + 1 (its operand h_{l-1}(qn - dil) is at least one step old),
-//      bias added, left for group A in the buffer of qn's parity
-template <class T, int LAYER>
+//      bias added, left for group A in the buffer of qn's parity.  (MB: operands of at most MB of the four input quads in flight
+//      at once - group A forms the last layer's product beside its 192 weight registers)
+template <class T, int LAYER, int MB = 4>
 __device__ __forceinline__ void older_sum(const float* lds, const float (&w)[2][16], const int qn, const int tb, float& az, float& ac) {
     constexpr int dil = 1 << LAYER;
     constexpr int R = T::ring_len(LAYER);
@@ -157,6 +159,7 @@ __device__ __forceinline__ void older_sum(const float* lds, const float (&w)[2][
         az = fmaf(w0.y, x.y, az); ac = fmaf(w1.y, x.y, ac);
         az = fmaf(w0.z, x.z, az); ac = fmaf(w1.z, x.z, ac);
         az = fmaf(w0.w, x.w, az); ac = fmaf(w1.w, x.w, ac);
+        if (MB < 4 && m % MB == MB - 1) __builtin_amdgcn_sched_barrier(0);
     }
     az = sum4(az); ac = sum4(ac);
 }
@@ -165,24 +168,24 @@ __device__ __forceinline__ void older_store(float* lds, const int qn, const int 
     const int o = tb >> 2, p = tb & 3, pr = p & 1;            // (called under p < 2)
     lds[T::o_old + (qn & 1) * (L * 2 * H) + LAYER * 2 * H + pr * H + o] = (p == 0 ? az : ac) + lds[T::o_bd + LAYER * 2 * H + pr * H + o];
 }
-template <class T, int LAYER>
+template <class T, int LAYER, int MB = 4>
 __device__ __forceinline__ void older_b(float* lds, const float (&w)[2][16], const int qn, const int tb) {
     float az, ac;
-    older_sum<T, LAYER>(lds, w, qn, tb, az, ac);
+    older_sum<T, LAYER, MB>(lds, w, qn, tb, az, ac);
     if ((tb & 3) < 2) older_store<T, LAYER>(lds, qn, tb, az, ac);
 }
-// three layers at once: one basic block of three independent chains (the stores' lane branch between them kept the scheduler from
+// several layers at once: one basic block of independent chains (the stores' lane branch between them kept the scheduler from
 // overlapping the products: 570 cycles each, one after the other)
-template <class T, int LA>
-__device__ __forceinline__ void older_b3(float* lds, const float (&w)[L][2][16], const int qn, const int tb) {
-    float az0, ac0, az1, ac1, az2, ac2;
-    older_sum<T, LA>(lds, w[LA], qn, tb, az0, ac0);
-    older_sum<T, LA + 1>(lds, w[LA + 1], qn, tb, az1, ac1);
-    older_sum<T, LA + 2>(lds, w[LA + 2], qn, tb, az2, ac2);
+template <int... LS> struct Layers {};
+template <class T, int NW, int... LS>
+__device__ __forceinline__ void older_bn(Layers<LS...>, float* lds, const float (&w)[NW][2][16], const int qn, const int tb) {
+    static_assert(((LS < NW) && ...), "register-resident halves only");
+    float az[sizeof...(LS)], ac[sizeof...(LS)];
+    int k = 0;
+    ((older_sum<T, LS>(lds, w[LS], qn, tb, az[k], ac[k]), ++k), ...);
     if ((tb & 3) < 2) {
-        older_store<T, LA>(lds, qn, tb, az0, ac0);
-        older_store<T, LA + 1>(lds, qn, tb, az1, ac1);
-        older_store<T, LA + 2>(lds, qn, tb, az2, ac2);
+        k = 0;
+        ((older_store<T, LS>(lds, qn, tb, az[k], ac[k]), ++k), ...);
     }
 }
 
@@ -259,6 +262,11 @@ __device__ __forceinline__ void skip_last_b(float* lds, const float4 (&wsl)[8], 
     if ((hp & 1) == 0) lds[T::o_skip + r + 32 * hp] = fmaxf(v, 0.f);
 }
 
+// group B's five older-tap products of position q + 1 (layer 5's is group A's, in skip-fin): those it forms in the merged phase and
+// those beside group A's out_1 (layer 0's operand is h0(q): not before the step's first barrier)
+using OlderMerged = Layers<3, 4>;
+using OlderOut1 = Layers<0, 1, 2>;
+
 // The program of one group (GA: group A).  The two groups run the SAME sequence of barriers; they are separate instantiations -
 // not one body with a run-time branch per phase - so that each has its own register allocation: as one body the allocation was the
 // union (192 weight registers of A + the out_skip weights B keeps in flight: 22-65 registers spilled inside the step loop).
@@ -316,7 +324,8 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     };
     for (int fr = fb0; fr < fb0 + 2 && fr < a.Tf; ++fr) load_frame(fr);
     // register-resident halves of the six matrices: group A tap 1 (current), group B tap 0 (older); rows (o, o + 64), inputs 16 p ..
-    float wreg[L][2][16];                                     // (group B: the last layer's entries stay unused - its half is in LDS)
+    constexpr int NWR = grpA ? L : L - 1;                     // (group B's half of the last layer is in LDS)
+    float wreg[NWR][2][16];
     {
         const int o = tg >> 2, p = tg & 3, k = grpA ? 1 : 0;
 #pragma unroll
@@ -327,20 +336,24 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const float4 t = src[v];
-                    if (l == L - 1 && !grpA) {                // group B keeps its half of the last layer in LDS
+                    if (l == L - 1 && !grpA) {                // group B leaves its half of the last layer in LDS (group A reads it)
                         *reinterpret_cast<float4*>(lds + T::o_wl + ((r * 4 + v) * NG + tg) * 4) = t;
-                        wreg[l][r][4 * v] = 0.f; wreg[l][r][4 * v + 1] = 0.f; wreg[l][r][4 * v + 2] = 0.f; wreg[l][r][4 * v + 3] = 0.f;
                     } else {
-                        wreg[l][r][4 * v] = t.x; wreg[l][r][4 * v + 1] = t.y; wreg[l][r][4 * v + 2] = t.z; wreg[l][r][4 * v + 3] = t.w;
+                        float (&wr)[16] = wreg[l < NWR ? l : 0][r];
+                        wr[4 * v] = t.x; wr[4 * v + 1] = t.y; wr[4 * v + 2] = t.z; wr[4 * v + 3] = t.w;
                     }
                 }
             }
     }
     __syncthreads();
     const float* sess_b = STREAM ? a.sess + (size_t)b * T::sess_floats : nullptr;
+    // (the session copies index from an opaque copy of tid: sharing their addresses with the one-time loads above kept those
+    //  registers live - spilled - across the step loop)
+    int tcp = tid;
+    asm volatile("" : "+v"(tcp));
     if (resume) {
-        for (int e = tid; e < T::ring_off(L); e += NT) lds[T::o_ring + e] = sess_b[e];
-        for (int e = tid; e < 2 * L * 2 * H; e += NT) lds[T::o_old + e] = sess_b[T::sess_old + e];
+        for (int e = tcp; e < T::ring_off(L); e += NT) lds[T::o_ring + e] = sess_b[e];
+        for (int e = tcp; e < 2 * L * 2 * H; e += NT) lds[T::o_old + e] = sess_b[T::sess_old + e];
         __syncthreads();
     }
 
@@ -403,29 +416,27 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
     };
-    // sampling noise staged off the chain (swn_decode_bl6.hip): wave 1 transforms tn = sign(e) log1p(-2|e|)
+    // sampling noise staged off the chain (swn_decode_bl6.hip): wave 1 transforms tn = sign(e) log1p(-2|e|) of 64 steps at once
+    // (lane = step) into a ring of NZB chunks, two chunks ahead of the tail that reads it.  Classic mode: the host-drawn deviate
+    // of chunk c + 1 is requested behind the transform of chunk c and stays in a register until then, so the pass - which
+    // stands at the head of a step, once per 64 steps - never waits for memory
+    float e_next = 0.f;
+    auto noise_load = [&](int c) {
+        const int step = c * T::NZC + tid - 64;
+        if (step < a.n_steps) e_next = a.noise[(size_t)b * a.n_steps + step];
+    };
     auto noise_chunk = [&](int c) {
-        if (EXT && tid >= 64 && tid < 128) {
+        if (grpA && tid >= 64 && tid < 128) {
             const int k = tid - 64, step = c * T::NZC + k;
             if (step < a.n_steps) {
-                const float e = swn_noise_laplace_at(a.nz, b, step, s0 + step, 0, a.n_steps, 1);
+                const float e = EXT ? swn_noise_laplace_at(a.nz, b, step, s0 + step, 0, a.n_steps, 1) : e_next;
                 const float sg = (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : 0.f);
                 lds[T::o_tnz + (c & (T::NZB - 1)) * T::NZC + k] = sg * log1pf(-2.f * fabsf(e));
             }
+            if (!EXT) noise_load(c + 1);
         }
     };
-    float e_next = 0.f;
-    auto noise_ahead = [&](int step) {
-        if (!EXT && tid == 64) {
-            if (step < a.n_steps) {
-                const float e = e_next;
-                const float sg = (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : 0.f);
-                lds[T::o_tnz + (step & 1) * 8] = sg * log1pf(-2.f * fabsf(e));
-            }
-            if (step + 1 < a.n_steps) e_next = a.noise[(size_t)b * a.n_steps + step + 1];
-        }
-    };
-    if (!EXT && tid == 64 && a.n_steps > 0) e_next = a.noise[(size_t)b * a.n_steps];
+    if (!EXT && grpA && tid >= 64 && tid < 128) noise_load(0);
     noise_chunk(0);
     noise_chunk(1);
 
@@ -435,7 +446,8 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     // diagnostic build only (tools/stamp_decode_w.py): per phase, the cycles each group's first wave WORKS between two barriers
     // (barrier waits excluded) leave through the `heads` debug buffer: [0..8) group A (phase 0 = the previous step's tail + layer
     // 0), [8] the tail's share of phase 0, [9] A's whole step, [10..18) group B, [20..26) of group B's phases L1 .. L5 and
-    // skip-fin the cycles from the barrier's release until the first out_skip weight register of the slice in flight has landed
+    // skip-fin the cycles from the barrier's release until the first out_skip weight register of the slice in flight has landed,
+    // [30..39) group A's wave 1 as [0..9) (the wave that stages the sampling noise: the first wave's stamps do not see that work)
     unsigned long long tw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tv[6] = {0, 0, 0, 0, 0, 0}, tstep = 0, tlast = 0, tbeg = 0;
 #define SWN_BAR(k) { tw[k] += __builtin_amdgcn_s_memtime() - tlast; lds_barrier(); tlast = __builtin_amdgcn_s_memtime(); }
     // (the empty asm uses the register, so the compiler places the vmcnt wait of the slice's oldest request in front of it)
@@ -445,9 +457,9 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
 #define SWN_WAIT_STAMP(k)
 #endif
     // one layer phase: group A runs the chain, group B prepares position q + 1 (and, during generation, accumulates out_skip)
-    // (OLD: the first layer whose older-tap product for position q + 1 group B forms in this phase, -1 = none; NOLD: how many,
-    //  1 or 3; X0: the row of h0(q) layer 0 reads)
-#define SWN_PHASE(LAYER, GEN, OLD, NOLD, X0)                                                                          \
+    // (GEN: a generation step - group B's older-tap products for position q + 1 then sit in the merged and the out_1 phase, and
+    //  layer 5's is group A's; in the prologue group B forms layer LAYER's in this phase.  X0: the row of h0(q) layer 0 reads)
+#define SWN_PHASE(LAYER, GEN, X0)                                                                                     \
     if constexpr (grpA) layer_a<T, LAYER>(lds, wreg[LAYER], q, wj, pb, tg,                                             \
                                           LAYER == 0 ? (X0) : lds + T::o_ring + T::ring_off(LAYER) +                   \
                                                                   (q & (T::ring_len(LAYER) - 1)) * H);                 \
@@ -459,8 +471,8 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             else { SWN_WAIT_STAMP(LAYER > 0 ? LAYER - 1 : 0) skip_roll_b<T, (LAYER > 0 ? LAYER : 1)>(lds, wsk2, wsl, sacc, tg, step0); } \
             __builtin_amdgcn_sched_barrier(0);                                                                         \
         }                                                                                                              \
-        if (OLD >= 0 && NOLD == 1) older_b<T, (OLD >= 0 ? OLD : 0)>(lds, wreg[OLD >= 0 ? OLD : 0], q + 1, tg);           \
-        if (OLD >= 0 && NOLD == 3) older_b3<T, (OLD >= 0 && OLD + 3 <= L ? OLD : 0)>(lds, wreg, q + 1, tg);              \
+        if (!(GEN)) older_b<T, LAYER>(lds, wreg[LAYER < NWR ? LAYER : 0], q + 1, tg);                                  \
+        else if (LAYER == 0) older_bn<T>(OlderMerged{}, lds, wreg, q + 1, tg);                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
     }                                                                                                                  \
     if (GEN) { SWN_BAR(LAYER) } else lds_barrier();
@@ -474,8 +486,8 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         input_seed(q);
         lds_barrier();
         const float* x0 = lds + T::o_ring + (q & 1) * H;
-        SWN_PHASE(0, false, 0, 1, x0) SWN_PHASE(1, false, 1, 1, x0) SWN_PHASE(2, false, 2, 1, x0) SWN_PHASE(3, false, 3, 1, x0)
-        SWN_PHASE(4, false, 4, 1, x0) SWN_PHASE(5, false, 5, 1, x0)
+        SWN_PHASE(0, false, x0) SWN_PHASE(1, false, x0) SWN_PHASE(2, false, x0) SWN_PHASE(3, false, x0)
+        SWN_PHASE(4, false, x0) SWN_PHASE(5, false, x0)
         (void)wsl; (void)sacc; (void)step0;
     }
 
@@ -484,7 +496,6 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     //      crossing (cond_taps) is written in that phase too: the buffer it fills was last read before the previous step's barriers,
     //      and the next reader comes U steps later.
     input_gen(RF + s0);
-    noise_ahead(0);
 #ifdef SWN_STAMP
     tlast = tbeg = __builtin_amdgcn_s_memtime();
 #endif
@@ -501,17 +512,18 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         unsigned step0 = 0;
         asm volatile("" : "+s"(step0));                       // opaque zero, see skip_issue_b
         const float* x0 = h0_row(q);
-        // group B's older-tap products of position q + 1 sit in the first phase (layers 3-5: no slice to consume yet, group A's tail
-        // + layer 0 the longest phase) and in the out_1 phase (layers 0-2: group A runs out_1 alone; layer 0 needs h0(q), which
+        // group B's older-tap products of position q + 1 sit in the first phase (OlderMerged: no slice to consume yet, group A's
+        // tail + layer 0 the longest phase) and in the out_1 phase (OlderOut1: group A runs out_1 alone; layer 0 needs h0(q), which
         // is not ready before the first barrier); all six beside the out_skip slices made group B take 1 050 cycles per layer phase
         // against group A's 710
-        SWN_PHASE(0, true, 3, 3, x0) SWN_PHASE(1, true, -1, 0, x0) SWN_PHASE(2, true, -1, 0, x0) SWN_PHASE(3, true, -1, 0, x0)
-        SWN_PHASE(4, true, -1, 0, x0) SWN_PHASE(5, true, -1, 0, x0)
-        // out_skip: the last slice and the reduction (group B); group A has nothing on this phase
+        SWN_PHASE(0, true, x0) SWN_PHASE(1, true, x0) SWN_PHASE(2, true, x0) SWN_PHASE(3, true, x0)
+        SWN_PHASE(4, true, x0) SWN_PHASE(5, true, x0)
+        // out_skip: the last slice and the reduction (group B).  Group A, otherwise idle here, forms layer 5's older-tap product of
+        // position q + 1 from group B's half in LDS, with group B's thread-to-row mapping and summation order (bit-identical): its
+        // operand h_4(q - 31) is 31 steps old, o_old[(q + 1) & 1][5] was last read in layer 5 of step q - 1 and is next read
+        // in layer 5 of step q + 1, two barriers ahead of the end of the step (the session copy of a chunk's last step)
         if constexpr (!grpA) { SWN_WAIT_STAMP(5) skip_last_b<T>(lds, wsl, sacc, tg); }
-        // the next step's deviate (classic mode: one lane of wave 1, a ~130-instruction log1p chain) where group A has no work:
-        // in the out_1 phase it made wave 1 the last of the group to reach the barrier
-        noise_ahead(i + 1);
+        else older_b<T, L - 1, 2>(lds, wreg[L - 1], q + 1, tg + (int)step0);   // (opaque zero: no address of it stays resident)
         SWN_BAR(6)
         if constexpr (grpA) {
             // out_1, 128 x 128, LDS-resident, by group A alone: thread (hr, hp) rows hr and hr + 64 over inputs 16 mm + 4 hp .. + 3 - one
@@ -543,7 +555,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
                 if ((tg & 63) < 4 && k < T::NO) lds[T::o_p2 + 4 * k + wv] = pz;
             }
         } else {
-            older_b3<T, 0>(lds, wreg, q + 1, tg);
+            older_bn<T>(OlderOut1{}, lds, wreg, q + 1, tg);
         }
         SWN_BAR(7)
         if constexpr (grpA) {
@@ -555,7 +567,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             // the partials' read, and the forced load is older than this step's stores - waiting for it must not wait for them
             // (vmcnt counts stores too)
             float tz = 0.f;                                // (an early read in the extended mode spilled four registers)
-            if constexpr (!EXT) tz = lds[T::o_tnz + (i & 1) * 8];
+            if constexpr (!EXT) tz = lds[T::o_tnz + (i & (T::NZB * T::NZC - 1))];
             float fv = 0.f;
             if (a.forced) fv = reinterpret_cast<const float*>(a.forced)[(size_t)b * a.n_steps + i];
             const float4 pz = *reinterpret_cast<const float4*>(lds + T::o_p2 + 4 * (ln < T::NO ? ln : T::NO - 1));
@@ -592,17 +604,12 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         if constexpr (grpA) tw[8] += __builtin_amdgcn_s_memtime() - tlast;
 #endif
     };
-    if constexpr (EXT) {
 #pragma unroll 1
-        for (int i0 = 0; i0 < a.n_steps; i0 += T::NZC) {
-            noise_chunk((i0 >> 6) + 2);
-            const int iend = i0 + T::NZC < a.n_steps ? i0 + T::NZC : a.n_steps;
+    for (int i0 = 0; i0 < a.n_steps; i0 += T::NZC) {
+        noise_chunk((i0 >> 6) + 2);
+        const int iend = i0 + T::NZC < a.n_steps ? i0 + T::NZC : a.n_steps;
 #pragma unroll 1
-            for (int i = i0; i < iend; ++i) gen_step(i);
-        }
-    } else {
-#pragma unroll 1
-        for (int i = 0; i < a.n_steps; ++i) gen_step(i);
+        for (int i = i0; i < iend; ++i) gen_step(i);
     }
 #ifdef SWN_STAMP
     { const unsigned long long tn = __builtin_amdgcn_s_memtime(); tw[0] += tn - tlast; tstep = tn - tbeg; }
@@ -610,8 +617,10 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     if constexpr (STREAM) {    // the state the next chunk resumes from (all LDS writes of the last step are behind barriers)
         __syncthreads();
         float* so = a.sess + (size_t)b * T::sess_floats;
-        for (int e = tid; e < T::ring_off(L); e += NT) so[e] = lds[T::o_ring + e];
-        for (int e = tid; e < 2 * L * 2 * H; e += NT) so[T::sess_old + e] = lds[T::o_old + e];
+        tcp = tid;
+        asm volatile("" : "+v"(tcp));
+        for (int e = tcp; e < T::ring_off(L); e += NT) so[e] = lds[T::o_ring + e];
+        for (int e = tcp; e < 2 * L * 2 * H; e += NT) so[T::sess_old + e] = lds[T::o_old + e];
         if (tid == 0) {
 #pragma unroll
             for (int k = 0; k < T::WN; ++k) so[T::sess_win + k] = win[k];
@@ -621,11 +630,11 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
 #undef SWN_BAR
 #undef SWN_WAIT_STAMP
 #ifdef SWN_STAMP
-    if ((tid == 0 || tid == NG) && b == 0 && a.heads) {
-        float* h = a.heads + (tid == 0 ? 0 : 10);
+    if ((tid == 0 || tid == 64 || tid == NG) && b == 0 && a.heads) {
+        float* h = a.heads + (tid == 0 ? 0 : tid == 64 ? 30 : 10);
         for (int k = 0; k < 9; ++k) h[k] = (float)((double)tw[k] / (double)a.n_steps);
         if (tid == 0) h[9] = (float)((double)tstep / (double)a.n_steps);
-        else for (int k = 0; k < 6; ++k) h[10 + k] = (float)((double)tv[k] / (double)a.n_steps);
+        else if (tid == NG) for (int k = 0; k < 6; ++k) h[10 + k] = (float)((double)tv[k] / (double)a.n_steps);
     }
 #endif
 }

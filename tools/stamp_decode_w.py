@@ -1,4 +1,5 @@
 """diagnostic: per-phase WORK cycles (barrier waits excluded) of the two wave groups of the wave-specialised BL6 decode kernel
+   (each group's first wave, and group A's wave 1, which stages the sampling noise)
    (needs the -DSWN_STAMP build: make -C shallow_wavenet_amd/csrc stamp ;
     SWN_HIP_LIB=shallow_wavenet_amd/libswn_hip_stamp.so python tools/stamp_decode_w.py)"""
 import sys, os
@@ -20,11 +21,11 @@ noise = torch.empty(1, n_steps, 1).uniform_(-0.4999, 0.5).cuda()
 for _ in range(2):
     out, heads = net.decode(aux, n_steps, noise, want_heads=True, variant=2)
 torch.cuda.synchronize()
-h = heads.flatten()[:26].cpu().numpy()
+h = heads.flatten()[:40].cpu().numpy()
 print("step total (group A clock): %.0f ticks" % h[9])
 for k, n in enumerate(names):
-    print("   %-10s A works %7.0f   B works %7.0f" % (n, h[k], h[10 + k]))
-print("   (of tail+L0: the tail, group A %7.0f)" % h[8])
-print("   sum        A %7.0f   B %7.0f" % (h[:8].sum(), h[10:18].sum()))
+    print("   %-10s A works %7.0f   B works %7.0f   A's wave 1 %7.0f" % (n, h[k], h[10 + k], h[30 + k]))
+print("   (of tail+L0: the tail, group A %7.0f, its wave 1 %7.0f)" % (h[8], h[38]))
+print("   sum        A %7.0f   B %7.0f   A's wave 1 %7.0f" % (h[:8].sum(), h[10:18].sum(), h[30:38].sum()))
 # group B, from the barrier's release until the first out_skip weight register of the slice in flight has landed
 print("   B's wait for its slice:  " + "  ".join("%s %.0f" % (n, h[20 + k]) for k, n in enumerate(names[1:7])))
