@@ -355,6 +355,36 @@ int    swn_decode_pool_stepped_chunk_models(const swn_net_desc* d, const float* 
                                             const swn_decode_io* io, float* session_dev, void* out_dev, float* heads_dev,
                                             void* stream);
 
+/* ---- stepped decode: a new session's prologue in parallel launches -------------------------------------------------------
+ * Before its first sample a session of the stepped chain fills its history rings: n_pro prologue positions, each a launch per
+ * layer (about 690 x 7 dependent launches on REF6).  None of that is autoregressive - the input sample of every prologue
+ * position is the seed padding (0 / class Q/2), the conditioning is frame 0 at phase 0 and the state starts from zeros - so
+ * swn_decode_stepped_prologue computes all positions of a level in ONE launch: setup, input level and one launch per layer.
+ * It zeroes and seeds the slot of every entry exactly as a SWN_CHUNK_BEGIN entry does and leaves each slot's whole state block
+ * bit-identical to what a BEGIN entry with it0 = 0, n_it = n_pro of swn_decode_pool_stepped_chunk leaves (the same sums in the
+ * same order).  Generation then continues through the existing calls: a pool entry with it0 = n_pro and no BEGIN, or
+ * swn_decode_chunk without BEGIN at step0 = 0.  A slot no entry names is not touched.
+ *   packed_dev | models_host, n_models, model_of_entry_host   one model (models_host and model_of_entry_host NULL), or one model
+ *                per entry as in the *_models calls (packed_dev is then not read)
+ *   n_slots      slots of session_dev: slot s lies at s * swn_decode_session_floats(d, 1, 3) floats, in the session of a
+ *                streamed decode of batch n_slots and in a stepped pool's session of capacity n_slots alike
+ *   io           only seed_dev is read: (n_entries, seg) fp32 | (n_entries) int32, indexed by entry, or NULL
+ *   work_dev     swn_decode_stepped_prologue_work_floats(d, n_entries) floats of scratch (two levels of n_pro x Hp floats per
+ *                entry); the query returns 0 for a geometry the stepped chain does not run or an entry count outside the range
+ * SWN_E_BADARG, checked before anything is launched: a null pointer, n_entries outside [1, SWN_DECODE_POOL_MAX_ENTRIES],
+ * n_slots < 1, a slot outside [0, n_slots) or in two entries, n_frames < 1, a non-NULL io->noise_dev or io->forced_dev, and
+ * the model rules of the *_models calls.  SWN_E_UNSUPPORTED: the stepped chain does not run this net with n_slots slots. */
+typedef struct swn_decode_stepped_prologue_entry {
+    const float* cond_dev;   /* this session's cond rows (n_frames, N) as swn_frontend wrote them: the prologue reads frame 0 */
+    int32_t n_frames;        /* >= 1 */
+    int32_t slot;            /* [0, n_slots) */
+} swn_decode_stepped_prologue_entry;
+size_t swn_decode_stepped_prologue_work_floats(const swn_net_desc* d, int n_entries);
+int    swn_decode_stepped_prologue(const swn_net_desc* d, const float* packed_dev, const float* const* models_host, int n_models,
+                                   const int32_t* model_of_entry_host, int n_slots,
+                                   const swn_decode_stepped_prologue_entry* entries_host, int n_entries,
+                                   const swn_decode_io* io, float* session_dev, float* work_dev, void* stream);
+
 /* ---- noise-shaping restoration on the device (run.sh stage 6 / 9: noise_shaping.py --inv false, run.sh:713-740) -------------
  * y = lowcut(MLSA_b(x)): the time-invariant MLSA filter of the coefficients b[0 .. order] (gain exp(b[0]) applied to the input,
  * Pade order `pade`, all-pass constant alpha; csrc/swn_dsp.c is the host version) followed by the causal FIR taps[0 .. n_taps-1],

@@ -48,6 +48,11 @@ class DecodeSteppedPoolEntry(ctypes.Structure):
                 ("n_it", c_int32), ("flags", c_int32), ("reserved", c_int32)]
 
 
+class DecodeSteppedPrologueEntry(ctypes.Structure):
+    """mirror of `swn_decode_stepped_prologue_entry` (include/swn_hip.h): one beginning session of a parallel prologue call."""
+    _fields_ = [("cond_dev", c_void_p), ("n_frames", c_int32), ("slot", c_int32)]
+
+
 class FrontendPoolEntry(ctypes.Structure):
     """mirror of `swn_frontend_pool_entry` (include/swn_hip.h): one session's share of a pool front end call."""
     _fields_ = [("aux_dev", c_void_p), ("new_dev", c_void_p), ("cond_dev", c_void_p), ("aux_stride", c_int32),
@@ -132,6 +137,10 @@ SIGNATURES = {
     "swn_decode_pool_stepped_chunk_models": (c_int, [POINTER(NetDesc), POINTER(c_void_p), c_int, POINTER(c_int32), c_int,
                                                      POINTER(DecodeSteppedPoolEntry), c_int, POINTER(DecodeIO), c_void_p,
                                                      c_void_p, c_void_p, c_void_p]),
+    "swn_decode_stepped_prologue_work_floats": (c_size_t, [POINTER(NetDesc), c_int]),
+    "swn_decode_stepped_prologue": (c_int, [POINTER(NetDesc), c_void_p, POINTER(c_void_p), c_int, POINTER(c_int32), c_int,
+                                            POINTER(DecodeSteppedPrologueEntry), c_int, POINTER(DecodeIO), c_void_p, c_void_p,
+                                            c_void_p]),
     "swn_postfilter_state_doubles": (c_size_t, [c_int, c_int, c_int]),
     "swn_postfilter_chunk": (c_int, [c_int, ctypes.c_double, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                      POINTER(PostfilterEntry), c_int, c_void_p]),

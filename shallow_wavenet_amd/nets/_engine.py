@@ -120,7 +120,7 @@ class EngineMixin:
             return net
         return cache[1]
 
-    def open_stream(self, batch: int, audio=None, variant: int = 0, post_filter=None):
+    def open_stream(self, batch: int, audio=None, variant: int = 0, post_filter=None, prologue: str = "stepped"):
         """a streamed decode of `batch` utterances on the module's current engine (shallow_wavenet_amd.streaming.DecodeStream):
         push features as they arrive, get the samples whose conditioning is final.  Bit-identical to batch_fast_generate with
         noise_source = "device" and the same key: the kernels draw the noise, keyed by `noise_rng_seed` when the caller
@@ -128,7 +128,8 @@ class EngineMixin:
         `noise_utterance_ids` / `noise_utterance_offset`.  The host-noise default of the Laplace model's
         batch_fast_generate draws the whole run up front in the reference's order and is not streamed (DecodeStream.advance
         takes host noise chunk by chunk).  audio: the seed waveform as batch_fast_generate takes it (None = zeros / Q/2).
-        post_filter: a postfilter.NoiseShapingRestorer - every chunk is also returned restored (run.sh stage 6) on the device."""
+        post_filter: a postfilter.NoiseShapingRestorer - every chunk is also returned restored (run.sh stage 6) on the device.
+        prologue: "stepped" | "parallel", as DecodeStream takes it (the latter on the stepped decode only)."""
         from .. import noise as _noise
         from ..streaming import DecodeStream
         net = self._engine()
@@ -144,9 +145,11 @@ class EngineMixin:
         return DecodeStream(net, batch, variant=variant, seed=seed,
                             rng_seed=_noise.draw_rng_seed() if key is None else int(key),
                             rng_utt0=int(getattr(self, "noise_utterance_offset", 0)),
-                            utt_ids=getattr(self, "noise_utterance_ids", None), post_filter=post_filter)
+                            utt_ids=getattr(self, "noise_utterance_ids", None), post_filter=post_filter,
+                            prologue=prologue)
 
-    def open_pool(self, capacity: int, variant: int = 0, post_filter=None, multi_model: bool = False):
+    def open_pool(self, capacity: int, variant: int = 0, post_filter=None, multi_model: bool = False,
+                  prologue: str = "stepped"):
         """a decode pool of `capacity` session slots on the module's current engine (shallow_wavenet_amd.streaming.DecodePool):
         independent utterances open, receive features and end at their own pace, and one launch per tick advances all of
         them.  The noise key follows open_stream: `noise_rng_seed` when the caller pinned one, else one fresh key per pool.
@@ -154,15 +157,18 @@ class EngineMixin:
         When the engine resolves to the stepped multi-launch decode (REF6-class nets: variant 0 or 3), the pool is a
         SteppedDecodePool (its step() also takes max_prologue).  post_filter: as open_stream, one slot per session.
         multi_model: the pool is to serve further nets of this geometry (add_model, open(model=k)): a net of the stepped
-        decode then gets a SteppedModelPool; the DecodePool of the other nets takes add_model as it is."""
+        decode then gets a SteppedModelPool; the DecodePool of the other nets takes add_model as it is.
+        prologue: "stepped" | "parallel", as SteppedDecodePool takes it; "parallel" on a net of another decode is a
+        ValueError."""
         from .. import _lib, noise as _noise, ops as _ops
-        from ..streaming import DecodePool, SteppedDecodePool, SteppedModelPool
+        from ..streaming import DecodePool, SteppedDecodePool, SteppedModelPool, _check_prologue
         key = getattr(self, "noise_rng_seed", None)
         rng_seed = _noise.draw_rng_seed() if key is None else int(key)
         net = self._engine()
         if _lib.lib().swn_decode_resolve_variant(_ops._desc(net.dlist), capacity, int(variant)) == 3:
             cls = SteppedModelPool if multi_model else SteppedDecodePool
-            return cls(net, capacity, rng_seed=rng_seed, post_filter=post_filter)
+            return cls(net, capacity, rng_seed=rng_seed, post_filter=post_filter, prologue=prologue)
+        _check_prologue(prologue, False)
         return DecodePool(net, capacity, variant=variant, rng_seed=rng_seed, post_filter=post_filter)
 
     def set_packed_engine(self, net: HipNet) -> None:

@@ -27,6 +27,7 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
                                             capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_stepped_chunk_models(models, model_of, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids,
                                                    desc, capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
+    torch.ops.swn.decode_stepped_prologue(models, model_of, session, conds, slots, seeds?, desc, n_slots)  -> ()
     torch.ops.swn.postfilter_chunk(image, state, inputs, slots, resets, order, alpha, pade, n_taps, capacity)  -> restored
     torch.ops.swn.stack_forward(packed, cond, audio, desc, want_hidden) -> (raw, work, hidden)
     torch.ops.swn.stack_forward_bf16(packed, wbf16, cond, audio, desc)  -> (raw, work)
@@ -674,6 +675,69 @@ def _(models, model_of, session, conds, slots, it0s, n_its, begins, seeds, utt_i
     return _stepped_pool_fake(models[0], conds, it0s, n_its, desc, want_heads, want_noise)
 
 
+def stepped_prologue_work_floats(d, n_entries: int) -> int:
+    """floats of scratch a parallel prologue call over n_entries sessions needs (swn_decode_stepped_prologue_work_floats); 0
+    when the stepped chain does not run the net"""
+    return int(_lib.lib().swn_decode_stepped_prologue_work_floats(ctypes.byref(d), int(n_entries)))
+
+
+def decode_stepped_prologue_impl(models: List[torch.Tensor], model_of: List[int], session: torch.Tensor,
+                                 conds: List[torch.Tensor], slots: List[int], seeds: Optional[torch.Tensor],
+                                 desc: List[int], n_slots: int) -> None:
+    """the prologue of new sessions of the stepped decode in parallel launches (swn_decode_stepped_prologue): entry e zeroes
+    slot slots[e] of `session` (the session of a DecodeStream of batch n_slots on variant 3, or a stepped pool's of capacity
+    n_slots; updated in place), seeds it from seeds[e] (laplace (E, seg) fp32 | softmax (E,) classes; None = zeros / Q/2) and
+    fills its history rings over conds[e] (n_frames, N) - every float of the slot as a BEGIN entry of
+    decode_pool_stepped_chunk with it0 = 0, n_it = n_pro leaves it.  models: one packed buffer for all entries (model_of is
+    then ignored), or up to 16 with model_of[e] naming entry e's.  Other slots are not touched."""
+    L = _lib.lib()
+    d = _desc(desc)
+    E = len(conds)
+    if len(slots) != E:
+        raise RuntimeError("decode_stepped_prologue: conds and slots must have one entry each")
+    if not 1 <= E <= _lib.DECODE_POOL_MAX_ENTRIES:
+        raise RuntimeError(f"decode_stepped_prologue: {E} entries, a call takes 1 .. {_lib.DECODE_POOL_MAX_ENTRIES}")
+    if len(models) == 1:
+        _need_cuda(models[0], "the packed parameters")
+        dev, packed, ptrs, of, n_models = models[0].device, models[0], None, None, 0
+    else:
+        dev, ptrs, of = _model_tables(L, d, models, model_of, E, "decode_stepped_prologue")
+        packed, n_models = None, len(models)
+    soft, seg, _, _, _, _ = _geom(d)
+    if session.device != dev or session.dtype != torch.float32 or not session.is_contiguous():
+        raise RuntimeError("session must be a contiguous fp32 tensor on the device of the packed parameters")
+    need = int(L.swn_decode_session_floats(ctypes.byref(d), int(n_slots), 3)) if int(n_slots) >= 1 else 0
+    work_floats = stepped_prologue_work_floats(d, E)
+    if need == 0 or work_floats == 0:
+        raise RuntimeError("decode_stepped_prologue: the stepped decode does not run this net with this many slots")
+    if session.numel() < need:
+        raise RuntimeError("session buffer too small for this (net, n_slots)")
+    table = (_lib.DecodeSteppedPrologueEntry * E)()
+    for e, c in enumerate(conds):
+        if c.device != dev or c.dtype != torch.float32 or not c.is_contiguous() or c.dim() != 2:
+            raise RuntimeError("every cond buffer must be a contiguous (n_frames, N) fp32 tensor on the device")
+        table[e] = _lib.DecodeSteppedPrologueEntry(cond_dev=c.data_ptr(), n_frames=int(c.shape[0]), slot=int(slots[e]))
+    if seeds is not None:
+        seeds = seeds.to(dev, torch.int32 if soft else torch.float32).contiguous()
+        if seeds.numel() != E * seg:
+            raise RuntimeError(f"seeds have {seeds.numel()} elements, expected {E * seg}")
+    work = torch.empty(work_floats, dtype=torch.float32, device=dev)
+    io = _lib.DecodeIO(noise_dev=None, forced_dev=None, seed_dev=_ptr(seeds), noise_out_dev=None, rng_seed=0, rng_utt0=0,
+                       reserved=0, rng_utt_ids_dev=None)
+    with _on(dev):
+        _lib.check(L.swn_decode_stepped_prologue(ctypes.byref(d), _ptr(packed), ptrs, n_models, of, int(n_slots), table, E,
+                                                 ctypes.byref(io), _ptr(session), _ptr(work), _stream(dev)),
+                   "decode_stepped_prologue")
+
+
+decode_stepped_prologue = custom_op("swn::decode_stepped_prologue", mutates_args=("session",))(decode_stepped_prologue_impl)
+
+
+@decode_stepped_prologue.register_fake
+def _(models, model_of, session, conds, slots, seeds, desc, n_slots):
+    return None
+
+
 def stepped_pool_plan(model_of: List[int], n_its: List[int], n_models: int, j: int = 0) -> Tuple[List[int], List[tuple]]:
     """the grouping swn_decode_pool_stepped_chunk_models launches by (swn_decode_stepped_pool_plan; pure host arithmetic) ->
     (table order, [(first table row, rows, model)] of the tiles of tick-local iteration j)"""
@@ -1189,7 +1253,8 @@ class LaplaceLossFunction(torch.autograd.Function):
 
 
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
-            "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "postfilter_chunk",
+            "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
+            "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
             "laplace_loss", "laplace_loss_backward")

@@ -25,6 +25,11 @@ grouped by model, so a tile of eight sessions fetches ONE model's weight rows.  
 Steps.  A generation step i reads cond frames up to ((i + 1) * seg - 1) // U, so with F final frames the steps
 [0, F * U // seg) can run (the bound of swn_decode).  Step counts come from frame counts on the host: nothing here
 waits for the device.
+
+Prologue.  A session of the stepped chain fills its history rings before its first sample: rf - seg + 1 positions, each a
+launch per layer.  prologue="parallel" (DecodeStream on variant 3, SteppedDecodePool, SteppedModelPool) fills them with
+swn_decode_stepped_prologue instead - all positions of a level in one launch, every float of the session bit-identical - before
+the first chunk / at the start of the tick in which the session has its first ready steps.  The default stays "stepped".
 """
 from __future__ import annotations
 
@@ -37,6 +42,18 @@ from . import ops as _ops          # registers torch.ops.swn.*
 from .config import NetConfig
 
 _O = torch.ops.swn
+
+PROLOGUES = ("stepped", "parallel")
+
+
+def _check_prologue(prologue, stepped: bool) -> str:
+    """the `prologue` keyword of the streams and pools: "stepped" | "parallel", the latter on the stepped chain only"""
+    if prologue not in PROLOGUES:
+        raise ValueError(f"prologue must be one of {PROLOGUES}, not {prologue!r}")
+    if prologue == "parallel" and not stepped:
+        raise ValueError('prologue="parallel" fills the history rings of the stepped multi-launch decode (variant 3); this '
+                         "net and variant resolve to another kernel, whose prologue runs inside its first launch")
+    return prologue
 
 
 def lookahead_frames(cfg: NetConfig) -> int:
@@ -70,6 +87,8 @@ class DecodeStream:
 
     post_filter   a postfilter.NoiseShapingRestorer: the stream claims `batch` of its slots (close() frees them) and
                   restores every chunk on the device (run.sh stage 6)
+    prologue      "stepped" (default) | "parallel": on the stepped chain (variant 3), fill the history rings before the first
+                  chunk with swn_decode_stepped_prologue - L + 2 launches instead of (rf - seg + 1) x (L + 1), same bits
 
     push / finish / advance return what HipNet.decode returns for the new steps: (out, heads) or, with want_noise,
     (out, heads, noise) - out laplace (B, n * seg) fp32 | softmax (B, n) int32 on the device, heads None unless asked for.
@@ -81,7 +100,7 @@ class DecodeStream:
 
     def __init__(self, net, batch: int, *, variant: int = 0, seed: Optional[torch.Tensor] = None, rng_seed: int = 0,
                  rng_utt0: int = 0, utt_ids: Optional[Sequence[int]] = None, want_heads: bool = False,
-                 want_noise: bool = False, post_filter=None):
+                 want_noise: bool = False, post_filter=None, prologue: str = "stepped"):
         cfg = net.cfg
         if not isinstance(batch, int) or batch < 1:
             raise ValueError(f"batch must be a positive integer, not {batch!r}")
@@ -98,6 +117,7 @@ class DecodeStream:
                              f"({lib.swn_strerror(resolved).decode()})")
         self.variant = int(variant)
         self.resolved_variant = resolved
+        self.prologue = _check_prologue(prologue, resolved == 3)
         self._session_floats = int(lib.swn_decode_session_floats(desc, batch, int(variant)))
         if seed is not None:
             seed = torch.as_tensor(seed)
@@ -235,8 +255,13 @@ class DecodeStream:
             self._session = torch.empty(self._session_floats, dtype=torch.float32, device=self.net.device)
         # n_frames of the call = the buffer's capacity (the per-utterance stride of the rows); the bound that matters is
         # the one on frames_final checked above - rows past it are zeros that no step of this chunk reads
+        begin = not self._begun
+        if begin and self.prologue == "parallel":
+            _O.decode_stepped_prologue([self.net.packed], [], self._session, [self._cond[b] for b in range(self.batch)],
+                                       list(range(self.batch)), self._seed, self.net.dlist, self.batch)
+            begin = False                           # the first chunk resumes from the filled session
         out, heads, used = _O.decode_chunk(self.net.packed, self._cond, self._session, noise, forced, self._seed,
-                                           self.net.dlist, self.steps_done, n, not self._begun, self.variant,
+                                           self.net.dlist, self.steps_done, n, begin, self.variant,
                                            self.rng_seed, self.rng_utt0, self.want_heads, self.want_noise, self._ids)
         self._begun = True
         self.steps_done += n
@@ -665,10 +690,13 @@ class SteppedDecodePool(DecodePool):
     with variant=3 (same rng_seed, utterance id and seed waveform).  Same interface and results as DecodePool; in addition,
     step(max_prologue=n) spreads a new session's prologue (rf - seg + 1 iterations, each a launch per layer) over ticks of at
     most n iterations, so the sessions already generating do not wait for all of it in one tick.  A session that only
-    advanced its prologue in a tick has no result for it."""
+    advanced its prologue in a tick has no result for it.
+    prologue="parallel": a tick first fills the history rings of the sessions that begin in it with one
+    swn_decode_stepped_prologue call per 64 of them (L + 2 launches, whatever their number), so they generate in the same tick
+    and max_prologue has nothing left to spread; same bits as the default "stepped"."""
 
     def __init__(self, net, capacity: int, *, rng_seed: int = 0, want_heads: bool = False, want_noise: bool = False,
-                 post_filter=None):
+                 post_filter=None, prologue: str = "stepped"):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
         self.net, self.cfg, self.capacity = net, net.cfg, capacity
@@ -681,6 +709,7 @@ class SteppedDecodePool(DecodePool):
             raise ValueError(f"the stepped decode does not run this net with {capacity} slots "
                              f"({lib.swn_strerror(lib.swn_decode_resolve_variant(desc, capacity, 3)).decode()})")
         self.variant = self.resolved_variant = 3
+        self.prologue = _check_prologue(prologue, True)
         self.n_pro = int(lib.swn_decode_stepped_prologue_iterations(desc))
         self.rng_seed = int(rng_seed) & 0x7FFFFFFFFFFFFFFF
         self.want_heads, self.want_noise = bool(want_heads), bool(want_noise)
@@ -712,16 +741,15 @@ class SteppedDecodePool(DecodePool):
         """one tick: every open session with ready steps runs the rest of its prologue (at most max_prologue iterations of
         it) and then up to min(ready, max_steps) steps, in calls of at most 64 sessions.  Returns {session: (out, heads) or
         (out, heads, noise)} for the sessions that generated, as DecodePool.step.  Nothing here waits for the device."""
+        if self.prologue == "parallel":
+            self._fill_prologues()
         calls = plan_stepped_tick([(s, s.steps_ready, s._it_done) for s in self._open.values()], self.n_pro, max_steps,
                                   max_prologue)
         results = {}
         for entries, models, of in self._calls(calls):
             sess = [e[0] for e in entries]
             begins = [s._it_done == 0 for s in sess]
-            seeds = None
-            if any(b and s._seed is not None for s, b in zip(sess, begins)):
-                seeds = torch.stack([s._seed.reshape(-1).to(torch.int32 if self.soft else torch.float32).cpu()
-                                     if s._seed is not None else self._default_seed() for s in sess])
+            seeds = self._seeds_of(sess, begins)
             args = (self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
                     [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
                     self.net.dlist, self.capacity, self.rng_seed, self.want_heads, self.want_noise)
@@ -740,6 +768,33 @@ class SteppedDecodePool(DecodePool):
                 h = heads[e:e + 1, :n] if self.want_heads else None
                 results[s] = (o, h, used[e:e + 1, :n]) if self.want_noise else (o, h)
         return self._post_filter(results)
+
+
+    def _seeds_of(self, sess, begins) -> Optional[torch.Tensor]:
+        """the seed rows of a call, one per entry, when a beginning session brought a seed waveform; else None"""
+        if not any(b and s._seed is not None for s, b in zip(sess, begins)):
+            return None
+        return torch.stack([s._seed.reshape(-1).to(torch.int32 if self.soft else torch.float32).cpu()
+                            if s._seed is not None else self._default_seed() for s in sess])
+
+    def _fill_prologues(self) -> None:
+        """prologue="parallel": the sessions that begin in this tick (nothing run yet, steps ready: their first frame is
+        final) get their history rings filled by one swn_decode_stepped_prologue call per 64 of them, cut at 16 models, and
+        stand at iteration n_pro afterwards - the tick then plans generation entries only."""
+        new = [(s,) for s in self._open.values() if s._it_done == 0 and s.steps_ready > 0]
+        limit = _lib.DECODE_POOL_MAX_ENTRIES
+        calls = [new[i:i + limit] for i in range(0, len(new), limit)]
+        if len(self._models) > 1:
+            calls = split_models(calls, lambda s: s.model)
+        for entries in calls:
+            sess = [e[0] for e in entries]
+            models, of = _local_models([s.model for s in sess])
+            _O.decode_stepped_prologue([self._models[m].packed for m in models], of, self._session,
+                                       [s._stream._cond[0] for s in sess], [s.slot for s in sess],
+                                       self._seeds_of(sess, [True] * len(sess)), self.net.dlist, self.capacity)
+            for s in sess:
+                s._it_done = self.n_pro
+                s._stream._begun = True
 
 
 class SteppedModelPool(SteppedDecodePool):
