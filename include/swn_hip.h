@@ -291,6 +291,37 @@ int    swn_decode_pool_chunk_models(const swn_net_desc* d, const float* const* m
                                     const swn_decode_io* io, float* session_dev,
                                     void* out_dev, float* heads_dev, int variant, void* stream);
 
+/* ---- decode with bf16 storage of the streamed head matrices ------------------------------------------------------------
+ * The symmetric BL6-class kernel (what variant 6 runs, and variants 0 / 2 for every net of the class but the single-sample
+ * Laplace ones) streams out_skip, out_1 and - softmax - out_2 from L2 at every step.  The *_w16 calls stream a bf16 image of
+ * those matrices instead: half the bytes, nothing else changed.  Semantics: out_skip.{l}.weight, out_1.weight and, for softmax
+ * nets, out_2.weight are rounded to bf16, round to nearest even (torch's tensor.to(torch.bfloat16)); a Laplace net's out_2 (a
+ * few rows resident on chip), every bias, the dilated-conv weights, the conditioning, activations, accumulation, gates and
+ * sampling stay fp32.  bf16 -> fp32 is exact and the kernel widens the stored values and runs the fp32 kernel's FMAs in the fp32
+ * kernel's order, so every output (out, heads, noise dump, session) is BIT-IDENTICAL to the fp32 call of the same variant on a
+ * model whose named matrices were rounded beforehand.  The session layout is that of the fp32 calls.
+ *   w16_dev     swn_decode_w16_bytes() bytes, filled by swn_pack_decode_w16 from packed_dev (one small launch; refill it
+ *               whenever packed_dev changes).  The query returns 0 for a net the symmetric BL6 kernel does not serve.
+ * swn_decode_w16 / swn_decode_chunk_w16 / swn_decode_pool_chunk_w16 take the arguments of swn_decode / swn_decode_chunk /
+ * swn_decode_pool_chunk plus w16_dev, with their argument rules (state_dev of swn_decode_w16 is not read and may be NULL).
+ * Checked before anything is launched: SWN_E_BADARG for a NULL w16_dev; SWN_E_UNSUPPORTED (text in swn_last_error_detail)
+ * when `variant` does not resolve to the symmetric BL6 kernel for the net - variant 0 / 2 on a single-sample Laplace net
+ * resolve to the wave-specialised kernel, so those nets need variant = 6; the stepped chain (launch-bound: weight bytes are
+ * not its limit), the generic kernel, the wave-specialised kernel and multi-model pools have no bf16 form, and no precision
+ * below bf16 exists. */
+size_t swn_decode_w16_bytes(const swn_net_desc* d);
+int    swn_pack_decode_w16(const swn_net_desc* d, const float* packed_dev, void* w16_dev, void* stream);
+int    swn_decode_w16(const swn_net_desc* d, const float* packed_dev, const float* cond_dev,
+                      int batch, int n_frames, int n_steps, const swn_decode_io* io,
+                      float* state_dev, void* out_dev, float* heads_dev, int variant, const void* w16_dev, void* stream);
+int    swn_decode_chunk_w16(const swn_net_desc* d, const float* packed_dev, const float* cond_dev, int batch, int n_frames,
+                            int step0, int n_steps, int flags, const swn_decode_io* io, float* session_dev,
+                            void* out_dev, float* heads_dev, int variant, const void* w16_dev, void* stream);
+int    swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* packed_dev, int capacity,
+                                 const swn_decode_pool_entry* entries_host, int n_entries,
+                                 const swn_decode_io* io, float* session_dev,
+                                 void* out_dev, float* heads_dev, int variant, const void* w16_dev, void* stream);
+
 /* ---- stepped decode pool: the decode pool of the stepped multi-launch decode (variant 3: REF6-class nets) -----------
  * Every launch of the stepped chain (input layer, L gated layers, skip / out_1 [/ out_2] mat-vecs, tail) serves all
  * entries of the table, each at its own iteration, so a tick costs about what one utterance's chunk costs while up to 64

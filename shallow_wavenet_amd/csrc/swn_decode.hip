@@ -629,3 +629,97 @@ extern "C" int swn_decode_pool_chunk_models(const swn_net_desc* d, const float* 
     for (int e = 0; e < n_entries; ++e) m.of[e] = (unsigned char)model_of_entry[e];
     return pool_chunk(d, nullptr, &m, capacity, entries, n_entries, io, session, out, heads, variant, stream_);
 }
+
+// ---- bf16 storage of the streamed head matrices ---------------------------------------------------------------------
+namespace {
+
+// the *_w16 calls run on the symmetric BL6 kernel alone: SWN_OK when `variant` resolves to it for (net, batch)
+int w16_kernel_check(const swn_net_desc* d, int batch, int variant, const char* where) {
+    const int k = resolve_kernel(d, batch, variant);
+    if (k == KSEL_BL6) return SWN_OK;
+    if (k == KSEL_BL6W)
+        swn_set_error_detail(where, "bf16 weights run on the symmetric BL6 kernel; this net resolves to the wave-specialised "
+                                    "kernel with this variant: pass variant = 6");
+    else
+        swn_set_error_detail(where, "bf16 weights run on the symmetric BL6 kernel only (variant 0, 2 or 6 on a net of its "
+                                    "class); the stepped and generic kernels are not served");
+    return SWN_E_UNSUPPORTED;
+}
+
+}  // namespace
+
+extern "C" int swn_decode_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                              int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, int variant,
+                              const void* w16, void* stream_) {
+    (void)state;                                           // the kernel keeps its state on chip
+    SwnGeom g;
+    int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (batch < 1 || n_frames < 1 || n_steps < 0 || !io || !w16) return SWN_E_BADARG;
+    if (n_steps > 0 && (!packed || !cond || !out)) return SWN_E_BADARG;
+    if ((long)n_steps * g.seg > (long)n_frames * g.U) return SWN_E_BADARG;   // conditioning too short
+    rc = w16_kernel_check(d, batch, variant, "swn_decode_w16");
+    if (rc < 0) return rc;
+    if (n_steps == 0) return SWN_OK;
+    const SwnNoise nz = swn_noise_of(io);
+    (void)hipGetLastError();
+    return swn_decode_bl6_w16_try(d, packed, w16, cond, batch, n_frames, n_steps, &nz, io->forced_dev, io->seed_dev, out, heads,
+                                  stream_);
+}
+
+extern "C" int swn_decode_chunk_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                    int step0, int n_steps, int flags, const swn_decode_io* io, float* session, void* out,
+                                    float* heads, int variant, const void* w16, void* stream_) {
+    SwnGeom g;
+    int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (!io || !session || !packed || !cond || !w16) return SWN_E_BADARG;
+    if (batch < 1 || n_frames < 1 || step0 < 0 || n_steps < 0 || (flags & ~SWN_CHUNK_BEGIN)) return SWN_E_BADARG;
+    const bool begin = (flags & SWN_CHUNK_BEGIN) != 0;
+    if (begin && step0 != 0) return SWN_E_BADARG;
+    if (n_steps > 0 && !out) return SWN_E_BADARG;
+    if (((long long)step0 + n_steps) * g.seg > (long long)n_frames * g.U) return SWN_E_BADARG;   // conditioning not final yet
+    rc = w16_kernel_check(d, batch, variant, "swn_decode_chunk_w16");
+    if (rc < 0) return rc;
+    if (n_steps == 0 && !begin) return SWN_OK;
+    const SwnNoise nz = swn_noise_of(io);
+    (void)hipGetLastError();
+    return swn_decode_bl6_w16_chunk(d, packed, w16, cond, batch, n_frames, step0, n_steps, begin ? 0 : 1, &nz, io->forced_dev,
+                                    io->seed_dev, session, out, heads, stream_);
+}
+
+extern "C" int swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* packed, int capacity,
+                                         const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                         float* session, void* out, float* heads, int variant, const void* w16,
+                                         void* stream_) {
+    SwnGeom g;
+    int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (!packed || !entries || !io || !session || !w16) return SWN_E_BADARG;
+    if (capacity < 1 || n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
+    if (io->noise_dev || io->forced_dev) return SWN_E_BADARG;    // pools draw their noise on the device, no teacher forcing
+    SwnPoolTable t = {};
+    int n_max = 0;
+    bool work = false;
+    for (int e = 0; e < n_entries; ++e) {
+        const swn_decode_pool_entry& en = entries[e];
+        const bool begin = (en.flags & SWN_CHUNK_BEGIN) != 0;
+        if (!en.cond_dev || en.n_frames < 1 || en.slot < 0 || en.slot >= capacity || en.step0 < 0 || en.n_steps < 0 ||
+            (en.flags & ~SWN_CHUNK_BEGIN) || en.reserved != 0)
+            return SWN_E_BADARG;
+        if (begin && en.step0 != 0) return SWN_E_BADARG;
+        if (((long long)en.step0 + en.n_steps) * g.seg > (long long)en.n_frames * g.U) return SWN_E_BADARG;
+        for (int f = 0; f < e; ++f)
+            if (entries[f].slot == en.slot) return SWN_E_BADARG;   // two workgroups on one session
+        t.e[e] = en;
+        n_max = en.n_steps > n_max ? en.n_steps : n_max;
+        work = work || begin || en.n_steps > 0;
+    }
+    if (n_max > 0 && !out) return SWN_E_BADARG;
+    rc = w16_kernel_check(d, capacity, variant, "swn_decode_pool_chunk_w16");
+    if (rc < 0) return rc;
+    if (!work) return SWN_OK;                              // every slot stays as it is
+    const SwnNoise nz = swn_pool_noise_of(io);
+    (void)hipGetLastError();
+    return swn_decode_bl6_w16_pool(d, packed, w16, &t, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
+}

@@ -18,6 +18,7 @@
 // 9 s_barriers per generated step (10 for softmax).
 #include "swn_decode_bl6_common.hpp"
 #include "swn_decode_internal.hpp"
+#include <type_traits>
 
 namespace {
 
@@ -177,10 +178,80 @@ __device__ __forceinline__ void layer_phase(float* lds, const float (&w)[2][16],
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// out_skip slice of one layer, 4 lanes per row, weights streamed from the lane-tiled copy.
+// The same three streams over the bf16 image (W16 instantiations; layout: Bl6W16Layout).  One 16-byte load holds slices
+// 2g (low halves) and 2g + 1 (high halves) of a lane's inputs; they are widened and accumulated slice 2g first, input by
+// input, into the accumulator the fp32 form uses - the same FMAs in the same order on the rounded weights.
 template <class T, int LAYER>
+__device__ __forceinline__ void skip_fma16(const float* lds, const uint4& w, int g, int hp, float& acc) {
+    const float4 x0 = *reinterpret_cast<const float4*>(lds + T::o_hcat + LAYER * H + 32 * g + 4 * hp);
+    const float4 x1 = *reinterpret_cast<const float4*>(lds + T::o_hcat + LAYER * H + 32 * g + 16 + 4 * hp);
+    acc = fmaf(w16_lo(w.x), x0.x, acc); acc = fmaf(w16_lo(w.y), x0.y, acc);
+    acc = fmaf(w16_lo(w.z), x0.z, acc); acc = fmaf(w16_lo(w.w), x0.w, acc);
+    acc = fmaf(w16_hi(w.x), x1.x, acc); acc = fmaf(w16_hi(w.y), x1.y, acc);
+    acc = fmaf(w16_hi(w.z), x1.z, acc); acc = fmaf(w16_hi(w.w), x1.w, acc);
+}
+template <class T, int LAYER>
+__device__ __forceinline__ void skip_slice16(const float* lds, __amdgpu_buffer_rsrc_t wsk, float (&sacc)[T::S / 128]) {
+    const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
+#pragma unroll
+    for (int ps = 0; ps < T::S / 128; ++ps)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const uint4 w = buf_ld4u(wsk, (unsigned)((hr + 128 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 2 + g) * T::S) * 64u);
+            skip_fma16<T, LAYER>(lds, w, g, hp, sacc[ps]);
+        }
+}
+template <class T, int LAYER>
+__device__ __forceinline__ void skip_issue(__amdgpu_buffer_rsrc_t wsk, uint4 (&wsl)[2 * (T::S / 128)]) {
+    const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
+#pragma unroll
+    for (int ps = 0; ps < T::S / 128; ++ps)
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+            wsl[ps * 2 + g] = buf_ld4u(wsk, (unsigned)((hr + 128 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 2 + g) * T::S) * 64u);
+}
+template <class T, int LAYER>
+__device__ __forceinline__ void skip_consume(const float* lds, const uint4 (&wsl)[2 * (T::S / 128)],
+                                             float (&sacc)[T::S / 128]) {
+    const int hp = threadIdx.x & 3;
+#pragma unroll
+    for (int ps = 0; ps < T::S / 128; ++ps)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) skip_fma16<T, LAYER>(lds, wsl[ps * 2 + g], g, hp, sacc[ps]);
+}
+// rows x NI mat-vec over image section [NI / 32][rows][4][4 words]: a0 takes the even slices, a1 the odd ones, as below
+template <int ROWS, int NI>
+__device__ __forceinline__ void tiled_matvec16(__amdgpu_buffer_rsrc_t wt, const float* bias, const float* x, float* y,
+                                               bool relu) {
+    const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
+#pragma unroll
+    for (int ps = 0; ps < ROWS / 128; ++ps) {
+        const int row = hr + 128 * ps;
+        float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+        for (int mm = 0; mm < NI / 16; mm += 2) {
+            const uint4 w = buf_ld4u(wt, (unsigned)(row * 4 + hp) * 16u, (unsigned)((mm / 2) * ROWS) * 64u);
+            const float4 x0 = *reinterpret_cast<const float4*>(x + 16 * mm + 4 * hp);
+            const float4 x1 = *reinterpret_cast<const float4*>(x + 16 * (mm + 1) + 4 * hp);
+            a0 = fmaf(w16_lo(w.x), x0.x, a0); a0 = fmaf(w16_lo(w.y), x0.y, a0);
+            a0 = fmaf(w16_lo(w.z), x0.z, a0); a0 = fmaf(w16_lo(w.w), x0.w, a0);
+            a1 = fmaf(w16_hi(w.x), x1.x, a1); a1 = fmaf(w16_hi(w.y), x1.y, a1);
+            a1 = fmaf(w16_hi(w.z), x1.z, a1); a1 = fmaf(w16_hi(w.w), x1.w, a1);
+        }
+        float v = sum4(a0 + a1);
+        if (hp == 0) {
+            v += bias[row];
+            y[row] = relu ? fmaxf(v, 0.f) : v;
+        }
+        if (ps + 1 < ROWS / 128) __builtin_amdgcn_sched_barrier(0);     // <= 8 loads (one pass of rows) in flight
+    }
+}
+
+// out_skip slice of one layer, 4 lanes per row, weights streamed from the lane-tiled copy.
+template <class T, int LAYER, bool W16 = false>
 __device__ __forceinline__ void skip_slice(const float* lds, __amdgpu_buffer_rsrc_t wsk2,
                                            float (&sacc)[T::S / 128]) {
+    if constexpr (W16) { skip_slice16<T, LAYER>(lds, wsk2, sacc); return; }
     constexpr int layer = LAYER;
     const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
 #pragma unroll
@@ -224,9 +295,10 @@ __device__ __forceinline__ void skip_consume(const float* lds, const float4 (&ws
 }
 
 // rows x NI mat-vec, 4 lanes per row, lane-tiled weights [NI/16][rows][4][4] streamed from L2.
-template <int ROWS, int NI>
+template <int ROWS, int NI, bool W16 = false>
 __device__ __forceinline__ void tiled_matvec(__amdgpu_buffer_rsrc_t wt, const float* bias,
                                              const float* x, float* y, bool relu) {
+    if constexpr (W16) { tiled_matvec16<ROWS, NI>(wt, bias, x, y, relu); return; }
     const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
 #pragma unroll
     for (int ps = 0; ps < ROWS / 128; ++ps) {
@@ -250,9 +322,11 @@ __device__ __forceinline__ void tiled_matvec(__amdgpu_buffer_rsrc_t wt, const fl
     }
 }
 
-template <bool POOL, bool MODELS> struct B6ArgsOf { using type = Bl6Args; };
+template <bool POOL, bool MODELS, bool W16 = false> struct B6ArgsOf { using type = Bl6Args; };
 template <> struct B6ArgsOf<true, false> { using type = Bl6PoolArgs; };
 template <> struct B6ArgsOf<true, true> { using type = Bl6PoolModelsArgs; };
+template <> struct B6ArgsOf<false, false, true> { using type = Bl6W16Args; };
+template <> struct B6ArgsOf<true, false, true> { using type = Bl6PoolW16Args; };
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6Args& launch, const Bl6Args&) { return launch; }
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, const Bl6Args& entry) { return entry; }
 
@@ -263,9 +337,12 @@ __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, con
 // window come from the session instead of the prologue, and they go back to it at the end.  The step itself is the same code.
 // POOL (with STREAM): one entry of a decode pool (swn_decode_pool_chunk); `a` holds the workgroup's entry as a batch-1 chunk
 // (swn_pool_entry_args), b = 0.  MODELS (with POOL): the entry's weights are those of its model (SwnPoolModels).
-template <class T, bool STREAM = false, bool POOL = false, bool MODELS = false>
-__global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL, MODELS>::type ka) {
+// W16 (with EXT, without MODELS): out_skip, out_1 and the softmax out_2 stream from the bf16 image ka.w16 instead of the fp32
+// lane-tiled copies, and the LDS-resident out_1 slices are widened from it; every other load and every FMA is the fp32 code.
+template <class T, bool STREAM = false, bool POOL = false, bool MODELS = false, bool W16 = false>
+__global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL, MODELS, W16>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    static_assert(!W16 || (T::EXT && !MODELS), "bf16 weights: extended single-model instantiations only");
     Bl6Args pa;                                            // POOL: this workgroup's entry as a batch-1 chunk
     if constexpr (POOL) {
         static_assert(STREAM && T::EXT, "pools run the streamed extended mode");
@@ -302,6 +379,16 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
         for (int e = tid; e < 2 * H; e += NT) { lds[T::o_cz + H + e] = P[a.y.cv + e]; lds[T::o_cz + 3 * H + e] = P[a.y.cc + e]; }
         for (int e = tid; e < T::NO * S; e += NT) lds[T::o_w2 + e] = P[a.y.w2 + (size_t)(e / S) * r4(S) + (e % S)];
         for (int e = tid; e < T::NO; e += NT) lds[T::o_w2 + T::NO * S + e] = P[a.y.b2 + e];
+        if constexpr (W16) {
+            // the resident out_1 slices hold the rounded values, widened once: slice mm is half mm & 1 of image slice mm / 2
+            const unsigned* w1i = reinterpret_cast<const unsigned*>(
+                static_cast<const char*>(ka.w16) + w16_layout(S, T::O1, T::NO, false).w1);
+            for (int e = tid; e < T::W1L * T::O1 * 16; e += NT) {
+                const int mm = e / (T::O1 * 16);
+                const unsigned w = w1i[(mm >> 1) * T::O1 * 16 + e % (T::O1 * 16)];
+                lds[T::o_w1l + e] = (mm & 1) ? w16_hi(w) : w16_lo(w);
+            }
+        } else
         for (int e = tid; e < T::W1L * T::O1 * 16; e += NT) lds[T::o_w1l + e] = P[a.y.w12 + e];
     }
     // conditioning frames are copied 16 B per lane through a buffer resource (32-bit offsets)
@@ -492,9 +579,16 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
     }
 
     // ---- generation (cswnv_shift1.py:348-402 / dswnv.py:338-374)
-    const __amdgpu_buffer_rsrc_t wsk2 = make_rsrc(P + a.y.wsk2, (unsigned)(L * S * 64 * sizeof(float)));
-    const __amdgpu_buffer_rsrc_t w12 = make_rsrc(P + a.y.w12, (unsigned)(T::O1 * S * sizeof(float)));
-    const __amdgpu_buffer_rsrc_t w22 = make_rsrc(P + a.y.w22, (unsigned)(T::NO * T::O1 * sizeof(float)));
+    // W16: the same three names over the sections of the bf16 image (half the bytes)
+    constexpr unsigned WB = W16 ? 2 : sizeof(float);
+    [[maybe_unused]] const Bl6W16Layout y16 = w16_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX);
+    auto wsrc = [&](size_t f32_off, [[maybe_unused]] size_t w16_off) -> const void* {
+        if constexpr (W16) return static_cast<const char*>(ka.w16) + w16_off;
+        else return P + f32_off;
+    };
+    const __amdgpu_buffer_rsrc_t wsk2 = make_rsrc(wsrc(a.y.wsk2, y16.wsk), (unsigned)(L * S * 64 * WB));
+    const __amdgpu_buffer_rsrc_t w12 = make_rsrc(wsrc(a.y.w12, y16.w1), (unsigned)(T::O1 * S * WB));
+    const __amdgpu_buffer_rsrc_t w22 = make_rsrc(wsrc(a.y.w22, y16.w2), (unsigned)(T::NO * T::O1 * WB));
 #ifdef SWN_STAMP
     // diagnostic build only (tools/stamp_decode.py): per-phase cycle sums of wave 0 leave the kernel
     // through the `heads` debug buffer, which this build writes nothing else into.
@@ -524,7 +618,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
         if constexpr (S == 128 && SEG <= 2) {
 #endif
             // out_skip weights are issued one phase ahead and stay in flight across the LDS-only barrier
-            float4 wsl[4];
+            typename std::conditional<W16, uint4[2], float4[4]>::type wsl;
             layer_phase<T, 0, SEG>(lds, wreg[0], q0, wj, pb); skip_issue<T, 0>(wsk2, wsl); lds_barrier(); STAMP(1)
             layer_phase<T, 1, SEG>(lds, wreg[1], q0, wj, pb); skip_consume<T, 0>(lds, wsl, sacc); skip_issue<T, 1>(wsk2, wsl); lds_barrier(); STAMP(2)
             layer_phase<T, 2, SEG>(lds, wreg[2], q0, wj, pb); skip_consume<T, 1>(lds, wsl, sacc); skip_issue<T, 2>(wsk2, wsl); lds_barrier(); STAMP(3)
@@ -534,7 +628,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
             skip_consume<T, 5>(lds, wsl, sacc);
 #ifdef SWN_W1PREF
             // out_1 weights: issued now, they fly during the reduction and the barrier
-            {
+            if constexpr (!W16) {
                 const int hr = tid >> 2, hp = tid & 3;
 #pragma unroll
                 for (int mm = 0; mm < 8; ++mm)
@@ -543,12 +637,12 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
 #endif
         } else {
             layer_phase<T, 0, SEG>(lds, wreg[0], q0, wj, pb); lds_barrier(); STAMP(1)
-            layer_phase<T, 1, SEG>(lds, wreg[1], q0, wj, pb); skip_slice<T, 0>(lds, wsk2, sacc); lds_barrier(); STAMP(2)
-            layer_phase<T, 2, SEG>(lds, wreg[2], q0, wj, pb); skip_slice<T, 1>(lds, wsk2, sacc); lds_barrier(); STAMP(3)
-            layer_phase<T, 3, SEG>(lds, wreg[3], q0, wj, pb); skip_slice<T, 2>(lds, wsk2, sacc); lds_barrier(); STAMP(4)
-            layer_phase<T, 4, SEG>(lds, wreg[4], q0, wj, pb); skip_slice<T, 3>(lds, wsk2, sacc); lds_barrier(); STAMP(5)
-            layer_phase<T, 5, SEG>(lds, wreg[5], q0, wj, pb); skip_slice<T, 4>(lds, wsk2, sacc); lds_barrier(); STAMP(6)
-            skip_slice<T, 5>(lds, wsk2, sacc);
+            layer_phase<T, 1, SEG>(lds, wreg[1], q0, wj, pb); skip_slice<T, 0, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(2)
+            layer_phase<T, 2, SEG>(lds, wreg[2], q0, wj, pb); skip_slice<T, 1, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(3)
+            layer_phase<T, 3, SEG>(lds, wreg[3], q0, wj, pb); skip_slice<T, 2, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(4)
+            layer_phase<T, 4, SEG>(lds, wreg[4], q0, wj, pb); skip_slice<T, 3, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(5)
+            layer_phase<T, 5, SEG>(lds, wreg[5], q0, wj, pb); skip_slice<T, 4, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(6)
+            skip_slice<T, 5, W16>(lds, wsk2, sacc);
         }
         {
             const int hr = tid >> 2, hp = tid & 3;
@@ -566,7 +660,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
 #ifndef SWN_W1PREF
         if constexpr (false) {
 #else
-        if constexpr (S == 128 && SEG <= 2) {
+        if constexpr (S == 128 && SEG <= 2 && !W16) {
 #endif
             const int hr = tid >> 2, hp = tid & 3;
             float a0 = 0.f, a1 = 0.f;
@@ -587,6 +681,15 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
                 constexpr int NG = S / 16 - T::W1L;
                 const int hr = tid >> 2, hp = tid & 3;
                 float4 wg[NG];
+                if constexpr (W16) {
+                    static_assert(T::W1L % 2 == 0 && NG % 2 == 0, "whole image slices on either side");
+#pragma unroll
+                    for (int g = 0; g < NG / 2; ++g) {
+                        const uint4 w = buf_ld4u(w12, (unsigned)(hr * 4 + hp) * 16u, (unsigned)((T::W1L / 2 + g) * T::O1) * 64u);
+                        wg[2 * g] = make_float4(w16_lo(w.x), w16_lo(w.y), w16_lo(w.z), w16_lo(w.w));
+                        wg[2 * g + 1] = make_float4(w16_hi(w.x), w16_hi(w.y), w16_hi(w.z), w16_hi(w.w));
+                    }
+                } else
 #pragma unroll
                 for (int mm = 0; mm < NG; ++mm) wg[mm] = buf_ld4(w12, (unsigned)(hr * 4 + hp) * 16u, (unsigned)((T::W1L + mm) * T::O1) * 64u);
                 float a0 = 0.f, a1 = 0.f;
@@ -606,7 +709,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
                 const float v = sum4(a0 + a1);
                 if (hp == 0) lds[T::o_o1 + hr] = fmaxf(v + lds[T::o_bias + S + hr], 0.f);
             } else {
-                tiled_matvec<T::O1, S>(w12, lds + T::o_bias + S, lds + T::o_skip, lds + T::o_o1, true);
+                tiled_matvec<T::O1, S, W16>(w12, lds + T::o_bias + S, lds + T::o_skip, lds + T::o_o1, true);
             }
         }
         lds_barrier(); STAMP(8)
@@ -663,7 +766,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
         } else {
             constexpr int Q = T::Q;
             constexpr int QL = Q > 0 ? (Q + 63) / 64 : 1;     // classes per lane (this branch is also compiled for Laplace nets)
-            tiled_matvec<T::NO, T::O1>(w22, lds + T::o_bias + S + T::O1, lds + T::o_o1, lds + T::o_o2, false);
+            tiled_matvec<T::NO, T::O1, W16>(w22, lds + T::o_bias + S + T::O1, lds + T::o_o1, lds + T::o_o2, false);
             lds_barrier();
             if (HEADS_ON && a.heads)
                 for (int e = tid; e < T::NO; e += NT) a.heads[((size_t)b * a.n_steps + i) * T::NO + e] = lds[T::o_o2 + e];
@@ -760,7 +863,117 @@ int with_tr(const SwnGeom& g, F&& f) {
     return SWN_E_UNSUPPORTED;
 }
 
+// the bf16 image of one section: fp32 lane-tiled slices [ns][rows][16] -> [ns / 2][rows][16] words, slice 2g rounded into
+// the low half and slice 2g + 1 into the high half (round to nearest even; a NaN stays a quiet NaN, as torch rounds)
+__device__ __forceinline__ unsigned bf16_rne(float f) {
+    const unsigned u = __builtin_bit_cast(unsigned, f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+struct W16PackArgs {
+    const float* src[3];       // wsk2, w12, w22 of the packed buffer
+    unsigned* dst[3];
+    unsigned words[3];         // words of each image section (0: none)
+    unsigned slice[3];         // words of one image slice = floats of one fp32 slice: rows * 16
+};
+__global__ __launch_bounds__(256) void pack_w16_kernel(const W16PackArgs a) {
+    const unsigned sec = blockIdx.y;
+    for (unsigned w = blockIdx.x * 256 + threadIdx.x; w < a.words[sec]; w += gridDim.x * 256) {
+        const unsigned g = w / a.slice[sec], rem = w % a.slice[sec];
+        const float lo = a.src[sec][(size_t)(2 * g) * a.slice[sec] + rem];
+        const float hi = a.src[sec][(size_t)(2 * g + 1) * a.slice[sec] + rem];
+        a.dst[sec][w] = bf16_rne(lo) | (bf16_rne(hi) << 16);
+    }
+}
+
+template <class T, bool STREAM = false>
+int launch_w16(const Bl6W16Args& a, hipStream_t st) {
+    return launch_kernel(decode_bl6_kernel<T, STREAM, false, false, true>, T::lds_bytes, a.B, a, st, "swn_decode_w16(bl6)");
+}
+
 }  // namespace
+
+// ---- bf16 storage of the streamed head matrices (swn_decode_w16 / swn_decode_chunk_w16 / swn_decode_pool_chunk_w16)
+extern "C" size_t swn_decode_w16_bytes(const swn_net_desc* d) {
+    SwnGeom g;
+    if (swn_make_geom(d, &g) < 0) return 0;
+    size_t n = 0;
+    with_tr(g, [&](auto t) {
+        using T = decltype(t);
+        n = w16_layout(T::S, T::O1, T::NO, T::KIND == SWN_KIND_SOFTMAX).total;
+        return SWN_OK;
+    });
+    return n;
+}
+
+extern "C" int swn_pack_decode_w16(const swn_net_desc* d, const float* packed, void* w16, void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (!packed || !w16) return SWN_E_BADARG;
+    if (swn_decode_w16_bytes(d) == 0) {
+        swn_set_error_detail("swn_pack_decode_w16", "bf16 weights exist for the nets the symmetric BL6 kernel serves only");
+        return SWN_E_UNSUPPORTED;
+    }
+    SwnLayout y;
+    swn_make_layout(&g, &y);
+    const bool soft = g.kind == SWN_KIND_SOFTMAX;
+    const Bl6W16Layout y16 = w16_layout(g.S, g.O1, g.NO, soft);
+    char* img = static_cast<char*>(w16);
+    W16PackArgs a;
+    a.src[0] = packed + y.wsk2; a.dst[0] = reinterpret_cast<unsigned*>(img + y16.wsk);
+    a.src[1] = packed + y.w12;  a.dst[1] = reinterpret_cast<unsigned*>(img + y16.w1);
+    a.src[2] = packed + y.w22;  a.dst[2] = reinterpret_cast<unsigned*>(img + y16.w2);
+    a.words[0] = (unsigned)(L * g.S * 32); a.slice[0] = (unsigned)(g.S * 16);
+    a.words[1] = (unsigned)(g.O1 * g.S / 2); a.slice[1] = (unsigned)(g.O1 * 16);
+    a.words[2] = soft ? (unsigned)(g.NO * g.O1 / 2) : 0u; a.slice[2] = (unsigned)(g.NO * 16);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(pack_w16_kernel, dim3(32, 3), dim3(256), 0, (hipStream_t)stream_, a);
+    return swn_launch_status("swn_pack_decode_w16");
+}
+
+extern "C" int swn_decode_bl6_w16_pool(const swn_net_desc* d, const float* packed, const void* w16, const SwnPoolTable* t,
+                                       int n_entries, int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out,
+                                       float* heads, void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    Bl6PoolW16Args p;
+    fill_args(p.c, g, packed, nullptr, nz, nullptr, seed, out, heads, n_entries, 0, n_max, 0, 0, sess);
+    p.t = *t;
+    p.w16 = w16;
+    hipStream_t st = (hipStream_t)stream_;
+    return with_tr(g, [&](auto tr) {
+        using T = typename decltype(tr)::Ext;
+        return launch_kernel(decode_bl6_kernel<T, true, true, false, true>, T::lds_bytes, n_entries, p, st,
+                             "swn_decode_pool_chunk_w16(bl6)");
+    });
+}
+
+extern "C" int swn_decode_bl6_w16_chunk(const swn_net_desc* d, const float* packed, const void* w16, const float* cond, int batch,
+                                        int n_frames, int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
+                                        const void* seed, float* sess, void* out, float* heads, void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    Bl6W16Args a;
+    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, step0, resume, sess);
+    a.w16 = w16;
+    hipStream_t st = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    return with_tr(g, [&](auto t) { return launch_w16<typename decltype(t)::Ext, true>(a, st); });
+}
+
+// the one-shot decode: always the extended instantiation (it also takes the host-drawn stream)
+extern "C" int swn_decode_bl6_w16_try(const swn_net_desc* d, const float* packed, const void* w16, const float* cond, int batch,
+                                      int n_frames, int n_steps, const SwnNoise* nz, const void* forced, const void* seed,
+                                      void* out, float* heads, void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    Bl6W16Args a;
+    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, 0, 0, nullptr);
+    a.w16 = w16;
+    hipStream_t st = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    return with_tr(g, [&](auto t) { return launch_w16<typename decltype(t)::Ext>(a, st); });
+}
 
 // one pool launch (swn_decode_pool_chunk checked the entries): one workgroup per entry, sessions [capacity][sess_floats]
 extern "C" int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t,

@@ -50,6 +50,32 @@ struct Bl6PoolModelsArgs : Bl6PoolArgs {
     SwnPoolModels m;
 };
 static_assert(sizeof(Bl6PoolModelsArgs) <= 4096, "kernel arguments are limited to 4 KB");
+// bf16 storage of the streamed head matrices (swn_decode_w16 and its chunk / pool forms, symmetric kernel only): the image
+// pointer rides behind the arguments of the fp32 launch in structs of its own, taken by instantiations of their own (W16), so
+// the fp32 kernels keep their arguments and their code.
+struct Bl6W16Args : Bl6Args {
+    const void* w16;
+};
+struct Bl6PoolW16Args : Bl6PoolArgs {
+    const void* w16;
+};
+static_assert(sizeof(Bl6PoolW16Args) <= 4096, "kernel arguments are limited to 4 KB");
+// The image (swn_pack_decode_w16): the three lane-tiled copies wsk2 / w12 / w22 of the packed buffer rounded to bf16 (nearest
+// even), slices 2g and 2g + 1 of 16 inputs folded into one: section [NS / 2][rows][4 lanes][4 words], word j of a lane =
+// bf16(slice 2g, input 4 lane + j) in bits 0-15 | bf16(slice 2g + 1, input 4 lane + j) in bits 16-31.  A lane's 16-byte load
+// then carries what two of its fp32 loads carry, and it widens (<< 16, & 0xffff0000: exact) and accumulates them in the
+// order of the fp32 kernel.  Byte offsets of the sections; w2 is empty for Laplace nets (their out_2 rows sit in LDS as fp32).
+struct Bl6W16Layout {
+    size_t wsk, w1, w2, total;
+};
+inline __host__ __device__ Bl6W16Layout w16_layout(int S, int O1, int NO, bool softmax) {
+    Bl6W16Layout y;
+    y.wsk = 0;
+    y.w1 = y.wsk + (size_t)L * S * 64 * 2;
+    y.w2 = y.w1 + (size_t)O1 * S * 2;
+    y.total = y.w2 + (softmax ? (size_t)NO * O1 * 2 : 0);
+    return y;
+}
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int pow2ceil(int x) { int r = 1; while (r < x) r <<= 1; return r; }
@@ -63,6 +89,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsig
 __device__ __forceinline__ float4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
     return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, soff_bytes, 0));
 }
+// 16 bytes of the bf16 image: four words of two bf16 each; lo / hi widen one half of a word to the fp32 it was rounded from
+__device__ __forceinline__ uint4 buf_ld4u(__amdgpu_buffer_rsrc_t r, unsigned voff_bytes, unsigned soff_bytes) {
+    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, voff_bytes, soff_bytes, 0));
+}
+__device__ __forceinline__ float w16_lo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
+__device__ __forceinline__ float w16_hi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {

@@ -46,6 +46,15 @@ int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoo
 int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, const SwnPoolModels* models,
                          int n_entries, int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
                          void* stream);
+// the symmetric kernel over the bf16 image of its streamed head matrices (w16: swn_pack_decode_w16), extended mode only
+int swn_decode_bl6_w16_try(const swn_net_desc* d, const float* packed, const void* w16, const float* cond, int batch,
+                           int n_frames, int n_steps, const SwnNoise* nz, const void* forced, const void* seed, void* out,
+                           float* heads, void* stream);
+int swn_decode_bl6_w16_chunk(const swn_net_desc* d, const float* packed, const void* w16, const float* cond, int batch,
+                             int n_frames, int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
+                             const void* seed, float* sess, void* out, float* heads, void* stream);
+int swn_decode_bl6_w16_pool(const swn_net_desc* d, const float* packed, const void* w16, const SwnPoolTable* t, int n_entries,
+                            int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads, void* stream);
 
 // swn_decode_stepped.hip (one launch per phase of a step, for the large geometries)
 size_t swn_decode_stepped_state_floats(const swn_net_desc* d, int batch);

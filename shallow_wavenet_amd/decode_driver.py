@@ -16,6 +16,9 @@ Device-drawn sampling noise (`--noise_source device`, the softmax default) is ke
 `torch.manual_seed(--seed)` and by each utterance's position in the unsorted `--feats` list, so an utterance draws
 the same stream whatever `--n_gpus` and wherever the length sort puts it.
 
+`--weights bf16` (not a reference flag) stores the head matrices the BL6-class decode kernel streams at every step as bf16
+(HipNet.decode(weights="bf16")); it passes through to the one-shot decode, `--stream_frames` and `--pool_slots`.
+
 `--restore_stats` / `--restore_writedir` (not reference flags) also restore every waveform on the device as run.sh stage 6
 does with `noise_shaping.py --inv false` (shallow_wavenet_amd.postfilter; --mcep_dim_start, --mcep_alpha and --mag as that
 script takes them) and write the restored WAVs under --restore_writedir; the unrestored WAVs under --outdir stay as they are.
@@ -164,6 +167,7 @@ def gpu_decode(kind: str, args, config, feat_list: Sequence[str], device, packed
         model.eval()
         model.noise_source = getattr(args, "noise_source", None)
         model.noise_rng_seed = rng_key
+        model.decode_weights = getattr(args, "weights", None) or "fp32"
         if global_index is None:
             global_index = list(range(len(feat_list)))
         model.set_packed_engine(HipNet(cfg, D.broadcast_packed(cfg, packed, device, src=packed_src_rank), device))
@@ -215,7 +219,7 @@ def stream_generate(model, seed, aux, n_samples_list, frames_per_push: int, rest
     the samples collected as they become final (shallow_wavenet_amd.streaming; device-drawn noise only).  With a restorer
     (postfilter.NoiseShapingRestorer): (samples, restored samples), each chunk restored on the device as it comes."""
     B = aux.shape[0]
-    stream = model.open_stream(B, seed, post_filter=restorer)
+    stream = model.open_stream(B, seed, variant=_weights_variant(model), post_filter=restorer)
     pieces, rpieces = [], []
     for r in [stream.push(aux[:, :, f0:f0 + frames_per_push]) for f0 in range(0, aux.shape[2], frames_per_push)] + [stream.finish()]:
         pieces.append(r[0])
@@ -234,6 +238,11 @@ def stream_generate(model, seed, aux, n_samples_list, frames_per_push: int, rest
     if restorer is None:
         return out
     return out, [restored[b, :n] for b, n in zip(range(B), n_samples_list)]
+
+
+def _weights_variant(model) -> int:
+    """--weights bf16 runs on the symmetric BL6 kernel alone (variant 6, as batch_fast_generate asks for it); else auto"""
+    return 6 if getattr(model, "decode_weights", "fp32") == "bf16" else 0
 
 
 def make_restorer(args, device):
@@ -259,7 +268,7 @@ def pool_decode(kind: str, args, model, feat_list: Sequence[str], global_index: 
     in list order as slots free up; each runs its own n_samples / seg steps over its own features, so its WAV is that of the
     default path with --batch_size 1 (device-drawn noise, utterance index = position in the unsorted list)."""
     cfg = model._cfg
-    pool = model.open_pool(args.pool_slots, post_filter=restorer)
+    pool = model.open_pool(args.pool_slots, variant=_weights_variant(model), post_filter=restorer)
     pending = list(range(len(feat_list)))
     live = {}                                   # session -> (utterance id, n_samples, out pieces, restored pieces)
     t0, n_tot = time.time(), 0
@@ -314,6 +323,10 @@ def make_parser() -> argparse.ArgumentParser:
                    help="not a reference flag: where the sampling noise is drawn - host = the torch CPU generator in "
                         "the reference's order (reproduces the reference's CPU decode), device = inside the kernels; "
                         "default: the model's own default (Laplace host, softmax device)")
+    p.add_argument("--weights", default="fp32", choices=["fp32", "bf16"],
+                   help="not a reference flag: bf16 = the head matrices the BL6-class decode kernel streams at every step "
+                        "(out_skip, out_1, softmax out_2) are stored as bf16, everything else stays fp32 (BL6-class nets "
+                        "only; applies to the one-shot decode, --stream_frames and --pool_slots)")
     p.add_argument("--stream_frames", default=0, type=int,
                    help="not a reference flag: > 0 decodes each batch as a stream, pushing this many feature frames at a "
                         "time (needs device-drawn noise; the WAVs are those of the one-shot decode)")

@@ -80,6 +80,7 @@ class EngineMixin:
     place (load_state_dict, optimizer step, .to()/.cuda()); SURVEY.md 8b 'Checkpoint / ownership'."""
 
     _cfg: NetConfig
+    decode_weights = "fp32"   # "bf16": batch_fast_generate / open_stream / open_pool stream the head matrices as bf16
     device_unfold = True      # packed gradients -> p.grad by one launch (False: the torch-op version, nets/_autograd.py)
 
     def _param_slots(self):
@@ -120,7 +121,8 @@ class EngineMixin:
             return net
         return cache[1]
 
-    def open_stream(self, batch: int, audio=None, variant: int = 0, post_filter=None, prologue: str = "stepped"):
+    def open_stream(self, batch: int, audio=None, variant: int = 0, post_filter=None, prologue: str = "stepped",
+                    weights: Optional[str] = None):
         """a streamed decode of `batch` utterances on the module's current engine (shallow_wavenet_amd.streaming.DecodeStream):
         push features as they arrive, get the samples whose conditioning is final.  Bit-identical to batch_fast_generate with
         noise_source = "device" and the same key: the kernels draw the noise, keyed by `noise_rng_seed` when the caller
@@ -129,7 +131,8 @@ class EngineMixin:
         batch_fast_generate draws the whole run up front in the reference's order and is not streamed (DecodeStream.advance
         takes host noise chunk by chunk).  audio: the seed waveform as batch_fast_generate takes it (None = zeros / Q/2).
         post_filter: a postfilter.NoiseShapingRestorer - every chunk is also returned restored (run.sh stage 6) on the device.
-        prologue: "stepped" | "parallel", as DecodeStream takes it (the latter on the stepped decode only)."""
+        prologue: "stepped" | "parallel", as DecodeStream takes it (the latter on the stepped decode only).
+        weights: "fp32" | "bf16" as DecodeStream takes it; None = the module's `decode_weights`."""
         from .. import noise as _noise
         from ..streaming import DecodeStream
         net = self._engine()
@@ -146,10 +149,10 @@ class EngineMixin:
                             rng_seed=_noise.draw_rng_seed() if key is None else int(key),
                             rng_utt0=int(getattr(self, "noise_utterance_offset", 0)),
                             utt_ids=getattr(self, "noise_utterance_ids", None), post_filter=post_filter,
-                            prologue=prologue)
+                            prologue=prologue, weights=resolve_decode_weights(self) if weights is None else weights)
 
     def open_pool(self, capacity: int, variant: int = 0, post_filter=None, multi_model: bool = False,
-                  prologue: str = "stepped"):
+                  prologue: str = "stepped", weights: Optional[str] = None):
         """a decode pool of `capacity` session slots on the module's current engine (shallow_wavenet_amd.streaming.DecodePool):
         independent utterances open, receive features and end at their own pace, and one launch per tick advances all of
         them.  The noise key follows open_stream: `noise_rng_seed` when the caller pinned one, else one fresh key per pool.
@@ -159,17 +162,19 @@ class EngineMixin:
         multi_model: the pool is to serve further nets of this geometry (add_model, open(model=k)): a net of the stepped
         decode then gets a SteppedModelPool; the DecodePool of the other nets takes add_model as it is.
         prologue: "stepped" | "parallel", as SteppedDecodePool takes it; "parallel" on a net of another decode is a
-        ValueError."""
+        ValueError.  weights: "fp32" | "bf16" as DecodePool takes it (one model, not on the stepped pools); None = the
+        module's `decode_weights`."""
         from .. import _lib, noise as _noise, ops as _ops
         from ..streaming import DecodePool, SteppedDecodePool, SteppedModelPool, _check_prologue
         key = getattr(self, "noise_rng_seed", None)
         rng_seed = _noise.draw_rng_seed() if key is None else int(key)
         net = self._engine()
+        weights = resolve_decode_weights(self) if weights is None else weights
         if _lib.lib().swn_decode_resolve_variant(_ops._desc(net.dlist), capacity, int(variant)) == 3:
             cls = SteppedModelPool if multi_model else SteppedDecodePool
-            return cls(net, capacity, rng_seed=rng_seed, post_filter=post_filter, prologue=prologue)
+            return cls(net, capacity, rng_seed=rng_seed, post_filter=post_filter, prologue=prologue, weights=weights)
         _check_prologue(prologue, False)
-        return DecodePool(net, capacity, variant=variant, rng_seed=rng_seed, post_filter=post_filter)
+        return DecodePool(net, capacity, variant=variant, rng_seed=rng_seed, post_filter=post_filter, weights=weights)
 
     def set_packed_engine(self, net: HipNet) -> None:
         """install an engine whose packed buffer arrived by RCCL broadcast (dist.py)."""
@@ -195,6 +200,23 @@ def resolve_noise_source(module, default: str) -> str:
     if src not in NOISE_SOURCES:
         raise ValueError(f"noise_source must be one of {NOISE_SOURCES} or None, not {src!r}")
     return src
+
+
+def resolve_decode_weights(module) -> str:
+    """`module.decode_weights`: "fp32" | "bf16" | None (= "fp32") - how batch_fast_generate, open_stream and open_pool store
+    the streamed head matrices (HipNet.decode(weights=...)).  batch_fast_generate takes no kernel variant, so with "bf16" it
+    asks for the one kernel that has the mode (variant 6: the symmetric BL6 kernel whatever the net)."""
+    from ..runtime import DECODE_WEIGHTS
+    w = getattr(module, "decode_weights", None) or "fp32"
+    if w not in DECODE_WEIGHTS:
+        raise ValueError(f"decode_weights must be one of {DECODE_WEIGHTS} or None, not {w!r}")
+    return w
+
+
+def decode_weight_kwargs(module) -> dict:
+    """the keywords batch_fast_generate adds to HipNet.decode for `module.decode_weights`"""
+    w = resolve_decode_weights(module)
+    return {} if w == "fp32" else {"weights": w, "variant": 6}
 
 
 def log_decode_speed(seg: int, n_steps: int, n_utts: int, seconds: float) -> None:

@@ -34,7 +34,7 @@ from shallow_wavenet_amd.config import NetConfig                      # noqa: E4
 from shallow_wavenet_amd import noise as _noise                       # noqa: E402
 from shallow_wavenet_amd.nets._engine import (                        # noqa: E402,F401
     CausalConv1d, EngineMixin, TwoSidedDilConv1d, UpSampling, dropout_device, initialize, log_decode_speed,
-    resolve_noise_source)
+    resolve_noise_source, decode_weight_kwargs)
 
 
 class CSWNV(EngineMixin, nn.Module):
@@ -173,14 +173,14 @@ class CSWNV(EngineMixin, nn.Module):
             seed = audio.reshape(B, -1)[:, -self.seg:] if torch.count_nonzero(audio).item() != 0 else None
             if resolve_noise_source(self, "host") == "host":
                 noise = _noise.laplace_uniform(self._cfg, n_steps, B)      # host CPU generator, reference order
-                out, _ = net.decode(aux, n_steps, noise, seed=seed)
+                out, _ = net.decode(aux, n_steps, noise, seed=seed, **decode_weight_kwargs(self))
             else:
                 # one fresh key per call unless the caller pinned one for the run (decode_driver: so that an utterance's
                 # stream depends only on (key, its global index), not on batching or on the number of GPUs)
                 key = getattr(self, "noise_rng_seed", None)
                 out, _ = net.decode(aux, n_steps, None, seed=seed, rng_seed=_noise.draw_rng_seed() if key is None else int(key),
                                     rng_utt0=int(getattr(self, "noise_utterance_offset", 0)),
-                                    utt_ids=getattr(self, "noise_utterance_ids", None))
+                                    utt_ids=getattr(self, "noise_utterance_ids", None), **decode_weight_kwargs(self))
             samples = out.cpu().numpy()                                   # DEVICE -> HOST, :426
             log_decode_speed(self.seg, n_steps, len(n_samples_list), time.time() - start)
         samples = samples[:, -max_samples:] if max_samples <= samples.shape[1] else samples

@@ -28,7 +28,7 @@ from shallow_wavenet_amd.config import NetConfig                      # noqa: E4
 from shallow_wavenet_amd import noise as _noise                       # noqa: E402
 from shallow_wavenet_amd.nets._engine import (                        # noqa: E402,F401
     CausalConv1d, EngineMixin, TwoSidedDilConv1d, UpSampling, dropout_device, initialize, log_decode_speed,
-    resolve_noise_source)
+    resolve_noise_source, decode_weight_kwargs)
 
 
 def encode_mu_law(x, mu=256):
@@ -158,14 +158,14 @@ class DSWNV(EngineMixin, nn.Module):
             seed = seed if torch.count_nonzero(seed - self.n_quantize // 2).item() != 0 else None
             if resolve_noise_source(self, "device") == "host":
                 noise = _noise.softmax_exponential(self._cfg, n_steps, B)     # Exp(1) draws of multinomial(n=1)
-                out, _ = net.decode(aux, n_steps, noise, seed=seed)
+                out, _ = net.decode(aux, n_steps, noise, seed=seed, **decode_weight_kwargs(self))
             else:
                 # one fresh key per call unless the caller pinned one for the run (decode_driver: so that an utterance's
                 # stream depends only on (key, its global index), not on batching or on the number of GPUs)
                 key = getattr(self, "noise_rng_seed", None)
                 out, _ = net.decode(aux, n_steps, None, seed=seed, rng_seed=_noise.draw_rng_seed() if key is None else int(key),
                                     rng_utt0=int(getattr(self, "noise_utterance_offset", 0)),
-                                    utt_ids=getattr(self, "noise_utterance_ids", None))
+                                    utt_ids=getattr(self, "noise_utterance_ids", None), **decode_weight_kwargs(self))
             samples = out.cpu().numpy().astype(np.int64)
             log_decode_speed(1, n_steps, len(n_samples_list), time.time() - start)
         return [samples[b, :n] for b, n in zip(range(B), n_samples_list)]

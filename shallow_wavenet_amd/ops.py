@@ -23,6 +23,10 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
                                     variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_chunk_models(models, model_of, session, conds, slots, step0s, n_steps, begins, seeds?, utt_ids,
                                            desc, capacity, variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
+    torch.ops.swn.pack_decode_w16(packed, desc)                    -> w16   (bf16 image of the streamed head matrices)
+    torch.ops.swn.decode_w16(packed, w16, cond, ...decode's arguments)            -> (out, heads, noise_used)
+    torch.ops.swn.decode_chunk_w16(packed, w16, cond, session, ...decode_chunk's) -> (out, heads, noise_used)
+    torch.ops.swn.decode_pool_chunk_w16(packed, w16, session, ...decode_pool_chunk's) -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_stepped_chunk(packed, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids, desc,
                                             capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_stepped_chunk_models(models, model_of, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids,
@@ -294,12 +298,31 @@ def _(models, model_of, auxs, conds, staged, n_news, n_receiveds, f0s, f1s, fina
 
 
 # ------------------------------------------------------------------------------------------ decode
+def _check_w16(w16: torch.Tensor, packed: torch.Tensor, d) -> torch.Tensor:
+    """the bf16 image of pack_decode_w16 as the *_w16 calls want it: uint8, contiguous, on the device of `packed`, of the
+    size the net's image has (a net the symmetric BL6 kernel does not serve has none)"""
+    need = _lib.lib().swn_decode_w16_bytes(ctypes.byref(d))
+    if need == 0:
+        raise RuntimeError("bf16 weights exist for the nets the symmetric BL6 decode kernel serves only")
+    if w16.device != packed.device or w16.dtype != torch.uint8 or not w16.is_contiguous() or w16.numel() != need:
+        raise RuntimeError(f"w16 must be the contiguous uint8 image of pack_decode_w16 ({need} bytes) on the device of the "
+                           "packed parameters")
+    return w16
+
+
 def decode_impl(packed: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor], forced: Optional[torch.Tensor],
            seed: Optional[torch.Tensor], desc: List[int], n_steps: int, variant: int, rng_seed: int, rng_utt0: int,
            want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """prologue + n_steps generation steps for every utterance (swn_decode).  noise None = drawn in the kernels, utterance
     b as global utterance utt_ids[b] (int32 (B), values < 2^31) or rng_utt0 + b."""
+    return _decode_call(None, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads,
+                        want_noise, utt_ids)
+
+
+def _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise,
+                 utt_ids):
+    """decode (w16 None: swn_decode) and decode_w16 (the bf16 image: swn_decode_w16)"""
     L = _lib.lib()
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
@@ -325,7 +348,9 @@ def decode_impl(packed: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.
         if utt_ids.numel() != B:
             raise RuntimeError(f"utt_ids has {utt_ids.numel()} elements, expected {B}")
     r = ctypes.byref(d)
-    state = torch.empty(L.swn_decode_state_floats(r, B), dtype=torch.float32, device=dev)
+    if w16 is not None:
+        _check_w16(w16, packed, d)
+    state = torch.empty(L.swn_decode_state_floats(r, B) if w16 is None else 0, dtype=torch.float32, device=dev)
     out = torch.empty((B, n_steps * seg), dtype=torch.int32 if soft else torch.float32, device=dev)
     heads = torch.empty((B, n_steps, n_out) if want_heads else (0,), dtype=torch.float32, device=dev)
     used = torch.empty((B, n_steps, width) if want_noise else (0,), dtype=torch.float32, device=dev)
@@ -334,12 +359,68 @@ def decode_impl(packed: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.
                        rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=int(rng_utt0) & 0xFFFFFFFF, reserved=0,
                        rng_utt_ids_dev=_ptr(utt_ids))
     with _on(dev):
-        _lib.check(L.swn_decode(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), _ptr(state), _ptr(out),
-                                _ptr(heads if want_heads else None), variant, _stream(dev)), "decode")
+        if w16 is None:
+            _lib.check(L.swn_decode(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), _ptr(state), _ptr(out),
+                                    _ptr(heads if want_heads else None), variant, _stream(dev)), "decode")
+        else:
+            _lib.check(L.swn_decode_w16(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), None, _ptr(out),
+                                        _ptr(heads if want_heads else None), variant, _ptr(w16), _stream(dev)), "decode_w16")
     return out, heads, used
 
 
 decode = custom_op("swn::decode", mutates_args=())(decode_impl)
+
+
+def pack_decode_w16_impl(packed: torch.Tensor, desc: List[int]) -> torch.Tensor:
+    """the bf16 image of the matrices the symmetric BL6 decode kernel streams (swn_pack_decode_w16): out_skip, out_1 and the
+    softmax out_2, rounded to nearest even and re-tiled; uint8 (swn_decode_w16_bytes)."""
+    L = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(packed, "the packed parameters")
+    n = L.swn_decode_w16_bytes(ctypes.byref(d))
+    if n == 0:
+        raise RuntimeError("bf16 weights exist for the nets the symmetric BL6 decode kernel serves only")
+    w16 = torch.empty(n, dtype=torch.uint8, device=packed.device)
+    with _on(packed.device):
+        _lib.check(L.swn_pack_decode_w16(ctypes.byref(d), _ptr(packed), _ptr(w16), _stream(packed.device)), "pack_decode_w16")
+    return w16
+
+
+pack_decode_w16 = custom_op("swn::pack_decode_w16", mutates_args=())(pack_decode_w16_impl)
+
+
+@pack_decode_w16.register_fake
+def _(packed, desc):
+    return packed.new_empty(_lib.lib().swn_decode_w16_bytes(ctypes.byref(_desc(desc))), dtype=torch.uint8)
+
+
+def decode_w16_impl(packed: torch.Tensor, w16: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor],
+                    forced: Optional[torch.Tensor], seed: Optional[torch.Tensor], desc: List[int], n_steps: int, variant: int,
+                    rng_seed: int, rng_utt0: int, want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode with the streamed head matrices stored as bf16 (swn_decode_w16; w16 = pack_decode_w16(packed, desc)):
+    bit-identical to decode on a model whose out_skip / out_1 / softmax out_2 weights were rounded to bf16.  The variant must
+    resolve to the symmetric BL6 kernel (6 for the single-sample Laplace nets)."""
+    return _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads,
+                        want_noise, utt_ids)
+
+
+decode_w16 = custom_op("swn::decode_w16", mutates_args=())(decode_w16_impl)
+
+
+@decode_w16.register_fake
+def _(packed, w16, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise, utt_ids=None):
+    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
+
+
+def _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise):
+    d = _desc(desc)
+    soft, seg, _, _, n_out, _ = _geom(d)
+    B = cond.shape[0]
+    width = d.n_quantize if soft else seg
+    return (packed.new_empty((B, n_steps * seg), dtype=torch.int32 if soft else torch.float32),
+            packed.new_empty((B, n_steps, n_out) if want_heads else (0,)),
+            packed.new_empty((B, n_steps, width) if want_noise else (0,)))
 
 
 @decode.register_fake
@@ -362,6 +443,13 @@ def decode_chunk_impl(packed: torch.Tensor, cond: torch.Tensor, session: torch.T
     """steps [step0, step0 + n_steps) of a streamed decode (swn_decode_chunk): `session` (swn_decode_session_floats() fp32,
     updated in place) carries the decode state from one chunk to the next; begin=True runs the prologue (step0 0).  cond
     holds the frames final so far (absolute indexing); noise / forced / out / heads / used noise are the chunk's rows."""
+    return _decode_chunk_call(None, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed,
+                              rng_utt0, want_heads, want_noise, utt_ids)
+
+
+def _decode_chunk_call(w16, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0,
+                       want_heads, want_noise, utt_ids):
+    """decode_chunk (w16 None: swn_decode_chunk) and decode_chunk_w16 (the bf16 image: swn_decode_chunk_w16)"""
     L = _lib.lib()
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
@@ -397,15 +485,38 @@ def decode_chunk_impl(packed: torch.Tensor, cond: torch.Tensor, session: torch.T
                        noise_out_dev=_ptr(used if want_noise else None),
                        rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=int(rng_utt0) & 0xFFFFFFFF, reserved=0,
                        rng_utt_ids_dev=_ptr(utt_ids))
+    args = (ctypes.byref(d), _ptr(packed), _ptr(cond), B, Tf, int(step0), int(n_steps), _lib.CHUNK_BEGIN if begin else 0,
+            ctypes.byref(io), _ptr(session), _ptr(out if n_steps > 0 else None), _ptr(heads if want_heads else None),
+            int(variant))
     with _on(dev):
-        _lib.check(L.swn_decode_chunk(ctypes.byref(d), _ptr(packed), _ptr(cond), B, Tf, int(step0), int(n_steps),
-                                      _lib.CHUNK_BEGIN if begin else 0, ctypes.byref(io), _ptr(session),
-                                      _ptr(out if n_steps > 0 else None), _ptr(heads if want_heads else None), int(variant),
-                                      _stream(dev)), "decode_chunk")
+        if w16 is None:
+            _lib.check(L.swn_decode_chunk(*args, _stream(dev)), "decode_chunk")
+        else:
+            _lib.check(L.swn_decode_chunk_w16(*args, _ptr(_check_w16(w16, packed, d)), _stream(dev)), "decode_chunk_w16")
     return out, heads, used
 
 
 decode_chunk = custom_op("swn::decode_chunk", mutates_args=("session",))(decode_chunk_impl)
+
+
+def decode_chunk_w16_impl(packed: torch.Tensor, w16: torch.Tensor, cond: torch.Tensor, session: torch.Tensor,
+                          noise: Optional[torch.Tensor], forced: Optional[torch.Tensor], seed: Optional[torch.Tensor],
+                          desc: List[int], step0: int, n_steps: int, begin: bool, variant: int, rng_seed: int, rng_utt0: int,
+                          want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode_chunk over the bf16 image of the streamed head matrices (swn_decode_chunk_w16): the chunks concatenate to
+    decode_w16 bit for bit; the session is laid out as decode_chunk's."""
+    return _decode_chunk_call(w16, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed,
+                              rng_utt0, want_heads, want_noise, utt_ids)
+
+
+decode_chunk_w16 = custom_op("swn::decode_chunk_w16", mutates_args=("session",))(decode_chunk_w16_impl)
+
+
+@decode_chunk_w16.register_fake
+def _(packed, w16, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0, want_heads,
+      want_noise, utt_ids=None):
+    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
 
 
 @decode_chunk.register_fake
@@ -484,6 +595,37 @@ def _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins,
 
 
 decode_pool_chunk = custom_op("swn::decode_pool_chunk", mutates_args=("session",))(decode_pool_chunk_impl)
+
+
+def decode_pool_chunk_w16_impl(packed: torch.Tensor, w16: torch.Tensor, session: torch.Tensor, conds: List[torch.Tensor],
+                               slots: List[int], step0s: List[int], n_steps: List[int], begins: List[bool],
+                               seeds: Optional[torch.Tensor], utt_ids: List[int], desc: List[int], capacity: int, variant: int,
+                               rng_seed: int, want_heads: bool, want_noise: bool
+                               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode_pool_chunk over the bf16 image of the streamed head matrices (swn_decode_pool_chunk_w16): every entry's rows
+    are bit-identical to decode_chunk_w16 of that session alone."""
+    L = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(packed, "the packed parameters")
+    dev = packed.device
+    _check_w16(w16, packed, d)
+    table, io, out, heads, used, n_max = _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins, seeds,
+                                                           utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
+    with _on(dev):
+        _lib.check(L.swn_decode_pool_chunk_w16(ctypes.byref(d), _ptr(packed), int(capacity), table, len(conds),
+                                               ctypes.byref(io), _ptr(session), _ptr(out if n_max > 0 else None),
+                                               _ptr(heads if want_heads else None), int(variant), _ptr(w16), _stream(dev)),
+                   "decode_pool_chunk_w16")
+    return out, heads, used
+
+
+decode_pool_chunk_w16 = custom_op("swn::decode_pool_chunk_w16", mutates_args=("session",))(decode_pool_chunk_w16_impl)
+
+
+@decode_pool_chunk_w16.register_fake
+def _(packed, w16, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
+      want_heads, want_noise):
+    return _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise)
 
 
 @decode_pool_chunk.register_fake
@@ -1253,6 +1395,7 @@ class LaplaceLossFunction(torch.autograd.Function):
 
 
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
+            "pack_decode_w16", "decode_w16", "decode_chunk_w16", "decode_pool_chunk_w16",
             "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
             "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",

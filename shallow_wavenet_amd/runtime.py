@@ -122,6 +122,60 @@ class train_precision:
         return False
 
 
+DECODE_WEIGHTS = ("fp32", "bf16")
+
+
+def bf16_weight_names(cfg: NetConfig) -> List[str]:
+    """the tensors decode(weights="bf16") stores as bf16: the matrices the symmetric BL6 kernel streams from L2 at every
+    step - out_skip.{l}.weight, out_1.weight and, for softmax nets, out_2.weight (a Laplace net's out_2 is a few rows that
+    stay on chip in fp32).  Biases and everything else stay fp32."""
+    names = [f"out_skip.{l}.weight" for l in range(cfg.L)] + ["out_1.weight"]
+    if cfg.kind == "softmax":
+        names.append("out_2.weight")
+    return names
+
+
+def bf16_weight_state_dict(cfg: NetConfig, state_dict) -> Dict[str, "np.ndarray | torch.Tensor"]:
+    """the state dict whose fp32 decode is what decode(weights="bf16") computes, bit for bit: a copy of `state_dict` with
+    exactly the tensors of bf16_weight_names rounded to bf16 (round to nearest even, as tensor.to(torch.bfloat16)) and
+    widened back to fp32.  Feed it to the fp32 path (same variant) or to the CPU oracle to judge the mode."""
+    out = dict(state_dict)
+    for name in bf16_weight_names(cfg):
+        if name not in out:
+            raise KeyError(f"state_dict is missing {name}")
+        v = out[name]
+        if isinstance(v, torch.Tensor):
+            out[name] = v.detach().to(torch.float32).to(torch.bfloat16).to(torch.float32)
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+            out[name] = t.to(torch.bfloat16).to(torch.float32).numpy()
+    return out
+
+
+def check_decode_weights(weights, cfg: NetConfig, batch: int, variant: int) -> str:
+    """the `weights` keyword of the decode calls: "fp32" | "bf16".  bf16 storage exists on the symmetric BL6 kernel alone, so
+    for "bf16" the (net, batch, variant) must resolve to it: ValueError otherwise, before any device work."""
+    if weights not in DECODE_WEIGHTS:
+        raise ValueError(f"weights must be one of {DECODE_WEIGHTS}, not {weights!r}")
+    if weights == "fp32":
+        return weights
+    L = _lib.lib()
+    desc = _lib.desc_from_cfg(cfg)
+    if L.swn_decode_w16_bytes(ctypes.byref(desc)) == 0:
+        raise ValueError('weights="bf16" runs on the symmetric BL6 decode kernel, which does not serve this net (the '
+                         "stepped chain and the generic kernel have no bf16 form)")
+    resolved = L.swn_decode_resolve_variant(ctypes.byref(desc), int(batch), int(variant))
+    if resolved == 6:
+        return weights
+    if resolved == 2 and cfg.kind == "laplace" and int(cfg.seg) == 1:
+        raise ValueError(f'weights="bf16": variant {variant} resolves to the wave-specialised kernel for this '
+                         "single-sample Laplace net, which has no bf16 form - pass variant=6 (the symmetric kernel)")
+    if resolved != 2:
+        raise ValueError(f'weights="bf16" runs on the symmetric BL6 decode kernel; variant {variant} does not resolve to it '
+                         "for this net - pass variant=6")
+    return weights
+
+
 def layout_offsets(cfg: NetConfig) -> Dict[str, int]:
     """float offsets of the packed sections (swn_layout_offsets)."""
     d = _lib.desc_from_cfg(cfg)
@@ -179,8 +233,13 @@ class HipNet:
     def decode(self, aux: torch.Tensor, n_steps: int, noise: Optional[torch.Tensor] = None,
                forced: Optional[torch.Tensor] = None, want_heads: bool = False, variant: int = 0,
                cond: Optional[torch.Tensor] = None, seed: Optional[torch.Tensor] = None, rng_seed: int = 0,
-               rng_utt0: int = 0, want_noise: bool = False, utt_ids: Optional[Sequence[int]] = None):
+               rng_utt0: int = 0, want_noise: bool = False, utt_ids: Optional[Sequence[int]] = None,
+               weights: str = "fp32"):
         """run prologue + n_steps generation steps for every utterance of the batch.
+
+        weights: "fp32" (default) | "bf16": out_skip, out_1 and the softmax out_2 weights stored and streamed as bf16 (round
+               to nearest even), everything else fp32 - bit-identical to the fp32 decode of bf16_weight_state_dict(...).
+               Symmetric BL6 kernel only: variant 6 for the single-sample Laplace nets, 0 or 6 for the others of the class.
 
         noise: laplace (B, n_steps, seg) | softmax (B, n_steps, Q), fp32, utterance-major - the host-drawn stream of
                the parity mode; None = the kernels draw it themselves (counter-based generator keyed by `rng_seed`,
@@ -190,16 +249,28 @@ class HipNet:
         returns (out, heads): out laplace (B, n_steps*seg) fp32 | softmax (B, n_steps) int32; with want_noise=True
         a third value: the noise the kernels used, in the layout of `noise`.
         """
+        bf16 = check_decode_weights(weights, self.cfg, int(aux.shape[0] if cond is None else cond.shape[0]), variant) == "bf16"
         if cond is None:
             cond = self.frontend(aux)
         ids = None if utt_ids is None else torch.as_tensor(list(utt_ids), dtype=torch.int32)
-        out, heads, used = _O.decode(self.packed, cond, noise, forced, seed, self.dlist, int(n_steps), int(variant),
-                                     int(rng_seed) & 0x7FFFFFFFFFFFFFFF, int(rng_utt0) & 0xFFFFFFFF, bool(want_heads),
-                                     bool(want_noise), ids)
+        args = (cond, noise, forced, seed, self.dlist, int(n_steps), int(variant), int(rng_seed) & 0x7FFFFFFFFFFFFFFF,
+                int(rng_utt0) & 0xFFFFFFFF, bool(want_heads), bool(want_noise), ids)
+        if bf16:
+            out, heads, used = _O.decode_w16(self.packed, self.decode_w16_image(), *args)
+        else:
+            out, heads, used = _O.decode(self.packed, *args)
         heads = heads if want_heads else None
         if want_noise:
             return out, heads, used
         return out, heads
+
+    def decode_w16_image(self) -> torch.Tensor:
+        """the bf16 image of the streamed head matrices (torch.ops.swn.pack_decode_w16), built on first use and rebuilt when
+        the packed parameters moved on (repack)"""
+        if getattr(self, "_w16", None) is None or getattr(self, "_w16_version", -1) != self.packed_version:
+            self._w16 = _O.pack_decode_w16(self.packed, self.dlist)
+            self._w16_version = self.packed_version
+        return self._w16
 
     # ------------------------------------------------------------------ teacher-forced stack
     def forward(self, aux: torch.Tensor, audio: torch.Tensor, want_hidden: bool = False,

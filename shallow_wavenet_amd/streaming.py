@@ -56,6 +56,13 @@ def _check_prologue(prologue, stepped: bool) -> str:
     return prologue
 
 
+def _check_weights(weights, cfg: NetConfig, batch: int, variant: int) -> str:
+    """the `weights` keyword of the streams and pools: runtime.check_decode_weights ("fp32" | "bf16", the latter where
+    (net, batch, variant) resolves to the symmetric BL6 kernel)"""
+    from .runtime import check_decode_weights
+    return check_decode_weights(weights, cfg, batch, variant)
+
+
 def lookahead_frames(cfg: NetConfig) -> int:
     """frames of right context conv_aux needs before a frame's conditioning is final: the half-width of the two-sided
     dilated stack, sum over layers of dilation * (k - 1) / 2 = (k ** layers - 1) / 2 for an odd kernel k."""
@@ -89,6 +96,9 @@ class DecodeStream:
                   restores every chunk on the device (run.sh stage 6)
     prologue      "stepped" (default) | "parallel": on the stepped chain (variant 3), fill the history rings before the first
                   chunk with swn_decode_stepped_prologue - L + 2 launches instead of (rf - seg + 1) x (L + 1), same bits
+    weights       "fp32" (default) | "bf16": the streamed head matrices stored as bf16, as HipNet.decode(weights=...) - the
+                  chunks then concatenate to that one-shot decode; the symmetric BL6 kernel only (variant=6 for the
+                  single-sample Laplace nets), ValueError otherwise
 
     push / finish / advance return what HipNet.decode returns for the new steps: (out, heads) or, with want_noise,
     (out, heads, noise) - out laplace (B, n * seg) fp32 | softmax (B, n) int32 on the device, heads None unless asked for.
@@ -100,10 +110,11 @@ class DecodeStream:
 
     def __init__(self, net, batch: int, *, variant: int = 0, seed: Optional[torch.Tensor] = None, rng_seed: int = 0,
                  rng_utt0: int = 0, utt_ids: Optional[Sequence[int]] = None, want_heads: bool = False,
-                 want_noise: bool = False, post_filter=None, prologue: str = "stepped"):
+                 want_noise: bool = False, post_filter=None, prologue: str = "stepped", weights: str = "fp32"):
         cfg = net.cfg
         if not isinstance(batch, int) or batch < 1:
             raise ValueError(f"batch must be a positive integer, not {batch!r}")
+        self.weights = _check_weights(weights, cfg, batch, variant)
         self.net, self.cfg, self.batch = net, cfg, batch
         self.soft = cfg.kind == "softmax"
         self.seg = 1 if self.soft else int(cfg.seg)
@@ -260,9 +271,12 @@ class DecodeStream:
             _O.decode_stepped_prologue([self.net.packed], [], self._session, [self._cond[b] for b in range(self.batch)],
                                        list(range(self.batch)), self._seed, self.net.dlist, self.batch)
             begin = False                           # the first chunk resumes from the filled session
-        out, heads, used = _O.decode_chunk(self.net.packed, self._cond, self._session, noise, forced, self._seed,
-                                           self.net.dlist, self.steps_done, n, begin, self.variant,
-                                           self.rng_seed, self.rng_utt0, self.want_heads, self.want_noise, self._ids)
+        args = (self._cond, self._session, noise, forced, self._seed, self.net.dlist, self.steps_done, n, begin, self.variant,
+                self.rng_seed, self.rng_utt0, self.want_heads, self.want_noise, self._ids)
+        if self.weights == "bf16":
+            out, heads, used = _O.decode_chunk_w16(self.net.packed, self.net.decode_w16_image(), *args)
+        else:
+            out, heads, used = _O.decode_chunk(self.net.packed, *args)
         self._begun = True
         self.steps_done += n
         heads = heads if self.want_heads else None
@@ -367,7 +381,8 @@ class PoolSession:
         self.slot, self.utt_id, self.model = slot, utt_id, model
         # the conditioning of a batch-1 DecodeStream over the session's model: the pool reads its _cond, steps_ready and
         # steps_done
-        self._stream = DecodeStream(pool._models[model], 1, variant=pool.variant, seed=seed, rng_seed=pool.rng_seed, utt_ids=[utt_id])
+        self._stream = DecodeStream(pool._models[model], 1, variant=pool.variant, seed=seed, rng_seed=pool.rng_seed, utt_ids=[utt_id],
+                                    weights=getattr(pool, "weights", "fp32"))
         self._seed = self._stream._seed
         self.closed = False
         self._pf_slot = pool.post_filter.open() if pool.post_filter is not None else None
@@ -418,6 +433,9 @@ class DecodePool:
     want_heads / want_noise   also return the raw out_2 rows / the noise used
     post_filter   a postfilter.NoiseShapingRestorer: every session holds one of its slots, and each tick ends with one
                post-filter call over the sessions that ran; each result then ends with the restored chunk (1, n * seg) fp32
+    weights    "fp32" (default) | "bf16": the streamed head matrices stored as bf16 (swn_decode_pool_chunk_w16), each session
+               bit-identical to its solo DecodeStream(weights="bf16").  Symmetric BL6 kernel only (variant=6 for the
+               single-sample Laplace nets); a bf16 pool serves one model (add_model raises) and no stepped pool has the mode
 
         k = pool.add_model(other_net)           # another net of the same NetConfig (the pool's own net is model 0)
         s = pool.open(seed=None, utt_id=None, model=0)   # a free slot; utt_id defaults to the admission counter
@@ -428,10 +446,11 @@ class DecodePool:
     """
 
     def __init__(self, net, capacity: int, *, variant: int = 0, rng_seed: int = 0, want_heads: bool = False,
-                 want_noise: bool = False, post_filter=None):
+                 want_noise: bool = False, post_filter=None, weights: str = "fp32"):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
         self.net, self.cfg, self.capacity = net, net.cfg, capacity
+        self.weights = _check_weights(weights, net.cfg, capacity, variant)
         self.soft = self.cfg.kind == "softmax"
         self.seg = 1 if self.soft else int(self.cfg.seg)
         desc = _ops._desc(net.dlist)
@@ -461,6 +480,8 @@ class DecodePool:
         """register another net of the pool's geometry (a voice fine-tuned from the same recipe) -> its model index for
         open(model=...).  A session slot's layout depends on the geometry only, so sessions of all models share the pool's
         slots and launches.  The pool may hold any number of models; the nets' packed buffers are read at call time."""
+        if self.weights != "fp32":
+            raise ValueError('add_model: a weights="bf16" pool serves one model - the multi-model launch has no bf16 form')
         if net.cfg != self.cfg:
             raise ValueError("add_model: the net's NetConfig differs from the pool's - the models of a pool share one geometry")
         if torch.device(net.device) != torch.device(self.net.device):
@@ -515,7 +536,9 @@ class DecodePool:
             args = (self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
                     [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
                     self.net.dlist, self.capacity, self.variant, self.rng_seed, self.want_heads, self.want_noise)
-            if len(models) == 1:
+            if self.weights == "bf16":
+                out, heads, used = _O.decode_pool_chunk_w16(self.net.packed, self.net.decode_w16_image(), *args)
+            elif len(models) == 1:
                 out, heads, used = _O.decode_pool_chunk(self._models[models[0]].packed, *args)
             else:
                 out, heads, used = _O.decode_pool_chunk_models([self._models[m].packed for m in models], of, *args)
@@ -696,9 +719,16 @@ class SteppedDecodePool(DecodePool):
     and max_prologue has nothing left to spread; same bits as the default "stepped"."""
 
     def __init__(self, net, capacity: int, *, rng_seed: int = 0, want_heads: bool = False, want_noise: bool = False,
-                 post_filter=None, prologue: str = "stepped"):
+                 post_filter=None, prologue: str = "stepped", weights: str = "fp32"):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
+        from .runtime import DECODE_WEIGHTS
+        if weights not in DECODE_WEIGHTS:
+            raise ValueError(f"weights must be one of {DECODE_WEIGHTS}, not {weights!r}")
+        if weights != "fp32":
+            raise ValueError('weights="bf16" is not served by the stepped decode pools: the chain is launch-bound, weight bytes '
+                             "are not its limit")
+        self.weights = "fp32"
         self.net, self.cfg, self.capacity = net, net.cfg, capacity
         self.soft = self.cfg.kind == "softmax"
         self.seg = 1 if self.soft else int(self.cfg.seg)
