@@ -350,32 +350,6 @@ __global__ __launch_bounds__(NT) void decode_generic_kernel(const typename Gener
         for (int e = tid; e < WN; e += NT) a.win[(size_t)b * WNR + e] = shist[e];
 }
 
-template <int SEGT>
-int launch_generic_pool(const DecPoolArgs& p, int n_entries, size_t lds, hipStream_t st) {
-    if (p.c.g.kind == SWN_KIND_LAPLACE)
-        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_LAPLACE, true, true>), dim3(n_entries), dim3(NT), lds, st, p);
-    else
-        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX, true, true>), dim3(n_entries), dim3(NT), lds, st, p);
-    return swn_launch_status("swn_decode_pool_chunk(generic)");
-}
-
-template <int SEGT>
-int launch_generic_pool(const DecPoolModelsArgs& p, int n_entries, size_t lds, hipStream_t st) {
-    if (p.c.g.kind == SWN_KIND_LAPLACE)
-        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_LAPLACE, true, true, true>), dim3(n_entries), dim3(NT), lds, st, p);
-    else
-        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX, true, true, true>), dim3(n_entries), dim3(NT), lds, st, p);
-    return swn_launch_status("swn_decode_pool_chunk_models(generic)");
-}
-
-template <int SEGT, bool STREAM = false>
-int launch_generic(const DecArgs& a, size_t lds, hipStream_t st) {
-    if (a.g.kind == SWN_KIND_LAPLACE)
-        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_LAPLACE, STREAM>), dim3(a.B), dim3(NT), lds, st, a);
-    else
-        hipLaunchKernelGGL((decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX, STREAM>), dim3(a.B), dim3(NT), lds, st, a);
-    return swn_launch_status("swn_decode(generic)");
-}
 
 int ring_plan(const SwnGeom& g, int* off, int* len) {
     int o = 0;
@@ -395,18 +369,48 @@ size_t generic_lds(const SwnGeom& g) {
     return lds_floats * sizeof(float);
 }
 
-// the generic kernel over a filled DecArgs (state = the rings, zeroed here unless a streamed chunk resumes)
-int generic_run(DecArgs& a, bool stream, hipStream_t st) {
-    const size_t lds = generic_lds(a.g);
+// one workgroup per utterance / pool entry
+template <int SEGT, bool STREAM, bool POOL, bool MODELS>
+int launch_generic(const typename GenericArgs<POOL, MODELS>::type& a, const SwnDecodeCall& c, size_t lds, const char* where) {
+    const auto kern = c.g.kind == SWN_KIND_LAPLACE ? &decode_generic_kernel<SEGT, SWN_KIND_LAPLACE, STREAM, POOL, MODELS>
+                                                   : &decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX, STREAM, POOL, MODELS>;
+    hipLaunchKernelGGL(kern, dim3(c.batch), dim3(NT), lds, c.hip_stream, a);
+    return swn_launch_status(where);
+}
+
+// the instantiation of a call: one-shot, streamed chunk, pool, pool over several models
+template <int SEGT>
+int launch_generic_call(const DecPoolModelsArgs& p, const SwnDecodeCall& c, size_t lds) {
+    if (c.models) return launch_generic<SEGT, true, true, true>(p, c, lds, "swn_decode_pool_chunk_models(generic)");
+    if (c.pool) return launch_generic<SEGT, true, true, false>(p, c, lds, "swn_decode_pool_chunk(generic)");
+    if (c.stream) return launch_generic<SEGT, true, false, false>(p.c, c, lds, "swn_decode(generic)");
+    return launch_generic<SEGT, false, false, false>(p.c, c, lds, "swn_decode(generic)");
+}
+
+// the generic kernel over a call: `state` holds the rings of c.capacity utterances (zeroed here unless a streamed chunk
+// resumes; a pool's BEGIN entries zero their own slots in the kernel), a stream's sample windows lie behind them
+int generic_run(const SwnDecodeCall& c) {
+    const size_t lds = generic_lds(c.g);
     if (lds > 160 * 1024) return SWN_E_UNSUPPORTED;
-    if (!(stream && a.resume) &&
-        hipMemsetAsync(a.state, 0, sizeof(float) * (size_t)a.state_stride * a.B, st) != hipSuccess)
+    DecPoolModelsArgs p;
+    DecArgs& a = p.c;
+    a.g = c.g;
+    swn_make_layout(&a.g, &a.y);
+    a.packed = c.packed; a.cond = c.cond; a.nz = c.nz; a.forced = c.forced; a.seed = c.seed; a.state = c.state;
+    a.out = c.out; a.heads = c.heads; a.B = c.batch; a.Tf = c.n_frames; a.n_steps = c.n_steps;
+    a.state_stride = ring_plan(a.g, a.ring_off, a.ring_len);
+    a.step0 = c.step0; a.resume = c.resume;
+    a.win = c.stream ? c.state + (size_t)a.state_stride * c.capacity : nullptr;
+    if (c.pool) p.t = *c.pool;
+    if (c.models) p.m = *c.models;
+    if (!c.pool && !c.resume &&
+        hipMemsetAsync(a.state, 0, sizeof(float) * (size_t)a.state_stride * a.B, c.hip_stream) != hipSuccess)
         return SWN_E_LAUNCH;
-    switch (generic_segt(a.g)) {
-        case 1: return stream ? launch_generic<1, true>(a, lds, st) : launch_generic<1>(a, lds, st);
-        case 2: return stream ? launch_generic<2, true>(a, lds, st) : launch_generic<2>(a, lds, st);
-        case 5: return stream ? launch_generic<5, true>(a, lds, st) : launch_generic<5>(a, lds, st);
-        default: return stream ? launch_generic<10, true>(a, lds, st) : launch_generic<10>(a, lds, st);
+    switch (generic_segt(c.g)) {
+        case 1: return launch_generic_call<1>(p, c, lds);
+        case 2: return launch_generic_call<2>(p, c, lds);
+        case 5: return launch_generic_call<5>(p, c, lds);
+        default: return launch_generic_call<10>(p, c, lds);
     }
 }
 
@@ -415,227 +419,27 @@ enum { KSEL_GENERIC = 1, KSEL_BL6W = 2, KSEL_STEPPED = 3, KSEL_BL6 = 6 };
 // the kernel that variant `variant` of swn_decode, swn_decode_chunk and swn_decode_pool_chunk runs for (net, batch): KSEL_*, or a
 // negative SWN_E_*.  0 = the best one that applies, 2 / 6 = the BL6 class only (6: the symmetric kernel, whatever the net - A/B
 // and parity runs), 3 = the stepped chain only, 1 = the generic kernel
-int resolve_kernel(const swn_net_desc* d, int batch, int variant) {
-    SwnGeom g;
-    const int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
+int resolve_kernel(const SwnGeom& g, int batch, int variant) {
     if (batch < 1) return SWN_E_BADARG;
-    if ((variant == 0 || variant == 2) && swn_decode_bl6w_session_floats(d) > 0) return KSEL_BL6W;
+    if ((variant == 0 || variant == 2) && swn_decode_bl6w_session_floats(g) > 0) return KSEL_BL6W;
     if (variant == 0 || variant == 2 || variant == 6) {
-        if (swn_decode_bl6_session_floats(d) > 0) return KSEL_BL6;
+        if (swn_decode_bl6_session_floats(g) > 0) return KSEL_BL6;
         if (variant != 0) return SWN_E_UNSUPPORTED;
     }
     if (variant < 0 || variant > 3) return SWN_E_BADARG;   // (4 and 5, the cohort and cluster experiments of ABI 2, are retired)
     // large geometries (REF6: MBs of weights per step) run one launch per phase over many CUs
     const bool big = (size_t)g.L * 2 * g.H * g.K * g.Hp >= (size_t)256 * 1024;
     if (variant == 3 || (variant == 0 && big)) {
-        if (swn_decode_stepped_supported(d, batch)) return KSEL_STEPPED;
+        if (swn_decode_stepped_supported(g, batch)) return KSEL_STEPPED;
         if (variant == 3) return SWN_E_UNSUPPORTED;
     }
     if (generic_lds(g) > 160 * 1024) return SWN_E_UNSUPPORTED;
     return KSEL_GENERIC;
 }
 
-}  // namespace
-
-extern "C" size_t swn_decode_state_floats(const swn_net_desc* d, int batch) {
-    SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1) return 0;
-    int off[SWN_MAXL], len[SWN_MAXL];
-    size_t a = (size_t)ring_plan(g, off, len) * batch;
-    const size_t b = swn_decode_stepped_state_floats(d, batch);
-    return a > b ? a : b;                                  // large enough for every kernel variant
-}
-
-extern "C" int swn_decode(const swn_net_desc* d, const float* packed, const float* cond, int batch,
-                          int n_frames, int n_steps, const swn_decode_io* io,
-                          float* state, void* out, float* heads, int variant, void* stream_) {
-    DecArgs a;
-    int rc = swn_make_geom(d, &a.g);
-    if (rc < 0) return rc;
-    if (batch < 1 || n_frames < 1 || n_steps < 0 || !io) return SWN_E_BADARG;
-    if (n_steps == 0) return SWN_OK;                       // nothing to generate (empty buffers may be null)
-    if (!packed || !cond || !out) return SWN_E_BADARG;
-    if ((long)n_steps * a.g.seg > (long)n_frames * a.g.U) return SWN_E_BADARG;   // conditioning too short
-    const SwnNoise nz = swn_noise_of(io);
-    const void* forced = io->forced_dev;
-    const void* seed = io->seed_dev;
-    hipStream_t st = (hipStream_t)stream_;
-    (void)hipGetLastError();   // drop stale errors of earlier runtime calls
-    const int k = resolve_kernel(d, batch, variant);
-    if (k == KSEL_BL6W) return swn_decode_bl6w_try(d, packed, cond, batch, n_frames, n_steps, &nz, forced, seed, out, heads, stream_);
-    if (k == KSEL_BL6) return swn_decode_bl6_try(d, packed, cond, batch, n_frames, n_steps, &nz, forced, seed, out, heads, stream_);
-    // the BL6 kernels keep their state on chip; every other kernel, and every refusal but that of a variant that asks for the
-    // BL6 class alone, wants the caller's state buffer first
-    if (!state && variant != 2 && variant != 6) return SWN_E_BADARG;
-    if (k < 0) return k;
-    if (k == KSEL_STEPPED)
-        return swn_decode_stepped(d, packed, cond, batch, n_frames, n_steps, &nz, forced, seed, state, out, heads, stream_);
-    swn_make_layout(&a.g, &a.y);
-    a.packed = packed; a.cond = cond; a.nz = nz; a.forced = forced; a.seed = seed; a.state = state;
-    a.out = out; a.heads = heads; a.B = batch; a.Tf = n_frames; a.n_steps = n_steps;
-    a.state_stride = ring_plan(a.g, a.ring_off, a.ring_len);
-    a.step0 = 0; a.resume = 0; a.win = nullptr;
-    return generic_run(a, false, st);
-}
-
-// ---- streamed decode ---------------------------------------------------------------------------------------------
-extern "C" int swn_decode_resolve_variant(const swn_net_desc* d, int batch, int variant) {
-    const int k = resolve_kernel(d, batch, variant);
-    if (k < 0) return k;
-    if (k == KSEL_BL6W) return 2;
-    if (k == KSEL_BL6) return variant == 6 ? 6 : 2;
-    return k;
-}
-
-extern "C" size_t swn_decode_session_floats(const swn_net_desc* d, int batch, int variant) {
-    const int k = resolve_kernel(d, batch, variant);
-    if (k < 0) return 0;
-    if (k == KSEL_BL6W) return swn_decode_bl6w_session_floats(d) * (size_t)batch;
-    if (k == KSEL_BL6) return swn_decode_bl6_session_floats(d) * (size_t)batch;
-    if (k == KSEL_STEPPED) return swn_decode_stepped_state_floats(d, batch);
-    SwnGeom g; swn_make_geom(d, &g);
-    int off[SWN_MAXL], len[SWN_MAXL];
-    return ((size_t)ring_plan(g, off, len) + swn_round4(generic_wn(g))) * (size_t)batch;   // rings, then the sample windows
-}
-
-extern "C" int swn_decode_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                int step0, int n_steps, int flags, const swn_decode_io* io, float* session,
-                                void* out, float* heads, int variant, void* stream_) {
-    SwnGeom g;
-    int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    if (!io || !session || !packed || !cond) return SWN_E_BADARG;
-    if (batch < 1 || n_frames < 1 || step0 < 0 || n_steps < 0 || (flags & ~SWN_CHUNK_BEGIN)) return SWN_E_BADARG;
-    const bool begin = (flags & SWN_CHUNK_BEGIN) != 0;
-    if (begin && step0 != 0) return SWN_E_BADARG;
-    if (n_steps > 0 && !out) return SWN_E_BADARG;
-    if (((long long)step0 + n_steps) * g.seg > (long long)n_frames * g.U) return SWN_E_BADARG;   // conditioning not final yet
-    const int k = resolve_kernel(d, batch, variant);
-    if (k < 0) return SWN_E_BADARG;
-    if (n_steps == 0 && !begin) return SWN_OK;             // nothing to generate, the session stays as it is
-    const SwnNoise nz = swn_noise_of(io);
-    const int resume = begin ? 0 : 1;
-    (void)hipGetLastError();
-    if (k == KSEL_BL6W)
-        return swn_decode_bl6w_chunk(d, packed, cond, batch, n_frames, step0, n_steps, resume, &nz, io->forced_dev, io->seed_dev,
-                                     session, out, heads, stream_);
-    if (k == KSEL_BL6)
-        return swn_decode_bl6_chunk(d, packed, cond, batch, n_frames, step0, n_steps, resume, &nz, io->forced_dev, io->seed_dev,
-                                    session, out, heads, stream_);
-    if (k == KSEL_STEPPED)
-        return swn_decode_stepped_chunk(d, packed, cond, batch, n_frames, step0, n_steps, resume, &nz, io->forced_dev,
-                                        io->seed_dev, session, out, heads, stream_);
-    DecArgs a;
-    a.g = g;
-    swn_make_layout(&a.g, &a.y);
-    a.packed = packed; a.cond = cond; a.nz = nz; a.forced = io->forced_dev; a.seed = io->seed_dev; a.state = session;
-    a.out = out; a.heads = heads; a.B = batch; a.Tf = n_frames; a.n_steps = n_steps;
-    a.state_stride = ring_plan(a.g, a.ring_off, a.ring_len);
-    a.step0 = step0; a.resume = resume; a.win = session + (size_t)a.state_stride * batch;
-    return generic_run(a, true, (hipStream_t)stream_);
-}
-
-// ---- decode pool ---------------------------------------------------------------------------------------------------
-namespace {
-
-int swn_make_geom_rc(const swn_net_desc* d) { SwnGeom g; return swn_make_geom(d, &g); }
-
-template <class PA>
-int launch_generic_pool_segt(const SwnGeom& g, const PA& p, int n_entries, hipStream_t st) {
-    const size_t lds = generic_lds(g);
-    switch (generic_segt(g)) {
-        case 1: return launch_generic_pool<1>(p, n_entries, lds, st);
-        case 2: return launch_generic_pool<2>(p, n_entries, lds, st);
-        case 5: return launch_generic_pool<5>(p, n_entries, lds, st);
-        default: return launch_generic_pool<10>(p, n_entries, lds, st);
-    }
-}
-
-// swn_decode_pool_chunk (models == nullptr: every entry runs `packed`) and swn_decode_pool_chunk_models (the checked table:
-// entry e runs models->p[models->of[e]], `packed` is not read)
-int pool_chunk(const swn_net_desc* d, const float* packed, const SwnPoolModels* models, int capacity,
-               const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
-               float* session, void* out, float* heads, int variant, void* stream_) {
-    SwnGeom g;
-    int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    if ((!packed && !models) || !entries || !io || !session) return SWN_E_BADARG;
-    if (capacity < 1 || n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
-    if (io->noise_dev || io->forced_dev) return SWN_E_BADARG;    // pools draw their noise on the device, no teacher forcing
-    SwnPoolTable t = {};
-    int n_max = 0;
-    bool work = false;
-    for (int e = 0; e < n_entries; ++e) {
-        const swn_decode_pool_entry& en = entries[e];
-        const bool begin = (en.flags & SWN_CHUNK_BEGIN) != 0;
-        if (!en.cond_dev || en.n_frames < 1 || en.slot < 0 || en.slot >= capacity || en.step0 < 0 || en.n_steps < 0 ||
-            (en.flags & ~SWN_CHUNK_BEGIN) || en.reserved != 0)
-            return SWN_E_BADARG;
-        if (begin && en.step0 != 0) return SWN_E_BADARG;
-        if (((long long)en.step0 + en.n_steps) * g.seg > (long long)en.n_frames * g.U) return SWN_E_BADARG;
-        for (int f = 0; f < e; ++f)
-            if (entries[f].slot == en.slot) return SWN_E_BADARG;   // two workgroups on one session
-        t.e[e] = en;
-        n_max = en.n_steps > n_max ? en.n_steps : n_max;
-        work = work || begin || en.n_steps > 0;
-    }
-    if (n_max > 0 && !out) return SWN_E_BADARG;
-    const int k = resolve_kernel(d, capacity, variant);
-    if (k == KSEL_STEPPED || variant == 3) return SWN_E_UNSUPPORTED;   // one launch per phase for all utterances at one step
-    if (k < 0) return SWN_E_BADARG;
-    if (!work) return SWN_OK;                              // every slot stays as it is
-    const SwnNoise nz = swn_pool_noise_of(io);
-    (void)hipGetLastError();
-    if (k == KSEL_BL6W)
-        return swn_decode_bl6w_pool(d, packed, &t, models, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
-    if (k == KSEL_BL6)
-        return swn_decode_bl6_pool(d, packed, &t, models, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
-    DecPoolModelsArgs p;
-    DecArgs& a = p.c;
-    a.g = g;
-    swn_make_layout(&a.g, &a.y);
-    a.packed = packed; a.cond = nullptr; a.nz = nz; a.forced = nullptr; a.seed = io->seed_dev; a.state = session;
-    a.out = out; a.heads = heads; a.B = n_entries; a.Tf = 0; a.n_steps = n_max;
-    a.state_stride = ring_plan(a.g, a.ring_off, a.ring_len);
-    a.step0 = 0; a.resume = 0; a.win = session + (size_t)a.state_stride * capacity;
-    p.t = t;
-    hipStream_t st = (hipStream_t)stream_;
-    if (!models) return launch_generic_pool_segt<DecPoolArgs>(g, p, n_entries, st);
-    p.m = *models;
-    return launch_generic_pool_segt(g, p, n_entries, st);
-}
-
-}  // namespace
-
-extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed, int capacity,
-                                     const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
-                                     float* session, void* out, float* heads, int variant, void* stream_) {
-    const int rc = swn_make_geom_rc(d);
-    if (rc < 0) return rc;
-    if (!packed) return SWN_E_BADARG;
-    return pool_chunk(d, packed, nullptr, capacity, entries, n_entries, io, session, out, heads, variant, stream_);
-}
-
-extern "C" int swn_decode_pool_chunk_models(const swn_net_desc* d, const float* const* models, int n_models,
-                                            const int32_t* model_of_entry, int capacity,
-                                            const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
-                                            float* session, void* out, float* heads, int variant, void* stream_) {
-    const int rc = swn_make_geom_rc(d);
-    if (rc < 0) return rc;
-    if (n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
-    if (swn_pool_models_check(models, n_models, model_of_entry, n_entries) < 0) return SWN_E_BADARG;
-    SwnPoolModels m = {};
-    for (int i = 0; i < SWN_POOL_MAX_MODELS; ++i) m.p[i] = models[i < n_models ? i : 0];
-    for (int e = 0; e < n_entries; ++e) m.of[e] = (unsigned char)model_of_entry[e];
-    return pool_chunk(d, nullptr, &m, capacity, entries, n_entries, io, session, out, heads, variant, stream_);
-}
-
-// ---- bf16 storage of the streamed head matrices ---------------------------------------------------------------------
-namespace {
-
 // the *_w16 calls run on the symmetric BL6 kernel alone: SWN_OK when `variant` resolves to it for (net, batch)
-int w16_kernel_check(const swn_net_desc* d, int batch, int variant, const char* where) {
-    const int k = resolve_kernel(d, batch, variant);
+int w16_kernel_check(const SwnGeom& g, int batch, int variant, const char* where) {
+    const int k = resolve_kernel(g, batch, variant);
     if (k == KSEL_BL6) return SWN_OK;
     if (k == KSEL_BL6W)
         swn_set_error_detail(where, "bf16 weights run on the symmetric BL6 kernel; this net resolves to the wave-specialised "
@@ -646,61 +450,76 @@ int w16_kernel_check(const swn_net_desc* d, int batch, int variant, const char* 
     return SWN_E_UNSUPPORTED;
 }
 
-}  // namespace
-
-extern "C" int swn_decode_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                              int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, int variant,
-                              const void* w16, void* stream_) {
-    (void)state;                                           // the kernel keeps its state on chip
-    SwnGeom g;
-    int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    if (batch < 1 || n_frames < 1 || n_steps < 0 || !io || !w16) return SWN_E_BADARG;
-    if (n_steps > 0 && (!packed || !cond || !out)) return SWN_E_BADARG;
-    if ((long)n_steps * g.seg > (long)n_frames * g.U) return SWN_E_BADARG;   // conditioning too short
-    rc = w16_kernel_check(d, batch, variant, "swn_decode_w16");
-    if (rc < 0) return rc;
-    if (n_steps == 0) return SWN_OK;
-    const SwnNoise nz = swn_noise_of(io);
-    (void)hipGetLastError();
-    return swn_decode_bl6_w16_try(d, packed, w16, cond, batch, n_frames, n_steps, &nz, io->forced_dev, io->seed_dev, out, heads,
-                                  stream_);
+// the kernel of a pool launch over one or several fp32 models: the stepped chain runs one launch per phase for all
+// utterances at one step, so it is not served here (swn_decode_pool_stepped_chunk is)
+int pool_kernel(const SwnGeom& g, int capacity, int variant) {
+    const int k = resolve_kernel(g, capacity, variant);
+    if (k == KSEL_STEPPED || variant == 3) return SWN_E_UNSUPPORTED;
+    return k < 0 ? SWN_E_BADARG : k;
 }
 
-extern "C" int swn_decode_chunk_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                    int step0, int n_steps, int flags, const swn_decode_io* io, float* session, void* out,
-                                    float* heads, int variant, const void* w16, void* stream_) {
-    SwnGeom g;
-    int rc = swn_make_geom(d, &g);
+// hands a checked call to kernel `k` (KSEL_*)
+int run_call(int k, const SwnDecodeCall& c) {
+    (void)hipGetLastError();   // drop stale errors of earlier runtime calls; only this call's launches are reported
+    if (k == KSEL_BL6W) return swn_decode_bl6w_run(c);
+    if (k == KSEL_BL6) return swn_decode_bl6_run(c);
+    if (k == KSEL_STEPPED) return swn_decode_stepped_run(c);
+    return generic_run(c);
+}
+
+// ---- the argument rules of the entry points (include/swn_hip.h) up to the variant: each makes the geometry, refuses what no
+// kernel takes and fills the record with what the caller passed.  The arguments keep the order of the C ABI.  What the fp32
+// and the *_w16 calls ask on top of these (the image, the kernel a variant resolves to) is in the entry points.
+
+// swn_decode, swn_decode_w16 (empty buffers may be null when there is nothing to generate)
+int oneshot_check(SwnDecodeCall& c, const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                  int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, void* stream_) {
+    const int rc = swn_make_geom(d, &c.g);
     if (rc < 0) return rc;
-    if (!io || !session || !packed || !cond || !w16) return SWN_E_BADARG;
+    if (batch < 1 || n_frames < 1 || n_steps < 0 || !io) return SWN_E_BADARG;
+    if (n_steps > 0 && (!packed || !cond || !out)) return SWN_E_BADARG;
+    if ((long)n_steps * c.g.seg > (long)n_frames * c.g.U) return SWN_E_BADARG;   // conditioning too short
+    c.packed = packed; c.cond = cond; c.batch = c.capacity = batch; c.n_frames = n_frames; c.n_steps = n_steps;
+    c.nz = swn_noise_of(io); c.forced = io->forced_dev; c.seed = io->seed_dev;
+    c.state = state; c.out = out; c.heads = heads; c.hip_stream = (hipStream_t)stream_;
+    return SWN_OK;
+}
+
+// swn_decode_chunk, swn_decode_chunk_w16
+int chunk_check(SwnDecodeCall& c, const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                int step0, int n_steps, int flags, const swn_decode_io* io, float* session, void* out, float* heads,
+                void* stream_) {
+    const int rc = swn_make_geom(d, &c.g);
+    if (rc < 0) return rc;
+    if (!io || !session || !packed || !cond) return SWN_E_BADARG;
     if (batch < 1 || n_frames < 1 || step0 < 0 || n_steps < 0 || (flags & ~SWN_CHUNK_BEGIN)) return SWN_E_BADARG;
     const bool begin = (flags & SWN_CHUNK_BEGIN) != 0;
     if (begin && step0 != 0) return SWN_E_BADARG;
     if (n_steps > 0 && !out) return SWN_E_BADARG;
-    if (((long long)step0 + n_steps) * g.seg > (long long)n_frames * g.U) return SWN_E_BADARG;   // conditioning not final yet
-    rc = w16_kernel_check(d, batch, variant, "swn_decode_chunk_w16");
-    if (rc < 0) return rc;
-    if (n_steps == 0 && !begin) return SWN_OK;
-    const SwnNoise nz = swn_noise_of(io);
-    (void)hipGetLastError();
-    return swn_decode_bl6_w16_chunk(d, packed, w16, cond, batch, n_frames, step0, n_steps, begin ? 0 : 1, &nz, io->forced_dev,
-                                    io->seed_dev, session, out, heads, stream_);
+    if (((long long)step0 + n_steps) * c.g.seg > (long long)n_frames * c.g.U) return SWN_E_BADARG;   // conditioning not final yet
+    c.packed = packed; c.cond = cond; c.batch = c.capacity = batch; c.n_frames = n_frames; c.step0 = step0; c.n_steps = n_steps;
+    c.stream = true; c.resume = !begin;
+    c.nz = swn_noise_of(io); c.forced = io->forced_dev; c.seed = io->seed_dev;
+    c.state = session; c.out = out; c.heads = heads; c.hip_stream = (hipStream_t)stream_;
+    return SWN_OK;
 }
+// nothing to generate and no prologue to run: the session stays as it is
+bool chunk_is_idle(const SwnDecodeCall& c) { return c.n_steps == 0 && c.resume; }
 
-extern "C" int swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* packed, int capacity,
-                                         const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
-                                         float* session, void* out, float* heads, int variant, const void* w16,
-                                         void* stream_) {
-    SwnGeom g;
-    int rc = swn_make_geom(d, &g);
+// swn_decode_pool_chunk, swn_decode_pool_chunk_models, swn_decode_pool_chunk_w16: the record of a streamed chunk over the
+// entries (n_steps = the most steps of an entry), the checked table in `t`; work = an entry has steps to run or begins
+int pool_check(SwnDecodeCall& c, SwnPoolTable& t, bool& work, const swn_net_desc* d, int capacity,
+               const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io, float* session, void* out,
+               float* heads, void* stream_) {
+    const int rc = swn_make_geom(d, &c.g);
     if (rc < 0) return rc;
-    if (!packed || !entries || !io || !session || !w16) return SWN_E_BADARG;
+    const SwnGeom& g = c.g;
+    if (!entries || !io || !session) return SWN_E_BADARG;
     if (capacity < 1 || n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
     if (io->noise_dev || io->forced_dev) return SWN_E_BADARG;    // pools draw their noise on the device, no teacher forcing
-    SwnPoolTable t = {};
+    t = {};
     int n_max = 0;
-    bool work = false;
+    work = false;
     for (int e = 0; e < n_entries; ++e) {
         const swn_decode_pool_entry& en = entries[e];
         const bool begin = (en.flags & SWN_CHUNK_BEGIN) != 0;
@@ -716,10 +535,155 @@ extern "C" int swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* pac
         work = work || begin || en.n_steps > 0;
     }
     if (n_max > 0 && !out) return SWN_E_BADARG;
-    rc = w16_kernel_check(d, capacity, variant, "swn_decode_pool_chunk_w16");
+    c.pool = &t; c.batch = n_entries; c.capacity = capacity; c.n_steps = n_max; c.stream = true;
+    c.nz = swn_pool_noise_of(io); c.seed = io->seed_dev;
+    c.state = session; c.out = out; c.heads = heads; c.hip_stream = (hipStream_t)stream_;
+    return SWN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t swn_decode_state_floats(const swn_net_desc* d, int batch) {
+    SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1) return 0;
+    int off[SWN_MAXL], len[SWN_MAXL];
+    size_t a = (size_t)ring_plan(g, off, len) * batch;
+    const size_t b = swn_decode_stepped_state_floats(g, batch);
+    return a > b ? a : b;                                  // large enough for every kernel variant
+}
+
+extern "C" int swn_decode(const swn_net_desc* d, const float* packed, const float* cond, int batch,
+                          int n_frames, int n_steps, const swn_decode_io* io,
+                          float* state, void* out, float* heads, int variant, void* stream_) {
+    SwnDecodeCall c;
+    const int rc = oneshot_check(c, d, packed, cond, batch, n_frames, n_steps, io, state, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (n_steps == 0) return SWN_OK;                       // nothing to generate, whatever the variant
+    const int k = resolve_kernel(c.g, batch, variant);
+    // the BL6 kernels keep their state on chip; every other kernel, and every refusal but that of a variant that asks for the
+    // BL6 class alone, wants the caller's state buffer first
+    if (k != KSEL_BL6W && k != KSEL_BL6) {
+        if (!state && variant != 2 && variant != 6) return SWN_E_BADARG;
+        if (k < 0) return k;
+    }
+    return run_call(k, c);
+}
+
+// ---- streamed decode ---------------------------------------------------------------------------------------------
+extern "C" int swn_decode_resolve_variant(const swn_net_desc* d, int batch, int variant) {
+    SwnGeom g;
+    const int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    const int k = resolve_kernel(g, batch, variant);
+    if (k < 0) return k;
+    if (k == KSEL_BL6W) return 2;
+    if (k == KSEL_BL6) return variant == 6 ? 6 : 2;
+    return k;
+}
+
+extern "C" size_t swn_decode_session_floats(const swn_net_desc* d, int batch, int variant) {
+    SwnGeom g;
+    if (swn_make_geom(d, &g) < 0) return 0;
+    const int k = resolve_kernel(g, batch, variant);
+    if (k < 0) return 0;
+    if (k == KSEL_BL6W) return swn_decode_bl6w_session_floats(g) * (size_t)batch;
+    if (k == KSEL_BL6) return swn_decode_bl6_session_floats(g) * (size_t)batch;
+    if (k == KSEL_STEPPED) return swn_decode_stepped_state_floats(g, batch);
+    int off[SWN_MAXL], len[SWN_MAXL];
+    return ((size_t)ring_plan(g, off, len) + swn_round4(generic_wn(g))) * (size_t)batch;   // rings, then the sample windows
+}
+
+extern "C" int swn_decode_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                int step0, int n_steps, int flags, const swn_decode_io* io, float* session,
+                                void* out, float* heads, int variant, void* stream_) {
+    SwnDecodeCall c;
+    const int rc = chunk_check(c, d, packed, cond, batch, n_frames, step0, n_steps, flags, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    const int k = resolve_kernel(c.g, batch, variant);
+    if (k < 0) return SWN_E_BADARG;
+    if (chunk_is_idle(c)) return SWN_OK;
+    return run_call(k, c);
+}
+
+// ---- decode pool ---------------------------------------------------------------------------------------------------
+extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed, int capacity,
+                                     const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                     float* session, void* out, float* heads, int variant, void* stream_) {
+    SwnDecodeCall c;
+    SwnPoolTable t;
+    bool work;
+    const int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (!packed) return SWN_E_BADARG;
+    const int k = pool_kernel(c.g, capacity, variant);
+    if (k < 0) return k;
+    if (!work) return SWN_OK;                              // every slot stays as it is
+    c.packed = packed;
+    return run_call(k, c);
+}
+
+// entry e runs models[model_of_entry[e]]
+extern "C" int swn_decode_pool_chunk_models(const swn_net_desc* d, const float* const* models, int n_models,
+                                            const int32_t* model_of_entry, int capacity,
+                                            const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                            float* session, void* out, float* heads, int variant, void* stream_) {
+    SwnDecodeCall c;
+    SwnPoolTable t;
+    bool work;
+    const int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (swn_pool_models_check(models, n_models, model_of_entry, n_entries) < 0) return SWN_E_BADARG;
+    const int k = pool_kernel(c.g, capacity, variant);
+    if (k < 0) return k;
+    if (!work) return SWN_OK;                              // every slot stays as it is
+    SwnPoolModels m = {};
+    for (int i = 0; i < SWN_POOL_MAX_MODELS; ++i) m.p[i] = models[i < n_models ? i : 0];
+    for (int e = 0; e < n_entries; ++e) m.of[e] = (unsigned char)model_of_entry[e];
+    c.models = &m;
+    return run_call(k, c);
+}
+
+// ---- bf16 storage of the streamed head matrices: the same rules, an image, and the symmetric BL6 kernel alone -----------
+extern "C" int swn_decode_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                              int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, int variant,
+                              const void* w16, void* stream_) {
+    SwnDecodeCall c;
+    int rc = oneshot_check(c, d, packed, cond, batch, n_frames, n_steps, io, state, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (!w16) return SWN_E_BADARG;
+    rc = w16_kernel_check(c.g, batch, variant, "swn_decode_w16");
+    if (rc < 0) return rc;
+    if (n_steps == 0) return SWN_OK;
+    c.w16 = w16;
+    return run_call(KSEL_BL6, c);
+}
+
+extern "C" int swn_decode_chunk_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                    int step0, int n_steps, int flags, const swn_decode_io* io, float* session, void* out,
+                                    float* heads, int variant, const void* w16, void* stream_) {
+    SwnDecodeCall c;
+    int rc = chunk_check(c, d, packed, cond, batch, n_frames, step0, n_steps, flags, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (!w16) return SWN_E_BADARG;
+    rc = w16_kernel_check(c.g, batch, variant, "swn_decode_chunk_w16");
+    if (rc < 0) return rc;
+    if (chunk_is_idle(c)) return SWN_OK;
+    c.w16 = w16;
+    return run_call(KSEL_BL6, c);
+}
+
+extern "C" int swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* packed, int capacity,
+                                         const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                         float* session, void* out, float* heads, int variant, const void* w16,
+                                         void* stream_) {
+    SwnDecodeCall c;
+    SwnPoolTable t;
+    bool work;
+    int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (!packed || !w16) return SWN_E_BADARG;
+    rc = w16_kernel_check(c.g, capacity, variant, "swn_decode_pool_chunk_w16");
     if (rc < 0) return rc;
     if (!work) return SWN_OK;                              // every slot stays as it is
-    const SwnNoise nz = swn_pool_noise_of(io);
-    (void)hipGetLastError();
-    return swn_decode_bl6_w16_pool(d, packed, w16, &t, n_entries, n_max, &nz, io->seed_dev, session, out, heads, stream_);
+    c.packed = packed; c.w16 = w16;
+    return run_call(KSEL_BL6, c);
 }

@@ -842,12 +842,6 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
 #endif
 }
 
-template <class T, bool STREAM = false>
-int launch_mode(const Bl6Args& a, hipStream_t st) {
-    static_assert(T::lds_bytes <= 160 * 1024, "LDS budget");
-    return launch_kernel(decode_bl6_kernel<T, STREAM>, T::lds_bytes, a.B, a, st, "swn_decode(bl6)");
-}
-
 // the instantiation a geometry runs: f(Tr<...>{}) for a BL6-class net, SWN_E_UNSUPPORTED otherwise
 template <class F>
 int with_tr(const SwnGeom& g, F&& f) {
@@ -886,9 +880,37 @@ __global__ __launch_bounds__(256) void pack_w16_kernel(const W16PackArgs a) {
     }
 }
 
-template <class T, bool STREAM = false>
-int launch_w16(const Bl6W16Args& a, hipStream_t st) {
-    return launch_kernel(decode_bl6_kernel<T, STREAM, false, false, true>, T::lds_bytes, a.B, a, st, "swn_decode_w16(bl6)");
+// the one-shot decode and the streamed chunk, one workgroup per utterance; `sess` holds sess_floats per utterance.  The
+// classic instantiation takes what it was written for (host-drawn noise, no dump, zero seed, fp32 weights); everything else
+// is the extended one's.
+template <bool W16>
+int launch_utts(const SwnDecodeCall& c, const char* where) {
+    typename B6ArgsOf<false, false, W16>::type a;
+    fill_args(a, c);
+    if constexpr (W16) a.w16 = c.w16;
+    return with_tr(c.g, [&](auto t) {
+        using T = decltype(t);
+        using X = typename T::Ext;
+        static_assert(T::lds_bytes <= 160 * 1024 && X::lds_bytes <= 160 * 1024, "LDS budget");
+        if (c.stream) return launch_kernel(decode_bl6_kernel<X, true, false, false, W16>, X::lds_bytes, a.B, a, c.hip_stream, where);
+        if constexpr (!W16)
+            if (!wants_ext(a)) return launch_kernel(decode_bl6_kernel<T>, T::lds_bytes, a.B, a, c.hip_stream, where);
+        return launch_kernel(decode_bl6_kernel<X, false, false, false, W16>, X::lds_bytes, a.B, a, c.hip_stream, where);
+    });
+}
+
+// one pool launch over the checked entry table: one workgroup per entry, sessions [capacity][sess_floats]
+template <bool MODELS, bool W16>
+int launch_pool(const SwnDecodeCall& c, const char* where) {
+    typename B6ArgsOf<true, MODELS, W16>::type p;
+    fill_args(p.c, c);
+    p.t = *c.pool;
+    if constexpr (MODELS) p.m = *c.models;
+    if constexpr (W16) p.w16 = c.w16;
+    return with_tr(c.g, [&](auto tr) {
+        using T = typename decltype(tr)::Ext;
+        return launch_kernel(decode_bl6_kernel<T, true, true, MODELS, W16>, T::lds_bytes, c.batch, p, c.hip_stream, where);
+    });
 }
 
 }  // namespace
@@ -931,109 +953,17 @@ extern "C" int swn_pack_decode_w16(const swn_net_desc* d, const float* packed, v
     return swn_launch_status("swn_pack_decode_w16");
 }
 
-extern "C" int swn_decode_bl6_w16_pool(const swn_net_desc* d, const float* packed, const void* w16, const SwnPoolTable* t,
-                                       int n_entries, int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out,
-                                       float* heads, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    Bl6PoolW16Args p;
-    fill_args(p.c, g, packed, nullptr, nz, nullptr, seed, out, heads, n_entries, 0, n_max, 0, 0, sess);
-    p.t = *t;
-    p.w16 = w16;
-    hipStream_t st = (hipStream_t)stream_;
-    return with_tr(g, [&](auto tr) {
-        using T = typename decltype(tr)::Ext;
-        return launch_kernel(decode_bl6_kernel<T, true, true, false, true>, T::lds_bytes, n_entries, p, st,
-                             "swn_decode_pool_chunk_w16(bl6)");
-    });
-}
-
-extern "C" int swn_decode_bl6_w16_chunk(const swn_net_desc* d, const float* packed, const void* w16, const float* cond, int batch,
-                                        int n_frames, int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
-                                        const void* seed, float* sess, void* out, float* heads, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    Bl6W16Args a;
-    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, step0, resume, sess);
-    a.w16 = w16;
-    hipStream_t st = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    return with_tr(g, [&](auto t) { return launch_w16<typename decltype(t)::Ext, true>(a, st); });
-}
-
-// the one-shot decode: always the extended instantiation (it also takes the host-drawn stream)
-extern "C" int swn_decode_bl6_w16_try(const swn_net_desc* d, const float* packed, const void* w16, const float* cond, int batch,
-                                      int n_frames, int n_steps, const SwnNoise* nz, const void* forced, const void* seed,
-                                      void* out, float* heads, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    Bl6W16Args a;
-    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, 0, 0, nullptr);
-    a.w16 = w16;
-    hipStream_t st = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    return with_tr(g, [&](auto t) { return launch_w16<typename decltype(t)::Ext>(a, st); });
-}
-
-// one pool launch (swn_decode_pool_chunk checked the entries): one workgroup per entry, sessions [capacity][sess_floats]
-extern "C" int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t,
-                                   const SwnPoolModels* models, int n_entries, int n_max, const SwnNoise* nz, const void* seed,
-                                   float* sess, void* out, float* heads, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    Bl6PoolModelsArgs p;
-    fill_args(p.c, g, packed, nullptr, nz, nullptr, seed, out, heads, n_entries, 0, n_max, 0, 0, sess);
-    p.t = *t;
-    hipStream_t st = (hipStream_t)stream_;
-    if (models) {
-        p.m = *models;
-        return with_tr(g, [&](auto tr) {
-            using T = typename decltype(tr)::Ext;
-            return launch_kernel(decode_bl6_kernel<T, true, true, true>, T::lds_bytes, n_entries, p, st,
-                                 "swn_decode_pool_chunk_models(bl6)");
-        });
-    }
-    const Bl6PoolArgs& p1 = p;
-    return with_tr(g, [&](auto tr) {
-        using T = typename decltype(tr)::Ext;
-        return launch_kernel(decode_bl6_kernel<T, true, true>, T::lds_bytes, n_entries, p1, st, "swn_decode_pool_chunk(bl6)");
-    });
+// a checked call on the symmetric kernel (swn_decode.hip)
+int swn_decode_bl6_run(const SwnDecodeCall& c) {
+    if (c.pool && c.w16) return launch_pool<false, true>(c, "swn_decode_pool_chunk_w16(bl6)");
+    if (c.pool && c.models) return launch_pool<true, false>(c, "swn_decode_pool_chunk_models(bl6)");
+    if (c.pool) return launch_pool<false, false>(c, "swn_decode_pool_chunk(bl6)");
+    return c.w16 ? launch_utts<true>(c, "swn_decode_w16(bl6)") : launch_utts<false>(c, "swn_decode(bl6)");
 }
 
 // streamed decode (swn_decode_chunk): per-utterance session floats of the symmetric kernel, 0 = not a BL6-class net
-extern "C" size_t swn_decode_bl6_session_floats(const swn_net_desc* d) {
-    SwnGeom g;
-    if (swn_make_geom(d, &g) < 0) return 0;
+size_t swn_decode_bl6_session_floats(const SwnGeom& g) {
     int n = 0;
     with_tr(g, [&](auto t) { n = decltype(t)::sess_floats; return SWN_OK; });
     return (size_t)n;
-}
-
-// one chunk on the symmetric kernel; `sess` holds swn_decode_bl6_session_floats() floats per utterance
-extern "C" int swn_decode_bl6_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                    int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
-                                    const void* seed, float* sess, void* out, float* heads, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    Bl6Args a;
-    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, step0, resume, sess);
-    hipStream_t st = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    return with_tr(g, [&](auto t) { return launch_mode<typename decltype(t)::Ext, true>(a, st); });
-}
-
-// the one-shot decode; SWN_E_UNSUPPORTED when the geometry is not a BL6-class one
-extern "C" int swn_decode_bl6_try(const swn_net_desc* d, const float* packed, const float* cond, int batch,
-                                  int n_frames, int n_steps, const SwnNoise* nz, const void* forced,
-                                  const void* seed, void* out, float* heads, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    Bl6Args a;
-    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, 0, 0, nullptr);
-    hipStream_t st = (hipStream_t)stream_;
-    (void)hipGetLastError();   // drop stale errors of earlier runtime calls; only our launches are reported
-    return with_tr(g, [&](auto t) {
-        using T = decltype(t);
-        return wants_ext(a) ? launch_mode<typename T::Ext>(a, st) : launch_mode<T>(a, st);
-    });
 }

@@ -4,9 +4,7 @@
 // their files.  Both kernels sit at the register limit: a change here changes the generated code of both.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "swn_geom.hpp"
-#include "swn_noise.hpp"
-#include "swn_pool.hpp"
+#include "swn_decode_internal.hpp"
 
 namespace swn_bl6 {
 
@@ -150,14 +148,12 @@ __device__ __forceinline__ void lds_barrier() {
 #define c_c1 lds[T::o_cz + 4 * H + o]
 
 // ---- host side
-// a launch (one-shot: step0 = resume = 0, sess = nullptr; pool: the launch-wide arguments over the entries)
-inline void fill_args(Bl6Args& a, const SwnGeom& g, const float* packed, const float* cond, const SwnNoise* nz,
-                      const void* forced, const void* seed, void* out, float* heads, int batch, int n_frames, int n_steps,
-                      int step0, int resume, float* sess) {
-    swn_make_layout(&g, &a.y);
-    a.P = packed; a.cond = cond; a.noise = nz->ptr; a.nz = *nz; a.forced = forced; a.seed = seed; a.out = out; a.heads = heads;
-    a.B = batch; a.Tf = n_frames; a.n_steps = n_steps; a.U = g.U; a.N = g.N;
-    a.step0 = step0; a.resume = resume; a.sess = sess;
+// the launch-wide arguments of a checked call (one-shot: step0 = resume = 0, no session; pool: those of a chunk over the entries)
+inline void fill_args(Bl6Args& a, const SwnDecodeCall& c) {
+    swn_make_layout(&c.g, &a.y);
+    a.P = c.packed; a.cond = c.cond; a.noise = c.nz.ptr; a.nz = c.nz; a.forced = c.forced; a.seed = c.seed; a.out = c.out;
+    a.heads = c.heads; a.B = c.batch; a.Tf = c.n_frames; a.n_steps = c.n_steps; a.U = c.g.U; a.N = c.g.N;
+    a.step0 = c.step0; a.resume = c.resume; a.sess = c.stream ? c.state : nullptr;
 }
 
 // the extended instantiation runs whenever the classic one's inputs (host-drawn noise, no dump, zero seed) are not given

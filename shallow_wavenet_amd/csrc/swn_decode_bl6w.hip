@@ -660,12 +660,6 @@ __global__ __launch_bounds__(NT) void decode_bl6w_pool_kernel(
     else decode_body<T, false, true, true>(a, lds);
 }
 
-template <class T, bool STREAM = false>
-int launch_mode(const Bl6Args& a, hipStream_t st) {
-    static_assert(T::lds_bytes <= 160 * 1024, "LDS budget");
-    return launch_kernel(decode_bl6w_kernel<T, STREAM>, T::lds_bytes, a.B, a, st, "swn_decode(bl6w)");
-}
-
 bool bl6w_applies(const SwnGeom& g) {
     return g.bl6 && g.U <= 256 && g.U >= 2 && !g.audio_in && g.kind == SWN_KIND_LAPLACE && g.S == 128 && g.O1 == 128 &&
            g.seg == 1 && (g.lpc == 0 || g.lpc == 4);
@@ -682,64 +676,38 @@ int with_tw(const SwnGeom& g, F&& f) {
 
 }  // namespace
 
-extern "C" int swn_decode_bl6w_try(const swn_net_desc* d, const float* packed, const float* cond, int batch,
-                                   int n_frames, int n_steps, const SwnNoise* nz, const void* forced,
-                                   const void* seed, void* out, float* heads, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
+// a checked call on the wave-specialised kernel (swn_decode.hip): a pool launch over the checked entry table (one workgroup
+// per entry, sessions [capacity][sess_floats]), a streamed chunk (`sess` holds sess_floats per utterance) or the one-shot decode
+int swn_decode_bl6w_run(const SwnDecodeCall& c) {
+    const hipStream_t st = c.hip_stream;
+    if (c.pool) {
+        Bl6PoolModelsArgs p;
+        fill_args(p.c, c);
+        p.t = *c.pool;
+        if (c.models) p.m = *c.models;
+        return with_tw(c.g, [&](auto tw) {
+            using T = typename decltype(tw)::Ext;
+            if (c.models)
+                return launch_kernel(decode_bl6w_pool_kernel<T, true>, T::lds_bytes, c.batch, p, st, "swn_decode_pool_chunk_models(bl6w)");
+            const Bl6PoolArgs& p1 = p;
+            return launch_kernel(decode_bl6w_pool_kernel<T>, T::lds_bytes, c.batch, p1, st, "swn_decode_pool_chunk(bl6w)");
+        });
+    }
     Bl6Args a;
-    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, 0, 0, nullptr);
-    hipStream_t st = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    return with_tw(g, [&](auto t) {
+    fill_args(a, c);
+    return with_tw(c.g, [&](auto t) {
         using T = decltype(t);
-        return wants_ext(a) ? launch_mode<typename T::Ext>(a, st) : launch_mode<T>(a, st);
+        using X = typename T::Ext;
+        static_assert(T::lds_bytes <= 160 * 1024 && X::lds_bytes <= 160 * 1024, "LDS budget");
+        if (c.stream) return launch_kernel(decode_bl6w_kernel<X, true>, X::lds_bytes, a.B, a, st, "swn_decode(bl6w)");
+        if (wants_ext(a)) return launch_kernel(decode_bl6w_kernel<X>, X::lds_bytes, a.B, a, st, "swn_decode(bl6w)");
+        return launch_kernel(decode_bl6w_kernel<T>, T::lds_bytes, a.B, a, st, "swn_decode(bl6w)");
     });
 }
 
 // streamed decode (swn_decode_chunk): per-utterance session floats of the wave-specialised kernel, 0 = it does not apply
-extern "C" size_t swn_decode_bl6w_session_floats(const swn_net_desc* d) {
-    SwnGeom g;
-    if (swn_make_geom(d, &g) < 0) return 0;
+size_t swn_decode_bl6w_session_floats(const SwnGeom& g) {
     int n = 0;
     with_tw(g, [&](auto t) { n = decltype(t)::sess_floats; return SWN_OK; });
     return (size_t)n;
-}
-
-// one chunk on the wave-specialised kernel; `sess` holds swn_decode_bl6w_session_floats() floats per utterance
-extern "C" int swn_decode_bl6w_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                     int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
-                                     const void* seed, float* sess, void* out, float* heads, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    Bl6Args a;
-    fill_args(a, g, packed, cond, nz, forced, seed, out, heads, batch, n_frames, n_steps, step0, resume, sess);
-    hipStream_t st = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    return with_tw(g, [&](auto t) { return launch_mode<typename decltype(t)::Ext, true>(a, st); });
-}
-
-// one pool launch (swn_decode_pool_chunk checked the entries): one workgroup per entry, sessions [capacity][sess_floats]
-extern "C" int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t,
-                                    const SwnPoolModels* models, int n_entries, int n_max, const SwnNoise* nz, const void* seed,
-                                    float* sess, void* out, float* heads, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    Bl6PoolModelsArgs p;
-    fill_args(p.c, g, packed, nullptr, nz, nullptr, seed, out, heads, n_entries, 0, n_max, 0, 0, sess);
-    p.t = *t;
-    hipStream_t st = (hipStream_t)stream_;
-    if (models) {
-        p.m = *models;
-        return with_tw(g, [&](auto tw) {
-            using T = typename decltype(tw)::Ext;
-            return launch_kernel(decode_bl6w_pool_kernel<T, true>, T::lds_bytes, n_entries, p, st,
-                                 "swn_decode_pool_chunk_models(bl6w)");
-        });
-    }
-    const Bl6PoolArgs& p1 = p;
-    return with_tw(g, [&](auto tw) {
-        using T = typename decltype(tw)::Ext;
-        return launch_kernel(decode_bl6w_pool_kernel<T>, T::lds_bytes, n_entries, p1, st, "swn_decode_pool_chunk(bl6w)");
-    });
 }

@@ -1,7 +1,8 @@
-// Library-internal interface between the decode dispatcher (swn_decode.hip) and the kernel files it hands a call to.  The
-// functions are C-linkage, so a prototype that drifted from its definition would link and misbehave at run time: every file
-// that defines one of them includes this header, which makes the compiler compare the two.
+// Library-internal interface between the decode dispatcher (swn_decode.hip) and the kernel files it hands a call to: the
+// record of one checked call, and per kernel file one run function that takes it.  The functions have C++ linkage, so a
+// declaration that drifted from its definition does not link; every file that defines one of them includes this header.
 #pragma once
+#include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
 #include "swn_noise.hpp"
 #include "swn_pool.hpp"
@@ -21,49 +22,41 @@ static inline SwnNoise swn_pool_noise_of(const swn_decode_io* io) {
     return nz;
 }
 
-extern "C" {
+// One call of swn_decode, swn_decode_chunk, swn_decode_pool_chunk or one of their *_w16 / *_models forms, as the dispatcher's
+// checks (swn_decode.hip) leave it: every field is valid for the kernel the call resolved to, and a run function only fills
+// its kernel's argument struct from it and picks the instantiation.
+struct SwnDecodeCall {
+    SwnGeom g;                                 // made once, by the check
+    const float* packed = nullptr;             // (not read when `models` is set)
+    const void* w16 = nullptr;                 // the bf16 image of the streamed head matrices; null: fp32 weights
+    const SwnPoolModels* models = nullptr;     // a pool over several models; null: one model
+    const SwnPoolTable* pool = nullptr;        // the checked entry table of a pool launch; null: not a pool
+    const float* cond = nullptr;               // (pool: every entry has its own)
+    int batch = 0;                             // utterances; pool: entries
+    int capacity = 0;                          // utterances `state` holds: batch; pool: the slots of the session buffer
+    int n_frames = 0;                          // (pool: every entry has its own)
+    int step0 = 0, n_steps = 0;                // pool: 0 and the most steps of an entry (n_max)
+    bool stream = false;                       // a chunk of a streamed decode (pools are streams); false: the one-shot decode
+    bool resume = false;                       // stream: the state comes from the session, no prologue
+    SwnNoise nz;
+    const void* forced = nullptr;
+    const void* seed = nullptr;
+    float* state = nullptr;                    // the one-shot decode's state buffer, or the session
+    void* out = nullptr;
+    float* heads = nullptr;
+    hipStream_t hip_stream = nullptr;
+};
 
-// swn_decode_bl6.hip (the symmetric BL6-class kernel) and swn_decode_bl6w.hip (the wave-specialised form for the
-// single-sample Laplace nets of that class).  *_try: the one-shot decode, SWN_E_UNSUPPORTED when the kernel does not take
-// the geometry.  *_session_floats: per-utterance session of a streamed decode (swn_decode_chunk), 0 = the kernel does not
-// apply.  *_chunk: one chunk.  *_pool: one pool launch over the entry table swn_decode_pool_chunk checked; with `models`
-// (swn_decode_pool_chunk_models) every entry runs its own model's weights and `packed` is not read.
-int swn_decode_bl6_try(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int n_steps,
-                       const SwnNoise* nz, const void* forced, const void* seed, void* out, float* heads, void* stream);
-int swn_decode_bl6w_try(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int n_steps,
-                        const SwnNoise* nz, const void* forced, const void* seed, void* out, float* heads, void* stream);
-size_t swn_decode_bl6_session_floats(const swn_net_desc* d);
-size_t swn_decode_bl6w_session_floats(const swn_net_desc* d);
-int swn_decode_bl6_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int step0,
-                         int n_steps, int resume, const SwnNoise* nz, const void* forced, const void* seed, float* sess,
-                         void* out, float* heads, void* stream);
-int swn_decode_bl6w_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int step0,
-                          int n_steps, int resume, const SwnNoise* nz, const void* forced, const void* seed, float* sess,
-                          void* out, float* heads, void* stream);
-int swn_decode_bl6_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, const SwnPoolModels* models,
-                        int n_entries, int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
-                        void* stream);
-int swn_decode_bl6w_pool(const swn_net_desc* d, const float* packed, const SwnPoolTable* t, const SwnPoolModels* models,
-                         int n_entries, int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads,
-                         void* stream);
-// the symmetric kernel over the bf16 image of its streamed head matrices (w16: swn_pack_decode_w16), extended mode only
-int swn_decode_bl6_w16_try(const swn_net_desc* d, const float* packed, const void* w16, const float* cond, int batch,
-                           int n_frames, int n_steps, const SwnNoise* nz, const void* forced, const void* seed, void* out,
-                           float* heads, void* stream);
-int swn_decode_bl6_w16_chunk(const swn_net_desc* d, const float* packed, const void* w16, const float* cond, int batch,
-                             int n_frames, int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
-                             const void* seed, float* sess, void* out, float* heads, void* stream);
-int swn_decode_bl6_w16_pool(const swn_net_desc* d, const float* packed, const void* w16, const SwnPoolTable* t, int n_entries,
-                            int n_max, const SwnNoise* nz, const void* seed, float* sess, void* out, float* heads, void* stream);
+// swn_decode_bl6.hip (the symmetric BL6-class kernel; the only one that takes `w16`) and swn_decode_bl6w.hip (the
+// wave-specialised form for the single-sample Laplace nets of that class).  *_session_floats: per-utterance session of a
+// streamed decode, 0 = the kernel does not take the geometry.
+size_t swn_decode_bl6_session_floats(const SwnGeom& g);
+size_t swn_decode_bl6w_session_floats(const SwnGeom& g);
+int swn_decode_bl6_run(const SwnDecodeCall& c);
+int swn_decode_bl6w_run(const SwnDecodeCall& c);
 
-// swn_decode_stepped.hip (one launch per phase of a step, for the large geometries)
-size_t swn_decode_stepped_state_floats(const swn_net_desc* d, int batch);
-int swn_decode_stepped_supported(const swn_net_desc* d, int batch);
-int swn_decode_stepped(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int n_steps,
-                       const SwnNoise* nz, const void* forced, const void* seed, float* state, void* out, float* heads,
-                       void* stream);
-int swn_decode_stepped_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                             int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced, const void* seed,
-                             float* sess, void* out, float* heads, void* stream);
-
-}  // extern "C"
+// swn_decode_stepped.hip (one launch per phase of a step, for the large geometries; no pools through this record: the stepped
+// pool has entry points of its own).  *_state_floats: the state buffer, which is also the session of a streamed decode.
+size_t swn_decode_stepped_state_floats(const SwnGeom& g, int batch);
+bool swn_decode_stepped_supported(const SwnGeom& g, int batch);
+int swn_decode_stepped_run(const SwnDecodeCall& c);

@@ -997,20 +997,20 @@ void launch_iteration(const StA<POOL, MODELS>& a, int it, bool in, bool gen, hip
     else launch_iteration_of<POOL, STREAM, SWN_KIND_SOFTMAX, MODELS>(a, it, in, gen, st);
 }
 
-// the launch chain of steps [step0, step0 + n_steps); stream = a chunk of a streamed decode: `state` is the session, which the
-// prologue fills only when !resume, and the tails take their STREAM form (chunk-local rows).  stream = false: swn_decode_stepped.
-int stepped_run(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames, int step0,
-                int n_steps, bool stream, bool resume, const SwnNoise* nz, const void* forced, const void* seed,
-                float* state, void* out, float* heads, void* stream_) {
+}  // namespace
+
+// the launch chain of a checked call (swn_decode.hip): steps [step0, step0 + n_steps); stream = a chunk of a streamed decode:
+// `state` is the session, which the prologue fills only when !resume, and the tails take their STREAM form (chunk-local rows)
+int swn_decode_stepped_run(const SwnDecodeCall& c) {
     StArgs a;
-    int rc = swn_make_geom(d, &a.g);
-    if (rc < 0) return rc;
+    a.g = c.g;
+    const int batch = c.batch, step0 = c.step0, n_steps = c.n_steps;
     if (!chain_takes(a.g, batch)) return SWN_E_UNSUPPORTED;
-    fill_args(a, packed, cond, *nz, forced, seed, state, out, heads, batch, n_frames, n_steps, step0);
-    hipStream_t st = (hipStream_t)stream_;
-    if (!resume) {
-        if (hipMemsetAsync(state, 0, sizeof(float) * (size_t)a.stride * batch, st) != hipSuccess) return SWN_E_LAUNCH;
-        if (a.g.kind == SWN_KIND_SOFTMAX || seed) hipLaunchKernelGGL(step_seed_kernel, dim3(batch), dim3(64), 0, st, a);
+    fill_args(a, c.packed, c.cond, c.nz, c.forced, c.seed, c.state, c.out, c.heads, batch, c.n_frames, n_steps, step0);
+    hipStream_t st = c.hip_stream;
+    if (!c.resume) {
+        if (hipMemsetAsync(c.state, 0, sizeof(float) * (size_t)a.stride * batch, st) != hipSuccess) return SWN_E_LAUNCH;
+        if (a.g.kind == SWN_KIND_SOFTMAX || c.seed) hipLaunchKernelGGL(step_seed_kernel, dim3(batch), dim3(64), 0, st, a);
     }
     if (batch >= ST_SEQ) {
         static bool attr_set = false;
@@ -1021,42 +1021,23 @@ int stepped_run(const swn_net_desc* d, const float* packed, const float* cond, i
     }
     // iterations: the prologue positions (not when resuming), then the chunk's generation steps at absolute indices
     const int it_gen0 = a.n_pro + step0, total = it_gen0 + n_steps;
-    for (int it = resume ? it_gen0 : 0; it < total; ++it) {
+    for (int it = c.resume ? it_gen0 : 0; it < total; ++it) {
         const bool in = it < a.n_pro || it == it_gen0, gen = it >= a.n_pro;
-        if (stream) launch_iteration<false, true>(a, it, in, gen, st);
+        if (c.stream) launch_iteration<false, true>(a, it, in, gen, st);
         else launch_iteration<false, false>(a, it, in, gen, st);
     }
     return swn_launch_status("swn_decode(stepped)");
 }
 
-}  // namespace
-
-extern "C" size_t swn_decode_stepped_state_floats(const swn_net_desc* d, int batch) {
+// the state buffer of the chain, which is also the session of a streamed decode
+size_t swn_decode_stepped_state_floats(const SwnGeom& g, int batch) {
     StArgs a;
-    if (swn_make_geom(d, &a.g) < 0 || batch < 1) return 0;
-    return (size_t)plan(a) * batch;
+    a.g = g;
+    return batch < 1 ? 0 : (size_t)plan(a) * batch;
 }
 
-extern "C" int swn_decode_stepped(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                  int n_steps, const SwnNoise* nz, const void* forced, const void* seed, float* state,
-                                  void* out, float* heads, void* stream_) {
-    return stepped_run(d, packed, cond, batch, n_frames, 0, n_steps, false, false, nz, forced, seed, state, out, heads, stream_);
-}
-
-// 1 when the stepped chain runs this (net, batch) (the conditions swn_decode_stepped returns SWN_E_UNSUPPORTED under)
-extern "C" int swn_decode_stepped_supported(const swn_net_desc* d, int batch) {
-    SwnGeom g;
-    if (swn_make_geom(d, &g) < 0 || batch < 1) return 0;
-    return chain_takes(g, batch) ? 1 : 0;
-}
-
-// one chunk of a streamed decode; the session is the state buffer of the chain (swn_decode_stepped_state_floats())
-extern "C" int swn_decode_stepped_chunk(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                                        int step0, int n_steps, int resume, const SwnNoise* nz, const void* forced,
-                                        const void* seed, float* sess, void* out, float* heads, void* stream_) {
-    return stepped_run(d, packed, cond, batch, n_frames, step0, n_steps, true, resume != 0, nz, forced, seed, sess, out, heads,
-                       stream_);
-}
+// whether the chain runs this (net, batch) (the conditions swn_decode_stepped_run returns SWN_E_UNSUPPORTED under)
+bool swn_decode_stepped_supported(const SwnGeom& g, int batch) { return batch >= 1 && chain_takes(g, batch); }
 
 // ---- stepped decode pool -------------------------------------------------------------------------------------------
 extern "C" int swn_decode_stepped_prologue_iterations(const swn_net_desc* d) {
@@ -1076,7 +1057,7 @@ struct StPoolCall {
 
 // the argument rules of swn_decode_pool_stepped_chunk (include/swn_hip.h), and with `models` those the call over several
 // models adds; nothing is launched before they pass
-int pool_check(const swn_net_desc* d, const SwnGeom& g, const float* packed, const float* const* models, int n_models,
+int pool_check(const SwnGeom& g, const float* packed, const float* const* models, int n_models,
                const int32_t* model_of_entry, int capacity, const swn_decode_stepped_pool_entry* entries, int n_entries,
                const swn_decode_io* io, const float* session, const void* out, StPoolCall& c) {
     if ((!models && !packed) || !entries || !io || !session) return SWN_E_BADARG;
@@ -1108,7 +1089,7 @@ int pool_check(const swn_net_desc* d, const SwnGeom& g, const float* packed, con
         any_begin = any_begin || begin;
     }
     if (n_max > 0 && !out) return SWN_E_BADARG;
-    if (!swn_decode_stepped_supported(d, capacity)) return SWN_E_UNSUPPORTED;
+    if (!swn_decode_stepped_supported(g, capacity)) return SWN_E_UNSUPPORTED;
     c.n_max = n_max; c.it_max = it_max; c.any_begin = any_begin;
     return SWN_OK;
 }
@@ -1131,7 +1112,7 @@ extern "C" int swn_decode_pool_stepped_chunk(const swn_net_desc* d, const float*
     if (rc < 0) return rc;
     const SwnGeom& g = a.g;
     StPoolCall c;
-    rc = pool_check(d, g, packed, nullptr, 0, nullptr, capacity, entries, n_entries, io, session, out, c);
+    rc = pool_check(g, packed, nullptr, 0, nullptr, capacity, entries, n_entries, io, session, out, c);
     if (rc != SWN_OK) return rc;
     const int n_pro = g.rf - g.seg + 1, n_max = c.n_max, it_max = c.it_max;
     const bool any_begin = c.any_begin;
@@ -1227,7 +1208,7 @@ extern "C" int swn_decode_pool_stepped_chunk_models(const swn_net_desc* d, const
     const SwnGeom& g = a.g;
     if (!models || !model_of_entry) return SWN_E_BADARG;
     StPoolCall c;
-    rc = pool_check(d, g, nullptr, models, n_models, model_of_entry, capacity, entries, n_entries, io, session, out, c);
+    rc = pool_check(g, nullptr, models, n_models, model_of_entry, capacity, entries, n_entries, io, session, out, c);
     if (rc != SWN_OK) return rc;
     const int n_pro = g.rf - g.seg + 1, it_max = c.it_max;
     if (!c.any_begin && it_max == 0) return SWN_OK;         // every slot stays as it is

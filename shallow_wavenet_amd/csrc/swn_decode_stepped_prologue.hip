@@ -264,7 +264,7 @@ extern "C" int swn_decode_stepped_prologue(const swn_net_desc* d, const float* p
         for (int f = 0; f < e; ++f)
             if (entries[f].slot == en.slot) return SWN_E_BADARG;   // two entries on one session
     }
-    if (!swn_decode_stepped_supported(d, n_slots) || pro_work_floats(g, n_entries) == 0) return SWN_E_UNSUPPORTED;
+    if (!swn_decode_stepped_supported(g, n_slots) || pro_work_floats(g, n_entries) == 0) return SWN_E_UNSUPPORTED;
 
     fill_args(a, models ? models[0] : packed, nullptr, swn_pool_noise_of(io), nullptr, io->seed_dev, session, nullptr, nullptr,
               n_entries, 0, 0, 0);

@@ -320,17 +320,12 @@ def decode_impl(packed: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.
                         want_noise, utt_ids)
 
 
-def _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise,
-                 utt_ids):
-    """decode (w16 None: swn_decode) and decode_w16 (the bf16 image: swn_decode_w16)"""
-    L = _lib.lib()
-    d = _desc(desc)
-    _need_cuda(packed, "the packed parameters")
-    dev = packed.device
+def _decode_io(d, dev, cond, noise, forced, seed, utt_ids, n_steps, rng_seed, rng_utt0, want_heads, want_noise):
+    """the checked inputs of the sampling loop and the outputs of decode / decode_chunk and their *_w16 forms over the
+    utterances of `cond` -> (io, out, heads, used); io keeps its tensors alive"""
     soft, seg, _, _, n_out, _ = _geom(d)
-    B, Tf = cond.shape[0], cond.shape[1]
+    B = cond.shape[0]
     width = d.n_quantize if soft else seg
-    cond = cond.contiguous()
     if noise is not None:
         noise = noise.to(dev, torch.float32).contiguous()
         if tuple(noise.shape) != (B, n_steps, width):
@@ -347,10 +342,6 @@ def _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant,
         utt_ids = utt_ids.to(dev, torch.int32).contiguous()
         if utt_ids.numel() != B:
             raise RuntimeError(f"utt_ids has {utt_ids.numel()} elements, expected {B}")
-    r = ctypes.byref(d)
-    if w16 is not None:
-        _check_w16(w16, packed, d)
-    state = torch.empty(L.swn_decode_state_floats(r, B) if w16 is None else 0, dtype=torch.float32, device=dev)
     out = torch.empty((B, n_steps * seg), dtype=torch.int32 if soft else torch.float32, device=dev)
     heads = torch.empty((B, n_steps, n_out) if want_heads else (0,), dtype=torch.float32, device=dev)
     used = torch.empty((B, n_steps, width) if want_noise else (0,), dtype=torch.float32, device=dev)
@@ -358,6 +349,25 @@ def _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant,
                        noise_out_dev=_ptr(used if want_noise else None),
                        rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=int(rng_utt0) & 0xFFFFFFFF, reserved=0,
                        rng_utt_ids_dev=_ptr(utt_ids))
+    io._keep = (noise, forced, seed, utt_ids)
+    return io, out, heads, used
+
+
+def _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise,
+                 utt_ids):
+    """decode (w16 None: swn_decode) and decode_w16 (the bf16 image: swn_decode_w16)"""
+    L = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(packed, "the packed parameters")
+    dev = packed.device
+    B, Tf = cond.shape[0], cond.shape[1]
+    cond = cond.contiguous()
+    io, out, heads, used = _decode_io(d, dev, cond, noise, forced, seed, utt_ids, n_steps, rng_seed, rng_utt0, want_heads,
+                                      want_noise)
+    r = ctypes.byref(d)
+    if w16 is not None:
+        _check_w16(w16, packed, d)
+    state = torch.empty(L.swn_decode_state_floats(r, B) if w16 is None else 0, dtype=torch.float32, device=dev)
     with _on(dev):
         if w16 is None:
             _lib.check(L.swn_decode(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), _ptr(state), _ptr(out),
@@ -425,13 +435,7 @@ def _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise):
 
 @decode.register_fake
 def _(packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise, utt_ids=None):
-    d = _desc(desc)
-    soft, seg, _, _, n_out, _ = _geom(d)
-    B = cond.shape[0]
-    width = d.n_quantize if soft else seg
-    return (packed.new_empty((B, n_steps * seg), dtype=torch.int32 if soft else torch.float32),
-            packed.new_empty((B, n_steps, n_out) if want_heads else (0,)),
-            packed.new_empty((B, n_steps, width) if want_noise else (0,)))
+    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
 
 
 # ------------------------------------------------------------------------------------------ streamed decode
@@ -454,37 +458,14 @@ def _decode_chunk_call(w16, packed, cond, session, noise, forced, seed, desc, st
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
     dev = packed.device
-    soft, seg, _, _, n_out, _ = _geom(d)
     B, Tf = cond.shape[0], cond.shape[1]
-    width = d.n_quantize if soft else seg
     cond = cond.contiguous()
     if session.device != dev or session.dtype != torch.float32 or not session.is_contiguous():
         raise RuntimeError("session must be a contiguous fp32 tensor on the device of the packed parameters")
     if session.numel() < L.swn_decode_session_floats(ctypes.byref(d), B, variant):
         raise RuntimeError("session buffer too small for this (net, batch, variant)")
-    if noise is not None:
-        noise = noise.to(dev, torch.float32).contiguous()
-        if tuple(noise.shape) != (B, n_steps, width):
-            raise RuntimeError(f"noise shape {tuple(noise.shape)} != {(B, n_steps, width)}")
-    if forced is not None:
-        forced = forced.to(dev, torch.int32 if soft else torch.float32).contiguous()
-        if forced.numel() != B * n_steps * seg:
-            raise RuntimeError("forced history has the wrong size")
-    if seed is not None:
-        seed = seed.to(dev, torch.int32 if soft else torch.float32).contiguous()
-        if seed.numel() != B * seg:
-            raise RuntimeError(f"seed waveform has {seed.numel()} elements, expected {B * seg}")
-    if utt_ids is not None:
-        utt_ids = utt_ids.to(dev, torch.int32).contiguous()
-        if utt_ids.numel() != B:
-            raise RuntimeError(f"utt_ids has {utt_ids.numel()} elements, expected {B}")
-    out = torch.empty((B, n_steps * seg), dtype=torch.int32 if soft else torch.float32, device=dev)
-    heads = torch.empty((B, n_steps, n_out) if want_heads else (0,), dtype=torch.float32, device=dev)
-    used = torch.empty((B, n_steps, width) if want_noise else (0,), dtype=torch.float32, device=dev)
-    io = _lib.DecodeIO(noise_dev=_ptr(noise), forced_dev=_ptr(forced), seed_dev=_ptr(seed),
-                       noise_out_dev=_ptr(used if want_noise else None),
-                       rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=int(rng_utt0) & 0xFFFFFFFF, reserved=0,
-                       rng_utt_ids_dev=_ptr(utt_ids))
+    io, out, heads, used = _decode_io(d, dev, cond, noise, forced, seed, utt_ids, n_steps, rng_seed, rng_utt0, want_heads,
+                                      want_noise)
     args = (ctypes.byref(d), _ptr(packed), _ptr(cond), B, Tf, int(step0), int(n_steps), _lib.CHUNK_BEGIN if begin else 0,
             ctypes.byref(io), _ptr(session), _ptr(out if n_steps > 0 else None), _ptr(heads if want_heads else None),
             int(variant))
@@ -522,13 +503,7 @@ def _(packed, w16, cond, session, noise, forced, seed, desc, step0, n_steps, beg
 @decode_chunk.register_fake
 def _(packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0, want_heads,
       want_noise, utt_ids=None):
-    d = _desc(desc)
-    soft, seg, _, _, n_out, _ = _geom(d)
-    B = cond.shape[0]
-    width = d.n_quantize if soft else seg
-    return (packed.new_empty((B, n_steps * seg), dtype=torch.int32 if soft else torch.float32),
-            packed.new_empty((B, n_steps, n_out) if want_heads else (0,)),
-            packed.new_empty((B, n_steps, width) if want_noise else (0,)))
+    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
 
 
 # ------------------------------------------------------------------------------------------ decode pool
@@ -542,24 +517,18 @@ def decode_pool_chunk_impl(packed: torch.Tensor, session: torch.Tensor, conds: L
     classes; None = zeros / Q/2).  Noise is drawn on the device, keyed by rng_seed and utt_ids[e].  out / heads / used noise
     are dense (E, n_max * seg) | (E, n_max, n_out) | (E, n_max, width), n_max = max(n_steps); rows past an entry's own steps
     are not written."""
-    L = _lib.lib()
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
-    dev = packed.device
-    table, io, out, heads, used, n_max = _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins, seeds,
-                                                           utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
-    with _on(dev):
-        _lib.check(L.swn_decode_pool_chunk(ctypes.byref(d), _ptr(packed), int(capacity), table, len(conds), ctypes.byref(io),
-                                           _ptr(session), _ptr(out if n_max > 0 else None),
-                                           _ptr(heads if want_heads else None), int(variant), _stream(dev)),
-                   "decode_pool_chunk")
-    return out, heads, used
+    return _decode_pool_call(_lib.lib().swn_decode_pool_chunk, d, packed.device, (_ptr(packed),), (), session, conds, slots,
+                             step0s, n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
 
 
-def _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed,
-                      want_heads, want_noise):
-    """the checked entry table, io block and outputs of a pool launch (decode_pool_chunk and decode_pool_chunk_models) ->
-    (table, io, out, heads, used, n_max); io keeps the seeds and ids alive"""
+def _decode_pool_call(call, d, dev, lead, trail, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, capacity,
+                      variant, rng_seed, want_heads, want_noise):
+    """one pool launch through the library's `call` (decode_pool_chunk and its *_w16 / *_models forms): checks the entries and
+    builds their table, the io block and the outputs.  `lead` are the call's arguments between the descriptor and the
+    capacity (the packed parameters, or the model tables), `trail` those between the variant and the stream (the bf16 image)"""
+    L = _lib.lib()
     soft, seg, _, _, n_out, _ = _geom(d)
     E = len(conds)
     if not (len(slots) == len(step0s) == len(n_steps) == len(begins) == len(utt_ids) == E):
@@ -590,8 +559,11 @@ def _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins,
     io = _lib.DecodeIO(noise_dev=None, forced_dev=None, seed_dev=_ptr(seeds),
                        noise_out_dev=_ptr(used if want_noise else None),
                        rng_seed=int(rng_seed) & 0xFFFFFFFFFFFFFFFF, rng_utt0=0, reserved=0, rng_utt_ids_dev=_ptr(ids))
-    io._keep = (seeds, ids)
-    return table, io, out, heads, used, n_max
+    with _on(dev):
+        _lib.check(call(ctypes.byref(d), *lead, int(capacity), table, E, ctypes.byref(io), _ptr(session),
+                        _ptr(out if n_max > 0 else None), _ptr(heads if want_heads else None), int(variant), *trail,
+                        _stream(dev)), call.__name__[len("swn_"):])
+    return out, heads, used
 
 
 decode_pool_chunk = custom_op("swn::decode_pool_chunk", mutates_args=("session",))(decode_pool_chunk_impl)
@@ -604,19 +576,12 @@ def decode_pool_chunk_w16_impl(packed: torch.Tensor, w16: torch.Tensor, session:
                                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """decode_pool_chunk over the bf16 image of the streamed head matrices (swn_decode_pool_chunk_w16): every entry's rows
     are bit-identical to decode_chunk_w16 of that session alone."""
-    L = _lib.lib()
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
-    dev = packed.device
     _check_w16(w16, packed, d)
-    table, io, out, heads, used, n_max = _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins, seeds,
-                                                           utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
-    with _on(dev):
-        _lib.check(L.swn_decode_pool_chunk_w16(ctypes.byref(d), _ptr(packed), int(capacity), table, len(conds),
-                                               ctypes.byref(io), _ptr(session), _ptr(out if n_max > 0 else None),
-                                               _ptr(heads if want_heads else None), int(variant), _ptr(w16), _stream(dev)),
-                   "decode_pool_chunk_w16")
-    return out, heads, used
+    return _decode_pool_call(_lib.lib().swn_decode_pool_chunk_w16, d, packed.device, (_ptr(packed),), (_ptr(w16),), session,
+                             conds, slots, step0s, n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed, want_heads,
+                             want_noise)
 
 
 decode_pool_chunk_w16 = custom_op("swn::decode_pool_chunk_w16", mutates_args=("session",))(decode_pool_chunk_w16_impl)
@@ -652,17 +617,11 @@ def decode_pool_chunk_models_impl(models: List[torch.Tensor], model_of: List[int
     """decode_pool_chunk over sessions of several models of one geometry (swn_decode_pool_chunk_models): entry e runs with the
     packed parameters models[model_of[e]] (at most 16 models per call); everything else as decode_pool_chunk, and every
     entry's rows bit-identical to decode_pool_chunk with that entry's model."""
-    L = _lib.lib()
     d = _desc(desc)
+    L = _lib.lib()
     dev, ptrs, of = _model_tables(L, d, models, model_of, len(conds), "decode_pool_chunk_models")
-    table, io, out, heads, used, n_max = _decode_pool_args(L, d, dev, session, conds, slots, step0s, n_steps, begins, seeds,
-                                                           utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
-    with _on(dev):
-        _lib.check(L.swn_decode_pool_chunk_models(ctypes.byref(d), ptrs, len(models), of, int(capacity), table, len(conds),
-                                                  ctypes.byref(io), _ptr(session), _ptr(out if n_max > 0 else None),
-                                                  _ptr(heads if want_heads else None), int(variant), _stream(dev)),
-                   "decode_pool_chunk_models")
-    return out, heads, used
+    return _decode_pool_call(L.swn_decode_pool_chunk_models, d, dev, (ptrs, len(models), of), (), session, conds, slots, step0s,
+                             n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
 
 
 decode_pool_chunk_models = custom_op("swn::decode_pool_chunk_models",
