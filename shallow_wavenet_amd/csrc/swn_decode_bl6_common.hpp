@@ -140,6 +140,28 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// The same barrier for a wave that has requested LDS reads it will use only behind it: rows no wave writes in the phase that
+// ends here, so nothing of them depends on the barrier.  lds_barrier() cannot carry them across - its release fence waits for
+// lgkmcnt(0) and no load moves over its acquire fence.  Here the wave waits until N operations are left on its LDS counter:
+// LDS serves one wave's operations in order, so with the N reads issued BEHIND the wave's last hand-off write of the phase
+// (lds_fence_compiler() between them, the issue order pinned with sched_barrier(0)) that write is retired and the reads stay in
+// flight through the s_barrier.  lgkmcnt also counts scalar loads, which return out of order: none may be outstanding at the call
+// (check the ISA of every instantiation; the compiler itself waits for lgkmcnt(0) before it uses one).  N <= 15: the counter has
+// four bits.
+__device__ __forceinline__ void lds_fence_compiler() { asm volatile("" ::: "memory"); }
+template <int N>
+__device__ __forceinline__ void lds_barrier_keep() {
+    static_assert(N >= 0 && N <= 15, "lgkmcnt is a four-bit counter");
+#ifdef SWN_SYNC
+    __syncthreads(); return;
+#endif
+    __builtin_amdgcn_sched_barrier(0);          // (arithmetic is free to cross the asm and the s_barrier: the multiply-adds the
+    asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(N) : "memory");   //  early reads feed moved in front of them, behind lgkmcnt(0))
+    __builtin_amdgcn_s_barrier();
+    lds_fence_compiler();
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // the five input-layer constants of channel `o` in a kernel's carve (cb[64], cv[2][64], cc[2][64] at T::o_cz of `lds`)
 #define c_b  lds[T::o_cz + o]
 #define c_v0 lds[T::o_cz + H + o]

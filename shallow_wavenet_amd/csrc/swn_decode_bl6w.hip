@@ -189,6 +189,46 @@ __device__ __forceinline__ void older_bn(Layers<LS...>, float* lds, const float 
     }
 }
 
+// The same products with their operand rows requested a phase early (older_rows in front of lds_barrier_keep, older_bn_x behind
+// it): the rows are at least one barrier old when they are requested, and behind the barrier the products are multiply-add chains
+// with nothing to wait for.  The order of the multiply-adds inside each chain is older_sum's.
+template <class T, int LAYER>
+__device__ __forceinline__ void older_rows(const float* lds, const int qn, const int tb, float4 (&x)[4]) {
+    constexpr int dil = 1 << LAYER;
+    constexpr int R = T::ring_len(LAYER);
+    const float* row = lds + T::o_ring + T::ring_off(LAYER) + ((qn - dil) & (R - 1)) * H + 16 * (tb & 3);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) x[m] = *reinterpret_cast<const float4*>(row + 4 * m);
+}
+__device__ __forceinline__ void older_sum_x(const float (&w)[2][16], const float4 (&x)[4], float& az, float& ac) {
+    az = 0.f; ac = 0.f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        az = fmaf(w[0][4 * m], x[m].x, az); ac = fmaf(w[1][4 * m], x[m].x, ac);
+        az = fmaf(w[0][4 * m + 1], x[m].y, az); ac = fmaf(w[1][4 * m + 1], x[m].y, ac);
+        az = fmaf(w[0][4 * m + 2], x[m].z, az); ac = fmaf(w[1][4 * m + 2], x[m].z, ac);
+        az = fmaf(w[0][4 * m + 3], x[m].w, az); ac = fmaf(w[1][4 * m + 3], x[m].w, ac);
+    }
+    az = sum4(az); ac = sum4(ac);
+}
+template <class T, int... LS>
+__device__ __forceinline__ void older_rows_n(Layers<LS...>, const float* lds, const int qn, const int tb, float4 (&x)[sizeof...(LS)][4]) {
+    int k = 0;
+    ((older_rows<T, LS>(lds, qn, tb, x[k]), ++k), ...);
+}
+template <class T, int NW, int... LS>
+__device__ __forceinline__ void older_bn_x(Layers<LS...>, float* lds, const float (&w)[NW][2][16], const float4 (&x)[sizeof...(LS)][4],
+                                           const int qn, const int tb) {
+    static_assert(((LS < NW) && ...), "register-resident halves only");
+    float az[sizeof...(LS)], ac[sizeof...(LS)];
+    int k = 0;
+    ((older_sum_x(w[LS], x[k], az[k], ac[k]), ++k), ...);
+    if ((tb & 3) < 2) {
+        k = 0;
+        ((older_store<T, LS>(lds, qn, tb, az[k], ac[k]), ++k), ...);
+    }
+}
+
 // ---- group B: out_skip, slice by slice.  Thread (r, hp): rows r and r + 64 over inputs 16 mm + 4 hp .. + 3 of the slice (the
 //      lane-tiled global copy wsk2 of the symmetric kernel: 1 KiB contiguous per wave instruction); weights issued a phase ahead
 //      (slice 0 whole, at the start of the step; the others by skip_roll_b).
@@ -452,9 +492,17 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
 #define SWN_BAR(k) { tw[k] += __builtin_amdgcn_s_memtime() - tlast; lds_barrier(); tlast = __builtin_amdgcn_s_memtime(); }
     // (the empty asm uses the register, so the compiler places the vmcnt wait of the slice's oldest request in front of it)
 #define SWN_WAIT_STAMP(k) { asm volatile("" :: "v"(wsl[0].x)); tv[k] += __builtin_amdgcn_s_memtime() - tlast; }
+    // a barrier that leaves N early reads in flight (lds_barrier_keep): the phase's work ends at SWN_PRE, behind the hand-off
+    // write and in front of the early reads - the stamp's s_memtime counts on lgkmcnt too and returns out of order, so it is
+    // waited for (lgkmcnt(0)) before the first of them is issued.  Issuing them is then in neither phase's figure, and the s_memtime
+    // behind the barrier makes the first use of an early read wait for all of them
+#define SWN_PRE(k) { tw[k] += __builtin_amdgcn_s_memtime() - tlast; asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+#define SWN_BAR_KEEP(k, N) { lds_barrier_keep<N>(); tlast = __builtin_amdgcn_s_memtime(); }
 #else
 #define SWN_BAR(k) lds_barrier();
 #define SWN_WAIT_STAMP(k)
+#define SWN_PRE(k)
+#define SWN_BAR_KEEP(k, N) lds_barrier_keep<N>();
 #endif
     // one layer phase: group A runs the chain, group B prepares position q + 1 (and, during generation, accumulates out_skip)
     // (GEN: a generation step - group B's older-tap products for position q + 1 then sit in the merged and the out_1 phase, and
@@ -522,25 +570,74 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         // position q + 1 from group B's half in LDS, with group B's thread-to-row mapping and summation order (bit-identical): its
         // operand h_4(q - 31) is 31 steps old, o_old[(q + 1) & 1][5] was last read in layer 5 of step q - 1 and is next read
         // in layer 5 of step q + 1, two barriers ahead of the end of the step (the session copy of a chunk's last step)
-        if constexpr (!grpA) { SWN_WAIT_STAMP(5) skip_last_b<T>(lds, wsl, sacc, tg); }
-        else older_b<T, L - 1, 2>(lds, wreg[L - 1], q + 1, tg + (int)step0);   // (opaque zero: no address of it stays resident)
-        SWN_BAR(6)
+        // Both groups then request, behind their hand-off write of this phase and in front of barrier 6 (lds_barrier_keep), rows the out_1
+        // phase reads that do not depend on that barrier.  Group B: the operand rows of OlderOut1, in wsl's registers and sixteen more -
+        // all older than barrier 5, none rewritten before barrier 7 (hazard table).  Group A (lpc 0; with lpc 4 it has no
+        // registers for it: 4 - 16 spilled): the out_1 weights of input blocks 0 and 1, both rows, in the working registers the product
+        // has freed - o_w1 is written once, in front of the step loop.
+        constexpr bool ROLL1 = T::LPC == 0;
+        float4 xo[3][4];
+        float4 w1e[2][2];
+        if constexpr (!grpA) {
+            SWN_WAIT_STAMP(5) skip_last_b<T>(lds, wsl, sacc, tg);
+            SWN_PRE(6)
+            lds_fence_compiler();
+            __builtin_amdgcn_sched_barrier(0);
+            older_rows_n<T>(OlderOut1{}, lds, q + 1, tg, xo);
+            __builtin_amdgcn_sched_barrier(0);
+            SWN_BAR_KEEP(6, 12)
+        } else {
+            older_b<T, L - 1, 2>(lds, wreg[L - 1], q + 1, tg + (int)step0);   // (opaque zero: no address of it stays resident)
+            if constexpr (ROLL1) {
+                SWN_PRE(6)
+                lds_fence_compiler();
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+                    for (int r = 0; r < 2; ++r)
+                        w1e[mm][r] = *reinterpret_cast<const float4*>(lds + T::o_w1 + ((mm * O1 + (tg >> 2) + 64 * r) * 4 + (tg & 3)) * 4);
+                __builtin_amdgcn_sched_barrier(0);
+                SWN_BAR_KEEP(6, 4)
+            } else {
+                SWN_BAR(6)
+            }
+        }
         if constexpr (grpA) {
             // out_1, 128 x 128, LDS-resident, by group A alone: thread (hr, hp) rows hr and hr + 64 over inputs 16 mm + 4 hp .. + 3 - one
             // read of the inputs serves both rows.  Group B meanwhile forms three of the older-tap products of position q + 1 (with
             // all eight waves on out_1 the phase took 1 020 cycles, and the six products had to sit beside the out_skip slices)
             const int hr = tg >> 2, hp = tg & 3;
             float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
-#pragma unroll
-            for (int mm = 0; mm < 8; ++mm) {
-                const float4 x0 = *reinterpret_cast<const float4*>(lds + T::o_skip + 16 * mm + 4 * hp);
-                const float4 w0 = *reinterpret_cast<const float4*>(lds + T::o_w1 + ((mm * O1 + hr) * 4 + hp) * 4);
-                const float4 w1 = *reinterpret_cast<const float4*>(lds + T::o_w1 + ((mm * O1 + hr + 64) * 4 + hp) * 4);
+            auto X = [&](int mm) { return *reinterpret_cast<const float4*>(lds + T::o_skip + 16 * mm + 4 * hp); };
+            auto W = [&](int mm, int r) { return *reinterpret_cast<const float4*>(lds + T::o_w1 + ((mm * O1 + hr + 64 * r) * 4 + hp) * 4); };
+            auto fma8 = [&](int mm, const float4& x0, const float4& w0, const float4& w1) {
                 float& acc = (mm & 1) ? a1 : a0;
                 float& bcc = (mm & 1) ? b1 : b0;
                 acc = fmaf(w0.x, x0.x, acc); acc = fmaf(w0.y, x0.y, acc); acc = fmaf(w0.z, x0.z, acc); acc = fmaf(w0.w, x0.w, acc);
                 bcc = fmaf(w1.x, x0.x, bcc); bcc = fmaf(w1.y, x0.y, bcc); bcc = fmaf(w1.z, x0.z, bcc); bcc = fmaf(w1.w, x0.w, bcc);
-                if ((mm & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // at most four slices of operands live beside the 192 weight registers
+            };
+            if constexpr (ROLL1) {
+                // rolled: the weights one input block ahead, the inputs two, each into the registers a block's multiply-adds have just
+                // freed (28 working registers hold two blocks of weights and three of inputs).  Left to the scheduler, the 24 reads
+                // were waited for about eight times, each issued a few instructions before; with the weights of three blocks early and
+                // the rest left to it, it read the inputs one block at a time behind lgkmcnt(0) (slower than the parent)
+                float4 xr[3] = {X(0), X(1), X(2)};
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int mm = 0; mm < 8; ++mm) {
+                    fma8(mm, xr[mm % 3], w1e[mm % 2][0], w1e[mm % 2][1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (mm + 2 < 8) { w1e[mm % 2][0] = W(mm + 2, 0); w1e[mm % 2][1] = W(mm + 2, 1); }
+                    if (mm + 3 < 8) xr[mm % 3] = X(mm + 3);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
+#pragma unroll
+                for (int mm = 0; mm < 8; ++mm) {
+                    fma8(mm, X(mm), W(mm, 0), W(mm, 1));
+                    if ((mm & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // at most four slices of operands live beside the 192 weight registers
+                }
             }
             const float v = sum4(a0 + a1), u = sum4(b0 + b1);
             // out_2 of this wave's 32 out_1 rows, off the chain: lane hp of every quad takes out_2 rows hp and hp + 4, the wave sums
@@ -555,7 +652,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
                 if ((tg & 63) < 4 && k < T::NO) lds[T::o_p2 + 4 * k + wv] = pz;
             }
         } else {
-            older_bn<T>(OlderOut1{}, lds, wreg, q + 1, tg);
+            older_bn_x<T>(OlderOut1{}, lds, wreg, xo, q + 1, tg);
         }
         SWN_BAR(7)
         if constexpr (grpA) {
@@ -629,6 +726,8 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
 #undef SWN_PHASE
 #undef SWN_BAR
 #undef SWN_WAIT_STAMP
+#undef SWN_PRE
+#undef SWN_BAR_KEEP
 #ifdef SWN_STAMP
     if ((tid == 0 || tid == 64 || tid == NG) && b == 0 && a.heads) {
         float* h = a.heads + (tid == 0 ? 0 : tid == 64 ? 30 : 10);
