@@ -631,6 +631,51 @@ int    swn_laplace_loss_backward(const swn_net_desc* d, const float* raw_dev, co
                                  const float* eps_dev, int batch, int tp, int skip, const float* g_nll_dev,
                                  const float* g_samples_dev, float* graw_dev, void* stream);
 
+/* ---- log-mel conditioning features from waveforms (melspec.py; csrc/swn_melspec.hip) --------------------------------------
+ * The definition, for a signal of len samples, len > n_fft / 2 (n_fft a multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT],
+ * 1 <= hop <= n_fft, hop need not divide n_fft; 1 <= n_mels <= SWN_LOGMEL_MAX_MELS; floor > 0):
+ *   frames     F = 1 + len / hop.  Frame f reads the padded positions p = f * hop - n_fft / 2 + j, j < n_fft; reflect padding
+ *              without repeating the edge sample: p < 0 -> -p, p >= len -> 2 (len - 1) - p
+ *              (torch.stft(center=True, pad_mode="reflect"))
+ *   window     periodic Hann, w[j] = 0.5 - 0.5 cos(2 pi j / n_fft)
+ *   amplitude  A[f][b] = | sum_j x[p] w[j] e^(-2 pi i j b / n_fft) |, b = 0 .. n_fft / 2: the amplitude, not the power
+ *   bank       HTK mel, mel(h) = 2595 log10(1 + h / 700), no area normalisation.  Points P_k = mel^-1 of n_mels + 2 equally
+ *              spaced values from mel(fmin) to mel(fmax), 0 <= fmin < fmax <= fs / 2;
+ *              W[m][b] = max(0, min((h_b - P_m) / (P_m+1 - P_m), (P_m+2 - h_b) / (P_m+2 - P_m+1))), h_b = b fs / n_fft,
+ *              evaluated in float64 on the host and stored as fp32; a filter's non-zero weights are one run of bins
+ *   mel        M[f][m] = sum_b W[m][b] A[f][b] over the filter's run in ascending b (one fmaf chain: the order is fixed)
+ *   output     ln(max(M, floor)) as fp32, or M itself when `linear` is 1, time-major: frame f at out + f * n_mels
+ * tables_dev (swn_logmel_table_floats floats): cos(2 pi m / n_fft) for m < n_fft, the window (n_fft), then the runs of
+ * weights of filter 0, 1, ... back to back, zero-filled to 2 (n_fft / 2 + 1) floats.  bank_host[n_mels] (HOST): the run of
+ * filter m as first bin | bins << 16.  fs, fmin and fmax exist only in how the caller built these two.
+ * Entry e (HOST table, at most SWN_LOGMEL_MAX_ENTRIES, carried in the launch arguments: no host copy, no synchronisation)
+ * is one row: wav_dev addresses the row's ABSOLUTE sample t0 and n_avail samples are there; len is the row's total length
+ * or -1 while it is not known yet; the call writes the frames [f0, f1), frame f at out_dev + (f - f0) * n_mels.  The kernel
+ * reads no sample outside [t0, t0 + n_avail).  A frame's values do not depend on the entry, the range or the call it is
+ * computed in: any partition of the frames, and any window that holds what a range reads, gives the same bits.
+ * work_dev: swn_logmel_work_bytes of scratch (the amplitudes of the call's frames).
+ * SWN_E_BADARG, found on the host before anything is launched, text in swn_last_error_detail: a null pointer, n_fft, hop,
+ * n_mels or floor out of range, linear not 0 / 1, n_entries out of range, a non-zero reserved field, a run outside the bins
+ * or more than 2 (n_fft / 2 + 1) weights, len <= n_fft / 2 or > 2^30, a window that leaves the signal, f0 < 0, f1 < f0,
+ * f1 > F, a frame whose span leaves the window, a frame that needs the reflected end (or any sample past the window) while
+ * len is -1.  Entries with f1 == f0 do nothing and may carry null pointers; a call without any frame launches nothing.
+ * The size queries return 0 for arguments the call refuses.  sizeof(swn_logmel_entry) == 40. */
+typedef struct swn_logmel_entry {
+    const float* wav_dev;      /* sample t0 of this row */
+    float*       out_dev;      /* frame f0 of this row's output, (f1 - f0) * n_mels floats */
+    int32_t t0;                /* absolute index of the first available sample, >= 0 */
+    int32_t n_avail;           /* samples available from t0 on */
+    int32_t len;               /* total length of the row, or -1: not known yet */
+    int32_t f0, f1;            /* frames to compute, 0 <= f0 <= f1 */
+    int32_t reserved;          /* 0 */
+} swn_logmel_entry;
+#define SWN_LOGMEL_MAX_MELS 128
+#define SWN_LOGMEL_MAX_ENTRIES 64
+size_t swn_logmel_table_floats(int n_fft, int n_mels);
+size_t swn_logmel_work_bytes(int n_fft, int hop, const swn_logmel_entry* entries_host, int n_entries);
+int    swn_logmel(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev, const int32_t* bank_host,
+                  const swn_logmel_entry* entries_host, int n_entries, float* work_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -66,6 +66,12 @@ class PostfilterEntry(ctypes.Structure):
                 ("flags", c_int32)]
 
 
+class LogMelEntry(ctypes.Structure):
+    """mirror of `swn_logmel_entry` (include/swn_hip.h): one row's share of a log-mel call."""
+    _fields_ = [("wav_dev", c_void_p), ("out_dev", c_void_p), ("t0", c_int32), ("n_avail", c_int32), ("len", c_int32),
+                ("f0", c_int32), ("f1", c_int32), ("reserved", c_int32)]
+
+
 ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
 DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
@@ -82,6 +88,7 @@ POSTFILTER_MAX_ORDER = 62                      # SWN_POSTFILTER_MAX_ORDER
 POSTFILTER_MAX_TAPS = 256                      # SWN_POSTFILTER_MAX_TAPS
 POSTFILTER_MULAW_ENTRIES = 256                 # SWN_POSTFILTER_MULAW_ENTRIES
 SPECTRAL_MAX_SIZES, SPECTRAL_MAX_FFT = 32, 2048   # SWN_SPECTRAL_MAX_SIZES, SWN_SPECTRAL_MAX_FFT
+LOGMEL_MAX_MELS, LOGMEL_MAX_ENTRIES = 128, 64     # SWN_LOGMEL_MAX_MELS, SWN_LOGMEL_MAX_ENTRIES
 
 
 def desc_from_cfg(cfg: NetConfig) -> NetDesc:
@@ -196,6 +203,10 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "swn_laplace_loss_backward": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    "swn_logmel_table_floats": (c_size_t, [c_int, c_int]),
+    "swn_logmel_work_bytes": (c_size_t, [c_int, c_int, POINTER(LogMelEntry), c_int]),
+    "swn_logmel": (c_int, [c_int, c_int, c_int, c_float, c_int, c_void_p, POINTER(c_int32), POINTER(LogMelEntry), c_int,
+                           c_void_p, c_void_p]),
 }
 
 

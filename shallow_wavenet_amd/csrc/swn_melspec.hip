@@ -1,0 +1,303 @@
+// Log-mel conditioning features from waveforms (melspec.py, swn_logmel of include/swn_hip.h), fp32 end to end.
+//
+// Definition (the contract; restated in include/swn_hip.h and melspec.py).  For a signal of len samples, len > n_fft / 2:
+//   frames      F = 1 + len / hop; frame f reads the padded positions p = f * hop - n_fft / 2 + j, j < n_fft, with reflect
+//               padding that does not repeat the edge sample: p < 0 -> -p, p >= len -> 2 (len - 1) - p
+//               (torch.stft(center=True, pad_mode="reflect"))
+//   window      periodic Hann, w[j] = 0.5 - 0.5 cos(2 pi j / n_fft)
+//   amplitude   A[f][b] = | sum_j x[p] w[j] e^(-2 pi i j b / n_fft) |, b = 0 .. n_fft / 2 (the amplitude, not the power)
+//   filter bank HTK mel (mel(h) = 2595 log10(1 + h / 700)), no area normalisation, n_mels + 2 points equally spaced in mel
+//               from fmin to fmax; W[m][b] = max(0, min(rising, falling)) at h_b = b fs / n_fft: evaluated in float64 on the
+//               host, stored as fp32, one run of consecutive bins per filter
+//   mel         M[f][m] = sum_b W[m][b] A[f][b] over the filter's run in ascending b (an fmaf chain: the order is fixed)
+//   output      ln(max(M, floor)), or M itself with `linear`, at out[frame][mel] (time-major)
+//
+// The transform is the dense DFT of each windowed frame on the exact-fp32 matrix instruction (v_mfma_f32_16x16x4_f32), as
+// in swn_spectral.hip, with the basis cos(2 pi m / n), m < n, indexed by (j * b) mod n; sin is the same table n / 4 entries
+// earlier (its sign does not matter to the amplitude).  What differs: the hop is arbitrary, so a block keeps the LDS image
+// of its tile as 16 separate windowed frames (pitch n + 2: the 16 rows x 2 k lanes of an operand read fall on 32 different
+// banks whatever the hop is) with the window folded into the image when it is filled, and each frame folded once
+// (y[j] +- y[j + n / 2] for the even / odd bins), which halves the product; one MFMA tile holds 16 frames of ONE
+// signal; the block owns all n / 2 + 1 bins of its frames (wave w takes the runs of 32 bins w, w + 4, ...), writes
+// their amplitudes to its own slice of the work buffer, and then applies the sparse triangular bank (weights in LDS), the
+// floor and the log.  No floating-point atomics, no reduction across lanes: row i of an MFMA result depends on row i of
+// the frame operand alone, the chain over j is the same in every row, and the mel chain runs over one frame's amplitudes,
+// so a frame's result does not depend on the tile, the row of the tile, the entry or the call it is computed in.
+//
+// Entries (swn_logmel_entry, host memory, checked before the launch and carried in the kernel arguments): a window
+// [t0, t0 + n_avail) onto each row's samples, the row's total length or -1 while unknown, and a frame range [f0, f1).
+// The kernel reads no sample outside the window; the rows of a tile past f1 are zero.
+#include <hip/hip_runtime.h>
+#include "swn_geom.hpp"
+#include "swn_mma.hpp"
+#include <cstdio>
+
+namespace {
+
+constexpr int LM_THREADS = 256;
+constexpr int LM_FR = 16;          // frames per tile = MFMA rows
+constexpr int LM_MAX_LEN = 1 << 30;   // 2 (len - 1) - p stays inside int
+
+struct LmEntry {
+    const float* wav;   // sample t0
+    float* out;         // frame f0
+    int t0, len, f0, f1, tile0;
+    int pad;
+};
+struct LmArgs {
+    LmEntry e[SWN_LOGMEL_MAX_ENTRIES];
+    int bank[SWN_LOGMEL_MAX_MELS];      // first bin | bins << 16 of each filter's run
+    unsigned short woff[SWN_LOGMEL_MAX_MELS];   // first weight of each run in the table
+    int n_entries, n, hop, n_mels, linear;
+    float floor_;
+};
+
+__host__ __device__ inline int lm_pitch(int n) { return n + 2; }
+__host__ __device__ inline int lm_amp_pitch(int n) { return (n / 2 + 1 + 3) & ~3; }
+__host__ __device__ inline size_t lm_lds_floats(int n) {
+    // 16 frames, cos table, weights (at most two filters cover a bin), weight offsets and runs
+    return (size_t)LM_FR * lm_pitch(n) + n + 2 * (n / 2 + 1) + 2 * SWN_LOGMEL_MAX_MELS;
+}
+
+int lm_fail(const char* what) {
+    swn_set_error_detail("swn_logmel", what);
+    return SWN_E_BADARG;
+}
+
+bool lm_sizes_ok(int n_fft, int n_mels) {
+    return n_fft >= 32 && n_fft <= SWN_SPECTRAL_MAX_FFT && n_fft % 32 == 0 && n_mels >= 1 && n_mels <= SWN_LOGMEL_MAX_MELS;
+}
+
+// the entry rules; *tiles receives the number of frame tiles of the call
+int lm_check_entries(int n, int hop, const swn_logmel_entry* en, int n_entries, long long* tiles) {
+    char msg[160];
+    if (!en) return lm_fail("entries_host is NULL");
+    if (n_entries < 1 || n_entries > SWN_LOGMEL_MAX_ENTRIES) return lm_fail("n_entries outside [1, SWN_LOGMEL_MAX_ENTRIES]");
+    if (hop < 1 || hop > n) return lm_fail("hop outside [1, n_fft]");
+    long long nt = 0;
+    for (int i = 0; i < n_entries; ++i) {
+        const swn_logmel_entry& e = en[i];
+        if (e.reserved != 0) { snprintf(msg, sizeof msg, "entry %d: reserved field is not 0", i); return lm_fail(msg); }
+        if (e.f0 < 0 || e.f1 < e.f0) { snprintf(msg, sizeof msg, "entry %d: frame range [%d, %d)", i, e.f0, e.f1); return lm_fail(msg); }
+        if (e.len != -1 && (e.len <= n / 2 || e.len > LM_MAX_LEN)) {
+            snprintf(msg, sizeof msg, "entry %d: length %d, need n_fft / 2 < len <= 2^30 (or -1 while unknown)", i, e.len);
+            return lm_fail(msg);
+        }
+        if (e.t0 < 0 || e.n_avail < 0 || (long long)e.t0 + e.n_avail > LM_MAX_LEN ||
+            (e.len != -1 && (long long)e.t0 + e.n_avail > e.len)) {
+            snprintf(msg, sizeof msg, "entry %d: window [%d, %d + %d) is not inside the signal", i, e.t0, e.t0, e.n_avail);
+            return lm_fail(msg);
+        }
+        if (e.f1 == e.f0) continue;
+        if (!e.wav_dev || !e.out_dev) { snprintf(msg, sizeof msg, "entry %d: null pointer", i); return lm_fail(msg); }
+        if (e.len != -1 && e.f1 > 1 + e.len / hop) {
+            snprintf(msg, sizeof msg, "entry %d: f1 = %d, a signal of %d samples has %d frames", i, e.f1, e.len, 1 + e.len / hop);
+            return lm_fail(msg);
+        }
+        // samples the range touches: frame f covers lo .. hi = f hop - n / 2 + (0 .. n - 1); the left reflection of a frame
+        // with lo < 0 reaches sample -lo, the right reflection of hi >= len comes back down to 2 (len - 1) - hi
+        const long long lo0 = (long long)e.f0 * hop - n / 2, hi1 = (long long)(e.f1 - 1) * hop - n / 2 + n - 1;
+        long long mn = lo0 < 0 ? 0 : lo0, mx = hi1;
+        if (lo0 < 0 && -lo0 > mx) mx = -lo0;
+        if (e.len == -1) {
+            if (mx >= (long long)e.t0 + e.n_avail) {
+                snprintf(msg, sizeof msg, "entry %d: frames [%d, %d) need sample %lld, the window ends at %lld and the total "
+                         "length is unknown (the reflected end needs it)", i, e.f0, e.f1, mx, (long long)e.t0 + e.n_avail);
+                return lm_fail(msg);
+            }
+        } else {
+            if (hi1 >= e.len) {
+                const long long back = 2LL * (e.len - 1) - hi1;
+                mn = back < mn ? back : mn;
+            }
+            if (mx > e.len - 1) mx = e.len - 1;
+        }
+        if (mn < e.t0 || mx >= (long long)e.t0 + e.n_avail) {
+            snprintf(msg, sizeof msg, "entry %d: frames [%d, %d) read samples [%lld, %lld], the window holds [%d, %lld)", i, e.f0,
+                     e.f1, mn, mx, e.t0, (long long)e.t0 + e.n_avail);
+            return lm_fail(msg);
+        }
+        nt += (e.f1 - e.f0 + LM_FR - 1) / LM_FR;
+    }
+    if (nt > (1 << 24)) return lm_fail("more than 2^24 frame tiles in one call");
+    *tiles = nt;
+    return SWN_OK;
+}
+
+__global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const LmArgs a, const float* __restrict__ tables, float* amp_work) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int n = a.n, hop = a.hop, pitch = lm_pitch(n), bins = n / 2 + 1, ap = lm_amp_pitch(n);
+    float* img = sm;                            // [16 frames][pitch]: windowed and folded, s then d
+    float* tab = img + LM_FR * pitch;           // cos(2 pi m / n)
+    float* wts = tab + n;                       // the filters' runs of weights, back to back
+    int* woff = reinterpret_cast<int*>(wts + 2 * bins);     // [n_mels] first weight of each run
+    int* sbank = woff + SWN_LOGMEL_MAX_MELS;                // [n_mels] first bin | bins << 16
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, kq = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    int ei = 0;
+    for (int i = 1; i < a.n_entries; ++i)       // the last entry whose first tile is not past this block (empty ones share
+        if (a.e[i].tile0 <= (int)blockIdx.x) ei = i;    // their tile0 with the next entry, which wins)
+    const LmEntry e = a.e[ei];
+    const int fbase = e.f0 + ((int)blockIdx.x - e.tile0) * LM_FR;    // first frame of the tile
+
+    for (int i = tid; i < n; i += LM_THREADS) tab[i] = tables[i];
+    for (int m = tid; m < a.n_mels; m += LM_THREADS) {
+        sbank[m] = a.bank[m];
+        woff[m] = a.woff[m];
+    }
+    const float* win = tables + n;
+    const float* wsrc = tables + 2 * n;
+    for (int i = tid; i < 2 * bins; i += LM_THREADS) wts[i] = wsrc[i];      // the table holds 2 bins floats, zero past the runs
+
+    // frame image, folded once: with y[j] = x[p(j)] w[j], X[b] = sum over j < n / 2 of (y[j] + (-1)^b y[j + n / 2]) e^(-2 pi i j b / n),
+    // so row fr holds s[j] = y[j] + y[j + n / 2] (even bins) and then d[j] = y[j] - y[j + n / 2] (odd bins), n / 2 each, and
+    // the product runs over half the frame.  2 x 2 independent loads in flight per thread
+    const int half = n / 2, total = LM_FR * half;
+    for (int e0 = tid; e0 < total; e0 += 2 * LM_THREADS) {
+        float y0[2], y1[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int el = e0 + u * LM_THREADS;
+            const int fr = el / half, j = el - fr * half, f = fbase + fr;
+            const bool in = el < total && f < e.f1;
+            int i0 = f * hop - half + j, i1 = i0 + half;
+            i0 = i0 < 0 ? -i0 : i0;                         // i1 >= 0; the left reflection stays below len (len > n / 2)
+            i0 = (e.len >= 0 && i0 >= e.len) ? 2 * (e.len - 1) - i0 : i0;
+            i1 = (e.len >= 0 && i1 >= e.len) ? 2 * (e.len - 1) - i1 : i1;
+            y0[u] = in ? e.wav[i0 - e.t0] * win[j] : 0.f;
+            y1[u] = in ? e.wav[i1 - e.t0] * win[j + half] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int el = e0 + u * LM_THREADS;
+            if (el < total) {
+                const int fr = el / half, j = el - fr * half;
+                img[fr * pitch + j] = y0[u] + y1[u];
+                img[fr * pitch + half + j] = y0[u] - y1[u];
+            }
+        }
+    }
+    __syncthreads();
+
+    // wave w: the runs of 32 bins w, w + 4, ... as a 16-bin tile of the even bins (operand s) and one of the odd bins
+    // (operand d); a bin past the last one reads valid table entries and is dropped
+    const int n_runs = (bins + 31) / 32, quarter = n / 4, steps = n / 8;
+    float* amp = amp_work + (size_t)blockIdx.x * LM_FR * ap;
+    const float* srow = img + c * pitch + kq;
+    const float* drow = srow + half;
+    for (int pp = w; pp < n_runs; pp += 4) {
+        const int b0 = 32 * pp + 2 * c, b1 = b0 + 1;
+        const int st0 = (4 * b0) % n, st1 = (4 * b1) % n;
+        int i0 = (kq * b0) % n, i1 = (kq * b1) % n;
+        swn_f32x4 acc[2][2] = {};                           // [even, odd][re, im]
+        for (int it = 0; it < steps; it += 2) {             // two k steps per trip: 12 LDS reads ahead of 8 MFMAs
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const float xs = srow[4 * (it + u)], xd = drow[4 * (it + u)];
+                int s0 = i0 - quarter; s0 += s0 < 0 ? n : 0;
+                int s1 = i1 - quarter; s1 += s1 < 0 ? n : 0;
+                const float c0 = tab[i0], n0 = tab[s0], c1 = tab[i1], n1 = tab[s1];     // cos, sin: the sign of Im is not needed
+                acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(xs, c0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(xs, n0, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(xd, c1, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(xd, n1, acc[1][1], 0, 0, 0);
+                i0 += st0; i0 -= i0 >= n ? n : 0;
+                i1 += st1; i1 -= i1 >= n ? n : 0;
+            }
+        }
+        // accumulator element i of lane (c, kq): frame 4 kq + i of the tile, bin 32 pp + 2 c (+ 1)
+#pragma unroll
+        for (int bt = 0; bt < 2; ++bt) {
+            const int b = b0 + bt;
+            if (b < bins) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float re = acc[bt][0][i], im = acc[bt][1][i];
+                    amp[(4 * kq + i) * ap + b] = sqrtf(re * re + im * im);
+                }
+            }
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    const int fr_n = e.f1 - fbase < LM_FR ? e.f1 - fbase : LM_FR;     // frames of this tile that exist (>= 1)
+    for (int o = tid; o < fr_n * a.n_mels; o += LM_THREADS) {
+        const int fr = o / a.n_mels, m = o - fr * a.n_mels;
+        const int start = sbank[m] & 0xffff, cnt = sbank[m] >> 16;
+        const float* ar = amp + fr * ap + start;
+        const float* wr = wts + woff[m];
+        float s = 0.f;
+        for (int k = 0; k < cnt; ++k) s = fmaf(wr[k], ar[k], s);
+        // the log in double, rounded once: logf lands up to 2 ulp from ln (measured at the floor), and a frame costs n_mels of these
+        e.out[(size_t)(fbase - e.f0 + fr) * a.n_mels + m] = a.linear ? s : (float)log((double)fmaxf(s, a.floor_));
+    }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------------------------ C ABI
+extern "C" size_t swn_logmel_table_floats(int n_fft, int n_mels) {
+    if (!lm_sizes_ok(n_fft, n_mels)) return 0;
+    return 2 * (size_t)n_fft + 2 * (size_t)(n_fft / 2 + 1);
+}
+
+extern "C" size_t swn_logmel_work_bytes(int n_fft, int hop, const swn_logmel_entry* entries_host, int n_entries) {
+    long long tiles = 0;
+    if (!lm_sizes_ok(n_fft, 1) || lm_check_entries(n_fft, hop, entries_host, n_entries, &tiles) != SWN_OK) return 0;
+    return (size_t)tiles * LM_FR * lm_amp_pitch(n_fft) * sizeof(float);
+}
+
+extern "C" int swn_logmel(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev,
+                          const int32_t* bank_host, const swn_logmel_entry* entries_host, int n_entries, float* work_dev,
+                          void* stream) {
+    if (n_fft < 32 || n_fft > SWN_SPECTRAL_MAX_FFT || n_fft % 32 != 0)
+        return lm_fail("n_fft is not a multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT]");
+    if (n_mels < 1 || n_mels > SWN_LOGMEL_MAX_MELS) return lm_fail("n_mels outside [1, SWN_LOGMEL_MAX_MELS]");
+    if (!(floor > 0.f) || !(floor < 3.0e38f)) return lm_fail("floor must be a finite number > 0");
+    if (linear != 0 && linear != 1) return lm_fail("linear must be 0 or 1");
+    long long tiles = 0;
+    const int rc = lm_check_entries(n_fft, hop, entries_host, n_entries, &tiles);
+    if (rc != SWN_OK) return rc;
+    if (!bank_host) return lm_fail("bank_host is NULL");
+    const int bins = n_fft / 2 + 1;
+    LmArgs a;
+    int nnz = 0;
+    for (int m = 0; m < n_mels; ++m) {
+        const int start = bank_host[m] & 0xffff, cnt = (int)((unsigned)bank_host[m] >> 16);
+        if (bank_host[m] < 0 || cnt < 1 || start + cnt > bins) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "filter %d: run of %d bins from bin %d, the transform has %d", m, cnt, start, bins);
+            return lm_fail(msg);
+        }
+        a.woff[m] = (unsigned short)(nnz < 0xffff ? nnz : 0xffff);      // nnz <= 2 bins is checked below
+        nnz += cnt;
+        a.bank[m] = bank_host[m];
+    }
+    if (nnz > 2 * bins) return lm_fail("the filter runs hold more than 2 (n_fft / 2 + 1) weights");
+    for (int m = n_mels; m < SWN_LOGMEL_MAX_MELS; ++m) a.bank[m] = a.woff[m] = 0;
+    if (tiles == 0) return SWN_OK;                          // no frame in any entry
+    if (!tables_dev || !work_dev) return lm_fail("null pointer");
+    int t = 0;
+    for (int i = 0; i < SWN_LOGMEL_MAX_ENTRIES; ++i) {
+        LmEntry& o = a.e[i];
+        if (i < n_entries) {
+            const swn_logmel_entry& e = entries_host[i];
+            o.wav = e.wav_dev; o.out = e.out_dev; o.t0 = e.t0; o.len = e.len; o.f0 = e.f0; o.f1 = e.f1; o.tile0 = t; o.pad = 0;
+            t += (e.f1 - e.f0 + LM_FR - 1) / LM_FR;
+        } else {
+            o.wav = nullptr; o.out = nullptr; o.t0 = o.len = o.f0 = o.f1 = o.pad = 0; o.tile0 = t;
+        }
+    }
+    a.n_entries = n_entries; a.n = n_fft; a.hop = hop; a.n_mels = n_mels; a.linear = linear; a.floor_ = floor;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    (void)hipGetLastError();
+    const size_t lds = lm_lds_floats(n_fft) * sizeof(float);
+    // dynamic LDS from 64 KB on: set on every call (the attribute is per device)
+    if (lds >= 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return swn_launch_status("swn_logmel (LDS size)");
+    hipLaunchKernelGGL(logmel_kernel, dim3((unsigned)tiles), dim3(LM_THREADS), lds, st, a, tables_dev, work_dev);
+    return swn_launch_status("swn_logmel");
+}

@@ -1,0 +1,160 @@
+"""Stage 1 of run.sh for the log-mel feature type: every waveform of a directory or list is read, optionally high-pass filtered
+(`dsp.low_cut_filter`, the filtered wav written under `--wavdir`), turned into log-mel features on the device in batches
+(`melspec.LogMelExtractor`, csrc/swn_melspec.hip; the definition is in melspec.py) and written as dataset `--string_path` of
+`<hdf5dir>/<name>.h5` - or `<name>.npz`, the side format of featio.py, where h5py is absent.  The flag names are those of the
+reference's stage-1 command that make sense here; `--feature_type world` is the WORLD / SPTK analysis, which needs pyworld and
+pysptk (dsp.extract_features raises the ImportError that says so).
+
+Frames: F = 1 + len // hop with hop = round(fs * shiftms / 1000) unless `--hop` is given - not WORLD's count when 5 ms is not an
+integer number of samples; the training drivers' validate_length trims features and waveform to each other.  The statistics
+of these features (`calc_stats --string_path /feat_logmel`) initialise scale_in as usual; the noise-shaping stages need
+mel-cepstrum statistics and do not apply to this feature type."""
+from __future__ import annotations
+
+import argparse
+import logging
+import multiprocessing as mp
+import os
+import sys
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import dsp, featio
+from .decode_driver import write_wav_pcm16
+from .noise_shaping_driver import list_waveforms, read_wav_fs
+
+FS, SHIFTMS, FFTL, HIGHPASS_CUTOFF = 22050, 5.0, 1024, 70      # the reference's stage-1 defaults
+BATCH = 16                                                     # utterances per device call
+MAX_JOBS = 16                                                  # worker processes that open the device
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="conditioning features from waveforms (log-mel on the device)")
+    p.add_argument("--expdir", default=None, help="experiment directory: the log goes to <expdir>/feature_extract.log")
+    p.add_argument("--waveforms", default=None, help="directory or list file of the input wav files")
+    p.add_argument("--hdf5dir", default=None, help="directory of the feature files")
+    p.add_argument("--wavdir", default=None, help="directory of the high-pass filtered wav files (none: not written)")
+    p.add_argument("--fs", default=FS, type=int, help="sampling frequency")
+    p.add_argument("--shiftms", default=SHIFTMS, type=float, help="frame shift in msec (the hop, unless --hop is given)")
+    p.add_argument("--fftl", default=FFTL, type=int, help="FFT length: a multiple of 32")
+    p.add_argument("--highpass_cutoff", default=HIGHPASS_CUTOFF, type=int, help="cut-off of the high-pass filter, 0: none")
+    p.add_argument("--n_jobs", default=1, type=int, help=f"number of worker processes (at most {MAX_JOBS})")
+    p.add_argument("--verbose", default=1, type=int, help="log level")
+    p.add_argument("--feature_type", default="logmel", choices=("logmel", "world"), help="not a reference flag")
+    p.add_argument("--n_mels", default=80, type=int, help="mel filters (logmel; not a reference flag)")
+    p.add_argument("--fmin", default=0.0, type=float, help="lowest filter edge in Hz (logmel; not a reference flag)")
+    p.add_argument("--fmax", default=None, type=float, help="highest filter edge in Hz, default fs / 2 (logmel; not a reference flag)")
+    p.add_argument("--hop", default=None, type=int, help="hop in samples, default round(fs * shiftms / 1000) (logmel; not a reference flag)")
+    p.add_argument("--floor", default=1e-5, type=float, help="floor of the mel amplitude under the log (logmel; not a reference flag)")
+    p.add_argument("--string_path", default="/feat_logmel", help="dataset name in the feature files (not a reference flag)")
+    return p
+
+
+def hop_of(args) -> int:
+    return int(args.hop) if args.hop is not None else int(round(args.fs * args.shiftms / 1000.0))
+
+
+def feature_path(hdf5dir: str, wav_name: str) -> str:
+    """<hdf5dir>/<name>.h5 where h5py is importable, else the .npz side format"""
+    try:
+        import h5py  # noqa: F401
+        ext = ".h5"
+    except ImportError:
+        ext = ".npz"
+    return os.path.join(hdf5dir, os.path.splitext(os.path.basename(wav_name))[0] + ext)
+
+
+def load_waveform(name: str, args) -> np.ndarray:
+    """the utterance as the features see it: mono float64, high-pass filtered (and written to --wavdir) when the cut-off is not 0.
+    ValueError when the file's sampling frequency is not --fs (the mel scale, the hop and the filter would all be wrong)."""
+    x, fs = read_wav_fs(name)
+    if fs != args.fs:
+        raise ValueError(f"{name}: sampling frequency {fs} does not match --fs {args.fs}")
+    if x.ndim > 1:
+        x = x[:, 0]
+    if args.highpass_cutoff != 0:
+        x = dsp.low_cut_filter(x, args.fs, cutoff=args.highpass_cutoff)
+        if args.wavdir:
+            os.makedirs(args.wavdir, exist_ok=True)
+            write_wav_pcm16(os.path.join(args.wavdir, os.path.basename(name)), np.clip(x, -1.0, 1.0), args.fs)
+    return x
+
+
+def extract_files(files: Sequence[str], args, device="cuda") -> int:
+    if args.feature_type == "world":
+        for name in files:
+            feats = dsp.extract_features(load_waveform(name, args), args.fs, shiftms=args.shiftms, fftl=args.fftl)
+            featio.write_dataset(feature_path(args.hdf5dir, name), args.string_path, feats)
+        return 0
+    from .melspec import LogMelExtractor
+    ext = LogMelExtractor(args.fs, args.fftl, hop_of(args), args.n_mels, args.fmin, args.fmax, args.floor, device)
+    rc = 0
+    for i in range(0, len(files), BATCH):
+        names: List[str] = []
+        waves: List[np.ndarray] = []
+        for name in files[i:i + BATCH]:
+            try:
+                x = load_waveform(name, args)
+            except ValueError as e:
+                logging.error("%s", e)
+                rc = 1
+                continue
+            if x.shape[0] <= args.fftl // 2:
+                logging.error("%s: %d samples, --fftl %d needs more than %d", name, x.shape[0], args.fftl, args.fftl // 2)
+                rc = 1
+                continue
+            names.append(name)
+            waves.append(x.astype(np.float32))
+        if not names:
+            continue
+        feats = ext(waves).cpu().numpy()
+        for name, x, f in zip(names, waves, feats):
+            out = feature_path(args.hdf5dir, name)
+            featio.write_dataset(out, args.string_path, f[:ext.frame_count(x.shape[0])])
+            logging.info("%s -> %s %s", name, out, (ext.frame_count(x.shape[0]), args.n_mels))
+    return rc
+
+
+def _job(files, args) -> None:
+    sys.exit(extract_files(files, args))
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    args = build_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO if args.verbose > 0 else logging.WARN, format="%(asctime)s %(message)s")
+    if not args.waveforms or not args.hdf5dir:
+        logging.error("--waveforms and --hdf5dir are required")
+        return 2
+    log_file = None
+    if args.expdir:
+        os.makedirs(args.expdir, exist_ok=True)
+        log_file = logging.FileHandler(os.path.join(args.expdir, "feature_extract.log"))
+        logging.getLogger().addHandler(log_file)
+    try:
+        return _run(args)
+    finally:
+        if log_file is not None:
+            logging.getLogger().removeHandler(log_file)
+            log_file.close()
+
+
+def _run(args) -> int:
+    files = list_waveforms(args.waveforms)
+    os.makedirs(args.hdf5dir, exist_ok=True)
+    n_jobs = min(args.n_jobs, MAX_JOBS)
+    if n_jobs <= 1 or len(files) <= 1:
+        return extract_files(files, args)
+    ctx = mp.get_context("spawn")
+    parts = [list(p) for p in np.array_split(np.asarray(files, dtype=object), n_jobs) if len(p)]
+    procs = [ctx.Process(target=_job, args=(p, args)) for p in parts]
+    for pr in procs:
+        pr.start()
+    for pr in procs:
+        pr.join()
+    # a worker that raised or was killed has a non-zero exit code too
+    return max(abs(pr.exitcode) for pr in procs)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

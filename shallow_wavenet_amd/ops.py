@@ -41,6 +41,7 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.laplace_head_backward(raw, gmu?, gb?, glogb?, ga?, gb_clip?, glogb_clip?, desc) -> grad_raw
     torch.ops.swn.spectral_loss(samples, targets, tables, sizes, keep_state) -> (l1, lsd, state)
     torch.ops.swn.spectral_loss_backward(grad_l1, state, tables, sizes, length) -> grad_samples
+    torch.ops.swn.logmel(wav, tables, bank, t0s, n_avails, lens, f0s, f1s, n_fft, hop, floor, linear) -> features
     torch.ops.swn.laplace_loss(raw, ctx?, target, eps, desc, skip) -> (nll, err, samples, targets, stats)
     torch.ops.swn.laplace_loss_backward(raw, ctx?, target, eps, g_nll, g_samples?, desc, skip) -> grad_raw
 """
@@ -1353,10 +1354,72 @@ class LaplaceLossFunction(torch.autograd.Function):
         return graw, None, None, None, None, None
 
 
+# ------------------------------------------------------------------------------------------ log-mel features
+def _logmel_check(n_fft: int, hop: int, n_mels: int, floor: float) -> None:
+    """the size rules of swn_logmel as messages (the library itself answers SWN_E_BADARG)."""
+    if n_fft % 32 != 0 or not 32 <= n_fft <= _lib.SPECTRAL_MAX_FFT:
+        raise RuntimeError(f"logmel: n_fft {n_fft} is not a multiple of 32 in [32, {_lib.SPECTRAL_MAX_FFT}]")
+    if not 1 <= hop <= n_fft:
+        raise RuntimeError(f"logmel: hop {hop} outside [1, n_fft = {n_fft}]")
+    if not 1 <= n_mels <= _lib.LOGMEL_MAX_MELS:
+        raise RuntimeError(f"logmel: n_mels {n_mels} outside [1, {_lib.LOGMEL_MAX_MELS}]")
+    if not floor > 0.0:
+        raise RuntimeError(f"logmel: floor {floor} must be > 0")
+
+
+def logmel_impl(wav: torch.Tensor, tables: torch.Tensor, bank: List[int], t0s: List[int], n_avails: List[int],
+                lens: List[int], f0s: List[int], f1s: List[int], n_fft: int, hop: int, floor: float,
+                linear: bool) -> torch.Tensor:
+    """wav (R, S): row r holds the samples [t0s[r], t0s[r] + n_avails[r]) of signal r, whose total length is lens[r] (-1: not
+    known yet) -> (R, max(f1 - f0), n_mels) log-mel (or, with linear, mel) amplitudes of the frames [f0s[r], f1s[r]) of each
+    row, zero past a row's own range (swn_logmel; the definition is in melspec.py).  tables / bank: melspec.tables()."""
+    Lb = _lib.lib()
+    _need_cuda(wav, "the waveforms")
+    dev = wav.device
+    n_mels = len(bank)
+    _logmel_check(n_fft, hop, n_mels, floor)
+    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
+        raise RuntimeError(f"logmel needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
+    R, S = wav.shape
+    if not (len(t0s) == len(n_avails) == len(lens) == len(f0s) == len(f1s) == R):
+        raise RuntimeError("logmel: t0s, n_avails, lens, f0s and f1s must have one entry per row")
+    if any(not 0 <= na <= S for na in n_avails):
+        raise RuntimeError(f"logmel: a row has more samples available than the buffer's {S} columns")
+    need = Lb.swn_logmel_table_floats(n_fft, n_mels)
+    if tables.device != dev or tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != need:
+        raise RuntimeError(f"logmel: tables must be {need} contiguous fp32 values on the device of the waveforms")
+    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
+    out = torch.zeros((R, fmax, n_mels), dtype=torch.float32, device=dev)
+    bank_c = (ctypes.c_int32 * n_mels)(*[int(b) for b in bank])
+    esz, osz = wav.element_size() * S, out.element_size() * fmax * n_mels
+    for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
+        r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
+        table = (_lib.LogMelEntry * (r1 - r0))(*[
+            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
+                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
+            for r in range(r0, r1)])
+        nb = Lb.swn_logmel_work_bytes(n_fft, hop, table, r1 - r0)
+        work = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=dev)
+        with _on(dev):
+            _lib.check(Lb.swn_logmel(n_fft, hop, n_mels, float(floor), int(bool(linear)), _ptr(tables), bank_c, table, r1 - r0,
+                                     _ptr(work), _stream(dev)), "logmel")
+    return out
+
+
+logmel = custom_op("swn::logmel", mutates_args=())(logmel_impl)
+
+
+@logmel.register_fake
+def _(wav, tables, bank, t0s, n_avails, lens, f0s, f1s, n_fft, hop, floor, linear):
+    _logmel_check(n_fft, hop, len(bank), floor)
+    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
+    return wav.new_empty((wav.shape[0], fmax, len(bank)), dtype=torch.float32)
+
+
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
             "pack_decode_w16", "decode_w16", "decode_chunk_w16", "decode_pool_chunk_w16",
             "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
             "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
-            "laplace_loss", "laplace_loss_backward")
+            "laplace_loss", "laplace_loss_backward", "logmel")
