@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <hip/hip_bf16.h>
 #include "swn_geom.hpp"
+#include "swn_train_internal.hpp"
 
 namespace {
 
@@ -854,8 +855,6 @@ __global__ void rowsT_to_bf16_kernel(const float* __restrict__ src, int ld, int 
     dst[e] = c < cols ? f2bf(src[(size_t)r * ld + c]) : (unsigned short)0;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // ---- interface to csrc/swn_train.hip ------------------------------------------------------------------------------------
@@ -869,22 +868,48 @@ bool swn_bl6_bwd_supported(const SwnGeom& g, int B, long Tp, int n_frames) {
 
 constexpr size_t IMG_WSK = 8 * 12 * 1024, IMG_W1 = 8 * 4 * 1024, IMG_W2T = 8 * 1024;     // fragment images, bytes
 
-size_t swn_bl6_bwd_scratch_bytes(const SwnGeom& g, int B, long Tp) {
-    const size_t row = al256((size_t)B * Tp * 256);              // one [B][Tp][128] bf16 or [B][Tp][64] fp32 buffer
-    return al256((size_t)g.L * LDS_REC) + al256((size_t)(g.L + 1) * LDS_DG) + IMG_WSK + 2 * IMG_W1 + IMG_W2T +
-           (size_t)(g.L + 5) * row;
+// swn_bl6_bwd_stack's scratch: byte offsets, every section 256-byte aligned.  row: one [B][Tp][128] bf16 or [B][Tp][64] fp32 buffer
+namespace {
+struct Bl6BwdScratch {
+    size_t wrec, wdg;                  // LDS images of the layer matrices: recompute, data gradient
+    size_t iwsk, iw1, iw1t, iw2t;      // fragment images of the head matrices
+    size_t E[2], dsk, s1, do1;         // rows: fp32 carries of the layer chain; d skip, relu(skip), d out_1 (bf16)
+    size_t da;                         // L rows, contiguous: d a of every layer
+    size_t total;                      // without dropout
+    size_t dgx16, wxt, drop_total;     // dropout mode: d gx of every layer [L][B][Tp][128] bf16 | transposed in_x image [A0x][L*128] bf16
+};
+Bl6BwdScratch bl6_bwd_scratch(const SwnGeom& g, int B, long Tp) {
+    Bl6BwdScratch o;
+    const size_t row = swn_al256((size_t)B * Tp * 256);
+    o.wrec = 0;
+    o.wdg = o.wrec + swn_al256((size_t)g.L * LDS_REC);
+    o.iwsk = o.wdg + swn_al256((size_t)(g.L + 1) * LDS_DG);
+    o.iw1 = o.iwsk + IMG_WSK;
+    o.iw1t = o.iw1 + IMG_W1;
+    o.iw2t = o.iw1t + IMG_W1;
+    o.E[0] = o.iw2t + IMG_W2T;
+    o.E[1] = o.E[0] + row;
+    o.dsk = o.E[1] + row;
+    o.s1 = o.dsk + row;
+    o.do1 = o.s1 + row;
+    o.da = o.do1 + row;
+    o.total = o.da + (size_t)g.L * row;
+    o.dgx16 = o.total;
+    o.wxt = o.dgx16 + swn_al256((size_t)g.L * B * Tp * 256);
+    o.drop_total = o.wxt + swn_al256((size_t)swn_a0x(&g) * g.L * 128 * 2);
+    return o;
 }
-// dropout mode: + d gx of every layer [L][B][Tp][128] bf16 and the transposed in_x image [A0x][L*128] bf16
-size_t swn_bl6_bwd_drop_scratch_bytes(const SwnGeom& g, int B, long Tp) {
-    return swn_bl6_bwd_scratch_bytes(g, B, Tp) + al256((size_t)g.L * B * Tp * 256) + al256((size_t)swn_a0x(&g) * g.L * 128 * 2);
+}  // namespace
+
+size_t swn_bl6_bwd_scratch_bytes(const SwnGeom& g, int B, long Tp, bool drop) {
+    const Bl6BwdScratch o = bl6_bwd_scratch(g, B, Tp);
+    return drop ? o.drop_total : o.total;
 }
-int swn_bf16g_plain(const unsigned short* A, int M, const unsigned short* src, size_t blk_stride, size_t src_bytes, int KB, int nblk,
-                    int Tp, int B, const float* bias, unsigned short* out_bf, int out_ld, float* out_f, int NO, hipStream_t st);
 
 // The whole stack backward behind d raw: head (out_2, out_1, skip), the gated layers, the input layer.  Fills dcond and every
 // sample-rate section of gpacked (zeroed by the caller): w2 b2 w1 b1 wsk bsk wd bd bx wup cb cv cc.
 // Dropout mode (gx16 != null: the forward was swn_bl6_drop_forward; cond and dcond are not used, scratch holds
-// swn_bl6_bwd_drop_scratch_bytes): fills wx and bxr instead of bx / wup, and dxm16 [B][Tx][A0x] bf16 = in_x^T d gx, the
+// swn_bl6_bwd_scratch_bytes(.., true)): fills wx and bxr instead of bx / wup, and dxm16 [B][Tx][A0x] bf16 = in_x^T d gx, the
 // gradient wrt the masked conditioning (the caller's xm backward turns it into d C, g w_up, g b_up).
 int swn_bl6_bwd_stack(const SwnGeom& g, const SwnLayout& y, const float* packed, const float* cond, const float* audio,
                       const void* hs_bf16, const float* grad_out, float* dcond, float* gpacked, void* scratch, int B, int n_frames,
@@ -892,23 +917,22 @@ int swn_bl6_bwd_stack(const SwnGeom& g, const SwnLayout& y, const float* packed,
     BwArgs a;
     a.P = packed; a.y = y; a.cond = cond; a.audio = audio; a.hs = reinterpret_cast<const unsigned short*>(hs_bf16);
     unsigned char* p = reinterpret_cast<unsigned char*>(scratch);
-    const size_t row = al256((size_t)B * Tp * 256);
-    unsigned short* wrec = reinterpret_cast<unsigned short*>(p); p += al256((size_t)g.L * LDS_REC);
-    unsigned short* wdg = reinterpret_cast<unsigned short*>(p);  p += al256((size_t)(g.L + 1) * LDS_DG);
-    unsigned short* iwsk = reinterpret_cast<unsigned short*>(p); p += IMG_WSK;
-    unsigned short* iw1 = reinterpret_cast<unsigned short*>(p);  p += IMG_W1;
-    unsigned short* iw1t = reinterpret_cast<unsigned short*>(p); p += IMG_W1;
-    unsigned short* iw2t = reinterpret_cast<unsigned short*>(p); p += IMG_W2T;
-    a.E[0] = reinterpret_cast<float*>(p); p += row;
-    a.E[1] = reinterpret_cast<float*>(p); p += row;
-    unsigned short* dsk = reinterpret_cast<unsigned short*>(p); p += row;
-    unsigned short* s1 = reinterpret_cast<unsigned short*>(p);  p += row;
-    unsigned short* do1 = reinterpret_cast<unsigned short*>(p); p += row;
+    const Bl6BwdScratch lo = bl6_bwd_scratch(g, B, Tp);
+    unsigned short* wrec = reinterpret_cast<unsigned short*>(p + lo.wrec);
+    unsigned short* wdg = reinterpret_cast<unsigned short*>(p + lo.wdg);
+    unsigned short* iwsk = reinterpret_cast<unsigned short*>(p + lo.iwsk);
+    unsigned short* iw1 = reinterpret_cast<unsigned short*>(p + lo.iw1);
+    unsigned short* iw1t = reinterpret_cast<unsigned short*>(p + lo.iw1t);
+    unsigned short* iw2t = reinterpret_cast<unsigned short*>(p + lo.iw2t);
+    a.E[0] = reinterpret_cast<float*>(p + lo.E[0]);
+    a.E[1] = reinterpret_cast<float*>(p + lo.E[1]);
+    unsigned short* dsk = reinterpret_cast<unsigned short*>(p + lo.dsk);
+    unsigned short* s1 = reinterpret_cast<unsigned short*>(p + lo.s1);
+    unsigned short* do1 = reinterpret_cast<unsigned short*>(p + lo.do1);
     a.dsk = dsk;
-    a.da = reinterpret_cast<unsigned short*>(p);                 // L buffers of B*Tp*256 bytes, contiguous (no padding)
-    p = reinterpret_cast<unsigned char*>(scratch) + swn_bl6_bwd_scratch_bytes(g, B, Tp);
-    a.gx16 = gx16; a.dgx16 = gx16 ? reinterpret_cast<unsigned short*>(p) : nullptr;
-    unsigned short* wxt = reinterpret_cast<unsigned short*>(p + al256((size_t)g.L * B * Tp * 256));      // dropout mode only
+    a.da = reinterpret_cast<unsigned short*>(p + lo.da);        // L buffers of B*Tp*256 bytes, contiguous (no padding)
+    a.gx16 = gx16; a.dgx16 = gx16 ? reinterpret_cast<unsigned short*>(p + lo.dgx16) : nullptr;
+    unsigned short* wxt = reinterpret_cast<unsigned short*>(p + lo.wxt);      // dropout mode only
     a.wrec = wrec; a.wdg = wdg;
     a.dcond = dcond; a.gP = gpacked;
     a.B = B; a.Tf = n_frames; a.Tp = (int)Tp; a.U = g.U; a.N = g.N; a.L = g.L; a.coff = g.seg;

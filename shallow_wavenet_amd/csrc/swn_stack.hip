@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
 #include "swn_mma.hpp"
+#include "swn_train_internal.hpp"
 
 namespace {
 
@@ -231,8 +232,6 @@ __global__ __launch_bounds__(256) void gemm_wx_kernel(const float* __restrict__ 
         }
 }
 
-size_t r64(size_t x) { return (x + 63) & ~(size_t)63; }
-
 // raw (B, NO, Tp) -> time-major mu / b / logb / a (+ clipped copies); one thread per (b, t)
 __global__ __launch_bounds__(256) void laplace_head_kernel(const float* __restrict__ raw, int Tp, int seg, int lpc,
                                                            float* mu, float* bsc, float* logb, float* acf,
@@ -266,13 +265,11 @@ extern "C" int swn_device_count(void) {
     return n;
 }
 
-// work = hidden states (only when the caller does not pass hs) + skip activations + out_1 activations
+// work = hidden states (only when the caller does not pass hs) + skip activations + out_1 activations (SwnFwdLayout)
 extern "C" size_t swn_forward_work_floats(const swn_net_desc* d, int batch, int n_frames) {
     SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1) return 0;
-    const long T = (long)n_frames * g.U;
-    const long Tp = g.kind == SWN_KIND_SOFTMAX ? T - 1 : T - 2 * g.seg + 1;
-    if (Tp < 1) return 0;
-    return r64((size_t)batch * (g.L + 1) * g.H * Tp) + r64((size_t)batch * g.S * Tp) + r64((size_t)batch * g.O1 * Tp);
+    const SwnTrainLen n = swn_train_len(g, n_frames);
+    return n.Tp < 1 ? 0 : swn_fwd_layout(g, batch, n.Tp).total;
 }
 
 namespace {
@@ -326,36 +323,6 @@ __global__ __launch_bounds__(256) void xm_fwd16_kernel(const float* __restrict__
 
 }  // namespace
 
-// relu(skip), relu(out_1) from the hidden states in `work` through the contraction kernels of the training mode (csrc/swn_train.hip)
-int swn_train_head_acts(const SwnGeom& g, const float* packed, float* work, int batch, long Tp, hipStream_t st);
-// gated layers of the dropout-mode forward in the mixed-precision mode (csrc/swn_train.hip)
-int swn_train_layers_forward_drop(const SwnGeom& g, const SwnLayout& y, const float* packed, const void* audio, const float* gx,
-                                  const float* const* drop_h, float* hs, float* a_scr, float* hmask, int B, int n_frames, int Tp,
-                                  hipStream_t st);
-// sample-rate in_x of every layer over the masked conditioning (csrc/swn_train.hip: generic time GEMM)
-int swn_train_inx_forward(const SwnGeom& g, const SwnLayout& y, const float* packed, const float* xm, float* gx,
-                          int B, int Tx, int Tp, hipStream_t st, unsigned short* wx16 = nullptr, bool g4 = false);
-// GEMM-stack geometries, mixed-precision mode: the dropout-mode forward on the bf16 time-major stack (csrc/swn_stack_bf16g.hip)
-int swn_bf16g_geom(const swn_net_desc* d, SwnGeom* g);
-size_t swn_bf16g_weight_bytes(const SwnGeom& g);
-int swn_bf16g_pack(const SwnGeom& g, const float* packed, void* wbf, hipStream_t st);
-size_t swn_bf16g_work_bytes(const SwnGeom& g, int batch, long Tp);
-int swn_bf16g_expand(const SwnGeom& g, const void* work, int batch, long Tp, float* fwd_work, bool hs_only, hipStream_t st);
-int swn_bf16g_forward(const SwnGeom& g, const float* packed, const void* wbf, const float* cond, const void* audio,
-                      int batch, int n_frames, void* work, float* out, hipStream_t st, float* a_keep,
-                      const float* gx, const float* const* drop_h, unsigned short* hm16);
-// BL6 class, mixed-precision mode, aux_drop the only mask that acts: the fused path (csrc/swn_stack_bf16.hip)
-int swn_bl6_drop_forward(const SwnGeom& g, const float* packed, const float* C, const float* audio, const float* drop_x,
-                         int batch, int n_frames, void* work, float* out, hipStream_t st);
-
-namespace {
-
-// does the dropout-mode forward of the mixed-precision mode run on the bf16 time-major GEMM stack?  (the geometry class of
-// csrc/swn_stack_bf16g.hip, its 32-bit operand offsets, a sequence long enough for the bf16-copy contractions)
-bool drop_g16(const swn_net_desc* d, int batch, long Tp) { return swn_drop_g16(d, batch, Tp); }
-
-}  // namespace
-
 bool swn_drop_g16(const swn_net_desc* d, int batch, long Tp) {
     SwnGeom g;
     if (swn_bf16g_geom(d, &g) != SWN_OK || Tp < 256) return false;
@@ -376,8 +343,8 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
     if (!packed || (!drop && !cond) || (drop && (!fe_work || !drop_h)) || !audio || !work || !out || batch < 1 ||
         batch > 65535 || n_frames < 1) return SWN_E_BADARG;
     swn_make_layout(&a.g, &a.y);
-    const long T = (long)n_frames * g.U;
-    const long Tp = g.kind == SWN_KIND_SOFTMAX ? T - 1 : T - 2 * g.seg + 1;
+    const SwnTrainLen n = swn_train_len(g, n_frames);
+    const long Tp = n.Tp;
     if (Tp < 1) return SWN_E_BADARG;
     {   // the tiled kernels address one utterance's operands with 32-bit byte offsets
         size_t widest = (size_t)(g.L + 1) * g.H;
@@ -390,58 +357,50 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
     }
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();   // drop stale errors of earlier runtime calls; only our launches are reported
-    if (drop && !hs && swn_call_mode() == SWN_PRECISION_BF16 && swn_bl6_drop_supported(g, batch, Tp, n_frames, drop_h)) {
-        size_t fe_off = (size_t)g.n_aux;                         // frame-rate activations: scaled | conv_aux layers
-        for (int i = 0; i + 1 < g.auxl; ++i) fe_off += g.aux_cout[i];
-        return swn_bl6_drop_forward(g, packed, fe_work + fe_off * (size_t)batch * n_frames, reinterpret_cast<const float*>(audio),
-                                    drop_x, batch, n_frames, work, out, st);
-    }
-    const size_t hs_floats = r64((size_t)batch * (g.L + 1) * g.H * Tp);
-    float* hbuf = hs ? hs : work;
-    float* skipb = work + hs_floats;
-    float* o1b = skipb + r64((size_t)batch * g.S * Tp);
+    const bool bf16 = swn_call_mode() == SWN_PRECISION_BF16;
+    const float* C = drop ? fe_work + swn_fe_layout(g, batch, n_frames).C : nullptr;      // the last conv_aux activation
+    if (drop && !hs && bf16 && swn_bl6_drop_supported(g, batch, Tp, n_frames, drop_h))
+        return swn_bl6_drop_forward(g, packed, C, reinterpret_cast<const float*>(audio), drop_x, batch, n_frames, work, out, st);
+    // the predicates that pick a section's use, each evaluated here once
+    const bool g16 = drop && swn_drop_g16(d, batch, Tp);                 // the layout ends with the GEMM stack's sections
+    const bool inx16 = drop && bf16 && swn_drop_inx16(&g, Tp);            // bf16 copies of the in_x operands
+    const bool stack16 = g16 && inx16 && !hs;                            // ... and the forward runs on the GEMM stack
+    const bool fwd16 = drop && bf16 && swn_drop_bf16_forward(&g);         // bf16-operand layers, pre-activations kept
+    const SwnFwdLayout lo = drop ? swn_fwd_drop_layout(g, batch, n, g16, g16 ? swn_bf16g_weight_bytes(g) : 0) : swn_fwd_layout(g, batch, Tp);
+    float* hbuf = hs ? hs : work + lo.hs;
+    float* skipb = work + lo.s1;
+    float* o1b = work + lo.r1;
     a.P = packed; a.cond = cond; a.audio = audio; a.hs = hbuf; a.B = batch; a.Tf = n_frames; a.Tp = (int)Tp;
-    a.coff = g.kind == SWN_KIND_SOFTMAX ? 1 : g.seg;
+    a.coff = n.coff;
     a.gx = nullptr;
     if (drop) {
-        // work tail: xm (B, A0x, Tx) | gx (B, L, 2H, Tp)
-        const int Tx = (int)(T - a.coff);
-        float* xm = o1b + r64((size_t)batch * g.O1 * Tp);
-        float* gx = xm + r64((size_t)batch * swn_a0x(&g) * Tx);
-        size_t fe_off = (size_t)g.n_aux;                         // frame-rate activations: scaled | conv_aux layers
-        for (int i = 0; i + 1 < g.auxl; ++i) fe_off += g.aux_cout[i];
-        const float* C = fe_work + fe_off * (size_t)batch * n_frames;
-        unsigned short* wx16 = nullptr;
-        if (swn_call_mode() == SWN_PRECISION_BF16 && swn_drop_inx16(&g, Tp)) {
-            // xm as bf16 rows in the same section (the backward of the same mode reads them there), the bf16 in_x matrix at the
-            // end of the work buffer
-            wx16 = reinterpret_cast<unsigned short*>(gx + r64((size_t)batch * g.L * 2 * g.H * Tp) +
-                                                     (size_t)g.L * r64((size_t)batch * 2 * g.H * Tp) + r64((size_t)batch * g.H * Tp));
+        const int Tx = (int)n.Tx;
+        float* xm = work + lo.xm;
+        float* gx = work + lo.gx;
+        // swn_drop_inx16: xm as bf16 rows in the same section (the backward of the same mode reads them there) and the bf16 in_x matrix
+        unsigned short* wx16 = inx16 ? reinterpret_cast<unsigned short*>(work + lo.wx16) : nullptr;
+        if (inx16)
             hipLaunchKernelGGL(xm_fwd16_kernel, dim3((Tx + 2047) / 2048, swn_a0x(&g), batch), dim3(256), 0, st, C, packed, a.y.wup, a.y.bup,
                                drop_x, reinterpret_cast<unsigned short*>(xm), g.A0, swn_a0x(&g), n_frames, g.U, a.coff, Tx, swn_pitch16(Tx));
-        } else
+        else
         hipLaunchKernelGGL(xm_fwd_kernel, dim3((Tx + 255) / 256, swn_a0x(&g), batch), dim3(256), 0, st, C, packed, a.y.wup, a.y.bup,
                            drop_x, xm, g.A0, swn_a0x(&g), n_frames, g.U, a.coff, Tx);
         // (the GEMM stack reads gx in the G4 layout, swn_geom.hpp; it needs the bf16-copy product kernel, i.e. wx16)
-        const bool g16 = !hs && swn_call_mode() == SWN_PRECISION_BF16 && drop_g16(d, batch, Tp) && wx16;
-        rc = swn_train_inx_forward(g, a.y, packed, xm, gx, batch, Tx, (int)Tp, st, wx16, g16);
+        rc = swn_train_inx_forward(g, a.y, packed, xm, gx, batch, Tx, (int)Tp, st, wx16, stack16);
         if (rc < 0) return rc;
         a.gx = gx;
     }
-    if (drop && !hs && swn_call_mode() == SWN_PRECISION_BF16 && drop_g16(d, batch, Tp) && swn_drop_inx16(&g, Tp)) {
+    if (stack16) {
         // GEMM-stack geometries: input layer, gated layers (gate epilogue on the sample-rate in_x rows, a dropped level read through
         // its masked copy, pre-activations kept for the backward) and head on the bf16 time-major stack of the forward without
         // dropout; what the backward reads in fp32 (hidden states, relu(skip), relu(out_1)) is expanded from it.  Replaces one
         // fp32-operand time GEMM + one element-wise gate launch per layer (475 -> ~330 us per layer at the run.sh geometry).
-        float* a_scr = const_cast<float*>(a.gx) + r64((size_t)batch * g.L * 2 * g.H * Tp);
-        float* tail = a_scr + (size_t)g.L * r64((size_t)batch * 2 * g.H * Tp) + r64((size_t)batch * g.H * Tp) +
-                      r64((size_t)g.L * 2 * g.H * swn_a0x(&g) / 2 + 1);
-        void* work16 = tail;
-        unsigned short* hm16 = reinterpret_cast<unsigned short*>(tail + r64((swn_bf16g_work_bytes(g, batch, Tp) + 3) / 4));
-        void* wbf = reinterpret_cast<float*>(hm16) + r64((size_t)batch * Tp * g.H / 2 + 1);
+        void* work16 = work + lo.work16;
+        void* wbf = work + lo.wbf;
         rc = swn_bf16g_pack(g, packed, wbf, st);
         if (rc < 0) return rc;
-        rc = swn_bf16g_forward(g, packed, wbf, nullptr, audio, batch, n_frames, work16, out, st, a_scr, a.gx, drop_h, hm16);
+        rc = swn_bf16g_forward(g, packed, wbf, nullptr, audio, batch, n_frames, work16, out, st, work + lo.a_keep, a.gx, drop_h,
+                               reinterpret_cast<unsigned short*>(work + lo.hm16));
         if (rc < 0) return rc;
         rc = swn_bf16g_expand(g, work16, batch, Tp, work, false, st);
         return rc < 0 ? rc : swn_launch_status(where);
@@ -452,13 +411,11 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
         if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(tf_input_kernel<SWN_KIND_LAPLACE>, grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(tf_input_kernel<SWN_KIND_SOFTMAX>, grid, dim3(256), 0, st, a);
     }
-    if (drop && swn_call_mode() == SWN_PRECISION_BF16 && swn_drop_bf16_forward(&g)) {
-        // mixed-precision mode: bf16-operand GEMM + element-wise gate per layer; after gx in the work buffer: the gate
-        // pre-activations of every layer (B, 2H, Tp) x L - kept, the backward of the same mode reads them instead of
-        // recomputing - | masked input of one layer (B, H, Tp)
-        float* a_scr = const_cast<float*>(a.gx) + r64((size_t)batch * g.L * 2 * g.H * Tp);
-        float* hmask = a_scr + (size_t)g.L * r64((size_t)batch * 2 * g.H * Tp);
-        rc = swn_train_layers_forward_drop(g, a.y, packed, audio, a.gx, drop_h, hbuf, a_scr, hmask, batch, n_frames, (int)Tp, st);
+    if (fwd16) {
+        // mixed-precision mode: bf16-operand GEMM + element-wise gate per layer; the gate pre-activations of every layer are
+        // kept (the backward of the same mode reads them instead of recomputing), a dropped level goes through hmask
+        rc = swn_train_layers_forward_drop(g, a.y, packed, audio, a.gx, drop_h, hbuf, work + lo.a_keep, lo.a_stride, work + lo.hmask,
+                                           batch, n_frames, (int)Tp, st);
         if (rc < 0) return rc;
     } else
     for (int l = 0; l < g.L; ++l) {
@@ -470,7 +427,7 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
     const size_t hstride = (size_t)(g.L + 1) * g.H * Tp;
     // skip: one GEMM over the L concatenated (undropped) hidden states (requires Hp == H, i.e. H % 4 == 0)
     if (g.Hp != g.H) return SWN_E_UNSUPPORTED;
-    if (drop && swn_call_mode() == SWN_PRECISION_BF16 && !hs && swn_drop_bf16_forward(&g)) {
+    if (fwd16 && !hs) {
         // mixed-precision mode: the two wide 1x1 layers as bf16-operand time GEMMs with bias + relu epilogues (0.5 ms each as
         // exact-fp32 gemm_wx at the run.sh geometry); out_2 (<= 16 rows) stays below
         rc = swn_train_head_acts(g, packed, work, batch, Tp, st);
@@ -499,23 +456,17 @@ extern "C" int swn_forward(const swn_net_desc* d, const float* packed, const flo
 extern "C" int swn_drop_fused_path(const swn_net_desc* d, int batch, int n_frames, const float* const* drop_h) {
     SwnGeom g;
     if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1 || g.kind != SWN_KIND_LAPLACE) return 0;
-    const long Tp = (long)n_frames * g.U - 2 * g.seg + 1;
+    const long Tp = swn_train_len(g, n_frames).Tp;
     return Tp >= 1 && swn_bl6_drop_supported(g, batch, Tp, n_frames, drop_h) ? 1 : 0;
 }
 
 extern "C" size_t swn_forward_drop_work_floats(const swn_net_desc* d, int batch, int n_frames) {
     SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1) return 0;
-    const size_t base = swn_forward_work_floats(d, batch, n_frames);
-    if (!base) return 0;
-    const long T = (long)n_frames * g.U;
-    const int coff = g.kind == SWN_KIND_SOFTMAX ? 1 : g.seg;
-    const long Tp = g.kind == SWN_KIND_SOFTMAX ? T - 1 : T - 2 * g.seg + 1;
-    // xm | gx | (mixed-precision forward) gate pre-activations of every layer | masked input of one layer
-    const size_t chain = base + r64((size_t)batch * swn_a0x(&g) * (T - coff)) + r64((size_t)batch * g.L * 2 * g.H * Tp) +
-                         (size_t)g.L * r64((size_t)batch * 2 * g.H * Tp) + r64((size_t)batch * g.H * Tp) +
-                         r64((size_t)g.L * 2 * g.H * swn_a0x(&g) / 2 + 1) +       // bf16 in_x matrix (swn_drop_inx16)
-                         (drop_g16(d, batch, Tp) ? r64((swn_bf16g_work_bytes(g, batch, Tp) + 3) / 4) + r64((size_t)batch * Tp * g.H / 2 + 1) +
-                                                       r64((swn_bf16g_weight_bytes(g) + 3) / 4) : 0);    // bf16 stack | masked level | bf16 weights
+    const SwnTrainLen n = swn_train_len(g, n_frames);
+    const long Tp = n.Tp;
+    if (Tp < 1) return 0;
+    const bool g16 = swn_drop_g16(d, batch, Tp);
+    const size_t chain = swn_fwd_drop_layout(g, batch, n, g16, g16 ? swn_bf16g_weight_bytes(g) : 0).drop_total;
     const size_t fused = g.bl6 ? (swn_bl6_drop_layout(g, batch, Tp).total + 3) / 4 : 0;      // the fused BL6 path's own layout
     return chain > fused ? chain : fused;
 }

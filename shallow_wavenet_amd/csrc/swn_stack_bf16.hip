@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include "swn_geom.hpp"
+#include "swn_train_internal.hpp"
 #include <cstdlib>
 
 namespace {
@@ -1022,26 +1023,6 @@ BfOffsets bf_offsets(const SwnGeom& g) {
     return o;
 }
 
-}  // namespace
-
-// large geometries (H a multiple of 64 beyond the BL6 class): tiled bf16 GEMM stack, csrc/swn_stack_bf16g.hip
-int swn_bf16g_geom(const swn_net_desc* d, SwnGeom* g);
-size_t swn_bf16g_weight_bytes(const SwnGeom& g);
-int swn_bf16g_pack(const SwnGeom& g, const float* packed, void* wbf, hipStream_t st);
-size_t swn_bf16g_work_bytes(const SwnGeom& g, int batch, long Tp);
-int swn_bf16g_expand(const SwnGeom& g, const void* work, int batch, long Tp, float* fwd_work, bool hs_only, hipStream_t st);
-int swn_train_head_acts(const SwnGeom& g, const float* packed, float* work, int batch, long Tp, hipStream_t st);
-int swn_bf16g_forward(const SwnGeom& g, const float* packed, const void* wbf, const float* cond, const void* audio,
-                      int batch, int n_frames, void* work, float* out, hipStream_t st, float* a_keep = nullptr,
-                      const float* gx = nullptr, const float* const* drop_h = nullptr, unsigned short* hm16 = nullptr);
-size_t swn_bf16g_keep_floats(const SwnGeom& g, int batch, long Tp);
-
-int swn_bf16g_plain(const unsigned short* A, int M, const unsigned short* src, size_t blk_stride, size_t src_bytes, int KB, int nblk,
-                    int Tp, int B, const float* bias, unsigned short* out_bf, int out_ld, float* out_f, int NO, hipStream_t st);
-bool swn_bl6_bwd_supported(const SwnGeom& g, int B, long Tp, int n_frames);                    // csrc/swn_bwd_bl6.hip
-
-namespace {
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 void pack_bl6_images(const SwnGeom& g, const SwnLayout& y, const float* packed, unsigned short* wbf, hipStream_t st) {
     const BfOffsets o = bf_offsets(g);
     hipLaunchKernelGGL(pack_wd_kernel, dim3((g.L * 8 * 4 * 512 + 255) / 256), dim3(256), 0, st, packed + y.wd, g.L, wbf + o.wd);
@@ -1052,7 +1033,7 @@ void pack_bl6_images(const SwnGeom& g, const SwnLayout& y, const float* packed, 
 }
 }  // namespace
 
-// ---- dropout mode of the BL6 class in the mixed-precision mode (SwnBl6DropLayout, csrc/swn_geom.hpp) -------------------------
+// ---- dropout mode of the BL6 class in the mixed-precision mode (SwnBl6DropLayout, swn_train_internal.hpp) -------------------------
 // With dilation_repeat == 1 the reference's hidden-state dropout lands on the last layer's output only
 // (cswnv_shift1.py:211-217: (l + 1) % dilation_depth == 0 <=> l = L - 1), which nothing reads: the step is the plain one with
 // the hoisted conditioning replaced by sample-rate in_x products of the masked conditioning.
@@ -1067,18 +1048,18 @@ SwnBl6DropLayout swn_bl6_drop_layout(const SwnGeom& g, int B, long Tp) {
     SwnBl6DropLayout o;
     const size_t npos = (size_t)B * Tp;
     o.hs16 = 0;
-    o.wbf = o.hs16 + al256((size_t)(g.L + 1) * npos * H * 2);
-    o.wx16 = o.wbf + al256(bf_offsets(g).total * 2);
-    o.xm16 = o.wx16 + al256((size_t)g.L * 128 * swn_a0x(&g) * 2);
-    o.gx16 = o.xm16 + al256(npos * swn_a0x(&g) * 2);
-    o.total = o.gx16 + al256(npos * g.L * 256);
+    o.wbf = o.hs16 + swn_al256((size_t)(g.L + 1) * npos * H * 2);
+    o.wx16 = o.wbf + swn_al256(bf_offsets(g).total * 2);
+    o.xm16 = o.wx16 + swn_al256((size_t)g.L * 128 * swn_a0x(&g) * 2);
+    o.gx16 = o.xm16 + swn_al256(npos * swn_a0x(&g) * 2);
+    o.total = o.gx16 + swn_al256(npos * g.L * 256);
     return o;
 }
 // C: the last conv_aux activation (B, A0, Tf) inside swn_frontend's work buffer; work: SwnBl6DropLayout.total bytes
 int swn_bl6_drop_forward(const SwnGeom& g, const float* packed, const float* C, const float* audio, const float* drop_x,
                          int batch, int n_frames, void* work, float* out, hipStream_t st) {
-    const long Tp = (long)n_frames * g.U - 2 * g.seg + 1;
-    const int Tx = (int)Tp, A0x = swn_a0x(&g);
+    const long Tp = swn_train_len(g, n_frames).Tp;
+    const int Tx = (int)Tp, A0x = swn_a0x(&g);                  // seg == 1: Tx == Tp
     const SwnBl6DropLayout lo = swn_bl6_drop_layout(g, batch, Tp);
     unsigned char* wb = reinterpret_cast<unsigned char*>(work);
     unsigned short* wx16 = reinterpret_cast<unsigned short*>(wb + lo.wx16);
@@ -1136,14 +1117,12 @@ extern "C" int swn_pack_bf16(const swn_net_desc* d, const float* packed, void* w
 extern "C" size_t swn_forward_bf16_work_bytes(const swn_net_desc* d, int batch, int n_frames) {
     SwnGeom g;
     if (batch < 1 || n_frames < 1) return 0;
-    if (bf_geom(d, &g) < 0) {
-        if (swn_bf16g_geom(d, &g) < 0) return 0;
-        const long Tpg = (long)n_frames * g.U - 2 * g.seg + 1;
-        return Tpg < 1 ? 0 : swn_bf16g_work_bytes(g, batch, Tpg);
-    }
-    const long Tp = (long)n_frames * g.U - 2 * g.seg + 1;
+    const bool small = bf_geom(d, &g) == SWN_OK;
+    if (!small && swn_bf16g_geom(d, &g) < 0) return 0;
+    const long Tp = swn_train_len(g, n_frames).Tp;
     if (Tp < 1) return 0;
-    return (size_t)(g.L + 1) * batch * Tp * H * sizeof(unsigned short);
+    // BL6 class: the hidden states alone, [L+1][B][Tp][64] bf16 (the fused head keeps the two activations on chip)
+    return small ? swn_bf16g_layout(g, batch, Tp).skip : swn_bf16g_layout(g, batch, Tp).total;
 }
 
 extern "C" int swn_forward_bf16(const swn_net_desc* d, const float* packed, const void* wbf, const float* cond,
@@ -1152,12 +1131,12 @@ extern "C" int swn_forward_bf16(const swn_net_desc* d, const float* packed, cons
     SwnGeom g; int rc = bf_geom(d, &g);
     if (rc == SWN_E_UNSUPPORTED && swn_bf16g_geom(d, &g) == SWN_OK) {
         if (!packed || !wbf || !cond || !audio || !work || !out || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
-        if ((long)n_frames * g.U - 2 * g.seg + 1 < 1) return SWN_E_BADARG;
+        if (swn_train_len(g, n_frames).Tp < 1) return SWN_E_BADARG;
         return swn_bf16g_forward(g, packed, wbf, cond, audio_, batch, n_frames, work, out, (hipStream_t)stream_);
     }
     if (rc < 0) return rc;
     if (!packed || !wbf || !cond || !audio || !work || !out || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
-    const long Tp = (long)n_frames * g.U - 2 * g.seg + 1;
+    const long Tp = swn_train_len(g, n_frames).Tp;
     if (Tp < 1) return SWN_E_BADARG;
     // 32-bit buffer offsets in the layer kernel: one layer of hidden states and the conditioning must stay < 2 GiB
     if ((size_t)batch * Tp * H * 2 >= (1ull << 31) || (size_t)batch * n_frames * g.N * 4 >= (1ull << 31)) return SWN_E_UNSUPPORTED;
@@ -1222,8 +1201,8 @@ extern "C" int swn_forward_bf16(const swn_net_desc* d, const float* packed, cons
 extern "C" size_t swn_forward_bf16_keep_floats(const swn_net_desc* d, int batch, int n_frames) {
     SwnGeom g;
     if (batch < 1 || n_frames < 1 || bf_geom(d, &g) == SWN_OK || swn_bf16g_geom(d, &g) < 0) return 0;
-    const long Tp = (long)n_frames * g.U - 2 * g.seg + 1;
-    return Tp < 1 ? 0 : swn_bf16g_keep_floats(g, batch, Tp);
+    const long Tp = swn_train_len(g, n_frames).Tp;
+    return Tp < 1 ? 0 : swn_bf16g_layout(g, batch, Tp).keep_total;
 }
 
 extern "C" int swn_forward_bf16_keep(const swn_net_desc* d, const float* packed, const void* wbf, const float* cond,
@@ -1234,7 +1213,7 @@ extern "C" int swn_forward_bf16_keep(const swn_net_desc* d, const float* packed,
     const int rc = swn_bf16g_geom(d, &g);
     if (rc < 0) return rc;
     if (!packed || !wbf || !cond || !audio_ || !work || !out || !a_keep || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
-    if ((long)n_frames * g.U - 2 * g.seg + 1 < 1) return SWN_E_BADARG;
+    if (swn_train_len(g, n_frames).Tp < 1) return SWN_E_BADARG;
     return swn_bf16g_forward(g, packed, wbf, cond, audio_, batch, n_frames, work, out, (hipStream_t)stream_, a_keep);
 }
 
@@ -1257,7 +1236,7 @@ extern "C" int swn_bf16_work_to_f32(const swn_net_desc* d, const float* packed, 
     const bool small = bf_geom(d, &g) == SWN_OK;
     if (!small) { const int rc = swn_bf16g_geom(d, &g); if (rc < 0) return rc; }
     if (!work_bf16 || !fwd_work || (small && !packed) || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
-    const long Tp = (long)n_frames * g.U - 2 * g.seg + 1;
+    const long Tp = swn_train_len(g, n_frames).Tp;
     if (Tp < 1) return SWN_E_BADARG;
     const int rc = swn_bf16g_expand(g, work_bf16, batch, Tp, fwd_work, small, (hipStream_t)stream_);
     if (rc < 0 || !small) return rc;

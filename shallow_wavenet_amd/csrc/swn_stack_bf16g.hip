@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include "swn_geom.hpp"
+#include "swn_train_internal.hpp"
 
 namespace {
 
@@ -747,32 +748,25 @@ __global__ __launch_bounds__(256) void bf16g_expand_kernel(const unsigned short*
 
 // what swn_bf16g_forward left in `work` -> the fp32 work layout of swn_forward: hs | relu(skip) | relu(out_1)
 int swn_bf16g_expand(const SwnGeom& g, const void* work, int batch, long Tp, float* fwd_work, bool hs_only, hipStream_t st) {
-    auto r64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
-    const unsigned short* hs = reinterpret_cast<const unsigned short*>(work);
-    const size_t lstride = (size_t)batch * Tp * g.H;
-    const unsigned short* skipb = hs + (size_t)(g.L + 1) * lstride;
-    const unsigned short* o1b = skipb + (size_t)batch * Tp * g.S;
-    float* s1 = fwd_work + r64((size_t)batch * (g.L + 1) * g.H * Tp);
-    float* r1 = s1 + r64((size_t)batch * g.S * Tp);
+    const SwnBf16gLayout lo = swn_bf16g_layout(g, batch, Tp);
+    const SwnFwdLayout fl = swn_fwd_layout(g, batch, Tp);
+    const unsigned char* wb = reinterpret_cast<const unsigned char*>(work);
+    const unsigned short* hs = reinterpret_cast<const unsigned short*>(wb + lo.hs);
+    const unsigned short* skipb = reinterpret_cast<const unsigned short*>(wb + lo.skip);
+    const unsigned short* o1b = reinterpret_cast<const unsigned short*>(wb + lo.o1);
+    float* s1 = fwd_work + fl.s1;
+    float* r1 = fwd_work + fl.r1;
     const unsigned tx = (unsigned)((Tp + 127) / 128);
     (void)hipGetLastError();
     // hidden states: matrix z = l * B + b  ->  dst [b][l][H][Tp]
     hipLaunchKernelGGL(bf16g_expand_kernel, dim3(tx, (g.H + 63) / 64, (g.L + 1) * batch), dim3(256), 0, st,
-                       hs, (size_t)Tp * g.H, g.H, (int)Tp, fwd_work, batch, (size_t)(g.L + 1) * g.H * Tp, (size_t)g.H * Tp);
+                       hs, (size_t)Tp * g.H, g.H, (int)Tp, fwd_work + fl.hs, batch, (size_t)(g.L + 1) * g.H * Tp, (size_t)g.H * Tp);
     if (hs_only) return swn_launch_status("swn_bf16_work_to_f32");
     hipLaunchKernelGGL(bf16g_expand_kernel, dim3(tx, (g.S + 63) / 64, batch), dim3(256), 0, st,
                        skipb, (size_t)Tp * g.S, g.S, (int)Tp, s1, batch, (size_t)g.S * Tp, (size_t)0);
     hipLaunchKernelGGL(bf16g_expand_kernel, dim3(tx, (g.O1 + 63) / 64, batch), dim3(256), 0, st,
                        o1b, (size_t)Tp * g.O1, g.O1, (int)Tp, r1, batch, (size_t)g.O1 * Tp, (size_t)0);
     return swn_launch_status("swn_bf16_work_to_f32");
-}
-
-size_t swn_bf16g_work_bytes(const SwnGeom& g, int batch, long Tp) {
-    return ((size_t)(g.L + 1) * g.H + g.S + g.O1) * batch * Tp * sizeof(unsigned short);
-}
-
-size_t swn_bf16g_keep_floats(const SwnGeom& g, int batch, long Tp) {
-    return (size_t)g.L * (((size_t)batch * 2 * g.H * Tp + 63) & ~(size_t)63);
 }
 
 // gx != null: the dropout mode (cswnv_shift1.py:194-198,211-217,269-278) - sample-rate in_x products instead of the hoisted
@@ -783,12 +777,14 @@ int swn_bf16g_forward(const SwnGeom& g, const float* packed, const void* wbf_, c
                       const float* gx, const float* const* drop_h, unsigned short* hm16) {
     SwnLayout y; swn_make_layout(&g, &y);
     const GOff o = g_offsets(g);
-    const long Tp = (long)n_frames * g.U - 2 * g.seg + 1;
+    const long Tp = swn_train_len(g, n_frames).Tp;
+    const SwnBf16gLayout lo = swn_bf16g_layout(g, batch, Tp);
     const unsigned short* wbf = reinterpret_cast<const unsigned short*>(wbf_);
-    unsigned short* hs = reinterpret_cast<unsigned short*>(work);
-    const size_t lstride = (size_t)batch * Tp * g.H;
-    unsigned short* skipb = hs + (size_t)(g.L + 1) * lstride;
-    unsigned short* o1b = skipb + (size_t)batch * Tp * g.S;
+    unsigned char* wb = reinterpret_cast<unsigned char*>(work);
+    unsigned short* hs = reinterpret_cast<unsigned short*>(wb + lo.hs);
+    const size_t lstride = (size_t)batch * Tp * g.H;               // one level of hs
+    unsigned short* skipb = reinterpret_cast<unsigned short*>(wb + lo.skip);
+    unsigned short* o1b = reinterpret_cast<unsigned short*>(wb + lo.o1);
     // 32-bit buffer offsets: every GEMM operand must stay below 2 GiB
     if ((size_t)g.L * lstride * 2 >= (1ull << 31) || (size_t)batch * Tp * (g.S > g.O1 ? g.S : g.O1) * 2 >= (1ull << 31)) return SWN_E_UNSUPPORTED;
     (void)hipGetLastError();
@@ -817,7 +813,7 @@ int swn_bf16g_forward(const SwnGeom& g, const float* packed, const void* wbf_, c
                                hs + (size_t)l * lstride, drop_h[l - 1], hm16, g.H, (int)Tp);
             a.src = hm16; a.hprev = hm16;
         }
-        a.a_out = a_keep ? a_keep + (size_t)l * (((size_t)batch * 2 * g.H * Tp + 63) & ~(size_t)63) : nullptr;
+        a.a_out = a_keep ? a_keep + (size_t)l * lo.keep_stride : nullptr;
         if (g.H == 192 && a.KB == 192 && launch_gate8(a, batch, st)) continue;      // LDS-DMA layer kernel of the run.sh Laplace geometry
         launch_gemm<EPI_GATE>(a, (int)tx, g.H / 64, batch, st);
     }

@@ -24,12 +24,11 @@
 #include <atomic>
 #include "swn_geom.hpp"
 #include "swn_mma.hpp"
+#include "swn_train_internal.hpp"
 
 namespace {
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
-constexpr int SWN_WUP_COPIES = 16;      // see wup_fold_kernel
 
 struct TimeGemm {
     const float* A; long a_sm, a_stap, a_sc;        // A(m, tap, c)
@@ -1360,8 +1359,6 @@ __global__ __launch_bounds__(256) void laplace_head_bwd_kernel(const float* __re
         graw[((size_t)b * NO + 2 * seg + k) * Tp + t] = ga ? ga[((size_t)b * Tp + t) * lpc + k] : 0.f;
 }
 
-size_t r64(size_t x) { return (x + 63) & ~(size_t)63; }
-
 // arithmetic mode of the training call in progress on this thread (SwnModeScope, csrc/swn_geom.hpp)
 thread_local int t_call_mode = SWN_PRECISION_FP32;
 inline bool mode_bf16() { return t_call_mode == SWN_PRECISION_BF16; }
@@ -1449,30 +1446,10 @@ void launch_reduce(ReduceGemm g, int B, hipStream_t st) {
 int  swn_call_mode() { return t_call_mode; }
 void swn_call_mode_set(int mode) { t_call_mode = mode; }
 
-static size_t chain_floats(const SwnGeom& g, int batch, int n_frames);
 extern "C" size_t swn_backward_work_floats(const swn_net_desc* d, int batch, int n_frames) {
     SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1) return 0;
-    const long T = (long)n_frames * g.U;
-    const long Tp = g.kind == SWN_KIND_SOFTMAX ? T - 1 : T - 2 * g.seg + 1;
-    if (Tp < 1) return 0;
-    return chain_floats(g, batch, n_frames);
-}
-static size_t chain_floats(const SwnGeom& g, int batch, int n_frames) {
-    const long T = (long)n_frames * g.U;
-    const long Tp = g.kind == SWN_KIND_SOFTMAX ? T - 1 : T - 2 * g.seg + 1;
-    size_t fw = (size_t)g.n_aux; for (int i = 0; i < g.auxl; ++i) fw += g.aux_cout[i];
-    return r64((size_t)batch * g.O1 * Tp) + r64((size_t)batch * g.S * Tp) + r64((size_t)batch * (g.L + 1) * g.H * Tp) +
-           2 * r64((size_t)batch * 2 * g.H * Tp) + r64((size_t)batch * n_frames * g.N) + r64(fw * batch * n_frames) +
-           (size_t)SWN_WUP_COPIES * 256 +     // partial upsampler-tap gradients of cond_bwd_kernel
-           r64((size_t)batch * 2 * g.H * ((Tp + 2 + 31) & ~31L)) +     // two bf16 copies of a layer's da (mixed-precision GEMM operands)
-           r64((size_t)g.L * g.K * g.H * 2 * g.H / 2) +               // transposed bf16 copy of the layer matrices (data gradients)
-           r64((size_t)batch * g.H * ((Tp + 2 + 31) & ~31L));          // two bf16 copies of a layer's input (weight gradients' Q operand)
-}
-// floats of the dropout chain's scratch (swn_backward_drop without the kept d gx): the chain's + d xm + one masked layer input
-static size_t drop_chain_floats(const SwnGeom& g, int batch, int n_frames) {
-    const long T = (long)n_frames * g.U;
-    const long Tp = g.kind == SWN_KIND_SOFTMAX ? T - 1 : T - 2 * g.seg + 1;
-    return chain_floats(g, batch, n_frames) + r64((size_t)batch * g.A0 * (T - (g.kind == SWN_KIND_SOFTMAX ? 1 : g.seg))) + r64((size_t)batch * g.H * Tp);
+    const SwnTrainLen n = swn_train_len(g, n_frames);
+    return n.Tp < 1 ? 0 : swn_bwd_layout(g, batch, n_frames, n, false).total;
 }
 
 namespace {
@@ -1637,8 +1614,9 @@ __global__ __launch_bounds__(256) void xm_bwd16_kernel(const unsigned short* __r
 int swn_train_head_acts(const SwnGeom& g, const float* packed, float* work, int B, long Tp, hipStream_t st) {
     if (g.Hp != g.H) return SWN_E_UNSUPPORTED;
     SwnLayout y; swn_make_layout(&g, &y);
-    float* skipb = work + r64((size_t)B * (g.L + 1) * g.H * Tp);
-    float* o1b = skipb + r64((size_t)B * g.S * Tp);
+    const SwnFwdLayout lo = swn_fwd_layout(g, B, Tp);
+    float* skipb = work + lo.s1;
+    float* o1b = work + lo.r1;
     (void)hipGetLastError();
     {   // skip[b][c][t] = relu(bsk[c] + sum_{l,i} Wsk[c][l*H+i] h_{l+1}[b][i][t])
         TimeGemm t = {packed + y.wsk, (long)g.L * g.Hp, 0, 1, work + (size_t)g.H * Tp, (long)(g.L + 1) * g.H * Tp, Tp, 1,
@@ -1686,8 +1664,8 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateBwd a, float* _
 }  // namespace
 
 int swn_train_layers_forward_drop(const SwnGeom& g, const SwnLayout& y, const float* packed, const void* audio, const float* gx,
-                                  const float* const* drop_h, float* hs, float* a_scr, float* hmask, int B, int n_frames, int Tp,
-                                  hipStream_t st) {
+                                  const float* const* drop_h, float* hs, float* a_scr, size_t a_stride, float* hmask, int B,
+                                  int n_frames, int Tp, hipStream_t st) {
     GateBwd ga{};
     ga.g = g; ga.y = y; ga.P = packed; ga.cond = nullptr; ga.audio = audio; ga.hs = hs; ga.dhs = nullptr; ga.a_da = a_scr;
     ga.dgx = nullptr; ga.B = B; ga.Tf = n_frames; ga.Tp = Tp; ga.coff = g.kind == SWN_KIND_SOFTMAX ? 1 : g.seg;
@@ -1704,7 +1682,7 @@ int swn_train_layers_forward_drop(const SwnGeom& g, const SwnLayout& y, const fl
             hipLaunchKernelGGL(mask_mul_kernel, dim3((unsigned)((npb / 4 + 255) / 256 + 1), B), dim3(256), 0, st, xin, hsb, in_mul, hmask, npb);
             xin = hmask; xin_sb = npb;
         }
-        float* al = a_scr + (size_t)l * r64((size_t)B * H2 * Tp);          // this layer's slot (kept for the backward)
+        float* al = a_scr + (size_t)l * a_stride;          // this layer's slot (kept for the backward)
         ga.a_da = al;
         TimeGemm t = {packed + y.wd + (size_t)l * H2 * g.K * g.Hp, (long)g.K * g.Hp, g.Hp, 1, xin, xin_sb, Tp, 1, al, (long)H2 * Tp, Tp,
                       nullptr, 0, 0, H2, g.K, H, Tp, 1, g.K - 1, g.dil[l], 0};
@@ -1763,19 +1741,10 @@ int swn_train_inx_forward(const SwnGeom& g, const SwnLayout& y, const float* pac
     return SWN_OK;
 }
 
-// fused per-layer backward of the BL6 class in the mixed-precision mode (csrc/swn_bwd_bl6.hip)
-bool swn_bl6_bwd_supported(const SwnGeom& g, int B, long Tp, int n_frames);
-size_t swn_bl6_bwd_scratch_bytes(const SwnGeom& g, int B, long Tp);
-size_t swn_bl6_bwd_drop_scratch_bytes(const SwnGeom& g, int B, long Tp);
-int swn_bl6_bwd_stack(const SwnGeom& g, const SwnLayout& y, const float* packed, const float* cond, const float* audio,
-                      const void* hs_bf16, const float* grad_out, float* dcond, float* gpacked, void* scratch, int B, int n_frames,
-                      long Tp, hipStream_t st, const unsigned short* gx16 = nullptr, const unsigned short* xm16 = nullptr,
-                      unsigned short* dxm16 = nullptr);
-
 namespace {
 
 // hs_bf16 != null: everything at sample rate runs through swn_bl6_bwd_stack (csrc/swn_bwd_bl6.hip; the caller has checked
-// swn_bl6_bwd_supported); `work` is then [dcond | front-end gradients | swn_bl6_bwd_scratch_bytes] and fwd_work is not read
+// swn_bl6_bwd_supported); `work` then holds the compact form of SwnBwdLayout (swn_bwd_bl6_layout) and fwd_work is not read
 int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, const float* cond,
                   const float* fe_work, const void* audio, const float* fwd_work, const float* hs_opt,
                   const float* drop_x, const float* const* drop_h,
@@ -1791,9 +1760,10 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
     if (g.Hp != g.H || g.K > 8 || g.U > 256) return SWN_E_UNSUPPORTED;
     swn_make_layout(&ga.g, &ga.y);
     const SwnLayout& y = ga.y;
-    const long T = (long)n_frames * g.U;
-    const int Tp = (int)(g.kind == SWN_KIND_SOFTMAX ? T - 1 : T - 2 * g.seg + 1);
-    if (Tp < 1) return SWN_E_BADARG;
+    const SwnTrainLen n = swn_train_len(g, n_frames);
+    const long T = n.T;
+    const int Tp = (int)n.Tp;
+    if (n.Tp < 1) return SWN_E_BADARG;
     // dropout mode, BL6 class, mixed-precision mode: the forward of the same call mode was swn_bl6_drop_forward (same predicate),
     // fwd_work holds its SwnBl6DropLayout and the layers take the fused backward with sample-rate in_x operands
     const bool drop_fused = drop && !hs_opt && !hs_bf16 && mode_bf16() && swn_bl6_drop_supported(g, batch, Tp, n_frames, drop_h);
@@ -1815,58 +1785,50 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();
     const int B = batch, H = g.H, H2 = 2 * g.H, L = g.L, S = g.S, O1 = g.O1, NO = g.NO;
-    // forward buffers (layout of swn_forward_work_floats): hs | s1 = relu(skip) | r1 = relu(out_1)
-    const size_t hs_floats = r64((size_t)B * (L + 1) * H * Tp);
+    const int coff = n.coff, Tx = (int)n.Tx;
+    const bool bf16 = mode_bf16(), chain = !hs_bf16;
+    // forward buffers: hs | s1 = relu(skip) | r1 = relu(out_1), and in the dropout mode swn_forward_drop's tail (xm, gx; in the
+    // mixed-precision mode every layer's gate pre-activations: the arithmetic mode must not change between a forward and its backward)
+    const bool g16 = chain && drop && swn_drop_g16(d, B, Tp);
+    const SwnFwdLayout fl = drop ? swn_fwd_drop_layout(g, B, n, g16, g16 ? swn_bf16g_weight_bytes(g) : 0) : swn_fwd_layout(g, B, Tp);
     const float* hs = hs_opt ? hs_opt : fwd_work;
-    const float* s1 = fwd_work + hs_floats;
-    const float* r1 = s1 + r64((size_t)B * S * Tp);
-    // scratch
-    float* do1 = work;
-    float* dskip = do1 + r64((size_t)B * O1 * Tp);
-    float* dhs = dskip + r64((size_t)B * S * Tp);
-    float* a_da = dhs + r64((size_t)B * (L + 1) * H * Tp);
-    float* dgx = a_da + r64((size_t)B * H2 * Tp);
-    float* dcond = dgx + r64((size_t)B * H2 * Tp);
-    float* dfe = dcond + r64((size_t)B * n_frames * g.N);
-    // dropout mode: forward work tail = xm | gx (swn_forward_drop); scratch tail = dxm
-    const int coff = g.kind == SWN_KIND_SOFTMAX ? 1 : g.seg;
-    const int Tx = (int)(T - coff);
-    size_t fe_tot = (size_t)g.n_aux; for (int i = 0; i < g.auxl; ++i) fe_tot += g.aux_cout[i];
-    const float* xm = r1 + r64((size_t)B * O1 * Tp);
-    const float* gx = xm + r64((size_t)B * swn_a0x(&g) * Tx);
-    // dropout mode in the mixed-precision mode: swn_forward_drop of the same mode kept every layer's gate pre-activations
-    // behind gx (the arithmetic mode must not change between a forward and its backward)
-    const float* saved_a = (drop && mode_bf16() && !hs_opt && swn_drop_bf16_forward(&g))
-                               ? gx + r64((size_t)B * L * H2 * Tp) : a_keep;   // a_keep: swn_forward_bf16_keep's buffer (same slots)
-    float* dxm = dfe + r64(fe_tot * B * n_frames);
-    float* hmask = dxm + r64((size_t)B * g.A0 * Tx);               // dropout mode only: masked input of a layer (B, H, Tp)
-    float* bl6_scratch = nullptr;
-    if (hs_bf16) {                                     // compact layout: none of the fp32 sample-rate scratch exists
-        dcond = work;
-        dfe = dcond + r64((size_t)B * n_frames * g.N);
-        dxm = dfe + r64(fe_tot * B * n_frames);
-        bl6_scratch = drop_fused ? dxm + r64((size_t)B * Tx * swn_a0x(&g) / 2) : dxm;      // dropout mode: d xm first, bf16 [B][Tx][A0x]
-    }
+    const float* s1 = chain ? fwd_work + fl.s1 : nullptr;
+    const float* r1 = chain ? fwd_work + fl.r1 : nullptr;
+    const float* xm = chain && drop ? fwd_work + fl.xm : nullptr;
+    const float* gx = chain && drop ? fwd_work + fl.gx : nullptr;
+    const float* saved_a = (chain && drop && bf16 && !hs_opt && swn_drop_bf16_forward(&g)) ? fwd_work + fl.a_keep
+                                                                                            : a_keep;   // swn_forward_bf16_keep's buffer
+    const size_t a_stride = swn_keep_stride(g, B, Tp);               // (the same slots in both)
+    // scratch: the chain's sections, or the compact form around the fused stack's own scratch (only dcond, dfe, dxm, bl6 then)
+    const SwnBwdLayout wl = chain ? swn_bwd_layout(g, B, n_frames, n, drop)
+                                  : swn_bwd_bl6_layout(g, B, n_frames, n, drop_fused, swn_bl6_bwd_scratch_bytes(g, B, Tp, drop_fused));
+    float* do1 = work + wl.do1;
+    float* dskip = work + wl.dskip;
+    float* dhs = work + wl.dhs;
+    float* a_da = work + wl.a_da;
+    float* dgx = work + wl.dgx;
+    float* dcond = work + wl.dcond;
+    float* dfe = work + wl.dfe;
+    float* dxm = work + wl.dxm;                                      // dropout mode; the fused path: bf16 [B][Tx][A0x]
+    float* hmask = work + wl.hmask;                                  // dropout mode: masked input of a layer (B, H, Tp)
+    float* bl6_scratch = chain ? nullptr : work + wl.bl6;
     if (hipMemsetAsync(gpacked, 0, y.total * sizeof(float), st) != hipSuccess) return SWN_E_LAUNCH;
-    // teacher-forced chain without dropout: the partial g w_up copies of cond_bwd_kernel sit where the dropout mode keeps dxm
-    float* wup_part = (!hs_bf16 && !drop) ? dxm : nullptr;
+    // teacher-forced chain without dropout: the partial g w_up copies of cond_bwd_kernel
+    float* wup_part = (chain && !drop) ? work + wl.wup_part : nullptr;
     // mixed-precision chain: gate_bwd also leaves da as bf16 rows (pitch = Tp rounded up to 32) for the layer weight gradients
-    const long da16_pitch = (Tp + 2 + 31) & ~31L, da16_odd = (long)B * H2 * da16_pitch;
-    unsigned short* da16 = nullptr;
-    if (!hs_bf16 && mode_bf16())
-        da16 = reinterpret_cast<unsigned short*>(drop ? hmask + r64((size_t)B * H * Tp) : dxm + (size_t)SWN_WUP_COPIES * 256);
+    const long da16_pitch = swn_da16_pitch(Tp), da16_odd = (long)B * H2 * da16_pitch;
+    unsigned short* da16 = (chain && bf16) ? reinterpret_cast<unsigned short*>(work + wl.da16) : nullptr;
     ga.da16 = da16; ga.da16_pitch = da16_pitch; ga.da16_odd = da16_odd;
     // ... and the layer's (masked) input, for the weight gradient's Q operand; second copy within 32-bit reach as for da
     const long h16_odd = (long)B * H * da16_pitch;
-    unsigned short* h16 = nullptr;
-    if (da16 && Tp >= 256 && ((size_t)h16_odd + (size_t)H * da16_pitch) * 2 < (1ull << 31))
-        h16 = da16 + 2 * r64((size_t)B * H2 * da16_pitch) + 2 * r64((size_t)L * g.K * H * H2 / 2);
+    const bool use_h16 = da16 && Tp >= 256 && ((size_t)h16_odd + (size_t)H * da16_pitch) * 2 < (1ull << 31);
+    unsigned short* h16 = use_h16 ? reinterpret_cast<unsigned short*>(work + wl.h16) : nullptr;
     ga.h16 = h16; ga.h16_odd = h16_odd;
-    unsigned short* wdt16 = nullptr;             // [l][tap][i][o2]
     // (the kernel reaches the second da copy through a 32-bit byte offset from an utterance's rows: it must stay below 2 GiB,
     //  else the data gradients keep their fp32 X operand)
-    if (da16 && g.Hp == H && H2 % 32 == 0 && ((size_t)da16_odd + (size_t)H2 * da16_pitch) * 2 < (1ull << 31)) {
-        wdt16 = da16 + 2 * r64((size_t)B * H2 * da16_pitch);
+    const bool use_wdt16 = da16 && g.Hp == H && H2 % 32 == 0 && ((size_t)da16_odd + (size_t)H2 * da16_pitch) * 2 < (1ull << 31);
+    unsigned short* wdt16 = use_wdt16 ? reinterpret_cast<unsigned short*>(work + wl.wdt16) : nullptr;             // [l][tap][i][o2]
+    if (wdt16) {
         hipLaunchKernelGGL(wd_t16_kernel, dim3(1024), dim3(256), 0, st, packed + y.wd, wdt16, L, g.K, H, g.Hp);
         // launch_reduce / launch_time take their bf16-copy kernels under exactly these conditions: nobody reads the fp32 da then
         ga.skip_da32 = Tp >= 256 ? 1 : 0;
@@ -1876,7 +1838,7 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
     // Only level 0 needs zeros: levels 1..L are written whole by the skip data gradient below (accumulate = 0) before anything
     // is added to them; d h_0 only ever receives additions.  (Zeroing all L + 1 levels was 710 MB = 0.11 ms per step at REF6.)
     // (hipMemset2DAsync's fill kernel took 273 us for these 8 rows of 12.7 MB; a plain grid-stride store kernel is at the HBM rate)
-    if (!hs_bf16) hipLaunchKernelGGL(zero_rows_kernel, dim3(512, B), dim3(256), 0, st, dhs, (size_t)(L + 1) * H * Tp, (size_t)H * Tp);
+    if (chain) hipLaunchKernelGGL(zero_rows_kernel, dim3(512, B), dim3(256), 0, st, dhs, (size_t)(L + 1) * H * Tp, (size_t)H * Tp);
     const long hsb = (long)(L + 1) * H * Tp;
 
     // ---- head: out_2, out_1, skip
@@ -1910,16 +1872,16 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
     // dropout chain, seg == 1: every layer's d gx is kept - (B, L, 2H, Tp) at the end of the work buffer - so that the gradient wrt
     // the masked conditioning is ONE contraction over the L * 2H rows of in_x behind the loop instead of L read-modify-write
     // passes over d xm (257 MB each way at the run.sh geometry)
-    float* dgx_all = (drop && !drop_fused && g.seg == 1) ? work + drop_chain_floats(g, B, n_frames) : nullptr;
+    float* dgx_all = (drop && !drop_fused && g.seg == 1) ? work + wl.dgx_all : nullptr;
     // swn_drop_inx16 (the forward of the same mode left xm as bf16 rows): d gx is kept as bf16 rows in that section instead, and the
     // transposed bf16 in_x matrix sits behind it
-    const bool inx16 = dgx_all && !hs_opt && mode_bf16() && da16 && swn_drop_inx16(&g, Tp);
-    unsigned short* dgx16_all = inx16 ? reinterpret_cast<unsigned short*>(dgx_all) : nullptr;
-    unsigned short* wxt16 = inx16 ? reinterpret_cast<unsigned short*>(dgx_all + r64((size_t)B * L * H2 * Tp)) : nullptr;
+    const bool inx16 = dgx_all && !hs_opt && da16 && swn_drop_inx16(&g, Tp);
+    unsigned short* dgx16_all = inx16 ? reinterpret_cast<unsigned short*>(work + wl.dgx16_all) : nullptr;
+    unsigned short* wxt16 = inx16 ? reinterpret_cast<unsigned short*>(work + wl.wxt16) : nullptr;
     ga.B = B; ga.Tf = n_frames; ga.Tp = Tp; ga.coff = coff;
     ga.gx = drop ? gx : nullptr;
     // the GEMM stack keeps its pre-activations - and, when it ran the dropout-mode forward, read its in_x rows - in the G4 layout
-    ga.g4 = (a_keep || (drop && !drop_fused && !hs_opt && mode_bf16() && swn_drop_g16(d, B, Tp) && swn_drop_inx16(&g, Tp))) ? 1 : 0;
+    ga.g4 = (a_keep || (g16 && inx16)) ? 1 : 0;
     ga.gwxa = g.audio_in ? gpacked + y.wxa : nullptr;
     // ---- layers, last to first
     if (hs_bf16) {
@@ -1951,7 +1913,7 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
             xin = hmask; xin_sb = npb;
         }
         ga.a_in = nullptr;
-        if (saved_a) ga.a_in = saved_a + (size_t)l * r64((size_t)B * H2 * Tp);   // the forward of the same mode kept them
+        if (saved_a) ga.a_in = saved_a + (size_t)l * a_stride;   // the forward of the same mode kept them
         else {   // a = Wd (*) h_{l-1}   (bias added in the gate kernel)
             TimeGemm t = {Wd, (long)g.K * g.Hp, g.Hp, 1, xin, xin_sb, Tp, 1, a_da, (long)H2 * Tp, Tp, nullptr, 0, 0,
                           H2, g.K, H, Tp, 1, g.K - 1, g.dil[l], 0};
@@ -2039,14 +2001,11 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
     else hipLaunchKernelGGL(input_bwd_kernel<SWN_KIND_SOFTMAX>, dim3(H, B), dim3(256), 0, st, ga, gpacked);
     // ---- frame-rate front end: cond = Wx . C ; C = conv_aux(scale_in(aux))
     {
-        const size_t bt = (size_t)B * n_frames;
-        // forward activations inside fe_work: scaled | aux conv outputs...
+        // forward activations inside fe_work (scaled | aux conv outputs...) and their gradients, in the same layout
+        const SwnFeLayout fe = swn_fe_layout(g, B, n_frames);
         const float* act[SWN_MAXAUX + 1]; float* dact[SWN_MAXAUX + 1];
-        int chn[SWN_MAXAUX + 1];
-        const float* p = fe_work; float* q = dfe;
-        chn[0] = g.n_aux; act[0] = p; dact[0] = q; p += bt * g.n_aux; q += bt * g.n_aux;
-        for (int i = 0; i < g.auxl; ++i) { chn[i + 1] = g.aux_cout[i]; act[i + 1] = p; dact[i + 1] = q; p += bt * g.aux_cout[i]; q += bt * g.aux_cout[i]; }
-        const float* C = act[g.auxl];
+        for (int i = 0; i <= g.auxl; ++i) { act[i] = fe_work + fe.act[i]; dact[i] = dfe + fe.act[i]; }
+        const float* C = fe_work + fe.C;
         if (drop_fused) {
             const int cb = (g.A0 + XM16_CC - 1) / XM16_CC;
             int FRx = (int)(((long)cb * n_frames * B) / 1024); FRx = FRx < 1 ? 1 : (FRx > 16 ? 16 : FRx);
@@ -2105,10 +2064,9 @@ extern "C" int swn_backward(const swn_net_desc* d, const float* packed, const fl
 // swn_forward_bf16 filled (bf16 time-major hidden states), fwd_work_dev its fp32 expansion (swn_bf16_work_to_f32).
 extern "C" size_t swn_backward_bf16_work_floats(const swn_net_desc* d, int batch, int n_frames) {
     SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1) return 0;
-    const long Tp = (long)n_frames * g.U - 2 * g.seg + 1;
-    if (g.kind != SWN_KIND_LAPLACE || Tp < 1 || !swn_bl6_bwd_supported(g, batch, Tp, n_frames)) return 0;
-    size_t fw = (size_t)g.n_aux; for (int i = 0; i < g.auxl; ++i) fw += g.aux_cout[i];
-    return r64((size_t)batch * n_frames * g.N) + r64(fw * batch * n_frames) + r64((swn_bl6_bwd_scratch_bytes(g, batch, Tp) + 3) / 4);
+    const SwnTrainLen n = swn_train_len(g, n_frames);
+    if (g.kind != SWN_KIND_LAPLACE || n.Tp < 1 || !swn_bl6_bwd_supported(g, batch, n.Tp, n_frames)) return 0;
+    return swn_bwd_bl6_layout(g, batch, n_frames, n, false, swn_bl6_bwd_scratch_bytes(g, batch, n.Tp, false)).total;
 }
 
 extern "C" int swn_backward_bf16(const swn_net_desc* d, const float* packed, const float* aux, const float* cond,
@@ -2133,19 +2091,14 @@ extern "C" int swn_backward_keep(const swn_net_desc* d, const float* packed, con
 }
 
 extern "C" size_t swn_backward_drop_work_floats(const swn_net_desc* d, int batch, int n_frames) {
-    SwnGeom g; if (swn_make_geom(d, &g) < 0) return 0;
-    if (!swn_backward_work_floats(d, batch, n_frames)) return 0;
-    const long T = (long)n_frames * g.U;
-    const long Tp = g.kind == SWN_KIND_SOFTMAX ? T - 1 : T - 2 * g.seg + 1;
-    // the generic chain's layout, + (seg == 1) every layer's d gx behind it
-    const size_t chain = drop_chain_floats(g, batch, n_frames) + (g.seg == 1 ? r64((size_t)batch * g.L * 2 * g.H * Tp) +
-                                                                   r64((size_t)swn_a0x(&g) * g.L * 2 * g.H / 2 + 1) : 0);   // + transposed bf16 in_x matrix
-    size_t fused = 0;                                  // the fused BL6 path: d cond (unused) | front-end gradients | d xm | its scratch
-    if (g.kind == SWN_KIND_LAPLACE && swn_bl6_bwd_supported(g, batch, Tp, n_frames)) {
-        size_t fw = (size_t)g.n_aux; for (int i = 0; i < g.auxl; ++i) fw += g.aux_cout[i];
-        fused = r64((size_t)batch * n_frames * g.N) + r64(fw * batch * n_frames) + r64((size_t)batch * swn_a0x(&g) * (T - g.seg) / 2) +
-                r64((swn_bl6_bwd_drop_scratch_bytes(g, batch, Tp) + 3) / 4);
-    }
+    SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1) return 0;
+    const SwnTrainLen n = swn_train_len(g, n_frames);
+    if (n.Tp < 1) return 0;
+    // the larger of the generic chain's layout and the fused BL6 path's
+    const size_t chain = swn_bwd_layout(g, batch, n_frames, n, true).total;
+    size_t fused = 0;
+    if (g.kind == SWN_KIND_LAPLACE && swn_bl6_bwd_supported(g, batch, n.Tp, n_frames))
+        fused = swn_bwd_bl6_layout(g, batch, n_frames, n, true, swn_bl6_bwd_scratch_bytes(g, batch, n.Tp, true)).total;
     return chain > fused ? chain : fused;
 }
 
