@@ -11,7 +11,9 @@ Harness-side shims (the reference files are not touched):
   * `torch.Tensor.cuda` -> identity, because cswnv_shift1.py:345,347 call .cuda()
     unconditionally and there is no GPU here (ordinary RuntimeError otherwise);
   * `torch.Tensor.uniform_` wrapped during generate to record the Laplace noise;
-  * a forward hook on `out_2` records the per-step head outputs.
+  * a forward hook on `out_2` records the per-step head outputs;
+  * `dswnv.OneHot` rebound with depth = n_quantize while a softmax net with n_quantize != 256 generates
+    (dswnv.py:312 relies on the default depth of 256).
 
 Usage:  python oracle/make_golden.py [--only NAME_SUBSTR] [--skip-big]
 """
@@ -73,11 +75,16 @@ def digest(a: np.ndarray) -> np.ndarray:
 
 
 def gen_laplace(name, cfg, frames, wseed, flavor, aux_seed, noise_seed, with_forward=True,
-                with_grads=False, solo_of=None):
+                with_grads=False, solo_of=None, n_steps=None, store_geometry=False, min_relu_margin=None):
+    """n_steps: decode that many steps only (every utterance min(frames * U, n_steps * seg) samples); None = all frames.
+    store_geometry: also record the reference module's receptive_field and padding list."""
     t0 = time.time()
     m, sd = build_ref(cfg, wseed, flavor)
     aux = ragged_aux(cfg, frames, aux_seed)
     n_samples = [f * cfg.U for f in frames]
+    if n_steps is not None:
+        assert max(n_samples) >= n_steps * cfg.seg
+        n_samples = [min(n, n_steps * cfg.seg) for n in n_samples]
     B = len(frames)
 
     rec, heads = [], []
@@ -111,6 +118,8 @@ def gen_laplace(name, cfg, frames, wseed, flavor, aux_seed, noise_seed, with_for
                heads=torch.stack(heads).numpy(), n_samples=np.array(n_samples))
     for b in range(B):
         out[f"samples_{b}"] = samples[b].astype(np.float32)
+    if store_geometry:
+        out["ref_rf"], out["ref_padding"] = np.int64(m.receptive_field), np.array(list(m.padding), dtype=np.int64)
 
     if with_forward:
         T = max(frames) * cfg.U
@@ -125,6 +134,10 @@ def gen_laplace(name, cfg, frames, wseed, flavor, aux_seed, noise_seed, with_for
         resc = m(torch.from_numpy(aux), torch.from_numpy(audio), do=False, clip=True)
         out["fwd_clip_n"] = len(resc)
         if with_grads:
+            if min_relu_margin is not None:
+                kink = relu_margin(cfg, sd, aux, audio)
+                assert kink >= min_relu_margin, f"{name}: a ReLU pre-activation at {kink:.1e}: pick another wseed"
+                out["relu_margin"] = np.float64(kink)
             mu, b, log_b = res[0], res[1], res[2]
             tgt = torch.from_numpy(rng.uniform(-0.9, 0.9, size=tuple(mu.shape)).astype(np.float32))
             loss = ref_c.LaplaceLoss()(mu, b, tgt, log_b=log_b, log=False)
@@ -273,19 +286,31 @@ def gen_seeded(name, cfg, frames, wseed, flavor, aux_seed, noise_seed):
 
 
 def gen_softmax(name, cfg, frames, wseed, flavor, aux_seed, noise_seed, head_stride=1,
-                with_forward=True, with_grads=False):
+                with_forward=True, with_grads=False, n_steps=None, fwd_span=64, store_q=True, store_geometry=False, min_relu_margin=None):
+    """n_steps as in gen_laplace; fwd_span: how many leading / trailing positions of the teacher-forced logits are stored;
+    store_q=False leaves the Exp(1) draws out (q_sha stays): cpu_ref.softmax_noise re-draws them from noise_seed."""
     t0 = time.time()
     m, sd = build_ref(cfg, wseed, flavor)
     aux = ragged_aux(cfg, frames, aux_seed)
     n_samples = [f * cfg.U for f in frames]
+    if n_steps is not None:
+        assert max(n_samples) >= n_steps
+        n_samples = [min(n, n_steps) for n in n_samples]
     B, Q = len(frames), cfg.n_quantize
     heads = []
     hook = m.out_2.register_forward_hook(lambda mod, i, o: heads.append(o.detach()[:, :, -1].clone()))
     torch.manual_seed(noise_seed)
+    # dswnv.py:312 calls OneHot(audio) with its default depth of 256, so batch_fast_generate as written runs at
+    # n_quantize = 256 only; for another class count the module-level name is rebound to the same function with
+    # depth = n_quantize for the duration of the call (a harness-side shim, the reference file is not touched)
+    orig_onehot = ref_d.OneHot
+    if Q != 256:
+        ref_d.OneHot = lambda x, depth=Q: orig_onehot(x, depth)
     try:
         samples = m.batch_fast_generate(torch.full((B, 1), Q // 2, dtype=torch.int64),
                                         torch.from_numpy(aux), n_samples, 4410)
     finally:
+        ref_d.OneHot = orig_onehot
         hook.remove()
     n_steps = len(heads)
     heads = torch.stack(heads).numpy()
@@ -302,10 +327,12 @@ def gen_softmax(name, cfg, frames, wseed, flavor, aux_seed, noise_seed, head_str
                q_sha=np.array(hashlib.sha256(q.tobytes()).hexdigest()),
                heads=heads[::head_stride], head_stride=head_stride,
                margin=margin.numpy().astype(np.float32), n_samples=np.array(n_samples))
-    if q.nbytes <= (1 << 20):
+    if store_q and q.nbytes <= (1 << 20):
         out["q"] = q
     for b in range(B):
         out[f"samples_{b}"] = samples[b].astype(np.int64)
+    if store_geometry:
+        out["ref_rf"], out["ref_padding"] = np.int64(m.receptive_field), np.array(list(m.padding), dtype=np.int64)
     if with_forward:
         T = max(frames) * cfg.U
         rng = np.random.Generator(np.random.PCG64([aux_seed, 5]))
@@ -316,9 +343,13 @@ def gen_softmax(name, cfg, frames, wseed, flavor, aux_seed, noise_seed, head_str
         logits = m(oh, torch.from_numpy(aux))
         out["fwd_audio_idx"] = idx_in
         out["fwd_logits_dig"] = digest(logits.detach().numpy())
-        out["fwd_logits_head"] = logits.detach().numpy()[:, :64]
-        out["fwd_logits_tail"] = logits.detach().numpy()[:, -64:]
+        out["fwd_logits_head"] = logits.detach().numpy()[:, :fwd_span]
+        out["fwd_logits_tail"] = logits.detach().numpy()[:, -fwd_span:]
         if with_grads:
+            if min_relu_margin is not None:
+                kink = relu_margin(cfg, sd, aux, idx_in)
+                assert kink >= min_relu_margin, f"{name}: a ReLU pre-activation at {kink:.1e}: pick another wseed"
+                out["relu_margin"] = np.float64(kink)
             tgt = torch.from_numpy(rng.integers(0, Q, size=(B, T - 1)).astype(np.int64))
             loss = torch.nn.CrossEntropyLoss()(logits.reshape(-1, Q), tgt.reshape(-1))
             loss.backward()
@@ -332,6 +363,68 @@ def gen_softmax(name, cfg, frames, wseed, flavor, aux_seed, noise_seed, head_str
     np.savez_compressed(os.path.join(GOLD, name + ".npz"), **out)
     print(f"[golden] {name}: steps={n_steps} B={B} {time.time() - t0:.1f}s "
           f"min margin={margin.min():.2e}")
+
+
+def relu_margin(cfg, sd, aux, audio):
+    """smallest |pre-activation| at the two ReLUs of the head (skip sum, out_1) over the teacher-forced batch, in float64.
+    Where it is ~1e-8 the fp32 summation order decides the side of the kink and with it a whole position's gradient, so
+    no elementwise bar can hold there (see the g9_drop_ref6_lap_s5l4 note below): fixtures with gradients keep clear."""
+    P = cpu_ref.as_params(sd, torch.float64)
+    with torch.no_grad():
+        if cfg.kind == "laplace":
+            audio = torch.from_numpy(audio).double()
+            x = cpu_ref._stack_seg(cfg, P, cpu_ref.upsample(cfg, P, cpu_ref.frontend(cfg, P, torch.from_numpy(aux).double()))[:, :, cfg.seg:])
+            h = torch.nn.functional.softsign(cpu_ref.causal_conv(cpu_ref._lift(cfg, P, audio), P["causal.conv.weight"],
+                                                                 P["causal.conv.bias"], 1)[:, :, cfg.seg - 1:])
+        else:
+            oh = cpu_ref.one_hot(torch.from_numpy(audio), cfg.n_quantize, dtype=torch.float64).transpose(1, 2)
+            x = cpu_ref.upsample(cfg, P, cpu_ref.frontend(cfg, P, torch.from_numpy(aux).double()))[:, :, 1:]
+            if cfg.audio_in_flag:
+                x = torch.cat((x, oh), 1)
+            h = torch.nn.functional.softsign(cpu_ref.causal_conv(cpu_ref._lift(cfg, P, oh), P["causal.conv.weight"], P["causal.conv.bias"], 1))
+        tot = None
+        for l in range(cfg.L):
+            sk, h = cpu_ref.gated_layer(cfg, P, l, x, h)
+            tot = sk if tot is None else tot + sk
+        y = torch.nn.functional.conv1d(torch.relu(tot), P["out_1.weight"], P["out_1.bias"])
+    return min(float(tot.abs().min()), float(y.abs().min()))
+
+
+def odd_nets():
+    """G10: geometries off the grid of the tiny / bl6 / ref6 families - pad lanes (H, S, out_1 width, A0 not multiples
+    of 4), an odd head width, seg between the kernels' compiled segment counts, aux kernels 1 / 5 with 1 / 3 layers,
+    BL6-shaped nets without a BL6 kernel, class counts off 64.  name -> (cfg, with_grads); every stack has L >= 3 (with
+    L <= 2 the reference's eval forward reaches dcrnn_drop, which does not exist at do_prob = 0)."""
+    lap = lambda **k: C.NetConfig(kind="laplace", **k)
+    smx = lambda **k: C.NetConfig(kind="softmax", **k)
+    nets = {
+        "g10_odd_laplace_h30_s50_seg3": (lap(n_aux=7, hid_chn=30, skip_chn=50, kernel_size=3, dilation_depth=2,
+                                             dilation_repeat=2, upsampling_factor=13, seg=3, lpc=3, aux_kernel_size=3,
+                                             aux_dilation_size=1, wav_conv_flag=True), False),
+        "g10_odd_laplace_h20_s33_k5": (lap(n_aux=3, hid_chn=20, skip_chn=33, kernel_size=5, dilation_depth=2,
+                                           dilation_repeat=2, upsampling_factor=7, seg=1, lpc=1, aux_kernel_size=5,
+                                           aux_dilation_size=2, wav_conv_flag=False), True),
+        "g10_odd_laplace_h36_seg7": (lap(n_aux=6, hid_chn=36, skip_chn=20, kernel_size=2, dilation_depth=3,
+                                         dilation_repeat=1, upsampling_factor=21, seg=7, lpc=0, aux_kernel_size=1,
+                                         aux_dilation_size=1, wav_conv_flag=True), True),
+        "g10_odd_laplace_seg4_c2d": (lap(n_aux=5, hid_chn=24, skip_chn=18, kernel_size=4, dilation_depth=1,
+                                         dilation_repeat=3, upsampling_factor=12, seg=4, lpc=5, aux_kernel_size=3,
+                                         aux_dilation_size=3, wav_conv_flag=True, aux_conv2d_flag=True), True),
+        "g10_odd_laplace_nearbl6_s144": (lap(n_aux=9, hid_chn=64, skip_chn=144, kernel_size=2, dilation_depth=6,
+                                             dilation_repeat=1, upsampling_factor=24, seg=1, lpc=0, aux_kernel_size=3,
+                                             aux_dilation_size=2, wav_conv_flag=True), True),
+        "g10_odd_laplace_nearbl6_seg2l0": (lap(n_aux=9, hid_chn=64, skip_chn=128, kernel_size=2, dilation_depth=6,
+                                               dilation_repeat=1, upsampling_factor=24, seg=2, lpc=0, aux_kernel_size=3,
+                                               aux_dilation_size=2, wav_conv_flag=True), False),
+        "g10_odd_smx_q90_h28_audioin": (smx(n_aux=5, hid_chn=28, skip_chn=30, kernel_size=2, dilation_depth=4,
+                                            dilation_repeat=1, upsampling_factor=9, n_quantize=90, aux_kernel_size=3,
+                                            aux_dilation_size=2, wav_conv_flag=False, audio_in_flag=True), True),
+        "g10_odd_smx_q300_h44_wav": (smx(n_aux=4, hid_chn=44, skip_chn=70, kernel_size=3, dilation_depth=2,
+                                         dilation_repeat=2, upsampling_factor=11, n_quantize=300, aux_kernel_size=3,
+                                         aux_dilation_size=1, wav_conv_flag=True), True),
+    }
+    assert all(cfg.L >= 3 for cfg, _ in nets.values())
+    return nets
 
 
 def gen_dropout(name, cfg, frames, wseed, flavor, aux_seed, drop_seed, p, do=True, big=False):
@@ -695,6 +788,22 @@ def main():
         jobs.append(("g9_drop_ref6_lap_s5l4", gen_dropout,
                      dict(cfg=C.ref6_laplace(5, 4), frames=[9, 8], wseed=78, flavor="trained", aux_seed=12, drop_seed=84,
                           p=0.5, big=True)))
+    # ---- G10: off-grid geometries, B = 2 ragged, (rf + 2U) // seg decode steps: past the receptive field and two frame
+    # boundaries.  Laplace nets carry trained-flavour weights, softmax nets xavier ones (top-2 margins stay above 1e-4)
+    for i, (name, (cfg, grads)) in enumerate(odd_nets().items()):
+        seg = cfg.seg if cfg.kind == "laplace" else 1
+        steps = (cfg.receptive_field + 2 * cfg.U) // seg
+        long = -(-steps * seg // cfg.U)                       # frames the decode needs
+        # weights: seed 91 + i, or the next one in steps of 100 at which no head ReLU of the gradient batch sits within 1e-6 of
+        # its kink (at 97 one out_1 pre-activation of the q90 net is 9.0e-9, at 98 one of the q300 net 1.6e-7: the fp32
+        # summation order then decides a whole position's gradient, the case the g9 note below describes)
+        wseed = {"g10_odd_smx_q90_h28_audioin": 191, "g10_odd_smx_q300_h44_wav": 198}.get(name, 91 + i)
+        kw = dict(cfg=cfg, frames=[long, long - 1], wseed=wseed, aux_seed=14, min_relu_margin=1e-6, noise_seed=41 + i, with_forward=True,
+                  with_grads=grads, n_steps=steps, store_geometry=True)
+        if cfg.kind == "laplace":
+            jobs.append((name, gen_laplace, dict(kw, flavor="trained")))
+        else:
+            jobs.append((name, gen_softmax, dict(kw, flavor="xavier", fwd_span=16, store_q=False)))
     for name, fn, kw in jobs:
         if args.only and args.only not in name:
             continue

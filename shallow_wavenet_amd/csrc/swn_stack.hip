@@ -355,6 +355,12 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
             return SWN_E_UNSUPPORTED;
         }
     }
+    // the skip GEMM reads the L hidden states as one (L*H)-row operand against wsk rows of L*Hp floats: H % 4 == 0 only.
+    // Refused here, ahead of the first launch, as swn_backward does: no buffer of the caller is touched.
+    if (g.Hp != g.H) {
+        swn_set_error_detail(where, "hid_chn is not a multiple of 4: the teacher-forced stack does not serve this net (nothing was launched)");
+        return SWN_E_UNSUPPORTED;
+    }
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();   // drop stale errors of earlier runtime calls; only our launches are reported
     const bool bf16 = swn_call_mode() == SWN_PRECISION_BF16;
@@ -425,8 +431,7 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
         else hipLaunchKernelGGL(tf_layer_kernel<SWN_KIND_SOFTMAX>, grid, dim3(256), 0, st, a, l, in_mul);
     }
     const size_t hstride = (size_t)(g.L + 1) * g.H * Tp;
-    // skip: one GEMM over the L concatenated (undropped) hidden states (requires Hp == H, i.e. H % 4 == 0)
-    if (g.Hp != g.H) return SWN_E_UNSUPPORTED;
+    // skip: one GEMM over the L concatenated (undropped) hidden states (Hp == H, checked ahead of the first launch)
     if (fwd16 && !hs) {
         // mixed-precision mode: the two wide 1x1 layers as bf16-operand time GEMMs with bias + relu epilogues (0.5 ms each as
         // exact-fp32 gemm_wx at the run.sh geometry); out_2 (<= 16 rows) stays below

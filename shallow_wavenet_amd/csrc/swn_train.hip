@@ -1757,7 +1757,11 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
     const bool drop = drop_x != nullptr;
     if (!packed || !aux || (!drop && !cond) || (drop && !drop_h) || !fe_work || !audio || (!fwd_work && !hs_bf16) || !grad_out || !work ||
         !gpacked || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
-    if (g.Hp != g.H || g.K > 8 || g.U > 256) return SWN_E_UNSUPPORTED;
+    if (g.Hp != g.H || g.K > 8 || g.U > 256) {
+        swn_set_error_detail(where, g.Hp != g.H ? "hid_chn is not a multiple of 4: the backward does not serve this net (nothing was launched)"
+                                                : "kernel_size > 8 or upsampling_factor > 256: the backward does not serve this net (nothing was launched)");
+        return SWN_E_UNSUPPORTED;
+    }
     swn_make_layout(&ga.g, &ga.y);
     const SwnLayout& y = ga.y;
     const SwnTrainLen n = swn_train_len(g, n_frames);

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from conftest import golden_names, load_golden
 from shallow_wavenet_amd import config as C
 from shallow_wavenet_amd.nets._autograd import unfold_packed_grads, unfold_packed_grads_device
 from shallow_wavenet_amd.runtime import HipNet
@@ -21,6 +22,10 @@ CASES = {
     "tiny_lap_nowav": C.tiny("laplace", wav_conv_flag=False), "tiny_softmax_nowav": C.tiny("softmax", wav_conv_flag=False),
     "tiny_softmax_audio_in": C.tiny("softmax", audio_in_flag=True),
 }
+# the off-grid nets of the g10 fixtures that the device unfold serves (all but the aux_conv2d one): padded rows in the
+# packed gradient, aux kernels 1 / 5, class counts off 64
+CASES.update({n[len("g10_"):]: cfg for n, cfg in ((n, load_golden(n)[0]) for n in golden_names("g10_odd_"))
+              if not (cfg.kind == "laplace" and cfg.aux_conv2d_flag and cfg.seg > 1)})
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
