@@ -678,6 +678,52 @@ size_t swn_logmel_work_bytes(int n_fft, int hop, const swn_logmel_entry* entries
 int    swn_logmel(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev, const int32_t* bank_host,
                   const swn_logmel_entry* entries_host, int n_entries, float* work_dev, void* stream);
 
+/* ---- log-mel pool: the new frames of many sessions per call (melspec.LogMelPool; csrc/swn_melspec.hip) -----------------------
+ * Every session owns one slot of win_dev: window_floats floats (swn_logmel_pool_window_floats(n_fft, max_chunk) = n_fft +
+ * max_chunk: under the streaming rule of melspec.py a session holds at most n_fft samples between calls) that hold the tail
+ * of its signal from the window's first float on.  new_dev is one staged buffer with the new samples of all entries, out_dev
+ * one output buffer.  Entry e (HOST table, at most SWN_LOGMEL_POOL_MAX_ENTRIES, integers only, carried in the launch
+ * arguments: no host copy, no synchronisation) says: before the call the window of `slot` holds the n_held samples from the
+ * ABSOLUTE index t0 on.  The call
+ *   1. drops n_drop samples from the window's front and appends the n_new samples at new_dev + new_off, so that the window
+ *      holds the samples [t0 + n_drop, t0 + n_held + n_new) from its first float, and then
+ *   2. computes the frames [f0, f1) from it, with the definition and the arithmetic of swn_logmel (a frame has the bits
+ *      swn_logmel gives it), and writes frame f, filter m at out_dev[out_off + m * out_stride + (f - f0)]: channel-major,
+ *      the (n_aux, frames) layout swn_frontend_pool stages.
+ * len is the signal's total length, or -1 while it is not known.  Two launches at most (the window update, one block per
+ * entry; the frame kernel), no copy; an entry without frames only updates its window, a call in which nothing moves and no
+ * frame is due launches nothing.  The kernels read no window float outside the held range and write none outside
+ * [0, n_held - n_drop + n_new).  The caller answers for win_dev holding a window for every slot it names and out_dev for
+ * every range.
+ * work_dev: swn_logmel_pool_work_bytes of scratch.
+ * SWN_E_BADARG, found on the host before anything is launched, text in swn_last_error_detail: a null pointer (new_dev only
+ * where an entry has new samples; out_dev, tables_dev and work_dev only where a frame is due), n_entries out of range, a slot
+ * named twice or negative, a negative count or offset, n_drop > n_held, n_held or n_held - n_drop + n_new beyond
+ * window_floats, window_floats outside [1, 2^24], a non-zero reserved field, output rows of two entries (or of one:
+ * out_stride < f1 - f0) that overlap, and every rule of swn_logmel for n_fft, hop, n_mels, floor, linear, the bank, len and
+ * the frame range, applied to the updated window: a frame whose samples (the reflected ones included) are not all in it,
+ * f1 > 1 + len / hop, a frame that needs the reflected end while len is -1.
+ * The size queries return 0 for arguments the call refuses.  sizeof(swn_logmel_pool_entry) == 48. */
+typedef struct swn_logmel_pool_entry {
+    int32_t slot;              /* which window of win_dev */
+    int32_t t0;                /* absolute index of the window's first sample before the call */
+    int32_t n_held;            /* samples in the window before the call */
+    int32_t n_drop;            /* samples to discard from its front, <= n_held */
+    int32_t new_off, n_new;    /* the entry's new samples: new_dev + new_off, n_new of them */
+    int32_t len;               /* total length of the signal, or -1: not known yet */
+    int32_t f0, f1;            /* frames to compute, 0 <= f0 <= f1 */
+    int32_t out_off;           /* frame f0 of filter 0 in out_dev */
+    int32_t out_stride;        /* floats between two filters' rows, >= f1 - f0 */
+    int32_t reserved;          /* 0 */
+} swn_logmel_pool_entry;
+#define SWN_LOGMEL_POOL_MAX_ENTRIES 64
+size_t swn_logmel_pool_window_floats(int n_fft, int max_chunk);
+size_t swn_logmel_pool_work_bytes(int n_fft, int hop, int n_mels, size_t window_floats,
+                                  const swn_logmel_pool_entry* entries_host, int n_entries);
+int    swn_logmel_pool(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev,
+                       const int32_t* bank_host, float* win_dev, size_t window_floats, const float* new_dev, float* out_dev,
+                       const swn_logmel_pool_entry* entries_host, int n_entries, float* work_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,12 @@ class LogMelEntry(ctypes.Structure):
                 ("f0", c_int32), ("f1", c_int32), ("reserved", c_int32)]
 
 
+class LogMelPoolEntry(ctypes.Structure):
+    """mirror of `swn_logmel_pool_entry` (include/swn_hip.h): one session's share of a log-mel pool call."""
+    _fields_ = [(n, c_int32) for n in ("slot", "t0", "n_held", "n_drop", "new_off", "n_new", "len", "f0", "f1", "out_off",
+                                       "out_stride", "reserved")]
+
+
 ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
 DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
@@ -89,6 +95,7 @@ POSTFILTER_MAX_TAPS = 256                      # SWN_POSTFILTER_MAX_TAPS
 POSTFILTER_MULAW_ENTRIES = 256                 # SWN_POSTFILTER_MULAW_ENTRIES
 SPECTRAL_MAX_SIZES, SPECTRAL_MAX_FFT = 32, 2048   # SWN_SPECTRAL_MAX_SIZES, SWN_SPECTRAL_MAX_FFT
 LOGMEL_MAX_MELS, LOGMEL_MAX_ENTRIES = 128, 64     # SWN_LOGMEL_MAX_MELS, SWN_LOGMEL_MAX_ENTRIES
+LOGMEL_POOL_MAX_ENTRIES = 64                   # SWN_LOGMEL_POOL_MAX_ENTRIES (include/swn_hip.h): entries per log-mel pool call
 
 
 def desc_from_cfg(cfg: NetConfig) -> NetDesc:
@@ -207,6 +214,10 @@ SIGNATURES = {
     "swn_logmel_work_bytes": (c_size_t, [c_int, c_int, POINTER(LogMelEntry), c_int]),
     "swn_logmel": (c_int, [c_int, c_int, c_int, c_float, c_int, c_void_p, POINTER(c_int32), POINTER(LogMelEntry), c_int,
                            c_void_p, c_void_p]),
+    "swn_logmel_pool_window_floats": (c_size_t, [c_int, c_int]),
+    "swn_logmel_pool_work_bytes": (c_size_t, [c_int, c_int, c_int, c_size_t, POINTER(LogMelPoolEntry), c_int]),
+    "swn_logmel_pool": (c_int, [c_int, c_int, c_int, c_float, c_int, c_void_p, POINTER(c_int32), c_void_p, c_size_t, c_void_p,
+                                c_void_p, POINTER(LogMelPoolEntry), c_int, c_void_p, c_void_p]),
 }
 
 

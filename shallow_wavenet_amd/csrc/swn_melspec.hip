@@ -27,10 +27,19 @@
 // Entries (swn_logmel_entry, host memory, checked before the launch and carried in the kernel arguments): a window
 // [t0, t0 + n_avail) onto each row's samples, the row's total length or -1 while unknown, and a frame range [f0, f1).
 // The kernel reads no sample outside the window; the rows of a tile past f1 are zero.
+//
+// Pool (swn_logmel_pool, melspec.LogMelPool): every session keeps the tail of its signal in a window of its own on the
+// device.  A call is two launches.  logmel_pool_update_kernel, one block per entry, moves the retained floats
+// [n_drop, n_held) to the window's front (ascending blocks of 256 floats, each read whole before it is written: a block's
+// destination lies below every later block's source) and appends the entry's new samples from the staged buffer.  Then
+// logmel_kernel<true> computes the frames from the updated windows with the arithmetic of swn_logmel and writes them
+// channel-major, out[m * out_stride + (f - f0)]: the layout the pool front end stages.
 #include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
 #include "swn_mma.hpp"
 #include <cstdio>
+#include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -42,7 +51,7 @@ struct LmEntry {
     const float* wav;   // sample t0
     float* out;         // frame f0
     int t0, len, f0, f1, tile0;
-    int pad;
+    int stride;         // channel-major output only: floats between two filters' rows
 };
 struct LmArgs {
     LmEntry e[SWN_LOGMEL_MAX_ENTRIES];
@@ -51,6 +60,18 @@ struct LmArgs {
     int n_entries, n, hop, n_mels, linear;
     float floor_;
 };
+static_assert(sizeof(LmArgs) + 2 * sizeof(void*) <= 4096, "the by-value kernel arguments must stay inside 4 KB");
+
+struct LpMove {
+    int slot, n_held, n_drop, new_off, n_new;
+};
+struct LpArgs {
+    LpMove e[SWN_LOGMEL_POOL_MAX_ENTRIES];
+    int window_floats;
+};
+static_assert(sizeof(LpArgs) + 2 * sizeof(void*) <= 4096, "the by-value kernel arguments must stay inside 4 KB");
+constexpr int LP_MAX_WINDOW = 1 << 24;      // floats per slot
+static_assert(SWN_LOGMEL_POOL_MAX_ENTRIES <= SWN_LOGMEL_MAX_ENTRIES, "a pool call's entries are one frame launch");
 
 __host__ __device__ inline int lm_pitch(int n) { return n + 2; }
 __host__ __device__ inline int lm_amp_pitch(int n) { return (n / 2 + 1 + 3) & ~3; }
@@ -59,8 +80,15 @@ __host__ __device__ inline size_t lm_lds_floats(int n) {
     return (size_t)LM_FR * lm_pitch(n) + n + 2 * (n / 2 + 1) + 2 * SWN_LOGMEL_MAX_MELS;
 }
 
+thread_local const char* lm_who = "swn_logmel";      // the entry point the checks below report for
+struct LmWho {
+    const char* before;
+    explicit LmWho(const char* who) : before(lm_who) { lm_who = who; }
+    ~LmWho() { lm_who = before; }
+};
+
 int lm_fail(const char* what) {
-    swn_set_error_detail("swn_logmel", what);
+    swn_set_error_detail(lm_who, what);
     return SWN_E_BADARG;
 }
 
@@ -69,7 +97,7 @@ bool lm_sizes_ok(int n_fft, int n_mels) {
 }
 
 // the entry rules; *tiles receives the number of frame tiles of the call
-int lm_check_entries(int n, int hop, const swn_logmel_entry* en, int n_entries, long long* tiles) {
+int lm_check_entries(int n, int hop, const swn_logmel_entry* en, int n_entries, long long* tiles, bool need_pointers = true) {
     char msg[160];
     if (!en) return lm_fail("entries_host is NULL");
     if (n_entries < 1 || n_entries > SWN_LOGMEL_MAX_ENTRIES) return lm_fail("n_entries outside [1, SWN_LOGMEL_MAX_ENTRIES]");
@@ -89,7 +117,7 @@ int lm_check_entries(int n, int hop, const swn_logmel_entry* en, int n_entries, 
             return lm_fail(msg);
         }
         if (e.f1 == e.f0) continue;
-        if (!e.wav_dev || !e.out_dev) { snprintf(msg, sizeof msg, "entry %d: null pointer", i); return lm_fail(msg); }
+        if (need_pointers && (!e.wav_dev || !e.out_dev)) { snprintf(msg, sizeof msg, "entry %d: null pointer", i); return lm_fail(msg); }
         if (e.len != -1 && e.f1 > 1 + e.len / hop) {
             snprintf(msg, sizeof msg, "entry %d: f1 = %d, a signal of %d samples has %d frames", i, e.f1, e.len, 1 + e.len / hop);
             return lm_fail(msg);
@@ -124,6 +152,8 @@ int lm_check_entries(int n, int hop, const swn_logmel_entry* en, int n_entries, 
     return SWN_OK;
 }
 
+// CM: the output is channel-major (swn_logmel_pool), else time-major (swn_logmel); nothing else differs
+template <bool CM>
 __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const LmArgs a, const float* __restrict__ tables, float* amp_work) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int n = a.n, hop = a.hop, pitch = lm_pitch(n), bins = n / 2 + 1, ap = lm_amp_pitch(n);
@@ -224,15 +254,36 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const LmArgs a, cons
 
     const int fr_n = e.f1 - fbase < LM_FR ? e.f1 - fbase : LM_FR;     // frames of this tile that exist (>= 1)
     for (int o = tid; o < fr_n * a.n_mels; o += LM_THREADS) {
-        const int fr = o / a.n_mels, m = o - fr * a.n_mels;
+        // channel-major: frames fastest, so that neighbouring lanes store neighbouring floats of a filter's row
+        const int fr = CM ? o % fr_n : o / a.n_mels, m = CM ? o / fr_n : o - fr * a.n_mels;
         const int start = sbank[m] & 0xffff, cnt = sbank[m] >> 16;
         const float* ar = amp + fr * ap + start;
         const float* wr = wts + woff[m];
         float s = 0.f;
         for (int k = 0; k < cnt; ++k) s = fmaf(wr[k], ar[k], s);
         // the log in double, rounded once: logf lands up to 2 ulp from ln (measured at the floor), and a frame costs n_mels of these
-        e.out[(size_t)(fbase - e.f0 + fr) * a.n_mels + m] = a.linear ? s : (float)log((double)fmaxf(s, a.floor_));
+        const float v = a.linear ? s : (float)log((double)fmaxf(s, a.floor_));
+        if (CM) e.out[(size_t)m * e.stride + (fbase - e.f0 + fr)] = v;
+        else e.out[(size_t)(fbase - e.f0 + fr) * a.n_mels + m] = v;
     }
+}
+
+// one block per entry: window[0 .. n_held - n_drop) <- window[n_drop .. n_held), then the n_new staged samples after them
+__global__ __launch_bounds__(LM_THREADS) void logmel_pool_update_kernel(const LpArgs a, float* __restrict__ win,
+                                                                         const float* __restrict__ staged) {
+    const LpMove e = a.e[blockIdx.x];
+    float* w = win + (size_t)e.slot * a.window_floats;
+    const int keep = e.n_held - e.n_drop, tid = threadIdx.x;
+    if (e.n_drop > 0) {
+        for (int base = 0; base < keep; base += LM_THREADS) {      // uniform trip count: every thread meets the barrier
+            const int i = base + tid;
+            const float v = i < keep ? w[i + e.n_drop] : 0.f;
+            __syncthreads();                    // the block [base, base + 256) is read whole before any of it is written
+            if (i < keep) w[i] = v;
+        }
+        __syncthreads();                        // the new samples may land on floats the last blocks still read
+    }
+    for (int i = tid; i < e.n_new; i += LM_THREADS) w[keep + i] = staged[e.new_off + i];
 }
 
 }  // namespace
@@ -249,20 +300,21 @@ extern "C" size_t swn_logmel_work_bytes(int n_fft, int hop, const swn_logmel_ent
     return (size_t)tiles * LM_FR * lm_amp_pitch(n_fft) * sizeof(float);
 }
 
-extern "C" int swn_logmel(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev,
-                          const int32_t* bank_host, const swn_logmel_entry* entries_host, int n_entries, float* work_dev,
-                          void* stream) {
+namespace {
+
+int lm_check_sizes(int n_fft, int n_mels, float floor, int linear) {
     if (n_fft < 32 || n_fft > SWN_SPECTRAL_MAX_FFT || n_fft % 32 != 0)
         return lm_fail("n_fft is not a multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT]");
     if (n_mels < 1 || n_mels > SWN_LOGMEL_MAX_MELS) return lm_fail("n_mels outside [1, SWN_LOGMEL_MAX_MELS]");
     if (!(floor > 0.f) || !(floor < 3.0e38f)) return lm_fail("floor must be a finite number > 0");
     if (linear != 0 && linear != 1) return lm_fail("linear must be 0 or 1");
-    long long tiles = 0;
-    const int rc = lm_check_entries(n_fft, hop, entries_host, n_entries, &tiles);
-    if (rc != SWN_OK) return rc;
+    return SWN_OK;
+}
+
+// the filters' runs into the launch arguments
+int lm_fill_bank(LmArgs& a, int n_fft, int n_mels, const int32_t* bank_host) {
     if (!bank_host) return lm_fail("bank_host is NULL");
     const int bins = n_fft / 2 + 1;
-    LmArgs a;
     int nnz = 0;
     for (int m = 0; m < n_mels; ++m) {
         const int start = bank_host[m] & 0xffff, cnt = (int)((unsigned)bank_host[m] >> 16);
@@ -277,27 +329,187 @@ extern "C" int swn_logmel(int n_fft, int hop, int n_mels, float floor, int linea
     }
     if (nnz > 2 * bins) return lm_fail("the filter runs hold more than 2 (n_fft / 2 + 1) weights");
     for (int m = n_mels; m < SWN_LOGMEL_MAX_MELS; ++m) a.bank[m] = a.woff[m] = 0;
-    if (tiles == 0) return SWN_OK;                          // no frame in any entry
-    if (!tables_dev || !work_dev) return lm_fail("null pointer");
+    return SWN_OK;
+}
+
+// the entries into the launch arguments (stride: channel-major calls), then the frame kernel
+template <bool CM>
+int lm_launch(LmArgs& a, int n_fft, int hop, int n_mels, float floor, int linear, const swn_logmel_entry* en, const int* strides,
+              int n_entries, long long tiles, const float* tables_dev, float* work_dev, hipStream_t st, const char* who) {
     int t = 0;
     for (int i = 0; i < SWN_LOGMEL_MAX_ENTRIES; ++i) {
         LmEntry& o = a.e[i];
         if (i < n_entries) {
-            const swn_logmel_entry& e = entries_host[i];
-            o.wav = e.wav_dev; o.out = e.out_dev; o.t0 = e.t0; o.len = e.len; o.f0 = e.f0; o.f1 = e.f1; o.tile0 = t; o.pad = 0;
+            const swn_logmel_entry& e = en[i];
+            o.wav = e.wav_dev; o.out = e.out_dev; o.t0 = e.t0; o.len = e.len; o.f0 = e.f0; o.f1 = e.f1; o.tile0 = t;
+            o.stride = strides ? strides[i] : 0;
             t += (e.f1 - e.f0 + LM_FR - 1) / LM_FR;
         } else {
-            o.wav = nullptr; o.out = nullptr; o.t0 = o.len = o.f0 = o.f1 = o.pad = 0; o.tile0 = t;
+            o.wav = nullptr; o.out = nullptr; o.t0 = o.len = o.f0 = o.f1 = o.stride = 0; o.tile0 = t;
         }
     }
     a.n_entries = n_entries; a.n = n_fft; a.hop = hop; a.n_mels = n_mels; a.linear = linear; a.floor_ = floor;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
     const size_t lds = lm_lds_floats(n_fft) * sizeof(float);
     // dynamic LDS from 64 KB on: set on every call (the attribute is per device)
-    if (lds >= 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel),
+    if (lds >= 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(logmel_kernel<CM>),
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return swn_launch_status("swn_logmel (LDS size)");
-    hipLaunchKernelGGL(logmel_kernel, dim3((unsigned)tiles), dim3(LM_THREADS), lds, st, a, tables_dev, work_dev);
-    return swn_launch_status("swn_logmel");
+        return swn_launch_status(CM ? "swn_logmel_pool (LDS size)" : "swn_logmel (LDS size)");
+    hipLaunchKernelGGL(logmel_kernel<CM>, dim3((unsigned)tiles), dim3(LM_THREADS), lds, st, a, tables_dev, work_dev);
+    return swn_launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int swn_logmel(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev,
+                          const int32_t* bank_host, const swn_logmel_entry* entries_host, int n_entries, float* work_dev,
+                          void* stream) {
+    int rc = lm_check_sizes(n_fft, n_mels, floor, linear);
+    if (rc != SWN_OK) return rc;
+    long long tiles = 0;
+    rc = lm_check_entries(n_fft, hop, entries_host, n_entries, &tiles);
+    if (rc != SWN_OK) return rc;
+    LmArgs a;
+    rc = lm_fill_bank(a, n_fft, n_mels, bank_host);
+    if (rc != SWN_OK) return rc;
+    if (tiles == 0) return SWN_OK;                          // no frame in any entry
+    if (!tables_dev || !work_dev) return lm_fail("null pointer");
+    (void)hipGetLastError();
+    return lm_launch<false>(a, n_fft, hop, n_mels, floor, linear, entries_host, nullptr, n_entries, tiles, tables_dev, work_dev,
+                            static_cast<hipStream_t>(stream), "swn_logmel");
+}
+
+// ------------------------------------------------------------------------------------------------------------------ pool
+namespace {
+
+// every rule of a pool call that needs no device pointer; rows[i] receives entry i as the frame kernel takes it (the window
+// after the update, pointers left null) and *tiles the frame tiles of the call
+int lp_check(int n_fft, int hop, int n_mels, size_t window_floats, const swn_logmel_pool_entry* en, int n_entries,
+             swn_logmel_entry* rows, long long* tiles) {
+    char msg[200];
+    if (!en) return lm_fail("entries_host is NULL");
+    if (n_entries < 1 || n_entries > SWN_LOGMEL_POOL_MAX_ENTRIES)
+        return lm_fail("n_entries outside [1, SWN_LOGMEL_POOL_MAX_ENTRIES]");
+    if (window_floats < 1 || window_floats > (size_t)LP_MAX_WINDOW) return lm_fail("window_floats outside [1, 2^24]");
+    for (int i = 0; i < n_entries; ++i) {
+        const swn_logmel_pool_entry& e = en[i];
+        if (e.reserved != 0) { snprintf(msg, sizeof msg, "entry %d: reserved field is not 0", i); return lm_fail(msg); }
+        if (e.slot < 0) { snprintf(msg, sizeof msg, "entry %d: slot %d", i, e.slot); return lm_fail(msg); }
+        for (int j = 0; j < i; ++j)
+            if (en[j].slot == e.slot) {
+                snprintf(msg, sizeof msg, "entries %d and %d name slot %d: a slot takes one entry per call", j, i, e.slot);
+                return lm_fail(msg);
+            }
+        if (e.t0 < 0 || e.n_held < 0 || e.n_drop < 0 || e.new_off < 0 || e.n_new < 0 || e.out_off < 0 || e.out_stride < 0) {
+            snprintf(msg, sizeof msg, "entry %d: a negative count or offset (t0 %d, n_held %d, n_drop %d, new_off %d, n_new %d, "
+                     "out_off %d, out_stride %d)", i, e.t0, e.n_held, e.n_drop, e.new_off, e.n_new, e.out_off, e.out_stride);
+            return lm_fail(msg);
+        }
+        if (e.n_drop > e.n_held) {
+            snprintf(msg, sizeof msg, "entry %d: n_drop %d exceeds the %d samples held", i, e.n_drop, e.n_held);
+            return lm_fail(msg);
+        }
+        const long long after = (long long)e.n_held - e.n_drop + e.n_new;
+        if ((size_t)e.n_held > window_floats || (size_t)after > window_floats) {
+            snprintf(msg, sizeof msg, "entry %d: %d held - %d dropped + %d new samples do not fit the window of %zu floats", i,
+                     e.n_held, e.n_drop, e.n_new, window_floats);
+            return lm_fail(msg);
+        }
+        if ((long long)e.new_off + e.n_new > (1LL << 30)) {
+            snprintf(msg, sizeof msg, "entry %d: new_off + n_new beyond 2^30", i);
+            return lm_fail(msg);
+        }
+        if ((long long)e.t0 + e.n_drop > LM_MAX_LEN) { snprintf(msg, sizeof msg, "entry %d: t0 + n_drop beyond 2^30", i); return lm_fail(msg); }
+        swn_logmel_entry& r = rows[i];
+        r.wav_dev = nullptr; r.out_dev = nullptr; r.len = e.len; r.f0 = e.f0; r.f1 = e.f1; r.reserved = 0;
+        r.t0 = e.t0 + e.n_drop;
+        r.n_avail = (int32_t)after;
+    }
+    const int rc = lm_check_entries(n_fft, hop, rows, n_entries, tiles, false);
+    if (rc != SWN_OK) return rc;
+    // the filters' rows of all entries, sorted by their first float: neighbours must not overlap
+    struct Row { long long begin, end; int entry; };
+    std::vector<Row> span;
+    span.reserve((size_t)n_entries * n_mels);
+    for (int i = 0; i < n_entries; ++i) {
+        const int nf = en[i].f1 - en[i].f0;
+        if (nf == 0) continue;
+        if ((long long)en[i].out_off + (long long)(n_mels - 1) * en[i].out_stride + nf > (1LL << 31) - 1) {
+            snprintf(msg, sizeof msg, "entry %d: the output range ends beyond 2^31 floats", i);
+            return lm_fail(msg);
+        }
+        for (int m = 0; m < n_mels; ++m) {
+            const long long begin = (long long)en[i].out_off + (long long)m * en[i].out_stride;
+            span.push_back(Row{begin, begin + nf, i});
+        }
+    }
+    std::sort(span.begin(), span.end(), [](const Row& x, const Row& y) { return x.begin < y.begin; });
+    for (size_t k = 1; k < span.size(); ++k)
+        if (span[k].begin < span[k - 1].end) {
+            snprintf(msg, sizeof msg, "the output ranges of entries %d and %d overlap at float %lld (out_off, out_stride and "
+                     "the frame counts)", span[k - 1].entry, span[k].entry, span[k].begin);
+            return lm_fail(msg);
+        }
+    return SWN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t swn_logmel_pool_window_floats(int n_fft, int max_chunk) {
+    if (!lm_sizes_ok(n_fft, 1) || max_chunk < 1 || (long long)n_fft + max_chunk > LP_MAX_WINDOW) return 0;
+    return (size_t)n_fft + (size_t)max_chunk;       // one window: what a session holds between calls plus one chunk
+}
+
+extern "C" size_t swn_logmel_pool_work_bytes(int n_fft, int hop, int n_mels, size_t window_floats,
+                                             const swn_logmel_pool_entry* entries_host, int n_entries) {
+    LmWho who("swn_logmel_pool_work_bytes");
+    swn_logmel_entry rows[SWN_LOGMEL_POOL_MAX_ENTRIES];
+    long long tiles = 0;
+    if (!lm_sizes_ok(n_fft, n_mels) || lp_check(n_fft, hop, n_mels, window_floats, entries_host, n_entries, rows, &tiles) != SWN_OK)
+        return 0;
+    return (size_t)tiles * LM_FR * lm_amp_pitch(n_fft) * sizeof(float);
+}
+
+extern "C" int swn_logmel_pool(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev,
+                               const int32_t* bank_host, float* win_dev, size_t window_floats, const float* new_dev,
+                               float* out_dev, const swn_logmel_pool_entry* entries_host, int n_entries, float* work_dev,
+                               void* stream) {
+    LmWho who("swn_logmel_pool");
+    int rc = lm_check_sizes(n_fft, n_mels, floor, linear);
+    if (rc != SWN_OK) return rc;
+    swn_logmel_entry rows[SWN_LOGMEL_POOL_MAX_ENTRIES];
+    long long tiles = 0;
+    rc = lp_check(n_fft, hop, n_mels, window_floats, entries_host, n_entries, rows, &tiles);
+    if (rc != SWN_OK) return rc;
+    LmArgs a;
+    rc = lm_fill_bank(a, n_fft, n_mels, bank_host);
+    if (rc != SWN_OK) return rc;
+    LpArgs u;
+    int strides[SWN_LOGMEL_POOL_MAX_ENTRIES];
+    bool moves = false, news = false;
+    for (int i = 0; i < SWN_LOGMEL_POOL_MAX_ENTRIES; ++i) {
+        const bool in = i < n_entries;
+        const swn_logmel_pool_entry* e = in ? entries_host + i : nullptr;
+        u.e[i] = in ? LpMove{e->slot, e->n_held, e->n_drop, e->new_off, e->n_new} : LpMove{0, 0, 0, 0, 0};
+        strides[i] = in ? e->out_stride : 0;
+        if (in) {
+            moves = moves || e->n_new > 0 || (e->n_drop > 0 && e->n_held > e->n_drop);
+            news = news || e->n_new > 0;
+        }
+    }
+    u.window_floats = (int)window_floats;
+    if (!win_dev || (news && !new_dev) || (tiles > 0 && (!tables_dev || !work_dev || !out_dev))) return lm_fail("null pointer");
+    for (int i = 0; i < n_entries; ++i) {
+        rows[i].wav_dev = win_dev + (size_t)entries_host[i].slot * window_floats;
+        rows[i].out_dev = out_dev ? out_dev + entries_host[i].out_off : nullptr;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    (void)hipGetLastError();
+    if (moves) {
+        hipLaunchKernelGGL(logmel_pool_update_kernel, dim3((unsigned)n_entries), dim3(LM_THREADS), 0, st, u, win_dev, new_dev);
+        rc = swn_launch_status("swn_logmel_pool (window update)");
+        if (rc != SWN_OK) return rc;
+    }
+    if (tiles == 0) return SWN_OK;                          // no frame in any entry
+    return lm_launch<true>(a, n_fft, hop, n_mels, floor, linear, rows, strides, n_entries, tiles, tables_dev, work_dev, st,
+                           "swn_logmel_pool");
 }

@@ -5,6 +5,8 @@ fully pinned feature type next to the WORLD / SPTK features of run.sh stage 1 (w
     feats = ext(wavs, lengths)                 # (R, F_max, n_mels), time-major like the feature files; zero past a row's frames
     stream = LogMelStream(ext)                 # the same frames, as the samples arrive
     new = stream.push(chunk); ...; last = stream.finish()
+    mels = LogMelPool(ext, capacity=64, max_chunk=4096)        # ... for many signals at once, one call per tick
+    m = mels.open(); new = mels.push_many({m: chunk, ...}, finish=[...])       # {session: (1, n_mels, k)}: what the decode pools take
 
 Definition (the contract; include/swn_hip.h and csrc/swn_melspec.hip restate it).  Parameters: `fs` sample rate; `n_fft` a
 multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT]; `hop` in 1 .. n_fft, which need not divide n_fft (the 22.05 kHz nets use 110,
@@ -29,7 +31,7 @@ concatenated output is bit-identical to the one-shot call.  There is no torch fa
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -162,6 +164,24 @@ class LogMelExtractor:
         return out[0] if one else out
 
 
+# ---- the streaming rule: the one place LogMelStream and LogMelPool take it from ------------------------------------------
+def frames_ready(n_fft: int, hop: int, n_received: int, final: bool = False) -> int:
+    """frames of a signal that can be computed once n_received samples are there.  While it goes on, those whose samples have
+    all arrived: frame 0 reads up to sample n_fft / 2 (the left reflection), frame f >= 1 up to f hop + n_fft / 2 - 1.  When
+    it ends there (`final`), all F = 1 + n_received // hop: the last ones read the reflected end."""
+    if final:
+        return frame_count(n_received, hop)
+    half = n_fft // 2
+    return 0 if n_received <= half else 1 + (n_received - half) // hop
+
+
+def keep_from(n_fft: int, hop: int, t0: int, n_frames: int) -> int:
+    """absolute index of the first sample a signal still needs after n_frames frames, when its buffer starts at t0: the next
+    frame starts at n_frames hop - n_fft / 2; the reflected end of the last frame comes back to one sample before the start
+    of a frame that begins exactly at the signal's end"""
+    return max(t0, n_frames * hop - n_fft // 2 - 1)
+
+
 class LogMelStream:
     """one signal's features as its samples arrive: `push` returns the frames that became computable, `finish` the rest
     (those that read the reflected end).  Only the tail of the signal that later frames still read is kept.  The
@@ -178,13 +198,10 @@ class LogMelStream:
     def computable(self, n_received: int) -> int:
         """frames whose samples have all arrived: frame 0 reads up to sample n_fft / 2 (the left reflection), frame
         f >= 1 up to f hop + n_fft / 2 - 1"""
-        half = self.ext.n_fft // 2
-        return 0 if n_received <= half else 1 + (n_received - half) // self.ext.hop
+        return frames_ready(self.ext.n_fft, self.ext.hop, n_received)
 
     def _drop_consumed(self) -> None:
-        # the next frame starts at n_frames hop - n_fft / 2; the reflected end of the last frame comes back to one sample
-        # before the start of a frame that begins exactly at the signal's end
-        keep = max(self.t0, self.n_frames * self.ext.hop - self.ext.n_fft // 2 - 1)
+        keep = keep_from(self.ext.n_fft, self.ext.hop, self.t0, self.n_frames)
         if keep > self.t0:
             self._buf = self._buf[keep - self.t0:]
             self.t0 = keep
@@ -213,4 +230,187 @@ class LogMelStream:
             raise RuntimeError("the stream is finished")
         self.ext._check_len(self.n_received)
         self.finished = True
-        return self._range(self.ext.frame_count(self.n_received), self.n_received)
+        return self._range(frames_ready(self.ext.n_fft, self.ext.hop, self.n_received, True), self.n_received)
+
+
+# ---- many signals at once ------------------------------------------------------------------------------------------------
+class MelPlanEntry(NamedTuple):
+    """one session's share of a pool call, as swn_logmel_pool_entry states it (offsets are those of the call's buffers)"""
+    key: object
+    t0: int             # absolute index of the window's first sample before the call
+    n_held: int         # samples in the window before the call
+    n_drop: int         # of which the call discards this many from the front
+    new_off: int
+    n_new: int
+    len: int            # the total length, or -1 while the signal goes on
+    f0: int
+    f1: int
+    out_off: int
+    out_stride: int
+
+
+def plan_mel_push(sessions: Sequence[Tuple[object, int, int, int, int, int, bool]], n_fft: int, hop: int, n_mels: int,
+                  limit: int = _lib.LOGMEL_POOL_MAX_ENTRIES) -> List[List[MelPlanEntry]]:
+    """the calls of one batched push.  sessions: (key, t0, n_held, n_frames, n_received, n_new, finishing) of every session that
+    is handed samples or ended, in the caller's order, where [t0, t0 + n_held) is what the session's window holds.  Each
+    one's entry first drops what the frames returned so far no longer need (keep_from; LogMelStream drops it right after
+    those frames, the window drops it at the start of its next call), appends the n_new samples, and computes the frames
+    [n_frames, frames_ready(n_received + n_new, finishing)).  After the call the session stands at t0 + n_drop,
+    n_held - n_drop + n_new, f1 and n_received + n_new.  The entries are split into calls of at most `limit`, offsets
+    counted per call.  Pure host arithmetic: nothing here touches a device."""
+    n_fft, hop, n_mels, limit = int(n_fft), int(hop), int(n_mels), int(limit)
+    if limit < 1:
+        raise ValueError(f"limit must be a positive integer, not {limit}")
+    calls: List[List[MelPlanEntry]] = []
+    for i in range(0, len(sessions), limit):
+        entries, new_off, out_off = [], 0, 0
+        for key, t0, n_held, n_frames, n_received, n_new, finishing in sessions[i:i + limit]:
+            t0, n_held, n_frames, n_received, n_new = int(t0), int(n_held), int(n_frames), int(n_received), int(n_new)
+            if min(t0, n_held, n_frames, n_received, n_new) < 0 or t0 + n_held != n_received:
+                raise ValueError(f"session {key!r}: a window [{t0}, {t0} + {n_held}) does not end at the {n_received} samples received")
+            after = n_received + n_new
+            if finishing and after <= n_fft // 2:
+                raise ValueError(f"session {key!r}: n_fft {n_fft} needs signals longer than {n_fft // 2} samples (reflect padding), "
+                                 f"got {after}")
+            n_drop = min(keep_from(n_fft, hop, t0, n_frames) - t0, n_held)
+            f1 = max(n_frames, frames_ready(n_fft, hop, after, bool(finishing)))
+            k = f1 - n_frames
+            entries.append(MelPlanEntry(key, t0, n_held, n_drop, new_off, n_new, after if finishing else -1, n_frames, f1,
+                                        out_off, k))
+            new_off += n_new
+            out_off += k * n_mels
+        calls.append(entries)
+    return calls
+
+
+class MelSession:
+    """one signal of a LogMelPool: `slot` is its window, n_received / n_frames / finished tell where it stands (as
+    LogMelStream's do).  Made by LogMelPool.open."""
+
+    def __init__(self, pool: "LogMelPool", slot: int) -> None:
+        self._pool, self.slot = pool, slot
+        self.t0 = 0                 # absolute index of the window's first sample
+        self.n_held = 0             # samples in the window (what the next call no longer needs is dropped by that call)
+        self.n_received = 0
+        self.n_frames = 0           # frames returned so far
+        self.finished = False
+        self.closed = False
+
+
+class LogMelPool:
+    """many signals' features as their samples arrive, one call per tick: push_many gives every session what
+    LogMelStream.push / finish would, bit for bit, with at most two launches and one staging copy per 64 sessions whatever
+    their number.  The sessions' tails live in `windows` (capacity, n_fft + max_chunk) on the device: there is no
+    per-session cat or slice, and the frames come back channel-major, (1, n_mels, k), as DecodePool.push_many,
+    SteppedDecodePool.push_many and DecodeStream.push take them."""
+
+    def __init__(self, extractor: LogMelExtractor, capacity: int, max_chunk: int, linear: bool = False) -> None:
+        if not isinstance(capacity, int) or capacity < 1:
+            raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
+        if not isinstance(max_chunk, int) or max_chunk < 1:
+            raise ValueError(f"max_chunk must be a positive integer, not {max_chunk!r}")
+        self.ext, self.capacity, self.max_chunk, self.linear = extractor, capacity, max_chunk, bool(linear)
+        floats = int(_lib.lib().swn_logmel_pool_window_floats(extractor.n_fft, max_chunk))
+        if floats == 0:
+            raise ValueError(f"no window for n_fft {extractor.n_fft} and chunks of {max_chunk} samples")
+        self.windows = torch.zeros((capacity, floats), dtype=torch.float32, device=extractor.device)
+        self._free = list(range(capacity))
+        self._open: Dict[int, MelSession] = {}
+        self._op = ops.logmel_pool_impl
+
+    def open(self) -> MelSession:
+        """claim a free slot for a new signal (whatever the slot held before is never read)"""
+        if not self._free:
+            raise RuntimeError(f"the pool is full: all {self.capacity} slots hold open sessions")
+        s = MelSession(self, self._free.pop(0))
+        self._open[s.slot] = s
+        return s
+
+    def close(self, s: MelSession) -> None:
+        """free the session's slot (finished or not)"""
+        if not isinstance(s, MelSession) or s.closed or self._open.get(s.slot) is not s:
+            raise RuntimeError("this session is not open in this pool")
+        s.closed = True
+        del self._open[s.slot]
+        self._free.append(s.slot)
+        self._free.sort()
+
+    def _check(self, chunks, finish) -> List[Tuple[MelSession, Optional[torch.Tensor], bool]]:
+        """(session, flat fp32 chunk or None, finishing) of a push_many call in its order; nothing is changed"""
+        if not isinstance(chunks, dict):
+            raise ValueError("chunks must map mel sessions to 1-D sample tensors")
+        finish = list(finish)
+        if len(set(map(id, finish))) != len(finish):
+            raise ValueError("a session is named twice in finish")
+        ending = set(map(id, finish))
+        order = [(s, c, id(s) in ending) for s, c in chunks.items()] + [(s, None, True) for s in finish if s not in chunks]
+        out = []
+        for s, c, fin in order:
+            if not isinstance(s, MelSession) or s.closed or self._open.get(s.slot) is not s:
+                if isinstance(s, MelSession) and s._pool is self and s.closed:
+                    raise RuntimeError(f"mel session of slot {s.slot} is closed")
+                raise RuntimeError("this session is not open in this pool")
+            if s.finished:
+                raise RuntimeError(f"mel session of slot {s.slot} is finished: no samples can be pushed after it ended")
+            if c is not None:
+                c = torch.as_tensor(c)
+                if c.dim() != 1:
+                    raise ValueError(f"samples must be a 1-D tensor, got shape {tuple(c.shape)}")
+                if c.numel() > self.max_chunk:
+                    raise ValueError(f"a chunk of {c.numel()} samples, the pool was built for at most {self.max_chunk}")
+                if c.dtype != torch.float32:
+                    c = c.to(torch.float32)
+            if fin:
+                self.ext._check_len(s.n_received + (0 if c is None else c.numel()))
+            out.append((s, c, fin))
+        return out
+
+    def _stage(self, pieces: List[torch.Tensor]) -> Optional[torch.Tensor]:
+        """the chunks of one call back to back in entry order, on the device: one host-to-device copy for the host chunks,
+        one cat for the device chunks (as DecodePool._stage)"""
+        flat = [c for c in pieces if c.numel() > 0]
+        if not flat:
+            return None
+        dev = self.ext.device
+        host = [i for i, c in enumerate(flat) if not c.is_cuda]
+        if host:
+            up = (flat[host[0]] if len(host) == 1 else torch.cat([flat[i] for i in host])).to(dev)
+            if len(host) == len(flat):
+                return up.contiguous()
+            at = 0
+            for i in host:
+                n = flat[i].numel()
+                flat[i] = up[at:at + n]
+                at += n
+        return flat[0].contiguous() if len(flat) == 1 else torch.cat(flat)
+
+    def push_many(self, chunks: dict, finish: Sequence[MelSession] = ()) -> Dict[MelSession, torch.Tensor]:
+        """one call for a whole tick of audio: push(chunk) for every session of `chunks` ({session: 1-D samples on the host or
+        the device, 0 .. max_chunk of them}) and finish for every session of `finish` (which may also have a last chunk in
+        `chunks`) -> {session: (1, n_mels, k) fp32 new frames on the device, k >= 0}, contiguous views of the calls' output
+        buffers.  Per 64 sessions: one staging copy, one swn_logmel_pool call (two launches).  Everything is checked first and
+        the counters move only after every call is enqueued: a call that raises leaves every session as it was."""
+        order = self._check(chunks, finish)
+        ext = self.ext
+        calls = plan_mel_push([(i, s.t0, s.n_held, s.n_frames, s.n_received, 0 if c is None else c.numel(), fin)
+                               for i, (s, c, fin) in enumerate(order)], ext.n_fft, ext.hop, ext.n_mels)
+        results: Dict[MelSession, torch.Tensor] = {}
+        for entries in calls:
+            staged = self._stage([order[e.key][1] for e in entries if e.n_new > 0])
+            out = self._op(self.windows, staged, ext._table, ext.bank, [order[e.key][0].slot for e in entries],
+                           [e.t0 for e in entries], [e.n_held for e in entries], [e.n_drop for e in entries],
+                           [e.n_new for e in entries], [e.len for e in entries], [e.f0 for e in entries],
+                           [e.f1 for e in entries], ext.n_fft, ext.hop, ext.floor, self.linear)
+            for e in entries:
+                k = e.f1 - e.f0
+                results[order[e.key][0]] = out[e.out_off:e.out_off + k * ext.n_mels].view(1, ext.n_mels, k)
+        # every call has been enqueued: only now do the sessions move
+        for entries in calls:
+            for e in entries:
+                s = order[e.key][0]
+                s.t0, s.n_held = e.t0 + e.n_drop, e.n_held - e.n_drop + e.n_new
+                s.n_received, s.n_frames = s.n_received + e.n_new, e.f1
+        for s, _c, fin in order:
+            if fin:
+                s.finished = True
+        return results

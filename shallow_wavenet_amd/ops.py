@@ -42,6 +42,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.spectral_loss(samples, targets, tables, sizes, keep_state) -> (l1, lsd, state)
     torch.ops.swn.spectral_loss_backward(grad_l1, state, tables, sizes, length) -> grad_samples
     torch.ops.swn.logmel(wav, tables, bank, t0s, n_avails, lens, f0s, f1s, n_fft, hop, floor, linear) -> features
+    torch.ops.swn.logmel_pool(win, staged, tables, bank, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s, n_fft, hop,
+                              floor, linear) -> features of all sessions, channel-major (updates win)
     torch.ops.swn.laplace_loss(raw, ctx?, target, eps, desc, skip) -> (nll, err, samples, targets, stats)
     torch.ops.swn.laplace_loss_backward(raw, ctx?, target, eps, g_nll, g_samples?, desc, skip) -> grad_raw
 """
@@ -1416,10 +1418,67 @@ def _(wav, tables, bank, t0s, n_avails, lens, f0s, f1s, n_fft, hop, floor, linea
     return wav.new_empty((wav.shape[0], fmax, len(bank)), dtype=torch.float32)
 
 
+def logmel_pool_impl(win: torch.Tensor, staged: Optional[torch.Tensor], tables: torch.Tensor, bank: List[int], slots: List[int],
+                     t0s: List[int], n_helds: List[int], n_drops: List[int], n_news: List[int], lens: List[int], f0s: List[int],
+                     f1s: List[int], n_fft: int, hop: int, floor: float, linear: bool) -> torch.Tensor:
+    """one log-mel pool call (swn_logmel_pool; at most LOGMEL_POOL_MAX_ENTRIES entries).  win (slots, window_floats): entry e's
+    window win[slots[e]] holds n_helds[e] samples from the absolute index t0s[e] on; the call drops n_drops[e] of them from
+    the front, appends the next n_news[e] samples of `staged` (the entries' new samples back to back; None when there are
+    none) and computes the frames [f0s[e], f1s[e]) -> a flat buffer with every entry's (n_mels, f1 - f0) block back to back
+    in entry order.  `win` is updated in place."""
+    Lb = _lib.lib()
+    _need_cuda(win, "the windows")
+    dev = win.device
+    n_mels, E = len(bank), len(slots)
+    _logmel_check(n_fft, hop, n_mels, floor)
+    if win.dim() != 2 or win.dtype != torch.float32 or not win.is_contiguous():
+        raise RuntimeError(f"logmel_pool needs a contiguous fp32 (slots, window) buffer, got {tuple(win.shape)} {win.dtype}")
+    if not 1 <= E <= _lib.LOGMEL_POOL_MAX_ENTRIES:
+        raise RuntimeError(f"logmel_pool: {E} entries, a call takes 1 .. {_lib.LOGMEL_POOL_MAX_ENTRIES}")
+    if not (len(t0s) == len(n_helds) == len(n_drops) == len(n_news) == len(lens) == len(f0s) == len(f1s) == E):
+        raise RuntimeError("logmel_pool: slots, t0s, n_helds, n_drops, n_news, lens, f0s and f1s must have one entry per session")
+    if any(not 0 <= s < win.shape[0] for s in slots):
+        raise RuntimeError(f"logmel_pool: a slot outside the buffer's {win.shape[0]} windows")
+    total_new = sum(int(n) for n in n_news)
+    if any(n < 0 for n in n_news) or (total_new > 0 and (staged is None or staged.device != dev or staged.dtype != torch.float32
+                                                         or not staged.is_contiguous() or staged.numel() != total_new)):
+        raise RuntimeError(f"logmel_pool: staged must be the {total_new} new samples as contiguous fp32 values on the windows' device")
+    need = Lb.swn_logmel_table_floats(n_fft, n_mels)
+    if tables.device != dev or tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != need:
+        raise RuntimeError(f"logmel_pool: tables must be {need} contiguous fp32 values on the device of the windows")
+    table = (_lib.LogMelPoolEntry * E)()
+    new_off = out_off = 0
+    for e in range(E):
+        k = max(int(f1s[e]) - int(f0s[e]), 0)
+        table[e] = _lib.LogMelPoolEntry(slot=int(slots[e]), t0=int(t0s[e]), n_held=int(n_helds[e]), n_drop=int(n_drops[e]),
+                                        new_off=new_off, n_new=int(n_news[e]), len=int(lens[e]), f0=int(f0s[e]), f1=int(f1s[e]),
+                                        out_off=out_off, out_stride=k, reserved=0)
+        new_off += int(n_news[e])
+        out_off += k * n_mels
+    out = torch.empty(out_off, dtype=torch.float32, device=dev)
+    nb = Lb.swn_logmel_pool_work_bytes(n_fft, hop, n_mels, win.shape[1], table, E)
+    work = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=dev)
+    bank_c = (ctypes.c_int32 * n_mels)(*[int(b) for b in bank])
+    with _on(dev):
+        _lib.check(Lb.swn_logmel_pool(n_fft, hop, n_mels, float(floor), int(bool(linear)), _ptr(tables), bank_c, _ptr(win),
+                                      win.shape[1], _ptr(staged), _ptr(out) if out_off else None, table, E, _ptr(work),
+                                      _stream(dev)), "logmel_pool")
+    return out
+
+
+logmel_pool = custom_op("swn::logmel_pool", mutates_args=("win",))(logmel_pool_impl)
+
+
+@logmel_pool.register_fake
+def _(win, staged, tables, bank, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s, n_fft, hop, floor, linear):
+    _logmel_check(n_fft, hop, len(bank), floor)
+    return win.new_empty((len(bank) * sum(max(f1 - f0, 0) for f0, f1 in zip(f0s, f1s)),), dtype=torch.float32)
+
+
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
             "pack_decode_w16", "decode_w16", "decode_chunk_w16", "decode_pool_chunk_w16",
             "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
             "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
-            "laplace_loss", "laplace_loss_backward", "logmel")
+            "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool")
