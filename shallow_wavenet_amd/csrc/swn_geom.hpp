@@ -164,7 +164,8 @@ static inline __host__ bool swn_drop_bf16_forward(const SwnGeom* g) { return g->
 // gradient, data gradient over every layer's kept d gx) read bf16 COPIES of their operands - the masked conditioning xm, d gx and
 // the in_x matrix - instead of rounding fp32 tensors on the way into LDS: the same products (the rounding is the one the fp32
 // route applies while staging), half the operand bytes, the kernels of the layer gradients.  Rows of swn_pitch16() elements.
-static inline __host__ bool swn_drop_inx16(const SwnGeom* g, long Tp) { return swn_drop_bf16_forward(g) && g->seg == 1 && Tp >= 256; }
+// (Asked only where swn_drop_bf16_forward holds: SwnTrainPath.)
+static inline __host__ bool swn_drop_inx16(const SwnGeom* g, long Tp) { return g->seg == 1 && Tp >= 256; }
 static inline __host__ long swn_pitch16(long T) { return (T + 2 + 31) & ~31L; }
 
 // "G4" layout of a (B, R, Tp) fp32 tensor that the MFMA epilogues of the mixed-precision GEMM-stack path write and read (R % 4 == 0):
@@ -185,18 +186,9 @@ static inline __host__ int swn_tensor_count(const SwnGeom* g) {
     return 2 + 2 * g->auxl + 2 + (g->conv2d ? 2 : 0) + (g->wav ? 2 : 0) + 2 + 6 * g->L + 4;
 }
 
-// Arithmetic mode of the training call in progress ON THIS THREAD: every training entry point takes it as an argument
-// (SWN_PRECISION_FP32 | SWN_PRECISION_BF16) and holds it in a SwnModeScope for the duration of the call, so the launch
-// helpers below it need no extra parameter and nothing outlives the call (the C ABI has no process-wide state).
-int  swn_call_mode();                 // csrc/swn_train.hip
-void swn_call_mode_set(int mode);
-struct SwnModeScope {
-    int prev;
-    explicit SwnModeScope(int mode) : prev(swn_call_mode()) { swn_call_mode_set(mode); }
-    ~SwnModeScope() { swn_call_mode_set(prev); }
-    SwnModeScope(const SwnModeScope&) = delete;
-    SwnModeScope& operator=(const SwnModeScope&) = delete;
-};
+// Arithmetic mode of a training call: every training entry point takes it as an argument (SWN_PRECISION_FP32 |
+// SWN_PRECISION_BF16) and hands it down as part of the call's resolved path (SwnTrainPath, csrc/swn_train_internal.hpp);
+// the library keeps no mode of its own.
 static inline bool swn_precision_ok(int mode) { return mode == SWN_PRECISION_FP32 || mode == SWN_PRECISION_BF16; }
 
 // thread-local text of the last HIP failure seen by an entry point (swn_last_error_detail())

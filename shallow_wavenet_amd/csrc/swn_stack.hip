@@ -334,7 +334,7 @@ namespace {
 
 int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, const float* fe_work, const void* audio,
                  int batch, int n_frames, const float* drop_x, const float* const* drop_h, float* work, float* out,
-                 float* hs, void* stream_, const char* where) {
+                 float* hs, int precision, void* stream_, const char* where) {
     FwdArgs a;
     int rc = swn_make_geom(d, &a.g);
     if (rc < 0) return rc;
@@ -363,16 +363,12 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
     }
     hipStream_t st = (hipStream_t)stream_;
     (void)hipGetLastError();   // drop stale errors of earlier runtime calls; only our launches are reported
-    const bool bf16 = swn_call_mode() == SWN_PRECISION_BF16;
+    // what this call runs and which sections it uses: the record the backward of the same call resolves too
+    const SwnTrainPath p = swn_train_path(d, g, batch, n_frames, n, drop ? SWN_TRAIN_DROP : SWN_TRAIN_PLAIN, precision, drop_h, hs != nullptr);
     const float* C = drop ? fe_work + swn_fe_layout(g, batch, n_frames).C : nullptr;      // the last conv_aux activation
-    if (drop && !hs && bf16 && swn_bl6_drop_supported(g, batch, Tp, n_frames, drop_h))
+    if (p.route == SWN_ROUTE_BL6_DROP)
         return swn_bl6_drop_forward(g, packed, C, reinterpret_cast<const float*>(audio), drop_x, batch, n_frames, work, out, st);
-    // the predicates that pick a section's use, each evaluated here once
-    const bool g16 = drop && swn_drop_g16(d, batch, Tp);                 // the layout ends with the GEMM stack's sections
-    const bool inx16 = drop && bf16 && swn_drop_inx16(&g, Tp);            // bf16 copies of the in_x operands
-    const bool stack16 = g16 && inx16 && !hs;                            // ... and the forward runs on the GEMM stack
-    const bool fwd16 = drop && bf16 && swn_drop_bf16_forward(&g);         // bf16-operand layers, pre-activations kept
-    const SwnFwdLayout lo = drop ? swn_fwd_drop_layout(g, batch, n, g16, g16 ? swn_bf16g_weight_bytes(g) : 0) : swn_fwd_layout(g, batch, Tp);
+    const SwnFwdLayout lo = swn_fwd_layout_of(g, batch, n, p);
     float* hbuf = hs ? hs : work + lo.hs;
     float* skipb = work + lo.s1;
     float* o1b = work + lo.r1;
@@ -383,20 +379,20 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
         const int Tx = (int)n.Tx;
         float* xm = work + lo.xm;
         float* gx = work + lo.gx;
-        // swn_drop_inx16: xm as bf16 rows in the same section (the backward of the same mode reads them there) and the bf16 in_x matrix
-        unsigned short* wx16 = inx16 ? reinterpret_cast<unsigned short*>(work + lo.wx16) : nullptr;
-        if (inx16)
+        // inx16: xm as bf16 rows in the same section (the backward reads them there) and the bf16 in_x matrix
+        unsigned short* wx16 = p.inx16 ? reinterpret_cast<unsigned short*>(work + lo.wx16) : nullptr;
+        if (p.inx16)
             hipLaunchKernelGGL(xm_fwd16_kernel, dim3((Tx + 2047) / 2048, swn_a0x(&g), batch), dim3(256), 0, st, C, packed, a.y.wup, a.y.bup,
                                drop_x, reinterpret_cast<unsigned short*>(xm), g.A0, swn_a0x(&g), n_frames, g.U, a.coff, Tx, swn_pitch16(Tx));
         else
         hipLaunchKernelGGL(xm_fwd_kernel, dim3((Tx + 255) / 256, swn_a0x(&g), batch), dim3(256), 0, st, C, packed, a.y.wup, a.y.bup,
                            drop_x, xm, g.A0, swn_a0x(&g), n_frames, g.U, a.coff, Tx);
         // (the GEMM stack reads gx in the G4 layout, swn_geom.hpp; it needs the bf16-copy product kernel, i.e. wx16)
-        rc = swn_train_inx_forward(g, a.y, packed, xm, gx, batch, Tx, (int)Tp, st, wx16, stack16);
+        rc = swn_train_inx_forward(g, a.y, packed, xm, gx, batch, Tx, (int)Tp, p.bf16, st, wx16, p.stack16);
         if (rc < 0) return rc;
         a.gx = gx;
     }
-    if (stack16) {
+    if (p.stack16) {
         // GEMM-stack geometries: input layer, gated layers (gate epilogue on the sample-rate in_x rows, a dropped level read through
         // its masked copy, pre-activations kept for the backward) and head on the bf16 time-major stack of the forward without
         // dropout; what the backward reads in fp32 (hidden states, relu(skip), relu(out_1)) is expanded from it.  Replaces one
@@ -417,7 +413,7 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
         if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(tf_input_kernel<SWN_KIND_LAPLACE>, grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(tf_input_kernel<SWN_KIND_SOFTMAX>, grid, dim3(256), 0, st, a);
     }
-    if (fwd16) {
+    if (p.fwd16) {
         // mixed-precision mode: bf16-operand GEMM + element-wise gate per layer; the gate pre-activations of every layer are
         // kept (the backward of the same mode reads them instead of recomputing), a dropped level goes through hmask
         rc = swn_train_layers_forward_drop(g, a.y, packed, audio, a.gx, drop_h, hbuf, work + lo.a_keep, lo.a_stride, work + lo.hmask,
@@ -432,10 +428,10 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
     }
     const size_t hstride = (size_t)(g.L + 1) * g.H * Tp;
     // skip: one GEMM over the L concatenated (undropped) hidden states (Hp == H, checked ahead of the first launch)
-    if (fwd16 && !hs) {
+    if (p.fwd16 && !hs) {
         // mixed-precision mode: the two wide 1x1 layers as bf16-operand time GEMMs with bias + relu epilogues (0.5 ms each as
         // exact-fp32 gemm_wx at the run.sh geometry); out_2 (<= 16 rows) stays below
-        rc = swn_train_head_acts(g, packed, work, batch, Tp, st);
+        rc = swn_train_head_acts(g, packed, work, batch, Tp, p.bf16, st);
         if (rc < 0) return rc;
     } else {
     hipLaunchKernelGGL(gemm_wx_kernel, dim3(tb64, (g.S + 63) / 64, batch), dim3(256), 0, st,
@@ -455,14 +451,15 @@ int forward_impl(const swn_net_desc* d, const float* packed, const float* cond, 
 
 extern "C" int swn_forward(const swn_net_desc* d, const float* packed, const float* cond, const void* audio,
                            int batch, int n_frames, float* work, float* out, float* hs, void* stream_) {
-    return forward_impl(d, packed, cond, nullptr, audio, batch, n_frames, nullptr, nullptr, work, out, hs, stream_, "swn_forward");
+    return forward_impl(d, packed, cond, nullptr, audio, batch, n_frames, nullptr, nullptr, work, out, hs, SWN_PRECISION_FP32, stream_,
+                        "swn_forward");
 }
 
 extern "C" int swn_drop_fused_path(const swn_net_desc* d, int batch, int n_frames, const float* const* drop_h) {
     SwnGeom g;
     if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1 || g.kind != SWN_KIND_LAPLACE) return 0;
-    const long Tp = swn_train_len(g, n_frames).Tp;
-    return Tp >= 1 && swn_bl6_drop_supported(g, batch, Tp, n_frames, drop_h) ? 1 : 0;
+    const SwnTrainLen n = swn_train_len(g, n_frames);
+    return n.Tp >= 1 && swn_train_path(d, g, batch, n_frames, n, SWN_TRAIN_DROP, SWN_PRECISION_BF16, drop_h, false).route == SWN_ROUTE_BL6_DROP ? 1 : 0;
 }
 
 extern "C" size_t swn_forward_drop_work_floats(const swn_net_desc* d, int batch, int n_frames) {
@@ -470,8 +467,8 @@ extern "C" size_t swn_forward_drop_work_floats(const swn_net_desc* d, int batch,
     const SwnTrainLen n = swn_train_len(g, n_frames);
     const long Tp = n.Tp;
     if (Tp < 1) return 0;
-    const bool g16 = swn_drop_g16(d, batch, Tp);
-    const size_t chain = swn_fwd_drop_layout(g, batch, n, g16, g16 ? swn_bf16g_weight_bytes(g) : 0).drop_total;
+    const SwnTrainPath p = swn_train_path(d, g, batch, n_frames, n, SWN_TRAIN_DROP, SWN_PRECISION_BF16, nullptr, false);
+    const size_t chain = swn_fwd_layout_of(g, batch, n, p).drop_total;
     const size_t fused = g.bl6 ? (swn_bl6_drop_layout(g, batch, Tp).total + 3) / 4 : 0;      // the fused BL6 path's own layout
     return chain > fused ? chain : fused;
 }
@@ -480,8 +477,7 @@ extern "C" int swn_forward_drop(const swn_net_desc* d, const float* packed, cons
                                 int batch, int n_frames, const float* drop_x, const float* const* drop_h,
                                 float* work, float* out, float* hs, int precision, void* stream_) {
     if (!drop_x || !swn_precision_ok(precision)) return SWN_E_BADARG;
-    SwnModeScope mode(precision);
-    return forward_impl(d, packed, nullptr, fe_work, audio, batch, n_frames, drop_x, drop_h, work, out, hs, stream_,
+    return forward_impl(d, packed, nullptr, fe_work, audio, batch, n_frames, drop_x, drop_h, work, out, hs, precision, stream_,
                         "swn_forward_drop");
 }
 

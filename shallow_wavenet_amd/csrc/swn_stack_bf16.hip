@@ -1231,7 +1231,6 @@ extern "C" int swn_bf16_train_forward_supported(const swn_net_desc* d) {
 extern "C" int swn_bf16_work_to_f32(const swn_net_desc* d, const float* packed, const void* work_bf16, int batch, int n_frames,
                                     float* fwd_work, int precision, void* stream_) {
     if (!swn_precision_ok(precision)) return SWN_E_BADARG;
-    SwnModeScope mode(precision);
     SwnGeom g;
     const bool small = bf_geom(d, &g) == SWN_OK;
     if (!small) { const int rc = swn_bf16g_geom(d, &g); if (rc < 0) return rc; }
@@ -1240,5 +1239,5 @@ extern "C" int swn_bf16_work_to_f32(const swn_net_desc* d, const float* packed, 
     if (Tp < 1) return SWN_E_BADARG;
     const int rc = swn_bf16g_expand(g, work_bf16, batch, Tp, fwd_work, small, (hipStream_t)stream_);
     if (rc < 0 || !small) return rc;
-    return swn_train_head_acts(g, packed, fwd_work, batch, Tp, (hipStream_t)stream_);
+    return swn_train_head_acts(g, packed, fwd_work, batch, Tp, precision == SWN_PRECISION_BF16, (hipStream_t)stream_);
 }

@@ -10,7 +10,7 @@
 //                       (weight gradients; split over time blocks, float atomics)
 // plus element-wise kernels for the gate, the rank-1 upsampler / hoisted in_x, the input layer and
 // the Laplace head.  Hidden states h_0..h_L saved by the forward are reused; the gate pre-activations
-// are recomputed (one extra conv GEMM per layer) instead of being stored.
+// are recomputed (one extra conv GEMM per layer) unless the forward of the call kept them (SwnPreact).
 //
 // Mixed-precision mode (precision = SWN_PRECISION_BF16): the same chain with bf16 operands on the matrix cores -
 //   time_gemm_bf16t_kernel / reduce_gemm_bf16s_kernel   128 x 128 tiles, fp32 operands rounded on the way into LDS
@@ -18,8 +18,12 @@
 //       operands read as bf16: gate_bwd_kernel leaves da and the layer input as bf16 rows (two copies each, the second moved
 //       right by one position so that every tap shift lands on an aligned element), wd_t16_kernel the transposed matrices;
 //       what the smaller operands buy is a third workgroup per CU
-// and the pre-activations are read back where the forward of the same mode kept them (swn_backward_keep).  The BL6 class takes
-// the fused per-layer backward of csrc/swn_bwd_bl6.hip instead.
+// and the pre-activations are read back where the forward of the same mode kept them (swn_backward_keep, the dropout chain at
+// H % 64 == 0).  The BL6 class takes the fused per-layer backward of csrc/swn_bwd_bl6.hip instead.
+//
+// Host side: a call resolves its path once (SwnTrainPath, csrc/swn_train_internal.hpp), carves its sections into a BwdCall
+// and runs the stages the path names: head, chain layers, all-layer in_x contractions, input layer - or the fused BL6 stack -
+// and the frame-rate front end.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include "swn_geom.hpp"
@@ -1359,13 +1363,10 @@ __global__ __launch_bounds__(256) void laplace_head_bwd_kernel(const float* __re
         graw[((size_t)b * NO + 2 * seg + k) * Tp + t] = ga ? ga[((size_t)b * Tp + t) * lpc + k] : 0.f;
 }
 
-// arithmetic mode of the training call in progress on this thread (SwnModeScope, csrc/swn_geom.hpp)
-thread_local int t_call_mode = SWN_PRECISION_FP32;
-inline bool mode_bf16() { return t_call_mode == SWN_PRECISION_BF16; }
-
-void launch_time(const TimeGemm& g, int B, hipStream_t st) {
+// bf16: the arithmetic mode of the call (SwnTrainPath::bf16) - bf16 operands on the matrix cores, else exact fp32
+void launch_time(const TimeGemm& g, int B, bool bf16, hipStream_t st) {
     const dim3 grid((g.T + 63) / 64, (g.M + 63) / 64, B);
-    if (mode_bf16()) {
+    if (bf16) {
         if (!g.xmul && g.x_st == 1 && g.KC % 32 == 0) {
             TimeGemm h = g;
             h.nb = B;
@@ -1403,11 +1404,11 @@ void launch_time(const TimeGemm& g, int B, hipStream_t st) {
     if (g.xmul) { hipLaunchKernelGGL(time_gemm_kernel<true>, lin, dim3(256), 0, st, h); return; }
     hipLaunchKernelGGL(time_gemm_kernel<false>, lin, dim3(256), 0, st, h);
 }
-void launch_reduce(ReduceGemm g, int B, hipStream_t st) {
+void launch_reduce(ReduceGemm g, int B, bool bf16, hipStream_t st) {
     g.TS = 512;
     const int nseg = (g.T + g.TS - 1) / g.TS;
     const dim3 grid((g.M + 63) / 64, (g.taps * g.KC + 63) / 64, B * nseg);
-    if (mode_bf16()) {
+    if (bf16) {
         if (!g.qmul && g.p_st == 1 && g.q_st == 1 && g.T >= 256) {
             // 128 x 128 tiles; time segments sized for a target number of workgroups
             const int mt = (g.M + 127) / 128, nt = (g.taps * g.KC + 127) / 128;
@@ -1442,9 +1443,6 @@ void launch_reduce(ReduceGemm g, int B, hipStream_t st) {
 }
 
 }  // namespace
-
-int  swn_call_mode() { return t_call_mode; }
-void swn_call_mode_set(int mode) { t_call_mode = mode; }
 
 extern "C" size_t swn_backward_work_floats(const swn_net_desc* d, int batch, int n_frames) {
     SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1) return 0;
@@ -1609,9 +1607,9 @@ __global__ __launch_bounds__(256) void xm_bwd16_kernel(const unsigned short* __r
 }  // namespace
 
 // relu(skip) and relu(out_1) from fp32 hidden states already in `work` (layout of swn_forward_work_floats) through the
-// contraction kernels of this file, i.e. in the arithmetic mode of the call (SwnModeScope): the tail of the training
+// contraction kernels of this file in the arithmetic mode of the call (`bf16`): the tail of the training
 // forward when the hidden states come from the BL6-class bf16 layer kernels (swn_bf16_work_to_f32).
-int swn_train_head_acts(const SwnGeom& g, const float* packed, float* work, int B, long Tp, hipStream_t st) {
+int swn_train_head_acts(const SwnGeom& g, const float* packed, float* work, int B, long Tp, bool bf16, hipStream_t st) {
     if (g.Hp != g.H) return SWN_E_UNSUPPORTED;
     SwnLayout y; swn_make_layout(&g, &y);
     const SwnFwdLayout lo = swn_fwd_layout(g, B, Tp);
@@ -1622,13 +1620,13 @@ int swn_train_head_acts(const SwnGeom& g, const float* packed, float* work, int 
         TimeGemm t = {packed + y.wsk, (long)g.L * g.Hp, 0, 1, work + (size_t)g.H * Tp, (long)(g.L + 1) * g.H * Tp, Tp, 1,
                       skipb, (long)g.S * Tp, Tp, nullptr, 0, 0, g.S, 1, g.L * g.H, (int)Tp, 1, 0, 1, 0};
         t.bias = packed + y.bsk; t.relu = 1;
-        launch_time(t, B, st);
+        launch_time(t, B, bf16, st);
     }
     {   // o1 = relu(b1 + W1 skip)
         TimeGemm t = {packed + y.w1, g.Sp, 0, 1, skipb, (long)g.S * Tp, Tp, 1, o1b, (long)g.O1 * Tp, Tp, nullptr, 0, 0,
                       g.O1, 1, g.S, (int)Tp, 1, 0, 1, 0};
         t.bias = packed + y.b1; t.relu = 1;
-        launch_time(t, B, st);
+        launch_time(t, B, bf16, st);
     }
     return swn_launch_status("swn_bf16_work_to_f32");
 }
@@ -1686,7 +1684,7 @@ int swn_train_layers_forward_drop(const SwnGeom& g, const SwnLayout& y, const fl
         ga.a_da = al;
         TimeGemm t = {packed + y.wd + (size_t)l * H2 * g.K * g.Hp, (long)g.K * g.Hp, g.Hp, 1, xin, xin_sb, Tp, 1, al, (long)H2 * Tp, Tp,
                       nullptr, 0, 0, H2, g.K, H, Tp, 1, g.K - 1, g.dil[l], 0};
-        launch_time(t, B, st);
+        launch_time(t, B, true, st);                       // (this forward exists in the mixed-precision mode only)
         const dim3 grid((Tp + 255) / 256, H, B);
         if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(gate_fwd_kernel<SWN_KIND_LAPLACE>, grid, dim3(256), 0, st, ga, hs);
         else hipLaunchKernelGGL(gate_fwd_kernel<SWN_KIND_SOFTMAX>, grid, dim3(256), 0, st, ga, hs);
@@ -1711,7 +1709,7 @@ __global__ __launch_bounds__(256) void wx16_kernel(const float* __restrict__ wx,
 }  // namespace
 
 int swn_train_inx_forward(const SwnGeom& g, const SwnLayout& y, const float* packed, const float* xm, float* gx,
-                          int B, int Tx, int Tp, hipStream_t st, unsigned short* wx16, bool g4) {
+                          int B, int Tx, int Tp, bool bf16, hipStream_t st, unsigned short* wx16, bool g4) {
     const int H2 = 2 * g.H;
     if (g.seg == 1) {                 // one launch over the L * 2H rows of the [N][A0p] matrix (row n = l*2H + o): gx is (B, L*2H, Tp)
         const int A0x = swn_a0x(&g);
@@ -1725,7 +1723,7 @@ int swn_train_inx_forward(const SwnGeom& g, const SwnLayout& y, const float* pac
             t.X16 = reinterpret_cast<const unsigned short*>(xm); t.x16_sb = (long)A0x * px; t.x16_sc = px; t.x16_odd = 0;
             t.y_g4 = g4 ? 1 : 0;
         }
-        launch_time(t, B, st);
+        launch_time(t, B, bf16, st);
         return SWN_OK;
     }
     for (int l = 0; l < g.L; ++l) {   // gx[b][l][o][t] = sum_{s,c} W[l][o][c*seg+s] xm[b][c][t+s]
@@ -1736,179 +1734,121 @@ int swn_train_inx_forward(const SwnGeom& g, const SwnLayout& y, const float* pac
                       xm, (long)A0x * Tx, Tx, 1, gx + (size_t)l * H2 * Tp, (long)g.L * H2 * Tp, Tp, nullptr, 0, 0,
                       H2, g.seg, A0x, Tp, 1, 0, 1, 0};
         t.XT = Tx;
-        launch_time(t, B, st);
+        launch_time(t, B, bf16, st);
     }
     return SWN_OK;
 }
 
 namespace {
 
-// hs_bf16 != null: everything at sample rate runs through swn_bl6_bwd_stack (csrc/swn_bwd_bl6.hip; the caller has checked
-// swn_bl6_bwd_supported); `work` then holds the compact form of SwnBwdLayout (swn_bwd_bl6_layout) and fwd_work is not read
-int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, const float* cond,
-                  const float* fe_work, const void* audio, const float* fwd_work, const float* hs_opt,
-                  const float* drop_x, const float* const* drop_h,
-                  const float* grad_out, int batch, int n_frames, float* work, float* gpacked, void* stream_,
-                  const char* where, const void* hs_bf16 = nullptr, const float* a_keep = nullptr) {
-    GateBwd ga{};
-    int rc = swn_make_geom(d, &ga.g);
-    if (rc < 0) return rc;
-    const SwnGeom& g = ga.g;
-    const bool drop = drop_x != nullptr;
-    if (!packed || !aux || (!drop && !cond) || (drop && !drop_h) || !fe_work || !audio || (!fwd_work && !hs_bf16) || !grad_out || !work ||
-        !gpacked || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
-    if (g.Hp != g.H || g.K > 8 || g.U > 256) {
-        swn_set_error_detail(where, g.Hp != g.H ? "hid_chn is not a multiple of 4: the backward does not serve this net (nothing was launched)"
-                                                : "kernel_size > 8 or upsampling_factor > 256: the backward does not serve this net (nothing was launched)");
-        return SWN_E_UNSUPPORTED;
-    }
-    swn_make_layout(&ga.g, &ga.y);
-    const SwnLayout& y = ga.y;
-    const SwnTrainLen n = swn_train_len(g, n_frames);
-    const long T = n.T;
-    const int Tp = (int)n.Tp;
-    if (n.Tp < 1) return SWN_E_BADARG;
-    // dropout mode, BL6 class, mixed-precision mode: the forward of the same call mode was swn_bl6_drop_forward (same predicate),
-    // fwd_work holds its SwnBl6DropLayout and the layers take the fused backward with sample-rate in_x operands
-    const bool drop_fused = drop && !hs_opt && !hs_bf16 && mode_bf16() && swn_bl6_drop_supported(g, batch, Tp, n_frames, drop_h);
-    SwnBl6DropLayout dlo{};
-    if (drop_fused) {
-        dlo = swn_bl6_drop_layout(g, batch, Tp);
-        hs_bf16 = reinterpret_cast<const unsigned char*>(fwd_work) + dlo.hs16;
-    }
-    {   // the contraction kernels address one utterance's operands with 32-bit byte offsets
-        size_t widest = (size_t)(g.L + 1) * g.H;
-        if ((size_t)g.S > widest) widest = g.S;
-        if ((size_t)g.O1 > widest) widest = g.O1;
-        if ((size_t)g.A0 > widest) widest = g.A0;
-        if (widest * (size_t)T * sizeof(float) >= (1ull << 31)) {
-            swn_set_error_detail(where, "one utterance's activations exceed 2 GiB: split the chunk");
-            return SWN_E_UNSUPPORTED;
-        }
-    }
-    hipStream_t st = (hipStream_t)stream_;
-    (void)hipGetLastError();
-    const int B = batch, H = g.H, H2 = 2 * g.H, L = g.L, S = g.S, O1 = g.O1, NO = g.NO;
-    const int coff = n.coff, Tx = (int)n.Tx;
-    const bool bf16 = mode_bf16(), chain = !hs_bf16;
-    // forward buffers: hs | s1 = relu(skip) | r1 = relu(out_1), and in the dropout mode swn_forward_drop's tail (xm, gx; in the
-    // mixed-precision mode every layer's gate pre-activations: the arithmetic mode must not change between a forward and its backward)
-    const bool g16 = chain && drop && swn_drop_g16(d, B, Tp);
-    const SwnFwdLayout fl = drop ? swn_fwd_drop_layout(g, B, n, g16, g16 ? swn_bf16g_weight_bytes(g) : 0) : swn_fwd_layout(g, B, Tp);
-    const float* hs = hs_opt ? hs_opt : fwd_work;
-    const float* s1 = chain ? fwd_work + fl.s1 : nullptr;
-    const float* r1 = chain ? fwd_work + fl.r1 : nullptr;
-    const float* xm = chain && drop ? fwd_work + fl.xm : nullptr;
-    const float* gx = chain && drop ? fwd_work + fl.gx : nullptr;
-    const float* saved_a = (chain && drop && bf16 && !hs_opt && swn_drop_bf16_forward(&g)) ? fwd_work + fl.a_keep
-                                                                                            : a_keep;   // swn_forward_bf16_keep's buffer
-    const size_t a_stride = swn_keep_stride(g, B, Tp);               // (the same slots in both)
-    // scratch: the chain's sections, or the compact form around the fused stack's own scratch (only dcond, dfe, dxm, bl6 then)
-    const SwnBwdLayout wl = chain ? swn_bwd_layout(g, B, n_frames, n, drop)
-                                  : swn_bwd_bl6_layout(g, B, n_frames, n, drop_fused, swn_bl6_bwd_scratch_bytes(g, B, Tp, drop_fused));
-    float* do1 = work + wl.do1;
-    float* dskip = work + wl.dskip;
-    float* dhs = work + wl.dhs;
-    float* a_da = work + wl.a_da;
-    float* dgx = work + wl.dgx;
-    float* dcond = work + wl.dcond;
-    float* dfe = work + wl.dfe;
-    float* dxm = work + wl.dxm;                                      // dropout mode; the fused path: bf16 [B][Tx][A0x]
-    float* hmask = work + wl.hmask;                                  // dropout mode: masked input of a layer (B, H, Tp)
-    float* bl6_scratch = chain ? nullptr : work + wl.bl6;
-    if (hipMemsetAsync(gpacked, 0, y.total * sizeof(float), st) != hipSuccess) return SWN_E_LAUNCH;
-    // teacher-forced chain without dropout: the partial g w_up copies of cond_bwd_kernel
-    float* wup_part = (chain && !drop) ? work + wl.wup_part : nullptr;
-    // mixed-precision chain: gate_bwd also leaves da as bf16 rows (pitch = Tp rounded up to 32) for the layer weight gradients
-    const long da16_pitch = swn_da16_pitch(Tp), da16_odd = (long)B * H2 * da16_pitch;
-    unsigned short* da16 = (chain && bf16) ? reinterpret_cast<unsigned short*>(work + wl.da16) : nullptr;
-    ga.da16 = da16; ga.da16_pitch = da16_pitch; ga.da16_odd = da16_odd;
-    // ... and the layer's (masked) input, for the weight gradient's Q operand; second copy within 32-bit reach as for da
-    const long h16_odd = (long)B * H * da16_pitch;
-    const bool use_h16 = da16 && Tp >= 256 && ((size_t)h16_odd + (size_t)H * da16_pitch) * 2 < (1ull << 31);
-    unsigned short* h16 = use_h16 ? reinterpret_cast<unsigned short*>(work + wl.h16) : nullptr;
-    ga.h16 = h16; ga.h16_odd = h16_odd;
-    // (the kernel reaches the second da copy through a 32-bit byte offset from an utterance's rows: it must stay below 2 GiB,
-    //  else the data gradients keep their fp32 X operand)
-    const bool use_wdt16 = da16 && g.Hp == H && H2 % 32 == 0 && ((size_t)da16_odd + (size_t)H2 * da16_pitch) * 2 < (1ull << 31);
-    unsigned short* wdt16 = use_wdt16 ? reinterpret_cast<unsigned short*>(work + wl.wdt16) : nullptr;             // [l][tap][i][o2]
-    if (wdt16) {
-        hipLaunchKernelGGL(wd_t16_kernel, dim3(1024), dim3(256), 0, st, packed + y.wd, wdt16, L, g.K, H, g.Hp);
-        // launch_reduce / launch_time take their bf16-copy kernels under exactly these conditions: nobody reads the fp32 da then
-        ga.skip_da32 = Tp >= 256 ? 1 : 0;
-    }
-    if (wup_part && hipMemsetAsync(wup_part, 0, (size_t)SWN_WUP_COPIES * 256 * sizeof(float), st) != hipSuccess) return SWN_E_LAUNCH;
-    // (the fused layer path writes d h_0 whole and keeps the other carries in its own buffers)
-    // Only level 0 needs zeros: levels 1..L are written whole by the skip data gradient below (accumulate = 0) before anything
-    // is added to them; d h_0 only ever receives additions.  (Zeroing all L + 1 levels was 710 MB = 0.11 ms per step at REF6.)
-    // (hipMemset2DAsync's fill kernel took 273 us for these 8 rows of 12.7 MB; a plain grid-stride store kernel is at the HBM rate)
-    if (chain) hipLaunchKernelGGL(zero_rows_kernel, dim3(512, B), dim3(256), 0, st, dhs, (size_t)(L + 1) * H * Tp, (size_t)H * Tp);
-    const long hsb = (long)(L + 1) * H * Tp;
+// One backward call: what the entry point was given, the call's resolved path and the sections of the two layouts - the
+// forward's buffers (SwnFwdLayout) and the scratch (SwnBwdLayout) - as pointers.  A section the path does not use is null.
+struct BwdCall {
+    SwnTrainPath p;
+    GateBwd ga;                       // geometry, parameter layout and the per-call fields of the gate kernels' argument
+    hipStream_t st;
+    int B, n_frames, Tp, Tx;
+    const float *packed, *aux, *fe_work, *grad_out, *drop_x;
+    const float* const* drop_h;
+    float* gpacked;
+    // the forward's buffers; chain: hidden states, relu(skip), relu(out_1), dropout: masked conditioning and in_x products
+    const float *hs, *s1, *r1, *xm, *gx;
+    const float* saved_a; size_t a_stride;           // kept gate pre-activations (SwnPreact), layer l at saved_a + l * a_stride
+    const void* hs16; const unsigned short *gx16, *xm16;       // fused BL6 routes: bf16 time-major hidden states; dropout: SwnBl6DropLayout
+    // scratch
+    float *do1, *dskip, *dhs, *a_da, *dgx, *dcond, *dfe, *dxm, *hmask, *wup_part, *dgx_all, *bl6;
+    unsigned short *da16, *h16, *wdt16, *dgx16_all, *wxt16;
+    long hsb, da16_pitch, da16_odd, h16_odd;
+    void time(const TimeGemm& t) const { launch_time(t, B, p.bf16, st); }
+    void reduce(const ReduceGemm& r) const { launch_reduce(r, B, p.bf16, st); }
+    // the stages
+    void head() const;
+    void chain_layers() const;
+    void cond_layer(const GateBwd& a) const;
+    void inx_layer(int l, const float* dgx_l) const;
+    void inx_all() const;
+    void frontend() const;
+};
 
-    // ---- head: out_2, out_1, skip
-    if (!hs_bf16) {
+// ---- head: out_2, out_1, skip
+void BwdCall::head() const {
+    const SwnGeom& g = ga.g; const SwnLayout& y = ga.y;
+    const int H = g.H, L = g.L, S = g.S, O1 = g.O1, NO = g.NO;
     {   // do1 = relu'(r1) . W2^T dY ; gW2 += dY r1^T
         TimeGemm t = {packed + y.w2, 1, 0, g.O1p, grad_out, (long)NO * Tp, Tp, 1, do1, (long)O1 * Tp, Tp, r1, (long)O1 * Tp, Tp,
                       O1, 1, NO, Tp, 1, 0, 1, 0};
-        launch_time(t, B, st);
+        time(t);
         ReduceGemm r = {grad_out, (long)NO * Tp, Tp, 1, r1, (long)O1 * Tp, Tp, 1, gpacked + y.w2, g.O1p, 0, 1, gpacked + y.b2,
                         NO, 1, O1, Tp, 1, 0, 1, 0};
-        launch_reduce(r, B, st);
+        reduce(r);
     }
     {   // dskip = relu'(s1) . W1^T do1 ; gW1 += do1 s1^T
         TimeGemm t = {packed + y.w1, 1, 0, g.Sp, do1, (long)O1 * Tp, Tp, 1, dskip, (long)S * Tp, Tp, s1, (long)S * Tp, Tp,
                       S, 1, O1, Tp, 1, 0, 1, 0};
-        launch_time(t, B, st);
+        time(t);
         ReduceGemm r = {do1, (long)O1 * Tp, Tp, 1, s1, (long)S * Tp, Tp, 1, gpacked + y.w1, g.Sp, 0, 1, gpacked + y.b1,
                         O1, 1, S, Tp, 1, 0, 1, 0};
-        launch_reduce(r, B, st);
+        reduce(r);
     }
     {   // dh_l (skip part) = Wsk_l^T dskip for all l at once ; gWsk += dskip hcat^T
         TimeGemm t = {packed + y.wsk, 1, 0, (long)L * g.Hp, dskip, (long)S * Tp, Tp, 1, dhs + (size_t)H * Tp, hsb, Tp, nullptr, 0, 0,
                       L * H, 1, S, Tp, 1, 0, 1, 0};
-        launch_time(t, B, st);
+        time(t);
         ReduceGemm r = {dskip, (long)S * Tp, Tp, 1, hs + (size_t)H * Tp, hsb, Tp, 1, gpacked + y.wsk, (long)L * g.Hp, 0, 1, gpacked + y.bsk,
                         S, 1, L * H, Tp, 1, 0, 1, 0};
-        launch_reduce(r, B, st);
+        reduce(r);
     }
+}
+
+// without dropout: a layer's d gx -> d cond (hoisted in_x), g bx, partial g w_up
+void BwdCall::cond_layer(const GateBwd& a) const {
+    const SwnGeom& g = a.g;
+    // frames per workgroup: as many as still leave ~768 workgroups
+    const int rb = (2 * g.H + 63) / 64;
+    int FR = (int)(((long)rb * n_frames * B) / 768); FR = FR < 1 ? 1 : (FR > 16 ? 16 : FR);
+    const dim3 cgrid(rb, (n_frames + FR - 1) / FR, B);
+    const size_t clds = (size_t)64 * ((g.U + g.seg - 1) | 1) * sizeof(float);
+    const int cch = (g.U + g.seg - 1 + 63) / 64;                              // 64-column chunks of a frame's tile (U <= 256: at most 5)
+    if (cch <= 2) hipLaunchKernelGGL(cond_bwd_kernel<2>, cgrid, dim3(256), clds, st, a, dcond, gpacked + a.y.bx, wup_part, FR);
+    else hipLaunchKernelGGL(cond_bwd_kernel<5>, cgrid, dim3(256), clds, st, a, dcond, gpacked + a.y.bx, wup_part, FR);
+}
+
+// dropout mode, seg > 1: layer l's two in_x contractions over its d gx (B, 2H, Tp)
+void BwdCall::inx_layer(const int l, const float* dgx_l) const {
+    const SwnGeom& g = ga.g; const SwnLayout& y = ga.y;
+    const int H2 = 2 * g.H;
+    const float* Wx = packed + y.wx + (size_t)l * g.seg * H2 * g.A0p;          // [s][o][c]
+    {   // g in_x.W[l][o][c*seg+s] += sum dgx[o][t] xm[c][t+s] ; g b_inx += rowsum(dgx)
+        ReduceGemm r = {dgx_l, (long)H2 * Tp, Tp, 1, xm, (long)swn_a0x(&g) * Tx, Tx, 1,
+                        gpacked + y.wx + (size_t)l * g.seg * H2 * g.A0p, g.A0p, (long)H2 * g.A0p, 1,
+                        gpacked + y.bxr + (size_t)l * H2, H2, g.seg, g.A0, Tp, 1, 0, 1, 0};
+        r.QT = Tx;
+        reduce(r);
     }
-    ga.P = packed; ga.cond = cond; ga.audio = audio; ga.hs = hs; ga.dhs = dhs; ga.a_da = a_da; ga.dgx = dgx; ga.dgx_sb = (long)H2 * Tp;
-    // dropout chain, seg == 1: every layer's d gx is kept - (B, L, 2H, Tp) at the end of the work buffer - so that the gradient wrt
-    // the masked conditioning is ONE contraction over the L * 2H rows of in_x behind the loop instead of L read-modify-write
-    // passes over d xm (257 MB each way at the run.sh geometry)
-    float* dgx_all = (drop && !drop_fused && g.seg == 1) ? work + wl.dgx_all : nullptr;
-    // swn_drop_inx16 (the forward of the same mode left xm as bf16 rows): d gx is kept as bf16 rows in that section instead, and the
-    // transposed bf16 in_x matrix sits behind it
-    const bool inx16 = dgx_all && !hs_opt && da16 && swn_drop_inx16(&g, Tp);
-    unsigned short* dgx16_all = inx16 ? reinterpret_cast<unsigned short*>(work + wl.dgx16_all) : nullptr;
-    unsigned short* wxt16 = inx16 ? reinterpret_cast<unsigned short*>(work + wl.wxt16) : nullptr;
-    ga.B = B; ga.Tf = n_frames; ga.Tp = Tp; ga.coff = coff;
-    ga.gx = drop ? gx : nullptr;
-    // the GEMM stack keeps its pre-activations - and, when it ran the dropout-mode forward, read its in_x rows - in the G4 layout
-    ga.g4 = (a_keep || (g16 && inx16)) ? 1 : 0;
-    ga.gwxa = g.audio_in ? gpacked + y.wxa : nullptr;
-    // ---- layers, last to first
-    if (hs_bf16) {
-        if ((drop && !drop_fused) || !swn_bl6_bwd_supported(g, B, Tp, n_frames)) return SWN_E_UNSUPPORTED;
-        const unsigned char* fw = reinterpret_cast<const unsigned char*>(fwd_work);
-        const int rcl = swn_bl6_bwd_stack(g, y, packed, cond, reinterpret_cast<const float*>(audio), hs_bf16, grad_out, dcond, gpacked,
-                                          bl6_scratch, B, n_frames, Tp, st,
-                                          drop_fused ? reinterpret_cast<const unsigned short*>(fw + dlo.gx16) : nullptr,
-                                          drop_fused ? reinterpret_cast<const unsigned short*>(fw + dlo.xm16) : nullptr,
-                                          drop_fused ? reinterpret_cast<unsigned short*>(dxm) : nullptr);
-        if (rcl < 0) return rcl;
+    {   // dxm[c][u] (+)= sum_{s,o} W[l][o][c*seg+s] dgx[o][u-s]
+        TimeGemm t = {Wx, 1, (long)H2 * g.A0p, g.A0p, dgx_l, (long)H2 * Tp, Tp, 1, dxm, (long)g.A0 * Tx, Tx, nullptr, 0, 0,
+                      g.A0, g.seg, H2, Tx, -1, 0, 1, l == g.L - 1 ? 0 : 1};
+        t.XT = Tp;
+        time(t);
     }
-    for (int l = hs_bf16 ? -1 : L - 1; l >= 0; --l) {
-        ga.l = l;
-        if (dgx_all) { dgx = dgx_all + (size_t)l * H2 * Tp; ga.dgx = dgx; ga.dgx_sb = (long)L * H2 * Tp; }
-        if (dgx16_all) { ga.dgx16 = dgx16_all + (size_t)l * H2 * da16_pitch; ga.dgx16_sb = (long)L * H2 * da16_pitch; }
-        else if (!drop && a_keep && da16 && da16_pitch <= 2L * Tp) {   // GEMM-stack class, no dropout: cond_bwd_kernel reads the bf16 rows
-            // (same section, half of it; the small nets keep fp32 here: the rounding moved a 2e-2 gradient check of the 32-channel fixtures)
-            ga.dgx16 = reinterpret_cast<unsigned short*>(dgx); ga.dgx16_sb = (long)H2 * da16_pitch;
+}
+
+// ---- gated layers of the chain, last to first
+void BwdCall::chain_layers() const {
+    GateBwd a = ga;                   // + the per-layer fields
+    const SwnGeom& g = a.g; const SwnLayout& y = a.y;
+    const int H = g.H, H2 = 2 * g.H, L = g.L;
+    for (int l = L - 1; l >= 0; --l) {
+        a.l = l;
+        float* dgx_l = dgx;
+        if (dgx_all) { dgx_l = dgx_all + (size_t)l * H2 * Tp; a.dgx = dgx_l; a.dgx_sb = (long)L * H2 * Tp; }
+        if (dgx16_all) { a.dgx16 = dgx16_all + (size_t)l * H2 * da16_pitch; a.dgx16_sb = (long)L * H2 * da16_pitch; }
+        else if (p.dgx16_cond) {   // cond_bwd_kernel reads the bf16 rows (same section, half of it)
+            a.dgx16 = reinterpret_cast<unsigned short*>(dgx_l); a.dgx16_sb = (long)H2 * da16_pitch;
         }
         // dropout mode: this layer's input is h_{l-1} times the mask drawn for layer l-1's output (cswnv_shift1.py:269-273)
-        const float* in_mul = (drop && l > 0) ? drop_h[l - 1] : nullptr;
-        ga.in_mul = in_mul;
+        const float* in_mul = (p.drop && l > 0) ? drop_h[l - 1] : nullptr;
+        a.in_mul = in_mul;
         const float* Wd = packed + y.wd + (size_t)l * H2 * g.K * g.Hp;                 // [o2][tap][i]
         const float* xin = hs + (size_t)l * H * Tp; long xin_sb = hsb;                 // the layer's input as the GEMMs read it
         if (in_mul) {
@@ -1916,21 +1856,21 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
             hipLaunchKernelGGL(mask_mul_kernel, dim3((unsigned)((npb / 4 + 255) / 256 + 1), B), dim3(256), 0, st, xin, hsb, in_mul, hmask, npb);
             xin = hmask; xin_sb = npb;
         }
-        ga.a_in = nullptr;
-        if (saved_a) ga.a_in = saved_a + (size_t)l * a_stride;   // the forward of the same mode kept them
+        a.a_in = nullptr;
+        if (saved_a) a.a_in = saved_a + (size_t)l * a_stride;   // the forward kept them
         else {   // a = Wd (*) h_{l-1}   (bias added in the gate kernel)
             TimeGemm t = {Wd, (long)g.K * g.Hp, g.Hp, 1, xin, xin_sb, Tp, 1, a_da, (long)H2 * Tp, Tp, nullptr, 0, 0,
                           H2, g.K, H, Tp, 1, g.K - 1, g.dil[l], 0};
-            launch_time(t, B, st);
+            time(t);
         }
-        if (ga.g4 && ga.a_in) {
+        if (a.g4 && a.a_in) {
             dim3 grid((Tp + 255) / 256, H / 4, B);
-            if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(gate_bwd_g4_kernel<SWN_KIND_LAPLACE>, grid, dim3(256), 0, st, ga);
-            else hipLaunchKernelGGL(gate_bwd_g4_kernel<SWN_KIND_SOFTMAX>, grid, dim3(256), 0, st, ga);
+            if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(gate_bwd_g4_kernel<SWN_KIND_LAPLACE>, grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(gate_bwd_g4_kernel<SWN_KIND_SOFTMAX>, grid, dim3(256), 0, st, a);
         } else {
             dim3 grid((Tp + 255) / 256, H, B);
-            if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(gate_bwd_kernel<SWN_KIND_LAPLACE>, grid, dim3(256), 0, st, ga);
-            else hipLaunchKernelGGL(gate_bwd_kernel<SWN_KIND_SOFTMAX>, grid, dim3(256), 0, st, ga);
+            if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(gate_bwd_kernel<SWN_KIND_LAPLACE>, grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(gate_bwd_kernel<SWN_KIND_SOFTMAX>, grid, dim3(256), 0, st, a);
         }
         {   // gWd += da X^T (taps shifted back), gbd += rowsum(da)
             ReduceGemm r = {a_da, (long)H2 * Tp, Tp, 1, xin, xin_sb, Tp, 1,
@@ -1938,7 +1878,7 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
                             H2, g.K, H, Tp, 1, g.K - 1, g.dil[l], 0};
             r.P16 = da16; r.p16_sb = (long)H2 * da16_pitch; r.p16_sm = da16_pitch;
             r.Q16 = h16; r.q16_sb = (long)H * da16_pitch; r.q16_sc = da16_pitch; r.q16_odd = h16_odd;
-            launch_reduce(r, B, st);
+            reduce(r);
         }
         {   // dh_{l-1} += Wd^T (*) da  (taps shifted forward): A(m=i, tap, c=o2) = Wd[o2][tap][i]
             TimeGemm t = {Wd, 1, g.Hp, (long)g.K * g.Hp, a_da, (long)H2 * Tp, Tp, 1, dhs + (size_t)l * H * Tp, hsb, Tp, nullptr, 0, 0,
@@ -1948,107 +1888,205 @@ int backward_impl(const swn_net_desc* d, const float* packed, const float* aux, 
                 t.A16 = wdt16 + (size_t)l * g.K * H * H2; t.a16_sm = H2; t.a16_stap = (long)H * H2;
                 t.X16 = da16; t.x16_sb = (long)H2 * da16_pitch; t.x16_sc = da16_pitch; t.x16_odd = da16_odd;
             }
-            launch_time(t, B, st);
+            time(t);
         }
-        if (!drop) {
-            // frames per workgroup: as many as still leave ~768 workgroups
-            const int rb = (H2 + 63) / 64;
-            int FR = (int)(((long)rb * n_frames * B) / 768); FR = FR < 1 ? 1 : (FR > 16 ? 16 : FR);
-            const dim3 cgrid(rb, (n_frames + FR - 1) / FR, B);
-            const size_t clds = (size_t)64 * ((g.U + g.seg - 1) | 1) * sizeof(float);
-            const int cch = (g.U + g.seg - 1 + 63) / 64;                              // 64-column chunks of a frame's tile (U <= 256: at most 5)
-            if (cch <= 2) hipLaunchKernelGGL(cond_bwd_kernel<2>, cgrid, dim3(256), clds, st, ga, dcond, gpacked + y.bx, wup_part, FR);
-            else hipLaunchKernelGGL(cond_bwd_kernel<5>, cgrid, dim3(256), clds, st, ga, dcond, gpacked + y.bx, wup_part, FR);
-        } else {
-            const float* Wx = packed + y.wx + (size_t)l * g.seg * H2 * g.A0p;          // [s][o][c]
-            if (!dgx_all) {   // g in_x.W[l][o][c*seg+s] += sum dgx[o][t] xm[c][t+s] ; g b_inx += rowsum(dgx)
-                ReduceGemm r = {dgx, ga.dgx_sb, Tp, 1, xm, (long)swn_a0x(&g) * Tx, Tx, 1,
-                                gpacked + y.wx + (size_t)l * g.seg * H2 * g.A0p, g.A0p, (long)H2 * g.A0p, 1,
-                                gpacked + y.bxr + (size_t)l * H2, H2, g.seg, g.A0, Tp, 1, 0, 1, 0};
-                r.QT = Tx;
-                launch_reduce(r, B, st);
-            }
-            if (!dgx_all) {   // dxm[c][u] (+)= sum_{s,o} W[l][o][c*seg+s] dgx[o][u-s]
-                TimeGemm t = {Wx, 1, (long)H2 * g.A0p, g.A0p, dgx, (long)H2 * Tp, Tp, 1, dxm, (long)g.A0 * Tx, Tx, nullptr, 0, 0,
-                              g.A0, g.seg, H2, Tx, -1, 0, 1, l == L - 1 ? 0 : 1};
-                t.XT = Tp;
-                launch_time(t, B, st);
-            }
+        if (!p.drop) cond_layer(a);
+        else if (!dgx_all) inx_layer(l, dgx_l);
+    }
+}
+
+// ---- dropout chain, seg == 1: the two in_x contractions over the kept d gx of all layers at once (row n = l*2H + o of the
+//      [N][A0p] matrix)
+void BwdCall::inx_all() const {
+    const SwnGeom& g = ga.g; const SwnLayout& y = ga.y;
+    const int H2 = 2 * g.H, L = g.L;
+    // g in_x.W[n][c] += sum dgx[n][t] xm[c][t] ; g b_inx[n] += rowsum(dgx[n])
+    ReduceGemm r = {dgx_all, (long)L * H2 * Tp, Tp, 1, xm, (long)swn_a0x(&g) * Tx, Tx, 1, gpacked + y.wx, g.A0p, 0, 1,
+                    gpacked + y.bxr, L * H2, 1, g.A0, Tp, 1, 0, 1, 0};
+    r.QT = Tx;
+    if (p.inx16) {
+        const long px = swn_pitch16(Tx);
+        r.P16 = dgx16_all; r.p16_sb = (long)L * H2 * da16_pitch; r.p16_sm = da16_pitch;
+        r.Q16 = reinterpret_cast<const unsigned short*>(xm); r.q16_sb = (long)swn_a0x(&g) * px; r.q16_sc = px; r.q16_odd = 0;
+    }
+    reduce(r);
+    // dxm[c][u] = sum_n in_x.W[n][c] dgx[n][u]
+    TimeGemm t = {packed + y.wx, 1, 0, g.A0p, dgx_all, (long)L * H2 * Tp, Tp, 1, dxm, (long)g.A0 * Tx, Tx, nullptr, 0, 0,
+                  g.A0, 1, L * H2, Tx, -1, 0, 1, 0};
+    t.XT = Tp;
+    if (p.inx16) {
+        hipLaunchKernelGGL(wx16_kernel, dim3(512), dim3(256), 0, st, packed + y.wx, L * H2, g.A0, g.A0p, swn_a0x(&g), nullptr, wxt16);
+        t.A16 = wxt16; t.a16_sm = L * H2; t.a16_stap = 0;
+        t.X16 = dgx16_all; t.x16_sb = (long)L * H2 * da16_pitch; t.x16_sc = da16_pitch; t.x16_odd = 0;
+    }
+    time(t);
+}
+
+// ---- frame-rate front end: cond = Wx . C ; C = conv_aux(scale_in(aux))
+void BwdCall::frontend() const {
+    const SwnGeom& g = ga.g; const SwnLayout& y = ga.y;
+    const int coff = ga.coff;
+    // forward activations inside fe_work (scaled | aux conv outputs...) and their gradients, in the same layout
+    const SwnFeLayout fe = swn_fe_layout(g, B, n_frames);
+    const float* act[SWN_MAXAUX + 1]; float* dact[SWN_MAXAUX + 1];
+    for (int i = 0; i <= g.auxl; ++i) { act[i] = fe_work + fe.act[i]; dact[i] = dfe + fe.act[i]; }
+    const float* C = fe_work + fe.C;
+    if (p.route == SWN_ROUTE_BL6_DROP) {             // d xm arrives as bf16 time-major rows
+        const int cb = (g.A0 + XM16_CC - 1) / XM16_CC;
+        int FRx = (int)(((long)cb * n_frames * B) / 1024); FRx = FRx < 1 ? 1 : (FRx > 16 ? 16 : FRx);
+        hipLaunchKernelGGL(xm_bwd16_kernel, dim3((n_frames + FRx - 1) / FRx, cb, B), dim3(256), 0, st,
+                           reinterpret_cast<const unsigned short*>(dxm), drop_x, C, packed, y.wup, dact[g.auxl], gpacked + y.wup,
+                           gpacked + y.bup, g.A0, swn_a0x(&g), n_frames, g.U, coff, Tx, FRx);
+    } else if (p.drop) {
+        const int cb = (g.A0 + XM_CC - 1) / XM_CC;
+        int FRx = (int)(((long)cb * n_frames * B) / 1024); FRx = FRx < 1 ? 1 : (FRx > 16 ? 16 : FRx);
+        hipLaunchKernelGGL(xm_bwd_kernel, dim3((n_frames + FRx - 1) / FRx, cb, B), dim3(256), 0, st, dxm, drop_x, C, packed, y.wup,
+                           dact[g.auxl], gpacked + y.wup, gpacked + y.bup, g.A0, n_frames, g.U, coff, Tx, FRx);
+    } else {   // dC[b][c][f] = sum_n Wx[n][c] dcond[b][f][n] ; gWx[n][c] += sum_{b,f} dcond[b][f][n] C[b][c][f]
+        TimeGemm t = {packed + y.wx, 1, 0, g.A0p, dcond, (long)n_frames * g.N, 1, g.N, dact[g.auxl], (long)g.A0 * n_frames, n_frames,
+                      nullptr, 0, 0, g.A0, 1, g.N, n_frames, 1, 0, 1, 0};
+        time(t);
+        ReduceGemm r = {dcond, (long)n_frames * g.N, 1, g.N, C, (long)g.A0 * n_frames, n_frames, 1, gpacked + y.wx, g.A0p, 0, 1, nullptr,
+                        g.N, 1, g.A0, n_frames, 1, 0, 1, 0};
+        reduce(r);
+    }
+    for (int i = g.auxl - 1; i >= 0; --i) {
+        const int ci = g.aux_cin[i], co = g.aux_cout[i], ks = g.auxk, half = (g.auxk - 1) / 2, dl = g.aux_dil[i];
+        {   // gW[co][ci][k] += sum dY[co][f] X[ci][f + (k-half)*dil] ; gb
+            ReduceGemm r = {dact[i + 1], (long)co * n_frames, n_frames, 1, act[i], (long)ci * n_frames, n_frames, 1,
+                            gpacked + y.aux_w[i], (long)ci * ks, 1, ks, gpacked + y.aux_b[i], co, ks, ci, n_frames, 1, half, dl, 0};
+            reduce(r);
+        }
+        {   // dX[ci][f] = sum_{k,co} W[co][ci][k] dY[co][f - (k-half)*dil]
+            TimeGemm t = {packed + y.aux_w[i], ks, 1, (long)ci * ks, dact[i + 1], (long)co * n_frames, n_frames, 1, dact[i],
+                          (long)ci * n_frames, n_frames, nullptr, 0, 0, ci, ks, co, n_frames, -1, half, dl, 0};
+            time(t);
         }
     }
-    if (dgx_all) {   // the two in_x contractions over all layers at once (seg == 1: row n = l*2H + o of the [N][A0p] matrix)
-        // g in_x.W[n][c] += sum dgx[n][t] xm[c][t] ; g b_inx[n] += rowsum(dgx[n])
-        ReduceGemm r = {dgx_all, (long)L * H2 * Tp, Tp, 1, xm, (long)swn_a0x(&g) * Tx, Tx, 1, gpacked + y.wx, g.A0p, 0, 1,
-                        gpacked + y.bxr, L * H2, 1, g.A0, Tp, 1, 0, 1, 0};
-        r.QT = Tx;
-        if (inx16) {
-            const long px = swn_pitch16(Tx);
-            r.P16 = dgx16_all; r.p16_sb = (long)L * H2 * da16_pitch; r.p16_sm = da16_pitch;
-            r.Q16 = reinterpret_cast<const unsigned short*>(xm); r.q16_sb = (long)swn_a0x(&g) * px; r.q16_sc = px; r.q16_odd = 0;
-        }
-        launch_reduce(r, B, st);
-        // dxm[c][u] = sum_n in_x.W[n][c] dgx[n][u]
-        TimeGemm t = {packed + y.wx, 1, 0, g.A0p, dgx_all, (long)L * H2 * Tp, Tp, 1, dxm, (long)g.A0 * Tx, Tx, nullptr, 0, 0,
-                      g.A0, 1, L * H2, Tx, -1, 0, 1, 0};
-        t.XT = Tp;
-        if (inx16) {
-            hipLaunchKernelGGL(wx16_kernel, dim3(512), dim3(256), 0, st, packed + y.wx, L * H2, g.A0, g.A0p, swn_a0x(&g), nullptr, wxt16);
-            t.A16 = wxt16; t.a16_sm = L * H2; t.a16_stap = 0;
-            t.X16 = dgx16_all; t.x16_sb = (long)L * H2 * da16_pitch; t.x16_sc = da16_pitch; t.x16_odd = 0;
-        }
-        launch_time(t, B, st);
+    {   // scale_in: 1x1 on the raw features
+        ReduceGemm r = {dact[0], (long)g.n_aux * n_frames, n_frames, 1, aux, (long)g.n_aux * n_frames, n_frames, 1,
+                        gpacked + y.scale_w, g.n_aux, 0, 1, gpacked + y.scale_b, g.n_aux, 1, g.n_aux, n_frames, 1, 0, 1, 0};
+        reduce(r);
     }
-    if (wup_part) hipLaunchKernelGGL(wup_fold_kernel, dim3(1), dim3(256), 0, st, wup_part, gpacked + y.wup, g.U);
-    // ---- input layer (the fused layer path has done it from its accumulators)
-    if (hs_bf16) {}
-    else if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(input_bwd_kernel<SWN_KIND_LAPLACE>, dim3(H, B), dim3(256), 0, st, ga, gpacked);
-    else hipLaunchKernelGGL(input_bwd_kernel<SWN_KIND_SOFTMAX>, dim3(H, B), dim3(256), 0, st, ga, gpacked);
-    // ---- frame-rate front end: cond = Wx . C ; C = conv_aux(scale_in(aux))
-    {
-        // forward activations inside fe_work (scaled | aux conv outputs...) and their gradients, in the same layout
-        const SwnFeLayout fe = swn_fe_layout(g, B, n_frames);
-        const float* act[SWN_MAXAUX + 1]; float* dact[SWN_MAXAUX + 1];
-        for (int i = 0; i <= g.auxl; ++i) { act[i] = fe_work + fe.act[i]; dact[i] = dfe + fe.act[i]; }
-        const float* C = fe_work + fe.C;
-        if (drop_fused) {
-            const int cb = (g.A0 + XM16_CC - 1) / XM16_CC;
-            int FRx = (int)(((long)cb * n_frames * B) / 1024); FRx = FRx < 1 ? 1 : (FRx > 16 ? 16 : FRx);
-            hipLaunchKernelGGL(xm_bwd16_kernel, dim3((n_frames + FRx - 1) / FRx, cb, B), dim3(256), 0, st,
-                               reinterpret_cast<const unsigned short*>(dxm), drop_x, C, packed, y.wup, dact[g.auxl], gpacked + y.wup,
-                               gpacked + y.bup, g.A0, swn_a0x(&g), n_frames, g.U, coff, Tx, FRx);
-        } else if (drop) {
-            const int cb = (g.A0 + XM_CC - 1) / XM_CC;
-            int FRx = (int)(((long)cb * n_frames * B) / 1024); FRx = FRx < 1 ? 1 : (FRx > 16 ? 16 : FRx);
-            hipLaunchKernelGGL(xm_bwd_kernel, dim3((n_frames + FRx - 1) / FRx, cb, B), dim3(256), 0, st, dxm, drop_x, C, packed, y.wup,
-                               dact[g.auxl], gpacked + y.wup, gpacked + y.bup, g.A0, n_frames, g.U, coff, Tx, FRx);
-        } else
-        {   // dC[b][c][f] = sum_n Wx[n][c] dcond[b][f][n] ; gWx[n][c] += sum_{b,f} dcond[b][f][n] C[b][c][f]
-            TimeGemm t = {packed + y.wx, 1, 0, g.A0p, dcond, (long)n_frames * g.N, 1, g.N, dact[g.auxl], (long)g.A0 * n_frames, n_frames,
-                          nullptr, 0, 0, g.A0, 1, g.N, n_frames, 1, 0, 1, 0};
-            launch_time(t, B, st);
-            ReduceGemm r = {dcond, (long)n_frames * g.N, 1, g.N, C, (long)g.A0 * n_frames, n_frames, 1, gpacked + y.wx, g.A0p, 0, 1, nullptr,
-                            g.N, 1, g.A0, n_frames, 1, 0, 1, 0};
-            launch_reduce(r, B, st);
-        }
-        for (int i = g.auxl - 1; i >= 0; --i) {
-            const int ci = g.aux_cin[i], co = g.aux_cout[i], ks = g.auxk, half = (g.auxk - 1) / 2, dl = g.aux_dil[i];
-            {   // gW[co][ci][k] += sum dY[co][f] X[ci][f + (k-half)*dil] ; gb
-                ReduceGemm r = {dact[i + 1], (long)co * n_frames, n_frames, 1, act[i], (long)ci * n_frames, n_frames, 1,
-                                gpacked + y.aux_w[i], (long)ci * ks, 1, ks, gpacked + y.aux_b[i], co, ks, ci, n_frames, 1, half, dl, 0};
-                launch_reduce(r, B, st);
-            }
-            {   // dX[ci][f] = sum_{k,co} W[co][ci][k] dY[co][f - (k-half)*dil]
-                TimeGemm t = {packed + y.aux_w[i], ks, 1, (long)ci * ks, dact[i + 1], (long)co * n_frames, n_frames, 1, dact[i],
-                              (long)ci * n_frames, n_frames, nullptr, 0, 0, ci, ks, co, n_frames, -1, half, dl, 0};
-                launch_time(t, B, st);
-            }
-        }
-        {   // scale_in: 1x1 on the raw features
-            ReduceGemm r = {dact[0], (long)g.n_aux * n_frames, n_frames, 1, aux, (long)g.n_aux * n_frames, n_frames, 1,
-                            gpacked + y.scale_w, g.n_aux, 0, 1, gpacked + y.scale_b, g.n_aux, 1, g.n_aux, n_frames, 1, 0, 1, 0};
-            launch_reduce(r, B, st);
+}
+
+// Every backward entry point: checks, the call's path, its sections, then the stages the path names.
+// hs_opt: the caller's own fp32 hidden states (plain, drop) | work_bf16: swn_forward_bf16's work buffer (SWN_TRAIN_BL6; fwd_work
+// is not read then) | a_keep: swn_forward_bf16_keep's pre-activations (SWN_TRAIN_KEEP); each null at the other entries
+int backward_impl(const int entry, const swn_net_desc* d, const float* packed, const float* aux, const float* cond,
+                  const float* fe_work, const void* audio, const float* fwd_work, const float* hs_opt, const void* work_bf16,
+                  const float* a_keep, const float* drop_x, const float* const* drop_h, const float* grad_out, int batch,
+                  int n_frames, float* work, float* gpacked, int precision, void* stream_, const char* where) {
+    BwdCall c{};
+    GateBwd& ga = c.ga;
+    int rc = swn_make_geom(d, &ga.g);
+    if (rc < 0) return rc;
+    const SwnGeom& g = ga.g;
+    const bool drop = drop_x != nullptr;
+    if (!packed || !aux || (!drop && !cond) || (drop && !drop_h) || !fe_work || !audio || (!fwd_work && !work_bf16) || !grad_out || !work ||
+        !gpacked || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
+    if (g.Hp != g.H || g.K > 8 || g.U > 256) {
+        swn_set_error_detail(where, g.Hp != g.H ? "hid_chn is not a multiple of 4: the backward does not serve this net (nothing was launched)"
+                                                : "kernel_size > 8 or upsampling_factor > 256: the backward does not serve this net (nothing was launched)");
+        return SWN_E_UNSUPPORTED;
+    }
+    swn_make_layout(&ga.g, &ga.y);
+    const SwnLayout& y = ga.y;
+    const SwnTrainLen n = swn_train_len(g, n_frames);
+    if (n.Tp < 1) return SWN_E_BADARG;
+    {   // the contraction kernels address one utterance's operands with 32-bit byte offsets
+        size_t widest = (size_t)(g.L + 1) * g.H;
+        if ((size_t)g.S > widest) widest = g.S;
+        if ((size_t)g.O1 > widest) widest = g.O1;
+        if ((size_t)g.A0 > widest) widest = g.A0;
+        if (widest * (size_t)n.T * sizeof(float) >= (1ull << 31)) {
+            swn_set_error_detail(where, "one utterance's activations exceed 2 GiB: split the chunk");
+            return SWN_E_UNSUPPORTED;
         }
     }
+    // the record the forward of this call resolved too: the arithmetic mode, the masks and the owner of hs must not change
+    // between a forward and its backward
+    const SwnTrainPath p = swn_train_path(d, g, batch, n_frames, n, entry, precision, drop_h, hs_opt != nullptr);
+    const bool chain = p.route == SWN_ROUTE_CHAIN, fused_drop = p.route == SWN_ROUTE_BL6_DROP;
+    if (!chain && !p.bl6_bwd) return SWN_E_UNSUPPORTED;
+    const int B = batch, H = g.H, H2 = 2 * g.H, L = g.L, Tp = (int)n.Tp;
+    hipStream_t st = (hipStream_t)stream_;
+    (void)hipGetLastError();
+    c.p = p; c.st = st; c.B = B; c.n_frames = n_frames; c.Tp = Tp; c.Tx = (int)n.Tx;
+    c.packed = packed; c.aux = aux; c.fe_work = fe_work; c.grad_out = grad_out; c.drop_x = drop_x; c.drop_h = drop_h; c.gpacked = gpacked;
+    c.hsb = (long)(L + 1) * H * Tp;
+    // forward buffers.  Chain: hs | s1 = relu(skip) | r1 = relu(out_1), and in the dropout mode swn_forward_drop's tail
+    if (chain) {
+        const SwnFwdLayout fl = swn_fwd_layout_of(g, B, n, p);
+        c.hs = hs_opt ? hs_opt : fwd_work;
+        c.s1 = fwd_work + fl.s1;
+        c.r1 = fwd_work + fl.r1;
+        if (drop) { c.xm = fwd_work + fl.xm; c.gx = fwd_work + fl.gx; }
+        c.saved_a = p.preact == SWN_PREACT_FWD_WORK ? fwd_work + fl.a_keep : p.preact == SWN_PREACT_CALLER ? a_keep : nullptr;
+        c.a_stride = swn_keep_stride(g, B, Tp);                      // (the same slots in both)
+    } else if (fused_drop) {
+        const SwnBl6DropLayout dlo = swn_bl6_drop_layout(g, B, Tp);
+        const unsigned char* fw = reinterpret_cast<const unsigned char*>(fwd_work);
+        c.hs16 = fw + dlo.hs16;
+        c.gx16 = reinterpret_cast<const unsigned short*>(fw + dlo.gx16);
+        c.xm16 = reinterpret_cast<const unsigned short*>(fw + dlo.xm16);
+    } else c.hs16 = work_bf16;
+    // scratch: the chain's sections, or the compact form around the fused stack's own scratch (only dcond, dfe, dxm, bl6 then)
+    const SwnBwdLayout wl = chain ? swn_bwd_layout(g, B, n_frames, n, drop)
+                                  : swn_bwd_bl6_layout(g, B, n_frames, n, fused_drop, swn_bl6_bwd_scratch_bytes(g, B, Tp, fused_drop));
+    c.dcond = work + wl.dcond;
+    c.dfe = work + wl.dfe;
+    c.dxm = work + wl.dxm;                                           // dropout mode; the fused path: bf16 [B][Tx][A0x]
+    c.da16_pitch = swn_da16_pitch(Tp); c.da16_odd = (long)B * H2 * c.da16_pitch; c.h16_odd = (long)B * H * c.da16_pitch;
+    if (chain) {
+        c.do1 = work + wl.do1; c.dskip = work + wl.dskip; c.dhs = work + wl.dhs; c.a_da = work + wl.a_da; c.dgx = work + wl.dgx;
+        c.hmask = work + wl.hmask;                                   // dropout mode: masked input of a layer (B, H, Tp)
+        if (!drop) c.wup_part = work + wl.wup_part;                  // the partial g w_up copies of cond_bwd_kernel
+        // mixed precision: bf16 rows (pitch = Tp rounded up to 32) of da, of the layer's (masked) input, the transposed matrices
+        if (p.da16) c.da16 = reinterpret_cast<unsigned short*>(work + wl.da16);
+        if (p.h16) c.h16 = reinterpret_cast<unsigned short*>(work + wl.h16);
+        if (p.wdt16) c.wdt16 = reinterpret_cast<unsigned short*>(work + wl.wdt16);             // [l][tap][i][o2]
+        // dropout chain, seg == 1: every layer's d gx is kept - (B, L, 2H, Tp) at the end of the work buffer - so that the gradient
+        // wrt the masked conditioning is ONE contraction over the L * 2H rows of in_x behind the loop instead of L read-modify-write
+        // passes over d xm (257 MB each way at the run.sh geometry); inx16: as bf16 rows in that section, the transposed bf16
+        // in_x matrix behind it
+        if (p.dgx_all) c.dgx_all = work + wl.dgx_all;
+        if (p.inx16) {
+            c.dgx16_all = reinterpret_cast<unsigned short*>(work + wl.dgx16_all);
+            c.wxt16 = reinterpret_cast<unsigned short*>(work + wl.wxt16);
+        }
+    } else c.bl6 = work + wl.bl6;
+    ga.P = packed; ga.cond = cond; ga.audio = audio; ga.hs = c.hs; ga.dhs = c.dhs; ga.a_da = c.a_da; ga.dgx = c.dgx; ga.dgx_sb = (long)H2 * Tp;
+    ga.B = B; ga.Tf = n_frames; ga.Tp = Tp; ga.coff = n.coff;
+    ga.gx = c.gx;
+    ga.g4 = p.g4 ? 1 : 0;
+    ga.gwxa = g.audio_in ? gpacked + y.wxa : nullptr;
+    ga.da16 = c.da16; ga.da16_pitch = c.da16_pitch; ga.da16_odd = c.da16_odd; ga.skip_da32 = p.skip_da32 ? 1 : 0;
+    ga.h16 = c.h16; ga.h16_odd = c.h16_odd;
+
+    if (hipMemsetAsync(gpacked, 0, y.total * sizeof(float), st) != hipSuccess) return SWN_E_LAUNCH;
+    if (chain) {
+        if (c.wdt16) hipLaunchKernelGGL(wd_t16_kernel, dim3(1024), dim3(256), 0, st, packed + y.wd, c.wdt16, L, g.K, H, g.Hp);
+        if (c.wup_part && hipMemsetAsync(c.wup_part, 0, (size_t)SWN_WUP_COPIES * 256 * sizeof(float), st) != hipSuccess) return SWN_E_LAUNCH;
+        // Only level 0 needs zeros: levels 1..L are written whole by the skip data gradient (accumulate = 0) before anything
+        // is added to them; d h_0 only ever receives additions.  (Zeroing all L + 1 levels was 710 MB = 0.11 ms per step at REF6.)
+        // (hipMemset2DAsync's fill kernel took 273 us for these 8 rows of 12.7 MB; a plain grid-stride store kernel is at the HBM rate)
+        hipLaunchKernelGGL(zero_rows_kernel, dim3(512, B), dim3(256), 0, st, c.dhs, (size_t)(L + 1) * H * Tp, (size_t)H * Tp);
+        c.head();
+        c.chain_layers();
+        if (c.dgx_all) c.inx_all();
+        if (c.wup_part) hipLaunchKernelGGL(wup_fold_kernel, dim3(1), dim3(256), 0, st, c.wup_part, gpacked + y.wup, g.U);
+        // ---- input layer
+        if (g.kind == SWN_KIND_LAPLACE) hipLaunchKernelGGL(input_bwd_kernel<SWN_KIND_LAPLACE>, dim3(H, B), dim3(256), 0, st, ga, gpacked);
+        else hipLaunchKernelGGL(input_bwd_kernel<SWN_KIND_SOFTMAX>, dim3(H, B), dim3(256), 0, st, ga, gpacked);
+    } else {
+        // ---- BL6 class, mixed precision: head, gated layers and input layer in the fused stack of csrc/swn_bwd_bl6.hip (it writes
+        //      d h_0 whole, keeps the other carries in its own buffers and does the input layer from its accumulators)
+        rc = swn_bl6_bwd_stack(g, y, packed, cond, reinterpret_cast<const float*>(audio), c.hs16, grad_out, c.dcond, gpacked, c.bl6, B,
+                               n_frames, Tp, st, c.gx16, c.xm16, fused_drop ? reinterpret_cast<unsigned short*>(c.dxm) : nullptr);
+        if (rc < 0) return rc;
+    }
+    c.frontend();
     return swn_launch_status(where);
 }
 
@@ -2059,9 +2097,8 @@ extern "C" int swn_backward(const swn_net_desc* d, const float* packed, const fl
                             const float* grad_out, int batch, int n_frames, float* work, float* gpacked, int precision,
                             void* stream_) {
     if (!swn_precision_ok(precision)) return SWN_E_BADARG;
-    SwnModeScope mode(precision);
-    return backward_impl(d, packed, aux, cond, fe_work, audio, fwd_work, hs_opt, nullptr, nullptr, grad_out, batch, n_frames,
-                         work, gpacked, stream_, "swn_backward");
+    return backward_impl(SWN_TRAIN_PLAIN, d, packed, aux, cond, fe_work, audio, fwd_work, hs_opt, nullptr, nullptr, nullptr, nullptr,
+                         grad_out, batch, n_frames, work, gpacked, precision, stream_, "swn_backward");
 }
 
 // mixed-precision backward of the BL6 class with the gated layers fused per layer: work_bf16_dev is the work buffer
@@ -2069,7 +2106,8 @@ extern "C" int swn_backward(const swn_net_desc* d, const float* packed, const fl
 extern "C" size_t swn_backward_bf16_work_floats(const swn_net_desc* d, int batch, int n_frames) {
     SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1) return 0;
     const SwnTrainLen n = swn_train_len(g, n_frames);
-    if (g.kind != SWN_KIND_LAPLACE || n.Tp < 1 || !swn_bl6_bwd_supported(g, batch, n.Tp, n_frames)) return 0;
+    if (g.kind != SWN_KIND_LAPLACE || n.Tp < 1 ||
+        !swn_train_path(d, g, batch, n_frames, n, SWN_TRAIN_BL6, SWN_PRECISION_BF16, nullptr, false).bl6_bwd) return 0;
     return swn_bwd_bl6_layout(g, batch, n_frames, n, false, swn_bl6_bwd_scratch_bytes(g, batch, n.Tp, false)).total;
 }
 
@@ -2078,9 +2116,8 @@ extern "C" int swn_backward_bf16(const swn_net_desc* d, const float* packed, con
                                  const float* grad_out, int batch, int n_frames, float* work, float* gpacked, void* stream_) {
     if (!work_bf16) return SWN_E_BADARG;
     if (swn_backward_bf16_work_floats(d, batch, n_frames) == 0) return SWN_E_UNSUPPORTED;
-    SwnModeScope mode(SWN_PRECISION_BF16);                 // this path exists in the mixed-precision arithmetic only
-    return backward_impl(d, packed, aux, cond, fe_work, audio, fwd_work, nullptr, nullptr, nullptr, grad_out, batch, n_frames,
-                         work, gpacked, stream_, "swn_backward_bf16", work_bf16);
+    return backward_impl(SWN_TRAIN_BL6, d, packed, aux, cond, fe_work, audio, fwd_work, nullptr, work_bf16, nullptr, nullptr, nullptr,
+                         grad_out, batch, n_frames, work, gpacked, SWN_PRECISION_BF16, stream_, "swn_backward_bf16");
 }
 
 // swn_backward after swn_forward_bf16_keep (GEMM-stack geometries, mixed-precision mode): the gate pre-activations come from
@@ -2089,9 +2126,8 @@ extern "C" int swn_backward_keep(const swn_net_desc* d, const float* packed, con
                                  const float* fe_work, const void* audio, const float* fwd_work, const float* a_keep,
                                  const float* grad_out, int batch, int n_frames, float* work, float* gpacked, void* stream_) {
     if (!a_keep) return SWN_E_BADARG;
-    SwnModeScope mode(SWN_PRECISION_BF16);                 // follows swn_forward_bf16_keep: mixed precision by construction
-    return backward_impl(d, packed, aux, cond, fe_work, audio, fwd_work, nullptr, nullptr, nullptr, grad_out, batch, n_frames,
-                         work, gpacked, stream_, "swn_backward_keep", nullptr, a_keep);
+    return backward_impl(SWN_TRAIN_KEEP, d, packed, aux, cond, fe_work, audio, fwd_work, nullptr, nullptr, a_keep, nullptr, nullptr,
+                         grad_out, batch, n_frames, work, gpacked, SWN_PRECISION_BF16, stream_, "swn_backward_keep");
 }
 
 extern "C" size_t swn_backward_drop_work_floats(const swn_net_desc* d, int batch, int n_frames) {
@@ -2101,7 +2137,7 @@ extern "C" size_t swn_backward_drop_work_floats(const swn_net_desc* d, int batch
     // the larger of the generic chain's layout and the fused BL6 path's
     const size_t chain = swn_bwd_layout(g, batch, n_frames, n, true).total;
     size_t fused = 0;
-    if (g.kind == SWN_KIND_LAPLACE && swn_bl6_bwd_supported(g, batch, n.Tp, n_frames))
+    if (swn_train_path(d, g, batch, n_frames, n, SWN_TRAIN_DROP, SWN_PRECISION_BF16, nullptr, false).bl6_bwd)
         fused = swn_bwd_bl6_layout(g, batch, n_frames, n, true, swn_bl6_bwd_scratch_bytes(g, batch, n.Tp, true)).total;
     return chain > fused ? chain : fused;
 }
@@ -2111,9 +2147,8 @@ extern "C" int swn_backward_drop(const swn_net_desc* d, const float* packed, con
                                  const float* const* drop_h, const float* grad_out, int batch, int n_frames, float* work,
                                  float* gpacked, int precision, void* stream_) {
     if (!drop_x || !swn_precision_ok(precision)) return SWN_E_BADARG;
-    SwnModeScope mode(precision);
-    return backward_impl(d, packed, aux, nullptr, fe_work, audio, fwd_work, hs_opt, drop_x, drop_h, grad_out, batch, n_frames,
-                         work, gpacked, stream_, "swn_backward_drop");
+    return backward_impl(SWN_TRAIN_DROP, d, packed, aux, nullptr, fe_work, audio, fwd_work, hs_opt, nullptr, nullptr, drop_x, drop_h,
+                         grad_out, batch, n_frames, work, gpacked, precision, stream_, "swn_backward_drop");
 }
 
 extern "C" int swn_laplace_head_backward(const swn_net_desc* d, const float* raw, int batch, int tp, const float* gmu,

@@ -9,19 +9,20 @@
 #include "swn_geom.hpp"
 
 // ---- cross-file functions ------------------------------------------------------------------------------------------------
-// swn_stack.hip: does the dropout-mode forward of the mixed-precision mode run on the bf16 time-major GEMM stack?  (the
+// swn_stack.hip: may the dropout-mode forward of the mixed-precision mode run on the bf16 time-major GEMM stack?  (the
 // geometry class of swn_stack_bf16g.hip, its 32-bit operand offsets, a sequence long enough for the bf16-copy contractions)
 bool swn_drop_g16(const swn_net_desc* d, int batch, long Tp);
 
-// swn_train.hip.  relu(skip), relu(out_1) from the hidden states in `work` (SwnFwdLayout) through the contraction kernels;
-// the gated layers of the dropout-mode forward in the mixed-precision mode (layer l's pre-activations kept at a_scr +
-// l * a_stride); the sample-rate in_x of every layer over the masked conditioning
-int swn_train_head_acts(const SwnGeom& g, const float* packed, float* work, int batch, long Tp, hipStream_t st);
+// swn_train.hip, through its contraction kernels in the arithmetic `bf16` (mixed precision) or exact fp32.  relu(skip),
+// relu(out_1) from the hidden states in `work` (SwnFwdLayout); the gated layers of the dropout-mode forward in the
+// mixed-precision mode (layer l's pre-activations kept at a_scr + l * a_stride); the sample-rate in_x of every layer over
+// the masked conditioning
+int swn_train_head_acts(const SwnGeom& g, const float* packed, float* work, int batch, long Tp, bool bf16, hipStream_t st);
 int swn_train_layers_forward_drop(const SwnGeom& g, const SwnLayout& y, const float* packed, const void* audio, const float* gx,
                                   const float* const* drop_h, float* hs, float* a_scr, size_t a_stride, float* hmask, int B,
                                   int n_frames, int Tp, hipStream_t st);
 int swn_train_inx_forward(const SwnGeom& g, const SwnLayout& y, const float* packed, const float* xm, float* gx,
-                          int B, int Tx, int Tp, hipStream_t st, unsigned short* wx16, bool g4);
+                          int B, int Tx, int Tp, bool bf16, hipStream_t st, unsigned short* wx16, bool g4);
 
 // swn_stack_bf16g.hip: the tiled bf16 GEMM stack of the large geometries (H a multiple of 64 beyond the BL6 class)
 int swn_bf16g_geom(const swn_net_desc* d, SwnGeom* g);
@@ -170,8 +171,7 @@ static inline SwnFwdLayout swn_fwd_drop_layout(const SwnGeom& g, int B, const Sw
 
 // backward scratch.  Float offsets; the bf16 sections hold rows of swn_da16_pitch(Tp) elements.  Two forms:
 // swn_bwd_layout      the chain (swn_backward, swn_backward_keep, swn_backward_drop off the fused path); drop: the dropout
-//                     mode's sections exist.  Which of the mixed-precision sections a call uses is its own decision
-//                     (arithmetic mode, 2 GiB reach of the kernels' 32-bit offsets)
+//                     mode's sections exist.  Which of the mixed-precision sections a call uses: SwnTrainPath below
 // swn_bwd_bl6_layout  the compact form of the fused BL6 path (swn_backward_bf16; swn_backward_drop after swn_bl6_drop_forward):
 //                     dcond | dfe | dxm | bl6, none of the other sections exists; bl6_bytes = swn_bl6_bwd_scratch_bytes(.., drop)
 struct SwnBwdLayout {
@@ -223,4 +223,81 @@ static inline SwnBwdLayout swn_bwd_bl6_layout(const SwnGeom& g, int B, int n_fra
     o.bl6 = drop ? o.dxm + swn_al((size_t)B * n.Tx * swn_a0x(&g) / 2) : o.dxm;
     o.total = o.bl6 + swn_al_bytes(bl6_bytes);
     return o;
+}
+
+// ---- the path of one call --------------------------------------------------------------------------------------------------
+// Which kernels a training call runs and which sections of its buffers they use, resolved ONCE from what the call is given.
+// A forward and the backward that follows it resolve the same record (same net, sizes, precision, masks, owner of hs); the
+// size queries resolve it too.  The predicates swn_drop_g16, swn_drop_inx16, swn_drop_bf16_forward, swn_bl6_drop_supported
+// and swn_bl6_bwd_supported are asked here and nowhere else.  Plain host arithmetic, no device call.
+enum SwnTrainEntry {      // the entry point that asks
+    SWN_TRAIN_PLAIN,      // swn_forward, swn_backward
+    SWN_TRAIN_KEEP,       // swn_backward_keep, after swn_forward_bf16_keep: mixed precision by construction
+    SWN_TRAIN_BL6,        // swn_backward_bf16, after swn_forward_bf16 at the BL6 class: mixed precision by construction
+    SWN_TRAIN_DROP        // swn_forward_drop, swn_backward_drop
+};
+enum SwnTrainRoute {
+    SWN_ROUTE_CHAIN,      // the generic chain of contraction kernels (SwnFwdLayout, swn_bwd_layout)
+    SWN_ROUTE_BL6,        // backward: swn_bl6_bwd_stack over swn_forward_bf16's hidden states (swn_bwd_bl6_layout)
+    SWN_ROUTE_BL6_DROP    // swn_bl6_drop_forward (SwnBl6DropLayout), swn_bl6_bwd_stack with sample-rate in_x operands
+};
+enum SwnPreact {          // where the backward takes a layer's gate pre-activations from
+    SWN_PREACT_RECOMPUTE, // one more conv GEMM per layer
+    SWN_PREACT_FWD_WORK,  // SwnFwdLayout::a_keep: the dropout forward of the same mode kept them
+    SWN_PREACT_CALLER     // swn_backward_keep's a_keep
+};
+struct SwnTrainPath {
+    bool bf16, drop;      // mixed-precision arithmetic; dropout mode
+    int route;
+    bool bl6_bwd;         // swn_bl6_bwd_stack serves this net and size (entries BL6 and DROP)
+    // dropout mode
+    bool g16;             // SwnFwdLayout ends with the GEMM stack's sections (whatever the precision: the sizes cover both)
+    bool fwd16;           // chain forward: bf16-operand layers, every layer's pre-activations kept
+    bool inx16;           // the three in_x contractions read bf16 copies: xm bf16 rows, wx16 / wxt16, d gx of all layers bf16 rows
+    bool stack16;         // ... and the forward runs on the GEMM stack
+    int preact;
+    bool g4;              // gx / the kept pre-activations are in the G4 layout (swn_geom.hpp)
+    // backward chain
+    bool da16;            // gate_bwd leaves da as bf16 rows
+    bool h16;             // ... and the layer's (masked) input: Q operand of the layer weight gradients
+    bool wdt16;           // transposed bf16 layer matrices: both operands of the layer data gradients are bf16
+    bool skip_da32;       // nobody reads the fp32 da then
+    bool dgx_all;         // every layer's d gx is kept, the in_x contractions run once behind the layers
+    bool dgx16_cond;      // without dropout: cond_bwd_kernel reads a layer's d gx as bf16 rows
+};
+// own_hs: the caller passes its own hidden-state buffer.  drop_h: the dropout mode's host array of mask pointers (else null)
+static inline SwnTrainPath swn_train_path(const swn_net_desc* d, const SwnGeom& g, int B, int n_frames, const SwnTrainLen& n,
+                                          int entry, int precision, const float* const* drop_h, bool own_hs) {
+    SwnTrainPath p{};
+    const long Tp = n.Tp;
+    p.drop = entry == SWN_TRAIN_DROP;
+    p.bf16 = precision == SWN_PRECISION_BF16 || entry == SWN_TRAIN_KEEP || entry == SWN_TRAIN_BL6;
+    p.bl6_bwd = (entry == SWN_TRAIN_BL6 || p.drop) && swn_bl6_bwd_supported(g, B, Tp, n_frames);
+    // dropout as run.sh trains the BL6 class (no mask between layers): the fused path, unless the caller wants fp32 hidden states
+    if (entry == SWN_TRAIN_BL6) p.route = SWN_ROUTE_BL6;
+    else if (p.drop && p.bf16 && !own_hs && swn_bl6_drop_supported(g, B, Tp, n_frames, drop_h)) p.route = SWN_ROUTE_BL6_DROP;
+    else p.route = SWN_ROUTE_CHAIN;
+    const bool chain = p.route == SWN_ROUTE_CHAIN;
+    p.g16 = p.drop && swn_drop_g16(d, B, Tp);
+    p.fwd16 = chain && p.drop && p.bf16 && swn_drop_bf16_forward(&g);
+    // a caller that owns hs gets the exact layout of the fp32 chain in every section it may read: no bf16 copies, and the
+    // backward recomputes the pre-activations
+    p.inx16 = p.fwd16 && !own_hs && swn_drop_inx16(&g, Tp);
+    p.stack16 = p.g16 && p.inx16;
+    p.preact = entry == SWN_TRAIN_KEEP ? SWN_PREACT_CALLER : p.fwd16 && !own_hs ? SWN_PREACT_FWD_WORK : SWN_PREACT_RECOMPUTE;
+    p.g4 = entry == SWN_TRAIN_KEEP || p.stack16;
+    // the kernels reach the second (odd) copy of da / h through a 32-bit byte offset from an utterance's rows: it must stay
+    // below 2 GiB, else that operand stays fp32
+    const size_t pitch = (size_t)swn_da16_pitch(Tp), H = g.H, H2 = 2 * H;
+    p.da16 = chain && p.bf16;
+    p.h16 = p.da16 && Tp >= 256 && ((size_t)B * H * pitch + H * pitch) * 2 < (1ull << 31);
+    p.wdt16 = p.da16 && g.Hp == g.H && H2 % 32 == 0 && ((size_t)B * H2 * pitch + H2 * pitch) * 2 < (1ull << 31);
+    p.skip_da32 = p.wdt16 && Tp >= 256;      // launch_reduce / launch_time take their bf16-copy kernels under exactly these conditions
+    p.dgx_all = chain && p.drop && g.seg == 1;
+    // (GEMM-stack class; the small nets keep fp32 here: the rounding moved a 2e-2 gradient check of the 32-channel fixtures)
+    p.dgx16_cond = entry == SWN_TRAIN_KEEP && p.da16 && (long)pitch <= 2L * Tp;
+    return p;
+}
+static inline SwnFwdLayout swn_fwd_layout_of(const SwnGeom& g, int B, const SwnTrainLen& n, const SwnTrainPath& p) {
+    return p.drop ? swn_fwd_drop_layout(g, B, n, p.g16, p.g16 ? swn_bf16g_weight_bytes(g) : 0) : swn_fwd_layout(g, B, n.Tp);
 }

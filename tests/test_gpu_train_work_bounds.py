@@ -213,7 +213,8 @@ def test_drop_bf16_ref6_stack(gpu_ok):          # GEMM-stack forward, dgx16_all 
     _drop(C.ref6_laplace(1, 4), 1, 3, BF16)
 
 
-def test_drop_bf16_ref6_own_hs(gpu_ok):         # bf16 in_x copies without the GEMM stack
+def test_drop_bf16_ref6_own_hs(gpu_ok):         # caller-owned hs: bf16-operand layers, no bf16 in_x copies, recomputed pre-activations
+                                                # (values: test_gpu_drop_own_hs_values.py)
     _drop(C.ref6_laplace(1, 4), 1, 3, BF16, own_hs=True)
 
 

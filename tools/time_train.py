@@ -1,5 +1,6 @@
 """dev tool: one training step (forward + backward HIP kernels) at the BASELINE cfg4 shape.
-  python tools/time_train.py [B Tf [fp32|bf16 [bl6|ref6]]]   (third argument: arithmetic of the backward contractions)"""
+  python tools/time_train.py [B Tf [fp32|bf16 [bl6|ref6|tiny]]]   (third argument: arithmetic of the backward contractions;
+  tiny: the smallest net alone, where the host's share of a step is largest)"""
 import sys, os
 _R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, _R)
 import torch
@@ -11,13 +12,16 @@ B, Tf = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (8, 150)
 from shallow_wavenet_amd.runtime import train_precision
 MODE = sys.argv[3] if len(sys.argv) > 3 else "fp32"
 train_precision(MODE)
-ONLY = sys.argv[4].upper() if len(sys.argv) > 4 else None      # optional 4th argument: bl6 | ref6
+ONLY = sys.argv[4].upper() if len(sys.argv) > 4 else None      # optional 4th argument: bl6 | ref6 | tiny
 WITH_OPT = len(sys.argv) > 5 and sys.argv[5] == "opt"           # optional 5th argument "opt": Adam step inside the loop
 CHAIN = len(sys.argv) > 6 and sys.argv[6] == "chain"            # optional 6th argument "chain": generic per-layer backward
 FUSED_ADAM = "fused_adam" in sys.argv                            # anywhere: torch.optim.Adam(fused=True)
 DROP = 0.5 if "drop" in sys.argv else 0.0                        # anywhere "drop": do_prob = 0.5 and forward(do=True), as run.sh trains
 SEG5 = "seg5" in sys.argv                                        # anywhere "seg5": seg = 5, lpc = 4 (run.sh's own setting)
-for nm, cfg in (("BL6", C.bl6_laplace(5, 4) if SEG5 else C.bl6_laplace(1, 0)), ("REF6", C.ref6_laplace(5, 4) if SEG5 else C.ref6_laplace(1, 4))):
+for nm, cfg in (("BL6", C.bl6_laplace(5, 4) if SEG5 else C.bl6_laplace(1, 0)), ("REF6", C.ref6_laplace(5, 4) if SEG5 else C.ref6_laplace(1, 4)),
+                ("TINY", C.tiny("laplace", 1, 0))):      # (tiny only when asked for by name)
+    if nm == "TINY" and ONLY != "TINY":
+        continue
     if ONLY and nm != ONLY:
         continue
     m = mc.CSWNV(**dict(cfg.ctor_kwargs(), do_prob=DROP))
