@@ -678,6 +678,33 @@ size_t swn_logmel_work_bytes(int n_fft, int hop, const swn_logmel_entry* entries
 int    swn_logmel(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev, const int32_t* bank_host,
                   const swn_logmel_entry* entries_host, int n_entries, float* work_dev, void* stream);
 
+/* ---- mel-cepstrum from waveforms (melspec.MelCepstrumExtractor; csrc/swn_melspec.hip) -----------------------------------------
+ * The definition.  Frames, reflect padding, periodic Hann window and amplitude A[f][b], b = 0 .. n_fft / 2, are exactly those
+ * of swn_logmel (F = 1 + len / hop).  Then, with 0 <= order <= min(SWN_MCEP_MAX_ORDER, n_fft / 2) and floor > 0:
+ *   1. L[f][b] = ln(max(A[f][b], floor)), evaluated in double and rounded once to fp32, as the log-mel output is
+ *   2. the real cepstrum v = irfft(L) of length n_fft
+ *   3. the one-sided cepstrum c[0] = v[0], c[k] = 2 v[k] for 0 < k < n_fft / 2, c[n_fft / 2] = v[n_fft / 2], so that
+ *      |exp(sum_k c(k) z^-k)| = A (the convention of the MLSA filter of swn_postfilter_chunk)
+ *   4. the frequency transform with all-pass constant alpha to order M = order (SPTK freqt): mc[f][0 .. M]
+ *   5. steps 2 - 4 are linear: mc[f] = G L[f], G of shape (M + 1, n_fft / 2 + 1), evaluated in float64 on the host, stored
+ *      as fp32, its columns zero-padded to a multiple of 4 (alpha exists only in how the caller built G)
+ *   6. output fp32, time-major: frame f, coefficient m at out_dev + (f - f0) * (order + 1) + m.  Each coefficient is one
+ *      chain over the bins in ascending order (the k order of the matrix instruction), so a frame's values do not depend on
+ *      the tile, the entry, the batch, the frame range or the window: any partition gives the same bits, as for swn_logmel.
+ * On the first n_fft / 2 + 1 cepstral coefficients this is pysptk.sp2mc(A^2, M, alpha); parity with pysptk is not pinned.  It
+ * is the cepstrum of the short-time spectrum, not of WORLD's cheaptrick envelope.
+ * tables_dev (swn_mcep_table_floats floats): cos(2 pi m / n_fft) for m < n_fft, the window (n_fft), then G row by row, every
+ * row (n_fft / 2 + 1 rounded up to 4) floats.  Entries, their rules and work_dev (swn_mcep_work_bytes) are those of
+ * swn_logmel, with out_dev holding (f1 - f0) * (order + 1) floats.
+ * SWN_E_BADARG, found on the host before anything is launched, text in swn_last_error_detail: order < 0, order >
+ * SWN_MCEP_MAX_ORDER, order > n_fft / 2, floor <= 0 or not finite, and everything swn_logmel refuses for n_fft, hop and the
+ * entries.  The size queries return 0 for arguments the call refuses. */
+#define SWN_MCEP_MAX_ORDER 63
+size_t swn_mcep_table_floats(int n_fft, int order);
+size_t swn_mcep_work_bytes(int n_fft, int hop, const swn_logmel_entry* entries_host, int n_entries);
+int    swn_mcep(int n_fft, int hop, int order, float floor, const float* tables_dev, const swn_logmel_entry* entries_host,
+                int n_entries, float* work_dev, void* stream);
+
 /* ---- log-mel pool: the new frames of many sessions per call (melspec.LogMelPool; csrc/swn_melspec.hip) -----------------------
  * Every session owns one slot of win_dev: window_floats floats (swn_logmel_pool_window_floats(n_fft, max_chunk) = n_fft +
  * max_chunk: under the streaming rule of melspec.py a session holds at most n_fft samples between calls) that hold the tail

@@ -96,6 +96,7 @@ POSTFILTER_MULAW_ENTRIES = 256                 # SWN_POSTFILTER_MULAW_ENTRIES
 SPECTRAL_MAX_SIZES, SPECTRAL_MAX_FFT = 32, 2048   # SWN_SPECTRAL_MAX_SIZES, SWN_SPECTRAL_MAX_FFT
 LOGMEL_MAX_MELS, LOGMEL_MAX_ENTRIES = 128, 64     # SWN_LOGMEL_MAX_MELS, SWN_LOGMEL_MAX_ENTRIES
 LOGMEL_POOL_MAX_ENTRIES = 64                   # SWN_LOGMEL_POOL_MAX_ENTRIES (include/swn_hip.h): entries per log-mel pool call
+MCEP_MAX_ORDER = 63                            # SWN_MCEP_MAX_ORDER (include/swn_hip.h)
 
 
 def desc_from_cfg(cfg: NetConfig) -> NetDesc:
@@ -214,6 +215,9 @@ SIGNATURES = {
     "swn_logmel_work_bytes": (c_size_t, [c_int, c_int, POINTER(LogMelEntry), c_int]),
     "swn_logmel": (c_int, [c_int, c_int, c_int, c_float, c_int, c_void_p, POINTER(c_int32), POINTER(LogMelEntry), c_int,
                            c_void_p, c_void_p]),
+    "swn_mcep_table_floats": (c_size_t, [c_int, c_int]),
+    "swn_mcep_work_bytes": (c_size_t, [c_int, c_int, POINTER(LogMelEntry), c_int]),
+    "swn_mcep": (c_int, [c_int, c_int, c_int, c_float, c_void_p, POINTER(LogMelEntry), c_int, c_void_p, c_void_p]),
     "swn_logmel_pool_window_floats": (c_size_t, [c_int, c_int]),
     "swn_logmel_pool_work_bytes": (c_size_t, [c_int, c_int, c_int, c_size_t, POINTER(LogMelPoolEntry), c_int]),
     "swn_logmel_pool": (c_int, [c_int, c_int, c_int, c_float, c_int, c_void_p, POINTER(c_int32), c_void_p, c_size_t, c_void_p,

@@ -34,6 +34,21 @@
 // destination lies below every later block's source) and appends the entry's new samples from the staged buffer.  Then
 // logmel_kernel<true> computes the frames from the updated windows with the arithmetic of swn_logmel and writes them
 // channel-major, out[m * out_stride + (f - f0)]: the layout the pool front end stages.
+//
+// Mel-cepstrum (swn_mcep, melspec.MelCepstrumExtractor; restated in include/swn_hip.h and melspec.py).  Frames, padding,
+// window and amplitude A[f][b] are those above.  Then
+//   log amplitude  L[f][b] = ln(max(A[f][b], floor)), floor > 0: in double, rounded once to fp32 (as the log-mel output)
+//   cepstrum       v = irfft(L) of length n_fft; one-sided c[0] = v[0], c[k] = 2 v[k] for 0 < k < n_fft / 2,
+//                  c[n_fft / 2] = v[n_fft / 2], so that |exp(sum_k c(k) z^-k)| = A: the convention of dsp.py and the MLSA filter
+//   mel-cepstrum   the frequency transform with all-pass constant alpha to order M (SPTK freqt): mc[f][0 .. M]
+//   as a product   these steps are linear: mc[f] = G L[f] with G (M + 1, n_fft / 2 + 1), evaluated in float64 on the host
+//                  (melspec.mcep_matrix), stored as fp32, its columns zero-padded to a multiple of 4
+//   output         fp32 at out[frame][coefficient] (time-major); each coefficient is one chain over the bins in ascending
+//                  order - the k order of the matrix instruction - so a frame's values do not depend on the tile, the row of
+//                  the tile, the entry, the batch, the frame range or the window, as for the log-mel frames
+// On the first n_fft / 2 + 1 cepstral coefficients this is what pysptk.sp2mc(A^2, M, alpha) computes (parity with pysptk is
+// not pinned: the library is absent).  It is the cepstrum of the short-time spectrum, not of WORLD's cheaptrick envelope.
+// The table of swn_mcep: cos, window, then G padded.  mcep_kernel below says how the block works.
 #include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
 #include "swn_mma.hpp"
@@ -62,6 +77,13 @@ struct LmArgs {
 };
 static_assert(sizeof(LmArgs) + 2 * sizeof(void*) <= 4096, "the by-value kernel arguments must stay inside 4 KB");
 
+struct McArgs {
+    LmEntry e[SWN_LOGMEL_MAX_ENTRIES];
+    int n_entries, n, hop, order;
+    float floor_;
+};
+static_assert(sizeof(McArgs) + 2 * sizeof(void*) <= 4096, "the by-value kernel arguments must stay inside 4 KB");
+
 struct LpMove {
     int slot, n_held, n_drop, new_off, n_new;
 };
@@ -79,6 +101,11 @@ __host__ __device__ inline size_t lm_lds_floats(int n) {
     // 16 frames, cos table, weights (at most two filters cover a bin), weight offsets and runs
     return (size_t)LM_FR * lm_pitch(n) + n + 2 * (n / 2 + 1) + 2 * SWN_LOGMEL_MAX_MELS;
 }
+
+// mel-cepstrum: the pitch of L (the bins rounded up to 4, plus 2: see mcep_kernel) and the block's LDS: the frame image, which
+// L later overlays (16 (n / 2 + 6) <= 16 (n + 2) floats), and the cos table
+__host__ __device__ inline int mc_l_pitch(int n) { return lm_amp_pitch(n) + 2; }
+__host__ __device__ inline size_t mc_lds_floats(int n) { return (size_t)LM_FR * lm_pitch(n) + n; }
 
 thread_local const char* lm_who = "swn_logmel";      // the entry point the checks below report for
 struct LmWho {
@@ -152,33 +179,27 @@ int lm_check_entries(int n, int hop, const swn_logmel_entry* en, int n_entries, 
     return SWN_OK;
 }
 
-// CM: the output is channel-major (swn_logmel_pool), else time-major (swn_logmel); nothing else differs
-template <bool CM>
-__global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const LmArgs a, const float* __restrict__ tables, float* amp_work) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int n = a.n, hop = a.hop, pitch = lm_pitch(n), bins = n / 2 + 1, ap = lm_amp_pitch(n);
-    float* img = sm;                            // [16 frames][pitch]: windowed and folded, s then d
-    float* tab = img + LM_FR * pitch;           // cos(2 pi m / n)
-    float* wts = tab + n;                       // the filters' runs of weights, back to back
-    int* woff = reinterpret_cast<int*>(wts + 2 * bins);     // [n_mels] first weight of each run
-    int* sbank = woff + SWN_LOGMEL_MAX_MELS;                // [n_mels] first bin | bins << 16
-    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, kq = lane >> 4;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-
+// the entry this block's tile belongs to; *fbase receives the first frame of the tile
+template <class Args>
+__device__ inline LmEntry lm_block_entry(const Args& a, int* fbase) {
     int ei = 0;
     for (int i = 1; i < a.n_entries; ++i)       // the last entry whose first tile is not past this block (empty ones share
         if (a.e[i].tile0 <= (int)blockIdx.x) ei = i;    // their tile0 with the next entry, which wins)
     const LmEntry e = a.e[ei];
-    const int fbase = e.f0 + ((int)blockIdx.x - e.tile0) * LM_FR;    // first frame of the tile
+    *fbase = e.f0 + ((int)blockIdx.x - e.tile0) * LM_FR;
+    return e;
+}
 
+// The phase logmel_kernel and mcep_kernel share: the cos table into `tab`, the windowed and folded frames of the tile into
+// `img`, a barrier, the DFT, and the amplitudes A[fr][b] to amp[fr * lm_amp_pitch(n) + b] (global memory).  The caller puts
+// __threadfence_block() and a barrier between this and its reads of amp; from that barrier on img is dead.
+__device__ __forceinline__ void lm_tile_amplitudes(int n, int hop, const LmEntry& e, int fbase, const float* __restrict__ tables,
+                                                   float* img, float* tab, float* amp) {
+    const int pitch = lm_pitch(n), bins = n / 2 + 1, ap = lm_amp_pitch(n);
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, kq = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int i = tid; i < n; i += LM_THREADS) tab[i] = tables[i];
-    for (int m = tid; m < a.n_mels; m += LM_THREADS) {
-        sbank[m] = a.bank[m];
-        woff[m] = a.woff[m];
-    }
     const float* win = tables + n;
-    const float* wsrc = tables + 2 * n;
-    for (int i = tid; i < 2 * bins; i += LM_THREADS) wts[i] = wsrc[i];      // the table holds 2 bins floats, zero past the runs
 
     // frame image, folded once: with y[j] = x[p(j)] w[j], X[b] = sum over j < n / 2 of (y[j] + (-1)^b y[j + n / 2]) e^(-2 pi i j b / n),
     // so row fr holds s[j] = y[j] + y[j + n / 2] (even bins) and then d[j] = y[j] - y[j + n / 2] (odd bins), n / 2 each, and
@@ -213,7 +234,6 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const LmArgs a, cons
     // wave w: the runs of 32 bins w, w + 4, ... as a 16-bin tile of the even bins (operand s) and one of the odd bins
     // (operand d); a bin past the last one reads valid table entries and is dropped
     const int n_runs = (bins + 31) / 32, quarter = n / 4, steps = n / 8;
-    float* amp = amp_work + (size_t)blockIdx.x * LM_FR * ap;
     const float* srow = img + c * pitch + kq;
     const float* drow = srow + half;
     for (int pp = w; pp < n_runs; pp += 4) {
@@ -249,6 +269,30 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const LmArgs a, cons
             }
         }
     }
+}
+
+// CM: the output is channel-major (swn_logmel_pool), else time-major (swn_logmel); nothing else differs
+template <bool CM>
+__global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const LmArgs a, const float* __restrict__ tables, float* amp_work) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int n = a.n, pitch = lm_pitch(n), bins = n / 2 + 1, ap = lm_amp_pitch(n);
+    float* img = sm;                            // [16 frames][pitch]: windowed and folded, s then d
+    float* tab = img + LM_FR * pitch;           // cos(2 pi m / n)
+    float* wts = tab + n;                       // the filters' runs of weights, back to back
+    int* woff = reinterpret_cast<int*>(wts + 2 * bins);     // [n_mels] first weight of each run
+    int* sbank = woff + SWN_LOGMEL_MAX_MELS;                // [n_mels] first bin | bins << 16
+    const int tid = threadIdx.x;
+    int fbase;
+    const LmEntry e = lm_block_entry(a, &fbase);
+
+    for (int m = tid; m < a.n_mels; m += LM_THREADS) {
+        sbank[m] = a.bank[m];
+        woff[m] = a.woff[m];
+    }
+    const float* wsrc = tables + 2 * n;
+    for (int i = tid; i < 2 * bins; i += LM_THREADS) wts[i] = wsrc[i];      // the table holds 2 bins floats, zero past the runs
+    float* amp = amp_work + (size_t)blockIdx.x * LM_FR * ap;
+    lm_tile_amplitudes(n, a.hop, e, fbase, tables, img, tab, amp);
     __threadfence_block();
     __syncthreads();
 
@@ -265,6 +309,65 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const LmArgs a, cons
         const float v = a.linear ? s : (float)log((double)fmaxf(s, a.floor_));
         if (CM) e.out[(size_t)m * e.stride + (fbase - e.f0 + fr)] = v;
         else e.out[(size_t)(fbase - e.f0 + fr) * a.n_mels + m] = v;
+    }
+}
+
+// Mel-cepstrum (swn_mcep; the definition is at the top of the file): the shared phase, then L = ln max(A, floor) of the tile's
+// 16 frames written over the dead frame image (pitch mc_l_pitch: with it a multiple of 4 plus 2, the 16 rows x 2 k lanes that
+// one half-wave's ds_read_b32 covers fall on 32 different banks; the columns from n / 2 + 1 on and the rows from f1 on are
+// zero), then mc = L G^T on v_mfma_f32_16x16x4_f32: the frames are the rows, K runs over the padded bins in ascending order,
+// wave w takes the 16-coefficient column tiles w, w + 4, ...; G comes from global memory (at most 64 x 1 028 floats, every
+// block reads the same ones).  Lane (c, kq) feeds L[c][4 s + kq] and G[16 t + c][4 s + kq] to step s and receives
+// frames 4 kq .. 4 kq + 3 of coefficient 16 t + c.  Coefficients past `order` are computed on zeros and not stored.
+__global__ __launch_bounds__(LM_THREADS) void mcep_kernel(const McArgs a, const float* __restrict__ tables, float* amp_work) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int n = a.n, bins = n / 2 + 1, ap = lm_amp_pitch(n), lp = mc_l_pitch(n), nc = a.order + 1;
+    float* img = sm;                            // [16 frames][lm_pitch(n)], then L [16 frames][lp]
+    float* tab = img + LM_FR * lm_pitch(n);     // cos(2 pi m / n)
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, kq = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int fbase;
+    const LmEntry e = lm_block_entry(a, &fbase);
+    float* amp = amp_work + (size_t)blockIdx.x * LM_FR * ap;
+    lm_tile_amplitudes(n, a.hop, e, fbase, tables, img, tab, amp);
+    __threadfence_block();
+    __syncthreads();                            // the amplitudes are there and no wave reads the image any more
+
+    const int fr_n = e.f1 - fbase < LM_FR ? e.f1 - fbase : LM_FR;     // frames of this tile that exist (>= 1)
+    for (int o = tid; o < LM_FR * lp; o += LM_THREADS) {
+        const int fr = o / lp, b = o - fr * lp;
+        // the log in double, rounded once, as the log-mel output takes it
+        img[o] = (fr < fr_n && b < bins) ? (float)log((double)fmaxf(amp[fr * ap + b], a.floor_)) : 0.f;
+    }
+    __syncthreads();
+
+    const float* G = tables + 2 * n;            // [order + 1][ap], zero from column n / 2 + 1 on
+    const float* lrow = img + c * lp + kq;
+    const int steps = ap / 4, n_tiles = (nc + 15) / 16;
+    for (int t = w; t < n_tiles; t += 4) {
+        const int col = 16 * t + c;
+        const bool live = col < nc;
+        const float* grow = G + (size_t)(live ? col : 0) * ap + kq;
+        swn_f32x4 acc = {};
+        int s = 0;
+        for (; s + 4 <= steps; s += 4) {        // four k steps per trip: the global loads ahead of the MFMAs
+            float g[4], l[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                g[u] = live ? grow[4 * (s + u)] : 0.f;
+                l[u] = lrow[4 * (s + u)];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(l[u], g[u], acc, 0, 0, 0);
+        }
+        for (; s < steps; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(lrow[4 * s], live ? grow[4 * s] : 0.f, acc, 0, 0, 0);
+        if (live) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int fr = 4 * kq + i;
+                if (fr < fr_n) e.out[(size_t)(fbase - e.f0 + fr) * nc + col] = acc[i];
+            }
+        }
     }
 }
 
@@ -332,13 +435,11 @@ int lm_fill_bank(LmArgs& a, int n_fft, int n_mels, const int32_t* bank_host) {
     return SWN_OK;
 }
 
-// the entries into the launch arguments (stride: channel-major calls), then the frame kernel
-template <bool CM>
-int lm_launch(LmArgs& a, int n_fft, int hop, int n_mels, float floor, int linear, const swn_logmel_entry* en, const int* strides,
-              int n_entries, long long tiles, const float* tables_dev, float* work_dev, hipStream_t st, const char* who) {
+// the entries into the launch arguments (stride: channel-major calls)
+void lm_fill_entries(LmEntry* out, const swn_logmel_entry* en, const int* strides, int n_entries) {
     int t = 0;
     for (int i = 0; i < SWN_LOGMEL_MAX_ENTRIES; ++i) {
-        LmEntry& o = a.e[i];
+        LmEntry& o = out[i];
         if (i < n_entries) {
             const swn_logmel_entry& e = en[i];
             o.wav = e.wav_dev; o.out = e.out_dev; o.t0 = e.t0; o.len = e.len; o.f0 = e.f0; o.f1 = e.f1; o.tile0 = t;
@@ -348,6 +449,13 @@ int lm_launch(LmArgs& a, int n_fft, int hop, int n_mels, float floor, int linear
             o.wav = nullptr; o.out = nullptr; o.t0 = o.len = o.f0 = o.f1 = o.stride = 0; o.tile0 = t;
         }
     }
+}
+
+// ... then the frame kernel
+template <bool CM>
+int lm_launch(LmArgs& a, int n_fft, int hop, int n_mels, float floor, int linear, const swn_logmel_entry* en, const int* strides,
+              int n_entries, long long tiles, const float* tables_dev, float* work_dev, hipStream_t st, const char* who) {
+    lm_fill_entries(a.e, en, strides, n_entries);
     a.n_entries = n_entries; a.n = n_fft; a.hop = hop; a.n_mels = n_mels; a.linear = linear; a.floor_ = floor;
     const size_t lds = lm_lds_floats(n_fft) * sizeof(float);
     // dynamic LDS from 64 KB on: set on every call (the attribute is per device)
@@ -376,6 +484,53 @@ extern "C" int swn_logmel(int n_fft, int hop, int n_mels, float floor, int linea
     (void)hipGetLastError();
     return lm_launch<false>(a, n_fft, hop, n_mels, floor, linear, entries_host, nullptr, n_entries, tiles, tables_dev, work_dev,
                             static_cast<hipStream_t>(stream), "swn_logmel");
+}
+
+// ---------------------------------------------------------------------------------------------------------- mel-cepstrum
+namespace {
+
+bool mc_sizes_ok(int n_fft, int order) {
+    return lm_sizes_ok(n_fft, 1) && order >= 0 && order <= SWN_MCEP_MAX_ORDER && order <= n_fft / 2;
+}
+
+}  // namespace
+
+extern "C" size_t swn_mcep_table_floats(int n_fft, int order) {
+    if (!mc_sizes_ok(n_fft, order)) return 0;
+    return 2 * (size_t)n_fft + (size_t)(order + 1) * lm_amp_pitch(n_fft);
+}
+
+extern "C" size_t swn_mcep_work_bytes(int n_fft, int hop, const swn_logmel_entry* entries_host, int n_entries) {
+    LmWho who("swn_mcep_work_bytes");
+    long long tiles = 0;
+    if (!lm_sizes_ok(n_fft, 1) || lm_check_entries(n_fft, hop, entries_host, n_entries, &tiles) != SWN_OK) return 0;
+    return (size_t)tiles * LM_FR * lm_amp_pitch(n_fft) * sizeof(float);
+}
+
+extern "C" int swn_mcep(int n_fft, int hop, int order, float floor, const float* tables_dev, const swn_logmel_entry* entries_host,
+                        int n_entries, float* work_dev, void* stream) {
+    LmWho who("swn_mcep");
+    if (!lm_sizes_ok(n_fft, 1)) return lm_fail("n_fft is not a multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT]");
+    if (order < 0 || order > SWN_MCEP_MAX_ORDER) return lm_fail("order outside [0, SWN_MCEP_MAX_ORDER]");
+    if (order > n_fft / 2) return lm_fail("order exceeds n_fft / 2: the one-sided cepstrum has n_fft / 2 + 1 coefficients");
+    if (!(floor > 0.f) || !(floor < 3.0e38f)) return lm_fail("floor must be a finite number > 0");
+    long long tiles = 0;
+    const int rc = lm_check_entries(n_fft, hop, entries_host, n_entries, &tiles);
+    if (rc != SWN_OK) return rc;
+    if (tiles == 0) return SWN_OK;                          // no frame in any entry
+    if (!tables_dev || !work_dev) return lm_fail("null pointer");
+    McArgs a;
+    lm_fill_entries(a.e, entries_host, nullptr, n_entries);
+    a.n_entries = n_entries; a.n = n_fft; a.hop = hop; a.order = order; a.floor_ = floor;
+    const size_t lds = mc_lds_floats(n_fft) * sizeof(float);
+    (void)hipGetLastError();
+    // dynamic LDS from 64 KB on: set on every call (the attribute is per device)
+    if (lds >= 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(mcep_kernel),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return swn_launch_status("swn_mcep (LDS size)");
+    hipLaunchKernelGGL(mcep_kernel, dim3((unsigned)tiles), dim3(LM_THREADS), lds, static_cast<hipStream_t>(stream), a, tables_dev,
+                       work_dev);
+    return swn_launch_status("swn_mcep");
 }
 
 // ------------------------------------------------------------------------------------------------------------------ pool

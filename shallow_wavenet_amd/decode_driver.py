@@ -21,7 +21,8 @@ the same stream whatever `--n_gpus` and wherever the length sort puts it.
 
 `--restore_stats` / `--restore_writedir` (not reference flags) also restore every waveform on the device as run.sh stage 6
 does with `noise_shaping.py --inv false` (shallow_wavenet_amd.postfilter; --mcep_dim_start, --mcep_alpha and --mag as that
-script takes them) and write the restored WAVs under --restore_writedir; the unrestored WAVs under --outdir stay as they are.
+script takes them, --stats_string_path as noise_shaping_driver: `/feat_mcep` with `--mcep_dim_start 0` for the mel-cepstra
+computed on the device) and write the restored WAVs under --restore_writedir; the unrestored WAVs under --outdir stay as they are.
 
 Feature files: `<utt>.npy` (T x n_aux float arrays) always; `<utt>.h5` with the dataset named by
 `config.string_path` when h5py is importable (it is not in the build image).
@@ -249,9 +250,10 @@ def make_restorer(args, device):
     """--restore_stats: the device post-filter of run.sh stage 6 (noise_shaping.py --inv false) for this run, else None"""
     if not getattr(args, "restore_stats", None):
         return None
-    from .noise_shaping_driver import mean_mcep_vector
+    from .noise_shaping_driver import STATS_STRING_PATH, mean_mcep_vector
     from .postfilter import NoiseShapingRestorer
-    return NoiseShapingRestorer(mean_mcep_vector(args.restore_stats), args.fs, args.mcep_alpha, mag=args.mag,
+    mean = mean_mcep_vector(args.restore_stats, getattr(args, "stats_string_path", STATS_STRING_PATH))
+    return NoiseShapingRestorer(mean, args.fs, args.mcep_alpha, mag=args.mag,
                                 mcep_dim_start=args.mcep_dim_start, inv=False,
                                 capacity=max(1, args.batch_size, getattr(args, "pool_slots", 0)), device=device)
 
@@ -333,12 +335,15 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--pool_slots", default=0, type=int,
                    help="not a reference flag: > 0 decodes the utterances through a decode pool of this many slots, each "
                         "over its own features and steps (needs device-drawn noise; the WAVs are those of --batch_size 1)")
-    from .noise_shaping_driver import MAG, MCEP_ALPHA, MCEP_DIM_START
+    from .noise_shaping_driver import MAG, MCEP_ALPHA, MCEP_DIM_START, STATS_STRING_PATH
     p.add_argument("--restore_stats", default=None, type=str,
                    help="not a reference flag: statistics file of the noise shaping (as noise_shaping.py --stats); with "
                         "--restore_writedir, every waveform is also restored on the device (run.sh stage 6, --inv false)")
     p.add_argument("--restore_writedir", default=None, type=str,
                    help="not a reference flag: directory of the restored WAVs (needs --restore_stats)")
+    p.add_argument("--stats_string_path", default=STATS_STRING_PATH, type=str,
+                   help="not a reference flag: the feature whose mean holds the mel-cepstrum (restoration; /feat_mcep with "
+                        "--mcep_dim_start 0 for the mel-cepstra of feature_extract_driver --mcep_dim)")
     p.add_argument("--mcep_dim_start", default=MCEP_DIM_START, type=int,
                    help="index of c(0) in the statistics vector (restoration; as noise_shaping.py)")
     p.add_argument("--mcep_alpha", default=MCEP_ALPHA, type=float,

@@ -1,14 +1,22 @@
-"""Stage 1 of run.sh for the log-mel feature type: every waveform of a directory or list is read, optionally high-pass filtered
-(`dsp.low_cut_filter`, the filtered wav written under `--wavdir`), turned into log-mel features on the device in batches
+"""Stage 1 of run.sh for the feature types computed on the device: every waveform of a directory or list is read, optionally
+high-pass filtered (`dsp.low_cut_filter`, the filtered wav written under `--wavdir`), turned into log-mel features in batches
 (`melspec.LogMelExtractor`, csrc/swn_melspec.hip; the definition is in melspec.py) and written as dataset `--string_path` of
 `<hdf5dir>/<name>.h5` - or `<name>.npz`, the side format of featio.py, where h5py is absent.  The flag names are those of the
 reference's stage-1 command that make sense here; `--feature_type world` is the WORLD / SPTK analysis, which needs pyworld and
 pysptk (dsp.extract_features raises the ImportError that says so).
 
+With `--mcep_dim M` (> 0) each batch also goes through `melspec.MelCepstrumExtractor` (order M, `--mcep_alpha`, `--mcep_floor`)
+and the mel-cepstra of the same frames are written as a second dataset `--mcep_string_path` (default `/feat_mcep`, M + 1
+columns, as the reference's mcep_dim counts) of the same file; `--feature_type mcep` writes them as the conditioning dataset
+instead (`--string_path` when it is given, else `--mcep_string_path`).  It is the mel-cepstrum of the short-time spectrum, not
+of WORLD's envelope, and parity with pysptk is not pinned (melspec.py).
+
 Frames: F = 1 + len // hop with hop = round(fs * shiftms / 1000) unless `--hop` is given - not WORLD's count when 5 ms is not an
 integer number of samples; the training drivers' validate_length trims features and waveform to each other.  The statistics
-of these features (`calc_stats --string_path /feat_logmel`) initialise scale_in as usual; the noise-shaping stages need
-mel-cepstrum statistics and do not apply to this feature type."""
+of these features (`calc_stats --string_path /feat_logmel`) initialise scale_in as usual.  The noise-shaping stages take the
+corpus-mean mel-cepstrum from the second dataset: `calc_stats --string_path /feat_mcep`, then `noise_shaping.py --stats ...
+--stats_string_path /feat_mcep --mcep_dim_start 0` (stages 3 / 6 / 9) and `decode_driver --restore_stats ...
+--stats_string_path /feat_mcep --mcep_dim_start 0` (stage 6 on the device); INTEGRATION.md has the recipe."""
 from __future__ import annotations
 
 import argparse
@@ -24,7 +32,8 @@ from . import dsp, featio
 from .decode_driver import write_wav_pcm16
 from .noise_shaping_driver import list_waveforms, read_wav_fs
 
-FS, SHIFTMS, FFTL, HIGHPASS_CUTOFF = 22050, 5.0, 1024, 70      # the reference's stage-1 defaults
+FS, SHIFTMS, FFTL, HIGHPASS_CUTOFF, MCEP_ALPHA = 22050, 5.0, 1024, 70, 0.455      # the reference's stage-1 defaults
+STRING_PATH = "/feat_logmel"
 BATCH = 16                                                     # utterances per device call
 MAX_JOBS = 16                                                  # worker processes that open the device
 
@@ -41,13 +50,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--highpass_cutoff", default=HIGHPASS_CUTOFF, type=int, help="cut-off of the high-pass filter, 0: none")
     p.add_argument("--n_jobs", default=1, type=int, help=f"number of worker processes (at most {MAX_JOBS})")
     p.add_argument("--verbose", default=1, type=int, help="log level")
-    p.add_argument("--feature_type", default="logmel", choices=("logmel", "world"), help="not a reference flag")
+    p.add_argument("--feature_type", default="logmel", choices=("logmel", "mcep", "world"), help="not a reference flag")
     p.add_argument("--n_mels", default=80, type=int, help="mel filters (logmel; not a reference flag)")
     p.add_argument("--fmin", default=0.0, type=float, help="lowest filter edge in Hz (logmel; not a reference flag)")
     p.add_argument("--fmax", default=None, type=float, help="highest filter edge in Hz, default fs / 2 (logmel; not a reference flag)")
     p.add_argument("--hop", default=None, type=int, help="hop in samples, default round(fs * shiftms / 1000) (logmel; not a reference flag)")
     p.add_argument("--floor", default=1e-5, type=float, help="floor of the mel amplitude under the log (logmel; not a reference flag)")
-    p.add_argument("--string_path", default="/feat_logmel", help="dataset name in the feature files (not a reference flag)")
+    p.add_argument("--string_path", default=STRING_PATH, help="dataset name in the feature files (not a reference flag)")
+    p.add_argument("--mcep_dim", default=0, type=int,
+                   help="order of the mel-cepstrum, 0: none; the dataset has mcep_dim + 1 columns (as the reference counts)")
+    p.add_argument("--mcep_alpha", default=MCEP_ALPHA, type=float, help="all-pass constant of the mel-cepstrum")
+    p.add_argument("--mcep_floor", default=1e-5, type=float, help="floor of the amplitude under the log (mel-cepstrum; not a reference flag)")
+    p.add_argument("--mcep_string_path", default="/feat_mcep", help="dataset name of the mel-cepstra (not a reference flag)")
     return p
 
 
@@ -87,8 +101,21 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
             feats = dsp.extract_features(load_waveform(name, args), args.fs, shiftms=args.shiftms, fftl=args.fftl)
             featio.write_dataset(feature_path(args.hdf5dir, name), args.string_path, feats)
         return 0
-    from .melspec import LogMelExtractor
-    ext = LogMelExtractor(args.fs, args.fftl, hop_of(args), args.n_mels, args.fmin, args.fmax, args.floor, device)
+    from .melspec import LogMelExtractor, MelCepstrumExtractor
+    as_cond = args.feature_type == "mcep"
+    if as_cond and args.mcep_dim <= 0:
+        logging.error("--feature_type mcep needs --mcep_dim > 0")
+        return 2
+    # (extractor, dataset) of every feature the files receive; all share the frames F = 1 + len // hop
+    jobs = []
+    if not as_cond:
+        jobs.append((LogMelExtractor(args.fs, args.fftl, hop_of(args), args.n_mels, args.fmin, args.fmax, args.floor, device),
+                     args.string_path))
+    if args.mcep_dim > 0:
+        dataset = args.string_path if as_cond and args.string_path != STRING_PATH else args.mcep_string_path
+        jobs.append((MelCepstrumExtractor(args.fs, args.fftl, hop_of(args), args.mcep_dim, args.mcep_alpha, args.mcep_floor,
+                                          device), dataset))
+    ext = jobs[0][0]
     rc = 0
     for i in range(0, len(files), BATCH):
         names: List[str] = []
@@ -108,11 +135,12 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
             waves.append(x.astype(np.float32))
         if not names:
             continue
-        feats = ext(waves).cpu().numpy()
-        for name, x, f in zip(names, waves, feats):
-            out = feature_path(args.hdf5dir, name)
-            featio.write_dataset(out, args.string_path, f[:ext.frame_count(x.shape[0])])
-            logging.info("%s -> %s %s", name, out, (ext.frame_count(x.shape[0]), args.n_mels))
+        for extractor, dataset in jobs:
+            feats = extractor(waves).cpu().numpy()
+            for name, x, f in zip(names, waves, feats):
+                out = feature_path(args.hdf5dir, name)
+                featio.write_dataset(out, dataset, f[:ext.frame_count(x.shape[0])])
+                logging.info("%s -> %s %s %s", name, out, dataset, (ext.frame_count(x.shape[0]), f.shape[1]))
     return rc
 
 

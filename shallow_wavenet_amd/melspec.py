@@ -7,6 +7,10 @@ fully pinned feature type next to the WORLD / SPTK features of run.sh stage 1 (w
     new = stream.push(chunk); ...; last = stream.finish()
     mels = LogMelPool(ext, capacity=64, max_chunk=4096)        # ... for many signals at once, one call per tick
     m = mels.open(); new = mels.push_many({m: chunk, ...}, finish=[...])       # {session: (1, n_mels, k)}: what the decode pools take
+    mc = MelCepstrumExtractor(fs=22050, n_fft=1024, hop=110, order=49, alpha=0.455, device="cuda:0")(wavs, lengths)
+                                               # (R, F_max, order + 1): the mel-cepstrum of the same short-time spectra
+                                               # (`torch.ops.swn.mcep`), for the statistics the noise-shaping stages need;
+                                               # its definition is in the class's docstring
 
 Definition (the contract; include/swn_hip.h and csrc/swn_melspec.hip restate it).  Parameters: `fs` sample rate; `n_fft` a
 multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT]; `hop` in 1 .. n_fft, which need not divide n_fft (the 22.05 kHz nets use 110,
@@ -96,6 +100,33 @@ def tables(fs: float, n_fft: int, n_mels: int, fmin: float = 0.0, fmax: Optional
     return table, bank
 
 
+def _padded_batch(ext, wavs, lengths: Optional[Sequence[int]]) -> Tuple[torch.Tensor, List[int]]:
+    """the waveforms of a call as one padded fp32 (R, S) batch on the extractor's device, and the rows' lengths"""
+    if torch.is_tensor(wavs) or isinstance(wavs, np.ndarray):
+        batch = torch.as_tensor(wavs)
+        if batch.dim() == 1:
+            batch = batch[None]
+        if batch.dim() != 2:
+            raise ValueError(f"wavs must be (R, S) or a list of 1-D signals, got shape {tuple(batch.shape)}")
+        lens = [batch.shape[1]] * batch.shape[0] if lengths is None else [int(n) for n in lengths]
+        batch = batch.to(ext.device, torch.float32).contiguous()
+    else:
+        rows = [torch.as_tensor(w).reshape(-1) for w in wavs]
+        if lengths is not None:
+            raise ValueError("a list of signals carries its own lengths")
+        lens = [int(r.numel()) for r in rows]
+        batch = torch.zeros((len(rows), max(lens + [1])), dtype=torch.float32, device=ext.device)
+        for i, r in enumerate(rows):
+            batch[i, :lens[i]] = r.to(ext.device, torch.float32)
+    if len(lens) != batch.shape[0] or batch.shape[0] < 1:
+        raise ValueError(f"{batch.shape[0]} rows, {len(lens)} lengths")
+    for n in lens:
+        ext._check_len(n)
+        if n > batch.shape[1]:
+            raise ValueError(f"length {n} exceeds the batch's {batch.shape[1]} columns")
+    return batch, lens
+
+
 class LogMelExtractor:
     """holds the tables on `device`; a call computes the features of a batch of waveforms."""
 
@@ -124,28 +155,7 @@ class LogMelExtractor:
     def __call__(self, wavs, lengths: Optional[Sequence[int]] = None, linear: bool = False) -> torch.Tensor:
         """wavs: a padded (R, S) batch with `lengths` (default: S for every row), one 1-D signal, or a list of R 1-D signals
         of their own lengths -> (R, F_max, n_mels), row r holding frame_count(lengths[r]) frames and zeros after them."""
-        if torch.is_tensor(wavs) or isinstance(wavs, np.ndarray):
-            batch = torch.as_tensor(wavs)
-            if batch.dim() == 1:
-                batch = batch[None]
-            if batch.dim() != 2:
-                raise ValueError(f"wavs must be (R, S) or a list of 1-D signals, got shape {tuple(batch.shape)}")
-            lens = [batch.shape[1]] * batch.shape[0] if lengths is None else [int(n) for n in lengths]
-            batch = batch.to(self.device, torch.float32).contiguous()
-        else:
-            rows = [torch.as_tensor(w).reshape(-1) for w in wavs]
-            if lengths is not None:
-                raise ValueError("a list of signals carries its own lengths")
-            lens = [int(r.numel()) for r in rows]
-            batch = torch.zeros((len(rows), max(lens + [1])), dtype=torch.float32, device=self.device)
-            for i, r in enumerate(rows):
-                batch[i, :lens[i]] = r.to(self.device, torch.float32)
-        if len(lens) != batch.shape[0] or batch.shape[0] < 1:
-            raise ValueError(f"{batch.shape[0]} rows, {len(lens)} lengths")
-        for n in lens:
-            self._check_len(n)
-            if n > batch.shape[1]:
-                raise ValueError(f"length {n} exceeds the batch's {batch.shape[1]} columns")
+        batch, lens = _padded_batch(self, wavs, lengths)
         R = len(lens)
         return self._op(batch, self._table, self.bank, [0] * R, lens, lens, [0] * R, [self.frame_count(n) for n in lens],
                         self.n_fft, self.hop, self.floor, bool(linear))
@@ -161,6 +171,120 @@ class LogMelExtractor:
         lst = lambda v: [int(v)] * buf.shape[0] if isinstance(v, (int, np.integer)) else [int(x) for x in v]
         out = self._op(buf, self._table, self.bank, lst(t0), lst(n_avail), lst(length), lst(f0), lst(f1), self.n_fft, self.hop,
                        self.floor, bool(linear))
+        return out[0] if one else out
+
+
+# ---- mel-cepstrum --------------------------------------------------------------------------------------------------------
+def _check_order(n_fft: int, order: int, alpha: float) -> None:
+    if not 0 <= order <= min(_lib.MCEP_MAX_ORDER, n_fft // 2):
+        raise ValueError(f"order {order} outside [0, min({_lib.MCEP_MAX_ORDER}, n_fft / 2 = {n_fft // 2})]")
+    if not abs(float(alpha)) < 1.0:
+        raise ValueError(f"|alpha| must be < 1, not {alpha!r}")
+
+
+def mcep_matrix(n_fft: int, order: int, alpha: float) -> np.ndarray:
+    """G (order + 1, n_fft // 2 + 1) in float64 with mc = G L: steps 2 - 4 of the definition as one matrix, G = T C.
+    C (bins, bins) takes L to the one-sided cepstrum: irfft of a real even spectrum is a cosine sum,
+    c[k] = e_k / n_fft * sum_b e_b L[b] cos(2 pi k b / n_fft) with e = 1 at 0 and n_fft / 2 and 2 between.
+    T (order + 1, bins) is the frequency transform: sum_m mc(m) w^m = sum_k c(k) ((w + alpha) / (1 + alpha w))^k, so column k
+    of T is the power series of the k-th power of the all-pass, truncated at w^order, each column from the one before:
+    times (w + alpha), then divided by (1 + alpha w)."""
+    n_fft, order = int(n_fft), int(order)
+    check_size(n_fft)
+    _check_order(n_fft, order, alpha)
+    bins, a = n_fft // 2 + 1, float(alpha)
+    e = np.full(bins, 2.0)
+    e[0] = e[-1] = 1.0
+    kb = (np.arange(bins)[:, None] * np.arange(bins)[None, :]) % n_fft         # the argument reduced exactly
+    C = e[:, None] * e[None, :] * np.cos(2.0 * np.pi * kb.astype(np.float64) / n_fft) / n_fft
+    T = np.zeros((order + 1, bins), dtype=np.float64)
+    p = np.zeros(order + 1, dtype=np.float64)
+    p[0] = 1.0                                                                  # the 0-th power
+    T[:, 0] = p
+    for k in range(1, bins):
+        q = a * p
+        q[1:] += p[:-1]                                                         # times (w + alpha)
+        r = np.empty_like(q)
+        r[0] = q[0]
+        for m in range(1, order + 1):
+            r[m] = q[m] - a * r[m - 1]                                          # divided by (1 + alpha w)
+        T[:, k] = p = r
+    return T @ C
+
+
+def mcep_tables(n_fft: int, order: int, alpha: float) -> np.ndarray:
+    """the table swn_mcep takes: cos(2 pi m / n_fft), the periodic Hann window, then G row by row as fp32 roundings of
+    mcep_matrix, every row zero-padded to the next multiple of 4 columns"""
+    G = mcep_matrix(n_fft, order, alpha)
+    bins = n_fft // 2 + 1
+    kp = (bins + 3) & ~3
+    table = np.zeros(2 * n_fft + (order + 1) * kp, dtype=np.float32)
+    table[:2 * n_fft] = size_tables(n_fft)
+    table[2 * n_fft:].reshape(order + 1, kp)[:, :bins] = G.astype(np.float32)
+    return table
+
+
+class MelCepstrumExtractor:
+    """Mel-cepstra of the short-time spectra the log-mel features are computed from, on the device (`torch.ops.swn.mcep`,
+    swn_mcep): for corpus statistics - the mean over a corpus is what the noise-shaping stages and `post_filter=` build their
+    MLSA filter from - and as a conditioning feature type.
+
+        ext = MelCepstrumExtractor(fs=22050, n_fft=1024, hop=110, order=49, alpha=0.455, device="cuda:0")
+        mc = ext(wavs, lengths)                # (R, F_max, order + 1), time-major; zero past a row's frames
+
+    Definition (the contract; include/swn_hip.h and csrc/swn_melspec.hip restate it).  Frames (F = 1 + len // hop), reflect
+    padding, periodic Hann window and amplitude A[f][b] = |DFT|, b = 0 .. n_fft / 2, are exactly those of the log-mel features
+    (the module docstring).  Then, with 0 <= order <= min(63, n_fft / 2), |alpha| < 1 and floor > 0 (default 1e-5):
+      1. L[f][b] = ln(max(A[f][b], floor)), evaluated in double and rounded once to fp32, as the log-mel output is.
+      2. The real cepstrum v = irfft(L) of length n_fft.
+      3. The one-sided cepstrum c[0] = v[0], c[k] = 2 v[k] for 0 < k < n_fft / 2, c[n_fft / 2] = v[n_fft / 2].  With this
+         convention |exp(sum_k c(k) z^-k)| = A: the one `dsp.py` and the MLSA filter use.
+      4. The frequency transform with all-pass constant alpha to order M (SPTK `freqt`): mc[f][0 .. M].
+      5. Steps 2 - 4 are linear: mc[f] = G L[f] with G = mcep_matrix(n_fft, M, alpha) of shape (M + 1, n_fft / 2 + 1),
+         evaluated in float64 on the host and stored as fp32, its columns zero-padded to a multiple of 4.
+      6. Output fp32, time-major out[frame][coefficient].  Each coefficient is one chain over the bins in ascending order (the
+         k order of the matrix instruction), so a frame's values do not depend on the tile, the row of the tile, the entry,
+         the batch, the frame range or the window they are computed from: any partition of the frames gives the same bits.
+    On the first n_fft / 2 + 1 cepstral coefficients this is what `pysptk.sp2mc(A**2, M, alpha)` computes; parity with pysptk
+    is NOT pinned (the library is absent), as for the MLSA filter.  It is the cepstrum of the short-time spectrum, not of
+    WORLD's cheaptrick envelope: pitch harmonics are in it.  How audio shaped with its mean sounds is not measured here.
+    There is no torch fall-back: without the library the call raises."""
+
+    def __init__(self, fs: float, n_fft: int, hop: int, order: int, alpha: float, floor: float = 1e-5, device="cuda") -> None:
+        self.fs, self.n_fft, self.hop, self.order = fs, int(n_fft), int(hop), int(order)
+        self.alpha, self.floor = float(alpha), float(floor)
+        check_size(self.n_fft)
+        if not 1 <= self.hop <= self.n_fft:
+            raise ValueError(f"hop {hop} outside [1, n_fft = {n_fft}]")
+        if not self.floor > 0.0:
+            raise ValueError(f"floor {floor} must be > 0")
+        table = mcep_tables(self.n_fft, self.order, self.alpha)
+        self.device = torch.device(device)
+        self._table = torch.from_numpy(table).to(self.device)
+        self._op = ops.mcep_impl
+
+    def frame_count(self, length: int) -> int:
+        return frame_count(length, self.hop)
+
+    _check_len = LogMelExtractor._check_len
+
+    def __call__(self, wavs, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """wavs as LogMelExtractor takes them -> (R, F_max, order + 1), row r holding frame_count(lengths[r]) frames and
+        zeros after them."""
+        batch, lens = _padded_batch(self, wavs, lengths)
+        R = len(lens)
+        return self._op(batch, self._table, [0] * R, lens, lens, [0] * R, [self.frame_count(n) for n in lens], self.n_fft,
+                        self.hop, self.order, self.floor)
+
+    def frames(self, wav: torch.Tensor, t0: Union[int, Sequence[int]], n_avail: Union[int, Sequence[int]],
+               length: Union[int, Sequence[int]], f0: Union[int, Sequence[int]], f1: Union[int, Sequence[int]]) -> torch.Tensor:
+        """frames [f0, f1) from a partial buffer, as LogMelExtractor.frames -> (f1 - f0, order + 1) or
+        (R, max(f1 - f0), order + 1)."""
+        one = wav.dim() == 1
+        buf = (wav[None] if one else wav).to(self.device, torch.float32).contiguous()
+        lst = lambda v: [int(v)] * buf.shape[0] if isinstance(v, (int, np.integer)) else [int(x) for x in v]
+        out = self._op(buf, self._table, lst(t0), lst(n_avail), lst(length), lst(f0), lst(f1), self.n_fft, self.hop, self.order,
+                       self.floor)
         return out[0] if one else out
 
 

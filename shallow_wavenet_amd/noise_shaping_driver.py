@@ -2,7 +2,11 @@
 filtered with the time-invariant MLSA filter built from the corpus-mean mel-cepstrum (`--inv true`: coefficients negated - how
 run.sh:529-543 applies the shaping; `--inv false`: how run.sh:725-740 restores a decoded waveform) and written as 16-bit PCM under
 `--writedir`.  Arithmetic: shallow_wavenet_amd/dsp.py (csrc/swn_dsp.c); the
-statistics file is read through featio (HDF5 when h5py is present, the .npz side format otherwise)."""
+statistics file is read through featio (HDF5 when h5py is present, the .npz side format otherwise).
+
+`--stats_string_path` (not a reference flag) names the feature whose statistics hold the mel-cepstrum: the default `/feat_org_lf0`
+is the reference's vector [uv, log f0, codeap.., mcep..] with c(0) at `--mcep_dim_start` 5; with the mel-cepstra that
+`feature_extract_driver --mcep_dim` writes on the device it is `/feat_mcep` and `--mcep_dim_start 0`."""
 from __future__ import annotations
 
 import argparse
@@ -19,6 +23,7 @@ from . import dsp, featio
 from .decode_driver import write_wav_pcm16
 
 FS, SHIFTMS, FFTL, MCEP_DIM_START, MCEP_ALPHA, MAG = 24000, 5.0, 1024, 5, 0.466, 0.5      # the reference's defaults
+STATS_STRING_PATH = "/feat_org_lf0"
 
 
 def _strtobool(v: str) -> bool:
@@ -44,6 +49,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--verbose", default=1, type=int, help="log level")
     p.add_argument("--n_jobs", default=1, type=int, help="number of worker processes")
     p.add_argument("--inv", default=False, type=_strtobool, help="inverse filtering")
+    p.add_argument("--stats_string_path", default=STATS_STRING_PATH,
+                   help="not a reference flag: the feature whose mean holds the mel-cepstrum (/feat_mcep with --mcep_dim_start 0)")
     return p
 
 
@@ -66,9 +73,10 @@ def list_waveforms(spec: str):
         return [ln.strip() for ln in f if ln.strip()]
 
 
-def mean_mcep_vector(stats: str) -> np.ndarray:
-    """/mean_org_lf0 of the statistics file (noise_shaping.py:166) through the lookup the training scripts use"""
-    mean, _ = featio.read_stats(stats, "/feat_org_lf0")
+def mean_mcep_vector(stats: str, string_path: str = STATS_STRING_PATH) -> np.ndarray:
+    """the mean of `string_path` in the statistics file - by default /mean_org_lf0 (noise_shaping.py:166) - through the lookup the
+    training scripts use"""
+    mean, _ = featio.read_stats(stats, string_path)
     return np.asarray(mean, dtype=np.float64)
 
 
@@ -97,7 +105,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         return 2
     files = list_waveforms(args.waveforms)
     os.makedirs(args.writedir, exist_ok=True)
-    mean = mean_mcep_vector(args.stats)
+    mean = mean_mcep_vector(args.stats, args.stats_string_path)
     if args.n_jobs <= 1 or len(files) <= 1:
         return shape_files(files, args, mean)
     ctx = mp.get_context("spawn")

@@ -44,6 +44,7 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.logmel(wav, tables, bank, t0s, n_avails, lens, f0s, f1s, n_fft, hop, floor, linear) -> features
     torch.ops.swn.logmel_pool(win, staged, tables, bank, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s, n_fft, hop,
                               floor, linear) -> features of all sessions, channel-major (updates win)
+    torch.ops.swn.mcep(wav, tables, t0s, n_avails, lens, f0s, f1s, n_fft, hop, order, floor) -> mel-cepstra
     torch.ops.swn.laplace_loss(raw, ctx?, target, eps, desc, skip) -> (nll, err, samples, targets, stats)
     torch.ops.swn.laplace_loss_backward(raw, ctx?, target, eps, g_nll, g_samples?, desc, skip) -> grad_raw
 """
@@ -1418,6 +1419,64 @@ def _(wav, tables, bank, t0s, n_avails, lens, f0s, f1s, n_fft, hop, floor, linea
     return wav.new_empty((wav.shape[0], fmax, len(bank)), dtype=torch.float32)
 
 
+def _mcep_check(n_fft: int, hop: int, order: int, floor: float) -> None:
+    """the size rules of swn_mcep as messages (the library itself answers SWN_E_BADARG)."""
+    if n_fft % 32 != 0 or not 32 <= n_fft <= _lib.SPECTRAL_MAX_FFT:
+        raise RuntimeError(f"mcep: n_fft {n_fft} is not a multiple of 32 in [32, {_lib.SPECTRAL_MAX_FFT}]")
+    if not 1 <= hop <= n_fft:
+        raise RuntimeError(f"mcep: hop {hop} outside [1, n_fft = {n_fft}]")
+    if not 0 <= order <= min(_lib.MCEP_MAX_ORDER, n_fft // 2):
+        raise RuntimeError(f"mcep: order {order} outside [0, min({_lib.MCEP_MAX_ORDER}, n_fft / 2 = {n_fft // 2})]")
+    if not floor > 0.0:
+        raise RuntimeError(f"mcep: floor {floor} must be > 0")
+
+
+def mcep_impl(wav: torch.Tensor, tables: torch.Tensor, t0s: List[int], n_avails: List[int], lens: List[int], f0s: List[int],
+              f1s: List[int], n_fft: int, hop: int, order: int, floor: float) -> torch.Tensor:
+    """wav (R, S), t0s, n_avails, lens, f0s, f1s: as logmel takes them -> (R, max(f1 - f0), order + 1) mel-cepstra of the frames
+    [f0s[r], f1s[r]) of each row, zero past a row's own range (swn_mcep; the definition is in melspec.py).  tables:
+    melspec.mcep_tables()."""
+    Lb = _lib.lib()
+    _need_cuda(wav, "the waveforms")
+    dev = wav.device
+    _mcep_check(n_fft, hop, order, floor)
+    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
+        raise RuntimeError(f"mcep needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
+    R, S = wav.shape
+    if not (len(t0s) == len(n_avails) == len(lens) == len(f0s) == len(f1s) == R):
+        raise RuntimeError("mcep: t0s, n_avails, lens, f0s and f1s must have one entry per row")
+    if any(not 0 <= na <= S for na in n_avails):
+        raise RuntimeError(f"mcep: a row has more samples available than the buffer's {S} columns")
+    need = Lb.swn_mcep_table_floats(n_fft, order)
+    if tables.device != dev or tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != need:
+        raise RuntimeError(f"mcep: tables must be {need} contiguous fp32 values on the device of the waveforms")
+    fmax, nc = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0]), order + 1
+    out = torch.zeros((R, fmax, nc), dtype=torch.float32, device=dev)
+    esz, osz = wav.element_size() * S, out.element_size() * fmax * nc
+    for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
+        r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
+        table = (_lib.LogMelEntry * (r1 - r0))(*[
+            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
+                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
+            for r in range(r0, r1)])
+        nb = Lb.swn_mcep_work_bytes(n_fft, hop, table, r1 - r0)
+        work = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=dev)
+        with _on(dev):
+            _lib.check(Lb.swn_mcep(n_fft, hop, order, float(floor), _ptr(tables), table, r1 - r0, _ptr(work), _stream(dev)),
+                       "mcep")
+    return out
+
+
+mcep = custom_op("swn::mcep", mutates_args=())(mcep_impl)
+
+
+@mcep.register_fake
+def _(wav, tables, t0s, n_avails, lens, f0s, f1s, n_fft, hop, order, floor):
+    _mcep_check(n_fft, hop, order, floor)
+    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
+    return wav.new_empty((wav.shape[0], fmax, order + 1), dtype=torch.float32)
+
+
 def logmel_pool_impl(win: torch.Tensor, staged: Optional[torch.Tensor], tables: torch.Tensor, bank: List[int], slots: List[int],
                      t0s: List[int], n_helds: List[int], n_drops: List[int], n_news: List[int], lens: List[int], f0s: List[int],
                      f1s: List[int], n_fft: int, hop: int, floor: float, linear: bool) -> torch.Tensor:
@@ -1481,4 +1540,4 @@ OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk"
             "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
-            "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool")
+            "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool", "mcep")
