@@ -751,6 +751,55 @@ int    swn_logmel_pool(int n_fft, int hop, int n_mels, float floor, int linear, 
                        const int32_t* bank_host, float* win_dev, size_t window_floats, const float* new_dev, float* out_dev,
                        const swn_logmel_pool_entry* entries_host, int n_entries, float* work_dev, void* stream);
 
+/* ---- stage-1 low cut on the device (melspec.LowCut; csrc/swn_lowcut.hip, csrc/swn_lowcut.hpp) --------------------------------
+ * The definition (melspec.py restates it).  Taps h[0 .. n_taps - 1] in fp64, 1 <= n_taps <= SWN_LOWCUT_MAX_TAPS; input samples
+ * x in fp32 with x[t] = 0 for t < 0.  Output sample t:
+ *     acc = 0.0;  for q = 0 .. n_taps - 1 ascending: acc = fma(h[q], (double)x[t - q], acc);  y[t] = (float)acc
+ * - the last stage of swn_postfilter_chunk: one fp64 fma chain over the taps in ascending order, rounded once to fp32.  Every
+ * output sample depends only on its absolute index and the signal, not on the chunking, the entry, the batch, the tile or the
+ * call: any partition of a signal into chunks gives the bits of the one-shot call.  The state of a session is its last
+ * n_taps - 1 RAW input samples in fp32 (exact: the inputs are fp32), which is what makes a call parallel over time.
+ *
+ * swn_lowcut_chunk: state_dev holds `capacity` slots of swn_lowcut_state_floats(n_taps) = n_taps - 1 floats, slot s from float
+ * s * (n_taps - 1) on, oldest sample first.  Entry e (HOST table, any number, launched in groups of SWN_LOWCUT_MAX_ENTRIES and
+ * carried in the launch arguments: no host copy, no synchronisation) filters the n samples at in_dev as the next chunk of the
+ * session in `slot` and writes n floats at out_dev; SWN_LOWCUT_RESET starts the slot from zero history, an entry with n == 0 and
+ * no RESET leaves its slot untouched.  Blocks cover (entry, tile of SWN_LOWCUT_TILE outputs).  Every tile of an entry reads the
+ * slot's state, so the filter launch writes no state: a second small launch (one block per entry, stream-ordered after the
+ * first) replaces it, reading it whole before writing where n < n_taps - 1 makes the new state a shift of the old one.
+ * SWN_E_BADARG, found on the host before anything is launched, text in swn_last_error_detail: n_taps out of range, a null
+ * pointer (in_dev / out_dev only where n > 0), capacity < 1, n_entries < 0, a slot outside [0, capacity) or named twice, n < 0,
+ * an unknown flag or a non-zero reserved field, in_dev and out_dev ranges of one entry that overlap.
+ * swn_lowcut_state_floats returns 0 for a refused n_taps (and for n_taps == 1, which has no state).
+ * sizeof(swn_lowcut_entry) == 32. */
+#define SWN_LOWCUT_MAX_TAPS 256
+#define SWN_LOWCUT_MAX_ENTRIES 64
+#define SWN_LOWCUT_TILE 1024            /* output samples per block */
+#define SWN_LOWCUT_RESET 1              /* flags: the slot starts from zero history */
+typedef struct swn_lowcut_entry {
+    const float* in_dev;     /* n raw fp32 samples */
+    float* out_dev;          /* n filtered fp32 samples; must not overlap in_dev's range */
+    int32_t slot;            /* [0, capacity) */
+    int32_t n;               /* >= 0; 0 with SWN_LOWCUT_RESET only clears the slot */
+    int32_t flags;           /* SWN_LOWCUT_RESET or 0 */
+    int32_t reserved;        /* 0 */
+} swn_lowcut_entry;
+size_t swn_lowcut_state_floats(int n_taps);
+int    swn_lowcut_chunk(int n_taps, const double* taps_dev, float* state_dev, int capacity,
+                        const swn_lowcut_entry* entries_host, int n_entries, void* stream);
+
+/* swn_logmel_pool_lowcut: swn_logmel_pool whose new samples are RAW; the window receives the filtered samples.  hist_dev holds
+ * one slot of n_taps - 1 floats per window slot (slot s from float s * (n_taps - 1) on, oldest first): after the call it holds
+ * the last n_taps - 1 raw samples before t0 + n_held + n_new.  An entry with t0 == 0 and n_held == 0 has received nothing yet
+ * and starts from zero history whatever the slot's floats hold; an entry with n_new == 0 leaves them untouched.  The filtering
+ * happens inside the window-update launch (one block per entry, which reads the history it needs before it replaces it), so a
+ * call still makes at most two launches.  A frame has the bits swn_logmel gives it on the filtered signal.  Every rule of
+ * swn_logmel_pool applies; SWN_E_BADARG also for n_taps outside [1, SWN_LOWCUT_MAX_TAPS] and a null taps_dev or hist_dev. */
+int    swn_logmel_pool_lowcut(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev,
+                              const int32_t* bank_host, float* win_dev, size_t window_floats, const float* new_dev, float* out_dev,
+                              const swn_logmel_pool_entry* entries_host, int n_entries, float* work_dev, int n_taps,
+                              const double* taps_dev, float* hist_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,12 @@ class LogMelPoolEntry(ctypes.Structure):
                                        "out_stride", "reserved")]
 
 
+class LowcutEntry(ctypes.Structure):
+    """mirror of `swn_lowcut_entry` (include/swn_hip.h): one session's share of a low-cut call."""
+    _fields_ = [("in_dev", c_void_p), ("out_dev", c_void_p), ("slot", c_int32), ("n", c_int32), ("flags", c_int32),
+                ("reserved", c_int32)]
+
+
 ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
 DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
@@ -93,6 +99,8 @@ POSTFILTER_RESET = 1                           # SWN_POSTFILTER_RESET
 POSTFILTER_MAX_ORDER = 62                      # SWN_POSTFILTER_MAX_ORDER
 POSTFILTER_MAX_TAPS = 256                      # SWN_POSTFILTER_MAX_TAPS
 POSTFILTER_MULAW_ENTRIES = 256                 # SWN_POSTFILTER_MULAW_ENTRIES
+LOWCUT_MAX_TAPS, LOWCUT_TILE = 256, 1024       # SWN_LOWCUT_MAX_TAPS, SWN_LOWCUT_TILE: output samples per block of the kernel
+LOWCUT_MAX_ENTRIES, LOWCUT_RESET = 64, 1       # SWN_LOWCUT_MAX_ENTRIES (entries per launch group), SWN_LOWCUT_RESET
 SPECTRAL_MAX_SIZES, SPECTRAL_MAX_FFT = 32, 2048   # SWN_SPECTRAL_MAX_SIZES, SWN_SPECTRAL_MAX_FFT
 LOGMEL_MAX_MELS, LOGMEL_MAX_ENTRIES = 128, 64     # SWN_LOGMEL_MAX_MELS, SWN_LOGMEL_MAX_ENTRIES
 LOGMEL_POOL_MAX_ENTRIES = 64                   # SWN_LOGMEL_POOL_MAX_ENTRIES (include/swn_hip.h): entries per log-mel pool call
@@ -222,6 +230,11 @@ SIGNATURES = {
     "swn_logmel_pool_work_bytes": (c_size_t, [c_int, c_int, c_int, c_size_t, POINTER(LogMelPoolEntry), c_int]),
     "swn_logmel_pool": (c_int, [c_int, c_int, c_int, c_float, c_int, c_void_p, POINTER(c_int32), c_void_p, c_size_t, c_void_p,
                                 c_void_p, POINTER(LogMelPoolEntry), c_int, c_void_p, c_void_p]),
+    "swn_lowcut_state_floats": (c_size_t, [c_int]),
+    "swn_lowcut_chunk": (c_int, [c_int, c_void_p, c_void_p, c_int, POINTER(LowcutEntry), c_int, c_void_p]),
+    "swn_logmel_pool_lowcut": (c_int, [c_int, c_int, c_int, c_float, c_int, c_void_p, POINTER(c_int32), c_void_p, c_size_t,
+                                       c_void_p, c_void_p, POINTER(LogMelPoolEntry), c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_void_p]),
 }
 
 

@@ -33,7 +33,10 @@
 // [n_drop, n_held) to the window's front (ascending blocks of 256 floats, each read whole before it is written: a block's
 // destination lies below every later block's source) and appends the entry's new samples from the staged buffer.  Then
 // logmel_kernel<true> computes the frames from the updated windows with the arithmetic of swn_logmel and writes them
-// channel-major, out[m * out_stride + (f - f0)]: the layout the pool front end stages.
+// channel-major, out[m * out_stride + (f - f0)]: the layout the pool front end stages.  swn_logmel_pool_lowcut runs
+// logmel_pool_update_kernel<true>: the staged samples are raw and reach the window through the stage-1 low cut
+// (swn_lowcut.hpp, the bits of swn_lowcut_chunk), whose state - the slot's last n_taps - 1 raw samples - lives in hist_dev and
+// is replaced by the same block.
 //
 // Mel-cepstrum (swn_mcep, melspec.MelCepstrumExtractor; restated in include/swn_hip.h and melspec.py).  Frames, padding,
 // window and amplitude A[f][b] are those above.  Then
@@ -51,6 +54,7 @@
 // The table of swn_mcep: cos, window, then G padded.  mcep_kernel below says how the block works.
 #include <hip/hip_runtime.h>
 #include "swn_geom.hpp"
+#include "swn_lowcut.hpp"
 #include "swn_mma.hpp"
 #include <cstdio>
 #include <algorithm>
@@ -93,6 +97,15 @@ struct LpArgs {
 };
 static_assert(sizeof(LpArgs) + 2 * sizeof(void*) <= 4096, "the by-value kernel arguments must stay inside 4 KB");
 constexpr int LP_MAX_WINDOW = 1 << 24;      // floats per slot
+static_assert(LM_THREADS == LC_THREADS, "the window update runs the low cut's tiles with its own block");
+// swn_logmel_pool_lowcut only: the taps, the slots' histories of raw samples, and which entries have received nothing yet
+struct LpFir {
+    const double* taps;
+    float* hist;
+    int n_taps;
+    unsigned long long fresh;               // bit e: entry e starts from zero history
+};
+static_assert(SWN_LOGMEL_POOL_MAX_ENTRIES <= 64, "one bit of LpFir::fresh per entry");
 static_assert(SWN_LOGMEL_POOL_MAX_ENTRIES <= SWN_LOGMEL_MAX_ENTRIES, "a pool call's entries are one frame launch");
 
 __host__ __device__ inline int lm_pitch(int n) { return n + 2; }
@@ -371,9 +384,32 @@ __global__ __launch_bounds__(LM_THREADS) void mcep_kernel(const McArgs a, const 
     }
 }
 
-// one block per entry: window[0 .. n_held - n_drop) <- window[n_drop .. n_held), then the n_new staged samples after them
+// swn_logmel_pool_lowcut: the entry's n_new RAW samples through the low cut (swn_lowcut.hpp: the bits of swn_lowcut_chunk) to
+// dst, tile after tile, and the slot's history of raw samples replaced.  Only the first tile reads the history (LC_TILE
+// exceeds it); every thread has picked up its float of the new history before the barrier behind that tile's load, and
+// writes it after it.
+__device__ __forceinline__ void lp_filter_new(const LpFir& f, int slot, bool fresh, const float* __restrict__ src, int n_new,
+                                              float* __restrict__ dst) {
+    __shared__ LcShared s;
+    const int H = f.n_taps - 1, tid = threadIdx.x;
+    float* slot_hist = f.hist + (size_t)slot * H;
+    const float* hist = fresh ? nullptr : slot_hist;
+    lc_load_taps(s, f.taps, f.n_taps);
+    const float next = tid < H ? lc_next_hist(src, n_new, hist, f.n_taps, tid) : 0.f;
+    for (int base = 0; base < n_new; base += LC_TILE) {             // uniform trip count: every thread meets the barriers
+        lc_load_tile(s, src, n_new, hist, f.n_taps, base);
+        __syncthreads();
+        if (base == 0 && tid < H) slot_hist[tid] = next;
+        lc_fir_tile(s, f.n_taps, n_new - base < LC_TILE ? n_new - base : LC_TILE, dst + base);
+        __syncthreads();                        // the next tile's load overwrites what this tile's chains read
+    }
+}
+
+// one block per entry: window[0 .. n_held - n_drop) <- window[n_drop .. n_held), then the n_new staged samples after them -
+// as they are (LC false: swn_logmel_pool) or through the low cut (LC true: swn_logmel_pool_lowcut)
+template <bool LC>
 __global__ __launch_bounds__(LM_THREADS) void logmel_pool_update_kernel(const LpArgs a, float* __restrict__ win,
-                                                                         const float* __restrict__ staged) {
+                                                                         const float* __restrict__ staged, const LpFir f) {
     const LpMove e = a.e[blockIdx.x];
     float* w = win + (size_t)e.slot * a.window_floats;
     const int keep = e.n_held - e.n_drop, tid = threadIdx.x;
@@ -386,7 +422,11 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_pool_update_kernel(const Lp
         }
         __syncthreads();                        // the new samples may land on floats the last blocks still read
     }
-    for (int i = tid; i < e.n_new; i += LM_THREADS) w[keep + i] = staged[e.new_off + i];
+    if constexpr (LC) {
+        if (e.n_new > 0) lp_filter_new(f, e.slot, (f.fresh >> blockIdx.x) & 1ull, staged + e.new_off, e.n_new, w + keep);
+    } else {
+        for (int i = tid; i < e.n_new; i += LM_THREADS) w[keep + i] = staged[e.new_off + i];
+    }
 }
 
 }  // namespace
@@ -624,13 +664,18 @@ extern "C" size_t swn_logmel_pool_work_bytes(int n_fft, int hop, int n_mels, siz
     return (size_t)tiles * LM_FR * lm_amp_pitch(n_fft) * sizeof(float);
 }
 
-extern "C" int swn_logmel_pool(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev,
-                               const int32_t* bank_host, float* win_dev, size_t window_floats, const float* new_dev,
-                               float* out_dev, const swn_logmel_pool_entry* entries_host, int n_entries, float* work_dev,
-                               void* stream) {
-    LmWho who("swn_logmel_pool");
+namespace {
+
+// swn_logmel_pool (fir null) and swn_logmel_pool_lowcut
+int lp_run(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev, const int32_t* bank_host,
+           float* win_dev, size_t window_floats, const float* new_dev, float* out_dev, const swn_logmel_pool_entry* entries_host,
+           int n_entries, float* work_dev, const LpFir* fir, void* stream) {
     int rc = lm_check_sizes(n_fft, n_mels, floor, linear);
     if (rc != SWN_OK) return rc;
+    if (fir) {
+        if (!lc_taps_ok(fir->n_taps)) return lm_fail("n_taps outside [1, SWN_LOWCUT_MAX_TAPS]");
+        if (!fir->taps || !fir->hist) return lm_fail("null pointer (taps_dev, hist_dev)");
+    }
     swn_logmel_entry rows[SWN_LOGMEL_POOL_MAX_ENTRIES];
     long long tiles = 0;
     rc = lp_check(n_fft, hop, n_mels, window_floats, entries_host, n_entries, rows, &tiles);
@@ -639,6 +684,7 @@ extern "C" int swn_logmel_pool(int n_fft, int hop, int n_mels, float floor, int 
     rc = lm_fill_bank(a, n_fft, n_mels, bank_host);
     if (rc != SWN_OK) return rc;
     LpArgs u;
+    LpFir f = fir ? *fir : LpFir{nullptr, nullptr, 0, 0ull};
     int strides[SWN_LOGMEL_POOL_MAX_ENTRIES];
     bool moves = false, news = false;
     for (int i = 0; i < SWN_LOGMEL_POOL_MAX_ENTRIES; ++i) {
@@ -649,6 +695,7 @@ extern "C" int swn_logmel_pool(int n_fft, int hop, int n_mels, float floor, int 
         if (in) {
             moves = moves || e->n_new > 0 || (e->n_drop > 0 && e->n_held > e->n_drop);
             news = news || e->n_new > 0;
+            if (e->t0 == 0 && e->n_held == 0) f.fresh |= 1ull << i;     // nothing received yet: zero history
         }
     }
     u.window_floats = (int)window_floats;
@@ -660,11 +707,37 @@ extern "C" int swn_logmel_pool(int n_fft, int hop, int n_mels, float floor, int 
     hipStream_t st = static_cast<hipStream_t>(stream);
     (void)hipGetLastError();
     if (moves) {
-        hipLaunchKernelGGL(logmel_pool_update_kernel, dim3((unsigned)n_entries), dim3(LM_THREADS), 0, st, u, win_dev, new_dev);
-        rc = swn_launch_status("swn_logmel_pool (window update)");
+        if (fir)
+            hipLaunchKernelGGL(logmel_pool_update_kernel<true>, dim3((unsigned)n_entries), dim3(LM_THREADS), 0, st, u, win_dev,
+                               new_dev, f);
+        else
+            hipLaunchKernelGGL(logmel_pool_update_kernel<false>, dim3((unsigned)n_entries), dim3(LM_THREADS), 0, st, u, win_dev,
+                               new_dev, f);
+        rc = swn_launch_status(fir ? "swn_logmel_pool_lowcut (window update)" : "swn_logmel_pool (window update)");
         if (rc != SWN_OK) return rc;
     }
     if (tiles == 0) return SWN_OK;                          // no frame in any entry
     return lm_launch<true>(a, n_fft, hop, n_mels, floor, linear, rows, strides, n_entries, tiles, tables_dev, work_dev, st,
-                           "swn_logmel_pool");
+                           fir ? "swn_logmel_pool_lowcut" : "swn_logmel_pool");
+}
+
+}  // namespace
+
+extern "C" int swn_logmel_pool(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev,
+                               const int32_t* bank_host, float* win_dev, size_t window_floats, const float* new_dev,
+                               float* out_dev, const swn_logmel_pool_entry* entries_host, int n_entries, float* work_dev,
+                               void* stream) {
+    LmWho who("swn_logmel_pool");
+    return lp_run(n_fft, hop, n_mels, floor, linear, tables_dev, bank_host, win_dev, window_floats, new_dev, out_dev, entries_host,
+                  n_entries, work_dev, nullptr, stream);
+}
+
+extern "C" int swn_logmel_pool_lowcut(int n_fft, int hop, int n_mels, float floor, int linear, const float* tables_dev,
+                                      const int32_t* bank_host, float* win_dev, size_t window_floats, const float* new_dev,
+                                      float* out_dev, const swn_logmel_pool_entry* entries_host, int n_entries, float* work_dev,
+                                      int n_taps, const double* taps_dev, float* hist_dev, void* stream) {
+    LmWho who("swn_logmel_pool_lowcut");
+    const LpFir fir{taps_dev, hist_dev, n_taps, 0ull};
+    return lp_run(n_fft, hop, n_mels, floor, linear, tables_dev, bank_host, win_dev, window_floats, new_dev, out_dev, entries_host,
+                  n_entries, work_dev, &fir, stream);
 }

@@ -16,7 +16,14 @@ integer number of samples; the training drivers' validate_length trims features 
 of these features (`calc_stats --string_path /feat_logmel`) initialise scale_in as usual.  The noise-shaping stages take the
 corpus-mean mel-cepstrum from the second dataset: `calc_stats --string_path /feat_mcep`, then `noise_shaping.py --stats ...
 --stats_string_path /feat_mcep --mcep_dim_start 0` (stages 3 / 6 / 9) and `decode_driver --restore_stats ...
---stats_string_path /feat_mcep --mcep_dim_start 0` (stage 6 on the device); INTEGRATION.md has the recipe."""
+--stats_string_path /feat_mcep --mcep_dim_start 0` (stage 6 on the device); INTEGRATION.md has the recipe.
+
+`--highpass_on device` moves the high-pass filter to the device (`melspec.LowCut`, csrc/swn_lowcut.hip): a batch of raw
+waveforms is filtered there, the features are taken from that device tensor with no host round trip, and the `--wavdir` files
+are written from it.  These are the bits `LogMelStream(low_cut=)` and `LogMelPool(low_cut=)` give a live session, so features
+taken this way and features taken while serving agree exactly.  The default `host` is `dsp.low_cut_filter` as before; the two
+settings differ by at most the rounding of the device definition (melspec.py): both sum the same products in fp64, in
+different orders, and the device rounds once to fp32, so a sample of a PCM16 file can differ by one step."""
 from __future__ import annotations
 
 import argparse
@@ -48,6 +55,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--shiftms", default=SHIFTMS, type=float, help="frame shift in msec (the hop, unless --hop is given)")
     p.add_argument("--fftl", default=FFTL, type=int, help="FFT length: a multiple of 32")
     p.add_argument("--highpass_cutoff", default=HIGHPASS_CUTOFF, type=int, help="cut-off of the high-pass filter, 0: none")
+    p.add_argument("--highpass_on", default="host", choices=("host", "device"),
+                   help="where the high-pass filter runs: host (dsp.low_cut_filter, scipy in float64) or device (melspec.LowCut: "
+                        "the bits of the live streams and pools).  The two differ by at most the rounding of the device "
+                        "definition - fp64 sums in different orders, rounded once to fp32 - so a PCM16 sample can differ by one "
+                        "step (not a reference flag)")
     p.add_argument("--n_jobs", default=1, type=int, help=f"number of worker processes (at most {MAX_JOBS})")
     p.add_argument("--verbose", default=1, type=int, help="log level")
     p.add_argument("--feature_type", default="logmel", choices=("logmel", "mcep", "world"), help="not a reference flag")
@@ -79,15 +91,21 @@ def feature_path(hdf5dir: str, wav_name: str) -> str:
     return os.path.join(hdf5dir, os.path.splitext(os.path.basename(wav_name))[0] + ext)
 
 
+def on_device(args) -> bool:
+    """the high-pass filter runs on the device (--highpass_on device with a cut-off)"""
+    return getattr(args, "highpass_on", "host") == "device" and args.highpass_cutoff != 0
+
+
 def load_waveform(name: str, args) -> np.ndarray:
-    """the utterance as the features see it: mono float64, high-pass filtered (and written to --wavdir) when the cut-off is not 0.
+    """the utterance as the features see it: mono float64, high-pass filtered (and written to --wavdir) when the cut-off is not 0
+    - or raw when the filter runs on the device (extract_files filters the batch and writes --wavdir from the result).
     ValueError when the file's sampling frequency is not --fs (the mel scale, the hop and the filter would all be wrong)."""
     x, fs = read_wav_fs(name)
     if fs != args.fs:
         raise ValueError(f"{name}: sampling frequency {fs} does not match --fs {args.fs}")
     if x.ndim > 1:
         x = x[:, 0]
-    if args.highpass_cutoff != 0:
+    if args.highpass_cutoff != 0 and not on_device(args):
         x = dsp.low_cut_filter(x, args.fs, cutoff=args.highpass_cutoff)
         if args.wavdir:
             os.makedirs(args.wavdir, exist_ok=True)
@@ -97,11 +115,14 @@ def load_waveform(name: str, args) -> np.ndarray:
 
 def extract_files(files: Sequence[str], args, device="cuda") -> int:
     if args.feature_type == "world":
+        if on_device(args):
+            logging.error("--highpass_on device serves the features computed on the device, not --feature_type world")
+            return 2
         for name in files:
             feats = dsp.extract_features(load_waveform(name, args), args.fs, shiftms=args.shiftms, fftl=args.fftl)
             featio.write_dataset(feature_path(args.hdf5dir, name), args.string_path, feats)
         return 0
-    from .melspec import LogMelExtractor, MelCepstrumExtractor
+    from .melspec import LogMelExtractor, LowCut, MelCepstrumExtractor
     as_cond = args.feature_type == "mcep"
     if as_cond and args.mcep_dim <= 0:
         logging.error("--feature_type mcep needs --mcep_dim > 0")
@@ -116,6 +137,7 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
         jobs.append((MelCepstrumExtractor(args.fs, args.fftl, hop_of(args), args.mcep_dim, args.mcep_alpha, args.mcep_floor,
                                           device), dataset))
     ext = jobs[0][0]
+    cut = LowCut(args.fs, args.highpass_cutoff, device=device) if on_device(args) else None
     rc = 0
     for i in range(0, len(files), BATCH):
         names: List[str] = []
@@ -135,8 +157,17 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
             waves.append(x.astype(np.float32))
         if not names:
             continue
+        batch, lengths = waves, None
+        if cut is not None:
+            # raw samples up, filtered on the device; the features read that tensor, the wav files are written from it
+            lengths = [x.shape[0] for x in waves]
+            batch = cut(waves)
+            if args.wavdir:
+                os.makedirs(args.wavdir, exist_ok=True)
+                for name, n, y in zip(names, lengths, batch.cpu().numpy()):
+                    write_wav_pcm16(os.path.join(args.wavdir, os.path.basename(name)), np.clip(y[:n], -1.0, 1.0), args.fs)
         for extractor, dataset in jobs:
-            feats = extractor(waves).cpu().numpy()
+            feats = extractor(batch, lengths).cpu().numpy()
             for name, x, f in zip(names, waves, feats):
                 out = feature_path(args.hdf5dir, name)
                 featio.write_dataset(out, dataset, f[:ext.frame_count(x.shape[0])])

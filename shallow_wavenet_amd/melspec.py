@@ -11,6 +11,9 @@ fully pinned feature type next to the WORLD / SPTK features of run.sh stage 1 (w
                                                # (R, F_max, order + 1): the mel-cepstrum of the same short-time spectra
                                                # (`torch.ops.swn.mcep`), for the statistics the noise-shaping stages need;
                                                # its definition is in the class's docstring
+    cut = LowCut(fs=22050, cutoff=70.0, device="cuda:0")       # the stage-1 low cut (`torch.ops.swn.lowcut_chunk`): what the
+    y = cut(wavs, lengths)                                     # training features were taken from; LogMelStream(ext, low_cut=cut)
+                                                               # and LogMelPool(..., low_cut=cut) take RAW samples and filter them
 
 Definition (the contract; include/swn_hip.h and csrc/swn_melspec.hip restate it).  Parameters: `fs` sample rate; `n_fft` a
 multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT]; `hop` in 1 .. n_fft, which need not divide n_fft (the 22.05 kHz nets use 110,
@@ -32,10 +35,19 @@ F = 1 + len // hop is NOT WORLD's frame count when 5 ms is not an integer number
 `dsp.world_frame_count` is unchanged); the training drivers' `validate_length` trims features and waveform to each other.
 A frame's values do not depend on the batch, the frame range or the buffer window it is computed from, so the stream's
 concatenated output is bit-identical to the one-shot call.  There is no torch fall-back: without the library the call raises.
+
+The low cut (the contract; include/swn_hip.h states it, csrc/swn_lowcut.hpp is its arithmetic).  Taps h[0 .. n_taps - 1] in fp64,
+1 <= n_taps <= SWN_LOWCUT_MAX_TAPS (256); input samples x in fp32, x[t] = 0 for t < 0.  Output sample t:
+    acc = 0.0;  for q = 0 .. n_taps - 1 ascending: acc = fma(h[q], (double)x[t - q], acc);  y[t] = (float)acc
+Every output sample depends only on its absolute index and the signal - not on the chunking, the entry, the batch, the tile or
+the call - so any partition of a signal into chunks gives the bits of the one-shot call, and a stream's or a pool's frames are
+the extractor's on the one-shot filtered signal.  A session's state is its last n_taps - 1 raw input samples in fp32 (exact: the
+inputs are fp32).  `dsp.low_cut_filter` (scipy's lfilter, float64 out) sums the same products in another order and is not
+rounded to fp32: the two differ by the rounding above, at most one step of a PCM16 file.
 """
 from __future__ import annotations
 
-from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
+from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -288,6 +300,102 @@ class MelCepstrumExtractor:
         return out[0] if one else out
 
 
+# ---- stage-1 low cut -----------------------------------------------------------------------------------------------------
+class LowCut:
+    """the causal FIR high-pass of run.sh stage 1 (`dsp.low_cut_taps(fs, cutoff)`: 255 taps) on the device, with the taps held
+    there as fp64 and `capacity` session slots; the definition is in the module docstring.
+
+        cut = LowCut(22050, cutoff=70.0, capacity=8, device="cuda:0")
+        y = cut(wavs, lengths)                   # one-shot: (rows, n_max) fp32, every row filtered from zero state
+        s = cut.open()                           # a free slot (or open(slot) for a given one); starts from zero history
+        out = cut.run({s: chunk})                # {slot: filtered chunk}; one device call for all slots
+        cut.close(s)
+    """
+
+    def __init__(self, fs: int, cutoff: float = 70.0, capacity: int = 1, device="cuda") -> None:
+        if not isinstance(capacity, int) or capacity < 1:
+            raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
+        if not 0.0 < float(cutoff) < int(fs) // 2:
+            raise ValueError(f"cutoff {cutoff!r} outside (0, fs / 2 = {int(fs) // 2})")
+        from . import dsp
+        self.fs, self.cutoff, self.capacity = int(fs), float(cutoff), capacity
+        self.taps = np.ascontiguousarray(dsp.low_cut_taps(self.fs, self.cutoff), dtype=np.float64)
+        self.n_taps = int(self.taps.size)
+        if not 1 <= self.n_taps <= _lib.LOWCUT_MAX_TAPS:
+            raise ValueError(f"{self.n_taps} taps, the device low cut takes 1 .. {_lib.LOWCUT_MAX_TAPS}")
+        self.device = torch.device(device)
+        self.state_floats = self.n_taps - 1
+        self._taps = torch.from_numpy(self.taps).to(self.device)
+        self._state = torch.zeros(max(1, capacity * self.state_floats), dtype=torch.float32, device=self.device)
+        self._free = list(range(capacity))
+        self._reset = set()                                   # opened slots that have not run yet
+        self._op = ops.lowcut_chunk_impl
+
+    def _check_len(self, length: int) -> None:
+        if length < 0:
+            raise ValueError(f"length {length}")
+
+    # ------------------------------------------------------------------ one shot
+    def __call__(self, wavs, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """wavs as LogMelExtractor takes them (a padded (R, S) batch with `lengths`, one 1-D signal, or a list of 1-D signals)
+        -> (R, max(lengths)) fp32 on the device: every row filtered from zero state, valid up to its length (the floats past
+        it are not written).  One device call; the open sessions' slots are not touched."""
+        batch, lens = _padded_batch(self, wavs, lengths)
+        R = len(lens)
+        state = torch.empty(max(1, R * self.state_floats), dtype=torch.float32, device=self.device)
+        return self._op(self._taps, state, [batch[r, :lens[r]] for r in range(R)], list(range(R)), [True] * R, R)
+
+    # ------------------------------------------------------------------ sessions
+    def open(self, slot: Optional[int] = None) -> int:
+        """claim a slot (the lowest free one when slot is None); its session starts from zero history."""
+        if slot is None:
+            if not self._free:
+                raise RuntimeError(f"the low cut is full: all {self.capacity} slots are open")
+            slot = self._free[0]
+        slot = int(slot)
+        if slot not in self._free:
+            raise RuntimeError(f"slot {slot} is not free (capacity {self.capacity})")
+        self._free.remove(slot)
+        self._reset.add(slot)
+        return slot
+
+    def close(self, slot: int) -> None:
+        """free the slot; a session opened in it later starts from zero history."""
+        slot = int(slot)
+        if slot in self._free or not 0 <= slot < self.capacity:
+            raise RuntimeError(f"slot {slot} is not open")
+        self._reset.discard(slot)
+        self._free.append(slot)
+        self._free.sort()
+
+    def run(self, chunks: Mapping[int, torch.Tensor]) -> Dict[int, torch.Tensor]:
+        """the next chunk (1-D samples, host or device, any length) of each open slot's session, all in one device call ->
+        {slot: filtered fp32 chunk (1-D, views of one dense output)}."""
+        slots = [int(s) for s in chunks]
+        for s in slots:
+            if s in self._free or not 0 <= s < self.capacity:
+                raise RuntimeError(f"slot {s} is not open")
+        if not slots:
+            return {}
+        xs = [torch.as_tensor(chunks[s]) for s in chunks]
+        for x in xs:
+            if x.dim() != 1:
+                raise ValueError(f"samples must be a 1-D tensor, got shape {tuple(x.shape)}")
+        xs = [x.to(self.device, torch.float32) for x in xs]
+        out = self._op(self._taps, self._state, xs, slots, [s in self._reset for s in slots], self.capacity)
+        self._reset.difference_update(slots)
+        return {s: out[e, :x.numel()] for e, (s, x) in enumerate(zip(slots, xs))}
+
+
+def _check_low_cut(low_cut, extractor: "LogMelExtractor") -> None:
+    if not isinstance(low_cut, LowCut):
+        raise ValueError(f"low_cut must be a LowCut or None, not {low_cut!r}")
+    if low_cut.device != extractor.device:
+        raise ValueError(f"the low cut is on {low_cut.device}, the extractor on {extractor.device}")
+    if low_cut.fs != int(extractor.fs):
+        raise ValueError(f"the low cut was built for fs {low_cut.fs}, the extractor for {extractor.fs}")
+
+
 # ---- the streaming rule: the one place LogMelStream and LogMelPool take it from ------------------------------------------
 def frames_ready(n_fft: int, hop: int, n_received: int, final: bool = False) -> int:
     """frames of a signal that can be computed once n_received samples are there.  While it goes on, those whose samples have
@@ -309,10 +417,16 @@ def keep_from(n_fft: int, hop: int, t0: int, n_frames: int) -> int:
 class LogMelStream:
     """one signal's features as its samples arrive: `push` returns the frames that became computable, `finish` the rest
     (those that read the reflected end).  Only the tail of the signal that later frames still read is kept.  The
-    concatenation of everything returned is bit-identical to the extractor's one-shot call on the whole signal."""
+    concatenation of everything returned is bit-identical to the extractor's one-shot call on the whole signal.  With
+    `low_cut` (a LowCut) the pushed samples are RAW and every push filters them first, in a slot of the low cut that the
+    stream opens for itself and frees when it finishes: the frames are the extractor's on low_cut(whole signal)."""
 
-    def __init__(self, extractor: LogMelExtractor, linear: bool = False) -> None:
+    def __init__(self, extractor: LogMelExtractor, linear: bool = False, low_cut: Optional[LowCut] = None) -> None:
         self.ext, self.linear = extractor, bool(linear)
+        self.low_cut, self._cut_slot = low_cut, None
+        if low_cut is not None:
+            _check_low_cut(low_cut, extractor)
+            self._cut_slot = low_cut.open()
         self._buf = torch.zeros(0, dtype=torch.float32, device=extractor.device)
         self.t0 = 0                 # absolute index of _buf[0]
         self.n_received = 0
@@ -344,6 +458,8 @@ class LogMelStream:
         if self.finished:
             raise RuntimeError("the stream is finished")
         s = torch.as_tensor(samples).reshape(-1).to(self.ext.device, torch.float32)
+        if self.low_cut is not None:
+            s = self.low_cut.run({self._cut_slot: s})[self._cut_slot]
         self._buf = torch.cat([self._buf, s])
         self.n_received += int(s.numel())
         return self._range(self.computable(self.n_received), -1)
@@ -354,6 +470,8 @@ class LogMelStream:
             raise RuntimeError("the stream is finished")
         self.ext._check_len(self.n_received)
         self.finished = True
+        if self.low_cut is not None:
+            self.low_cut.close(self._cut_slot)
         return self._range(frames_ready(self.ext.n_fft, self.ext.hop, self.n_received, True), self.n_received)
 
 
@@ -426,9 +544,13 @@ class LogMelPool:
     LogMelStream.push / finish would, bit for bit, with at most two launches and one staging copy per 64 sessions whatever
     their number.  The sessions' tails live in `windows` (capacity, n_fft + max_chunk) on the device: there is no
     per-session cat or slice, and the frames come back channel-major, (1, n_mels, k), as DecodePool.push_many,
-    SteppedDecodePool.push_many and DecodeStream.push take them."""
+    SteppedDecodePool.push_many and DecodeStream.push take them.  With `low_cut` (a LowCut) the chunks are RAW samples: the
+    window update filters them (`torch.ops.swn.logmel_pool_lowcut`, still two launches per call) and every session's frames are
+    the extractor's on low_cut(whole signal).  The pool owns `hist` (capacity, n_taps - 1), each window slot's last raw samples;
+    a session opened in a freed slot starts from zero history.  The LowCut's own slots are not used."""
 
-    def __init__(self, extractor: LogMelExtractor, capacity: int, max_chunk: int, linear: bool = False) -> None:
+    def __init__(self, extractor: LogMelExtractor, capacity: int, max_chunk: int, linear: bool = False,
+                 low_cut: Optional[LowCut] = None) -> None:
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
         if not isinstance(max_chunk, int) or max_chunk < 1:
@@ -441,6 +563,11 @@ class LogMelPool:
         self._free = list(range(capacity))
         self._open: Dict[int, MelSession] = {}
         self._op = ops.logmel_pool_impl
+        self.low_cut, self.hist = low_cut, None
+        if low_cut is not None:
+            _check_low_cut(low_cut, extractor)
+            self.hist = torch.zeros((capacity, max(1, low_cut.n_taps - 1)), dtype=torch.float32, device=extractor.device)
+            self._cut_op = ops.logmel_pool_lowcut_impl
 
     def open(self) -> MelSession:
         """claim a free slot for a new signal (whatever the slot held before is never read)"""
@@ -512,7 +639,7 @@ class LogMelPool:
         """one call for a whole tick of audio: push(chunk) for every session of `chunks` ({session: 1-D samples on the host or
         the device, 0 .. max_chunk of them}) and finish for every session of `finish` (which may also have a last chunk in
         `chunks`) -> {session: (1, n_mels, k) fp32 new frames on the device, k >= 0}, contiguous views of the calls' output
-        buffers.  Per 64 sessions: one staging copy, one swn_logmel_pool call (two launches).  Everything is checked first and
+        buffers.  Per 64 sessions: one staging copy, one swn_logmel_pool (with a low cut: swn_logmel_pool_lowcut) call (two launches).  Everything is checked first and
         the counters move only after every call is enqueued: a call that raises leaves every session as it was."""
         order = self._check(chunks, finish)
         ext = self.ext
@@ -521,10 +648,17 @@ class LogMelPool:
         results: Dict[MelSession, torch.Tensor] = {}
         for entries in calls:
             staged = self._stage([order[e.key][1] for e in entries if e.n_new > 0])
-            out = self._op(self.windows, staged, ext._table, ext.bank, [order[e.key][0].slot for e in entries],
-                           [e.t0 for e in entries], [e.n_held for e in entries], [e.n_drop for e in entries],
-                           [e.n_new for e in entries], [e.len for e in entries], [e.f0 for e in entries],
-                           [e.f1 for e in entries], ext.n_fft, ext.hop, ext.floor, self.linear)
+            if self.low_cut is None:
+                out = self._op(self.windows, staged, ext._table, ext.bank, [order[e.key][0].slot for e in entries],
+                               [e.t0 for e in entries], [e.n_held for e in entries], [e.n_drop for e in entries],
+                               [e.n_new for e in entries], [e.len for e in entries], [e.f0 for e in entries],
+                               [e.f1 for e in entries], ext.n_fft, ext.hop, ext.floor, self.linear)
+            else:
+                out = self._cut_op(self.windows, self.hist, staged, ext._table, ext.bank, self.low_cut._taps,
+                                   [order[e.key][0].slot for e in entries], [e.t0 for e in entries],
+                                   [e.n_held for e in entries], [e.n_drop for e in entries], [e.n_new for e in entries],
+                                   [e.len for e in entries], [e.f0 for e in entries], [e.f1 for e in entries], ext.n_fft,
+                                   ext.hop, ext.floor, self.linear)
             for e in entries:
                 k = e.f1 - e.f0
                 results[order[e.key][0]] = out[e.out_off:e.out_off + k * ext.n_mels].view(1, ext.n_mels, k)

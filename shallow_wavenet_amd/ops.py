@@ -45,6 +45,9 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.logmel_pool(win, staged, tables, bank, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s, n_fft, hop,
                               floor, linear) -> features of all sessions, channel-major (updates win)
     torch.ops.swn.mcep(wav, tables, t0s, n_avails, lens, f0s, f1s, n_fft, hop, order, floor) -> mel-cepstra
+    torch.ops.swn.lowcut_chunk(taps, state, inputs, slots, resets, capacity) -> low-cut chunks (updates state)
+    torch.ops.swn.logmel_pool_lowcut(win, hist, staged, tables, bank, taps, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s,
+                                     n_fft, hop, floor, linear) -> logmel_pool on raw samples (updates win and hist)
     torch.ops.swn.laplace_loss(raw, ctx?, target, eps, desc, skip) -> (nll, err, samples, targets, stats)
     torch.ops.swn.laplace_loss_backward(raw, ctx?, target, eps, g_nll, g_samples?, desc, skip) -> grad_raw
 """
@@ -1485,6 +1488,13 @@ def logmel_pool_impl(win: torch.Tensor, staged: Optional[torch.Tensor], tables: 
     the front, appends the next n_news[e] samples of `staged` (the entries' new samples back to back; None when there are
     none) and computes the frames [f0s[e], f1s[e]) -> a flat buffer with every entry's (n_mels, f1 - f0) block back to back
     in entry order.  `win` is updated in place."""
+    return _logmel_pool_call(win, staged, tables, bank, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s, n_fft, hop, floor,
+                             linear, None, None)
+
+
+def _logmel_pool_call(win, staged, tables, bank, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s, n_fft, hop, floor, linear,
+                      hist, taps) -> torch.Tensor:
+    """logmel_pool (hist and taps None: swn_logmel_pool) and logmel_pool_lowcut (swn_logmel_pool_lowcut)"""
     Lb = _lib.lib()
     _need_cuda(win, "the windows")
     dev = win.device
@@ -1519,9 +1529,15 @@ def logmel_pool_impl(win: torch.Tensor, staged: Optional[torch.Tensor], tables: 
     work = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=dev)
     bank_c = (ctypes.c_int32 * n_mels)(*[int(b) for b in bank])
     with _on(dev):
-        _lib.check(Lb.swn_logmel_pool(n_fft, hop, n_mels, float(floor), int(bool(linear)), _ptr(tables), bank_c, _ptr(win),
-                                      win.shape[1], _ptr(staged), _ptr(out) if out_off else None, table, E, _ptr(work),
-                                      _stream(dev)), "logmel_pool")
+        if taps is None:
+            _lib.check(Lb.swn_logmel_pool(n_fft, hop, n_mels, float(floor), int(bool(linear)), _ptr(tables), bank_c, _ptr(win),
+                                          win.shape[1], _ptr(staged), _ptr(out) if out_off else None, table, E, _ptr(work),
+                                          _stream(dev)), "logmel_pool")
+        else:
+            _lib.check(Lb.swn_logmel_pool_lowcut(n_fft, hop, n_mels, float(floor), int(bool(linear)), _ptr(tables), bank_c,
+                                                 _ptr(win), win.shape[1], _ptr(staged), _ptr(out) if out_off else None, table, E,
+                                                 _ptr(work), taps.numel(), _ptr(taps), _ptr(hist), _stream(dev)),
+                       "logmel_pool_lowcut")
     return out
 
 
@@ -1534,10 +1550,88 @@ def _(win, staged, tables, bank, slots, t0s, n_helds, n_drops, n_news, lens, f0s
     return win.new_empty((len(bank) * sum(max(f1 - f0, 0) for f0, f1 in zip(f0s, f1s)),), dtype=torch.float32)
 
 
+# ------------------------------------------------------------------------------------------ stage-1 low cut
+def _lowcut_taps_check(taps: torch.Tensor, what: str) -> int:
+    if taps.dim() != 1 or taps.dtype != torch.float64 or not taps.is_contiguous() or not 1 <= taps.numel() <= _lib.LOWCUT_MAX_TAPS:
+        raise RuntimeError(f"{what}: taps must be 1 .. {_lib.LOWCUT_MAX_TAPS} contiguous fp64 values")
+    return taps.numel()
+
+
+def lowcut_chunk_impl(taps: torch.Tensor, state: torch.Tensor, inputs: List[torch.Tensor], slots: List[int],
+                      resets: List[bool], capacity: int) -> torch.Tensor:
+    """one call of the device low cut (swn_lowcut_chunk; the definition is in melspec.py): entry e filters inputs[e] (1-D fp32)
+    as the next chunk of the session in slot slots[e] of `state` (at least capacity * (n_taps - 1) fp32, the slots' last raw
+    samples, updated in place); resets[e] starts that slot from zero history.  taps: the n_taps fp64 taps.  Any number of
+    entries.  -> (E, n_max) fp32, rows past an entry's own length not written."""
+    L = _lib.lib()
+    dev = taps.device
+    _need_cuda(taps, "the taps")
+    n_taps = _lowcut_taps_check(taps, "lowcut_chunk")
+    E = len(inputs)
+    if not (len(slots) == len(resets) == E):
+        raise RuntimeError("lowcut_chunk: inputs, slots and resets must have one entry each")
+    if (state.device != dev or state.dtype != torch.float32 or not state.is_contiguous()
+            or state.numel() < max(1, (n_taps - 1) * int(capacity))):
+        raise RuntimeError("lowcut_chunk: state must be a contiguous fp32 tensor of capacity * (n_taps - 1) values (at least one) "
+                           "on the device of the taps")
+    ins = []
+    for x in inputs:
+        if x.device != dev or x.dim() != 1 or x.dtype != torch.float32:
+            raise RuntimeError("lowcut_chunk: every input must be a 1-D fp32 tensor on the device")
+        ins.append(x.contiguous())
+    n_max = max((x.numel() for x in ins), default=0)
+    out = torch.empty((E, n_max), dtype=torch.float32, device=dev)
+    table = (_lib.LowcutEntry * max(E, 1))()
+    for e, x in enumerate(ins):
+        n = x.numel()
+        table[e] = _lib.LowcutEntry(in_dev=x.data_ptr() if n else None, out_dev=out[e].data_ptr() if n else None,
+                                    slot=int(slots[e]), n=n, flags=_lib.LOWCUT_RESET if resets[e] else 0, reserved=0)
+    with _on(dev):
+        _lib.check(L.swn_lowcut_chunk(n_taps, _ptr(taps), _ptr(state), int(capacity), table, E, _stream(dev)), "lowcut_chunk")
+    return out
+
+
+lowcut_chunk = custom_op("swn::lowcut_chunk", mutates_args=("state",))(lowcut_chunk_impl)
+
+
+@lowcut_chunk.register_fake
+def _(taps, state, inputs, slots, resets, capacity):
+    return taps.new_empty((len(inputs), max((x.numel() for x in inputs), default=0)), dtype=torch.float32)
+
+
+def logmel_pool_lowcut_impl(win: torch.Tensor, hist: torch.Tensor, staged: Optional[torch.Tensor], tables: torch.Tensor,
+                            bank: List[int], taps: torch.Tensor, slots: List[int], t0s: List[int], n_helds: List[int],
+                            n_drops: List[int], n_news: List[int], lens: List[int], f0s: List[int], f1s: List[int], n_fft: int,
+                            hop: int, floor: float, linear: bool) -> torch.Tensor:
+    """logmel_pool whose `staged` samples are RAW: they reach the windows through the low cut of `taps` (n_taps fp64 values;
+    swn_logmel_pool_lowcut, the bits of lowcut_chunk).  hist (slots, n_taps - 1) fp32 - at least one column - holds every
+    window slot's last raw samples; an entry with t0 == 0 and n_held == 0 starts from zero history whatever its row holds.
+    `win` and `hist` are updated in place."""
+    _need_cuda(win, "the windows")
+    n_taps = _lowcut_taps_check(taps, "logmel_pool_lowcut")
+    if taps.device != win.device:
+        raise RuntimeError("logmel_pool_lowcut: the taps must be on the device of the windows")
+    if (hist.device != win.device or hist.dtype != torch.float32 or not hist.is_contiguous() or hist.dim() != 2
+            or hist.shape[0] != win.shape[0] or hist.shape[1] != max(1, n_taps - 1)):
+        raise RuntimeError(f"logmel_pool_lowcut: hist must be a contiguous fp32 ({win.shape[0]}, {max(1, n_taps - 1)}) buffer on "
+                           "the device of the windows")
+    return _logmel_pool_call(win, staged, tables, bank, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s, n_fft, hop, floor,
+                             linear, hist, taps)
+
+
+logmel_pool_lowcut = custom_op("swn::logmel_pool_lowcut", mutates_args=("win", "hist"))(logmel_pool_lowcut_impl)
+
+
+@logmel_pool_lowcut.register_fake
+def _(win, hist, staged, tables, bank, taps, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s, n_fft, hop, floor, linear):
+    _logmel_check(n_fft, hop, len(bank), floor)
+    return win.new_empty((len(bank) * sum(max(f1 - f0, 0) for f0, f1 in zip(f0s, f1s)),), dtype=torch.float32)
+
+
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
             "pack_decode_w16", "decode_w16", "decode_chunk_w16", "decode_pool_chunk_w16",
             "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
             "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
-            "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool", "mcep")
+            "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool", "mcep", "lowcut_chunk", "logmel_pool_lowcut")
