@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import postfilter_ref as R
 from shallow_wavenet_amd import config as C
 from shallow_wavenet_amd import decode_driver as DD
 from shallow_wavenet_amd import dsp, featio
@@ -51,11 +52,26 @@ def test_one_shot_matches_host_noise_shaping(gpu_ok, pade, inv):
     r = NoiseShapingRestorer(MEAN, fs, ALPHA, inv=inv, pade=pade, device=DEV)
     xs = [_signal(n, i) for i, n in enumerate([1, 4410, 66000])]
     ys = r.restore([x.to(DEV) for x in xs])
-    for x, y in zip(xs, ys):
+    # the exact reference (tests/postfilter_ref.py) of each signal's first 4 410 samples, one batched run; from zero state the
+    # reference of a prefix is the prefix of the reference
+    n_ref = 4410
+    xr = np.zeros((len(xs), n_ref))
+    for i, x in enumerate(xs):
+        xr[i, :min(n_ref, x.numel())] = x.numpy()[:n_ref]
+    ref, _ = R.restore_ref(xr, r.b, ALPHA, pade, r.taps)
+    l1, tail = R.impulse_l1(r.b, ALPHA, pade, r.taps)
+    assert tail < 1e-20
+    for i, (x, y) in enumerate(zip(xs, ys)):
         assert y.dtype == torch.float32 and y.numel() == x.numel()
+        got = y.cpu().numpy().astype(np.float64)
         want = _host(x.numpy(), fs, inv, pade)
-        err = float(np.abs(y.cpu().numpy().astype(np.float64) - want).max())
+        err = float(np.abs(got - want).max())
         assert err <= 1e-6, (pade, inv, x.numel(), err)
+        k = min(n_ref, x.numel())
+        bound = R.output_bound(ref[i, :k], R.e64(r.order, pade, r.n_taps, l1, float(np.abs(xr[i]).max())))
+        share = float((np.abs(got[:k] - ref[i, :k]) / bound).max())
+        print(f"pade {pade} inv {inv} n {x.numel()}: share of the bound {share:.3f}")
+        assert share <= 1.0, (pade, inv, x.numel(), share)
     assert float(np.abs(want).max()) > 0.1                                        # it filtered something
 
 
