@@ -800,6 +800,66 @@ int    swn_logmel_pool_lowcut(int n_fft, int hop, int n_mels, float floor, int l
                               const swn_logmel_pool_entry* entries_host, int n_entries, float* work_dev, int n_taps,
                               const double* taps_dev, float* hist_dev, void* stream);
 
+/* ---- rational resampler on the device (melspec.Resampler; csrc/swn_resample.hip) -----------------------------------------------
+ * The definition (melspec.py restates it, tests/resample_ref.py pins it).  fs_in and fs_out are integers, up = L = fs_out / g and
+ * down = M = fs_in / g with g = gcd(fs_in, fs_out).  Prototype filter h[0 .. N - 1] in fp64, N = n_taps odd, D = (N - 1) / 2
+ * (melspec.resample_taps: L * firwin(2 * 10 * max(L, M) + 1, 1 / max(L, M), ("kaiser", 5.0)), the filter of scipy's resample_poly).
+ * Polyphase table P[r][q], r < L, q < Q = ceil(N / L): P[r][q] = h[r + q L], and 0.0 where r + q L >= N; fp64 on the device, row
+ * by row (swn_resample_table_doubles = L Q doubles).  Output sample n (absolute index) of a signal of `len` fp32 input samples,
+ * x[t] = 0 outside [0, len):
+ *     p = n M + D (64-bit),  r = p mod L,  i0 = p div L
+ *     acc = +0.0;  for q = 0 .. Q - 1 ascending: acc = fma(P[r][q], (double)x[i0 - q], acc);  y[n] = (float)acc
+ * and there are ceil(len L / M) outputs: one fp64 fma chain in a fixed order, rounded once to fp32 - the arithmetic of
+ * swn_lowcut_chunk.  A sample's bits depend only on its absolute index and the signal, not on the chunking, the entry, the batch,
+ * the tile or the call.  Streaming rule (melspec.resample_ready is the one place it is written): while the signal goes on and T
+ * inputs have arrived, the computable outputs are those with i0 <= T - 1 - none if T L - 1 - D < 0, else (T L - 1 - D) div M + 1 of
+ * them; when the signal ends at T, all ceil(T L / M).  A session's state is its last Q - 1 RAW inputs in fp32 (exact), which is
+ * what makes a call parallel over time.
+ *
+ * swn_resample_chunk: state_dev holds `capacity` slots of swn_resample_state_floats(up, n_taps) = Q - 1 floats, slot s from float
+ * s (Q - 1) on, oldest sample first.  Entry e (HOST table, any number, launched in groups of SWN_RESAMPLE_MAX_ENTRIES and carried
+ * in the launch arguments: no host copy, no synchronisation) is one session's next chunk: in_dev holds the n_in new inputs at
+ * absolute indices [in0, in0 + n_in), out_dev receives the n_out outputs at absolute indices [out0, out0 + n_out); len is the
+ * signal's length, or -1 while it is unknown.  An entry with in0 == 0 starts from zero history whatever the slot holds;
+ * n_in == 0 && n_out == 0 leaves the slot untouched; n_in == 0 with len == in0 is the flush at the end.  Blocks cover (entry, tile
+ * of SWN_RESAMPLE_TILE outputs); a block stages the input span its tile reads (from the chunk, or from the slot's state below the
+ * chunk's first sample) in LDS and writes its outputs; the table is read through the caches.  That launch writes no state: a
+ * second small launch, one block per entry and stream-ordered behind the first, replaces it, reading the old state whole before
+ * writing any of it.
+ * SWN_E_BADARG, found on the host before anything is launched, text in swn_last_error_detail:
+ *   - up or down < 1, or not coprime; n_taps even or outside [1, SWN_RESAMPLE_MAX_TAPS]; up > SWN_RESAMPLE_MAX_UP;
+ *     Q > SWN_RESAMPLE_MAX_Q; a tile's input span ceil(SWN_RESAMPLE_TILE down / up) + Q > SWN_RESAMPLE_MAX_SPAN
+ *   - a null table_dev or state_dev, capacity < 1, n_entries < 0, a null entries_host with n_entries > 0; a null in_dev with
+ *     n_in > 0 or a null out_dev with n_out > 0
+ *   - a slot outside [0, capacity) or named twice; n_in, n_out, in0 or out0 < 0, len < -1, an index too large for the 64-bit
+ *     arithmetic; a non-zero reserved field; in_dev and out_dev ranges of one entry that overlap
+ *   - an output that is not computable: i0 > in0 + n_in - 1 for the last output while len is -1; or, with len given,
+ *     len != in0 + n_in, or an output index >= ceil(len up / down)
+ *   - an output that reads below the state: i0 of output out0 is < in0.
+ * The size queries return 0 for refused arguments (swn_resample_state_floats also for Q == 1, which has no state).
+ * sizeof(swn_resample_entry) == 56. */
+#define SWN_RESAMPLE_MAX_UP 1024
+#define SWN_RESAMPLE_MAX_Q 256
+#define SWN_RESAMPLE_MAX_TAPS 65535
+#define SWN_RESAMPLE_MAX_ENTRIES 64
+#define SWN_RESAMPLE_TILE 1024          /* output samples per block */
+#define SWN_RESAMPLE_MAX_SPAN 8192      /* floats of a block's LDS image of the input */
+typedef struct swn_resample_entry {
+    const float* in_dev;     /* n_in raw fp32 inputs, absolute indices [in0, in0 + n_in) */
+    float* out_dev;          /* n_out fp32 outputs, absolute indices [out0, out0 + n_out); must not overlap in_dev's range */
+    int64_t in0;             /* inputs the session received before this chunk; 0 starts from zero history */
+    int64_t out0;            /* outputs the session was given before this chunk */
+    int64_t len;             /* the signal's length (then == in0 + n_in), or -1 while it goes on */
+    int32_t n_in;            /* >= 0 */
+    int32_t n_out;           /* >= 0 */
+    int32_t slot;            /* [0, capacity) */
+    int32_t reserved;        /* 0 */
+} swn_resample_entry;
+size_t swn_resample_table_doubles(int up, int down, int n_taps);
+size_t swn_resample_state_floats(int up, int n_taps);
+int    swn_resample_chunk(int up, int down, int n_taps, const double* table_dev, float* state_dev, int capacity,
+                          const swn_resample_entry* entries_host, int n_entries, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ import ctypes
 import os
 import subprocess
 import threading
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 from .config import NetConfig
 
@@ -84,6 +84,12 @@ class LowcutEntry(ctypes.Structure):
                 ("reserved", c_int32)]
 
 
+class ResampleEntry(ctypes.Structure):
+    """mirror of `swn_resample_entry` (include/swn_hip.h): one session's next chunk of a resampler call."""
+    _fields_ = [("in_dev", c_void_p), ("out_dev", c_void_p), ("in0", c_int64), ("out0", c_int64), ("len", c_int64),
+                ("n_in", c_int32), ("n_out", c_int32), ("slot", c_int32), ("reserved", c_int32)]
+
+
 ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
 DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
@@ -101,6 +107,8 @@ POSTFILTER_MAX_TAPS = 256                      # SWN_POSTFILTER_MAX_TAPS
 POSTFILTER_MULAW_ENTRIES = 256                 # SWN_POSTFILTER_MULAW_ENTRIES
 LOWCUT_MAX_TAPS, LOWCUT_TILE = 256, 1024       # SWN_LOWCUT_MAX_TAPS, SWN_LOWCUT_TILE: output samples per block of the kernel
 LOWCUT_MAX_ENTRIES, LOWCUT_RESET = 64, 1       # SWN_LOWCUT_MAX_ENTRIES (entries per launch group), SWN_LOWCUT_RESET
+RESAMPLE_MAX_UP, RESAMPLE_MAX_Q, RESAMPLE_MAX_TAPS = 1024, 256, 65535    # SWN_RESAMPLE_MAX_UP, _MAX_Q, _MAX_TAPS
+RESAMPLE_MAX_ENTRIES, RESAMPLE_TILE, RESAMPLE_MAX_SPAN = 64, 1024, 8192  # SWN_RESAMPLE_MAX_ENTRIES, _TILE (outputs per block), _MAX_SPAN
 SPECTRAL_MAX_SIZES, SPECTRAL_MAX_FFT = 32, 2048   # SWN_SPECTRAL_MAX_SIZES, SWN_SPECTRAL_MAX_FFT
 LOGMEL_MAX_MELS, LOGMEL_MAX_ENTRIES = 128, 64     # SWN_LOGMEL_MAX_MELS, SWN_LOGMEL_MAX_ENTRIES
 LOGMEL_POOL_MAX_ENTRIES = 64                   # SWN_LOGMEL_POOL_MAX_ENTRIES (include/swn_hip.h): entries per log-mel pool call
@@ -235,6 +243,9 @@ SIGNATURES = {
     "swn_logmel_pool_lowcut": (c_int, [c_int, c_int, c_int, c_float, c_int, c_void_p, POINTER(c_int32), c_void_p, c_size_t,
                                        c_void_p, c_void_p, POINTER(LogMelPoolEntry), c_int, c_void_p, c_int, c_void_p, c_void_p,
                                        c_void_p]),
+    "swn_resample_table_doubles": (c_size_t, [c_int, c_int, c_int]),
+    "swn_resample_state_floats": (c_size_t, [c_int, c_int]),
+    "swn_resample_chunk": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, POINTER(ResampleEntry), c_int, c_void_p]),
 }
 
 

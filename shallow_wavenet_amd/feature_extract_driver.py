@@ -23,10 +23,17 @@ waveforms is filtered there, the features are taken from that device tensor with
 are written from it.  These are the bits `LogMelStream(low_cut=)` and `LogMelPool(low_cut=)` give a live session, so features
 taken this way and features taken while serving agree exactly.  The default `host` is `dsp.low_cut_filter` as before; the two
 settings differ by at most the rounding of the device definition (melspec.py): both sum the same products in fp64, in
-different orders, and the device rounds once to fp32, so a sample of a PCM16 file can differ by one step."""
+different orders, and the device rounds once to fp32, so a sample of a PCM16 file can differ by one step.
+
+`--resample true` takes files of any sampling frequency: a file whose own rate is not --fs is resampled to --fs on the device
+(`melspec.Resampler`, csrc/swn_resample.hip: the filter of scipy's resample_poly as one fp64 fma chain per sample, rounded once
+to fp32) before the high-pass filter, wherever that runs; `--wavdir` then receives audio at --fs.  These are the bits
+`LogMelStream(resample=)` and `LogMelPool(resample=)` give a live session fed at the file's rate.  Without the flag such a file
+is refused, as before."""
 from __future__ import annotations
 
 import argparse
+import functools
 import logging
 import multiprocessing as mp
 import os
@@ -37,7 +44,7 @@ import numpy as np
 
 from . import dsp, featio
 from .decode_driver import write_wav_pcm16
-from .noise_shaping_driver import list_waveforms, read_wav_fs
+from .noise_shaping_driver import _strtobool, list_waveforms, read_wav_fs
 
 FS, SHIFTMS, FFTL, HIGHPASS_CUTOFF, MCEP_ALPHA = 22050, 5.0, 1024, 70, 0.455      # the reference's stage-1 defaults
 STRING_PATH = "/feat_logmel"
@@ -60,6 +67,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "the bits of the live streams and pools).  The two differ by at most the rounding of the device "
                         "definition - fp64 sums in different orders, rounded once to fp32 - so a PCM16 sample can differ by one "
                         "step (not a reference flag)")
+    p.add_argument("--resample", default=False, type=_strtobool,
+                   help="true: a file whose sampling frequency is not --fs is resampled to --fs on the device (melspec.Resampler) "
+                        "before the high-pass filter; false: it is refused (not a reference flag)")
     p.add_argument("--n_jobs", default=1, type=int, help=f"number of worker processes (at most {MAX_JOBS})")
     p.add_argument("--verbose", default=1, type=int, help="log level")
     p.add_argument("--feature_type", default="logmel", choices=("logmel", "mcep", "world"), help="not a reference flag")
@@ -96,15 +106,24 @@ def on_device(args) -> bool:
     return getattr(args, "highpass_on", "host") == "device" and args.highpass_cutoff != 0
 
 
-def load_waveform(name: str, args) -> np.ndarray:
+@functools.lru_cache(maxsize=8)
+def _resampler(fs_in: int, fs_out: int, device: str):
+    from .melspec import Resampler
+    return Resampler(fs_in, fs_out, device=device)
+
+
+def load_waveform(name: str, args, device="cuda") -> np.ndarray:
     """the utterance as the features see it: mono float64, high-pass filtered (and written to --wavdir) when the cut-off is not 0
     - or raw when the filter runs on the device (extract_files filters the batch and writes --wavdir from the result).
-    ValueError when the file's sampling frequency is not --fs (the mel scale, the hop and the filter would all be wrong)."""
+    ValueError when the file's sampling frequency is not --fs (the mel scale, the hop and the filter would all be wrong) - unless
+    --resample is true: then the file is resampled to --fs on `device` first (fp32 values, which float64 holds exactly)."""
     x, fs = read_wav_fs(name)
-    if fs != args.fs:
+    if fs != args.fs and not getattr(args, "resample", False):
         raise ValueError(f"{name}: sampling frequency {fs} does not match --fs {args.fs}")
     if x.ndim > 1:
         x = x[:, 0]
+    if fs != args.fs:
+        x = _resampler(int(fs), int(args.fs), str(device))(x.astype(np.float32))[0].cpu().numpy().astype(np.float64)
     if args.highpass_cutoff != 0 and not on_device(args):
         x = dsp.low_cut_filter(x, args.fs, cutoff=args.highpass_cutoff)
         if args.wavdir:
@@ -119,7 +138,7 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
             logging.error("--highpass_on device serves the features computed on the device, not --feature_type world")
             return 2
         for name in files:
-            feats = dsp.extract_features(load_waveform(name, args), args.fs, shiftms=args.shiftms, fftl=args.fftl)
+            feats = dsp.extract_features(load_waveform(name, args, device), args.fs, shiftms=args.shiftms, fftl=args.fftl)
             featio.write_dataset(feature_path(args.hdf5dir, name), args.string_path, feats)
         return 0
     from .melspec import LogMelExtractor, LowCut, MelCepstrumExtractor
@@ -144,7 +163,7 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
         waves: List[np.ndarray] = []
         for name in files[i:i + BATCH]:
             try:
-                x = load_waveform(name, args)
+                x = load_waveform(name, args, device)
             except ValueError as e:
                 logging.error("%s", e)
                 rc = 1

@@ -14,6 +14,9 @@ fully pinned feature type next to the WORLD / SPTK features of run.sh stage 1 (w
     cut = LowCut(fs=22050, cutoff=70.0, device="cuda:0")       # the stage-1 low cut (`torch.ops.swn.lowcut_chunk`): what the
     y = cut(wavs, lengths)                                     # training features were taken from; LogMelStream(ext, low_cut=cut)
                                                                # and LogMelPool(..., low_cut=cut) take RAW samples and filter them
+    res = Resampler(fs_in=48000, fs_out=22050, device="cuda:0")    # the rational resampler (`torch.ops.swn.resample_chunk`) in
+    y = res(wavs, lengths)                                     # front of it: LogMelStream(ext, resample=res, low_cut=cut) and
+                                                               # LogMelPool(..., resample=res, low_cut=cut) take samples at fs_in
 
 Definition (the contract; include/swn_hip.h and csrc/swn_melspec.hip restate it).  Parameters: `fs` sample rate; `n_fft` a
 multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT]; `hop` in 1 .. n_fft, which need not divide n_fft (the 22.05 kHz nets use 110,
@@ -44,9 +47,24 @@ the call - so any partition of a signal into chunks gives the bits of the one-sh
 the extractor's on the one-shot filtered signal.  A session's state is its last n_taps - 1 raw input samples in fp32 (exact: the
 inputs are fp32).  `dsp.low_cut_filter` (scipy's lfilter, float64 out) sums the same products in another order and is not
 rounded to fp32: the two differ by the rounding above, at most one step of a PCM16 file.
+
+The resampler (the contract; include/swn_hip.h states it, tests/resample_ref.py pins it).  fs_in and fs_out are integers,
+L = fs_out / g and M = fs_in / g with g = gcd(fs_in, fs_out).  Prototype filter h[0 .. N - 1] in fp64, N odd, from
+`resample_taps(L, M, half_len=10, beta=5.0)`: N = 2 * 10 * max(L, M) + 1 and h = L * scipy.signal.firwin(N, 1 / max(L, M),
+window=("kaiser", 5.0)), the filter of `scipy.signal.resample_poly`; D = (N - 1) / 2.  Polyphase table P[r][q], r < L,
+q < Q = ceil(N / L): P[r][q] = h[r + q L], and 0.0 where r + q L >= N (`resample_table`), fp64 on the device, row by row.  Output
+sample n (absolute index) of a signal of `len` input samples, x[t] = 0 outside [0, len):
+    p = n M + D (64-bit),  r = p mod L,  i0 = p div L
+    acc = +0.0;  for q = 0 .. Q - 1 ascending: acc = fma(P[r][q], (double)x[i0 - q], acc);  y[n] = (float)acc
+and there are ceil(len L / M) outputs.  One fp64 fma chain in a fixed order, rounded once to fp32: a sample's bits depend only on
+its absolute index and the signal, not on the chunking, the entry, the batch, the tile or the call.  Streaming rule
+(`resample_ready`, the one place it is written): while the signal goes on and T inputs have arrived, the computable outputs are
+those with i0 <= T - 1 - none if T L - 1 - D < 0, else (T L - 1 - D) div M + 1 of them; when the signal ends at T, all
+ceil(T L / M).  A session's state is its last Q - 1 raw inputs in fp32 (exact), so a call is parallel over time.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -396,6 +414,181 @@ def _check_low_cut(low_cut, extractor: "LogMelExtractor") -> None:
         raise ValueError(f"the low cut was built for fs {low_cut.fs}, the extractor for {extractor.fs}")
 
 
+# ---- rational resampler --------------------------------------------------------------------------------------------------
+def resample_ratio(fs_in: int, fs_out: int) -> Tuple[int, int]:
+    """(L, M) = (fs_out / g, fs_in / g), g = gcd(fs_in, fs_out): 48 000 -> 24 000 Hz is 1 / 2"""
+    for name, fs in (("fs_in", fs_in), ("fs_out", fs_out)):
+        if isinstance(fs, bool) or not isinstance(fs, (int, np.integer)) or fs < 1:
+            raise ValueError(f"{name} must be a positive integer number of Hz, not {fs!r}")
+    g = math.gcd(int(fs_in), int(fs_out))
+    return int(fs_out) // g, int(fs_in) // g
+
+
+def resample_taps(L: int, M: int, half_len: int = 10, beta: float = 5.0) -> np.ndarray:
+    """the prototype filter in fp64: N = 2 * half_len * max(L, M) + 1 taps, L * firwin(N, 1 / max(L, M), ("kaiser", beta)) -
+    with the defaults the filter `scipy.signal.resample_poly(x, L, M)` designs for itself"""
+    from scipy.signal import firwin
+    L, M, half_len = int(L), int(M), int(half_len)
+    if L < 1 or M < 1 or half_len < 1:
+        raise ValueError(f"L, M and half_len must be positive, got {L}, {M}, {half_len}")
+    top = max(L, M)
+    return L * firwin(2 * half_len * top + 1, 1.0 / top, window=("kaiser", float(beta)))
+
+
+def resample_table(h, L: int) -> np.ndarray:
+    """the polyphase table (L, Q = ceil(N / L)) in fp64: P[r][q] = h[r + q L], and 0.0 where r + q L >= N"""
+    h = np.asarray(h, dtype=np.float64).reshape(-1)
+    L = int(L)
+    Q = -(-h.size // L)
+    flat = np.zeros(Q * L, dtype=np.float64)
+    flat[:h.size] = h
+    return np.ascontiguousarray(flat.reshape(Q, L).T)
+
+
+def resample_ready(L: int, M: int, n_taps: int, n_received: int, final: bool = False) -> int:
+    """the streaming rule: outputs of a signal that can be computed once n_received inputs are there.  While it goes on, those
+    whose newest input i0 = (n M + D) div L has arrived, D = (n_taps - 1) / 2; when it ends there (`final`), all
+    ceil(n_received L / M): the last ones read the zeros past the end."""
+    T = int(n_received)
+    if final:
+        return -(-T * L // M)
+    a = T * L - 1 - (int(n_taps) - 1) // 2
+    return 0 if a < 0 else a // M + 1
+
+
+class Resampler:
+    """the rational resampler fs_in -> fs_out on the device, with the polyphase table held there as fp64 and `capacity` session
+    slots; the definition is in the module docstring.
+
+        res = Resampler(48000, 22050, capacity=8, device="cuda:0")
+        y = res(wavs, lengths)                   # one-shot: (rows, max outputs) fp32; row r holds res.out_count(lengths[r]) values
+        s = res.open()                           # a free slot (or open(slot) for a given one); starts from zero history
+        out = res.run({s: chunk})                # {slot: the outputs that became computable}; one device call for all slots
+        out = res.run({}, finish=[s])            # ... the signal ends: the rest (a last chunk may come in the same call)
+        res.close(s)
+    """
+
+    def __init__(self, fs_in: int, fs_out: int, capacity: int = 1, device="cuda", half_len: int = 10, beta: float = 5.0) -> None:
+        if not isinstance(capacity, int) or capacity < 1:
+            raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
+        self.L, self.M = resample_ratio(fs_in, fs_out)
+        if fs_in == fs_out:
+            raise ValueError(f"fs_in == fs_out == {fs_in}: there is nothing to resample (leave resample=None)")
+        self.fs_in, self.fs_out, self.capacity = int(fs_in), int(fs_out), capacity
+        self.taps = np.ascontiguousarray(resample_taps(self.L, self.M, half_len, beta), dtype=np.float64)
+        self.n_taps = int(self.taps.size)
+        self.delay = (self.n_taps - 1) // 2
+        self.table = resample_table(self.taps, self.L)
+        self.Q = int(self.table.shape[1])
+        if int(_lib.lib().swn_resample_table_doubles(self.L, self.M, self.n_taps)) != self.table.size:
+            raise ValueError(f"{fs_in} -> {fs_out} Hz is {self.L} / {self.M} with {self.n_taps} taps (Q = {self.Q}): the device "
+                             f"resampler takes up <= {_lib.RESAMPLE_MAX_UP}, Q <= {_lib.RESAMPLE_MAX_Q}, n_taps <= "
+                             f"{_lib.RESAMPLE_MAX_TAPS} and ceil({_lib.RESAMPLE_TILE} down / up) + Q <= {_lib.RESAMPLE_MAX_SPAN}")
+        self.device = torch.device(device)
+        self.state_floats = self.Q - 1
+        self._table = torch.from_numpy(self.table.reshape(-1)).to(self.device)
+        self._state = torch.zeros(max(1, capacity * self.state_floats), dtype=torch.float32, device=self.device)
+        self._free = list(range(capacity))
+        self._at: Dict[int, List[int]] = {}                   # open slot -> [inputs received, outputs returned, ended]
+        self._op = ops.resample_chunk_impl
+
+    def _check_len(self, length: int) -> None:
+        if length < 0:
+            raise ValueError(f"length {length}")
+
+    def ready(self, n_received: int, final: bool = False) -> int:
+        """the streaming rule (resample_ready) of this resampler"""
+        return resample_ready(self.L, self.M, self.n_taps, n_received, final)
+
+    def out_count(self, length: int) -> int:
+        """ceil(length L / M): the outputs of a signal of `length` inputs"""
+        return self.ready(length, True)
+
+    # ------------------------------------------------------------------ one shot
+    def __call__(self, wavs, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """wavs as LogMelExtractor takes them (a padded (R, S) batch with `lengths`, one 1-D signal, or a list of 1-D signals)
+        -> (R, out_count(max(lengths))) fp32 on the device: every row resampled from zero state, valid up to out_count of its
+        length (the floats past it are not written).  One device call; the open sessions' slots are not touched."""
+        batch, lens = _padded_batch(self, wavs, lengths)
+        R = len(lens)
+        state = torch.empty(max(1, R * self.state_floats), dtype=torch.float32, device=self.device)
+        return self._op(self._table, state, [batch[r, :lens[r]] for r in range(R)], list(range(R)), [0] * R, [0] * R,
+                        [self.out_count(n) for n in lens], lens, self.L, self.M, self.n_taps, R, False)
+
+    # ------------------------------------------------------------------ sessions
+    def open(self, slot: Optional[int] = None) -> int:
+        """claim a slot (the lowest free one when slot is None); its session starts from zero history."""
+        if slot is None:
+            if not self._free:
+                raise RuntimeError(f"the resampler is full: all {self.capacity} slots are open")
+            slot = self._free[0]
+        slot = int(slot)
+        if slot not in self._free:
+            raise RuntimeError(f"slot {slot} is not free (capacity {self.capacity})")
+        self._free.remove(slot)
+        self._at[slot] = [0, 0, False]
+        return slot
+
+    def close(self, slot: int) -> None:
+        """free the slot; a session opened in it later starts from zero history."""
+        slot = int(slot)
+        if slot not in self._at:
+            raise RuntimeError(f"slot {slot} is not open")
+        del self._at[slot]
+        self._free.append(slot)
+        self._free.sort()
+
+    def run(self, chunks: Mapping[int, torch.Tensor], finish: Sequence[int] = ()) -> Dict[int, torch.Tensor]:
+        """the next chunk (1-D samples at fs_in, host or device, any length) of each open slot's session, all in one device call
+        -> {slot: the fp32 outputs at fs_out that became computable (1-D, views of one dense buffer), possibly none}.  The
+        signals of the slots in `finish` end here (after their chunk of this call, if they have one): they receive all their
+        remaining outputs, and take no samples afterwards."""
+        ending = [int(s) for s in finish]
+        if len(set(ending)) != len(ending):
+            raise ValueError("a slot is named twice in finish")
+        slots = [int(s) for s in chunks] + [s for s in ending if s not in {int(k) for k in chunks}]
+        for s in slots:
+            if s not in self._at:
+                raise RuntimeError(f"slot {s} is not open")
+            if self._at[s][2]:
+                raise RuntimeError(f"the signal of slot {s} has ended: no samples can be run after it finished")
+        if not slots:
+            return {}
+        xs = [torch.as_tensor(c) for c in chunks.values()]
+        for x in xs:
+            if x.dim() != 1:
+                raise ValueError(f"samples must be a 1-D tensor, got shape {tuple(x.shape)}")
+        xs = [x.to(self.device, torch.float32) for x in xs]
+        xs += [torch.zeros(0, dtype=torch.float32, device=self.device)] * (len(slots) - len(xs))
+        in0s, out0s, n_outs, lens = [], [], [], []
+        for s, x in zip(slots, xs):
+            got, given, _ = self._at[s]
+            end = got + int(x.numel())
+            in0s.append(got)
+            out0s.append(given)
+            n_outs.append(self.ready(end, s in ending) - given)
+            lens.append(end if s in ending else -1)
+        out = self._op(self._table, self._state, xs, slots, in0s, out0s, n_outs, lens, self.L, self.M, self.n_taps, self.capacity,
+                       True)
+        res, at = {}, 0
+        for s, x, k in zip(slots, xs, n_outs):
+            self._at[s] = [self._at[s][0] + int(x.numel()), self._at[s][1] + k, s in ending]
+            res[s] = out[at:at + k]
+            at += k
+        return res
+
+
+def _check_resample(resample, low_cut, extractor: "LogMelExtractor") -> None:
+    if not isinstance(resample, Resampler):
+        raise ValueError(f"resample must be a Resampler or None, not {resample!r}")
+    if resample.device != extractor.device:
+        raise ValueError(f"the resampler is on {resample.device}, the extractor on {extractor.device}")
+    if resample.fs_out != int(extractor.fs):
+        raise ValueError(f"the resampler delivers fs {resample.fs_out}, the extractor was built for {extractor.fs}")
+    if low_cut is not None and isinstance(low_cut, LowCut) and low_cut.fs != resample.fs_out:
+        raise ValueError(f"the resampler delivers fs {resample.fs_out}, the low cut was built for {low_cut.fs}")
+
+
 # ---- the streaming rule: the one place LogMelStream and LogMelPool take it from ------------------------------------------
 def frames_ready(n_fft: int, hop: int, n_received: int, final: bool = False) -> int:
     """frames of a signal that can be computed once n_received samples are there.  While it goes on, those whose samples have
@@ -419,14 +612,28 @@ class LogMelStream:
     (those that read the reflected end).  Only the tail of the signal that later frames still read is kept.  The
     concatenation of everything returned is bit-identical to the extractor's one-shot call on the whole signal.  With
     `low_cut` (a LowCut) the pushed samples are RAW and every push filters them first, in a slot of the low cut that the
-    stream opens for itself and frees when it finishes: the frames are the extractor's on low_cut(whole signal)."""
+    stream opens for itself and frees when it finishes: the frames are the extractor's on low_cut(whole signal).  With
+    `resample` (a Resampler whose fs_out is the extractor's fs) the pushed samples are at its fs_in and every push resamples
+    them first, likewise in a slot of its own - resample, then low cut, then frames; `finish` flushes the resampler's last
+    outputs through the low cut before the last frames: the frames are the extractor's on low_cut(resample(whole signal))."""
 
-    def __init__(self, extractor: LogMelExtractor, linear: bool = False, low_cut: Optional[LowCut] = None) -> None:
+    def __init__(self, extractor: LogMelExtractor, linear: bool = False, low_cut: Optional[LowCut] = None,
+                 resample: Optional[Resampler] = None) -> None:
         self.ext, self.linear = extractor, bool(linear)
         self.low_cut, self._cut_slot = low_cut, None
+        self.resample, self._res_slot = resample, None
         if low_cut is not None:
             _check_low_cut(low_cut, extractor)
-            self._cut_slot = low_cut.open()
+        if resample is not None:
+            _check_resample(resample, low_cut, extractor)
+            self._res_slot = resample.open()
+        if low_cut is not None:
+            try:
+                self._cut_slot = low_cut.open()
+            except RuntimeError:
+                if resample is not None:
+                    resample.close(self._res_slot)
+                raise
         self._buf = torch.zeros(0, dtype=torch.float32, device=extractor.device)
         self.t0 = 0                 # absolute index of _buf[0]
         self.n_received = 0
@@ -458,16 +665,27 @@ class LogMelStream:
         if self.finished:
             raise RuntimeError("the stream is finished")
         s = torch.as_tensor(samples).reshape(-1).to(self.ext.device, torch.float32)
+        if self.resample is not None:
+            s = self.resample.run({self._res_slot: s})[self._res_slot]
+        self._take(s)
+        return self._range(self.computable(self.n_received), -1)
+
+    def _take(self, s: torch.Tensor) -> None:
+        """samples at the extractor's fs: through the low cut, into the buffer"""
         if self.low_cut is not None:
             s = self.low_cut.run({self._cut_slot: s})[self._cut_slot]
         self._buf = torch.cat([self._buf, s])
         self.n_received += int(s.numel())
-        return self._range(self.computable(self.n_received), -1)
 
     def finish(self) -> torch.Tensor:
         """the signal ends here -> the remaining frames up to F = 1 + n_received // hop"""
         if self.finished:
             raise RuntimeError("the stream is finished")
+        if self.resample is not None:
+            got, given, _ = self.resample._at[self._res_slot]
+            self.ext._check_len(self.n_received + self.resample.ready(got, True) - given)
+            self._take(self.resample.run({}, finish=[self._res_slot])[self._res_slot])
+            self.resample.close(self._res_slot)
         self.ext._check_len(self.n_received)
         self.finished = True
         if self.low_cut is not None:
@@ -535,6 +753,7 @@ class MelSession:
         self.n_held = 0             # samples in the window (what the next call no longer needs is dropped by that call)
         self.n_received = 0
         self.n_frames = 0           # frames returned so far
+        self.n_in = 0               # with a resampler: samples at fs_in received so far (n_received counts those at the extractor's fs)
         self.finished = False
         self.closed = False
 
@@ -547,10 +766,15 @@ class LogMelPool:
     SteppedDecodePool.push_many and DecodeStream.push take them.  With `low_cut` (a LowCut) the chunks are RAW samples: the
     window update filters them (`torch.ops.swn.logmel_pool_lowcut`, still two launches per call) and every session's frames are
     the extractor's on low_cut(whole signal).  The pool owns `hist` (capacity, n_taps - 1), each window slot's last raw samples;
-    a session opened in a freed slot starts from zero history.  The LowCut's own slots are not used."""
+    a session opened in a freed slot starts from zero history.  The LowCut's own slots are not used.  With `resample` (a
+    Resampler whose fs_out is the extractor's fs) the chunks are samples at its fs_in: one `torch.ops.swn.resample_staged` call
+    per 64 sessions writes every session's newly computable samples straight into the buffer the pool call then takes as its
+    staged new samples, and that call (with or without a low cut) follows unchanged - resample, then low cut, then frames.
+    `max_chunk` stays in samples at the extractor's fs: a chunk that yields more is refused before any launch.  The pool owns
+    `res_state` (capacity, Q - 1), each slot's last raw inputs; the Resampler's own slots are not used."""
 
     def __init__(self, extractor: LogMelExtractor, capacity: int, max_chunk: int, linear: bool = False,
-                 low_cut: Optional[LowCut] = None) -> None:
+                 low_cut: Optional[LowCut] = None, resample: Optional[Resampler] = None) -> None:
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
         if not isinstance(max_chunk, int) or max_chunk < 1:
@@ -568,6 +792,11 @@ class LogMelPool:
             _check_low_cut(low_cut, extractor)
             self.hist = torch.zeros((capacity, max(1, low_cut.n_taps - 1)), dtype=torch.float32, device=extractor.device)
             self._cut_op = ops.logmel_pool_lowcut_impl
+        self.resample, self.res_state = resample, None
+        if resample is not None:
+            _check_resample(resample, low_cut, extractor)
+            self.res_state = torch.zeros((capacity, max(1, resample.state_floats)), dtype=torch.float32, device=extractor.device)
+            self._res_op = ops.resample_staged_impl
 
     def open(self) -> MelSession:
         """claim a free slot for a new signal (whatever the slot held before is never read)"""
@@ -607,14 +836,40 @@ class LogMelPool:
                 c = torch.as_tensor(c)
                 if c.dim() != 1:
                     raise ValueError(f"samples must be a 1-D tensor, got shape {tuple(c.shape)}")
-                if c.numel() > self.max_chunk:
+                if self.resample is not None:
+                    n = self._yield(s, c, fin)
+                    if n > self.max_chunk:
+                        raise ValueError(f"a chunk of {c.numel()} samples at {self.resample.fs_in} Hz yields {n} at "
+                                         f"{self.resample.fs_out} Hz, the pool was built for at most {self.max_chunk}")
+                elif c.numel() > self.max_chunk:
                     raise ValueError(f"a chunk of {c.numel()} samples, the pool was built for at most {self.max_chunk}")
                 if c.dtype != torch.float32:
                     c = c.to(torch.float32)
             if fin:
-                self.ext._check_len(s.n_received + (0 if c is None else c.numel()))
+                self.ext._check_len(s.n_received + (self._yield(s, c, fin) if self.resample is not None else
+                                                    0 if c is None else c.numel()))
             out.append((s, c, fin))
         return out
+
+    def _yield(self, s: MelSession, c: Optional[torch.Tensor], fin: bool) -> int:
+        """with a resampler: the samples at the extractor's fs that chunk c (or the end of the signal) makes computable"""
+        return self.resample.ready(s.n_in + (0 if c is None else c.numel()), fin) - s.n_received
+
+    def _resampled(self, entries: List[MelPlanEntry], order) -> Optional[torch.Tensor]:
+        """one resampler call for the sessions of a pool call: their chunks at fs_in, staged as usual, become the pool call's
+        staged new samples - every entry's n_new outputs back to back in entry order, written there by the kernel"""
+        res = self.resample
+        raw = [order[e.key][1] for e in entries]
+        counts = [0 if c is None else c.numel() for c in raw]
+        if not any(counts) and not any(e.n_new for e in entries):
+            return None
+        sess = [order[e.key][0] for e in entries]
+        out = self._res_op(res._table, self.res_state, self._stage([c for c in raw if c is not None]), counts,
+                           [s.slot for s in sess], [s.n_in for s in sess], [s.n_received for s in sess],
+                           [e.n_new for e in entries],
+                           [s.n_in + n if order[e.key][2] else -1 for s, n, e in zip(sess, counts, entries)], res.L, res.M,
+                           res.n_taps, self.capacity)
+        return out if out.numel() else None
 
     def _stage(self, pieces: List[torch.Tensor]) -> Optional[torch.Tensor]:
         """the chunks of one call back to back in entry order, on the device: one host-to-device copy for the host chunks,
@@ -639,15 +894,23 @@ class LogMelPool:
         """one call for a whole tick of audio: push(chunk) for every session of `chunks` ({session: 1-D samples on the host or
         the device, 0 .. max_chunk of them}) and finish for every session of `finish` (which may also have a last chunk in
         `chunks`) -> {session: (1, n_mels, k) fp32 new frames on the device, k >= 0}, contiguous views of the calls' output
-        buffers.  Per 64 sessions: one staging copy, one swn_logmel_pool (with a low cut: swn_logmel_pool_lowcut) call (two launches).  Everything is checked first and
+        buffers.  Per 64 sessions: one staging copy, one swn_logmel_pool (with a low cut: swn_logmel_pool_lowcut) call (two launches),
+        with a resampler one swn_resample_chunk call (two launches) in front of it, whose chunks are at fs_in.  Everything is checked first and
         the counters move only after every call is enqueued: a call that raises leaves every session as it was."""
         order = self._check(chunks, finish)
         ext = self.ext
-        calls = plan_mel_push([(i, s.t0, s.n_held, s.n_frames, s.n_received, 0 if c is None else c.numel(), fin)
-                               for i, (s, c, fin) in enumerate(order)], ext.n_fft, ext.hop, ext.n_mels)
+        if self.resample is not None:
+            calls = plan_mel_push([(i, s.t0, s.n_held, s.n_frames, s.n_received, self._yield(s, c, fin), fin)
+                                   for i, (s, c, fin) in enumerate(order)], ext.n_fft, ext.hop, ext.n_mels)
+        else:
+            calls = plan_mel_push([(i, s.t0, s.n_held, s.n_frames, s.n_received, 0 if c is None else c.numel(), fin)
+                                   for i, (s, c, fin) in enumerate(order)], ext.n_fft, ext.hop, ext.n_mels)
         results: Dict[MelSession, torch.Tensor] = {}
         for entries in calls:
-            staged = self._stage([order[e.key][1] for e in entries if e.n_new > 0])
+            if self.resample is not None:
+                staged = self._resampled(entries, order)
+            else:
+                staged = self._stage([order[e.key][1] for e in entries if e.n_new > 0])
             if self.low_cut is None:
                 out = self._op(self.windows, staged, ext._table, ext.bank, [order[e.key][0].slot for e in entries],
                                [e.t0 for e in entries], [e.n_held for e in entries], [e.n_drop for e in entries],
@@ -668,7 +931,9 @@ class LogMelPool:
                 s = order[e.key][0]
                 s.t0, s.n_held = e.t0 + e.n_drop, e.n_held - e.n_drop + e.n_new
                 s.n_received, s.n_frames = s.n_received + e.n_new, e.f1
-        for s, _c, fin in order:
+        for s, c, fin in order:
+            if self.resample is not None and c is not None:
+                s.n_in += int(c.numel())
             if fin:
                 s.finished = True
         return results

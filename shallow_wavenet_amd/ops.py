@@ -48,6 +48,10 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.lowcut_chunk(taps, state, inputs, slots, resets, capacity) -> low-cut chunks (updates state)
     torch.ops.swn.logmel_pool_lowcut(win, hist, staged, tables, bank, taps, slots, t0s, n_helds, n_drops, n_news, lens, f0s, f1s,
                                      n_fft, hop, floor, linear) -> logmel_pool on raw samples (updates win and hist)
+    torch.ops.swn.resample_chunk(table, state, inputs, slots, in0s, out0s, n_outs, lens, up, down, n_taps, capacity, dense)
+                                     -> resampled chunks (updates state)
+    torch.ops.swn.resample_staged(table, state, staged, n_ins, slots, in0s, out0s, n_outs, lens, up, down, n_taps, capacity)
+                                     -> resample_chunk on chunks staged back to back, dense outputs (updates state)
     torch.ops.swn.laplace_loss(raw, ctx?, target, eps, desc, skip) -> (nll, err, samples, targets, stats)
     torch.ops.swn.laplace_loss_backward(raw, ctx?, target, eps, g_nll, g_samples?, desc, skip) -> grad_raw
 """
@@ -1628,10 +1632,112 @@ def _(win, hist, staged, tables, bank, taps, slots, t0s, n_helds, n_drops, n_new
     return win.new_empty((len(bank) * sum(max(f1 - f0, 0) for f0, f1 in zip(f0s, f1s)),), dtype=torch.float32)
 
 
+# ------------------------------------------------------------------------------------------ rational resampler
+def _resample_call(table, state, in_ptrs, n_ins, slots, in0s, out0s, n_outs, lens, up, down, n_taps, capacity, dense, what):
+    """the checks and the swn_resample_chunk call that resample_chunk and resample_staged share: entry e reads n_ins[e] floats
+    at the device address in_ptrs[e]"""
+    Lb = _lib.lib()
+    dev = table.device
+    _need_cuda(table, "the polyphase table")
+    up, down, n_taps, capacity = int(up), int(down), int(n_taps), int(capacity)
+    doubles = int(Lb.swn_resample_table_doubles(up, down, n_taps))
+    if doubles == 0:
+        raise RuntimeError(f"{what}: no table for up {up}, down {down}, n_taps {n_taps} (coprime, n_taps odd, up <= "
+                           f"{_lib.RESAMPLE_MAX_UP}, Q <= {_lib.RESAMPLE_MAX_Q})")
+    H = doubles // up - 1
+    if table.dim() != 1 or table.dtype != torch.float64 or not table.is_contiguous() or table.numel() != doubles:
+        raise RuntimeError(f"{what}: table must be {doubles} contiguous fp64 values")
+    E = len(n_ins)
+    if not (len(slots) == len(in0s) == len(out0s) == len(n_outs) == len(lens) == E):
+        raise RuntimeError(f"{what}: the inputs, slots, in0s, out0s, n_outs and lens must have one entry each")
+    if (state.device != dev or state.dtype != torch.float32 or not state.is_contiguous()
+            or state.numel() < max(1, H * capacity)):
+        raise RuntimeError(f"{what}: state must be a contiguous fp32 tensor of capacity * (Q - 1) values (at least one) on the "
+                           "device of the table")
+    counts = [int(n) for n in n_outs]
+    if min(counts, default=0) < 0:
+        raise RuntimeError(f"{what}: a negative output count")
+    if dense:
+        out, stride = torch.empty((sum(counts),), dtype=torch.float32, device=dev), 0
+    else:
+        out = torch.empty((E, max(counts, default=0)), dtype=torch.float32, device=dev)
+        stride = 4 * out.shape[1]
+    tab = (_lib.ResampleEntry * max(E, 1))()
+    at = out.data_ptr()
+    for e in range(E):
+        k = counts[e]
+        tab[e] = _lib.ResampleEntry(in_ptrs[e] if n_ins[e] else None, at if k else None, int(in0s[e]), int(out0s[e]), int(lens[e]),
+                                    n_ins[e], k, int(slots[e]), 0)
+        at += stride if stride else 4 * k
+    with _on(dev):
+        _lib.check(Lb.swn_resample_chunk(up, down, n_taps, _ptr(table), _ptr(state), capacity, tab, E, _stream(dev)), what)
+    return out
+
+
+def resample_chunk_impl(table: torch.Tensor, state: torch.Tensor, inputs: List[torch.Tensor], slots: List[int], in0s: List[int],
+                        out0s: List[int], n_outs: List[int], lens: List[int], up: int, down: int, n_taps: int, capacity: int,
+                        dense: bool) -> torch.Tensor:
+    """one call of the device resampler (swn_resample_chunk; the definition is in melspec.py): entry e takes inputs[e] (1-D fp32,
+    the session's inputs [in0s[e], in0s[e] + n)) as the next chunk of the session in slot slots[e] of `state` (at least
+    capacity * (Q - 1) fp32, the slots' last raw inputs, updated in place) and computes its outputs
+    [out0s[e], out0s[e] + n_outs[e]); lens[e] is the signal's length (the chunk then ends it), or -1 while it goes on.  An entry
+    with in0 == 0 starts from zero history.  table: the up * Q fp64 values of the polyphase table, row by row.  Any number of
+    entries.  -> dense: a flat buffer with every entry's outputs back to back in entry order; else (E, max n_out) fp32, rows
+    past an entry's own count not written."""
+    dev = table.device
+    ins = []
+    for x in inputs:
+        if x.device != dev or x.dim() != 1 or x.dtype != torch.float32:
+            raise RuntimeError("resample_chunk: every input must be a 1-D fp32 tensor on the device of the table")
+        ins.append(x.contiguous())
+    return _resample_call(table, state, [x.data_ptr() for x in ins], [x.numel() for x in ins], slots, in0s, out0s, n_outs, lens,
+                          up, down, n_taps, capacity, dense, "resample_chunk")
+
+
+resample_chunk = custom_op("swn::resample_chunk", mutates_args=("state",))(resample_chunk_impl)
+
+
+@resample_chunk.register_fake
+def _(table, state, inputs, slots, in0s, out0s, n_outs, lens, up, down, n_taps, capacity, dense):
+    if dense:
+        return table.new_empty((sum(n_outs),), dtype=torch.float32)
+    return table.new_empty((len(inputs), max(n_outs, default=0)), dtype=torch.float32)
+
+
+def resample_staged_impl(table: torch.Tensor, state: torch.Tensor, staged: Optional[torch.Tensor], n_ins: List[int],
+                         slots: List[int], in0s: List[int], out0s: List[int], n_outs: List[int], lens: List[int], up: int,
+                         down: int, n_taps: int, capacity: int) -> torch.Tensor:
+    """resample_chunk for a whole tick of a pool, with no tensor per entry: `staged` holds the entries' chunks back to back in
+    entry order (n_ins[e] fp32 samples each; None when there are none), as logmel_pool takes its new samples -> a flat buffer
+    with every entry's n_outs[e] outputs back to back in entry order: what the pool call that follows takes as `staged`."""
+    total = sum(int(n) for n in n_ins)
+    if min((int(n) for n in n_ins), default=0) < 0:
+        raise RuntimeError("resample_staged: a negative input count")
+    if total and (staged is None or staged.device != table.device or staged.dim() != 1 or staged.dtype != torch.float32
+                  or not staged.is_contiguous() or staged.numel() < total):
+        raise RuntimeError(f"resample_staged: staged must be a contiguous 1-D fp32 tensor of at least {total} samples on the device "
+                           "of the table")
+    ptrs, at = [], staged.data_ptr() if total else 0
+    for n in n_ins:
+        ptrs.append(at)
+        at += 4 * int(n)
+    return _resample_call(table, state, ptrs, [int(n) for n in n_ins], slots, in0s, out0s, n_outs, lens, up, down, n_taps,
+                          capacity, True, "resample_staged")
+
+
+resample_staged = custom_op("swn::resample_staged", mutates_args=("state",))(resample_staged_impl)
+
+
+@resample_staged.register_fake
+def _(table, state, staged, n_ins, slots, in0s, out0s, n_outs, lens, up, down, n_taps, capacity):
+    return table.new_empty((sum(n_outs),), dtype=torch.float32)
+
+
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
             "pack_decode_w16", "decode_w16", "decode_chunk_w16", "decode_pool_chunk_w16",
             "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
             "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
-            "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool", "mcep", "lowcut_chunk", "logmel_pool_lowcut")
+            "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool", "mcep", "lowcut_chunk", "logmel_pool_lowcut",
+            "resample_chunk", "resample_staged")
