@@ -307,8 +307,8 @@ int    swn_decode_pool_chunk_models(const swn_net_desc* d, const float* const* m
  * Checked before anything is launched: SWN_E_BADARG for a NULL w16_dev; SWN_E_UNSUPPORTED (text in swn_last_error_detail)
  * when `variant` does not resolve to the symmetric BL6 kernel for the net - variant 0 / 2 on a single-sample Laplace net
  * resolve to the wave-specialised kernel, so those nets need variant = 6; the stepped chain (launch-bound: weight bytes are
- * not its limit), the generic kernel, the wave-specialised kernel and multi-model pools have no bf16 form, and no precision
- * below bf16 exists. */
+ * not its limit), the generic kernel, the wave-specialised kernel and multi-model pools have no bf16 form.  One precision
+ * below bf16 exists: the *_w8 calls below. */
 size_t swn_decode_w16_bytes(const swn_net_desc* d);
 int    swn_pack_decode_w16(const swn_net_desc* d, const float* packed_dev, void* w16_dev, void* stream);
 int    swn_decode_w16(const swn_net_desc* d, const float* packed_dev, const float* cond_dev,
@@ -321,6 +321,40 @@ int    swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* packed_dev,
                                  const swn_decode_pool_entry* entries_host, int n_entries,
                                  const swn_decode_io* io, float* session_dev,
                                  void* out_dev, float* heads_dev, int variant, const void* w16_dev, void* stream);
+
+/* ---- decode with FP8 (E4M3) storage of the streamed head matrices -------------------------------------------------------
+ * The *_w8 calls are the *_w16 calls over a quarter of the fp32 bytes: the same kernel, the same tensors, the same guarantee.
+ * The definition (also in runtime.py and DESIGN 3.1):
+ *   tensors   out_skip.{l}.weight, out_1.weight and, for softmax nets, out_2.weight; everything else, biases included, fp32.
+ *   format    OCP E4M3FN: 1 sign, 4 exponent (bias 7), 3 fraction bits; subnormals in steps of 2^-9; largest finite value 448;
+ *             no infinities; codes 0x7f / 0xff are NaN and are never produced.
+ *   scale     one power of two per output row r of each matrix, chosen without a logarithm: amax = max_k |W[r][k]|; e_r = 0
+ *             if amax is 0; else frexp gives amax = m 2^x with m in [0.5, 1), and e_r = 9 - x if m <= 0.875 (448 = 0.875 x 2^9),
+ *             else 8 - x; e_r is clamped to [-100, 100].  Then amax 2^e_r <= 448 and the row uses the top binade whenever it
+ *             can (behind the lower clamp, amax >= 0.875 x 2^109, larger products saturate to +-448).
+ *   code      q[r][k] = the E4M3 value nearest to W[r][k] 2^e_r, ties to the even fraction; the sign of a zero is kept.
+ *   refusal   a weight that is not finite: SWN_E_BADARG from swn_pack_decode_w8 (which therefore waits for its stream).
+ *   weight    the dequantised W^[r][k] = q[r][k] 2^-e_r; both scalings are exact in fp32.
+ *   kernel    widens each streamed code to exactly W^ in fp32 (v_cvt_scalef32_pk_f32_fp8 with the row's 2^-e_r, exact for
+ *             powers of two) and runs the fp32 kernel's FMAs in the fp32 kernel's order: every output is BIT-IDENTICAL to
+ *             the fp32 call of the same variant on a model whose named matrices were replaced by W^.
+ *   w8_dev    swn_decode_w8_bytes() bytes = one per weight + four per row (the fp32 2^-e_r), filled by swn_pack_decode_w8
+ *             from packed_dev; refill it whenever packed_dev changes.  0 for a net the symmetric BL6 kernel does not serve.
+ * Arguments, checks and refusals are those of the *_w16 counterparts with w8_dev in place of w16_dev.
+ * swn_e4m3_table writes what the kernels' conversion makes of codes 0 .. 255 at `scale` (a power of two) into out_dev[256]. */
+size_t swn_decode_w8_bytes(const swn_net_desc* d);
+int    swn_pack_decode_w8(const swn_net_desc* d, const float* packed_dev, void* w8_dev, void* stream);
+int    swn_decode_w8(const swn_net_desc* d, const float* packed_dev, const float* cond_dev,
+                     int batch, int n_frames, int n_steps, const swn_decode_io* io,
+                     float* state_dev, void* out_dev, float* heads_dev, int variant, const void* w8_dev, void* stream);
+int    swn_decode_chunk_w8(const swn_net_desc* d, const float* packed_dev, const float* cond_dev, int batch, int n_frames,
+                           int step0, int n_steps, int flags, const swn_decode_io* io, float* session_dev,
+                           void* out_dev, float* heads_dev, int variant, const void* w8_dev, void* stream);
+int    swn_decode_pool_chunk_w8(const swn_net_desc* d, const float* packed_dev, int capacity,
+                                const swn_decode_pool_entry* entries_host, int n_entries,
+                                const swn_decode_io* io, float* session_dev,
+                                void* out_dev, float* heads_dev, int variant, const void* w8_dev, void* stream);
+int    swn_e4m3_table(float* out_dev /*256*/, float scale, void* stream);
 
 /* ---- stepped decode pool: the decode pool of the stepped multi-launch decode (variant 3: REF6-class nets) -----------
  * Every launch of the stepped chain (input layer, L gated layers, skip / out_1 [/ out_2] mat-vecs, tail) serves all

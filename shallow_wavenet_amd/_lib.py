@@ -168,6 +168,15 @@ SIGNATURES = {
                                      POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "swn_decode_pool_chunk_w16": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodePoolEntry), c_int,
                                           POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "swn_decode_w8_bytes": (c_size_t, [POINTER(NetDesc)]),
+    "swn_pack_decode_w8": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p]),
+    "swn_decode_w8": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecodeIO),
+                              c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "swn_decode_chunk_w8": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                    POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "swn_decode_pool_chunk_w8": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodePoolEntry), c_int,
+                                         POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "swn_e4m3_table": (c_int, [c_void_p, c_float, c_void_p]),
     "swn_decode_stepped_prologue_iterations": (c_int, [POINTER(NetDesc)]),
     "swn_decode_pool_stepped_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodeSteppedPoolEntry), c_int,
                                               POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -450,6 +450,19 @@ int w16_kernel_check(const SwnGeom& g, int batch, int variant, const char* where
     return SWN_E_UNSUPPORTED;
 }
 
+// ... and so do the *_w8 calls
+int w8_kernel_check(const SwnGeom& g, int batch, int variant, const char* where) {
+    const int k = resolve_kernel(g, batch, variant);
+    if (k == KSEL_BL6) return SWN_OK;
+    if (k == KSEL_BL6W)
+        swn_set_error_detail(where, "e4m3 weights run on the symmetric BL6 kernel; this net resolves to the wave-specialised "
+                                    "kernel with this variant: pass variant = 6");
+    else
+        swn_set_error_detail(where, "e4m3 weights run on the symmetric BL6 kernel only (variant 0, 2 or 6 on a net of its "
+                                    "class); the stepped and generic kernels are not served");
+    return SWN_E_UNSUPPORTED;
+}
+
 // the kernel of a pool launch over one or several fp32 models: the stepped chain runs one launch per phase for all
 // utterances at one step, so it is not served here (swn_decode_pool_stepped_chunk is)
 int pool_kernel(const SwnGeom& g, int capacity, int variant) {
@@ -469,9 +482,9 @@ int run_call(int k, const SwnDecodeCall& c) {
 
 // ---- the argument rules of the entry points (include/swn_hip.h) up to the variant: each makes the geometry, refuses what no
 // kernel takes and fills the record with what the caller passed.  The arguments keep the order of the C ABI.  What the fp32
-// and the *_w16 calls ask on top of these (the image, the kernel a variant resolves to) is in the entry points.
+// and the *_w16 / *_w8 calls ask on top of these (the image, the kernel a variant resolves to) is in the entry points.
 
-// swn_decode, swn_decode_w16 (empty buffers may be null when there is nothing to generate)
+// swn_decode, swn_decode_w16, swn_decode_w8 (empty buffers may be null when there is nothing to generate)
 int oneshot_check(SwnDecodeCall& c, const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
                   int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, void* stream_) {
     const int rc = swn_make_geom(d, &c.g);
@@ -485,7 +498,7 @@ int oneshot_check(SwnDecodeCall& c, const swn_net_desc* d, const float* packed, 
     return SWN_OK;
 }
 
-// swn_decode_chunk, swn_decode_chunk_w16
+// swn_decode_chunk, swn_decode_chunk_w16, swn_decode_chunk_w8
 int chunk_check(SwnDecodeCall& c, const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
                 int step0, int n_steps, int flags, const swn_decode_io* io, float* session, void* out, float* heads,
                 void* stream_) {
@@ -506,7 +519,7 @@ int chunk_check(SwnDecodeCall& c, const swn_net_desc* d, const float* packed, co
 // nothing to generate and no prologue to run: the session stays as it is
 bool chunk_is_idle(const SwnDecodeCall& c) { return c.n_steps == 0 && c.resume; }
 
-// swn_decode_pool_chunk, swn_decode_pool_chunk_models, swn_decode_pool_chunk_w16: the record of a streamed chunk over the
+// swn_decode_pool_chunk, swn_decode_pool_chunk_models, swn_decode_pool_chunk_w16 / _w8: the record of a streamed chunk over the
 // entries (n_steps = the most steps of an entry), the checked table in `t`; work = an entry has steps to run or begins
 int pool_check(SwnDecodeCall& c, SwnPoolTable& t, bool& work, const swn_net_desc* d, int capacity,
                const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io, float* session, void* out,
@@ -685,5 +698,51 @@ extern "C" int swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* pac
     if (rc < 0) return rc;
     if (!work) return SWN_OK;                              // every slot stays as it is
     c.packed = packed; c.w16 = w16;
+    return run_call(KSEL_BL6, c);
+}
+
+// ---- FP8 (E4M3) storage of the streamed head matrices: the rules of the *_w16 calls over the image of swn_pack_decode_w8 --
+extern "C" int swn_decode_w8(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                             int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, int variant,
+                             const void* w8, void* stream_) {
+    SwnDecodeCall c;
+    int rc = oneshot_check(c, d, packed, cond, batch, n_frames, n_steps, io, state, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (!w8) return SWN_E_BADARG;
+    rc = w8_kernel_check(c.g, batch, variant, "swn_decode_w8");
+    if (rc < 0) return rc;
+    if (n_steps == 0) return SWN_OK;
+    c.w8 = w8;
+    return run_call(KSEL_BL6, c);
+}
+
+extern "C" int swn_decode_chunk_w8(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                                   int step0, int n_steps, int flags, const swn_decode_io* io, float* session, void* out,
+                                   float* heads, int variant, const void* w8, void* stream_) {
+    SwnDecodeCall c;
+    int rc = chunk_check(c, d, packed, cond, batch, n_frames, step0, n_steps, flags, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (!w8) return SWN_E_BADARG;
+    rc = w8_kernel_check(c.g, batch, variant, "swn_decode_chunk_w8");
+    if (rc < 0) return rc;
+    if (chunk_is_idle(c)) return SWN_OK;
+    c.w8 = w8;
+    return run_call(KSEL_BL6, c);
+}
+
+extern "C" int swn_decode_pool_chunk_w8(const swn_net_desc* d, const float* packed, int capacity,
+                                        const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                        float* session, void* out, float* heads, int variant, const void* w8,
+                                        void* stream_) {
+    SwnDecodeCall c;
+    SwnPoolTable t;
+    bool work;
+    int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (!packed || !w8) return SWN_E_BADARG;
+    rc = w8_kernel_check(c.g, capacity, variant, "swn_decode_pool_chunk_w8");
+    if (rc < 0) return rc;
+    if (!work) return SWN_OK;                              // every slot stays as it is
+    c.packed = packed; c.w8 = w8;
     return run_call(KSEL_BL6, c);
 }

@@ -247,11 +247,91 @@ __device__ __forceinline__ void tiled_matvec16(__amdgpu_buffer_rsrc_t wt, const 
     }
 }
 
+// ... and over the FP8 image (W8 instantiations; layout: Bl6W8Layout).  One 16-byte load holds the four slices 4g .. 4g + 3
+// of a lane's inputs - for out_skip all 64 inputs of a layer's row quarter; w8_slices widens them to code * 2^-e_row, and
+// they are accumulated slice by slice, input by input, into the accumulators the fp32 form uses.  The rows' 2^-e sit in LDS
+// at w8_o_sc: [L][S] out_skip, [O1] out_1, [NO] out_2 - behind the kernel's carve, except for the nets that keep out_1 slices
+// resident (W1L > 0, LDS full): there the resident slices stay codes (a quarter of the fp32 slices' room, one 16-byte LDS read
+// for all four, widened at every step) and the scales follow them inside the W1L region.
+template <class T> constexpr int w8_sc_floats() { return L * T::S + T::O1 + (T::KIND == SWN_KIND_SOFTMAX ? T::NO : 0); }
+template <class T> constexpr int w8_o_sc() { return T::W1L > 0 ? T::o_w1l + (T::W1L / 4) * T::O1 * 16 : T::o_end; }
+template <class T> constexpr size_t w8_lds_bytes() {
+    static_assert(T::W1L % 4 == 0 && (T::W1L == 0 || w8_o_sc<T>() + w8_sc_floats<T>() <= T::o_end), "codes and scales fit the W1L region");
+    return T::W1L > 0 ? T::lds_bytes : T::lds_bytes + (size_t)w8_sc_floats<T>() * sizeof(float);
+}
+template <class T, int LAYER>
+__device__ __forceinline__ void skip_fma8(const float* lds, const uint4& w, int row, int hp, float& acc) {
+    float4 s[4];
+    w8_slices(w, lds[w8_o_sc<T>() + LAYER * T::S + row], s);
+#pragma unroll
+    for (int mm = 0; mm < 4; ++mm) {
+        const float4 x = *reinterpret_cast<const float4*>(lds + T::o_hcat + LAYER * H + 16 * mm + 4 * hp);
+        acc = fmaf(s[mm].x, x.x, acc); acc = fmaf(s[mm].y, x.y, acc);
+        acc = fmaf(s[mm].z, x.z, acc); acc = fmaf(s[mm].w, x.w, acc);
+    }
+}
+template <class T, int LAYER>
+__device__ __forceinline__ void skip_slice8(const float* lds, __amdgpu_buffer_rsrc_t wsk, float (&sacc)[T::S / 128]) {
+    const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
+#pragma unroll
+    for (int ps = 0; ps < T::S / 128; ++ps) {
+        const uint4 w = buf_ld4u(wsk, (unsigned)((hr + 128 * ps) * 4 + hp) * 16u, (unsigned)(LAYER * T::S) * 64u);
+        skip_fma8<T, LAYER>(lds, w, hr + 128 * ps, hp, sacc[ps]);
+    }
+}
+template <class T, int LAYER>
+__device__ __forceinline__ void skip_issue(__amdgpu_buffer_rsrc_t wsk, uint4 (&wsl)[T::S / 128]) {
+    const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
+#pragma unroll
+    for (int ps = 0; ps < T::S / 128; ++ps)
+        wsl[ps] = buf_ld4u(wsk, (unsigned)((hr + 128 * ps) * 4 + hp) * 16u, (unsigned)(LAYER * T::S) * 64u);
+}
+template <class T, int LAYER>
+__device__ __forceinline__ void skip_consume(const float* lds, const uint4 (&wsl)[T::S / 128], float (&sacc)[T::S / 128]) {
+    const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
+#pragma unroll
+    for (int ps = 0; ps < T::S / 128; ++ps) skip_fma8<T, LAYER>(lds, wsl[ps], hr + 128 * ps, hp, sacc[ps]);
+}
+// rows x NI mat-vec over image section [NI / 64][rows][4][4 words]; sc: the rows' 2^-e in LDS.  a0 takes the even slices,
+// a1 the odd ones, each in rising order, as below
+template <int ROWS, int NI>
+__device__ __forceinline__ void tiled_matvec8(__amdgpu_buffer_rsrc_t wt, const float* bias, const float* sc, const float* x,
+                                              float* y, bool relu) {
+    static_assert(NI % 64 == 0, "whole image slices");
+    const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
+#pragma unroll
+    for (int ps = 0; ps < ROWS / 128; ++ps) {
+        const int row = hr + 128 * ps;
+        const float scale = sc[row];
+        float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+        for (int g = 0; g < NI / 64; ++g) {
+            const uint4 w = buf_ld4u(wt, (unsigned)(row * 4 + hp) * 16u, (unsigned)(g * ROWS) * 64u);
+            float4 s[4];
+            w8_slices(w, scale, s);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float4 xv = *reinterpret_cast<const float4*>(x + 16 * (4 * g + k) + 4 * hp);
+                float& acc = (k & 1) ? a1 : a0;
+                acc = fmaf(s[k].x, xv.x, acc); acc = fmaf(s[k].y, xv.y, acc);
+                acc = fmaf(s[k].z, xv.z, acc); acc = fmaf(s[k].w, xv.w, acc);
+            }
+        }
+        float v = sum4(a0 + a1);
+        if (hp == 0) {
+            v += bias[row];
+            y[row] = relu ? fmaxf(v, 0.f) : v;
+        }
+        if (ps + 1 < ROWS / 128) __builtin_amdgcn_sched_barrier(0);     // <= 4 loads (one pass of rows) in flight
+    }
+}
+
 // out_skip slice of one layer, 4 lanes per row, weights streamed from the lane-tiled copy.
-template <class T, int LAYER, bool W16 = false>
+template <class T, int LAYER, int WK = WK_F32>
 __device__ __forceinline__ void skip_slice(const float* lds, __amdgpu_buffer_rsrc_t wsk2,
                                            float (&sacc)[T::S / 128]) {
-    if constexpr (W16) { skip_slice16<T, LAYER>(lds, wsk2, sacc); return; }
+    if constexpr (WK == WK_BF16) { skip_slice16<T, LAYER>(lds, wsk2, sacc); return; }
+    if constexpr (WK == WK_E4M3) { skip_slice8<T, LAYER>(lds, wsk2, sacc); return; }
     constexpr int layer = LAYER;
     const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
 #pragma unroll
@@ -295,10 +375,11 @@ __device__ __forceinline__ void skip_consume(const float* lds, const float4 (&ws
 }
 
 // rows x NI mat-vec, 4 lanes per row, lane-tiled weights [NI/16][rows][4][4] streamed from L2.
-template <int ROWS, int NI, bool W16 = false>
+template <int ROWS, int NI, int WK = WK_F32>
 __device__ __forceinline__ void tiled_matvec(__amdgpu_buffer_rsrc_t wt, const float* bias,
-                                             const float* x, float* y, bool relu) {
-    if constexpr (W16) { tiled_matvec16<ROWS, NI>(wt, bias, x, y, relu); return; }
+                                             const float* x, float* y, bool relu, [[maybe_unused]] const float* sc = nullptr) {
+    if constexpr (WK == WK_BF16) { tiled_matvec16<ROWS, NI>(wt, bias, x, y, relu); return; }
+    if constexpr (WK == WK_E4M3) { tiled_matvec8<ROWS, NI>(wt, bias, sc, x, y, relu); return; }
     const int hr = threadIdx.x >> 2, hp = threadIdx.x & 3;
 #pragma unroll
     for (int ps = 0; ps < ROWS / 128; ++ps) {
@@ -322,11 +403,13 @@ __device__ __forceinline__ void tiled_matvec(__amdgpu_buffer_rsrc_t wt, const fl
     }
 }
 
-template <bool POOL, bool MODELS, bool W16 = false> struct B6ArgsOf { using type = Bl6Args; };
+template <bool POOL, bool MODELS, int WK = WK_F32> struct B6ArgsOf { using type = Bl6Args; };
 template <> struct B6ArgsOf<true, false> { using type = Bl6PoolArgs; };
 template <> struct B6ArgsOf<true, true> { using type = Bl6PoolModelsArgs; };
-template <> struct B6ArgsOf<false, false, true> { using type = Bl6W16Args; };
-template <> struct B6ArgsOf<true, false, true> { using type = Bl6PoolW16Args; };
+template <> struct B6ArgsOf<false, false, WK_BF16> { using type = Bl6W16Args; };
+template <> struct B6ArgsOf<true, false, WK_BF16> { using type = Bl6PoolW16Args; };
+template <> struct B6ArgsOf<false, false, WK_E4M3> { using type = Bl6W8Args; };
+template <> struct B6ArgsOf<true, false, WK_E4M3> { using type = Bl6PoolW8Args; };
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6Args& launch, const Bl6Args&) { return launch; }
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, const Bl6Args& entry) { return entry; }
 
@@ -337,12 +420,14 @@ __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, con
 // window come from the session instead of the prologue, and they go back to it at the end.  The step itself is the same code.
 // POOL (with STREAM): one entry of a decode pool (swn_decode_pool_chunk); `a` holds the workgroup's entry as a batch-1 chunk
 // (swn_pool_entry_args), b = 0.  MODELS (with POOL): the entry's weights are those of its model (SwnPoolModels).
-// W16 (with EXT, without MODELS): out_skip, out_1 and the softmax out_2 stream from the bf16 image ka.w16 instead of the fp32
-// lane-tiled copies, and the LDS-resident out_1 slices are widened from it; every other load and every FMA is the fp32 code.
-template <class T, bool STREAM = false, bool POOL = false, bool MODELS = false, bool W16 = false>
-__global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL, MODELS, W16>::type ka) {
+// WK = WK_BF16 (W16; with EXT, without MODELS): out_skip, out_1 and the softmax out_2 stream from the bf16 image ka.w16 instead
+// of the fp32 lane-tiled copies, and the LDS-resident out_1 slices are widened from it; every other load and every FMA is the
+// fp32 code.  WK = WK_E4M3 (W8): the same over the FP8 image ka.w8, whose row scales are copied into LDS behind the carve.
+template <class T, bool STREAM = false, bool POOL = false, bool MODELS = false, int WK = WK_F32>
+__global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL, MODELS, WK>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    static_assert(!W16 || (T::EXT && !MODELS), "bf16 weights: extended single-model instantiations only");
+    constexpr bool W16 = WK == WK_BF16, W8 = WK == WK_E4M3;
+    static_assert(WK == WK_F32 || (T::EXT && !MODELS), "bf16 / e4m3 weights: extended single-model instantiations only");
     Bl6Args pa;                                            // POOL: this workgroup's entry as a batch-1 chunk
     if constexpr (POOL) {
         static_assert(STREAM && T::EXT, "pools run the streamed extended mode");
@@ -388,8 +473,19 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
                 const unsigned w = w1i[(mm >> 1) * T::O1 * 16 + e % (T::O1 * 16)];
                 lds[T::o_w1l + e] = (mm & 1) ? w16_hi(w) : w16_lo(w);
             }
+        } else if constexpr (W8) {
+            // ... or stay codes: the first W1L / 4 image slices as they lie in the image (bit patterns, not numbers)
+            const unsigned* w1i = reinterpret_cast<const unsigned*>(
+                static_cast<const char*>(ka.w8) + w8_layout(S, T::O1, T::NO, false).w1);
+            unsigned* dst = reinterpret_cast<unsigned*>(lds + T::o_w1l);
+            for (int e = tid; e < (T::W1L / 4) * T::O1 * 16; e += NT) dst[e] = w1i[e];
         } else
         for (int e = tid; e < T::W1L * T::O1 * 16; e += NT) lds[T::o_w1l + e] = P[a.y.w12 + e];
+    }
+    if constexpr (W8) {   // the rows' 2^-e: the three scale sections of the image are one run of floats
+        const float* sc = reinterpret_cast<const float*>(
+            static_cast<const char*>(ka.w8) + w8_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX).ssk);
+        for (int e = tid; e < w8_sc_floats<T>(); e += NT) lds[w8_o_sc<T>() + e] = sc[e];
     }
     // conditioning frames are copied 16 B per lane through a buffer resource (32-bit offsets)
     const __amdgpu_buffer_rsrc_t condr =
@@ -580,15 +676,18 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
 
     // ---- generation (cswnv_shift1.py:348-402 / dswnv.py:338-374)
     // W16: the same three names over the sections of the bf16 image (half the bytes)
-    constexpr unsigned WB = W16 ? 2 : sizeof(float);
+    // W8: over the code sections of the FP8 image (a quarter)
+    constexpr unsigned WB = W8 ? 1 : W16 ? 2 : sizeof(float);
     [[maybe_unused]] const Bl6W16Layout y16 = w16_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX);
-    auto wsrc = [&](size_t f32_off, [[maybe_unused]] size_t w16_off) -> const void* {
+    [[maybe_unused]] const Bl6W8Layout y8 = w8_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX);
+    auto wsrc = [&](size_t f32_off, [[maybe_unused]] size_t w16_off, [[maybe_unused]] size_t w8_off) -> const void* {
         if constexpr (W16) return static_cast<const char*>(ka.w16) + w16_off;
+        else if constexpr (W8) return static_cast<const char*>(ka.w8) + w8_off;
         else return P + f32_off;
     };
-    const __amdgpu_buffer_rsrc_t wsk2 = make_rsrc(wsrc(a.y.wsk2, y16.wsk), (unsigned)(L * S * 64 * WB));
-    const __amdgpu_buffer_rsrc_t w12 = make_rsrc(wsrc(a.y.w12, y16.w1), (unsigned)(T::O1 * S * WB));
-    const __amdgpu_buffer_rsrc_t w22 = make_rsrc(wsrc(a.y.w22, y16.w2), (unsigned)(T::NO * T::O1 * WB));
+    const __amdgpu_buffer_rsrc_t wsk2 = make_rsrc(wsrc(a.y.wsk2, y16.wsk, y8.wsk), (unsigned)(L * S * 64 * WB));
+    const __amdgpu_buffer_rsrc_t w12 = make_rsrc(wsrc(a.y.w12, y16.w1, y8.w1), (unsigned)(T::O1 * S * WB));
+    const __amdgpu_buffer_rsrc_t w22 = make_rsrc(wsrc(a.y.w22, y16.w2, y8.w2), (unsigned)(T::NO * T::O1 * WB));
 #ifdef SWN_STAMP
     // diagnostic build only (tools/stamp_decode.py): per-phase cycle sums of wave 0 leave the kernel
     // through the `heads` debug buffer, which this build writes nothing else into.
@@ -618,7 +717,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
         if constexpr (S == 128 && SEG <= 2) {
 #endif
             // out_skip weights are issued one phase ahead and stay in flight across the LDS-only barrier
-            typename std::conditional<W16, uint4[2], float4[4]>::type wsl;
+            typename std::conditional<W8, uint4[1], typename std::conditional<W16, uint4[2], float4[4]>::type>::type wsl;
             layer_phase<T, 0, SEG>(lds, wreg[0], q0, wj, pb); skip_issue<T, 0>(wsk2, wsl); lds_barrier(); STAMP(1)
             layer_phase<T, 1, SEG>(lds, wreg[1], q0, wj, pb); skip_consume<T, 0>(lds, wsl, sacc); skip_issue<T, 1>(wsk2, wsl); lds_barrier(); STAMP(2)
             layer_phase<T, 2, SEG>(lds, wreg[2], q0, wj, pb); skip_consume<T, 1>(lds, wsl, sacc); skip_issue<T, 2>(wsk2, wsl); lds_barrier(); STAMP(3)
@@ -628,7 +727,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
             skip_consume<T, 5>(lds, wsl, sacc);
 #ifdef SWN_W1PREF
             // out_1 weights: issued now, they fly during the reduction and the barrier
-            if constexpr (!W16) {
+            if constexpr (WK == WK_F32) {
                 const int hr = tid >> 2, hp = tid & 3;
 #pragma unroll
                 for (int mm = 0; mm < 8; ++mm)
@@ -637,12 +736,12 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
 #endif
         } else {
             layer_phase<T, 0, SEG>(lds, wreg[0], q0, wj, pb); lds_barrier(); STAMP(1)
-            layer_phase<T, 1, SEG>(lds, wreg[1], q0, wj, pb); skip_slice<T, 0, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(2)
-            layer_phase<T, 2, SEG>(lds, wreg[2], q0, wj, pb); skip_slice<T, 1, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(3)
-            layer_phase<T, 3, SEG>(lds, wreg[3], q0, wj, pb); skip_slice<T, 2, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(4)
-            layer_phase<T, 4, SEG>(lds, wreg[4], q0, wj, pb); skip_slice<T, 3, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(5)
-            layer_phase<T, 5, SEG>(lds, wreg[5], q0, wj, pb); skip_slice<T, 4, W16>(lds, wsk2, sacc); lds_barrier(); STAMP(6)
-            skip_slice<T, 5, W16>(lds, wsk2, sacc);
+            layer_phase<T, 1, SEG>(lds, wreg[1], q0, wj, pb); skip_slice<T, 0, WK>(lds, wsk2, sacc); lds_barrier(); STAMP(2)
+            layer_phase<T, 2, SEG>(lds, wreg[2], q0, wj, pb); skip_slice<T, 1, WK>(lds, wsk2, sacc); lds_barrier(); STAMP(3)
+            layer_phase<T, 3, SEG>(lds, wreg[3], q0, wj, pb); skip_slice<T, 2, WK>(lds, wsk2, sacc); lds_barrier(); STAMP(4)
+            layer_phase<T, 4, SEG>(lds, wreg[4], q0, wj, pb); skip_slice<T, 3, WK>(lds, wsk2, sacc); lds_barrier(); STAMP(5)
+            layer_phase<T, 5, SEG>(lds, wreg[5], q0, wj, pb); skip_slice<T, 4, WK>(lds, wsk2, sacc); lds_barrier(); STAMP(6)
+            skip_slice<T, 5, WK>(lds, wsk2, sacc);
         }
         {
             const int hr = tid >> 2, hp = tid & 3;
@@ -660,7 +759,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
 #ifndef SWN_W1PREF
         if constexpr (false) {
 #else
-        if constexpr (S == 128 && SEG <= 2 && !W16) {
+        if constexpr (S == 128 && SEG <= 2 && WK == WK_F32) {
 #endif
             const int hr = tid >> 2, hp = tid & 3;
             float a0 = 0.f, a1 = 0.f;
@@ -681,6 +780,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
                 constexpr int NG = S / 16 - T::W1L;
                 const int hr = tid >> 2, hp = tid & 3;
                 float4 wg[NG];
+                [[maybe_unused]] float4 wl[4];                       // W8: the resident slices, widened from their codes
                 if constexpr (W16) {
                     static_assert(T::W1L % 2 == 0 && NG % 2 == 0, "whole image slices on either side");
 #pragma unroll
@@ -689,13 +789,21 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
                         wg[2 * g] = make_float4(w16_lo(w.x), w16_lo(w.y), w16_lo(w.z), w16_lo(w.w));
                         wg[2 * g + 1] = make_float4(w16_hi(w.x), w16_hi(w.y), w16_hi(w.z), w16_hi(w.w));
                     }
+                } else if constexpr (W8) {
+                    static_assert(T::W1L == 4 && NG == 4, "one image slice on either side");
+                    const uint4 w = buf_ld4u(w12, (unsigned)(hr * 4 + hp) * 16u, (unsigned)((T::W1L / 4) * T::O1) * 64u);
+                    const float scale = lds[w8_o_sc<T>() + L * S + hr];
+                    w8_slices(*reinterpret_cast<const uint4*>(lds + T::o_w1l + (hr * 4 + hp) * 4), scale, wl);
+                    w8_slices(w, scale, wg);
                 } else
 #pragma unroll
                 for (int mm = 0; mm < NG; ++mm) wg[mm] = buf_ld4(w12, (unsigned)(hr * 4 + hp) * 16u, (unsigned)((T::W1L + mm) * T::O1) * 64u);
                 float a0 = 0.f, a1 = 0.f;
 #pragma unroll
                 for (int mm = 0; mm < T::W1L; ++mm) {
-                    const float4 w0 = *reinterpret_cast<const float4*>(lds + T::o_w1l + ((mm * T::O1 + hr) * 4 + hp) * 4);
+                    float4 w0;
+                    if constexpr (W8) w0 = wl[mm & 3];
+                    else w0 = *reinterpret_cast<const float4*>(lds + T::o_w1l + ((mm * T::O1 + hr) * 4 + hp) * 4);
                     const float4 x0 = *reinterpret_cast<const float4*>(lds + T::o_skip + 16 * mm + 4 * hp);
                     float& acc = (mm & 1) ? a1 : a0;
                     acc = fmaf(w0.x, x0.x, acc); acc = fmaf(w0.y, x0.y, acc); acc = fmaf(w0.z, x0.z, acc); acc = fmaf(w0.w, x0.w, acc);
@@ -709,7 +817,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
                 const float v = sum4(a0 + a1);
                 if (hp == 0) lds[T::o_o1 + hr] = fmaxf(v + lds[T::o_bias + S + hr], 0.f);
             } else {
-                tiled_matvec<T::O1, S, W16>(w12, lds + T::o_bias + S, lds + T::o_skip, lds + T::o_o1, true);
+                tiled_matvec<T::O1, S, WK>(w12, lds + T::o_bias + S, lds + T::o_skip, lds + T::o_o1, true, lds + w8_o_sc<T>() + L * S);
             }
         }
         lds_barrier(); STAMP(8)
@@ -766,7 +874,8 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
         } else {
             constexpr int Q = T::Q;
             constexpr int QL = Q > 0 ? (Q + 63) / 64 : 1;     // classes per lane (this branch is also compiled for Laplace nets)
-            tiled_matvec<T::NO, T::O1, W16>(w22, lds + T::o_bias + S + T::O1, lds + T::o_o1, lds + T::o_o2, false);
+            tiled_matvec<T::NO, T::O1, WK>(w22, lds + T::o_bias + S + T::O1, lds + T::o_o1, lds + T::o_o2, false,
+                                           lds + w8_o_sc<T>() + L * S + T::O1);
             lds_barrier();
             if (HEADS_ON && a.heads)
                 for (int e = tid; e < T::NO; e += NT) a.heads[((size_t)b * a.n_steps + i) * T::NO + e] = lds[T::o_o2 + e];
@@ -880,36 +989,97 @@ __global__ __launch_bounds__(256) void pack_w16_kernel(const W16PackArgs a) {
     }
 }
 
+// The FP8 image (Bl6W8Layout) from the same three lane-tiled copies: one thread per output row of a matrix finds the row's
+// largest magnitude, derives e_r from its exponent and fraction (frexp without a logarithm: amax = m 2^x, m in [0.5, 1);
+// e_r = 9 - x if m <= 0.875, else 8 - x, clamped to [-100, 100]; 0 for a zero row), writes 2^-e_r and the row's codes.
+// A section holds `mats` matrices of `ns` slices of 16 inputs and `rows` rows (out_skip: L matrices of 4 slices).
+__device__ __forceinline__ unsigned e4m3_rne(float v) {      // nearest E4M3FN code, ties to even; the sign of a zero is kept
+    const unsigned sign = (__builtin_bit_cast(unsigned, v) >> 24) & 0x80u;
+    const float a = fabsf(v);
+    if (!(a <= 448.f)) return sign | 0x7eu;                 // only behind the lower clamp of e_r: saturate, never a NaN code
+    if (a < 0.015625f) return sign | (unsigned)rintf(a * 512.f);          // subnormal steps of 2^-9; 8 = the code of 2^-6
+    const unsigned u = __builtin_bit_cast(unsigned, a);
+    return sign | (((u + 0x7ffffu + ((u >> 20) & 1u)) >> 20) - (120u << 3));
+}
+struct W8PackArgs {
+    const float* src[3];       // wsk2, w12, w22 of the packed buffer
+    unsigned* dst[3];          // code sections
+    float* sc[3];              // scale sections
+    int mats[3], ns[3], rows[3];   // mats = 0: no such section
+    int* bad;                  // set when a weight is not finite
+};
+__global__ __launch_bounds__(256) void pack_w8_kernel(const W8PackArgs a) {
+    const int sec = blockIdx.y, idx = blockIdx.x * 256 + threadIdx.x;
+    const int rows = a.rows[sec], ns = a.ns[sec];
+    if (idx >= a.mats[sec] * rows) return;
+    const int m = idx / rows, r = idx % rows;
+    const float* src = a.src[sec] + ((size_t)m * ns * rows + r) * 16;
+    unsigned amax = 0;                                      // bits of the largest magnitude (ordered as the values are)
+    for (int sl = 0; sl < ns; ++sl)
+        for (int k = 0; k < 16; ++k) {
+            const unsigned u = __builtin_bit_cast(unsigned, src[(size_t)sl * rows * 16 + k]) & 0x7fffffffu;
+            amax = u > amax ? u : amax;
+        }
+    if (amax >= 0x7f800000u) { *a.bad = 1; return; }
+    int e = 0;
+    if (amax != 0) {
+        const int x = (int)(amax >> 23) - 126;              // (a subnormal's true x is smaller still: clamped either way)
+        e = ((amax & 0x7fffffu) <= 0x600000u ? 9 : 8) - x;
+        e = e < -100 ? -100 : e > 100 ? 100 : e;
+    }
+    const float up = __builtin_bit_cast(float, (unsigned)(127 + e) << 23);
+    a.sc[sec][idx] = __builtin_bit_cast(float, (unsigned)(127 - e) << 23);
+    unsigned* dst = a.dst[sec] + ((size_t)m * (ns / 4) * rows + r) * 16;
+    for (int g = 0; g < ns / 4; ++g)
+        for (int k = 0; k < 16; ++k) {
+            unsigned w = 0;
+            for (int s = 0; s < 4; ++s) w |= e4m3_rne(src[(size_t)(4 * g + s) * rows * 16 + k] * up) << (8 * s);
+            dst[(size_t)g * rows * 16 + k] = w;
+        }
+}
+// what w8_pair makes of every code: code c sits in byte c & 3 of a word whose other bytes hold other codes
+__global__ __launch_bounds__(256) void e4m3_table_kernel(float* out, float scale) {
+    const unsigned c = threadIdx.x, pos = c & 3u;
+    const unsigned w = (((~c) & 0xffu) * 0x01010101u & ~(0xffu << (8 * pos))) | (c << (8 * pos));
+    float f[4];
+    w8_word(w, scale, f);
+    out[c] = pos == 0 ? f[0] : pos == 1 ? f[1] : pos == 2 ? f[2] : f[3];
+}
+
 // the one-shot decode and the streamed chunk, one workgroup per utterance; `sess` holds sess_floats per utterance.  The
 // classic instantiation takes what it was written for (host-drawn noise, no dump, zero seed, fp32 weights); everything else
 // is the extended one's.
-template <bool W16>
+template <int WK>
 int launch_utts(const SwnDecodeCall& c, const char* where) {
-    typename B6ArgsOf<false, false, W16>::type a;
+    typename B6ArgsOf<false, false, WK>::type a;
     fill_args(a, c);
-    if constexpr (W16) a.w16 = c.w16;
+    if constexpr (WK == WK_BF16) a.w16 = c.w16;
+    if constexpr (WK == WK_E4M3) a.w8 = c.w8;
     return with_tr(c.g, [&](auto t) {
         using T = decltype(t);
         using X = typename T::Ext;
-        static_assert(T::lds_bytes <= 160 * 1024 && X::lds_bytes <= 160 * 1024, "LDS budget");
-        if (c.stream) return launch_kernel(decode_bl6_kernel<X, true, false, false, W16>, X::lds_bytes, a.B, a, c.hip_stream, where);
-        if constexpr (!W16)
+        static_assert(T::lds_bytes <= 160 * 1024 && X::lds_bytes <= 160 * 1024 && w8_lds_bytes<X>() <= 160 * 1024, "LDS budget");
+        constexpr size_t xlds = WK == WK_E4M3 ? w8_lds_bytes<X>() : X::lds_bytes;   // W8: the row scales behind the carve
+        if (c.stream) return launch_kernel(decode_bl6_kernel<X, true, false, false, WK>, xlds, a.B, a, c.hip_stream, where);
+        if constexpr (WK == WK_F32)
             if (!wants_ext(a)) return launch_kernel(decode_bl6_kernel<T>, T::lds_bytes, a.B, a, c.hip_stream, where);
-        return launch_kernel(decode_bl6_kernel<X, false, false, false, W16>, X::lds_bytes, a.B, a, c.hip_stream, where);
+        return launch_kernel(decode_bl6_kernel<X, false, false, false, WK>, xlds, a.B, a, c.hip_stream, where);
     });
 }
 
 // one pool launch over the checked entry table: one workgroup per entry, sessions [capacity][sess_floats]
-template <bool MODELS, bool W16>
+template <bool MODELS, int WK>
 int launch_pool(const SwnDecodeCall& c, const char* where) {
-    typename B6ArgsOf<true, MODELS, W16>::type p;
+    typename B6ArgsOf<true, MODELS, WK>::type p;
     fill_args(p.c, c);
     p.t = *c.pool;
     if constexpr (MODELS) p.m = *c.models;
-    if constexpr (W16) p.w16 = c.w16;
+    if constexpr (WK == WK_BF16) p.w16 = c.w16;
+    if constexpr (WK == WK_E4M3) p.w8 = c.w8;
     return with_tr(c.g, [&](auto tr) {
         using T = typename decltype(tr)::Ext;
-        return launch_kernel(decode_bl6_kernel<T, true, true, MODELS, W16>, T::lds_bytes, c.batch, p, c.hip_stream, where);
+        constexpr size_t lds = WK == WK_E4M3 ? w8_lds_bytes<T>() : T::lds_bytes;
+        return launch_kernel(decode_bl6_kernel<T, true, true, MODELS, WK>, lds, c.batch, p, c.hip_stream, where);
     });
 }
 
@@ -953,12 +1123,76 @@ extern "C" int swn_pack_decode_w16(const swn_net_desc* d, const float* packed, v
     return swn_launch_status("swn_pack_decode_w16");
 }
 
+// ---- FP8 (E4M3) storage of the streamed head matrices (swn_decode_w8 / swn_decode_chunk_w8 / swn_decode_pool_chunk_w8)
+extern "C" size_t swn_decode_w8_bytes(const swn_net_desc* d) {
+    SwnGeom g;
+    if (swn_make_geom(d, &g) < 0) return 0;
+    size_t n = 0;
+    with_tr(g, [&](auto t) {
+        using T = decltype(t);
+        n = w8_layout(T::S, T::O1, T::NO, T::KIND == SWN_KIND_SOFTMAX).total;
+        return SWN_OK;
+    });
+    return n;
+}
+
+// (the one call of the family that waits for its stream: a weight that is not finite is reported as SWN_E_BADARG)
+extern "C" int swn_pack_decode_w8(const swn_net_desc* d, const float* packed, void* w8, void* stream_) {
+    SwnGeom g; int rc = swn_make_geom(d, &g);
+    if (rc < 0) return rc;
+    if (!packed || !w8) return SWN_E_BADARG;
+    if (swn_decode_w8_bytes(d) == 0) {
+        swn_set_error_detail("swn_pack_decode_w8", "e4m3 weights exist for the nets the symmetric BL6 kernel serves only");
+        return SWN_E_UNSUPPORTED;
+    }
+    SwnLayout y;
+    swn_make_layout(&g, &y);
+    const bool soft = g.kind == SWN_KIND_SOFTMAX;
+    const Bl6W8Layout y8 = w8_layout(g.S, g.O1, g.NO, soft);
+    char* img = static_cast<char*>(w8);
+    hipStream_t st = (hipStream_t)stream_;
+    W8PackArgs a;
+    a.src[0] = packed + y.wsk2; a.dst[0] = reinterpret_cast<unsigned*>(img + y8.wsk); a.sc[0] = reinterpret_cast<float*>(img + y8.ssk);
+    a.src[1] = packed + y.w12;  a.dst[1] = reinterpret_cast<unsigned*>(img + y8.w1);  a.sc[1] = reinterpret_cast<float*>(img + y8.s1);
+    a.src[2] = packed + y.w22;  a.dst[2] = reinterpret_cast<unsigned*>(img + y8.w2);  a.sc[2] = reinterpret_cast<float*>(img + y8.s2);
+    a.mats[0] = L; a.ns[0] = 4; a.rows[0] = g.S;
+    a.mats[1] = 1; a.ns[1] = g.S / 16; a.rows[1] = g.O1;
+    a.mats[2] = soft ? 1 : 0; a.ns[2] = g.O1 / 16; a.rows[2] = g.NO;
+    (void)hipGetLastError();
+    if (hipMalloc(reinterpret_cast<void**>(&a.bad), sizeof(int)) != hipSuccess) return SWN_E_LAUNCH;
+    int bad = 0;
+    bool ok = hipMemsetAsync(a.bad, 0, sizeof(int), st) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(pack_w8_kernel, dim3((L * g.S + 255) / 256, 3), dim3(256), 0, st, a);
+        rc = swn_launch_status("swn_pack_decode_w8");
+        ok = hipMemcpyAsync(&bad, a.bad, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    (void)hipFree(a.bad);
+    if (!ok) return SWN_E_LAUNCH;
+    if (rc < 0) return rc;
+    if (bad) {
+        swn_set_error_detail("swn_pack_decode_w8", "a weight of out_skip / out_1 / out_2 is not finite");
+        return SWN_E_BADARG;
+    }
+    return SWN_OK;
+}
+
+extern "C" int swn_e4m3_table(float* out, float scale, void* stream_) {
+    if (!out) return SWN_E_BADARG;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(e4m3_table_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream_, out, scale);
+    return swn_launch_status("swn_e4m3_table");
+}
+
 // a checked call on the symmetric kernel (swn_decode.hip)
 int swn_decode_bl6_run(const SwnDecodeCall& c) {
-    if (c.pool && c.w16) return launch_pool<false, true>(c, "swn_decode_pool_chunk_w16(bl6)");
-    if (c.pool && c.models) return launch_pool<true, false>(c, "swn_decode_pool_chunk_models(bl6)");
-    if (c.pool) return launch_pool<false, false>(c, "swn_decode_pool_chunk(bl6)");
-    return c.w16 ? launch_utts<true>(c, "swn_decode_w16(bl6)") : launch_utts<false>(c, "swn_decode(bl6)");
+    if (c.pool && c.w8) return launch_pool<false, WK_E4M3>(c, "swn_decode_pool_chunk_w8(bl6)");
+    if (c.pool && c.w16) return launch_pool<false, WK_BF16>(c, "swn_decode_pool_chunk_w16(bl6)");
+    if (c.pool && c.models) return launch_pool<true, WK_F32>(c, "swn_decode_pool_chunk_models(bl6)");
+    if (c.pool) return launch_pool<false, WK_F32>(c, "swn_decode_pool_chunk(bl6)");
+    if (c.w8) return launch_utts<WK_E4M3>(c, "swn_decode_w8(bl6)");
+    return c.w16 ? launch_utts<WK_BF16>(c, "swn_decode_w16(bl6)") : launch_utts<WK_F32>(c, "swn_decode(bl6)");
 }
 
 // streamed decode (swn_decode_chunk): per-utterance session floats of the symmetric kernel, 0 = not a BL6-class net

@@ -75,6 +75,39 @@ inline __host__ __device__ Bl6W16Layout w16_layout(int S, int O1, int NO, bool s
     return y;
 }
 
+// FP8 (OCP E4M3FN) storage of the same matrices (swn_decode_w8 and its chunk / pool forms), likewise in structs and
+// instantiations of its own (W8).  Contract (include/swn_hip.h): per output row r of each matrix one power of two 2^e_r that
+// brings the row's largest magnitude into the top binade of E4M3 (<= 448), code = nearest E4M3 value of W 2^e_r, ties to even;
+// the kernel widens a code to exactly code * 2^-e_r in fp32 (w8_pair) and runs the fp32 kernel's FMAs in the fp32 kernel's order.
+struct Bl6W8Args : Bl6Args {
+    const void* w8;
+};
+struct Bl6PoolW8Args : Bl6PoolArgs {
+    const void* w8;
+};
+static_assert(sizeof(Bl6PoolW8Args) <= 4096, "kernel arguments are limited to 4 KB");
+// The image (swn_pack_decode_w8): the W16 image with four slices of 16 inputs folded into a word instead of two - section
+// [NS / 4][rows][4 lanes][4 words], byte s of word j of a lane = code(slice 4g + s, input 4 lane + j), so a lane's 16-byte load
+// carries what four of its fp32 loads carry and v_cvt_scalef32_pk_f32_fp8 widens bytes (0, 1) or (2, 3) of a word at once.
+// Behind the three code sections: one fp32 2^-e_r per row, [L][S] for out_skip, [O1] for out_1, (softmax) [NO] for out_2; the
+// kernel keeps them in LDS behind its carve (T::o_end).  Byte offsets; w2 / s2 are empty for Laplace nets.
+struct Bl6W8Layout {
+    size_t wsk, w1, w2, ssk, s1, s2, total;
+};
+inline __host__ __device__ Bl6W8Layout w8_layout(int S, int O1, int NO, bool softmax) {
+    Bl6W8Layout y;
+    y.wsk = 0;
+    y.w1 = y.wsk + (size_t)L * S * 64;
+    y.w2 = y.w1 + (size_t)O1 * S;
+    y.ssk = y.w2 + (softmax ? (size_t)NO * O1 : 0);
+    y.s1 = y.ssk + (size_t)L * S * 4;
+    y.s2 = y.s1 + (size_t)O1 * 4;
+    y.total = y.s2 + (softmax ? (size_t)NO * 4 : 0);
+    return y;
+}
+// storage of the streamed head matrices, the last template argument of the symmetric kernel
+enum : int { WK_F32 = 0, WK_BF16 = 1, WK_E4M3 = 2 };
+
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int pow2ceil(int x) { int r = 1; while (r < x) r <<= 1; return r; }
 constexpr int r4(int x) { return (x + 3) & ~3; }
@@ -93,6 +126,26 @@ __device__ __forceinline__ uint4 buf_ld4u(__amdgpu_buffer_rsrc_t r, unsigned vof
 }
 __device__ __forceinline__ float w16_lo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float w16_hi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
+// two E4M3 codes of a word of the FP8 image - bytes (0, 1), or (2, 3) with HI - as code * scale in fp32; scale is the row's
+// power of two 2^-e_r, for which the scaled conversion is exact (tests: swn_e4m3_table against the format's definition).
+// Every widening of the W8 instantiations, the resident out_1 slices and swn_e4m3_table included, goes through this helper.
+template <bool HI>
+__device__ __forceinline__ float2 w8_pair(unsigned w, float scale) {
+    const auto v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(w, scale, HI);
+    return make_float2(v[0], v[1]);
+}
+// the four slices of word w: f[s] = byte s
+__device__ __forceinline__ void w8_word(unsigned w, float scale, float (&f)[4]) {
+    const float2 lo = w8_pair<false>(w, scale), hi = w8_pair<true>(w, scale);
+    f[0] = lo.x; f[1] = lo.y; f[2] = hi.x; f[3] = hi.y;
+}
+// a 16-byte load of the image as four fp32 slices of four inputs: s[k] = slice 4g + k
+__device__ __forceinline__ void w8_slices(const uint4& w, float scale, float4 (&s)[4]) {
+    float x[4], y[4], z[4], q[4];
+    w8_word(w.x, scale, x); w8_word(w.y, scale, y); w8_word(w.z, scale, z); w8_word(w.w, scale, q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = make_float4(x[k], y[k], z[k], q[k]);
+}
 
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {

@@ -17,7 +17,8 @@ Device-drawn sampling noise (`--noise_source device`, the softmax default) is ke
 the same stream whatever `--n_gpus` and wherever the length sort puts it.
 
 `--weights bf16` (not a reference flag) stores the head matrices the BL6-class decode kernel streams at every step as bf16
-(HipNet.decode(weights="bf16")); it passes through to the one-shot decode, `--stream_frames` and `--pool_slots`.
+(HipNet.decode(weights="bf16")), `--weights e4m3` as OCP FP8 E4M3 codes with one power-of-two scale per row
+(HipNet.decode(weights="e4m3")); either passes through to the one-shot decode, `--stream_frames` and `--pool_slots`.
 
 `--restore_stats` / `--restore_writedir` (not reference flags) also restore every waveform on the device as run.sh stage 6
 does with `noise_shaping.py --inv false` (shallow_wavenet_amd.postfilter; --mcep_dim_start, --mcep_alpha and --mag as that
@@ -242,8 +243,8 @@ def stream_generate(model, seed, aux, n_samples_list, frames_per_push: int, rest
 
 
 def _weights_variant(model) -> int:
-    """--weights bf16 runs on the symmetric BL6 kernel alone (variant 6, as batch_fast_generate asks for it); else auto"""
-    return 6 if getattr(model, "decode_weights", "fp32") == "bf16" else 0
+    """--weights bf16 / e4m3 run on the symmetric BL6 kernel alone (variant 6, as batch_fast_generate asks for it); else auto"""
+    return 6 if getattr(model, "decode_weights", "fp32") in ("bf16", "e4m3") else 0
 
 
 def make_restorer(args, device):
@@ -325,10 +326,11 @@ def make_parser() -> argparse.ArgumentParser:
                    help="not a reference flag: where the sampling noise is drawn - host = the torch CPU generator in "
                         "the reference's order (reproduces the reference's CPU decode), device = inside the kernels; "
                         "default: the model's own default (Laplace host, softmax device)")
-    p.add_argument("--weights", default="fp32", choices=["fp32", "bf16"],
+    p.add_argument("--weights", default="fp32", choices=["fp32", "bf16", "e4m3"],
                    help="not a reference flag: bf16 = the head matrices the BL6-class decode kernel streams at every step "
-                        "(out_skip, out_1, softmax out_2) are stored as bf16, everything else stays fp32 (BL6-class nets "
-                        "only; applies to the one-shot decode, --stream_frames and --pool_slots)")
+                        "(out_skip, out_1, softmax out_2) are stored as bf16, e4m3 = as OCP FP8 E4M3 codes with one "
+                        "power-of-two scale per output row; everything else stays fp32 (BL6-class nets only; applies to "
+                        "the one-shot decode, --stream_frames and --pool_slots)")
     p.add_argument("--stream_frames", default=0, type=int,
                    help="not a reference flag: > 0 decodes each batch as a stream, pushing this many feature frames at a "
                         "time (needs device-drawn noise; the WAVs are those of the one-shot decode)")

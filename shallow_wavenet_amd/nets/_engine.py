@@ -80,7 +80,7 @@ class EngineMixin:
     place (load_state_dict, optimizer step, .to()/.cuda()); SURVEY.md 8b 'Checkpoint / ownership'."""
 
     _cfg: NetConfig
-    decode_weights = "fp32"   # "bf16": batch_fast_generate / open_stream / open_pool stream the head matrices as bf16
+    decode_weights = "fp32"   # "bf16" | "e4m3": batch_fast_generate / open_stream / open_pool stream the head matrices so
     device_unfold = True      # packed gradients -> p.grad by one launch (False: the torch-op version, nets/_autograd.py)
 
     def _param_slots(self):
@@ -132,7 +132,7 @@ class EngineMixin:
         takes host noise chunk by chunk).  audio: the seed waveform as batch_fast_generate takes it (None = zeros / Q/2).
         post_filter: a postfilter.NoiseShapingRestorer - every chunk is also returned restored (run.sh stage 6) on the device.
         prologue: "stepped" | "parallel", as DecodeStream takes it (the latter on the stepped decode only).
-        weights: "fp32" | "bf16" as DecodeStream takes it; None = the module's `decode_weights`."""
+        weights: "fp32" | "bf16" | "e4m3" as DecodeStream takes it; None = the module's `decode_weights`."""
         from .. import noise as _noise
         from ..streaming import DecodeStream
         net = self._engine()
@@ -162,7 +162,7 @@ class EngineMixin:
         multi_model: the pool is to serve further nets of this geometry (add_model, open(model=k)): a net of the stepped
         decode then gets a SteppedModelPool; the DecodePool of the other nets takes add_model as it is.
         prologue: "stepped" | "parallel", as SteppedDecodePool takes it; "parallel" on a net of another decode is a
-        ValueError.  weights: "fp32" | "bf16" as DecodePool takes it (one model, not on the stepped pools); None = the
+        ValueError.  weights: "fp32" | "bf16" | "e4m3" as DecodePool takes it (one model, not on the stepped pools); None = the
         module's `decode_weights`."""
         from .. import _lib, noise as _noise, ops as _ops
         from ..streaming import DecodePool, SteppedDecodePool, SteppedModelPool, _check_prologue
@@ -203,8 +203,8 @@ def resolve_noise_source(module, default: str) -> str:
 
 
 def resolve_decode_weights(module) -> str:
-    """`module.decode_weights`: "fp32" | "bf16" | None (= "fp32") - how batch_fast_generate, open_stream and open_pool store
-    the streamed head matrices (HipNet.decode(weights=...)).  batch_fast_generate takes no kernel variant, so with "bf16" it
+    """`module.decode_weights`: "fp32" | "bf16" | "e4m3" | None (= "fp32") - how batch_fast_generate, open_stream and open_pool
+    store the streamed head matrices (HipNet.decode(weights=...)).  batch_fast_generate takes no kernel variant, so with "bf16" / "e4m3" it
     asks for the one kernel that has the mode (variant 6: the symmetric BL6 kernel whatever the net)."""
     from ..runtime import DECODE_WEIGHTS
     w = getattr(module, "decode_weights", None) or "fp32"

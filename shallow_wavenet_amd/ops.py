@@ -27,6 +27,9 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.decode_w16(packed, w16, cond, ...decode's arguments)            -> (out, heads, noise_used)
     torch.ops.swn.decode_chunk_w16(packed, w16, cond, session, ...decode_chunk's) -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_chunk_w16(packed, w16, session, ...decode_pool_chunk's) -> (out, heads, noise_used)
+    torch.ops.swn.pack_decode_w8(packed, desc)                     -> w8    (FP8 E4M3 image of the same matrices + row scales)
+    torch.ops.swn.decode_w8 / decode_chunk_w8 / decode_pool_chunk_w8(packed, w8, ...)  as the *_w16 ops, over that image
+    torch.ops.swn.e4m3_table(like, scale)                          -> (256,) fp32: the kernels' conversion of codes 0 .. 255
     torch.ops.swn.decode_pool_stepped_chunk(packed, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids, desc,
                                             capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_stepped_chunk_models(models, model_of, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids,
@@ -321,6 +324,17 @@ def _check_w16(w16: torch.Tensor, packed: torch.Tensor, d) -> torch.Tensor:
     return w16
 
 
+def _check_w8(w8: torch.Tensor, packed: torch.Tensor, d) -> torch.Tensor:
+    """the FP8 image of pack_decode_w8 as the *_w8 calls want it (the rules of _check_w16)"""
+    need = _lib.lib().swn_decode_w8_bytes(ctypes.byref(d))
+    if need == 0:
+        raise RuntimeError("e4m3 weights exist for the nets the symmetric BL6 decode kernel serves only")
+    if w8.device != packed.device or w8.dtype != torch.uint8 or not w8.is_contiguous() or w8.numel() != need:
+        raise RuntimeError(f"w8 must be the contiguous uint8 image of pack_decode_w8 ({need} bytes) on the device of the "
+                           "packed parameters")
+    return w8
+
+
 def decode_impl(packed: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor], forced: Optional[torch.Tensor],
            seed: Optional[torch.Tensor], desc: List[int], n_steps: int, variant: int, rng_seed: int, rng_utt0: int,
            want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
@@ -365,8 +379,9 @@ def _decode_io(d, dev, cond, noise, forced, seed, utt_ids, n_steps, rng_seed, rn
 
 
 def _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise,
-                 utt_ids):
-    """decode (w16 None: swn_decode) and decode_w16 (the bf16 image: swn_decode_w16)"""
+                 utt_ids, fp8=False):
+    """decode (w16 None: swn_decode), decode_w16 (the bf16 image: swn_decode_w16) and decode_w8 (fp8: `w16` is the FP8
+    image: swn_decode_w8)"""
     L = _lib.lib()
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
@@ -377,15 +392,16 @@ def _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant,
                                       want_noise)
     r = ctypes.byref(d)
     if w16 is not None:
-        _check_w16(w16, packed, d)
+        (_check_w8 if fp8 else _check_w16)(w16, packed, d)
     state = torch.empty(L.swn_decode_state_floats(r, B) if w16 is None else 0, dtype=torch.float32, device=dev)
     with _on(dev):
         if w16 is None:
             _lib.check(L.swn_decode(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), _ptr(state), _ptr(out),
                                     _ptr(heads if want_heads else None), variant, _stream(dev)), "decode")
         else:
-            _lib.check(L.swn_decode_w16(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), None, _ptr(out),
-                                        _ptr(heads if want_heads else None), variant, _ptr(w16), _stream(dev)), "decode_w16")
+            call, name = (L.swn_decode_w8, "decode_w8") if fp8 else (L.swn_decode_w16, "decode_w16")
+            _lib.check(call(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), None, _ptr(out),
+                            _ptr(heads if want_heads else None), variant, _ptr(w16), _stream(dev)), name)
     return out, heads, used
 
 
@@ -434,6 +450,67 @@ def _(packed, w16, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, 
     return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
 
 
+def pack_decode_w8_impl(packed: torch.Tensor, desc: List[int]) -> torch.Tensor:
+    """the FP8 (OCP E4M3) image of the matrices the symmetric BL6 decode kernel streams (swn_pack_decode_w8): per output row a
+    power-of-two scale and the nearest-even codes (runtime.e4m3_quantise), re-tiled, then one fp32 2^-e per row; uint8
+    (swn_decode_w8_bytes).  Waits for the stream: a weight that is not finite is an error."""
+    L = _lib.lib()
+    d = _desc(desc)
+    _need_cuda(packed, "the packed parameters")
+    n = L.swn_decode_w8_bytes(ctypes.byref(d))
+    if n == 0:
+        raise RuntimeError("e4m3 weights exist for the nets the symmetric BL6 decode kernel serves only")
+    w8 = torch.empty(n, dtype=torch.uint8, device=packed.device)
+    with _on(packed.device):
+        _lib.check(L.swn_pack_decode_w8(ctypes.byref(d), _ptr(packed), _ptr(w8), _stream(packed.device)), "pack_decode_w8")
+    return w8
+
+
+pack_decode_w8 = custom_op("swn::pack_decode_w8", mutates_args=())(pack_decode_w8_impl)
+
+
+@pack_decode_w8.register_fake
+def _(packed, desc):
+    return packed.new_empty(_lib.lib().swn_decode_w8_bytes(ctypes.byref(_desc(desc))), dtype=torch.uint8)
+
+
+def decode_w8_impl(packed: torch.Tensor, w8: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor],
+                   forced: Optional[torch.Tensor], seed: Optional[torch.Tensor], desc: List[int], n_steps: int, variant: int,
+                   rng_seed: int, rng_utt0: int, want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode with the streamed head matrices stored as FP8 E4M3 (swn_decode_w8; w8 = pack_decode_w8(packed, desc)):
+    bit-identical to decode on the model of runtime.e4m3_weight_state_dict.  The variant must resolve to the symmetric BL6
+    kernel (6 for the single-sample Laplace nets)."""
+    return _decode_call(w8, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads,
+                        want_noise, utt_ids, fp8=True)
+
+
+decode_w8 = custom_op("swn::decode_w8", mutates_args=())(decode_w8_impl)
+
+
+@decode_w8.register_fake
+def _(packed, w8, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise, utt_ids=None):
+    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
+
+
+def e4m3_table_impl(like: torch.Tensor, scale: float) -> torch.Tensor:
+    """what the W8 kernels' conversion helper makes of the E4M3 codes 0 .. 255 at `scale` (swn_e4m3_table): (256,) fp32 on the
+    device of `like`"""
+    _need_cuda(like, "the tensor that names the device")
+    out = torch.empty(256, dtype=torch.float32, device=like.device)
+    with _on(like.device):
+        _lib.check(_lib.lib().swn_e4m3_table(_ptr(out), float(scale), _stream(like.device)), "e4m3_table")
+    return out
+
+
+e4m3_table = custom_op("swn::e4m3_table", mutates_args=())(e4m3_table_impl)
+
+
+@e4m3_table.register_fake
+def _(like, scale):
+    return like.new_empty(256, dtype=torch.float32)
+
+
 def _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise):
     d = _desc(desc)
     soft, seg, _, _, n_out, _ = _geom(d)
@@ -463,8 +540,9 @@ def decode_chunk_impl(packed: torch.Tensor, cond: torch.Tensor, session: torch.T
 
 
 def _decode_chunk_call(w16, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0,
-                       want_heads, want_noise, utt_ids):
-    """decode_chunk (w16 None: swn_decode_chunk) and decode_chunk_w16 (the bf16 image: swn_decode_chunk_w16)"""
+                       want_heads, want_noise, utt_ids, fp8=False):
+    """decode_chunk (w16 None: swn_decode_chunk), decode_chunk_w16 (the bf16 image: swn_decode_chunk_w16) and decode_chunk_w8
+    (fp8: `w16` is the FP8 image: swn_decode_chunk_w8)"""
     L = _lib.lib()
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
@@ -483,6 +561,8 @@ def _decode_chunk_call(w16, packed, cond, session, noise, forced, seed, desc, st
     with _on(dev):
         if w16 is None:
             _lib.check(L.swn_decode_chunk(*args, _stream(dev)), "decode_chunk")
+        elif fp8:
+            _lib.check(L.swn_decode_chunk_w8(*args, _ptr(_check_w8(w16, packed, d)), _stream(dev)), "decode_chunk_w8")
         else:
             _lib.check(L.swn_decode_chunk_w16(*args, _ptr(_check_w16(w16, packed, d)), _stream(dev)), "decode_chunk_w16")
     return out, heads, used
@@ -507,6 +587,26 @@ decode_chunk_w16 = custom_op("swn::decode_chunk_w16", mutates_args=("session",))
 
 @decode_chunk_w16.register_fake
 def _(packed, w16, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0, want_heads,
+      want_noise, utt_ids=None):
+    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
+
+
+def decode_chunk_w8_impl(packed: torch.Tensor, w8: torch.Tensor, cond: torch.Tensor, session: torch.Tensor,
+                         noise: Optional[torch.Tensor], forced: Optional[torch.Tensor], seed: Optional[torch.Tensor],
+                         desc: List[int], step0: int, n_steps: int, begin: bool, variant: int, rng_seed: int, rng_utt0: int,
+                         want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
+                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode_chunk over the FP8 image of the streamed head matrices (swn_decode_chunk_w8): the chunks concatenate to
+    decode_w8 bit for bit; the session is laid out as decode_chunk's."""
+    return _decode_chunk_call(w8, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed,
+                              rng_utt0, want_heads, want_noise, utt_ids, fp8=True)
+
+
+decode_chunk_w8 = custom_op("swn::decode_chunk_w8", mutates_args=("session",))(decode_chunk_w8_impl)
+
+
+@decode_chunk_w8.register_fake
+def _(packed, w8, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0, want_heads,
       want_noise, utt_ids=None):
     return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
 
@@ -600,6 +700,30 @@ decode_pool_chunk_w16 = custom_op("swn::decode_pool_chunk_w16", mutates_args=("s
 
 @decode_pool_chunk_w16.register_fake
 def _(packed, w16, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
+      want_heads, want_noise):
+    return _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise)
+
+
+def decode_pool_chunk_w8_impl(packed: torch.Tensor, w8: torch.Tensor, session: torch.Tensor, conds: List[torch.Tensor],
+                              slots: List[int], step0s: List[int], n_steps: List[int], begins: List[bool],
+                              seeds: Optional[torch.Tensor], utt_ids: List[int], desc: List[int], capacity: int, variant: int,
+                              rng_seed: int, want_heads: bool, want_noise: bool
+                              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode_pool_chunk over the FP8 image of the streamed head matrices (swn_decode_pool_chunk_w8): every entry's rows are
+    bit-identical to decode_chunk_w8 of that session alone."""
+    d = _desc(desc)
+    _need_cuda(packed, "the packed parameters")
+    _check_w8(w8, packed, d)
+    return _decode_pool_call(_lib.lib().swn_decode_pool_chunk_w8, d, packed.device, (_ptr(packed),), (_ptr(w8),), session,
+                             conds, slots, step0s, n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed, want_heads,
+                             want_noise)
+
+
+decode_pool_chunk_w8 = custom_op("swn::decode_pool_chunk_w8", mutates_args=("session",))(decode_pool_chunk_w8_impl)
+
+
+@decode_pool_chunk_w8.register_fake
+def _(packed, w8, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
       want_heads, want_noise):
     return _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise)
 
@@ -1735,6 +1859,7 @@ def _(table, state, staged, n_ins, slots, in0s, out0s, n_outs, lens, up, down, n
 
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
             "pack_decode_w16", "decode_w16", "decode_chunk_w16", "decode_pool_chunk_w16",
+            "pack_decode_w8", "decode_w8", "decode_chunk_w8", "decode_pool_chunk_w8", "e4m3_table",
             "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
             "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",

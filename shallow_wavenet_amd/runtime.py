@@ -122,7 +122,7 @@ class train_precision:
         return False
 
 
-DECODE_WEIGHTS = ("fp32", "bf16")
+DECODE_WEIGHTS = ("fp32", "bf16", "e4m3")
 
 
 def bf16_weight_names(cfg: NetConfig) -> List[str]:
@@ -152,27 +152,96 @@ def bf16_weight_state_dict(cfg: NetConfig, state_dict) -> Dict[str, "np.ndarray 
     return out
 
 
+# ---- weights="e4m3": FP8 storage of the same tensors.  The definition (also include/swn_hip.h and DESIGN 3.1):
+#   tensors  those of bf16_weight_names(cfg); everything else, biases included, stays fp32
+#   format   OCP E4M3FN: 1 sign bit, 4 exponent bits (bias 7), 3 fraction bits; subnormals in steps of 2^-9; largest finite
+#            value 448; no infinities; codes 0x7f / 0xff are NaN and are never produced
+#   scale    one power of two per output row r of each matrix, chosen without a logarithm: amax = max_k |W[r][k]|; e_r = 0 if
+#            amax is 0; else frexp gives amax = m 2^x with m in [0.5, 1) and e_r = 9 - x if m <= 0.875 (448 = 0.875 x 2^9), else
+#            8 - x; e_r is clamped to [-100, 100].  Then amax 2^e_r <= 448 and the row uses the top binade whenever it can
+#            (behind the lower clamp, amax >= 0.875 x 2^109, larger products saturate to +-448)
+#   code     q[r][k] = the E4M3 value nearest to W[r][k] 2^e_r, ties to the even fraction; the sign of a zero is kept
+#   refusal  a weight that is not finite: ValueError here, SWN_E_BADARG from swn_pack_decode_w8
+#   weight   the dequantised W^[r][k] = q[r][k] 2^-e_r; both scalings are exact in fp32
+#   kernel   each streamed code is widened to exactly W^ in fp32 and enters the fp32 kernel's fmaf chain in its order, so the
+#            mode is bit-identical to the fp32 symmetric kernel on e4m3_weight_state_dict(cfg, sd)
+E4M3_MAX = 448.0
+
+
+def e4m3_values() -> np.ndarray:
+    """the fp32 value of every E4M3FN code 0 .. 255 (0x7f / 0xff: NaN)"""
+    c = np.arange(256)
+    ex, fr = (c >> 3) & 15, (c & 7).astype(np.float64)
+    v = np.where(ex == 0, fr * 2.0 ** -9, (1 + fr / 8) * 2.0 ** (ex.astype(np.float64) - 7))
+    v = np.where((c & 0x7f) == 0x7f, np.nan, v)
+    return (np.where(c & 0x80, -v, v)).astype(np.float32)
+
+
+def e4m3_quantise(w) -> "Tuple[np.ndarray, np.ndarray]":
+    """(codes uint8 of w's shape, e int32 per row) of a weight matrix under the definition above; a row is everything behind
+    the first axis (a conv weight (rows, inputs, 1) counts as (rows, inputs)).  ValueError for a weight that is not finite."""
+    w = np.ascontiguousarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float32)
+    if w.ndim < 1 or w.size == 0:
+        raise ValueError("e4m3_quantise wants a matrix with at least one row")
+    if not np.isfinite(w).all():
+        raise ValueError("e4m3_quantise: a weight is not finite")
+    rows = w.reshape(w.shape[0], -1)
+    amax = np.abs(rows).max(axis=1)
+    m, x = np.frexp(amax)
+    e = np.where(m <= np.float32(0.875), 9 - x, 8 - x)
+    e = np.where(amax == 0, 0, np.clip(e, -100, 100)).astype(np.int32)
+    v = rows * np.ldexp(np.float32(1), e)[:, None]                        # exact: a power of two, no overflow (|e| <= 100)
+    a = np.minimum(np.abs(v), np.float32(E4M3_MAX))                       # (only behind the lower clamp: saturate)
+    sub = np.rint(a * np.float32(512)).astype(np.uint32)                  # below 2^-6: steps of 2^-9, ties to even; 8 = 2^-6
+    u = a.view(np.uint32)
+    nrm = ((u + np.uint32(0x7ffff) + ((u >> np.uint32(20)) & np.uint32(1))) >> np.uint32(20)) - np.uint32(120 << 3)
+    code = np.where(a < np.float32(2.0 ** -6), sub, nrm).astype(np.uint8)
+    code |= (np.signbit(v).astype(np.uint8) << 7)
+    return code.reshape(w.shape), e
+
+
+def e4m3_dequantise(codes: np.ndarray, e: np.ndarray) -> np.ndarray:
+    """W^ = value(code) 2^-e_row in fp32 (exact)"""
+    rows = e4m3_values()[codes.reshape(codes.shape[0], -1)] * np.ldexp(np.float32(1), -e.astype(np.int32))[:, None]
+    return rows.astype(np.float32).reshape(codes.shape)
+
+
+def e4m3_weight_state_dict(cfg: NetConfig, state_dict) -> Dict[str, "np.ndarray | torch.Tensor"]:
+    """the state dict whose fp32 decode is what decode(weights="e4m3") computes, bit for bit: a copy of `state_dict` with
+    exactly the tensors of bf16_weight_names quantised (e4m3_quantise) and widened back to fp32; every other tensor is the
+    same object.  Feed it to the fp32 path (same variant) or to the CPU oracle to judge the mode."""
+    out = dict(state_dict)
+    for name in bf16_weight_names(cfg):
+        if name not in out:
+            raise KeyError(f"state_dict is missing {name}")
+        v = out[name]
+        deq = e4m3_dequantise(*e4m3_quantise(v))
+        out[name] = torch.from_numpy(deq) if isinstance(v, torch.Tensor) else deq
+    return out
+
+
 def check_decode_weights(weights, cfg: NetConfig, batch: int, variant: int) -> str:
-    """the `weights` keyword of the decode calls: "fp32" | "bf16".  bf16 storage exists on the symmetric BL6 kernel alone, so
-    for "bf16" the (net, batch, variant) must resolve to it: ValueError otherwise, before any device work."""
+    """the `weights` keyword of the decode calls: "fp32" | "bf16" | "e4m3".  bf16 and e4m3 storage exist on the symmetric BL6
+    kernel alone, so for them the (net, batch, variant) must resolve to it: ValueError otherwise, before any device work."""
     if weights not in DECODE_WEIGHTS:
         raise ValueError(f"weights must be one of {DECODE_WEIGHTS}, not {weights!r}")
     if weights == "fp32":
         return weights
     L = _lib.lib()
     desc = _lib.desc_from_cfg(cfg)
-    if L.swn_decode_w16_bytes(ctypes.byref(desc)) == 0:
-        raise ValueError('weights="bf16" runs on the symmetric BL6 decode kernel, which does not serve this net (the '
-                         "stepped chain and the generic kernel have no bf16 form)")
+    size = L.swn_decode_w16_bytes if weights == "bf16" else L.swn_decode_w8_bytes
+    if size(ctypes.byref(desc)) == 0:
+        raise ValueError(f'weights="{weights}" runs on the symmetric BL6 decode kernel, which does not serve this net (the '
+                         f"stepped chain and the generic kernel have no {weights} form)")
     resolved = L.swn_decode_resolve_variant(ctypes.byref(desc), int(batch), int(variant))
     if resolved == 6:
         return weights
     if resolved == 2 and cfg.kind == "laplace" and int(cfg.seg) == 1:
-        raise ValueError(f'weights="bf16": variant {variant} resolves to the wave-specialised kernel for this '
-                         "single-sample Laplace net, which has no bf16 form - pass variant=6 (the symmetric kernel)")
+        raise ValueError(f'weights="{weights}": variant {variant} resolves to the wave-specialised kernel for this '
+                         f"single-sample Laplace net, which has no {weights} form - pass variant=6 (the symmetric kernel)")
     if resolved != 2:
-        raise ValueError(f'weights="bf16" runs on the symmetric BL6 decode kernel; variant {variant} does not resolve to it '
-                         "for this net - pass variant=6")
+        raise ValueError(f'weights="{weights}" runs on the symmetric BL6 decode kernel; variant {variant} does not resolve to '
+                         "it for this net - pass variant=6")
     return weights
 
 
@@ -239,6 +308,8 @@ class HipNet:
 
         weights: "fp32" (default) | "bf16": out_skip, out_1 and the softmax out_2 weights stored and streamed as bf16 (round
                to nearest even), everything else fp32 - bit-identical to the fp32 decode of bf16_weight_state_dict(...).
+               "e4m3": the same tensors as OCP FP8 E4M3 codes with one power-of-two scale per output row (a quarter of the
+               fp32 bytes) - bit-identical to the fp32 decode of e4m3_weight_state_dict(...).
                Symmetric BL6 kernel only: variant 6 for the single-sample Laplace nets, 0 or 6 for the others of the class.
 
         noise: laplace (B, n_steps, seg) | softmax (B, n_steps, Q), fp32, utterance-major - the host-drawn stream of
@@ -249,14 +320,16 @@ class HipNet:
         returns (out, heads): out laplace (B, n_steps*seg) fp32 | softmax (B, n_steps) int32; with want_noise=True
         a third value: the noise the kernels used, in the layout of `noise`.
         """
-        bf16 = check_decode_weights(weights, self.cfg, int(aux.shape[0] if cond is None else cond.shape[0]), variant) == "bf16"
+        weights = check_decode_weights(weights, self.cfg, int(aux.shape[0] if cond is None else cond.shape[0]), variant)
         if cond is None:
             cond = self.frontend(aux)
         ids = None if utt_ids is None else torch.as_tensor(list(utt_ids), dtype=torch.int32)
         args = (cond, noise, forced, seed, self.dlist, int(n_steps), int(variant), int(rng_seed) & 0x7FFFFFFFFFFFFFFF,
                 int(rng_utt0) & 0xFFFFFFFF, bool(want_heads), bool(want_noise), ids)
-        if bf16:
+        if weights == "bf16":
             out, heads, used = _O.decode_w16(self.packed, self.decode_w16_image(), *args)
+        elif weights == "e4m3":
+            out, heads, used = _O.decode_w8(self.packed, self.decode_w8_image(), *args)
         else:
             out, heads, used = _O.decode(self.packed, *args)
         heads = heads if want_heads else None
@@ -271,6 +344,14 @@ class HipNet:
             self._w16 = _O.pack_decode_w16(self.packed, self.dlist)
             self._w16_version = self.packed_version
         return self._w16
+
+    def decode_w8_image(self) -> torch.Tensor:
+        """the FP8 (E4M3) image of the streamed head matrices and their row scales (torch.ops.swn.pack_decode_w8), built on
+        first use and rebuilt when the packed parameters moved on (repack)"""
+        if getattr(self, "_w8", None) is None or getattr(self, "_w8_version", -1) != self.packed_version:
+            self._w8 = _O.pack_decode_w8(self.packed, self.dlist)
+            self._w8_version = self.packed_version
+        return self._w8
 
     # ------------------------------------------------------------------ teacher-forced stack
     def forward(self, aux: torch.Tensor, audio: torch.Tensor, want_hidden: bool = False,

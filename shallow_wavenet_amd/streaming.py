@@ -57,7 +57,7 @@ def _check_prologue(prologue, stepped: bool) -> str:
 
 
 def _check_weights(weights, cfg: NetConfig, batch: int, variant: int) -> str:
-    """the `weights` keyword of the streams and pools: runtime.check_decode_weights ("fp32" | "bf16", the latter where
+    """the `weights` keyword of the streams and pools: runtime.check_decode_weights ("fp32" | "bf16" | "e4m3", the latter two where
     (net, batch, variant) resolves to the symmetric BL6 kernel)"""
     from .runtime import check_decode_weights
     return check_decode_weights(weights, cfg, batch, variant)
@@ -96,7 +96,7 @@ class DecodeStream:
                   restores every chunk on the device (run.sh stage 6)
     prologue      "stepped" (default) | "parallel": on the stepped chain (variant 3), fill the history rings before the first
                   chunk with swn_decode_stepped_prologue - L + 2 launches instead of (rf - seg + 1) x (L + 1), same bits
-    weights       "fp32" (default) | "bf16": the streamed head matrices stored as bf16, as HipNet.decode(weights=...) - the
+    weights       "fp32" (default) | "bf16" | "e4m3": the streamed head matrices stored as bf16 / FP8, as HipNet.decode(weights=...) - the
                   chunks then concatenate to that one-shot decode; the symmetric BL6 kernel only (variant=6 for the
                   single-sample Laplace nets), ValueError otherwise
 
@@ -275,6 +275,8 @@ class DecodeStream:
                 self.rng_seed, self.rng_utt0, self.want_heads, self.want_noise, self._ids)
         if self.weights == "bf16":
             out, heads, used = _O.decode_chunk_w16(self.net.packed, self.net.decode_w16_image(), *args)
+        elif self.weights == "e4m3":
+            out, heads, used = _O.decode_chunk_w8(self.net.packed, self.net.decode_w8_image(), *args)
         else:
             out, heads, used = _O.decode_chunk(self.net.packed, *args)
         self._begun = True
@@ -433,9 +435,10 @@ class DecodePool:
     want_heads / want_noise   also return the raw out_2 rows / the noise used
     post_filter   a postfilter.NoiseShapingRestorer: every session holds one of its slots, and each tick ends with one
                post-filter call over the sessions that ran; each result then ends with the restored chunk (1, n * seg) fp32
-    weights    "fp32" (default) | "bf16": the streamed head matrices stored as bf16 (swn_decode_pool_chunk_w16), each session
-               bit-identical to its solo DecodeStream(weights="bf16").  Symmetric BL6 kernel only (variant=6 for the
-               single-sample Laplace nets); a bf16 pool serves one model (add_model raises) and no stepped pool has the mode
+    weights    "fp32" (default) | "bf16" | "e4m3": the streamed head matrices stored as bf16 (swn_decode_pool_chunk_w16) or FP8
+               E4M3 (swn_decode_pool_chunk_w8), each session bit-identical to its solo DecodeStream of that mode.  Symmetric BL6
+               kernel only (variant=6 for the single-sample Laplace nets); such a pool serves one model (add_model raises) and
+               no stepped pool has the modes
 
         k = pool.add_model(other_net)           # another net of the same NetConfig (the pool's own net is model 0)
         s = pool.open(seed=None, utt_id=None, model=0)   # a free slot; utt_id defaults to the admission counter
@@ -481,7 +484,8 @@ class DecodePool:
         open(model=...).  A session slot's layout depends on the geometry only, so sessions of all models share the pool's
         slots and launches.  The pool may hold any number of models; the nets' packed buffers are read at call time."""
         if self.weights != "fp32":
-            raise ValueError('add_model: a weights="bf16" pool serves one model - the multi-model launch has no bf16 form')
+            raise ValueError(f'add_model: a weights="{self.weights}" pool serves one model - the multi-model launch has no '
+                             f"{self.weights} form")
         if net.cfg != self.cfg:
             raise ValueError("add_model: the net's NetConfig differs from the pool's - the models of a pool share one geometry")
         if torch.device(net.device) != torch.device(self.net.device):
@@ -538,6 +542,8 @@ class DecodePool:
                     self.net.dlist, self.capacity, self.variant, self.rng_seed, self.want_heads, self.want_noise)
             if self.weights == "bf16":
                 out, heads, used = _O.decode_pool_chunk_w16(self.net.packed, self.net.decode_w16_image(), *args)
+            elif self.weights == "e4m3":
+                out, heads, used = _O.decode_pool_chunk_w8(self.net.packed, self.net.decode_w8_image(), *args)
             elif len(models) == 1:
                 out, heads, used = _O.decode_pool_chunk(self._models[models[0]].packed, *args)
             else:
@@ -726,7 +732,7 @@ class SteppedDecodePool(DecodePool):
         if weights not in DECODE_WEIGHTS:
             raise ValueError(f"weights must be one of {DECODE_WEIGHTS}, not {weights!r}")
         if weights != "fp32":
-            raise ValueError('weights="bf16" is not served by the stepped decode pools: the chain is launch-bound, weight bytes '
+            raise ValueError(f'weights="{weights}" is not served by the stepped decode pools: the chain is launch-bound, weight bytes '
                              "are not its limit")
         self.weights = "fp32"
         self.net, self.cfg, self.capacity = net, net.cfg, capacity
