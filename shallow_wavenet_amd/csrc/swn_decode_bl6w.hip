@@ -18,7 +18,10 @@
 //     the symmetric kernel took), only out_skip streams from L2;
 //   * out_1 is group A's alone (two rows per thread), and out_2 beside it as one partial sum per wave; the sum of the four partials
 //     + sampling + the next input layer run in every wave of group A, each forming its own copy of h0 and going straight on into
-//     layer 0 (wave 0 alone stores the sample and the heads).
+//     layer 0 (wave 0 alone stores the sample and the heads).  Between the sample and layer 0's first LDS read stands the input
+//     layer's arithmetic and its one LDS write only: the next step's conditioning taps, parity offset and layer-0 row are formed
+//     while the tail waits for the partials (one step ahead), the wave's own h0 is read back without a wait (LDS serves a wave's
+//     operations in order), and the sample and heads stores and the loop latch come behind the write.
 // Same arithmetic per element as the symmetric kernel up to the order of the partial sums (1e-7 relative); same noise, seed,
 // forced-input and heads interface (swn_decode_bl6.hip: classic = host-drawn noise, zero seed; extended = in-kernel generator,
 // noise dump, caller's seed waveform).  8 barriers per step.  cswnv_shift1.py:281-430.
@@ -88,13 +91,13 @@ __device__ __forceinline__ float sum_quads(float v) {
 }
 // ---- group A: layer LAYER at position q - current tap, gate epilogue, hand-off.  Thread (o, p): rows o (gate) and o + 64
 //      (candidate) over inputs 16 p .. 16 p + 15 of h_{l-1}(q), read from the row `xr`; lanes 0 / 1 of the quad finish the gate / the
-//      candidate.
+//      candidate.  `po`: the offset of position q's parity in o_old, (q & 1) * L * 2 * H (the step loop forms it one step ahead).
 template <class T, int LAYER>
-__device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], const int q, const float wj, const int pb, const int ta,
-                                        const float* xr) {
+__device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], const int q, const float wj, const int pb, const int po,
+                                        const int ta, const float* xr) {
     const int o = ta >> 2, p = ta & 3, pr = p & 1;
     // epilogue operands first: their LDS latency hides under the FMAs
-    const float e_old = lds[T::o_old + (q & 1) * (L * 2 * H) + LAYER * 2 * H + pr * H + o];
+    const float e_old = lds[T::o_old + po + LAYER * 2 * H + pr * H + o];
     const float e_gx = fmaf(wj, lds[T::o_gp + pb + LAYER * 2 * H + pr * H + o], lds[T::o_bx + LAYER * 2 * H + pr * H + o]);
     const float e_hp = xr[o];
     float az = 0.f, ac = 0.f;
@@ -442,18 +445,20 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     const int wv = __builtin_amdgcn_readfirstlane(tg >> 6);   // wave inside the group
     float kcb = 0.f, kv0 = 0.f, kv1 = 0.f, kc0 = 0.f, kc1 = 0.f;
     if (grpA) { const int o = tg & (H - 1); kcb = c_b; kv0 = c_v0; kv1 = c_v1; kc0 = c_c0; kc1 = c_c1; }
-    auto h0_row = [&](int qn) -> float* {
-        return wv == 0 ? lds + T::o_ring + (qn & 1) * H : lds + T::o_h0w + (wv - 1) * H;
+    auto h0_row = [&](int qn) -> int {                        // (float offset in LDS)
+        return wv == 0 ? T::o_ring + (qn & 1) * H : T::o_h0w + (wv - 1) * H;
     };
-    auto input_gen = [&](int qn) {
+    // `row`: h0_row of the position the window now ends in front of
+    auto input_gen = [&](int row) {
         if constexpr (grpA) {
             float acc = kcb;
             acc += fmaf(kv0, win[T::WN - 2], kc0);
             acc += fmaf(kv1, win[T::WN - 1], kc1);
-            h0_row(qn)[tg & (H - 1)] = ssign(acc);
-            // the row is read by the other lanes of this wave only: LDS serves a wave's instructions in order, so its own
-            // counter is all the ordering needed (the clobber keeps the compiler from moving the reads above the write)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds[row + (tg & (H - 1))] = ssign(acc);
+            // the row is read by the other lanes of this wave only, and LDS serves a wave's instructions in issue order: a read
+            // issued behind the write returns the written data, no wait between them.  The clobber keeps the
+            // compiler from moving the reads above the write
+            lds_fence_compiler();
         }
     };
     // sampling noise staged off the chain (swn_decode_bl6.hip): wave 1 transforms tn = sign(e) log1p(-2|e|) of 64 steps at once
@@ -508,7 +513,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     // (GEN: a generation step - group B's older-tap products for position q + 1 then sit in the merged and the out_1 phase, and
     //  layer 5's is group A's; in the prologue group B forms layer LAYER's in this phase.  X0: the row of h0(q) layer 0 reads)
 #define SWN_PHASE(LAYER, GEN, X0)                                                                                     \
-    if constexpr (grpA) layer_a<T, LAYER>(lds, wreg[LAYER], q, wj, pb, tg,                                             \
+    if constexpr (grpA) layer_a<T, LAYER>(lds, wreg[LAYER], q, wj, pb, po, tg,                                         \
                                           LAYER == 0 ? (X0) : lds + T::o_ring + T::ring_off(LAYER) +                   \
                                                                   (q & (T::ring_len(LAYER) - 1)) * H);                 \
     else {                                                                                                             \
@@ -531,6 +536,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         float wj; int pb;
         float4 wsl[8]; float sacc[2]; const unsigned step0 = 0;
         cond_taps(q, wj, pb);
+        const int po = (q & 1) * (L * 2 * H);
         input_seed(q);
         lds_barrier();
         const float* x0 = lds + T::o_ring + (q & 1) * H;
@@ -540,17 +546,49 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     }
 
     // ---- generation (cswnv_shift1.py:348-402).  Eight barriers per step: the first phase of step q is the tail of step q - 1
-    //      (out_2, head, sample, h0(q) in every wave of group A) followed by layer 0 of step q.  The conditioning refill of a frame
-    //      crossing (cond_taps) is written in that phase too: the buffer it fills was last read before the previous step's barriers,
-    //      and the next reader comes U steps later.
-    input_gen(RF + s0);
+    //      (out_2, head, sample, h0(q) in every wave of group A) followed by layer 0 of step q.
+    //      The chain runs from the sample through the input layer into layer 0's first LDS read, so nothing else stands there: the
+    //      conditioning taps of step q (wj, pb), the parity offset of o_old and layer 0's row are formed one step AHEAD, in the
+    //      tail of step q - 1 behind the reads it issues after barrier 7 (taps_ahead; in front of the loop for the first step - a
+    //      resumed chunk and a pool entry prime them from their own step0 like the one-shot decode from 0), and the sample and
+    //      heads stores and the loop's induction updates come behind the input layer.  Generation steps advance by one, so the
+    //      position in the frame is counted (rel_c; cond_taps' clamps never bind behind the prologue).  All of it is group A's:
+    //      group B reads none of these values.
+    //      The conditioning refill of a frame crossing stays where it was, at the head of the first step of the new frame fb, as one
+    //      load - wait - write of group A's threads 0 .. PF / 4 - 1 behind the `fill_c` flag the look-ahead left: the buffer it
+    //      fills was last read in layer 5 of the previous step, in front of its barrier 5, and the next reader comes U steps later
+    //      (handed to group B and split into a request and a later write it was slower than the parent).
+    int rel_c = s0 - fb0 * U;                 // position of the step in progress in its frame fb
+    bool fill_c = false;                      // the step in progress is the first of its frame and frame fb + 1 exists (never the
+                                              //  first step of a launch: the one-time loads above brought frames fb0 and fb0 + 1)
+    float wj_c = 0.f;
+    int pb_c = 0, po_c = 0, x0_c = 0;
+    auto taps_ahead = [&](int qn) {           // what step qn reads, from the counters already advanced to it
+        wj_c = lds[T::o_wup + rel_c];
+        pb_c = (fb & 1) * T::PF;
+        po_c = (qn & 1) * (L * 2 * H);
+        x0_c = h0_row(qn);
+        // formed here, not at their uses behind the sample
+        asm volatile("" : "+s"(pb_c), "+s"(po_c), "+s"(x0_c));
+    };
+    auto frame_advance = [&]() {
+        rel_c += 1;
+        const bool cross = rel_c >= U;
+        if (cross) { rel_c = 0; fb += 1; }
+        fill_c = cross && fb + 1 < a.Tf;    // one scalar flag: the head of the step tests it and nothing else
+    };
+    if constexpr (grpA) taps_ahead(RF + s0);
+    input_gen(x0_c);
 #ifdef SWN_STAMP
     tlast = tbeg = __builtin_amdgcn_s_memtime();
 #endif
     auto gen_step = [&](const int i) __attribute__((always_inline)) {
         const int q = RF + s0 + i;
-        float wj; int pb;
-        cond_taps(q, wj, pb);
+        const float wj = wj_c;
+        const int pb = pb_c, po = po_c;
+        if constexpr (grpA) {
+            if (fill_c) load_frame(fb + 1);                       // first step of frame fb: refill the buffer the old frame left
+        }
         float4 wsl[8];
         float sacc[2] = {0.f, 0.f};
         if constexpr (!grpA) {                                // the out_skip bias enters in lane 0 of each row's quad
@@ -559,7 +597,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         }
         unsigned step0 = 0;
         asm volatile("" : "+s"(step0));                       // opaque zero, see skip_issue_b
-        const float* x0 = h0_row(q);
+        const float* x0 = lds + x0_c;
         // group B's older-tap products of position q + 1 sit in the first phase (OlderMerged: no slice to consume yet, group A's
         // tail + layer 0 the longest phase) and in the out_1 phase (OlderOut1: group A runs out_1 alone; layer 0 needs h0(q), which
         // is not ready before the first barrier); all six beside the out_skip slices made group B take 1 050 cycles per layer phase
@@ -617,11 +655,18 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
                 acc = fmaf(w0.x, x0.x, acc); acc = fmaf(w0.y, x0.y, acc); acc = fmaf(w0.z, x0.z, acc); acc = fmaf(w0.w, x0.w, acc);
                 bcc = fmaf(w1.x, x0.x, bcc); bcc = fmaf(w1.y, x0.y, bcc); bcc = fmaf(w1.z, x0.z, bcc); bcc = fmaf(w1.w, x0.w, bcc);
             };
+            float e_b1[2] = {0.f, 0.f}, e_w2[2] = {0.f, 0.f}, e_b2 = 0.f;     // (rolled loop only)
+            const int e_kc = hp < T::NO ? hp : T::NO - 1;
             if constexpr (ROLL1) {
                 // rolled: the weights one input block ahead, the inputs two, each into the registers a block's multiply-adds have just
                 // freed (28 working registers hold two blocks of weights and three of inputs).  Left to the scheduler, the 24 reads
                 // were waited for about eight times, each issued a few instructions before; with the weights of three blocks early and
                 // the rest left to it, it read the inputs one block at a time behind lgkmcnt(0) (slower than the parent)
+                // The epilogue's five constants - the two out_1 biases, this lane's out_2 column at both rows, b2; all written
+                // once in front of the step loop - ride in the roll: blocks 5 and 6 request them into registers their
+                // multiply-adds have freed (the inputs' last request leaves with block 4, the weights' with block 5), so the
+                // reduction and the out_2 product find them landed instead of asking for them behind the last multiply-add
+                static_assert(T::NO <= 4, "one round of out_2 rows");
                 float4 xr[3] = {X(0), X(1), X(2)};
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -630,6 +675,11 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
                     __builtin_amdgcn_sched_barrier(0);
                     if (mm + 2 < 8) { w1e[mm % 2][0] = W(mm + 2, 0); w1e[mm % 2][1] = W(mm + 2, 1); }
                     if (mm + 3 < 8) xr[mm % 3] = X(mm + 3);
+                    if (mm == 5) {
+                        e_b1[0] = lds[T::o_bias + S + hr]; e_b1[1] = lds[T::o_bias + S + hr + 64];
+                        e_w2[0] = lds[T::o_w2 + e_kc * S + hr]; e_w2[1] = lds[T::o_w2 + e_kc * S + hr + 64];
+                    }
+                    if (mm == 6) e_b2 = lds[T::o_w2 + T::NO * S + e_kc];
                     __builtin_amdgcn_sched_barrier(0);
                 }
             } else {
@@ -642,14 +692,20 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             const float v = sum4(a0 + a1), u = sum4(b0 + b1);
             // out_2 of this wave's 32 out_1 rows, off the chain: lane hp of every quad takes out_2 rows hp and hp + 4, the wave sums
             // them (sum_quads) and its first quad leaves them in o_p2 for the tail; wave 0's lane 0 .. 3 carry b2
-            const float o1a = fmaxf(v + lds[T::o_bias + S + hr], 0.f), o1b = fmaxf(u + lds[T::o_bias + S + hr + 64], 0.f);
+            if constexpr (ROLL1) {
+                const float o1a = fmaxf(v + e_b1[0], 0.f), o1b = fmaxf(u + e_b1[1], 0.f);
+                const float pz = sum_quads(fmaf(e_w2[1], o1b, fmaf(e_w2[0], o1a, tg < 4 ? e_b2 : 0.f)));
+                if ((tg & 63) < 4 && hp < T::NO) lds[T::o_p2 + 4 * hp + wv] = pz;
+            } else {
+                const float o1a = fmaxf(v + lds[T::o_bias + S + hr], 0.f), o1b = fmaxf(u + lds[T::o_bias + S + hr + 64], 0.f);
 #pragma unroll
-            for (int j = 0; j < (T::NO + 3) / 4; ++j) {
-                const int k = hp + 4 * j, kc = k < T::NO ? k : T::NO - 1;
-                const float* w2 = lds + T::o_w2 + kc * S;
-                const float b2 = lds[T::o_w2 + T::NO * S + kc];
-                const float pz = sum_quads(fmaf(w2[hr + 64], o1b, fmaf(w2[hr], o1a, tg < 4 ? b2 : 0.f)));
-                if ((tg & 63) < 4 && k < T::NO) lds[T::o_p2 + 4 * k + wv] = pz;
+                for (int j = 0; j < (T::NO + 3) / 4; ++j) {
+                    const int k = hp + 4 * j, kc = k < T::NO ? k : T::NO - 1;
+                    const float* w2 = lds + T::o_w2 + kc * S;
+                    const float b2 = lds[T::o_w2 + T::NO * S + kc];
+                    const float pz = sum_quads(fmaf(w2[hr + 64], o1b, fmaf(w2[hr], o1a, tg < 4 ? b2 : 0.f)));
+                    if ((tg & 63) < 4 && k < T::NO) lds[T::o_p2 + 4 * k + wv] = pz;
+                }
             }
         } else {
             older_bn_x<T>(OlderOut1{}, lds, wreg, xo, q + 1, tg);
@@ -668,35 +724,43 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             float fv = 0.f;
             if (a.forced) fv = reinterpret_cast<const float*>(a.forced)[(size_t)b * a.n_steps + i];
             const float4 pz = *reinterpret_cast<const float4*>(lds + T::o_p2 + 4 * (ln < T::NO ? ln : T::NO - 1));
+            // step q + 1's taps, row and offsets while the partials are on their way: wj's read joins the batch waited for here,
+            // and nothing of this is left to do between the sample and layer 0
+            __builtin_amdgcn_sched_barrier(0);
+            frame_advance();
+            taps_ahead(q + 1);
+            __builtin_amdgcn_sched_barrier(0);
             const float acc = (pz.x + pz.y) + (pz.z + pz.w);   // lane k < NO: out_2 row k
             // the NO head outputs sit in lanes 0 .. NO - 1: broadcast them through scalar registers (an LDS write, a wave barrier and
             // a broadcast read stood here: ~150 cycles of the chain the whole workgroup waits for)
             float o2[T::NO];
 #pragma unroll
             for (int k = 0; k < T::NO; ++k) o2[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, acc), k));
+            float sv;
             {
 #pragma clang fp contract(off)
-                float* outp = reinterpret_cast<float*>(a.out) + (size_t)b * a.n_steps + (size_t)i;
                 const float mu = o2[0];
                 const float bsc = sigm(o2[1]);                 // exp(logsigmoid(y))
                 float lpv = 0.f;
 #pragma unroll
                 for (int k = 0; k < T::LPC; ++k) lpv += o2[2 + T::LPC - 1 - k] * win[T::WN - T::LPC + k];
                 const float t = bsc * (EXT ? lds[T::o_tnz + ((i >> 6) & (T::NZB - 1)) * T::NZC + (i & (T::NZC - 1))] : tz);
-                float sv = (T::LPC > 0) ? (lpv + mu) - t : mu - t;
+                sv = (T::LPC > 0) ? (lpv + mu) - t : mu - t;
                 sv = fminf(fmaxf(sv, -1.f), 1.f);
-                // the window is updated BEFORE the sample and the heads are stored: the input layer that follows would otherwise
-                // wait for the stores themselves (a use of the forced load behind a conditional store compiles to vmcnt(0))
+                // the window is updated and the next input layer formed BEFORE the sample and the heads are stored: the stores, their
+                // lane branches and addresses are not on the chain, and a use of the forced load behind a conditional store would
+                // wait for the stores themselves (it compiles to vmcnt(0)); the forced load stays older than every store of its step
                 float fd = a.forced ? fv : sv;
                 asm volatile("" : "+v"(fd));
 #pragma unroll
                 for (int k = 0; k + 1 < T::WN; ++k) win[k] = win[k + 1];
                 win[T::WN - 1] = fd;
-                if (tid == 0) outp[0] = sv;
             }
+            if (i + 1 < a.n_steps) input_gen(x0_c);
+            __builtin_amdgcn_sched_barrier(0);                 // the stores stay behind the input layer's write
+            if (tid == 0) reinterpret_cast<float*>(a.out)[(size_t)b * a.n_steps + (size_t)i] = sv;
             if (HEADS_ON && a.heads && wv == 0 && ln < T::NO) a.heads[((size_t)b * a.n_steps + i) * T::NO + ln] = acc;
         }
-        if (i + 1 < a.n_steps) input_gen(q + 1);
 #ifdef SWN_STAMP
         if constexpr (grpA) tw[8] += __builtin_amdgcn_s_memtime() - tlast;
 #endif
