@@ -8,11 +8,16 @@
 //     W[:, tap 1] h_{l-1}(t)  +  W[:, tap 0] h_{l-1}(t - dil)  +  b
 // and the second product does not depend on the step in progress - for every layer it is known one step ahead (dil >= 1).  So:
 //   * group A (waves 0-3, one per SIMD) owns the chain: per layer the CURRENT-tap half (128 rows x 64 inputs: thread (o, p) two
-//     rows x 16 inputs, reduced over 4 lanes), the gate epilogue, the hand-off through LDS;
+//     rows x 16 inputs, reduced over 4 lanes - the two quad sums transposed, so that lane 0 of the quad ends with the gate's
+//     and lane 1 with the candidate's in two DPP steps), the gate epilogue (one straight line for both lanes: sigmoid | tanh
+//     from the same exp_c / rcp_c, no branch for a saturated tanh - the arithmetic itself returns +-1 there), the hand-off
+//     through LDS;
 //   * group B (waves 4-7, the other wave of every SIMD) works one step AHEAD and off the chain: the OLDER-tap halves (+ bias) of
 //     layers 0-4 for step t + 1, left in LDS (formed where group B has room: two in the first phase, three beside group A's
 //     out_1; the last layer's is formed by group A, from group B's half in LDS, in the one phase where the chain waits for
-//     group B), and the whole out_skip accumulation of step t (slice l in the phase after layer l);
+//     group B - with lpc 0 half of its operands are requested a phase early, in front of barrier 5), and the whole out_skip
+//     accumulation of step t (slice l in the phase after layer l: its four input quads read at the head of the phase, the
+//     next slice's weights requested quarter by quarter behind the multiply-adds that free their registers);
 //   * group A keeps its halves of all six matrices in registers (192 per thread), group B five of them (160) and the sixth in LDS
 //     (it also holds a slice of out_skip weights in flight); the out_1 matrix is LDS-resident whole (the 64 KB the sixth layer of
 //     the symmetric kernel took), only out_skip streams from L2;
@@ -89,6 +94,13 @@ __device__ __forceinline__ float sum_quads(float v) {
     asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(v), "+v"(w));   // the two halves
     return v + w;
 }
+// two quad sums in the steps of one: every lane gives the partial `own` of the sum its parity keeps and the partial `other` of
+// the sum its neighbour keeps; lanes 0 / 2 get the sum of the even lanes' `own` and the odd lanes' `other`, lanes 1 / 3 the other one
+__device__ __forceinline__ float quad_sum_by_parity(float own, float other) {
+    float s = own + dpp_f<0xB1>(other);     // quad_perm [1,0,3,2]: p0 + p1 | p2 + p3
+    s += dpp_f<0x4E>(s);                    // quad_perm [2,3,0,1]
+    return s;
+}
 // ---- group A: layer LAYER at position q - current tap, gate epilogue, hand-off.  Thread (o, p): rows o (gate) and o + 64
 //      (candidate) over inputs 16 p .. 16 p + 15 of h_{l-1}(q), read from the row `xr`; lanes 0 / 1 of the quad finish the gate / the
 //      candidate.  `po`: the offset of position q's parity in o_old, (q & 1) * L * 2 * H (the step loop forms it one step ahead).
@@ -109,21 +121,26 @@ __device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], con
         az = fmaf(w[0][4 * m + 2], x.z, az); ac = fmaf(w[1][4 * m + 2], x.z, ac);
         az = fmaf(w[0][4 * m + 3], x.w, az); ac = fmaf(w[1][4 * m + 3], x.w, ac);
     }
-    az = sum4(az); ac = sum4(ac);
+    // the two quad sums transposed: a lane of even parity keeps its gate partial and hands over its candidate partial, a lane of
+    // odd parity the reverse, so two DPP steps leave the gate sum in lanes 0 / 2 and the candidate sum in lanes 1 / 3 - each
+    // associated (p0 + p1) + (p2 + p3) as sum4 forms it (bit-identical), without the select between two full sums
+    const float sq = quad_sum_by_parity(pr ? ac : az, pr ? az : ac);
     __builtin_amdgcn_sched_barrier(0);              // keep the gate epilogue behind the reduction
     if (p < 2) {
-        const float sa = (p == 0 ? az : ac) + e_old;
+        const float sa = sq + e_old;
         const float v = e_gx * sa;
-        float res;
-        if (fabsf(v) > 9.02f && p == 1) {
-            res = copysignf(1.f, v);                                       // tanh saturated in fp32
-        } else {
-            // (plain v_exp_f32 / v_rcp_f32 without the corrections - nine instructions fewer on the chain - measured the same step
-            //  time: the phase waits for both groups, not for this arithmetic)
-            const float e = exp_c(p == 0 ? -v : -2.f * fabsf(v));
-            const float r = rcp_c(1.f + e);
-            res = p == 0 ? r : copysignf((1.f - e) * r, v);                // z | tanh
-        }
+        // One straight-line epilogue, no branch around the transcendentals for a saturated tanh lane (tanh_c's |v| > 9.02 test:
+        // the gate lanes never took it, so it saved no instruction and put a compare, an exec-mask save and a branch on the chain).
+        // The result does not need it: for |v| > 9.02, e <= 1.5e-8 < 2^-25, so 1 + e, rcp_c(1), and 1 - e are all exactly 1 and
+        // the line below returns copysign(1, v) - the parent's bits for every finite v.  The clamp at 64 changes no finite result
+        // (e is already 0 in fp32 from |v| = 52) and keeps exp_c's correction term from becoming 0 * inf where v * log2(e)
+        // overflows: |v| >= 1.18e38 and +-inf give +-1 as before.  A NaN pre-activation now gives +-1 in the candidate (v_min
+        // drops it) where the parent passed it on; the gate lane of the same channel still passes its own.
+        // (plain v_exp_f32 / v_rcp_f32 without the corrections - nine instructions fewer on the chain - measured the same step
+        //  time: the phase waits for both groups, not for this arithmetic)
+        const float e = exp_c(p == 0 ? -v : -2.f * fminf(fabsf(v), 64.f));
+        const float r = rcp_c(1.f + e);
+        const float res = p == 0 ? r : copysignf((1.f - e) * r, v);        // z | tanh
         const float c = dpp_f<0xF5>(res);                                  // quad_perm [1,1,3,3]: lane 0 <- lane 1
         if (p == 0) {
             const float hn = (1.f - res) * c + res * e_hp;
@@ -175,6 +192,44 @@ template <class T, int LAYER, int MB = 4>
 __device__ __forceinline__ void older_b(float* lds, const float (&w)[2][16], const int qn, const int tb) {
     float az, ac;
     older_sum<T, LAYER, MB>(lds, w, qn, tb, az, ac);
+    if ((tb & 3) < 2) older_store<T, LAYER>(lds, qn, tb, az, ac);
+}
+// The last layer's product as group A forms it in skip-fin (older_b<T, L - 1, 2>), with the operands of input quads 0 and 1 - the
+// ring row and group B's half of the matrix in o_wl, six 16-byte reads - requested a phase early (older_last_rows behind layer 5's
+// hand-off write and in front of lds_barrier_keep<6>, older_last_x behind the barrier): h_4(qn - 32) is 31 steps old and o_wl is
+// written once, so neither depends on that barrier.  Quads 2 and 3 are read as before; the order of the multiply-adds is older_sum's.
+template <class T>
+__device__ __forceinline__ void older_last_rows(const float* lds, const int qn, const int tb, float4 (&x)[2], float4 (&w)[2][2]) {
+    constexpr int LAYER = L - 1, dil = 1 << LAYER, R = T::ring_len(LAYER);
+    const float* row = lds + T::o_ring + T::ring_off(LAYER) + ((qn - dil) & (R - 1)) * H + 16 * (tb & 3);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        x[m] = *reinterpret_cast<const float4*>(row + 4 * m);
+        w[m][0] = *reinterpret_cast<const float4*>(lds + T::o_wl + (m * NG + tb) * 4);
+        w[m][1] = *reinterpret_cast<const float4*>(lds + T::o_wl + ((4 + m) * NG + tb) * 4);
+    }
+}
+template <class T>
+__device__ __forceinline__ void older_last_x(float* lds, const float4 (&xe)[2], const float4 (&we)[2][2], const int qn, const int tb) {
+    constexpr int LAYER = L - 1, dil = 1 << LAYER, R = T::ring_len(LAYER);
+    const float* row = lds + T::o_ring + T::ring_off(LAYER) + ((qn - dil) & (R - 1)) * H + 16 * (tb & 3);
+    float az = 0.f, ac = 0.f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        float4 x, w0, w1;
+        if (m < 2) { x = xe[m]; w0 = we[m][0]; w1 = we[m][1]; }
+        else {
+            x = *reinterpret_cast<const float4*>(row + 4 * m);
+            w0 = *reinterpret_cast<const float4*>(lds + T::o_wl + (m * NG + tb) * 4);
+            w1 = *reinterpret_cast<const float4*>(lds + T::o_wl + ((4 + m) * NG + tb) * 4);
+        }
+        az = fmaf(w0.x, x.x, az); ac = fmaf(w1.x, x.x, ac);
+        az = fmaf(w0.y, x.y, az); ac = fmaf(w1.y, x.y, ac);
+        az = fmaf(w0.z, x.z, az); ac = fmaf(w1.z, x.z, ac);
+        az = fmaf(w0.w, x.w, az); ac = fmaf(w1.w, x.w, ac);
+        if (m == 1) __builtin_amdgcn_sched_barrier(0);
+    }
+    az = sum4(az); ac = sum4(ac);
     if ((tb & 3) < 2) older_store<T, LAYER>(lds, qn, tb, az, ac);
 }
 // several layers at once: one basic block of independent chains (the stores' lane branch between them kept the scheduler from
@@ -246,35 +301,38 @@ __device__ __forceinline__ void skip_issue_b(__amdgpu_buffer_rsrc_t wsk2, float4
         for (int mm = 0; mm < 4; ++mm)
             wsl[ps * 4 + mm] = buf_ld4(wsk2, (unsigned)((r + 64 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 4 + mm) * S) * 64u + step0);
 }
-// the rolling request of a layer phase: slice LAYER - 1 is consumed half by half (inputs 16 mm .., mm = 0, 1, then 2, 3, both rows),
-// and behind each half the same half of slice LAYER is requested into the four float4 it has just freed (a second buffer does
-// not fit beside the 160 weight registers).  The four waves' 32 KB of requests then no longer queue at the end of the phase, in
-// front of the barrier: the first half leaves behind the phase's first sixteen multiply-adds.  The order of the multiply-adds inside each sacc
-// chain is that of a whole-slice pass.  (Measured per launch of 66 000 steps: whole slice behind its consumption 208.0 ms,
-// halves 188.5 ms, quarters 200.6 ms, eighths 226.1 ms.)
+// the rolling request of a layer phase: slice LAYER - 1 is consumed quarter by quarter (inputs 16 mm .., mm = 0 .. 3, both rows),
+// and behind each quarter the same quarter of slice LAYER is requested into the two float4 it has just freed (a second buffer
+// does not fit beside the 160 weight registers).  The four waves' 32 KB of requests then no longer queue at the end of the
+// phase, in front of the barrier: the first quarter leaves behind the phase's first eight multiply-adds.  All four input quads are
+// read at the head of the phase - the row o_hcat[LAYER - 1] is complete at the barrier -, so the phase pays one LDS round trip
+// and no piece waits for a read issued behind the previous piece's requests.  The order of the multiply-adds inside each sacc
+// chain is that of a whole-slice pass.
+// (Measured per launch of 66 000 steps with the inputs read piece by piece, each pair of reads behind the previous piece's
+//  requests: whole slice behind its consumption 208.0 ms, halves 188.5 ms, quarters 200.6 ms, eighths 226.1 ms - every extra
+//  piece paid another exposed round trip.  In this build, one session: halves 175.5 ms and quarters 176.9 ms with the reads
+//  piece by piece, quarters 166.2 ms and eighths - one row of one quad - 166.2 ms with the four reads at the head; in another
+//  session, both without layer_a's transposed reduction: halves 172.5 ms, quarters 167.4 ms with the reads at the head.  DESIGN 3.1.)
 template <class T, int LAYER>
 __device__ __forceinline__ void skip_roll_b(const float* lds, __amdgpu_buffer_rsrc_t wsk2, float4 (&wsl)[8], float (&sacc)[2], const int tb,
                                             const unsigned step0) {
     static_assert(LAYER >= 1 && LAYER < L, "slice LAYER - 1 in flight, slice LAYER to request");
     const int r = tb >> 2, hp = tb & 3;
+    float4 xs[4];
 #pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
+    for (int mm = 0; mm < 4; ++mm) xs[mm] = *reinterpret_cast<const float4*>(lds + T::o_hcat + (LAYER - 1) * H + 16 * mm + 4 * hp);
 #pragma unroll
-        for (int mm = 2 * hf; mm < 2 * hf + 2; ++mm) {
-            const float4 x = *reinterpret_cast<const float4*>(lds + T::o_hcat + (LAYER - 1) * H + 16 * mm + 4 * hp);
+    for (int mm = 0; mm < 4; ++mm) {
 #pragma unroll
-            for (int ps = 0; ps < 2; ++ps) {
-                const float4 w = wsl[ps * 4 + mm];
-                sacc[ps] = fmaf(w.x, x.x, sacc[ps]); sacc[ps] = fmaf(w.y, x.y, sacc[ps]);
-                sacc[ps] = fmaf(w.z, x.z, sacc[ps]); sacc[ps] = fmaf(w.w, x.w, sacc[ps]);
-            }
+        for (int ps = 0; ps < 2; ++ps) {
+            const float4 x = xs[mm], w = wsl[ps * 4 + mm];
+            sacc[ps] = fmaf(w.x, x.x, sacc[ps]); sacc[ps] = fmaf(w.y, x.y, sacc[ps]);
+            sacc[ps] = fmaf(w.z, x.z, sacc[ps]); sacc[ps] = fmaf(w.w, x.w, sacc[ps]);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int mm = 2 * hf; mm < 2 * hf + 2; ++mm)
-#pragma unroll
-            for (int ps = 0; ps < 2; ++ps)
-                wsl[ps * 4 + mm] = buf_ld4(wsk2, (unsigned)((r + 64 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 4 + mm) * S) * 64u + step0);
+        for (int ps = 0; ps < 2; ++ps)
+            wsl[ps * 4 + mm] = buf_ld4(wsk2, (unsigned)((r + 64 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 4 + mm) * S) * 64u + step0);
         __builtin_amdgcn_sched_barrier(0);
     }
     // pin the partial sums to this phase: only the end of the step uses them, and the optimiser otherwise sinks all six slices'
@@ -512,12 +570,12 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     // one layer phase: group A runs the chain, group B prepares position q + 1 (and, during generation, accumulates out_skip)
     // (GEN: a generation step - group B's older-tap products for position q + 1 then sit in the merged and the out_1 phase, and
     //  layer 5's is group A's; in the prologue group B forms layer LAYER's in this phase.  X0: the row of h0(q) layer 0 reads)
-#define SWN_PHASE(LAYER, GEN, X0)                                                                                     \
+#define SWN_PHASE_WORK(LAYER, GEN, X0)                                                                                \
     if constexpr (grpA) layer_a<T, LAYER>(lds, wreg[LAYER], q, wj, pb, po, tg,                                         \
                                           LAYER == 0 ? (X0) : lds + T::o_ring + T::ring_off(LAYER) +                   \
                                                                   (q & (T::ring_len(LAYER) - 1)) * H);                 \
     else {                                                                                                             \
-        if (GEN) {   /* slice 0 is requested whole at the start of the step; every later slice rolls in, half by half, behind */ \
+        if (GEN) {   /* slice 0 is requested whole at the start of the step; every later slice rolls in by quarters, behind    */ \
                      /* the multiply-adds that free its registers (both slices live at once are 64 registers beside the 160   */ \
                      /* of the weights)                                                                                       */ \
             if (LAYER == 0) skip_issue_b<0>(wsk2, wsl, tg, step0);                                                     \
@@ -527,8 +585,8 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         if (!(GEN)) older_b<T, LAYER>(lds, wreg[LAYER < NWR ? LAYER : 0], q + 1, tg);                                  \
         else if (LAYER == 0) older_bn<T>(OlderMerged{}, lds, wreg, q + 1, tg);                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
-    }                                                                                                                  \
-    if (GEN) { SWN_BAR(LAYER) } else lds_barrier();
+    }
+#define SWN_PHASE(LAYER, GEN, X0) SWN_PHASE_WORK(LAYER, GEN, X0) if (GEN) { SWN_BAR(LAYER) } else lds_barrier();
 
     // ---- prologue: seed positions 0 .. rf - 1 (cswnv_shift1.py:321-334)
 #pragma unroll 1
@@ -603,7 +661,23 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         // is not ready before the first barrier); all six beside the out_skip slices made group B take 1 050 cycles per layer phase
         // against group A's 710
         SWN_PHASE(0, true, x0) SWN_PHASE(1, true, x0) SWN_PHASE(2, true, x0) SWN_PHASE(3, true, x0)
-        SWN_PHASE(4, true, x0) SWN_PHASE(5, true, x0)
+        SWN_PHASE(4, true, x0)
+        // layer 5, and behind group A's hand-off write of it the first half of the operands of the product group A forms in
+        // skip-fin (older_last_rows): they ride through barrier 5 in the registers layer 5 has freed.  lpc 0 only: with lpc 4 the
+        // 24 registers spill (2 - 4 VGPRs, 12 bytes of scratch in all five lpc 4 kernels), and those keep the parent's form
+        constexpr bool EARLY5 = T::LPC == 0;
+        float4 xl[2], wl[2][2];
+        SWN_PHASE_WORK(5, true, x0)
+        if constexpr (grpA && EARLY5) {
+            SWN_PRE(5)
+            lds_fence_compiler();
+            __builtin_amdgcn_sched_barrier(0);
+            older_last_rows<T>(lds, q + 1, tg + (int)step0, xl, wl);   // (opaque zero: no address of it stays resident)
+            __builtin_amdgcn_sched_barrier(0);
+            SWN_BAR_KEEP(5, 6)
+        } else {
+            SWN_BAR(5)
+        }
         // out_skip: the last slice and the reduction (group B).  Group A, otherwise idle here, forms layer 5's older-tap product of
         // position q + 1 from group B's half in LDS, with group B's thread-to-row mapping and summation order (bit-identical): its
         // operand h_4(q - 31) is 31 steps old, o_old[(q + 1) & 1][5] was last read in layer 5 of step q - 1 and is next read
@@ -625,7 +699,8 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             __builtin_amdgcn_sched_barrier(0);
             SWN_BAR_KEEP(6, 12)
         } else {
-            older_b<T, L - 1, 2>(lds, wreg[L - 1], q + 1, tg + (int)step0);   // (opaque zero: no address of it stays resident)
+            if constexpr (EARLY5) older_last_x<T>(lds, xl, wl, q + 1, tg + (int)step0);
+            else older_b<T, L - 1, 2>(lds, wreg[L - 1], q + 1, tg + (int)step0);   // (opaque zero: no address of it stays resident)
             if constexpr (ROLL1) {
                 SWN_PRE(6)
                 lds_fence_compiler();
@@ -788,6 +863,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         }
     }
 #undef SWN_PHASE
+#undef SWN_PHASE_WORK
 #undef SWN_BAR
 #undef SWN_WAIT_STAMP
 #undef SWN_PRE
