@@ -160,22 +160,6 @@ SIGNATURES = {
     "swn_decode_pool_chunk_models": (c_int, [POINTER(NetDesc), POINTER(c_void_p), c_int, POINTER(c_int32), c_int,
                                              POINTER(DecodePoolEntry), c_int, POINTER(DecodeIO), c_void_p, c_void_p, c_void_p,
                                              c_int, c_void_p]),
-    "swn_decode_w16_bytes": (c_size_t, [POINTER(NetDesc)]),
-    "swn_pack_decode_w16": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p]),
-    "swn_decode_w16": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecodeIO),
-                               c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "swn_decode_chunk_w16": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                     POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "swn_decode_pool_chunk_w16": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodePoolEntry), c_int,
-                                          POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "swn_decode_w8_bytes": (c_size_t, [POINTER(NetDesc)]),
-    "swn_pack_decode_w8": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p]),
-    "swn_decode_w8": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecodeIO),
-                              c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "swn_decode_chunk_w8": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                    POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "swn_decode_pool_chunk_w8": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodePoolEntry), c_int,
-                                         POINTER(DecodeIO), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "swn_e4m3_table": (c_int, [c_void_p, c_float, c_void_p]),
     "swn_decode_stepped_prologue_iterations": (c_int, [POINTER(NetDesc)]),
     "swn_decode_pool_stepped_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodeSteppedPoolEntry), c_int,
@@ -256,6 +240,16 @@ SIGNATURES = {
     "swn_resample_state_floats": (c_size_t, [c_int, c_int]),
     "swn_resample_chunk": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, POINTER(ResampleEntry), c_int, c_void_p]),
 }
+
+
+# the stored formats of the streamed head matrices (ops.DECODE_IMAGES): the size and the packing of the image, and the three
+# decode calls with the image between the variant and the stream
+for _s in ("w16", "w8"):
+    SIGNATURES[f"swn_decode_{_s}_bytes"] = (c_size_t, [POINTER(NetDesc)])
+    SIGNATURES[f"swn_pack_decode_{_s}"] = (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p])
+    for _n in ("swn_decode", "swn_decode_chunk", "swn_decode_pool_chunk"):
+        _res, _args = SIGNATURES[_n]
+        SIGNATURES[f"{_n}_{_s}"] = (_res, _args[:-1] + [c_void_p] + _args[-1:])
 
 
 STAMP_PATH = os.path.join(_HERE, "libswn_hip.so.srchash")

@@ -14,6 +14,7 @@
 //   head   = out_2(relu(out_1(relu(sum_l out_skip_l(h_l)))))   at the last position of a step
 // The "true zero" left padding of the reference prologue is reproduced by zero-initialised
 // rings: a slot that would hold a negative position has not been written yet.
+#include <cstdio>
 #include <hip/hip_runtime.h>
 #include "swn_decode_internal.hpp"
 
@@ -437,29 +438,19 @@ int resolve_kernel(const SwnGeom& g, int batch, int variant) {
     return KSEL_GENERIC;
 }
 
-// the *_w16 calls run on the symmetric BL6 kernel alone: SWN_OK when `variant` resolves to it for (net, batch)
-int w16_kernel_check(const SwnGeom& g, int batch, int variant, const char* where) {
+// the *_w16 / *_w8 calls run on the symmetric BL6 kernel alone: SWN_OK when `variant` resolves to it for (net, batch)
+int image_kernel_check(int wk, const SwnGeom& g, int batch, int variant, const char* where) {
+    static const char* const word[] = {"fp32", "bf16", "e4m3"};   // by WK_*
     const int k = resolve_kernel(g, batch, variant);
     if (k == KSEL_BL6) return SWN_OK;
+    char detail[256];
     if (k == KSEL_BL6W)
-        swn_set_error_detail(where, "bf16 weights run on the symmetric BL6 kernel; this net resolves to the wave-specialised "
-                                    "kernel with this variant: pass variant = 6");
+        snprintf(detail, sizeof detail, "%s weights run on the symmetric BL6 kernel; this net resolves to the wave-specialised "
+                                        "kernel with this variant: pass variant = 6", word[wk]);
     else
-        swn_set_error_detail(where, "bf16 weights run on the symmetric BL6 kernel only (variant 0, 2 or 6 on a net of its "
-                                    "class); the stepped and generic kernels are not served");
-    return SWN_E_UNSUPPORTED;
-}
-
-// ... and so do the *_w8 calls
-int w8_kernel_check(const SwnGeom& g, int batch, int variant, const char* where) {
-    const int k = resolve_kernel(g, batch, variant);
-    if (k == KSEL_BL6) return SWN_OK;
-    if (k == KSEL_BL6W)
-        swn_set_error_detail(where, "e4m3 weights run on the symmetric BL6 kernel; this net resolves to the wave-specialised "
-                                    "kernel with this variant: pass variant = 6");
-    else
-        swn_set_error_detail(where, "e4m3 weights run on the symmetric BL6 kernel only (variant 0, 2 or 6 on a net of its "
-                                    "class); the stepped and generic kernels are not served");
+        snprintf(detail, sizeof detail, "%s weights run on the symmetric BL6 kernel only (variant 0, 2 or 6 on a net of its "
+                                        "class); the stepped and generic kernels are not served", word[wk]);
+    swn_set_error_detail(where, detail);
     return SWN_E_UNSUPPORTED;
 }
 
@@ -655,94 +646,96 @@ extern "C" int swn_decode_pool_chunk_models(const swn_net_desc* d, const float* 
     return run_call(k, c);
 }
 
-// ---- bf16 storage of the streamed head matrices: the same rules, an image, and the symmetric BL6 kernel alone -----------
-extern "C" int swn_decode_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
-                              int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, int variant,
-                              const void* w16, void* stream_) {
+// ---- bf16 / FP8 (E4M3) storage of the streamed head matrices: the same rules, the image of swn_pack_decode_w16 / _w8 in
+// format `wk`, and the symmetric BL6 kernel alone; `where` names the entry point
+namespace {
+
+int oneshot_image(int wk, const void* image, const char* where, const swn_net_desc* d, const float* packed, const float* cond,
+                  int batch, int n_frames, int n_steps, const swn_decode_io* io, float* state, void* out, float* heads,
+                  int variant, void* stream_) {
     SwnDecodeCall c;
     int rc = oneshot_check(c, d, packed, cond, batch, n_frames, n_steps, io, state, out, heads, stream_);
     if (rc < 0) return rc;
-    if (!w16) return SWN_E_BADARG;
-    rc = w16_kernel_check(c.g, batch, variant, "swn_decode_w16");
+    if (!image) return SWN_E_BADARG;
+    rc = image_kernel_check(wk, c.g, batch, variant, where);
     if (rc < 0) return rc;
     if (n_steps == 0) return SWN_OK;
-    c.w16 = w16;
+    c.wk = wk; c.image = image;
     return run_call(KSEL_BL6, c);
+}
+
+int chunk_image(int wk, const void* image, const char* where, const swn_net_desc* d, const float* packed, const float* cond,
+                int batch, int n_frames, int step0, int n_steps, int flags, const swn_decode_io* io, float* session, void* out,
+                float* heads, int variant, void* stream_) {
+    SwnDecodeCall c;
+    int rc = chunk_check(c, d, packed, cond, batch, n_frames, step0, n_steps, flags, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (!image) return SWN_E_BADARG;
+    rc = image_kernel_check(wk, c.g, batch, variant, where);
+    if (rc < 0) return rc;
+    if (chunk_is_idle(c)) return SWN_OK;
+    c.wk = wk; c.image = image;
+    return run_call(KSEL_BL6, c);
+}
+
+int pool_image(int wk, const void* image, const char* where, const swn_net_desc* d, const float* packed, int capacity,
+               const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io, float* session, void* out,
+               float* heads, int variant, void* stream_) {
+    SwnDecodeCall c;
+    SwnPoolTable t;
+    bool work;
+    int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (!packed || !image) return SWN_E_BADARG;
+    rc = image_kernel_check(wk, c.g, capacity, variant, where);
+    if (rc < 0) return rc;
+    if (!work) return SWN_OK;                              // every slot stays as it is
+    c.packed = packed; c.wk = wk; c.image = image;
+    return run_call(KSEL_BL6, c);
+}
+
+}  // namespace
+
+extern "C" int swn_decode_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
+                              int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, int variant,
+                              const void* w16, void* stream_) {
+    return oneshot_image(WK_BF16, w16, "swn_decode_w16", d, packed, cond, batch, n_frames, n_steps, io, state, out, heads, variant,
+                         stream_);
 }
 
 extern "C" int swn_decode_chunk_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
                                     int step0, int n_steps, int flags, const swn_decode_io* io, float* session, void* out,
                                     float* heads, int variant, const void* w16, void* stream_) {
-    SwnDecodeCall c;
-    int rc = chunk_check(c, d, packed, cond, batch, n_frames, step0, n_steps, flags, io, session, out, heads, stream_);
-    if (rc < 0) return rc;
-    if (!w16) return SWN_E_BADARG;
-    rc = w16_kernel_check(c.g, batch, variant, "swn_decode_chunk_w16");
-    if (rc < 0) return rc;
-    if (chunk_is_idle(c)) return SWN_OK;
-    c.w16 = w16;
-    return run_call(KSEL_BL6, c);
+    return chunk_image(WK_BF16, w16, "swn_decode_chunk_w16", d, packed, cond, batch, n_frames, step0, n_steps, flags, io, session,
+                       out, heads, variant, stream_);
 }
 
 extern "C" int swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* packed, int capacity,
                                          const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
                                          float* session, void* out, float* heads, int variant, const void* w16,
                                          void* stream_) {
-    SwnDecodeCall c;
-    SwnPoolTable t;
-    bool work;
-    int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
-    if (rc < 0) return rc;
-    if (!packed || !w16) return SWN_E_BADARG;
-    rc = w16_kernel_check(c.g, capacity, variant, "swn_decode_pool_chunk_w16");
-    if (rc < 0) return rc;
-    if (!work) return SWN_OK;                              // every slot stays as it is
-    c.packed = packed; c.w16 = w16;
-    return run_call(KSEL_BL6, c);
+    return pool_image(WK_BF16, w16, "swn_decode_pool_chunk_w16", d, packed, capacity, entries, n_entries, io, session, out, heads,
+                      variant, stream_);
 }
 
-// ---- FP8 (E4M3) storage of the streamed head matrices: the rules of the *_w16 calls over the image of swn_pack_decode_w8 --
 extern "C" int swn_decode_w8(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
                              int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, int variant,
                              const void* w8, void* stream_) {
-    SwnDecodeCall c;
-    int rc = oneshot_check(c, d, packed, cond, batch, n_frames, n_steps, io, state, out, heads, stream_);
-    if (rc < 0) return rc;
-    if (!w8) return SWN_E_BADARG;
-    rc = w8_kernel_check(c.g, batch, variant, "swn_decode_w8");
-    if (rc < 0) return rc;
-    if (n_steps == 0) return SWN_OK;
-    c.w8 = w8;
-    return run_call(KSEL_BL6, c);
+    return oneshot_image(WK_E4M3, w8, "swn_decode_w8", d, packed, cond, batch, n_frames, n_steps, io, state, out, heads, variant,
+                         stream_);
 }
 
 extern "C" int swn_decode_chunk_w8(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
                                    int step0, int n_steps, int flags, const swn_decode_io* io, float* session, void* out,
                                    float* heads, int variant, const void* w8, void* stream_) {
-    SwnDecodeCall c;
-    int rc = chunk_check(c, d, packed, cond, batch, n_frames, step0, n_steps, flags, io, session, out, heads, stream_);
-    if (rc < 0) return rc;
-    if (!w8) return SWN_E_BADARG;
-    rc = w8_kernel_check(c.g, batch, variant, "swn_decode_chunk_w8");
-    if (rc < 0) return rc;
-    if (chunk_is_idle(c)) return SWN_OK;
-    c.w8 = w8;
-    return run_call(KSEL_BL6, c);
+    return chunk_image(WK_E4M3, w8, "swn_decode_chunk_w8", d, packed, cond, batch, n_frames, step0, n_steps, flags, io, session,
+                       out, heads, variant, stream_);
 }
 
 extern "C" int swn_decode_pool_chunk_w8(const swn_net_desc* d, const float* packed, int capacity,
                                         const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
                                         float* session, void* out, float* heads, int variant, const void* w8,
                                         void* stream_) {
-    SwnDecodeCall c;
-    SwnPoolTable t;
-    bool work;
-    int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
-    if (rc < 0) return rc;
-    if (!packed || !w8) return SWN_E_BADARG;
-    rc = w8_kernel_check(c.g, capacity, variant, "swn_decode_pool_chunk_w8");
-    if (rc < 0) return rc;
-    if (!work) return SWN_OK;                              // every slot stays as it is
-    c.packed = packed; c.w8 = w8;
-    return run_call(KSEL_BL6, c);
+    return pool_image(WK_E4M3, w8, "swn_decode_pool_chunk_w8", d, packed, capacity, entries, n_entries, io, session, out, heads,
+                      variant, stream_);
 }

@@ -403,13 +403,12 @@ __device__ __forceinline__ void tiled_matvec(__amdgpu_buffer_rsrc_t wt, const fl
     }
 }
 
-template <bool POOL, bool MODELS, int WK = WK_F32> struct B6ArgsOf { using type = Bl6Args; };
+template <bool POOL, bool MODELS, int WK = WK_F32> struct B6ArgsOf;
+template <> struct B6ArgsOf<false, false> { using type = Bl6Args; };
 template <> struct B6ArgsOf<true, false> { using type = Bl6PoolArgs; };
 template <> struct B6ArgsOf<true, true> { using type = Bl6PoolModelsArgs; };
-template <> struct B6ArgsOf<false, false, WK_BF16> { using type = Bl6W16Args; };
-template <> struct B6ArgsOf<true, false, WK_BF16> { using type = Bl6PoolW16Args; };
-template <> struct B6ArgsOf<false, false, WK_E4M3> { using type = Bl6W8Args; };
-template <> struct B6ArgsOf<true, false, WK_E4M3> { using type = Bl6PoolW8Args; };
+template <int WK> struct B6ArgsOf<false, false, WK> { using type = Bl6ImageArgs; };       // every stored format but fp32
+template <int WK> struct B6ArgsOf<true, false, WK> { using type = Bl6PoolImageArgs; };
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6Args& launch, const Bl6Args&) { return launch; }
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, const Bl6Args& entry) { return entry; }
 
@@ -420,9 +419,9 @@ __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, con
 // window come from the session instead of the prologue, and they go back to it at the end.  The step itself is the same code.
 // POOL (with STREAM): one entry of a decode pool (swn_decode_pool_chunk); `a` holds the workgroup's entry as a batch-1 chunk
 // (swn_pool_entry_args), b = 0.  MODELS (with POOL): the entry's weights are those of its model (SwnPoolModels).
-// WK = WK_BF16 (W16; with EXT, without MODELS): out_skip, out_1 and the softmax out_2 stream from the bf16 image ka.w16 instead
+// WK = WK_BF16 (W16; with EXT, without MODELS): out_skip, out_1 and the softmax out_2 stream from the bf16 image ka.img instead
 // of the fp32 lane-tiled copies, and the LDS-resident out_1 slices are widened from it; every other load and every FMA is the
-// fp32 code.  WK = WK_E4M3 (W8): the same over the FP8 image ka.w8, whose row scales are copied into LDS behind the carve.
+// fp32 code.  WK = WK_E4M3 (W8): the same over the FP8 image ka.img, whose row scales are copied into LDS behind the carve.
 template <class T, bool STREAM = false, bool POOL = false, bool MODELS = false, int WK = WK_F32>
 __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL, MODELS, WK>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -467,7 +466,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
         if constexpr (W16) {
             // the resident out_1 slices hold the rounded values, widened once: slice mm is half mm & 1 of image slice mm / 2
             const unsigned* w1i = reinterpret_cast<const unsigned*>(
-                static_cast<const char*>(ka.w16) + w16_layout(S, T::O1, T::NO, false).w1);
+                static_cast<const char*>(ka.img) + w16_layout(S, T::O1, T::NO, false).w1);
             for (int e = tid; e < T::W1L * T::O1 * 16; e += NT) {
                 const int mm = e / (T::O1 * 16);
                 const unsigned w = w1i[(mm >> 1) * T::O1 * 16 + e % (T::O1 * 16)];
@@ -476,7 +475,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
         } else if constexpr (W8) {
             // ... or stay codes: the first W1L / 4 image slices as they lie in the image (bit patterns, not numbers)
             const unsigned* w1i = reinterpret_cast<const unsigned*>(
-                static_cast<const char*>(ka.w8) + w8_layout(S, T::O1, T::NO, false).w1);
+                static_cast<const char*>(ka.img) + w8_layout(S, T::O1, T::NO, false).w1);
             unsigned* dst = reinterpret_cast<unsigned*>(lds + T::o_w1l);
             for (int e = tid; e < (T::W1L / 4) * T::O1 * 16; e += NT) dst[e] = w1i[e];
         } else
@@ -484,7 +483,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
     }
     if constexpr (W8) {   // the rows' 2^-e: the three scale sections of the image are one run of floats
         const float* sc = reinterpret_cast<const float*>(
-            static_cast<const char*>(ka.w8) + w8_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX).ssk);
+            static_cast<const char*>(ka.img) + w8_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX).ssk);
         for (int e = tid; e < w8_sc_floats<T>(); e += NT) lds[w8_o_sc<T>() + e] = sc[e];
     }
     // conditioning frames are copied 16 B per lane through a buffer resource (32-bit offsets)
@@ -681,8 +680,8 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
     [[maybe_unused]] const Bl6W16Layout y16 = w16_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX);
     [[maybe_unused]] const Bl6W8Layout y8 = w8_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX);
     auto wsrc = [&](size_t f32_off, [[maybe_unused]] size_t w16_off, [[maybe_unused]] size_t w8_off) -> const void* {
-        if constexpr (W16) return static_cast<const char*>(ka.w16) + w16_off;
-        else if constexpr (W8) return static_cast<const char*>(ka.w8) + w8_off;
+        if constexpr (W16) return static_cast<const char*>(ka.img) + w16_off;
+        else if constexpr (W8) return static_cast<const char*>(ka.img) + w8_off;
         else return P + f32_off;
     };
     const __amdgpu_buffer_rsrc_t wsk2 = make_rsrc(wsrc(a.y.wsk2, y16.wsk, y8.wsk), (unsigned)(L * S * 64 * WB));
@@ -1053,8 +1052,7 @@ template <int WK>
 int launch_utts(const SwnDecodeCall& c, const char* where) {
     typename B6ArgsOf<false, false, WK>::type a;
     fill_args(a, c);
-    if constexpr (WK == WK_BF16) a.w16 = c.w16;
-    if constexpr (WK == WK_E4M3) a.w8 = c.w8;
+    if constexpr (WK != WK_F32) a.img = c.image;
     return with_tr(c.g, [&](auto t) {
         using T = decltype(t);
         using X = typename T::Ext;
@@ -1074,8 +1072,7 @@ int launch_pool(const SwnDecodeCall& c, const char* where) {
     fill_args(p.c, c);
     p.t = *c.pool;
     if constexpr (MODELS) p.m = *c.models;
-    if constexpr (WK == WK_BF16) p.w16 = c.w16;
-    if constexpr (WK == WK_E4M3) p.w8 = c.w8;
+    if constexpr (WK != WK_F32) p.img = c.image;
     return with_tr(c.g, [&](auto tr) {
         using T = typename decltype(tr)::Ext;
         constexpr size_t lds = WK == WK_E4M3 ? w8_lds_bytes<T>() : T::lds_bytes;
@@ -1083,31 +1080,45 @@ int launch_pool(const SwnDecodeCall& c, const char* where) {
     });
 }
 
-}  // namespace
-
-// ---- bf16 storage of the streamed head matrices (swn_decode_w16 / swn_decode_chunk_w16 / swn_decode_pool_chunk_w16)
-extern "C" size_t swn_decode_w16_bytes(const swn_net_desc* d) {
+// bytes of the image of format `wk` for net `d`; 0: the symmetric kernel does not serve the net
+size_t image_bytes(const swn_net_desc* d, int wk) {
     SwnGeom g;
     if (swn_make_geom(d, &g) < 0) return 0;
     size_t n = 0;
     with_tr(g, [&](auto t) {
         using T = decltype(t);
-        n = w16_layout(T::S, T::O1, T::NO, T::KIND == SWN_KIND_SOFTMAX).total;
+        constexpr bool soft = T::KIND == SWN_KIND_SOFTMAX;
+        n = wk == WK_BF16 ? w16_layout(T::S, T::O1, T::NO, soft).total : w8_layout(T::S, T::O1, T::NO, soft).total;
         return SWN_OK;
     });
     return n;
 }
 
-extern "C" int swn_pack_decode_w16(const swn_net_desc* d, const float* packed, void* w16, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
+// what swn_pack_decode_w16 / _w8 check before they launch; on SWN_OK `g` and `y` are the net's geometry and packed layout
+int pack_image_check(const swn_net_desc* d, const float* packed, void* image, int wk, const char* where, const char* refusal,
+                     SwnGeom& g, SwnLayout& y) {
+    const int rc = swn_make_geom(d, &g);
     if (rc < 0) return rc;
-    if (!packed || !w16) return SWN_E_BADARG;
-    if (swn_decode_w16_bytes(d) == 0) {
-        swn_set_error_detail("swn_pack_decode_w16", "bf16 weights exist for the nets the symmetric BL6 kernel serves only");
+    if (!packed || !image) return SWN_E_BADARG;
+    if (image_bytes(d, wk) == 0) {
+        swn_set_error_detail(where, refusal);
         return SWN_E_UNSUPPORTED;
     }
-    SwnLayout y;
     swn_make_layout(&g, &y);
+    return SWN_OK;
+}
+
+}  // namespace
+
+// ---- bf16 storage of the streamed head matrices (swn_decode_w16 / swn_decode_chunk_w16 / swn_decode_pool_chunk_w16)
+extern "C" size_t swn_decode_w16_bytes(const swn_net_desc* d) { return image_bytes(d, WK_BF16); }
+
+extern "C" int swn_pack_decode_w16(const swn_net_desc* d, const float* packed, void* w16, void* stream_) {
+    SwnGeom g;
+    SwnLayout y;
+    const int rc = pack_image_check(d, packed, w16, WK_BF16, "swn_pack_decode_w16",
+                                    "bf16 weights exist for the nets the symmetric BL6 kernel serves only", g, y);
+    if (rc < 0) return rc;
     const bool soft = g.kind == SWN_KIND_SOFTMAX;
     const Bl6W16Layout y16 = w16_layout(g.S, g.O1, g.NO, soft);
     char* img = static_cast<char*>(w16);
@@ -1124,29 +1135,15 @@ extern "C" int swn_pack_decode_w16(const swn_net_desc* d, const float* packed, v
 }
 
 // ---- FP8 (E4M3) storage of the streamed head matrices (swn_decode_w8 / swn_decode_chunk_w8 / swn_decode_pool_chunk_w8)
-extern "C" size_t swn_decode_w8_bytes(const swn_net_desc* d) {
-    SwnGeom g;
-    if (swn_make_geom(d, &g) < 0) return 0;
-    size_t n = 0;
-    with_tr(g, [&](auto t) {
-        using T = decltype(t);
-        n = w8_layout(T::S, T::O1, T::NO, T::KIND == SWN_KIND_SOFTMAX).total;
-        return SWN_OK;
-    });
-    return n;
-}
+extern "C" size_t swn_decode_w8_bytes(const swn_net_desc* d) { return image_bytes(d, WK_E4M3); }
 
 // (the one call of the family that waits for its stream: a weight that is not finite is reported as SWN_E_BADARG)
 extern "C" int swn_pack_decode_w8(const swn_net_desc* d, const float* packed, void* w8, void* stream_) {
-    SwnGeom g; int rc = swn_make_geom(d, &g);
-    if (rc < 0) return rc;
-    if (!packed || !w8) return SWN_E_BADARG;
-    if (swn_decode_w8_bytes(d) == 0) {
-        swn_set_error_detail("swn_pack_decode_w8", "e4m3 weights exist for the nets the symmetric BL6 kernel serves only");
-        return SWN_E_UNSUPPORTED;
-    }
+    SwnGeom g;
     SwnLayout y;
-    swn_make_layout(&g, &y);
+    int rc = pack_image_check(d, packed, w8, WK_E4M3, "swn_pack_decode_w8",
+                              "e4m3 weights exist for the nets the symmetric BL6 kernel serves only", g, y);
+    if (rc < 0) return rc;
     const bool soft = g.kind == SWN_KIND_SOFTMAX;
     const Bl6W8Layout y8 = w8_layout(g.S, g.O1, g.NO, soft);
     char* img = static_cast<char*>(w8);
@@ -1187,12 +1184,17 @@ extern "C" int swn_e4m3_table(float* out, float scale, void* stream_) {
 
 // a checked call on the symmetric kernel (swn_decode.hip)
 int swn_decode_bl6_run(const SwnDecodeCall& c) {
-    if (c.pool && c.w8) return launch_pool<false, WK_E4M3>(c, "swn_decode_pool_chunk_w8(bl6)");
-    if (c.pool && c.w16) return launch_pool<false, WK_BF16>(c, "swn_decode_pool_chunk_w16(bl6)");
-    if (c.pool && c.models) return launch_pool<true, WK_F32>(c, "swn_decode_pool_chunk_models(bl6)");
-    if (c.pool) return launch_pool<false, WK_F32>(c, "swn_decode_pool_chunk(bl6)");
-    if (c.w8) return launch_utts<WK_E4M3>(c, "swn_decode_w8(bl6)");
-    return c.w16 ? launch_utts<WK_BF16>(c, "swn_decode_w16(bl6)") : launch_utts<WK_F32>(c, "swn_decode(bl6)");
+    if (c.pool) switch (c.wk) {
+        case WK_E4M3: return launch_pool<false, WK_E4M3>(c, "swn_decode_pool_chunk_w8(bl6)");
+        case WK_BF16: return launch_pool<false, WK_BF16>(c, "swn_decode_pool_chunk_w16(bl6)");
+        default: return c.models ? launch_pool<true, WK_F32>(c, "swn_decode_pool_chunk_models(bl6)")
+                                 : launch_pool<false, WK_F32>(c, "swn_decode_pool_chunk(bl6)");
+    }
+    switch (c.wk) {
+        case WK_E4M3: return launch_utts<WK_E4M3>(c, "swn_decode_w8(bl6)");
+        case WK_BF16: return launch_utts<WK_BF16>(c, "swn_decode_w16(bl6)");
+        default: return launch_utts<WK_F32>(c, "swn_decode(bl6)");
+    }
 }
 
 // streamed decode (swn_decode_chunk): per-utterance session floats of the symmetric kernel, 0 = not a BL6-class net

@@ -48,17 +48,17 @@ struct Bl6PoolModelsArgs : Bl6PoolArgs {
     SwnPoolModels m;
 };
 static_assert(sizeof(Bl6PoolModelsArgs) <= 4096, "kernel arguments are limited to 4 KB");
-// bf16 storage of the streamed head matrices (swn_decode_w16 and its chunk / pool forms, symmetric kernel only): the image
-// pointer rides behind the arguments of the fp32 launch in structs of its own, taken by instantiations of their own (W16), so
-// the fp32 kernels keep their arguments and their code.
-struct Bl6W16Args : Bl6Args {
-    const void* w16;
+// bf16 / FP8 storage of the streamed head matrices (swn_decode_w16, swn_decode_w8 and their chunk / pool forms, symmetric
+// kernel only): the image pointer rides behind the arguments of the fp32 launch in structs of its own, taken by instantiations
+// of their own (WK_BF16, WK_E4M3), so the fp32 kernels keep their arguments and their code.
+struct Bl6ImageArgs : Bl6Args {
+    const void* img;
 };
-struct Bl6PoolW16Args : Bl6PoolArgs {
-    const void* w16;
+struct Bl6PoolImageArgs : Bl6PoolArgs {
+    const void* img;
 };
-static_assert(sizeof(Bl6PoolW16Args) <= 4096, "kernel arguments are limited to 4 KB");
-// The image (swn_pack_decode_w16): the three lane-tiled copies wsk2 / w12 / w22 of the packed buffer rounded to bf16 (nearest
+static_assert(sizeof(Bl6PoolImageArgs) <= 4096, "kernel arguments are limited to 4 KB");
+// The bf16 image (swn_pack_decode_w16): the three lane-tiled copies wsk2 / w12 / w22 of the packed buffer rounded to bf16 (nearest
 // even), slices 2g and 2g + 1 of 16 inputs folded into one: section [NS / 2][rows][4 lanes][4 words], word j of a lane =
 // bf16(slice 2g, input 4 lane + j) in bits 0-15 | bf16(slice 2g + 1, input 4 lane + j) in bits 16-31.  A lane's 16-byte load
 // then carries what two of its fp32 loads carry, and it widens (<< 16, & 0xffff0000: exact) and accumulates them in the
@@ -75,17 +75,10 @@ inline __host__ __device__ Bl6W16Layout w16_layout(int S, int O1, int NO, bool s
     return y;
 }
 
-// FP8 (OCP E4M3FN) storage of the same matrices (swn_decode_w8 and its chunk / pool forms), likewise in structs and
-// instantiations of its own (W8).  Contract (include/swn_hip.h): per output row r of each matrix one power of two 2^e_r that
-// brings the row's largest magnitude into the top binade of E4M3 (<= 448), code = nearest E4M3 value of W 2^e_r, ties to even;
-// the kernel widens a code to exactly code * 2^-e_r in fp32 (w8_pair) and runs the fp32 kernel's FMAs in the fp32 kernel's order.
-struct Bl6W8Args : Bl6Args {
-    const void* w8;
-};
-struct Bl6PoolW8Args : Bl6PoolArgs {
-    const void* w8;
-};
-static_assert(sizeof(Bl6PoolW8Args) <= 4096, "kernel arguments are limited to 4 KB");
+// FP8 (OCP E4M3FN) storage of the same matrices (swn_decode_w8 and its chunk / pool forms).  Contract (include/swn_hip.h):
+// per output row r of each matrix one power of two 2^e_r that brings the row's largest magnitude into the top binade of E4M3
+// (<= 448), code = nearest E4M3 value of W 2^e_r, ties to even; the kernel widens a code to exactly code * 2^-e_r in fp32
+// (w8_pair) and runs the fp32 kernel's FMAs in the fp32 kernel's order.
 // The image (swn_pack_decode_w8): the W16 image with four slices of 16 inputs folded into a word instead of two - section
 // [NS / 4][rows][4 lanes][4 words], byte s of word j of a lane = code(slice 4g + s, input 4 lane + j), so a lane's 16-byte load
 // carries what four of its fp32 loads carry and v_cvt_scalef32_pk_f32_fp8 widens bytes (0, 1) or (2, 3) of a word at once.
@@ -105,8 +98,6 @@ inline __host__ __device__ Bl6W8Layout w8_layout(int S, int O1, int NO, bool sof
     y.total = y.s2 + (softmax ? (size_t)NO * 4 : 0);
     return y;
 }
-// storage of the streamed head matrices, the last template argument of the symmetric kernel
-enum : int { WK_F32 = 0, WK_BF16 = 1, WK_E4M3 = 2 };
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr int pow2ceil(int x) { int r = 1; while (r < x) r <<= 1; return r; }

@@ -22,14 +22,17 @@ static inline SwnNoise swn_pool_noise_of(const swn_decode_io* io) {
     return nz;
 }
 
+// storage of the streamed head matrices: of a call (SwnDecodeCall::wk), and the last template argument of the symmetric kernel
+enum : int { WK_F32 = 0, WK_BF16 = 1, WK_E4M3 = 2 };
+
 // One call of swn_decode, swn_decode_chunk, swn_decode_pool_chunk or one of their *_w16 / *_w8 / *_models forms, as the dispatcher's
 // checks (swn_decode.hip) leave it: every field is valid for the kernel the call resolved to, and a run function only fills
 // its kernel's argument struct from it and picks the instantiation.
 struct SwnDecodeCall {
     SwnGeom g;                                 // made once, by the check
     const float* packed = nullptr;             // (not read when `models` is set)
-    const void* w16 = nullptr;                 // the bf16 image of the streamed head matrices; null: fp32 weights
-    const void* w8 = nullptr;                  // ... or their FP8 (E4M3) image; at most one of the two is set
+    int wk = WK_F32;                           // how the streamed head matrices are stored (WK_*) ...
+    const void* image = nullptr;               // ... and their image in that format (swn_pack_decode_w16 / _w8); fp32: null
     const SwnPoolModels* models = nullptr;     // a pool over several models; null: one model
     const SwnPoolTable* pool = nullptr;        // the checked entry table of a pool launch; null: not a pool
     const float* cond = nullptr;               // (pool: every entry has its own)
@@ -48,7 +51,7 @@ struct SwnDecodeCall {
     hipStream_t hip_stream = nullptr;
 };
 
-// swn_decode_bl6.hip (the symmetric BL6-class kernel; the only one that takes `w16` / `w8`) and swn_decode_bl6w.hip (the
+// swn_decode_bl6.hip (the symmetric BL6-class kernel; the only one that takes an `image`) and swn_decode_bl6w.hip (the
 // wave-specialised form for the single-sample Laplace nets of that class).  *_session_floats: per-utterance session of a
 // streamed decode, 0 = the kernel does not take the geometry.
 size_t swn_decode_bl6_session_floats(const SwnGeom& g);

@@ -23,12 +23,11 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
                                     variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_chunk_models(models, model_of, session, conds, slots, step0s, n_steps, begins, seeds?, utt_ids,
                                            desc, capacity, variant, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
-    torch.ops.swn.pack_decode_w16(packed, desc)                    -> w16   (bf16 image of the streamed head matrices)
-    torch.ops.swn.decode_w16(packed, w16, cond, ...decode's arguments)            -> (out, heads, noise_used)
-    torch.ops.swn.decode_chunk_w16(packed, w16, cond, session, ...decode_chunk's) -> (out, heads, noise_used)
-    torch.ops.swn.decode_pool_chunk_w16(packed, w16, session, ...decode_pool_chunk's) -> (out, heads, noise_used)
-    torch.ops.swn.pack_decode_w8(packed, desc)                     -> w8    (FP8 E4M3 image of the same matrices + row scales)
-    torch.ops.swn.decode_w8 / decode_chunk_w8 / decode_pool_chunk_w8(packed, w8, ...)  as the *_w16 ops, over that image
+    per stored format of the streamed head matrices (DECODE_IMAGES: bf16 -> w16, e4m3 -> w8; one factory, _image_ops):
+    torch.ops.swn.pack_decode_<sfx>(packed, desc)                  -> image (w16: bf16; w8: FP8 E4M3 codes + row scales)
+    torch.ops.swn.decode_<sfx>(packed, image, cond, ...decode's arguments)            -> (out, heads, noise_used)
+    torch.ops.swn.decode_chunk_<sfx>(packed, image, cond, session, ...decode_chunk's) -> (out, heads, noise_used)
+    torch.ops.swn.decode_pool_chunk_<sfx>(packed, image, session, ...decode_pool_chunk's) -> (out, heads, noise_used)
     torch.ops.swn.e4m3_table(like, scale)                          -> (256,) fp32: the kernels' conversion of codes 0 .. 255
     torch.ops.swn.decode_pool_stepped_chunk(packed, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids, desc,
                                             capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
@@ -61,7 +60,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Sequence, Tuple
+import inspect
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch.library import custom_op
@@ -312,27 +312,45 @@ def _(models, model_of, auxs, conds, staged, n_news, n_receiveds, f0s, f1s, fina
 
 
 # ------------------------------------------------------------------------------------------ decode
-def _check_w16(w16: torch.Tensor, packed: torch.Tensor, d) -> torch.Tensor:
-    """the bf16 image of pack_decode_w16 as the *_w16 calls want it: uint8, contiguous, on the device of `packed`, of the
+class DecodeImage(NamedTuple):
+    """a storage format, other than fp32, of the head matrices the symmetric BL6 decode kernel streams (out_skip, out_1, the
+    softmax out_2).  pack_decode_<suffix> builds its image, and decode_<suffix>, decode_chunk_<suffix> and
+    decode_pool_chunk_<suffix> take it behind the packed parameters (_image_ops); the C entry points carry the same suffix."""
+    name: str       # the `weights` keyword of the decode calls
+    suffix: str
+
+    def bytes(self, d) -> int:
+        """of the image of net `d` (swn_decode_<suffix>_bytes); 0: the symmetric kernel does not serve the net"""
+        return getattr(_lib.lib(), f"swn_decode_{self.suffix}_bytes")(ctypes.byref(d))
+
+
+# bf16: the weights rounded to nearest even and re-tiled - bit-identical to the fp32 decode of runtime.bf16_weight_state_dict.
+# e4m3: per output row a power-of-two scale and the nearest-even OCP FP8 E4M3 codes (runtime.e4m3_quantise), re-tiled, then one
+#       fp32 2^-e per row - bit-identical to the fp32 decode of runtime.e4m3_weight_state_dict.
+# A further format is a row here, its C entry points, and its instantiation of the kernel.
+DECODE_IMAGES = {f.name: f for f in (DecodeImage("bf16", "w16"), DecodeImage("e4m3", "w8"))}
+
+
+def _check_image(fmt: DecodeImage, image: torch.Tensor, packed: torch.Tensor, d) -> torch.Tensor:
+    """the image of pack_decode_<suffix> as the *_<suffix> calls want it: uint8, contiguous, on the device of `packed`, of the
     size the net's image has (a net the symmetric BL6 kernel does not serve has none)"""
-    need = _lib.lib().swn_decode_w16_bytes(ctypes.byref(d))
+    need = fmt.bytes(d)
     if need == 0:
-        raise RuntimeError("bf16 weights exist for the nets the symmetric BL6 decode kernel serves only")
-    if w16.device != packed.device or w16.dtype != torch.uint8 or not w16.is_contiguous() or w16.numel() != need:
-        raise RuntimeError(f"w16 must be the contiguous uint8 image of pack_decode_w16 ({need} bytes) on the device of the "
-                           "packed parameters")
-    return w16
+        raise RuntimeError(f"{fmt.name} weights exist for the nets the symmetric BL6 decode kernel serves only")
+    if image.device != packed.device or image.dtype != torch.uint8 or not image.is_contiguous() or image.numel() != need:
+        raise RuntimeError(f"{fmt.suffix} must be the contiguous uint8 image of pack_decode_{fmt.suffix} ({need} bytes) on the "
+                           "device of the packed parameters")
+    return image
 
 
-def _check_w8(w8: torch.Tensor, packed: torch.Tensor, d) -> torch.Tensor:
-    """the FP8 image of pack_decode_w8 as the *_w8 calls want it (the rules of _check_w16)"""
-    need = _lib.lib().swn_decode_w8_bytes(ctypes.byref(d))
-    if need == 0:
-        raise RuntimeError("e4m3 weights exist for the nets the symmetric BL6 decode kernel serves only")
-    if w8.device != packed.device or w8.dtype != torch.uint8 or not w8.is_contiguous() or w8.numel() != need:
-        raise RuntimeError(f"w8 must be the contiguous uint8 image of pack_decode_w8 ({need} bytes) on the device of the "
-                           "packed parameters")
-    return w8
+def _image_entry(stem: str, fmt: Optional[DecodeImage], image, packed, d):
+    """the C entry point of the decode call `stem` over weights stored as `fmt` (None: fp32: swn_<stem>, else
+    swn_<stem>_<suffix>) -> (the function, its name in error texts, its arguments between the variant and the stream: the
+    checked image)"""
+    if fmt is None:
+        return getattr(_lib.lib(), "swn_" + stem), stem, ()
+    name = f"{stem}_{fmt.suffix}"
+    return getattr(_lib.lib(), "swn_" + name), name, (_ptr(_check_image(fmt, image, packed, d)),)
 
 
 def decode_impl(packed: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor], forced: Optional[torch.Tensor],
@@ -341,12 +359,12 @@ def decode_impl(packed: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.
            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """prologue + n_steps generation steps for every utterance (swn_decode).  noise None = drawn in the kernels, utterance
     b as global utterance utt_ids[b] (int32 (B), values < 2^31) or rng_utt0 + b."""
-    return _decode_call(None, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads,
+    return _decode_call(None, None, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads,
                         want_noise, utt_ids)
 
 
 def _decode_io(d, dev, cond, noise, forced, seed, utt_ids, n_steps, rng_seed, rng_utt0, want_heads, want_noise):
-    """the checked inputs of the sampling loop and the outputs of decode / decode_chunk and their *_w16 forms over the
+    """the checked inputs of the sampling loop and the outputs of decode / decode_chunk and their image forms over the
     utterances of `cond` -> (io, out, heads, used); io keeps its tensors alive"""
     soft, seg, _, _, n_out, _ = _geom(d)
     B = cond.shape[0]
@@ -378,10 +396,9 @@ def _decode_io(d, dev, cond, noise, forced, seed, utt_ids, n_steps, rng_seed, rn
     return io, out, heads, used
 
 
-def _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise,
-                 utt_ids, fp8=False):
-    """decode (w16 None: swn_decode), decode_w16 (the bf16 image: swn_decode_w16) and decode_w8 (fp8: `w16` is the FP8
-    image: swn_decode_w8)"""
+def _decode_call(fmt, image, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads,
+                 want_noise, utt_ids=None):
+    """decode (fmt None: swn_decode) and decode_<suffix> over the image of a stored format (swn_decode_<suffix>)"""
     L = _lib.lib()
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
@@ -391,106 +408,16 @@ def _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant,
     io, out, heads, used = _decode_io(d, dev, cond, noise, forced, seed, utt_ids, n_steps, rng_seed, rng_utt0, want_heads,
                                       want_noise)
     r = ctypes.byref(d)
-    if w16 is not None:
-        (_check_w8 if fp8 else _check_w16)(w16, packed, d)
-    state = torch.empty(L.swn_decode_state_floats(r, B) if w16 is None else 0, dtype=torch.float32, device=dev)
+    call, name, trail = _image_entry("decode", fmt, image, packed, d)
+    # (the symmetric BL6 kernel, the only one that takes an image, keeps its state on chip)
+    state = torch.empty(L.swn_decode_state_floats(r, B), dtype=torch.float32, device=dev) if fmt is None else None
     with _on(dev):
-        if w16 is None:
-            _lib.check(L.swn_decode(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), _ptr(state), _ptr(out),
-                                    _ptr(heads if want_heads else None), variant, _stream(dev)), "decode")
-        else:
-            call, name = (L.swn_decode_w8, "decode_w8") if fp8 else (L.swn_decode_w16, "decode_w16")
-            _lib.check(call(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), None, _ptr(out),
-                            _ptr(heads if want_heads else None), variant, _ptr(w16), _stream(dev)), name)
+        _lib.check(call(r, _ptr(packed), _ptr(cond), B, Tf, n_steps, ctypes.byref(io), _ptr(state), _ptr(out),
+                        _ptr(heads if want_heads else None), variant, *trail, _stream(dev)), name)
     return out, heads, used
 
 
 decode = custom_op("swn::decode", mutates_args=())(decode_impl)
-
-
-def pack_decode_w16_impl(packed: torch.Tensor, desc: List[int]) -> torch.Tensor:
-    """the bf16 image of the matrices the symmetric BL6 decode kernel streams (swn_pack_decode_w16): out_skip, out_1 and the
-    softmax out_2, rounded to nearest even and re-tiled; uint8 (swn_decode_w16_bytes)."""
-    L = _lib.lib()
-    d = _desc(desc)
-    _need_cuda(packed, "the packed parameters")
-    n = L.swn_decode_w16_bytes(ctypes.byref(d))
-    if n == 0:
-        raise RuntimeError("bf16 weights exist for the nets the symmetric BL6 decode kernel serves only")
-    w16 = torch.empty(n, dtype=torch.uint8, device=packed.device)
-    with _on(packed.device):
-        _lib.check(L.swn_pack_decode_w16(ctypes.byref(d), _ptr(packed), _ptr(w16), _stream(packed.device)), "pack_decode_w16")
-    return w16
-
-
-pack_decode_w16 = custom_op("swn::pack_decode_w16", mutates_args=())(pack_decode_w16_impl)
-
-
-@pack_decode_w16.register_fake
-def _(packed, desc):
-    return packed.new_empty(_lib.lib().swn_decode_w16_bytes(ctypes.byref(_desc(desc))), dtype=torch.uint8)
-
-
-def decode_w16_impl(packed: torch.Tensor, w16: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor],
-                    forced: Optional[torch.Tensor], seed: Optional[torch.Tensor], desc: List[int], n_steps: int, variant: int,
-                    rng_seed: int, rng_utt0: int, want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
-                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """decode with the streamed head matrices stored as bf16 (swn_decode_w16; w16 = pack_decode_w16(packed, desc)):
-    bit-identical to decode on a model whose out_skip / out_1 / softmax out_2 weights were rounded to bf16.  The variant must
-    resolve to the symmetric BL6 kernel (6 for the single-sample Laplace nets)."""
-    return _decode_call(w16, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads,
-                        want_noise, utt_ids)
-
-
-decode_w16 = custom_op("swn::decode_w16", mutates_args=())(decode_w16_impl)
-
-
-@decode_w16.register_fake
-def _(packed, w16, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise, utt_ids=None):
-    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
-
-
-def pack_decode_w8_impl(packed: torch.Tensor, desc: List[int]) -> torch.Tensor:
-    """the FP8 (OCP E4M3) image of the matrices the symmetric BL6 decode kernel streams (swn_pack_decode_w8): per output row a
-    power-of-two scale and the nearest-even codes (runtime.e4m3_quantise), re-tiled, then one fp32 2^-e per row; uint8
-    (swn_decode_w8_bytes).  Waits for the stream: a weight that is not finite is an error."""
-    L = _lib.lib()
-    d = _desc(desc)
-    _need_cuda(packed, "the packed parameters")
-    n = L.swn_decode_w8_bytes(ctypes.byref(d))
-    if n == 0:
-        raise RuntimeError("e4m3 weights exist for the nets the symmetric BL6 decode kernel serves only")
-    w8 = torch.empty(n, dtype=torch.uint8, device=packed.device)
-    with _on(packed.device):
-        _lib.check(L.swn_pack_decode_w8(ctypes.byref(d), _ptr(packed), _ptr(w8), _stream(packed.device)), "pack_decode_w8")
-    return w8
-
-
-pack_decode_w8 = custom_op("swn::pack_decode_w8", mutates_args=())(pack_decode_w8_impl)
-
-
-@pack_decode_w8.register_fake
-def _(packed, desc):
-    return packed.new_empty(_lib.lib().swn_decode_w8_bytes(ctypes.byref(_desc(desc))), dtype=torch.uint8)
-
-
-def decode_w8_impl(packed: torch.Tensor, w8: torch.Tensor, cond: torch.Tensor, noise: Optional[torch.Tensor],
-                   forced: Optional[torch.Tensor], seed: Optional[torch.Tensor], desc: List[int], n_steps: int, variant: int,
-                   rng_seed: int, rng_utt0: int, want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
-                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """decode with the streamed head matrices stored as FP8 E4M3 (swn_decode_w8; w8 = pack_decode_w8(packed, desc)):
-    bit-identical to decode on the model of runtime.e4m3_weight_state_dict.  The variant must resolve to the symmetric BL6
-    kernel (6 for the single-sample Laplace nets)."""
-    return _decode_call(w8, packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads,
-                        want_noise, utt_ids, fp8=True)
-
-
-decode_w8 = custom_op("swn::decode_w8", mutates_args=())(decode_w8_impl)
-
-
-@decode_w8.register_fake
-def _(packed, w8, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise, utt_ids=None):
-    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
 
 
 def e4m3_table_impl(like: torch.Tensor, scale: float) -> torch.Tensor:
@@ -522,7 +449,7 @@ def _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise):
 
 
 @decode.register_fake
-def _(packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise, utt_ids=None):
+def _decode_op_fake(packed, cond, noise, forced, seed, desc, n_steps, variant, rng_seed, rng_utt0, want_heads, want_noise, utt_ids=None):
     return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
 
 
@@ -535,14 +462,14 @@ def decode_chunk_impl(packed: torch.Tensor, cond: torch.Tensor, session: torch.T
     """steps [step0, step0 + n_steps) of a streamed decode (swn_decode_chunk): `session` (swn_decode_session_floats() fp32,
     updated in place) carries the decode state from one chunk to the next; begin=True runs the prologue (step0 0).  cond
     holds the frames final so far (absolute indexing); noise / forced / out / heads / used noise are the chunk's rows."""
-    return _decode_chunk_call(None, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed,
-                              rng_utt0, want_heads, want_noise, utt_ids)
+    return _decode_chunk_call(None, None, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant,
+                              rng_seed, rng_utt0, want_heads, want_noise, utt_ids)
 
 
-def _decode_chunk_call(w16, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0,
-                       want_heads, want_noise, utt_ids, fp8=False):
-    """decode_chunk (w16 None: swn_decode_chunk), decode_chunk_w16 (the bf16 image: swn_decode_chunk_w16) and decode_chunk_w8
-    (fp8: `w16` is the FP8 image: swn_decode_chunk_w8)"""
+def _decode_chunk_call(fmt, image, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed,
+                       rng_utt0, want_heads, want_noise, utt_ids=None):
+    """decode_chunk (fmt None: swn_decode_chunk) and decode_chunk_<suffix> over the image of a stored format
+    (swn_decode_chunk_<suffix>)"""
     L = _lib.lib()
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
@@ -558,61 +485,17 @@ def _decode_chunk_call(w16, packed, cond, session, noise, forced, seed, desc, st
     args = (ctypes.byref(d), _ptr(packed), _ptr(cond), B, Tf, int(step0), int(n_steps), _lib.CHUNK_BEGIN if begin else 0,
             ctypes.byref(io), _ptr(session), _ptr(out if n_steps > 0 else None), _ptr(heads if want_heads else None),
             int(variant))
+    call, name, trail = _image_entry("decode_chunk", fmt, image, packed, d)
     with _on(dev):
-        if w16 is None:
-            _lib.check(L.swn_decode_chunk(*args, _stream(dev)), "decode_chunk")
-        elif fp8:
-            _lib.check(L.swn_decode_chunk_w8(*args, _ptr(_check_w8(w16, packed, d)), _stream(dev)), "decode_chunk_w8")
-        else:
-            _lib.check(L.swn_decode_chunk_w16(*args, _ptr(_check_w16(w16, packed, d)), _stream(dev)), "decode_chunk_w16")
+        _lib.check(call(*args, *trail, _stream(dev)), name)
     return out, heads, used
 
 
 decode_chunk = custom_op("swn::decode_chunk", mutates_args=("session",))(decode_chunk_impl)
 
 
-def decode_chunk_w16_impl(packed: torch.Tensor, w16: torch.Tensor, cond: torch.Tensor, session: torch.Tensor,
-                          noise: Optional[torch.Tensor], forced: Optional[torch.Tensor], seed: Optional[torch.Tensor],
-                          desc: List[int], step0: int, n_steps: int, begin: bool, variant: int, rng_seed: int, rng_utt0: int,
-                          want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
-                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """decode_chunk over the bf16 image of the streamed head matrices (swn_decode_chunk_w16): the chunks concatenate to
-    decode_w16 bit for bit; the session is laid out as decode_chunk's."""
-    return _decode_chunk_call(w16, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed,
-                              rng_utt0, want_heads, want_noise, utt_ids)
-
-
-decode_chunk_w16 = custom_op("swn::decode_chunk_w16", mutates_args=("session",))(decode_chunk_w16_impl)
-
-
-@decode_chunk_w16.register_fake
-def _(packed, w16, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0, want_heads,
-      want_noise, utt_ids=None):
-    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
-
-
-def decode_chunk_w8_impl(packed: torch.Tensor, w8: torch.Tensor, cond: torch.Tensor, session: torch.Tensor,
-                         noise: Optional[torch.Tensor], forced: Optional[torch.Tensor], seed: Optional[torch.Tensor],
-                         desc: List[int], step0: int, n_steps: int, begin: bool, variant: int, rng_seed: int, rng_utt0: int,
-                         want_heads: bool, want_noise: bool, utt_ids: Optional[torch.Tensor] = None
-                         ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """decode_chunk over the FP8 image of the streamed head matrices (swn_decode_chunk_w8): the chunks concatenate to
-    decode_w8 bit for bit; the session is laid out as decode_chunk's."""
-    return _decode_chunk_call(w8, packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed,
-                              rng_utt0, want_heads, want_noise, utt_ids, fp8=True)
-
-
-decode_chunk_w8 = custom_op("swn::decode_chunk_w8", mutates_args=("session",))(decode_chunk_w8_impl)
-
-
-@decode_chunk_w8.register_fake
-def _(packed, w8, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0, want_heads,
-      want_noise, utt_ids=None):
-    return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
-
-
 @decode_chunk.register_fake
-def _(packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0, want_heads,
+def _decode_chunk_op_fake(packed, cond, session, noise, forced, seed, desc, step0, n_steps, begin, variant, rng_seed, rng_utt0, want_heads,
       want_noise, utt_ids=None):
     return _decode_fake(packed, cond, desc, n_steps, want_heads, want_noise)
 
@@ -628,17 +511,26 @@ def decode_pool_chunk_impl(packed: torch.Tensor, session: torch.Tensor, conds: L
     classes; None = zeros / Q/2).  Noise is drawn on the device, keyed by rng_seed and utt_ids[e].  out / heads / used noise
     are dense (E, n_max * seg) | (E, n_max, n_out) | (E, n_max, width), n_max = max(n_steps); rows past an entry's own steps
     are not written."""
+    return _decode_pool_chunk_call(None, None, packed, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc,
+                                   capacity, variant, rng_seed, want_heads, want_noise)
+
+
+def _decode_pool_chunk_call(fmt, image, packed, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity,
+                            variant, rng_seed, want_heads, want_noise):
+    """decode_pool_chunk (fmt None: swn_decode_pool_chunk) and decode_pool_chunk_<suffix> over the image of a stored format
+    (swn_decode_pool_chunk_<suffix>)"""
     d = _desc(desc)
     _need_cuda(packed, "the packed parameters")
-    return _decode_pool_call(_lib.lib().swn_decode_pool_chunk, d, packed.device, (_ptr(packed),), (), session, conds, slots,
-                             step0s, n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
+    call, _, trail = _image_entry("decode_pool_chunk", fmt, image, packed, d)
+    return _decode_pool_call(call, d, packed.device, (_ptr(packed),), trail, session, conds, slots, step0s, n_steps, begins,
+                             seeds, utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
 
 
 def _decode_pool_call(call, d, dev, lead, trail, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, capacity,
                       variant, rng_seed, want_heads, want_noise):
-    """one pool launch through the library's `call` (decode_pool_chunk and its *_w16 / *_models forms): checks the entries and
+    """one pool launch through the library's `call` (decode_pool_chunk and its image / *_models forms): checks the entries and
     builds their table, the io block and the outputs.  `lead` are the call's arguments between the descriptor and the
-    capacity (the packed parameters, or the model tables), `trail` those between the variant and the stream (the bf16 image)"""
+    capacity (the packed parameters, or the model tables), `trail` those between the variant and the stream (the image)"""
     L = _lib.lib()
     soft, seg, _, _, n_out, _ = _geom(d)
     E = len(conds)
@@ -680,56 +572,8 @@ def _decode_pool_call(call, d, dev, lead, trail, session, conds, slots, step0s, 
 decode_pool_chunk = custom_op("swn::decode_pool_chunk", mutates_args=("session",))(decode_pool_chunk_impl)
 
 
-def decode_pool_chunk_w16_impl(packed: torch.Tensor, w16: torch.Tensor, session: torch.Tensor, conds: List[torch.Tensor],
-                               slots: List[int], step0s: List[int], n_steps: List[int], begins: List[bool],
-                               seeds: Optional[torch.Tensor], utt_ids: List[int], desc: List[int], capacity: int, variant: int,
-                               rng_seed: int, want_heads: bool, want_noise: bool
-                               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """decode_pool_chunk over the bf16 image of the streamed head matrices (swn_decode_pool_chunk_w16): every entry's rows
-    are bit-identical to decode_chunk_w16 of that session alone."""
-    d = _desc(desc)
-    _need_cuda(packed, "the packed parameters")
-    _check_w16(w16, packed, d)
-    return _decode_pool_call(_lib.lib().swn_decode_pool_chunk_w16, d, packed.device, (_ptr(packed),), (_ptr(w16),), session,
-                             conds, slots, step0s, n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed, want_heads,
-                             want_noise)
-
-
-decode_pool_chunk_w16 = custom_op("swn::decode_pool_chunk_w16", mutates_args=("session",))(decode_pool_chunk_w16_impl)
-
-
-@decode_pool_chunk_w16.register_fake
-def _(packed, w16, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
-      want_heads, want_noise):
-    return _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise)
-
-
-def decode_pool_chunk_w8_impl(packed: torch.Tensor, w8: torch.Tensor, session: torch.Tensor, conds: List[torch.Tensor],
-                              slots: List[int], step0s: List[int], n_steps: List[int], begins: List[bool],
-                              seeds: Optional[torch.Tensor], utt_ids: List[int], desc: List[int], capacity: int, variant: int,
-                              rng_seed: int, want_heads: bool, want_noise: bool
-                              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """decode_pool_chunk over the FP8 image of the streamed head matrices (swn_decode_pool_chunk_w8): every entry's rows are
-    bit-identical to decode_chunk_w8 of that session alone."""
-    d = _desc(desc)
-    _need_cuda(packed, "the packed parameters")
-    _check_w8(w8, packed, d)
-    return _decode_pool_call(_lib.lib().swn_decode_pool_chunk_w8, d, packed.device, (_ptr(packed),), (_ptr(w8),), session,
-                             conds, slots, step0s, n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed, want_heads,
-                             want_noise)
-
-
-decode_pool_chunk_w8 = custom_op("swn::decode_pool_chunk_w8", mutates_args=("session",))(decode_pool_chunk_w8_impl)
-
-
-@decode_pool_chunk_w8.register_fake
-def _(packed, w8, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
-      want_heads, want_noise):
-    return _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise)
-
-
 @decode_pool_chunk.register_fake
-def _(packed, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
+def _decode_pool_chunk_op_fake(packed, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
       want_heads, want_noise):
     return _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise)
 
@@ -742,6 +586,64 @@ def _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise):
     return (packed.new_empty((E, n_max * seg), dtype=torch.int32 if soft else torch.float32),
             packed.new_empty((E, n_max, n_out) if want_heads else (0,)),
             packed.new_empty((E, n_max, width) if want_noise else (0,)))
+
+
+# ------------------------------------------------------------------------------------------ decode over a stored format
+def _image_ops(fmt: DecodeImage) -> dict:
+    """registers the four ops of a stored format -> {name: op, name_impl: function}: pack_decode_<suffix>(packed, desc) -> the
+    image, uint8; and decode_<suffix>, decode_chunk_<suffix>, decode_pool_chunk_<suffix>: the fp32 ops with the image as their
+    second argument (named <suffix>), in everything else - annotations, defaults, the mutated session - the fp32 signature.
+    The variant must resolve to the symmetric BL6 kernel (6 for the single-sample Laplace nets); the chunks of a stream
+    concatenate to the one-shot decode of the format bit for bit, and a pool entry's rows are those of its session alone."""
+    s = fmt.suffix
+
+    def pack_impl(packed: torch.Tensor, desc: List[int]) -> torch.Tensor:
+        d = _desc(desc)
+        _need_cuda(packed, "the packed parameters")
+        n = fmt.bytes(d)
+        if n == 0:
+            raise RuntimeError(f"{fmt.name} weights exist for the nets the symmetric BL6 decode kernel serves only")
+        image = torch.empty(n, dtype=torch.uint8, device=packed.device)
+        with _on(packed.device):
+            _lib.check(getattr(_lib.lib(), f"swn_pack_decode_{s}")(ctypes.byref(d), _ptr(packed), _ptr(image),
+                                                                   _stream(packed.device)), f"pack_decode_{s}")
+        return image
+
+    made = {f"pack_decode_{s}_impl": pack_impl, f"pack_decode_{s}": custom_op(f"swn::pack_decode_{s}", pack_impl, mutates_args=())}
+    made[f"pack_decode_{s}"].register_fake(lambda packed, desc: packed.new_empty(fmt.bytes(_desc(desc)), dtype=torch.uint8))
+
+    def image_form(fp32_impl, call, fake, mutates):
+        def impl(packed, image, *args, **kw):
+            return call(fmt, image, packed, *args, **kw)
+
+        sig = inspect.signature(fp32_impl)                  # what the op's schema is inferred from
+        par = list(sig.parameters.values())
+        impl.__signature__ = sig.replace(parameters=par[:1] + [par[0].replace(name=s)] + par[1:])
+        name = f"{fp32_impl.__name__[:-len('_impl')]}_{s}"
+        impl.__name__ = impl.__qualname__ = name + "_impl"
+        made[name + "_impl"] = impl
+        made[name] = custom_op(f"swn::{name}", impl, mutates_args=mutates)
+        made[name].register_fake(lambda packed, image, *args, **kw: fake(packed, *args, **kw))
+
+    image_form(decode_impl, _decode_call, _decode_op_fake, ())
+    image_form(decode_chunk_impl, _decode_chunk_call, _decode_chunk_op_fake, ("session",))
+    image_form(decode_pool_chunk_impl, _decode_pool_chunk_call, _decode_pool_chunk_op_fake, ("session",))
+    return made
+
+
+for _fmt in DECODE_IMAGES.values():
+    globals().update(_image_ops(_fmt))
+
+
+def decode_lead(net, op: str, weights: str):
+    """the name of the op of torch.ops.swn that runs the decode call `op` ("decode" | "decode_chunk" | "decode_pool_chunk") of
+    `net` (a runtime.HipNet) with weights stored as `weights` ("fp32" or a key of DECODE_IMAGES, checked by
+    runtime.check_decode_weights), and the op's leading arguments: the packed parameters and, unless fp32, the format's image
+    (net.decode_<suffix>_image())"""
+    if weights == "fp32":
+        return op, (net.packed,)
+    suffix = DECODE_IMAGES[weights].suffix
+    return f"{op}_{suffix}", (net.packed, getattr(net, f"decode_{suffix}_image")())
 
 
 def decode_pool_chunk_models_impl(models: List[torch.Tensor], model_of: List[int], session: torch.Tensor,

@@ -122,7 +122,7 @@ class train_precision:
         return False
 
 
-DECODE_WEIGHTS = ("fp32", "bf16", "e4m3")
+DECODE_WEIGHTS = ("fp32",) + tuple(_ops.DECODE_IMAGES)   # the `weights` keyword of the decode calls
 
 
 def bf16_weight_names(cfg: NetConfig) -> List[str]:
@@ -229,8 +229,7 @@ def check_decode_weights(weights, cfg: NetConfig, batch: int, variant: int) -> s
         return weights
     L = _lib.lib()
     desc = _lib.desc_from_cfg(cfg)
-    size = L.swn_decode_w16_bytes if weights == "bf16" else L.swn_decode_w8_bytes
-    if size(ctypes.byref(desc)) == 0:
+    if _ops.DECODE_IMAGES[weights].bytes(desc) == 0:
         raise ValueError(f'weights="{weights}" runs on the symmetric BL6 decode kernel, which does not serve this net (the '
                          f"stepped chain and the generic kernel have no {weights} form)")
     resolved = L.swn_decode_resolve_variant(ctypes.byref(desc), int(batch), int(variant))
@@ -268,6 +267,7 @@ class HipNet:
         self.lib = _lib.lib()
         self.packed = packed.to(self.device, non_blocking=False).contiguous()
         self.packed_version = 0          # bumped by repack(): derived copies (bf16 weights) follow it
+        self._decode_images = {}         # weights -> (packed_version, image): _decode_image
         self.fused_backward = True       # mixed-precision mode, BL6 class: swn_backward_bf16 (False: the generic chain)
         self.keep_preactivations = True  # mixed-precision mode, GEMM-stack class: swn_forward_bf16_keep + swn_backward_keep
 
@@ -326,32 +326,29 @@ class HipNet:
         ids = None if utt_ids is None else torch.as_tensor(list(utt_ids), dtype=torch.int32)
         args = (cond, noise, forced, seed, self.dlist, int(n_steps), int(variant), int(rng_seed) & 0x7FFFFFFFFFFFFFFF,
                 int(rng_utt0) & 0xFFFFFFFF, bool(want_heads), bool(want_noise), ids)
-        if weights == "bf16":
-            out, heads, used = _O.decode_w16(self.packed, self.decode_w16_image(), *args)
-        elif weights == "e4m3":
-            out, heads, used = _O.decode_w8(self.packed, self.decode_w8_image(), *args)
-        else:
-            out, heads, used = _O.decode(self.packed, *args)
+        op, lead = _ops.decode_lead(self, "decode", weights)
+        out, heads, used = getattr(_O, op)(*lead, *args)
         heads = heads if want_heads else None
         if want_noise:
             return out, heads, used
         return out, heads
 
+    def _decode_image(self, weights: str) -> torch.Tensor:
+        """the image of the streamed head matrices in a stored format (torch.ops.swn.pack_decode_<suffix>), built on first use
+        and rebuilt when the packed parameters moved on (repack)"""
+        version, image = self._decode_images.get(weights, (None, None))
+        if version != self.packed_version:
+            image = getattr(_O, "pack_decode_" + _ops.DECODE_IMAGES[weights].suffix)(self.packed, self.dlist)
+            self._decode_images[weights] = (self.packed_version, image)
+        return image
+
     def decode_w16_image(self) -> torch.Tensor:
-        """the bf16 image of the streamed head matrices (torch.ops.swn.pack_decode_w16), built on first use and rebuilt when
-        the packed parameters moved on (repack)"""
-        if getattr(self, "_w16", None) is None or getattr(self, "_w16_version", -1) != self.packed_version:
-            self._w16 = _O.pack_decode_w16(self.packed, self.dlist)
-            self._w16_version = self.packed_version
-        return self._w16
+        """the bf16 image of the streamed head matrices"""
+        return self._decode_image("bf16")
 
     def decode_w8_image(self) -> torch.Tensor:
-        """the FP8 (E4M3) image of the streamed head matrices and their row scales (torch.ops.swn.pack_decode_w8), built on
-        first use and rebuilt when the packed parameters moved on (repack)"""
-        if getattr(self, "_w8", None) is None or getattr(self, "_w8_version", -1) != self.packed_version:
-            self._w8 = _O.pack_decode_w8(self.packed, self.dlist)
-            self._w8_version = self.packed_version
-        return self._w8
+        """the FP8 (E4M3) image of the streamed head matrices and their row scales"""
+        return self._decode_image("e4m3")
 
     # ------------------------------------------------------------------ teacher-forced stack
     def forward(self, aux: torch.Tensor, audio: torch.Tensor, want_hidden: bool = False,

@@ -273,12 +273,8 @@ class DecodeStream:
             begin = False                           # the first chunk resumes from the filled session
         args = (self._cond, self._session, noise, forced, self._seed, self.net.dlist, self.steps_done, n, begin, self.variant,
                 self.rng_seed, self.rng_utt0, self.want_heads, self.want_noise, self._ids)
-        if self.weights == "bf16":
-            out, heads, used = _O.decode_chunk_w16(self.net.packed, self.net.decode_w16_image(), *args)
-        elif self.weights == "e4m3":
-            out, heads, used = _O.decode_chunk_w8(self.net.packed, self.net.decode_w8_image(), *args)
-        else:
-            out, heads, used = _O.decode_chunk(self.net.packed, *args)
+        op, lead = _ops.decode_lead(self.net, "decode_chunk", self.weights)
+        out, heads, used = getattr(_O, op)(*lead, *args)
         self._begun = True
         self.steps_done += n
         heads = heads if self.want_heads else None
@@ -540,12 +536,9 @@ class DecodePool:
             args = (self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
                     [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
                     self.net.dlist, self.capacity, self.variant, self.rng_seed, self.want_heads, self.want_noise)
-            if self.weights == "bf16":
-                out, heads, used = _O.decode_pool_chunk_w16(self.net.packed, self.net.decode_w16_image(), *args)
-            elif self.weights == "e4m3":
-                out, heads, used = _O.decode_pool_chunk_w8(self.net.packed, self.net.decode_w8_image(), *args)
-            elif len(models) == 1:
-                out, heads, used = _O.decode_pool_chunk(self._models[models[0]].packed, *args)
+            if len(models) == 1:                    # (a pool of stored weights serves its own net alone: add_model)
+                op, lead = _ops.decode_lead(self._models[models[0]], "decode_pool_chunk", self.weights)
+                out, heads, used = getattr(_O, op)(*lead, *args)
             else:
                 out, heads, used = _O.decode_pool_chunk_models([self._models[m].packed for m in models], of, *args)
             for e, (s, step0, n) in enumerate(entries):

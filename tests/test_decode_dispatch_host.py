@@ -1,7 +1,7 @@
 """CPU: the return code of every decode entry point of the C ABI (swn_decode, swn_decode_chunk, swn_decode_pool_chunk,
-swn_decode_pool_chunk_models and the three *_w16 forms) for the argument combinations that are decided before a launch -
-the common refusals, and the places where the fp32 and the bf16 family answer differently.  Fake non-null addresses: no row
-of these tables reaches a launch."""
+swn_decode_pool_chunk_models and the three *_w16 and *_w8 forms) for the argument combinations that are decided before a
+launch - the common refusals, and the places where the fp32 family and the families over a stored image answer differently.
+Fake non-null addresses: no row of these tables reaches a launch."""
 import ctypes
 
 import pytest
@@ -18,8 +18,9 @@ REF = C.ref6_laplace()                         # the stepped chain at variants 0
 TINY = C.tiny("laplace", 2, 4)                 # the generic kernel at variants 0 and 1
 NETS = {"smx": SMX, "s1": S1, "s5": S5, "ref": REF, "tiny": TINY}
 
-VARIANT6 = "variant = 6"                       # detail text of a *_w16 call that resolves to the wave-specialised kernel ...
+VARIANT6 = "variant = 6"                       # detail text of a *_w16 / *_w8 call that resolves to the wave-specialised kernel ...
 BL6_ONLY = "symmetric BL6 kernel only"         # ... and to any other kernel, or to none
+WORD = {"w16": "bf16", "w8": "e4m3"}           # ... both of which name the format of the call's image
 
 
 def _p(v):
@@ -35,14 +36,15 @@ def _detail():
     return _lib.lib().swn_last_error_detail().decode()
 
 
-def _run(call, rows):
-    """rows of (keyword arguments, return code[, text the error detail holds])"""
+def _run(call, rows, word=None):
+    """rows of (keyword arguments, return code[, text the error detail holds - next to `word`, if given])"""
     for row in rows:
         kw, want, text = row if len(row) == 3 else (*row, None)
         got = call(**kw)
         assert got == want, (kw, got, want)
         if text is not None:
             assert text in _detail(), (kw, _detail())
+            assert word is None or word + " weights" in _detail(), (kw, _detail())
 
 
 def test_the_nets_resolve_to_the_kernels_these_tables_assume():
@@ -59,12 +61,13 @@ def test_the_nets_resolve_to_the_kernels_these_tables_assume():
 
 
 # ------------------------------------------------------------------------------------------------------------------ one-shot
-def _oneshot(w16):
+def _oneshot(fmt):
+    """fmt: None (swn_decode), "w16" (swn_decode_w16) or "w8" (swn_decode_w8)"""
     def call(net=SMX, variant=0, packed=1, cond=1, batch=1, frames=4, n_steps=4, io=1, state=1, out=1, image=1, desc=1):
         lib, d = _lib.lib(), _lib.desc_from_cfg(net)
         args = [ctypes.byref(d) if desc else None, _p(packed), _p(cond), batch, frames, n_steps,
                 ctypes.byref(_io()) if io else None, _p(state), _p(out), None, variant]
-        return lib.swn_decode_w16(*args, _p(image), None) if w16 else lib.swn_decode(*args, None)
+        return getattr(lib, "swn_decode_" + fmt)(*args, _p(image), None) if fmt else lib.swn_decode(*args, None)
     return call
 
 
@@ -78,7 +81,7 @@ ONESHOT_COMMON = [
 
 
 def test_swn_decode():
-    _run(_oneshot(False), ONESHOT_COMMON + [
+    _run(_oneshot(None), ONESHOT_COMMON + [
         # nothing to generate: SWN_OK before the buffers and the variant are looked at
         (dict(n_steps=0, packed=0, cond=0, out=0, state=0), OK),
         (dict(n_steps=0, variant=99), OK), (dict(net=REF, n_steps=0, variant=2, state=0), OK),
@@ -97,8 +100,7 @@ def test_swn_decode():
     ])
 
 
-def test_swn_decode_w16():
-    _run(_oneshot(True), ONESHOT_COMMON + [
+ONESHOT_IMAGE = ONESHOT_COMMON + [
         (dict(image=0), BADARG), (dict(image=0, n_steps=0), BADARG),
         # nothing to generate: still an image and a variant that resolves to the symmetric kernel
         (dict(n_steps=0, packed=0, cond=0, out=0, state=0), OK), (dict(net=S1, n_steps=0, variant=6, packed=0), OK),
@@ -114,17 +116,26 @@ def test_swn_decode_w16():
         (dict(variant=4), UNSUPPORTED, BL6_ONLY), (dict(variant=-1), UNSUPPORTED), (dict(variant=7), UNSUPPORTED),
         # the other checks come before the variant
         (dict(net=REF, out=0), BADARG), (dict(net=S1, n_steps=4 * 110 + 1), BADARG), (dict(net=S1, image=0), BADARG),
-    ])
+]
+
+
+def test_swn_decode_w16():
+    _run(_oneshot("w16"), ONESHOT_IMAGE, WORD["w16"])
+
+
+def test_swn_decode_w8():
+    _run(_oneshot("w8"), ONESHOT_IMAGE, WORD["w8"])
 
 
 # --------------------------------------------------------------------------------------------------------------------- chunk
-def _chunk(w16):
+def _chunk(fmt):
+    """fmt: None (swn_decode_chunk), "w16" (swn_decode_chunk_w16) or "w8" (swn_decode_chunk_w8)"""
     def call(net=SMX, variant=0, packed=1, cond=1, batch=1, frames=4, step0=0, n_steps=4, flags=1, io=1, session=1, out=1,
              image=1, desc=1):
         lib, d = _lib.lib(), _lib.desc_from_cfg(net)
         args = [ctypes.byref(d) if desc else None, _p(packed), _p(cond), batch, frames, step0, n_steps, flags,
                 ctypes.byref(_io()) if io else None, _p(session), _p(out), None, variant]
-        return lib.swn_decode_chunk_w16(*args, _p(image), None) if w16 else lib.swn_decode_chunk(*args, None)
+        return getattr(lib, "swn_decode_chunk_" + fmt)(*args, _p(image), None) if fmt else lib.swn_decode_chunk(*args, None)
     return call
 
 
@@ -147,7 +158,7 @@ CHUNK_COMMON = [
 
 
 def test_swn_decode_chunk():
-    _run(_chunk(False), CHUNK_COMMON + [
+    _run(_chunk(None), CHUNK_COMMON + [
         (dict(net=S1, n_steps=0, flags=0, out=0), OK), (dict(net=REF, n_steps=0, flags=0, out=0), OK),
         (dict(net=TINY, n_steps=0, flags=0, out=0, variant=3), OK),
         # an unresolvable (net, batch, variant) is a bad argument here, with or without work
@@ -157,8 +168,7 @@ def test_swn_decode_chunk():
     ])
 
 
-def test_swn_decode_chunk_w16():
-    _run(_chunk(True), CHUNK_COMMON + [
+CHUNK_IMAGE = CHUNK_COMMON + [
         (dict(image=0), BADARG), (dict(image=0, n_steps=0, flags=0), BADARG),
         # what does not resolve to the symmetric kernel is unsupported, with the detail text, with or without work
         (dict(net=S1), UNSUPPORTED, VARIANT6), (dict(net=S1, variant=2), UNSUPPORTED, VARIANT6),
@@ -170,7 +180,15 @@ def test_swn_decode_chunk_w16():
         (dict(net=REF, n_steps=0, flags=0, out=0), UNSUPPORTED, BL6_ONLY),
         # the other checks come before the variant
         (dict(net=S1, out=0), BADARG), (dict(net=REF, step0=1), BADARG), (dict(net=S1, image=0), BADARG),
-    ])
+]
+
+
+def test_swn_decode_chunk_w16():
+    _run(_chunk("w16"), CHUNK_IMAGE, WORD["w16"])
+
+
+def test_swn_decode_chunk_w8():
+    _run(_chunk("w8"), CHUNK_IMAGE, WORD["w8"])
 
 
 # ---------------------------------------------------------------------------------------------------------------------- pool
@@ -183,7 +201,8 @@ IDLE = [dict(slot=0, step0=5, n_steps=0, flags=0), dict(slot=1, n_steps=0, flags
 
 
 def _pool(kind):
-    """kind: "fp32" (swn_decode_pool_chunk), "w16" (swn_decode_pool_chunk_w16) or "models" (swn_decode_pool_chunk_models)"""
+    """kind: "fp32" (swn_decode_pool_chunk), "w16" / "w8" (swn_decode_pool_chunk_w16 / _w8) or "models"
+    (swn_decode_pool_chunk_models)"""
     def call(net=SMX, variant=0, packed=1, capacity=2, entries=(dict(),), n_entries=None, table=1, io=1, session=1, out=1,
              image=1, desc=1, models=(1, 2), n_models=None, of=None, null_models=False, null_of=False):
         lib, d = _lib.lib(), _lib.desc_from_cfg(net)
@@ -195,8 +214,9 @@ def _pool(kind):
         tail = [capacity, tab, E, io, _p(session), _p(out), None, variant]
         if kind == "fp32":
             return lib.swn_decode_pool_chunk(ctypes.byref(d) if desc else None, _p(packed), *tail, None)
-        if kind == "w16":
-            return lib.swn_decode_pool_chunk_w16(ctypes.byref(d) if desc else None, _p(packed), *tail, _p(image), None)
+        if kind in WORD:
+            return getattr(lib, "swn_decode_pool_chunk_" + kind)(ctypes.byref(d) if desc else None, _p(packed), *tail, _p(image),
+                                                                 None)
         of = [e % len(models) for e in range(max(1, len(rows)))] if of is None else of
         ptrs = None if null_models else (ctypes.c_void_p * max(1, len(models)))(*[m or None for m in models])
         idx = None if null_of else (ctypes.c_int32 * max(1, len(of)))(*of)
@@ -258,8 +278,7 @@ def test_swn_decode_pool_chunk_models():
     ])
 
 
-def test_swn_decode_pool_chunk_w16():
-    _run(_pool("w16"), POOL_COMMON + [
+POOL_IMAGE = POOL_COMMON + [
         (dict(packed=0), BADARG), (dict(image=0), BADARG), (dict(image=0, entries=IDLE), BADARG),
         # what does not resolve to the symmetric kernel is unsupported, with the detail text, with or without work
         (dict(net=S1), UNSUPPORTED, VARIANT6), (dict(net=S1, variant=2), UNSUPPORTED, VARIANT6),
@@ -270,7 +289,15 @@ def test_swn_decode_pool_chunk_w16():
         (dict(net=S1, entries=IDLE, out=0), UNSUPPORTED, VARIANT6), (dict(net=REF, entries=IDLE, out=0), UNSUPPORTED, BL6_ONLY),
         # the other checks come before the variant
         (dict(net=REF, out=0), BADARG), (dict(net=S1, entries=[dict(slot=2)]), BADARG), (dict(net=S1, image=0), BADARG),
-    ])
+]
+
+
+def test_swn_decode_pool_chunk_w16():
+    _run(_pool("w16"), POOL_IMAGE, WORD["w16"])
+
+
+def test_swn_decode_pool_chunk_w8():
+    _run(_pool("w8"), POOL_IMAGE, WORD["w8"])
 
 
 @pytest.mark.parametrize("name", sorted(NETS))
