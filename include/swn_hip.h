@@ -178,7 +178,14 @@ int    swn_frontend_pool(const swn_net_desc* d, const float* packed_dev, const s
  *       computed from valid addresses and never stored), so the call still makes 3 + aux_dilation_size launches whatever
  *       n_entries and n_models are.  work_dev holds swn_frontend_pool_models_work_floats() floats (it includes that padding).
  *   swn_decode_pool_chunk_models (declared behind swn_decode_pool_chunk below)   the workgroup of entry e runs with the weight
- *       pointer of its model; the stepped chain is SWN_E_UNSUPPORTED as in swn_decode_pool_chunk. */
+ *       pointer of its model; the stepped chain is SWN_E_UNSUPPORTED as in swn_decode_pool_chunk.
+ *   swn_decode_pool_chunk_models_w16 / _w8 (declared behind swn_decode_pool_chunk_w16 / _w8 below)   the same launch over the
+ *       bf16 / FP8 images of the models: images_host is a HOST array of n_models DEVICE pointers, images_host[m] the image
+ *       swn_pack_decode_w16 / _w8 made of models_host[m]; the workgroup of entry e reads its model's packed buffer AND its
+ *       model's image, the resident out_1 slices and the FP8 row scales included.  SWN_E_BADARG in addition: a null images_host
+ *       or a null image of a model below n_models; then SWN_E_UNSUPPORTED as swn_decode_pool_chunk_w16 / _w8 refuse (the variant
+ *       must resolve to the symmetric BL6 kernel).  Every entry's rows are bit-identical to swn_decode_pool_chunk_w16 / _w8
+ *       made with that entry's model and image. */
 #define SWN_POOL_MAX_MODELS 16
 size_t swn_frontend_pool_models_work_floats(const swn_net_desc* d, const swn_frontend_pool_entry* entries_host,
                                             const int32_t* model_of_entry_host, int n_entries, int n_models);
@@ -307,8 +314,12 @@ int    swn_decode_pool_chunk_models(const swn_net_desc* d, const float* const* m
  * Checked before anything is launched: SWN_E_BADARG for a NULL w16_dev; SWN_E_UNSUPPORTED (text in swn_last_error_detail)
  * when `variant` does not resolve to the symmetric BL6 kernel for the net - variant 0 / 2 on a single-sample Laplace net
  * resolve to the wave-specialised kernel, so those nets need variant = 6; the stepped chain (launch-bound: weight bytes are
- * not its limit), the generic kernel, the wave-specialised kernel and multi-model pools have no bf16 form.  One precision
- * below bf16 exists: the *_w8 calls below. */
+ * not its limit), the generic kernel and the wave-specialised kernel have no bf16 form.  One precision below bf16 exists: the
+ * *_w8 calls below.
+ * swn_decode_pool_chunk_models_w16 is swn_decode_pool_chunk_models over one image per model (see "pools over several models"
+ * above): its arguments plus images_host, n_models device pointers in a host array.  Checked in this order before anything is
+ * launched: the rules of swn_decode_pool_chunk, those of the model tables, a NULL images_host or images_host[m] (m < n_models)
+ * is SWN_E_BADARG, then the refusals of swn_decode_pool_chunk_w16. */
 size_t swn_decode_w16_bytes(const swn_net_desc* d);
 int    swn_pack_decode_w16(const swn_net_desc* d, const float* packed_dev, void* w16_dev, void* stream);
 int    swn_decode_w16(const swn_net_desc* d, const float* packed_dev, const float* cond_dev,
@@ -321,6 +332,12 @@ int    swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* packed_dev,
                                  const swn_decode_pool_entry* entries_host, int n_entries,
                                  const swn_decode_io* io, float* session_dev,
                                  void* out_dev, float* heads_dev, int variant, const void* w16_dev, void* stream);
+int    swn_decode_pool_chunk_models_w16(const swn_net_desc* d, const float* const* models_host, int n_models,
+                                        const int32_t* model_of_entry_host, int capacity,
+                                        const swn_decode_pool_entry* entries_host, int n_entries,
+                                        const swn_decode_io* io, float* session_dev,
+                                        void* out_dev, float* heads_dev, int variant, const void* const* images_host,
+                                        void* stream);
 
 /* ---- decode with FP8 (E4M3) storage of the streamed head matrices -------------------------------------------------------
  * The *_w8 calls are the *_w16 calls over a quarter of the fp32 bytes: the same kernel, the same tensors, the same guarantee.
@@ -340,7 +357,8 @@ int    swn_decode_pool_chunk_w16(const swn_net_desc* d, const float* packed_dev,
  *             the fp32 call of the same variant on a model whose named matrices were replaced by W^.
  *   w8_dev    swn_decode_w8_bytes() bytes = one per weight + four per row (the fp32 2^-e_r), filled by swn_pack_decode_w8
  *             from packed_dev; refill it whenever packed_dev changes.  0 for a net the symmetric BL6 kernel does not serve.
- * Arguments, checks and refusals are those of the *_w16 counterparts with w8_dev in place of w16_dev.
+ * Arguments, checks and refusals are those of the *_w16 counterparts with w8_dev in place of w16_dev (and, for
+ * swn_decode_pool_chunk_models_w8, the images of swn_pack_decode_w8 in images_host).
  * swn_e4m3_table writes what the kernels' conversion makes of codes 0 .. 255 at `scale` (a power of two) into out_dev[256]. */
 size_t swn_decode_w8_bytes(const swn_net_desc* d);
 int    swn_pack_decode_w8(const swn_net_desc* d, const float* packed_dev, void* w8_dev, void* stream);
@@ -354,6 +372,12 @@ int    swn_decode_pool_chunk_w8(const swn_net_desc* d, const float* packed_dev, 
                                 const swn_decode_pool_entry* entries_host, int n_entries,
                                 const swn_decode_io* io, float* session_dev,
                                 void* out_dev, float* heads_dev, int variant, const void* w8_dev, void* stream);
+int    swn_decode_pool_chunk_models_w8(const swn_net_desc* d, const float* const* models_host, int n_models,
+                                       const int32_t* model_of_entry_host, int capacity,
+                                       const swn_decode_pool_entry* entries_host, int n_entries,
+                                       const swn_decode_io* io, float* session_dev,
+                                       void* out_dev, float* heads_dev, int variant, const void* const* images_host,
+                                       void* stream);
 int    swn_e4m3_table(float* out_dev /*256*/, float scale, void* stream);
 
 /* ---- stepped decode pool: the decode pool of the stepped multi-launch decode (variant 3: REF6-class nets) -----------

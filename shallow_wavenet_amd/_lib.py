@@ -243,13 +243,14 @@ SIGNATURES = {
 
 
 # the stored formats of the streamed head matrices (ops.DECODE_IMAGES): the size and the packing of the image, and the three
-# decode calls with the image between the variant and the stream
+# decode calls with the image between the variant and the stream; the pool over several models takes a host array of images there
 for _s in ("w16", "w8"):
     SIGNATURES[f"swn_decode_{_s}_bytes"] = (c_size_t, [POINTER(NetDesc)])
     SIGNATURES[f"swn_pack_decode_{_s}"] = (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p])
-    for _n in ("swn_decode", "swn_decode_chunk", "swn_decode_pool_chunk"):
+    for _n, _image in (("swn_decode", c_void_p), ("swn_decode_chunk", c_void_p), ("swn_decode_pool_chunk", c_void_p),
+                       ("swn_decode_pool_chunk_models", POINTER(c_void_p))):
         _res, _args = SIGNATURES[_n]
-        SIGNATURES[f"{_n}_{_s}"] = (_res, _args[:-1] + [c_void_p] + _args[-1:])
+        SIGNATURES[f"{_n}_{_s}"] = (_res, _args[:-1] + [_image] + _args[-1:])
 
 
 STAMP_PATH = os.path.join(_HERE, "libswn_hip.so.srchash")

@@ -694,7 +694,53 @@ int pool_image(int wk, const void* image, const char* where, const swn_net_desc*
     return run_call(KSEL_BL6, c);
 }
 
+// ... over several models: entry e runs models[model_of_entry[e]] with images_host[model_of_entry[e]]
+int pool_models_image(int wk, const void* const* images_host, const char* where, const swn_net_desc* d,
+                      const float* const* models, int n_models, const int32_t* model_of_entry, int capacity,
+                      const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io, float* session, void* out,
+                      float* heads, int variant, void* stream_) {
+    SwnDecodeCall c;
+    SwnPoolTable t;
+    bool work;
+    int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    if (rc < 0) return rc;
+    if (swn_pool_models_check(models, n_models, model_of_entry, n_entries) < 0) return SWN_E_BADARG;
+    if (!images_host) return SWN_E_BADARG;
+    for (int m = 0; m < n_models; ++m)
+        if (!images_host[m]) return SWN_E_BADARG;
+    rc = image_kernel_check(wk, c.g, capacity, variant, where);
+    if (rc < 0) return rc;
+    if (!work) return SWN_OK;                              // every slot stays as it is
+    SwnPoolModels m = {};
+    const void* images[SWN_POOL_MAX_MODELS];
+    for (int i = 0; i < SWN_POOL_MAX_MODELS; ++i) {
+        m.p[i] = models[i < n_models ? i : 0];
+        images[i] = images_host[i < n_models ? i : 0];
+    }
+    for (int e = 0; e < n_entries; ++e) m.of[e] = (unsigned char)model_of_entry[e];
+    c.models = &m; c.images = images; c.wk = wk;
+    return run_call(KSEL_BL6, c);
+}
+
 }  // namespace
+
+extern "C" int swn_decode_pool_chunk_models_w16(const swn_net_desc* d, const float* const* models, int n_models,
+                                                const int32_t* model_of_entry, int capacity,
+                                                const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                                float* session, void* out, float* heads, int variant,
+                                                const void* const* images_host, void* stream_) {
+    return pool_models_image(WK_BF16, images_host, "swn_decode_pool_chunk_models_w16", d, models, n_models, model_of_entry,
+                             capacity, entries, n_entries, io, session, out, heads, variant, stream_);
+}
+
+extern "C" int swn_decode_pool_chunk_models_w8(const swn_net_desc* d, const float* const* models, int n_models,
+                                               const int32_t* model_of_entry, int capacity,
+                                               const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                               float* session, void* out, float* heads, int variant,
+                                               const void* const* images_host, void* stream_) {
+    return pool_models_image(WK_E4M3, images_host, "swn_decode_pool_chunk_models_w8", d, models, n_models, model_of_entry,
+                             capacity, entries, n_entries, io, session, out, heads, variant, stream_);
+}
 
 extern "C" int swn_decode_w16(const swn_net_desc* d, const float* packed, const float* cond, int batch, int n_frames,
                               int n_steps, const swn_decode_io* io, float* state, void* out, float* heads, int variant,

@@ -409,6 +409,7 @@ template <> struct B6ArgsOf<true, false> { using type = Bl6PoolArgs; };
 template <> struct B6ArgsOf<true, true> { using type = Bl6PoolModelsArgs; };
 template <int WK> struct B6ArgsOf<false, false, WK> { using type = Bl6ImageArgs; };       // every stored format but fp32
 template <int WK> struct B6ArgsOf<true, false, WK> { using type = Bl6PoolImageArgs; };
+template <int WK> struct B6ArgsOf<true, true, WK> { using type = Bl6PoolModelsImageArgs; };
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6Args& launch, const Bl6Args&) { return launch; }
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, const Bl6Args& entry) { return entry; }
 
@@ -419,19 +420,32 @@ __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, con
 // window come from the session instead of the prologue, and they go back to it at the end.  The step itself is the same code.
 // POOL (with STREAM): one entry of a decode pool (swn_decode_pool_chunk); `a` holds the workgroup's entry as a batch-1 chunk
 // (swn_pool_entry_args), b = 0.  MODELS (with POOL): the entry's weights are those of its model (SwnPoolModels).
-// WK = WK_BF16 (W16; with EXT, without MODELS): out_skip, out_1 and the softmax out_2 stream from the bf16 image ka.img instead
-// of the fp32 lane-tiled copies, and the LDS-resident out_1 slices are widened from it; every other load and every FMA is the
-// fp32 code.  WK = WK_E4M3 (W8): the same over the FP8 image ka.img, whose row scales are copied into LDS behind the carve.
+// WK = WK_BF16 (W16; with EXT): out_skip, out_1 and the softmax out_2 stream from the bf16 image `img` instead of the fp32
+// lane-tiled copies, and the LDS-resident out_1 slices are widened from it; every other load and every FMA is the fp32 code.
+// WK = WK_E4M3 (W8): the same over the FP8 image `img`, whose row scales are copied into LDS behind the carve.  `img` is the
+// launch's image ka.img, or with MODELS the image of the entry's model, ka.img[model] - read through the model index once, so
+// the one-time loads (resident out_1 slices, W8 codes and row scales) and the three streams all take the entry's own image.
 template <class T, bool STREAM = false, bool POOL = false, bool MODELS = false, int WK = WK_F32>
 __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL, MODELS, WK>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr bool W16 = WK == WK_BF16, W8 = WK == WK_E4M3;
-    static_assert(WK == WK_F32 || (T::EXT && !MODELS), "bf16 / e4m3 weights: extended single-model instantiations only");
+    static_assert(WK == WK_F32 || T::EXT, "stored formats: extended instantiations only");
     Bl6Args pa;                                            // POOL: this workgroup's entry as a batch-1 chunk
+    [[maybe_unused]] const void* img_e = nullptr;          // stored formats with MODELS: the image of this entry's model
+    // stored formats: the image every section below is read from (one model: the launch's, read where it is used)
+    [[maybe_unused]] auto img = [&]() -> const void* {
+        if constexpr (WK == WK_F32) return nullptr;
+        else if constexpr (MODELS) return img_e;
+        else return ka.img;
+    };
     if constexpr (POOL) {
         static_assert(STREAM && T::EXT, "pools run the streamed extended mode");
         pa = ka.c;
-        if constexpr (MODELS) pa.P = swn_pool_model(ka.m);
+        if constexpr (MODELS && WK != WK_F32) {            // the entry's model names its packed buffer and its image
+            const int mi = swn_pool_model_index(ka.m);
+            pa.P = ka.m.p[mi];
+            img_e = ka.img[mi];
+        } else if constexpr (MODELS) pa.P = swn_pool_model(ka.m);
         if (!swn_pool_entry_args(pa, ka.t, T::SEG, T::KIND == SWN_KIND_SOFTMAX ? T::Q : T::SEG, T::NO)) return;
         pa.sess += (size_t)swn_pool_slot(ka.t) * T::sess_floats;
     }
@@ -466,7 +480,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
         if constexpr (W16) {
             // the resident out_1 slices hold the rounded values, widened once: slice mm is half mm & 1 of image slice mm / 2
             const unsigned* w1i = reinterpret_cast<const unsigned*>(
-                static_cast<const char*>(ka.img) + w16_layout(S, T::O1, T::NO, false).w1);
+                static_cast<const char*>(img()) + w16_layout(S, T::O1, T::NO, false).w1);
             for (int e = tid; e < T::W1L * T::O1 * 16; e += NT) {
                 const int mm = e / (T::O1 * 16);
                 const unsigned w = w1i[(mm >> 1) * T::O1 * 16 + e % (T::O1 * 16)];
@@ -475,7 +489,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
         } else if constexpr (W8) {
             // ... or stay codes: the first W1L / 4 image slices as they lie in the image (bit patterns, not numbers)
             const unsigned* w1i = reinterpret_cast<const unsigned*>(
-                static_cast<const char*>(ka.img) + w8_layout(S, T::O1, T::NO, false).w1);
+                static_cast<const char*>(img()) + w8_layout(S, T::O1, T::NO, false).w1);
             unsigned* dst = reinterpret_cast<unsigned*>(lds + T::o_w1l);
             for (int e = tid; e < (T::W1L / 4) * T::O1 * 16; e += NT) dst[e] = w1i[e];
         } else
@@ -483,7 +497,7 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
     }
     if constexpr (W8) {   // the rows' 2^-e: the three scale sections of the image are one run of floats
         const float* sc = reinterpret_cast<const float*>(
-            static_cast<const char*>(ka.img) + w8_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX).ssk);
+            static_cast<const char*>(img()) + w8_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX).ssk);
         for (int e = tid; e < w8_sc_floats<T>(); e += NT) lds[w8_o_sc<T>() + e] = sc[e];
     }
     // conditioning frames are copied 16 B per lane through a buffer resource (32-bit offsets)
@@ -680,8 +694,8 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
     [[maybe_unused]] const Bl6W16Layout y16 = w16_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX);
     [[maybe_unused]] const Bl6W8Layout y8 = w8_layout(S, T::O1, T::NO, KIND == SWN_KIND_SOFTMAX);
     auto wsrc = [&](size_t f32_off, [[maybe_unused]] size_t w16_off, [[maybe_unused]] size_t w8_off) -> const void* {
-        if constexpr (W16) return static_cast<const char*>(ka.img) + w16_off;
-        else if constexpr (W8) return static_cast<const char*>(ka.img) + w8_off;
+        if constexpr (W16) return static_cast<const char*>(img()) + w16_off;
+        else if constexpr (W8) return static_cast<const char*>(img()) + w8_off;
         else return P + f32_off;
     };
     const __amdgpu_buffer_rsrc_t wsk2 = make_rsrc(wsrc(a.y.wsk2, y16.wsk, y8.wsk), (unsigned)(L * S * 64 * WB));
@@ -1072,7 +1086,9 @@ int launch_pool(const SwnDecodeCall& c, const char* where) {
     fill_args(p.c, c);
     p.t = *c.pool;
     if constexpr (MODELS) p.m = *c.models;
-    if constexpr (WK != WK_F32) p.img = c.image;
+    if constexpr (WK != WK_F32 && MODELS) {
+        for (int m = 0; m < SWN_POOL_MAX_MODELS; ++m) p.img[m] = c.images[m];   // (filled to the end, as the model table is)
+    } else if constexpr (WK != WK_F32) p.img = c.image;
     return with_tr(c.g, [&](auto tr) {
         using T = typename decltype(tr)::Ext;
         constexpr size_t lds = WK == WK_E4M3 ? w8_lds_bytes<T>() : T::lds_bytes;
@@ -1185,8 +1201,10 @@ extern "C" int swn_e4m3_table(float* out, float scale, void* stream_) {
 // a checked call on the symmetric kernel (swn_decode.hip)
 int swn_decode_bl6_run(const SwnDecodeCall& c) {
     if (c.pool) switch (c.wk) {
-        case WK_E4M3: return launch_pool<false, WK_E4M3>(c, "swn_decode_pool_chunk_w8(bl6)");
-        case WK_BF16: return launch_pool<false, WK_BF16>(c, "swn_decode_pool_chunk_w16(bl6)");
+        case WK_E4M3: return c.models ? launch_pool<true, WK_E4M3>(c, "swn_decode_pool_chunk_models_w8(bl6)")
+                                      : launch_pool<false, WK_E4M3>(c, "swn_decode_pool_chunk_w8(bl6)");
+        case WK_BF16: return c.models ? launch_pool<true, WK_BF16>(c, "swn_decode_pool_chunk_models_w16(bl6)")
+                                      : launch_pool<false, WK_BF16>(c, "swn_decode_pool_chunk_w16(bl6)");
         default: return c.models ? launch_pool<true, WK_F32>(c, "swn_decode_pool_chunk_models(bl6)")
                                  : launch_pool<false, WK_F32>(c, "swn_decode_pool_chunk(bl6)");
     }

@@ -58,6 +58,12 @@ struct Bl6PoolImageArgs : Bl6PoolArgs {
     const void* img;
 };
 static_assert(sizeof(Bl6PoolImageArgs) <= 4096, "kernel arguments are limited to 4 KB");
+// ... and of a multi-model pool launch over a stored format (swn_decode_pool_chunk_models_w16 / _w8): one image per model behind
+// the model table, indexed like its packed buffers (m.of[entry]); 128 bytes more
+struct Bl6PoolModelsImageArgs : Bl6PoolModelsArgs {
+    const void* img[SWN_POOL_MAX_MODELS];
+};
+static_assert(sizeof(Bl6PoolModelsImageArgs) <= 4096, "kernel arguments are limited to 4 KB");
 // The bf16 image (swn_pack_decode_w16): the three lane-tiled copies wsk2 / w12 / w22 of the packed buffer rounded to bf16 (nearest
 // even), slices 2g and 2g + 1 of 16 inputs folded into one: section [NS / 2][rows][4 lanes][4 words], word j of a lane =
 // bf16(slice 2g, input 4 lane + j) in bits 0-15 | bf16(slice 2g + 1, input 4 lane + j) in bits 16-31.  A lane's 16-byte load

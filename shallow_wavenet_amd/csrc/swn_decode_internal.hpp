@@ -32,8 +32,9 @@ struct SwnDecodeCall {
     SwnGeom g;                                 // made once, by the check
     const float* packed = nullptr;             // (not read when `models` is set)
     int wk = WK_F32;                           // how the streamed head matrices are stored (WK_*) ...
-    const void* image = nullptr;               // ... and their image in that format (swn_pack_decode_w16 / _w8); fp32: null
+    const void* image = nullptr;               // ... and their image in that format (swn_pack_decode_w16 / _w8); fp32, `models`: null
     const SwnPoolModels* models = nullptr;     // a pool over several models; null: one model
+    const void* const* images = nullptr;       // ... and, over a stored format, their images: SWN_POOL_MAX_MODELS of them, as models->p
     const SwnPoolTable* pool = nullptr;        // the checked entry table of a pool launch; null: not a pool
     const float* cond = nullptr;               // (pool: every entry has its own)
     int batch = 0;                             // utterances; pool: entries

@@ -49,6 +49,8 @@ struct SwnPoolModels {
     unsigned char of[SWN_DECODE_POOL_MAX_ENTRIES];
 };
 __device__ __forceinline__ const float* swn_pool_model(const SwnPoolModels& m) { return m.p[m.of[blockIdx.x]]; }
+// ... and the index itself, for launches that carry a second per-model table beside p (the images of a stored format)
+__device__ __forceinline__ int swn_pool_model_index(const SwnPoolModels& m) { return m.of[blockIdx.x]; }
 
 // the checks the *_models entry points add to their single-model twins; SWN_OK or SWN_E_BADARG
 inline int swn_pool_models_check(const float* const* models, int n_models, const int32_t* model_of_entry, int n_entries) {

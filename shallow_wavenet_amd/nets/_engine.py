@@ -160,12 +160,13 @@ class EngineMixin:
         When the engine resolves to the stepped multi-launch decode (REF6-class nets: variant 0 or 3), the pool is a
         SteppedDecodePool (its step() also takes max_prologue).  post_filter: as open_stream, one slot per session.
         multi_model: the pool is to serve further nets of this geometry (add_model, open(model=k)): a net of the stepped
-        decode then gets a SteppedModelPool; the DecodePool of the other nets takes add_model as it is.
+        decode then gets a SteppedModelPool; the DecodePool of the other nets takes add_model as it is with fp32 weights,
+        and with weights="bf16" | "e4m3" the pool is a DecodeModelPool (several models over stored weights in one launch).
         prologue: "stepped" | "parallel", as SteppedDecodePool takes it; "parallel" on a net of another decode is a
-        ValueError.  weights: "fp32" | "bf16" | "e4m3" as DecodePool takes it (one model, not on the stepped pools); None = the
-        module's `decode_weights`."""
+        ValueError.  weights: "fp32" | "bf16" | "e4m3" as DecodePool takes it (one model unless multi_model; not on the
+        stepped pools); None = the module's `decode_weights`."""
         from .. import _lib, noise as _noise, ops as _ops
-        from ..streaming import DecodePool, SteppedDecodePool, SteppedModelPool, _check_prologue
+        from ..streaming import DecodeModelPool, DecodePool, SteppedDecodePool, SteppedModelPool, _check_prologue
         key = getattr(self, "noise_rng_seed", None)
         rng_seed = _noise.draw_rng_seed() if key is None else int(key)
         net = self._engine()
@@ -174,7 +175,8 @@ class EngineMixin:
             cls = SteppedModelPool if multi_model else SteppedDecodePool
             return cls(net, capacity, rng_seed=rng_seed, post_filter=post_filter, prologue=prologue, weights=weights)
         _check_prologue(prologue, False)
-        return DecodePool(net, capacity, variant=variant, rng_seed=rng_seed, post_filter=post_filter, weights=weights)
+        cls = DecodeModelPool if multi_model and weights != "fp32" else DecodePool
+        return cls(net, capacity, variant=variant, rng_seed=rng_seed, post_filter=post_filter, weights=weights)
 
     def set_packed_engine(self, net: HipNet) -> None:
         """install an engine whose packed buffer arrived by RCCL broadcast (dist.py)."""

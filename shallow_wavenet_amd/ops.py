@@ -28,6 +28,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.decode_<sfx>(packed, image, cond, ...decode's arguments)            -> (out, heads, noise_used)
     torch.ops.swn.decode_chunk_<sfx>(packed, image, cond, session, ...decode_chunk's) -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_chunk_<sfx>(packed, image, session, ...decode_pool_chunk's) -> (out, heads, noise_used)
+    torch.ops.swn.decode_pool_chunk_models_<sfx>(models, images, model_of, session, ...decode_pool_chunk_models')
+                                                                   -> (out, heads, noise_used)   (images[m]: the image of models[m])
     torch.ops.swn.e4m3_table(like, scale)                          -> (256,) fp32: the kernels' conversion of codes 0 .. 255
     torch.ops.swn.decode_pool_stepped_chunk(packed, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids, desc,
                                             capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
@@ -588,11 +590,51 @@ def _decode_pool_fake(packed, conds, n_steps, desc, want_heads, want_noise):
             packed.new_empty((E, n_max, width) if want_noise else (0,)))
 
 
+def decode_pool_chunk_models_impl(models: List[torch.Tensor], model_of: List[int], session: torch.Tensor,
+                                  conds: List[torch.Tensor], slots: List[int], step0s: List[int], n_steps: List[int],
+                                  begins: List[bool], seeds: Optional[torch.Tensor], utt_ids: List[int], desc: List[int],
+                                  capacity: int, variant: int, rng_seed: int, want_heads: bool, want_noise: bool
+                                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """decode_pool_chunk over sessions of several models of one geometry (swn_decode_pool_chunk_models): entry e runs with the
+    packed parameters models[model_of[e]] (at most 16 models per call); everything else as decode_pool_chunk, and every
+    entry's rows bit-identical to decode_pool_chunk with that entry's model."""
+    return _decode_pool_chunk_models_call(None, None, models, model_of, session, conds, slots, step0s, n_steps, begins, seeds,
+                                          utt_ids, desc, capacity, variant, rng_seed, want_heads, want_noise)
+
+
+def _decode_pool_chunk_models_call(fmt, images, models, model_of, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids,
+                                   desc, capacity, variant, rng_seed, want_heads, want_noise):
+    """decode_pool_chunk_models (fmt None: swn_decode_pool_chunk_models) and decode_pool_chunk_models_<suffix> over one image
+    of a stored format per model (swn_decode_pool_chunk_models_<suffix>): images[m] is the image of models[m]"""
+    d = _desc(desc)
+    L = _lib.lib()
+    name = "decode_pool_chunk_models" + ("" if fmt is None else f"_{fmt.suffix}")
+    dev, ptrs, of = _model_tables(L, d, models, model_of, len(conds), name)
+    trail = ()
+    if fmt is not None:
+        if len(images) != len(models):
+            raise RuntimeError(f"{name}: {len(images)} images for {len(models)} models")
+        trail = ((ctypes.c_void_p * len(models))(*[_check_image(fmt, im, t, d).data_ptr() for im, t in zip(images, models)]),)
+    return _decode_pool_call(getattr(L, "swn_" + name), d, dev, (ptrs, len(models), of), trail, session, conds, slots, step0s,
+                             n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
+
+
+decode_pool_chunk_models = custom_op("swn::decode_pool_chunk_models",
+                                     mutates_args=("session",))(decode_pool_chunk_models_impl)
+
+
+@decode_pool_chunk_models.register_fake
+def _decode_pool_chunk_models_op_fake(models, model_of, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc,
+                                      capacity, variant, rng_seed, want_heads, want_noise):
+    return _decode_pool_fake(models[0], conds, n_steps, desc, want_heads, want_noise)
+
+
 # ------------------------------------------------------------------------------------------ decode over a stored format
 def _image_ops(fmt: DecodeImage) -> dict:
-    """registers the four ops of a stored format -> {name: op, name_impl: function}: pack_decode_<suffix>(packed, desc) -> the
-    image, uint8; and decode_<suffix>, decode_chunk_<suffix>, decode_pool_chunk_<suffix>: the fp32 ops with the image as their
-    second argument (named <suffix>), in everything else - annotations, defaults, the mutated session - the fp32 signature.
+    """registers the five ops of a stored format -> {name: op, name_impl: function}: pack_decode_<suffix>(packed, desc) -> the
+    image, uint8; and decode_<suffix>, decode_chunk_<suffix>, decode_pool_chunk_<suffix>, decode_pool_chunk_models_<suffix>:
+    the fp32 ops with the image (the models form: one image per model, Tensor[]) as their second argument (named <suffix>), in
+    everything else - annotations, defaults, the mutated session - the fp32 signature.
     The variant must resolve to the symmetric BL6 kernel (6 for the single-sample Laplace nets); the chunks of a stream
     concatenate to the one-shot decode of the format bit for bit, and a pool entry's rows are those of its session alone."""
     s = fmt.suffix
@@ -628,6 +670,8 @@ def _image_ops(fmt: DecodeImage) -> dict:
     image_form(decode_impl, _decode_call, _decode_op_fake, ())
     image_form(decode_chunk_impl, _decode_chunk_call, _decode_chunk_op_fake, ("session",))
     image_form(decode_pool_chunk_impl, _decode_pool_chunk_call, _decode_pool_chunk_op_fake, ("session",))
+    # ... and the pool over several models: `models` first, then one image per model (Tensor[] <suffix>)
+    image_form(decode_pool_chunk_models_impl, _decode_pool_chunk_models_call, _decode_pool_chunk_models_op_fake, ("session",))
     return made
 
 
@@ -646,29 +690,13 @@ def decode_lead(net, op: str, weights: str):
     return f"{op}_{suffix}", (net.packed, getattr(net, f"decode_{suffix}_image")())
 
 
-def decode_pool_chunk_models_impl(models: List[torch.Tensor], model_of: List[int], session: torch.Tensor,
-                                  conds: List[torch.Tensor], slots: List[int], step0s: List[int], n_steps: List[int],
-                                  begins: List[bool], seeds: Optional[torch.Tensor], utt_ids: List[int], desc: List[int],
-                                  capacity: int, variant: int, rng_seed: int, want_heads: bool, want_noise: bool
-                                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """decode_pool_chunk over sessions of several models of one geometry (swn_decode_pool_chunk_models): entry e runs with the
-    packed parameters models[model_of[e]] (at most 16 models per call); everything else as decode_pool_chunk, and every
-    entry's rows bit-identical to decode_pool_chunk with that entry's model."""
-    d = _desc(desc)
-    L = _lib.lib()
-    dev, ptrs, of = _model_tables(L, d, models, model_of, len(conds), "decode_pool_chunk_models")
-    return _decode_pool_call(L.swn_decode_pool_chunk_models, d, dev, (ptrs, len(models), of), (), session, conds, slots, step0s,
-                             n_steps, begins, seeds, utt_ids, capacity, variant, rng_seed, want_heads, want_noise)
-
-
-decode_pool_chunk_models = custom_op("swn::decode_pool_chunk_models",
-                                     mutates_args=("session",))(decode_pool_chunk_models_impl)
-
-
-@decode_pool_chunk_models.register_fake
-def _(models, model_of, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc, capacity, variant, rng_seed,
-      want_heads, want_noise):
-    return _decode_pool_fake(models[0], conds, n_steps, desc, want_heads, want_noise)
+def decode_models_lead(nets, op: str, weights: str):
+    """decode_lead for a call over several models (op: "decode_pool_chunk_models"): the op's name and its leading arguments, the
+    nets' packed parameters and, unless fp32, their images of the format - both read now, so a repacked net brings its new ones"""
+    if weights == "fp32":
+        return op, ([n.packed for n in nets],)
+    suffix = DECODE_IMAGES[weights].suffix
+    return f"{op}_{suffix}", ([n.packed for n in nets], [getattr(n, f"decode_{suffix}_image")() for n in nets])
 
 
 def stepped_pool_session_floats(d, capacity: int) -> int:
@@ -1762,7 +1790,8 @@ def _(table, state, staged, n_ins, slots, in0s, out0s, n_outs, lens, up, down, n
 OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk", "decode_pool_chunk", "decode_pool_stepped_chunk",
             "pack_decode_w16", "decode_w16", "decode_chunk_w16", "decode_pool_chunk_w16",
             "pack_decode_w8", "decode_w8", "decode_chunk_w8", "decode_pool_chunk_w8", "e4m3_table",
-            "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
+            "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_chunk_models_w16", "decode_pool_chunk_models_w8",
+            "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
             "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",

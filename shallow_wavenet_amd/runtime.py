@@ -335,7 +335,8 @@ class HipNet:
 
     def _decode_image(self, weights: str) -> torch.Tensor:
         """the image of the streamed head matrices in a stored format (torch.ops.swn.pack_decode_<suffix>), built on first use
-        and rebuilt when the packed parameters moved on (repack)"""
+        and rebuilt when the packed parameters moved on (repack).  Streams and pools - a DecodeModelPool for every model of
+        a launch - ask for it at call time, as they read `packed`."""
         version, image = self._decode_images.get(weights, (None, None))
         if version != self.packed_version:
             image = getattr(_O, "pack_decode_" + _ops.DECODE_IMAGES[weights].suffix)(self.packed, self.dlist)

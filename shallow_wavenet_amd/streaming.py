@@ -18,6 +18,8 @@ Models.  A deployment holds one checkpoint per target speaker, all of one geomet
 registers further nets of the pool's NetConfig and open(model=k) binds a session to one of them; a tick whose sessions name
 more than one model issues the *_models ops (swn_decode_pool_chunk_models, swn_frontend_pool_models), which take at most 16
 models per call - split_models cuts the planned calls accordingly.  A tick over one model issues the single-model ops.
+Over bf16 / E4M3 head matrices (weights=...) the pool of several models is DecodeModelPool: its mixed ticks issue
+decode_pool_chunk_models_w16 / _w8 with one image per model of the call; a DecodePool of stored weights keeps to one model.
 The nets people fine-tune per speaker (REF6) decode on the stepped chain: their multi-voice pool is SteppedModelPool
 (swn_decode_pool_stepped_chunk_models), whose launch chain serves the sessions of all models of a call at once - the table is
 grouped by model, so a tile of eight sessions fetches ONE model's weight rows.  SteppedDecodePool stays the one-model pool.
@@ -433,8 +435,8 @@ class DecodePool:
                post-filter call over the sessions that ran; each result then ends with the restored chunk (1, n * seg) fp32
     weights    "fp32" (default) | "bf16" | "e4m3": the streamed head matrices stored as bf16 (swn_decode_pool_chunk_w16) or FP8
                E4M3 (swn_decode_pool_chunk_w8), each session bit-identical to its solo DecodeStream of that mode.  Symmetric BL6
-               kernel only (variant=6 for the single-sample Laplace nets); such a pool serves one model (add_model raises) and
-               no stepped pool has the modes
+               kernel only (variant=6 for the single-sample Laplace nets); such a DecodePool serves one model (add_model raises:
+               DecodeModelPool is the pool of several models over stored weights) and no stepped pool has the modes
 
         k = pool.add_model(other_net)           # another net of the same NetConfig (the pool's own net is model 0)
         s = pool.open(seed=None, utt_id=None, model=0)   # a free slot; utt_id defaults to the admission counter
@@ -443,6 +445,8 @@ class DecodePool:
         results = pool.step(max_steps=None)    # one tick -> {session: (out, heads[, noise])}, views of the launch outputs
         pool.close(s)                          # frees the slot, finished or not
     """
+
+    _stored_models = False        # add_model on a pool of stored weights: DecodeModelPool's
 
     def __init__(self, net, capacity: int, *, variant: int = 0, rng_seed: int = 0, want_heads: bool = False,
                  want_noise: bool = False, post_filter=None, weights: str = "fp32"):
@@ -479,9 +483,9 @@ class DecodePool:
         """register another net of the pool's geometry (a voice fine-tuned from the same recipe) -> its model index for
         open(model=...).  A session slot's layout depends on the geometry only, so sessions of all models share the pool's
         slots and launches.  The pool may hold any number of models; the nets' packed buffers are read at call time."""
-        if self.weights != "fp32":
-            raise ValueError(f'add_model: a weights="{self.weights}" pool serves one model - the multi-model launch has no '
-                             f"{self.weights} form")
+        if self.weights != "fp32" and not self._stored_models:
+            raise ValueError(f'add_model: a weights="{self.weights}" DecodePool serves one model - DecodeModelPool serves '
+                             f"several models over {self.weights} weights")
         if net.cfg != self.cfg:
             raise ValueError("add_model: the net's NetConfig differs from the pool's - the models of a pool share one geometry")
         if torch.device(net.device) != torch.device(self.net.device):
@@ -536,11 +540,12 @@ class DecodePool:
             args = (self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
                     [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
                     self.net.dlist, self.capacity, self.variant, self.rng_seed, self.want_heads, self.want_noise)
-            if len(models) == 1:                    # (a pool of stored weights serves its own net alone: add_model)
+            if len(models) == 1:
                 op, lead = _ops.decode_lead(self._models[models[0]], "decode_pool_chunk", self.weights)
                 out, heads, used = getattr(_O, op)(*lead, *args)
-            else:
-                out, heads, used = _O.decode_pool_chunk_models([self._models[m].packed for m in models], of, *args)
+            else:                                   # (stored weights: a DecodeModelPool - one image per model of the call)
+                op, lead = _ops.decode_models_lead([self._models[m] for m in models], "decode_pool_chunk_models", self.weights)
+                out, heads, used = getattr(_O, op)(*lead, of, *args)
             for e, (s, step0, n) in enumerate(entries):
                 s._stream.steps_done = step0 + n
                 s._stream._begun = True
@@ -671,6 +676,20 @@ class DecodePool:
         if self.soft:
             return torch.full((1,), int(self.cfg.n_quantize) // 2, dtype=torch.int32)
         return torch.zeros(self.seg, dtype=torch.float32)
+
+
+class DecodeModelPool(DecodePool):
+    """a decode pool of any `weights` whose sessions may each run a different model of the pool's geometry - one checkpoint per
+    target speaker - in the SAME launch, also over bf16 / E4M3 head matrices (swn_decode_pool_chunk_models_w16 / _w8): the
+    workgroup of a session reads its model's packed parameters and its model's image, so each session's output is bit-identical
+    to its solo DecodeStream(model, 1, weights=...) whatever shares its launch.  add_model / open(model=k) and everything else
+    as DecodePool; with weights="fp32" it is DecodePool.  A tick whose sessions name several models issues
+    decode_pool_chunk_models_<suffix> with the packed buffers and decode_<suffix>_image() of the launch's models, both read at
+    call time (a repacked net brings its new image), in calls cut at 16 models (split_models); a tick over one model issues the
+    single-model op with that model, so a pool that never mixes pays nothing.  push_many / PoolSession.push are DecodePool's:
+    the front end has no stored format."""
+
+    _stored_models = True
 
 
 # -------------------------------------------------------------------------------------------------- stepped decode pool
