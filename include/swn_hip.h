@@ -121,7 +121,13 @@ int    swn_unfold_grads_device(const swn_net_desc* d, const float* gpacked_dev, 
  *   aux_dev   (B, n_aux, Tf)             in
  *   work_dev  swn_frontend_work_floats() scratch
  *   cond_dev  (B, Tf, L*seg*2H)          out; NULL = stop after conv_aux (the dropout mode, swn_forward_drop, applies
- *                                        in_x at sample rate and reads only the activations kept in work_dev) */
+ *                                        in_x at sample rate and reads only the activations kept in work_dev)
+ * swn_frontend_conv_lds_bytes: which kernel serves conv_aux layer `layer` (0-based) - the bytes of dynamic LDS swn_frontend
+ * requests for it when the layer runs with its window and weight rows staged in LDS (k = 3, at most 150 KB:
+ * 4 * (cin * (64 + 2 * dilation) + 16 * cin * 3) - the window of all input rows and sixteen weight rows; above 48 KB the launch first raises the kernel's limit), 0 when it runs unstaged (any
+ * other k, a larger layer) or when the descriptor or the layer index is refused.  swn_frontend decides by the same function;
+ * only a refusal of the raised limit at run time sends a staged layer to the unstaged kernel (same bits). */
+size_t swn_frontend_conv_lds_bytes(const swn_net_desc* d, int layer);
 size_t swn_frontend_work_floats(const swn_net_desc* d, int batch, int n_frames);
 size_t swn_cond_floats(const swn_net_desc* d, int batch, int n_frames);
 int    swn_frontend(const swn_net_desc* d, const float* packed_dev, const float* aux_dev,

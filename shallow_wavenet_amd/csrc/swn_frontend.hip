@@ -227,7 +227,22 @@ __global__ __launch_bounds__(256) void cond_gemm_kernel(
     }
 }
 
+// Dynamic LDS of conv_aux layer i when conv1d_same_lds_kernel serves it, 0 when it runs unstaged: the 64 frames and the halo of
+// `dil` on each side of all cin input rows, and the sixteen output channels' weight rows.  Staged: k = 3 up to 150 KB.
+constexpr size_t FE_LDS_DEFAULT = 48 * 1024;               // above it the launch first raises the kernel's dynamic LDS limit
+constexpr size_t FE_LDS_MAX = 150 * 1024;
+size_t fe_conv_lds_bytes(const SwnGeom& g, int i) {
+    if (g.auxk != 3) return 0;
+    const size_t lds = ((size_t)g.aux_cin[i] * (64 + 2 * g.aux_dil[i]) + 16 * (size_t)g.aux_cin[i] * 3) * sizeof(float);
+    return lds <= FE_LDS_MAX ? lds : 0;
+}
+
 }  // namespace
+
+extern "C" size_t swn_frontend_conv_lds_bytes(const swn_net_desc* d, int layer) {
+    SwnGeom g; if (swn_make_geom(d, &g) < 0 || layer < 0 || layer >= g.auxl) return 0;
+    return fe_conv_lds_bytes(g, layer);
+}
 
 extern "C" size_t swn_frontend_work_floats(const swn_net_desc* d, int batch, int n_frames) {
     SwnGeom g; if (swn_make_geom(d, &g) < 0 || batch < 1 || n_frames < 1) return 0;
@@ -261,9 +276,9 @@ extern "C" int swn_frontend(const swn_net_desc* d, const float* packed, const fl
     cur += bt * g.n_aux;
     for (int i = 0; i < g.auxl; ++i) {
         dim3 grid((n_frames + 63) / 64, (g.aux_cout[i] + 15) / 16, batch);
-        const size_t lds = ((size_t)g.aux_cin[i] * (64 + 2 * g.aux_dil[i]) + 16 * (size_t)g.aux_cin[i] * 3) * sizeof(float);
-        bool staged = g.auxk == 3 && lds <= 150 * 1024;
-        if (staged && lds > 48 * 1024) {
+        const size_t lds = fe_conv_lds_bytes(g, i);       // what swn_frontend_conv_lds_bytes reports
+        bool staged = lds > 0;
+        if (staged && lds > FE_LDS_DEFAULT) {
             static size_t granted = 0;                     // the attribute is per function: raise it when a larger geometry comes
             if (lds > granted) {
                 if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_same_lds_kernel),

@@ -36,39 +36,27 @@ def _seg(cfg):
 class _Utt:
     """one utterance driven through frontend_pool: its features, its session buffers and where it stands"""
 
-    def __init__(self, cfg, F, seed, N, rng, one_piece=False):
+    def __init__(self, cfg, F, seed, N, rng, one_piece=False, pieces=(0, 8)):
         self.full = torch.from_numpy(synth_aux(cfg, 1, F, seed=seed)).to(DEV)
-        self.F, self.one_piece = F, one_piece
+        self.F, self.one_piece, self.pieces = F, one_piece, pieces
         self.aux = torch.zeros((cfg.n_aux, F + int(rng.integers(0, 9))), dtype=torch.float32, device=DEV)
         self.cond = torch.zeros((F + int(rng.integers(0, 3)), N), dtype=torch.float32, device=DEV)
         self.received = self.final = 0
         self.ended = False
 
     def next_entry(self, rng, la):
-        """(piece, n_received, f0, f1, final) of this utterance's next call: 0 to 7 new frames; the features end with the last
-        piece or, as often, with an empty call after it"""
-        k = self.F if self.one_piece else int(rng.integers(0, 8))
+        """(piece, n_received, f0, f1, final) of this utterance's next call: 0 to 7 new frames (pieces[0] to pieces[1] - 1);
+        the features end with the last piece or, as often, with an empty call after it"""
+        k = self.F if self.one_piece else int(rng.integers(*self.pieces))
         a, b = self.received, min(self.F, self.received + k)
         fin = b == self.F and (a == b or self.one_piece or rng.random() < 0.5)
         f1 = b if fin else max(0, b - la)
         return self.full[0, :, a:b].contiguous().reshape(-1), b, self.final, max(self.final, f1), fin
 
 
-OP_NETS = [("tiny_lap", C.tiny("laplace", 2, 4)), ("bl6_lap", C.bl6_laplace()), ("bl6_s5l4", C.bl6_laplace(5, 4)),
-           ("bl6_smx", C.bl6_softmax()), ("ref6_lap", C.ref6_laplace()), ("ref6_smx", C.ref6_softmax())]
-
-
-@pytest.mark.parametrize("n_utt", [1, 7, 64])
-@pytest.mark.parametrize("name,cfg", OP_NETS, ids=[n[0] for n in OP_NETS])
-def test_op_rows_equal_the_one_shot_front_end(gpu_ok, name, cfg, n_utt):
-    """n_utt utterances of 5 to 40 frames, one of 600 frames in pushes of 0 to 7 and one of 600 frames in one piece, every one
-    an entry at its own position of every call until it has ended"""
-    net = _net(name, cfg)
-    rng = np.random.default_rng(1000 + n_utt + len(name))
-    la = lookahead_frames(cfg)
-    N = cfg.L * _seg(cfg) * 2 * cfg.H
-    utts = [_Utt(cfg, int(rng.integers(5, 41)), 300 + i, N, rng) for i in range(n_utt)]
-    utts += [_Utt(cfg, 600, 298, N, rng), _Utt(cfg, 600, 299, N, rng, one_piece=True)]
+def _drive_op(net, utts, rng, la, name):
+    """every utterance an entry at its own position of every frontend_pool call (64 entries per call) until it has ended; then
+    every cond row against the one-shot front end over the whole utterance"""
     dirty = torch.zeros((), dtype=torch.int64, device=DEV)
     calls = 0
     while any(not u.ended for u in utts):
@@ -92,6 +80,25 @@ def test_op_rows_equal_the_one_shot_front_end(gpu_ok, name, cfg, n_utt):
         assert u.final == u.F and torch.equal(u.cond[:u.F], want), (name, i, u.F)
         assert torch.equal(u.aux[:, :u.F], u.full[0]), (name, i)
         assert int(torch.count_nonzero(u.aux[:, u.F:])) == 0
+    return calls
+
+
+OP_NETS = [("tiny_lap", C.tiny("laplace", 2, 4)), ("bl6_lap", C.bl6_laplace()), ("bl6_s5l4", C.bl6_laplace(5, 4)),
+           ("bl6_smx", C.bl6_softmax()), ("ref6_lap", C.ref6_laplace()), ("ref6_smx", C.ref6_softmax())]
+
+
+@pytest.mark.parametrize("n_utt", [1, 7, 64])
+@pytest.mark.parametrize("name,cfg", OP_NETS, ids=[n[0] for n in OP_NETS])
+def test_op_rows_equal_the_one_shot_front_end(gpu_ok, name, cfg, n_utt):
+    """n_utt utterances of 5 to 40 frames, one of 600 frames in pushes of 0 to 7 and one of 600 frames in one piece, every one
+    an entry at its own position of every call until it has ended"""
+    net = _net(name, cfg)
+    rng = np.random.default_rng(1000 + n_utt + len(name))
+    la = lookahead_frames(cfg)
+    N = cfg.L * _seg(cfg) * 2 * cfg.H
+    utts = [_Utt(cfg, int(rng.integers(5, 41)), 300 + i, N, rng) for i in range(n_utt)]
+    utts += [_Utt(cfg, 600, 298, N, rng), _Utt(cfg, 600, 299, N, rng, one_piece=True)]
+    _drive_op(net, utts, rng, la, name)
 
 
 def test_rejected_op_call_changes_nothing(gpu_ok):
