@@ -17,7 +17,8 @@
 //     out_1; the last layer's is formed by group A, from group B's half in LDS, in the one phase where the chain waits for
 //     group B - with lpc 0 half of its operands are requested a phase early, in front of barrier 5), and the whole out_skip
 //     accumulation of step t (slice l in the phase after layer l: its four input quads read at the head of the phase, the
-//     next slice's weights requested quarter by quarter behind the multiply-adds that free their registers);
+//     next slice's weights requested quarter by quarter behind the multiply-adds that free their registers; in the classic lpc 0
+//     kernel slice 0 does not stream: it stays in 32 registers of group B from the launch's start);
 //   * group A keeps its halves of all six matrices in registers (192 per thread), group B five of them (160) and the sixth in LDS
 //     (it also holds a slice of out_skip weights in flight); the out_1 matrix is LDS-resident whole (the 64 KB the sixth layer of
 //     the symmetric kernel took), only out_skip streams from L2;
@@ -26,13 +27,23 @@
 //     layer 0 (wave 0 alone stores the sample and the heads).  Between the sample and layer 0's first LDS read stands the input
 //     layer's arithmetic and its one LDS write only: the next step's conditioning taps, parity offset and layer-0 row are formed
 //     while the tail waits for the partials (one step ahead), the wave's own h0 is read back without a wait (LDS serves a wave's
-//     operations in order), and the sample and heads stores and the loop latch come behind the write.
+//     operations in order), and in the classic lpc 0 kernel the sample and heads stores wait one step: the loop is rotated, they leave behind layer 0's
+//     first LDS reads of the next step, with the refill test and the noise staging (the last step's behind the loop).
 // Same arithmetic per element as the symmetric kernel up to the order of the partial sums (1e-7 relative); same noise, seed,
 // forced-input and heads interface (swn_decode_bl6.hip: classic = host-drawn noise, zero seed; extended = in-kernel generator,
 // noise dump, caller's seed waveform).  8 barriers per step.  cswnv_shift1.py:281-430.
 #include <type_traits>
 #include "swn_decode_bl6_common.hpp"
 #include "swn_decode_internal.hpp"
+
+// diagnostic builds only (the forms profiles/decode_bl6w_resident_bench.json compares): -DSWN_RES_SLICE=-1 streams every out_skip
+// slice as the parent did, =5 keeps the last slice resident instead of the first; -DSWN_ROTATE=0 leaves group A's loop unrotated
+#ifndef SWN_RES_SLICE
+#define SWN_RES_SLICE 0
+#endif
+#ifndef SWN_ROTATE
+#define SWN_ROTATE 1
+#endif
 
 namespace {
 
@@ -104,18 +115,38 @@ __device__ __forceinline__ float quad_sum_by_parity(float own, float other) {
 // ---- group A: layer LAYER at position q - current tap, gate epilogue, hand-off.  Thread (o, p): rows o (gate) and o + 64
 //      (candidate) over inputs 16 p .. 16 p + 15 of h_{l-1}(q), read from the row `xr`; lanes 0 / 1 of the quad finish the gate / the
 //      candidate.  `po`: the offset of position q's parity in o_old, (q & 1) * L * 2 * H (the step loop forms it one step ahead).
-template <class T, int LAYER>
+//      `behind`: work that is not the chain's, issued behind the layer's first LDS reads - the epilogue operands and NQ of the four
+//      input quads - and in front of their first use, so that it runs while the reads are on their way (the rotated step loop: the
+//      previous step's stores, the refill test, the noise staging); the other quads are read behind it, under the first
+//      quads' multiply-adds.  NoWork: the reads stay where the multiply-adds want them.
+//      (NQ, one session, k samples/s of the headline beside the parent's 397.6: 0 quads early 398.7, one 403.1, two 403.9, three
+//       401.8, all four 396.4 - every early quad holds four registers through the stores, and from three on a kernel spills)
+struct NoWork { __device__ __forceinline__ void operator()() const {} };
+template <class T, int LAYER, int NQ = 2, class BEHIND = NoWork>
 __device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], const int q, const float wj, const int pb, const int po,
-                                        const int ta, const float* xr) {
+                                        const int ta, const float* xr, BEHIND&& behind = NoWork{}) {
+    constexpr bool ROT = !std::is_same<typename std::decay<BEHIND>::type, NoWork>::value;
     const int o = ta >> 2, p = ta & 3, pr = p & 1;
     // epilogue operands first: their LDS latency hides under the FMAs
     const float e_old = lds[T::o_old + po + LAYER * 2 * H + pr * H + o];
-    const float e_gx = fmaf(wj, lds[T::o_gp + pb + LAYER * 2 * H + pr * H + o], lds[T::o_bx + LAYER * 2 * H + pr * H + o]);
+    const float g_gp = lds[T::o_gp + pb + LAYER * 2 * H + pr * H + o], g_bx = lds[T::o_bx + LAYER * 2 * H + pr * H + o];
     const float e_hp = xr[o];
+    static_assert(NQ >= 0 && NQ <= 4, "early quads");
+    float4 xq[4];
+    if constexpr (ROT) {
+#pragma unroll
+        for (int m = 0; m < NQ; ++m) xq[m] = *reinterpret_cast<const float4*>(xr + 16 * p + 4 * m);
+        __builtin_amdgcn_sched_barrier(0);
+        behind();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const float e_gx = fmaf(wj, g_gp, g_bx);
     float az = 0.f, ac = 0.f;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        const float4 x = *reinterpret_cast<const float4*>(xr + 16 * p + 4 * m);
+        float4 x;
+        if (ROT && m < NQ) x = xq[m];
+        else x = *reinterpret_cast<const float4*>(xr + 16 * p + 4 * m);
         az = fmaf(w[0][4 * m], x.x, az); ac = fmaf(w[1][4 * m], x.x, ac);
         az = fmaf(w[0][4 * m + 1], x.y, az); ac = fmaf(w[1][4 * m + 1], x.y, ac);
         az = fmaf(w[0][4 * m + 2], x.z, az); ac = fmaf(w[1][4 * m + 2], x.z, ac);
@@ -313,9 +344,12 @@ __device__ __forceinline__ void skip_issue_b(__amdgpu_buffer_rsrc_t wsk2, float4
 //  piece paid another exposed round trip.  In this build, one session: halves 175.5 ms and quarters 176.9 ms with the reads
 //  piece by piece, quarters 166.2 ms and eighths - one row of one quad - 166.2 ms with the four reads at the head; in another
 //  session, both without layer_a's transposed reduction: halves 172.5 ms, quarters 167.4 ms with the reads at the head.  DESIGN 3.1.)
-template <class T, int LAYER>
-__device__ __forceinline__ void skip_roll_b(const float* lds, __amdgpu_buffer_rsrc_t wsk2, float4 (&wsl)[8], float (&sacc)[2], const int tb,
-                                            const unsigned step0) {
+// (`wcur`: the registers slice LAYER - 1 is consumed from, `wnext`: those slice LAYER is requested into - the same eight of the
+//  rolling buffer, or, for a slice kept resident across the steps, the resident registers on one side of it: consumed and left
+//  as they are, with the buffer free for the requests.  REQ false: the next slice is resident, nothing is requested)
+template <class T, int LAYER, bool REQ = true>
+__device__ __forceinline__ void skip_roll_b(const float* lds, __amdgpu_buffer_rsrc_t wsk2, const float4 (&wcur)[8], float4 (&wnext)[8],
+                                            float (&sacc)[2], const int tb, const unsigned step0) {
     static_assert(LAYER >= 1 && LAYER < L, "slice LAYER - 1 in flight, slice LAYER to request");
     const int r = tb >> 2, hp = tb & 3;
     float4 xs[4];
@@ -325,14 +359,14 @@ __device__ __forceinline__ void skip_roll_b(const float* lds, __amdgpu_buffer_rs
     for (int mm = 0; mm < 4; ++mm) {
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) {
-            const float4 x = xs[mm], w = wsl[ps * 4 + mm];
+            const float4 x = xs[mm], w = wcur[ps * 4 + mm];
             sacc[ps] = fmaf(w.x, x.x, sacc[ps]); sacc[ps] = fmaf(w.y, x.y, sacc[ps]);
             sacc[ps] = fmaf(w.z, x.z, sacc[ps]); sacc[ps] = fmaf(w.w, x.w, sacc[ps]);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps)
-            wsl[ps * 4 + mm] = buf_ld4(wsk2, (unsigned)((r + 64 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 4 + mm) * S) * 64u + step0);
+            if (REQ) wnext[ps * 4 + mm] = buf_ld4(wsk2, (unsigned)((r + 64 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 4 + mm) * S) * 64u + step0);
         __builtin_amdgcn_sched_barrier(0);
     }
     // pin the partial sums to this phase: only the end of the step uses them, and the optimiser otherwise sinks all six slices'
@@ -544,6 +578,23 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     noise_chunk(1);
 
     const __amdgpu_buffer_rsrc_t wsk2 = make_rsrc(P + a.y.wsk2, (unsigned)(L * S * 64 * sizeof(float)));
+    // One out_skip slice RESIDENT in group B, in the 32 registers it has left beside the 160 of its weights, the rolling slice
+    // and the rows in flight: loaded once here (of a pool entry's own model: P is the entry's), consumed every step where
+    // the rolling buffer would have held it, never rewritten.  Slice 0: the merged phase requests nothing and L1 consumes the
+    // resident registers while it requests slice 1 into the empty buffer.  Slice 5: L5 requests nothing and skip-fin waits for no
+    // load.  Either way the stream is 160 KB per step instead of 192.  (RES < 0: the parent's form, every slice streamed)
+    // Slice 0 is built: in one session the headline ran 399.9 k samples/s with it, 394.2 with slice 5, 395.5 as the parent, and
+    // slice 5 spills 2 - 8 registers in the chunk and pool kernels, slice 0 in none of the ten.
+    // The classic lpc 0 kernel alone takes this form and the rotated loop below (NEWFORM): it is the one whose launch they shorten
+    // (2.530 -> 2.492 us per step).  The extended kernels fit them without a spill and are SLOWER with them - a streamed chunk of
+    // 220 steps 2.581 -> 2.603 us per step with the slice, 2.619 with the rotation, 2.643 with both, the one-shot extended decode
+    // and the pool tick no faster - so they keep the parent's form; the classic lpc 4 kernel keeps it too.
+    constexpr bool NEWFORM = !EXT && T::LPC == 0;
+    constexpr int RES = (grpA || !NEWFORM) ? -1 : SWN_RES_SLICE;
+    static_assert(RES == -1 || RES == 0 || RES == L - 1, "the first or the last slice");
+    float4 wres[8];
+    if constexpr (RES == 0) skip_issue_b<0>(wsk2, wres, tg, 0u);
+    if constexpr (RES == L - 1) skip_issue_b<L - 1>(wsk2, wres, tg, 0u);
 
 #ifdef SWN_STAMP
     // diagnostic build only (tools/stamp_decode_w.py): per phase, the cycles each group's first wave WORKS between two barriers
@@ -578,8 +629,11 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         if (GEN) {   /* slice 0 is requested whole at the start of the step; every later slice rolls in by quarters, behind    */ \
                      /* the multiply-adds that free its registers (both slices live at once are 64 registers beside the 160   */ \
                      /* of the weights)                                                                                       */ \
-            if (LAYER == 0) skip_issue_b<0>(wsk2, wsl, tg, step0);                                                     \
-            else { SWN_WAIT_STAMP(LAYER > 0 ? LAYER - 1 : 0) skip_roll_b<T, (LAYER > 0 ? LAYER : 1)>(lds, wsk2, wsl, sacc, tg, step0); } \
+                     /* (a resident slice 0 is consumed in L1 from its own registers, a resident slice 5 is not requested in L5) */ \
+            if (LAYER == 0) { if (RES != 0) skip_issue_b<0>(wsk2, wsl, tg, step0); }                                   \
+            else if (LAYER == 1 && RES == 0) skip_roll_b<T, 1>(lds, wsk2, wres, wsl, sacc, tg, step0);                 \
+            else { SWN_WAIT_STAMP(LAYER > 0 ? LAYER - 1 : 0)                                                           \
+                   skip_roll_b<T, (LAYER > 0 ? LAYER : 1), !(LAYER == L - 1 && RES == L - 1)>(lds, wsk2, wsl, wsl, sacc, tg, step0); } \
             __builtin_amdgcn_sched_barrier(0);                                                                         \
         }                                                                                                              \
         if (!(GEN)) older_b<T, LAYER>(lds, wreg[LAYER < NWR ? LAYER : 0], q + 1, tg);                                  \
@@ -609,10 +663,11 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     //      conditioning taps of step q (wj, pb), the parity offset of o_old and layer 0's row are formed one step AHEAD, in the
     //      tail of step q - 1 behind the reads it issues after barrier 7 (taps_ahead; in front of the loop for the first step - a
     //      resumed chunk and a pool entry prime them from their own step0 like the one-shot decode from 0), and the sample and
-    //      heads stores and the loop's induction updates come behind the input layer.  Generation steps advance by one, so the
+    //      heads stores come behind the input layer's write, or one step later behind layer 0's first reads (the rotated loop, below).  Generation steps advance by one, so the
     //      position in the frame is counted (rel_c; cond_taps' clamps never bind behind the prologue).  All of it is group A's:
     //      group B reads none of these values.
-    //      The conditioning refill of a frame crossing stays where it was, at the head of the first step of the new frame fb, as one
+    //      The conditioning refill of a frame crossing stays in the first step of the new frame fb (rotated: behind layer 0's first
+    //      reads, in front of the stores - its wait must not be for them), as one
     //      load - wait - write of group A's threads 0 .. PF / 4 - 1 behind the `fill_c` flag the look-ahead left: the buffer it
     //      fills was last read in layer 5 of the previous step, in front of its barrier 5, and the next reader comes U steps later
     //      (handed to group B and split into a request and a later write it was slower than the parent).
@@ -640,13 +695,46 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
 #ifdef SWN_STAMP
     tlast = tbeg = __builtin_amdgcn_s_memtime();
 #endif
+    // Group A's loop ROTATED by the stores: the sample and the heads of step i wait in two registers (sv_p, acc_p) and are stored
+    // in step i + 1, behind layer 0's LDS reads and in front of their first use - their lane branches and addresses, the refill
+    // test and the noise staging with them -, so that between the input layer's write and those reads stands the loop's branch
+    // alone.  The last step's stores follow the loop.  (ROT false: the parent's loop, stores behind the input layer's write)
+    constexpr bool ROT = SWN_ROTATE && NEWFORM;
+    constexpr int ROTQ = 2;                   // input quads of layer 0 read in front of the stores (layer_a)
+    float sv_p = 0.f, acc_p = 0.f;
+    // (rotated: through buffer resources over the utterance's rows - the step enters as a scalar offset, so the stores bring no
+    //  64-bit address arithmetic into layer 0 and hold no address register beside its operands; without a heads buffer the
+    //  resource is empty and the hardware drops the store)
+    const __amdgpu_buffer_rsrc_t outr =
+        make_rsrc(reinterpret_cast<float*>(a.out) + (size_t)b * a.n_steps, (unsigned)((size_t)a.n_steps * sizeof(float)));
+    const __amdgpu_buffer_rsrc_t headr =
+        make_rsrc(HEADS_ON && a.heads ? a.heads + (size_t)b * a.n_steps * T::NO : nullptr,
+                  HEADS_ON && a.heads ? (unsigned)((size_t)a.n_steps * T::NO * sizeof(float)) : 0u);
+    auto store_step = [&](const int ip) __attribute__((always_inline)) {
+        if constexpr (grpA && ROT) {
+            if (tid == 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sv_p), outr, 0u, (unsigned)ip * 4u, 0);
+            if (wv == 0 && (tg & 63) < T::NO)
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc_p), headr, (unsigned)(tg & 63) * 4u,
+                                                      (unsigned)(ip * T::NO) * 4u, 0);
+        } else if constexpr (grpA) {
+            if (tid == 0) reinterpret_cast<float*>(a.out)[(size_t)b * a.n_steps + (size_t)ip] = sv_p;
+            if (HEADS_ON && a.heads && wv == 0 && (tg & 63) < T::NO) a.heads[((size_t)b * a.n_steps + ip) * T::NO + (tg & 63)] = acc_p;
+        }
+    };
     auto gen_step = [&](const int i) __attribute__((always_inline)) {
         const int q = RF + s0 + i;
         const float wj = wj_c;
         const int pb = pb_c, po = po_c;
-        if constexpr (grpA) {
+        if constexpr (grpA && !ROT) {
             if (fill_c) load_frame(fb + 1);                       // first step of frame fb: refill the buffer the old frame left
         }
+        // the rotated loop: what stood between the input layer's write and layer 0's first read - the stores of the previous
+        // step, the staging of the sampling noise every 64th step, the refill test - goes behind layer 0's reads (layer_a)
+        auto behind0 = [&]() __attribute__((always_inline)) {
+            if ((i & (T::NZC - 1)) == 0) noise_chunk((i >> 6) + 2);
+            if (fill_c) load_frame(fb + 1);
+            if (i > 0) store_step(i - 1);
+        };
         float4 wsl[8];
         float sacc[2] = {0.f, 0.f};
         if constexpr (!grpA) {                                // the out_skip bias enters in lane 0 of each row's quad
@@ -660,7 +748,13 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         // tail + layer 0 the longest phase) and in the out_1 phase (OlderOut1: group A runs out_1 alone; layer 0 needs h0(q), which
         // is not ready before the first barrier); all six beside the out_skip slices made group B take 1 050 cycles per layer phase
         // against group A's 710
-        SWN_PHASE(0, true, x0) SWN_PHASE(1, true, x0) SWN_PHASE(2, true, x0) SWN_PHASE(3, true, x0)
+        if constexpr (grpA && ROT) {
+            layer_a<T, 0, ROTQ>(lds, wreg[0], q, wj, pb, po, tg, x0, behind0);
+            SWN_BAR(0)
+        } else {
+            SWN_PHASE(0, true, x0)
+        }
+        SWN_PHASE(1, true, x0) SWN_PHASE(2, true, x0) SWN_PHASE(3, true, x0)
         SWN_PHASE(4, true, x0)
         // layer 5, and behind group A's hand-off write of it the first half of the operands of the product group A forms in
         // skip-fin (older_last_rows): they ride through barrier 5 in the registers layer 5 has freed.  lpc 0 only: with lpc 4 the
@@ -691,7 +785,8 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         float4 xo[3][4];
         float4 w1e[2][2];
         if constexpr (!grpA) {
-            SWN_WAIT_STAMP(5) skip_last_b<T>(lds, wsl, sacc, tg);
+            if constexpr (RES == L - 1) skip_last_b<T>(lds, wres, sacc, tg);
+            else { SWN_WAIT_STAMP(5) skip_last_b<T>(lds, wsl, sacc, tg); }
             SWN_PRE(6)
             lds_fence_compiler();
             __builtin_amdgcn_sched_barrier(0);
@@ -833,19 +928,30 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             }
             if (i + 1 < a.n_steps) input_gen(x0_c);
             __builtin_amdgcn_sched_barrier(0);                 // the stores stay behind the input layer's write
-            if (tid == 0) reinterpret_cast<float*>(a.out)[(size_t)b * a.n_steps + (size_t)i] = sv;
-            if (HEADS_ON && a.heads && wv == 0 && ln < T::NO) a.heads[((size_t)b * a.n_steps + i) * T::NO + ln] = acc;
+            if constexpr (ROT) { sv_p = sv; acc_p = acc; }
+            else {
+                if (tid == 0) reinterpret_cast<float*>(a.out)[(size_t)b * a.n_steps + (size_t)i] = sv;
+                if (HEADS_ON && a.heads && wv == 0 && ln < T::NO) a.heads[((size_t)b * a.n_steps + i) * T::NO + ln] = acc;
+            }
         }
 #ifdef SWN_STAMP
         if constexpr (grpA) tw[8] += __builtin_amdgcn_s_memtime() - tlast;
 #endif
     };
+    if constexpr (ROT) {
+        // one flat loop (the noise staging of every 64th step sits in layer 0 with the stores), and the last step's stores behind
+        // it - in front of the session copy's barrier
 #pragma unroll 1
-    for (int i0 = 0; i0 < a.n_steps; i0 += T::NZC) {
-        noise_chunk((i0 >> 6) + 2);
-        const int iend = i0 + T::NZC < a.n_steps ? i0 + T::NZC : a.n_steps;
+        for (int i = 0; i < a.n_steps; ++i) gen_step(i);
+        if (a.n_steps > 0) store_step(a.n_steps - 1);
+    } else {
 #pragma unroll 1
-        for (int i = i0; i < iend; ++i) gen_step(i);
+        for (int i0 = 0; i0 < a.n_steps; i0 += T::NZC) {
+            noise_chunk((i0 >> 6) + 2);
+            const int iend = i0 + T::NZC < a.n_steps ? i0 + T::NZC : a.n_steps;
+#pragma unroll 1
+            for (int i = i0; i < iend; ++i) gen_step(i);
+        }
     }
 #ifdef SWN_STAMP
     { const unsigned long long tn = __builtin_amdgcn_s_memtime(); tw[0] += tn - tlast; tstep = tn - tbeg; }
