@@ -14,7 +14,8 @@
 //     through LDS;
 //   * group B (waves 4-7, the other wave of every SIMD) works one step AHEAD and off the chain: the OLDER-tap halves (+ bias) of
 //     layers 0-4 for step t + 1, left in LDS (formed where group B has room: two in the first phase, three beside group A's
-//     out_1; the last layer's is formed by group A, from group B's half in LDS, in the one phase where the chain waits for
+//     out_1 - in the classic lpc 0 kernel three and two; the last layer's is formed by group A, from group B's half in LDS,
+//     in the one phase where the chain waits for
 //     group B - with lpc 0 half of its operands are requested a phase early, in front of barrier 5), and the whole out_skip
 //     accumulation of step t (slice l in the phase after layer l: its four input quads read at the head of the phase, the
 //     next slice's weights requested quarter by quarter behind the multiply-adds that free their registers; in the classic lpc 0
@@ -44,6 +45,22 @@
 #ifndef SWN_ROTATE
 #define SWN_ROTATE 1
 #endif
+// -DSWN_OLDER2_MERGED=0: layer 2's older-tap product stays beside out_1 (the parent's placement); -DSWN_EARLY_ROWS=n: of the two
+// products left beside out_1, n have their operand rows read in front of barrier 6 (built: 1; 2 and 0 measured).
+// -DSWN_HANDOFF=bits: group B takes over from group A 1 the stores, 2 the conditioning refill, 4 the noise staging.  Built: 0 -
+// group A does all three itself, behind layer 0's reads; no subset was faster on the final build.
+// Timing only, samples wrong by construction, never tested or shipped: -DSWN_DIAG_NOSIDE (nobody stores, refills or stages the
+// noise inside the loop), -DSWN_DIAG_NOSIDE_B (with a hand-off: group B's share is left out), -DSWN_DIAG_NOSTREAM (group B
+// requests no out_skip slice in L1 - L5 and consumes what its registers hold)
+#ifndef SWN_HANDOFF
+#define SWN_HANDOFF 0
+#endif
+#ifndef SWN_OLDER2_MERGED
+#define SWN_OLDER2_MERGED 1
+#endif
+#ifndef SWN_EARLY_ROWS
+#define SWN_EARLY_ROWS 1
+#endif
 
 namespace {
 
@@ -58,6 +75,7 @@ struct Tw {
     static constexpr int LPC = LPC_;
     static constexpr bool EXT = EXT_;
     using Ext = Tw<LPC_, true>;
+    static constexpr bool NEWFORM = !EXT_ && LPC_ == 0;   // the classic lpc 0 kernel: resident slice, hand-off ring (decode_body)
     static constexpr int NO = 2 + LPC_;
     static constexpr int WN = cmax(1, LPC_) + 1;
     static constexpr int ring_len(int l) { return pow2ceil((1 << l) + 1); }
@@ -83,7 +101,11 @@ struct Tw {
                                                            // too (192 + the out_skip weights in flight) the kernel spilled 22-35 registers
     static constexpr int o_h0w = o_wl + 8 * NG * 4;        // h0 of the next position as waves 1-3 of group A form it, [3][H] (wave 0's copy
                                                            // is the layer-0 ring slot); past 64 KB: addressed from a per-wave base
-    static constexpr int o_end = o_h0w + 3 * H;
+    // (classic lpc 0 with the hand-off) the NO head sums and the sample of the last NHO steps, [NHO][HO] with the sample at NO:
+    // written by group A's wave 0 one step late, stored to memory by group B 64 steps at a time (decode_body)
+    static constexpr int o_ho = o_h0w + 3 * H;
+    static constexpr int HO = 4, NHO = 128;
+    static constexpr int o_end = o_ho + (NEWFORM && (SWN_HANDOFF & 1) && SWN_ROTATE ? NHO * HO : 0);
     static constexpr size_t lds_bytes = (size_t)o_end * sizeof(float);
     // per-utterance session of a streamed decode: the history rings, the older-tap products group B formed one step ahead
     // (both parities, as LDS holds them), then the sample window
@@ -399,8 +421,15 @@ __device__ __forceinline__ void skip_last_b(float* lds, const float4 (&wsl)[8], 
 
 // group B's five older-tap products of position q + 1 (layer 5's is group A's, in skip-fin): those it forms in the merged phase and
 // those beside group A's out_1 (layer 0's operand is h0(q): not before the step's first barrier)
-using OlderMerged = Layers<3, 4>;
-using OlderOut1 = Layers<0, 1, 2>;
+// (MOVE2, the classic lpc 0 kernel: layer 2's too sits in the merged phase, where group B has 600 cycles of slack - its operand
+//  h_1(q - 3) is three steps old -, and skip-fin, where group B arrives last, requests the rows of two products, not three)
+template <bool MOVE2> using OlderMergedT = typename std::conditional<MOVE2, Layers<2, 3, 4>, Layers<3, 4>>::type;
+template <bool MOVE2> using OlderOut1T = typename std::conditional<MOVE2, Layers<0, 1>, Layers<0, 1, 2>>::type;
+// the products beside out_1 whose rows are read in front of barrier 6 (E of them) and those read behind it
+template <int E> struct Out1Split;
+template <> struct Out1Split<2> { using Early = Layers<0, 1>; using Late = Layers<>; };
+template <> struct Out1Split<1> { using Early = Layers<0>; using Late = Layers<1>; };
+template <> struct Out1Split<0> { using Early = Layers<>; using Late = Layers<0, 1>; };
 
 // The program of one group (GA: group A).  The two groups run the SAME sequence of barriers; they are separate instantiations -
 // not one body with a run-time branch per phase - so that each has its own register allocation: as one body the allocation was the
@@ -553,18 +582,41 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             lds_fence_compiler();
         }
     };
+    // Group A's side work handed to group B (HOFF, diagnostic: not built, see SWN_HANDOFF): the stores of the sample and the heads,
+    // the conditioning refill and the noise staging in group B's merged phase (below, at gen_step)
+#ifdef SWN_DIAG_NOSIDE
+    constexpr bool NOSIDE = T::NEWFORM;
+#else
+    constexpr bool NOSIDE = false;
+#endif
+#ifdef SWN_DIAG_NOSTREAM
+    constexpr bool NOSTREAM = T::NEWFORM;
+#else
+    constexpr bool NOSTREAM = false;
+#endif
+    constexpr bool HOFF = T::NEWFORM && (SWN_HANDOFF & 7) && SWN_ROTATE;
+    constexpr bool HO_ST = HOFF && (SWN_HANDOFF & 1), HO_RF = HOFF && (SWN_HANDOFF & 2), HO_NZ = HOFF && (SWN_HANDOFF & 4);
+    constexpr bool MOVE2 = T::NEWFORM && SWN_OLDER2_MERGED;
+    using OlderMerged = OlderMergedT<MOVE2>;
+    using OlderOut1 = OlderOut1T<MOVE2>;
+    constexpr int NOUT1 = MOVE2 ? 2 : 3;                      // products beside out_1 ...
+    constexpr int NEARLY = MOVE2 ? SWN_EARLY_ROWS : NOUT1;    // ... and how many of them have their rows read in front of barrier 6
+    static_assert(NEARLY >= 0 && NEARLY <= NOUT1, "early rows");
     // sampling noise staged off the chain (swn_decode_bl6.hip): wave 1 transforms tn = sign(e) log1p(-2|e|) of 64 steps at once
     // (lane = step) into a ring of NZB chunks, two chunks ahead of the tail that reads it.  Classic mode: the host-drawn deviate
     // of chunk c + 1 is requested behind the transform of chunk c and stays in a register until then, so the pass - which
     // stands at the head of a step, once per 64 steps - never waits for memory
+    // (HO_NZ: the second wave of group B stages it, in its merged phase)
+    constexpr bool NZG = HO_NZ ? !grpA : grpA;
+    const int tn = HO_NZ ? tg : tid;
     float e_next = 0.f;
     auto noise_load = [&](int c) {
-        const int step = c * T::NZC + tid - 64;
+        const int step = c * T::NZC + tn - 64;
         if (step < a.n_steps) e_next = a.noise[(size_t)b * a.n_steps + step];
     };
     auto noise_chunk = [&](int c) {
-        if (grpA && tid >= 64 && tid < 128) {
-            const int k = tid - 64, step = c * T::NZC + k;
+        if (NZG && tn >= 64 && tn < 128) {
+            const int k = tn - 64, step = c * T::NZC + k;
             if (step < a.n_steps) {
                 const float e = EXT ? swn_noise_laplace_at(a.nz, b, step, s0 + step, 0, a.n_steps, 1) : e_next;
                 const float sg = (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : 0.f);
@@ -573,7 +625,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             if (!EXT) noise_load(c + 1);
         }
     };
-    if (!EXT && grpA && tid >= 64 && tid < 128) noise_load(0);
+    if (!EXT && NZG && tn >= 64 && tn < 128) noise_load(0);
     noise_chunk(0);
     noise_chunk(1);
 
@@ -589,7 +641,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     // (2.530 -> 2.492 us per step).  The extended kernels fit them without a spill and are SLOWER with them - a streamed chunk of
     // 220 steps 2.581 -> 2.603 us per step with the slice, 2.619 with the rotation, 2.643 with both, the one-shot extended decode
     // and the pool tick no faster - so they keep the parent's form; the classic lpc 4 kernel keeps it too.
-    constexpr bool NEWFORM = !EXT && T::LPC == 0;
+    constexpr bool NEWFORM = T::NEWFORM;
     constexpr int RES = (grpA || !NEWFORM) ? -1 : SWN_RES_SLICE;
     static_assert(RES == -1 || RES == 0 || RES == L - 1, "the first or the last slice");
     float4 wres[8];
@@ -631,9 +683,9 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
                      /* of the weights)                                                                                       */ \
                      /* (a resident slice 0 is consumed in L1 from its own registers, a resident slice 5 is not requested in L5) */ \
             if (LAYER == 0) { if (RES != 0) skip_issue_b<0>(wsk2, wsl, tg, step0); }                                   \
-            else if (LAYER == 1 && RES == 0) skip_roll_b<T, 1>(lds, wsk2, wres, wsl, sacc, tg, step0);                 \
+            else if (LAYER == 1 && RES == 0) skip_roll_b<T, 1, !NOSTREAM>(lds, wsk2, wres, wsl, sacc, tg, step0);      \
             else { SWN_WAIT_STAMP(LAYER > 0 ? LAYER - 1 : 0)                                                           \
-                   skip_roll_b<T, (LAYER > 0 ? LAYER : 1), !(LAYER == L - 1 && RES == L - 1)>(lds, wsk2, wsl, wsl, sacc, tg, step0); } \
+                   skip_roll_b<T, (LAYER > 0 ? LAYER : 1), !(LAYER == L - 1 && RES == L - 1) && !NOSTREAM>(lds, wsk2, wsl, wsl, sacc, tg, step0); } \
             __builtin_amdgcn_sched_barrier(0);                                                                         \
         }                                                                                                              \
         if (!(GEN)) older_b<T, LAYER>(lds, wreg[LAYER < NWR ? LAYER : 0], q + 1, tg);                                  \
@@ -721,6 +773,45 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             if (HEADS_ON && a.heads && wv == 0 && (tg & 63) < T::NO) a.heads[((size_t)b * a.n_steps + ip) * T::NO + (tg & 63)] = acc_p;
         }
     };
+    // HOFF - the hand-off (not built: SWN_HANDOFF = 0; measured and dropped): the sample and the NO head sums of
+    // step i wait in sv_p / acc_p as in the rotated loop, and behind
+    // layer 0's first reads of step i + 1 wave 0 of group A writes them to slot i & 127 of the ring o_ho - two LDS writes behind
+    // one scalar branch, nothing else - and goes on.  Group B's first wave stores them 64 steps at a time (lane = step, one
+    // dword of `out` and one dwordx2 of `heads` per lane): chunk c, steps 64 c .. 64 c + 63, in the merged phase of step
+    // 64 c + 65 - its last slot was written in front of barrier 0 of step 64 c + 64, eight barriers earlier, and its half of the
+    // ring is next written in step 64 c + 129.  What is left - at most 65 steps - is stored behind the loop, the last step's
+    // slot write and a barrier.  (A store per step from group B cost 3.6 % of the launch: every wave of group B counts its
+    // weight stream down with vmcnt, a store counts there too, and its acknowledgement takes longer than the two phases to the
+    // next wait - group A's waves wait for no load.  Once per 64 steps that wait is nothing.)
+    // Group B's threads also refill the conditioning (its own rel_c / fb / fill_c, advanced at the end of its step: the buffer
+    // was last read in front of barrier 5 of the previous step, its next reader is U steps away) and its second wave stages
+    // the noise (slot (i / 64 + 2) & 3, read from step 64 (i / 64 + 2) on), all in the merged phase.
+    static_assert(!HOFF || (T::PF / 4 <= NG && T::NO == 2 && T::HO == 4), "one refill request per thread, a slot is {head, head, sample, -}");
+    auto ho_write = [&](const int ip) __attribute__((always_inline)) {
+        if constexpr (grpA) {
+            // (every lane from NO - 1 on holds row NO - 1's sum and writes it to the same word: no lane branch)
+            if (wv == 0) {
+                float* const slot = lds + T::o_ho + (ip & (T::NHO - 1)) * T::HO;
+                slot[(tg & 63) < T::NO ? (tg & 63) : T::NO - 1] = acc_p;
+                slot[T::NO] = sv_p;
+            }
+        }
+    };
+    auto load_frame_b = [&](int fr) {
+        if (tg < T::PF / 4)
+            *reinterpret_cast<float4*>(lds + T::o_gp + (fr & 1) * T::PF + 4 * tg) =
+                buf_ld4(condr, (unsigned)tg * 16u, (unsigned)(fr * a.N * 4));
+    };
+    auto store_chunk_b = [&](const int c) __attribute__((always_inline)) {
+        const int step = c * 64 + tg;
+        if (tg < 64 && step < a.n_steps) {
+            const float4 v = *reinterpret_cast<const float4*>(lds + T::o_ho + (step & (T::NHO - 1)) * T::HO);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v.z), outr, (unsigned)tg * 4u, (unsigned)c * 256u, 0);
+            using u2 = unsigned __attribute__((ext_vector_type(2)));
+            u2 h; h.x = __builtin_bit_cast(unsigned, v.x); h.y = __builtin_bit_cast(unsigned, v.y);
+            __builtin_amdgcn_raw_buffer_store_b64(h, headr, (unsigned)tg * 8u, (unsigned)c * 512u, 0);
+        }
+    };
     auto gen_step = [&](const int i) __attribute__((always_inline)) {
         const int q = RF + s0 + i;
         const float wj = wj_c;
@@ -731,9 +822,11 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         // the rotated loop: what stood between the input layer's write and layer 0's first read - the stores of the previous
         // step, the staging of the sampling noise every 64th step, the refill test - goes behind layer 0's reads (layer_a)
         auto behind0 = [&]() __attribute__((always_inline)) {
-            if ((i & (T::NZC - 1)) == 0) noise_chunk((i >> 6) + 2);
-            if (fill_c) load_frame(fb + 1);
-            if (i > 0) store_step(i - 1);
+            if constexpr (NOSIDE) return;
+            if constexpr (!HO_NZ) { if ((i & (T::NZC - 1)) == 0) noise_chunk((i >> 6) + 2); }
+            if constexpr (!HO_RF) { if (fill_c) load_frame(fb + 1); }
+            if constexpr (HO_ST) { if (i > 0) ho_write(i - 1); }
+            else { if (i > 0) store_step(i - 1); }
         };
         float4 wsl[8];
         float sacc[2] = {0.f, 0.f};
@@ -748,6 +841,22 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         // tail + layer 0 the longest phase) and in the out_1 phase (OlderOut1: group A runs out_1 alone; layer 0 needs h0(q), which
         // is not ready before the first barrier); all six beside the out_skip slices made group B take 1 050 cycles per layer phase
         // against group A's 710
+#ifdef SWN_DIAG_NOSIDE_B
+        constexpr bool SIDE_B = false;
+#else
+        constexpr bool SIDE_B = HOFF && !grpA && !NOSIDE;
+#endif
+        if constexpr (SIDE_B) {
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (HO_NZ) { if ((i & (T::NZC - 1)) == 0) noise_chunk((i >> 6) + 2); }
+            if constexpr (HO_RF) { if (fill_c) load_frame_b(fb + 1); }   // (in front of the stores: its wait must not be for them)
+            if constexpr (HO_ST) { if ((i & 63) == 1 && i > 1) store_chunk_b((i >> 6) - 1); }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (NOSTREAM && !grpA) {                        // (opaque contents: the multiply-adds stay)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) asm volatile("" : "=v"(wsl[k].x), "=v"(wsl[k].y), "=v"(wsl[k].z), "=v"(wsl[k].w));
+        }
         if constexpr (grpA && ROT) {
             layer_a<T, 0, ROTQ>(lds, wreg[0], q, wj, pb, po, tg, x0, behind0);
             SWN_BAR(0)
@@ -782,7 +891,10 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         // registers for it: 4 - 16 spilled): the out_1 weights of input blocks 0 and 1, both rows, in the working registers the product
         // has freed - o_w1 is written once, in front of the step loop.
         constexpr bool ROLL1 = T::LPC == 0;
-        float4 xo[3][4];
+        // (MOVE2: two products are left here; of those, Out1Split's Early have their rows requested in front of barrier 6 and the
+        //  Late ones behind it, where group B's out_1 phase has over 300 cycles to expose them in)
+        using Split = Out1Split<MOVE2 ? NEARLY : 2>;
+        float4 xo[cmax(NEARLY, 1)][4];
         float4 w1e[2][2];
         if constexpr (!grpA) {
             if constexpr (RES == L - 1) skip_last_b<T>(lds, wres, sacc, tg);
@@ -790,9 +902,17 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             SWN_PRE(6)
             lds_fence_compiler();
             __builtin_amdgcn_sched_barrier(0);
-            older_rows_n<T>(OlderOut1{}, lds, q + 1, tg, xo);
-            __builtin_amdgcn_sched_barrier(0);
-            SWN_BAR_KEEP(6, 12)
+            if constexpr (!MOVE2) {
+                older_rows_n<T>(OlderOut1{}, lds, q + 1, tg, xo);
+                __builtin_amdgcn_sched_barrier(0);
+                SWN_BAR_KEEP(6, 12)
+            } else if constexpr (NEARLY > 0) {
+                older_rows_n<T>(typename Split::Early{}, lds, q + 1, tg, xo);
+                __builtin_amdgcn_sched_barrier(0);
+                SWN_BAR_KEEP(6, 4 * NEARLY)
+            } else {
+                SWN_BAR_KEEP(6, 0)
+            }
         } else {
             if constexpr (EARLY5) older_last_x<T>(lds, xl, wl, q + 1, tg + (int)step0);
             else older_b<T, L - 1, 2>(lds, wreg[L - 1], q + 1, tg + (int)step0);   // (opaque zero: no address of it stays resident)
@@ -877,8 +997,11 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
                     if ((tg & 63) < 4 && k < T::NO) lds[T::o_p2 + 4 * k + wv] = pz;
                 }
             }
-        } else {
+        } else if constexpr (!MOVE2) {
             older_bn_x<T>(OlderOut1{}, lds, wreg, xo, q + 1, tg);
+        } else {
+            if constexpr (NEARLY > 0) older_bn_x<T>(typename Split::Early{}, lds, wreg, xo, q + 1, tg);
+            if constexpr (NEARLY < NOUT1) older_bn<T>(typename Split::Late{}, lds, wreg, q + 1, tg);
         }
         SWN_BAR(7)
         if constexpr (grpA) {
@@ -934,6 +1057,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
                 if (HEADS_ON && a.heads && wv == 0 && ln < T::NO) a.heads[((size_t)b * a.n_steps + i) * T::NO + ln] = acc;
             }
         }
+        if constexpr (HO_RF && !grpA) frame_advance();          // group B's own counters, for its refill test of step i + 1
 #ifdef SWN_STAMP
         if constexpr (grpA) tw[8] += __builtin_amdgcn_s_memtime() - tlast;
 #endif
@@ -943,7 +1067,14 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         // it - in front of the session copy's barrier
 #pragma unroll 1
         for (int i = 0; i < a.n_steps; ++i) gen_step(i);
-        if (a.n_steps > 0) store_step(a.n_steps - 1);
+        if constexpr (HO_ST) {
+            // the chunks the loop has not stored (it stored chunk c in step 64 c + 65)
+            if constexpr (grpA) { if (a.n_steps > 0) ho_write(a.n_steps - 1); }
+            lds_barrier();
+            if constexpr (!grpA) {
+                for (int c = a.n_steps >= 66 ? ((a.n_steps - 66) >> 6) + 1 : 0; c * 64 < a.n_steps; ++c) store_chunk_b(c);
+            }
+        } else if (a.n_steps > 0) store_step(a.n_steps - 1);
     } else {
 #pragma unroll 1
         for (int i0 = 0; i0 < a.n_steps; i0 += T::NZC) {
