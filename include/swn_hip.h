@@ -386,6 +386,39 @@ int    swn_decode_pool_chunk_models_w8(const swn_net_desc* d, const float* const
                                        void* stream);
 int    swn_e4m3_table(float* out_dev /*256*/, float scale, void* stream);
 
+/* ---- wide decode pool launch: up to 256 sessions per launch, the entry table on the device ----------------------------------
+ * swn_decode_pool_chunk and its forms carry their table in the 4 KB of kernel arguments, hence 64 entries.  The wide call takes
+ * up to SWN_DECODE_POOL_WIDE_MAX_ENTRIES (one workgroup per CU of an MI355X): it writes the table into table_dev - small setup
+ * launches of 64 rows each, from their own kernel arguments - and the decode launch reads row blockIdx.x from there (scalar
+ * loads).  Every row also holds the entry's packed buffer and image, so ONE entry point serves one model (n_models = 1) and
+ * several, fp32 and stored weights; it is the whole wide surface.  Every session's rows and slot are BIT-IDENTICAL to those of
+ * the 64-entry calls (the same kernels' bodies run the same batch-1 chunk), whatever shares its launch.
+ *   arguments     those of swn_decode_pool_chunk_models, with its layouts (io arrays indexed by entry 0 .. n_entries - 1), then
+ *   images_host   weight_format SWN_WEIGHTS_FP32: not read, may be NULL; else n_models device pointers in a host array, the
+ *                 images of swn_pack_decode_w16 (SWN_WEIGHTS_BF16) / swn_pack_decode_w8 (SWN_WEIGHTS_E4M3) of models_host[m]
+ *   table_dev     swn_decode_pool_wide_table_bytes(n_entries) bytes of device memory (0 for n_entries outside the range), 16-byte
+ *                 aligned, owned by the call until its launches have run: it is written and read on `stream`, so a buffer
+ *                 that is reused must be reused on that stream (or after an event).  Its content is private to the library.
+ * Like the 64-entry calls the call neither synchronises nor copies on the host.  Checked before anything is launched, in this
+ * order: the rules of swn_decode_pool_chunk with n_entries in [1, SWN_DECODE_POOL_WIDE_MAX_ENTRIES] - a slot in two entries is
+ * SWN_E_BADARG wherever they sit; the model rules of swn_decode_pool_chunk_models with n_models in [1,
+ * SWN_DECODE_POOL_WIDE_MAX_ENTRIES] (no table of 16 bounds them: the rows carry the pointers); an unknown weight_format, a NULL
+ * table_dev or, for a stored format, a NULL images_host / images_host[m] is SWN_E_BADARG; then SWN_E_UNSUPPORTED as the
+ * 64-entry calls refuse: the stepped chain for fp32 (swn_decode_pool_stepped_chunk serves it, 64 entries per call), and for a
+ * stored format the refusals of swn_decode_pool_chunk_w16 / _w8, in their words.
+ * What a wide tick still does per 64: the pool front end, the log-mel pool, the low cut, the resampler and the post-filter. */
+#define SWN_DECODE_POOL_WIDE_MAX_ENTRIES 256
+#define SWN_WEIGHTS_FP32 0
+#define SWN_WEIGHTS_BF16 1
+#define SWN_WEIGHTS_E4M3 2
+size_t swn_decode_pool_wide_table_bytes(int n_entries);
+int    swn_decode_pool_chunk_wide(const swn_net_desc* d, const float* const* models_host, int n_models,
+                                  const int32_t* model_of_entry_host, int capacity,
+                                  const swn_decode_pool_entry* entries_host, int n_entries,
+                                  const swn_decode_io* io, float* session_dev,
+                                  void* out_dev, float* heads_dev, int variant, const void* const* images_host,
+                                  int weight_format, void* table_dev, void* stream);
+
 /* ---- stepped decode pool: the decode pool of the stepped multi-launch decode (variant 3: REF6-class nets) -----------
  * Every launch of the stepped chain (input layer, L gated layers, skip / out_1 [/ out_2] mat-vecs, tail) serves all
  * entries of the table, each at its own iteration, so a tick costs about what one utterance's chunk costs while up to 64

@@ -92,6 +92,8 @@ class ResampleEntry(ctypes.Structure):
 
 ABI_VERSION = 3
 DECODE_POOL_MAX_ENTRIES = 64                   # SWN_DECODE_POOL_MAX_ENTRIES (include/swn_hip.h): entries per pool launch
+DECODE_POOL_WIDE_MAX_ENTRIES = 256             # SWN_DECODE_POOL_WIDE_MAX_ENTRIES: entries per wide launch (swn_decode_pool_chunk_wide)
+WEIGHTS_FP32, WEIGHTS_BF16, WEIGHTS_E4M3 = 0, 1, 2   # SWN_WEIGHTS_*: the weight_format of swn_decode_pool_chunk_wide
 DECODE_STEPPED_POOL_TABLE_FLOATS = 512          # SWN_DECODE_STEPPED_POOL_TABLE_FLOATS (include/swn_hip.h)
 DECODE_STEPPED_POOL_MODELS_TABLE_FLOATS = 640   # SWN_DECODE_STEPPED_POOL_MODELS_TABLE_FLOATS (include/swn_hip.h)
 DECODE_STEPPED_POOL_MAX_TILES = 23             # SWN_DECODE_STEPPED_POOL_MAX_TILES (include/swn_hip.h)
@@ -161,6 +163,10 @@ SIGNATURES = {
     "swn_decode_pool_chunk_models": (c_int, [POINTER(NetDesc), POINTER(c_void_p), c_int, POINTER(c_int32), c_int,
                                              POINTER(DecodePoolEntry), c_int, POINTER(DecodeIO), c_void_p, c_void_p, c_void_p,
                                              c_int, c_void_p]),
+    "swn_decode_pool_wide_table_bytes": (c_size_t, [c_int]),
+    "swn_decode_pool_chunk_wide": (c_int, [POINTER(NetDesc), POINTER(c_void_p), c_int, POINTER(c_int32), c_int,
+                                           POINTER(DecodePoolEntry), c_int, POINTER(DecodeIO), c_void_p, c_void_p, c_void_p,
+                                           c_int, POINTER(c_void_p), c_int, c_void_p, c_void_p]),
     "swn_e4m3_table": (c_int, [c_void_p, c_float, c_void_p]),
     "swn_decode_stepped_prologue_iterations": (c_int, [POINTER(NetDesc)]),
     "swn_decode_pool_stepped_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_int, POINTER(DecodeSteppedPoolEntry), c_int,

@@ -108,13 +108,21 @@ struct DecPoolModelsArgs : DecPoolArgs {
     SwnPoolModels m;
 };
 static_assert(sizeof(DecPoolModelsArgs) <= 4096, "kernel arguments are limited to 4 KB");
-template <bool POOL, bool MODELS> struct GenericArgs { using type = DecArgs; };
-template <> struct GenericArgs<true, false> { using type = DecPoolArgs; };
-template <> struct GenericArgs<true, true> { using type = DecPoolModelsArgs; };
+// ... and of a wide pool launch (swn_decode_pool_chunk_wide): the table lies in device memory
+struct DecPoolWideArgs {
+    DecArgs c;
+    const SwnPoolWideRow* rows;
+};
+template <bool POOL, bool MODELS, bool WIDE = false> struct GenericArgs { using type = DecArgs; };
+template <> struct GenericArgs<true, false, false> { using type = DecPoolArgs; };
+template <> struct GenericArgs<true, true, false> { using type = DecPoolModelsArgs; };
+template <> struct GenericArgs<true, false, true> { using type = DecPoolWideArgs; };
 __device__ __forceinline__ const DecArgs& pool_or_launch(const DecArgs& launch, const DecArgs&) { return launch; }
 __device__ __forceinline__ const DecArgs& pool_or_launch(const DecPoolArgs&, const DecArgs& entry) { return entry; }
+__device__ __forceinline__ const DecArgs& pool_or_launch(const DecPoolWideArgs&, const DecArgs& entry) { return entry; }
 __device__ __forceinline__ const DecArgs& launch_args(const DecArgs& launch) { return launch; }
 __device__ __forceinline__ const DecArgs& launch_args(const DecPoolArgs& launch) { return launch.c; }
+__device__ __forceinline__ const DecArgs& launch_args(const DecPoolWideArgs& launch) { return launch.c; }
 
 // STREAM: a chunk of a streamed decode (swn_decode_chunk): steps [step0, step0 + n_steps) with absolute positions and
 // generator counters, chunk-local out / heads / noise / forced rows; the rings stay in the session (a.state) and the sample
@@ -124,11 +132,22 @@ __device__ __forceinline__ const DecArgs& launch_args(const DecPoolArgs& launch)
 // session buffer belong to other streams).
 // MODELS (with POOL): the entry's weights are those of its model (SwnPoolModels); an instantiation of its own, so that the
 // single-model pool kernel stays the code it was.
-template <int SEGT, int KIND, bool STREAM = false, bool POOL = false, bool MODELS = false>
-__global__ __launch_bounds__(NT) void decode_generic_kernel(const typename GenericArgs<POOL, MODELS>::type ka) {
+// WIDE (with POOL, without MODELS): the entry, its model's packed buffer included, is row blockIdx.x of the launch's device table
+// (swn_decode_pool_chunk_wide); again an instantiation of its own.
+template <int SEGT, int KIND, bool STREAM = false, bool POOL = false, bool MODELS = false, bool WIDE = false>
+__global__ __launch_bounds__(NT) void decode_generic_kernel(const typename GenericArgs<POOL, MODELS, WIDE>::type ka) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     DecArgs pa;                                             // POOL: this workgroup's entry as a batch-1 chunk
-    if constexpr (POOL) {
+    if constexpr (WIDE) {
+        static_assert(POOL && !MODELS, "a wide launch is a pool launch whose rows name the models");
+        pa = ka.c;
+        const SwnPoolWideRow row = swn_pool_wide_row(ka.rows);
+        pa.packed = row.model;
+        const SwnGeom& g = ka.c.g;
+        if (!swn_pool_entry_args(pa, row.e, g.seg, KIND == SWN_KIND_SOFTMAX ? g.Q : g.seg, g.NO)) return;
+        pa.state += (size_t)row.e.slot * pa.state_stride;
+        pa.win += (size_t)row.e.slot * swn_round4((g.K - 1 > g.lpc ? g.K - 1 : g.lpc) + g.seg);
+    } else if constexpr (POOL) {
         static_assert(POOL || !MODELS, "only pools take a model table");
         pa = ka.c;
         if constexpr (MODELS) pa.packed = swn_pool_model(ka.m);
@@ -371,17 +390,21 @@ size_t generic_lds(const SwnGeom& g) {
 }
 
 // one workgroup per utterance / pool entry
-template <int SEGT, bool STREAM, bool POOL, bool MODELS>
-int launch_generic(const typename GenericArgs<POOL, MODELS>::type& a, const SwnDecodeCall& c, size_t lds, const char* where) {
-    const auto kern = c.g.kind == SWN_KIND_LAPLACE ? &decode_generic_kernel<SEGT, SWN_KIND_LAPLACE, STREAM, POOL, MODELS>
-                                                   : &decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX, STREAM, POOL, MODELS>;
+template <int SEGT, bool STREAM, bool POOL, bool MODELS, bool WIDE = false>
+int launch_generic(const typename GenericArgs<POOL, MODELS, WIDE>::type& a, const SwnDecodeCall& c, size_t lds, const char* where) {
+    const auto kern = c.g.kind == SWN_KIND_LAPLACE ? &decode_generic_kernel<SEGT, SWN_KIND_LAPLACE, STREAM, POOL, MODELS, WIDE>
+                                                   : &decode_generic_kernel<SEGT, SWN_KIND_SOFTMAX, STREAM, POOL, MODELS, WIDE>;
     hipLaunchKernelGGL(kern, dim3(c.batch), dim3(NT), lds, c.hip_stream, a);
     return swn_launch_status(where);
 }
 
-// the instantiation of a call: one-shot, streamed chunk, pool, pool over several models
+// the instantiation of a call: one-shot, streamed chunk, pool, pool over several models, wide pool
 template <int SEGT>
 int launch_generic_call(const DecPoolModelsArgs& p, const SwnDecodeCall& c, size_t lds) {
+    if (c.wide) {
+        const DecPoolWideArgs w = {p.c, c.wide};
+        return launch_generic<SEGT, true, true, false, true>(w, c, lds, "swn_decode_pool_chunk_wide(generic)");
+    }
     if (c.models) return launch_generic<SEGT, true, true, true>(p, c, lds, "swn_decode_pool_chunk_models(generic)");
     if (c.pool) return launch_generic<SEGT, true, true, false>(p, c, lds, "swn_decode_pool_chunk(generic)");
     if (c.stream) return launch_generic<SEGT, true, false, false>(p.c, c, lds, "swn_decode(generic)");
@@ -404,7 +427,7 @@ int generic_run(const SwnDecodeCall& c) {
     a.win = c.stream ? c.state + (size_t)a.state_stride * c.capacity : nullptr;
     if (c.pool) p.t = *c.pool;
     if (c.models) p.m = *c.models;
-    if (!c.pool && !c.resume &&
+    if (!c.pool && !c.wide && !c.resume &&
         hipMemsetAsync(a.state, 0, sizeof(float) * (size_t)a.state_stride * a.B, c.hip_stream) != hipSuccess)
         return SWN_E_LAUNCH;
     switch (generic_segt(c.g)) {
@@ -512,16 +535,17 @@ bool chunk_is_idle(const SwnDecodeCall& c) { return c.n_steps == 0 && c.resume; 
 
 // swn_decode_pool_chunk, swn_decode_pool_chunk_models, swn_decode_pool_chunk_w16 / _w8: the record of a streamed chunk over the
 // entries (n_steps = the most steps of an entry), the checked table in `t`; work = an entry has steps to run or begins
-int pool_check(SwnDecodeCall& c, SwnPoolTable& t, bool& work, const swn_net_desc* d, int capacity,
+// (the wide call, swn_decode_pool_chunk_wide, keeps the caller's entries instead of a table: t null, max_entries its own limit)
+int pool_check(SwnDecodeCall& c, SwnPoolTable* t, bool& work, const swn_net_desc* d, int capacity,
                const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io, float* session, void* out,
-               float* heads, void* stream_) {
+               float* heads, void* stream_, int max_entries = SWN_DECODE_POOL_MAX_ENTRIES) {
     const int rc = swn_make_geom(d, &c.g);
     if (rc < 0) return rc;
     const SwnGeom& g = c.g;
     if (!entries || !io || !session) return SWN_E_BADARG;
-    if (capacity < 1 || n_entries < 1 || n_entries > SWN_DECODE_POOL_MAX_ENTRIES) return SWN_E_BADARG;
+    if (capacity < 1 || n_entries < 1 || n_entries > max_entries) return SWN_E_BADARG;
     if (io->noise_dev || io->forced_dev) return SWN_E_BADARG;    // pools draw their noise on the device, no teacher forcing
-    t = {};
+    if (t) *t = {};
     int n_max = 0;
     work = false;
     for (int e = 0; e < n_entries; ++e) {
@@ -534,12 +558,12 @@ int pool_check(SwnDecodeCall& c, SwnPoolTable& t, bool& work, const swn_net_desc
         if (((long long)en.step0 + en.n_steps) * g.seg > (long long)en.n_frames * g.U) return SWN_E_BADARG;
         for (int f = 0; f < e; ++f)
             if (entries[f].slot == en.slot) return SWN_E_BADARG;   // two workgroups on one session
-        t.e[e] = en;
+        if (t) t->e[e] = en;
         n_max = en.n_steps > n_max ? en.n_steps : n_max;
         work = work || begin || en.n_steps > 0;
     }
     if (n_max > 0 && !out) return SWN_E_BADARG;
-    c.pool = &t; c.batch = n_entries; c.capacity = capacity; c.n_steps = n_max; c.stream = true;
+    c.pool = t; c.batch = n_entries; c.capacity = capacity; c.n_steps = n_max; c.stream = true;
     c.nz = swn_pool_noise_of(io); c.seed = io->seed_dev;
     c.state = session; c.out = out; c.heads = heads; c.hip_stream = (hipStream_t)stream_;
     return SWN_OK;
@@ -615,7 +639,7 @@ extern "C" int swn_decode_pool_chunk(const swn_net_desc* d, const float* packed,
     SwnDecodeCall c;
     SwnPoolTable t;
     bool work;
-    const int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    const int rc = pool_check(c, &t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
     if (rc < 0) return rc;
     if (!packed) return SWN_E_BADARG;
     const int k = pool_kernel(c.g, capacity, variant);
@@ -633,7 +657,7 @@ extern "C" int swn_decode_pool_chunk_models(const swn_net_desc* d, const float* 
     SwnDecodeCall c;
     SwnPoolTable t;
     bool work;
-    const int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    const int rc = pool_check(c, &t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
     if (rc < 0) return rc;
     if (swn_pool_models_check(models, n_models, model_of_entry, n_entries) < 0) return SWN_E_BADARG;
     const int k = pool_kernel(c.g, capacity, variant);
@@ -684,7 +708,7 @@ int pool_image(int wk, const void* image, const char* where, const swn_net_desc*
     SwnDecodeCall c;
     SwnPoolTable t;
     bool work;
-    int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    int rc = pool_check(c, &t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
     if (rc < 0) return rc;
     if (!packed || !image) return SWN_E_BADARG;
     rc = image_kernel_check(wk, c.g, capacity, variant, where);
@@ -702,7 +726,7 @@ int pool_models_image(int wk, const void* const* images_host, const char* where,
     SwnDecodeCall c;
     SwnPoolTable t;
     bool work;
-    int rc = pool_check(c, t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
+    int rc = pool_check(c, &t, work, d, capacity, entries, n_entries, io, session, out, heads, stream_);
     if (rc < 0) return rc;
     if (swn_pool_models_check(models, n_models, model_of_entry, n_entries) < 0) return SWN_E_BADARG;
     if (!images_host) return SWN_E_BADARG;
@@ -784,4 +808,75 @@ extern "C" int swn_decode_pool_chunk_w8(const swn_net_desc* d, const float* pack
                                         void* stream_) {
     return pool_image(WK_E4M3, w8, "swn_decode_pool_chunk_w8", d, packed, capacity, entries, n_entries, io, session, out, heads,
                       variant, stream_);
+}
+
+// ---- wide pool launch: the entry table in device memory (swn_pool.hpp) -----------------------------------------------------
+namespace {
+
+static_assert(WK_F32 == SWN_WEIGHTS_FP32 && WK_BF16 == SWN_WEIGHTS_BF16 && WK_E4M3 == SWN_WEIGHTS_E4M3, "one code per format");
+
+// the rows one setup launch brings in its kernel arguments
+struct PoolWideSetupArgs {
+    SwnPoolWideRow r[SWN_POOL_WIDE_SETUP_ROWS];
+};
+static_assert(sizeof(PoolWideSetupArgs) + 16 <= 4096, "kernel arguments are limited to 4 KB");
+
+// block k writes row k of its launch, one dword per lane (vector stores), to the device table the decode launch reads
+__global__ __launch_bounds__(64) void pool_wide_setup_kernel(const PoolWideSetupArgs a, SwnPoolWideRow* tab, int n_rows) {
+    const int k = blockIdx.x, tid = threadIdx.x;
+    if (k < n_rows && tid < (int)(sizeof(SwnPoolWideRow) / 4))
+        reinterpret_cast<int*>(tab + k)[tid] = reinterpret_cast<const int*>(&a.r[k])[tid];
+}
+
+}  // namespace
+
+extern "C" size_t swn_decode_pool_wide_table_bytes(int n_entries) {
+    if (n_entries < 1 || n_entries > SWN_DECODE_POOL_WIDE_MAX_ENTRIES) return 0;
+    return (size_t)n_entries * sizeof(SwnPoolWideRow);
+}
+
+extern "C" int swn_decode_pool_chunk_wide(const swn_net_desc* d, const float* const* models, int n_models,
+                                          const int32_t* model_of_entry, int capacity,
+                                          const swn_decode_pool_entry* entries, int n_entries, const swn_decode_io* io,
+                                          float* session, void* out, float* heads, int variant,
+                                          const void* const* images_host, int weight_format, void* table_dev, void* stream_) {
+    SwnDecodeCall c;
+    bool work;
+    int rc = pool_check(c, nullptr, work, d, capacity, entries, n_entries, io, session, out, heads, stream_,
+                        SWN_DECODE_POOL_WIDE_MAX_ENTRIES);
+    if (rc < 0) return rc;
+    if (swn_pool_models_check(models, n_models, model_of_entry, n_entries, SWN_DECODE_POOL_WIDE_MAX_ENTRIES) < 0) return SWN_E_BADARG;
+    if (weight_format != SWN_WEIGHTS_FP32 && weight_format != SWN_WEIGHTS_BF16 && weight_format != SWN_WEIGHTS_E4M3)
+        return SWN_E_BADARG;
+    if (!table_dev || (reinterpret_cast<uintptr_t>(table_dev) & 15)) return SWN_E_BADARG;
+    int k = KSEL_BL6;
+    if (weight_format == SWN_WEIGHTS_FP32) {
+        k = pool_kernel(c.g, capacity, variant);
+        if (k < 0) return k;
+    } else {
+        if (!images_host) return SWN_E_BADARG;
+        for (int m = 0; m < n_models; ++m)
+            if (!images_host[m]) return SWN_E_BADARG;
+        rc = image_kernel_check(weight_format, c.g, capacity, variant, "swn_decode_pool_chunk_wide");
+        if (rc < 0) return rc;
+    }
+    if (!work) return SWN_OK;                              // every slot stays as it is
+    // the table: row e = entry e, its model's packed buffer and image; SWN_POOL_WIDE_SETUP_ROWS rows per setup launch
+    SwnPoolWideRow* rows = static_cast<SwnPoolWideRow*>(table_dev);
+    (void)hipGetLastError();
+    for (int e0 = 0; e0 < n_entries; e0 += SWN_POOL_WIDE_SETUP_ROWS) {
+        const int n = n_entries - e0 < SWN_POOL_WIDE_SETUP_ROWS ? n_entries - e0 : SWN_POOL_WIDE_SETUP_ROWS;
+        PoolWideSetupArgs a = {};
+        for (int e = 0; e < n; ++e) {
+            const int m = model_of_entry[e0 + e];
+            a.r[e].e = entries[e0 + e];
+            a.r[e].model = models[m];
+            a.r[e].image = weight_format == SWN_WEIGHTS_FP32 ? nullptr : images_host[m];
+        }
+        hipLaunchKernelGGL(pool_wide_setup_kernel, dim3(n), dim3(64), 0, c.hip_stream, a, rows + e0, n);
+        rc = swn_launch_status("swn_decode_pool_chunk_wide(setup)");
+        if (rc < 0) return rc;
+    }
+    c.wide = rows; c.wk = weight_format;
+    return run_call(k, c);
 }

@@ -412,6 +412,10 @@ template <int WK> struct B6ArgsOf<true, false, WK> { using type = Bl6PoolImageAr
 template <int WK> struct B6ArgsOf<true, true, WK> { using type = Bl6PoolModelsImageArgs; };
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6Args& launch, const Bl6Args&) { return launch; }
 __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, const Bl6Args& entry) { return entry; }
+__device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolWideArgs&, const Bl6Args& entry) { return entry; }
+// (a wide launch has one argument struct for every format: its rows carry the images)
+template <bool POOL, bool MODELS, int WK, bool WIDE>
+using B6KernelArgs = typename std::conditional<WIDE, Bl6PoolWideArgs, typename B6ArgsOf<POOL, MODELS, WK>::type>::type;
 
 // EXT = false: the classic instantiation (host-drawn noise stream, zero seed) - the code the round-1 measurements
 // belong to, kept instruction for instruction; EXT = true adds the in-kernel generator / noise dump / seed waveform.
@@ -425,8 +429,10 @@ __device__ __forceinline__ const Bl6Args& pool_or_launch(const Bl6PoolArgs&, con
 // WK = WK_E4M3 (W8): the same over the FP8 image `img`, whose row scales are copied into LDS behind the carve.  `img` is the
 // launch's image ka.img, or with MODELS the image of the entry's model, ka.img[model] - read through the model index once, so
 // the one-time loads (resident out_1 slices, W8 codes and row scales) and the three streams all take the entry's own image.
-template <class T, bool STREAM = false, bool POOL = false, bool MODELS = false, int WK = WK_F32>
-__global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<POOL, MODELS, WK>::type ka) {
+// WIDE (with POOL, without MODELS): the entry, its model's packed buffer and its image are row blockIdx.x of the launch's device
+// table (swn_decode_pool_chunk_wide), whatever the format.
+template <class T, bool STREAM = false, bool POOL = false, bool MODELS = false, int WK = WK_F32, bool WIDE = false>
+__global__ __launch_bounds__(NT) void decode_bl6_kernel(const B6KernelArgs<POOL, MODELS, WK, WIDE> ka) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr bool W16 = WK == WK_BF16, W8 = WK == WK_E4M3;
     static_assert(WK == WK_F32 || T::EXT, "stored formats: extended instantiations only");
@@ -435,10 +441,18 @@ __global__ __launch_bounds__(NT) void decode_bl6_kernel(const typename B6ArgsOf<
     // stored formats: the image every section below is read from (one model: the launch's, read where it is used)
     [[maybe_unused]] auto img = [&]() -> const void* {
         if constexpr (WK == WK_F32) return nullptr;
-        else if constexpr (MODELS) return img_e;
+        else if constexpr (MODELS || WIDE) return img_e;
         else return ka.img;
     };
-    if constexpr (POOL) {
+    if constexpr (WIDE) {
+        static_assert(POOL && !MODELS && STREAM && T::EXT, "a wide launch is a pool launch whose rows name the models");
+        pa = ka.c;
+        const SwnPoolWideRow row = swn_pool_wide_row(ka.rows);
+        pa.P = row.model;
+        img_e = row.image;
+        if (!swn_pool_entry_args(pa, row.e, T::SEG, T::KIND == SWN_KIND_SOFTMAX ? T::Q : T::SEG, T::NO)) return;
+        pa.sess += (size_t)row.e.slot * T::sess_floats;
+    } else if constexpr (POOL) {
         static_assert(STREAM && T::EXT, "pools run the streamed extended mode");
         pa = ka.c;
         if constexpr (MODELS && WK != WK_F32) {            // the entry's model names its packed buffer and its image
@@ -1096,6 +1110,20 @@ int launch_pool(const SwnDecodeCall& c, const char* where) {
     });
 }
 
+// ... and one wide pool launch over the call's device table (swn_decode_pool_chunk_wide)
+template <int WK>
+int launch_pool_wide(const SwnDecodeCall& c) {
+    Bl6PoolWideArgs p;
+    fill_args(p.c, c);
+    p.rows = c.wide;
+    return with_tr(c.g, [&](auto tr) {
+        using T = typename decltype(tr)::Ext;
+        constexpr size_t lds = WK == WK_E4M3 ? w8_lds_bytes<T>() : T::lds_bytes;
+        return launch_kernel(decode_bl6_kernel<T, true, true, false, WK, true>, lds, c.batch, p, c.hip_stream,
+                             "swn_decode_pool_chunk_wide(bl6)");
+    });
+}
+
 // bytes of the image of format `wk` for net `d`; 0: the symmetric kernel does not serve the net
 size_t image_bytes(const swn_net_desc* d, int wk) {
     SwnGeom g;
@@ -1200,6 +1228,11 @@ extern "C" int swn_e4m3_table(float* out, float scale, void* stream_) {
 
 // a checked call on the symmetric kernel (swn_decode.hip)
 int swn_decode_bl6_run(const SwnDecodeCall& c) {
+    if (c.wide) switch (c.wk) {
+        case WK_E4M3: return launch_pool_wide<WK_E4M3>(c);
+        case WK_BF16: return launch_pool_wide<WK_BF16>(c);
+        default: return launch_pool_wide<WK_F32>(c);
+    }
     if (c.pool) switch (c.wk) {
         case WK_E4M3: return c.models ? launch_pool<true, WK_E4M3>(c, "swn_decode_pool_chunk_models_w8(bl6)")
                                       : launch_pool<false, WK_E4M3>(c, "swn_decode_pool_chunk_w8(bl6)");

@@ -64,6 +64,12 @@ struct Bl6PoolModelsImageArgs : Bl6PoolModelsArgs {
     const void* img[SWN_POOL_MAX_MODELS];
 };
 static_assert(sizeof(Bl6PoolModelsImageArgs) <= 4096, "kernel arguments are limited to 4 KB");
+// ... and of a wide pool launch (swn_decode_pool_chunk_wide): the table lies in device memory, and its rows carry each entry's
+// packed buffer and image - one struct for every weight format, taken by instantiations of their own (WIDE)
+struct Bl6PoolWideArgs {
+    Bl6Args c;
+    const SwnPoolWideRow* rows;
+};
 // The bf16 image (swn_pack_decode_w16): the three lane-tiled copies wsk2 / w12 / w22 of the packed buffer rounded to bf16 (nearest
 // even), slices 2g and 2g + 1 of 16 inputs folded into one: section [NS / 2][rows][4 lanes][4 words], word j of a lane =
 // bf16(slice 2g, input 4 lane + j) in bits 0-15 | bf16(slice 2g + 1, input 4 lane + j) in bits 16-31.  A lane's 16-byte load

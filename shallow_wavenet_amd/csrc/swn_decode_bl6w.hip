@@ -1136,6 +1136,20 @@ __global__ __launch_bounds__(NT) void decode_bl6w_pool_kernel(
     else decode_body<T, false, true, true>(a, lds);
 }
 
+// ... of a wide launch (swn_decode_pool_chunk_wide): the entry and its model's packed buffer are row blockIdx.x of the device table
+template <class T>
+__global__ __launch_bounds__(NT) void decode_bl6w_pool_wide_kernel(const Bl6PoolWideArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    static_assert(T::EXT, "pools run the extended mode");
+    Bl6Args a = p.c;
+    const SwnPoolWideRow row = swn_pool_wide_row(p.rows);
+    a.P = row.model;
+    if (!swn_pool_entry_args(a, row.e, 1, 1, T::NO)) return;
+    a.sess += (size_t)row.e.slot * T::sess_floats;
+    if (threadIdx.x < NG) decode_body<T, true, true, true>(a, lds);   // wave-uniform
+    else decode_body<T, false, true, true>(a, lds);
+}
+
 bool bl6w_applies(const SwnGeom& g) {
     return g.bl6 && g.U <= 256 && g.U >= 2 && !g.audio_in && g.kind == SWN_KIND_LAPLACE && g.S == 128 && g.O1 == 128 &&
            g.seg == 1 && (g.lpc == 0 || g.lpc == 4);
@@ -1156,6 +1170,15 @@ int with_tw(const SwnGeom& g, F&& f) {
 // per entry, sessions [capacity][sess_floats]), a streamed chunk (`sess` holds sess_floats per utterance) or the one-shot decode
 int swn_decode_bl6w_run(const SwnDecodeCall& c) {
     const hipStream_t st = c.hip_stream;
+    if (c.wide) {
+        Bl6PoolWideArgs p;
+        fill_args(p.c, c);
+        p.rows = c.wide;
+        return with_tw(c.g, [&](auto tw) {
+            using T = typename decltype(tw)::Ext;
+            return launch_kernel(decode_bl6w_pool_wide_kernel<T>, T::lds_bytes, c.batch, p, st, "swn_decode_pool_chunk_wide(bl6w)");
+        });
+    }
     if (c.pool) {
         Bl6PoolModelsArgs p;
         fill_args(p.c, c);

@@ -31,11 +31,13 @@ enum : int { WK_F32 = 0, WK_BF16 = 1, WK_E4M3 = 2 };
 struct SwnDecodeCall {
     SwnGeom g;                                 // made once, by the check
     const float* packed = nullptr;             // (not read when `models` is set)
-    int wk = WK_F32;                           // how the streamed head matrices are stored (WK_*) ...
+    int wk = WK_F32;                           // how the streamed head matrices are stored (WK_*: SWN_WEIGHTS_* of the ABI) ...
     const void* image = nullptr;               // ... and their image in that format (swn_pack_decode_w16 / _w8); fp32, `models`: null
     const SwnPoolModels* models = nullptr;     // a pool over several models; null: one model
     const void* const* images = nullptr;       // ... and, over a stored format, their images: SWN_POOL_MAX_MODELS of them, as models->p
     const SwnPoolTable* pool = nullptr;        // the checked entry table of a pool launch; null: not a pool
+    const SwnPoolWideRow* wide = nullptr;      // a wide pool launch: its device table, written by the call's setup launches
+                                               // (then pool, models, image and images are null: the rows carry them)
     const float* cond = nullptr;               // (pool: every entry has its own)
     int batch = 0;                             // utterances; pool: entries
     int capacity = 0;                          // utterances `state` holds: batch; pool: the slots of the session buffer

@@ -152,7 +152,7 @@ class EngineMixin:
                             prologue=prologue, weights=resolve_decode_weights(self) if weights is None else weights)
 
     def open_pool(self, capacity: int, variant: int = 0, post_filter=None, multi_model: bool = False,
-                  prologue: str = "stepped", weights: Optional[str] = None):
+                  prologue: str = "stepped", weights: Optional[str] = None, launch_width: int = 64):
         """a decode pool of `capacity` session slots on the module's current engine (shallow_wavenet_amd.streaming.DecodePool):
         independent utterances open, receive features and end at their own pace, and one launch per tick advances all of
         them.  The noise key follows open_stream: `noise_rng_seed` when the caller pinned one, else one fresh key per pool.
@@ -164,7 +164,8 @@ class EngineMixin:
         and with weights="bf16" | "e4m3" the pool is a DecodeModelPool (several models over stored weights in one launch).
         prologue: "stepped" | "parallel", as SteppedDecodePool takes it; "parallel" on a net of another decode is a
         ValueError.  weights: "fp32" | "bf16" | "e4m3" as DecodePool takes it (one model unless multi_model; not on the
-        stepped pools); None = the module's `decode_weights`."""
+        stepped pools); None = the module's `decode_weights`.  launch_width: sessions per decode launch, 1 .. 256, as
+        DecodePool takes it (above 64: the wide launch; a ValueError on the stepped pools)."""
         from .. import _lib, noise as _noise, ops as _ops
         from ..streaming import DecodeModelPool, DecodePool, SteppedDecodePool, SteppedModelPool, _check_prologue
         key = getattr(self, "noise_rng_seed", None)
@@ -173,10 +174,12 @@ class EngineMixin:
         weights = resolve_decode_weights(self) if weights is None else weights
         if _lib.lib().swn_decode_resolve_variant(_ops._desc(net.dlist), capacity, int(variant)) == 3:
             cls = SteppedModelPool if multi_model else SteppedDecodePool
-            return cls(net, capacity, rng_seed=rng_seed, post_filter=post_filter, prologue=prologue, weights=weights)
+            return cls(net, capacity, rng_seed=rng_seed, post_filter=post_filter, prologue=prologue, weights=weights,
+                       launch_width=launch_width)
         _check_prologue(prologue, False)
         cls = DecodeModelPool if multi_model and weights != "fp32" else DecodePool
-        return cls(net, capacity, variant=variant, rng_seed=rng_seed, post_filter=post_filter, weights=weights)
+        return cls(net, capacity, variant=variant, rng_seed=rng_seed, post_filter=post_filter, weights=weights,
+                   launch_width=launch_width)
 
     def set_packed_engine(self, net: HipNet) -> None:
         """install an engine whose packed buffer arrived by RCCL broadcast (dist.py)."""

@@ -31,6 +31,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.decode_pool_chunk_models_<sfx>(models, images, model_of, session, ...decode_pool_chunk_models')
                                                                    -> (out, heads, noise_used)   (images[m]: the image of models[m])
     torch.ops.swn.e4m3_table(like, scale)                          -> (256,) fp32: the kernels' conversion of codes 0 .. 255
+    torch.ops.swn.decode_pool_chunk_wide(models, images, weights, model_of, session, ...decode_pool_chunk_models')
+                                                                   -> (out, heads, noise_used)   (up to 256 entries per launch)
     torch.ops.swn.decode_pool_stepped_chunk(packed, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids, desc,
                                             capacity, rng_seed, want_heads, want_noise)  -> (out, heads, noise_used)
     torch.ops.swn.decode_pool_stepped_chunk_models(models, model_of, session, conds, slots, it0s, n_its, begins, seeds?, utt_ids,
@@ -263,11 +265,12 @@ def _(packed, auxs, conds, staged, n_news, n_receiveds, f0s, f1s, finals, desc):
     return None
 
 
-def _model_tables(L, d, models: List[torch.Tensor], model_of: List[int], E: int, what: str):
+def _model_tables(L, d, models: List[torch.Tensor], model_of: List[int], E: int, what: str,
+                  max_models: int = _lib.POOL_MAX_MODELS):
     """the checked model arguments of a *_models call -> (device, HOST array of the models' device pointers, int32 array of
     the entries' model indices).  Every model buffer is fp32, contiguous, on one HIP device and swn_packed_floats long."""
-    if not 1 <= len(models) <= _lib.POOL_MAX_MODELS:
-        raise RuntimeError(f"{what}: {len(models)} models, a call takes 1 .. {_lib.POOL_MAX_MODELS}")
+    if not 1 <= len(models) <= max_models:
+        raise RuntimeError(f"{what}: {len(models)} models, a call takes 1 .. {max_models}")
     _need_cuda(models[0], "the packed parameters")
     dev = models[0].device
     total = L.swn_packed_floats(ctypes.byref(d))
@@ -529,17 +532,19 @@ def _decode_pool_chunk_call(fmt, image, packed, session, conds, slots, step0s, n
 
 
 def _decode_pool_call(call, d, dev, lead, trail, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, capacity,
-                      variant, rng_seed, want_heads, want_noise):
-    """one pool launch through the library's `call` (decode_pool_chunk and its image / *_models forms): checks the entries and
-    builds their table, the io block and the outputs.  `lead` are the call's arguments between the descriptor and the
-    capacity (the packed parameters, or the model tables), `trail` those between the variant and the stream (the image)"""
+                      variant, rng_seed, want_heads, want_noise, max_entries: int = _lib.DECODE_POOL_MAX_ENTRIES,
+                      what: str = "decode_pool_chunk"):
+    """one pool launch through the library's `call` (decode_pool_chunk and its image / *_models / wide forms): checks the
+    entries and builds their table, the io block and the outputs.  `lead` are the call's arguments between the descriptor and
+    the capacity (the packed parameters, or the model tables), `trail` those between the variant and the stream (the image; the
+    wide call: images, format and table buffer), max_entries the call's limit, `what` the op's name in error texts"""
     L = _lib.lib()
     soft, seg, _, _, n_out, _ = _geom(d)
     E = len(conds)
     if not (len(slots) == len(step0s) == len(n_steps) == len(begins) == len(utt_ids) == E):
-        raise RuntimeError("decode_pool_chunk: conds, slots, step0s, n_steps, begins and utt_ids must have one entry each")
-    if not 1 <= E <= _lib.DECODE_POOL_MAX_ENTRIES:
-        raise RuntimeError(f"decode_pool_chunk: {E} entries, a launch takes 1 .. {_lib.DECODE_POOL_MAX_ENTRIES}")
+        raise RuntimeError(f"{what}: conds, slots, step0s, n_steps, begins and utt_ids must have one entry each")
+    if not 1 <= E <= max_entries:
+        raise RuntimeError(f"{what}: {E} entries, a launch takes 1 .. {max_entries}")
     width = d.n_quantize if soft else seg
     if session.device != dev or session.dtype != torch.float32 or not session.is_contiguous():
         raise RuntimeError("session must be a contiguous fp32 tensor on the device of the packed parameters")
@@ -627,6 +632,60 @@ decode_pool_chunk_models = custom_op("swn::decode_pool_chunk_models",
 def _decode_pool_chunk_models_op_fake(models, model_of, session, conds, slots, step0s, n_steps, begins, seeds, utt_ids, desc,
                                       capacity, variant, rng_seed, want_heads, want_noise):
     return _decode_pool_fake(models[0], conds, n_steps, desc, want_heads, want_noise)
+
+
+# ------------------------------------------------------------------------------------------ wide decode pool launch
+_WIDE_FORMATS = {"fp32": _lib.WEIGHTS_FP32, "bf16": _lib.WEIGHTS_BF16, "e4m3": _lib.WEIGHTS_E4M3}
+
+
+def decode_pool_chunk_wide_impl(models: List[torch.Tensor], images: List[torch.Tensor], weights: str, model_of: List[int],
+                                session: torch.Tensor, conds: List[torch.Tensor], slots: List[int], step0s: List[int],
+                                n_steps: List[int], begins: List[bool], seeds: Optional[torch.Tensor], utt_ids: List[int],
+                                desc: List[int], capacity: int, variant: int, rng_seed: int, want_heads: bool,
+                                want_noise: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """one WIDE launch of a decode pool (swn_decode_pool_chunk_wide): up to 256 entries, their table in a device buffer this op
+    allocates per call (as it does out and heads, so the caching allocator's stream rules keep it alive for the launches).
+    Entry e runs with models[model_of[e]] - one model or any number up to the entries' - and, for weights "bf16" | "e4m3",
+    images[model_of[e]] (the images of pack_decode_w16 / _w8, one per model; weights "fp32": images is empty).  Everything
+    else, and every entry's rows bit for bit, as decode_pool_chunk / decode_pool_chunk_models and their stored forms."""
+    d = _desc(desc)
+    L = _lib.lib()
+    E = len(conds)
+    if weights not in _WIDE_FORMATS:
+        raise RuntimeError(f"decode_pool_chunk_wide: weights must be one of {sorted(_WIDE_FORMATS)}, not {weights!r}")
+    dev, ptrs, of = _model_tables(L, d, models, model_of, E, "decode_pool_chunk_wide", _lib.DECODE_POOL_WIDE_MAX_ENTRIES)
+    imgs = None
+    if weights != "fp32":
+        if len(images) != len(models):
+            raise RuntimeError(f"decode_pool_chunk_wide: {len(images)} images for {len(models)} models")
+        fmt = DECODE_IMAGES[weights]
+        imgs = (ctypes.c_void_p * len(models))(*[_check_image(fmt, im, t, d).data_ptr() for im, t in zip(images, models)])
+    elif len(images) != 0:
+        raise RuntimeError("decode_pool_chunk_wide: fp32 weights take no images")
+    table = torch.empty(max(1, L.swn_decode_pool_wide_table_bytes(E)), dtype=torch.uint8, device=dev)
+    return _decode_pool_call(L.swn_decode_pool_chunk_wide, d, dev, (ptrs, len(models), of),
+                             (imgs, _WIDE_FORMATS[weights], _ptr(table)), session, conds, slots, step0s, n_steps, begins, seeds,
+                             utt_ids, capacity, variant, rng_seed, want_heads, want_noise, _lib.DECODE_POOL_WIDE_MAX_ENTRIES,
+                             "decode_pool_chunk_wide")
+
+
+decode_pool_chunk_wide = custom_op("swn::decode_pool_chunk_wide", mutates_args=("session",))(decode_pool_chunk_wide_impl)
+
+
+@decode_pool_chunk_wide.register_fake
+def _decode_pool_chunk_wide_op_fake(models, images, weights, model_of, session, conds, slots, step0s, n_steps, begins, seeds,
+                                    utt_ids, desc, capacity, variant, rng_seed, want_heads, want_noise):
+    return _decode_pool_fake(models[0], conds, n_steps, desc, want_heads, want_noise)
+
+
+def decode_wide_lead(nets, weights: str):
+    """the leading arguments of decode_pool_chunk_wide for the models `nets` with weights stored as `weights`: their packed
+    parameters, their images of the format (none for fp32) - both read now, so a repacked net brings its new ones - and the
+    format's name"""
+    if weights == "fp32":
+        return [n.packed for n in nets], [], weights
+    suffix = DECODE_IMAGES[weights].suffix
+    return [n.packed for n in nets], [getattr(n, f"decode_{suffix}_image")() for n in nets], weights
 
 
 # ------------------------------------------------------------------------------------------ decode over a stored format
@@ -1791,6 +1850,7 @@ OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk"
             "pack_decode_w16", "decode_w16", "decode_chunk_w16", "decode_pool_chunk_w16",
             "pack_decode_w8", "decode_w8", "decode_chunk_w8", "decode_pool_chunk_w8", "e4m3_table",
             "frontend_pool_models", "decode_pool_chunk_models", "decode_pool_chunk_models_w16", "decode_pool_chunk_models_w8",
+            "decode_pool_chunk_wide",
             "decode_pool_stepped_chunk_models", "decode_stepped_prologue",
             "postfilter_chunk",
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",

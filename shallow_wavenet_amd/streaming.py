@@ -24,6 +24,11 @@ The nets people fine-tune per speaker (REF6) decode on the stepped chain: their 
 (swn_decode_pool_stepped_chunk_models), whose launch chain serves the sessions of all models of a call at once - the table is
 grouped by model, so a tile of eight sessions fetches ONE model's weight rows.  SteppedDecodePool stays the one-model pool.
 
+Width.  A decode launch of the calls above takes 64 sessions (its table travels in the kernel arguments).  launch_width > 64
+on DecodePool / DecodeModelPool makes a tick issue the wide launch instead (swn_decode_pool_chunk_wide: up to 256 sessions, the
+table in device memory, every row naming its model and image - so no cut at 16 models), the same bits per session.  push_many,
+the post-filter and the stepped pools keep 64.
+
 Steps.  A generation step i reads cond frames up to ((i + 1) * seg - 1) // U, so with F final frames the steps
 [0, F * U // seg) can run (the bound of swn_decode).  Step counts come from frame counts on the host: nothing here
 waits for the device.
@@ -63,6 +68,19 @@ def _check_weights(weights, cfg: NetConfig, batch: int, variant: int) -> str:
     (net, batch, variant) resolves to the symmetric BL6 kernel)"""
     from .runtime import check_decode_weights
     return check_decode_weights(weights, cfg, batch, variant)
+
+
+def _check_launch_width(launch_width, stepped: bool) -> int:
+    """the launch_width keyword of the pools: sessions per decode launch, 1 .. 256; above 64 the tick issues the wide launch
+    (swn_decode_pool_chunk_wide), which the stepped chain does not have"""
+    if not isinstance(launch_width, int) or isinstance(launch_width, bool) or \
+            not 1 <= launch_width <= _lib.DECODE_POOL_WIDE_MAX_ENTRIES:
+        raise ValueError(f"launch_width must be an integer in 1 .. {_lib.DECODE_POOL_WIDE_MAX_ENTRIES}, not {launch_width!r}")
+    if stepped and launch_width > _lib.DECODE_POOL_MAX_ENTRIES:
+        raise ValueError(f"launch_width={launch_width}: the stepped decode pools take at most {_lib.DECODE_POOL_MAX_ENTRIES} "
+                         "sessions per call - every launch of the chain tiles its sessions by a plan made for 64 entries, and "
+                         "the wide launch (one workgroup per session) has no stepped form")
+    return launch_width
 
 
 def lookahead_frames(cfg: NetConfig) -> int:
@@ -437,6 +455,11 @@ class DecodePool:
                E4M3 (swn_decode_pool_chunk_w8), each session bit-identical to its solo DecodeStream of that mode.  Symmetric BL6
                kernel only (variant=6 for the single-sample Laplace nets); such a DecodePool serves one model (add_model raises:
                DecodeModelPool is the pool of several models over stored weights) and no stepped pool has the modes
+    launch_width   sessions per decode launch, 1 .. 256 (default 64).  Up to 64 a tick issues swn_decode_pool_chunk and its
+               forms, whose entry table travels in the kernel arguments.  Above 64 it issues the wide launch
+               (swn_decode_pool_chunk_wide: the table in device memory, one workgroup per session, every session's bits
+               unchanged) once per launch_width sessions, for any number of models.  The batched features, the post-filter
+               and the log-mel pool keep their groups of 64
 
         k = pool.add_model(other_net)           # another net of the same NetConfig (the pool's own net is model 0)
         s = pool.open(seed=None, utt_id=None, model=0)   # a free slot; utt_id defaults to the admission counter
@@ -449,9 +472,10 @@ class DecodePool:
     _stored_models = False        # add_model on a pool of stored weights: DecodeModelPool's
 
     def __init__(self, net, capacity: int, *, variant: int = 0, rng_seed: int = 0, want_heads: bool = False,
-                 want_noise: bool = False, post_filter=None, weights: str = "fp32"):
+                 want_noise: bool = False, post_filter=None, weights: str = "fp32", launch_width: int = 64):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
+        self.launch_width = _check_launch_width(launch_width, False)
         self.net, self.cfg, self.capacity = net, net.cfg, capacity
         self.weights = _check_weights(weights, net.cfg, capacity, variant)
         self.soft = self.cfg.kind == "softmax"
@@ -521,12 +545,13 @@ class DecodePool:
 
     def step(self, max_steps: Optional[int] = None) -> dict:
         """one tick: every open session with ready steps advances by min(ready, max_steps) of them, in launches of at most
-        64 sessions.  Returns {session: (out, heads) or (out, heads, noise)} for the sessions that ran - out laplace
+        launch_width sessions.  Returns {session: (out, heads) or (out, heads, noise)} for the sessions that ran - out laplace
         (1, n * seg) fp32 | softmax (1, n) int32, heads (1, n, n_out) or None, noise (1, n, width) - views of the dense
         launch outputs.  Nothing here waits for the device."""
-        launches = plan_tick([(s, s.steps_ready, s.steps_done) for s in self._open.values()], max_steps)
+        launches = plan_tick([(s, s.steps_ready, s.steps_done) for s in self._open.values()], max_steps, self.launch_width)
+        wide = self.launch_width > _lib.DECODE_POOL_MAX_ENTRIES   # the rows of a wide launch name each entry's model themselves
         several = len(self._models) > 1             # a pool of one model pays nothing for the others
-        if several:
+        if several and not wide:
             launches = split_models(launches, lambda s: s.model)
         results = {}
         for entries in launches:
@@ -540,7 +565,10 @@ class DecodePool:
             args = (self._session, [s._stream._cond[0] for s in sess], [s.slot for s in sess],
                     [e[1] for e in entries], [e[2] for e in entries], begins, seeds, [s.utt_id for s in sess],
                     self.net.dlist, self.capacity, self.variant, self.rng_seed, self.want_heads, self.want_noise)
-            if len(models) == 1:
+            if wide:
+                lead = _ops.decode_wide_lead([self._models[m] for m in models], self.weights)
+                out, heads, used = _O.decode_pool_chunk_wide(*lead, of if several else [0] * len(sess), *args)
+            elif len(models) == 1:
                 op, lead = _ops.decode_lead(self._models[models[0]], "decode_pool_chunk", self.weights)
                 out, heads, used = getattr(_O, op)(*lead, *args)
             else:                                   # (stored weights: a DecodeModelPool - one image per model of the call)
@@ -737,9 +765,11 @@ class SteppedDecodePool(DecodePool):
     and max_prologue has nothing left to spread; same bits as the default "stepped"."""
 
     def __init__(self, net, capacity: int, *, rng_seed: int = 0, want_heads: bool = False, want_noise: bool = False,
-                 post_filter=None, prologue: str = "stepped", weights: str = "fp32"):
+                 post_filter=None, prologue: str = "stepped", weights: str = "fp32", launch_width: int = 64):
         if not isinstance(capacity, int) or capacity < 1:
             raise ValueError(f"capacity must be a positive integer, not {capacity!r}")
+        _check_launch_width(launch_width, True)     # (validated only: the stepped pools keep their calls of 64)
+        self.launch_width = _lib.DECODE_POOL_MAX_ENTRIES
         from .runtime import DECODE_WEIGHTS
         if weights not in DECODE_WEIGHTS:
             raise ValueError(f"weights must be one of {DECODE_WEIGHTS}, not {weights!r}")
