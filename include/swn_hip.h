@@ -583,6 +583,25 @@ int    swn_forward_bf16(const swn_net_desc* d, const float* packed_dev, const vo
                         const float* cond_dev, const void* audio_dev, int batch, int n_frames,
                         void* work_dev, float* out_dev, void* stream);
 
+/* Which kernels swn_forward_bf16 runs for a call of this geometry and size (host only, nothing is launched): one of
+ * SWN_BF16_PATH_*, or the negative SWN_E_* code with which swn_forward_bf16 refuses the call given non-null pointers.
+ * swn_forward_bf16 switches on this same value.  BL6 class, in this order (U the upsampling factor, frames = batch *
+ * n_frames):
+ *   FUSED          seg 1, 33 <= U <= 112, six layers, frames <= 3072: bf16_stack_fused_kernel, all gated layers in one launch
+ *   UNITS4_HALVES  seg 1, 65 <= U <= 112, frames < 2048: half-frame units; FUSED takes all of these except in diagnostic
+ *                  builds (SWN_OLD_UNITS), which have no FUSED
+ *   UNITS4 / UNITS5 / UNITS7   seg 1, 16 <= U <= 64 / 65 <= U <= 80 / 81 <= U <= 112: bf16_layer_units_kernel<4 / 5 / 7>
+ *   LAYER0         seg > 1, U < 16 or U > 112: bf16_layer_kernel<0>
+ * GEMM_STACK: the other geometry class (swn_stack_bf16g.hip). */
+#define SWN_BF16_PATH_FUSED         0
+#define SWN_BF16_PATH_UNITS4        1
+#define SWN_BF16_PATH_UNITS4_HALVES 2
+#define SWN_BF16_PATH_UNITS5        3
+#define SWN_BF16_PATH_UNITS7        4
+#define SWN_BF16_PATH_LAYER0        5
+#define SWN_BF16_PATH_GEMM_STACK    6
+int    swn_forward_bf16_path(const swn_net_desc* d, int batch, int n_frames);
+
 /* mixed-precision training: expand what swn_forward_bf16 kept in work_dev (bf16, time-major) into the fp32 work layout
  * of swn_forward (hidden states | relu(skip) | relu(out_1); swn_forward_work_floats() floats), so that swn_backward can
  * follow a bf16 forward of the same (cond, audio).  GEMM-stack class: all three are expanded from memory.  BL6 class:

@@ -102,6 +102,8 @@ POOL_MAX_MODELS = 16                           # SWN_POOL_MAX_MODELS (include/sw
 FRONTEND_FINAL = 1                             # SWN_FRONTEND_FINAL: the entry's features end at n_received
 CHUNK_BEGIN = 1                                # SWN_CHUNK_BEGIN (include/swn_hip.h): first chunk of a streamed decode
 PRECISION_FP32, PRECISION_BF16 = 0, 1          # SWN_PRECISION_* (include/swn_hip.h)
+# SWN_BF16_PATH_* (include/swn_hip.h): what swn_forward_bf16_path returns, by value
+BF16_PATHS = ("fused", "units4", "units4_halves", "units5", "units7", "layer0", "gemm_stack")
 POSTFILTER_IN_F32, POSTFILTER_IN_MULAW = 0, 1   # SWN_POSTFILTER_IN_* (include/swn_hip.h)
 POSTFILTER_RESET = 1                           # SWN_POSTFILTER_RESET
 POSTFILTER_MAX_ORDER = 62                      # SWN_POSTFILTER_MAX_ORDER
@@ -191,6 +193,7 @@ SIGNATURES = {
     "swn_forward_bf16_work_bytes": (c_size_t, [POINTER(NetDesc), c_int, c_int]),
     "swn_forward_bf16": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p]),
+    "swn_forward_bf16_path": (c_int, [POINTER(NetDesc), c_int, c_int]),
     "swn_backward_work_floats": (c_size_t, [POINTER(NetDesc), c_int, c_int]),
     "swn_backward": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),

@@ -1125,21 +1125,50 @@ extern "C" size_t swn_forward_bf16_work_bytes(const swn_net_desc* d, int batch, 
     return small ? swn_bf16g_layout(g, batch, Tp).skip : swn_bf16g_layout(g, batch, Tp).total;
 }
 
+// The ONE dispatch decision of swn_forward_bf16: which kernels a call runs (SWN_BF16_PATH_*), or the SWN_E_* code it is
+// refused with, in the order the checks have always had (`null_arg`: one of the call's pointers is null).  The launcher
+// switches on this value and swn_forward_bf16_path reports it, so the two cannot drift apart.
+static int bf16_forward_path(const swn_net_desc* d, int batch, int n_frames, bool null_arg, SwnGeom* g) {
+    const int rc = bf_geom(d, g);
+    const bool gemm = rc == SWN_E_UNSUPPORTED && swn_bf16g_geom(d, g) == SWN_OK;
+    if (rc < 0 && !gemm) return rc;
+    if (null_arg || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
+    const long Tp = swn_train_len(*g, n_frames).Tp;
+    if (Tp < 1) return SWN_E_BADARG;
+    if (gemm) return SWN_BF16_PATH_GEMM_STACK;
+    // 32-bit buffer offsets in the layer kernel: one layer of hidden states and the conditioning must stay < 2 GiB
+    if ((size_t)batch * Tp * H * 2 >= (1ull << 31) || (size_t)batch * n_frames * g->N * 4 >= (1ull << 31)) return SWN_E_UNSUPPORTED;
+    const int nch = (g->U + 15) / 16;                                  // 16-position chunks per conditioning frame
+    if (g->seg != 1 || g->U < 16 || nch > 7) return SWN_BF16_PATH_LAYER0;
+    const int n_units = batch * ((int)((Tp - 1 + g->seg) / g->U) + 1);  // frame units: frames per utterance x batch
+#if !defined(SWN_OLD_UNITS)           // diagnostic builds only: the per-layer launches for A/B timing
+    // all six gated layers in one launch (bf16_stack_fused_kernel): one workgroup per CU walks a contiguous range of frames.
+    // Up to ~12 frames per workgroup (cfg4's own 8 x 150: 4.7) it beats six per-layer launches (4 x 150: 0.091 / 0.104 ms,
+    // 8 x 150: 0.122 / 0.141, 16 x 150: 0.198 / 0.221); from 32 x 150 on the two tie (0.369 / 0.363, 64 x 150: 0.713 / 0.707) and
+    // the per-layer kernels, which need no halo, keep the large sizes
+    if (g->U >= 33 && g->L == FZ_NL && n_units <= 3072) return SWN_BF16_PATH_FUSED;
+#endif
+    // few frames per wave: halve the units (4 + 3 chunks for U = 110) so that the waves finish together.  In the default
+    // build the fused kernel takes every such call (nch > 4 means U >= 65, fewer than 2 048 units are at most 3 072 frames
+    // and a BL6-class net has FZ_NL layers): only SWN_OLD_UNITS builds run this branch
+    if (nch > 4 && n_units < 2 * 1024) return SWN_BF16_PATH_UNITS4_HALVES;
+    return nch <= 4 ? SWN_BF16_PATH_UNITS4 : nch == 5 ? SWN_BF16_PATH_UNITS5 : SWN_BF16_PATH_UNITS7;
+}
+
+extern "C" int swn_forward_bf16_path(const swn_net_desc* d, int batch, int n_frames) {
+    SwnGeom g;
+    return bf16_forward_path(d, batch, n_frames, false, &g);
+}
+
 extern "C" int swn_forward_bf16(const swn_net_desc* d, const float* packed, const void* wbf, const float* cond,
                                 const void* audio_, int batch, int n_frames, void* work, float* out, void* stream_) {
     const float* audio = reinterpret_cast<const float*>(audio_);      // BL6 class: Laplace, float waveform
-    SwnGeom g; int rc = bf_geom(d, &g);
-    if (rc == SWN_E_UNSUPPORTED && swn_bf16g_geom(d, &g) == SWN_OK) {
-        if (!packed || !wbf || !cond || !audio || !work || !out || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
-        if (swn_train_len(g, n_frames).Tp < 1) return SWN_E_BADARG;
+    SwnGeom g;
+    const int path = bf16_forward_path(d, batch, n_frames, !packed || !wbf || !cond || !audio || !work || !out, &g);
+    if (path < 0) return path;
+    if (path == SWN_BF16_PATH_GEMM_STACK)
         return swn_bf16g_forward(g, packed, wbf, cond, audio_, batch, n_frames, work, out, (hipStream_t)stream_);
-    }
-    if (rc < 0) return rc;
-    if (!packed || !wbf || !cond || !audio || !work || !out || batch < 1 || batch > 65535 || n_frames < 1) return SWN_E_BADARG;
     const long Tp = swn_train_len(g, n_frames).Tp;
-    if (Tp < 1) return SWN_E_BADARG;
-    // 32-bit buffer offsets in the layer kernel: one layer of hidden states and the conditioning must stay < 2 GiB
-    if ((size_t)batch * Tp * H * 2 >= (1ull << 31) || (size_t)batch * n_frames * g.N * 4 >= (1ull << 31)) return SWN_E_UNSUPPORTED;
     BfArgs a;
     swn_make_layout(&g, &a.y);
     const BfOffsets o = bf_offsets(g);
@@ -1154,39 +1183,40 @@ extern "C" int swn_forward_bf16(const swn_net_desc* d, const float* packed, cons
     const int n_tiles = batch * (int)((Tp + TN - 1) / TN);
     const int n_chunks = batch * (int)((Tp + 15) / 16);
     const int grid = (n_chunks + 3) / 4 < 256 ? (n_chunks + 3) / 4 : 256;      // persistent: one workgroup (4 waves x 512 VGPRs) per CU
-    const int nch = (g.U + 15) / 16;
-#if !defined(SWN_OLD_UNITS)           // diagnostic builds only: the per-layer launches for A/B timing
-    // all six gated layers in one launch (bf16_stack_fused_kernel): one workgroup per CU walks a contiguous range of frames.
-    // Up to ~12 frames per workgroup (cfg4's own 8 x 150: 4.7) it beats six per-layer launches (4 x 150: 0.091 / 0.104 ms,
-    // 8 x 150: 0.122 / 0.141, 16 x 150: 0.198 / 0.221); from 32 x 150 on the two tie (0.369 / 0.363, 64 x 150: 0.713 / 0.707) and
-    // the per-layer kernels, which need no halo, keep the large sizes
-    if (g.seg == 1 && g.U >= 33 && nch <= 7 && g.L == FZ_NL && batch * ((int)((Tp - 1 + a.coff) / g.U) + 1) <= 3072) {
-        const int Fu = (int)((Tp - 1 + a.coff) / g.U) + 1;           // frames per utterance
-        const int n_fr = batch * Fu;
-        const int ug = n_fr < 256 ? n_fr : 256;
+    const int Fu = (int)((Tp - 1 + a.coff) / g.U) + 1;               // frames (= frame units) per utterance
+    const int n_units = batch * Fu;
+    const int ug = (n_units + 3) / 4 < 256 ? (n_units + 3) / 4 : 256;
+    switch (path) {
+    case SWN_BF16_PATH_FUSED: {
+        const int fg = n_units < 256 ? n_units : 256;
         static bool attr_set = false;
         if (!attr_set) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(bf16_stack_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     FZ_LDS_BYTES) != hipSuccess) return SWN_E_LAUNCH;
             attr_set = true;
         }
-        hipLaunchKernelGGL(bf16_stack_fused_kernel, dim3(ug), dim3(768), FZ_LDS_BYTES, st, a, n_fr, Fu);
-    } else
-#endif
-    if (g.seg == 1 && g.U >= 16 && nch <= 7) {
-        const int Fu = (int)((Tp - 1 + a.coff) / g.U) + 1;           // frame units per utterance
-        const int n_units = batch * Fu;
-        const int ug = (n_units + 3) / 4 < 256 ? (n_units + 3) / 4 : 256;
-        // few frames per wave: halve the units (4 + 3 chunks for U = 110) so that the waves finish together
-        const bool halves = nch > 4 && nch <= 8 && n_units < 2 * 1024;
+        hipLaunchKernelGGL(bf16_stack_fused_kernel, dim3(fg), dim3(768), FZ_LDS_BYTES, st, a, n_units, Fu);
+        break;
+    }
+    case SWN_BF16_PATH_UNITS4_HALVES: {
         const int n_half = 2 * n_units, ugh = (n_half + 3) / 4 < 256 ? (n_half + 3) / 4 : 256;
-        for (int l = 0; l < g.L; ++l) {
-            if (halves) hipLaunchKernelGGL(bf16_layer_units_kernel<4>, dim3(ugh), dim3(256), 0, st, a, l, g.dil[l], n_half, Fu, 2);
-            else if (nch <= 4) hipLaunchKernelGGL(bf16_layer_units_kernel<4>, dim3(ug), dim3(256), 0, st, a, l, g.dil[l], n_units, Fu, 1);
-            else if (nch == 5) hipLaunchKernelGGL(bf16_layer_units_kernel<5>, dim3(ug), dim3(256), 0, st, a, l, g.dil[l], n_units, Fu, 1);
-            else hipLaunchKernelGGL(bf16_layer_units_kernel<7>, dim3(ug), dim3(256), 0, st, a, l, g.dil[l], n_units, Fu, 1);
-        }
-    } else {
+        for (int l = 0; l < g.L; ++l)
+            hipLaunchKernelGGL(bf16_layer_units_kernel<4>, dim3(ugh), dim3(256), 0, st, a, l, g.dil[l], n_half, Fu, 2);
+        break;
+    }
+    case SWN_BF16_PATH_UNITS4:
+        for (int l = 0; l < g.L; ++l)
+            hipLaunchKernelGGL(bf16_layer_units_kernel<4>, dim3(ug), dim3(256), 0, st, a, l, g.dil[l], n_units, Fu, 1);
+        break;
+    case SWN_BF16_PATH_UNITS5:
+        for (int l = 0; l < g.L; ++l)
+            hipLaunchKernelGGL(bf16_layer_units_kernel<5>, dim3(ug), dim3(256), 0, st, a, l, g.dil[l], n_units, Fu, 1);
+        break;
+    case SWN_BF16_PATH_UNITS7:
+        for (int l = 0; l < g.L; ++l)
+            hipLaunchKernelGGL(bf16_layer_units_kernel<7>, dim3(ug), dim3(256), 0, st, a, l, g.dil[l], n_units, Fu, 1);
+        break;
+    default:                                                         // SWN_BF16_PATH_LAYER0
         for (int l = 0; l < g.L; ++l)
             hipLaunchKernelGGL(bf16_layer_kernel<0>, dim3(grid), dim3(256), 0, st, a, l, g.dil[l], n_chunks);
     }

@@ -24,6 +24,7 @@ def test_every_declared_symbol_is_exported_and_bound():
     lib = _lib.lib()
     names = _declared_symbols()
     assert len(names) >= 14
+    assert "swn_forward_bf16_path" in names           # the dispatch decision of swn_forward_bf16, readable from the host
     for n in names:
         assert hasattr(lib, n), n
         assert n in _lib.SIGNATURES, f"{n} declared in the header but not bound in _lib.py"

@@ -10,11 +10,15 @@ in test_gpu_mixed_backward_edges.py.
     `single` case changes side between the two graphs or lies within the case's gap of zero; and margin * D_k + floor_k stays
     below what the old tests allow that tensor (5e-2 ||g|| + 1e-3 of the largest norm, 1e-1 for the softmax nets), so the new
     file cannot be the weaker check anywhere.
+  - the forward yardstick of tests/bf16_forward_ref.py (test_gpu_bf16_forward_paths.py): at the geometries it adds (seg 5 at the
+    BL6 class, U = 15, 113, 240) `rounded` with every rounding off is `exact` bit for bit and the hoisted form agrees to 1e-12;
+    per case D_rms and D_fwd are positive and m_f D_fwd lies below test_gpu_bf16_stack.py's 3e-3 x max(1, |raw| max).
 """
 import numpy as np
 import pytest
 import torch
 
+import bf16_forward_ref as F
 import mixed_ref as M
 from conftest import golden_names, load_golden
 from oracle import cpu_ref
@@ -115,6 +119,48 @@ def test_rounding_switched_off_is_exact(case):
     assert np.abs(raw_h - raw_e).max() <= 1e-12 * max(1.0, np.abs(raw_e).max())
     for k in g_e:
         assert np.linalg.norm((g_h[k] - g_e[k]).ravel()) <= 1e-12 * np.linalg.norm(g_e[k].ravel()) + 1e-300, k
+
+
+FWD_CASES = F.cases()
+
+
+@pytest.mark.parametrize("case", [c for c in FWD_CASES if c.path == "layer0" and c.B <= 3], ids=lambda c: c.name)
+def test_rounding_switched_off_is_exact_at_the_forward_geometries(case):
+    """the geometries bf16_forward_ref.py adds to those of cases(): seg 5 at the BL6 class (five conditioning taps per
+    position in the hoisted form), U = 15, U = 113 and U = 240 (frames shorter than a chunk, longer than seven)"""
+    cfg, sd, aux, audio = F.inputs_of(case)
+    grad_raw = np.random.Generator(np.random.PCG64(5)).standard_normal((case.rows, cfg.n_out, case.Tp)) / case.Tp
+    raw_e, g_e = M.exact(cfg, sd, aux, audio, grad_raw)
+    raw_0, g_0 = M.rounded(cfg, sd, aux, audio, grad_raw, path=None)
+    assert raw_e.shape == (case.rows, cfg.n_out, case.Tp)
+    assert np.array_equal(raw_0, raw_e)
+    for k in g_e:
+        assert np.array_equal(g_0[k], g_e[k]), k
+    raw_h, g_h = M.rounded(cfg, sd, aux, audio, grad_raw, path="hoisted")
+    assert np.abs(raw_h - raw_e).max() <= 1e-12 * max(1.0, np.abs(raw_e).max())
+    for k in g_e:
+        assert np.linalg.norm((g_h[k] - g_e[k]).ravel()) <= 1e-12 * np.linalg.norm(g_e[k].ravel()) + 1e-300, k
+
+
+@pytest.mark.parametrize("case", FWD_CASES + [F.TRAIN_CASE], ids=lambda c: c.name)
+def test_forward_yardstick_of_every_case(case):
+    """D_fwd and D_rms exist, the padded utterance is among the rows, and the new bound lies below what
+    test_gpu_bf16_stack.py allows (3e-3 x max(1, |raw| max)), so the new file cannot be the weaker check anywhere"""
+    y = F.yardstick_of(case)
+    assert y.raw_exact.shape == y.raw_rounded.shape == (case.rows, case.cfg().n_out, case.Tp)
+    assert np.isfinite(y.raw_exact).all() and np.isfinite(y.raw_rounded).all()
+    assert 0.0 < y.D_rms <= y.D_fwd
+    assert F.MARGIN_FWD[case.path] * y.D_fwd < y.old_bound, (case.name, F.MARGIN_FWD[case.path] * y.D_fwd, y.old_bound)
+    aux = F.inputs_of(case)[2]
+    pad = min(F.PAD_ROW, case.rows - 1)
+    assert case.Tf == 1 or (not aux[pad, :, 1:].any() and aux[pad, :, 0].any())
+    assert all(aux[b, :, -1].any() for b in range(case.rows) if b != pad)
+
+
+def test_forward_cases_cover_every_kernel_of_the_dispatch_table():
+    assert {c.path for c in FWD_CASES} == set(F.MARGIN_FWD) == {"fused", "units4", "units5", "units7", "layer0"}
+    assert len({c.name for c in FWD_CASES}) == len(FWD_CASES)
+    assert max(c.B * c.Tp for c in FWD_CASES) <= 350_000
 
 
 def test_margins_cover_every_group():
