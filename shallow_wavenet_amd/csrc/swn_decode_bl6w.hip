@@ -19,7 +19,8 @@
 //     group B - with lpc 0 half of its operands are requested a phase early, in front of barrier 5), and the whole out_skip
 //     accumulation of step t (slice l in the phase after layer l: its four input quads read at the head of the phase, the
 //     next slice's weights requested quarter by quarter behind the multiply-adds that free their registers; in the classic lpc 0
-//     kernel slice 0 does not stream: it stays in 32 registers of group B from the launch's start);
+//     kernel slice 0 does not stream: it stays in 32 registers of group B from the launch's start, the last load of slices 1 - 4
+//     is requested at the head of the next phase, and the input quads of slices 0 - 4 come from the ring rows group A writes);
 //   * group A keeps its halves of all six matrices in registers (192 per thread), group B five of them (160) and the sixth in LDS
 //     (it also holds a slice of out_skip weights in flight); the out_1 matrix is LDS-resident whole (the 64 KB the sixth layer of
 //     the symmetric kernel took), only out_skip streams from L2;
@@ -61,6 +62,28 @@
 #ifndef SWN_EARLY_ROWS
 #define SWN_EARLY_ROWS 1
 #endif
+// The classic lpc 0 kernel, both groups' layer phases started ahead of the barrier:
+// -DSWN_LEAD=n: of the eight loads of out_skip slice l, the last n (0, 1, 2 = a quarter, 4 = a half) are not requested at the end
+// of phase L(l) but at the head of L(l + 1), behind its four LDS reads and in front of its first multiply-add (skip_roll_b);
+// -DSWN_RINGX=0: group A writes every layer's output to o_hcat too and group B reads its slice's inputs there (the parent's form);
+// 1: layers 0 - 4 leave o_hcat alone, group B reads the ring row group A has just written.
+// Built: one load and the ring rows - 412.3 k samples/s of the headline beside the parent's 407.3; a quarter 406.8, a half 376.1,
+// one load without the ring rows and the ring rows without a lead both below the parent.
+// Timing only, never tested or shipped: -DSWN_DIAG_PLAINEXP (layer_a's epilogue on the bare v_exp_f32 / v_rcp_f32)
+#ifndef SWN_LEAD
+#define SWN_LEAD 1
+#endif
+#ifndef SWN_RINGX
+#define SWN_RINGX 1
+#endif
+// (the stamp build hands skip_roll_b the counter of its wait for the loads requested at the head of the phase)
+#ifdef SWN_STAMP
+#define SWN_TDEF_PARAM , unsigned long long& tdef
+#define SWN_TDEF_ARG(k) , td[k]
+#else
+#define SWN_TDEF_PARAM
+#define SWN_TDEF_ARG(k)
+#endif
 
 namespace {
 
@@ -76,6 +99,8 @@ struct Tw {
     static constexpr bool EXT = EXT_;
     using Ext = Tw<LPC_, true>;
     static constexpr bool NEWFORM = !EXT_ && LPC_ == 0;   // the classic lpc 0 kernel: resident slice, hand-off ring (decode_body)
+    static constexpr int LEAD = NEWFORM ? SWN_LEAD : 0;   // loads of a slice requested at the head of the next phase (skip_roll_b)
+    static constexpr bool RINGX = NEWFORM && SWN_RINGX;   // group B's inputs of slices 0 - 4 come from the rings, not from o_hcat
     static constexpr int NO = 2 + LPC_;
     static constexpr int WN = cmax(1, LPC_) + 1;
     static constexpr int ring_len(int l) { return pow2ceil((1 << l) + 1); }
@@ -191,8 +216,13 @@ __device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], con
         // drops it) where the parent passed it on; the gate lane of the same channel still passes its own.
         // (plain v_exp_f32 / v_rcp_f32 without the corrections - nine instructions fewer on the chain - measured the same step
         //  time: the phase waits for both groups, not for this arithmetic)
+#ifdef SWN_DIAG_PLAINEXP
+        const float e = __builtin_amdgcn_exp2f((p == 0 ? -v : -2.f * fminf(fabsf(v), 64.f)) * 1.44269504f);
+        const float r = __builtin_amdgcn_rcpf(1.f + e);
+#else
         const float e = exp_c(p == 0 ? -v : -2.f * fminf(fabsf(v), 64.f));
         const float r = rcp_c(1.f + e);
+#endif
         const float res = p == 0 ? r : copysignf((1.f - e) * r, v);        // z | tanh
         const float c = dpp_f<0xF5>(res);                                  // quad_perm [1,1,3,3]: lane 0 <- lane 1
         if (p == 0) {
@@ -201,7 +231,8 @@ __device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], con
                 constexpr int R2 = T::ring_len(LAYER + 1 < L ? LAYER + 1 : LAYER);
                 lds[T::o_ring + T::ring_off(LAYER + 1 < L ? LAYER + 1 : LAYER) + (q & (R2 - 1)) * H + o] = hn;
             }
-            lds[T::o_hcat + LAYER * H + o] = hn;
+            // (RINGX: group B reads layers 0 - 4 from the ring slot just written; the last layer has no ring)
+            if (!T::RINGX || LAYER + 1 >= L) lds[T::o_hcat + LAYER * H + o] = hn;
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -369,16 +400,50 @@ __device__ __forceinline__ void skip_issue_b(__amdgpu_buffer_rsrc_t wsk2, float4
 // (`wcur`: the registers slice LAYER - 1 is consumed from, `wnext`: those slice LAYER is requested into - the same eight of the
 //  rolling buffer, or, for a slice kept resident across the steps, the resident registers on one side of it: consumed and left
 //  as they are, with the buffer free for the requests.  REQ false: the next slice is resident, nothing is requested)
-template <class T, int LAYER, bool REQ = true>
-__device__ __forceinline__ void skip_roll_b(const float* lds, __amdgpu_buffer_rsrc_t wsk2, const float4 (&wcur)[8], float4 (&wnext)[8],
-                                            float (&sacc)[2], const int tb, const unsigned step0) {
+// The request LEADS across the barrier (the classic lpc 0 kernel, T::LEAD loads): a slice's eight loads are numbered in request
+// order, k = 2 mm + ps.  Phase L(LAYER) leaves the last DEFER of slice LAYER unrequested - their registers, freed by the
+// phase's last multiply-adds, stay empty through the barrier - and requests at its own head, behind the four LDS reads and in
+// front of the first multiply-add, the last HEAD of slice LAYER - 1, which phase L(LAYER - 1) left out: they are consumed last,
+// three quarters of a phase later.  So the vector-memory path has work while the inputs' round trip keeps the multiply-adds
+// waiting, and the end of the phase, in front of the barrier, issues nothing.  HEAD_OWN (L1 beside a resident slice 0: the rolling
+// buffer is empty): the head requests the FIRST HEAD loads of slice LAYER itself.  Every request is issued and consumed inside
+// one step, in the order of k, so vmcnt counts down as before and no prologue, chunk or pool primes anything.
+// q: the position of the step; with T::RINGX the inputs h_{LAYER-1}(q) are read from ring LAYER's slot q & (R - 1), which group
+// A wrote in front of the barrier and rewrites R steps later, not from o_hcat.
+template <class T, int LAYER, bool REQ = true, int HEAD = 0, int DEFER = 0, bool HEAD_OWN = false>
+__device__ __forceinline__ void skip_roll_b(const float* lds, __amdgpu_buffer_rsrc_t wsk2, float4 (&wcur)[8], float4 (&wnext)[8],
+                                            float (&sacc)[2], const int tb, const unsigned step0, const int q SWN_TDEF_PARAM) {
     static_assert(LAYER >= 1 && LAYER < L, "slice LAYER - 1 in flight, slice LAYER to request");
+    static_assert(HEAD >= 0 && HEAD <= 4 && DEFER >= 0 && DEFER <= 4, "at most half a slice leads");
     const int r = tb >> 2, hp = tb & 3;
+    auto request = [&](float4 (&dst)[8], const int slice, const int k) __attribute__((always_inline)) {
+        const int mm = k >> 1, ps = k & 1;
+        dst[ps * 4 + mm] = buf_ld4(wsk2, (unsigned)((r + 64 * ps) * 4 + hp) * 16u, (unsigned)((slice * 4 + mm) * S) * 64u + step0);
+    };
+    constexpr int R = T::ring_len(LAYER);
+    const float* xrow = T::RINGX ? lds + T::o_ring + T::ring_off(LAYER) + (q & (R - 1)) * H : lds + T::o_hcat + (LAYER - 1) * H;
     float4 xs[4];
 #pragma unroll
-    for (int mm = 0; mm < 4; ++mm) xs[mm] = *reinterpret_cast<const float4*>(lds + T::o_hcat + (LAYER - 1) * H + 16 * mm + 4 * hp);
+    for (int mm = 0; mm < 4; ++mm) xs[mm] = *reinterpret_cast<const float4*>(xrow + 16 * mm + 4 * hp);
+    if constexpr (REQ && HEAD > 0) {
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < HEAD; ++k) {
+            if (HEAD_OWN) request(wnext, LAYER, k);
+            else request(wcur, LAYER - 1, 8 - HEAD + k);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int mm = 0; mm < 4; ++mm) {
+#ifdef SWN_STAMP
+        if (!HEAD_OWN && HEAD > 0 && mm == (8 - HEAD) >> 1) {     // the wait for the first load requested at the head
+            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            asm volatile("" :: "v"(wcur[((8 - HEAD) & 1) * 4 + mm].x));
+            tdef += __builtin_amdgcn_s_memtime() - t0;
+        }
+#endif
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) {
             const float4 x = xs[mm], w = wcur[ps * 4 + mm];
@@ -387,8 +452,10 @@ __device__ __forceinline__ void skip_roll_b(const float* lds, __amdgpu_buffer_rs
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
-            if (REQ) wnext[ps * 4 + mm] = buf_ld4(wsk2, (unsigned)((r + 64 * ps) * 4 + hp) * 16u, (unsigned)((LAYER * 4 + mm) * S) * 64u + step0);
+        for (int ps = 0; ps < 2; ++ps) {
+            const int k = 2 * mm + ps;
+            if (REQ && k >= (HEAD_OWN ? HEAD : 0) && k < 8 - DEFER) request(wnext, LAYER, k);
+        }
         __builtin_amdgcn_sched_barrier(0);
     }
     // pin the partial sums to this phase: only the end of the step uses them, and the optimiser otherwise sinks all six slices'
@@ -644,6 +711,9 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     constexpr bool NEWFORM = T::NEWFORM;
     constexpr int RES = (grpA || !NEWFORM) ? -1 : SWN_RES_SLICE;
     static_assert(RES == -1 || RES == 0 || RES == L - 1, "the first or the last slice");
+    // the rolling request leads beside a resident slice 0 only: L1 then finds the rolling buffer empty (skip_roll_b, HEAD_OWN)
+    constexpr int LEADB = RES == 0 ? T::LEAD : 0;
+    static_assert(LEADB == 0 || LEADB == 1 || LEADB == 2 || LEADB == 4, "one load, a quarter or a half of a slice");
     float4 wres[8];
     if constexpr (RES == 0) skip_issue_b<0>(wsk2, wres, tg, 0u);
     if constexpr (RES == L - 1) skip_issue_b<L - 1>(wsk2, wres, tg, 0u);
@@ -654,7 +724,9 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     // 0), [8] the tail's share of phase 0, [9] A's whole step, [10..18) group B, [20..26) of group B's phases L1 .. L5 and
     // skip-fin the cycles from the barrier's release until the first out_skip weight register of the slice in flight has landed,
     // [30..39) group A's wave 1 as [0..9) (the wave that stages the sampling noise: the first wave's stamps do not see that work)
-    unsigned long long tw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tv[6] = {0, 0, 0, 0, 0, 0}, tstep = 0, tlast = 0, tbeg = 0;
+    // [44..49) of group B's phases L1 .. L5 the cycles it waits, in front of their first use, for the loads it requested at the
+    // head of the phase (skip_roll_b; two s_memtime round trips included; L1 requests its own slice there and waits for nothing)
+    unsigned long long tw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tv[6] = {0, 0, 0, 0, 0, 0}, td[5] = {0, 0, 0, 0, 0}, tstep = 0, tlast = 0, tbeg = 0;
 #define SWN_BAR(k) { tw[k] += __builtin_amdgcn_s_memtime() - tlast; lds_barrier(); tlast = __builtin_amdgcn_s_memtime(); }
     // (the empty asm uses the register, so the compiler places the vmcnt wait of the slice's oldest request in front of it)
 #define SWN_WAIT_STAMP(k) { asm volatile("" :: "v"(wsl[0].x)); tv[k] += __builtin_amdgcn_s_memtime() - tlast; }
@@ -683,9 +755,13 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
                      /* of the weights)                                                                                       */ \
                      /* (a resident slice 0 is consumed in L1 from its own registers, a resident slice 5 is not requested in L5) */ \
             if (LAYER == 0) { if (RES != 0) skip_issue_b<0>(wsk2, wsl, tg, step0); }                                   \
-            else if (LAYER == 1 && RES == 0) skip_roll_b<T, 1, !NOSTREAM>(lds, wsk2, wres, wsl, sacc, tg, step0);      \
+                     /* (LEADB loads of every slice but the last lead across the barrier, skip_roll_b)                        */ \
+            else if (LAYER == 1 && RES == 0)                                                                           \
+                skip_roll_b<T, 1, !NOSTREAM, LEADB, LEADB, true>(lds, wsk2, wres, wsl, sacc, tg, step0, q SWN_TDEF_ARG(0)); \
             else { SWN_WAIT_STAMP(LAYER > 0 ? LAYER - 1 : 0)                                                           \
-                   skip_roll_b<T, (LAYER > 0 ? LAYER : 1), !(LAYER == L - 1 && RES == L - 1) && !NOSTREAM>(lds, wsk2, wsl, wsl, sacc, tg, step0); } \
+                   skip_roll_b<T, (LAYER > 0 ? LAYER : 1), !(LAYER == L - 1 && RES == L - 1) && !NOSTREAM,             \
+                               (LAYER >= 2 ? LEADB : 0), (LAYER < L - 1 ? LEADB : 0)>(lds, wsk2, wsl, wsl, sacc, tg, step0, q \
+                                                                                      SWN_TDEF_ARG(LAYER > 0 ? LAYER - 1 : 0)); } \
             __builtin_amdgcn_sched_barrier(0);                                                                         \
         }                                                                                                              \
         if (!(GEN)) older_b<T, LAYER>(lds, wreg[LAYER < NWR ? LAYER : 0], q + 1, tg);                                  \
@@ -1110,7 +1186,10 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         float* h = a.heads + (tid == 0 ? 0 : tid == 64 ? 30 : 10);
         for (int k = 0; k < 9; ++k) h[k] = (float)((double)tw[k] / (double)a.n_steps);
         if (tid == 0) h[9] = (float)((double)tstep / (double)a.n_steps);
-        else if (tid == NG) for (int k = 0; k < 6; ++k) h[10 + k] = (float)((double)tv[k] / (double)a.n_steps);
+        else if (tid == NG) {
+            for (int k = 0; k < 6; ++k) h[10 + k] = (float)((double)tv[k] / (double)a.n_steps);
+            for (int k = 0; k < 5; ++k) h[34 + k] = (float)((double)td[k] / (double)a.n_steps);
+        }
     }
 #endif
 }

@@ -21,7 +21,7 @@ noise = torch.empty(1, n_steps, 1).uniform_(-0.4999, 0.5).cuda()
 for _ in range(2):
     out, heads = net.decode(aux, n_steps, noise, want_heads=True, variant=2)
 torch.cuda.synchronize()
-h = heads.flatten()[:40].cpu().numpy()
+h = heads.flatten()[:50].cpu().numpy()
 print("step total (group A clock): %.0f ticks" % h[9])
 for k, n in enumerate(names):
     print("   %-10s A works %7.0f   B works %7.0f   A's wave 1 %7.0f" % (n, h[k], h[10 + k], h[30 + k]))
@@ -29,3 +29,6 @@ print("   (of tail+L0: the tail, group A %7.0f, its wave 1 %7.0f)" % (h[8], h[38
 print("   sum        A %7.0f   B %7.0f   A's wave 1 %7.0f" % (h[:8].sum(), h[10:18].sum(), h[30:38].sum()))
 # group B, from the barrier's release until the first out_skip weight register of the slice in flight has landed
 print("   B's wait for its slice:  " + "  ".join("%s %.0f" % (n, h[20 + k]) for k, n in enumerate(names[1:7])))
+# group B, its wait for the out_skip loads it requested at the head of the phase (the last of the previous phase's slice), taken
+# in front of their first use three quarters of a phase later; includes two s_memtime round trips
+print("   B's wait for the head-of-phase loads:  " + "  ".join("%s %.0f" % (n, h[44 + k]) for k, n in enumerate(names[1:6])))
