@@ -976,6 +976,45 @@ size_t swn_resample_state_floats(int up, int n_taps);
 int    swn_resample_chunk(int up, int down, int n_taps, const double* table_dev, float* state_dev, int capacity,
                           const swn_resample_entry* entries_host, int n_entries, void* stream);
 
+/* ---- F0 and voicing from waveforms (pitch.F0Extractor; csrc/swn_f0.hip) ---------------------------------------------------------
+ * The definition (pitch.py restates it, tests/f0_ref.py pins it).  fs > 0; 1 <= hop <= SWN_F0_MAX_HOP; SWN_F0_MIN_WIN <= win = W <=
+ * SWN_F0_MAX_WIN, any integer; lags 2 <= lag_lo <= lag_hi <= SWN_F0_MAX_LAG - 1 (pitch.f0_lags: lag_lo = floor(fs / maxf0),
+ * lag_hi = ceil(fs / minf0)); 0 < threshold <= 1.  With L1 = lag_hi + 1 a frame spans S = W + L1 samples (swn_f0_span).  Input
+ * samples are fp32 and finite, len >= 1 of them, and x[t] = 0 outside [0, len): the padding is zeros, not reflection.
+ *   frames      F = 1 + len / hop, the grid of swn_logmel.  Frame f reads x[s .. s + S) with s = f * hop - S / 2.
+ *   difference  for tau = 1 .. L1, in fp64, one chain over j = 0 .. W - 1 ascending, from acc = +0.0:
+ *                   diff = (double)x[s + j] - (double)x[s + j + tau];  acc = fma(diff, diff, acc);      d(tau) = acc
+ *   normalised  c(0) = 0, c(tau) = c(tau - 1) + d(tau) strictly in this order; d'(tau) = (d(tau) * (double)tau) / c(tau) if
+ *               c(tau) > 0, else 1.0; d'(0) = 1
+ *   decision    scan tau = lag_lo .. lag_hi ascending; at the first tau with d'(tau) < threshold walk to the local minimum
+ *               (while tau < lag_hi and d'(tau + 1) < d'(tau): tau += 1): the frame is voiced with lag tau*.  If no tau is below
+ *               the threshold the frame is unvoiced and tau* is the first arg-min of d' over [lag_lo, lag_hi]
+ *   refinement  voiced frames only: ym, y0, yp = d'(tau* - 1), d'(tau*), d'(tau* + 1); den = ym - 2 y0 + yp;
+ *               shift = 0.5 * (ym - yp) / den if den > 0 and y0 <= ym and y0 <= yp, else 0; f0 = fs / ((double)tau* + shift)
+ *   output      fp32, each value rounded once, frame f at out_dev + (f - f0) * 2: [0] = F0 in Hz, exactly 0.0 when unvoiced;
+ *               [1] = d'(tau*), the aperiodicity (1.0 on silence)
+ * A frame's two values depend on the signal and the frame index alone - not on the entry, the batch, the frame range, the window
+ * or the call: any partition gives the same bits.  Streaming rule (pitch.f0_frames_ready is the one place it is written): while
+ * the signal goes on, frame f is computable iff f * hop - S / 2 + S <= n_received; when it ends, all 1 + n_received / hop
+ * frames are.  The latency is S - S / 2 samples (n_fft / 2 for swn_logmel).  This is not WORLD's Harvest and parity with it is
+ * not claimed.
+ * Entries are swn_logmel_entry with the meaning swn_logmel gives them (wav_dev at absolute sample t0, n_avail samples there, len
+ * or -1, the frames [f0, f1), reserved 0); out_dev holds (f1 - f0) * 2 floats.  At most SWN_LOGMEL_MAX_ENTRIES entries, carried
+ * in the launch arguments: one launch, one block per frame, no scratch buffer, no host copy, no synchronisation.  The kernel
+ * reads nothing outside [t0, t0 + n_avail).
+ * SWN_E_BADARG, found on the host before anything is launched, text in swn_last_error_detail: fs, hop, win, the lags or the
+ * threshold out of range, a null pointer, n_entries out of range, a non-zero reserved field, len < 1 or > 2^30, a window that
+ * leaves the signal, f0 < 0, f1 < f0, f1 > F, a frame whose in-signal samples are not all in the window, a frame that needs
+ * samples past the window while len is -1, more than 2^24 frames in one call.  Entries with f1 == f0 do nothing and may carry
+ * null pointers; a call without any frame launches nothing.  swn_f0_span returns S, or 0 for a win or lag_hi the call refuses. */
+#define SWN_F0_MAX_HOP 4096
+#define SWN_F0_MIN_WIN 16
+#define SWN_F0_MAX_WIN 2048
+#define SWN_F0_MAX_LAG 1536
+int    swn_f0_span(int win, int lag_hi);
+int    swn_f0(double fs, int hop, int win, int lag_lo, int lag_hi, double threshold, const swn_logmel_entry* entries_host,
+              int n_entries, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

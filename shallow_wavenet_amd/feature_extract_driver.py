@@ -29,7 +29,16 @@ different orders, and the device rounds once to fp32, so a sample of a PCM16 fil
 (`melspec.Resampler`, csrc/swn_resample.hip: the filter of scipy's resample_poly as one fp64 fma chain per sample, rounded once
 to fp32) before the high-pass filter, wherever that runs; `--wavdir` then receives audio at --fs.  These are the bits
 `LogMelStream(resample=)` and `LogMelPool(resample=)` give a live session fed at the file's rate.  Without the flag such a file
-is refused, as before."""
+is refused, as before.
+
+`--f0 true` adds F0 and voicing (`pitch.F0Extractor`, csrc/swn_f0.hip; the definition is in pitch.py - a difference-function
+estimator in a fixed arithmetic, not WORLD's Harvest): dataset `--f0_string_path` (default `/feat_f0`) of shape (F, 2), raw
+`[F0 in Hz or 0.0 when unvoiced, aperiodicity]` of the same frames, taken from the same batch as the other features (the
+device-filtered one under `--highpass_on device`).  `--minf0` / `--maxf0` are the reference's flags, `--f0_win` / `--f0_threshold`
+the estimator's window and threshold.  `--f0_cond true` prepends `pitch.uv_lf0` - `[uv, log of the bridged, 20 Hz low-passed F0]`,
+the first two columns of the reference's layout, at the frame rate round(fs / hop) - to the conditioning dataset: with
+`--feature_type mcep` the file holds `[uv, lf0, c(0 .. M)]`, which `noise_shaping.py --mcep_dim_start 2` reads.  A file without a
+voiced frame has no continuous F0: it is logged and skipped, and the driver returns 1."""
 from __future__ import annotations
 
 import argparse
@@ -47,6 +56,7 @@ from .decode_driver import write_wav_pcm16
 from .noise_shaping_driver import _strtobool, list_waveforms, read_wav_fs
 
 FS, SHIFTMS, FFTL, HIGHPASS_CUTOFF, MCEP_ALPHA = 22050, 5.0, 1024, 70, 0.455      # the reference's stage-1 defaults
+MINF0, MAXF0 = 40, 700
 STRING_PATH = "/feat_logmel"
 BATCH = 16                                                     # utterances per device call
 MAX_JOBS = 16                                                  # worker processes that open the device
@@ -84,6 +94,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mcep_alpha", default=MCEP_ALPHA, type=float, help="all-pass constant of the mel-cepstrum")
     p.add_argument("--mcep_floor", default=1e-5, type=float, help="floor of the amplitude under the log (mel-cepstrum; not a reference flag)")
     p.add_argument("--mcep_string_path", default="/feat_mcep", help="dataset name of the mel-cepstra (not a reference flag)")
+    p.add_argument("--minf0", default=MINF0, type=int, help="minimum f0")
+    p.add_argument("--maxf0", default=MAXF0, type=int, help="maximum f0")
+    p.add_argument("--f0", default=False, type=_strtobool,
+                   help="true: write [F0 in Hz, aperiodicity] per frame (pitch.F0Extractor) as dataset --f0_string_path "
+                        "(not a reference flag)")
+    p.add_argument("--f0_string_path", default="/feat_f0", help="dataset name of the F0 frames (not a reference flag)")
+    p.add_argument("--f0_cond", default=False, type=_strtobool,
+                   help="true: prepend [uv, log F0 (continuous, smoothed)] (pitch.uv_lf0) to the conditioning dataset of "
+                        "--feature_type logmel / mcep (not a reference flag)")
+    p.add_argument("--f0_win", default=1024, type=int, help="window of the F0 estimator in samples (not a reference flag)")
+    p.add_argument("--f0_threshold", default=0.1, type=float,
+                   help="voicing threshold of the F0 estimator on the normalised difference function (not a reference flag)")
     return p
 
 
@@ -133,7 +155,11 @@ def load_waveform(name: str, args, device="cuda") -> np.ndarray:
 
 
 def extract_files(files: Sequence[str], args, device="cuda") -> int:
+    want_f0, f0_cond = bool(getattr(args, "f0", False)), bool(getattr(args, "f0_cond", False))
     if args.feature_type == "world":
+        if want_f0 or f0_cond:
+            logging.error("--f0 / --f0_cond serve the features computed on the device; --feature_type world has its own F0")
+            return 2
         if on_device(args):
             logging.error("--highpass_on device serves the features computed on the device, not --feature_type world")
             return 2
@@ -156,6 +182,10 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
         jobs.append((MelCepstrumExtractor(args.fs, args.fftl, hop_of(args), args.mcep_dim, args.mcep_alpha, args.mcep_floor,
                                           device), dataset))
     ext = jobs[0][0]
+    f0_ext = None
+    if want_f0 or f0_cond:
+        from .pitch import F0Extractor, uv_lf0
+        f0_ext = F0Extractor(args.fs, hop_of(args), args.minf0, args.maxf0, args.f0_win, args.f0_threshold, device)
     cut = LowCut(args.fs, args.highpass_cutoff, device=device) if on_device(args) else None
     rc = 0
     for i in range(0, len(files), BATCH):
@@ -185,12 +215,34 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
                 os.makedirs(args.wavdir, exist_ok=True)
                 for name, n, y in zip(names, lengths, batch.cpu().numpy()):
                     write_wav_pcm16(os.path.join(args.wavdir, os.path.basename(name)), np.clip(y[:n], -1.0, 1.0), args.fs)
-        for extractor, dataset in jobs:
+        lead: List[Optional[np.ndarray]] = [None] * len(names)     # --f0_cond: the [uv, lf0] columns of each file
+        skip = [False] * len(names)
+        if f0_ext is not None:
+            f0ap = f0_ext(batch, lengths).cpu().numpy()
+            for k, (name, x) in enumerate(zip(names, waves)):
+                contour = f0ap[k, :ext.frame_count(x.shape[0])]
+                if f0_cond:
+                    try:
+                        lead[k] = uv_lf0(contour[:, 0], int(round(args.fs / hop_of(args)))).astype(np.float32)
+                    except ValueError as e:
+                        logging.error("%s: %s (--f0_cond needs one for the continuous F0): skipped", name, e)
+                        rc, skip[k] = 1, True
+                        continue
+                if want_f0:
+                    out = feature_path(args.hdf5dir, name)
+                    featio.write_dataset(out, args.f0_string_path, contour)
+                    logging.info("%s -> %s %s %s", name, out, args.f0_string_path, contour.shape)
+        for j, (extractor, dataset) in enumerate(jobs):
             feats = extractor(batch, lengths).cpu().numpy()
-            for name, x, f in zip(names, waves, feats):
+            for k, (name, x, f) in enumerate(zip(names, waves, feats)):
+                if skip[k]:
+                    continue
                 out = feature_path(args.hdf5dir, name)
-                featio.write_dataset(out, dataset, f[:ext.frame_count(x.shape[0])])
-                logging.info("%s -> %s %s %s", name, out, dataset, (ext.frame_count(x.shape[0]), f.shape[1]))
+                f = f[:ext.frame_count(x.shape[0])]
+                if j == 0 and lead[k] is not None:                  # the conditioning dataset
+                    f = np.concatenate([lead[k], f], axis=1)
+                featio.write_dataset(out, dataset, f)
+                logging.info("%s -> %s %s %s", name, out, dataset, f.shape)
     return rc
 
 

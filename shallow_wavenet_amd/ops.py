@@ -58,6 +58,7 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
                                      -> resampled chunks (updates state)
     torch.ops.swn.resample_staged(table, state, staged, n_ins, slots, in0s, out0s, n_outs, lens, up, down, n_taps, capacity)
                                      -> resample_chunk on chunks staged back to back, dense outputs (updates state)
+    torch.ops.swn.f0(wav, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshold) -> (F0 in Hz, aperiodicity) per frame
     torch.ops.swn.laplace_loss(raw, ctx?, target, eps, desc, skip) -> (nll, err, samples, targets, stats)
     torch.ops.swn.laplace_loss_backward(raw, ctx?, target, eps, g_nll, g_samples?, desc, skip) -> grad_raw
 """
@@ -1597,6 +1598,60 @@ def _(wav, tables, t0s, n_avails, lens, f0s, f1s, n_fft, hop, order, floor):
     return wav.new_empty((wav.shape[0], fmax, order + 1), dtype=torch.float32)
 
 
+def _f0_check(fs: float, hop: int, win: int, lag_lo: int, lag_hi: int, threshold: float) -> None:
+    """the size rules of swn_f0 as messages (the library itself answers SWN_E_BADARG)."""
+    if not (fs > 0.0 and fs < float("inf")):
+        raise RuntimeError(f"f0: fs {fs} must be a finite number > 0")
+    if not 1 <= hop <= _lib.F0_MAX_HOP:
+        raise RuntimeError(f"f0: hop {hop} outside [1, {_lib.F0_MAX_HOP}]")
+    if not _lib.F0_MIN_WIN <= win <= _lib.F0_MAX_WIN:
+        raise RuntimeError(f"f0: win {win} outside [{_lib.F0_MIN_WIN}, {_lib.F0_MAX_WIN}]")
+    if not 2 <= lag_lo <= lag_hi <= _lib.F0_MAX_LAG - 1:
+        raise RuntimeError(f"f0: lags [{lag_lo}, {lag_hi}], need 2 <= lag_lo <= lag_hi <= {_lib.F0_MAX_LAG - 1}")
+    if not 0.0 < threshold <= 1.0:
+        raise RuntimeError(f"f0: threshold {threshold} outside (0, 1]")
+
+
+def f0_impl(wav: torch.Tensor, t0s: List[int], n_avails: List[int], lens: List[int], f0s: List[int], f1s: List[int], fs: float,
+            hop: int, win: int, lag_lo: int, lag_hi: int, threshold: float) -> torch.Tensor:
+    """wav (R, S), t0s, n_avails, lens, f0s, f1s: as logmel takes them -> (R, max(f1 - f0), 2): [F0 in Hz or 0.0 when unvoiced,
+    aperiodicity d'(tau*)] of the frames [f0s[r], f1s[r]) of each row, zero past a row's own range (swn_f0; the definition is
+    in pitch.py)."""
+    Lb = _lib.lib()
+    _need_cuda(wav, "the waveforms")
+    dev = wav.device
+    _f0_check(fs, hop, win, lag_lo, lag_hi, threshold)
+    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
+        raise RuntimeError(f"f0 needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
+    R, S = wav.shape
+    if not (len(t0s) == len(n_avails) == len(lens) == len(f0s) == len(f1s) == R):
+        raise RuntimeError("f0: t0s, n_avails, lens, f0s and f1s must have one entry per row")
+    if any(not 0 <= na <= S for na in n_avails):
+        raise RuntimeError(f"f0: a row has more samples available than the buffer's {S} columns")
+    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
+    out = torch.zeros((R, fmax, 2), dtype=torch.float32, device=dev)
+    esz, osz = wav.element_size() * S, out.element_size() * fmax * 2
+    for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
+        r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
+        table = (_lib.LogMelEntry * (r1 - r0))(*[
+            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
+                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
+            for r in range(r0, r1)])
+        with _on(dev):
+            _lib.check(Lb.swn_f0(float(fs), hop, win, lag_lo, lag_hi, float(threshold), table, r1 - r0, _stream(dev)), "f0")
+    return out
+
+
+f0 = custom_op("swn::f0", mutates_args=())(f0_impl)
+
+
+@f0.register_fake
+def _(wav, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshold):
+    _f0_check(fs, hop, win, lag_lo, lag_hi, threshold)
+    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
+    return wav.new_empty((wav.shape[0], fmax, 2), dtype=torch.float32)
+
+
 def logmel_pool_impl(win: torch.Tensor, staged: Optional[torch.Tensor], tables: torch.Tensor, bank: List[int], slots: List[int],
                      t0s: List[int], n_helds: List[int], n_drops: List[int], n_news: List[int], lens: List[int], f0s: List[int],
                      f1s: List[int], n_fft: int, hop: int, floor: float, linear: bool) -> torch.Tensor:
@@ -1856,4 +1911,4 @@ OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk"
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
             "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool", "mcep", "lowcut_chunk", "logmel_pool_lowcut",
-            "resample_chunk", "resample_staged")
+            "resample_chunk", "resample_staged", "f0")

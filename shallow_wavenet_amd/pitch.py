@@ -1,0 +1,178 @@
+"""F0 and voicing from waveforms on the device (`torch.ops.swn.f0`, csrc/swn_f0.hip): the contour the reference's features start
+with - `[uv, log F0 (continuous, smoothed), ...]` - without WORLD, by a fully pinned definition of its own.
+
+    ext = F0Extractor(fs=22050, hop=110, minf0=40, maxf0=700, device="cuda:0")
+    f0ap = ext(wavs, lengths)                  # (R, F_max, 2): [F0 in Hz or 0.0 when unvoiced, aperiodicity]; zero past a row's frames
+    stream = F0Stream(ext)                     # the same frames, as the samples arrive
+    new = stream.push(chunk); ...; last = stream.finish()
+    cond = uv_lf0(f0ap[0, :F, 0].cpu().numpy(), frame_rate=200)     # (F, 2): [uv, log of the bridged, smoothed F0] on the host
+
+Definition (the contract; include/swn_hip.h and csrc/swn_f0.hip restate it, tests/f0_ref.py pins it).  Parameters: `fs` > 0;
+`hop` in 1 .. 4096; `win` = W in 16 .. 2048, any integer; lags 2 <= lag_lo <= lag_hi <= 1535, which `f0_lags` derives from Hz as
+lag_lo = floor(fs / maxf0), lag_hi = ceil(fs / minf0); `threshold` in (0, 1].  With L1 = lag_hi + 1 a frame spans S = W + L1
+samples.  Input samples are fp32 and finite, len >= 1 of them; outside [0, len) x[t] = 0: the padding is zeros, not reflection.
+  * Frames: F = 1 + len // hop, the grid of the log-mel features.  Frame f reads x[s .. s + S) with s = f * hop - S // 2.
+  * Difference function: for tau = 1 .. L1, in fp64, one chain over j = 0 .. W - 1 ascending from acc = +0.0:
+    diff = (double)x[s + j] - (double)x[s + j + tau]; acc = fma(diff, diff, acc); d(tau) = acc.
+  * Cumulative mean normalisation: c(0) = 0, c(tau) = c(tau - 1) + d(tau) strictly in this order; d'(tau) = (d(tau) * tau) / c(tau)
+    if c(tau) > 0, else 1.0; d'(0) = 1.
+  * Decision: scan tau = lag_lo .. lag_hi ascending; at the first tau with d'(tau) < threshold walk to the local minimum (while
+    tau < lag_hi and d'(tau + 1) < d'(tau): tau += 1); the frame is voiced with lag tau*.  If no tau is below the threshold the frame
+    is unvoiced and tau* is the first arg-min of d' over [lag_lo, lag_hi].
+  * Refinement (voiced frames): ym, y0, yp = d'(tau* - 1), d'(tau*), d'(tau* + 1); den = ym - 2 y0 + yp; shift = 0.5 (ym - yp) / den
+    if den > 0 and y0 <= ym and y0 <= yp, else 0; f0 = fs / (tau* + shift).
+  * Output, fp32, each value rounded once: [0] = F0 in Hz, exactly 0.0 when unvoiced; [1] = d'(tau*), the aperiodicity (1.0 on
+    silence).
+A frame's two values depend on the signal and the frame index alone - not on the batch, the frame range, the buffer window or
+the call - so the stream's concatenated output is bit-identical to the one-shot call.  Streaming rule (`f0_frames_ready`, the one
+place it is written): while the signal goes on, frame f is computable iff f * hop - S // 2 + S <= n_received; when it ends, all
+1 + n_received // hop frames are.  The latency is S - S // 2 samples (n_fft / 2 for the log-mel features): 789 samples, 36 ms, at
+the shipped geometry (22 050 Hz, win 1024, 40 Hz).  There is no torch fall-back: without the library the call raises.
+
+This is the difference-function estimator of de Cheveigne and Kawahara (YIN, 2002) in a fixed arithmetic, not WORLD's Harvest:
+parity with Harvest is not claimed and not pinned.  Out of scope here: a pool variant (one call per tick for many sessions),
+`low_cut=` and `resample=` arguments on the stream (compose it with `Resampler.run` / `LowCut.run`), aperiodicity coding, and any
+smoothing or octave correction of the contour on the device (`uv_lf0` bridges and smooths on the host, with dsp.py's helpers)."""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib, dsp, ops
+from .melspec import _padded_batch, frame_count
+
+
+def f0_lags(fs: float, minf0: float, maxf0: float) -> Tuple[int, int]:
+    """(lag_lo, lag_hi) = (floor(fs / maxf0), ceil(fs / minf0)); ValueError where swn_f0 would refuse them"""
+    if not (fs > 0 and 0 < minf0 <= maxf0):
+        raise ValueError(f"need fs > 0 and 0 < minf0 <= maxf0, got fs {fs}, minf0 {minf0}, maxf0 {maxf0}")
+    lo, hi = int(math.floor(fs / maxf0)), int(math.ceil(fs / minf0))
+    if not 2 <= lo <= hi <= _lib.F0_MAX_LAG - 1:
+        raise ValueError(f"fs {fs}, minf0 {minf0}, maxf0 {maxf0} give the lags [{lo}, {hi}]: need 2 <= lag_lo <= lag_hi <= "
+                         f"{_lib.F0_MAX_LAG - 1}")
+    return lo, hi
+
+
+def f0_span(win: int, lag_hi: int) -> int:
+    """S = win + lag_hi + 1, the samples a frame reads"""
+    return int(win) + int(lag_hi) + 1
+
+
+def f0_frames_ready(hop: int, win: int, lag_hi: int, n_received: int, final: bool = False) -> int:
+    """frames of a signal that can be computed once n_received samples are there.  While it goes on, frame f is computable iff
+    f * hop - S // 2 + S <= n_received; when it ends there (`final`), all F = 1 + n_received // hop (the rest is zeros)."""
+    if final:
+        return frame_count(n_received, hop)
+    S = f0_span(win, lag_hi)
+    ahead = S - S // 2
+    return 0 if n_received < ahead else 1 + (n_received - ahead) // hop
+
+
+class F0Extractor:
+    """holds the geometry; a call computes [F0, aperiodicity] of every frame of a batch of waveforms on `device`."""
+
+    def __init__(self, fs: float, hop: int, minf0: float = 40.0, maxf0: float = 700.0, win: int = 1024, threshold: float = 0.1,
+                 device="cuda") -> None:
+        self.fs, self.hop, self.win, self.threshold = float(fs), int(hop), int(win), float(threshold)
+        self.minf0, self.maxf0 = float(minf0), float(maxf0)
+        self.lag_lo, self.lag_hi = f0_lags(self.fs, self.minf0, self.maxf0)
+        if not 1 <= self.hop <= _lib.F0_MAX_HOP:
+            raise ValueError(f"hop {hop} outside [1, {_lib.F0_MAX_HOP}]")
+        if not _lib.F0_MIN_WIN <= self.win <= _lib.F0_MAX_WIN:
+            raise ValueError(f"win {win} outside [{_lib.F0_MIN_WIN}, {_lib.F0_MAX_WIN}]")
+        if not 0.0 < self.threshold <= 1.0:
+            raise ValueError(f"threshold {threshold} outside (0, 1]")
+        self.span = f0_span(self.win, self.lag_hi)
+        self.device = torch.device(device)
+        self._op = ops.f0_impl
+
+    def frame_count(self, length: int) -> int:
+        return frame_count(length, self.hop)
+
+    def _check_len(self, length: int) -> None:
+        if length < 1:
+            raise ValueError(f"a signal needs at least one sample, got {length}")
+
+    def _run(self, buf, t0s, n_avails, lens, f0s, f1s) -> torch.Tensor:
+        return self._op(buf, t0s, n_avails, lens, f0s, f1s, self.fs, self.hop, self.win, self.lag_lo, self.lag_hi, self.threshold)
+
+    def __call__(self, wavs, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """wavs: a padded (R, S) batch with `lengths` (default: S for every row), one 1-D signal, or a list of R 1-D signals of
+        their own lengths -> (R, F_max, 2), row r holding frame_count(lengths[r]) frames and zeros after them."""
+        batch, lens = _padded_batch(self, wavs, lengths)
+        R = len(lens)
+        return self._run(batch, [0] * R, lens, lens, [0] * R, [self.frame_count(n) for n in lens])
+
+    def frames(self, wav: torch.Tensor, t0: Union[int, Sequence[int]], n_avail: Union[int, Sequence[int]],
+               length: Union[int, Sequence[int]], f0: Union[int, Sequence[int]], f1: Union[int, Sequence[int]]) -> torch.Tensor:
+        """frames [f0, f1) from a partial buffer: `wav` (S,) or (R, S) holds the samples [t0, t0 + n_avail) of each signal, whose
+        total length is `length` or -1 while it is not known -> (f1 - f0, 2) or (R, max(f1 - f0), 2).  A range whose in-signal
+        samples are not all in the buffer is refused."""
+        one = wav.dim() == 1
+        buf = (wav[None] if one else wav).to(self.device, torch.float32).contiguous()
+        lst = lambda v: [int(v)] * buf.shape[0] if isinstance(v, (int, np.integer)) else [int(x) for x in v]
+        out = self._run(buf, lst(t0), lst(n_avail), lst(length), lst(f0), lst(f1))
+        return out[0] if one else out
+
+
+class F0Stream:
+    """one signal's [F0, aperiodicity] frames as its samples arrive: `push` returns the frames that became computable, `finish`
+    the rest (those that read the zeros past the end).  Only the tail of the signal that later frames still read is kept.  The
+    concatenation of everything returned is bit-identical to the extractor's one-shot call on the whole signal.  The samples are
+    at the extractor's rate, already filtered: a caller that has raw audio at another rate runs `Resampler.run` and `LowCut.run`
+    on each chunk first."""
+
+    def __init__(self, extractor: F0Extractor) -> None:
+        self.ext = extractor
+        self._buf = torch.zeros(0, dtype=torch.float32, device=extractor.device)
+        self.t0 = 0                 # absolute index of _buf[0]
+        self.n_received = 0
+        self.n_frames = 0           # frames returned so far
+        self.finished = False
+
+    def computable(self, n_received: int, final: bool = False) -> int:
+        return f0_frames_ready(self.ext.hop, self.ext.win, self.ext.lag_hi, n_received, final)
+
+    def _range(self, f1: int, length: int) -> torch.Tensor:
+        f0 = self.n_frames
+        if f1 > f0:
+            out = self.ext.frames(self._buf, self.t0, int(self._buf.numel()), length, f0, f1)
+            self.n_frames = f1
+        else:
+            out = torch.zeros((0, 2), dtype=torch.float32, device=self.ext.device)
+        # the next frame's first sample; with hop > S it may not have arrived yet
+        keep = min(self.n_received, max(self.t0, self.n_frames * self.ext.hop - self.ext.span // 2))
+        if keep > self.t0:
+            self._buf = self._buf[keep - self.t0:]
+            self.t0 = keep
+        return out
+
+    def push(self, samples) -> torch.Tensor:
+        """append 1-D samples -> (k, 2) new frames, k >= 0"""
+        if self.finished:
+            raise RuntimeError("the stream is finished")
+        s = torch.as_tensor(samples).reshape(-1).to(self.ext.device, torch.float32)
+        self._buf = torch.cat([self._buf, s])
+        self.n_received += int(s.numel())
+        return self._range(self.computable(self.n_received), -1)
+
+    def finish(self) -> torch.Tensor:
+        """the signal ends here -> the remaining frames up to F = 1 + n_received // hop"""
+        if self.finished:
+            raise RuntimeError("the stream is finished")
+        self.ext._check_len(self.n_received)
+        self.finished = True
+        return self._range(self.computable(self.n_received, True), self.n_received)
+
+
+def uv_lf0(f0_column, frame_rate: int) -> np.ndarray:
+    """(F,) F0 in Hz with 0.0 on unvoiced frames -> (F, 2) float64 [uv, log(low_pass_filter(continuous_f0(f0), frame_rate, 20))]:
+    the first two columns of the reference's feature layout, by the helpers of dsp.py (feature_extract.py:296-305).  ValueError
+    when no frame is voiced."""
+    f0 = np.asarray(f0_column, dtype=np.float64).reshape(-1)
+    uv, cont = dsp.continuous_f0(f0)
+    lf0 = np.log(dsp.low_pass_filter(cont, int(frame_rate), cutoff=20))
+    return np.stack([uv.astype(np.float64), lf0], axis=1)
