@@ -1015,6 +1015,52 @@ int    swn_f0_span(int win, int lag_hi);
 int    swn_f0(double fs, int hop, int win, int lag_lo, int lag_hi, double threshold, const swn_logmel_entry* entries_host,
               int n_entries, void* stream);
 
+/* ---- Band aperiodicity from waveforms (pitch.BandAperiodicityExtractor; csrc/swn_f0.hip) -----------------------------------------
+ * Per frame: swn_f0's two values and, for each of B band-pass filters, how far the band signal is from periodic at the frame's
+ * decided lag, coded in dB - the counterpart of the reference's `codeap` columns, by a definition of this project's own.  This is
+ * not WORLD's D4C / code_aperiodicity: parity with them is neither claimed nor pinned.
+ * The definition (pitch.py restates it, tests/bap_ref.py pins it).  Everything about F0 is swn_f0's, unchanged: fs, hop, win = W,
+ * lag_lo, lag_hi, threshold, L1 = lag_hi + 1, S = W + L1, zeros outside [0, len), F = 1 + len / hop, frame f at s = f hop - S / 2
+ * with its decided lag tau* (defined on unvoiced frames too) and its voicing decision.  New: 1 <= n_bands = B <=
+ * SWN_BAP_MAX_BANDS filters of n_taps = T fp64 taps h_b[0 .. T) each, T odd, 1 <= T <= SWN_BAP_MAX_TAPS, c = (T - 1) / 2, as a
+ * device table of B * T doubles (the call knows nothing of Hz: the band edges exist only in how the caller built the table);
+ * a sum window SWN_F0_MIN_WIN <= band_win = Wb <= W; a floor, 0 < floor < 1.
+ *   band signal  for every integer t, x = 0 outside [0, len):  y_b[t] = sum_k h_b[k] * (double)x[t + c - k], one fp64 chain
+ *                acc = fma(h_b[k], x, acc), k ascending from acc = +0.0.  Centred: no group delay is left in it.
+ *   frame sums   s_b = f hop - (Wb + tau*) / 2 (C division of a non-negative number): the windows [s_b, s_b + Wb) and
+ *                [s_b + tau*, s_b + tau* + Wb) lie inside [s, s + S).  Over j = 0 .. Wb - 1:
+ *                    d = sum (y_b[s_b + j] - y_b[s_b + j + tau*])^2,  e0 = sum y_b[s_b + j]^2,  e1 = sum y_b[s_b + j + tau*]^2
+ *   order        of each sum, depending on Wb alone: partial chain l = 0 .. 63 runs over j = l, l + 64, .. ascending by fma
+ *                (diff = y0 - y1 rounded, then fma(diff, diff, acc); fma(y, y, acc)) from +0.0; the 64 partials are then added
+ *                into +0.0 in ascending l
+ *   ratio        e = e0 + e1; ap = d / e if e > 0, else 1.0: 0 for a band exactly periodic at tau*, about 1 for noise, at most 2
+ *   coded        10 * log10(min(max(ap, (double)floor), 1.0)) dB (<= 0) on voiced frames; exactly 0.0 on unvoiced frames
+ *   output       fp32, each value rounded once, frame f at out_dev + (f - f0) * (2 + B): [0], [1] have swn_f0's bits for the same
+ *                frame, [2 + b] is the coded value of band b
+ * A frame reads x[s - c .. s + S + c) (swn_bap_reach = S + 2 c samples).  Its values depend on the signal and the frame index
+ * alone: any batch, frame range, window or chunking gives the same bits.  Streaming rule (pitch.bap_frames_ready is the one place
+ * it is written): while the signal goes on, frame f is computable iff f hop - S / 2 + S + c <= n_received; when it ends, all F
+ * frames are.  The latency is S - S / 2 + c samples.
+ * Known limits: tau* is an integer lag, so a band around frequency nu cannot go below about 1 - cos(pi nu / fs) for a period
+ * that falls between two lags, and vibrato inside the window raises the value further.
+ * Entries are swn_logmel_entry with swn_f0's meaning; out_dev holds (f1 - f0) * (2 + B) floats.  Two launches per call: one
+ * fills the fp64 scratch work_dev (swn_bap_work_bytes for the same entries; 8-byte aligned) with y_b over the samples each
+ * entry's frame range spans, in tiles of SWN_BAP_TILE samples; one runs a block per frame.  No atomics, no host copy, no
+ * synchronisation.  The kernels read nothing outside [t0, t0 + n_avail).
+ * SWN_E_BADARG, found on the host before anything is launched, text in swn_last_error_detail: everything swn_f0 refuses;
+ * n_bands, n_taps (even counts included), band_win or floor out of range; a null taps_dev or work_dev; a frame range whose
+ * in-signal samples, INCLUDING the c samples on either side, are not all in the window; a frame range that needs samples past
+ * the window while len is -1.  Entries with f1 == f0 do nothing; a call without any frame launches nothing.  swn_bap_reach
+ * returns S + 2 c, swn_bap_work_bytes the scratch size in bytes; both return 0 for arguments the call refuses. */
+#define SWN_BAP_MAX_BANDS 5
+#define SWN_BAP_MAX_TAPS 255
+#define SWN_BAP_TILE 1280
+int    swn_bap_reach(int win, int lag_hi, int n_taps);
+size_t swn_bap_work_bytes(int hop, int win, int lag_hi, int n_bands, const swn_logmel_entry* entries_host, int n_entries);
+int    swn_bap(double fs, int hop, int win, int lag_lo, int lag_hi, double threshold, int band_win, int n_bands, int n_taps,
+               const double* taps_dev, float floor, const swn_logmel_entry* entries_host, int n_entries, void* work_dev,
+               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

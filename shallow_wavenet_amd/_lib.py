@@ -118,6 +118,7 @@ LOGMEL_MAX_MELS, LOGMEL_MAX_ENTRIES = 128, 64     # SWN_LOGMEL_MAX_MELS, SWN_LOG
 LOGMEL_POOL_MAX_ENTRIES = 64                   # SWN_LOGMEL_POOL_MAX_ENTRIES (include/swn_hip.h): entries per log-mel pool call
 MCEP_MAX_ORDER = 63                            # SWN_MCEP_MAX_ORDER (include/swn_hip.h)
 F0_MAX_HOP, F0_MIN_WIN, F0_MAX_WIN, F0_MAX_LAG = 4096, 16, 2048, 1536    # SWN_F0_MAX_HOP, _MIN_WIN, _MAX_WIN, _MAX_LAG
+BAP_MAX_BANDS, BAP_MAX_TAPS, BAP_TILE = 5, 255, 1280                     # SWN_BAP_MAX_BANDS, _MAX_TAPS, _TILE
 
 
 def desc_from_cfg(cfg: NetConfig) -> NetDesc:
@@ -252,6 +253,10 @@ SIGNATURES = {
     "swn_resample_chunk": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, POINTER(ResampleEntry), c_int, c_void_p]),
     "swn_f0_span": (c_int, [c_int, c_int]),
     "swn_f0": (c_int, [ctypes.c_double, c_int, c_int, c_int, c_int, ctypes.c_double, POINTER(LogMelEntry), c_int, c_void_p]),
+    "swn_bap_reach": (c_int, [c_int, c_int, c_int]),
+    "swn_bap_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int, POINTER(LogMelEntry), c_int]),
+    "swn_bap": (c_int, [ctypes.c_double, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_int, c_int, c_void_p, ctypes.c_float,
+                POINTER(LogMelEntry), c_int, c_void_p, c_void_p]),
 }
 
 

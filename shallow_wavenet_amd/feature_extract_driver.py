@@ -38,7 +38,15 @@ device-filtered one under `--highpass_on device`).  `--minf0` / `--maxf0` are th
 the estimator's window and threshold.  `--f0_cond true` prepends `pitch.uv_lf0` - `[uv, log of the bridged, 20 Hz low-passed F0]`,
 the first two columns of the reference's layout, at the frame rate round(fs / hop) - to the conditioning dataset: with
 `--feature_type mcep` the file holds `[uv, lf0, c(0 .. M)]`, which `noise_shaping.py --mcep_dim_start 2` reads.  A file without a
-voiced frame has no continuous F0: it is logged and skipped, and the driver returns 1."""
+voiced frame has no continuous F0: it is logged and skipped, and the driver returns 1.
+
+`--bap true` adds the band aperiodicity (`pitch.BandAperiodicityExtractor`, the same file's swn_bap; the definition is in
+pitch.py - this project's own measure, not WORLD's D4C / code_aperiodicity): dataset `--bap_string_path` (default `/feat_bap`) of
+shape (F, B), the coded aperiodicity in dB of the B = `pitch.bap_bands(fs)` bands the reference codes at this rate (2 at 22.05
+kHz; a rate below 12 kHz has none and is refused), with `--bap_taps` taps per band-pass and the sum window `--bap_win`.  One call
+serves `--f0` / `--f0_cond` too: `/feat_f0` is its columns 0 - 1.  With `--f0_cond true` the conditioning dataset becomes `[uv,
+lf0, bap_0 .. bap_{B-1}, features]`, the reference's column order, so `noise_shaping.py --mcep_dim_start` is 2 + B - run.sh's
+`stdim`."""
 from __future__ import annotations
 
 import argparse
@@ -106,6 +114,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--f0_win", default=1024, type=int, help="window of the F0 estimator in samples (not a reference flag)")
     p.add_argument("--f0_threshold", default=0.1, type=float,
                    help="voicing threshold of the F0 estimator on the normalised difference function (not a reference flag)")
+    p.add_argument("--bap", default=False, type=_strtobool,
+                   help="true: write the coded band aperiodicity in dB per frame (pitch.BandAperiodicityExtractor) as dataset "
+                        "--bap_string_path, and with --f0_cond true put it behind [uv, lf0] (not a reference flag)")
+    p.add_argument("--bap_string_path", default="/feat_bap", help="dataset name of the band aperiodicity (not a reference flag)")
+    p.add_argument("--bap_taps", default=255, type=int, help="taps of each band-pass filter, odd (not a reference flag)")
+    p.add_argument("--bap_win", default=256, type=int,
+                   help="sum window of the band aperiodicity in samples, clipped to --f0_win (not a reference flag)")
     return p
 
 
@@ -156,9 +171,11 @@ def load_waveform(name: str, args, device="cuda") -> np.ndarray:
 
 def extract_files(files: Sequence[str], args, device="cuda") -> int:
     want_f0, f0_cond = bool(getattr(args, "f0", False)), bool(getattr(args, "f0_cond", False))
+    want_bap = bool(getattr(args, "bap", False))
     if args.feature_type == "world":
-        if want_f0 or f0_cond:
-            logging.error("--f0 / --f0_cond serve the features computed on the device; --feature_type world has its own F0")
+        if want_f0 or f0_cond or want_bap:
+            logging.error("--f0 / --f0_cond / --bap serve the features computed on the device; --feature_type world has its own "
+                          "F0 and aperiodicity")
             return 2
         if on_device(args):
             logging.error("--highpass_on device serves the features computed on the device, not --feature_type world")
@@ -183,7 +200,15 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
                                           device), dataset))
     ext = jobs[0][0]
     f0_ext = None
-    if want_f0 or f0_cond:
+    if want_bap:                                                    # one call serves the F0 columns too
+        from .pitch import BandAperiodicityExtractor, uv_lf0
+        try:
+            f0_ext = BandAperiodicityExtractor(args.fs, hop_of(args), args.minf0, args.maxf0, args.f0_win, args.f0_threshold,
+                                               n_taps=args.bap_taps, band_win=args.bap_win, device=device)
+        except ValueError as e:
+            logging.error("--bap: %s", e)
+            return 2
+    elif want_f0 or f0_cond:
         from .pitch import F0Extractor, uv_lf0
         f0_ext = F0Extractor(args.fs, hop_of(args), args.minf0, args.maxf0, args.f0_win, args.f0_threshold, device)
     cut = LowCut(args.fs, args.highpass_cutoff, device=device) if on_device(args) else None
@@ -215,15 +240,17 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
                 os.makedirs(args.wavdir, exist_ok=True)
                 for name, n, y in zip(names, lengths, batch.cpu().numpy()):
                     write_wav_pcm16(os.path.join(args.wavdir, os.path.basename(name)), np.clip(y[:n], -1.0, 1.0), args.fs)
-        lead: List[Optional[np.ndarray]] = [None] * len(names)     # --f0_cond: the [uv, lf0] columns of each file
+        lead: List[Optional[np.ndarray]] = [None] * len(names)     # --f0_cond: the [uv, lf0 (, bap)] columns of each file
         skip = [False] * len(names)
         if f0_ext is not None:
             f0ap = f0_ext(batch, lengths).cpu().numpy()
             for k, (name, x) in enumerate(zip(names, waves)):
-                contour = f0ap[k, :ext.frame_count(x.shape[0])]
+                frames = f0ap[k, :ext.frame_count(x.shape[0])]
+                contour, bap = np.ascontiguousarray(frames[:, :2]), np.ascontiguousarray(frames[:, 2:])
                 if f0_cond:
                     try:
-                        lead[k] = uv_lf0(contour[:, 0], int(round(args.fs / hop_of(args)))).astype(np.float32)
+                        lead[k] = np.concatenate([uv_lf0(contour[:, 0], int(round(args.fs / hop_of(args)))).astype(np.float32),
+                                                  bap], axis=1)
                     except ValueError as e:
                         logging.error("%s: %s (--f0_cond needs one for the continuous F0): skipped", name, e)
                         rc, skip[k] = 1, True
@@ -232,6 +259,10 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
                     out = feature_path(args.hdf5dir, name)
                     featio.write_dataset(out, args.f0_string_path, contour)
                     logging.info("%s -> %s %s %s", name, out, args.f0_string_path, contour.shape)
+                if want_bap:
+                    out = feature_path(args.hdf5dir, name)
+                    featio.write_dataset(out, args.bap_string_path, bap)
+                    logging.info("%s -> %s %s %s", name, out, args.bap_string_path, bap.shape)
         for j, (extractor, dataset) in enumerate(jobs):
             feats = extractor(batch, lengths).cpu().numpy()
             for k, (name, x, f) in enumerate(zip(names, waves, feats)):

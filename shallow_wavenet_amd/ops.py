@@ -59,6 +59,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.resample_staged(table, state, staged, n_ins, slots, in0s, out0s, n_outs, lens, up, down, n_taps, capacity)
                                      -> resample_chunk on chunks staged back to back, dense outputs (updates state)
     torch.ops.swn.f0(wav, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshold) -> (F0 in Hz, aperiodicity) per frame
+    torch.ops.swn.bap(wav, taps, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshold, band_win, floor)
+                                                    -> (F0 in Hz, aperiodicity, B coded band aperiodicities in dB) per frame
     torch.ops.swn.laplace_loss(raw, ctx?, target, eps, desc, skip) -> (nll, err, samples, targets, stats)
     torch.ops.swn.laplace_loss_backward(raw, ctx?, target, eps, g_nll, g_samples?, desc, skip) -> grad_raw
 """
@@ -1652,6 +1654,73 @@ def _(wav, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshol
     return wav.new_empty((wav.shape[0], fmax, 2), dtype=torch.float32)
 
 
+def _bap_check(taps: torch.Tensor, win: int, band_win: int, floor: float) -> Tuple[int, int]:
+    """the size rules swn_bap adds to swn_f0's, as messages -> (n_bands, n_taps)"""
+    if taps.dim() != 2 or taps.dtype != torch.float64:
+        raise RuntimeError(f"bap: taps must be a (n_bands, n_taps) float64 tensor, got {tuple(taps.shape)} {taps.dtype}")
+    B, T = int(taps.shape[0]), int(taps.shape[1])
+    if not 1 <= B <= _lib.BAP_MAX_BANDS:
+        raise RuntimeError(f"bap: {B} bands, need 1 .. {_lib.BAP_MAX_BANDS}")
+    if not (1 <= T <= _lib.BAP_MAX_TAPS and T % 2 == 1):
+        raise RuntimeError(f"bap: {T} taps, need an odd count in 1 .. {_lib.BAP_MAX_TAPS}")
+    if not _lib.F0_MIN_WIN <= band_win <= win:
+        raise RuntimeError(f"bap: band_win {band_win} outside [{_lib.F0_MIN_WIN}, win = {win}]")
+    if not 0.0 < floor < 1.0:
+        raise RuntimeError(f"bap: floor {floor} outside (0, 1)")
+    return B, T
+
+
+def bap_impl(wav: torch.Tensor, taps: torch.Tensor, t0s: List[int], n_avails: List[int], lens: List[int], f0s: List[int],
+             f1s: List[int], fs: float, hop: int, win: int, lag_lo: int, lag_hi: int, threshold: float, band_win: int,
+             floor: float) -> torch.Tensor:
+    """wav (R, S), t0s, n_avails, lens, f0s, f1s: as f0 takes them; taps: contiguous (B, T) float64 band-pass filters on wav's
+    device -> (R, max(f1 - f0), 2 + B): f0's two values and the B coded band aperiodicities in dB of the frames [f0s[r], f1s[r])
+    of each row, zero past a row's own range (swn_bap; the definition is in pitch.py)."""
+    Lb = _lib.lib()
+    _need_cuda(wav, "the waveforms")
+    dev = wav.device
+    _f0_check(fs, hop, win, lag_lo, lag_hi, threshold)
+    B, T = _bap_check(taps, win, band_win, floor)
+    if taps.device != dev or not taps.is_contiguous():
+        raise RuntimeError("bap: taps must be contiguous and on the waveforms' device")
+    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
+        raise RuntimeError(f"bap needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
+    R, S = wav.shape
+    if not (len(t0s) == len(n_avails) == len(lens) == len(f0s) == len(f1s) == R):
+        raise RuntimeError("bap: t0s, n_avails, lens, f0s and f1s must have one entry per row")
+    if any(not 0 <= na <= S for na in n_avails):
+        raise RuntimeError(f"bap: a row has more samples available than the buffer's {S} columns")
+    fmax, cols = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0]), 2 + B
+    out = torch.zeros((R, fmax, cols), dtype=torch.float32, device=dev)
+    esz, osz = wav.element_size() * S, out.element_size() * fmax * cols
+    groups = []
+    for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
+        r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
+        table = (_lib.LogMelEntry * (r1 - r0))(*[
+            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
+                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
+            for r in range(r0, r1)])
+        groups.append((table, r1 - r0, int(Lb.swn_bap_work_bytes(hop, win, lag_hi, B, table, r1 - r0))))
+    # one scratch for all groups, which run one after the other on the stream (never empty: the call refuses a null pointer)
+    work = torch.empty((max([b for _, _, b in groups] + [8]) // 8,), dtype=torch.float64, device=dev)
+    for table, n, _ in groups:
+        with _on(dev):
+            _lib.check(Lb.swn_bap(float(fs), hop, win, lag_lo, lag_hi, float(threshold), band_win, B, T, taps.data_ptr(), float(floor),
+                                  table, n, work.data_ptr(), _stream(dev)), "bap")
+    return out
+
+
+bap = custom_op("swn::bap", mutates_args=())(bap_impl)
+
+
+@bap.register_fake
+def _(wav, taps, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshold, band_win, floor):
+    _f0_check(fs, hop, win, lag_lo, lag_hi, threshold)
+    B, _ = _bap_check(taps, win, band_win, floor)
+    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
+    return wav.new_empty((wav.shape[0], fmax, 2 + B), dtype=torch.float32)
+
+
 def logmel_pool_impl(win: torch.Tensor, staged: Optional[torch.Tensor], tables: torch.Tensor, bank: List[int], slots: List[int],
                      t0s: List[int], n_helds: List[int], n_drops: List[int], n_news: List[int], lens: List[int], f0s: List[int],
                      f1s: List[int], n_fft: int, hop: int, floor: float, linear: bool) -> torch.Tensor:
@@ -1911,4 +1980,4 @@ OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk"
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
             "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool", "mcep", "lowcut_chunk", "logmel_pool_lowcut",
-            "resample_chunk", "resample_staged", "f0")
+            "resample_chunk", "resample_staged", "f0", "bap")

@@ -31,12 +31,21 @@ the shipped geometry (22 050 Hz, win 1024, 40 Hz).  There is no torch fall-back:
 
 This is the difference-function estimator of de Cheveigne and Kawahara (YIN, 2002) in a fixed arithmetic, not WORLD's Harvest:
 parity with Harvest is not claimed and not pinned.  Out of scope here: a pool variant (one call per tick for many sessions),
-`low_cut=` and `resample=` arguments on the stream (compose it with `Resampler.run` / `LowCut.run`), aperiodicity coding, and any
-smoothing or octave correction of the contour on the device (`uv_lf0` bridges and smooths on the host, with dsp.py's helpers)."""
+`low_cut=` and `resample=` arguments on the streams (compose them with `Resampler.run` / `LowCut.run`), and any smoothing or
+octave correction of the contour on the device (`uv_lf0` bridges and smooths on the host, with dsp.py's helpers).
+
+Band aperiodicity (`torch.ops.swn.bap`, swn_bap in the same file) adds the reference's `codeap` columns to those two:
+
+    ext = BandAperiodicityExtractor(fs=22050, hop=110, device="cuda:0")       # bands bap_bands(fs), 255 taps, band_win 256
+    f = ext(wavs, lengths)                     # (R, F_max, 2 + B): [F0, aperiodicity, coded aperiodicity of band 0 .. B - 1 in dB]
+    stream = BapStream(ext)                    # the same frames as the samples arrive, (n_taps - 1) / 2 samples later than F0Stream's
+
+Its definition, limits and streaming rule (`bap_frames_ready`) are in BandAperiodicityExtractor's docstring; it is this project's
+own measure, not WORLD's D4C / `code_aperiodicity`, and parity with them is neither claimed nor pinned."""
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence, Tuple, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -132,6 +141,8 @@ class F0Stream:
         self.n_received = 0
         self.n_frames = 0           # frames returned so far
         self.finished = False
+        self._behind = extractor.span // 2      # samples a frame reads before f * hop
+        self._cols = 2
 
     def computable(self, n_received: int, final: bool = False) -> int:
         return f0_frames_ready(self.ext.hop, self.ext.win, self.ext.lag_hi, n_received, final)
@@ -142,9 +153,9 @@ class F0Stream:
             out = self.ext.frames(self._buf, self.t0, int(self._buf.numel()), length, f0, f1)
             self.n_frames = f1
         else:
-            out = torch.zeros((0, 2), dtype=torch.float32, device=self.ext.device)
+            out = torch.zeros((0, self._cols), dtype=torch.float32, device=self.ext.device)
         # the next frame's first sample; with hop > S it may not have arrived yet
-        keep = min(self.n_received, max(self.t0, self.n_frames * self.ext.hop - self.ext.span // 2))
+        keep = min(self.n_received, max(self.t0, self.n_frames * self.ext.hop - self._behind))
         if keep > self.t0:
             self._buf = self._buf[keep - self.t0:]
             self.t0 = keep
@@ -166,6 +177,110 @@ class F0Stream:
         self.ext._check_len(self.n_received)
         self.finished = True
         return self._range(self.computable(self.n_received, True), self.n_received)
+
+
+# ---- band aperiodicity: the reference's `codeap` columns ------------------------------------------------------------------------
+BAP_FLOOR = 1e-6
+
+
+def bap_bands(fs: float) -> List[Tuple[float, float]]:
+    """the band edges in Hz, one band per coded aperiodicity of the reference at this rate: B = floor(min(15000, fs / 2 - 3000) /
+    3000) bands (2 at 22.05 kHz, 1 at 16 kHz, 3 at 24 kHz, 5 at 44.1 / 48 kHz, none at 8 kHz - so 2 + B is run.sh's `stdim`), band
+    b spanning 3000 b + 1500 .. 3000 b + 4500 Hz around the reference's coding frequencies 3000 (b + 1)"""
+    n = int(math.floor(min(15000.0, fs / 2.0 - 3000.0) / 3000.0))
+    return [(3000.0 * b + 1500.0, 3000.0 * b + 4500.0) for b in range(max(n, 0))]
+
+
+def bap_taps(fs: float, bands: Sequence[Tuple[float, float]], n_taps: int = 255) -> np.ndarray:
+    """(B, n_taps) float64: one linear-phase band-pass (scipy.signal.firwin, Hamming) per (lo, hi) band in Hz"""
+    from scipy.signal import firwin
+    if n_taps < 1 or n_taps > _lib.BAP_MAX_TAPS or n_taps % 2 == 0:
+        raise ValueError(f"n_taps {n_taps}: need an odd count in 1 .. {_lib.BAP_MAX_TAPS}")
+    rows = []
+    for lo, hi in bands:
+        if not 0.0 < lo < hi < fs / 2.0:
+            raise ValueError(f"band ({lo}, {hi}) Hz: need 0 < lo < hi < fs / 2 = {fs / 2.0}")
+        rows.append(firwin(n_taps, [lo, hi], pass_zero=False, fs=fs))
+    return np.ascontiguousarray(np.asarray(rows, dtype=np.float64).reshape(len(rows), n_taps))
+
+
+def bap_reach(win: int, lag_hi: int, n_taps: int) -> int:
+    """S + 2 c, the samples a frame reads"""
+    return f0_span(win, lag_hi) + int(n_taps) - 1
+
+
+def bap_frames_ready(hop: int, win: int, lag_hi: int, n_taps: int, n_received: int, final: bool = False) -> int:
+    """frames of a signal that can be computed once n_received samples are there.  While it goes on, frame f is computable iff
+    f * hop - S // 2 + S + c <= n_received, c = (n_taps - 1) // 2; when it ends there (`final`), all F = 1 + n_received // hop."""
+    if final:
+        return frame_count(n_received, hop)
+    S = f0_span(win, lag_hi)
+    ahead = S - S // 2 + (int(n_taps) - 1) // 2
+    return 0 if n_received < ahead else 1 + (n_received - ahead) // hop
+
+
+class BandAperiodicityExtractor(F0Extractor):
+    """[F0, aperiodicity, coded aperiodicity of B bands in dB] of every frame (`torch.ops.swn.bap`, swn_bap): the F0 columns have
+    F0Extractor's bits, column 2 + b is 10 log10 of how far band b is from periodic at the frame's decided lag, clamped to
+    [floor, 1] (<= 0 dB), exactly 0.0 on unvoiced frames - the counterpart of the reference's `codeap` columns.
+
+    Definition (the contract; include/swn_hip.h states it in full, tests/bap_ref.py pins it).  With F0's W, L1, S, s = f hop -
+    S // 2 and the frame's decided lag tau*: B filters of T odd fp64 taps h_b, c = (T - 1) / 2; y_b[t] = sum_k h_b[k] x[t + c - k]
+    (one fp64 fma chain, k ascending; x = 0 outside the signal); s_b = f hop - (Wb + tau*) // 2; over j < Wb: d = sum (y_b[s_b + j]
+    - y_b[s_b + j + tau*])^2, e0 = sum y_b[s_b + j]^2, e1 = sum y_b[s_b + j + tau*]^2, each as 64 interleaved fma chains added in
+    order; ap = d / (e0 + e1), or 1.0 when that is 0; coded 10 log10(min(max(ap, floor), 1)).  A frame reads x[s - c .. s + S + c).
+    Frames are bit-identical under any batch, frame range, window or chunking.  The latency is S - S // 2 + c samples: 916
+    samples, 41.5 ms, at the shipped geometry with 255 taps.
+
+    This is not WORLD's D4C nor its `code_aperiodicity`: parity with them is neither claimed nor pinned.  Known limits: tau* is
+    an integer lag, so a band around frequency nu cannot go below about 1 - cos(pi nu / fs) for a period that falls between two
+    lags, and vibrato inside the window raises the value further (a shorter `band_win` recovers some of that: the default is 256).
+
+    `bands`: (lo, hi) edges in Hz, default `bap_bands(fs)` (ValueError when that is empty: below 12 kHz the reference codes no
+    band); `taps`: an explicit (B, T) float64 table instead of `bands` / `n_taps`; `band_win` is clipped to `win`."""
+
+    def __init__(self, fs: float, hop: int, minf0: float = 40.0, maxf0: float = 700.0, win: int = 1024, threshold: float = 0.1,
+                 bands: Optional[Sequence[Tuple[float, float]]] = None, n_taps: int = 255, band_win: int = 256,
+                 floor: float = BAP_FLOOR, device="cuda", taps=None) -> None:
+        super().__init__(fs, hop, minf0, maxf0, win, threshold, device)
+        if taps is None:
+            self.bands = list(bap_bands(self.fs) if bands is None else bands)
+            if not self.bands:
+                raise ValueError(f"no aperiodicity band at fs {fs}: pass `bands`")
+            taps = bap_taps(self.fs, self.bands, n_taps)
+        else:
+            self.bands = None
+        table = np.ascontiguousarray(np.asarray(taps, dtype=np.float64))
+        if table.ndim != 2 or not 1 <= table.shape[0] <= _lib.BAP_MAX_BANDS:
+            raise ValueError(f"taps of shape {table.shape}: need (B, T) with 1 <= B <= {_lib.BAP_MAX_BANDS}")
+        if not (1 <= table.shape[1] <= _lib.BAP_MAX_TAPS and table.shape[1] % 2 == 1):
+            raise ValueError(f"{table.shape[1]} taps: need an odd count in 1 .. {_lib.BAP_MAX_TAPS}")
+        if not 0.0 < float(floor) < 1.0:
+            raise ValueError(f"floor {floor} outside (0, 1)")
+        if int(band_win) < _lib.F0_MIN_WIN:
+            raise ValueError(f"band_win {band_win} below {_lib.F0_MIN_WIN}")
+        self.n_bands, self.n_taps = int(table.shape[0]), int(table.shape[1])
+        self.band_win, self.floor = min(int(band_win), self.win), float(floor)
+        self.reach = bap_reach(self.win, self.lag_hi, self.n_taps)
+        self.taps = torch.from_numpy(table).to(self.device)
+        self._op = ops.bap_impl
+
+    def _run(self, buf, t0s, n_avails, lens, f0s, f1s) -> torch.Tensor:
+        return self._op(buf, self.taps, t0s, n_avails, lens, f0s, f1s, self.fs, self.hop, self.win, self.lag_lo, self.lag_hi,
+                        self.threshold, self.band_win, self.floor)
+
+
+class BapStream(F0Stream):
+    """F0Stream for a BandAperiodicityExtractor: frames of 2 + B values, each c = (n_taps - 1) // 2 samples later than F0's, and
+    a tail that starts c samples earlier: at n_frames * hop - S // 2 - c."""
+
+    def __init__(self, extractor: BandAperiodicityExtractor) -> None:
+        super().__init__(extractor)
+        self._behind = extractor.span // 2 + (extractor.n_taps - 1) // 2
+        self._cols = 2 + extractor.n_bands
+
+    def computable(self, n_received: int, final: bool = False) -> int:
+        return bap_frames_ready(self.ext.hop, self.ext.win, self.ext.lag_hi, self.ext.n_taps, n_received, final)
 
 
 def uv_lf0(f0_column, frame_rate: int) -> np.ndarray:
