@@ -22,6 +22,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "swn_frame_entry.hpp"
 #include "swn_geom.hpp"
 
 #pragma clang fp contract(off)      // the chains are explicit fma calls; nothing else may be fused or re-associated
@@ -33,7 +34,6 @@ constexpr int F0_WAVES = F0_THREADS / 64;
 constexpr int F0_SIDE = 5;                              // neighbouring lags per lane
 constexpr int F0_GROUP = 64 * F0_SIDE;                  // lags per wave and round
 constexpr int F0_MAX_SPAN = SWN_F0_MAX_WIN + SWN_F0_MAX_LAG;
-constexpr int F0_MAX_LEN = 1 << 30;
 constexpr long long F0_MAX_FRAMES = 1LL << 24;          // frames (= blocks) per call
 
 struct F0Entry {
@@ -327,23 +327,9 @@ int f0_check(const char* who, double fs, int hop, int win, int lag_lo, int lag_h
         o.wav = nullptr; o.out = nullptr; o.t0 = o.n_avail = o.len = o.f0 = o.f1 = 0; o.blk0 = (int)blocks;
         if (i >= n_entries) continue;
         const swn_logmel_entry& e = entries_host[i];
-        if (e.reserved != 0) { snprintf(msg, sizeof msg, "entry %d: reserved field is not 0", i); return fail(msg); }
-        if (e.f0 < 0 || e.f1 < e.f0) { snprintf(msg, sizeof msg, "entry %d: frame range [%d, %d)", i, e.f0, e.f1); return fail(msg); }
-        if (e.len != -1 && (e.len < 1 || e.len > F0_MAX_LEN)) {
-            snprintf(msg, sizeof msg, "entry %d: length %d, need 1 <= len <= 2^30 (or -1 while unknown)", i, e.len);
-            return fail(msg);
-        }
-        if (e.t0 < 0 || e.n_avail < 0 || (long long)e.t0 + e.n_avail > F0_MAX_LEN ||
-            (e.len != -1 && (long long)e.t0 + e.n_avail > e.len)) {
-            snprintf(msg, sizeof msg, "entry %d: window [%d, %d + %d) is not inside the signal", i, e.t0, e.t0, e.n_avail);
-            return fail(msg);
-        }
-        if (e.f1 == e.f0) continue;
-        if (!e.wav_dev || !e.out_dev) { snprintf(msg, sizeof msg, "entry %d: null pointer", i); return fail(msg); }
-        if (e.len != -1 && e.f1 > 1 + e.len / hop) {
-            snprintf(msg, sizeof msg, "entry %d: f1 = %d, a signal of %d samples has %d frames", i, e.f1, e.len, 1 + e.len / hop);
-            return fail(msg);
-        }
+        const int rc = frame_entry_check(e, i, hop, 1, "1 <= len", true, fail);
+        if (rc == FE_EMPTY) continue;
+        if (rc != SWN_OK) return rc;
         // samples the range touches: frame f covers f hop - S / 2 + (-c .. S - 1 + c); those outside [0, len) are zeros
         const long long end = (long long)e.t0 + e.n_avail;
         const long long lo = (long long)e.f0 * hop - S / 2 - c, hi = (long long)(e.f1 - 1) * hop - S / 2 + S - 1 + c;

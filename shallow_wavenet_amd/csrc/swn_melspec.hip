@@ -53,6 +53,7 @@
 // not pinned: the library is absent).  It is the cepstrum of the short-time spectrum, not of WORLD's cheaptrick envelope.
 // The table of swn_mcep: cos, window, then G padded.  mcep_kernel below says how the block works.
 #include <hip/hip_runtime.h>
+#include "swn_frame_entry.hpp"
 #include "swn_geom.hpp"
 #include "swn_lowcut.hpp"
 #include "swn_mma.hpp"
@@ -64,7 +65,7 @@ namespace {
 
 constexpr int LM_THREADS = 256;
 constexpr int LM_FR = 16;          // frames per tile = MFMA rows
-constexpr int LM_MAX_LEN = 1 << 30;   // 2 (len - 1) - p stays inside int
+constexpr int LM_MAX_LEN = FE_MAX_LEN;   // 2^30: 2 (len - 1) - p stays inside int
 
 struct LmEntry {
     const float* wav;   // sample t0
@@ -145,23 +146,9 @@ int lm_check_entries(int n, int hop, const swn_logmel_entry* en, int n_entries, 
     long long nt = 0;
     for (int i = 0; i < n_entries; ++i) {
         const swn_logmel_entry& e = en[i];
-        if (e.reserved != 0) { snprintf(msg, sizeof msg, "entry %d: reserved field is not 0", i); return lm_fail(msg); }
-        if (e.f0 < 0 || e.f1 < e.f0) { snprintf(msg, sizeof msg, "entry %d: frame range [%d, %d)", i, e.f0, e.f1); return lm_fail(msg); }
-        if (e.len != -1 && (e.len <= n / 2 || e.len > LM_MAX_LEN)) {
-            snprintf(msg, sizeof msg, "entry %d: length %d, need n_fft / 2 < len <= 2^30 (or -1 while unknown)", i, e.len);
-            return lm_fail(msg);
-        }
-        if (e.t0 < 0 || e.n_avail < 0 || (long long)e.t0 + e.n_avail > LM_MAX_LEN ||
-            (e.len != -1 && (long long)e.t0 + e.n_avail > e.len)) {
-            snprintf(msg, sizeof msg, "entry %d: window [%d, %d + %d) is not inside the signal", i, e.t0, e.t0, e.n_avail);
-            return lm_fail(msg);
-        }
-        if (e.f1 == e.f0) continue;
-        if (need_pointers && (!e.wav_dev || !e.out_dev)) { snprintf(msg, sizeof msg, "entry %d: null pointer", i); return lm_fail(msg); }
-        if (e.len != -1 && e.f1 > 1 + e.len / hop) {
-            snprintf(msg, sizeof msg, "entry %d: f1 = %d, a signal of %d samples has %d frames", i, e.f1, e.len, 1 + e.len / hop);
-            return lm_fail(msg);
-        }
+        const int rc = frame_entry_check(e, i, hop, n / 2 + 1, "n_fft / 2 < len", need_pointers, lm_fail);
+        if (rc == FE_EMPTY) continue;
+        if (rc != SWN_OK) return rc;
         // samples the range touches: frame f covers lo .. hi = f hop - n / 2 + (0 .. n - 1); the left reflection of a frame
         // with lo < 0 reaches sample -lo, the right reflection of hi >= len comes back down to 2 (len - 1) - hi
         const long long lo0 = (long long)e.f0 * hop - n / 2, hi1 = (long long)(e.f1 - 1) * hop - n / 2 + n - 1;

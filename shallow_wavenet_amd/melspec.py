@@ -157,8 +157,51 @@ def _padded_batch(ext, wavs, lengths: Optional[Sequence[int]]) -> Tuple[torch.Te
     return batch, lens
 
 
-class LogMelExtractor:
-    """holds the tables on `device`; a call computes the features of a batch of waveforms."""
+def _check_reflect_len(n_fft: int, length: int) -> None:
+    if length <= n_fft // 2:
+        raise ValueError(f"n_fft {n_fft} needs signals longer than {n_fft // 2} samples (reflect padding), got {length}")
+
+
+def _per_row(v, rows: int) -> List[int]:
+    return [int(v)] * rows if isinstance(v, (int, np.integer)) else [int(x) for x in v]
+
+
+class _FrameExtractor:
+    """what LogMelExtractor, MelCepstrumExtractor and pitch.F0Extractor share: the one-shot call and the frames of a partial
+    buffer, both as one call of the frame-range contract ops._frame_entries states.  A subclass's constructor sets `hop`, `device`
+    and `_op`; it supplies `_check_len(length)` (ValueError for a signal too short) and `_run(buf, t0s, n_avails, lens, f0s,
+    f1s, *more)`, which hands `self._op` the contract's lists with the subclass's own arguments around them."""
+
+    def frame_count(self, length: int) -> int:
+        return frame_count(length, self.hop)
+
+    def _whole(self, wavs, lengths, *more) -> torch.Tensor:
+        batch, lens = _padded_batch(self, wavs, lengths)
+        R = len(lens)
+        return self._run(batch, [0] * R, lens, lens, [0] * R, [self.frame_count(n) for n in lens], *more)
+
+    def _partial(self, wav, t0, n_avail, length, f0, f1, *more) -> torch.Tensor:
+        one = wav.dim() == 1
+        buf = (wav[None] if one else wav).to(self.device, torch.float32).contiguous()
+        out = self._run(buf, *[_per_row(v, buf.shape[0]) for v in (t0, n_avail, length, f0, f1)], *more)
+        return out[0] if one else out
+
+    def __call__(self, wavs, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """wavs: a padded (R, S) batch with `lengths` (default: S for every row), one 1-D signal, or a list of R 1-D signals
+        of their own lengths -> (R, F_max, columns), row r holding frame_count(lengths[r]) frames and zeros after them."""
+        return self._whole(wavs, lengths)
+
+    def frames(self, wav: torch.Tensor, t0: Union[int, Sequence[int]], n_avail: Union[int, Sequence[int]],
+               length: Union[int, Sequence[int]], f0: Union[int, Sequence[int]], f1: Union[int, Sequence[int]]) -> torch.Tensor:
+        """frames [f0, f1) from a partial buffer: `wav` (S,) or (R, S) holds the samples [t0, t0 + n_avail) of each signal,
+        whose total length is `length` or -1 while it is not known -> (f1 - f0, columns) or (R, max(f1 - f0), columns).  A
+        range whose in-signal samples (for log-mel and mel-cepstrum the reflected ones included) are not all in the buffer is
+        refused."""
+        return self._partial(wav, t0, n_avail, length, f0, f1)
+
+
+class LogMelExtractor(_FrameExtractor):
+    """holds the tables on `device`; a call computes the features of a batch of waveforms: n_mels columns."""
 
     def __init__(self, fs: float, n_fft: int, hop: int, n_mels: int, fmin: float = 0.0, fmax: Optional[float] = None,
                  floor: float = 1e-5, device="cuda") -> None:
@@ -174,34 +217,21 @@ class LogMelExtractor:
         self._table = torch.from_numpy(table).to(self.device)
         self._op = ops.logmel_impl
 
-    def frame_count(self, length: int) -> int:
-        return frame_count(length, self.hop)
-
     def _check_len(self, length: int) -> None:
-        if length <= self.n_fft // 2:
-            raise ValueError(f"n_fft {self.n_fft} needs signals longer than {self.n_fft // 2} samples (reflect padding), "
-                             f"got {length}")
+        _check_reflect_len(self.n_fft, length)
+
+    def _run(self, buf, t0s, n_avails, lens, f0s, f1s, linear=False) -> torch.Tensor:
+        return self._op(buf, self._table, self.bank, t0s, n_avails, lens, f0s, f1s, self.n_fft, self.hop, self.floor, bool(linear))
 
     def __call__(self, wavs, lengths: Optional[Sequence[int]] = None, linear: bool = False) -> torch.Tensor:
-        """wavs: a padded (R, S) batch with `lengths` (default: S for every row), one 1-D signal, or a list of R 1-D signals
-        of their own lengths -> (R, F_max, n_mels), row r holding frame_count(lengths[r]) frames and zeros after them."""
-        batch, lens = _padded_batch(self, wavs, lengths)
-        R = len(lens)
-        return self._op(batch, self._table, self.bank, [0] * R, lens, lens, [0] * R, [self.frame_count(n) for n in lens],
-                        self.n_fft, self.hop, self.floor, bool(linear))
+        """as _FrameExtractor.__call__ -> (R, F_max, n_mels); `linear`: the mel amplitudes themselves, not their logarithms"""
+        return self._whole(wavs, lengths, linear)
 
     def frames(self, wav: torch.Tensor, t0: Union[int, Sequence[int]], n_avail: Union[int, Sequence[int]],
                length: Union[int, Sequence[int]], f0: Union[int, Sequence[int]], f1: Union[int, Sequence[int]],
                linear: bool = False) -> torch.Tensor:
-        """frames [f0, f1) from a partial buffer: `wav` (S,) or (R, S) holds the samples [t0, t0 + n_avail) of each signal,
-        whose total length is `length` or -1 while it is not known -> (f1 - f0, n_mels) or (R, max(f1 - f0), n_mels).  A
-        range whose samples (the reflected ones included) are not all in the buffer is refused."""
-        one = wav.dim() == 1
-        buf = (wav[None] if one else wav).to(self.device, torch.float32).contiguous()
-        lst = lambda v: [int(v)] * buf.shape[0] if isinstance(v, (int, np.integer)) else [int(x) for x in v]
-        out = self._op(buf, self._table, self.bank, lst(t0), lst(n_avail), lst(length), lst(f0), lst(f1), self.n_fft, self.hop,
-                       self.floor, bool(linear))
-        return out[0] if one else out
+        """as _FrameExtractor.frames -> (f1 - f0, n_mels) or (R, max(f1 - f0), n_mels)"""
+        return self._partial(wav, t0, n_avail, length, f0, f1, linear)
 
 
 # ---- mel-cepstrum --------------------------------------------------------------------------------------------------------
@@ -254,7 +284,7 @@ def mcep_tables(n_fft: int, order: int, alpha: float) -> np.ndarray:
     return table
 
 
-class MelCepstrumExtractor:
+class MelCepstrumExtractor(_FrameExtractor):
     """Mel-cepstra of the short-time spectra the log-mel features are computed from, on the device (`torch.ops.swn.mcep`,
     swn_mcep): for corpus statistics - the mean over a corpus is what the noise-shaping stages and `post_filter=` build their
     MLSA filter from - and as a conditioning feature type.
@@ -293,32 +323,44 @@ class MelCepstrumExtractor:
         self._table = torch.from_numpy(table).to(self.device)
         self._op = ops.mcep_impl
 
-    def frame_count(self, length: int) -> int:
-        return frame_count(length, self.hop)
+    def _check_len(self, length: int) -> None:
+        _check_reflect_len(self.n_fft, length)
 
-    _check_len = LogMelExtractor._check_len
-
-    def __call__(self, wavs, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
-        """wavs as LogMelExtractor takes them -> (R, F_max, order + 1), row r holding frame_count(lengths[r]) frames and
-        zeros after them."""
-        batch, lens = _padded_batch(self, wavs, lengths)
-        R = len(lens)
-        return self._op(batch, self._table, [0] * R, lens, lens, [0] * R, [self.frame_count(n) for n in lens], self.n_fft,
-                        self.hop, self.order, self.floor)
-
-    def frames(self, wav: torch.Tensor, t0: Union[int, Sequence[int]], n_avail: Union[int, Sequence[int]],
-               length: Union[int, Sequence[int]], f0: Union[int, Sequence[int]], f1: Union[int, Sequence[int]]) -> torch.Tensor:
-        """frames [f0, f1) from a partial buffer, as LogMelExtractor.frames -> (f1 - f0, order + 1) or
-        (R, max(f1 - f0), order + 1)."""
-        one = wav.dim() == 1
-        buf = (wav[None] if one else wav).to(self.device, torch.float32).contiguous()
-        lst = lambda v: [int(v)] * buf.shape[0] if isinstance(v, (int, np.integer)) else [int(x) for x in v]
-        out = self._op(buf, self._table, lst(t0), lst(n_avail), lst(length), lst(f0), lst(f1), self.n_fft, self.hop, self.order,
-                       self.floor)
-        return out[0] if one else out
+    def _run(self, buf, t0s, n_avails, lens, f0s, f1s) -> torch.Tensor:
+        return self._op(buf, self._table, t0s, n_avails, lens, f0s, f1s, self.n_fft, self.hop, self.order, self.floor)
 
 
 # ---- stage-1 low cut -----------------------------------------------------------------------------------------------------
+class _Slots:
+    """the session slots of a LowCut or a Resampler: which of the `capacity` are free (`free`, sorted); `noun` is what the
+    "the ... is full" message names"""
+
+    def __init__(self, capacity: int, noun: str) -> None:
+        self.capacity, self.noun, self.free = capacity, noun, list(range(capacity))
+
+    def open(self, slot: Optional[int] = None) -> int:
+        if slot is None:
+            if not self.free:
+                raise RuntimeError(f"the {self.noun} is full: all {self.capacity} slots are open")
+            slot = self.free[0]
+        slot = int(slot)
+        if slot not in self.free:
+            raise RuntimeError(f"slot {slot} is not free (capacity {self.capacity})")
+        self.free.remove(slot)
+        return slot
+
+    def need_open(self, slot: int) -> None:
+        if slot in self.free or not 0 <= slot < self.capacity:
+            raise RuntimeError(f"slot {slot} is not open")
+
+    def close(self, slot: int) -> int:
+        slot = int(slot)
+        self.need_open(slot)
+        self.free.append(slot)
+        self.free.sort()
+        return slot
+
+
 class LowCut:
     """the causal FIR high-pass of run.sh stage 1 (`dsp.low_cut_taps(fs, cutoff)`: 255 taps) on the device, with the taps held
     there as fp64 and `capacity` session slots; the definition is in the module docstring.
@@ -345,7 +387,8 @@ class LowCut:
         self.state_floats = self.n_taps - 1
         self._taps = torch.from_numpy(self.taps).to(self.device)
         self._state = torch.zeros(max(1, capacity * self.state_floats), dtype=torch.float32, device=self.device)
-        self._free = list(range(capacity))
+        self._slots = _Slots(capacity, "low cut")
+        self._free = self._slots.free
         self._reset = set()                                   # opened slots that have not run yet
         self._op = ops.lowcut_chunk_impl
 
@@ -366,33 +409,20 @@ class LowCut:
     # ------------------------------------------------------------------ sessions
     def open(self, slot: Optional[int] = None) -> int:
         """claim a slot (the lowest free one when slot is None); its session starts from zero history."""
-        if slot is None:
-            if not self._free:
-                raise RuntimeError(f"the low cut is full: all {self.capacity} slots are open")
-            slot = self._free[0]
-        slot = int(slot)
-        if slot not in self._free:
-            raise RuntimeError(f"slot {slot} is not free (capacity {self.capacity})")
-        self._free.remove(slot)
+        slot = self._slots.open(slot)
         self._reset.add(slot)
         return slot
 
     def close(self, slot: int) -> None:
         """free the slot; a session opened in it later starts from zero history."""
-        slot = int(slot)
-        if slot in self._free or not 0 <= slot < self.capacity:
-            raise RuntimeError(f"slot {slot} is not open")
-        self._reset.discard(slot)
-        self._free.append(slot)
-        self._free.sort()
+        self._reset.discard(self._slots.close(slot))
 
     def run(self, chunks: Mapping[int, torch.Tensor]) -> Dict[int, torch.Tensor]:
         """the next chunk (1-D samples, host or device, any length) of each open slot's session, all in one device call ->
         {slot: filtered fp32 chunk (1-D, views of one dense output)}."""
         slots = [int(s) for s in chunks]
         for s in slots:
-            if s in self._free or not 0 <= s < self.capacity:
-                raise RuntimeError(f"slot {s} is not open")
+            self._slots.need_open(s)
         if not slots:
             return {}
         xs = [torch.as_tensor(chunks[s]) for s in chunks]
@@ -488,7 +518,8 @@ class Resampler:
         self.state_floats = self.Q - 1
         self._table = torch.from_numpy(self.table.reshape(-1)).to(self.device)
         self._state = torch.zeros(max(1, capacity * self.state_floats), dtype=torch.float32, device=self.device)
-        self._free = list(range(capacity))
+        self._slots = _Slots(capacity, "resampler")
+        self._free = self._slots.free
         self._at: Dict[int, List[int]] = {}                   # open slot -> [inputs received, outputs returned, ended]
         self._op = ops.resample_chunk_impl
 
@@ -518,25 +549,13 @@ class Resampler:
     # ------------------------------------------------------------------ sessions
     def open(self, slot: Optional[int] = None) -> int:
         """claim a slot (the lowest free one when slot is None); its session starts from zero history."""
-        if slot is None:
-            if not self._free:
-                raise RuntimeError(f"the resampler is full: all {self.capacity} slots are open")
-            slot = self._free[0]
-        slot = int(slot)
-        if slot not in self._free:
-            raise RuntimeError(f"slot {slot} is not free (capacity {self.capacity})")
-        self._free.remove(slot)
+        slot = self._slots.open(slot)
         self._at[slot] = [0, 0, False]
         return slot
 
     def close(self, slot: int) -> None:
         """free the slot; a session opened in it later starts from zero history."""
-        slot = int(slot)
-        if slot not in self._at:
-            raise RuntimeError(f"slot {slot} is not open")
-        del self._at[slot]
-        self._free.append(slot)
-        self._free.sort()
+        del self._at[self._slots.close(slot)]
 
     def run(self, chunks: Mapping[int, torch.Tensor], finish: Sequence[int] = ()) -> Dict[int, torch.Tensor]:
         """the next chunk (1-D samples at fs_in, host or device, any length) of each open slot's session, all in one device call
@@ -548,8 +567,7 @@ class Resampler:
             raise ValueError("a slot is named twice in finish")
         slots = [int(s) for s in chunks] + [s for s in ending if s not in {int(k) for k in chunks}]
         for s in slots:
-            if s not in self._at:
-                raise RuntimeError(f"slot {s} is not open")
+            self._slots.need_open(s)
             if self._at[s][2]:
                 raise RuntimeError(f"the signal of slot {s} has ended: no samples can be run after it finished")
         if not slots:
@@ -607,7 +625,59 @@ def keep_from(n_fft: int, hop: int, t0: int, n_frames: int) -> int:
     return max(t0, n_frames * hop - n_fft // 2 - 1)
 
 
-class LogMelStream:
+class _FrameStream:
+    """what LogMelStream, pitch.F0Stream and pitch.BapStream share: one signal's frames as its samples arrive.  `push` returns
+    the frames that became computable, `finish` the rest; `_buf` holds the samples from the absolute index `t0` on, and after
+    every call only the tail that later frames still read.  A subclass supplies `computable(n_received, final=False)`, its
+    streaming rule, and `_keep()`, the absolute index of the first sample it still needs; `cols` is a frame's width and `more`
+    what the extractor's `frames` takes after the range."""
+
+    def __init__(self, extractor: _FrameExtractor, cols: int, *more) -> None:
+        self.ext, self._cols, self._more = extractor, cols, more
+        self._buf = torch.zeros(0, dtype=torch.float32, device=extractor.device)
+        self.t0 = 0                 # absolute index of _buf[0]
+        self.n_received = 0
+        self.n_frames = 0           # frames returned so far
+        self.finished = False
+
+    def _take(self, s: torch.Tensor) -> None:
+        self._buf = torch.cat([self._buf, s])
+        self.n_received += int(s.numel())
+
+    def _end(self) -> None:
+        """what `finish` does before the last frames: the signal must be long enough"""
+        self.ext._check_len(self.n_received)
+
+    def _range(self, f1: int, length: int) -> torch.Tensor:
+        f0 = self.n_frames
+        if f1 > f0:
+            out = self.ext.frames(self._buf, self.t0, int(self._buf.numel()), length, f0, f1, *self._more)
+            self.n_frames = f1
+        else:
+            out = torch.zeros((0, self._cols), dtype=torch.float32, device=self.ext.device)
+        keep = self._keep()
+        if keep > self.t0:
+            self._buf = self._buf[keep - self.t0:]
+            self.t0 = keep
+        return out
+
+    def push(self, samples) -> torch.Tensor:
+        """append 1-D samples -> (k, columns) new frames, k >= 0"""
+        if self.finished:
+            raise RuntimeError("the stream is finished")
+        self._take(torch.as_tensor(samples).reshape(-1).to(self.ext.device, torch.float32))
+        return self._range(self.computable(self.n_received), -1)
+
+    def finish(self) -> torch.Tensor:
+        """the signal ends here -> the remaining frames up to F = 1 + n_received // hop"""
+        if self.finished:
+            raise RuntimeError("the stream is finished")
+        self._end()
+        self.finished = True
+        return self._range(self.computable(self.n_received, True), self.n_received)
+
+
+class LogMelStream(_FrameStream):
     """one signal's features as its samples arrive: `push` returns the frames that became computable, `finish` the rest
     (those that read the reflected end).  Only the tail of the signal that later frames still read is kept.  The
     concatenation of everything returned is bit-identical to the extractor's one-shot call on the whole signal.  With
@@ -619,7 +689,7 @@ class LogMelStream:
 
     def __init__(self, extractor: LogMelExtractor, linear: bool = False, low_cut: Optional[LowCut] = None,
                  resample: Optional[Resampler] = None) -> None:
-        self.ext, self.linear = extractor, bool(linear)
+        self.linear = bool(linear)
         self.low_cut, self._cut_slot = low_cut, None
         self.resample, self._res_slot = resample, None
         if low_cut is not None:
@@ -634,63 +704,33 @@ class LogMelStream:
                 if resample is not None:
                     resample.close(self._res_slot)
                 raise
-        self._buf = torch.zeros(0, dtype=torch.float32, device=extractor.device)
-        self.t0 = 0                 # absolute index of _buf[0]
-        self.n_received = 0
-        self.n_frames = 0           # frames returned so far
-        self.finished = False
+        super().__init__(extractor, extractor.n_mels, self.linear)
 
-    def computable(self, n_received: int) -> int:
+    def computable(self, n_received: int, final: bool = False) -> int:
         """frames whose samples have all arrived: frame 0 reads up to sample n_fft / 2 (the left reflection), frame
-        f >= 1 up to f hop + n_fft / 2 - 1"""
-        return frames_ready(self.ext.n_fft, self.ext.hop, n_received)
+        f >= 1 up to f hop + n_fft / 2 - 1; with `final`, all of a signal that ends there"""
+        return frames_ready(self.ext.n_fft, self.ext.hop, n_received, final)
 
-    def _drop_consumed(self) -> None:
-        keep = keep_from(self.ext.n_fft, self.ext.hop, self.t0, self.n_frames)
-        if keep > self.t0:
-            self._buf = self._buf[keep - self.t0:]
-            self.t0 = keep
+    def _keep(self) -> int:
+        return keep_from(self.ext.n_fft, self.ext.hop, self.t0, self.n_frames)
 
-    def _range(self, f1: int, length: int) -> torch.Tensor:
-        f0 = self.n_frames
-        if f1 <= f0:
-            return torch.zeros((0, self.ext.n_mels), dtype=torch.float32, device=self.ext.device)
-        out = self.ext.frames(self._buf, self.t0, int(self._buf.numel()), length, f0, f1, self.linear)
-        self.n_frames = f1
-        self._drop_consumed()
-        return out
-
-    def push(self, samples) -> torch.Tensor:
-        """append 1-D samples -> (k, n_mels) new frames, k >= 0"""
-        if self.finished:
-            raise RuntimeError("the stream is finished")
-        s = torch.as_tensor(samples).reshape(-1).to(self.ext.device, torch.float32)
-        if self.resample is not None:
+    def _take(self, s: torch.Tensor, resampled: bool = False) -> None:
+        """pushed samples: through the resampler (unless they are its own last outputs) and the low cut, into the buffer"""
+        if self.resample is not None and not resampled:
             s = self.resample.run({self._res_slot: s})[self._res_slot]
-        self._take(s)
-        return self._range(self.computable(self.n_received), -1)
-
-    def _take(self, s: torch.Tensor) -> None:
-        """samples at the extractor's fs: through the low cut, into the buffer"""
         if self.low_cut is not None:
             s = self.low_cut.run({self._cut_slot: s})[self._cut_slot]
-        self._buf = torch.cat([self._buf, s])
-        self.n_received += int(s.numel())
+        super()._take(s)
 
-    def finish(self) -> torch.Tensor:
-        """the signal ends here -> the remaining frames up to F = 1 + n_received // hop"""
-        if self.finished:
-            raise RuntimeError("the stream is finished")
+    def _end(self) -> None:
         if self.resample is not None:
             got, given, _ = self.resample._at[self._res_slot]
             self.ext._check_len(self.n_received + self.resample.ready(got, True) - given)
-            self._take(self.resample.run({}, finish=[self._res_slot])[self._res_slot])
+            self._take(self.resample.run({}, finish=[self._res_slot])[self._res_slot], resampled=True)
             self.resample.close(self._res_slot)
-        self.ext._check_len(self.n_received)
-        self.finished = True
+        super()._end()
         if self.low_cut is not None:
             self.low_cut.close(self._cut_slot)
-        return self._range(frames_ready(self.ext.n_fft, self.ext.hop, self.n_received, True), self.n_received)
 
 
 # ---- many signals at once ------------------------------------------------------------------------------------------------

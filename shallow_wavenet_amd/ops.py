@@ -1481,16 +1481,63 @@ class LaplaceLossFunction(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------ log-mel features
+def _stft_check(op: str, n_fft: int, hop: int, floor: float, own: Tuple[bool, str]) -> None:
+    """the n_fft / hop / floor rules swn_logmel and swn_mcep share, as messages, with the op's `own` rule (holds, message)
+    between hop's and floor's"""
+    if n_fft % 32 != 0 or not 32 <= n_fft <= _lib.SPECTRAL_MAX_FFT:
+        raise RuntimeError(f"{op}: n_fft {n_fft} is not a multiple of 32 in [32, {_lib.SPECTRAL_MAX_FFT}]")
+    if not 1 <= hop <= n_fft:
+        raise RuntimeError(f"{op}: hop {hop} outside [1, n_fft = {n_fft}]")
+    if not own[0]:
+        raise RuntimeError(f"{op}: {own[1]}")
+    if not floor > 0.0:
+        raise RuntimeError(f"{op}: floor {floor} must be > 0")
+
+
+def _tables_check(op: str, tables: torch.Tensor, need: int, dev, of: str) -> None:
+    if tables.device != dev or tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != need:
+        raise RuntimeError(f"{op}: tables must be {need} contiguous fp32 values on the device of the {of}")
+
+
+def _fmax(f0s: List[int], f1s: List[int]) -> int:
+    return max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
+
+
+def _frames_fake(wav, f0s, f1s, cols: int) -> torch.Tensor:
+    """the output of a frame-range op for shape inference"""
+    return wav.new_empty((wav.shape[0], _fmax(f0s, f1s), cols), dtype=torch.float32)
+
+
+def _frame_entries(op: str, wav: torch.Tensor, t0s: List[int], n_avails: List[int], lens: List[int], f0s: List[int],
+                   f1s: List[int], cols: int):
+    """the contract of logmel, mcep, f0 and bap: row r of the contiguous fp32 buffer wav (R, S) holds the samples [t0s[r],
+    t0s[r] + n_avails[r]) of signal r, whose total length is lens[r] (-1: not known yet); the call computes its frames [f0s[r],
+    f1s[r]).  Checks the buffer and the lists -> (the zeroed (R, max(f1 - f0), cols) output, the launch groups [(LogMelEntry
+    table, n), ...] of at most LOGMEL_MAX_ENTRIES rows each, in row order)."""
+    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
+        raise RuntimeError(f"{op} needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
+    R, S = wav.shape
+    if not (len(t0s) == len(n_avails) == len(lens) == len(f0s) == len(f1s) == R):
+        raise RuntimeError(f"{op}: t0s, n_avails, lens, f0s and f1s must have one entry per row")
+    if any(not 0 <= na <= S for na in n_avails):
+        raise RuntimeError(f"{op}: a row has more samples available than the buffer's {S} columns")
+    fmax = _fmax(f0s, f1s)
+    out = torch.zeros((R, fmax, cols), dtype=torch.float32, device=wav.device)
+    esz, osz = wav.element_size() * S, out.element_size() * fmax * cols
+    groups = []
+    for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
+        r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
+        groups.append(((_lib.LogMelEntry * (r1 - r0))(*[
+            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
+                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
+            for r in range(r0, r1)]), r1 - r0))
+    return out, groups
+
+
 def _logmel_check(n_fft: int, hop: int, n_mels: int, floor: float) -> None:
     """the size rules of swn_logmel as messages (the library itself answers SWN_E_BADARG)."""
-    if n_fft % 32 != 0 or not 32 <= n_fft <= _lib.SPECTRAL_MAX_FFT:
-        raise RuntimeError(f"logmel: n_fft {n_fft} is not a multiple of 32 in [32, {_lib.SPECTRAL_MAX_FFT}]")
-    if not 1 <= hop <= n_fft:
-        raise RuntimeError(f"logmel: hop {hop} outside [1, n_fft = {n_fft}]")
-    if not 1 <= n_mels <= _lib.LOGMEL_MAX_MELS:
-        raise RuntimeError(f"logmel: n_mels {n_mels} outside [1, {_lib.LOGMEL_MAX_MELS}]")
-    if not floor > 0.0:
-        raise RuntimeError(f"logmel: floor {floor} must be > 0")
+    _stft_check("logmel", n_fft, hop, floor, (1 <= n_mels <= _lib.LOGMEL_MAX_MELS,
+                                              f"n_mels {n_mels} outside [1, {_lib.LOGMEL_MAX_MELS}]"))
 
 
 def logmel_impl(wav: torch.Tensor, tables: torch.Tensor, bank: List[int], t0s: List[int], n_avails: List[int],
@@ -1504,30 +1551,14 @@ def logmel_impl(wav: torch.Tensor, tables: torch.Tensor, bank: List[int], t0s: L
     dev = wav.device
     n_mels = len(bank)
     _logmel_check(n_fft, hop, n_mels, floor)
-    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
-        raise RuntimeError(f"logmel needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
-    R, S = wav.shape
-    if not (len(t0s) == len(n_avails) == len(lens) == len(f0s) == len(f1s) == R):
-        raise RuntimeError("logmel: t0s, n_avails, lens, f0s and f1s must have one entry per row")
-    if any(not 0 <= na <= S for na in n_avails):
-        raise RuntimeError(f"logmel: a row has more samples available than the buffer's {S} columns")
-    need = Lb.swn_logmel_table_floats(n_fft, n_mels)
-    if tables.device != dev or tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != need:
-        raise RuntimeError(f"logmel: tables must be {need} contiguous fp32 values on the device of the waveforms")
-    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
-    out = torch.zeros((R, fmax, n_mels), dtype=torch.float32, device=dev)
+    out, groups = _frame_entries("logmel", wav, t0s, n_avails, lens, f0s, f1s, n_mels)
+    _tables_check("logmel", tables, Lb.swn_logmel_table_floats(n_fft, n_mels), dev, "waveforms")
     bank_c = (ctypes.c_int32 * n_mels)(*[int(b) for b in bank])
-    esz, osz = wav.element_size() * S, out.element_size() * fmax * n_mels
-    for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
-        r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
-        table = (_lib.LogMelEntry * (r1 - r0))(*[
-            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
-                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
-            for r in range(r0, r1)])
-        nb = Lb.swn_logmel_work_bytes(n_fft, hop, table, r1 - r0)
+    for table, n in groups:
+        nb = Lb.swn_logmel_work_bytes(n_fft, hop, table, n)
         work = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=dev)
         with _on(dev):
-            _lib.check(Lb.swn_logmel(n_fft, hop, n_mels, float(floor), int(bool(linear)), _ptr(tables), bank_c, table, r1 - r0,
+            _lib.check(Lb.swn_logmel(n_fft, hop, n_mels, float(floor), int(bool(linear)), _ptr(tables), bank_c, table, n,
                                      _ptr(work), _stream(dev)), "logmel")
     return out
 
@@ -1538,20 +1569,13 @@ logmel = custom_op("swn::logmel", mutates_args=())(logmel_impl)
 @logmel.register_fake
 def _(wav, tables, bank, t0s, n_avails, lens, f0s, f1s, n_fft, hop, floor, linear):
     _logmel_check(n_fft, hop, len(bank), floor)
-    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
-    return wav.new_empty((wav.shape[0], fmax, len(bank)), dtype=torch.float32)
+    return _frames_fake(wav, f0s, f1s, len(bank))
 
 
 def _mcep_check(n_fft: int, hop: int, order: int, floor: float) -> None:
     """the size rules of swn_mcep as messages (the library itself answers SWN_E_BADARG)."""
-    if n_fft % 32 != 0 or not 32 <= n_fft <= _lib.SPECTRAL_MAX_FFT:
-        raise RuntimeError(f"mcep: n_fft {n_fft} is not a multiple of 32 in [32, {_lib.SPECTRAL_MAX_FFT}]")
-    if not 1 <= hop <= n_fft:
-        raise RuntimeError(f"mcep: hop {hop} outside [1, n_fft = {n_fft}]")
-    if not 0 <= order <= min(_lib.MCEP_MAX_ORDER, n_fft // 2):
-        raise RuntimeError(f"mcep: order {order} outside [0, min({_lib.MCEP_MAX_ORDER}, n_fft / 2 = {n_fft // 2})]")
-    if not floor > 0.0:
-        raise RuntimeError(f"mcep: floor {floor} must be > 0")
+    _stft_check("mcep", n_fft, hop, floor, (0 <= order <= min(_lib.MCEP_MAX_ORDER, n_fft // 2),
+                                            f"order {order} outside [0, min({_lib.MCEP_MAX_ORDER}, n_fft / 2 = {n_fft // 2})]"))
 
 
 def mcep_impl(wav: torch.Tensor, tables: torch.Tensor, t0s: List[int], n_avails: List[int], lens: List[int], f0s: List[int],
@@ -1563,30 +1587,13 @@ def mcep_impl(wav: torch.Tensor, tables: torch.Tensor, t0s: List[int], n_avails:
     _need_cuda(wav, "the waveforms")
     dev = wav.device
     _mcep_check(n_fft, hop, order, floor)
-    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
-        raise RuntimeError(f"mcep needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
-    R, S = wav.shape
-    if not (len(t0s) == len(n_avails) == len(lens) == len(f0s) == len(f1s) == R):
-        raise RuntimeError("mcep: t0s, n_avails, lens, f0s and f1s must have one entry per row")
-    if any(not 0 <= na <= S for na in n_avails):
-        raise RuntimeError(f"mcep: a row has more samples available than the buffer's {S} columns")
-    need = Lb.swn_mcep_table_floats(n_fft, order)
-    if tables.device != dev or tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != need:
-        raise RuntimeError(f"mcep: tables must be {need} contiguous fp32 values on the device of the waveforms")
-    fmax, nc = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0]), order + 1
-    out = torch.zeros((R, fmax, nc), dtype=torch.float32, device=dev)
-    esz, osz = wav.element_size() * S, out.element_size() * fmax * nc
-    for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
-        r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
-        table = (_lib.LogMelEntry * (r1 - r0))(*[
-            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
-                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
-            for r in range(r0, r1)])
-        nb = Lb.swn_mcep_work_bytes(n_fft, hop, table, r1 - r0)
+    out, groups = _frame_entries("mcep", wav, t0s, n_avails, lens, f0s, f1s, order + 1)
+    _tables_check("mcep", tables, Lb.swn_mcep_table_floats(n_fft, order), dev, "waveforms")
+    for table, n in groups:
+        nb = Lb.swn_mcep_work_bytes(n_fft, hop, table, n)
         work = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=dev)
         with _on(dev):
-            _lib.check(Lb.swn_mcep(n_fft, hop, order, float(floor), _ptr(tables), table, r1 - r0, _ptr(work), _stream(dev)),
-                       "mcep")
+            _lib.check(Lb.swn_mcep(n_fft, hop, order, float(floor), _ptr(tables), table, n, _ptr(work), _stream(dev)), "mcep")
     return out
 
 
@@ -1596,8 +1603,7 @@ mcep = custom_op("swn::mcep", mutates_args=())(mcep_impl)
 @mcep.register_fake
 def _(wav, tables, t0s, n_avails, lens, f0s, f1s, n_fft, hop, order, floor):
     _mcep_check(n_fft, hop, order, floor)
-    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
-    return wav.new_empty((wav.shape[0], fmax, order + 1), dtype=torch.float32)
+    return _frames_fake(wav, f0s, f1s, order + 1)
 
 
 def _f0_check(fs: float, hop: int, win: int, lag_lo: int, lag_hi: int, threshold: float) -> None:
@@ -1623,24 +1629,10 @@ def f0_impl(wav: torch.Tensor, t0s: List[int], n_avails: List[int], lens: List[i
     _need_cuda(wav, "the waveforms")
     dev = wav.device
     _f0_check(fs, hop, win, lag_lo, lag_hi, threshold)
-    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
-        raise RuntimeError(f"f0 needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
-    R, S = wav.shape
-    if not (len(t0s) == len(n_avails) == len(lens) == len(f0s) == len(f1s) == R):
-        raise RuntimeError("f0: t0s, n_avails, lens, f0s and f1s must have one entry per row")
-    if any(not 0 <= na <= S for na in n_avails):
-        raise RuntimeError(f"f0: a row has more samples available than the buffer's {S} columns")
-    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
-    out = torch.zeros((R, fmax, 2), dtype=torch.float32, device=dev)
-    esz, osz = wav.element_size() * S, out.element_size() * fmax * 2
-    for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
-        r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
-        table = (_lib.LogMelEntry * (r1 - r0))(*[
-            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
-                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
-            for r in range(r0, r1)])
+    out, groups = _frame_entries("f0", wav, t0s, n_avails, lens, f0s, f1s, 2)
+    for table, n in groups:
         with _on(dev):
-            _lib.check(Lb.swn_f0(float(fs), hop, win, lag_lo, lag_hi, float(threshold), table, r1 - r0, _stream(dev)), "f0")
+            _lib.check(Lb.swn_f0(float(fs), hop, win, lag_lo, lag_hi, float(threshold), table, n, _stream(dev)), "f0")
     return out
 
 
@@ -1650,8 +1642,7 @@ f0 = custom_op("swn::f0", mutates_args=())(f0_impl)
 @f0.register_fake
 def _(wav, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshold):
     _f0_check(fs, hop, win, lag_lo, lag_hi, threshold)
-    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
-    return wav.new_empty((wav.shape[0], fmax, 2), dtype=torch.float32)
+    return _frames_fake(wav, f0s, f1s, 2)
 
 
 def _bap_check(taps: torch.Tensor, win: int, band_win: int, floor: float) -> Tuple[int, int]:
@@ -1683,27 +1674,11 @@ def bap_impl(wav: torch.Tensor, taps: torch.Tensor, t0s: List[int], n_avails: Li
     B, T = _bap_check(taps, win, band_win, floor)
     if taps.device != dev or not taps.is_contiguous():
         raise RuntimeError("bap: taps must be contiguous and on the waveforms' device")
-    if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
-        raise RuntimeError(f"bap needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
-    R, S = wav.shape
-    if not (len(t0s) == len(n_avails) == len(lens) == len(f0s) == len(f1s) == R):
-        raise RuntimeError("bap: t0s, n_avails, lens, f0s and f1s must have one entry per row")
-    if any(not 0 <= na <= S for na in n_avails):
-        raise RuntimeError(f"bap: a row has more samples available than the buffer's {S} columns")
-    fmax, cols = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0]), 2 + B
-    out = torch.zeros((R, fmax, cols), dtype=torch.float32, device=dev)
-    esz, osz = wav.element_size() * S, out.element_size() * fmax * cols
-    groups = []
-    for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
-        r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
-        table = (_lib.LogMelEntry * (r1 - r0))(*[
-            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
-                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
-            for r in range(r0, r1)])
-        groups.append((table, r1 - r0, int(Lb.swn_bap_work_bytes(hop, win, lag_hi, B, table, r1 - r0))))
+    out, groups = _frame_entries("bap", wav, t0s, n_avails, lens, f0s, f1s, 2 + B)
     # one scratch for all groups, which run one after the other on the stream (never empty: the call refuses a null pointer)
-    work = torch.empty((max([b for _, _, b in groups] + [8]) // 8,), dtype=torch.float64, device=dev)
-    for table, n, _ in groups:
+    nb = max([int(Lb.swn_bap_work_bytes(hop, win, lag_hi, B, table, n)) for table, n in groups] + [8])
+    work = torch.empty((nb // 8,), dtype=torch.float64, device=dev)
+    for table, n in groups:
         with _on(dev):
             _lib.check(Lb.swn_bap(float(fs), hop, win, lag_lo, lag_hi, float(threshold), band_win, B, T, taps.data_ptr(), float(floor),
                                   table, n, work.data_ptr(), _stream(dev)), "bap")
@@ -1717,8 +1692,7 @@ bap = custom_op("swn::bap", mutates_args=())(bap_impl)
 def _(wav, taps, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshold, band_win, floor):
     _f0_check(fs, hop, win, lag_lo, lag_hi, threshold)
     B, _ = _bap_check(taps, win, band_win, floor)
-    fmax = max([f1 - f0 for f0, f1 in zip(f0s, f1s)] + [0])
-    return wav.new_empty((wav.shape[0], fmax, 2 + B), dtype=torch.float32)
+    return _frames_fake(wav, f0s, f1s, 2 + B)
 
 
 def logmel_pool_impl(win: torch.Tensor, staged: Optional[torch.Tensor], tables: torch.Tensor, bank: List[int], slots: List[int],
@@ -1753,9 +1727,7 @@ def _logmel_pool_call(win, staged, tables, bank, slots, t0s, n_helds, n_drops, n
     if any(n < 0 for n in n_news) or (total_new > 0 and (staged is None or staged.device != dev or staged.dtype != torch.float32
                                                          or not staged.is_contiguous() or staged.numel() != total_new)):
         raise RuntimeError(f"logmel_pool: staged must be the {total_new} new samples as contiguous fp32 values on the windows' device")
-    need = Lb.swn_logmel_table_floats(n_fft, n_mels)
-    if tables.device != dev or tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() != need:
-        raise RuntimeError(f"logmel_pool: tables must be {need} contiguous fp32 values on the device of the windows")
+    _tables_check("logmel_pool", tables, Lb.swn_logmel_table_floats(n_fft, n_mels), dev, "windows")
     table = (_lib.LogMelPoolEntry * E)()
     new_off = out_off = 0
     for e in range(E):

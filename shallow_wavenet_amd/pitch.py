@@ -51,7 +51,7 @@ import numpy as np
 import torch
 
 from . import _lib, dsp, ops
-from .melspec import _padded_batch, frame_count
+from .melspec import _FrameExtractor, _FrameStream, frame_count
 
 
 def f0_lags(fs: float, minf0: float, maxf0: float) -> Tuple[int, int]:
@@ -80,8 +80,9 @@ def f0_frames_ready(hop: int, win: int, lag_hi: int, n_received: int, final: boo
     return 0 if n_received < ahead else 1 + (n_received - ahead) // hop
 
 
-class F0Extractor:
-    """holds the geometry; a call computes [F0, aperiodicity] of every frame of a batch of waveforms on `device`."""
+class F0Extractor(_FrameExtractor):
+    """holds the geometry; a call computes [F0, aperiodicity] of every frame of a batch of waveforms on `device`: (R, F_max, 2),
+    and `frames` those of a range from a partial buffer."""
 
     def __init__(self, fs: float, hop: int, minf0: float = 40.0, maxf0: float = 700.0, win: int = 1024, threshold: float = 0.1,
                  device="cuda") -> None:
@@ -98,9 +99,6 @@ class F0Extractor:
         self.device = torch.device(device)
         self._op = ops.f0_impl
 
-    def frame_count(self, length: int) -> int:
-        return frame_count(length, self.hop)
-
     def _check_len(self, length: int) -> None:
         if length < 1:
             raise ValueError(f"a signal needs at least one sample, got {length}")
@@ -108,26 +106,8 @@ class F0Extractor:
     def _run(self, buf, t0s, n_avails, lens, f0s, f1s) -> torch.Tensor:
         return self._op(buf, t0s, n_avails, lens, f0s, f1s, self.fs, self.hop, self.win, self.lag_lo, self.lag_hi, self.threshold)
 
-    def __call__(self, wavs, lengths: Optional[Sequence[int]] = None) -> torch.Tensor:
-        """wavs: a padded (R, S) batch with `lengths` (default: S for every row), one 1-D signal, or a list of R 1-D signals of
-        their own lengths -> (R, F_max, 2), row r holding frame_count(lengths[r]) frames and zeros after them."""
-        batch, lens = _padded_batch(self, wavs, lengths)
-        R = len(lens)
-        return self._run(batch, [0] * R, lens, lens, [0] * R, [self.frame_count(n) for n in lens])
 
-    def frames(self, wav: torch.Tensor, t0: Union[int, Sequence[int]], n_avail: Union[int, Sequence[int]],
-               length: Union[int, Sequence[int]], f0: Union[int, Sequence[int]], f1: Union[int, Sequence[int]]) -> torch.Tensor:
-        """frames [f0, f1) from a partial buffer: `wav` (S,) or (R, S) holds the samples [t0, t0 + n_avail) of each signal, whose
-        total length is `length` or -1 while it is not known -> (f1 - f0, 2) or (R, max(f1 - f0), 2).  A range whose in-signal
-        samples are not all in the buffer is refused."""
-        one = wav.dim() == 1
-        buf = (wav[None] if one else wav).to(self.device, torch.float32).contiguous()
-        lst = lambda v: [int(v)] * buf.shape[0] if isinstance(v, (int, np.integer)) else [int(x) for x in v]
-        out = self._run(buf, lst(t0), lst(n_avail), lst(length), lst(f0), lst(f1))
-        return out[0] if one else out
-
-
-class F0Stream:
+class F0Stream(_FrameStream):
     """one signal's [F0, aperiodicity] frames as its samples arrive: `push` returns the frames that became computable, `finish`
     the rest (those that read the zeros past the end).  Only the tail of the signal that later frames still read is kept.  The
     concatenation of everything returned is bit-identical to the extractor's one-shot call on the whole signal.  The samples are
@@ -135,48 +115,15 @@ class F0Stream:
     on each chunk first."""
 
     def __init__(self, extractor: F0Extractor) -> None:
-        self.ext = extractor
-        self._buf = torch.zeros(0, dtype=torch.float32, device=extractor.device)
-        self.t0 = 0                 # absolute index of _buf[0]
-        self.n_received = 0
-        self.n_frames = 0           # frames returned so far
-        self.finished = False
+        super().__init__(extractor, 2)
         self._behind = extractor.span // 2      # samples a frame reads before f * hop
-        self._cols = 2
 
     def computable(self, n_received: int, final: bool = False) -> int:
         return f0_frames_ready(self.ext.hop, self.ext.win, self.ext.lag_hi, n_received, final)
 
-    def _range(self, f1: int, length: int) -> torch.Tensor:
-        f0 = self.n_frames
-        if f1 > f0:
-            out = self.ext.frames(self._buf, self.t0, int(self._buf.numel()), length, f0, f1)
-            self.n_frames = f1
-        else:
-            out = torch.zeros((0, self._cols), dtype=torch.float32, device=self.ext.device)
+    def _keep(self) -> int:
         # the next frame's first sample; with hop > S it may not have arrived yet
-        keep = min(self.n_received, max(self.t0, self.n_frames * self.ext.hop - self._behind))
-        if keep > self.t0:
-            self._buf = self._buf[keep - self.t0:]
-            self.t0 = keep
-        return out
-
-    def push(self, samples) -> torch.Tensor:
-        """append 1-D samples -> (k, 2) new frames, k >= 0"""
-        if self.finished:
-            raise RuntimeError("the stream is finished")
-        s = torch.as_tensor(samples).reshape(-1).to(self.ext.device, torch.float32)
-        self._buf = torch.cat([self._buf, s])
-        self.n_received += int(s.numel())
-        return self._range(self.computable(self.n_received), -1)
-
-    def finish(self) -> torch.Tensor:
-        """the signal ends here -> the remaining frames up to F = 1 + n_received // hop"""
-        if self.finished:
-            raise RuntimeError("the stream is finished")
-        self.ext._check_len(self.n_received)
-        self.finished = True
-        return self._range(self.computable(self.n_received, True), self.n_received)
+        return min(self.n_received, max(self.t0, self.n_frames * self.ext.hop - self._behind))
 
 
 # ---- band aperiodicity: the reference's `codeap` columns ------------------------------------------------------------------------
