@@ -246,6 +246,11 @@ int    swn_decode(const swn_net_desc* d, const float* packed_dev, const float* c
                   int batch, int n_frames, int n_steps, const swn_decode_io* io,
                   float* state_dev, void* out_dev, float* heads_dev,
                   int variant, void* stream);
+/* Bytes of dynamic LDS one workgroup of the wave-specialised kernel (variant 2) takes for this net: the classic
+ * instantiation (host-drawn noise, zero seed), or with extended != 0 the one the noise generator, the noise dump, a seed
+ * waveform, streamed chunks and pools run.  0 when the descriptor is refused or the kernel does not serve the geometry.
+ * Every word the kernel addresses lies inside it (at most 160 KB). */
+size_t swn_decode_bl6w_lds_bytes(const swn_net_desc* d, int extended);
 
 /* ---- streamed decode: swn_decode in resumable chunks, bit-identical to the one-shot call --------------------------
  * A session holds everything a decode kernel carries from one step to the next (history rings, sample window, and

@@ -158,6 +158,7 @@ SIGNATURES = {
     "swn_decode_state_floats": (c_size_t, [POINTER(NetDesc), c_int]),
     "swn_decode": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, POINTER(DecodeIO),
                            c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "swn_decode_bl6w_lds_bytes": (c_size_t, [POINTER(NetDesc), c_int]),
     "swn_decode_resolve_variant": (c_int, [POINTER(NetDesc), c_int, c_int]),
     "swn_decode_session_floats": (c_size_t, [POINTER(NetDesc), c_int, c_int]),
     "swn_decode_chunk": (c_int, [POINTER(NetDesc), c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(DecodeIO),

@@ -76,6 +76,31 @@
 #ifndef SWN_RINGX
 #define SWN_RINGX 1
 #endif
+// The classic lpc 0 kernel, instructions taken off group A's chain that produce nothing the result needs (each
+// switch 0 = the parent's form; no multiply-add, operand or summation order differs, the samples are the parent's bits with
+// every subset).  Built: SWN_SWAP_ROWS and SWN_FLAT_EPILOGUE - 421.1 k samples/s of the headline beside the parent's 413.2.
+// Measured and left out: SWN_CARRY_HP (393.5 k alone beside 413.1, and 2 % off every build that has it) and SWN_PLAIN_TAIL
+// (416.1 - 416.5 k on top of the built form's 419.6 - 420.6).
+// -DSWN_CARRY_HP: layer l + 1's highway operand is the `hn` the same thread wrote to ring l + 1 one phase earlier - it stays in a
+// register instead of coming back through LDS (layers 1 - 5, prologue too; layer 0's h0 lives in another lane mapping);
+// -DSWN_SWAP_ROWS: lanes of odd p load their gate and candidate rows swapped, so the partial sums are "own" / "other" in every
+// lane and quad_sum_by_parity takes them without the two selects;
+// -DSWN_FLAT_EPILOGUE: the gate epilogue runs on all four lanes of the quad (lanes 2 / 3 hold the sums of lanes 0 / 1) with no
+// exec mask; the hand-off store of lanes p != 0 goes to a per-thread dump word behind the carve (o_dump, 1 KB);
+// -DSWN_PLAIN_TAIL: the one-shot launch without forced inputs runs a copy of the kernel that has no forced load, wait or select
+// in the tail and forms the next input layer behind the last step too (its row exists and nobody reads it).
+#ifndef SWN_CARRY_HP
+#define SWN_CARRY_HP 0
+#endif
+#ifndef SWN_SWAP_ROWS
+#define SWN_SWAP_ROWS 1
+#endif
+#ifndef SWN_FLAT_EPILOGUE
+#define SWN_FLAT_EPILOGUE 1
+#endif
+#ifndef SWN_PLAIN_TAIL
+#define SWN_PLAIN_TAIL 0
+#endif
 // (the stamp build hands skip_roll_b the counter of its wait for the loads requested at the head of the phase)
 #ifdef SWN_STAMP
 #define SWN_TDEF_PARAM , unsigned long long& tdef
@@ -130,14 +155,31 @@ struct Tw {
     // written by group A's wave 0 one step late, stored to memory by group B 64 steps at a time (decode_body)
     static constexpr int o_ho = o_h0w + 3 * H;
     static constexpr int HO = 4, NHO = 128;
-    static constexpr int o_end = o_ho + (NEWFORM && (SWN_HANDOFF & 1) && SWN_ROTATE ? NHO * HO : 0);
+    // group A's chain trims (the switches above), the classic lpc 0 kernel alone
+    static constexpr bool CARRY_HP = NEWFORM && SWN_CARRY_HP;
+    static constexpr bool SWAP_ROWS = NEWFORM && SWN_SWAP_ROWS;
+    static constexpr bool FLAT_EPI = NEWFORM && SWN_FLAT_EPILOGUE;
+    static constexpr bool PLAIN_TAIL = NEWFORM && SWN_PLAIN_TAIL;
+    // (FLAT_EPI) one dump word per thread of group A: where lanes p != 0 of a quad leave the hand-off value nobody reads
+    static constexpr int o_dump = o_ho + (NEWFORM && (SWN_HANDOFF & 1) && SWN_ROTATE ? NHO * HO : 0);
+    static constexpr int o_end = o_dump + (FLAT_EPI ? NG : 0);
     static constexpr size_t lds_bytes = (size_t)o_end * sizeof(float);
+    static_assert(o_dump == o_wl + 8 * NG * 4 + 3 * H + (o_dump - o_ho) && (o_dump - o_ho == 0 || o_dump - o_ho == NHO * HO),
+                  "the carve ends with group B's last-layer half, the three h0 copies and the hand-off ring");
+    static_assert(o_end - o_dump == (FLAT_EPI ? NG : 0) && (!FLAT_EPI || o_dump + (NG - 1) == o_end - 1),
+                  "one dump word per thread of group A, the last one the carve's last float");
+    static_assert(o_dump % 4 == 0 && (size_t)o_end * sizeof(float) <= 160 * 1024, "16-byte carve, 160 KB of LDS");
     // per-utterance session of a streamed decode: the history rings, the older-tap products group B formed one step ahead
     // (both parities, as LDS holds them), then the sample window
     static constexpr int sess_old = ring_off(L);
     static constexpr int sess_win = sess_old + 2 * L * 2 * H;
     static constexpr int sess_floats = sess_win + r4(WN);
 };
+// the dump words are the classic lpc 0 kernel's alone: 39 308 floats of the parent's carve and 256 behind them
+static_assert((SWN_HANDOFF & 1) || Tw<0, false>::o_dump == 39308, "classic lpc 0 carve");
+static_assert((SWN_HANDOFF & 1) || !SWN_FLAT_EPILOGUE || Tw<0, false>::o_end == 39564, "classic lpc 0 carve with the dump words");
+static_assert(Tw<0, true>::o_end == Tw<0, true>::o_dump && Tw<4, false>::o_end == Tw<4, false>::o_dump &&
+              Tw<4, true>::o_end == Tw<4, true>::o_dump, "the other kernels keep the parent's carve");
 
 // the sum over the wave's 16 quads, per position in the quad: lane hp of the first quad gets the sum of lanes hp + 4 n
 // (the swaps in inline assembly, with the two wait states a VALU write needs before them: the compiler returns the builtins'
@@ -169,15 +211,18 @@ __device__ __forceinline__ float quad_sum_by_parity(float own, float other) {
 //      (NQ, one session, k samples/s of the headline beside the parent's 397.6: 0 quads early 398.7, one 403.1, two 403.9, three
 //       401.8, all four 396.4 - every early quad holds four registers through the stores, and from three on a kernel spills)
 struct NoWork { __device__ __forceinline__ void operator()() const {} };
+//      Returns `hn` (lane p = 0 of the quad; with T::FLAT_EPI lanes p != 0 return a finite value nobody needs) and takes the
+//      previous layer's as `hp_in`: with T::CARRY_HP it is the highway operand of layers 1 - 5 - the value this thread wrote to
+//      the row `xr` one phase earlier.
 template <class T, int LAYER, int NQ = 2, class BEHIND = NoWork>
-__device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], const int q, const float wj, const int pb, const int po,
-                                        const int ta, const float* xr, BEHIND&& behind = NoWork{}) {
+__device__ __forceinline__ float layer_a(float* lds, const float (&w)[2][16], const int q, const float wj, const int pb, const int po,
+                                         const int ta, const float* xr, const float hp_in, BEHIND&& behind = NoWork{}) {
     constexpr bool ROT = !std::is_same<typename std::decay<BEHIND>::type, NoWork>::value;
     const int o = ta >> 2, p = ta & 3, pr = p & 1;
     // epilogue operands first: their LDS latency hides under the FMAs
     const float e_old = lds[T::o_old + po + LAYER * 2 * H + pr * H + o];
     const float g_gp = lds[T::o_gp + pb + LAYER * 2 * H + pr * H + o], g_bx = lds[T::o_bx + LAYER * 2 * H + pr * H + o];
-    const float e_hp = xr[o];
+    const float e_hp = (T::CARRY_HP && LAYER >= 1) ? hp_in : xr[o];
     static_assert(NQ >= 0 && NQ <= 4, "early quads");
     float4 xq[4];
     if constexpr (ROT) {
@@ -202,8 +247,28 @@ __device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], con
     // the two quad sums transposed: a lane of even parity keeps its gate partial and hands over its candidate partial, a lane of
     // odd parity the reverse, so two DPP steps leave the gate sum in lanes 0 / 2 and the candidate sum in lanes 1 / 3 - each
     // associated (p0 + p1) + (p2 + p3) as sum4 forms it (bit-identical), without the select between two full sums
-    const float sq = quad_sum_by_parity(pr ? ac : az, pr ? az : ac);
+    // (T::SWAP_ROWS: lanes of odd parity hold the candidate row in w[0] and the gate row in w[1] - az is every lane's own partial)
+    const float sq = T::SWAP_ROWS ? quad_sum_by_parity(az, ac) : quad_sum_by_parity(pr ? ac : az, pr ? az : ac);
     __builtin_amdgcn_sched_barrier(0);              // keep the gate epilogue behind the reduction
+    float hn = 0.f;
+    if constexpr (T::FLAT_EPI) {
+        // all four lanes: lanes 2 / 3 hold the sums and the operands of lanes 0 / 1 (every index above goes by pr), so the same
+        // line runs in them with no exec mask; lane 2 forms lane 0's hn again, lanes 1 / 3 something finite from the candidate.
+        // Only the store is the lane's own: p = 0 writes the ring slot (the last layer o_hcat), the others their dump word
+        const float sa = sq + e_old;
+        const float v = e_gx * sa;
+        const float e = exp_c(pr == 0 ? -v : -2.f * fminf(fabsf(v), 64.f));
+        const float r = rcp_c(1.f + e);
+        const float res = pr == 0 ? r : copysignf((1.f - e) * r, v);        // z | tanh
+        const float c = dpp_f<0xF5>(res);                                  // quad_perm [1,1,3,3]: lanes 0 / 2 <- lanes 1 / 3
+        hn = (1.f - res) * c + res * e_hp;
+        constexpr int R2 = T::ring_len(LAYER + 1 < L ? LAYER + 1 : LAYER);
+        const int dst = LAYER + 1 < L ? T::o_ring + T::ring_off(LAYER + 1 < L ? LAYER + 1 : LAYER) + (q & (R2 - 1)) * H + o
+                                      : T::o_hcat + LAYER * H + o;
+        static_assert(T::RINGX || !T::FLAT_EPI, "one hand-off store per layer");
+        float* const own = lds + T::o_dump + ta;
+        *(p == 0 ? lds + dst : own) = hn;
+    } else
     if (p < 2) {
         const float sa = sq + e_old;
         const float v = e_gx * sa;
@@ -226,7 +291,7 @@ __device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], con
         const float res = p == 0 ? r : copysignf((1.f - e) * r, v);        // z | tanh
         const float c = dpp_f<0xF5>(res);                                  // quad_perm [1,1,3,3]: lane 0 <- lane 1
         if (p == 0) {
-            const float hn = (1.f - res) * c + res * e_hp;
+            hn = (1.f - res) * c + res * e_hp;
             if (LAYER + 1 < L) {
                 constexpr int R2 = T::ring_len(LAYER + 1 < L ? LAYER + 1 : LAYER);
                 lds[T::o_ring + T::ring_off(LAYER + 1 < L ? LAYER + 1 : LAYER) + (q & (R2 - 1)) * H + o] = hn;
@@ -236,6 +301,7 @@ __device__ __forceinline__ void layer_a(float* lds, const float (&w)[2][16], con
         }
     }
     __builtin_amdgcn_sched_barrier(0);
+    return hn;
 }
 
 // ---- group B: older-tap product of layer LAYER for position qn = q + 1 (its operand h_{l-1}(qn - dil) is at least one step old),
@@ -508,8 +574,11 @@ template <> struct Out1Split<0> { using Early = Layers<>; using Late = Layers<0,
 // layer is then formed by the same input_gen as in the one-shot loop.  At the end all of it goes back to the session.
 // POOL (with STREAM): one entry of a decode pool (swn_decode_pool_chunk); `a` already holds it as a batch-1 chunk, b = 0.  The
 // noise staging and the frame boundaries follow the entry's own step0 and n_steps, so entries of one launch sit at any phase.
-template <class T, bool GA, bool STREAM, bool POOL = false>
+// PLAIN (T::PLAIN_TAIL, the one-shot launch): the caller gave no forced inputs - the tail has no forced load, wait or select,
+// and the next input layer is formed behind the last step as well.
+template <class T, bool GA, bool STREAM, bool POOL = false, bool PLAIN = false>
 __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
+    static_assert(!PLAIN || (T::PLAIN_TAIL && !STREAM), "the one-shot classic lpc 0 kernel");
     constexpr bool EXT = T::EXT;
     static_assert(!STREAM || EXT, "streamed chunks run the extended mode");
     constexpr bool grpA = GA;
@@ -563,7 +632,9 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         for (int l = 0; l < L; ++l)
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-                const float4* src = reinterpret_cast<const float4*>(P + a.y.wd + (((size_t)l * 2 * H + o + r * H) * 2 + k) * H + 16 * p);
+                // (T::SWAP_ROWS: group A's lanes of odd p hold the candidate row as row 0 and the gate row as row 1, layer_a)
+                const int rs = (grpA && T::SWAP_ROWS) ? r ^ (p & 1) : r;
+                const float4* src = reinterpret_cast<const float4*>(P + a.y.wd + (((size_t)l * 2 * H + o + rs * H) * 2 + k) * H + 16 * p);
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const float4 t = src[v];
@@ -746,9 +817,9 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     // (GEN: a generation step - group B's older-tap products for position q + 1 then sit in the merged and the out_1 phase, and
     //  layer 5's is group A's; in the prologue group B forms layer LAYER's in this phase.  X0: the row of h0(q) layer 0 reads)
 #define SWN_PHASE_WORK(LAYER, GEN, X0)                                                                                \
-    if constexpr (grpA) layer_a<T, LAYER>(lds, wreg[LAYER], q, wj, pb, po, tg,                                         \
-                                          LAYER == 0 ? (X0) : lds + T::o_ring + T::ring_off(LAYER) +                   \
-                                                                  (q & (T::ring_len(LAYER) - 1)) * H);                 \
+    if constexpr (grpA) hcar = layer_a<T, LAYER>(lds, wreg[LAYER], q, wj, pb, po, tg,                                  \
+                                                 LAYER == 0 ? (X0) : lds + T::o_ring + T::ring_off(LAYER) +            \
+                                                                         (q & (T::ring_len(LAYER) - 1)) * H, hcar);    \
     else {                                                                                                             \
         if (GEN) {   /* slice 0 is requested whole at the start of the step; every later slice rolls in by quarters, behind    */ \
                      /* the multiply-adds that free its registers (both slices live at once are 64 registers beside the 160   */ \
@@ -775,6 +846,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
     for (int q = resume ? n_pro : 0; q < n_pro; ++q) {
         float wj; int pb;
         float4 wsl[8]; float sacc[2]; const unsigned step0 = 0;
+        float hcar = 0.f;                     // group A: the layer's hn, the next layer's highway operand (layer_a)
         cond_taps(q, wj, pb);
         const int po = (q & 1) * (L * 2 * H);
         input_seed(q);
@@ -782,7 +854,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         const float* x0 = lds + T::o_ring + (q & 1) * H;
         SWN_PHASE(0, false, x0) SWN_PHASE(1, false, x0) SWN_PHASE(2, false, x0) SWN_PHASE(3, false, x0)
         SWN_PHASE(4, false, x0) SWN_PHASE(5, false, x0)
-        (void)wsl; (void)sacc; (void)step0;
+        (void)wsl; (void)sacc; (void)step0; (void)hcar;
     }
 
     // ---- generation (cswnv_shift1.py:348-402).  Eight barriers per step: the first phase of step q is the tail of step q - 1
@@ -906,6 +978,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
         };
         float4 wsl[8];
         float sacc[2] = {0.f, 0.f};
+        float hcar = 0.f;                                     // group A: the layer's hn, the next layer's highway operand (layer_a)
         if constexpr (!grpA) {                                // the out_skip bias enters in lane 0 of each row's quad
             const float bs0 = lds[T::o_bias + (tg >> 2)], bs1 = lds[T::o_bias + (tg >> 2) + 64];
             if ((tg & 3) == 0) { sacc[0] = bs0; sacc[1] = bs1; }
@@ -934,7 +1007,7 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             for (int k = 0; k < 8; ++k) asm volatile("" : "=v"(wsl[k].x), "=v"(wsl[k].y), "=v"(wsl[k].z), "=v"(wsl[k].w));
         }
         if constexpr (grpA && ROT) {
-            layer_a<T, 0, ROTQ>(lds, wreg[0], q, wj, pb, po, tg, x0, behind0);
+            hcar = layer_a<T, 0, ROTQ>(lds, wreg[0], q, wj, pb, po, tg, x0, hcar, behind0);
             SWN_BAR(0)
         } else {
             SWN_PHASE(0, true, x0)
@@ -1091,7 +1164,8 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
             float tz = 0.f;                                // (an early read in the extended mode spilled four registers)
             if constexpr (!EXT) tz = lds[T::o_tnz + (i & (T::NZB * T::NZC - 1))];
             float fv = 0.f;
-            if (a.forced) fv = reinterpret_cast<const float*>(a.forced)[(size_t)b * a.n_steps + i];
+            const bool forced_on = !PLAIN && a.forced;
+            if (forced_on) fv = reinterpret_cast<const float*>(a.forced)[(size_t)b * a.n_steps + i];
             const float4 pz = *reinterpret_cast<const float4*>(lds + T::o_p2 + 4 * (ln < T::NO ? ln : T::NO - 1));
             // step q + 1's taps, row and offsets while the partials are on their way: wj's read joins the batch waited for here,
             // and nothing of this is left to do between the sample and layer 0
@@ -1119,13 +1193,14 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
                 // the window is updated and the next input layer formed BEFORE the sample and the heads are stored: the stores, their
                 // lane branches and addresses are not on the chain, and a use of the forced load behind a conditional store would
                 // wait for the stores themselves (it compiles to vmcnt(0)); the forced load stays older than every store of its step
-                float fd = a.forced ? fv : sv;
+                float fd = forced_on ? fv : sv;
                 asm volatile("" : "+v"(fd));
 #pragma unroll
                 for (int k = 0; k + 1 < T::WN; ++k) win[k] = win[k + 1];
                 win[T::WN - 1] = fd;
             }
-            if (i + 1 < a.n_steps) input_gen(x0_c);
+            // (PLAIN: behind the last step too - the row exists, nobody reads it, and the test leaves the chain)
+            if (PLAIN || i + 1 < a.n_steps) input_gen(x0_c);
             __builtin_amdgcn_sched_barrier(0);                 // the stores stay behind the input layer's write
             if constexpr (ROT) { sv_p = sv; acc_p = acc; }
             else {
@@ -1194,11 +1269,11 @@ __device__ __forceinline__ void decode_body(const Bl6Args& a, float* lds) {
 #endif
 }
 
-template <class T, bool STREAM = false>
+template <class T, bool STREAM = false, bool PLAIN = false>
 __global__ __launch_bounds__(NT) void decode_bl6w_kernel(const Bl6Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    if (threadIdx.x < NG) decode_body<T, true, STREAM>(a, lds);       // wave-uniform
-    else decode_body<T, false, STREAM>(a, lds);
+    if (threadIdx.x < NG) decode_body<T, true, STREAM, false, PLAIN>(a, lds);       // wave-uniform
+    else decode_body<T, false, STREAM, false, PLAIN>(a, lds);
 }
 
 // MODELS: the entry's weights are those of its model (SwnPoolModels)
@@ -1279,11 +1354,31 @@ int swn_decode_bl6w_run(const SwnDecodeCall& c) {
         static_assert(T::lds_bytes <= 160 * 1024 && X::lds_bytes <= 160 * 1024, "LDS budget");
         if (c.stream) return launch_kernel(decode_bl6w_kernel<X, true>, X::lds_bytes, a.B, a, st, "swn_decode(bl6w)");
         if (wants_ext(a)) return launch_kernel(decode_bl6w_kernel<X>, X::lds_bytes, a.B, a, st, "swn_decode(bl6w)");
+        // (T::PLAIN_TAIL: without forced inputs the copy whose tail has none of their instructions)
+        if constexpr (T::PLAIN_TAIL) {
+            if (!a.forced) return launch_kernel(decode_bl6w_kernel<T, false, true>, T::lds_bytes, a.B, a, st, "swn_decode(bl6w)");
+        }
         return launch_kernel(decode_bl6w_kernel<T>, T::lds_bytes, a.B, a, st, "swn_decode(bl6w)");
     });
 }
 
 // streamed decode (swn_decode_chunk): per-utterance session floats of the wave-specialised kernel, 0 = it does not apply
+// bytes of dynamic LDS a launch of the wave-specialised kernel takes (classic or extended instantiation), 0 = it does not apply
+size_t swn_decode_bl6w_lds(const SwnGeom& g, bool extended) {
+    size_t n = 0;
+    with_tw(g, [&](auto t) {
+        using T = decltype(t);
+        n = extended ? T::Ext::lds_bytes : T::lds_bytes;
+        return SWN_OK;
+    });
+    return n;
+}
+extern "C" size_t swn_decode_bl6w_lds_bytes(const swn_net_desc* d, int extended) {
+    SwnGeom g;
+    if (swn_make_geom(d, &g) < 0) return 0;
+    return swn_decode_bl6w_lds(g, extended != 0);
+}
+
 size_t swn_decode_bl6w_session_floats(const SwnGeom& g) {
     int n = 0;
     with_tw(g, [&](auto t) { n = decltype(t)::sess_floats; return SWN_OK; });
