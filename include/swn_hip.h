@@ -1066,6 +1066,68 @@ int    swn_bap(double fs, int hop, int win, int lag_lo, int lag_hi, double thres
                const double* taps_dev, float floor, const swn_logmel_entry* entries_host, int n_entries, void* work_dev,
                void* stream);
 
+/* ---- spectral envelope by F0-adaptive smoothing, and its mel-cepstrum (melspec.SpectralEnvelopeExtractor; csrc/swn_envelope.hip) ---
+ * The envelope swn_mcep does not compute: a frame is analysed under a window of three pitch periods and its power spectrum
+ * smoothed over 2 f0 / 3, so the harmonics are not in it.  It is CheapTrick's procedure (Morise 2015) in a fixed arithmetic; it
+ * omits WORLD's added noise and its eps and has a floor instead.  Parity with pyworld / pysptk is neither claimed nor pinned.
+ * The definition (melspec.py restates it, tests/envelope_ref.py pins it).  fs > 0; n_fft a multiple of 32 in [32,
+ * SWN_SPECTRAL_MAX_FFT]; 1 <= hop <= SWN_F0_MAX_HOP; 0 <= order <= min(SWN_MCEP_MAX_ORDER, n_fft / 2); floor > 0, an amplitude,
+ * fp32; q1 (CheapTrick's -0.15); default_f0.  With D = fs / n_fft and f0_floor = 3 fs / (n_fft - 3) the call needs f0_floor <
+ * default_f0 <= fs / 4 (fs 8 000 needs n_fft >= 64, 22 050 needs 160).  Input: len >= 1 finite fp32 samples, x[t] = 0 outside
+ * [0, len) (zero padding, as swn_f0); F = 1 + len / hop frames on the grid of the other extractors; one fp32 value f0[f] per frame,
+ * any number (column 0 of swn_f0 is the intended source).  Everything below is IEEE double in the order written; every sum is one
+ * chain in ascending index from +0.0 with fma; each output value is rounded once to fp32.
+ *   1. f0e = (double)f0[f] if f0_floor < f0[f] <= fs / 4, else default_f0: unvoiced 0.0, NaN and values outside take the default
+ *   2. hl = floor(1.5 fs / f0e + 0.5), so 2 hl + 1 <= n_fft - 1; w[k] = 0.5 cos(pi k f0e / (1.5 fs)) + 0.5 for k = -hl .. hl;
+ *      w /= sqrt(sum w^2); xw[k] = x[f hop + k] w[k]; then xw[k] -= w[k] (sum xw / sum w) with the normalised w
+ *   3. P[b] = |sum_k xw[k] e^(-2 pi i b (k + hl) / n_fft)|^2 = re^2 + im^2, b = 0 .. n_fft / 2; the twiddle of sample j = k + hl is
+ *      T[(b j) mod n_fft] for re and T[(b j + n_fft / 4) mod n_fft] for im, T[m] = cos(2 pi m / n_fft) the host's fp64 table
+ *   4. DC correction from the uncorrected P: for b = 0 .. floor(f0e / D): u = f0e / D - b, i = floor(u),
+ *      P'[b] = (P[b] + P[i]) + (u - i)(P[i + 1] - P[i]); P' = P elsewhere
+ *   5. box smoothing of width wd = 2 f0e / 3 over the spectrum as one rectangle of width D per bin, mirrored at 0 and Nyquist:
+ *      S[b] = (1 / wd) sum_n ov(n) P'[mir(n)], n ascending from floor((b D - wd / 2) / D + 0.5) to floor((b D + wd / 2) / D + 0.5),
+ *      ov(n) = min(b D + wd / 2, (n + 0.5) D) - max(b D - wd / 2, (n - 0.5) D), terms with ov <= 0 skipped,
+ *      mir(n) = -n for n < 0, n_fft - n for n > n_fft / 2, else n
+ *   6. L[b] = ln max(S[b], floor^2)
+ *   7. v[k] = (1 / n_fft) sum_b e_b L[b] T[(k b) mod n_fft], k = 0 .. n_fft / 2, e = 1 at 0 and n_fft / 2 and 2 between (irfft);
+ *      l_s[0] = 1, l_s[k] = sin(x) / x with x = pi f0e k / fs; l_c[k] = (1 - 2 q1) + 2 q1 cos(2 pi k f0e / fs);
+ *      ct[k] = v[k] l_s[k] l_c[k]
+ *   8. what = SWN_ENVELOPE_MCEP: the one-sided cepstrum of the log AMPLITUDE envelope, c[0] = ct[0] / 2, c[k] = ct[k], c[n_fft / 2]
+ *      = ct[n_fft / 2] / 2, then mc[m] = sum_k G[m][k] c[k], G the fp64 matrix (order + 1, n_fft / 2 + 1) of SPTK's freqt on the
+ *      unit vectors (alpha exists only in how the caller built G); frame f, coefficient m at out_dev + (f - f0) (order + 1) + m.
+ *      what = SWN_ENVELOPE_LOGAMP: E[b] = 0.5 sum_k e_k ct[k] T[(k b) mod n_fft], ln of the amplitude envelope, n_fft / 2 + 1
+ *      values per frame.
+ * A frame's values depend on the signal, the frame index and that frame's f0 value alone - not on the batch, the entry, the
+ * frame range, the window or the call: any partition gives the same bits.  Streaming rule (melspec.envelope_frames_ready is the
+ * one place it is written): frame f is computable iff f hop + n_fft / 2 <= n_received, or when the signal has ended.
+ * tables_dev (swn_envelope_table_doubles doubles): T, then G row by row.  Entries follow the rules of swn_logmel_entry (a HOST
+ * table of at most SWN_LOGMEL_MAX_ENTRIES, carried in the launch arguments; no read outside [t0, t0 + n_avail); len may be -1
+ * while unknown); f0_dev addresses the F0 of frame f0 of the range, f1 - f0 floats.  One launch, a block per frame, the frame's
+ * vectors in LDS; work_dev (swn_envelope_work_bytes, 8-byte aligned) is reserved scratch.
+ * SWN_E_BADARG, found on the host before anything is launched, text in swn_last_error_detail: every rule above, what not 0 / 1,
+ * a null pointer, n_entries out of range, a non-zero reserved field, len < 1 or > 2^30, a window that leaves the signal, f0 < 0,
+ * f1 < f0, f1 > F, a frame whose span [f hop - (n_fft / 2 - 1), f hop + n_fft / 2) leaves the window where it lies inside the
+ * signal, or reaches past the window while len is -1, more than 2^24 frames in one call.  Entries with f1 == f0 do nothing and may
+ * carry null pointers; a call without any frame launches nothing.  The size queries return 0 for arguments the call refuses.
+ * sizeof(swn_envelope_entry) == 48. */
+typedef struct swn_envelope_entry {
+    const float* wav_dev;      /* sample t0 of this row */
+    float*       out_dev;      /* frame f0 of this row's output, (f1 - f0) * columns floats */
+    const float* f0_dev;       /* F0 in Hz of frame f0 of this row, f1 - f0 floats */
+    int32_t t0;                /* absolute index of the first available sample, >= 0 */
+    int32_t n_avail;           /* samples available from t0 on */
+    int32_t len;               /* total length of the row, or -1: not known yet */
+    int32_t f0, f1;            /* frames to compute, 0 <= f0 <= f1 */
+    int16_t reserved;          /* 0 */
+    int16_t reserved2;         /* 0 */
+} swn_envelope_entry;
+#define SWN_ENVELOPE_MCEP 0
+#define SWN_ENVELOPE_LOGAMP 1
+size_t swn_envelope_table_doubles(int n_fft, int order);
+size_t swn_envelope_work_bytes(int n_fft, int hop, const swn_envelope_entry* entries_host, int n_entries);
+int    swn_envelope(double fs, int n_fft, int hop, int order, float floor, double q1, double default_f0, int what,
+                    const double* tables_dev, const swn_envelope_entry* entries_host, int n_entries, void* work_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

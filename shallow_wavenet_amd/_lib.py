@@ -72,6 +72,12 @@ class LogMelEntry(ctypes.Structure):
                 ("f0", c_int32), ("f1", c_int32), ("reserved", c_int32)]
 
 
+class EnvelopeEntry(ctypes.Structure):
+    """mirror of `swn_envelope_entry` (include/swn_hip.h): one row's share of a spectral envelope call."""
+    _fields_ = [("wav_dev", c_void_p), ("out_dev", c_void_p), ("f0_dev", c_void_p), ("t0", c_int32), ("n_avail", c_int32),
+                ("len", c_int32), ("f0", c_int32), ("f1", c_int32), ("reserved", ctypes.c_int16), ("reserved2", ctypes.c_int16)]
+
+
 class LogMelPoolEntry(ctypes.Structure):
     """mirror of `swn_logmel_pool_entry` (include/swn_hip.h): one session's share of a log-mel pool call."""
     _fields_ = [(n, c_int32) for n in ("slot", "t0", "n_held", "n_drop", "new_off", "n_new", "len", "f0", "f1", "out_off",
@@ -119,6 +125,7 @@ LOGMEL_POOL_MAX_ENTRIES = 64                   # SWN_LOGMEL_POOL_MAX_ENTRIES (in
 MCEP_MAX_ORDER = 63                            # SWN_MCEP_MAX_ORDER (include/swn_hip.h)
 F0_MAX_HOP, F0_MIN_WIN, F0_MAX_WIN, F0_MAX_LAG = 4096, 16, 2048, 1536    # SWN_F0_MAX_HOP, _MIN_WIN, _MAX_WIN, _MAX_LAG
 BAP_MAX_BANDS, BAP_MAX_TAPS, BAP_TILE = 5, 255, 1280                     # SWN_BAP_MAX_BANDS, _MAX_TAPS, _TILE
+ENVELOPE_MCEP, ENVELOPE_LOGAMP = 0, 1                                    # SWN_ENVELOPE_MCEP, SWN_ENVELOPE_LOGAMP
 
 
 def desc_from_cfg(cfg: NetConfig) -> NetDesc:
@@ -258,6 +265,10 @@ SIGNATURES = {
     "swn_bap_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int, POINTER(LogMelEntry), c_int]),
     "swn_bap": (c_int, [ctypes.c_double, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_int, c_int, c_void_p, ctypes.c_float,
                 POINTER(LogMelEntry), c_int, c_void_p, c_void_p]),
+    "swn_envelope_table_doubles": (c_size_t, [c_int, c_int]),
+    "swn_envelope_work_bytes": (c_size_t, [c_int, c_int, POINTER(EnvelopeEntry), c_int]),
+    "swn_envelope": (c_int, [ctypes.c_double, c_int, c_int, c_int, ctypes.c_float, ctypes.c_double, ctypes.c_double, c_int, c_void_p,
+                     POINTER(EnvelopeEntry), c_int, c_void_p, c_void_p]),
 }
 
 

@@ -1,6 +1,7 @@
 // Host only.  The rules of a swn_logmel_entry that do not depend on the feature: row i of a call holds the samples [t0, t0 +
 // n_avail) of a signal of len samples (-1: not known yet) and asks for its frames [f0, f1) of F = 1 + len / hop.  swn_logmel,
-// swn_mcep and the rows of swn_logmel_pool (swn_melspec.hip) and swn_f0 and swn_bap (swn_f0.hip) check every entry with this
+// swn_mcep and the rows of swn_logmel_pool (swn_melspec.hip), swn_f0 and swn_bap (swn_f0.hip) and swn_envelope (swn_envelope.hip, whose
+// entry carries one pointer more) check every entry with this
 // before their own rule: which samples the range reads, and whether the window holds them.
 #pragma once
 #include <cstdio>

@@ -46,7 +46,14 @@ shape (F, B), the coded aperiodicity in dB of the B = `pitch.bap_bands(fs)` band
 kHz; a rate below 12 kHz has none and is refused), with `--bap_taps` taps per band-pass and the sum window `--bap_win`.  One call
 serves `--f0` / `--f0_cond` too: `/feat_f0` is its columns 0 - 1.  With `--f0_cond true` the conditioning dataset becomes `[uv,
 lf0, bap_0 .. bap_{B-1}, features]`, the reference's column order, so `noise_shaping.py --mcep_dim_start` is 2 + B - run.sh's
-`stdim`."""
+`stdim`.
+
+`--mcep_envelope true` (with `--mcep_dim M` > 0) takes the mel-cepstra from the F0-adaptive spectral envelope
+(`melspec.SpectralEnvelopeExtractor`, csrc/swn_envelope.hip; the definition is in melspec.py - CheapTrick's procedure in a fixed
+arithmetic, parity with WORLD neither claimed nor pinned) instead of the short-time spectrum: the pitch harmonics are not in
+them.  The F0 is column 0 of the batch's one `F0Extractor` / `BandAperiodicityExtractor` call, with `--minf0` / `--maxf0` /
+`--f0_win` / `--f0_threshold` as for `--f0`; that call is issued even without `--f0`, and `/feat_f0` is still written only when
+asked.  Datasets, columns and the noise-shaping recipe stay as above.  Without the flag the files are what they were."""
 from __future__ import annotations
 
 import argparse
@@ -102,6 +109,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mcep_alpha", default=MCEP_ALPHA, type=float, help="all-pass constant of the mel-cepstrum")
     p.add_argument("--mcep_floor", default=1e-5, type=float, help="floor of the amplitude under the log (mel-cepstrum; not a reference flag)")
     p.add_argument("--mcep_string_path", default="/feat_mcep", help="dataset name of the mel-cepstra (not a reference flag)")
+    p.add_argument("--mcep_envelope", default=False, type=_strtobool,
+                   help="true: the mel-cepstra are those of the F0-adaptive spectral envelope (melspec.SpectralEnvelopeExtractor) at "
+                        "the F0 of the batch's F0 / band aperiodicity call, not of the short-time spectrum; needs --mcep_dim > 0 "
+                        "(not a reference flag)")
     p.add_argument("--minf0", default=MINF0, type=int, help="minimum f0")
     p.add_argument("--maxf0", default=MAXF0, type=int, help="maximum f0")
     p.add_argument("--f0", default=False, type=_strtobool,
@@ -172,7 +183,11 @@ def load_waveform(name: str, args, device="cuda") -> np.ndarray:
 def extract_files(files: Sequence[str], args, device="cuda") -> int:
     want_f0, f0_cond = bool(getattr(args, "f0", False)), bool(getattr(args, "f0_cond", False))
     want_bap = bool(getattr(args, "bap", False))
+    want_env = bool(getattr(args, "mcep_envelope", False))
     if args.feature_type == "world":
+        if want_env:
+            logging.error("--mcep_envelope serves the features computed on the device, not --feature_type world")
+            return 2
         if want_f0 or f0_cond or want_bap:
             logging.error("--f0 / --f0_cond / --bap serve the features computed on the device; --feature_type world has its own "
                           "F0 and aperiodicity")
@@ -184,8 +199,11 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
             feats = dsp.extract_features(load_waveform(name, args, device), args.fs, shiftms=args.shiftms, fftl=args.fftl)
             featio.write_dataset(feature_path(args.hdf5dir, name), args.string_path, feats)
         return 0
-    from .melspec import LogMelExtractor, LowCut, MelCepstrumExtractor
+    from .melspec import LogMelExtractor, LowCut, MelCepstrumExtractor, SpectralEnvelopeExtractor
     as_cond = args.feature_type == "mcep"
+    if want_env and args.mcep_dim <= 0:
+        logging.error("--mcep_envelope needs --mcep_dim > 0")
+        return 2
     if as_cond and args.mcep_dim <= 0:
         logging.error("--feature_type mcep needs --mcep_dim > 0")
         return 2
@@ -196,8 +214,17 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
                      args.string_path))
     if args.mcep_dim > 0:
         dataset = args.string_path if as_cond and args.string_path != STRING_PATH else args.mcep_string_path
-        jobs.append((MelCepstrumExtractor(args.fs, args.fftl, hop_of(args), args.mcep_dim, args.mcep_alpha, args.mcep_floor,
-                                          device), dataset))
+        if want_env:
+            try:
+                env_ext = SpectralEnvelopeExtractor(args.fs, args.fftl, hop_of(args), args.mcep_dim, args.mcep_alpha,
+                                                    args.mcep_floor, device=device)
+            except ValueError as e:
+                logging.error("--mcep_envelope: %s", e)
+                return 2
+            jobs.append((env_ext, dataset))
+        else:
+            jobs.append((MelCepstrumExtractor(args.fs, args.fftl, hop_of(args), args.mcep_dim, args.mcep_alpha, args.mcep_floor,
+                                              device), dataset))
     ext = jobs[0][0]
     f0_ext = None
     if want_bap:                                                    # one call serves the F0 columns too
@@ -208,7 +235,7 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
         except ValueError as e:
             logging.error("--bap: %s", e)
             return 2
-    elif want_f0 or f0_cond:
+    elif want_f0 or f0_cond or want_env:                            # the envelope takes its F0 from this call
         from .pitch import F0Extractor, uv_lf0
         f0_ext = F0Extractor(args.fs, hop_of(args), args.minf0, args.maxf0, args.f0_win, args.f0_threshold, device)
     cut = LowCut(args.fs, args.highpass_cutoff, device=device) if on_device(args) else None
@@ -242,8 +269,12 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
                     write_wav_pcm16(os.path.join(args.wavdir, os.path.basename(name)), np.clip(y[:n], -1.0, 1.0), args.fs)
         lead: List[Optional[np.ndarray]] = [None] * len(names)     # --f0_cond: the [uv, lf0 (, bap)] columns of each file
         skip = [False] * len(names)
+        f0_dev = None                                               # --mcep_envelope: the batch's F0 column, on the device
         if f0_ext is not None:
-            f0ap = f0_ext(batch, lengths).cpu().numpy()
+            f0ap = f0_ext(batch, lengths)
+            if want_env:
+                f0_dev = f0ap[..., 0].contiguous()
+            f0ap = f0ap.cpu().numpy()
             for k, (name, x) in enumerate(zip(names, waves)):
                 frames = f0ap[k, :ext.frame_count(x.shape[0])]
                 contour, bap = np.ascontiguousarray(frames[:, :2]), np.ascontiguousarray(frames[:, 2:])
@@ -264,7 +295,8 @@ def extract_files(files: Sequence[str], args, device="cuda") -> int:
                     featio.write_dataset(out, args.bap_string_path, bap)
                     logging.info("%s -> %s %s %s", name, out, args.bap_string_path, bap.shape)
         for j, (extractor, dataset) in enumerate(jobs):
-            feats = extractor(batch, lengths).cpu().numpy()
+            feats = (extractor(batch, lengths, f0_dev) if isinstance(extractor, SpectralEnvelopeExtractor) else
+                     extractor(batch, lengths)).cpu().numpy()
             for k, (name, x, f) in enumerate(zip(names, waves, feats)):
                 if skip[k]:
                     continue

@@ -11,6 +11,10 @@ fully pinned feature type next to the WORLD / SPTK features of run.sh stage 1 (w
                                                # (R, F_max, order + 1): the mel-cepstrum of the same short-time spectra
                                                # (`torch.ops.swn.mcep`), for the statistics the noise-shaping stages need;
                                                # its definition is in the class's docstring
+    env = SpectralEnvelopeExtractor(fs=22050, n_fft=1024, hop=110, order=49, alpha=0.455, device="cuda:0")
+    mc = env(wavs, lengths, f0)                # (R, F_max, order + 1): the mel-cepstrum of the F0-adaptive spectral envelope
+                                               # (`torch.ops.swn.envelope`) at the per-frame F0 of pitch.F0Extractor - without the
+                                               # pitch harmonics the short-time spectrum carries; definition in the class's docstring
     cut = LowCut(fs=22050, cutoff=70.0, device="cuda:0")       # the stage-1 low cut (`torch.ops.swn.lowcut_chunk`): what the
     y = cut(wavs, lengths)                                     # training features were taken from; LogMelStream(ext, low_cut=cut)
                                                                # and LogMelPool(..., low_cut=cut) take RAW samples and filter them
@@ -167,7 +171,7 @@ def _per_row(v, rows: int) -> List[int]:
 
 
 class _FrameExtractor:
-    """what LogMelExtractor, MelCepstrumExtractor and pitch.F0Extractor share: the one-shot call and the frames of a partial
+    """what LogMelExtractor, MelCepstrumExtractor, SpectralEnvelopeExtractor and pitch.F0Extractor share: the one-shot call and the frames of a partial
     buffer, both as one call of the frame-range contract ops._frame_entries states.  A subclass's constructor sets `hop`, `device`
     and `_op`; it supplies `_check_len(length)` (ValueError for a signal too short) and `_run(buf, t0s, n_avails, lens, f0s,
     f1s, *more)`, which hands `self._op` the contract's lists with the subclass's own arguments around them."""
@@ -328,6 +332,192 @@ class MelCepstrumExtractor(_FrameExtractor):
 
     def _run(self, buf, t0s, n_avails, lens, f0s, f1s) -> torch.Tensor:
         return self._op(buf, self._table, t0s, n_avails, lens, f0s, f1s, self.n_fft, self.hop, self.order, self.floor)
+
+
+# ---- spectral envelope by F0-adaptive smoothing ----------------------------------------------------------------------------
+ENVELOPE_OUTPUTS = {"mcep": _lib.ENVELOPE_MCEP, "logamp": _lib.ENVELOPE_LOGAMP}
+
+
+def envelope_f0_floor(fs: float, n_fft: int) -> float:
+    """the lowest F0 a transform of n_fft points can analyse: 3 fs / (n_fft - 3), so that three periods fit the frame"""
+    return 3.0 * float(fs) / (float(n_fft) - 3.0)
+
+
+def _check_envelope(fs: float, n_fft: int, hop: int, order: int, alpha: float, floor: float, q1: float, default_f0: float) -> None:
+    check_size(n_fft)
+    if not (fs > 0.0 and math.isfinite(fs)):
+        raise ValueError(f"fs {fs!r} must be a finite number > 0")
+    if not 1 <= hop <= _lib.F0_MAX_HOP:
+        raise ValueError(f"hop {hop} outside [1, {_lib.F0_MAX_HOP}]")
+    _check_order(n_fft, order, alpha)
+    if not (floor > 0.0 and math.isfinite(floor) and float(np.float32(floor)) > 0.0 and math.isfinite(float(np.float32(floor)))):
+        raise ValueError(f"floor {floor!r} must be a finite fp32 number > 0")
+    if not math.isfinite(q1):
+        raise ValueError(f"q1 {q1!r} must be finite")
+    lo = envelope_f0_floor(fs, n_fft)
+    if not lo < default_f0 <= fs / 4.0:
+        raise ValueError(f"default_f0 {default_f0!r} outside (3 fs / (n_fft - 3) = {lo:g}, fs / 4 = {fs / 4.0:g}]: n_fft {n_fft} "
+                         f"is too short for fs {fs} (8 000 Hz needs 64, 22 050 Hz needs 160)")
+
+
+def envelope_matrix(n_fft: int, order: int, alpha: float) -> np.ndarray:
+    """G (order + 1, n_fft // 2 + 1) in float64 with mc = G c: SPTK's `freqt` recursion run on the unit vectors, coefficient by
+    coefficient (for every input coefficient from the last to the first: g[0] = c + alpha d[0]; g[1] = (1 - alpha^2) d[0] +
+    alpha d[1]; g[j] = d[j - 1] + alpha (d[j] - g[j - 1]), d the g of the step before)."""
+    n_fft, order = int(n_fft), int(order)
+    check_size(n_fft)
+    _check_order(n_fft, order, alpha)
+    bins = n_fft // 2 + 1
+    a = np.float64(alpha)
+    b = np.float64(1.0) - a * a
+    c = np.eye(bins, dtype=np.float64)
+    g = np.zeros((bins, order + 1), dtype=np.float64)
+    for i in range(bins - 1, -1, -1):
+        d = g.copy()
+        g[:, 0] = c[:, i] + a * d[:, 0]
+        if order >= 1:
+            g[:, 1] = b * d[:, 0] + a * d[:, 1]
+        for j in range(2, order + 1):
+            g[:, j] = d[:, j - 1] + a * (d[:, j] - g[:, j - 1])
+    return np.ascontiguousarray(g.T)
+
+
+def envelope_tables(n_fft: int, order: int, alpha: float) -> np.ndarray:
+    """the float64 table swn_envelope takes: cos(2 pi m / n_fft) for m < n_fft, then envelope_matrix row by row"""
+    G = envelope_matrix(n_fft, order, alpha)
+    return np.concatenate([np.cos(2.0 * np.pi * np.arange(n_fft, dtype=np.float64) / n_fft), G.reshape(-1)])
+
+
+def envelope_frames_ready(n_fft: int, hop: int, n_received: int, final: bool = False) -> int:
+    """the streaming rule of the spectral envelope, the one place it is written: frame f spans [f hop - (n_fft / 2 - 1),
+    f hop + n_fft / 2) whatever its F0, so while the signal goes on it is computable iff f hop + n_fft / 2 <= n_received; when the
+    signal ends there (`final`), all F = 1 + n_received // hop are.  Not `frames_ready`: there frame 0 reads the reflected sample
+    n_fft / 2 and needs one sample more."""
+    if final:
+        return frame_count(n_received, hop)
+    half = n_fft // 2
+    return 0 if n_received < half else 1 + (n_received - half) // hop
+
+
+class SpectralEnvelopeExtractor(_FrameExtractor):
+    """The spectral envelope by F0-adaptive smoothing, and its mel-cepstrum, on the device (`torch.ops.swn.envelope`,
+    swn_envelope): what `MelCepstrumExtractor` is not - its fixed 1 024-sample frame resolves the harmonics, so the pitch is in
+    its coefficients; here a frame is analysed under a window of three pitch periods and smoothed over 2 f0 / 3.
+
+        f0 = F0Extractor(fs=22050, hop=110, device="cuda:0")(wavs, lengths)[..., 0]        # (R, F_max) Hz, 0.0 when unvoiced
+        ext = SpectralEnvelopeExtractor(fs=22050, n_fft=1024, hop=110, order=49, alpha=0.455, device="cuda:0")
+        mc = ext(wavs, lengths, f0)            # (R, F_max, order + 1), time-major; zero past a row's frames
+        part = ext.frames(buf, t0, n_avail, length, f0, f1, f0_values)      # frames [f0, f1) from a partial buffer
+        E = SpectralEnvelopeExtractor(..., output="logamp")(wavs, lengths, f0)             # (R, F_max, n_fft / 2 + 1): ln amplitude
+
+    It is CheapTrick's procedure (Morise 2015) in a fixed arithmetic.  It omits WORLD's added noise and its eps and has a floor
+    instead.  Parity with pyworld / pysptk is neither claimed nor pinned, as for F0 and the aperiodicity.
+
+    Definition (the contract; include/swn_hip.h restates it, tests/envelope_ref.py pins it).  Parameters: fs > 0; n_fft a
+    multiple of 32 in [32, SWN_SPECTRAL_MAX_FFT]; 1 <= hop <= SWN_F0_MAX_HOP; 0 <= order <= min(63, n_fft / 2) with |alpha| < 1;
+    floor > 0, an amplitude, given as fp32 (default 1e-5); q1 (default -0.15); default_f0 (default 500.0).  With D = fs / n_fft
+    and f0_floor = 3 fs / (n_fft - 3) the geometry is refused unless f0_floor < default_f0 <= fs / 4: fs 8 000 needs n_fft >= 64,
+    22 050 needs 160.  Input: len >= 1 finite fp32 samples, x[t] = 0 outside [0, len) (zero padding, as F0Extractor); F = 1 +
+    len // hop frames, the grid of the other extractors; one fp32 value f0[f] per frame, any number - F0Extractor's column 0 is
+    the intended source.  Everything below is IEEE double in the order written, every sum one chain in ascending index from +0.0
+    with fma, each output value rounded once to fp32.
+      1. Effective F0: f0e = (double)f0[f] if f0_floor < f0[f] <= fs / 4, else default_f0.  Unvoiced 0.0, NaN, values under the
+         floor and values over fs / 4 all take the default.
+      2. Window: hl = floor(1.5 fs / f0e + 0.5), so 2 hl + 1 <= n_fft - 1 always.  For k = -hl .. hl: w[k] = 0.5 cos(pi k f0e /
+         (1.5 fs)) + 0.5; w /= sqrt(sum w^2); xw[k] = x[f hop + k] w[k]; then xw[k] -= w[k] (sum xw / sum w), w already normalised.
+      3. Power: P[b] = |sum_k xw[k] e^(-2 pi i b (k + hl) / n_fft)|^2 = re^2 + im^2 for b = 0 .. n_fft / 2; with j = k + hl the
+         twiddles are T[(b j) mod n_fft] (re) and T[(b j + n_fft / 4) mod n_fft] (im), T[m] = cos(2 pi m / n_fft) the fp64 table
+         evaluated on the host.
+      4. DC correction, from the uncorrected P: for b = 0 .. floor(f0e / D): u = f0e / D - b, i = floor(u), P'[b] = (P[b] + P[i])
+         + (u - i)(P[i + 1] - P[i]); P' = P elsewhere.
+      5. Box smoothing of width wd = 2 f0e / 3 over the spectrum taken as one rectangle of width D per bin, mirrored at 0 and at
+         Nyquist: S[b] = (1 / wd) sum_n ov(n) P'[mir(n)], n ascending from floor((b D - wd / 2) / D + 0.5) to floor((b D + wd / 2)
+         / D + 0.5), ov(n) = min(b D + wd / 2, (n + 0.5) D) - max(b D - wd / 2, (n - 0.5) D), terms with ov <= 0 skipped,
+         mir(n) = -n for n < 0, n_fft - n for n > n_fft / 2, else n.
+      6. Log: L[b] = ln max(S[b], floor^2).
+      7. Liftering: v[k] = (1 / n_fft) sum_b e_b L[b] T[(k b) mod n_fft] for k = 0 .. n_fft / 2, e = 1 at 0 and n_fft / 2 and 2
+         between (irfft as a cosine sum); l_s[0] = 1, l_s[k] = sin(pi f0e k / fs) / (pi f0e k / fs); l_c[k] = (1 - 2 q1) + 2 q1
+         cos(2 pi k f0e / fs); ct[k] = v[k] l_s[k] l_c[k].
+      8. Outputs.  "mcep": the one-sided cepstrum of the log AMPLITUDE envelope, c[0] = ct[0] / 2, c[k] = ct[k] for 0 < k <
+         n_fft / 2, c[n_fft / 2] = ct[n_fft / 2] / 2, then mc[0 .. order] = freqt(c, order, alpha) as the fp64 matrix
+         `envelope_matrix` (order + 1, n_fft / 2 + 1), built on the host from unit vectors.  "logamp": E[b] = 0.5 (ct[0] + 2
+         sum_{0<k<n/2} ct[k] cos(2 pi k b / n_fft) + ct[n/2] (-1)^b), ln of the amplitude envelope, n_fft / 2 + 1 values.
+    A frame's values depend on the signal, the frame index and that frame's F0 value alone, not on the batch, the entry, the
+    frame range, the buffer window or the call: any partition gives the same bits, as for the other extractors.  Streaming rule
+    (`envelope_frames_ready`): frame f is computable iff f hop + n_fft / 2 <= n_received, or when the signal has ended.
+    There is no torch fall-back: without the library the call raises.
+
+    Not covered: an EnvelopeStream or a pool variant (`frames` serves ranges; the rule above is for it); `low_cut=` /
+    `resample=` (filter and resample first, as for F0Stream); parity with WORLD; time-varying noise shaping; `swn_mcep` and
+    MelCepstrumExtractor are unchanged."""
+
+    def __init__(self, fs: float, n_fft: int, hop: int, order: int, alpha: float, floor: float = 1e-5, q1: float = -0.15,
+                 default_f0: float = 500.0, output: str = "mcep", device="cuda") -> None:
+        self.fs, self.n_fft, self.hop, self.order = float(fs), int(n_fft), int(hop), int(order)
+        self.alpha, self.floor, self.q1, self.default_f0 = float(alpha), float(floor), float(q1), float(default_f0)
+        if output not in ENVELOPE_OUTPUTS:
+            raise ValueError(f"output must be one of {sorted(ENVELOPE_OUTPUTS)}, not {output!r}")
+        self.output, self._what = output, ENVELOPE_OUTPUTS[output]
+        _check_envelope(self.fs, self.n_fft, self.hop, self.order, self.alpha, self.floor, self.q1, self.default_f0)
+        self.cols = self.order + 1 if output == "mcep" else self.n_fft // 2 + 1
+        table = envelope_tables(self.n_fft, self.order, self.alpha)
+        self.device = torch.device(device)
+        self._table = torch.from_numpy(table).to(self.device)
+        self._op = ops.envelope_impl
+
+    def _check_len(self, length: int) -> None:
+        if length < 1:
+            raise ValueError(f"a signal needs at least one sample, got {length}")
+
+    def _check_ranges(self, t0s, n_avails, lens, f0s, f1s) -> None:
+        """the entry rules of swn_envelope, as ValueErrors before anything is launched"""
+        half = self.n_fft // 2
+        for r, (t0, na, n, f0, f1) in enumerate(zip(t0s, n_avails, lens, f0s, f1s)):
+            if f0 < 0 or f1 < f0:
+                raise ValueError(f"row {r}: frame range [{f0}, {f1})")
+            if n != -1 and not 1 <= n <= 1 << 30:
+                raise ValueError(f"row {r}: length {n}, need 1 <= len <= 2^30 (or -1 while unknown)")
+            if t0 < 0 or na < 0 or t0 + na > 1 << 30 or (n != -1 and t0 + na > n):
+                raise ValueError(f"row {r}: window [{t0}, {t0} + {na}) is not inside the signal")
+            if f1 == f0:
+                continue
+            if n != -1 and f1 > self.frame_count(n):
+                raise ValueError(f"row {r}: f1 = {f1}, a signal of {n} samples has {self.frame_count(n)} frames")
+            lo, hi = max(0, f0 * self.hop - (half - 1)), (f1 - 1) * self.hop + half - 1
+            if n == -1:
+                if hi >= t0 + na:
+                    raise ValueError(f"row {r}: frames [{f0}, {f1}) need sample {hi}, the window ends at {t0 + na} and the total "
+                                     f"length is unknown")
+            else:
+                hi = min(hi, n - 1)
+            if lo <= hi and (lo < t0 or hi >= t0 + na):
+                raise ValueError(f"row {r}: frames [{f0}, {f1}) read samples [{lo}, {hi}], the window holds [{t0}, {t0 + na})")
+
+    def _run(self, buf, t0s, n_avails, lens, f0s, f1s, f0_values) -> torch.Tensor:
+        self._check_ranges(t0s, n_avails, lens, f0s, f1s)
+        if f0_values is None:
+            raise ValueError("the spectral envelope needs one F0 value per frame (F0Extractor's column 0)")
+        f0v = torch.as_tensor(f0_values)
+        if f0v.dim() == 1:
+            f0v = f0v[None]
+        need = max([b - a for a, b in zip(f0s, f1s)] + [0])
+        if f0v.dim() != 2 or f0v.shape[0] != buf.shape[0] or f0v.shape[1] < need:
+            raise ValueError(f"f0 must hold one value per frame, ({buf.shape[0]}, >= {need}), got {tuple(f0v.shape)}")
+        f0v = f0v.to(self.device, torch.float32).contiguous()
+        return self._op(buf, f0v, self._table, t0s, n_avails, lens, f0s, f1s, self.fs, self.n_fft, self.hop, self.order,
+                        self.floor, self.q1, self.default_f0, self._what)
+
+    def __call__(self, wavs, lengths: Optional[Sequence[int]] = None, f0=None) -> torch.Tensor:
+        """wavs, lengths: as _FrameExtractor.__call__; f0: (R, >= F_max) fp32, row r holding the F0 in Hz of its frames (what
+        lies past a row's frames is not read) -> (R, F_max, order + 1) or, with output="logamp", (R, F_max, n_fft / 2 + 1)"""
+        return self._whole(wavs, lengths, f0)
+
+    def frames(self, wav: torch.Tensor, t0: Union[int, Sequence[int]], n_avail: Union[int, Sequence[int]],
+               length: Union[int, Sequence[int]], f0: Union[int, Sequence[int]], f1: Union[int, Sequence[int]],
+               f0_values=None) -> torch.Tensor:
+        """as _FrameExtractor.frames; f0_values: (f1 - f0,) or (R, >= max(f1 - f0)), the F0 of the frames f0, f0 + 1, ... of each
+        row -> (f1 - f0, columns) or (R, max(f1 - f0), columns)"""
+        return self._partial(wav, t0, n_avail, length, f0, f1, f0_values)
 
 
 # ---- stage-1 low cut -----------------------------------------------------------------------------------------------------

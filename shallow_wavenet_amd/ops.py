@@ -61,6 +61,8 @@ implementations are registered so the ops trace under `torch.compile` / `FakeTen
     torch.ops.swn.f0(wav, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshold) -> (F0 in Hz, aperiodicity) per frame
     torch.ops.swn.bap(wav, taps, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, threshold, band_win, floor)
                                                     -> (F0 in Hz, aperiodicity, B coded band aperiodicities in dB) per frame
+    torch.ops.swn.envelope(wav, f0, tables, t0s, n_avails, lens, f0s, f1s, fs, n_fft, hop, order, floor, q1, default_f0, what)
+                                                    -> mel-cepstra (what 0) or log amplitudes (what 1) of the F0-adaptive envelope
     torch.ops.swn.laplace_loss(raw, ctx?, target, eps, desc, skip) -> (nll, err, samples, targets, stats)
     torch.ops.swn.laplace_loss_backward(raw, ctx?, target, eps, g_nll, g_samples?, desc, skip) -> grad_raw
 """
@@ -1509,11 +1511,13 @@ def _frames_fake(wav, f0s, f1s, cols: int) -> torch.Tensor:
 
 
 def _frame_entries(op: str, wav: torch.Tensor, t0s: List[int], n_avails: List[int], lens: List[int], f0s: List[int],
-                   f1s: List[int], cols: int):
-    """the contract of logmel, mcep, f0 and bap: row r of the contiguous fp32 buffer wav (R, S) holds the samples [t0s[r],
-    t0s[r] + n_avails[r]) of signal r, whose total length is lens[r] (-1: not known yet); the call computes its frames [f0s[r],
-    f1s[r]).  Checks the buffer and the lists -> (the zeroed (R, max(f1 - f0), cols) output, the launch groups [(LogMelEntry
-    table, n), ...] of at most LOGMEL_MAX_ENTRIES rows each, in row order)."""
+                   f1s: List[int], cols: int, f0: Optional[torch.Tensor] = None):
+    """the contract of logmel, mcep, f0, bap and envelope: row r of the contiguous fp32 buffer wav (R, S) holds the samples
+    [t0s[r], t0s[r] + n_avails[r]) of signal r, whose total length is lens[r] (-1: not known yet); the call computes its frames
+    [f0s[r], f1s[r]).  Checks the buffer and the lists -> (the zeroed (R, max(f1 - f0), cols) output, the launch groups
+    [(LogMelEntry table, n), ...] of at most LOGMEL_MAX_ENTRIES rows each, in row order).  With `f0` (envelope), a contiguous fp32
+    (R, >= max(f1 - f0)) tensor on wav's device whose row r holds the F0 of the frames f0s[r], f0s[r] + 1, ..., the tables are
+    EnvelopeEntry and carry its rows."""
     if wav.dim() != 2 or wav.dtype != torch.float32 or not wav.is_contiguous():
         raise RuntimeError(f"{op} needs a contiguous fp32 (R, S) buffer, got {tuple(wav.shape)} {wav.dtype}")
     R, S = wav.shape
@@ -1524,12 +1528,20 @@ def _frame_entries(op: str, wav: torch.Tensor, t0s: List[int], n_avails: List[in
     fmax = _fmax(f0s, f1s)
     out = torch.zeros((R, fmax, cols), dtype=torch.float32, device=wav.device)
     esz, osz = wav.element_size() * S, out.element_size() * fmax * cols
+    kind, more = _lib.LogMelEntry, lambda r: {}
+    if f0 is not None:
+        if (f0.dim() != 2 or f0.dtype != torch.float32 or not f0.is_contiguous() or f0.device != wav.device or f0.shape[0] != R
+                or f0.shape[1] < fmax):
+            raise RuntimeError(f"{op}: f0 must be a contiguous fp32 ({R}, >= {fmax}) tensor on the waveforms' device, got "
+                               f"{tuple(f0.shape)} {f0.dtype} on {f0.device}")
+        fsz = f0.element_size() * f0.shape[1]
+        kind, more = _lib.EnvelopeEntry, lambda r: {"f0_dev": f0.data_ptr() + r * fsz, "reserved2": 0}
     groups = []
     for r0 in range(0, R, _lib.LOGMEL_MAX_ENTRIES):
         r1 = min(R, r0 + _lib.LOGMEL_MAX_ENTRIES)
-        groups.append(((_lib.LogMelEntry * (r1 - r0))(*[
-            _lib.LogMelEntry(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
-                             n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0)
+        groups.append(((kind * (r1 - r0))(*[
+            kind(wav_dev=wav.data_ptr() + r * esz, out_dev=out.data_ptr() + r * osz, t0=int(t0s[r]),
+                 n_avail=int(n_avails[r]), len=int(lens[r]), f0=int(f0s[r]), f1=int(f1s[r]), reserved=0, **more(r))
             for r in range(r0, r1)]), r1 - r0))
     return out, groups
 
@@ -1693,6 +1705,60 @@ def _(wav, taps, t0s, n_avails, lens, f0s, f1s, fs, hop, win, lag_lo, lag_hi, th
     _f0_check(fs, hop, win, lag_lo, lag_hi, threshold)
     B, _ = _bap_check(taps, win, band_win, floor)
     return _frames_fake(wav, f0s, f1s, 2 + B)
+
+
+def _envelope_check(fs: float, n_fft: int, hop: int, order: int, floor: float, q1: float, default_f0: float, what: int) -> int:
+    """the size rules of swn_envelope as messages (the library itself answers SWN_E_BADARG) -> the columns of a frame"""
+    if not (fs > 0.0 and fs < float("inf")):
+        raise RuntimeError(f"envelope: fs {fs} must be a finite number > 0")
+    if n_fft % 32 != 0 or not 32 <= n_fft <= _lib.SPECTRAL_MAX_FFT:
+        raise RuntimeError(f"envelope: n_fft {n_fft} is not a multiple of 32 in [32, {_lib.SPECTRAL_MAX_FFT}]")
+    if not 1 <= hop <= _lib.F0_MAX_HOP:
+        raise RuntimeError(f"envelope: hop {hop} outside [1, {_lib.F0_MAX_HOP}]")
+    if not 0 <= order <= min(_lib.MCEP_MAX_ORDER, n_fft // 2):
+        raise RuntimeError(f"envelope: order {order} outside [0, min({_lib.MCEP_MAX_ORDER}, n_fft / 2 = {n_fft // 2})]")
+    if not 0.0 < floor < float("inf"):
+        raise RuntimeError(f"envelope: floor {floor} must be a finite number > 0")
+    if not abs(q1) < float("inf"):
+        raise RuntimeError(f"envelope: q1 {q1} must be finite")
+    if not 3.0 * fs / (n_fft - 3.0) < default_f0 <= fs / 4.0:
+        raise RuntimeError(f"envelope: default_f0 {default_f0} outside (3 fs / (n_fft - 3) = {3.0 * fs / (n_fft - 3.0):g}, "
+                           f"fs / 4 = {fs / 4.0:g}]: n_fft {n_fft} is too short for fs {fs}")
+    if what not in (_lib.ENVELOPE_MCEP, _lib.ENVELOPE_LOGAMP):
+        raise RuntimeError(f"envelope: what {what} is neither ENVELOPE_MCEP (0) nor ENVELOPE_LOGAMP (1)")
+    return order + 1 if what == _lib.ENVELOPE_MCEP else n_fft // 2 + 1
+
+
+def envelope_impl(wav: torch.Tensor, f0: torch.Tensor, tables: torch.Tensor, t0s: List[int], n_avails: List[int], lens: List[int],
+                  f0s: List[int], f1s: List[int], fs: float, n_fft: int, hop: int, order: int, floor: float, q1: float,
+                  default_f0: float, what: int) -> torch.Tensor:
+    """wav (R, S), t0s, n_avails, lens, f0s, f1s: as f0 takes them; f0: contiguous fp32 (R, >= max(f1 - f0)), row r holding the
+    F0 in Hz of the frames f0s[r], f0s[r] + 1, ...; tables: melspec.envelope_tables(), float64 -> (R, max(f1 - f0), order + 1)
+    mel-cepstra of the F0-adaptive spectral envelope (what 0) or (R, max(f1 - f0), n_fft / 2 + 1) log amplitudes of it (what 1)
+    of the frames [f0s[r], f1s[r]) of each row, zero past a row's own range (swn_envelope; the definition is in melspec.py)."""
+    Lb = _lib.lib()
+    _need_cuda(wav, "the waveforms")
+    dev = wav.device
+    cols = _envelope_check(fs, n_fft, hop, order, floor, q1, default_f0, what)
+    out, groups = _frame_entries("envelope", wav, t0s, n_avails, lens, f0s, f1s, cols, f0)
+    need = int(Lb.swn_envelope_table_doubles(n_fft, order))
+    if tables.device != dev or tables.dtype != torch.float64 or not tables.is_contiguous() or tables.numel() != need:
+        raise RuntimeError(f"envelope: tables must be {need} contiguous float64 values on the device of the waveforms")
+    nb = max([int(Lb.swn_envelope_work_bytes(n_fft, hop, table, n)) for table, n in groups] + [8])
+    work = torch.empty((nb // 8,), dtype=torch.float64, device=dev)
+    for table, n in groups:
+        with _on(dev):
+            _lib.check(Lb.swn_envelope(float(fs), n_fft, hop, order, float(floor), float(q1), float(default_f0), what,
+                                       tables.data_ptr(), table, n, work.data_ptr(), _stream(dev)), "envelope")
+    return out
+
+
+envelope = custom_op("swn::envelope", mutates_args=())(envelope_impl)
+
+
+@envelope.register_fake
+def _(wav, f0, tables, t0s, n_avails, lens, f0s, f1s, fs, n_fft, hop, order, floor, q1, default_f0, what):
+    return _frames_fake(wav, f0s, f1s, _envelope_check(fs, n_fft, hop, order, floor, q1, default_f0, what))
 
 
 def logmel_pool_impl(win: torch.Tensor, staged: Optional[torch.Tensor], tables: torch.Tensor, bank: List[int], slots: List[int],
@@ -1952,4 +2018,4 @@ OP_NAMES = ("pack_params", "frontend", "frontend_pool", "decode", "decode_chunk"
             "stack_forward", "pack_bf16", "stack_forward_bf16", "laplace_head",
             "laplace_head_backward", "stack_backward", "stack_backward_bf16", "spectral_loss", "spectral_loss_backward",
             "laplace_loss", "laplace_loss_backward", "logmel", "logmel_pool", "mcep", "lowcut_chunk", "logmel_pool_lowcut",
-            "resample_chunk", "resample_staged", "f0", "bap")
+            "resample_chunk", "resample_staged", "f0", "bap", "envelope")
